@@ -7,7 +7,7 @@ BASELINE.json configs[2] family (synthetic 100 leaves x 400 sites, 200 V / 30 D 
 the flattened inputs already resident in HBM.  The product path is: C++ host (linearham's PhyloHMM
 surface, liblinearham_host.so) -> C ABI -> HIP kernels (liblinearham_hip.so).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 Multi-GPU: `--gpus N` with no launcher environment starts its own N rank processes (one per GPU) as fresh
 children before this process has touched the GPU, and relays rank 0's JSON line; under
@@ -45,6 +45,7 @@ WORKLOADS = {
 }
 PMC_PROFILE = {"config2": "r04b_bench_pmc_per_launch.json", "config4": "r03_config4_pmc_per_launch.json"}
 GEN_VERSION = 2                # bump when tools/synth_family.py changes what it writes
+DUMP_LIMIT_BYTES = 64 << 20    # --dump-outputs: at most this much in all
 
 
 def log(*a):
@@ -340,6 +341,22 @@ def mixed_n_rate(args, lib, T, R, n, dev, stream):
     return res
 
 
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array as out_dir/<name>.npy in float64.  Arrays whose leading axis would take the dump past
+    DUMP_LIMIT_BYTES keep a fixed, seeded sample of their rows (sorted), the same for every build of the project."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    budget = DUMP_LIMIT_BYTES // max(len(arrays), 1)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        row_bytes = a[:1].nbytes or 8
+        if a.nbytes > budget:
+            keep = np.sort(np.random.default_rng(0).choice(a.shape[0], budget // row_bytes, replace=False))
+            log("[bench] %s: %d of %d rows dumped (seeded sample)" % (name, keep.size, a.shape[0]))
+            a = a[keep]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def live_k1_traffic(args):
     """HBM-side bytes of one K1 launch, measured NOW on this box: FETCH_SIZE and WRITE_SIZE of the pruning kernel from two short
     child runs of this script under `rocprofv3 --pmc` (counters cannot be collected inside the measuring process, and the two
@@ -417,7 +434,12 @@ def parse_args():
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="collective backend; gloo (through host copies) only to rehearse the multi-rank path on "
                          "a box with fewer GPUs than ranks -- ranks then share devices (LOCAL_RANK modulo)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy: loglik.npy, the "
+                         "per-sample log-likelihoods of every rank in global sample order (float64)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     global BRLEN_MEAN, DEV_LEAVES
     BRLEN_MEAN = args.brlen_mean
     DEV_LEAVES = args.leaves if args.brlen_mean is not None else None
@@ -532,6 +554,8 @@ def worker(args, rank, local_rank, world):
     lib.check(lib.lib.lh_profile_enable(C.c_void_p(fam_handle), 0))
     ll_host = loglik.cpu().numpy()
     ll_all = sharding.unshard(res.cpu().numpy(), n_total, world) if rank == 0 else None
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"loglik": ll_all})
 
     # the same step with the arrays SampleNaiveSequence consumes (forward rows + ScaleMatrix counts) written
     dt_fwd = None

@@ -79,6 +79,34 @@ def test_bench_config3_preset():
     assert out["delta_logl_vs_cpu_max_rel"] < 1e-9 and out["value"] > 0
 
 
+@pytest.mark.gpu
+def test_bench_dump_outputs_are_the_last_step_and_repeat(tmp_path):
+    """--dump-outputs writes the log-likelihoods of the last timed step; two runs with different step counts see the
+    same inputs and dump the same values, and the result line reports the steps it timed."""
+    import numpy as np
+    dumps = []
+    for steps in (1, 3):
+        d = tmp_path / ("s%d" % steps)
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--preset", "small", "--steps", str(steps),
+                            "--warmup", "1", "--no-cpu-baseline", "--no-extras", "--no-forward-rate", "--dump-outputs",
+                            str(d)], env=_clean_env(), capture_output=True, text=True, timeout=900)
+        assert p.returncode == 0, p.stderr[-3000:]
+        out = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][0])
+        assert out["steps"] == steps and out["ms_per_step"] > 0
+        ll = np.load(d / "loglik.npy")
+        assert ll.dtype == np.float64 and ll.shape == (out["config"]["tree_samples_per_step"],)
+        assert np.isfinite(ll).all()
+        dumps.append(ll)
+    assert np.array_equal(dumps[0], dumps[1])
+
+
+def test_bench_rejects_zero_steps():
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], env=_clean_env(),
+                       capture_output=True, text=True, timeout=120)
+    assert p.returncode == 2 and "--steps" in p.stderr
+    assert not [l for l in p.stdout.splitlines() if l.startswith("{")]
+
+
 def test_bench_launcher_fails_loudly_without_gpu():
     """On a box without a GPU the ranks refuse to run (no CPU fallback) and the launcher reports failure."""
     import torch
