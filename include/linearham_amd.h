@@ -219,6 +219,44 @@ int lh_eval_sample_batch_device(lh_family* fam, int32_t n, int32_t n_tips, int32
                                 int32_t num_rates, const uint32_t* words, double* loglik, double* rates,
                                 int32_t* states, void* hip_stream);
 
+/* ---- exact posterior state marginals (K5: forward filtering / backward smoothing over the forward arrays) ----
+ * Every member may be NULL.  log_offset is an input: lw_i = loglik_i - log_offset_i (0 when NULL), e.g. the
+ * RevBayes log-likelihood of the row, so that w_i = exp(lw_i - max lw) is the row's importance weight
+ * (scripts/run_bootstrap_asr_ess.R:29-32).
+ *   loglik       [n]                   as lh_eval_batch
+ *   posterior    [n][lh_forward_size]  posterior of every state, in the layout of lh_eval_outputs.forward:
+ *                                      V genes | V-D rows x (left | NTI x 4 | right) | D genes | D-J rows | J genes;
+ *                                      entries of states that do not exist are 0.  NaN for a sample whose loglik is
+ *                                      not finite (an overflowed row in the active mode, or a rejected schedule)
+ *   weighted_sum [lh_forward_size]     sum_i w_i posterior_i, in a fixed order; samples with w_i = 0 or a
+ *                                      non-finite lw_i are left out
+ *   weight_stats [3]                   max lw (-inf if none is finite), sum w_i, sum w_i^2
+ * Batches combine exactly: rescale each one's sums by exp(max_b - max). */
+typedef struct {
+  const double* log_offset;
+  double* loglik;
+  double* posterior;
+  double* weighted_sum;
+  double* weight_stats;
+} lh_posterior_outputs;
+
+/* lh_eval_batch followed by K5.  Needs lh_family_set_sampler (the junction tables K5 reads).  Host pointers; a
+ * malformed schedule fails the call as in lh_eval_sample_batch. */
+int lh_eval_posterior_batch(lh_family* fam, int32_t n, int32_t n_tips, int32_t max_depth, const int32_t* ops,
+                            const double* brlen, const double* er, const double* pi, const double* alpha,
+                            int32_t num_rates, const lh_posterior_outputs* outs);
+
+/* The same with every array (outs' members included) resident on the handle's device; enqueued on `hip_stream`
+ * without synchronising.  A schedule K0c rejects gives that sample NaN posteriors, leaves it out of weighted_sum and
+ * raises the handle's error word (lh_family_status). */
+int lh_eval_posterior_batch_device(lh_family* fam, int32_t n, int32_t n_tips, int32_t max_depth, const int32_t* ops,
+                                   const double* brlen, const double* er, const double* pi, const double* alpha,
+                                   int32_t num_rates, const lh_posterior_outputs* outs, void* hip_stream);
+
+/* Time of K5 (smoothing and reduction) over the lh_eval_posterior_batch[_device] calls made while profiling was
+ * enabled (HIP events on the launch stream); resets the counters. */
+int lh_posterior_profile_read(lh_family* fam, double* ms_posterior, int64_t* n_launches);
+
 /* Tree in rooted-at-naive form: tips are nodes 0..T-1 (0 = `naive`, i = MSA row i-1), inner nodes
  * T..2T-3.  children[2*(v-T)+{0,1}] are the two children of inner node v when the tree is rooted at
  * `root`, the inner node adjacent to `naive`.  Writes the kernel's post-order schedule:

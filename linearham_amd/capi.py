@@ -46,6 +46,14 @@ EXPORTS = ["lh_last_error", "lh_device_count", "lh_family_create", "lh_family_de
            "lh_profile_enable", "lh_profile_read", "lh_asr_profile_read", "lh_family_set_extended_range", "lh_warmup", "lh_host_alloc", "lh_host_free", "lh_family_set_sampler",
            "lh_sample_words", "lh_sample_states", "lh_eval_sample_batch", "lh_set_device", "lh_family_status",
            "lh_eval_sample_batch_device", "lh_family_prune_form"]
+# K5 (exact posterior state marginals)
+POSTERIOR_EXPORTS = ["lh_eval_posterior_batch", "lh_eval_posterior_batch_device", "lh_posterior_profile_read"]
+EXPORTS += POSTERIOR_EXPORTS
+
+
+class _PosteriorOutputs(C.Structure):
+    _fields_ = [("log_offset", c_f64p), ("loglik", c_f64p), ("posterior", c_f64p), ("weighted_sum", c_f64p),
+                ("weight_stats", c_f64p)]
 
 
 def library_path():
@@ -97,6 +105,13 @@ class HipLibrary:
                 [C.c_int32] + [C.c_void_p] * 5
             lib.lh_sample_words.argtypes = [C.c_void_p]
             lib.lh_sample_states.argtypes = [C.c_void_p]
+        if hasattr(lib, "lh_eval_posterior_batch"):
+            lib.lh_eval_posterior_batch.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, c_i32p, c_f64p, c_f64p,
+                                                    c_f64p, c_f64p, C.c_int32, C.POINTER(_PosteriorOutputs)]
+            lib.lh_eval_posterior_batch_device.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + \
+                [C.c_void_p] * 5 + [C.c_int32, C.POINTER(_PosteriorOutputs), C.c_void_p]
+            lib.lh_posterior_profile_read.argtypes = [C.c_void_p, c_f64p, C.POINTER(C.c_int64)]
+            lib.lh_forward_size.argtypes = [C.c_void_p]
         if hasattr(lib, "lh_set_device"):      # (absent from round-2 builds loaded through LH_LIB_DIR for comparisons)
             lib.lh_set_device.argtypes = [C.c_int32]
             lib.lh_family_status.argtypes = [C.c_void_p]
@@ -110,6 +125,41 @@ class HipLibrary:
 
     def device_count(self):
         return self.lib.lh_device_count()
+
+    def eval_posterior_batch(self, family, n_tips, max_depth, ops, brlen, er, pi, alpha, num_rates, log_offset=None,
+                             want=("loglik", "posterior", "weighted_sum", "weight_stats")):
+        """K0-K2 + K5 on a family handle (a raw lh_family* or a Family) that has sampler tables.  Returns a dict with the
+        members of `want`: loglik [n], posterior [n, forward_size], weighted_sum [forward_size], weight_stats [3]
+        (max lw, sum w, sum w^2 with lw = loglik - log_offset)."""
+        h = family.handle if isinstance(family, Family) else family
+        ops = np.ascontiguousarray(ops, dtype=np.int32)
+        n = ops.shape[0]
+        brlen, er, pi, alpha = _f64(brlen), _f64(er), _f64(pi), _f64(alpha)
+        fs = self.lib.lh_forward_size(h)
+        res = {}
+        if "loglik" in want:
+            res["loglik"] = np.zeros(n)
+        if "posterior" in want:
+            res["posterior"] = np.zeros((n, fs))
+        if "weighted_sum" in want:
+            res["weighted_sum"] = np.zeros(fs)
+        if "weight_stats" in want:
+            res["weight_stats"] = np.zeros(3)
+        lo = None if log_offset is None else _f64(log_offset)
+
+        def ptr(a):
+            return a.ctypes.data_as(c_f64p) if a is not None else None
+        outs = _PosteriorOutputs(ptr(lo), ptr(res.get("loglik")), ptr(res.get("posterior")), ptr(res.get("weighted_sum")),
+                                 ptr(res.get("weight_stats")))
+        self.check(self.lib.lh_eval_posterior_batch(h, n, n_tips, max_depth, ops.ctypes.data_as(c_i32p), ptr(brlen),
+                                                    ptr(er), ptr(pi), ptr(alpha), num_rates, C.byref(outs)))
+        return res
+
+    def posterior_profile_read(self, family):
+        h = family.handle if isinstance(family, Family) else family
+        ms, k = C.c_double(), C.c_int64()
+        self.check(self.lib.lh_posterior_profile_read(h, C.byref(ms), C.byref(k)))
+        return ms.value, k.value
 
     def schedule_tree(self, n_tips, children, root):
         """children: int32 [(T-2)*2]; returns (ops [T-2,4] int32, max_depth)."""

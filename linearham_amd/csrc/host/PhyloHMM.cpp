@@ -379,6 +379,123 @@ void PhyloHMM::SampleStatesWithWords(const uint32_t* words, int n_words, std::ve
   host_states.push_back(s.vgerm_state_ind);
 }
 
+std::vector<double> PhyloHMM::NaivePosterior(double* loglik) {
+  Require(have_tree_, "InitializePhyloParameters must be called first");
+  CreateFamily();
+  Require(device_sampler_, "the family has no device sampler tables (needed by the posterior kernel)");
+  const int T = tree_.n_tips;
+  std::vector<int32_t> ops((std::size_t)(T - 2) * 4);
+  int32_t depth = 0;
+  CheckHip(lh_schedule_tree(T, tree_.children.data(), tree_.root, ops.data(), &depth), "lh_schedule_tree");
+  std::vector<double> post(lh_forward_size(family_));
+  lh_posterior_outputs outs{nullptr, loglik, post.data(), nullptr, nullptr};
+  CheckHip(lh_eval_posterior_batch(family_, 1, T, depth, ops.data(), tree_.brlen.data(), er_.data(), pi_.data(), &alpha_,
+                                   num_rates_, &outs),
+           "lh_eval_posterior_batch");
+  return post;
+}
+
+// One walk over the compact posterior layout (lh_eval_outputs.forward: V | V-D rows | D | D-J rows | J): calls
+// germ(region letter, gene name, index in the region, value, region) for every germline-region gene and
+// junc(junction, row, dense state, site, naive base, value) for every junction state.  (Dense state posteriors in the
+// shapes of the forward members: linearham_amd/posterior.py.)
+template <typename G, typename J>
+static void WalkPosterior(const std::string& locus, const std::map<std::string, std::pair<int, int>>& fb,
+                          const RegionStates& vgerm, const RegionStates& vd, const RegionStates& dgerm,
+                          const RegionStates& dj, const RegionStates& jgerm, const double* post, G&& germ, J&& junc) {
+  const bool igh = locus == "igh";
+  std::size_t off = 0;
+  auto region = [&](char letter, const RegionStates& R) {
+    int g = 0;
+    for (const auto& kv : R.ggene_ranges) germ(letter, kv.first, g, post[off + g], R), ++g;
+    off += R.ggene_ranges.size();
+  };
+  auto junction = [&](const RegionStates& Jn, const RegionStates& L, const RegionStates& Rt, int site0, int W) {
+    const int nL = (int)L.ggene_ranges.size(), nR = (int)Rt.ggene_ranges.size();
+    const std::size_t stride = (std::size_t)nL + 5 * (std::size_t)nR;
+    int l = 0;
+    for (const auto& kv : L.ggene_ranges) {
+      const auto it = Jn.ggene_ranges.find(kv.first);
+      if (it != Jn.ggene_ranges.end())
+        for (int k = it->second.first; k < it->second.second; ++k) {
+          const int i = Jn.site_inds[k] - site0;
+          junc(Jn, i, k, Jn.site_inds[k], Jn.naive_bases[k], post[off + i * stride + l]);
+        }
+      ++l;
+    }
+    int r = 0;
+    for (const auto& kv : Rt.ggene_ranges) {
+      const auto it = Jn.ggene_ranges.find(kv.first);
+      Require(it != Jn.ggene_ranges.end(), "posterior layout: right gene missing from its junction");
+      const int rs = it->second.first, re = it->second.second;
+      for (int i = 0; i < W; ++i)
+        for (int a = 0; a < 4; ++a) junc(Jn, i, rs + a, site0 + i, a, post[off + i * stride + nL + 4 * r + a]);
+      for (int k = rs + 4; k < re; ++k) {
+        const int i = Jn.site_inds[k] - site0;
+        junc(Jn, i, k, Jn.site_inds[k], Jn.naive_bases[k], post[off + i * stride + nL + 4 * (std::size_t)nR + r]);
+      }
+      ++r;
+    }
+    off += (std::size_t)W * stride;
+  };
+  region('V', vgerm);
+  if (igh) {
+    junction(vd, vgerm, dgerm, fb.at("v_r").first, fb.at("d_l").second - fb.at("v_r").first);
+    region('D', dgerm);
+    junction(dj, dgerm, jgerm, fb.at("d_r").first, fb.at("j_l").second - fb.at("d_r").first);
+  } else {
+    junction(vd, vgerm, jgerm, fb.at("v_r").first, fb.at("j_l").second - fb.at("v_r").first);
+  }
+  region('J', jgerm);
+}
+
+PhyloHMM::NaiveMarginalsResult PhyloHMM::MapPosterior(const double* post) const {
+  NaiveMarginalsResult m;
+  m.site_base.assign(msa_.cols(), {0.0, 0.0, 0.0, 0.0, 0.0});
+  WalkPosterior(
+      locus_, flexbounds_, vgerm_, vd_junction_, dgerm_, dj_junction_, jgerm_, post,
+      [&](char letter, const std::string& name, int, double p, const RegionStates& R) {
+        m.genes.emplace_back(letter, name, p);
+        const auto& rg = R.ggene_ranges.at(name);
+        for (int k = rg.first; k < rg.second; ++k) m.site_base[R.site_inds[k]][R.naive_bases[k]] += p;
+      },
+      [&](const RegionStates&, int, int, int site, int base, double p) { m.site_base[site][base] += p; });
+  for (auto& s : m.site_base) s[4] += 1.0 - (s[0] + s[1] + s[2] + s[3] + s[4]);  // what no state writes stays N
+  return m;
+}
+
+PhyloHMM::NaiveMarginalsResult PhyloHMM::NaiveMarginals() {
+  double ll = 0;
+  const std::vector<double> post = NaivePosterior(&ll);
+  return MapPosterior(post.data());
+}
+
+void PhyloHMM::WriteSiteTable(std::ostream& o, const NaiveMarginalsResult& m) {
+  static const char kBases[] = "ACGTN";
+  char buf[64];
+  o << "site\tA\tC\tG\tT\tN\tmap_base\n";
+  for (std::size_t s = 0; s < m.site_base.size(); ++s) {
+    const auto& p = m.site_base[s];
+    o << s;
+    for (double v : p) {
+      std::snprintf(buf, sizeof buf, "%.17g", v);
+      o << '\t' << buf;
+    }
+    o << '\t' << kBases[std::max_element(p.begin(), p.end()) - p.begin()] << '\n';
+  }
+}
+
+void PhyloHMM::WriteGeneTable(std::ostream& o, const NaiveMarginalsResult& m) {
+  std::vector<std::tuple<char, std::string, double>> g = m.genes;
+  std::stable_sort(g.begin(), g.end(), [](const auto& a, const auto& b) { return std::get<2>(a) > std::get<2>(b); });
+  char buf[64];
+  o << "region\tgene\tprobability\n";
+  for (const auto& t : g) {
+    std::snprintf(buf, sizeof buf, "%.17g", std::get<2>(t));
+    o << std::get<0>(t) << '\t' << std::get<1>(t) << '\t' << buf << '\n';
+  }
+}
+
 void PhyloHMM::RunForwardAlgorithm() {
   UnpackForward(pending_forward_.data(), pending_scalers_.data());
   loglikelihood_ = pending_loglik_;
@@ -1400,6 +1517,58 @@ void PhyloHMM::SetExtendedRange(bool on) {
   if (lh_family_set_extended_range(family(), on ? 1 : 0)) throw std::runtime_error(lh_last_error());
   for (lh_family* f : more_families_)
     if (lh_family_set_extended_range(f, on ? 1 : 0)) throw std::runtime_error(lh_last_error());
+}
+
+void PhyloHMM::RunMarginalsPipeline(const std::string& input_path, const std::string& output_prefix, int num_rates,
+                                    double burnin_frac) {
+  Require(devices_.size() <= 1, "the marginals pipeline runs on one device: --devices may list only one");
+  Require(burnin_frac >= 0.0 && burnin_frac < 1.0, "burn-in fraction must be in [0, 1)");
+  CreateFamily();
+  Require(device_sampler_, "the family has no device sampler tables (needed by the posterior kernel)");
+  TsvTable table = TsvTable::Read(input_path, "RevBayes output file");
+  const char* names[15] = {"Iteration", "Likelihood", "Prior", "alpha", "er[1]", "er[2]", "er[3]", "er[4]",
+                           "er[5]", "er[6]",  "pi[1]", "pi[2]", "pi[3]", "pi[4]", "tree"};
+  table.Locate(names, 15, table.col, input_path);
+  const std::size_t N = table.rows.size();
+  const std::size_t first = (std::size_t)std::floor(burnin_frac * (double)N);
+  const std::size_t FS = (std::size_t)lh_forward_size(family_);
+  constexpr std::size_t kBatch = 49152;
+  // running combination of the batches' (sum w pi, max lw, sum w, sum w^2), each relative to the running max
+  std::vector<double> total(FS, 0.0), wsum(FS);
+  double mx = -INFINITY, s1 = 0.0, s2 = 0.0;
+  std::size_t skipped = 0;
+  for (std::size_t off = first; off < N; off += kBatch) {
+    const std::size_t m = std::min(kBatch, N - off);
+    TableBatch tb = FlattenTable(table, off, off + m, false, true, input_path);
+    const DeviceBatch& b = tb.dev;
+    std::vector<double> ll(m);
+    double st[3];
+    lh_posterior_outputs outs{tb.lik.data(), ll.data(), nullptr, wsum.data(), st};
+    CheckHip(lh_eval_posterior_batch(family_, b.n, b.n_tips, b.max_depth, b.ops.data(), b.brlen.data(), b.er.data(),
+                                     b.pi.data(), b.alpha.data(), num_rates, &outs),
+             "lh_eval_posterior_batch");
+    for (std::size_t i = 0; i < m; ++i)
+      if (!std::isfinite(ll[i] - tb.lik[i])) ++skipped;
+    if (!std::isfinite(st[0])) continue;
+    const double nm = std::max(mx, st[0]);
+    const double fo = std::isfinite(mx) ? std::exp(mx - nm) : 0.0, fn = std::exp(st[0] - nm);
+    for (std::size_t j = 0; j < FS; ++j) total[j] = total[j] * fo + wsum[j] * fn;
+    s1 = s1 * fo + st[1] * fn;
+    s2 = s2 * fo * fo + st[2] * fn * fn;
+    mx = nm;
+  }
+  Require(s1 > 0.0, "marginals pipeline: no row with a finite weight");
+  for (double& v : total) v /= s1;
+  const NaiveMarginalsResult res = MapPosterior(total.data());
+  std::ofstream sites(output_prefix + ".sites.tsv"), genes(output_prefix + ".genes.tsv"),
+      summary(output_prefix + ".summary.tsv");
+  Require(sites.good() && genes.good() && summary.good(), "Can't write " + output_prefix + ".*.tsv");
+  WriteSiteTable(sites, res);
+  WriteGeneTable(genes, res);
+  char buf[64];
+  std::snprintf(buf, sizeof buf, "%.17g", s1 * s1 / s2);
+  summary << "key\tvalue\nrows_used\t" << (N - first - skipped) << "\nrows_skipped_nonfinite\t" << skipped
+          << "\nkish_ess\t" << buf << "\n";
 }
 
 }  // namespace linearham

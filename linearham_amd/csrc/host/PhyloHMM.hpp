@@ -5,7 +5,11 @@
 #ifndef LINEARHAM_PHYLOHMM_
 #define LINEARHAM_PHYLOHMM_
 
+#include <array>
 #include <fstream>
+#include <map>
+#include <ostream>
+#include <tuple>
 #include <memory>
 #include <string>
 #include <vector>
@@ -91,6 +95,25 @@ class PhyloHMM : public HMM {
   /// outputs GIVEN (n_words >= RawDrawsPerSample(), at most 624), once by the device sampler (lh_eval_sample_batch)
   /// and once by the host sampler (HMM::SampleRow on a std::mt19937 whose state is set so that it returns exactly these
   /// words).  States as lh_eval_sample_batch lays them out.
+  // Exact posterior state marginals of the current tree (K5, lh_eval_posterior_batch), in the compact layout of
+  // lh_eval_outputs.forward; NaN if the log-likelihood is not finite.  Needs the device sampler tables.
+  std::vector<double> NaivePosterior(double* loglik);
+  /// What the compact posteriors mean: per alignment site the distribution of the naive base over A, C, G, T, N, and
+  /// the posterior of every V / D / J gene (region letter, gene name as the pipeline's VGene / DGene / JGene spell it).
+  struct NaiveMarginalsResult {
+    std::vector<std::array<double, 5>> site_base;
+    std::vector<std::tuple<char, std::string, double>> genes;
+  };
+  NaiveMarginalsResult MapPosterior(const double* post) const;
+  /// After InitializePhyloEmission: the exact marginals of the current tree (K5).
+  NaiveMarginalsResult NaiveMarginals();
+  /// Importance-weighted marginals over a RevBayes table: the first floor(burnin_frac * rows) rows are dropped
+  /// (scripts/run_bootstrap_asr_ess.R:23), each row is weighted by exp(LHLogLikelihood - RBLogLikelihood), batches of at
+  /// most 49 152 rows are combined in file order.  Writes <prefix>.sites.tsv, .genes.tsv and .summary.tsv.
+  void RunMarginalsPipeline(const std::string& input_path, const std::string& output_prefix, int num_rates,
+                            double burnin_frac);
+  static void WriteSiteTable(std::ostream& o, const NaiveMarginalsResult& m);
+  static void WriteGeneTable(std::ostream& o, const NaiveMarginalsResult& m);
   void SampleStatesWithWords(const uint32_t* words, int n_words, std::vector<int32_t>& device_states,
                              std::vector<int32_t>& host_states);
 

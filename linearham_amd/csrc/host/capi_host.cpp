@@ -241,6 +241,42 @@ int lhh_phylo_sample_words(void* h, const uint32_t* words, int n_words, int32_t*
   });
 }
 
+// PhyloHMM::NaivePosterior: post [cap >= lh_forward_size]; *n receives the count, *loglik the log-likelihood.
+// post == NULL: only *n (the family's lh_forward_size), nothing is evaluated.
+int lhh_phylo_posterior(void* h, double* post, int cap, int* n, double* loglik) {
+  return Guard([&] {
+    if (!post) {
+      *n = (int)lh_forward_size(dynamic_cast<PhyloHMM&>(*static_cast<HMM*>(h)).family());
+      return;
+    }
+    const std::vector<double> p = dynamic_cast<PhyloHMM&>(*static_cast<HMM*>(h)).NaivePosterior(loglik);
+    if ((int)p.size() > cap) throw std::runtime_error("lhh_phylo_posterior: output too small");
+    std::copy(p.begin(), p.end(), post);
+    *n = (int)p.size();
+  });
+}
+
+// PhyloHMM::NaiveMarginals through the C++ mapping: site_base [L][5]; the gene table as lines "R\tgene\tp" in *genes.
+int lhh_phylo_naive_marginals(void* h, double* site_base, int cap_sites, const char** genes) {
+  return Guard([&] {
+    const PhyloHMM::NaiveMarginalsResult m = dynamic_cast<PhyloHMM&>(*static_cast<HMM*>(h)).NaiveMarginals();
+    if ((int)m.site_base.size() > cap_sites) throw std::runtime_error("lhh_phylo_naive_marginals: output too small");
+    for (std::size_t s = 0; s < m.site_base.size(); ++s)
+      for (int b = 0; b < 5; ++b) site_base[s * 5 + b] = m.site_base[s][b];
+    std::ostringstream o;
+    PhyloHMM::WriteGeneTable(o, m);
+    g_out = o.str();
+    *genes = g_out.c_str();
+  });
+}
+
+int lhh_run_marginals_pipeline(void* h, const char* input_path, const char* output_prefix, int num_rates,
+                               double burnin_frac) {
+  return Guard([&] {
+    dynamic_cast<PhyloHMM&>(*static_cast<HMM*>(h)).RunMarginalsPipeline(input_path, output_prefix, num_rates, burnin_frac);
+  });
+}
+
 int lhh_run_pipeline(void* h, const char* input_path, const char* output_path, int num_rates) {
   return Guard([&] { dynamic_cast<PhyloHMM&>(*static_cast<HMM*>(h)).RunPipeline(input_path, output_path, num_rates); });
 }

@@ -1,6 +1,7 @@
 // `linearham` command line (same sub-commands and flag names as src/linearham.cpp:268-455 of the
 // reference, without TCLAP): --compute-logl | --sample | --pipeline; plus --asr, the per-tree body of
-// scripts/run_bootstrap_asr_ess.R:48-104 on a --pipeline output table.
+// scripts/run_bootstrap_asr_ess.R:48-104 on a --pipeline output table, and --marginals / --marginals-pipeline, the exact
+// posterior of the naive sequence (one tree / importance-weighted over a RevBayes table).
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -54,8 +55,12 @@ int main(int argc, char** argv) {
   try {
     if (argc < 2 || std::string(argv[1]) == "-h" || std::string(argv[1]) == "--help") {
       std::cout << "A Phylo-HMM implementation for B cell receptor sequence analysis.\n"
-                   "USAGE: linearham {--compute-logl|--sample|--pipeline|--asr} --yaml-path <string> --cluster-ind <int> "
-                   "--hmm-param-dir <string> [--seed <int>] [--num-rates <int>] [--extended-range <0|1>] [--devices <a,b,...>] ...\n";
+                   "USAGE: linearham {--compute-logl|--sample|--pipeline|--asr|--marginals|--marginals-pipeline} --yaml-path <string> "
+                   "--cluster-ind <int> --hmm-param-dir <string> [--seed <int>] [--num-rates <int>] [--extended-range <0|1>] "
+                   "[--devices <a,b,...>] ...\n"
+                   "  --marginals: the arguments of --compute-logl; prints the per-site naive-base table and the gene table\n"
+                   "  --marginals-pipeline --input-path <RevBayes table> --output-path <prefix> [--burnin-frac <f>]: writes\n"
+                   "    <prefix>.sites.tsv, <prefix>.genes.tsv and <prefix>.summary.tsv (one device)\n";
       return argc < 2 ? EXIT_FAILURE : EXIT_SUCCESS;
     }
     const auto t_main = std::chrono::steady_clock::now();
@@ -63,7 +68,8 @@ int main(int argc, char** argv) {
     auto since_start = [&] { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t_main).count(); };
     const std::string subcmd = argv[1];
     const Args a = Parse(argc, argv, 2);
-    if (subcmd != "--compute-logl" && subcmd != "--sample" && subcmd != "--pipeline" && subcmd != "--asr")
+    if (subcmd != "--compute-logl" && subcmd != "--sample" && subcmd != "--pipeline" && subcmd != "--asr" &&
+        subcmd != "--marginals" && subcmd != "--marginals-pipeline")
       throw std::invalid_argument("'" + subcmd + "' is not a valid subcommand.");
     const std::string yaml_path = a.one("yaml-path");
     const int cluster_ind = std::stoi(a.one("cluster-ind"));
@@ -81,6 +87,8 @@ int main(int argc, char** argv) {
         device_list.push_back(std::stoi(devs.substr(pos, comma - pos)));
         pos = comma + 1;
       }
+      if (device_list.size() > 1 && subcmd == "--marginals-pipeline")
+        throw std::invalid_argument("--marginals-pipeline runs on one device: --devices may list only one");
       if (device_list.size() > 1 && subcmd != "--pipeline")
         std::fprintf(stderr, "linearham: %s evaluates on one device; of --devices only device %d is used\n", subcmd.c_str(),
                      device_list[0]);
@@ -115,6 +123,11 @@ int main(int argc, char** argv) {
       if (timing) std::fprintf(stderr, "[main] family released at %.3f s\n", since_start());
       return EXIT_SUCCESS;
     }
+    if (subcmd == "--marginals-pipeline") {
+      phylo_hmm_ptr->RunMarginalsPipeline(a.one("input-path"), a.one("output-path"), num_rates,
+                                          std::stod(a.opt("burnin-frac", "0")));
+      return EXIT_SUCCESS;
+    }
     if (subcmd == "--asr") {
       phylo_hmm_ptr->RunAsr(a.one("input-path"), a.one("output-path"), (uint64_t)std::stoll(a.opt("seed", "0")));
       return EXIT_SUCCESS;
@@ -124,6 +137,11 @@ int main(int argc, char** argv) {
     phylo_hmm_ptr->InitializePhyloEmission();
     if (subcmd == "--compute-logl") {
       std::cout << phylo_hmm_ptr->LogLikelihood() << std::endl;
+    } else if (subcmd == "--marginals") {
+      const linearham::PhyloHMM::NaiveMarginalsResult m = phylo_hmm_ptr->NaiveMarginals();
+      linearham::PhyloHMM::WriteSiteTable(std::cout, m);
+      std::cout << "\n";
+      linearham::PhyloHMM::WriteGeneTable(std::cout, m);
     } else {
       const int N = std::stoi(a.opt("N", "1"));
       for (int i = 0; i < N; i++) std::cout << phylo_hmm_ptr->SampleNaiveSequence() << std::endl;

@@ -80,6 +80,15 @@ struct AsrWs {  // K3's CLV area and the device copies of lh_asr_batch's host ar
   std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
 };
 
+struct PosteriorWs {  // K5's device buffers (grow-only): forward / posterior arrays, loglik, weights, slab partial sums,
+                      // and lh_eval_posterior_batch's device copies of its host arrays
+  size_t cap[12] = {0};
+  void* ptr[12] = {nullptr};
+  double ms = 0;  // K5 time of the profiled launches (lh_profile_enable)
+  int64_t launches = 0;
+  std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
+};
+
 struct Staging {  // device copies of host inputs/outputs for the host-pointer entry points
   size_t cap[10] = {0};
   void* ptr[10] = {nullptr};
@@ -109,6 +118,7 @@ struct lh_family {
   Workspace ws;
   ForwardWs fws;
   AsrWs asr;
+  PosteriorWs post;
   Staging st;
   HostPipe pipe;
   bool profile = false;
@@ -773,6 +783,12 @@ void lh_family_destroy(lh_family* f) {
     for (hipEvent_t e : es.e) (void)hipEventDestroy(e);
   for (void* p : f->smp.ptr)
     if (p) (void)hipFree(p);
+  for (void* p : f->post.ptr)
+    if (p) (void)hipFree(p);
+  for (auto& ev : f->post.events) {
+    (void)hipEventDestroy(ev.first);
+    (void)hipEventDestroy(ev.second);
+  }
   if (f->smp.pinned) (void)hipHostFree(f->smp.pinned);
   for (void* p : f->pipe.pinned)
     if (p) (void)hipHostFree(p);
@@ -1591,6 +1607,130 @@ int lh_forward_batch(lh_family* f, int32_t n, const double* em, double* loglik, 
       LH_HIP(hipMemcpy(outs->scaler_counts, d_outs.scaler_counts, sizeof(int32_t) * SS * n,
                        hipMemcpyDeviceToHost));
   }
+  return 0;
+}
+
+// K5's grow-only device buffers (a growing call first waits for earlier work that may still use the old one)
+static int post_buf(lh_family* f, int slot, size_t bytes, void** out) {
+  PosteriorWs& pw = f->post;
+  if (bytes > pw.cap[slot]) {
+    LH_HIP(hipDeviceSynchronize());
+    if (pw.ptr[slot]) LH_HIP(hipFree(pw.ptr[slot]));
+    pw.ptr[slot] = nullptr;
+    pw.cap[slot] = 0;
+    LH_HIP(hipMalloc(&pw.ptr[slot], std::max<size_t>(bytes, 64)));
+    pw.cap[slot] = std::max<size_t>(bytes, 64);
+  }
+  *out = pw.ptr[slot];
+  return 0;
+}
+
+int lh_eval_posterior_batch_device(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops,
+                                   const double* brlen, const double* er, const double* pi, const double* alpha, int32_t R,
+                                   const lh_posterior_outputs* outs, void* hip_stream) {
+  if (!f) return fail("lh_eval_posterior_batch_device: null family");
+  DeviceGuard guard(f);
+  if (!f->have_sampler) return fail("lh_eval_posterior_batch_device: lh_family_set_sampler has not been called");
+  if (n <= 0) return n == 0 ? 0 : fail("lh_eval_posterior_batch_device: negative batch size");
+  hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+  const lh_posterior_outputs none{nullptr, nullptr, nullptr, nullptr, nullptr};
+  const lh_posterior_outputs& o = outs ? *outs : none;
+  const size_t FS = f->host.forward_size;
+  // the forward arrays go where the posteriors are wanted: K5 overwrites them in place
+  double* post = o.posterior;
+  double* ll = o.loglik;
+  if (!post && post_buf(f, 0, sizeof(double) * FS * n, (void**)&post)) return 1;
+  if (!ll && post_buf(f, 1, sizeof(double) * n, (void**)&ll)) return 1;
+  double *w = nullptr, *stats = o.weight_stats, *partial = nullptr;
+  const bool reduce = o.weighted_sum || o.weight_stats;
+  if (reduce) {
+    if (post_buf(f, 2, sizeof(double) * n, (void**)&w)) return 1;
+    if (!stats && post_buf(f, 3, sizeof(double) * 3, (void**)&stats)) return 1;
+    if (o.weighted_sum && post_buf(f, 4, sizeof(double) * FS * lh::posterior_slabs(n), (void**)&partial)) return 1;
+  }
+  lh_eval_outputs eo{nullptr, nullptr, post, nullptr};
+  if (lh_eval_batch_device(f, n, T, max_depth, ops, brlen, er, pi, alpha, R, ll, &eo, hip_stream)) return 1;
+  std::pair<hipEvent_t, hipEvent_t> ev{nullptr, nullptr};
+  if (f->profile) {
+    LH_HIP(hipEventCreate(&ev.first));
+    LH_HIP(hipEventCreate(&ev.second));
+    LH_HIP(hipEventRecord(ev.first, stream));
+  }
+  lh::launch_posterior(f->sampler_dev, n, post, FS, ll, stream);
+  if (reduce) lh::launch_posterior_reduce(n, FS, post, ll, o.log_offset, w, partial, o.weighted_sum, stats, stream);
+  if (f->profile) {
+    LH_HIP(hipEventRecord(ev.second, stream));
+    f->post.events.push_back(ev);
+  }
+  LH_HIP(hipGetLastError());
+  return 0;
+}
+
+int lh_eval_posterior_batch(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops,
+                            const double* brlen, const double* er, const double* pi, const double* alpha, int32_t R,
+                            const lh_posterior_outputs* outs) {
+  if (!f) return fail("lh_eval_posterior_batch: null family");
+  DeviceGuard guard(f);
+  if (!f->have_sampler) return fail("lh_eval_posterior_batch: lh_family_set_sampler has not been called");
+  if (n <= 0) return n == 0 ? 0 : fail("lh_eval_posterior_batch: negative batch size");
+  if (T < 3) return fail("lh_eval_posterior_batch: need at least 3 tips");
+  if (!ops || !brlen || !er || !pi || !alpha) return fail("lh_eval_posterior_batch: null array");
+  const lh_posterior_outputs none{nullptr, nullptr, nullptr, nullptr, nullptr};
+  const lh_posterior_outputs& o = outs ? *outs : none;
+  const size_t nodes = 2 * (size_t)T - 2, n_ops = (size_t)T - 2, FS = f->host.forward_size;
+  // slots 5..10: the inputs; 0, 1, 11, 3: posterior, loglik, weighted sum, weight statistics
+  const size_t in_bytes[6] = {sizeof(int32_t) * 4 * n_ops * n, sizeof(double) * nodes * n, sizeof(double) * 6 * n,
+                              sizeof(double) * 4 * n, sizeof(double) * n, sizeof(double) * n};
+  const void* src[6] = {ops, brlen, er, pi, alpha, o.log_offset};
+  void* d[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  for (int a = 0; a < 6; ++a) {
+    if (!src[a]) continue;
+    if (post_buf(f, 5 + a, in_bytes[a], &d[a])) return 1;
+  }
+  lh_posterior_outputs dev{(const double*)d[5], nullptr, nullptr, nullptr, nullptr};
+  if (post_buf(f, 0, sizeof(double) * FS * n, (void**)&dev.posterior)) return 1;
+  if (post_buf(f, 1, sizeof(double) * n, (void**)&dev.loglik)) return 1;
+  if (o.weighted_sum && post_buf(f, 11, sizeof(double) * FS, (void**)&dev.weighted_sum)) return 1;
+  if (o.weight_stats && post_buf(f, 3, sizeof(double) * 3, (void**)&dev.weight_stats)) return 1;
+  if (!o.posterior && !o.weighted_sum && !o.weight_stats && !o.loglik) return 0;  // nothing asked for
+  LH_HIP(hipDeviceSynchronize());  // earlier calls may still be using the buffers
+  for (int a = 0; a < 6; ++a)
+    if (src[a]) LH_HIP(hipMemcpyAsync(d[a], src[a], in_bytes[a], hipMemcpyHostToDevice, nullptr));
+  if (lh_eval_posterior_batch_device(f, n, T, max_depth, (const int32_t*)d[0], (const double*)d[1], (const double*)d[2],
+                                     (const double*)d[3], (const double*)d[4], R, &dev, nullptr))
+    return 1;
+  // the schedules are checked on the host while the device works on them, as in lh_eval_sample_batch
+  if (!valid_schedules(ops, (size_t)n, T, (int)nodes, max_depth)) {
+    (void)hipDeviceSynchronize();
+    (void)check_async_error(f, "lh_eval_posterior_batch");
+    return fail("lh_eval_posterior_batch: malformed schedule op (use lh_schedule_tree)");
+  }
+  if (check_async_error(f, "lh_eval_posterior_batch")) return 1;
+  if (o.loglik) LH_HIP(hipMemcpy(o.loglik, dev.loglik, sizeof(double) * n, hipMemcpyDeviceToHost));
+  if (o.posterior) LH_HIP(hipMemcpy(o.posterior, dev.posterior, sizeof(double) * FS * n, hipMemcpyDeviceToHost));
+  if (o.weighted_sum) LH_HIP(hipMemcpy(o.weighted_sum, dev.weighted_sum, sizeof(double) * FS, hipMemcpyDeviceToHost));
+  if (o.weight_stats) LH_HIP(hipMemcpy(o.weight_stats, dev.weight_stats, sizeof(double) * 3, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int lh_posterior_profile_read(lh_family* f, double* ms_posterior, int64_t* n_launches) {
+  if (!f) return fail("null family");
+  DeviceGuard guard(f);
+  PosteriorWs& pw = f->post;
+  for (auto& ev : pw.events) {
+    LH_HIP(hipEventSynchronize(ev.second));
+    float ms = 0;
+    LH_HIP(hipEventElapsedTime(&ms, ev.first, ev.second));
+    pw.ms += ms;
+    ++pw.launches;
+    (void)hipEventDestroy(ev.first);
+    (void)hipEventDestroy(ev.second);
+  }
+  pw.events.clear();
+  if (ms_posterior) *ms_posterior = pw.ms;
+  if (n_launches) *n_launches = pw.launches;
+  pw.ms = 0;
+  pw.launches = 0;
   return 0;
 }
 

@@ -174,6 +174,17 @@ struct DevSampler {
 void launch_sample(const DevSampler& smp, const DevSampler* smp_dev, int n, const double* fwd, size_t forward_size, const uint32_t* words,
                    int words_per_sample, int32_t* states, hipStream_t stream);
 
+// K5 (lh_posterior.hip): the compact forward arrays post[n][forward_size] are replaced in place by the posterior state
+// marginals of the same entries (NaN for a sample whose loglik is not finite).
+void launch_posterior(const DevSampler* smp_dev, int n, double* post, size_t forward_size, const double* loglik,
+                      hipStream_t stream);
+// K5's reduction: w[n] = exp(lw - max lw), lw = loglik - log_offset (log_offset may be null; 0 where lw is not
+// finite), stats[3] = max lw, sum w, sum w^2; weighted_sum[forward_size] = sum_i w_i post[i] (skipped if null), through
+// partial[posterior_slabs(n)][forward_size].  Fixed summation order, no atomics.
+int posterior_slabs(int n);
+void launch_posterior_reduce(int n, size_t forward_size, const double* post, const double* loglik, const double* log_offset,
+                             double* w, double* partial, double* weighted_sum, double* stats, hipStream_t stream);
+
 // P = I + U expm1(lambda * t*r) Uinv, clamped at 0 (K1's prologue).
 // e: lambda[4] | U[4][4] | Uinv[4][4]
 // (mode 0 is the stationary one, eigenvalue 0 -- K0a orders them so -- and contributes nothing: three modes are summed)

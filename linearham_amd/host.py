@@ -62,6 +62,26 @@ def newick_arrays(newick, labels):
     return children, root.value, brlen
 
 
+def _parse_gene_table(text):
+    genes = {}
+    for line in text.strip().split("\n")[1:]:
+        reg, name, p = line.split("\t")
+        genes.setdefault(reg, {})[name] = float(p)
+    return genes
+
+
+def read_marginals(prefix):
+    """(site_base [L][5], {"V"|"D"|"J": {gene: p}}, summary dict) from the files RunMarginalsPipeline writes."""
+    lines = open(prefix + ".sites.tsv").read().strip().split("\n")[1:]
+    sb = np.array([[float(x) for x in ln.split("\t")[1:6]] for ln in lines])
+    genes = _parse_gene_table(open(prefix + ".genes.tsv").read())
+    summary = {}
+    for ln in open(prefix + ".summary.tsv").read().strip().split("\n")[1:]:
+        k, v = ln.split("\t")
+        summary[k] = float(v) if k == "kish_ess" else int(v)
+    return sb, genes, summary
+
+
 class _HMM:
     def __init__(self, handle):
         self.h = handle
@@ -133,6 +153,41 @@ class PhyloHMM(_HMM):
         _check(self.lib.lhh_phylo_sample_words(self.h, w.ctypes.data, len(w), d.ctypes.data, s.ctypes.data, 4096,
                                                C.byref(n)))
         return d[:n.value].copy(), s[:n.value].copy()
+
+    def naive_posterior(self):
+        """(compact posterior [lh_forward_size], log-likelihood) of the current tree: K0-K2 + K5 on the device."""
+        self.lib.lhh_phylo_posterior.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int),
+                                                 C.POINTER(C.c_double)]
+        n, ll = C.c_int(), C.c_double()
+        _check(self.lib.lhh_phylo_posterior(self.h, None, 0, C.byref(n), None))
+        buf = np.zeros(n.value)
+        _check(self.lib.lhh_phylo_posterior(self.h, buf.ctypes.data, n.value, C.byref(n), C.byref(ll)))
+        return buf, ll.value
+
+    def dense_posteriors(self):
+        """Exact state posteriors of the current tree in the shapes of the forward members (dump(2)): vgerm, vd_junction,
+        dgerm, dj_junction, jgerm."""
+        from . import posterior
+        return posterior.dense_posteriors(self.dump(1), self.naive_posterior()[0])
+
+    def naive_marginals(self):
+        """(site_base [L][5] over A, C, G, T, N; {"V"|"D"|"J": {gene: posterior}}) of the current tree
+        (PhyloHMM::NaiveMarginals)."""
+        L = self.sizes()["n_sites"]
+        sb = np.zeros((L, 5))
+        out = C.c_char_p()
+        self.lib.lhh_phylo_naive_marginals.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_char_p)]
+        _check(self.lib.lhh_phylo_naive_marginals(self.h, sb.ctypes.data, L, C.byref(out)))
+        return sb, _parse_gene_table(out.value.decode())
+
+    def run_marginals_pipeline(self, input_path, output_prefix, num_rates, burnin_frac=0.0):
+        """PhyloHMM::RunMarginalsPipeline: importance-weighted exact marginals over a RevBayes table (burn-in
+        floor(burnin_frac * rows), weights exp(LHLogLikelihood - RBLogLikelihood)).  Writes <prefix>.sites.tsv,
+        .genes.tsv and .summary.tsv and returns (site_base, genes, summary) read back from them."""
+        self.lib.lhh_run_marginals_pipeline.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_int, C.c_double]
+        _check(self.lib.lhh_run_marginals_pipeline(self.h, input_path.encode(), output_prefix.encode(), num_rates,
+                                                   C.c_double(burnin_frac)))
+        return read_marginals(output_prefix)
 
     def run_pipeline(self, input_path, output_path, num_rates):
         _check(self.lib.lhh_run_pipeline(self.h, input_path.encode(), output_path.encode(), num_rates))
