@@ -1,6 +1,7 @@
 // C ABI of liblinearham_hip.so (see include/linearham_amd.h): family upload, tree scheduling,
 // batched evaluation.  Host-side code only; the kernels live in lh_model/lh_prune/lh_forward.hip.
 #include <algorithm>
+#include <array>
 #include <map>
 #include <cstdio>
 #include <cstring>
@@ -8,6 +9,7 @@
 #include <chrono>
 #include <string>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #include "lh_device.h"
@@ -53,61 +55,154 @@ int fail(const std::string& msg) {
       return fail(std::string(#expr) + ": " + hipGetErrorString(e_));                     \
   } while (0)
 
-struct Workspace {
-  int n_cap = 0, R = 0, T = 0;
-  double *rates = nullptr, *eig = nullptr, *site_lik = nullptr;
-  int32_t* site_scal = nullptr;
-  lh::PruneWs prune{};  // K0c's checked / rewritten schedules and K1's scratch area; err_flag is the family's
+// A grow-only buffer of device memory or (Pinned) page-locked host memory.  ensure() leaves at least 64 bytes, so that an
+// empty request still gets an address.  Growing first waits for the device: queued work may still read the old allocation.
+// Buffers only grow, so the steady state neither allocates nor waits.
+template <bool Pinned>
+class Buffer {
+ public:
+  Buffer() = default;
+  Buffer(const Buffer&) = delete;
+  Buffer& operator=(const Buffer&) = delete;
+  ~Buffer() { release(); }
+  int ensure(size_t bytes) {
+    bytes = std::max<size_t>(bytes, 64);
+    if (bytes <= cap_) return 0;
+    if (p_) {
+      LH_HIP(hipDeviceSynchronize());
+      release();
+    }
+    LH_HIP(Pinned ? hipHostMalloc(&p_, bytes, hipHostMallocDefault) : hipMalloc(&p_, bytes));
+    cap_ = bytes;
+    return 0;
+  }
+  template <typename T = void>
+  T* get() const { return static_cast<T*>(p_); }
+
+ private:
+  void release() {
+    if (p_) (void)(Pinned ? hipHostFree(p_) : hipFree(p_));
+    p_ = nullptr;
+    cap_ = 0;
+  }
+  void* p_ = nullptr;
+  size_t cap_ = 0;
+};
+using DevBuf = Buffer<false>;
+using PinnedBuf = Buffer<true>;
+
+// lh_profile_enable's kernel times: HIP events at the Stages + 1 boundaries of every profiled launch group, summed and
+// reset by a read.
+template <int Stages>
+class KernelTimer {
+ public:
+  KernelTimer() = default;
+  KernelTimer(const KernelTimer&) = delete;
+  KernelTimer& operator=(const KernelTimer&) = delete;
+  ~KernelTimer() {
+    for (Events& es : done_) destroy(es);
+    destroy(open_);
+  }
+  // begin() records boundary 0 on `s`, mark(k) boundary k, end() the last one
+  int begin(hipStream_t s) {
+    destroy(open_);  // (a launch group that failed leaves its set open)
+    for (hipEvent_t& e : open_) LH_HIP(hipEventCreate(&e));
+    return mark(0, s);
+  }
+  int mark(int k, hipStream_t s) {
+    LH_HIP(hipEventRecord(open_[k], s));
+    return 0;
+  }
+  int end(hipStream_t s) {
+    if (mark(Stages, s)) return 1;
+    done_.push_back(std::exchange(open_, Events{}));
+    return 0;
+  }
+  // Waits for the launch groups recorded since the last read and hands out their times per stage (ms[Stages]) and their
+  // number; either may be null.
+  int read(double* ms, int64_t* launches) {
+    double sum[Stages] = {};
+    hipError_t e = hipSuccess;
+    for (Events& es : done_) {
+      if (e == hipSuccess) e = hipEventSynchronize(es[Stages]);
+      for (int k = 0; k < Stages && e == hipSuccess; ++k) {
+        float t = 0;
+        e = hipEventElapsedTime(&t, es[k], es[k + 1]);
+        sum[k] += t;
+      }
+      destroy(es);
+    }
+    const int64_t n = (int64_t)done_.size();
+    done_.clear();
+    LH_HIP(e);
+    if (ms) std::copy(sum, sum + Stages, ms);
+    if (launches) *launches = n;
+    return 0;
+  }
+
+ private:
+  using Events = std::array<hipEvent_t, Stages + 1>;
+  static void destroy(Events& es) {
+    for (hipEvent_t& e : es)
+      if (e) (void)hipEventDestroy(std::exchange(e, nullptr));
+  }
+  std::vector<Events> done_;
+  Events open_{};
 };
 
-struct ForwardWs {  // K2a -> K2b hand-off, sized by the largest batch seen
-  int n_cap = 0;
-  double *gem = nullptr, *jem = nullptr, *dxf = nullptr;
-  int32_t *gcnt = nullptr, *jrs = nullptr, *dxc = nullptr;
+struct Workspace {  // K0-K2's scratch (ensure_workspace)
+  DevBuf rates, eig, site_lik, site_scal;
+  DevBuf scratch, wops, wlen, tabs, hdr;  // K0c's checked / rewritten schedules and K1's scratch area
+  lh::PruneWs prune{};                    // the same five as launch_prune takes them; err_flag is the family's
 };
 
-struct AsrWs {  // K3's CLV area and the device copies of lh_asr_batch's host arrays (grow-only)
-  size_t clv_cap = 0;
-  double* clv = nullptr;
-  size_t choice_cap = 0;
-  uint8_t* choice = nullptr;  // K3a -> K3b when the caller does not ask for the rate categories
-  size_t desc_cap = 0;
-  void* desc = nullptr;       // K3s -> K3b schedule descriptors
-  size_t cap[8] = {0};
-  void* ptr[8] = {nullptr};
-  double ms = 0;          // K3 time of the profiled launches (lh_profile_enable)
-  int64_t launches = 0;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
+struct ForwardWs {  // K2a -> K2b hand-off (run_forward)
+  DevBuf gem, jem, dxf, gcnt, jrs, dxc;
 };
 
-struct PosteriorWs {  // K5's device buffers (grow-only): forward / posterior arrays, loglik, weights, slab partial sums,
-                      // and lh_eval_posterior_batch's device copies of its host arrays
-  size_t cap[12] = {0};
-  void* ptr[12] = {nullptr};
-  double ms = 0;  // K5 time of the profiled launches (lh_profile_enable)
-  int64_t launches = 0;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
+struct AsrWs {  // K3's scratch
+  DevBuf clv;
+  DevBuf choice;  // K3a -> K3b when the caller does not ask for the rate categories
+  DevBuf desc;    // K3s -> K3b schedule descriptors
 };
 
-struct Staging {  // device copies of host inputs/outputs for the host-pointer entry points
-  size_t cap[10] = {0};
-  void* ptr[10] = {nullptr};
+struct PosteriorWs {  // K5's arrays that the caller of lh_eval_posterior_batch_device does not hand in
+  DevBuf loglik, weights, stats, partial;
+};
+
+// Device copies of the host-pointer entry points' arrays.  The entry points share them on purpose: each waits for the device
+// before it fills them and before it returns, and a handle is driven by one thread at a time.
+struct HostInputs {
+  DevBuf ops, brlen, er, pi, alpha;
+  DevBuf rates, naive;  // lh_asr_batch
+  DevBuf words;         // lh_eval_sample_batch
+  DevBuf log_offset;    // lh_eval_posterior_batch
+  DevBuf em;            // lh_forward_batch
+};
+struct HostOutputs {
+  DevBuf loglik, rates, xmsa_emission, forward, scaler_counts;
+  DevBuf states;                     // lh_eval_sample_batch
+  DevBuf anc, rate_choice;           // lh_asr_batch
+  DevBuf weighted_sum, weight_stats;  // lh_eval_posterior_batch
 };
 
 // lh_eval_batch's host -> device pipeline: two pinned staging slots, a copy stream and a compute stream
 struct HostPipe {
-  void* pinned[2] = {nullptr, nullptr};
-  size_t cap = 0;
+  PinnedBuf pinned[2];
   hipStream_t copy = nullptr, comp = nullptr;
   hipEvent_t staged[2] = {nullptr, nullptr};
-};
-
-struct EventSet {
-  hipEvent_t e[4];
+  ~HostPipe() {
+    for (hipEvent_t e : staged)
+      if (e) (void)hipEventDestroy(e);
+    if (copy) (void)hipStreamDestroy(copy);
+    if (comp) (void)hipStreamDestroy(comp);
+  }
 };
 
 }  // namespace
 
+// Everything a handle owns.  Its buffers, events and streams release themselves; lh_family_destroy deletes the handle with
+// its device current.
 struct lh_family {
   int device = 0;
   lh::DevFamily host{};            // device pointers inside
@@ -119,25 +214,23 @@ struct lh_family {
   ForwardWs fws;
   AsrWs asr;
   PosteriorWs post;
-  Staging st;
+  // forward arrays that stay on the device, shared by K4 and K5 in both their forms: K4 draws from them, K5 overwrites
+  // them with the posteriors (calls on a handle do not overlap: they also share the workspace)
+  DevBuf forward_dev;
+  HostInputs in;
+  HostOutputs out;
+  PinnedBuf staging;  // stage_inputs' page-locked slot
   HostPipe pipe;
   bool profile = false;
+  KernelTimer<3> eval_timer;  // model, prune, forward
+  KernelTimer<1> asr_timer, post_timer;
   bool extended = false;  // lh_family_set_extended_range
   bool have_sampler = false;
   lh::DevSampler sampler{};  // device pointers inside (arena)
   const lh::DevSampler* sampler_dev = nullptr;  // its device copy (K4 reads the tables' addresses from memory)
-  struct {                   // lh_eval_sample_batch's device buffers (grow-only)
-    size_t cap[9] = {0};
-    void* ptr[9] = {nullptr};
-    void* pinned = nullptr;  // page-locked staging of the six input arrays
-    size_t pinned_cap = 0;
-  } smp;
   int32_t n_ucol_used = 0;  // (naive base, pattern) pairs some xMSA column has (lh_family_info)
   int32_t* err_flag = nullptr;  // device word (arena): K0c sets it when a schedule is malformed (lh_family_status)
   std::string k1_form;          // the K1 kernel form of the last evaluation (lh_family_prune_form)
-  std::vector<EventSet> events;
-  double ms[3] = {0, 0, 0};
-  int64_t launches = 0;
 };
 
 namespace {
@@ -409,48 +502,21 @@ size_t k1_bytes_per_sample(const lh_family* f, int T, int R) {
          z.tabs_per_sample * sizeof(int4) + sizeof(int4);
 }
 
+// Sizes the workspace for launch groups of n samples (buffers only grow: a smaller R or T reuses them).
 int ensure_workspace(lh_family* f, int n, int R, int T) {
   Workspace& w = f->ws;
-  if (n <= w.n_cap && R == w.R && T == w.T) return 0;
-  void** bufs[] = {(void**)&w.rates,         (void**)&w.eig,        (void**)&w.site_lik,   (void**)&w.site_scal,
-                   (void**)&w.prune.scratch, (void**)&w.prune.wops, (void**)&w.prune.wlen, (void**)&w.prune.tabs,
-                   (void**)&w.prune.hdr};
-  for (void** b : bufs) {
-    if (*b) LH_HIP(hipFree(*b));
-    *b = nullptr;
-  }
-  w.n_cap = 0;
-  const size_t L = f->host.n_prune;
-  const int cap = std::max(n, 1);
-  LH_HIP(hipMalloc((void**)&w.rates, sizeof(double) * cap * R));
-  LH_HIP(hipMalloc((void**)&w.eig, sizeof(double) * cap * 36));
+  const size_t L = std::max<size_t>(f->host.n_prune, 1), cap = std::max(n, 1);
   // K1's scratch area per (sample, rate): the walk's P-matrices and cherry tables; K0c's per-sample schedule arrays
   const lh::PruneWsSizes z = lh::prune_ws_sizes(T, f->host.msa_mixed_n != 0);
   const size_t n_ops = (size_t)std::max(T - 2, 1);
-  LH_HIP(hipMalloc((void**)&w.prune.scratch, sizeof(double) * cap * R * z.scratch_doubles_per_rate));
-  LH_HIP(hipMalloc((void**)&w.prune.wops, sizeof(int2) * cap * n_ops));
-  LH_HIP(hipMalloc((void**)&w.prune.wlen, sizeof(double) * cap * n_ops));
-  LH_HIP(hipMalloc((void**)&w.prune.tabs, sizeof(int4) * cap * z.tabs_per_sample));
-  LH_HIP(hipMalloc((void**)&w.prune.hdr, sizeof(int4) * cap));
-  w.prune.err_flag = f->err_flag;
-  LH_HIP(hipMalloc((void**)&w.site_lik, sizeof(double) * cap * R * 5 * std::max(L, (size_t)1)));
-  LH_HIP(hipMalloc((void**)&w.site_scal, sizeof(int32_t) * cap * R * std::max(L, (size_t)1)));
-  w.n_cap = cap;
-  w.R = R;
-  w.T = T;
-  return 0;
-}
-
-int stage(lh_family* f, int slot, size_t bytes, void** out) {
-  Staging& s = f->st;
-  if (bytes > s.cap[slot]) {
-    if (s.ptr[slot]) LH_HIP(hipFree(s.ptr[slot]));
-    s.ptr[slot] = nullptr;
-    s.cap[slot] = 0;
-    LH_HIP(hipMalloc(&s.ptr[slot], bytes));
-    s.cap[slot] = bytes;
-  }
-  *out = s.ptr[slot];
+  if (w.rates.ensure(sizeof(double) * cap * R) || w.eig.ensure(sizeof(double) * cap * 36) ||
+      w.scratch.ensure(sizeof(double) * cap * R * z.scratch_doubles_per_rate) || w.wops.ensure(sizeof(int2) * cap * n_ops) ||
+      w.wlen.ensure(sizeof(double) * cap * n_ops) || w.tabs.ensure(sizeof(int4) * cap * z.tabs_per_sample) ||
+      w.hdr.ensure(sizeof(int4) * cap) || w.site_lik.ensure(sizeof(double) * cap * R * 5 * L) ||
+      w.site_scal.ensure(sizeof(int32_t) * cap * R * L))
+    return 1;
+  w.prune = {w.scratch.get<double>(), w.wops.get<int2>(), w.wlen.get<double>(), w.tabs.get<int4>(), w.hdr.get<int4>(),
+             f->err_flag};
   return 0;
 }
 
@@ -465,26 +531,159 @@ int run_forward(lh_family* f, int n, int R, const double* site_lik, const int32_
   int32_t* sco =
       (outs && outs->scaler_counts) ? outs->scaler_counts + sample_offset * f->host.scaler_size : nullptr;
   ForwardWs& w = f->fws;
-  if (n > w.n_cap) {
-    // growing the hand-off buffers: earlier launches on other streams may still be using them
-    LH_HIP(hipDeviceSynchronize());
-    void** bufs[] = {(void**)&w.gem, (void**)&w.jem, (void**)&w.gcnt, (void**)&w.jrs, (void**)&w.dxf, (void**)&w.dxc};
-    for (void** b : bufs) {
-      if (*b) LH_HIP(hipFree(*b));
-      *b = nullptr;
-    }
-    w.n_cap = 0;
-    LH_HIP(hipMalloc((void**)&w.jrs, sizeof(int32_t) * (size_t)n * std::max(f->host.vd.n_rows + f->host.dj.n_rows, 1)));
-    LH_HIP(hipMalloc((void**)&w.dxf, sizeof(double) * (size_t)n * 32));
-    LH_HIP(hipMalloc((void**)&w.dxc, sizeof(int32_t) * (size_t)n));
-    LH_HIP(hipMalloc((void**)&w.gem, sizeof(double) * (size_t)n * std::max<int64_t>(f->host.gem_size, 1)));
-    LH_HIP(hipMalloc((void**)&w.jem, sizeof(double) * (size_t)n * std::max(f->host.n_jcols, 1)));
-    LH_HIP(hipMalloc((void**)&w.gcnt, sizeof(int32_t) * (size_t)n * 3));
-    w.n_cap = n;
-  }
-  lh::launch_forward(f->host, f->dev, n, R, site_lik, site_scal, pi, em_in, em_out, w.gem, w.gcnt, w.jem, w.jrs, w.dxf, w.dxc,
-                     loglik_dev, fwd, sco, f->extended, stream);
+  const size_t m = n;
+  if (w.jrs.ensure(sizeof(int32_t) * m * std::max(f->host.vd.n_rows + f->host.dj.n_rows, 1)) ||
+      w.dxf.ensure(sizeof(double) * m * 32) || w.dxc.ensure(sizeof(int32_t) * m) ||
+      w.gem.ensure(sizeof(double) * m * std::max<int64_t>(f->host.gem_size, 1)) ||
+      w.jem.ensure(sizeof(double) * m * std::max(f->host.n_jcols, 1)) || w.gcnt.ensure(sizeof(int32_t) * m * 3))
+    return 1;
+  lh::launch_forward(f->host, f->dev, n, R, site_lik, site_scal, pi, em_in, em_out, w.gem.get<double>(), w.gcnt.get<int32_t>(),
+                     w.jem.get<double>(), w.jrs.get<int32_t>(), w.dxf.get<double>(), w.dxc.get<int32_t>(), loglik_dev, fwd, sco,
+                     f->extended, stream);
   LH_HIP(hipGetLastError());
+  return 0;
+}
+
+// Reads (and clears) the handle's asynchronous error word after synchronising its device.
+int check_async_error(lh_family* f, const char* who) {
+  int32_t flag = 0;
+  LH_HIP(hipDeviceSynchronize());
+  LH_HIP(hipMemcpy(&flag, f->err_flag, sizeof(flag), hipMemcpyDeviceToHost));
+  if (flag) {
+    LH_HIP(hipMemset(f->err_flag, 0, sizeof(flag)));
+    return fail(std::string(who) + ": malformed schedule op (use lh_schedule_tree); the affected samples' results are NaN");
+  }
+  return 0;
+}
+
+// The argument checks of every entry point that evaluates trees, `w` naming it in the messages.  Returns 1 (error set) for
+// a malformed call, -1 for an empty batch and 0 otherwise: `if (int rc = check_batch(...)) return rc > 0;`
+int check_batch(const lh_family* f, const std::string& w, int n, int T, int R, int max_depth, bool needs_sampler = false) {
+  if (!f) return fail(w + ": null family");
+  if (needs_sampler && !f->have_sampler) return fail(w + ": lh_family_set_sampler has not been called");
+  if (n < 0) return fail(w + ": negative batch size");
+  if (n == 0) return -1;
+  if (f->host.n_seqs < 1) return fail(w + ": family was created without an MSA (forward-only)");
+  if (T != f->host.n_seqs + 1) return fail(w + ": n_tips must equal n_seqs + 1 (naive)");
+  if (T < 3) return fail(w + ": need at least 3 tips");
+  if (R < 1 || R > 64) return fail(w + ": num_rates out of range");
+  if (max_depth < 0 || max_depth > 16) return fail(w + ": max_depth out of range");
+  // (launch_prune checks the LDS need of the form it takes -- trees this large with a stack deeper than four slots do not fit)
+  if ((size_t)T * 128 > 160 * 1024) return fail(w + ": too many tips for the LDS tip table");
+  return 0;
+}
+
+// One schedule op as lh_schedule_tree writes it (a malformed op would index out of bounds on the device).
+bool valid_op(const int32_t* op, int T, int nodes, int max_depth) {
+  const int kind = op[0] & 15;
+  const bool push = op[0] & lh::OP_PUSH_FLAG;
+  const int rank = op[0] >> lh::OP_RANK_SHIFT;  // bits 5-7 unused
+  bool ok = (op[0] & 0xe0) == 0 && op[0] >= 0 && kind <= 2 && rank <= T - 3;
+  if (kind == lh::OP_CHERRY) ok = ok && op[1] >= 1 && op[1] < T && op[2] >= 1 && op[2] < T;
+  if (kind == lh::OP_TIP_ACC) ok = ok && !push && op[1] >= 1 && op[1] < T && op[2] >= T && op[2] < nodes;
+  if (kind == lh::OP_POP_ACC) ok = ok && !push && op[1] >= T && op[1] < nodes && op[2] >= T && op[2] < nodes;
+  if (push || kind == lh::OP_POP_ACC) ok = ok && op[3] >= 0 && op[3] < max_depth;
+  return ok;
+}
+
+// One sample's schedule: every op well-formed, and the rank field of each op the running count of inner-branch matrices
+// lh_schedule_tree leaves there (a tip-accumulate op takes one, a pop-accumulate op two, a cherry none; T - 3 in all) --
+// the fused K1 prologue files its matrices by that number.  (The kernels check the same thing again on the device:
+// schedules may also arrive in device memory.)
+// And the stack discipline: a push goes to slot = the number of pending siblings, a pop takes the last one, none is left at
+// the end (a schedule that breaks it within the slot range computes a finite, wrong likelihood; the device checks repeat this).
+bool valid_schedule(const int32_t* ops, int T, int nodes, int max_depth) {
+  int count = 0, depth = 0;
+  for (int k = 0; k < T - 2; ++k) {
+    const int32_t* op = ops + (size_t)k * 4;
+    if (!valid_op(op, T, nodes, max_depth)) return false;
+    const int kind = op[0] & 15, rank = op[0] >> lh::OP_RANK_SHIFT;
+    if (kind == lh::OP_CHERRY) {
+      if (rank != 0 && rank != count) return false;
+      if (((op[0] & lh::OP_PUSH_FLAG) != 0) != (k != 0)) return false;  // the first op has no accumulator to set aside, every later cherry does
+      if (k != 0 && op[3] != depth++) return false;
+    } else {
+      if (rank != count) return false;
+      count += kind == lh::OP_POP_ACC ? 2 : 1;
+      if (kind == lh::OP_POP_ACC && op[3] != --depth) return false;
+    }
+  }
+  return count == T - 3 && depth == 0;
+}
+
+// fn(lo, hi) on nw threads that split [0, n) between them (on the calling thread when nw is 1)
+template <typename Fn>
+void in_threads(size_t n, int nw, Fn&& fn) {
+  if (nw <= 1) return fn((size_t)0, n);
+  std::vector<std::thread> pool;
+  for (int t = 0; t < nw; ++t) pool.emplace_back(fn, n * t / nw, n * (t + 1) / nw);
+  for (std::thread& th : pool) th.join();
+}
+
+// All schedules of a batch; a few threads when the batch is large (0.19 us per op on one core: 0.4 ms per 2048 samples of
+// a 101-tip tree, as much as the device then needs for K0-K2).
+bool valid_schedules(const int32_t* ops, size_t n, int T, int nodes, int max_depth) {
+  const size_t n_ops = (size_t)T - 2;
+  const int nw = (int)std::max<size_t>(1, std::min<size_t>({(size_t)std::thread::hardware_concurrency(), (size_t)8, n * n_ops / 65536}));
+  std::atomic<bool> bad{false};
+  in_threads(n, nw, [&](size_t lo, size_t hi) {
+    for (size_t i = lo; i < hi && !bad; ++i)
+      if (!valid_schedule(ops + i * n_ops * 4, T, nodes, max_depth)) bad = true;
+  });
+  return !bad;
+}
+
+struct HostIn { const void* src; size_t bytes; DevBuf* dst; };  // a host array to copy in (src null: none)
+struct HostOut { void* dst; const void* src; size_t bytes; };    // a device result to copy back (dst null: not wanted)
+
+// Host inputs of a host-pointer entry point -> their device buffers.  The caller's arrays are ordinary pageable memory:
+// copied from there, every transfer has the driver lock and unlock their pages, which stalls for milliseconds whenever
+// other threads of the process are busy allocating (RunPipeline's formatting workers are).  One memcpy each into the
+// handle's page-locked slot (64-byte aligned) costs a fraction of that; the copies go on the default stream.
+int stage_inputs(lh_family* f, std::initializer_list<HostIn> in) {
+  auto padded = [](size_t b) { return (b + 63) & ~(size_t)63; };
+  size_t total = 0;
+  for (const HostIn& a : in)
+    if (a.src) {
+      if (a.dst->ensure(a.bytes)) return 1;
+      total += padded(a.bytes);
+    }
+  if (f->staging.ensure(total)) return 1;
+  LH_HIP(hipDeviceSynchronize());  // earlier calls may still be using the buffers
+  char* slot = f->staging.get<char>();
+  for (const HostIn& a : in)
+    if (a.src) {
+      memcpy(slot, a.src, a.bytes);
+      LH_HIP(hipMemcpyAsync(a.dst->get(), slot, a.bytes, hipMemcpyHostToDevice, nullptr));
+      slot += padded(a.bytes);
+    }
+  return 0;
+}
+
+// `want` (a host output the caller asked for) gets device buffer b, `bytes` long, as *d; else *d is null.
+template <typename T>
+int out_buf(const T* want, DevBuf& b, size_t bytes, T** d) {
+  if (want && b.ensure(bytes)) return 1;
+  *d = want ? b.get<T>() : nullptr;
+  return 0;
+}
+
+// The host-pointer calls check their schedules on the host WHILE the device works on them: the kernels make the same checks
+// themselves (a malformed op costs that sample a NaN and the handle an error code, never an out-of-bounds access), so
+// nothing is risked by the order.  A batch the host check refuses hands nothing back:
+int refuse_schedules(lh_family* f, const char* who) {
+  (void)hipDeviceSynchronize();
+  (void)check_async_error(f, who);  // (the device found it too: one report is enough)
+  return fail(std::string(who) + ": malformed schedule op (use lh_schedule_tree)");
+}
+
+// The end of a host-pointer call: waits for the device, reads K0c's verdict on the schedules as the device saw them (`who`
+// null: the call ran none), and copies the results back.
+int copy_back(lh_family* f, const char* who, std::initializer_list<HostOut> out) {
+  if (!who) LH_HIP(hipDeviceSynchronize());
+  if (who && check_async_error(f, who)) return 1;
+  for (const HostOut& o : out)
+    if (o.dst) LH_HIP(hipMemcpy(o.dst, o.src, o.bytes, hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -762,41 +961,7 @@ void lh_family_destroy(lh_family* f) {
   if (!f) return;
   DeviceGuard guard(f);
   for (void* p : f->allocs) (void)hipFree(p);
-  Workspace& w = f->ws;
-  void* bufs[] = {w.rates,    w.eig,       w.site_lik, w.site_scal, w.prune.scratch, w.prune.wops, w.prune.wlen,
-                  w.prune.tabs, w.prune.hdr, f->fws.gem, f->fws.jem,  f->fws.gcnt,     f->fws.jrs,   f->fws.dxf,
-                  f->fws.dxc};
-  for (void* b : bufs)
-    if (b) (void)hipFree(b);
-  for (void* p : f->st.ptr)
-    if (p) (void)hipFree(p);
-  if (f->asr.clv) (void)hipFree(f->asr.clv);
-  if (f->asr.choice) (void)hipFree(f->asr.choice);
-  if (f->asr.desc) (void)hipFree(f->asr.desc);
-  for (void* p : f->asr.ptr)
-    if (p) (void)hipFree(p);
-  for (auto& ev : f->asr.events) {
-    (void)hipEventDestroy(ev.first);
-    (void)hipEventDestroy(ev.second);
-  }
-  for (EventSet& es : f->events)
-    for (hipEvent_t e : es.e) (void)hipEventDestroy(e);
-  for (void* p : f->smp.ptr)
-    if (p) (void)hipFree(p);
-  for (void* p : f->post.ptr)
-    if (p) (void)hipFree(p);
-  for (auto& ev : f->post.events) {
-    (void)hipEventDestroy(ev.first);
-    (void)hipEventDestroy(ev.second);
-  }
-  if (f->smp.pinned) (void)hipHostFree(f->smp.pinned);
-  for (void* p : f->pipe.pinned)
-    if (p) (void)hipHostFree(p);
-  for (hipEvent_t e : f->pipe.staged)
-    if (e) (void)hipEventDestroy(e);
-  if (f->pipe.copy) (void)hipStreamDestroy(f->pipe.copy);
-  if (f->pipe.comp) (void)hipStreamDestroy(f->pipe.comp);
-  delete f;
+  delete f;  // the members release their buffers, events and streams while the guard keeps the family's device current
 }
 
 int64_t lh_forward_size(const lh_family* f) { return f ? f->host.forward_size : 0; }
@@ -1018,18 +1183,6 @@ int lh_family_set_sampler(lh_family* f, const lh_sampler_desc* desc) {
 int32_t lh_sample_words(const lh_family* f) { return f && f->have_sampler ? f->sampler.words_per_sample : 0; }
 int32_t lh_sample_states(const lh_family* f) { return f && f->have_sampler ? f->sampler.states_per_sample : 0; }
 
-// Reads (and clears) the handle's asynchronous error word after synchronising its device.
-static int check_async_error(lh_family* f, const char* who) {
-  int32_t flag = 0;
-  LH_HIP(hipDeviceSynchronize());
-  LH_HIP(hipMemcpy(&flag, f->err_flag, sizeof(flag), hipMemcpyDeviceToHost));
-  if (flag) {
-    LH_HIP(hipMemset(f->err_flag, 0, sizeof(flag)));
-    return fail(std::string(who) + ": malformed schedule op (use lh_schedule_tree); the affected samples' results are NaN");
-  }
-  return 0;
-}
-
 int lh_family_status(lh_family* f) {
   if (!f) return fail("lh_family_status: null family");
   DeviceGuard guard(f);
@@ -1045,61 +1198,25 @@ int lh_profile_enable(lh_family* f, int enable) {
 int lh_profile_read(lh_family* f, double* ms_model, double* ms_prune, double* ms_forward, int64_t* n_launches) {
   if (!f) return fail("null family");
   DeviceGuard guard(f);
-  for (EventSet& es : f->events) {
-    LH_HIP(hipEventSynchronize(es.e[3]));
-    for (int k = 0; k < 3; ++k) {
-      float ms = 0;
-      LH_HIP(hipEventElapsedTime(&ms, es.e[k], es.e[k + 1]));
-      f->ms[k] += ms;
-    }
-    for (hipEvent_t e : es.e) (void)hipEventDestroy(e);
-    ++f->launches;
-  }
-  f->events.clear();
-  if (ms_model) *ms_model = f->ms[0];
-  if (ms_prune) *ms_prune = f->ms[1];
-  if (ms_forward) *ms_forward = f->ms[2];
-  if (n_launches) *n_launches = f->launches;
-  f->ms[0] = f->ms[1] = f->ms[2] = 0;
-  f->launches = 0;
+  double ms[3];
+  if (f->eval_timer.read(ms, n_launches)) return 1;
+  if (ms_model) *ms_model = ms[0];
+  if (ms_prune) *ms_prune = ms[1];
+  if (ms_forward) *ms_forward = ms[2];
   return 0;
 }
 
 int lh_asr_profile_read(lh_family* f, double* ms_sampling, int64_t* n_launches) {
   if (!f) return fail("null family");
   DeviceGuard guard(f);
-  AsrWs& a = f->asr;
-  for (auto& ev : a.events) {
-    LH_HIP(hipEventSynchronize(ev.second));
-    float ms = 0;
-    LH_HIP(hipEventElapsedTime(&ms, ev.first, ev.second));
-    a.ms += ms;
-    ++a.launches;
-    (void)hipEventDestroy(ev.first);
-    (void)hipEventDestroy(ev.second);
-  }
-  a.events.clear();
-  if (ms_sampling) *ms_sampling = a.ms;
-  if (n_launches) *n_launches = a.launches;
-  a.ms = 0;
-  a.launches = 0;
-  return 0;
+  return f->asr_timer.read(ms_sampling, n_launches);
 }
 
 int lh_eval_batch_device(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops,
                          const double* brlen, const double* er, const double* pi, const double* alpha,
                          int32_t R, double* loglik, const lh_eval_outputs* outs, void* hip_stream) {
-  if (!f) return fail("lh_eval_batch: null family");
+  if (int rc = check_batch(f, "lh_eval_batch", n, T, R, max_depth)) return rc > 0;
   DeviceGuard guard(f);
-  if (n < 0) return fail("lh_eval_batch: negative batch size");
-  if (n == 0) return 0;
-  if (f->host.n_seqs < 1) return fail("lh_eval_batch: family was created without an MSA (forward-only)");
-  if (T != f->host.n_seqs + 1) return fail("lh_eval_batch: n_tips must equal n_seqs + 1 (naive)");
-  if (T < 3) return fail("lh_eval_batch: need at least 3 tips");
-  if (R < 1 || R > 64) return fail("lh_eval_batch: num_rates out of range");
-  if (max_depth < 0 || max_depth > 16) return fail("lh_eval_batch: max_depth out of range");
-  // (launch_prune checks the LDS need of the form it takes -- trees this large with a stack deeper than four slots do not fit)
-  if ((size_t)T * 128 > 160 * 1024) return fail("lh_eval_batch: too many tips for the LDS tip table");
   if (!ops || !brlen || !er || !pi || !alpha || !loglik) return fail("lh_eval_batch: null array");
   hipStream_t stream = static_cast<hipStream_t>(hip_stream);
   // launch groups of at most kChunk samples and at most ~16 GB of per-sample workspace
@@ -1108,93 +1225,28 @@ int lh_eval_batch_device(lh_family* f, int32_t n, int32_t T, int32_t max_depth, 
   const int chunk = std::min<int>(n, std::min(kChunk, by_memory));
   if (ensure_workspace(f, chunk, R, T)) return 1;
   Workspace& w = f->ws;
+  double *eig = w.eig.get<double>(), *site_lik = w.site_lik.get<double>();
+  int32_t* site_scal = w.site_scal.get<int32_t>();
   const size_t nodes = 2 * (size_t)T - 2, n_ops = (size_t)T - 2, C = f->host.n_xmsa;
   for (int off = 0; off < n; off += chunk) {
     const int m = std::min(chunk, n - off);
-    EventSet es;
-    if (f->profile) {
-      for (hipEvent_t& e : es.e) LH_HIP(hipEventCreate(&e));
-      LH_HIP(hipEventRecord(es.e[0], stream));
-    }
-    double* rates = (outs && outs->rates) ? outs->rates + (size_t)off * R : w.rates;
+    if (f->profile && f->eval_timer.begin(stream)) return 1;
+    double* rates = (outs && outs->rates) ? outs->rates + (size_t)off * R : w.rates.get<double>();
     double* em_out = (outs && outs->xmsa_emission) ? outs->xmsa_emission + (size_t)off * C : nullptr;
-    lh::launch_model_setup(m, R, er + (size_t)off * 6, pi + (size_t)off * 4, alpha + off, rates, w.eig,
-                           stream);
-    if (f->profile) LH_HIP(hipEventRecord(es.e[1], stream));
+    lh::launch_model_setup(m, R, er + (size_t)off * 6, pi + (size_t)off * 4, alpha + off, rates, eig, stream);
+    if (f->profile && f->eval_timer.mark(1, stream)) return 1;
     const int planes = lh::launch_prune(f->host, m, R, T, max_depth, ops + (size_t)off * n_ops * 4,
-                                        brlen + (size_t)off * nodes, rates, w.eig, w.prune, pi + (size_t)off * 4,
-                                        w.site_lik, w.site_scal, stream);
+                                        brlen + (size_t)off * nodes, rates, eig, w.prune, pi + (size_t)off * 4, site_lik,
+                                        site_scal, stream);
     if (planes < 0) return fail(std::string("lh_eval_batch: ") + lh::prune_last_error());
     f->k1_form = lh::prune_last_form();
-    if (f->profile) LH_HIP(hipEventRecord(es.e[2], stream));
-    if (run_forward(f, m, planes, w.site_lik, w.site_scal, pi + (size_t)off * 4, nullptr, em_out, loglik + off, outs, off,
-                    stream))
+    if (f->profile && f->eval_timer.mark(2, stream)) return 1;
+    if (run_forward(f, m, planes, site_lik, site_scal, pi + (size_t)off * 4, nullptr, em_out, loglik + off, outs, off, stream))
       return 1;
-    if (f->profile) {
-      LH_HIP(hipEventRecord(es.e[3], stream));
-      f->events.push_back(es);
-    }
+    if (f->profile && f->eval_timer.end(stream)) return 1;
     LH_HIP(hipGetLastError());
   }
   return 0;
-}
-
-// One schedule op as lh_schedule_tree writes it (a malformed op would index out of bounds on the device).
-static bool valid_op(const int32_t* op, int T, int nodes, int max_depth) {
-  const int kind = op[0] & 15;
-  const bool push = op[0] & lh::OP_PUSH_FLAG;
-  const int rank = op[0] >> lh::OP_RANK_SHIFT;  // bits 5-7 unused
-  bool ok = (op[0] & 0xe0) == 0 && op[0] >= 0 && kind <= 2 && rank <= T - 3;
-  if (kind == lh::OP_CHERRY) ok = ok && op[1] >= 1 && op[1] < T && op[2] >= 1 && op[2] < T;
-  if (kind == lh::OP_TIP_ACC) ok = ok && !push && op[1] >= 1 && op[1] < T && op[2] >= T && op[2] < nodes;
-  if (kind == lh::OP_POP_ACC) ok = ok && !push && op[1] >= T && op[1] < nodes && op[2] >= T && op[2] < nodes;
-  if (push || kind == lh::OP_POP_ACC) ok = ok && op[3] >= 0 && op[3] < max_depth;
-  return ok;
-}
-
-// One sample's schedule: every op well-formed, and the rank field of each op the running count of inner-branch matrices
-// lh_schedule_tree leaves there (a tip-accumulate op takes one, a pop-accumulate op two, a cherry none; T - 3 in all) --
-// the fused K1 prologue files its matrices by that number.  (The kernels check the same thing again on the device:
-// schedules may also arrive in device memory.)
-// And the stack discipline: a push goes to slot = the number of pending siblings, a pop takes the last one, none is left at
-// the end (a schedule that breaks it within the slot range computes a finite, wrong likelihood; the device checks repeat this).
-static bool valid_schedule(const int32_t* ops, int T, int nodes, int max_depth) {
-  int count = 0, depth = 0;
-  for (int k = 0; k < T - 2; ++k) {
-    const int32_t* op = ops + (size_t)k * 4;
-    if (!valid_op(op, T, nodes, max_depth)) return false;
-    const int kind = op[0] & 15, rank = op[0] >> lh::OP_RANK_SHIFT;
-    if (kind == lh::OP_CHERRY) {
-      if (rank != 0 && rank != count) return false;
-      if (((op[0] & lh::OP_PUSH_FLAG) != 0) != (k != 0)) return false;  // the first op has no accumulator to set aside, every later cherry does
-      if (k != 0 && op[3] != depth++) return false;
-    } else {
-      if (rank != count) return false;
-      count += kind == lh::OP_POP_ACC ? 2 : 1;
-      if (kind == lh::OP_POP_ACC && op[3] != --depth) return false;
-    }
-  }
-  return count == T - 3 && depth == 0;
-}
-
-// All schedules of a batch; a few threads when the batch is large (0.19 us per op on one core: 0.4 ms per 2048 samples of
-// a 101-tip tree, as much as the device then needs for K0-K2).
-static bool valid_schedules(const int32_t* ops, size_t n, int T, int nodes, int max_depth) {
-  const size_t n_ops = (size_t)T - 2;
-  const int nw = (int)std::max<size_t>(1, std::min<size_t>({(size_t)std::thread::hardware_concurrency(), (size_t)8, n * n_ops / 65536}));
-  std::atomic<bool> bad{false};
-  auto work = [&](size_t lo, size_t hi) {
-    for (size_t i = lo; i < hi && !bad; ++i)
-      if (!valid_schedule(ops + i * n_ops * 4, T, nodes, max_depth)) bad = true;
-  };
-  if (nw == 1) {
-    work(0, n);
-  } else {
-    std::vector<std::thread> pool;
-    for (int t = 0; t < nw; ++t) pool.emplace_back(work, n * t / nw, n * (t + 1) / nw);
-    for (std::thread& th : pool) th.join();
-  }
-  return !bad;
 }
 
 // Host pointers in, host pointers out.  The batch moves in sub-chunks through two pinned staging slots:
@@ -1203,35 +1255,34 @@ static bool valid_schedules(const int32_t* ops, size_t n, int T, int nodes, int 
 int lh_eval_batch(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops,
                   const double* brlen, const double* er, const double* pi, const double* alpha, int32_t R,
                   double* loglik, const lh_eval_outputs* outs) {
-  if (!f) return fail("lh_eval_batch: null family");
+  if (int rc = check_batch(f, "lh_eval_batch", n, T, R, max_depth)) return rc > 0;
   DeviceGuard guard(f);
-  if (n <= 0) return n == 0 ? 0 : fail("lh_eval_batch: negative batch size");
-  if (T < 3) return fail("lh_eval_batch: need at least 3 tips");
   if (!ops || !brlen || !er || !pi || !alpha || !loglik) return fail("lh_eval_batch: null array");
   const size_t nodes = 2 * (size_t)T - 2, n_ops = (size_t)T - 2;
-  void *d_ops, *d_brlen, *d_er, *d_pi, *d_alpha, *d_ll;
-  if (stage(f, 0, sizeof(int32_t) * 4 * n_ops * n, &d_ops)) return 1;
-  if (stage(f, 1, sizeof(double) * nodes * n, &d_brlen)) return 1;
-  if (stage(f, 2, sizeof(double) * 6 * n, &d_er)) return 1;
-  if (stage(f, 3, sizeof(double) * 4 * n, &d_pi)) return 1;
-  if (stage(f, 4, sizeof(double) * n, &d_alpha)) return 1;
-  if (stage(f, 5, sizeof(double) * n, &d_ll)) return 1;
-  lh_eval_outputs d_outs{nullptr, nullptr, nullptr, nullptr};
   const size_t C = f->host.n_xmsa, FS = f->host.forward_size, SS = f->host.scaler_size;
-  if (outs) {
-    if (outs->rates && stage(f, 6, sizeof(double) * R * n, (void**)&d_outs.rates)) return 1;
-    if (outs->xmsa_emission && stage(f, 7, sizeof(double) * C * n, (void**)&d_outs.xmsa_emission)) return 1;
-    if (outs->forward && stage(f, 8, sizeof(double) * FS * n, (void**)&d_outs.forward)) return 1;
-    if (outs->scaler_counts && stage(f, 9, sizeof(int32_t) * SS * n, (void**)&d_outs.scaler_counts)) return 1;
-  }
+  const lh_eval_outputs none{nullptr, nullptr, nullptr, nullptr};
+  const lh_eval_outputs& o = outs ? *outs : none;
+  HostOutputs& out = f->out;
+  lh_eval_outputs d_outs{nullptr, nullptr, nullptr, nullptr};
+  if (out.loglik.ensure(sizeof(double) * n) || out_buf(o.rates, out.rates, sizeof(double) * R * n, &d_outs.rates) ||
+      out_buf(o.xmsa_emission, out.xmsa_emission, sizeof(double) * C * n, &d_outs.xmsa_emission) ||
+      out_buf(o.forward, out.forward, sizeof(double) * FS * n, &d_outs.forward) ||
+      out_buf(o.scaler_counts, out.scaler_counts, sizeof(int32_t) * SS * n, &d_outs.scaler_counts))
+    return 1;
+  double* d_ll = out.loglik.get<double>();
 
   // per-sample bytes of the five input arrays, in the order they sit in a staging slot
   const size_t bytes[5] = {sizeof(int32_t) * 4 * n_ops, sizeof(double) * nodes, sizeof(double) * 6,
                            sizeof(double) * 4, sizeof(double)};
   const char* src[5] = {(const char*)ops, (const char*)brlen, (const char*)er, (const char*)pi, (const char*)alpha};
-  char* dst[5] = {(char*)d_ops, (char*)d_brlen, (char*)d_er, (char*)d_pi, (char*)d_alpha};
+  DevBuf* in[5] = {&f->in.ops, &f->in.brlen, &f->in.er, &f->in.pi, &f->in.alpha};
+  char* dst[5];
   size_t per_sample = 0;
-  for (size_t b : bytes) per_sample += b;
+  for (int a = 0; a < 5; ++a) {
+    if (in[a]->ensure(bytes[a] * n)) return 1;
+    dst[a] = in[a]->get<char>();
+    per_sample += bytes[a];
+  }
   const int kSub = lh::debug_options().host_sub;  // (default 12 288: whole rounds of all kernels for configs[2]-like shapes)
   const int sub = std::min<int>(n, kSub);
   HostPipe& hp = f->pipe;
@@ -1240,15 +1291,7 @@ int lh_eval_batch(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const i
     LH_HIP(hipStreamCreateWithFlags(&hp.comp, hipStreamNonBlocking));
     for (hipEvent_t& e : hp.staged) LH_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
   }
-  if (hp.cap < per_sample * sub) {
-    for (void*& p : hp.pinned) {
-      if (p) LH_HIP(hipHostFree(p));
-      p = nullptr;
-    }
-    hp.cap = 0;
-    for (void*& p : hp.pinned) LH_HIP(hipHostMalloc(&p, per_sample * sub, hipHostMallocDefault));
-    hp.cap = per_sample * sub;
-  }
+  if (hp.pinned[0].ensure(per_sample * sub) || hp.pinned[1].ensure(per_sample * sub)) return 1;
   LH_HIP(hipDeviceSynchronize());  // the staging buffers may still be in use by an earlier device-pointer call
 
   const int n_workers = (int)std::max(1u, std::min(std::thread::hardware_concurrency(), 8u));
@@ -1258,31 +1301,13 @@ int lh_eval_batch(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const i
   for (int off = 0; off < n && !rc; off += sub, slot ^= 1) {
     const int m = std::min(sub, n - off);
     if (slot_used[slot]) LH_HIP(hipEventSynchronize(hp.staged[slot]));  // its last copy has left the slot
-    char* base = static_cast<char*>(hp.pinned[slot]);
-    char* part[5];
-    {
-      size_t o = 0;
-      for (int a = 0; a < 5; ++a) {
-        part[a] = base + o;
-        o += bytes[a] * m;
-      }
-    }
+    char* part[5] = {hp.pinned[slot].get<char>()};
+    for (int a = 1; a < 5; ++a) part[a] = part[a - 1] + bytes[a - 1] * m;
     std::atomic<bool> bad{false};
     const int nw = std::max(1, std::min(n_workers, m / 256));
-    auto in_threads = [&](auto&& fn) {
-      if (nw == 1) {
-        fn(0, m);
-      } else {
-        std::vector<std::thread> pool;
-        for (int t = 0; t < nw; ++t)
-          pool.emplace_back(fn, (int)((long long)m * t / nw), (int)((long long)m * (t + 1) / nw));
-        for (std::thread& th : pool) th.join();
-      }
-    };
     // the sub-chunk's inputs into the pinned slot ...
-    in_threads([&](int lo, int hi) {
-      for (int a = 0; a < 5; ++a)
-        memcpy(part[a] + bytes[a] * lo, src[a] + bytes[a] * ((size_t)off + lo), bytes[a] * (size_t)(hi - lo));
+    in_threads(m, nw, [&](size_t lo, size_t hi) {
+      for (int a = 0; a < 5; ++a) memcpy(part[a] + bytes[a] * lo, src[a] + bytes[a] * (off + lo), bytes[a] * (hi - lo));
     });
     for (int a = 0; a < 5; ++a)
       if (hipMemcpyAsync(dst[a] + bytes[a] * off, part[a], bytes[a] * m, hipMemcpyHostToDevice, hp.copy) !=
@@ -1292,61 +1317,45 @@ int lh_eval_batch(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const i
     LH_HIP(hipEventRecord(hp.staged[slot], hp.copy));
     slot_used[slot] = true;
     LH_HIP(hipStreamWaitEvent(hp.comp, hp.staged[slot], 0));
-    lh_eval_outputs o{d_outs.rates ? d_outs.rates + (size_t)off * R : nullptr,
-                      d_outs.xmsa_emission ? d_outs.xmsa_emission + (size_t)off * C : nullptr,
-                      d_outs.forward ? d_outs.forward + (size_t)off * FS : nullptr,
-                      d_outs.scaler_counts ? d_outs.scaler_counts + (size_t)off * SS : nullptr};
+    lh_eval_outputs sub_outs{d_outs.rates ? d_outs.rates + (size_t)off * R : nullptr,
+                             d_outs.xmsa_emission ? d_outs.xmsa_emission + (size_t)off * C : nullptr,
+                             d_outs.forward ? d_outs.forward + (size_t)off * FS : nullptr,
+                             d_outs.scaler_counts ? d_outs.scaler_counts + (size_t)off * SS : nullptr};
     rc = lh_eval_batch_device(f, m, T, max_depth, (const int32_t*)(dst[0] + bytes[0] * off),
                               (const double*)(dst[1] + bytes[1] * off), (const double*)(dst[2] + bytes[2] * off),
                               (const double*)(dst[3] + bytes[3] * off), (const double*)(dst[4] + bytes[4] * off), R,
-                              (double*)d_ll + off, &o, hp.comp);
+                              d_ll + off, &sub_outs, hp.comp);
     if (rc) break;
-    // ... and its schedules checked on the host while the device works on them (the kernels make the same checks: a
-    // malformed op is a NaN and an error code there, never an out-of-bounds access; a refused batch hands nothing back)
-    in_threads([&](int lo, int hi) {
-      for (int i = lo; i < hi && !bad; ++i)
-        if (!valid_schedule(ops + ((size_t)off + i) * n_ops * 4, T, (int)nodes, max_depth)) bad = true;
+    // ... and its schedules checked on the host while the device works on them
+    in_threads(m, nw, [&](size_t lo, size_t hi) {
+      for (size_t i = lo; i < hi && !bad; ++i)
+        if (!valid_schedule(ops + (off + i) * n_ops * 4, T, (int)nodes, max_depth)) bad = true;
     });
-    if (bad) {
-      (void)hipDeviceSynchronize();
-      (void)check_async_error(f, "lh_eval_batch");  // (the device found it too: one report is enough)
-      rc = fail("lh_eval_batch: malformed schedule op (use lh_schedule_tree)");
-    }
+    if (bad) rc = refuse_schedules(f, "lh_eval_batch");
   }
   if (hipDeviceSynchronize() != hipSuccess && !rc) rc = fail("lh_eval_batch: device synchronisation failed");
-  if (!rc && check_async_error(f, "lh_eval_batch")) rc = 1;  // K0c's verdict on the schedules as the device saw them
   if (rc) return 1;
-  LH_HIP(hipMemcpy(loglik, d_ll, sizeof(double) * n, hipMemcpyDeviceToHost));
-  if (outs) {
-    if (outs->rates) LH_HIP(hipMemcpy(outs->rates, d_outs.rates, sizeof(double) * R * n, hipMemcpyDeviceToHost));
-    if (outs->xmsa_emission)
-      LH_HIP(hipMemcpy(outs->xmsa_emission, d_outs.xmsa_emission, sizeof(double) * C * n, hipMemcpyDeviceToHost));
-    if (outs->forward)
-      LH_HIP(hipMemcpy(outs->forward, d_outs.forward, sizeof(double) * FS * n, hipMemcpyDeviceToHost));
-    if (outs->scaler_counts)
-      LH_HIP(hipMemcpy(outs->scaler_counts, d_outs.scaler_counts, sizeof(int32_t) * SS * n,
-                       hipMemcpyDeviceToHost));
-  }
-  return 0;
+  return copy_back(f, "lh_eval_batch",  // (K0c's verdict on the schedules as the device saw them)
+                   {{loglik, d_ll, sizeof(double) * n},
+                    {o.rates, d_outs.rates, sizeof(double) * R * n},
+                    {o.xmsa_emission, d_outs.xmsa_emission, sizeof(double) * C * n},
+                    {o.forward, d_outs.forward, sizeof(double) * FS * n},
+                    {o.scaler_counts, d_outs.scaler_counts, sizeof(int32_t) * SS * n}});
 }
 
 int lh_eval_sample_batch_device(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops,
                                 const double* brlen, const double* er, const double* pi, const double* alpha, int32_t R,
                                 const uint32_t* words, double* loglik, double* rates, int32_t* states, void* hip_stream) {
-  if (!f) return fail("lh_eval_sample_batch_device: null family");
+  if (int rc = check_batch(f, "lh_eval_sample_batch_device", n, T, R, max_depth, true)) return rc > 0;
   DeviceGuard guard(f);
-  if (!f->have_sampler) return fail("lh_eval_sample_batch_device: lh_family_set_sampler has not been called");
-  if (n <= 0) return n == 0 ? 0 : fail("lh_eval_sample_batch_device: negative batch size");
   if (!words || !states) return fail("lh_eval_sample_batch_device: null array");
   hipStream_t stream = static_cast<hipStream_t>(hip_stream);
   const size_t FS = f->host.forward_size;
-  void* d_fwd;  // the forward arrays never leave the device (grow-only slot; a growing call waits for earlier work)
-  if (sizeof(double) * FS * n > f->st.cap[8]) LH_HIP(hipDeviceSynchronize());
-  if (stage(f, 8, sizeof(double) * FS * n, &d_fwd)) return 1;
-  lh_eval_outputs outs{rates, nullptr, (double*)d_fwd, nullptr};
+  if (f->forward_dev.ensure(sizeof(double) * FS * n)) return 1;
+  double* fwd = f->forward_dev.get<double>();
+  lh_eval_outputs outs{rates, nullptr, fwd, nullptr};
   if (lh_eval_batch_device(f, n, T, max_depth, ops, brlen, er, pi, alpha, R, loglik, &outs, hip_stream)) return 1;
-  const lh::DevSampler& smp = f->sampler;
-  lh::launch_sample(smp, f->sampler_dev, n, (const double*)d_fwd, FS, words, smp.words_per_sample, states, stream);
+  lh::launch_sample(f->sampler, f->sampler_dev, n, fwd, FS, words, f->sampler.words_per_sample, states, stream);
   LH_HIP(hipGetLastError());
   return 0;
 }
@@ -1354,82 +1363,49 @@ int lh_eval_sample_batch_device(lh_family* f, int32_t n, int32_t T, int32_t max_
 int lh_eval_sample_batch(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops,
                          const double* brlen, const double* er, const double* pi, const double* alpha, int32_t R,
                          const uint32_t* words, double* loglik, double* rates, int32_t* states) {
-  if (!f) return fail("lh_eval_sample_batch: null family");
+  if (int rc = check_batch(f, "lh_eval_sample_batch", n, T, R, max_depth, true)) return rc > 0;
   DeviceGuard guard(f);
-  if (!f->have_sampler) return fail("lh_eval_sample_batch: lh_family_set_sampler has not been called");
-  if (n <= 0) return n == 0 ? 0 : fail("lh_eval_sample_batch: negative batch size");
-  if (T < 3) return fail("lh_eval_sample_batch: need at least 3 tips");
   if (!ops || !brlen || !er || !pi || !alpha || !words || !loglik || !states) return fail("lh_eval_sample_batch: null array");
   const size_t nodes = 2 * (size_t)T - 2, n_ops = (size_t)T - 2, FS = f->host.forward_size;
   static const bool timing = lh::debug_options().sample_timing;  // stage times of every call, on stderr
   auto now = [] { return std::chrono::steady_clock::now(); };
   auto t0 = now();
-  auto t1 = now();
   const lh::DevSampler& smp = f->sampler;
-  const size_t bytes[9] = {sizeof(int32_t) * 4 * n_ops * n, sizeof(double) * nodes * n, sizeof(double) * 6 * n,
-                           sizeof(double) * 4 * n, sizeof(double) * n, sizeof(uint32_t) * smp.words_per_sample * (size_t)n,
-                           sizeof(double) * n /* loglik */, sizeof(double) * R * n /* rates */,
-                           sizeof(int32_t) * smp.states_per_sample * (size_t)n};
-  LH_HIP(hipDeviceSynchronize());  // earlier calls may still be using the buffers
-  void* d[9];
-  for (int a = 0; a < 9; ++a) {
-    if (bytes[a] > f->smp.cap[a]) {
-      if (f->smp.ptr[a]) LH_HIP(hipFree(f->smp.ptr[a]));
-      f->smp.ptr[a] = nullptr;
-      f->smp.cap[a] = 0;
-      LH_HIP(hipMalloc(&f->smp.ptr[a], bytes[a]));
-      f->smp.cap[a] = bytes[a];
-    }
-    d[a] = f->smp.ptr[a];
-  }
-  void* d_fwd;  // the forward arrays never leave the device
-  if (stage(f, 8, sizeof(double) * FS * n, &d_fwd)) return 1;
-  // The caller's arrays are ordinary pageable memory: copied from there, every transfer has the driver lock and
-  // unlock their pages, which stalls for milliseconds whenever other threads of the process are busy allocating
-  // (RunPipeline's formatting workers are).  One memcpy into a page-locked slot costs a fraction of that.
-  size_t in_bytes = 0;
-  for (int a = 0; a < 6; ++a) in_bytes += (bytes[a] + 63) & ~(size_t)63;
-  if (in_bytes > f->smp.pinned_cap) {
-    if (f->smp.pinned) LH_HIP(hipHostFree(f->smp.pinned));
-    f->smp.pinned = nullptr;
-    f->smp.pinned_cap = 0;
-    LH_HIP(hipHostMalloc(&f->smp.pinned, in_bytes, hipHostMallocDefault));
-    f->smp.pinned_cap = in_bytes;
-  }
+  HostInputs& in = f->in;
+  HostOutputs& out = f->out;
+  const size_t ll_bytes = sizeof(double) * n, rates_bytes = sizeof(double) * R * n,
+               states_bytes = sizeof(int32_t) * smp.states_per_sample * (size_t)n;
+  if (out.loglik.ensure(ll_bytes) || out.rates.ensure(rates_bytes) || out.states.ensure(states_bytes) ||
+      f->forward_dev.ensure(sizeof(double) * FS * n))
+    return 1;
   auto t2 = now();
-  const void* src[6] = {ops, brlen, er, pi, alpha, words};
-  {
-    char* slot = static_cast<char*>(f->smp.pinned);
-    for (int a = 0; a < 6; ++a) {
-      memcpy(slot, src[a], bytes[a]);
-      LH_HIP(hipMemcpyAsync(d[a], slot, bytes[a], hipMemcpyHostToDevice, nullptr));
-      slot += (bytes[a] + 63) & ~(size_t)63;
-    }
-  }
+  if (stage_inputs(f, {{ops, sizeof(int32_t) * 4 * n_ops * n, &in.ops},
+                       {brlen, sizeof(double) * nodes * n, &in.brlen},
+                       {er, sizeof(double) * 6 * n, &in.er},
+                       {pi, sizeof(double) * 4 * n, &in.pi},
+                       {alpha, sizeof(double) * n, &in.alpha},
+                       {words, sizeof(uint32_t) * smp.words_per_sample * (size_t)n, &in.words}}))
+    return 1;
   auto t3 = now();
-  lh_eval_outputs outs{(double*)d[7], nullptr, (double*)d_fwd, nullptr};
-  if (lh_eval_batch_device(f, n, T, max_depth, (const int32_t*)d[0], (const double*)d[1], (const double*)d[2],
-                           (const double*)d[3], (const double*)d[4], R, (double*)d[6], &outs, nullptr))
+  double* fwd = f->forward_dev.get<double>();
+  lh_eval_outputs outs{out.rates.get<double>(), nullptr, fwd, nullptr};
+  if (lh_eval_batch_device(f, n, T, max_depth, in.ops.get<const int32_t>(), in.brlen.get<const double>(),
+                           in.er.get<const double>(), in.pi.get<const double>(), in.alpha.get<const double>(), R,
+                           out.loglik.get<double>(), &outs, nullptr))
     return 1;
   if (timing) LH_HIP(hipDeviceSynchronize());
   auto t4 = now();
-  lh::launch_sample(smp, f->sampler_dev, n, (const double*)d_fwd, FS, (const uint32_t*)d[5], smp.words_per_sample, (int32_t*)d[8], nullptr);
+  lh::launch_sample(smp, f->sampler_dev, n, fwd, FS, in.words.get<const uint32_t>(), smp.words_per_sample,
+                    out.states.get<int32_t>(), nullptr);
   LH_HIP(hipGetLastError());
   if (timing) LH_HIP(hipDeviceSynchronize());
   auto t5 = now();
-  // The schedules are checked on the host WHILE the device works on them: the kernels make the same checks themselves (a
-  // malformed op costs that sample a NaN and the handle an error code, never an out-of-bounds access), so nothing is
-  // risked by the order, and a refused batch hands nothing back.
-  if (!valid_schedules(ops, (size_t)n, T, (int)nodes, max_depth)) {
-    (void)hipDeviceSynchronize();
-    (void)check_async_error(f, "lh_eval_sample_batch");  // (the device found it too: one report is enough)
-    return fail("lh_eval_sample_batch: malformed schedule op (use lh_schedule_tree)");
-  }
+  if (!valid_schedules(ops, (size_t)n, T, (int)nodes, max_depth)) return refuse_schedules(f, "lh_eval_sample_batch");
   auto t6 = now();
-  LH_HIP(hipMemcpy(loglik, d[6], bytes[6], hipMemcpyDeviceToHost));
-  if (rates) LH_HIP(hipMemcpy(rates, d[7], bytes[7], hipMemcpyDeviceToHost));
-  LH_HIP(hipMemcpy(states, d[8], bytes[8], hipMemcpyDeviceToHost));
-  if (check_async_error(f, "lh_eval_sample_batch")) return 1;
+  if (copy_back(f, "lh_eval_sample_batch",
+                {{loglik, out.loglik.get(), ll_bytes}, {rates, out.rates.get(), rates_bytes},
+                 {states, out.states.get(), states_bytes}}))
+    return 1;
   if (timing) {
     auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
       return std::chrono::duration<double, std::milli>(b - a).count();
@@ -1446,16 +1422,8 @@ int lh_asr_batch_device(lh_family* f, int32_t n, int32_t T, int32_t max_depth, c
                         const double* brlen, const double* er, const double* pi, const double* rates, int32_t R,
                         const uint8_t* naive, uint64_t seed, uint64_t first_sample, uint8_t* anc,
                         uint8_t* rate_choice, void* hip_stream) {
-  if (!f) return fail("lh_asr_batch: null family");
+  if (int rc = check_batch(f, "lh_asr_batch", n, T, R, max_depth)) return rc > 0;
   DeviceGuard guard(f);
-  if (n < 0) return fail("lh_asr_batch: negative batch size");
-  if (n == 0) return 0;
-  if (f->host.n_seqs < 1) return fail("lh_asr_batch: family was created without an MSA");
-  if (T != f->host.n_seqs + 1) return fail("lh_asr_batch: n_tips must equal n_seqs + 1 (naive)");
-  if (T < 3) return fail("lh_asr_batch: need at least 3 tips");
-  if (R < 1 || R > 64) return fail("lh_asr_batch: num_rates out of range");
-  if (max_depth < 0 || max_depth > 16) return fail("lh_asr_batch: max_depth out of range");
-  if ((size_t)T * 128 > 160 * 1024) return fail("lh_asr_batch: too many tips for the LDS tip table");
   if (lh::asr_lds_bytes(T, f->host.n_sites, R, f->host.n_prune) > 160 * 1024)
     return fail("lh_asr_batch: tree / alignment too large for the sampling kernel's LDS tables");
   if (!ops || !brlen || !er || !pi || !rates || !naive || !anc) return fail("lh_asr_batch: null array");
@@ -1468,115 +1436,71 @@ int lh_asr_batch_device(lh_family* f, int32_t n, int32_t T, int32_t max_depth, c
   const int chunk = std::min<int>(n, std::min(8192, by_memory));
   if (ensure_workspace(f, chunk, R, T)) return 1;
   AsrWs& aw = f->asr;
-  if (aw.clv_cap < clv_per_sample * chunk) {
-    LH_HIP(hipDeviceSynchronize());
-    if (aw.clv) LH_HIP(hipFree(aw.clv));
-    aw.clv = nullptr;
-    aw.clv_cap = 0;
-    LH_HIP(hipMalloc((void**)&aw.clv, clv_per_sample * chunk));
-    aw.clv_cap = clv_per_sample * chunk;
-  }
-  if (aw.desc_cap < lh::asr_desc_bytes(T) * chunk) {
-    LH_HIP(hipDeviceSynchronize());
-    if (aw.desc) LH_HIP(hipFree(aw.desc));
-    aw.desc = nullptr;
-    aw.desc_cap = 0;
-    LH_HIP(hipMalloc(&aw.desc, lh::asr_desc_bytes(T) * chunk));
-    aw.desc_cap = lh::asr_desc_bytes(T) * chunk;
-  }
-  if (!rate_choice && aw.choice_cap < L * (size_t)chunk) {
-    LH_HIP(hipDeviceSynchronize());
-    if (aw.choice) LH_HIP(hipFree(aw.choice));
-    aw.choice = nullptr;
-    aw.choice_cap = 0;
-    LH_HIP(hipMalloc((void**)&aw.choice, L * (size_t)chunk));
-    aw.choice_cap = L * (size_t)chunk;
-  }
+  if (aw.clv.ensure(clv_per_sample * chunk) || aw.desc.ensure(lh::asr_desc_bytes(T) * chunk) ||
+      (!rate_choice && aw.choice.ensure(L * (size_t)chunk)))
+    return 1;
   Workspace& w = f->ws;
+  double *eig = w.eig.get<double>(), *site_lik = w.site_lik.get<double>();
+  int32_t* site_scal = w.site_scal.get<int32_t>();
   for (int off = 0; off < n; off += chunk) {
     const int m = std::min(chunk, n - off);
     const double* r_m = rates + (size_t)off * R;
     const double* pi_m = pi + (size_t)off * 4;
     const int32_t* ops_m = ops + (size_t)off * n_ops * 4;
     const double* bl_m = brlen + (size_t)off * nodes;
-    lh::launch_gtr_setup(m, er + (size_t)off * 6, pi_m, w.eig, stream);
+    lh::launch_gtr_setup(m, er + (size_t)off * 6, pi_m, eig, stream);
     // per-rate planes: K1 must not mix the categories here
-    const int planes = lh::launch_prune(f->host, m, R, T, max_depth, ops_m, bl_m, r_m, w.eig, w.prune, pi_m,
-                                        w.site_lik, w.site_scal, stream, false);
+    const int planes = lh::launch_prune(f->host, m, R, T, max_depth, ops_m, bl_m, r_m, eig, w.prune, pi_m, site_lik,
+                                        site_scal, stream, false);
     if (planes < 0) return fail(std::string("lh_asr_batch: ") + lh::prune_last_error());
     f->k1_form = lh::prune_last_form();
     if (planes != R && f->host.n_prune > 0) return fail("lh_asr_batch: internal error (rate planes were mixed)");
-    std::pair<hipEvent_t, hipEvent_t> ev;
-    if (f->profile) {
-      LH_HIP(hipEventCreate(&ev.first));
-      LH_HIP(hipEventCreate(&ev.second));
-      LH_HIP(hipEventRecord(ev.first, stream));
-    }
-    if (lh::launch_asr(f->host, m, R, T, ops_m, bl_m, r_m, w.eig, pi_m, w.site_lik, w.site_scal,
-                       naive + (size_t)off * L, seed, first_sample + (uint64_t)off, aw.clv, aw.desc,
-                       anc + (size_t)off * n_ops * L,
-                       rate_choice ? rate_choice + (size_t)off * L : aw.choice, w.prune.hdr, stream))
+    if (f->profile && f->asr_timer.begin(stream)) return 1;
+    if (lh::launch_asr(f->host, m, R, T, ops_m, bl_m, r_m, eig, pi_m, site_lik, site_scal, naive + (size_t)off * L, seed,
+                       first_sample + (uint64_t)off, aw.clv.get<double>(), aw.desc.get(), anc + (size_t)off * n_ops * L,
+                       rate_choice ? rate_choice + (size_t)off * L : aw.choice.get<uint8_t>(), w.prune.hdr, stream))
       return fail("lh_asr_batch: launch failed");
-    if (f->profile) {
-      LH_HIP(hipEventRecord(ev.second, stream));
-      aw.events.push_back(ev);
-    }
+    if (f->profile && f->asr_timer.end(stream)) return 1;
     LH_HIP(hipGetLastError());
   }
-  return 0;
-}
-
-static int asr_stage(lh_family* f, int slot, size_t bytes, void** out) {
-  AsrWs& a = f->asr;
-  if (bytes > a.cap[slot]) {
-    if (a.ptr[slot]) LH_HIP(hipFree(a.ptr[slot]));
-    a.ptr[slot] = nullptr;
-    a.cap[slot] = 0;
-    LH_HIP(hipMalloc(&a.ptr[slot], bytes));
-    a.cap[slot] = bytes;
-  }
-  *out = a.ptr[slot];
   return 0;
 }
 
 int lh_asr_batch(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops, const double* brlen,
                  const double* er, const double* pi, const double* rates, int32_t R, const uint8_t* naive,
                  uint64_t seed, uint64_t first_sample, uint8_t* anc, uint8_t* rate_choice) {
-  if (!f) return fail("lh_asr_batch: null family");
+  if (int rc = check_batch(f, "lh_asr_batch", n, T, R, max_depth)) return rc > 0;
   DeviceGuard guard(f);
-  if (n < 0) return fail("lh_asr_batch: negative batch size");
-  if (n == 0) return 0;
-  if (T < 3 || T != f->host.n_seqs + 1) return fail("lh_asr_batch: n_tips must equal n_seqs + 1 (naive)");
-  if (R < 1 || R > 64) return fail("lh_asr_batch: num_rates out of range");
-  if (max_depth < 0 || max_depth > 16) return fail("lh_asr_batch: max_depth out of range");
   if (!ops || !brlen || !er || !pi || !rates || !naive || !anc) return fail("lh_asr_batch: null array");
   const size_t nodes = 2 * (size_t)T - 2, n_ops = (size_t)T - 2, L = f->host.n_sites;
   if (!valid_schedules(ops, (size_t)n, T, (int)nodes, max_depth))
     return fail("lh_asr_batch: malformed schedule op (use lh_schedule_tree)");
   for (size_t k = 0; k < (size_t)n * L; ++k)
     if (naive[k] > 4) return fail("lh_asr_batch: naive base out of range");
-  LH_HIP(hipDeviceSynchronize());
+  HostInputs& in = f->in;
+  HostOutputs& out = f->out;
   // sub-batches bound the device copy of the output (anc: (T-2) * L bytes per sample)
   const int sub = (int)std::max<size_t>(1, std::min<size_t>(n, ((size_t)1 << 30) / std::max<size_t>(n_ops * L, 1)));
   for (int off = 0; off < n; off += sub) {
     const int m = std::min(sub, n - off);
-    const size_t bytes[7] = {sizeof(int32_t) * 4 * n_ops * m, sizeof(double) * nodes * m, sizeof(double) * 6 * m,
-                             sizeof(double) * 4 * m,          sizeof(double) * R * m,     L * m,
-                             n_ops * L * m};
-    const void* src[6] = {ops + (size_t)off * n_ops * 4, brlen + (size_t)off * nodes, er + (size_t)off * 6,
-                          pi + (size_t)off * 4,          rates + (size_t)off * R,     naive + (size_t)off * L};
-    void* d[8];
-    for (int a = 0; a < 7; ++a)
-      if (asr_stage(f, a, bytes[a], &d[a])) return 1;
-    if (asr_stage(f, 7, L * m, &d[7])) return 1;
-    for (int a = 0; a < 6; ++a) LH_HIP(hipMemcpy(d[a], src[a], bytes[a], hipMemcpyHostToDevice));
-    if (lh_asr_batch_device(f, m, T, max_depth, (const int32_t*)d[0], (const double*)d[1], (const double*)d[2],
-                            (const double*)d[3], (const double*)d[4], R, (const uint8_t*)d[5], seed,
-                            first_sample + (uint64_t)off, (uint8_t*)d[6], (uint8_t*)d[7], nullptr))
+    const size_t anc_bytes = n_ops * L * m, choice_bytes = L * m;
+    if (out.anc.ensure(anc_bytes) || out.rate_choice.ensure(choice_bytes) ||
+        stage_inputs(f, {{ops + (size_t)off * n_ops * 4, sizeof(int32_t) * 4 * n_ops * m, &in.ops},
+                         {brlen + (size_t)off * nodes, sizeof(double) * nodes * m, &in.brlen},
+                         {er + (size_t)off * 6, sizeof(double) * 6 * m, &in.er},
+                         {pi + (size_t)off * 4, sizeof(double) * 4 * m, &in.pi},
+                         {rates + (size_t)off * R, sizeof(double) * R * m, &in.rates},
+                         {naive + (size_t)off * L, L * m, &in.naive}}))
       return 1;
-    if (check_async_error(f, "lh_asr_batch")) return 1;
-    LH_HIP(hipMemcpy(anc + (size_t)off * n_ops * L, d[6], bytes[6], hipMemcpyDeviceToHost));
-    if (rate_choice) LH_HIP(hipMemcpy(rate_choice + (size_t)off * L, d[7], L * m, hipMemcpyDeviceToHost));
+    if (lh_asr_batch_device(f, m, T, max_depth, in.ops.get<const int32_t>(), in.brlen.get<const double>(),
+                            in.er.get<const double>(), in.pi.get<const double>(), in.rates.get<const double>(), R,
+                            in.naive.get<const uint8_t>(), seed, first_sample + (uint64_t)off, out.anc.get<uint8_t>(),
+                            out.rate_choice.get<uint8_t>(), nullptr))
+      return 1;
+    if (copy_back(f, "lh_asr_batch",
+                  {{anc + (size_t)off * n_ops * L, out.anc.get(), anc_bytes},
+                   {rate_choice ? rate_choice + (size_t)off * L : nullptr, out.rate_choice.get(), choice_bytes}}))
+      return 1;
   }
   return 0;
 }
@@ -1587,81 +1511,52 @@ int lh_forward_batch(lh_family* f, int32_t n, const double* em, double* loglik, 
   if (n <= 0) return n == 0 ? 0 : fail("lh_forward_batch: negative batch size");
   if (!em || !loglik) return fail("lh_forward_batch: null array");
   const size_t C = f->host.n_xmsa, FS = f->host.forward_size, SS = f->host.scaler_size;
-  void *d_em, *d_ll;
-  if (stage(f, 7, sizeof(double) * C * n, &d_em)) return 1;
-  if (stage(f, 5, sizeof(double) * n, &d_ll)) return 1;
-  LH_HIP(hipMemcpy(d_em, em, sizeof(double) * C * n, hipMemcpyHostToDevice));
+  const lh_eval_outputs none{nullptr, nullptr, nullptr, nullptr};
+  const lh_eval_outputs& o = outs ? *outs : none;
+  HostOutputs& out = f->out;
   lh_eval_outputs d_outs{nullptr, nullptr, nullptr, nullptr};
-  if (outs) {
-    if (outs->forward && stage(f, 8, sizeof(double) * FS * n, (void**)&d_outs.forward)) return 1;
-    if (outs->scaler_counts && stage(f, 9, sizeof(int32_t) * SS * n, (void**)&d_outs.scaler_counts)) return 1;
-  }
-  if (run_forward(f, n, 1, nullptr, nullptr, nullptr, (const double*)d_em, nullptr, (double*)d_ll, &d_outs, 0, nullptr))
+  if (out.loglik.ensure(sizeof(double) * n) || out_buf(o.forward, out.forward, sizeof(double) * FS * n, &d_outs.forward) ||
+      out_buf(o.scaler_counts, out.scaler_counts, sizeof(int32_t) * SS * n, &d_outs.scaler_counts) ||
+      stage_inputs(f, {{em, sizeof(double) * C * n, &f->in.em}}))
     return 1;
-  LH_HIP(hipDeviceSynchronize());
-  LH_HIP(hipMemcpy(loglik, d_ll, sizeof(double) * n, hipMemcpyDeviceToHost));
-  if (outs) {
-    if (outs->forward)
-      LH_HIP(hipMemcpy(outs->forward, d_outs.forward, sizeof(double) * FS * n, hipMemcpyDeviceToHost));
-    if (outs->scaler_counts)
-      LH_HIP(hipMemcpy(outs->scaler_counts, d_outs.scaler_counts, sizeof(int32_t) * SS * n,
-                       hipMemcpyDeviceToHost));
-  }
-  return 0;
-}
-
-// K5's grow-only device buffers (a growing call first waits for earlier work that may still use the old one)
-static int post_buf(lh_family* f, int slot, size_t bytes, void** out) {
-  PosteriorWs& pw = f->post;
-  if (bytes > pw.cap[slot]) {
-    LH_HIP(hipDeviceSynchronize());
-    if (pw.ptr[slot]) LH_HIP(hipFree(pw.ptr[slot]));
-    pw.ptr[slot] = nullptr;
-    pw.cap[slot] = 0;
-    LH_HIP(hipMalloc(&pw.ptr[slot], std::max<size_t>(bytes, 64)));
-    pw.cap[slot] = std::max<size_t>(bytes, 64);
-  }
-  *out = pw.ptr[slot];
-  return 0;
+  if (run_forward(f, n, 1, nullptr, nullptr, nullptr, f->in.em.get<const double>(), nullptr, out.loglik.get<double>(),
+                  &d_outs, 0, nullptr))
+    return 1;
+  return copy_back(f, nullptr,
+                   {{loglik, out.loglik.get(), sizeof(double) * n},
+                    {o.forward, d_outs.forward, sizeof(double) * FS * n},
+                    {o.scaler_counts, d_outs.scaler_counts, sizeof(int32_t) * SS * n}});
 }
 
 int lh_eval_posterior_batch_device(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops,
                                    const double* brlen, const double* er, const double* pi, const double* alpha, int32_t R,
                                    const lh_posterior_outputs* outs, void* hip_stream) {
-  if (!f) return fail("lh_eval_posterior_batch_device: null family");
+  if (int rc = check_batch(f, "lh_eval_posterior_batch_device", n, T, R, max_depth, true)) return rc > 0;
   DeviceGuard guard(f);
-  if (!f->have_sampler) return fail("lh_eval_posterior_batch_device: lh_family_set_sampler has not been called");
-  if (n <= 0) return n == 0 ? 0 : fail("lh_eval_posterior_batch_device: negative batch size");
   hipStream_t stream = static_cast<hipStream_t>(hip_stream);
   const lh_posterior_outputs none{nullptr, nullptr, nullptr, nullptr, nullptr};
   const lh_posterior_outputs& o = outs ? *outs : none;
   const size_t FS = f->host.forward_size;
+  PosteriorWs& pw = f->post;
+  // what the caller does not hand in comes from the handle's buffers
+  auto own = [](double*& p, DevBuf& b, size_t bytes) {
+    if (!p && b.ensure(bytes)) return 1;
+    if (!p) p = b.get<double>();
+    return 0;
+  };
   // the forward arrays go where the posteriors are wanted: K5 overwrites them in place
-  double* post = o.posterior;
-  double* ll = o.loglik;
-  if (!post && post_buf(f, 0, sizeof(double) * FS * n, (void**)&post)) return 1;
-  if (!ll && post_buf(f, 1, sizeof(double) * n, (void**)&ll)) return 1;
-  double *w = nullptr, *stats = o.weight_stats, *partial = nullptr;
+  double *post = o.posterior, *ll = o.loglik, *w = nullptr, *stats = o.weight_stats, *partial = nullptr;
   const bool reduce = o.weighted_sum || o.weight_stats;
-  if (reduce) {
-    if (post_buf(f, 2, sizeof(double) * n, (void**)&w)) return 1;
-    if (!stats && post_buf(f, 3, sizeof(double) * 3, (void**)&stats)) return 1;
-    if (o.weighted_sum && post_buf(f, 4, sizeof(double) * FS * lh::posterior_slabs(n), (void**)&partial)) return 1;
-  }
+  if (own(post, f->forward_dev, sizeof(double) * FS * n) || own(ll, pw.loglik, sizeof(double) * n) ||
+      (reduce && (own(w, pw.weights, sizeof(double) * n) || own(stats, pw.stats, sizeof(double) * 3) ||
+                  (o.weighted_sum && own(partial, pw.partial, sizeof(double) * FS * lh::posterior_slabs(n))))))
+    return 1;
   lh_eval_outputs eo{nullptr, nullptr, post, nullptr};
   if (lh_eval_batch_device(f, n, T, max_depth, ops, brlen, er, pi, alpha, R, ll, &eo, hip_stream)) return 1;
-  std::pair<hipEvent_t, hipEvent_t> ev{nullptr, nullptr};
-  if (f->profile) {
-    LH_HIP(hipEventCreate(&ev.first));
-    LH_HIP(hipEventCreate(&ev.second));
-    LH_HIP(hipEventRecord(ev.first, stream));
-  }
+  if (f->profile && f->post_timer.begin(stream)) return 1;
   lh::launch_posterior(f->sampler_dev, n, post, FS, ll, stream);
   if (reduce) lh::launch_posterior_reduce(n, FS, post, ll, o.log_offset, w, partial, o.weighted_sum, stats, stream);
-  if (f->profile) {
-    LH_HIP(hipEventRecord(ev.second, stream));
-    f->post.events.push_back(ev);
-  }
+  if (f->profile && f->post_timer.end(stream)) return 1;
   LH_HIP(hipGetLastError());
   return 0;
 }
@@ -1669,69 +1564,45 @@ int lh_eval_posterior_batch_device(lh_family* f, int32_t n, int32_t T, int32_t m
 int lh_eval_posterior_batch(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops,
                             const double* brlen, const double* er, const double* pi, const double* alpha, int32_t R,
                             const lh_posterior_outputs* outs) {
-  if (!f) return fail("lh_eval_posterior_batch: null family");
+  if (int rc = check_batch(f, "lh_eval_posterior_batch", n, T, R, max_depth, true)) return rc > 0;
   DeviceGuard guard(f);
-  if (!f->have_sampler) return fail("lh_eval_posterior_batch: lh_family_set_sampler has not been called");
-  if (n <= 0) return n == 0 ? 0 : fail("lh_eval_posterior_batch: negative batch size");
-  if (T < 3) return fail("lh_eval_posterior_batch: need at least 3 tips");
   if (!ops || !brlen || !er || !pi || !alpha) return fail("lh_eval_posterior_batch: null array");
   const lh_posterior_outputs none{nullptr, nullptr, nullptr, nullptr, nullptr};
   const lh_posterior_outputs& o = outs ? *outs : none;
-  const size_t nodes = 2 * (size_t)T - 2, n_ops = (size_t)T - 2, FS = f->host.forward_size;
-  // slots 5..10: the inputs; 0, 1, 11, 3: posterior, loglik, weighted sum, weight statistics
-  const size_t in_bytes[6] = {sizeof(int32_t) * 4 * n_ops * n, sizeof(double) * nodes * n, sizeof(double) * 6 * n,
-                              sizeof(double) * 4 * n, sizeof(double) * n, sizeof(double) * n};
-  const void* src[6] = {ops, brlen, er, pi, alpha, o.log_offset};
-  void* d[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  for (int a = 0; a < 6; ++a) {
-    if (!src[a]) continue;
-    if (post_buf(f, 5 + a, in_bytes[a], &d[a])) return 1;
-  }
-  lh_posterior_outputs dev{(const double*)d[5], nullptr, nullptr, nullptr, nullptr};
-  if (post_buf(f, 0, sizeof(double) * FS * n, (void**)&dev.posterior)) return 1;
-  if (post_buf(f, 1, sizeof(double) * n, (void**)&dev.loglik)) return 1;
-  if (o.weighted_sum && post_buf(f, 11, sizeof(double) * FS, (void**)&dev.weighted_sum)) return 1;
-  if (o.weight_stats && post_buf(f, 3, sizeof(double) * 3, (void**)&dev.weight_stats)) return 1;
   if (!o.posterior && !o.weighted_sum && !o.weight_stats && !o.loglik) return 0;  // nothing asked for
-  LH_HIP(hipDeviceSynchronize());  // earlier calls may still be using the buffers
-  for (int a = 0; a < 6; ++a)
-    if (src[a]) LH_HIP(hipMemcpyAsync(d[a], src[a], in_bytes[a], hipMemcpyHostToDevice, nullptr));
-  if (lh_eval_posterior_batch_device(f, n, T, max_depth, (const int32_t*)d[0], (const double*)d[1], (const double*)d[2],
-                                     (const double*)d[3], (const double*)d[4], R, &dev, nullptr))
+  const size_t nodes = 2 * (size_t)T - 2, n_ops = (size_t)T - 2, FS = f->host.forward_size;
+  HostInputs& in = f->in;
+  HostOutputs& out = f->out;
+  lh_posterior_outputs dev{nullptr, nullptr, nullptr, nullptr, nullptr};
+  if (f->forward_dev.ensure(sizeof(double) * FS * n) || out.loglik.ensure(sizeof(double) * n) ||
+      out_buf(o.weighted_sum, out.weighted_sum, sizeof(double) * FS, &dev.weighted_sum) ||
+      out_buf(o.weight_stats, out.weight_stats, sizeof(double) * 3, &dev.weight_stats) ||
+      stage_inputs(f, {{ops, sizeof(int32_t) * 4 * n_ops * n, &in.ops},
+                       {brlen, sizeof(double) * nodes * n, &in.brlen},
+                       {er, sizeof(double) * 6 * n, &in.er},
+                       {pi, sizeof(double) * 4 * n, &in.pi},
+                       {alpha, sizeof(double) * n, &in.alpha},
+                       {o.log_offset, sizeof(double) * n, &in.log_offset}}))
     return 1;
-  // the schedules are checked on the host while the device works on them, as in lh_eval_sample_batch
-  if (!valid_schedules(ops, (size_t)n, T, (int)nodes, max_depth)) {
-    (void)hipDeviceSynchronize();
-    (void)check_async_error(f, "lh_eval_posterior_batch");
-    return fail("lh_eval_posterior_batch: malformed schedule op (use lh_schedule_tree)");
-  }
-  if (check_async_error(f, "lh_eval_posterior_batch")) return 1;
-  if (o.loglik) LH_HIP(hipMemcpy(o.loglik, dev.loglik, sizeof(double) * n, hipMemcpyDeviceToHost));
-  if (o.posterior) LH_HIP(hipMemcpy(o.posterior, dev.posterior, sizeof(double) * FS * n, hipMemcpyDeviceToHost));
-  if (o.weighted_sum) LH_HIP(hipMemcpy(o.weighted_sum, dev.weighted_sum, sizeof(double) * FS, hipMemcpyDeviceToHost));
-  if (o.weight_stats) LH_HIP(hipMemcpy(o.weight_stats, dev.weight_stats, sizeof(double) * 3, hipMemcpyDeviceToHost));
-  return 0;
+  dev.log_offset = o.log_offset ? in.log_offset.get<const double>() : nullptr;
+  dev.loglik = out.loglik.get<double>();
+  dev.posterior = f->forward_dev.get<double>();
+  if (lh_eval_posterior_batch_device(f, n, T, max_depth, in.ops.get<const int32_t>(), in.brlen.get<const double>(),
+                                     in.er.get<const double>(), in.pi.get<const double>(), in.alpha.get<const double>(), R,
+                                     &dev, nullptr))
+    return 1;
+  if (!valid_schedules(ops, (size_t)n, T, (int)nodes, max_depth)) return refuse_schedules(f, "lh_eval_posterior_batch");
+  return copy_back(f, "lh_eval_posterior_batch",
+                   {{o.loglik, dev.loglik, sizeof(double) * n},
+                    {o.posterior, dev.posterior, sizeof(double) * FS * n},
+                    {o.weighted_sum, dev.weighted_sum, sizeof(double) * FS},
+                    {o.weight_stats, dev.weight_stats, sizeof(double) * 3}});
 }
 
 int lh_posterior_profile_read(lh_family* f, double* ms_posterior, int64_t* n_launches) {
   if (!f) return fail("null family");
   DeviceGuard guard(f);
-  PosteriorWs& pw = f->post;
-  for (auto& ev : pw.events) {
-    LH_HIP(hipEventSynchronize(ev.second));
-    float ms = 0;
-    LH_HIP(hipEventElapsedTime(&ms, ev.first, ev.second));
-    pw.ms += ms;
-    ++pw.launches;
-    (void)hipEventDestroy(ev.first);
-    (void)hipEventDestroy(ev.second);
-  }
-  pw.events.clear();
-  if (ms_posterior) *ms_posterior = pw.ms;
-  if (n_launches) *n_launches = pw.launches;
-  pw.ms = 0;
-  pw.launches = 0;
-  return 0;
+  return f->post_timer.read(ms_posterior, n_launches);
 }
 
 }  // extern "C"

@@ -9,7 +9,11 @@ label=$1
 flags=${2:-}
 out=$root/linearham_amd/lib_exp/$label
 mkdir -p "$out"
+# the product library's source list (linearham_amd/build.py HIP_SOURCES)
+mapfile -t srcs < <(cd "$root" && python3 -c "from linearham_amd.build import CSRC, HIP_SOURCES
+import os
+print('\n'.join(os.path.join(CSRC, s) for s in HIP_SOURCES))")
 hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -Wno-unused-result $flags -I "$root/include" -I "$root/linearham_amd/csrc" \
-  "$root"/linearham_amd/csrc/lh_{model,prune,forward,asr,sample,capi}.hip -o "$out/liblinearham_hip.so"
+  "${srcs[@]}" -o "$out/liblinearham_hip.so"
 cp "$root/linearham_amd/lib/liblinearham_host.so" "$out/"
 echo "built $out ($flags)"
