@@ -257,6 +257,56 @@ int lh_eval_posterior_batch_device(lh_family* fam, int32_t n, int32_t n_tips, in
  * enabled (HIP events on the launch stream); resets the counters. */
 int lh_posterior_profile_read(lh_family* fam, double* ms_posterior, int64_t* n_launches);
 
+/* ---- exact posterior probabilities of candidate naive sequences (K6) ----
+ * Every state writes a fixed naive base on a fixed site and its emission depends on that pair only, so for a naive
+ * sequence s and a tree sample t:  log P(s | data, t) = log P_HMM(s) + sum_i log E_t[s_i, i] - loglik_t, with
+ * P_HMM(s) the probability of the state paths whose naive sequence is s (HMM::SampleNaiveSequence's naive_bases_,
+ * src/HMM.cpp:358-431; padding writes N).  This is the exact form of the probabilities scripts/tabulate_naive_probs.py
+ * counts from sampled naive sequences.
+ *
+ * Registers K candidates seqs[K][n_sites] (A,C,G,T,N = 0..4; 1 <= K <= 65536) on the handle, replacing any earlier
+ * set, and computes log P_HMM(s_k) on the device: the forward sweep over the family's tables with indicator emissions
+ * (K6a).  log_prior [K] (may be NULL) receives them; a candidate no state path produces gets -inf, which is a result,
+ * not an error.  Fails for a byte above 4 or a family without an MSA. */
+int lh_family_set_candidates(lh_family* fam, int32_t K, const uint8_t* seqs, double* log_prior);
+
+/* Every member may be NULL.  log_offset is an input, as for K5: lw_i = loglik_i - log_offset_i.
+ *   loglik       [n]     as lh_eval_batch
+ *   log_cand     [n][K]  log P(s_k | data, t_i); NaN for a row whose loglik is not finite (an overflowed row in the
+ *                        active mode, or a rejected schedule)
+ *   weighted_sum [K]     sum_i w_i P(s_k | data, t_i) in a fixed order, rows with w_i = 0 or a non-finite lw_i left out;
+ *                        divided by weight_stats[1] it is the posterior probability of s_k
+ *   weight_stats [3]     max lw, sum w_i, sum w_i^2 (the same as lh_eval_posterior_batch's for the same rows)
+ * Batches combine exactly: rescale each one's sums by exp(max_b - max). */
+typedef struct {
+  const double* log_offset;
+  double* loglik;
+  double* log_cand;
+  double* weighted_sum;
+  double* weight_stats;
+} lh_candidate_outputs;
+
+/* lh_eval_batch followed by K6b for the handle's candidates (lh_family_set_candidates first).  Host pointers; a
+ * malformed schedule fails the call as in lh_eval_batch. */
+int lh_eval_candidates_batch(lh_family* fam, int32_t n, int32_t n_tips, int32_t max_depth, const int32_t* ops,
+                             const double* brlen, const double* er, const double* pi, const double* alpha,
+                             int32_t num_rates, const lh_candidate_outputs* outs);
+
+/* The same with every array (outs' members included) resident on the handle's device; enqueued on `hip_stream`
+ * without synchronising.  A schedule K0c rejects gives that row NaN, leaves it out of the sums and raises the
+ * handle's error word (lh_family_status). */
+int lh_eval_candidates_batch_device(lh_family* fam, int32_t n, int32_t n_tips, int32_t max_depth, const int32_t* ops,
+                                    const double* brlen, const double* er, const double* pi, const double* alpha,
+                                    int32_t num_rates, const lh_candidate_outputs* outs, void* hip_stream);
+
+/* The number of candidates registered on the handle (0: none, or the last lh_family_set_candidates failed) and the
+ * number of sites every candidate has (the alignment's).  Either pointer may be NULL. */
+int lh_candidates_info(const lh_family* fam, int32_t* n_candidates, int32_t* n_sites);
+
+/* Times while profiling was enabled (HIP events): ms[0] = K6a over the lh_family_set_candidates calls, ms[1] = K6b
+ * (weights, scoring, reduction) over the evaluation calls, whose number goes to n_launches; resets the counters. */
+int lh_candidates_profile_read(lh_family* fam, double* ms, int64_t* n_launches);
+
 /* Tree in rooted-at-naive form: tips are nodes 0..T-1 (0 = `naive`, i = MSA row i-1), inner nodes
  * T..2T-3.  children[2*(v-T)+{0,1}] are the two children of inner node v when the tree is rooted at
  * `root`, the inner node adjacent to `naive`.  Writes the kernel's post-order schedule:

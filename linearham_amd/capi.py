@@ -49,10 +49,19 @@ EXPORTS = ["lh_last_error", "lh_device_count", "lh_family_create", "lh_family_de
 # K5 (exact posterior state marginals)
 POSTERIOR_EXPORTS = ["lh_eval_posterior_batch", "lh_eval_posterior_batch_device", "lh_posterior_profile_read"]
 EXPORTS += POSTERIOR_EXPORTS
+# K6 (exact posterior probabilities of candidate naive sequences)
+CANDIDATE_EXPORTS = ["lh_family_set_candidates", "lh_eval_candidates_batch", "lh_eval_candidates_batch_device",
+                     "lh_candidates_profile_read", "lh_candidates_info"]
+EXPORTS += CANDIDATE_EXPORTS
 
 
 class _PosteriorOutputs(C.Structure):
     _fields_ = [("log_offset", c_f64p), ("loglik", c_f64p), ("posterior", c_f64p), ("weighted_sum", c_f64p),
+                ("weight_stats", c_f64p)]
+
+
+class _CandidateOutputs(C.Structure):
+    _fields_ = [("log_offset", c_f64p), ("loglik", c_f64p), ("log_cand", c_f64p), ("weighted_sum", c_f64p),
                 ("weight_stats", c_f64p)]
 
 
@@ -112,6 +121,14 @@ class HipLibrary:
                 [C.c_void_p] * 5 + [C.c_int32, C.POINTER(_PosteriorOutputs), C.c_void_p]
             lib.lh_posterior_profile_read.argtypes = [C.c_void_p, c_f64p, C.POINTER(C.c_int64)]
             lib.lh_forward_size.argtypes = [C.c_void_p]
+        if hasattr(lib, "lh_family_set_candidates"):
+            lib.lh_family_set_candidates.argtypes = [C.c_void_p, C.c_int32, c_u8p, c_f64p]
+            lib.lh_eval_candidates_batch.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, c_i32p, c_f64p, c_f64p,
+                                                     c_f64p, c_f64p, C.c_int32, C.POINTER(_CandidateOutputs)]
+            lib.lh_eval_candidates_batch_device.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + \
+                [C.c_void_p] * 5 + [C.c_int32, C.POINTER(_CandidateOutputs), C.c_void_p]
+            lib.lh_candidates_profile_read.argtypes = [C.c_void_p, c_f64p, C.POINTER(C.c_int64)]
+            lib.lh_candidates_info.argtypes = [C.c_void_p, c_i32p, c_i32p]
         if hasattr(lib, "lh_set_device"):      # (absent from round-2 builds loaded through LH_LIB_DIR for comparisons)
             lib.lh_set_device.argtypes = [C.c_int32]
             lib.lh_family_status.argtypes = [C.c_void_p]
@@ -160,6 +177,70 @@ class HipLibrary:
         ms, k = C.c_double(), C.c_int64()
         self.check(self.lib.lh_posterior_profile_read(h, C.byref(ms), C.byref(k)))
         return ms.value, k.value
+
+    def candidates_info(self, family):
+        """(candidates registered on the handle, sites every candidate has): lh_candidates_info."""
+        h = family.handle if isinstance(family, Family) else family
+        k, L = C.c_int32(), C.c_int32()
+        self.check(self.lib.lh_candidates_info(h, C.byref(k), C.byref(L)))
+        return k.value, L.value
+
+    def set_candidates(self, family, seqs, n_sites=None):
+        """K6a: registers candidate naive sequences seqs [K][L] (A,C,G,T,N = 0..4) on a family handle (a raw lh_family* or
+        a Family) and returns log P_HMM(s_k) [K] (-inf: no state path produces the candidate).  L must be the family's
+        alignment length (n_sites, if given, must be too)."""
+        h = family.handle if isinstance(family, Family) else family
+        seqs = np.asarray(seqs)
+        if seqs.ndim != 2 or seqs.shape[0] < 1:
+            raise ValueError("lh_family_set_candidates: candidates must be a non-empty [K][L] array")
+        if seqs.dtype.kind not in "iu" or seqs.min() < 0 or seqs.max() > 4:
+            raise ValueError("lh_family_set_candidates: bases must be integers 0..4 (A,C,G,T,N)")
+        for want in (lambda: n_sites, lambda: self.candidates_info(h)[1]):
+            L = want()
+            if L is not None and seqs.shape[1] != L:
+                raise ValueError("lh_family_set_candidates: candidates have %d sites, the family's alignment %d"
+                                 % (seqs.shape[1], L))
+        seqs = np.ascontiguousarray(seqs, dtype=np.uint8)
+        out = np.zeros(seqs.shape[0])
+        self.check(self.lib.lh_family_set_candidates(h, seqs.shape[0], seqs.ctypes.data_as(c_u8p),
+                                                     out.ctypes.data_as(c_f64p)))
+        return out
+
+    def eval_candidates_batch(self, family, n_tips, max_depth, ops, brlen, er, pi, alpha, num_rates, n_candidates=None,
+                              log_offset=None, want=("loglik", "log_cand", "weighted_sum", "weight_stats")):
+        """K0-K2 + K6b on a handle with candidates (set_candidates).  Returns a dict with the members of `want`:
+        loglik [n], log_cand [n, K] (log P(s_k | data, t_i)), weighted_sum [K], weight_stats [3], K = the candidates
+        registered on the handle (n_candidates, if given, must equal it)."""
+        h = family.handle if isinstance(family, Family) else family
+        ops = np.ascontiguousarray(ops, dtype=np.int32)
+        n = ops.shape[0]
+        brlen, er, pi, alpha = _f64(brlen), _f64(er), _f64(pi), _f64(alpha)
+        K, _ = self.candidates_info(h)
+        if n_candidates is not None and n_candidates != K:
+            raise ValueError("lh_eval_candidates_batch: %d candidates expected, the handle has %d" % (n_candidates, K))
+        if K == 0:
+            raise RuntimeError("linearham_hip: lh_eval_candidates_batch: lh_family_set_candidates has not been called")
+        if ops.ndim != 3 or n < 1 or any(np.asarray(a).shape[0] != n for a in (brlen, er, pi, alpha)) or \
+                (log_offset is not None and np.asarray(log_offset).shape != (n,)):
+            raise ValueError("lh_eval_candidates_batch: the per-row arrays must all have n rows")
+        shapes = {"loglik": (n,), "log_cand": (n, K), "weighted_sum": (K,), "weight_stats": (3,)}
+        res = {k: np.zeros(shapes[k]) for k in want}
+        lo = None if log_offset is None else _f64(log_offset)
+
+        def ptr(a):
+            return a.ctypes.data_as(c_f64p) if a is not None else None
+        outs = _CandidateOutputs(ptr(lo), ptr(res.get("loglik")), ptr(res.get("log_cand")), ptr(res.get("weighted_sum")),
+                                 ptr(res.get("weight_stats")))
+        self.check(self.lib.lh_eval_candidates_batch(h, n, n_tips, max_depth, ops.ctypes.data_as(c_i32p), ptr(brlen),
+                                                     ptr(er), ptr(pi), ptr(alpha), num_rates, C.byref(outs)))
+        return res
+
+    def candidates_profile_read(self, family):
+        """(K6a ms, K6b ms, evaluation calls) since the last read."""
+        h = family.handle if isinstance(family, Family) else family
+        ms, k = (C.c_double * 2)(), C.c_int64()
+        self.check(self.lib.lh_candidates_profile_read(h, ms, C.byref(k)))
+        return ms[0], ms[1], k.value
 
     def schedule_tree(self, n_tips, children, root):
         """children: int32 [(T-2)*2]; returns (ops [T-2,4] int32, max_depth)."""

@@ -170,6 +170,19 @@ struct PosteriorWs {  // K5's arrays that the caller of lh_eval_posterior_batch_
   DevBuf loglik, weights, stats, partial;
 };
 
+// K6 (lh_naive_probs.hip).  The prior P_HMM(s) of a candidate is the forward sweep over indicator emissions, one per
+// caller column: `twin` is the family created once more without its alignment (lh_family_create), whose columns are
+// the caller's one to one; col_site / col_base are the caller's column -> (site, naive base) map.
+struct CandidateWs {
+  lh_family* twin = nullptr;
+  std::string twin_error;  // why there is no twin
+  const int32_t* col_site = nullptr;  // [n_xmsa] (arena)
+  const uint8_t* col_base = nullptr;  // [n_xmsa] (arena)
+  lh::CandidateTables tab{};          // K == 0: lh_family_set_candidates has not been called
+  DevBuf seqs, em, prior, idx, agree, lem_cols;  // the candidates and their tables
+  DevBuf loglik, weights, stats, partial, lem, base;  // K6b's arrays the caller does not hand in
+};
+
 // Device copies of the host-pointer entry points' arrays.  The entry points share them on purpose: each waits for the device
 // before it fills them and before it returns, and a handle is driven by one thread at a time.
 struct HostInputs {
@@ -183,7 +196,8 @@ struct HostOutputs {
   DevBuf loglik, rates, xmsa_emission, forward, scaler_counts;
   DevBuf states;                     // lh_eval_sample_batch
   DevBuf anc, rate_choice;           // lh_asr_batch
-  DevBuf weighted_sum, weight_stats;  // lh_eval_posterior_batch
+  DevBuf weighted_sum, weight_stats;  // lh_eval_posterior_batch, lh_eval_candidates_batch
+  DevBuf log_cand, log_prior;         // lh_eval_candidates_batch, lh_family_set_candidates
 };
 
 // lh_eval_batch's host -> device pipeline: two pinned staging slots, a copy stream and a compute stream
@@ -214,6 +228,7 @@ struct lh_family {
   ForwardWs fws;
   AsrWs asr;
   PosteriorWs post;
+  CandidateWs cand;
   // forward arrays that stay on the device, shared by K4 and K5 in both their forms: K4 draws from them, K5 overwrites
   // them with the posteriors (calls on a handle do not overlap: they also share the workspace)
   DevBuf forward_dev;
@@ -224,6 +239,7 @@ struct lh_family {
   bool profile = false;
   KernelTimer<3> eval_timer;  // model, prune, forward
   KernelTimer<1> asr_timer, post_timer;
+  KernelTimer<1> prior_timer, cand_timer;  // K6a, K6b
   bool extended = false;  // lh_family_set_extended_range
   bool have_sampler = false;
   lh::DevSampler sampler{};  // device pointers inside (arena)
@@ -526,7 +542,7 @@ static const int kChunk = lh::debug_options().chunk;
 
 int run_forward(lh_family* f, int n, int R, const double* site_lik, const int32_t* site_scal, const double* pi,
                 const double* em_in, double* em_out, double* loglik_dev, const lh_eval_outputs* outs,
-                size_t sample_offset, hipStream_t stream) {
+                size_t sample_offset, hipStream_t stream, const lh::LogEmRequest& lem = lh::LogEmRequest{}) {
   double* fwd = (outs && outs->forward) ? outs->forward + sample_offset * f->host.forward_size : nullptr;
   int32_t* sco =
       (outs && outs->scaler_counts) ? outs->scaler_counts + sample_offset * f->host.scaler_size : nullptr;
@@ -539,7 +555,7 @@ int run_forward(lh_family* f, int n, int R, const double* site_lik, const int32_
     return 1;
   lh::launch_forward(f->host, f->dev, n, R, site_lik, site_scal, pi, em_in, em_out, w.gem.get<double>(), w.gcnt.get<int32_t>(),
                      w.jem.get<double>(), w.jrs.get<int32_t>(), w.dxf.get<double>(), w.dxc.get<int32_t>(), loglik_dev, fwd, sco,
-                     f->extended, stream);
+                     f->extended, stream, lem);
   LH_HIP(hipGetLastError());
   return 0;
 }
@@ -947,6 +963,16 @@ int lh_family_create(const lh_family_desc* desc, lh_family** out) {
       f->allocs.push_back(p);
     }
   }
+  if (!rc && desc->n_seqs > 0) {
+    // K6a's twin (CandidateWs); a family it cannot be made for still evaluates, and lh_family_set_candidates says why
+    rc = upload(f, desc->xmsa_site, C, &f->cand.col_site) || upload(f, desc->xmsa_naive_base, C, &f->cand.col_base);
+    lh_family_desc d2 = *desc;
+    d2.n_seqs = 0;
+    d2.msa = nullptr;
+    const std::string keep = g_error;
+    if (!rc && lh_family_create(&d2, &f->cand.twin)) f->cand.twin_error = g_error;
+    g_error = keep;
+  }
   if (rc) {
     std::string keep = g_error;
     lh_family_destroy(f);
@@ -960,6 +986,7 @@ int lh_family_create(const lh_family_desc* desc, lh_family** out) {
 void lh_family_destroy(lh_family* f) {
   if (!f) return;
   DeviceGuard guard(f);
+  lh_family_destroy(std::exchange(f->cand.twin, nullptr));
   for (void* p : f->allocs) (void)hipFree(p);
   delete f;  // the members release their buffers, events and streams while the guard keeps the family's device current
 }
@@ -1212,9 +1239,12 @@ int lh_asr_profile_read(lh_family* f, double* ms_sampling, int64_t* n_launches) 
   return f->asr_timer.read(ms_sampling, n_launches);
 }
 
-int lh_eval_batch_device(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops,
-                         const double* brlen, const double* er, const double* pi, const double* alpha,
-                         int32_t R, double* loglik, const lh_eval_outputs* outs, void* hip_stream) {
+namespace {
+
+// lh_eval_batch_device's body; lem: K6b's log emissions of every sample (lem.out[n][lem.n]), or none.
+int eval_device(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops, const double* brlen,
+                const double* er, const double* pi, const double* alpha, int32_t R, double* loglik,
+                const lh_eval_outputs* outs, void* hip_stream, const lh::LogEmRequest& lem) {
   if (int rc = check_batch(f, "lh_eval_batch", n, T, R, max_depth)) return rc > 0;
   DeviceGuard guard(f);
   if (!ops || !brlen || !er || !pi || !alpha || !loglik) return fail("lh_eval_batch: null array");
@@ -1241,12 +1271,22 @@ int lh_eval_batch_device(lh_family* f, int32_t n, int32_t T, int32_t max_depth, 
     if (planes < 0) return fail(std::string("lh_eval_batch: ") + lh::prune_last_error());
     f->k1_form = lh::prune_last_form();
     if (f->profile && f->eval_timer.mark(2, stream)) return 1;
-    if (run_forward(f, m, planes, site_lik, site_scal, pi + (size_t)off * 4, nullptr, em_out, loglik + off, outs, off, stream))
+    const lh::LogEmRequest lem_m{lem.cols, lem.n, lem.out ? lem.out + (size_t)off * lem.n : nullptr};
+    if (run_forward(f, m, planes, site_lik, site_scal, pi + (size_t)off * 4, nullptr, em_out, loglik + off, outs, off, stream,
+                    lem_m))
       return 1;
     if (f->profile && f->eval_timer.end(stream)) return 1;
     LH_HIP(hipGetLastError());
   }
   return 0;
+}
+
+}  // namespace
+
+int lh_eval_batch_device(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops,
+                         const double* brlen, const double* er, const double* pi, const double* alpha,
+                         int32_t R, double* loglik, const lh_eval_outputs* outs, void* hip_stream) {
+  return eval_device(f, n, T, max_depth, ops, brlen, er, pi, alpha, R, loglik, outs, hip_stream, lh::LogEmRequest{});
 }
 
 // Host pointers in, host pointers out.  The batch moves in sub-chunks through two pinned staging slots:
@@ -1603,6 +1643,185 @@ int lh_posterior_profile_read(lh_family* f, double* ms_posterior, int64_t* n_lau
   if (!f) return fail("null family");
   DeviceGuard guard(f);
   return f->post_timer.read(ms_posterior, n_launches);
+}
+
+// ---- K6: posterior probabilities of candidate naive sequences (lh_naive_probs.hip) ----
+
+int lh_family_set_candidates(lh_family* f, int32_t K, const uint8_t* seqs, double* log_prior) {
+  const std::string W = "lh_family_set_candidates";
+  if (!f) return fail(W + ": null family");
+  DeviceGuard guard(f);
+  CandidateWs& cw = f->cand;
+  if (f->host.n_seqs < 1) return fail(W + ": family was created without an MSA (forward-only)");
+  if (!cw.twin) return fail(W + ": no constrained forward sweep for this family: " + cw.twin_error);
+  if (K < 1 || K > 65536) return fail(W + ": K must be 1 .. 65536 candidates");
+  if (!seqs) return fail(W + ": null array");
+  const int L = f->host.n_sites, C = f->host.n_xmsa, NPr = f->host.n_prune;
+  for (size_t i = 0; i < (size_t)K * L; ++i)
+    if (seqs[i] > 4)
+      return fail(W + ": candidate " + std::to_string(i / L) + ", site " + std::to_string(i % L) + ": base " +
+                  std::to_string(seqs[i]) + " is not one of A,C,G,T,N = 0..4");
+  // the u-column of (site, base), as lh_family_create numbers them
+  std::vector<int32_t> site_pat(std::max(L, 1));
+  LH_HIP(hipMemcpy(site_pat.data(), f->host.site_pat, sizeof(int32_t) * L, hipMemcpyDeviceToHost));
+  auto ucol = [&](int i, int b) { return site_pat[i] < NPr ? b * NPr + site_pat[i] : 5 * NPr + b; };
+  std::vector<int32_t> var_sites;
+  std::vector<char> agrees(L, 1);
+  for (int i = 0; i < L; ++i) {
+    for (int k = 1; k < K && agrees[i]; ++k) agrees[i] = seqs[(size_t)k * L + i] == seqs[i];
+    if (!agrees[i]) var_sites.push_back(i);
+  }
+  // K2a's list: the variable sites' u-columns first (the scoring kernel's LDS), then the rest of the agreeing sites'
+  std::vector<int32_t> pos(f->host.n_ucol, -1), lem_cols;
+  const size_t V = var_sites.size();
+  std::vector<uint16_t> idx(V * K);
+  for (size_t v = 0; v < V; ++v)
+    for (int k = 0; k < K; ++k) {
+      const int u = ucol(var_sites[v], seqs[(size_t)k * L + var_sites[v]]);
+      if (pos[u] < 0) {
+        pos[u] = (int32_t)lem_cols.size();
+        lem_cols.push_back(u);
+      }
+      idx[v * K + k] = (uint16_t)pos[u];
+    }
+  const int n_vlem = (int)lem_cols.size();
+  if ((size_t)n_vlem * sizeof(double) > lh::candidate_lds_limit())
+    return fail(W + ": the candidates differ at too many (site, base) pairs for the scoring kernel's LDS (" +
+                std::to_string(n_vlem) + ")");
+  std::vector<double> agree;
+  for (int i = 0; i < L; ++i)
+    if (agrees[i]) {
+      const int u = ucol(i, seqs[i]);
+      if (pos[u] < 0) {
+        pos[u] = (int32_t)lem_cols.size();
+        lem_cols.push_back(u);
+      }
+    }
+  agree.assign(lem_cols.size(), 0.0);
+  for (int i = 0; i < L; ++i)
+    if (agrees[i]) agree[pos[ucol(i, seqs[i])]] += 1.0;
+  cw.tab.K = 0;  // the arguments are good: the old tables go before their buffers change (a call failing below leaves none)
+  if (cw.seqs.ensure((size_t)K * L) || cw.idx.ensure(sizeof(uint16_t) * idx.size()) ||
+      cw.agree.ensure(sizeof(double) * agree.size()) || cw.lem_cols.ensure(sizeof(int32_t) * lem_cols.size()) ||
+      cw.prior.ensure(sizeof(double) * K) ||
+      stage_inputs(f, {{seqs, (size_t)K * L, &cw.seqs},
+                       {idx.empty() ? nullptr : idx.data(), sizeof(uint16_t) * idx.size(), &cw.idx},
+                       {agree.empty() ? nullptr : agree.data(), sizeof(double) * agree.size(), &cw.agree},
+                       {lem_cols.empty() ? nullptr : lem_cols.data(), sizeof(int32_t) * lem_cols.size(), &cw.lem_cols}}))
+    return 1;
+  // K6a: the constrained forward sweep, in groups of candidates (the indicator emissions take C doubles each)
+  const int chunk = std::min(K, 4096);
+  if (cw.em.ensure(sizeof(double) * chunk * C)) return 1;
+  if (f->profile && f->prior_timer.begin(nullptr)) return 1;
+  for (int off = 0; off < K; off += chunk) {
+    const int m = std::min(chunk, K - off);
+    lh::launch_candidate_indicators(m, L, C, cw.seqs.get<uint8_t>() + (size_t)off * L, cw.col_site, cw.col_base,
+                                    cw.em.get<double>(), nullptr);
+    if (run_forward(cw.twin, m, 1, nullptr, nullptr, nullptr, cw.em.get<const double>(), nullptr,
+                    cw.prior.get<double>() + off, nullptr, 0, nullptr))
+      return 1;
+  }
+  if (f->profile && f->prior_timer.end(nullptr)) return 1;
+  LH_HIP(hipGetLastError());
+  cw.tab = {K, (int32_t)V, (int32_t)lem_cols.size(), n_vlem, cw.idx.get<const uint16_t>(), cw.agree.get<const double>(),
+            cw.prior.get<const double>()};
+  return copy_back(f, nullptr, {{log_prior, cw.prior.get(), sizeof(double) * K}});
+}
+
+int lh_eval_candidates_batch_device(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops,
+                                    const double* brlen, const double* er, const double* pi, const double* alpha, int32_t R,
+                                    const lh_candidate_outputs* outs, void* hip_stream) {
+  const std::string W = "lh_eval_candidates_batch_device";
+  if (int rc = check_batch(f, W, n, T, R, max_depth)) return rc > 0;
+  DeviceGuard guard(f);
+  CandidateWs& cw = f->cand;
+  const lh::CandidateTables& tab = cw.tab;
+  if (tab.K == 0) return fail(W + ": lh_family_set_candidates has not been called");
+  hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+  const lh_candidate_outputs none{nullptr, nullptr, nullptr, nullptr, nullptr};
+  const lh_candidate_outputs& o = outs ? *outs : none;
+  auto own = [](double*& p, DevBuf& b, size_t bytes) {
+    if (!p && b.ensure(bytes)) return 1;
+    if (!p) p = b.get<double>();
+    return 0;
+  };
+  double *ll = o.loglik, *w = nullptr, *stats = o.weight_stats, *partial = nullptr;
+  const bool reduce = o.weighted_sum || o.weight_stats;
+  const int slabs = lh::candidate_slabs(n);
+  if (own(ll, cw.loglik, sizeof(double) * n) || cw.lem.ensure(sizeof(double) * n * (size_t)tab.n_lem) ||
+      cw.base.ensure(sizeof(double) * n) ||
+      (reduce && (own(w, cw.weights, sizeof(double) * n) || own(stats, cw.stats, sizeof(double) * 3) ||
+                  (o.weighted_sum && own(partial, cw.partial, sizeof(double) * slabs * (size_t)tab.K)))))
+    return 1;
+  const lh::LogEmRequest lem{cw.lem_cols.get<const int32_t>(), tab.n_lem, cw.lem.get<double>()};
+  if (eval_device(f, n, T, max_depth, ops, brlen, er, pi, alpha, R, ll, nullptr, hip_stream, lem)) return 1;
+  if (f->profile && f->cand_timer.begin(stream)) return 1;
+  if (reduce) lh::launch_posterior_reduce(n, 0, nullptr, ll, o.log_offset, w, nullptr, nullptr, stats, stream);
+  if (o.log_cand || o.weighted_sum)
+    lh::launch_candidates(tab, n, cw.lem.get<const double>(), ll, o.weighted_sum ? w : nullptr, cw.base.get<double>(),
+                          o.log_cand, partial, stream);
+  if (o.weighted_sum) lh::launch_slab_sum(slabs, tab.K, partial, o.weighted_sum, stream);
+  if (f->profile && f->cand_timer.end(stream)) return 1;
+  LH_HIP(hipGetLastError());
+  return 0;
+}
+
+int lh_eval_candidates_batch(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops,
+                             const double* brlen, const double* er, const double* pi, const double* alpha, int32_t R,
+                             const lh_candidate_outputs* outs) {
+  const std::string W = "lh_eval_candidates_batch";
+  if (int rc = check_batch(f, W, n, T, R, max_depth)) return rc > 0;
+  DeviceGuard guard(f);
+  if (!ops || !brlen || !er || !pi || !alpha) return fail(W + ": null array");
+  if (f->cand.tab.K == 0) return fail(W + ": lh_family_set_candidates has not been called");
+  const lh_candidate_outputs none{nullptr, nullptr, nullptr, nullptr, nullptr};
+  const lh_candidate_outputs& o = outs ? *outs : none;
+  if (!o.log_cand && !o.weighted_sum && !o.weight_stats && !o.loglik) return 0;  // nothing asked for
+  const size_t nodes = 2 * (size_t)T - 2, n_ops = (size_t)T - 2, K = f->cand.tab.K;
+  HostInputs& in = f->in;
+  HostOutputs& out = f->out;
+  lh_candidate_outputs dev{nullptr, nullptr, nullptr, nullptr, nullptr};
+  if (out.loglik.ensure(sizeof(double) * n) || out_buf(o.log_cand, out.log_cand, sizeof(double) * K * n, &dev.log_cand) ||
+      out_buf(o.weighted_sum, out.weighted_sum, sizeof(double) * K, &dev.weighted_sum) ||
+      out_buf(o.weight_stats, out.weight_stats, sizeof(double) * 3, &dev.weight_stats) ||
+      stage_inputs(f, {{ops, sizeof(int32_t) * 4 * n_ops * n, &in.ops},
+                       {brlen, sizeof(double) * nodes * n, &in.brlen},
+                       {er, sizeof(double) * 6 * n, &in.er},
+                       {pi, sizeof(double) * 4 * n, &in.pi},
+                       {alpha, sizeof(double) * n, &in.alpha},
+                       {o.log_offset, sizeof(double) * n, &in.log_offset}}))
+    return 1;
+  dev.log_offset = o.log_offset ? in.log_offset.get<const double>() : nullptr;
+  dev.loglik = out.loglik.get<double>();
+  if (lh_eval_candidates_batch_device(f, n, T, max_depth, in.ops.get<const int32_t>(), in.brlen.get<const double>(),
+                                      in.er.get<const double>(), in.pi.get<const double>(), in.alpha.get<const double>(), R,
+                                      &dev, nullptr))
+    return 1;
+  if (!valid_schedules(ops, (size_t)n, T, (int)nodes, max_depth)) return refuse_schedules(f, W.c_str());
+  return copy_back(f, W.c_str(),
+                   {{o.loglik, dev.loglik, sizeof(double) * n},
+                    {o.log_cand, dev.log_cand, sizeof(double) * K * n},
+                    {o.weighted_sum, dev.weighted_sum, sizeof(double) * K},
+                    {o.weight_stats, dev.weight_stats, sizeof(double) * 3}});
+}
+
+int lh_candidates_info(const lh_family* f, int32_t* n_candidates, int32_t* n_sites) {
+  if (!f) return fail("lh_candidates_info: null family");
+  if (n_candidates) *n_candidates = f->cand.tab.K;
+  if (n_sites) *n_sites = f->host.n_sites;
+  return 0;
+}
+
+int lh_candidates_profile_read(lh_family* f, double* ms, int64_t* n_launches) {
+  if (!f) return fail("null family");
+  DeviceGuard guard(f);
+  double a = 0.0, b = 0.0;
+  if (f->prior_timer.read(&a, nullptr) || f->cand_timer.read(&b, n_launches)) return 1;
+  if (ms) {
+    ms[0] = a;
+    ms[1] = b;
+  }
+  return 0;
 }
 
 }  // extern "C"

@@ -184,6 +184,30 @@ void launch_posterior(const DevSampler* smp_dev, int n, double* post, size_t for
 int posterior_slabs(int n);
 void launch_posterior_reduce(int n, size_t forward_size, const double* post, const double* loglik, const double* log_offset,
                              double* w, double* partial, double* weighted_sum, double* stats, hipStream_t stream);
+// out[j] = sum over k < n_slabs, in order, of partial[k][j] (K5's last reduction step; K6b's too)
+void launch_slab_sum(int n_slabs, size_t size, const double* partial, double* out, hipStream_t stream);
+
+// K6 (lh_naive_probs.hip): exact posterior probabilities of candidate naive sequences.
+// K6a: em[k][c] = 1 where candidate k has the naive base of the caller's column c at its site, else 0 (the
+// indicator emissions of the constrained forward sweep), for K candidates of L sites and C columns.
+void launch_candidate_indicators(int K, int L, int C, const uint8_t* seqs, const int32_t* col_site, const uint8_t* col_base,
+                                 double* em, hipStream_t stream);
+// K6b's tables (lh_family_set_candidates): the log emissions K2a writes per sample are lem[n][n_lem] (LogEmRequest);
+// the first n_vlem of them are the u-columns of the variable sites, which idx[V][K] (uint16) names per (variable site,
+// candidate); agree[n_lem] counts the sites where all candidates agree on each u-column.
+struct CandidateTables {
+  int32_t K, V, n_lem, n_vlem;
+  const uint16_t* idx;
+  const double* agree;
+  const double* log_prior;  // [K]
+};
+// log_cand[n][K] (may be null) = log_prior + sum of the candidate's log emissions - loglik (NaN for a row whose loglik is
+// not finite); base[n] scratch; when w is not null, partial[candidate_slabs(n)][K] receives the slabs' sums
+// of w_i exp(log_cand[i][k]) (rows with w_i = 0 skipped), in order.
+int candidate_slabs(int n);
+size_t candidate_lds_limit();  // largest n_vlem * 8 the scoring kernel takes
+void launch_candidates(const CandidateTables& t, int n, const double* lem, const double* loglik, const double* w,
+                       double* base, double* log_cand, double* partial, hipStream_t stream);
 
 // P = I + U expm1(lambda * t*r) Uinv, clamped at 0 (K1's prologue).
 // e: lambda[4] | U[4][4] | Uinv[4][4]
@@ -250,11 +274,18 @@ size_t asr_slots(int L, int R);  // slots per sample in K3's CLV area: clv[n][T-
 // extended: the opt-in extended-range mode (include/linearham_amd.h, lh_family_set_extended_range); jrs[n][rows
 // of both junctions] is then the K2a -> K2b hand-off of the junction rows' emission scaler counts.
 // fam_dev: the device copy of fam (K2a reads the descriptor from memory instead of taking it by value).
+// lem: K6b's optional request (lh_naive_probs.hip), with site_lik only: K2a also writes out[sample][j], j < lem.n, the
+// log emission of u-column cols[j] less 256 log 2 per 2^-256 count in the extended-range mode.
+struct LogEmRequest {
+  const int32_t* cols = nullptr;
+  int n = 0;
+  double* out = nullptr;
+};
 void launch_forward(const DevFamily& fam, const DevFamily* fam_dev, int n, int R, const double* site_lik,
                     const int32_t* site_scal, const double* pi, const double* em_in, double* em_out, double* gem,
                     int32_t* gcnt, double* jem,
                     int32_t* jrs, double* dxf, int32_t* dxc, double* loglik, double* forward_out, int32_t* scaler_out,
-                    bool extended, hipStream_t stream);
+                    bool extended, hipStream_t stream, const LogEmRequest& lem = LogEmRequest{});
 size_t forward_lds_bytes(const DevFamily& fam);
 
 // Every environment switch of the device library in one place: hooks that tests/ use to push a family onto a kernel

@@ -423,12 +423,15 @@ __device__ static int fill_consensus(const DevSegments& seg, const double* em, i
   return mx;
 }
 
-template <int kG, bool kFromSiteLik, bool kByteOff, bool kExt = false>
+// kLem (K6b's request, lh_naive_probs.hip): also write lem[n][n_lem] = log of the emission of u-column lem_cols[j], less
+// its 2^-256 count in the extended-range mode -- the values this kernel assembles, before anything underflows.
+template <int kG, bool kFromSiteLik, bool kByteOff, bool kExt = false, bool kLem = false>
 __global__ void __launch_bounds__(kFwdThreads) __attribute__((amdgpu_num_sgpr(80)))  // 80: eight workgroups per CU
     emission_kernel(const DevFamily* __restrict__ fam_dev, int R, const double* __restrict__ site_lik,
                     const int32_t* __restrict__ site_scal, const double* __restrict__ pi,
                     const double* __restrict__ em_in, double* __restrict__ em_out, double* __restrict__ gem_all,
-                    int32_t* __restrict__ gcnt_all, double* __restrict__ jem_all, int32_t* __restrict__ jrs_all) {
+                    int32_t* __restrict__ gcnt_all, double* __restrict__ jem_all, int32_t* __restrict__ jrs_all,
+                    const int32_t* __restrict__ lem_cols, int n_lem, double* __restrict__ lem_all) {
   // (the family descriptor is read from its device copy where a field is needed: passed by value it took more
   // scalar registers than the 96 that still admit seven workgroups per CU)
   const DevFamily& fam = *fam_dev;
@@ -546,6 +549,15 @@ __global__ void __launch_bounds__(kFwdThreads) __attribute__((amdgpu_num_sgpr(80
   {
     double* jem = jem_all + s * fam.n_jcols;
     for (int j = tid; j < fam.n_jcols; j += kFwdThreads) jem[j] = em[fam.jcols[j]];
+  }
+  if constexpr (kLem) {
+    double* lem = lem_all + s * n_lem;
+    for (int j = tid; j < n_lem; j += kFwdThreads) {
+      const int u = lem_cols[j];
+      double l = log(em[u]);
+      if constexpr (kExt) l -= ems[u] * kLogScaleFactor;
+      lem[j] = l;
+    }
   }
   if constexpr (kExt) {
     // ... and the 2^-256 count of each junction row: all columns of a row belong to one alignment site, whose
@@ -1628,23 +1640,41 @@ size_t forward_lds_bytes(const DevFamily& fam) {
   return a > b ? a : b;
 }
 
+template <int kG, bool kSite, bool kByteOff, bool kExt, bool kLem>
+static void launch_emission_l(const DevFamily& fam, const DevFamily* fam_dev, int n, int R, const double* site_lik,
+                              const int32_t* site_scal, const double* pi, const double* em_in, double* em_out,
+                              double* gem, int32_t* gcnt, double* jem, int32_t* jrs, const LogEmRequest& lem,
+                              hipStream_t stream) {
+  const size_t lds = emission_lds_bytes(fam, kExt);
+  if (lds > 64 * 1024)
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(emission_kernel<kG, kSite, kByteOff, kExt, kLem>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL((emission_kernel<kG, kSite, kByteOff, kExt, kLem>), dim3(n), dim3(kFwdThreads), lds, stream, fam_dev,
+                     R, site_lik, site_scal, pi, em_in, em_out, gem, gcnt, jem, jrs, lem.cols, lem.n, lem.out);
+}
+
 template <int kG, bool kSite, bool kByteOff, bool kExt>
 static void launch_emission_k(const DevFamily& fam, const DevFamily* fam_dev, int n, int R, const double* site_lik,
                               const int32_t* site_scal, const double* pi, const double* em_in, double* em_out,
-                              double* gem, int32_t* gcnt, double* jem, int32_t* jrs, hipStream_t stream) {
-  const size_t lds = emission_lds_bytes(fam, kExt);
-  if (lds > 64 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(emission_kernel<kG, kSite, kByteOff, kExt>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL((emission_kernel<kG, kSite, kByteOff, kExt>), dim3(n), dim3(kFwdThreads), lds, stream, fam_dev, R,
-                     site_lik, site_scal, pi, em_in, em_out, gem, gcnt, jem, jrs);
+                              double* gem, int32_t* gcnt, double* jem, int32_t* jrs, const LogEmRequest& lem,
+                              hipStream_t stream) {
+  if constexpr (kSite) {
+    if (lem.out) {
+      launch_emission_l<kG, kSite, kByteOff, kExt, true>(fam, fam_dev, n, R, site_lik, site_scal, pi, em_in, em_out, gem,
+                                                         gcnt, jem, jrs, lem, stream);
+      return;
+    }
+  }
+  launch_emission_l<kG, kSite, kByteOff, kExt, false>(fam, fam_dev, n, R, site_lik, site_scal, pi, em_in, em_out, gem, gcnt,
+                                                      jem, jrs, lem, stream);
 }
 
 template <int kG>
 static void launch_emission_g(const DevFamily& fam, const DevFamily* fam_dev, int n, int R, const double* site_lik,
                               const int32_t* site_scal, const double* pi, const double* em_in, double* em_out,
-                              double* gem, int32_t* gcnt, double* jem, int32_t* jrs, bool ext, hipStream_t stream) {
-#define LH_ARGS fam, fam_dev, n, R, site_lik, site_scal, pi, em_in, em_out, gem, gcnt, jem, jrs, stream
+                              double* gem, int32_t* gcnt, double* jem, int32_t* jrs, bool ext, const LogEmRequest& lem,
+                              hipStream_t stream) {
+#define LH_ARGS fam, fam_dev, n, R, site_lik, site_scal, pi, em_in, em_out, gem, gcnt, jem, jrs, lem, stream
   if (ext) {  // opt-in mode: one index form is enough
     if (site_lik) {
       if (fam.idx_byte_offsets)
@@ -1754,15 +1784,16 @@ static void launch_junction_a(int gb, const DevFamily& fam, int n, const double*
 
 // site_lik != null: emissions are assembled from K1's output (em_out optional);
 // site_lik == null: emissions are taken from em_in (SimpleHMM / lh_forward_batch).
+// lem.out != null (site_lik != null only): K2a also writes the log emissions K6b reads (LogEmRequest, lh_device.h).
 // gem [n][gem_size], gcnt [n][3], jem [n][n_jcols]: per-sample hand-off buffers between K2a and K2b
 // (+ jrs [n][junction rows] in the extended-range mode); dxf [n][32], dxc [n]: between the two K2b kernels of the
 // pair form.
 void launch_forward(const DevFamily& fam, const DevFamily* fam_dev, int n, int R, const double* site_lik,
                     const int32_t* site_scal, const double* pi, const double* em_in, double* em_out, double* gem,
                     int32_t* gcnt, double* jem, int32_t* jrs, double* dxf, int32_t* dxc, double* loglik,
-                    double* forward_out, int32_t* scaler_out, bool ext, hipStream_t stream) {
+                    double* forward_out, int32_t* scaler_out, bool ext, hipStream_t stream, const LogEmRequest& lem) {
   const int slots = (fam.max_genes + kFwdThreads - 1) / kFwdThreads;
-#define LH_ARGS fam, fam_dev, n, R, site_lik, site_scal, pi, em_in, em_out, gem, gcnt, jem, jrs, ext, stream
+#define LH_ARGS fam, fam_dev, n, R, site_lik, site_scal, pi, em_in, em_out, gem, gcnt, jem, jrs, ext, lem, stream
   if (slots <= 1)
     launch_emission_g<1>(LH_ARGS);
   else if (slots <= 2)

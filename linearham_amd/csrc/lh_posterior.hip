@@ -287,6 +287,11 @@ void launch_posterior(const DevSampler* smp_dev, int n, double* post, size_t for
 
 int posterior_slabs(int n) { return (n + kSlab - 1) / kSlab; }
 
+void launch_slab_sum(int n_slabs, size_t size, const double* partial, double* out, hipStream_t stream) {
+  hipLaunchKernelGGL(slab_sum_kernel, dim3((unsigned)((size + kRedThreads - 1) / kRedThreads)), dim3(kRedThreads), 0, stream,
+                     n_slabs, size, partial, out);
+}
+
 void launch_posterior_reduce(int n, size_t forward_size, const double* post, const double* loglik, const double* log_offset,
                              double* w, double* partial, double* weighted_sum, double* stats, hipStream_t stream) {
   hipLaunchKernelGGL(weight_kernel, dim3(1), dim3(kRedThreads), 0, stream, n, loglik, log_offset, w, stats);
