@@ -303,6 +303,11 @@ int lh_eval_candidates_batch_device(lh_family* fam, int32_t n, int32_t n_tips, i
  * number of sites every candidate has (the alignment's).  Either pointer may be NULL. */
 int lh_candidates_info(const lh_family* fam, int32_t* n_candidates, int32_t* n_sites);
 
+/* Read-only layout of the registered candidate tables (all 0 when none are registered): n_var_sites = the sites where
+ * the candidates do not all agree (V), n_lem = the u-columns K2a writes log emissions for, n_vlem = the first n_lem
+ * entries that belong to variable sites (K6b's LDS row holds n_vlem doubles).  Any pointer may be NULL. */
+int lh_candidates_layout(const lh_family* fam, int32_t* n_var_sites, int32_t* n_lem, int32_t* n_vlem);
+
 /* Times while profiling was enabled (HIP events): ms[0] = K6a over the lh_family_set_candidates calls, ms[1] = K6b
  * (weights, scoring, reduction) over the evaluation calls, whose number goes to n_launches; resets the counters. */
 int lh_candidates_profile_read(lh_family* fam, double* ms, int64_t* n_launches);

@@ -51,7 +51,7 @@ POSTERIOR_EXPORTS = ["lh_eval_posterior_batch", "lh_eval_posterior_batch_device"
 EXPORTS += POSTERIOR_EXPORTS
 # K6 (exact posterior probabilities of candidate naive sequences)
 CANDIDATE_EXPORTS = ["lh_family_set_candidates", "lh_eval_candidates_batch", "lh_eval_candidates_batch_device",
-                     "lh_candidates_profile_read", "lh_candidates_info"]
+                     "lh_candidates_profile_read", "lh_candidates_info", "lh_candidates_layout"]
 EXPORTS += CANDIDATE_EXPORTS
 
 
@@ -129,6 +129,7 @@ class HipLibrary:
                 [C.c_void_p] * 5 + [C.c_int32, C.POINTER(_CandidateOutputs), C.c_void_p]
             lib.lh_candidates_profile_read.argtypes = [C.c_void_p, c_f64p, C.POINTER(C.c_int64)]
             lib.lh_candidates_info.argtypes = [C.c_void_p, c_i32p, c_i32p]
+            lib.lh_candidates_layout.argtypes = [C.c_void_p, c_i32p, c_i32p, c_i32p]
         if hasattr(lib, "lh_set_device"):      # (absent from round-2 builds loaded through LH_LIB_DIR for comparisons)
             lib.lh_set_device.argtypes = [C.c_int32]
             lib.lh_family_status.argtypes = [C.c_void_p]
@@ -184,6 +185,14 @@ class HipLibrary:
         k, L = C.c_int32(), C.c_int32()
         self.check(self.lib.lh_candidates_info(h, C.byref(k), C.byref(L)))
         return k.value, L.value
+
+    def candidates_layout(self, family):
+        """(variable sites V, log-emission u-columns n_lem, of which the variable sites' n_vlem) of the registered
+        candidate tables: lh_candidates_layout."""
+        h = family.handle if isinstance(family, Family) else family
+        v, a, b = C.c_int32(), C.c_int32(), C.c_int32()
+        self.check(self.lib.lh_candidates_layout(h, C.byref(v), C.byref(a), C.byref(b)))
+        return v.value, a.value, b.value
 
     def set_candidates(self, family, seqs, n_sites=None):
         """K6a: registers candidate naive sequences seqs [K][L] (A,C,G,T,N = 0..4) on a family handle (a raw lh_family* or

@@ -1812,6 +1812,15 @@ int lh_candidates_info(const lh_family* f, int32_t* n_candidates, int32_t* n_sit
   return 0;
 }
 
+int lh_candidates_layout(const lh_family* f, int32_t* n_var_sites, int32_t* n_lem, int32_t* n_vlem) {
+  if (!f) return fail("lh_candidates_layout: null family");
+  const lh::CandidateTables& t = f->cand.tab;
+  if (n_var_sites) *n_var_sites = t.V;
+  if (n_lem) *n_lem = t.n_lem;
+  if (n_vlem) *n_vlem = t.n_vlem;
+  return 0;
+}
+
 int lh_candidates_profile_read(lh_family* f, double* ms, int64_t* n_launches) {
   if (!f) return fail("null family");
   DeviceGuard guard(f);

@@ -79,12 +79,13 @@ def by_enumeration(h):
 
 
 def _indicator_chain(h, s):
-    """posterior_oracle's chain with every emission replaced by the indicator of s (plain values, no scaling)."""
-    s = np.asarray(s)
+    """posterior_oracle's chain with every emission replaced by the indicator of s (plain values, no scaling); s = None:
+    every indicator 1, the prior chain over all state paths."""
+    s = None if s is None else np.asarray(s)
     rows, writes = row_writes(h)
 
     def ind(ws):
-        return float(all(s[site] == b for site, b in ws))
+        return 1.0 if s is None else float(all(s[site] == b for site, b in ws))
 
     igh = h.locus == "igh"
     nv = len(h.vgerm.state_strs)
@@ -123,6 +124,101 @@ def constrained_log_prior(h, s):
         c += math.log(z)
         a = a / z
     return c
+
+
+def log_prior_mass(h):
+    """log of the total probability of every state path (the prior chain's forward sweep): the normaliser of
+    prior_draws' frequencies, P(draw = s) = exp(constrained_log_prior(s) - log_prior_mass)."""
+    c = 0.0
+    a = None
+    for v, T in _indicator_chain(h, None):
+        a = v.copy() if T is None else (a @ T) * v
+        z = a.sum()
+        c += math.log(z)
+        a = a / z
+    return c
+
+
+def prior_draws(h, n, rng):
+    """n naive sequences [n][L] (uint8, A,C,G,T,N = 0..4) drawn from the HMM's prior over state paths: forward filtering
+    and backward sampling on _indicator_chain's chain with every indicator 1, then the path's writes (sites no state
+    writes stay N).  Every draw is written by a path of non-zero probability, so its constrained_log_prior is finite."""
+    chain = _indicator_chain(h, None)
+    _, writes = row_writes(h)
+    alphas = []
+    a = None
+    for v, T in chain:
+        a = v.copy() if T is None else (a @ T) * v
+        a = a / a.sum()
+        alphas.append(a)
+
+    def draw(p):  # one state per column of p [S][n] (columns unnormalised), by inverse CDF
+        cum = np.cumsum(p, axis=0)
+        u = rng.random(p.shape[1]) * cum[-1]
+        return np.minimum((cum <= u[None, :]).sum(axis=0), p.shape[0] - 1)
+
+    path = [None] * len(chain)
+    path[-1] = draw(np.repeat(alphas[-1][:, None], n, axis=1))
+    for t in range(len(chain) - 2, -1, -1):
+        T = chain[t + 1][1]
+        path[t] = draw(alphas[t][:, None] * T[:, path[t + 1]])
+    L = h.msa.shape[1]
+    out = np.full((n, L), 4, dtype=np.uint8)
+    for t, ks in enumerate(path):
+        for k in np.unique(ks):
+            w = writes[t][k]
+            if w:
+                sites, bases = zip(*w)
+                out[np.ix_(ks == k, np.asarray(sites))] = np.asarray(bases, dtype=np.uint8)
+    return out
+
+
+def candidate_layout(msa, seqs):
+    """Host restatement of K6b's tables (lh_candidates_layout): (V, n_lem, n_vlem) for candidates seqs [K][L] on an
+    alignment msa [N][L].  A (site, base) pair's u-column is its (alignment column pattern, base) pair -- two sites
+    with identical columns share it (lh_family_create) -- so V = the sites where the candidates do not all agree,
+    n_vlem = the distinct (pattern, base) pairs over the variable sites and every candidate, n_lem = those and the
+    agreeing sites' (pattern, base) pairs together."""
+    msa, seqs = np.asarray(msa), np.asarray(seqs)
+    pats = {}
+    pat = np.array([pats.setdefault(msa[:, i].tobytes(), len(pats)) for i in range(msa.shape[1])])
+    var = np.nonzero((seqs != seqs[:1]).any(axis=0))[0]
+    vpairs = {(int(pat[i]), int(b)) for i in var for b in np.unique(seqs[:, i])}
+    agree = np.setdiff1d(np.arange(msa.shape[1]), var)
+    apairs = {(int(pat[i]), int(seqs[0, i])) for i in agree}
+    return len(var), len(vpairs | apairs), len(vpairs)
+
+
+def gather_slots(msa, seqs):
+    """lh_family_set_candidates' gather table, restated: (slots, idx) with slots the variable sites' (pattern, base)
+    pairs in the order K6b's LDS row holds them (variable sites in site order, candidates in order, first appearance)
+    and idx [V][K] each (variable site, candidate)'s slot."""
+    msa, seqs = np.asarray(msa), np.asarray(seqs)
+    pats = {}
+    pat = np.array([pats.setdefault(msa[:, i].tobytes(), len(pats)) for i in range(msa.shape[1])])
+    var = np.nonzero((seqs != seqs[:1]).any(axis=0))[0]
+    pos, slots = {}, []
+    idx = np.zeros((len(var), len(seqs)), dtype=np.int64)
+    for v, i in enumerate(var):
+        for k in range(len(seqs)):
+            key = (int(pat[i]), int(seqs[k, i]))
+            if key not in pos:
+                pos[key] = len(slots)
+                slots.append((int(i), int(seqs[k, i])))  # (a site with that pattern, base)
+            idx[v, k] = pos[key]
+    return var, slots, idx
+
+
+def log_emission_sums(h, seqs):
+    """log_emission_sum for every row of seqs [K][L] at once."""
+    seqs = np.asarray(seqs)
+    L = seqs.shape[1]
+    with np.errstate(divide="ignore"):
+        le = np.append(np.log(h.xmsa_emission), -math.inf)
+    ids = np.full((5, L), len(le) - 1)
+    for (b, i), x in h.xmsa_ids.items():
+        ids[b, i] = x
+    return le[ids[seqs, np.arange(L)[None, :]]].sum(axis=1)
 
 
 def log_emission_sum(h, s):
