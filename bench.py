@@ -7,7 +7,14 @@ BASELINE.json configs[2] family (synthetic 100 leaves x 400 sites, 200 V / 30 D 
 the flattened inputs already resident in HBM.  The product path is: C++ host (linearham's PhyloHMM
 surface, liblinearham_host.so) -> C ABI -> HIP kernels (liblinearham_hip.so).
 
-  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run does what the headline needs and no more: it generates the family (into a directory of its own, removed
+at exit), sets up, warms up, times the K steps, writes the dump if asked and prints the line.  `--full` adds the
+measurements and checks beside the headline: the CPU baseline and the parity check against the CPU oracle
+(`cpu_baseline`, `delta_logl_vs_cpu_max_rel`), the rate with the forward arrays written, the extra keys measured
+outside the `value` region (pipeline rows, the ancestral-sequence step, ragged reads) and K1's HBM traffic from live
+rocprofv3 passes (`roofline.traffic`; a plain run quotes the committed profile and says so).
 
 Multi-GPU: `--gpus N` with no launcher environment starts its own N rank processes (one per GPU) as fresh
 children before this process has touched the GPU, and relays rank 0's JSON line; under
@@ -18,6 +25,7 @@ an evaluation, one RCCL gather of the per-sample log-likelihoods per step.  Prin
 import argparse
 import json
 import os
+import shutil
 import sys
 import tempfile
 import time
@@ -44,7 +52,6 @@ WORKLOADS = {
                       "inside alignment columns (not the headline workload; its rate is the extra key mixed_n_evals_per_s)",
 }
 PMC_PROFILE = {"config2": "r04b_bench_pmc_per_launch.json", "config4": "r03_config4_pmc_per_launch.json"}
-GEN_VERSION = 2                # bump when tools/synth_family.py changes what it writes
 DUMP_LIMIT_BYTES = 64 << 20    # --dump-outputs: at most this much in all
 
 
@@ -72,38 +79,97 @@ def preset_spec(preset, batch):
     return sf.Spec.small(n_samples=max(min(batch, 64), 16))
 
 
-def family_dir(preset, spec):
-    tag = "" if spec.brlen_mean == 0.01 else "_bl%g" % spec.brlen_mean
-    if DEV_LEAVES is not None:
-        tag += "_l%d" % DEV_LEAVES
-    return os.path.join(tempfile.gettempdir(), "lh_bench_%s_n%d_v%d%s" % (preset, spec.n_samples, GEN_VERSION, tag))
-
-
-def prepare_family(preset, batch, may_generate, wait_s=600):
-    """The synthetic family in the reference's file formats (deterministic).  One process generates it
-    (into a scratch directory, renamed into place when complete); the others wait for it."""
+def _tree_rows(job):
+    """Rows s0 .. s1-1 of the trees.tsv that tools/synth_family.generate() writes, drawn from the state its row stream
+    has at row s0: the body of generate()'s row loop, unchanged (a worker of generate_family)."""
+    import numpy as np
     from tools import synth_family as sf
+    edges, T, labels, n_nni, state, s0, s1 = job
+    srng = np.random.default_rng(0)
+    srng.bit_generator.state = state
+    out = []
+    for s in range(s0, s1):
+        e2 = {k: list(v) for k, v in edges.items()}
+        for _ in range(n_nni):
+            sf.nni(e2, T, srng)
+        for v in e2.values():
+            v[2] = max(v[2] * float(srng.lognormal(0.0, 0.3)), 1e-6)
+        er = srng.dirichlet(np.ones(6))
+        pi = srng.dirichlet(np.ones(4))
+        pi = np.clip(pi, 0.01, None)
+        pi /= pi.sum()
+        alpha = max(float(srng.exponential(1.0)), 0.05)
+        lik = -1000.0 - 10.0 * srng.random()
+        row = [str(s * 10), "%.4f" % (lik - 50), "%.4f" % lik, "-50.0", "%.8g" % alpha] + \
+            ["%.8g" % x for x in er] + ["%.8g" % x for x in pi] + [sf.newick(e2, T, labels)]
+        out.append("\t".join(row) + "\n")
+    return "".join(out)
+
+
+def generate_family(spec, outdir, workers):
+    """tools/synth_family.generate(spec, outdir), byte for byte, with the rows of trees.tsv built by `workers` processes.
+    generate() draws every row from one stream (PCG64 seeded spec.seed + 1) and spends nearly all its time building and
+    formatting the rows (about a millisecond each on one core; configs[2] has 49 152).  A first pass here makes the same
+    draws without building anything and records the stream's state where each chunk of rows begins; the workers build
+    their chunks from those states (_tree_rows).  tests/test_bench_family.py holds the files equal to generate()'s."""
+    import copy
+    import multiprocessing as mp
+    from concurrent.futures import ProcessPoolExecutor
+    import numpy as np
+    from tools import synth_family as sf
+    n = spec.n_samples
+    if workers <= 1:
+        return sf.generate(spec, outdir)
+    head = copy.copy(spec)
+    head.n_samples = 0
+    meta = sf.generate(head, outdir)       # germline set, cluster.yaml, the table's header line
+    T = spec.n_leaves + 1
+    labels = ["naive"] + ["s%d" % i for i in range(spec.n_leaves)]
+    tree = sf.balanced_unrooted_tree if spec.tree_shape == "balanced" else sf.random_unrooted_tree
+    edges = tree(T, np.random.default_rng(spec.seed), spec.brlen_mean)
+    # the draws of one row: per NNI move an internal edge (NNI keeps their number) and one of two neighbours at either
+    # end of it, then a log-normal factor per edge, er, pi, alpha and the likelihood
+    n_internal = sum(1 for a, b, _ in edges.values() if a >= T and b >= T)
+    srng = np.random.default_rng(spec.seed + 1)
+    chunk = -(-n // (4 * workers))
+    # fresh interpreters, not forks: the caller may already hold the GPU
+    with ProcessPoolExecutor(workers, mp_context=mp.get_context("spawn")) as ex, \
+            open(os.path.join(outdir, "trees.tsv"), "a") as f:
+        parts = []
+        for s in range(n):
+            if s % chunk == 0:
+                job = (edges, T, labels, spec.n_nni, srng.bit_generator.state, s, min(s + chunk, n))
+                parts.append(ex.submit(_tree_rows, job))
+            for _ in range(spec.n_nni if n_internal else 0):
+                srng.integers(n_internal)
+                srng.integers(2)
+                srng.integers(2)
+            srng.lognormal(0.0, 0.3, size=len(edges))
+            srng.dirichlet(np.ones(6))
+            srng.dirichlet(np.ones(4))
+            srng.exponential(1.0)
+            srng.random()
+        for part in parts:
+            f.write(part.result())
+    meta["n_samples"] = n
+    with open(os.path.join(outdir, "meta.json"), "w") as f:
+        json.dump(meta, f, indent=1)
+    return meta
+
+
+RUN_DIRS = []                  # families this process generated; main() removes them when the run ends
+
+
+def prepare_family(preset, batch):
+    """The synthetic family in the reference's file formats, generated for this run into a directory of its own
+    (deterministic: every run writes the same bytes, and no run reads what another wrote).  Returns (dir, spec)."""
     spec = preset_spec(preset, batch)
-    d = family_dir(preset, spec)
-    done = os.path.join(d, "meta.json")
-    if os.path.exists(done):
-        return d, spec
-    if may_generate:
-        tmp = "%s.tmp%d" % (d, os.getpid())
-        t0 = time.time()
-        sf.generate(spec, tmp)
-        try:
-            os.rename(tmp, d)
-        except OSError:            # somebody else finished first
-            import shutil
-            shutil.rmtree(tmp, ignore_errors=True)
-        log("[bench] generated %s (%d tree samples) in %.1fs" % (d, spec.n_samples, time.time() - t0))
-        return d, spec
+    d = tempfile.mkdtemp(prefix="lh_bench_%s_" % preset)
+    RUN_DIRS.append(d)
     t0 = time.time()
-    while not os.path.exists(done):
-        if time.time() - t0 > wait_s:
-            raise SystemExit("timed out waiting for %s" % d)
-        time.sleep(0.5)
+    workers = min(usable_cores(), 16) if spec.n_samples >= 1024 else 1
+    generate_family(spec, d, workers)
+    log("[bench] generated %s (%d tree samples, %d processes) in %.1fs" % (d, spec.n_samples, workers, time.time() - t0))
     return d, spec
 
 
@@ -300,7 +366,7 @@ def mixed_n_rate(args, lib, T, R, n, dev, stream):
     import numpy as np
     import torch
     from linearham_amd import host
-    fam_dir, spec = prepare_family("config2_ragged", n, may_generate=True)
+    fam_dir, spec = prepare_family("config2_ragged", n)
     hmm = host.PhyloHMM(os.path.join(fam_dir, "cluster.yaml"), 0, os.path.join(fam_dir, "hmm_params"), 0)
     flat = hmm.flatten_tsv(os.path.join(fam_dir, "trees.tsv"), n)
     assert flat["n_tips"] == T
@@ -364,7 +430,6 @@ def live_k1_traffic(args):
     (bytes per launch with the gfx950 factor 2 x FETCH + WRITE, note) or (None, reason)."""
     import csv
     import glob
-    import shutil
     import subprocess
     exe = shutil.which("rocprofv3") or "/opt/rocm/bin/rocprofv3"
     if not os.path.exists(exe):
@@ -373,8 +438,8 @@ def live_k1_traffic(args):
     for ctr in ("FETCH_SIZE", "WRITE_SIZE"):
         out = tempfile.mkdtemp(prefix="lh_pmc_")
         cmd = [exe, "--pmc", ctr, "--output-format", "csv", "-d", out, "-o", "run", "--", sys.executable, os.path.abspath(__file__),
-               "--preset", args.preset, "--batch", str(args.batch), "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
-               "--no-check", "--no-extras", "--no-forward-rate", "--no-live-pmc"]
+               "--preset", args.preset, "--batch", str(args.batch), "--steps", "2", "--warmup", "1", "--no-check",
+               "--family-dir", args.family_dir]
         if BRLEN_MEAN is not None:
             cmd += ["--brlen-mean", repr(BRLEN_MEAN)]
         try:
@@ -413,22 +478,29 @@ def parse_args():
                          "(default 0.01: 253 site patterns for config2; 0.002 gives a family with ~100 patterns)")
     ap.add_argument("--leaves", type=int, default=None,
                     help="development only, with --brlen-mean: leaves of the synthetic tree (default 100)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the CPU baseline and the parity check against the CPU oracle, the rate with "
+                         "the forward arrays written, the extra keys measured outside the `value` region and K1's HBM "
+                         "traffic from live rocprofv3 passes (each can be left out with its --no-* option below)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline (the parity check stays)")
     ap.add_argument("--pcie", action="store_true",
-                    help="also time the host-pointer entry point (PCIe-inclusive rate; its launch groups are "
+                    help="with --full: also time the host-pointer entry point (PCIe-inclusive rate; its launch groups are "
                          "sub-batches of 6144, so leave it off when profiling per-launch kernel durations)")
-    ap.add_argument("--no-check", action="store_true", help="kernel timing experiments only")
-    ap.add_argument("--no-forward-rate", action="store_true", help="skip the second timed loop (forward arrays on)")
+    ap.add_argument("--no-check", action="store_true",
+                    help="kernel timing experiments only: no check of the results, not even for non-finite log-likelihoods")
+    ap.add_argument("--no-forward-rate", action="store_true",
+                    help="with --full: skip the second timed loop (forward arrays on)")
     ap.add_argument("--cpu-budget-s", type=float, default=20.0)
     ap.add_argument("--cpu-samples", type=int, default=192,
                     help="evaluations of the CPU baseline sample (also the rows the parity check covers)")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the extra keys measured outside the `value` region (pipeline_rows_per_s, asr_tree_samples_per_s)")
+                    help="with --full: skip the extra keys measured outside the `value` region (pipeline_rows_per_s, "
+                         "asr_tree_samples_per_s, mixed_n_evals_per_s)")
     ap.add_argument("--no-live-pmc", action="store_true",
-                    help="do not spawn the two short `rocprofv3 --pmc` child runs that measure K1's HBM traffic for roofline.traffic "
-                         "(the figure then comes from the committed profile and says so)")
+                    help="with --full: do not spawn the two short `rocprofv3 --pmc` child runs that measure K1's HBM traffic "
+                         "for roofline.traffic (the figure then comes from the committed profile and says so, as in a plain run)")
     ap.add_argument("--no-mixed-n", action="store_true",
-                    help="skip the extra key mixed_n_evals_per_s (the configs[2] family with ragged reads, outside `value`)")
+                    help="with --full: skip the extra key mixed_n_evals_per_s (the configs[2] family with ragged reads, outside `value`)")
     ap.add_argument("--timeout-s", type=float, default=1500.0,
                     help="--gpus N without a launcher: stop the rank processes after this many seconds (exit status 124)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
@@ -437,9 +509,13 @@ def parse_args():
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last one computed as DIR/<name>.npy: loglik.npy, the "
                          "per-sample log-likelihoods of every rank in global sample order (float64)")
+    # this run's family, generated by the process that started this one (the launcher; a --full run for its rocprofv3 children)
+    ap.add_argument("--family-dir", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.pcie and not args.full:
+        ap.error("--pcie is a measurement of --full")
     global BRLEN_MEAN, DEV_LEAVES
     BRLEN_MEAN = args.brlen_mean
     DEV_LEAVES = args.leaves if args.brlen_mean is not None else None
@@ -452,8 +528,8 @@ def launcher(args):
     """--gpus N without a launcher environment: this process stays off the GPU, prepares the input files,
     starts N fresh rank processes and relays rank 0's JSON line."""
     from linearham_amd import sharding
-    prepare_family(args.preset, args.batch, may_generate=True)
-    argv = [sys.executable, os.path.abspath(__file__)] + sys.argv[1:]
+    fam_dir, _ = prepare_family(args.preset, args.batch)
+    argv = [sys.executable, os.path.abspath(__file__)] + sys.argv[1:] + ["--family-dir", fam_dir]
     status, out = sharding.spawn_ranks(argv, args.gpus, timeout_s=args.timeout_s)
     sys.stdout.write(out)
     sys.stdout.flush()
@@ -487,8 +563,13 @@ def worker(args, rank, local_rank, world):
         else:
             dist.init_process_group(backend="gloo")
 
-    # ---- synthetic family in the reference's file formats (deterministic; one copy per box) -------
-    fam_dir, spec = prepare_family(args.preset, args.batch, may_generate=(rank == 0))
+    # ---- synthetic family in the reference's file formats (deterministic; one per run) ---------------
+    fam_dir, spec = args.family_dir, preset_spec(args.preset, args.batch)
+    if fam_dir is None:
+        # a rank of torch.distributed.run: rank 0 generates the family, the others read it (one box)
+        box = [prepare_family(args.preset, args.batch)[0] if rank == 0 else None]
+        dist.broadcast_object_list(box, src=0)
+        fam_dir = box[0]
 
     # ---- product path: C++ host builds the family + flattens the tree table -----------------------
     t0 = time.time()
@@ -559,7 +640,7 @@ def worker(args, rank, local_rank, world):
 
     # the same step with the arrays SampleNaiveSequence consumes (forward rows + ScaleMatrix counts) written
     dt_fwd = None
-    if not args.no_forward_rate and n > 0:
+    if args.full and not args.no_forward_rate and n > 0:
         fsize, ssize = lib.lib.lh_forward_size(C.c_void_p(fam_handle)), lib.lib.lh_scaler_size(C.c_void_p(fam_handle))
         fwd = torch.empty((n, fsize), dtype=torch.float64, device=dev)
         sco = torch.empty((n, ssize), dtype=torch.int32, device=dev)
@@ -614,7 +695,8 @@ def worker(args, rank, local_rank, world):
                     traffic = (2.0 * k1["FETCH_SIZE"] + k1["WRITE_SIZE"]) * 1024.0
                     traffic_note = ("NOT measured by this run (%s): profiles/%s, HBM-side bytes per K1 launch from separate "
                                     "rocprofv3 --pmc passes of this same command (2 x FETCH_SIZE + WRITE_SIZE)"
-                                    % (traffic_note or "live counters off", PMC_PROFILE.get(args.preset)))
+                                    % (traffic_note or ("live counters off" if args.full else "live counters are a --full measurement"),
+                                       PMC_PROFILE.get(args.preset)))
         model_bytes_per_eval = Cx * (2 * (T - 2) * R * 32 + T + 8)   # CLV-streaming model
         out = {
             "metric": "phylo-HMM log-likelihood evals/sec (100-leaf x 400-site family)",
@@ -659,7 +741,7 @@ def worker(args, rank, local_rank, world):
             out["evals_per_s_with_forward"] = n_total / dt_fwd
             out["with_forward_note"] = ("the same step with lh_eval_outputs.forward and .scaler_counts written (what "
                                         "SampleNaiveSequence consumes); `value` leaves them off, as SURVEY 8(d) excludes sampling")
-        if world == 1 and not args.no_extras and n > 0:
+        if world == 1 and args.full and not args.no_extras and n > 0:
             out.update(extra_rates(args, lib, fam_handle, hmm, d, T, depth, R, n, dev, stream, fam_dir, sizes, shard))
         if world == 1 and args.pcie:
             # PCIe-inclusive rate through the host-pointer entry point (never `value`): H2D of the
@@ -677,7 +759,7 @@ def worker(args, rank, local_rank, world):
             out["pcie_inclusive_evals_per_s"] = n * reps / (time.perf_counter() - t1)
             if not args.no_check and not np.array_equal(ll_pcie, ll_host, equal_nan=True):
                 raise SystemExit("host-pointer and device-pointer entry points disagree")
-        if not args.no_check:
+        if args.full and not args.no_check:
             # parity against the CPU oracle: at N = 1 on the timed baseline sample, at N > 1 on a few samples of
             # every rank's shard (global sample g was evaluated by rank g mod N)
             want_base = world == 1 and not args.no_cpu_baseline
@@ -708,20 +790,26 @@ def main():
     args = parse_args()
     from linearham_amd import sharding
     env = sharding.rank_env()
-    if env is None:
-        if args.gpus > 1:
-            return launcher(args)
-        env = (0, 0, 1)
-    rank, local_rank, world = env
-    global LIVE_TRAFFIC
-    under_profiler = any(k.startswith(("ROCPROF", "ROCP_")) for k in os.environ) or "rocprofiler" in os.environ.get("LD_PRELOAD", "")
-    if world == 1 and not args.no_live_pmc and not under_profiler and args.preset in ("config2", "config4"):
-        t0 = time.time()
-        LIVE_TRAFFIC = live_k1_traffic(args)
-        log("[bench] K1 HBM traffic from live rocprofv3 passes: %s (%.0f s)" % (LIVE_TRAFFIC, time.time() - t0))
-    if world != args.gpus:
-        log("warning: WORLD_SIZE=%d but --gpus %d; using WORLD_SIZE" % (world, args.gpus))
-    return worker(args, rank, local_rank, world)
+    try:
+        if env is None:
+            if args.gpus > 1:
+                return launcher(args)
+            env = (0, 0, 1)
+        rank, local_rank, world = env
+        if world == 1 and args.family_dir is None:       # before this process touches the GPU
+            args.family_dir = prepare_family(args.preset, args.batch)[0]
+        global LIVE_TRAFFIC
+        under_profiler = any(k.startswith(("ROCPROF", "ROCP_")) for k in os.environ) or "rocprofiler" in os.environ.get("LD_PRELOAD", "")
+        if args.full and world == 1 and not args.no_live_pmc and not under_profiler and args.preset in ("config2", "config4"):
+            t0 = time.time()
+            LIVE_TRAFFIC = live_k1_traffic(args)
+            log("[bench] K1 HBM traffic from live rocprofv3 passes: %s (%.0f s)" % (LIVE_TRAFFIC, time.time() - t0))
+        if world != args.gpus:
+            log("warning: WORLD_SIZE=%d but --gpus %d; using WORLD_SIZE" % (world, args.gpus))
+        return worker(args, rank, local_rank, world)
+    finally:
+        for d in RUN_DIRS:
+            shutil.rmtree(d, ignore_errors=True)
 
 
 if __name__ == "__main__":

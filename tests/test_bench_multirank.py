@@ -22,8 +22,8 @@ def test_bench_two_ranks_without_torchrun():
     """Two ranks sharing the one GPU of the test box (gloo gather through host memory): n_gpus == 2, every rank's
     samples checked against the CPU oracle."""
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--preset",
-                        "small", "--steps", "2", "--warmup", "1"], env=_clean_env(), capture_output=True, text=True,
-                       timeout=900)
+                        "small", "--steps", "2", "--warmup", "1", "--full"], env=_clean_env(), capture_output=True,
+                       text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, p.stdout
@@ -42,7 +42,7 @@ def test_bench_two_ranks_on_the_real_family_reuse_the_table():
     rotation: every rank still works through 6144 distinct rows), every rank parses only the rows it evaluates, and
     samples of both shards are checked against the CPU oracle."""
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--preset",
-                        "config2", "--batch", "6144", "--steps", "2", "--warmup", "1", "--no-forward-rate"],
+                        "config2", "--batch", "6144", "--steps", "2", "--warmup", "1", "--full", "--no-forward-rate"],
                        env=_clean_env(), capture_output=True, text=True, timeout=1200)
     assert p.returncode == 0, p.stderr[-3000:]
     out = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][0])
@@ -56,7 +56,7 @@ def test_bench_two_ranks_on_the_real_family_reuse_the_table():
 @pytest.mark.gpu
 def test_bench_single_rank_small():
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--preset", "small", "--steps", "2", "--warmup",
-                        "1"], env=_clean_env(), capture_output=True, text=True, timeout=900)
+                        "1", "--full"], env=_clean_env(), capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     out = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][0])
     assert out["n_gpus"] == 1 and out["delta_logl_vs_cpu_max_rel"] < 1e-9
@@ -66,12 +66,33 @@ def test_bench_single_rank_small():
 
 
 @pytest.mark.gpu
+def test_bench_plain_run_prints_the_headline_only(tmp_path):
+    """Without --full the run times the steps and prints the line: the headline keys, none of the measurements and
+    checks --full adds, and no family left behind in the temporary directory."""
+    tmp = str(tmp_path)
+    env = dict(_clean_env(), TMPDIR=tmp)
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--preset", "small", "--steps", "3", "--warmup",
+                        "1"], env=env, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, p.stdout
+    out = json.loads(lines[0])
+    assert out["unit"] == "evals/s" and out["higher_is_better"] is True and out["dtype"] == "f64"
+    assert out["steps"] == 3 and out["value"] > 0 and out["ms_per_step"] > 0
+    assert abs(out["value"] * out["ms_per_step"] * 1e-3 - out["config"]["tree_samples_per_step"]) < 1e-6 * out["value"]
+    for key in ("cpu_baseline", "delta_logl_vs_cpu_max_rel", "evals_per_s_with_forward", "pipeline_rows_per_s",
+                "asr_tree_samples_per_s", "mixed_n_evals_per_s", "pcie_inclusive_evals_per_s"):
+        assert key not in out, key
+    assert not [f for f in os.listdir(tmp) if f.startswith("lh_bench_")]
+
+
+@pytest.mark.gpu
 def test_bench_config3_preset():
     """BASELINE.json configs[3] on one rank: 10 000 DISTINCT tree samples of the configs[2] family (NNI-perturbed
     topologies, LogNormal(0, 0.3) branch-length factors), every one evaluated once per step; with N ranks the same
     10 000 are divided (strong scaling).  The first samples are checked against the CPU oracle."""
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--preset", "config3", "--steps", "2", "--warmup",
-                        "1", "--no-cpu-baseline"], env=_clean_env(), capture_output=True, text=True, timeout=900)
+                        "1", "--full", "--no-cpu-baseline"], env=_clean_env(), capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     out = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][0])
     assert out["scaling"] == "strong" and out["config"]["tree_samples_per_step"] == 10000

@@ -1,12 +1,13 @@
 #!/bin/bash
 # Kernel times and counters of the device side of RunPipeline (K0-K2 with the forward arrays written, then K4) at the
-# configs[2] size: `bench.py --no-mixed-n` runs it as its pipeline_rows_per_s extra.  Writes gpurun_out/k4_profile.txt.
+# configs[2] size: `bench.py --full --no-mixed-n` runs it as its pipeline_rows_per_s extra.  Writes k4_profile.txt to the
+# output folder.
 # usage (GPU box, repo root): bash tools/profile_k4.sh
 root=${GRAFT_REPO_ROOT:-$(pwd)}
 out=$root/gpurun_out/k4_profile.txt
 mkdir -p $root/gpurun_out
 cd /tmp && export TMPDIR=/tmp
-args="--no-cpu-baseline --no-check --no-mixed-n --steps 3 --warmup 1"
+args="--full --no-cpu-baseline --no-check --no-mixed-n --steps 3 --warmup 1"
 rm -rf /tmp/k4p_trace
 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/k4p_trace -o run -- python3 $root/bench.py $args > /dev/null 2> /tmp/k4p_trace.err
 echo "# kernel-trace averages (us): bench.py $args" > $out
