@@ -312,6 +312,45 @@ int lh_candidates_layout(const lh_family* fam, int32_t* n_var_sites, int32_t* n_
  * (weights, scoring, reduction) over the evaluation calls, whose number goes to n_launches; resets the counters. */
 int lh_candidates_profile_read(lh_family* fam, double* ms, int64_t* n_launches);
 
+/* ---- naive sequences of sampled states (K6c) ----
+ * The naive sequence a row of lh_eval_sample_batch's states stands for -- what HMM::ApplySampledStates writes into the
+ * row's naive_seq -- as bytes seqs[n][n_sites] (A,C,G,T,N = 0..4; sites no state covers are N), and a 64-bit hash of
+ * each: equal sequences have equal hashes, bit for bit on every run and batch split (LH_COLLECT_HASH_BITS=n masks them
+ * to n bits, a test hook).  Needs lh_family_set_sampler and a family with an MSA.
+ *
+ * lh_eval_sample_batch followed by K6c: loglik [n] and hash [n]; states [n][lh_sample_states()] may be NULL.  The
+ * batch's sequences stay in the handle's workspace for lh_draws_resolve / lh_draws_rows_read.  Host pointers. */
+int lh_eval_draw_batch(lh_family* fam, int32_t n, int32_t n_tips, int32_t max_depth, const int32_t* ops,
+                       const double* brlen, const double* er, const double* pi, const double* alpha,
+                       int32_t num_rates, const uint32_t* words, double* loglik, uint64_t* hash, int32_t* states);
+
+/* The same with every array resident on the handle's device (states may be NULL: the handle's workspace); enqueued on
+ * `hip_stream` without synchronising. */
+int lh_eval_draw_batch_device(lh_family* fam, int32_t n, int32_t n_tips, int32_t max_depth, const int32_t* ops,
+                              const double* brlen, const double* er, const double* pi, const double* alpha,
+                              int32_t num_rates, const uint32_t* words, double* loglik, uint64_t* hash,
+                              int32_t* states, void* hip_stream);
+
+/* K6c on caller-given states [n][lh_sample_states()] (host pointers): seqs [n][n_sites] and hash [n] (either may be
+ * NULL).  The rows become the handle's last batch, as after lh_eval_draw_batch. */
+int lh_naive_sequences(lh_family* fam, int32_t n, const int32_t* states, uint8_t* seqs, uint64_t* hash);
+
+/* The handle's candidate store: rows of the last batch assigned to candidates.  cand [n] (n = the last batch's rows)
+ * holds each row's candidate id, -1 for a row left out; ids at or above the store's count are new and must be
+ * consecutive, each with a row of the batch: the first such row's bytes are appended to the store.  Every assigned row
+ * is then compared with its candidate's stored bytes; the rows that differ (hash collisions) go to mismatch_rows [n]
+ * in row order, their number to *n_mismatch.  Either output may be NULL. */
+int lh_draws_resolve(lh_family* fam, int32_t n, const int32_t* cand, int32_t* n_mismatch, int32_t* mismatch_rows);
+/* seqs [n_rows][n_sites]: the bytes of rows[k] of the last batch. */
+int lh_draws_rows_read(lh_family* fam, int32_t n_rows, const int32_t* rows, uint8_t* seqs);
+/* *K: the number of stored candidates; seqs [K][n_sites] (may be NULL) their bytes. */
+int lh_draws_candidates_read(lh_family* fam, int32_t* K, uint8_t* seqs);
+/* Empties the candidate store. */
+int lh_draws_reset(lh_family* fam);
+/* Time of K6c (assembly and hash) over the draw / lh_naive_sequences calls made while profiling was enabled (HIP
+ * events); resets the counters. */
+int lh_collect_profile_read(lh_family* fam, double* ms, int64_t* n_launches);
+
 /* Tree in rooted-at-naive form: tips are nodes 0..T-1 (0 = `naive`, i = MSA row i-1), inner nodes
  * T..2T-3.  children[2*(v-T)+{0,1}] are the two children of inner node v when the tree is rooted at
  * `root`, the inner node adjacent to `naive`.  Writes the kernel's post-order schedule:

@@ -53,6 +53,10 @@ EXPORTS += POSTERIOR_EXPORTS
 CANDIDATE_EXPORTS = ["lh_family_set_candidates", "lh_eval_candidates_batch", "lh_eval_candidates_batch_device",
                      "lh_candidates_profile_read", "lh_candidates_info", "lh_candidates_layout"]
 EXPORTS += CANDIDATE_EXPORTS
+# K6c (naive sequences of sampled states, the candidate store)
+COLLECT_EXPORTS = ["lh_eval_draw_batch", "lh_eval_draw_batch_device", "lh_naive_sequences", "lh_draws_resolve",
+                   "lh_draws_rows_read", "lh_draws_candidates_read", "lh_draws_reset", "lh_collect_profile_read"]
+EXPORTS += COLLECT_EXPORTS
 
 
 class _PosteriorOutputs(C.Structure):
@@ -130,6 +134,18 @@ class HipLibrary:
             lib.lh_candidates_profile_read.argtypes = [C.c_void_p, c_f64p, C.POINTER(C.c_int64)]
             lib.lh_candidates_info.argtypes = [C.c_void_p, c_i32p, c_i32p]
             lib.lh_candidates_layout.argtypes = [C.c_void_p, c_i32p, c_i32p, c_i32p]
+        if hasattr(lib, "lh_naive_sequences"):
+            c_u64p = C.POINTER(C.c_uint64)
+            lib.lh_eval_draw_batch.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, c_i32p, c_f64p, c_f64p,
+                                               c_f64p, c_f64p, C.c_int32, C.POINTER(C.c_uint32), c_f64p, c_u64p, c_i32p]
+            lib.lh_eval_draw_batch_device.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 5 + \
+                [C.c_int32] + [C.c_void_p] * 5
+            lib.lh_naive_sequences.argtypes = [C.c_void_p, C.c_int32, c_i32p, c_u8p, c_u64p]
+            lib.lh_draws_resolve.argtypes = [C.c_void_p, C.c_int32, c_i32p, c_i32p, c_i32p]
+            lib.lh_draws_rows_read.argtypes = [C.c_void_p, C.c_int32, c_i32p, c_u8p]
+            lib.lh_draws_candidates_read.argtypes = [C.c_void_p, c_i32p, c_u8p]
+            lib.lh_draws_reset.argtypes = [C.c_void_p]
+            lib.lh_collect_profile_read.argtypes = [C.c_void_p, c_f64p, C.POINTER(C.c_int64)]
         if hasattr(lib, "lh_set_device"):      # (absent from round-2 builds loaded through LH_LIB_DIR for comparisons)
             lib.lh_set_device.argtypes = [C.c_int32]
             lib.lh_family_status.argtypes = [C.c_void_p]
@@ -250,6 +266,76 @@ class HipLibrary:
         ms, k = (C.c_double * 2)(), C.c_int64()
         self.check(self.lib.lh_candidates_profile_read(h, ms, C.byref(k)))
         return ms[0], ms[1], k.value
+
+    # ---- K6c: naive sequences of sampled states and the candidate store ----
+    def naive_sequences(self, family, states):
+        """K6c on states [n][lh_sample_states()]: (seqs [n][L] uint8, A,C,G,T,N = 0..4; hash [n] uint64)."""
+        h = family.handle if isinstance(family, Family) else family
+        states = np.ascontiguousarray(states, dtype=np.int32)
+        n = states.shape[0]
+        _, L = self.candidates_info(h)
+        seqs = np.zeros((n, L), dtype=np.uint8)
+        hsh = np.zeros(n, dtype=np.uint64)
+        self.check(self.lib.lh_naive_sequences(h, n, states.ctypes.data_as(c_i32p), seqs.ctypes.data_as(c_u8p),
+                                               hsh.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return seqs, hsh
+
+    def eval_draw_batch(self, family, n_tips, max_depth, ops, brlen, er, pi, alpha, num_rates, words, want_states=False):
+        """lh_eval_draw_batch: (loglik [n], hash [n], states [n][S] or None); the sequences stay on the handle."""
+        h = family.handle if isinstance(family, Family) else family
+        ops = np.ascontiguousarray(ops, dtype=np.int32)
+        n = ops.shape[0]
+        brlen, er, pi, alpha = _f64(brlen), _f64(er), _f64(pi), _f64(alpha)
+        words = np.ascontiguousarray(words, dtype=np.uint32)
+        ll = np.zeros(n)
+        hsh = np.zeros(n, dtype=np.uint64)
+        st = np.zeros((n, self.lib.lh_sample_states(h)), dtype=np.int32) if want_states else None
+        self.check(self.lib.lh_eval_draw_batch(h, n, n_tips, max_depth, ops.ctypes.data_as(c_i32p),
+                                               brlen.ctypes.data_as(c_f64p), er.ctypes.data_as(c_f64p),
+                                               pi.ctypes.data_as(c_f64p), alpha.ctypes.data_as(c_f64p), num_rates,
+                                               words.ctypes.data_as(C.POINTER(C.c_uint32)), ll.ctypes.data_as(c_f64p),
+                                               hsh.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                               st.ctypes.data_as(c_i32p) if st is not None else None))
+        return ll, hsh, st
+
+    def draws_resolve(self, family, cand):
+        """lh_draws_resolve: the rows of the last batch whose bytes differ from their candidate's."""
+        h = family.handle if isinstance(family, Family) else family
+        cand = np.ascontiguousarray(cand, dtype=np.int32)
+        rows = np.zeros(max(len(cand), 1), dtype=np.int32)
+        nm = C.c_int32()
+        self.check(self.lib.lh_draws_resolve(h, len(cand), cand.ctypes.data_as(c_i32p), C.byref(nm),
+                                             rows.ctypes.data_as(c_i32p)))
+        return rows[:nm.value].copy()
+
+    def draws_rows_read(self, family, rows):
+        h = family.handle if isinstance(family, Family) else family
+        rows = np.ascontiguousarray(rows, dtype=np.int32)
+        _, L = self.candidates_info(h)
+        out = np.zeros((len(rows), L), dtype=np.uint8)
+        self.check(self.lib.lh_draws_rows_read(h, len(rows), rows.ctypes.data_as(c_i32p), out.ctypes.data_as(c_u8p)))
+        return out
+
+    def draws_candidates_read(self, family):
+        """The candidate store: [K][L] uint8."""
+        h = family.handle if isinstance(family, Family) else family
+        k = C.c_int32()
+        self.check(self.lib.lh_draws_candidates_read(h, C.byref(k), None))
+        _, L = self.candidates_info(h)
+        out = np.zeros((k.value, L), dtype=np.uint8)
+        self.check(self.lib.lh_draws_candidates_read(h, C.byref(k), out.ctypes.data_as(c_u8p)))
+        return out
+
+    def draws_reset(self, family):
+        h = family.handle if isinstance(family, Family) else family
+        self.check(self.lib.lh_draws_reset(h))
+
+    def collect_profile_read(self, family):
+        """(K6c ms, launches) since the last read."""
+        h = family.handle if isinstance(family, Family) else family
+        ms, k = C.c_double(), C.c_int64()
+        self.check(self.lib.lh_collect_profile_read(h, C.byref(ms), C.byref(k)))
+        return ms.value, k.value
 
     def schedule_tree(self, n_tips, children, root):
         """children: int32 [(T-2)*2]; returns (ops [T-2,4] int32, max_depth)."""

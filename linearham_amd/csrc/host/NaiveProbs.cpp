@@ -1,0 +1,237 @@
+#include "NaiveProbs.hpp"
+
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <fstream>
+#include <map>
+#include <stdexcept>
+#include <unordered_map>
+
+namespace linearham {
+
+namespace {
+
+// the standard code over T, C, A, G (first base slowest)
+const char kCode[] = "FFLLSSSSYY**CC*WLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG";
+
+int CodeIndex(char b) {
+  switch (b) {
+    case 'T': return 0;
+    case 'C': return 1;
+    case 'A': return 2;
+    case 'G': return 3;
+    default: return -1;
+  }
+}
+
+char TranslateCodon(const char* c) {
+  char aa = 0;
+  for (int x = 0; x < 4; ++x)
+    for (int y = 0; y < 4; ++y)
+      for (int z = 0; z < 4; ++z) {
+        const int i = CodeIndex(c[0]), j = CodeIndex(c[1]), k = CodeIndex(c[2]);
+        if ((i >= 0 && x != i) || (j >= 0 && y != j) || (k >= 0 && z != k)) continue;
+        if (c[0] != 'N' && i < 0) return 'X';
+        if (c[1] != 'N' && j < 0) return 'X';
+        if (c[2] != 'N' && k < 0) return 'X';
+        const char a = kCode[x * 16 + y * 4 + z];
+        if (aa && a != aa) return 'X';
+        aa = a;
+      }
+  return aa ? aa : 'X';
+}
+
+}  // namespace
+
+std::string TranslateDna(const std::string& dna) {
+  std::string aa;
+  for (std::size_t i = 0; i + 3 <= dna.size(); i += 3) aa.push_back(TranslateCodon(dna.data() + i));
+  return aa;
+}
+
+std::string ReprDouble(double v) {
+  if (std::isnan(v)) return "nan";
+  if (std::isinf(v)) return v > 0 ? "inf" : "-inf";
+  if (v == 0.0) return std::signbit(v) ? "-0.0" : "0.0";
+  const bool neg = v < 0;
+  const double a = std::fabs(v);
+  std::string digits;
+  int decpt = 0;  // a = 0.<digits> x 10^decpt
+  char buf[64];
+  for (int p = 1; p <= 17 && digits.empty(); ++p) {
+    std::snprintf(buf, sizeof buf, "%.*e", p - 1, a);
+    const char* e = std::strchr(buf, 'e');
+    std::string m;
+    for (const char* q = buf; q < e; ++q)
+      if (*q != '.') m.push_back(*q);
+    const int ex = std::atoi(e + 1);
+    // the correctly rounded p digits and their two neighbours: the closest one that reads back to `a`
+    const unsigned long long M = std::strtoull(m.c_str(), nullptr, 10);
+    long double best_err = -1;
+    for (long long d = -1; d <= 1; ++d) {
+      const unsigned long long c = M + d;
+      if (c == 0) continue;
+      std::snprintf(buf, sizeof buf, "%llue%d", c, ex - (p - 1));
+      if (std::strtod(buf, nullptr) != a) continue;
+      const long double err = std::fabs(std::strtold(buf, nullptr) - (long double)a);
+      if (best_err >= 0 && err >= best_err) continue;
+      best_err = err;
+      std::string s = std::to_string(c);
+      decpt = ex + 1 + (int)s.size() - p;  // (999 + 1 carries into one more digit)
+      while (s.size() > 1 && s.back() == '0') s.pop_back();
+      digits = s;
+    }
+  }
+  std::string out = neg ? "-" : "";
+  const int nd = (int)digits.size();
+  if (decpt > -4 && decpt <= 16) {
+    if (decpt <= 0)
+      out += "0." + std::string(-decpt, '0') + digits;
+    else if (decpt >= nd)
+      out += digits + std::string(decpt - nd, '0') + ".0";
+    else
+      out += digits.substr(0, decpt) + "." + digits.substr(decpt);
+  } else {
+    out += digits.substr(0, 1);
+    if (nd > 1) out += "." + digits.substr(1);
+    const int e = decpt - 1;
+    std::snprintf(buf, sizeof buf, "e%c%02d", e < 0 ? '-' : '+', std::abs(e));
+    out += buf;
+  }
+  return out;
+}
+
+std::vector<std::string> ReadCandidateFile(const std::string& path, int n_sites) {
+  std::ifstream in(path);
+  if (!in) throw std::runtime_error("Can't read candidate file " + path);
+  std::vector<std::string> seqs;
+  std::vector<int> line_of;
+  std::string line, cur;
+  int ln = 0, cur_line = 0, header_line = 0;
+  bool fasta = false;
+  auto refuse_empty_record = [&] {
+    if (header_line && cur.empty())
+      throw std::runtime_error(path + ", line " + std::to_string(header_line) + ": FASTA header without a sequence");
+  };
+  auto flush = [&] {
+    if (cur.empty()) return;
+    seqs.push_back(cur);
+    line_of.push_back(cur_line);
+    cur.clear();
+  };
+  while (std::getline(in, line)) {
+    ++ln;
+    if (!line.empty() && line.back() == '\r') line.pop_back();
+    if (line.empty()) continue;
+    if (line[0] == '>') {
+      refuse_empty_record();
+      fasta = true;
+      flush();
+      header_line = ln;
+      continue;
+    }
+    for (char& ch : line) {
+      if (ch >= 'a' && ch <= 'z') ch = (char)(ch - 'a' + 'A');
+      if (!std::strchr("ACGTN", ch) || ch == 0)
+        throw std::runtime_error(path + ", line " + std::to_string(ln) + ": character '" + std::string(1, ch) +
+                                 "' is not one of ACGTN");
+    }
+    if (fasta) {
+      if (cur.empty()) cur_line = ln;
+      cur += line;
+    } else {
+      cur_line = ln;
+      cur = line;
+      flush();
+    }
+  }
+  refuse_empty_record();
+  flush();
+  if (seqs.empty()) throw std::runtime_error(path + ": no candidate sequences");
+  if (seqs.size() > 65536) throw std::runtime_error(path + ": more than 65536 candidates");
+  std::unordered_map<std::string, int> seen;
+  for (std::size_t k = 0; k < seqs.size(); ++k) {
+    if ((int)seqs[k].size() != n_sites)
+      throw std::runtime_error(path + ", line " + std::to_string(line_of[k]) + ": sequence of " +
+                               std::to_string(seqs[k].size()) + " sites, the alignment has " + std::to_string(n_sites));
+    const auto r = seen.emplace(seqs[k], line_of[k]);
+    if (!r.second)
+      throw std::runtime_error(path + ", line " + std::to_string(line_of[k]) + ": repeats the sequence of line " +
+                               std::to_string(r.first->second));
+  }
+  return seqs;
+}
+
+std::vector<std::size_t> RankCandidates(const NaiveProbsTable& t) {
+  std::vector<std::size_t> idx(t.seqs.size());
+  for (std::size_t k = 0; k < idx.size(); ++k) idx[k] = k;
+  std::stable_sort(idx.begin(), idx.end(), [&](std::size_t a, std::size_t b) { return t.prob[a] > t.prob[b]; });
+  return idx;
+}
+
+void WriteNaiveTable(std::ostream& o, const NaiveProbsTable& t, bool with_sampled) {
+  char buf[64];
+  auto num = [&](double v) {
+    std::snprintf(buf, sizeof buf, "%.17g", v);
+    return std::string(buf);
+  };
+  o << "rank\tNaiveSequence\tprobability\tlog_prior" << (with_sampled ? "\tsampled_count\tsampled_frequency" : "") << "\n";
+  const std::vector<std::size_t> idx = RankCandidates(t);
+  for (std::size_t r = 0; r < idx.size(); ++r) {
+    const std::size_t k = idx[r];
+    o << (r + 1) << '\t' << t.seqs[k] << '\t' << num(t.prob[k]) << '\t' << num(t.log_prior[k]);
+    if (with_sampled) {
+      if (t.sampled)
+        o << '\t' << t.count[k] << '\t' << num(t.freq[k]);
+      else
+        o << "\tNA\tNA";
+    }
+    o << '\n';
+  }
+}
+
+namespace {
+
+struct AaGroup {
+  std::string aa;
+  double p = 0.0;
+  std::vector<std::size_t> members;  // candidate order
+};
+
+std::vector<AaGroup> GroupByTranslation(const NaiveProbsTable& t) {
+  std::vector<AaGroup> g;
+  std::unordered_map<std::string, std::size_t> at;
+  for (std::size_t k = 0; k < t.seqs.size(); ++k) {
+    const std::string aa = TranslateDna(t.seqs[k]);
+    const auto r = at.emplace(aa, g.size());
+    if (r.second) g.push_back(AaGroup{aa, 0.0, {}});
+    AaGroup& x = g[r.first->second];
+    x.p += t.prob[k];
+    x.members.push_back(k);
+  }
+  std::stable_sort(g.begin(), g.end(), [](const AaGroup& a, const AaGroup& b) { return a.p > b.p; });
+  for (AaGroup& x : g)
+    std::stable_sort(x.members.begin(), x.members.end(),
+                     [&](std::size_t a, std::size_t b) { return t.prob[a] > t.prob[b]; });
+  return g;
+}
+
+}  // namespace
+
+void WriteAaFasta(std::ostream& o, const NaiveProbsTable& t) {
+  const std::vector<AaGroup> g = GroupByTranslation(t);
+  for (std::size_t i = 0; i < g.size(); ++i) o << ">naive_" << i << "_" << ReprDouble(g[i].p) << "\n" << g[i].aa << "\n";
+}
+
+void WriteDnaMap(std::ostream& o, const NaiveProbsTable& t) {
+  const std::vector<AaGroup> g = GroupByTranslation(t);
+  for (std::size_t i = 0; i < g.size(); ++i) {
+    o << ">naive_" << i << "_" << ReprDouble(g[i].p) << "\n";
+    for (std::size_t k : g[i].members) o << ReprDouble(t.prob[k]) << "," << t.seqs[k] << "\n";
+  }
+}
+
+}  // namespace linearham

@@ -1,5 +1,7 @@
 #include "PhyloHMM.hpp"
 
+#include "NaiveProbs.hpp"
+
 #include <cerrno>
 #include <fcntl.h>
 #include <sched.h>
@@ -20,6 +22,7 @@
 #include <mutex>
 #include <sstream>
 #include <thread>
+#include <unordered_map>
 
 namespace linearham {
 
@@ -1569,6 +1572,300 @@ void PhyloHMM::RunMarginalsPipeline(const std::string& input_path, const std::st
   std::snprintf(buf, sizeof buf, "%.17g", s1 * s1 / s2);
   summary << "key\tvalue\nrows_used\t" << (N - first - skipped) << "\nrows_skipped_nonfinite\t" << skipped
           << "\nkish_ess\t" << buf << "\n";
+}
+
+
+namespace {
+
+// ACGTN strings -> bytes 0..4 (the naive-base alphabet)
+std::vector<uint8_t> EncodeSeqs(const std::vector<std::string>& seqs, const std::string& alphabet, int L) {
+  std::vector<uint8_t> b(seqs.size() * (std::size_t)L);
+  for (std::size_t k = 0; k < seqs.size(); ++k) {
+    Require((int)seqs[k].size() == L, "candidate " + std::to_string(k) + " does not have the alignment's length");
+    for (int j = 0; j < L; ++j) {
+      const std::size_t a = alphabet.find(seqs[k][j]);
+      Require(a != std::string::npos && a < 5, "candidate " + std::to_string(k) + " holds a character outside ACGTN");
+      b[k * L + j] = (uint8_t)a;
+    }
+  }
+  return b;
+}
+
+}  // namespace
+
+std::vector<double> PhyloHMM::CandidatePosterior(const std::vector<std::string>& seqs, double* loglik,
+                                                 std::vector<double>* log_prior) {
+  Require(have_tree_, "InitializePhyloParameters must be called first");
+  Require(!seqs.empty(), "CandidatePosterior: no candidates");
+  CreateFamily();
+  const int L = msa_.cols(), K = (int)seqs.size();
+  const std::vector<uint8_t> b = EncodeSeqs(seqs, alphabet_, L);
+  std::vector<double> prior(K);
+  CheckHip(lh_family_set_candidates(family_, K, b.data(), prior.data()), "lh_family_set_candidates");
+  const int T = tree_.n_tips;
+  std::vector<int32_t> ops((std::size_t)(T - 2) * 4);
+  int32_t depth = 0;
+  CheckHip(lh_schedule_tree(T, tree_.children.data(), tree_.root, ops.data(), &depth), "lh_schedule_tree");
+  std::vector<double> lc(K);
+  double ll = 0;
+  lh_candidate_outputs outs{nullptr, &ll, lc.data(), nullptr, nullptr};
+  CheckHip(lh_eval_candidates_batch(family_, 1, T, depth, ops.data(), tree_.brlen.data(), er_.data(), pi_.data(), &alpha_,
+                                    num_rates_, &outs),
+           "lh_eval_candidates_batch");
+  if (loglik) *loglik = ll;
+  if (log_prior) *log_prior = prior;
+  return lc;
+}
+
+// Pass 1 draws every used row's naive sequence with the std::mt19937 words RunPipeline gives that row (row r: words
+// r * RawDrawsPerSample() on), on the device where the family has its sampler tables: K4's states become bytes and a
+// hash there (K6c), the host maps hashes to candidate ids in row order and the device checks every row's bytes against
+// its candidate's (lh_draws_resolve); rows whose hash collides with another sequence's are resolved by their bytes.
+// Candidates are numbered by first appearance at the end, so both paths, every batch size and every hash width give
+// the same ids.  Pass 2 scores the candidates exactly (K6b) and combines the batches as RunMarginalsPipeline does.
+void PhyloHMM::RunNaiveProbsPipeline(const std::string& input_path, const std::string& output_prefix, int num_rates,
+                                     double burnin_frac, const std::string& candidates_path, int max_candidates) {
+  Require(devices_.size() <= 1, "the naive-probabilities pipeline runs on one device: --devices may list only one");
+  Require(burnin_frac >= 0.0 && burnin_frac < 1.0, "burn-in fraction must be in [0, 1)");
+  Require(max_candidates >= 1 && max_candidates <= 65536, "max-candidates must be in 1 .. 65536");
+  CreateFamily();
+  // stage times on stderr (LH_PIPELINE_TIMING): table parsing, device calls, host collection, per pass
+  const bool timing = host_options().pipeline_timing;
+  auto now = [] { return std::chrono::steady_clock::now(); };
+  auto secs = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
+    return std::chrono::duration<double>(b - a).count();
+  };
+  double p1_parse = 0, p1_dev = 0, p1_collect = 0, p1_total = 0, p2_prior = 0, p2_parse = 0, p2_dev = 0, p2_total = 0;
+  TsvTable table = TsvTable::Read(input_path, "RevBayes output file");
+  const char* names[15] = {"Iteration", "Likelihood", "Prior", "alpha", "er[1]", "er[2]", "er[3]", "er[4]",
+                           "er[5]", "er[6]",  "pi[1]", "pi[2]", "pi[3]", "pi[4]", "tree"};
+  table.Locate(names, 15, table.col, input_path);
+  const std::size_t N = table.rows.size();
+  const std::size_t first = (std::size_t)std::floor(burnin_frac * (double)N);
+  const std::size_t U = N - first;  // rows after the burn-in
+  const int L = msa_.cols();
+  const std::size_t kBatch = host_options().pipeline_batch > 0 ? (std::size_t)host_options().pipeline_batch : 49152;
+  NaiveProbsTable t;
+  std::vector<int32_t> row_id;  // pass 1: candidate of every row after the burn-in (-1: non-finite row or dropped)
+  std::vector<double> ll1;
+  int64_t draws_distinct = -1, dropped = 0;
+  const auto t_p1 = now();
+  if (candidates_path.empty()) {
+    const int raw = RawDrawsPerSample();
+    row_id.assign(U, -1);
+    ll1.assign(U, 0.0);
+    std::vector<std::string> distinct;  // by pass-1 id
+    if (device_sampler_) {
+      CheckHip(lh_draws_reset(family_), "lh_draws_reset");
+      std::unordered_map<uint64_t, int32_t> by_hash;  // hash -> store id of the first sequence seen with it
+      std::unordered_map<std::string, int32_t> exact;  // store ids made by resolving collisions, by their bytes
+      int32_t K = 0;
+      std::mt19937 word_rng = rng_;
+      word_rng.discard((unsigned long long)first * (unsigned long long)raw);
+      for (std::size_t off = first; off < N; off += kBatch) {
+        const std::size_t m = std::min(kBatch, N - off);
+        const auto t0 = now();
+        TableBatch tb = FlattenTable(table, off, off + m, false, true, input_path);
+        const DeviceBatch& b = tb.dev;
+        const auto t1 = now();
+        p1_parse += secs(t0, t1);
+        std::vector<uint32_t> words(m * (std::size_t)raw);
+        for (uint32_t& x : words) x = (uint32_t)word_rng();
+        std::vector<uint64_t> hash(m);
+        double* ll = ll1.data() + (off - first);
+        CheckHip(lh_eval_draw_batch(family_, b.n, b.n_tips, b.max_depth, b.ops.data(), b.brlen.data(), b.er.data(),
+                                    b.pi.data(), b.alpha.data(), num_rates, words.data(), ll, hash.data(), nullptr),
+                 "lh_eval_draw_batch");
+        const auto t2 = now();
+        p1_dev += secs(t1, t2);
+        int32_t* cand = row_id.data() + (off - first);
+        for (std::size_t i = 0; i < m; ++i) {
+          if (!std::isfinite(ll[i] - tb.lik[i])) continue;
+          const auto r = by_hash.emplace(hash[i], K);
+          if (r.second) ++K;
+          cand[i] = r.first->second;
+        }
+        std::vector<int32_t> mism(m);
+        std::vector<uint8_t> bytes;
+        for (int round = 0;; ++round) {
+          int32_t nm = 0;
+          CheckHip(lh_draws_resolve(family_, (int32_t)m, cand, &nm, mism.data()), "lh_draws_resolve");
+          if (nm == 0) break;
+          Require(round == 0, "naive-probabilities pipeline: rows still differ from their candidates after resolution");
+          bytes.resize((std::size_t)nm * L);
+          CheckHip(lh_draws_rows_read(family_, nm, mism.data(), bytes.data()), "lh_draws_rows_read");
+          for (int32_t q = 0; q < nm; ++q) {
+            std::string s((std::size_t)L, 'N');
+            for (int j = 0; j < L; ++j) s[j] = alphabet_[bytes[(std::size_t)q * L + j]];
+            const auto r = exact.emplace(s, K);
+            if (r.second) ++K;
+            cand[mism[q]] = r.first->second;
+          }
+        }
+        p1_collect += secs(t2, now());
+      }
+      int32_t Ks = 0;
+      CheckHip(lh_draws_candidates_read(family_, &Ks, nullptr), "lh_draws_candidates_read");
+      std::vector<uint8_t> store((std::size_t)Ks * L);
+      CheckHip(lh_draws_candidates_read(family_, &Ks, store.data()), "lh_draws_candidates_read");
+      // renumber by first appearance
+      std::vector<int32_t> remap(Ks, -1);
+      for (int32_t& id : row_id) {
+        if (id < 0) continue;
+        if (remap[id] < 0) {
+          remap[id] = (int32_t)distinct.size();
+          std::string s((std::size_t)L, 'N');
+          for (int j = 0; j < L; ++j) s[j] = alphabet_[store[(std::size_t)id * L + j]];
+          distinct.push_back(s);
+        }
+        id = remap[id];
+      }
+    } else {
+      // the host sampler (LH_HOST_SAMPLING, or no device sampler tables): forward arrays to the host, HMM::SampleRow
+      EnsureSamplingLists();
+      std::mt19937 rng = rng_;
+      rng.discard((unsigned long long)first * (unsigned long long)raw);
+      std::unordered_map<std::string, int32_t> ids;
+      const std::size_t FS = lh_forward_size(family_), SS = lh_scaler_size(family_);
+      const std::size_t kSub = std::min<std::size_t>(kBatch, 1024);
+      std::vector<double> fwd(kSub * FS);
+      std::vector<int32_t> sco(kSub * SS);
+      RowSampler s;
+      for (std::size_t off = first; off < N; off += kSub) {
+        const std::size_t m = std::min(kSub, N - off);
+        const auto t0 = now();
+        TableBatch tb = FlattenTable(table, off, off + m, false, true, input_path);
+        const DeviceBatch& b = tb.dev;
+        const auto t1 = now();
+        p1_parse += secs(t0, t1);
+        double* ll = ll1.data() + (off - first);
+        lh_eval_outputs outs{nullptr, nullptr, fwd.data(), sco.data()};
+        CheckHip(lh_eval_batch(family_, b.n, b.n_tips, b.max_depth, b.ops.data(), b.brlen.data(), b.er.data(), b.pi.data(),
+                               b.alpha.data(), num_rates, ll, &outs),
+                 "lh_eval_batch");
+        const auto t2 = now();
+        p1_dev += secs(t1, t2);
+        for (std::size_t i = 0; i < m; ++i) {
+          if (!std::isfinite(ll[i] - tb.lik[i])) {
+            rng.discard((unsigned long long)raw);
+            continue;
+          }
+          SampleRow(s, fwd.data() + i * FS, rng);
+          const auto r = ids.emplace(s.naive_seq, (int32_t)distinct.size());
+          if (r.second) distinct.push_back(s.naive_seq);
+          row_id[off - first + i] = r.first->second;
+        }
+        p1_collect += secs(t2, now());
+      }
+    }
+    // counts, and the limit: the most drawn, ties by first appearance, kept in first-appearance order
+    std::vector<int64_t> count(distinct.size(), 0);
+    for (int32_t id : row_id)
+      if (id >= 0) ++count[id];
+    draws_distinct = (int64_t)distinct.size();
+    Require(!distinct.empty(), "naive-probabilities pipeline: no row with a finite weight");
+    std::vector<int32_t> keep(distinct.size());
+    for (std::size_t k = 0; k < keep.size(); ++k) keep[k] = (int32_t)k;
+    if ((int64_t)distinct.size() > max_candidates) {
+      std::stable_sort(keep.begin(), keep.end(), [&](int32_t a, int32_t b) { return count[a] > count[b]; });
+      keep.resize(max_candidates);
+      std::sort(keep.begin(), keep.end());
+      dropped = draws_distinct - max_candidates;
+    }
+    std::vector<int32_t> new_id(distinct.size(), -1);
+    for (std::size_t k = 0; k < keep.size(); ++k) {
+      new_id[keep[k]] = (int32_t)k;
+      t.seqs.push_back(distinct[keep[k]]);
+      t.count.push_back(count[keep[k]]);
+    }
+    for (int32_t& id : row_id)
+      if (id >= 0) id = new_id[id];
+    t.sampled = true;
+  } else {
+    t.seqs = ReadCandidateFile(candidates_path, L);
+  }
+
+  p1_total = secs(t_p1, now());
+  // pass 2: exact probabilities
+  const auto t_p2 = now();
+  const int K = (int)t.seqs.size();
+  const std::vector<uint8_t> bytes = EncodeSeqs(t.seqs, alphabet_, L);
+  t.log_prior.assign(K, 0.0);
+  CheckHip(lh_family_set_candidates(family_, K, bytes.data(), t.log_prior.data()), "lh_family_set_candidates");
+  p2_prior = secs(t_p2, now());
+  std::vector<double> total(K, 0.0), wsum(K), lw(U);
+  double mx = -INFINITY, s1 = 0.0, s2 = 0.0;
+  std::size_t skipped = 0;
+  for (std::size_t off = first; off < N; off += kBatch) {
+    const std::size_t m = std::min(kBatch, N - off);
+    const auto t0 = now();
+    TableBatch tb = FlattenTable(table, off, off + m, false, true, input_path);
+    const DeviceBatch& b = tb.dev;
+    const auto t1 = now();
+    p2_parse += secs(t0, t1);
+    std::vector<double> ll(m);
+    double st[3];
+    lh_candidate_outputs outs{tb.lik.data(), ll.data(), nullptr, wsum.data(), st};
+    CheckHip(lh_eval_candidates_batch(family_, b.n, b.n_tips, b.max_depth, b.ops.data(), b.brlen.data(), b.er.data(),
+                                      b.pi.data(), b.alpha.data(), num_rates, &outs),
+             "lh_eval_candidates_batch");
+    p2_dev += secs(t1, now());
+    for (std::size_t i = 0; i < m; ++i) {
+      lw[off - first + i] = ll[i] - tb.lik[i];
+      if (!std::isfinite(lw[off - first + i])) ++skipped;
+      if (!ll1.empty() && std::memcmp(&ll[i], &ll1[off - first + i], sizeof(double)) != 0)
+        throw std::runtime_error("naive-probabilities pipeline: the two passes' log-likelihoods differ at row " +
+                                 std::to_string(off + i));
+    }
+    if (!std::isfinite(st[0])) continue;
+    const double nm = std::max(mx, st[0]);
+    const double fo = std::isfinite(mx) ? std::exp(mx - nm) : 0.0, fn = std::exp(st[0] - nm);
+    for (int k = 0; k < K; ++k) total[k] = total[k] * fo + wsum[k] * fn;
+    s1 = s1 * fo + st[1] * fn;
+    s2 = s2 * fo * fo + st[2] * fn * fn;
+    mx = nm;
+  }
+  Require(s1 > 0.0, "naive-probabilities pipeline: no row with a finite weight");
+  p2_total = secs(t_p2, now());
+  if (timing)
+    std::fprintf(stderr,
+                 "[RunNaiveProbsPipeline] %zu rows; pass 1 (%s): parse %.4f s, device %.4f s, collect %.4f s, total %.4f s; "
+                 "pass 2 (%d candidates): priors %.4f s, parse %.4f s, device %.4f s, total %.4f s\n",
+                 U, !candidates_path.empty() ? "skipped" : device_sampler_ ? "device draws" : "host draws", p1_parse, p1_dev,
+                 p1_collect, p1_total, K, p2_prior, p2_parse, p2_dev, p2_total);
+  t.prob.resize(K);
+  double covered = 0.0;
+  for (int k = 0; k < K; ++k) {
+    t.prob[k] = total[k] / s1;
+    covered += t.prob[k];
+  }
+  if (t.sampled) {  // self-normalised sampled frequencies, weights as K5 / K6b form them, summed in row order
+    double lmax = -INFINITY;
+    for (double x : lw)
+      if (std::isfinite(x)) lmax = std::max(lmax, x);
+    std::vector<double> f(K, 0.0);
+    double W = 0.0;
+    for (std::size_t i = 0; i < U; ++i) {
+      if (!std::isfinite(lw[i])) continue;
+      const double w = std::exp(lw[i] - lmax);
+      W += w;
+      if (row_id[i] >= 0) f[row_id[i]] += w;
+    }
+    t.freq.resize(K);
+    for (int k = 0; k < K; ++k) t.freq[k] = f[k] / W;
+  }
+  std::ofstream naive(output_prefix + ".naive.tsv"), aa(output_prefix + ".aa.fasta"), dnamap(output_prefix + ".dnamap"),
+      summary(output_prefix + ".summary.tsv");
+  Require(naive.good() && aa.good() && dnamap.good() && summary.good(), "Can't write " + output_prefix + ".*");
+  WriteNaiveTable(naive, t);
+  WriteAaFasta(aa, t);
+  WriteDnaMap(dnamap, t);
+  char buf[64], cov[64];
+  std::snprintf(buf, sizeof buf, "%.17g", s1 * s1 / s2);
+  std::snprintf(cov, sizeof cov, "%.17g", covered);
+  summary << "key\tvalue\nrows_used\t" << (U - skipped) << "\nrows_skipped_nonfinite\t" << skipped << "\nkish_ess\t" << buf
+          << "\ndraws_distinct\t" << (draws_distinct < 0 ? std::string("NA") : std::to_string(draws_distinct))
+          << "\ncandidates\t" << K << "\ncandidates_dropped\t" << dropped << "\ncovered_mass\t" << cov << "\n";
 }
 
 }  // namespace linearham

@@ -112,6 +112,18 @@ class PhyloHMM : public HMM {
   /// most 49 152 rows are combined in file order.  Writes <prefix>.sites.tsv, .genes.tsv and .summary.tsv.
   void RunMarginalsPipeline(const std::string& input_path, const std::string& output_prefix, int num_rates,
                             double burnin_frac);
+  /// Exact log P(s | data, tree) of every candidate naive sequence (ACGTN strings of the alignment's length) for the
+  /// current tree (K6: lh_family_set_candidates + lh_eval_candidates_batch); -inf for a sequence no state path writes.
+  /// After InitializePhyloParameters.  log_prior (optional) receives log P_HMM(s).
+  std::vector<double> CandidatePosterior(const std::vector<std::string>& seqs, double* loglik,
+                                         std::vector<double>* log_prior = nullptr);
+  /// Exact posterior probabilities of naive sequences over a RevBayes table, with RunMarginalsPipeline's burn-in and
+  /// weights.  The candidates are the distinct naive sequences drawn for the used rows (pass 1: K0-K2 + K4 + K6c on the
+  /// same std::mt19937 stream as RunPipeline), the `max_candidates` most drawn of them, or the sequences of
+  /// `candidates_path` when it is not empty; pass 2 scores them exactly (K6).  Writes <prefix>.naive.tsv, .aa.fasta,
+  /// .dnamap and .summary.tsv.
+  void RunNaiveProbsPipeline(const std::string& input_path, const std::string& output_prefix, int num_rates,
+                             double burnin_frac, const std::string& candidates_path, int max_candidates = 65536);
   static void WriteSiteTable(std::ostream& o, const NaiveMarginalsResult& m);
   static void WriteGeneTable(std::ostream& o, const NaiveMarginalsResult& m);
   void SampleStatesWithWords(const uint32_t* words, int n_words, std::vector<int32_t>& device_states,

@@ -1,13 +1,16 @@
 // Test/bench-facing C entry points of liblinearham_host.so: construct the C++ host classes and dump
 // their accessors as JSON so that the pytest suite can compare them with the reference's goldens
 // (test/test.cpp) -- the role the Catch binary plays upstream.
+#include <chrono>
 #include <cmath>
+#include <unordered_map>
 #include <cstring>
 #include <iomanip>
 #include <sstream>
 #include <random>
 #include <string>
 
+#include "NaiveProbs.hpp"
 #include "PhyloHMM.hpp"
 #include "SimpleHMM.hpp"
 
@@ -274,6 +277,116 @@ int lhh_run_marginals_pipeline(void* h, const char* input_path, const char* outp
                                double burnin_frac) {
   return Guard([&] {
     dynamic_cast<PhyloHMM&>(*static_cast<HMM*>(h)).RunMarginalsPipeline(input_path, output_prefix, num_rates, burnin_frac);
+  });
+}
+
+// PhyloHMM::CandidatePosterior: seqs = K candidates of n_sites characters, back to back; log_post [K], log_prior [K]
+// (may be NULL), *loglik.
+int lhh_phylo_candidate_posterior(void* h, int K, const char* seqs, double* log_post, double* log_prior, double* loglik) {
+  return Guard([&] {
+    PhyloHMM& p = dynamic_cast<PhyloHMM&>(*static_cast<HMM*>(h));
+    const std::size_t L = p.msa().cols();
+    std::vector<std::string> v;
+    for (int k = 0; k < K; ++k) v.emplace_back(seqs + k * L, L);
+    std::vector<double> lp;
+    const std::vector<double> lc = p.CandidatePosterior(v, loglik, &lp);
+    std::copy(lc.begin(), lc.end(), log_post);
+    if (log_prior) std::copy(lp.begin(), lp.end(), log_prior);
+  });
+}
+
+// K6c against HMM::ApplySampledStates on the same states [n][lh_sample_states()]: dev_seqs [n][L] (0..4) and hash [n]
+// from lh_naive_sequences, host_seqs [n][L] the host's naive_seq characters.
+int lhh_phylo_naive_sequences(void* h, int n, const int32_t* states, uint8_t* dev_seqs, uint64_t* hash, char* host_seqs) {
+  return Guard([&] {
+    PhyloHMM& p = dynamic_cast<PhyloHMM&>(*static_cast<HMM*>(h));
+    lh_family* f = p.family();
+    const std::size_t L = p.msa().cols(), S = (std::size_t)lh_sample_states(f);
+    if (S == 0) throw std::runtime_error("the family has no device sampler");
+    if (lh_naive_sequences(f, n, states, dev_seqs, hash)) throw std::runtime_error(lh_last_error());
+    HMM::RowSampler s;
+    for (int i = 0; i < n; ++i) {
+      p.ApplySampledStates(s, states + i * S);
+      std::copy(s.naive_seq.begin(), s.naive_seq.end(), host_seqs + i * L);
+    }
+  });
+}
+
+// The host way of collecting draws, for the benchmark: HMM::ApplySampledStates on states [n][S] and a map from the naive
+// sequence strings to ids in first-appearance order; *n_distinct, and the seconds it took in *seconds.
+int lhh_phylo_apply_states_map(void* h, int n, const int32_t* states, int* n_distinct, double* seconds) {
+  return Guard([&] {
+    PhyloHMM& p = dynamic_cast<PhyloHMM&>(*static_cast<HMM*>(h));
+    const std::size_t S = (std::size_t)lh_sample_states(p.family());
+    const auto t0 = std::chrono::steady_clock::now();
+    std::unordered_map<std::string, int> ids;
+    std::vector<int> row(n);
+    HMM::RowSampler s;
+    for (int i = 0; i < n; ++i) {
+      p.ApplySampledStates(s, states + i * S);
+      row[i] = ids.emplace(s.naive_seq, (int)ids.size()).first->second;
+    }
+    *seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    *n_distinct = (int)ids.size();
+  });
+}
+
+int lhh_run_naive_probs_pipeline(void* h, const char* input_path, const char* output_prefix, int num_rates,
+                                 double burnin_frac, const char* candidates_path, int max_candidates) {
+  return Guard([&] {
+    dynamic_cast<PhyloHMM&>(*static_cast<HMM*>(h))
+        .RunNaiveProbsPipeline(input_path, output_prefix, num_rates, burnin_frac, candidates_path ? candidates_path : "",
+                               max_candidates);
+  });
+}
+
+// The naive-probability writers and helpers on caller data (no GPU).  seqs: K lines; count / freq NULL: no sampled
+// columns (NA).  *out: the .naive.tsv text, then a line "\x1e", the .aa.fasta text, "\x1e", the .dnamap text.
+int lhh_naive_probs_write(int K, const char* seqs, const double* prob, const double* log_prior, const int64_t* count,
+                          const double* freq, const char** out) {
+  return Guard([&] {
+    NaiveProbsTable t;
+    std::istringstream in(seqs);
+    std::string line;
+    while (std::getline(in, line))
+      if (!line.empty()) t.seqs.push_back(line);
+    if ((int)t.seqs.size() != K) throw std::runtime_error("lhh_naive_probs_write: K does not match the sequences");
+    t.prob.assign(prob, prob + K);
+    t.log_prior.assign(log_prior, log_prior + K);
+    if (count && freq) {
+      t.sampled = true;
+      t.count.assign(count, count + K);
+      t.freq.assign(freq, freq + K);
+    }
+    std::ostringstream o;
+    WriteNaiveTable(o, t);
+    o << "\x1e\n";
+    WriteAaFasta(o, t);
+    o << "\x1e\n";
+    WriteDnaMap(o, t);
+    g_out = o.str();
+    *out = g_out.c_str();
+  });
+}
+int lhh_translate(const char* dna, const char** out) {
+  return Guard([&] {
+    g_out = TranslateDna(dna);
+    *out = g_out.c_str();
+  });
+}
+int lhh_repr_double(double v, const char** out) {
+  return Guard([&] {
+    g_out = ReprDouble(v);
+    *out = g_out.c_str();
+  });
+}
+// ReadCandidateFile: the sequences, one per line
+int lhh_read_candidates(const char* path, int n_sites, const char** out) {
+  return Guard([&] {
+    std::string s;
+    for (const std::string& q : ReadCandidateFile(path, n_sites)) s += q + "\n";
+    g_out = s;
+    *out = g_out.c_str();
   });
 }
 

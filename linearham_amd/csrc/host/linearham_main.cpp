@@ -1,8 +1,10 @@
 // `linearham` command line (same sub-commands and flag names as src/linearham.cpp:268-455 of the
 // reference, without TCLAP): --compute-logl | --sample | --pipeline; plus --asr, the per-tree body of
 // scripts/run_bootstrap_asr_ess.R:48-104 on a --pipeline output table, and --marginals / --marginals-pipeline, the exact
-// posterior of the naive sequence (one tree / importance-weighted over a RevBayes table).
+// posterior of the naive sequence (one tree / importance-weighted over a RevBayes table), and --naive-probs /
+// --naive-probs-pipeline, exact posterior probabilities of naive sequences (tabulate_naive_probs.py's table).
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <iostream>
@@ -12,6 +14,7 @@
 #include <thread>
 #include <vector>
 
+#include "NaiveProbs.hpp"
 #include "PhyloHMM.hpp"
 
 namespace {
@@ -55,12 +58,17 @@ int main(int argc, char** argv) {
   try {
     if (argc < 2 || std::string(argv[1]) == "-h" || std::string(argv[1]) == "--help") {
       std::cout << "A Phylo-HMM implementation for B cell receptor sequence analysis.\n"
-                   "USAGE: linearham {--compute-logl|--sample|--pipeline|--asr|--marginals|--marginals-pipeline} --yaml-path <string> "
+                   "USAGE: linearham {--compute-logl|--sample|--pipeline|--asr|--marginals|--marginals-pipeline|--naive-probs|--naive-probs-pipeline} --yaml-path <string> "
                    "--cluster-ind <int> --hmm-param-dir <string> [--seed <int>] [--num-rates <int>] [--extended-range <0|1>] "
                    "[--devices <a,b,...>] ...\n"
                    "  --marginals: the arguments of --compute-logl; prints the per-site naive-base table and the gene table\n"
                    "  --marginals-pipeline --input-path <RevBayes table> --output-path <prefix> [--burnin-frac <f>]: writes\n"
-                   "    <prefix>.sites.tsv, <prefix>.genes.tsv and <prefix>.summary.tsv (one device)\n";
+                   "    <prefix>.sites.tsv, <prefix>.genes.tsv and <prefix>.summary.tsv (one device)\n"
+                   "  --naive-probs: the arguments of --compute-logl and --candidates-path <file>; prints the exact posterior\n"
+                   "    probability of every candidate naive sequence for that tree\n"
+                   "  --naive-probs-pipeline --input-path <RevBayes table> --output-path <prefix> [--burnin-frac <f>]\n"
+                   "    [--candidates-path <file>] [--max-candidates <n>]: writes <prefix>.naive.tsv, <prefix>.aa.fasta,\n"
+                   "    <prefix>.dnamap and <prefix>.summary.tsv (one device)\n";
       return argc < 2 ? EXIT_FAILURE : EXIT_SUCCESS;
     }
     const auto t_main = std::chrono::steady_clock::now();
@@ -69,7 +77,8 @@ int main(int argc, char** argv) {
     const std::string subcmd = argv[1];
     const Args a = Parse(argc, argv, 2);
     if (subcmd != "--compute-logl" && subcmd != "--sample" && subcmd != "--pipeline" && subcmd != "--asr" &&
-        subcmd != "--marginals" && subcmd != "--marginals-pipeline")
+        subcmd != "--marginals" && subcmd != "--marginals-pipeline" && subcmd != "--naive-probs" &&
+        subcmd != "--naive-probs-pipeline")
       throw std::invalid_argument("'" + subcmd + "' is not a valid subcommand.");
     const std::string yaml_path = a.one("yaml-path");
     const int cluster_ind = std::stoi(a.one("cluster-ind"));
@@ -87,8 +96,8 @@ int main(int argc, char** argv) {
         device_list.push_back(std::stoi(devs.substr(pos, comma - pos)));
         pos = comma + 1;
       }
-      if (device_list.size() > 1 && subcmd == "--marginals-pipeline")
-        throw std::invalid_argument("--marginals-pipeline runs on one device: --devices may list only one");
+      if (device_list.size() > 1 && (subcmd == "--marginals-pipeline" || subcmd == "--naive-probs-pipeline"))
+        throw std::invalid_argument(subcmd + " runs on one device: --devices may list only one");
       if (device_list.size() > 1 && subcmd != "--pipeline")
         std::fprintf(stderr, "linearham: %s evaluates on one device; of --devices only device %d is used\n", subcmd.c_str(),
                      device_list[0]);
@@ -128,6 +137,12 @@ int main(int argc, char** argv) {
                                           std::stod(a.opt("burnin-frac", "0")));
       return EXIT_SUCCESS;
     }
+    if (subcmd == "--naive-probs-pipeline") {
+      phylo_hmm_ptr->RunNaiveProbsPipeline(a.one("input-path"), a.one("output-path"), num_rates,
+                                           std::stod(a.opt("burnin-frac", "0")), a.opt("candidates-path", ""),
+                                           std::stoi(a.opt("max-candidates", "65536")));
+      return EXIT_SUCCESS;
+    }
     if (subcmd == "--asr") {
       phylo_hmm_ptr->RunAsr(a.one("input-path"), a.one("output-path"), (uint64_t)std::stoll(a.opt("seed", "0")));
       return EXIT_SUCCESS;
@@ -137,6 +152,13 @@ int main(int argc, char** argv) {
     phylo_hmm_ptr->InitializePhyloEmission();
     if (subcmd == "--compute-logl") {
       std::cout << phylo_hmm_ptr->LogLikelihood() << std::endl;
+    } else if (subcmd == "--naive-probs") {
+      linearham::NaiveProbsTable t;
+      t.seqs = linearham::ReadCandidateFile(a.one("candidates-path"), (int)phylo_hmm_ptr->msa().cols());
+      double ll = 0;
+      const std::vector<double> lc = phylo_hmm_ptr->CandidatePosterior(t.seqs, &ll, &t.log_prior);
+      for (double x : lc) t.prob.push_back(std::exp(x));
+      linearham::WriteNaiveTable(std::cout, t, false);
     } else if (subcmd == "--marginals") {
       const linearham::PhyloHMM::NaiveMarginalsResult m = phylo_hmm_ptr->NaiveMarginals();
       linearham::PhyloHMM::WriteSiteTable(std::cout, m);

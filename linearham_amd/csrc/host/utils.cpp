@@ -103,6 +103,7 @@ const HostOptions& host_options() {
     o.pipeline_timing = std::getenv("LH_PIPELINE_TIMING") != nullptr;
     o.host_sampling = std::getenv("LH_HOST_SAMPLING") != nullptr;
     if (const char* e = std::getenv("LH_HOST_THREADS")) o.host_threads = std::max(1, std::atoi(e));
+    if (const char* e = std::getenv("LH_PIPELINE_BATCH")) o.pipeline_batch = std::max(1, std::atoi(e));
     return o;
   }();
   return opts;

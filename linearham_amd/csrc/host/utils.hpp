@@ -74,6 +74,7 @@ struct HostOptions {
   bool pipeline_timing = false;  // LH_PIPELINE_TIMING: stage times of RunPipeline / RunASR / main on stderr
   bool host_sampling = false;    // LH_HOST_SAMPLING: HMM::SampleRow on the host even where the device sampler could run
   int host_threads = 0;          // LH_HOST_THREADS=<n>: worker threads per host stage (0: from the affinity mask)
+  int pipeline_batch = 0;        // LH_PIPELINE_BATCH=<n>: rows per batch of RunNaiveProbsPipeline (0: 49 152)
 };
 const HostOptions& host_options();
 

@@ -33,6 +33,7 @@ const DebugOptions& debug_options() {
     o.k1_segments = set("LH_K1_SEGMENTS");
     o.k1_seg_waves = num("LH_K1_SEG_WAVES", o.k1_seg_waves);
     o.k1_no_fuse = set("LH_K1_NO_FUSE");
+    o.collect_hash_bits = std::min(64, std::max(1, num("LH_COLLECT_HASH_BITS", o.collect_hash_bits)));
     return o;
   }();
   return opts;
@@ -183,6 +184,17 @@ struct CandidateWs {
   DevBuf loglik, weights, stats, partial, lem, base;  // K6b's arrays the caller does not hand in
 };
 
+// K6c (lh_collect.hip): the naive sequences of the last lh_eval_draw_batch / lh_naive_sequences batch, and the
+// candidate store lh_draws_resolve appends to (store[cur], K candidates; grown by copying into the other buffer).
+struct CollectWs {
+  DevBuf seqs, hash, flag, cand, pairs, states;
+  DevBuf gather_rows, gather_out;  // lh_draws_rows_read
+  DevBuf store[2];
+  int cur = 0;
+  int32_t K = 0, n_last = -1;
+  size_t cap = 0;  // candidates store[cur] holds room for
+};
+
 // Device copies of the host-pointer entry points' arrays.  The entry points share them on purpose: each waits for the device
 // before it fills them and before it returns, and a handle is driven by one thread at a time.
 struct HostInputs {
@@ -229,6 +241,7 @@ struct lh_family {
   AsrWs asr;
   PosteriorWs post;
   CandidateWs cand;
+  CollectWs collect;
   // forward arrays that stay on the device, shared by K4 and K5 in both their forms: K4 draws from them, K5 overwrites
   // them with the posteriors (calls on a handle do not overlap: they also share the workspace)
   DevBuf forward_dev;
@@ -240,6 +253,7 @@ struct lh_family {
   KernelTimer<3> eval_timer;  // model, prune, forward
   KernelTimer<1> asr_timer, post_timer;
   KernelTimer<1> prior_timer, cand_timer;  // K6a, K6b
+  KernelTimer<1> collect_timer;             // K6c
   bool extended = false;  // lh_family_set_extended_range
   bool have_sampler = false;
   lh::DevSampler sampler{};  // device pointers inside (arena)
@@ -1400,25 +1414,25 @@ int lh_eval_sample_batch_device(lh_family* f, int32_t n, int32_t T, int32_t max_
   return 0;
 }
 
-int lh_eval_sample_batch(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops,
-                         const double* brlen, const double* er, const double* pi, const double* alpha, int32_t R,
-                         const uint32_t* words, double* loglik, double* rates, int32_t* states) {
-  if (int rc = check_batch(f, "lh_eval_sample_batch", n, T, R, max_depth, true)) return rc > 0;
-  DeviceGuard guard(f);
-  if (!ops || !brlen || !er || !pi || !alpha || !words || !loglik || !states) return fail("lh_eval_sample_batch: null array");
+}  // extern "C"
+
+namespace {
+
+// What lh_eval_sample_batch and lh_eval_draw_batch share: the host arrays staged, K0-K2 with the forward arrays kept on
+// the device (rates into out.rates when want_rates), K4's draws into out.states, loglik into out.loglik.  With `sync` the
+// device is waited for after the evaluation and after the sampling; stamps[4] receive the times after the buffers, the
+// copies in, the evaluation and the sampling.
+int sample_host_batch(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops, const double* brlen,
+                      const double* er, const double* pi, const double* alpha, int32_t R, const uint32_t* words,
+                      bool want_rates, bool sync, std::chrono::steady_clock::time_point* stamps) {
   const size_t nodes = 2 * (size_t)T - 2, n_ops = (size_t)T - 2, FS = f->host.forward_size;
-  static const bool timing = lh::debug_options().sample_timing;  // stage times of every call, on stderr
-  auto now = [] { return std::chrono::steady_clock::now(); };
-  auto t0 = now();
   const lh::DevSampler& smp = f->sampler;
   HostInputs& in = f->in;
   HostOutputs& out = f->out;
-  const size_t ll_bytes = sizeof(double) * n, rates_bytes = sizeof(double) * R * n,
-               states_bytes = sizeof(int32_t) * smp.states_per_sample * (size_t)n;
-  if (out.loglik.ensure(ll_bytes) || out.rates.ensure(rates_bytes) || out.states.ensure(states_bytes) ||
-      f->forward_dev.ensure(sizeof(double) * FS * n))
+  if (out.loglik.ensure(sizeof(double) * n) || (want_rates && out.rates.ensure(sizeof(double) * R * n)) ||
+      out.states.ensure(sizeof(int32_t) * smp.states_per_sample * (size_t)n) || f->forward_dev.ensure(sizeof(double) * FS * n))
     return 1;
-  auto t2 = now();
+  stamps[0] = std::chrono::steady_clock::now();
   if (stage_inputs(f, {{ops, sizeof(int32_t) * 4 * n_ops * n, &in.ops},
                        {brlen, sizeof(double) * nodes * n, &in.brlen},
                        {er, sizeof(double) * 6 * n, &in.er},
@@ -1426,22 +1440,45 @@ int lh_eval_sample_batch(lh_family* f, int32_t n, int32_t T, int32_t max_depth, 
                        {alpha, sizeof(double) * n, &in.alpha},
                        {words, sizeof(uint32_t) * smp.words_per_sample * (size_t)n, &in.words}}))
     return 1;
-  auto t3 = now();
+  stamps[1] = std::chrono::steady_clock::now();
   double* fwd = f->forward_dev.get<double>();
-  lh_eval_outputs outs{out.rates.get<double>(), nullptr, fwd, nullptr};
+  lh_eval_outputs outs{want_rates ? out.rates.get<double>() : nullptr, nullptr, fwd, nullptr};
   if (lh_eval_batch_device(f, n, T, max_depth, in.ops.get<const int32_t>(), in.brlen.get<const double>(),
                            in.er.get<const double>(), in.pi.get<const double>(), in.alpha.get<const double>(), R,
                            out.loglik.get<double>(), &outs, nullptr))
     return 1;
-  if (timing) LH_HIP(hipDeviceSynchronize());
-  auto t4 = now();
+  if (sync) LH_HIP(hipDeviceSynchronize());
+  stamps[2] = std::chrono::steady_clock::now();
   lh::launch_sample(smp, f->sampler_dev, n, fwd, FS, in.words.get<const uint32_t>(), smp.words_per_sample,
                     out.states.get<int32_t>(), nullptr);
   LH_HIP(hipGetLastError());
-  if (timing) LH_HIP(hipDeviceSynchronize());
-  auto t5 = now();
+  if (sync) LH_HIP(hipDeviceSynchronize());
+  stamps[3] = std::chrono::steady_clock::now();
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int lh_eval_sample_batch(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops,
+                         const double* brlen, const double* er, const double* pi, const double* alpha, int32_t R,
+                         const uint32_t* words, double* loglik, double* rates, int32_t* states) {
+  if (int rc = check_batch(f, "lh_eval_sample_batch", n, T, R, max_depth, true)) return rc > 0;
+  DeviceGuard guard(f);
+  if (!ops || !brlen || !er || !pi || !alpha || !words || !loglik || !states) return fail("lh_eval_sample_batch: null array");
+  const size_t nodes = 2 * (size_t)T - 2;
+  static const bool timing = lh::debug_options().sample_timing;  // stage times of every call, on stderr
+  auto now = [] { return std::chrono::steady_clock::now(); };
+  auto t0 = now();
+  std::chrono::steady_clock::time_point st[4];
+  if (sample_host_batch(f, n, T, max_depth, ops, brlen, er, pi, alpha, R, words, true, timing, st)) return 1;
+  const auto t2 = st[0], t3 = st[1], t4 = st[2], t5 = st[3];
   if (!valid_schedules(ops, (size_t)n, T, (int)nodes, max_depth)) return refuse_schedules(f, "lh_eval_sample_batch");
   auto t6 = now();
+  HostOutputs& out = f->out;
+  const size_t ll_bytes = sizeof(double) * n, rates_bytes = sizeof(double) * R * n,
+               states_bytes = sizeof(int32_t) * f->sampler.states_per_sample * (size_t)n;
   if (copy_back(f, "lh_eval_sample_batch",
                 {{loglik, out.loglik.get(), ll_bytes}, {rates, out.rates.get(), rates_bytes},
                  {states, out.states.get(), states_bytes}}))
@@ -1831,6 +1868,225 @@ int lh_candidates_profile_read(lh_family* f, double* ms, int64_t* n_launches) {
     ms[1] = b;
   }
   return 0;
+}
+
+// ---- K6c: naive sequences of sampled states, and the candidate store (lh_collect.hip) ----
+
+}  // extern "C"
+
+namespace {
+
+// K6c's tables: pointers the family already holds (the twin's segments and junction matrices, K4's state classes, K6a's
+// column map).  Fails when the family has no sampler or no twin.
+int collect_tables(lh_family* f, const std::string& who, lh::CollectTables* t) {
+  if (!f->have_sampler) return fail(who + ": lh_family_set_sampler has not been called");
+  if (f->host.n_seqs < 1) return fail(who + ": family was created without an MSA (forward-only)");
+  if (!f->cand.twin) return fail(who + ": no column tables for this family: " + f->cand.twin_error);
+  const lh::DevFamily& w = f->cand.twin->host;
+  *t = lh::CollectTables{};
+  t->L = f->host.n_sites;
+  t->has_d = f->host.has_d;
+  t->states_per_sample = f->sampler.states_per_sample;
+  t->n_cols = f->host.n_xmsa;
+  t->seg_scale = w.idx_byte_offsets ? 8 : 1;
+  t->seg_sentinel = w.n_ucol * t->seg_scale;
+  auto seg = [](const lh::DevSegments& d) { return lh::CollectSegments{d.n_genes, d.n_chunks, d.inds_c}; };
+  t->vg = seg(w.vgerm);
+  t->jg = seg(w.jgerm);
+  if (w.has_d) t->dg = seg(w.dgerm);
+  auto junc = [](const lh::DevJunction& d, const lh::DevSampleJunction& s) {
+    return lh::CollectJunction{d.n_rows, d.n_left, d.n_right, d.left_pad, d.right_pad, s.n_states,
+                               d.left_xmsa, d.right_xmsa, d.nti_xmsa, s.state_class};
+  };
+  t->vd = junc(w.vd, f->sampler.vd);
+  if (w.has_d) t->dj = junc(w.dj, f->sampler.dj);
+  t->jcols = w.jcols;
+  t->n_jcols = w.n_jcols;
+  t->col_site = f->cand.col_site;
+  t->col_base = f->cand.col_base;
+  const int bits = lh::debug_options().collect_hash_bits;
+  t->hash_mask = bits >= 64 ? ~0ull : ((1ull << bits) - 1);
+  if (lh::collect_lds_bytes(t->L) > 160 * 1024) return fail(who + ": alignment too long for the assembly kernel's LDS");
+  return 0;
+}
+
+// assembles the batch's rows into the handle's workspace (seqs [n][L], hash [n]) from device states
+int collect_launch(lh_family* f, const lh::CollectTables& t, int n, const int32_t* states, hipStream_t stream) {
+  CollectWs& c = f->collect;
+  if (c.seqs.ensure((size_t)n * t.L) || c.hash.ensure(sizeof(uint64_t) * n)) return 1;
+  if (f->profile && f->collect_timer.begin(stream)) return 1;
+  lh::launch_collect(t, n, states, c.seqs.get<uint8_t>(), c.hash.get<uint64_t>(), stream);
+  LH_HIP(hipGetLastError());
+  if (f->profile && f->collect_timer.end(stream)) return 1;
+  c.n_last = n;
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int lh_eval_draw_batch_device(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops,
+                              const double* brlen, const double* er, const double* pi, const double* alpha, int32_t R,
+                              const uint32_t* words, double* loglik, uint64_t* hash, int32_t* states, void* hip_stream) {
+  const std::string W = "lh_eval_draw_batch_device";
+  if (int rc = check_batch(f, W, n, T, R, max_depth, true)) return rc > 0;
+  DeviceGuard guard(f);
+  lh::CollectTables t;
+  if (collect_tables(f, W, &t)) return 1;
+  if (!words || !loglik || !hash) return fail(W + ": null array");
+  CollectWs& c = f->collect;
+  if (!states) {
+    if (c.states.ensure(sizeof(int32_t) * t.states_per_sample * (size_t)n)) return 1;
+    states = c.states.get<int32_t>();
+  }
+  if (lh_eval_sample_batch_device(f, n, T, max_depth, ops, brlen, er, pi, alpha, R, words, loglik, nullptr, states,
+                                  hip_stream))
+    return 1;
+  hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+  if (collect_launch(f, t, n, states, stream)) return 1;
+  LH_HIP(hipMemcpyAsync(hash, c.hash.get(), sizeof(uint64_t) * n, hipMemcpyDeviceToDevice, stream));
+  return 0;
+}
+
+int lh_eval_draw_batch(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops, const double* brlen,
+                       const double* er, const double* pi, const double* alpha, int32_t R, const uint32_t* words,
+                       double* loglik, uint64_t* hash, int32_t* states) {
+  const std::string W = "lh_eval_draw_batch";
+  if (int rc = check_batch(f, W, n, T, R, max_depth, true)) return rc > 0;
+  DeviceGuard guard(f);
+  lh::CollectTables t;
+  if (collect_tables(f, W, &t)) return 1;
+  if (!ops || !brlen || !er || !pi || !alpha || !words || !loglik || !hash) return fail(W + ": null array");
+  std::chrono::steady_clock::time_point st[4];
+  if (sample_host_batch(f, n, T, max_depth, ops, brlen, er, pi, alpha, R, words, false, false, st)) return 1;
+  HostOutputs& out = f->out;
+  if (collect_launch(f, t, n, out.states.get<const int32_t>(), nullptr)) return 1;
+  if (!valid_schedules(ops, (size_t)n, T, 2 * T - 2, max_depth)) return refuse_schedules(f, W.c_str());
+  return copy_back(f, W.c_str(),
+                   {{loglik, out.loglik.get(), sizeof(double) * n},
+                    {hash, f->collect.hash.get(), sizeof(uint64_t) * n},
+                    {states, out.states.get(), sizeof(int32_t) * f->sampler.states_per_sample * (size_t)n}});
+}
+
+int lh_naive_sequences(lh_family* f, int32_t n, const int32_t* states, uint8_t* seqs, uint64_t* hash) {
+  const std::string W = "lh_naive_sequences";
+  if (!f) return fail(W + ": null family");
+  DeviceGuard guard(f);
+  lh::CollectTables t;
+  if (collect_tables(f, W, &t)) return 1;
+  if (n < 0) return fail(W + ": negative row count");
+  if (n == 0) return 0;
+  if (!states) return fail(W + ": null array");
+  CollectWs& c = f->collect;
+  const size_t sb = sizeof(int32_t) * t.states_per_sample * (size_t)n;
+  if (c.states.ensure(sb)) return 1;
+  LH_HIP(hipDeviceSynchronize());
+  LH_HIP(hipMemcpy(c.states.get(), states, sb, hipMemcpyHostToDevice));
+  if (collect_launch(f, t, n, c.states.get<const int32_t>(), nullptr)) return 1;
+  return copy_back(f, nullptr, {{seqs, c.seqs.get(), (size_t)n * t.L}, {hash, c.hash.get(), sizeof(uint64_t) * n}});
+}
+
+int lh_draws_resolve(lh_family* f, int32_t n, const int32_t* cand, int32_t* n_mismatch, int32_t* mismatch_rows) {
+  const std::string W = "lh_draws_resolve";
+  if (!f) return fail(W + ": null family");
+  DeviceGuard guard(f);
+  CollectWs& c = f->collect;
+  if (n != c.n_last) return fail(W + ": n differs from the last batch's row count");
+  if (n > 0 && !cand) return fail(W + ": null array");
+  const int L = f->host.n_sites;
+  // new candidates: ids K .. K_new - 1, each with a first row in this batch
+  int32_t K_new = c.K;
+  for (int32_t i = 0; i < n; ++i) {
+    if (cand[i] < -1) return fail(W + ": candidate id below -1");
+    K_new = std::max(K_new, cand[i] + 1);
+  }
+  std::vector<int32_t> first((size_t)(K_new - c.K), -1), pairs;
+  for (int32_t i = 0; i < n; ++i)
+    if (cand[i] >= c.K && first[cand[i] - c.K] < 0) first[cand[i] - c.K] = i;
+  for (size_t k = 0; k < first.size(); ++k) {
+    if (first[k] < 0) return fail(W + ": new candidate ids must be consecutive, each with a row of the batch");
+    pairs.push_back(c.K + (int32_t)k);
+    pairs.push_back(first[k]);
+  }
+  LH_HIP(hipDeviceSynchronize());
+  if ((size_t)K_new > c.cap) {  // grow the store, keeping what it holds
+    const size_t cap = std::max<size_t>({(size_t)K_new, 2 * c.cap, 256});
+    DevBuf& nb = c.store[c.cur ^ 1];
+    if (nb.ensure(cap * L)) return 1;
+    if (c.K > 0) LH_HIP(hipMemcpy(nb.get(), c.store[c.cur].get(), (size_t)c.K * L, hipMemcpyDeviceToDevice));
+    c.cur ^= 1;
+    c.cap = cap;
+  }
+  if (n == 0) {
+    if (n_mismatch) *n_mismatch = 0;
+    return 0;
+  }
+  if (c.cand.ensure(sizeof(int32_t) * n) || c.flag.ensure(n) || c.pairs.ensure(sizeof(int32_t) * pairs.size())) return 1;
+  LH_HIP(hipMemcpy(c.cand.get(), cand, sizeof(int32_t) * n, hipMemcpyHostToDevice));
+  if (!pairs.empty()) LH_HIP(hipMemcpy(c.pairs.get(), pairs.data(), sizeof(int32_t) * pairs.size(), hipMemcpyHostToDevice));
+  uint8_t* store = c.store[c.cur].get<uint8_t>();
+  lh::launch_collect_append((int)(pairs.size() / 2), n, L, K_new, c.pairs.get<const int32_t>(), c.seqs.get<const uint8_t>(),
+                            store, nullptr);
+  lh::launch_collect_verify(n, L, K_new, c.seqs.get<const uint8_t>(), c.cand.get<const int32_t>(), store,
+                            c.flag.get<uint8_t>(), nullptr);
+  LH_HIP(hipGetLastError());
+  std::vector<uint8_t> flag(n);
+  LH_HIP(hipMemcpy(flag.data(), c.flag.get(), n, hipMemcpyDeviceToHost));
+  c.K = K_new;
+  int32_t m = 0;
+  for (int32_t i = 0; i < n; ++i)
+    if (flag[i]) {
+      if (mismatch_rows) mismatch_rows[m] = i;
+      ++m;
+    }
+  if (n_mismatch) *n_mismatch = m;
+  return 0;
+}
+
+int lh_draws_rows_read(lh_family* f, int32_t n_rows, const int32_t* rows, uint8_t* seqs) {
+  const std::string W = "lh_draws_rows_read";
+  if (!f) return fail(W + ": null family");
+  DeviceGuard guard(f);
+  CollectWs& c = f->collect;
+  const size_t L = f->host.n_sites;
+  if (n_rows > 0 && (!rows || !seqs)) return fail(W + ": null array");
+  for (int32_t k = 0; k < n_rows; ++k)
+    if (rows[k] < 0 || rows[k] >= c.n_last) return fail(W + ": row outside the last batch");
+  if (n_rows <= 0) return 0;
+  if (c.gather_rows.ensure(sizeof(int32_t) * n_rows) || c.gather_out.ensure((size_t)n_rows * L)) return 1;
+  LH_HIP(hipDeviceSynchronize());
+  LH_HIP(hipMemcpy(c.gather_rows.get(), rows, sizeof(int32_t) * n_rows, hipMemcpyHostToDevice));
+  lh::launch_collect_gather(n_rows, c.n_last, (int)L, c.gather_rows.get<const int32_t>(), c.seqs.get<const uint8_t>(),
+                            c.gather_out.get<uint8_t>(), nullptr);
+  LH_HIP(hipGetLastError());
+  LH_HIP(hipMemcpy(seqs, c.gather_out.get(), (size_t)n_rows * L, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int lh_draws_candidates_read(lh_family* f, int32_t* K, uint8_t* seqs) {
+  if (!f) return fail("lh_draws_candidates_read: null family");
+  DeviceGuard guard(f);
+  CollectWs& c = f->collect;
+  if (K) *K = c.K;
+  if (seqs && c.K > 0) {
+    LH_HIP(hipDeviceSynchronize());
+    LH_HIP(hipMemcpy(seqs, c.store[c.cur].get(), (size_t)c.K * f->host.n_sites, hipMemcpyDeviceToHost));
+  }
+  return 0;
+}
+
+int lh_draws_reset(lh_family* f) {
+  if (!f) return fail("lh_draws_reset: null family");
+  f->collect.K = 0;
+  f->collect.n_last = -1;
+  return 0;
+}
+
+int lh_collect_profile_read(lh_family* f, double* ms, int64_t* n_launches) {
+  if (!f) return fail("null family");
+  DeviceGuard guard(f);
+  return f->collect_timer.read(ms, n_launches);
 }
 
 }  // extern "C"

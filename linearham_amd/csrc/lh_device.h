@@ -209,6 +209,42 @@ size_t candidate_lds_limit();  // largest n_vlem * 8 the scoring kernel takes
 void launch_candidates(const CandidateTables& t, int n, const double* lem, const double* loglik, const double* w,
                        double* base, double* log_cand, double* partial, hipStream_t stream);
 
+// K6c (lh_collect.hip): the naive sequences of K4's state rows.  Every pointer is one the family already holds: the K6
+// twin's germline segments and junction column matrices (its columns are the caller's one to one), K4's state classes
+// and K6a's caller column -> (site, naive base) map.
+struct CollectSegments {
+  int32_t n_genes, n_chunks;
+  const uint4* inds;  // DevSegments::inds_c of the twin
+};
+struct CollectJunction {
+  int32_t n_rows, n_left, n_right, left_pad, right_pad, n_states;
+  const int32_t *left_xmsa, *right_xmsa, *nti_xmsa;  // the twin's DevJunction tables (compact junction-column positions)
+  const int32_t* state_class;                         // DevSampleJunction::state_class
+};
+struct CollectTables {
+  int32_t L, has_d, states_per_sample, n_cols;
+  int32_t seg_scale, seg_sentinel;  // the twin's segment entries: column * seg_scale, padding = seg_sentinel
+  CollectSegments vg, dg, jg;
+  CollectJunction vd, dj;
+  const int32_t* jcols;  // the twin's compact junction-column list (caller columns)
+  int32_t n_jcols;
+  const int32_t* col_site;
+  const uint8_t* col_base;
+  uint64_t hash_mask;  // ~0, or the low LH_COLLECT_HASH_BITS bits (DebugOptions)
+};
+// seqs[n][L] (A,C,G,T,N = 0..4) and hash[n] of states[n][states_per_sample]
+void launch_collect(const CollectTables& t, int n, const int32_t* states, uint8_t* seqs, uint64_t* hash, hipStream_t stream);
+size_t collect_lds_bytes(int L);
+// flag[n]: 1 where row i differs from store[cand[i]] (cand[i] < 0: 0; cand[i] >= K: 1)
+void launch_collect_verify(int n, int L, int K, const uint8_t* seqs, const int32_t* cand, const uint8_t* store,
+                           uint8_t* flag, hipStream_t stream);
+// store[pairs[2p]] = seqs[pairs[2p + 1]] for p < n_pairs (candidate, row)
+void launch_collect_append(int n_pairs, int n, int L, int K, const int32_t* pairs, const uint8_t* seqs, uint8_t* store,
+                           hipStream_t stream);
+// out[q][..] = seqs[rows[q]][..] for q < n_rows (rows outside 0..n-1 read as N)
+void launch_collect_gather(int n_rows, int n, int L, const int32_t* rows, const uint8_t* seqs, uint8_t* out,
+                           hipStream_t stream);
+
 // P = I + U expm1(lambda * t*r) Uinv, clamped at 0 (K1's prologue).
 // e: lambda[4] | U[4][4] | Uinv[4][4]
 // (mode 0 is the stationary one, eigenvalue 0 -- K0a orders them so -- and contributes nothing: three modes are summed)
@@ -308,6 +344,8 @@ struct DebugOptions {
   bool k1_segments = false;    // LH_K1_SEGMENTS: the segmented tip table (large trees) on small trees too
   int k1_seg_waves = 4;        // LH_K1_SEG_WAVES=<4|5>: register budget of the segmented kernels
   bool k1_no_fuse = false;     // LH_K1_NO_FUSE: one workgroup per (sample, rate)
+  int collect_hash_bits = 64;  // LH_COLLECT_HASH_BITS=<n>: K6c's row hashes masked to n bits (tests: collisions common,
+                               // the exact resolution runs; results unchanged)
 };
 const DebugOptions& debug_options();
 

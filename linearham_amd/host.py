@@ -82,6 +82,95 @@ def read_marginals(prefix):
     return sb, genes, summary
 
 
+def read_naive_probs(prefix):
+    """The files RunNaiveProbsPipeline writes: dict(naive = list of row dicts of <prefix>.naive.tsv in rank order
+    (probability / log_prior floats, sampled_count int or None, sampled_frequency float or None), aa = [(name, p, aa)]
+    of <prefix>.aa.fasta, dnamap = {name: [(p, dna)]} of <prefix>.dnamap, summary = dict of <prefix>.summary.tsv)."""
+    return dict(naive=parse_naive_table(open(prefix + ".naive.tsv").read()), aa=_parse_aa(open(prefix + ".aa.fasta").read()),
+                dnamap=_parse_dnamap(open(prefix + ".dnamap").read()), summary=_parse_summary(open(prefix + ".summary.tsv").read()))
+
+
+def parse_naive_table(text):
+    """Rows of a .naive.tsv table (or of `linearham --naive-probs`'s output, which has no sampled columns)."""
+    lines = text.strip("\n").split("\n")
+    head = lines[0].split("\t")
+    rows = []
+    for ln in lines[1:]:
+        d = dict(zip(head, ln.split("\t")))
+        r = dict(rank=int(d["rank"]), seq=d["NaiveSequence"], probability=float(d["probability"]),
+                 log_prior=float(d["log_prior"]))
+        if "sampled_count" in d:
+            r["sampled_count"] = None if d["sampled_count"] == "NA" else int(d["sampled_count"])
+            r["sampled_frequency"] = None if d["sampled_frequency"] == "NA" else float(d["sampled_frequency"])
+        rows.append(r)
+    return rows
+
+
+def _parse_aa(text):
+    lines = text.strip("\n").split("\n")
+    return [(lines[i][1:], float(lines[i][1:].split("_")[2]), lines[i + 1]) for i in range(0, len(lines), 2)]
+
+
+def _parse_dnamap(text):
+    out, name = {}, None
+    for ln in text.strip("\n").split("\n"):
+        if ln.startswith(">"):
+            name = ln[1:]
+            out[name] = []
+        else:
+            p, dna = ln.split(",")
+            out[name].append((float(p), dna))
+    return out
+
+
+def _parse_summary(text):
+    out = {}
+    for ln in text.strip().split("\n")[1:]:
+        k, v = ln.split("\t")
+        out[k] = None if v == "NA" else (float(v) if k in ("kish_ess", "covered_mass") else int(v))
+    return out
+
+
+def translate(dna):
+    """The host's translation (NaiveProbs.hpp TranslateDna)."""
+    out = C.c_char_p()
+    _check(load_host().lhh_translate(dna.encode(), C.byref(out)))
+    return out.value.decode()
+
+
+def repr_double(v):
+    """The host's repr(float) formatting (NaiveProbs.hpp ReprDouble)."""
+    out = C.c_char_p()
+    lib = load_host()
+    lib.lhh_repr_double.argtypes = [C.c_double, C.POINTER(C.c_char_p)]
+    _check(lib.lhh_repr_double(v, C.byref(out)))
+    return out.value.decode()
+
+
+def read_candidates(path, n_sites):
+    """The host's candidate-file reader: the sequences (raises RuntimeError with its message on a refusal)."""
+    out = C.c_char_p()
+    _check(load_host().lhh_read_candidates(path.encode(), n_sites, C.byref(out)))
+    return out.value.decode().split()
+
+
+def naive_probs_write(seqs, prob, log_prior, count=None, freq=None):
+    """The host writers on caller data: (.naive.tsv, .aa.fasta, .dnamap) texts."""
+    K = len(seqs)
+    lib = load_host()
+    lib.lhh_naive_probs_write.argtypes = [C.c_int, C.c_char_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.POINTER(C.c_char_p)]
+    p, lp = np.ascontiguousarray(prob, dtype=np.float64), np.ascontiguousarray(log_prior, dtype=np.float64)
+    c = None if count is None else np.ascontiguousarray(count, dtype=np.int64)
+    f = None if freq is None else np.ascontiguousarray(freq, dtype=np.float64)
+    out = C.c_char_p()
+    _check(lib.lhh_naive_probs_write(K, "\n".join(seqs).encode(), p.ctypes.data, lp.ctypes.data,
+                                     None if c is None else c.ctypes.data, None if f is None else f.ctypes.data,
+                                     C.byref(out)))
+    a, b, d = out.value.decode().split("\x1e\n")
+    return a, b, d
+
+
 class _HMM:
     def __init__(self, handle):
         self.h = handle
@@ -188,6 +277,42 @@ class PhyloHMM(_HMM):
         _check(self.lib.lhh_run_marginals_pipeline(self.h, input_path.encode(), output_prefix.encode(), num_rates,
                                                    C.c_double(burnin_frac)))
         return read_marginals(output_prefix)
+
+    def candidate_posterior(self, seqs):
+        """(log P(s | data, tree) [K], log-likelihood, log P_HMM(s) [K]) of ACGTN candidate strings for the current tree
+        (PhyloHMM::CandidatePosterior; -inf for a sequence no state path writes)."""
+        K = len(seqs)
+        lp, pr = np.zeros(K), np.zeros(K)
+        ll = C.c_double()
+        self.lib.lhh_phylo_candidate_posterior.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_void_p, C.c_void_p,
+                                                           C.POINTER(C.c_double)]
+        _check(self.lib.lhh_phylo_candidate_posterior(self.h, K, "".join(seqs).encode(), lp.ctypes.data, pr.ctypes.data,
+                                                      C.byref(ll)))
+        return lp, ll.value, pr
+
+    def naive_sequences(self, states):
+        """K6c and HMM::ApplySampledStates on the same states [n][S]: (device bytes [n][L], hashes [n], host strings)."""
+        st = np.ascontiguousarray(states, dtype=np.int32)
+        n = st.shape[0]
+        L = self.sizes()["n_sites"]
+        seqs = np.zeros((n, L), dtype=np.uint8)
+        hsh = np.zeros(n, dtype=np.uint64)
+        host = C.create_string_buffer(n * L + 1)
+        self.lib.lhh_phylo_naive_sequences.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p]
+        _check(self.lib.lhh_phylo_naive_sequences(self.h, n, st.ctypes.data, seqs.ctypes.data, hsh.ctypes.data, host))
+        raw = host.raw[:n * L].decode()
+        return seqs, hsh, [raw[i * L:(i + 1) * L] for i in range(n)]
+
+    def run_naive_probs_pipeline(self, input_path, output_prefix, num_rates, burnin_frac=0.0, candidates_path=None,
+                                 max_candidates=65536):
+        """PhyloHMM::RunNaiveProbsPipeline; returns read_naive_probs(output_prefix)."""
+        self.lib.lhh_run_naive_probs_pipeline.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_int, C.c_double,
+                                                          C.c_char_p, C.c_int]
+        _check(self.lib.lhh_run_naive_probs_pipeline(self.h, input_path.encode(), output_prefix.encode(), num_rates,
+                                                     C.c_double(burnin_frac),
+                                                     candidates_path.encode() if candidates_path else None,
+                                                     max_candidates))
+        return read_naive_probs(output_prefix)
 
     def run_pipeline(self, input_path, output_path, num_rates):
         _check(self.lib.lhh_run_pipeline(self.h, input_path.encode(), output_path.encode(), num_rates))
