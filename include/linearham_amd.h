@@ -351,6 +351,49 @@ int lh_draws_reset(lh_family* fam);
  * events); resets the counters. */
 int lh_collect_profile_read(lh_family* fam, double* ms, int64_t* n_launches);
 
+/* ---- the lineage of a seed sequence (K7) ----
+ * The lineage of tree sample i is the chain of inner nodes from the seed tip's parent up to the tree's root (naive's
+ * neighbour): path[i][0..P) in lh_schedule_tree numbering (T + k), padded with -1; P = the batch's longest chain.  Its
+ * slots are s < P: row anc[i][path[i][s] - T][0..L) of the sampled states; s = P: the sample's naive sequence.  A flat
+ * slot is i * (P + 1) + s.  Per slot the kernel writes a 64-bit hash of the bases and one of their translation
+ * (standard code, frame 0, truncated to whole codons, stop = '*', a codon with N = the one symbol all its resolutions
+ * give, else 'X').  Hash bits depend on the sequence alone -- a naive sequence gets lh_naive_sequences' hash -- and
+ * LH_COLLECT_HASH_BITS masks them too.  Padding slots get LH_LINEAGE_PAD_HASH; a sample whose (device-resident)
+ * schedule the sampling kernel refused gets all-ones in every slot, and the handle's error word is raised.
+ *
+ * lh_asr_batch followed by K7 (host pointers): lh_asr_batch's inputs and random numbers, path [n][P]; nt_hash, aa_hash
+ * [n][P+1].  The sampled states are not copied back: they stay in the handle's workspace, whole, for
+ * lh_lineage_resolve / lh_lineage_rows_read, so a batch with more than 1 GiB of them is refused (the message names
+ * the largest n).  The next lh_asr_batch or lh_lineage_batch on the handle overwrites them. */
+#define LH_LINEAGE_PAD_HASH 0ull
+int lh_lineage_batch(lh_family* fam, int32_t n, int32_t n_tips, int32_t max_depth, const int32_t* ops,
+                     const double* brlen, const double* er, const double* pi, const double* rates, int32_t num_rates,
+                     const uint8_t* naive, uint64_t seed, uint64_t first_sample, const int32_t* path,
+                     int32_t path_len, uint64_t* nt_hash, uint64_t* aa_hash);
+
+/* K7 alone, every array resident on the handle's device (anc [n][T-2][L] as lh_asr_batch_device leaves it, naive
+ * [n][L], path [n][P]); enqueued on `hip_stream` without synchronising.  Path entries outside T .. 2T-3 count as
+ * padding.  The arrays become the handle's last lineage batch and must stay as they are while it is resolved. */
+int lh_lineage_collect_device(lh_family* fam, int32_t n, int32_t n_tips, const uint8_t* anc, const uint8_t* naive,
+                              const int32_t* path, int32_t path_len, uint64_t* nt_hash, uint64_t* aa_hash,
+                              void* hip_stream);
+
+/* The handle's lineage store: slots of the last lineage batch assigned to sequences.  ids [n_slots] (n_slots = the
+ * last batch's n * (P + 1), flat slot order) holds each slot's sequence id, -1 for a slot left out (padding); ids at
+ * or above the store's count are new and must be consecutive, each with a slot of the batch: the first such slot's
+ * bases are appended to the store.  Every assigned slot is then compared with its id's stored bases; the slots that
+ * differ (hash collisions) go to mismatch_slots [n_slots] in order, their number to *n_mismatch.  Either may be NULL. */
+int lh_lineage_resolve(lh_family* fam, int32_t n_slots, const int32_t* ids, int32_t* n_mismatch,
+                       int32_t* mismatch_slots);
+/* seqs [n_slots][n_sites]: the bases of flat slots slots[k] of the last lineage batch (padding slots read as N). */
+int lh_lineage_rows_read(lh_family* fam, int32_t n_slots, const int32_t* slots, uint8_t* seqs);
+/* *K: the number of stored sequences; seqs [count][n_sites] (may be NULL) the bases of ids first .. first+count-1. */
+int lh_lineage_store_read(lh_family* fam, int32_t first, int32_t count, int32_t* K, uint8_t* seqs);
+/* Empties the lineage store and forgets the last batch. */
+int lh_lineage_reset(lh_family* fam);
+/* Time of K7 over the lineage calls made while profiling was enabled (HIP events); resets the counters. */
+int lh_lineage_profile_read(lh_family* fam, double* ms, int64_t* n_launches);
+
 /* Tree in rooted-at-naive form: tips are nodes 0..T-1 (0 = `naive`, i = MSA row i-1), inner nodes
  * T..2T-3.  children[2*(v-T)+{0,1}] are the two children of inner node v when the tree is rooted at
  * `root`, the inner node adjacent to `naive`.  Writes the kernel's post-order schedule:

@@ -57,6 +57,11 @@ EXPORTS += CANDIDATE_EXPORTS
 COLLECT_EXPORTS = ["lh_eval_draw_batch", "lh_eval_draw_batch_device", "lh_naive_sequences", "lh_draws_resolve",
                    "lh_draws_rows_read", "lh_draws_candidates_read", "lh_draws_reset", "lh_collect_profile_read"]
 EXPORTS += COLLECT_EXPORTS
+# K7 (the lineage of a seed sequence, the lineage store)
+LINEAGE_EXPORTS = ["lh_lineage_batch", "lh_lineage_collect_device", "lh_lineage_resolve", "lh_lineage_rows_read",
+                   "lh_lineage_store_read", "lh_lineage_reset", "lh_lineage_profile_read"]
+EXPORTS += LINEAGE_EXPORTS
+LINEAGE_PAD_HASH = 0  # LH_LINEAGE_PAD_HASH
 
 
 class _PosteriorOutputs(C.Structure):
@@ -146,6 +151,18 @@ class HipLibrary:
             lib.lh_draws_candidates_read.argtypes = [C.c_void_p, c_i32p, c_u8p]
             lib.lh_draws_reset.argtypes = [C.c_void_p]
             lib.lh_collect_profile_read.argtypes = [C.c_void_p, c_f64p, C.POINTER(C.c_int64)]
+        if hasattr(lib, "lh_lineage_batch"):
+            c_u64p = C.POINTER(C.c_uint64)
+            lib.lh_lineage_batch.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, c_i32p, c_f64p, c_f64p, c_f64p,
+                                             c_f64p, C.c_int32, c_u8p, C.c_uint64, C.c_uint64, c_i32p, C.c_int32,
+                                             c_u64p, c_u64p]
+            lib.lh_lineage_collect_device.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                                      C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+            lib.lh_lineage_resolve.argtypes = [C.c_void_p, C.c_int32, c_i32p, c_i32p, c_i32p]
+            lib.lh_lineage_rows_read.argtypes = [C.c_void_p, C.c_int32, c_i32p, c_u8p]
+            lib.lh_lineage_store_read.argtypes = [C.c_void_p, C.c_int32, C.c_int32, c_i32p, c_u8p]
+            lib.lh_lineage_reset.argtypes = [C.c_void_p]
+            lib.lh_lineage_profile_read.argtypes = [C.c_void_p, c_f64p, C.POINTER(C.c_int64)]
         if hasattr(lib, "lh_set_device"):      # (absent from round-2 builds loaded through LH_LIB_DIR for comparisons)
             lib.lh_set_device.argtypes = [C.c_int32]
             lib.lh_family_status.argtypes = [C.c_void_p]
@@ -539,6 +556,71 @@ class Family:
             er.ctypes.data_as(c_f64p), pi.ctypes.data_as(c_f64p), rates.ctypes.data_as(c_f64p), rates.shape[1],
             naive.ctypes.data_as(c_u8p), seed, first_sample, anc.ctypes.data_as(c_u8p), choice.ctypes.data_as(c_u8p)))
         return anc, choice
+
+    # ---- K7: the lineage of a seed sequence and the lineage store ----
+    def lineage_batch(self, n_tips, max_depth, ops, brlen, er, pi, rates, naive, seed, path, first_sample=0):
+        """lh_lineage_batch: lh_asr_batch's inputs and path [n][P] (inner nodes seed's parent .. root, -1 padding);
+        returns (nt_hash, aa_hash), each [n][P+1] uint64, slot P = the naive sequence.  The sampled states stay on the
+        handle for lineage_resolve / lineage_rows_read."""
+        ops, brlen, er, pi, rates = _i32(ops), _f64(brlen), _f64(er), _f64(pi), _f64(rates)
+        naive = np.ascontiguousarray(naive, dtype=np.uint8)
+        path = _i32(path)
+        n, L = naive.shape
+        assert ops.shape == (n, n_tips - 2, 4) and brlen.shape == (n, 2 * n_tips - 2)
+        assert er.shape == (n, 6) and pi.shape == (n, 4) and rates.shape[0] == n and path.shape[0] == n
+        P = path.shape[1]
+        nt = np.zeros((n, P + 1), dtype=np.uint64)
+        aa = np.zeros((n, P + 1), dtype=np.uint64)
+        u64 = C.POINTER(C.c_uint64)
+        self.hip.check(self.hip.lib.lh_lineage_batch(
+            self.handle, n, n_tips, max_depth, ops.ctypes.data_as(c_i32p), brlen.ctypes.data_as(c_f64p),
+            er.ctypes.data_as(c_f64p), pi.ctypes.data_as(c_f64p), rates.ctypes.data_as(c_f64p), rates.shape[1],
+            naive.ctypes.data_as(c_u8p), seed, first_sample, path.ctypes.data_as(c_i32p), P, nt.ctypes.data_as(u64),
+            aa.ctypes.data_as(u64)))
+        self._lineage_sites = L
+        return nt, aa
+
+    def lineage_collect_device(self, n, n_tips, anc_ptr, naive_ptr, path_ptr, path_len, nt_hash_ptr, aa_hash_ptr,
+                               stream=0):
+        """lh_lineage_collect_device: K7 alone on device pointers, enqueued on `stream`."""
+        self.hip.check(self.hip.lib.lh_lineage_collect_device(self.handle, n, n_tips, anc_ptr, naive_ptr, path_ptr,
+                                                              path_len, nt_hash_ptr, aa_hash_ptr, stream))
+
+    def lineage_resolve(self, ids):
+        """lh_lineage_resolve on ids [n][P+1] (or flat): the flat slots whose bases differ from their id's."""
+        ids = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+        slots = np.zeros(max(len(ids), 1), dtype=np.int32)
+        nm = C.c_int32()
+        self.hip.check(self.hip.lib.lh_lineage_resolve(self.handle, len(ids), ids.ctypes.data_as(c_i32p), C.byref(nm),
+                                                       slots.ctypes.data_as(c_i32p)))
+        return slots[:nm.value].copy()
+
+    def lineage_rows_read(self, slots, n_sites=None):
+        """The bases [len(slots)][L] of flat slots of the last lineage batch."""
+        slots = np.ascontiguousarray(slots, dtype=np.int32)
+        out = np.zeros((len(slots), n_sites or self._lineage_sites), dtype=np.uint8)
+        self.hip.check(self.hip.lib.lh_lineage_rows_read(self.handle, len(slots), slots.ctypes.data_as(c_i32p),
+                                                         out.ctypes.data_as(c_u8p)))
+        return out
+
+    def lineage_store_read(self, first=0, count=None, n_sites=None):
+        """The lineage store's sequences first .. first+count-1 (default: all): [count][L] uint8."""
+        k = C.c_int32()
+        self.hip.check(self.hip.lib.lh_lineage_store_read(self.handle, 0, 0, C.byref(k), None))
+        count = k.value - first if count is None else count
+        out = np.zeros((count, n_sites or self._lineage_sites), dtype=np.uint8)
+        self.hip.check(self.hip.lib.lh_lineage_store_read(self.handle, first, count, C.byref(k),
+                                                          out.ctypes.data_as(c_u8p)))
+        return out
+
+    def lineage_reset(self):
+        self.hip.check(self.hip.lib.lh_lineage_reset(self.handle))
+
+    def lineage_profile_read(self):
+        """(K7 ms, launches) since the last read."""
+        ms, k = C.c_double(), C.c_int64()
+        self.hip.check(self.hip.lib.lh_lineage_profile_read(self.handle, C.byref(ms), C.byref(k)))
+        return ms.value, k.value
 
     def set_extended_range(self, on=True):
         self.hip.check(self.hip.lib.lh_family_set_extended_range(self.handle, int(on)))

@@ -1,0 +1,318 @@
+#include "Lineage.hpp"
+
+#include <algorithm>
+#include <fstream>
+#include <numeric>
+#include <stdexcept>
+
+#include "NaiveProbs.hpp"
+
+namespace linearham {
+
+namespace {
+
+// str(float(count) / denominator), remembered: a table has few distinct counts and ReprDouble searches for its digits
+class Fractions {
+ public:
+  const std::string& operator()(int64_t count, int64_t denominator) {
+    const auto r = text_.emplace(std::make_pair(count, denominator), std::string());
+    if (r.second) r.first->second = ReprDouble((double)count / (double)denominator);
+    return r.first->second;
+  }
+
+ private:
+  std::map<std::pair<int64_t, int64_t>, std::string> text_;
+};
+
+}  // namespace
+
+void LineageTabulator::Counted::Add(int key) {
+  int pos = -1;
+  if (keys.size() <= kLinear) {  // most counters hold a key or two: no index until there are many
+    for (std::size_t k = 0; k < keys.size() && pos < 0; ++k)
+      if (keys[k] == key) pos = (int)k;
+  } else {
+    if (at.empty())
+      for (std::size_t k = 0; k < keys.size(); ++k) at.emplace(keys[k], (int)k);
+    const auto it = at.find(key);
+    if (it != at.end()) pos = it->second;
+  }
+  if (pos < 0) {
+    pos = (int)keys.size();
+    keys.push_back(key);
+    counts.push_back(0);
+    if (!at.empty()) at.emplace(key, pos);
+  }
+  ++counts[pos];
+}
+
+std::vector<int> LineageTabulator::Counted::MostCommon() const {
+  std::vector<int> order(keys.size());
+  std::iota(order.begin(), order.end(), 0);
+  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return counts[a] > counts[b]; });
+  return order;
+}
+
+int LineageTabulator::AddSequence(const std::string& nt) {
+  const auto r = nt_id_.emplace(nt, (int)nt_.size());
+  if (r.second) {
+    nt_.push_back(nt);
+    const std::string aa = TranslateDna(nt);
+    const auto a = aa_id_.emplace(aa, (int)aa_.size());
+    if (a.second) aa_.push_back(aa);
+    aa_of_nt_.push_back(a.first->second);
+  }
+  return r.first->second;
+}
+
+void LineageTabulator::AddTree(const std::vector<std::string>& seqs, int path_len) {
+  std::vector<int> ids;
+  for (const std::string& s : seqs) ids.push_back(AddSequence(s));
+  AddTree(ids, path_len);
+}
+
+void LineageTabulator::AddTree(const std::vector<int>& ids, int path_len) {
+  if (ids.size() < 2) throw std::runtime_error("lineage: a tree's lineage holds at least naive and the seed");
+  for (int id : ids)
+    if (id < 0 || id >= (int)nt_.size()) throw std::runtime_error("lineage: unknown sequence id");
+  ++num_trees_;
+  longest_path_ = std::max<int64_t>(longest_path_, path_len);
+  std::vector<int> l;
+  for (int id : ids) l.push_back(aa_of_nt_[id]);
+  // node_dt: groupby(l, translate), then frozenset(g)
+  for (std::size_t lo = 0; lo < l.size();) {
+    std::size_t hi = lo;
+    while (hi < l.size() && l[hi] == l[lo]) ++hi;
+    if (node_dt_.size() < aa_.size()) node_dt_.resize(aa_.size());
+    Counted& c = node_dt_[l[lo]];
+    for (std::size_t k = lo; k < hi; ++k)
+      if (std::find(ids.begin() + lo, ids.begin() + k, ids[k]) == ids.begin() + k) c.Add(ids[k]);
+    lo = hi;
+  }
+  // node_c: frozenset(l)
+  for (std::size_t k = 0; k < l.size(); ++k)
+    if (std::find(l.begin(), l.begin() + k, l[k]) == l.begin() + k) node_c_.Add(l[k]);
+  // edge_c: zip(l[:-1], l[1:]) without the pairs the script never shows
+  for (std::size_t k = 0; k + 1 < l.size(); ++k) {
+    if (l[k] == l[k + 1]) continue;
+    const std::pair<int, int> e{l[k], l[k + 1]};
+    const auto r = edge_at_.emplace(e, (int)edge_keys_.size());
+    if (r.second) {
+      edge_keys_.push_back(e);
+      edge_counts_.push_back(0);
+    }
+    ++edge_counts_[r.first->second];
+  }
+  naive_c_.Add(l.front());
+  if (std::find(seed_aa_.begin(), seed_aa_.end(), l.back()) == seed_aa_.end()) seed_aa_.push_back(l.back());
+}
+
+LineageTables LineageTabulator::Finish(const std::string& seed_name) const {
+  if (num_trees_ == 0) throw std::runtime_error("lineage: no trees");
+  if (seed_aa_.size() != 1)
+    throw std::runtime_error("lineage: the seed " + seed_name + " has " + std::to_string(seed_aa_.size()) +
+                             " different translations over the trees");
+  LineageTables t;
+  t.num_trees = num_trees_;
+  t.distinct_nt = (int64_t)nt_.size();
+  t.distinct_aa = (int64_t)aa_.size();
+  t.longest_path = longest_path_;
+  Fractions frac;
+  std::unordered_map<int, std::string> naive_name;
+  {
+    int i = 0;
+    for (int p : naive_c_.MostCommon())
+      naive_name[naive_c_.keys[p]] =
+          "naive_" + std::to_string(i++) + "_" + frac(naive_c_.counts[p], num_trees_);
+  }
+  std::unordered_map<int, int> node_of_aa;
+  int n_inter = 0;
+  for (int p : node_c_.MostCommon()) {
+    const int aa = node_c_.keys[p];
+    LineageTables::Node nd;
+    nd.aa = aa_[aa];
+    nd.count = node_c_.counts[p];
+    const auto nn = naive_name.find(aa);
+    if (aa == seed_aa_[0]) {
+      nd.name = seed_name;
+      nd.kind = "seed";
+    } else if (nn != naive_name.end()) {
+      nd.name = nn->second;
+      nd.kind = "naive";
+    } else {
+      nd.name = "intermediate_" + std::to_string(n_inter++) + "_" + frac(nd.count, num_trees_);
+      nd.kind = "intermediate";
+    }
+    const Counted& dt = node_dt_[aa];
+    for (int q : dt.MostCommon()) nd.dna.emplace_back(dt.counts[q], nt_[dt.keys[q]]);
+    node_of_aa[aa] = (int)t.nodes.size();
+    t.nodes.push_back(std::move(nd));
+  }
+  std::vector<int> order(edge_keys_.size());
+  std::iota(order.begin(), order.end(), 0);
+  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return edge_counts_[a] > edge_counts_[b]; });
+  for (int e : order)
+    t.edges.push_back({node_of_aa.at(edge_keys_[e].first), node_of_aa.at(edge_keys_[e].second), edge_counts_[e]});
+  return t;
+}
+
+std::string FindMuts(const std::string& orig, const std::string& mutated) {
+  std::string out;
+  for (std::size_t k = 0; k < orig.size() && k < mutated.size(); ++k) {
+    if (orig[k] == mutated[k]) continue;
+    if (!out.empty()) out.push_back(' ');
+    out += orig[k] + std::to_string(k + 1) + mutated[k];
+  }
+  return out;
+}
+
+void WriteLineageFasta(std::ostream& o, const LineageTables& t) {
+  for (const auto& n : t.nodes) o << ">" << n.name << "\n" << n.aa << "\n";
+}
+
+void WriteLineageDnaMap(std::ostream& o, const LineageTables& t) {
+  Fractions frac;
+  for (const auto& n : t.nodes) {
+    o << ">" << n.name << "\n";
+    for (const auto& d : n.dna) o << frac(d.first, t.num_trees) << "," << d.second << "\n";
+  }
+}
+
+void WriteLineageNodes(std::ostream& o, const LineageTables& t) {
+  Fractions frac;
+  o << "name\tkind\tcount\tfraction\n";
+  for (const auto& n : t.nodes) o << n.name << "\t" << n.kind << "\t" << n.count << "\t" << frac(n.count, t.num_trees) << "\n";
+}
+
+void WriteLineageEdges(std::ostream& o, const LineageTables& t) {
+  Fractions frac;
+  o << "parent\tchild\tcount\tfraction\tparent_fraction\tmutations\n";
+  for (const auto& e : t.edges) {
+    const auto &a = t.nodes[e.parent], &b = t.nodes[e.child];
+    o << a.name << "\t" << b.name << "\t" << e.count << "\t" << frac(e.count, t.num_trees) << "\t"
+      << frac(e.count, a.count) << "\t" << FindMuts(a.aa, b.aa) << "\n";
+  }
+}
+
+void WriteLineageSummary(std::ostream& o, const LineageTables& t, int64_t collisions) {
+  o << "key\tvalue\nrows\t" << t.num_trees << "\ndistinct_nt\t" << t.distinct_nt << "\ndistinct_aa\t" << t.distinct_aa
+    << "\nlongest_path\t" << t.longest_path << "\nhash_collisions_resolved\t" << collisions << "\n";
+}
+
+void WriteLineageFiles(const std::string& prefix, const LineageTables& t, int64_t collisions) {
+  std::ofstream fasta(prefix + ".fasta"), dnamap(prefix + ".dnamap"), nodes(prefix + ".nodes.tsv"),
+      edges(prefix + ".edges.tsv"), summary(prefix + ".summary.tsv");
+  if (!fasta || !dnamap || !nodes || !edges || !summary) throw std::runtime_error("Can't write " + prefix + ".*");
+  WriteLineageFasta(fasta, t);
+  WriteLineageDnaMap(dnamap, t);
+  WriteLineageNodes(nodes, t);
+  WriteLineageEdges(edges, t);
+  WriteLineageSummary(summary, t, collisions);
+}
+
+std::vector<std::string> LineageOfAnnotatedTree(const std::string& s, const std::string& seed_seq) {
+  struct Node {
+    int parent = -1;
+    std::string label, ancestral;
+    bool annotated = false, tip = true;
+  };
+  std::vector<Node> nodes;
+  std::vector<int> open;  // the nodes whose '(' is open
+  int last = -1;          // the node the next label / comment / length belongs to
+  const std::string key = "&ancestral=\"";
+  auto fresh = [&] {
+    Node n;
+    n.parent = open.empty() ? -1 : open.back();
+    nodes.push_back(n);
+    return (int)nodes.size() - 1;
+  };
+  std::size_t k = 0;
+  bool done = false;
+  while (k < s.size() && !done) {
+    const char c = s[k];
+    if (c == '(') {
+      const int v = fresh();
+      nodes[v].tip = false;
+      open.push_back(v);
+      last = -1;
+      ++k;
+    } else if (c == ',') {
+      if (last < 0) fresh();  // an empty subtree
+      last = -1;
+      ++k;
+    } else if (c == ')') {
+      if (open.empty()) throw std::runtime_error("lineage: unbalanced ')' in tree");
+      if (last < 0) fresh();
+      last = open.back();
+      open.pop_back();
+      ++k;
+    } else if (c == ';') {
+      done = true;
+    } else if (c == '[') {
+      const std::size_t e = s.find(']', k);
+      if (e == std::string::npos) throw std::runtime_error("lineage: unterminated comment in tree");
+      if (last < 0) last = fresh();
+      const std::size_t a = s.find(key, k);
+      if (a != std::string::npos && a < e) {
+        const std::size_t q = s.find('"', a + key.size());
+        if (q == std::string::npos || q > e) throw std::runtime_error("lineage: malformed ancestral annotation");
+        nodes[last].ancestral = s.substr(a + key.size(), q - a - key.size());
+        nodes[last].annotated = true;
+      }
+      k = e + 1;
+    } else if (c == ':') {
+      if (last < 0) last = fresh();
+      ++k;
+      while (k < s.size() && std::string("(),;[").find(s[k]) == std::string::npos) ++k;
+    } else if (c == ' ' || c == '\t' || c == '\r') {
+      ++k;
+    } else {
+      if (last < 0) last = fresh();
+      const std::size_t b = k;
+      while (k < s.size() && std::string("(),;[:").find(s[k]) == std::string::npos) ++k;
+      nodes[last].label += s.substr(b, k - b);
+    }
+  }
+  if (!open.empty()) throw std::runtime_error("lineage: unbalanced '(' in tree");
+  auto find_tip = [&](const std::string& name) {
+    for (std::size_t v = 0; v < nodes.size(); ++v)
+      if (nodes[v].tip && nodes[v].label == name) return (int)v;
+    return -1;
+  };
+  const int seed = find_tip(seed_seq), naive = find_tip("naive");
+  if (seed < 0) throw std::runtime_error("seed node with label '" + seed_seq + "' not found in tree");
+  if (naive < 0) throw std::runtime_error("no tip 'naive' in tree");
+  std::vector<std::string> l;
+  auto take = [&](int v) {
+    if (!nodes[v].annotated) throw std::runtime_error("lineage: a node above '" + seed_seq + "' has no ancestral annotation");
+    l.push_back(nodes[v].ancestral);
+  };
+  for (int v = seed; v >= 0; v = nodes[v].parent) take(v);
+  take(naive);
+  std::reverse(l.begin(), l.end());
+  return l;
+}
+
+void TabulateLineageTrees(const std::string& trees_path, const std::string& seed_seq, const std::string& prefix) {
+  if (seed_seq == "naive") throw std::runtime_error("the seed sequence cannot be 'naive': the lineage ends there");
+  std::ifstream in(trees_path);
+  if (!in) throw std::runtime_error("Can't open trees file " + trees_path);
+  LineageTabulator tab;
+  std::string line;
+  std::size_t n_line = 0;
+  while (std::getline(in, line)) {
+    ++n_line;
+    if (line.find_first_not_of(" \t\r") == std::string::npos) continue;
+    std::vector<std::string> l;
+    try {
+      l = LineageOfAnnotatedTree(line, seed_seq);
+    } catch (const std::exception& e) {
+      throw std::runtime_error(trees_path + " line " + std::to_string(n_line) + ": " + e.what());
+    }
+    // naive, the root RunAsr adds on the naive branch, naive's neighbour .. seed's parent, seed
+    tab.AddTree(l, std::max(0, (int)l.size() - 3));
+  }
+  WriteLineageFiles(prefix, tab.Finish(seed_seq), 0);
+}
+
+}  // namespace linearham

@@ -1,0 +1,97 @@
+// Ancestral lineage tables of a seed sequence (scripts/tabulate_lineage_probs.py:95-144): which amino-acid sequences
+// stood on the path from the naive sequence to the seed, in how many trees, and which followed which.  Pure host code.
+#ifndef LINEARHAM_LINEAGE_
+#define LINEARHAM_LINEAGE_
+
+#include <cstdint>
+#include <map>
+#include <ostream>
+#include <string>
+#include <unordered_map>
+#include <utility>
+#include <vector>
+
+namespace linearham {
+
+/// The finished tables.  Nodes are in node_c.most_common() order (descending count, ties by first appearance), edges
+/// likewise; fractions are count / num_trees.
+struct LineageTables {
+  struct Node {
+    std::string name, kind, aa;  // kind: seed / naive / intermediate
+    int64_t count = 0;
+    std::vector<std::pair<int64_t, std::string>> dna;  // node_dt[aa].most_common(): (count, nucleotide sequence)
+  };
+  struct Edge {
+    int parent = 0, child = 0;  // indices into nodes; never equal
+    int64_t count = 0;
+  };
+  std::vector<Node> nodes;
+  std::vector<Edge> edges;
+  int64_t num_trees = 0, distinct_nt = 0, distinct_aa = 0, longest_path = 0;
+};
+
+/// The script's counting.  A tree is its lineage as a list of nucleotide sequences naive, root, ..., seed's parent,
+/// seed (the script's reversed `l`); the rules, oddities included:
+///  - node_c: each distinct translation of a tree counts once for that tree;
+///  - node_dt: for every run of consecutive equal translations, each distinct nucleotide sequence of the run counts
+///    once, so a translation that returns after a change counts its nucleotide sequences again;
+///  - edge_c: consecutive pairs of translations; pairs with equal ends are never shown by the script and are left out;
+///  - "first appearance" is list order inside a tree (the script iterates a frozenset there, which has no order).
+class LineageTabulator {
+ public:
+  /// Registers a nucleotide sequence (translated once) and returns its id; equal sequences share an id.
+  int AddSequence(const std::string& nt);
+  /// One tree, as ids from AddSequence; `path_len` (inner nodes between seed and naive) feeds longest_path.
+  void AddTree(const std::vector<int>& ids, int path_len);
+  void AddTree(const std::vector<std::string>& seqs, int path_len);
+  /// Names as the script gives them: the seed's translation is `seed_name`; a translation that is some tree's naive
+  /// translation is naive_<i>_<fraction> as tabulate_naive_probs.py:57-60 numbers them over these trees' naive
+  /// sequences; every other is intermediate_<i>_<fraction>.  Throws if no tree was added or the seeds' translations
+  /// differ (the script's assert len(seed_s) == 1).
+  LineageTables Finish(const std::string& seed_name) const;
+
+ private:
+  struct Counted {  // a Counter: insertion-ordered keys with counts
+    std::vector<int> keys;
+    std::vector<int64_t> counts;
+    std::unordered_map<int, int> at;  // key -> position, kept once there are more than kLinear keys
+    static constexpr std::size_t kLinear = 8;
+    void Add(int key);
+    std::vector<int> MostCommon() const;  // positions into keys
+  };
+  std::vector<std::string> nt_, aa_;
+  std::vector<int> aa_of_nt_;
+  std::unordered_map<std::string, int> nt_id_, aa_id_;
+  Counted node_c_, naive_c_;
+  std::vector<Counted> node_dt_;  // aa -> Counter of nt
+  std::vector<std::pair<int, int>> edge_keys_;
+  std::vector<int64_t> edge_counts_;
+  std::map<std::pair<int, int>, int> edge_at_;
+  std::vector<int> seed_aa_;  // distinct seed translations
+  int64_t num_trees_ = 0, longest_path_ = 0;
+};
+
+/// find_muts: "<orig><1-based position><mutated>" for every differing position, space-separated.
+std::string FindMuts(const std::string& orig, const std::string& mutated);
+
+/// <prefix>.fasta and .dnamap byte for byte as the script writes them; .nodes.tsv (name, kind, count, fraction),
+/// .edges.tsv (parent, child, count, fraction, parent_fraction, mutations) and .summary.tsv (rows, distinct_nt,
+/// distinct_aa, longest_path, hash_collisions_resolved).  Fractions print as Python's str(float).
+void WriteLineageFasta(std::ostream& o, const LineageTables& t);
+void WriteLineageDnaMap(std::ostream& o, const LineageTables& t);
+void WriteLineageNodes(std::ostream& o, const LineageTables& t);
+void WriteLineageEdges(std::ostream& o, const LineageTables& t);
+void WriteLineageSummary(std::ostream& o, const LineageTables& t, int64_t collisions);
+void WriteLineageFiles(const std::string& prefix, const LineageTables& t, int64_t collisions);
+
+/// One line of PhyloHMM::RunAsr's output (annotated Newick): the [&ancestral="..."] strings on the way seed, its
+/// ancestors up to the top node, then the tip `naive`, as seqs_of_tree collects them, reversed (naive first).
+/// Throws when the tree has no tip `seed_seq` or `naive`, or a node on the way has no annotation.
+std::vector<std::string> LineageOfAnnotatedTree(const std::string& newick, const std::string& seed_seq);
+
+/// tabulate_lineage_probs.py for a file of RunAsr lines: needs no family and no device.  Writes the five files.
+void TabulateLineageTrees(const std::string& trees_path, const std::string& seed_seq, const std::string& prefix);
+
+}  // namespace linearham
+
+#endif  // LINEARHAM_LINEAGE_

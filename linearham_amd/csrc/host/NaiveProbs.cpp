@@ -1,6 +1,7 @@
 #include "NaiveProbs.hpp"
 
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -47,8 +48,34 @@ char TranslateCodon(const char* c) {
 }  // namespace
 
 std::string TranslateDna(const std::string& dna) {
+  // TranslateCodon of every codon over ACGTN, tabulated once (a character outside the alphabet gives X)
+  static const std::array<char, 125> table = [] {
+    std::array<char, 125> t{};
+    const char* alphabet = "ACGTN";
+    for (int a = 0; a < 5; ++a)
+      for (int b = 0; b < 5; ++b)
+        for (int c = 0; c < 5; ++c) {
+          const char codon[3] = {alphabet[a], alphabet[b], alphabet[c]};
+          t[a * 25 + b * 5 + c] = TranslateCodon(codon);
+        }
+    return t;
+  }();
+  auto index = [](char b) {
+    switch (b) {
+      case 'A': return 0;
+      case 'C': return 1;
+      case 'G': return 2;
+      case 'T': return 3;
+      case 'N': return 4;
+      default: return -1;
+    }
+  };
   std::string aa;
-  for (std::size_t i = 0; i + 3 <= dna.size(); i += 3) aa.push_back(TranslateCodon(dna.data() + i));
+  aa.reserve(dna.size() / 3);
+  for (std::size_t i = 0; i + 3 <= dna.size(); i += 3) {
+    const int a = index(dna[i]), b = index(dna[i + 1]), c = index(dna[i + 2]);
+    aa.push_back(a < 0 || b < 0 || c < 0 ? 'X' : table[a * 25 + b * 5 + c]);
+  }
   return aa;
 }
 

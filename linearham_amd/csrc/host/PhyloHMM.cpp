@@ -1,5 +1,6 @@
 #include "PhyloHMM.hpp"
 
+#include "Lineage.hpp"
 #include "NaiveProbs.hpp"
 
 #include <cerrno>
@@ -1388,7 +1389,13 @@ std::string PhyloHMM::AnnotatedNewick(const TreeArrays& tr, const std::string& n
   return out + ")" + comment(tr.root) + ";";
 }
 
-void PhyloHMM::RunAsr(const std::string& input_path, const std::string& output_path, uint64_t seed) {
+struct PhyloHMM::AsrRow {
+  TreeSample ts;
+  std::vector<double> sr;
+  std::string naive;
+};
+
+std::vector<PhyloHMM::AsrRow> PhyloHMM::ReadAsrRows(const std::string& input_path, int* num_rates) const {
   std::ifstream in(input_path);
   if (!in) throw std::runtime_error("Can't open linearham output file " + input_path);
   std::string line;
@@ -1414,14 +1421,9 @@ void PhyloHMM::RunAsr(const std::string& input_path, const std::string& output_p
     sr_col.push_back(c);
   }
   if (sr_col.empty()) throw std::runtime_error("Missing column \"sr[1]\" in " + input_path);
-  const int R = (int)sr_col.size();
+  *num_rates = (int)sr_col.size();
   const int L = (int)msa_.cols();
-  struct Row {
-    TreeSample ts;
-    std::vector<double> sr;
-    std::string naive;
-  };
-  std::vector<Row> rows;
+  std::vector<AsrRow> rows;
   while (std::getline(in, line)) {
     if (line.empty()) continue;
     const std::vector<std::string> f = SplitTsv(line);
@@ -1429,7 +1431,7 @@ void PhyloHMM::RunAsr(const std::string& input_path, const std::string& output_p
       if (c >= (int)f.size()) throw std::runtime_error("Too few columns in " + input_path);
       return f[c];
     };
-    Row r;
+    AsrRow r;
     for (int k = 0; k < 6; ++k) r.ts.er.push_back(std::stod(get(col[k])));
     for (int k = 0; k < 4; ++k) r.ts.pi.push_back(std::stod(get(col[6 + k])));
     r.ts.alpha = 1.0;  // unused: the rates come from the sr[] columns
@@ -1439,6 +1441,31 @@ void PhyloHMM::RunAsr(const std::string& input_path, const std::string& output_p
     for (int c : sr_col) r.sr.push_back(std::stod(get(c)));
     rows.push_back(std::move(r));
   }
+  return rows;
+}
+
+void PhyloHMM::EncodeAsrRows(const std::vector<AsrRow>& rows, std::size_t off, std::size_t m, int R,
+                             std::vector<TreeSample>* samples, std::vector<double>* rates,
+                             std::vector<uint8_t>* naive) const {
+  const int L = (int)msa_.cols();
+  samples->clear();
+  for (std::size_t i = 0; i < m; ++i) samples->push_back(rows[off + i].ts);
+  rates->assign(m * R, 0.0);
+  naive->assign(m * (std::size_t)L, 0);
+  for (std::size_t i = 0; i < m; ++i) {
+    std::copy(rows[off + i].sr.begin(), rows[off + i].sr.end(), rates->begin() + i * R);
+    for (int j = 0; j < L; ++j) {
+      const std::size_t a = alphabet_.find(rows[off + i].naive[j]);
+      if (a == std::string::npos) throw std::runtime_error("NaiveSequence holds a character outside the alphabet");
+      (*naive)[i * L + j] = (uint8_t)a;
+    }
+  }
+}
+
+void PhyloHMM::RunAsr(const std::string& input_path, const std::string& output_path, uint64_t seed) {
+  int R = 0;
+  const std::vector<AsrRow> rows = ReadAsrRows(input_path, &R);
+  const int L = (int)msa_.cols();
   CreateFamily();
   std::ofstream outfile(output_path);
   if (!outfile) throw std::runtime_error("Can't open output file " + output_path);
@@ -1447,19 +1474,11 @@ void PhyloHMM::RunAsr(const std::string& input_path, const std::string& output_p
   for (std::size_t off = 0; off < rows.size(); off += kBatch) {
     const std::size_t m = std::min(kBatch, rows.size() - off);
     std::vector<TreeSample> samples;
-    for (std::size_t i = 0; i < m; ++i) samples.push_back(rows[off + i].ts);
+    std::vector<double> rates;
+    std::vector<uint8_t> naive, anc(m * (std::size_t)(T - 2) * L);
+    EncodeAsrRows(rows, off, m, R, &samples, &rates, &naive);
     std::vector<TreeArrays> trees;
     const DeviceBatch b = FlattenBatch(samples, &trees);
-    std::vector<double> rates(m * R);
-    std::vector<uint8_t> naive(m * (std::size_t)L), anc(m * (std::size_t)(T - 2) * L);
-    for (std::size_t i = 0; i < m; ++i) {
-      std::copy(rows[off + i].sr.begin(), rows[off + i].sr.end(), rates.begin() + i * R);
-      for (int j = 0; j < L; ++j) {
-        const std::size_t a = alphabet_.find(rows[off + i].naive[j]);
-        if (a == std::string::npos) throw std::runtime_error("NaiveSequence holds a character outside the alphabet");
-        naive[i * L + j] = (uint8_t)a;
-      }
-    }
     CheckHip(lh_asr_batch(family_, b.n, b.n_tips, b.max_depth, b.ops.data(), b.brlen.data(), b.er.data(), b.pi.data(),
                           rates.data(), R, naive.data(), seed, (uint64_t)off, anc.data(), nullptr),
              "lh_asr_batch");
@@ -1482,6 +1501,148 @@ void PhyloHMM::RunAsr(const std::string& input_path, const std::string& output_p
     }
     for (std::size_t i = 0; i < m; ++i) outfile << lines[i] << "\n";
   }
+}
+
+void PhyloHMM::RunLineagePipeline(const std::string& input_path, const std::string& seed_seq,
+                                  const std::string& output_prefix, uint64_t seed) {
+  Require(seed_seq != "naive", "the seed sequence cannot be 'naive': the lineage ends there");
+  const int T = (int)xmsa_labels_.size();
+  int seed_tip = -1;
+  for (int v = 1; v < T; ++v)
+    if (xmsa_labels_[v] == seed_seq) seed_tip = v;
+  Require(seed_tip > 0, "the seed sequence '" + seed_seq + "' is not a sequence of this clonal family");
+  const bool timing = host_options().pipeline_timing;
+  auto now = [] { return std::chrono::steady_clock::now(); };
+  auto secs = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
+    return std::chrono::duration<double>(b - a).count();
+  };
+  const auto t_start = now();
+  double t_flat = 0, t_dev = 0, t_resolve = 0, t_count = 0;
+  int R = 0;
+  const std::vector<AsrRow> rows = ReadAsrRows(input_path, &R);
+  const auto t_read = now();
+  const int L = (int)msa_.cols();
+  CreateFamily();
+  CheckHip(lh_lineage_reset(family_), "lh_lineage_reset");
+  auto decode = [&](const uint8_t* b) {
+    std::string s((std::size_t)L, 'N');
+    for (int j = 0; j < L; ++j) s[j] = alphabet_[std::min<std::size_t>(b[j], alphabet_.size() - 1)];
+    return s;
+  };
+  LineageTabulator tab;
+  std::string seed_nt((std::size_t)L, 'N');
+  for (int j = 0; j < L; ++j) seed_nt[j] = alphabet_[msa_(seed_tip - 1, j)];
+  const int seed_id = tab.AddSequence(seed_nt);  // (tips keep their observed characters: one sequence for every tree)
+  std::unordered_map<uint64_t, int32_t> by_hash;   // base hash -> store id of the first sequence seen with it
+  std::unordered_map<std::string, int32_t> exact;  // store ids made by resolving collisions, by their bases
+  std::vector<int> tab_of_store;                   // store id -> tabulator id
+  std::vector<uint64_t> aa_of_store;               // store id -> translation hash of its first slot
+  int32_t K = 0;
+  int64_t collisions = 0;
+  const std::size_t kBatch = host_options().lineage_batch > 0 ? (std::size_t)host_options().lineage_batch : 1024;
+  for (std::size_t off = 0; off < rows.size(); off += kBatch) {
+    const std::size_t m = std::min(kBatch, rows.size() - off);
+    const auto t0 = now();
+    std::vector<TreeSample> samples;
+    std::vector<double> rates;
+    std::vector<uint8_t> naive;
+    EncodeAsrRows(rows, off, m, R, &samples, &rates, &naive);
+    std::vector<TreeArrays> trees;
+    const DeviceBatch b = FlattenBatch(samples, &trees);
+    // the seed tip's ancestors up to naive's neighbour
+    std::vector<std::vector<int32_t>> chain(m);
+    std::size_t P = 1;
+    std::vector<int> parent(2 * (std::size_t)T - 2);
+    for (std::size_t i = 0; i < m; ++i) {
+      const TreeArrays& tr = trees[i];
+      std::fill(parent.begin(), parent.end(), -1);
+      for (int v = T; v < 2 * T - 2; ++v)
+        for (int c = 0; c < 2; ++c) parent[tr.children[2 * (std::size_t)(v - T) + c]] = v;
+      for (int v = parent[seed_tip]; v >= T; v = parent[v]) {
+        chain[i].push_back(v);
+        if (v == tr.root || (int)chain[i].size() > T) break;
+      }
+      Require(!chain[i].empty() && chain[i].back() == tr.root,
+              "row " + std::to_string(off + i) + ": the seed sequence '" + seed_seq + "' does not descend from the root");
+      P = std::max(P, chain[i].size());
+    }
+    std::vector<int32_t> path(m * P, -1);
+    for (std::size_t i = 0; i < m; ++i) std::copy(chain[i].begin(), chain[i].end(), path.begin() + i * P);
+    const std::size_t S = P + 1;
+    std::vector<uint64_t> nt_hash(m * S), aa_hash(m * S);
+    const auto t1 = now();
+    CheckHip(lh_lineage_batch(family_, b.n, b.n_tips, b.max_depth, b.ops.data(), b.brlen.data(), b.er.data(), b.pi.data(),
+                              rates.data(), R, naive.data(), seed, (uint64_t)off, path.data(), (int32_t)P,
+                              nt_hash.data(), aa_hash.data()),
+             "lh_lineage_batch");
+    const auto t2 = now();
+    // ids by hash; lh_lineage_resolve then compares every slot with its id's bases, so no hash decides alone
+    std::vector<int32_t> ids(m * S, -1);
+    const int32_t K_before = K;
+    for (std::size_t i = 0; i < m; ++i)
+      for (std::size_t s = 0; s < S; ++s) {
+        if (s < P && s >= chain[i].size()) continue;
+        const auto r = by_hash.emplace(nt_hash[i * S + s], K);
+        if (r.second) ++K;
+        ids[i * S + s] = r.first->second;
+      }
+    std::vector<int32_t> mism(m * S);
+    std::vector<uint8_t> bytes;
+    for (int round = 0;; ++round) {
+      int32_t nm = 0;
+      CheckHip(lh_lineage_resolve(family_, (int32_t)(m * S), ids.data(), &nm, mism.data()), "lh_lineage_resolve");
+      if (nm == 0) break;
+      Require(round == 0, "lineage pipeline: slots still differ from their sequences after resolution");
+      collisions += nm;
+      bytes.resize((std::size_t)nm * L);
+      CheckHip(lh_lineage_rows_read(family_, nm, mism.data(), bytes.data()), "lh_lineage_rows_read");
+      for (int32_t q = 0; q < nm; ++q) {
+        const auto r = exact.emplace(decode(bytes.data() + (std::size_t)q * L), K);
+        if (r.second) ++K;
+        ids[mism[q]] = r.first->second;
+      }
+    }
+    // only the bases of the sequences first seen in this batch come back
+    if (K > K_before) {
+      bytes.resize((std::size_t)(K - K_before) * L);
+      CheckHip(lh_lineage_store_read(family_, K_before, K - K_before, nullptr, bytes.data()), "lh_lineage_store_read");
+      for (int32_t k = K_before; k < K; ++k)
+        tab_of_store.push_back(tab.AddSequence(decode(bytes.data() + (std::size_t)(k - K_before) * L)));
+      aa_of_store.resize(K);
+      std::vector<bool> have(K - K_before, false);
+      for (std::size_t x = 0; x < m * S; ++x)
+        if (ids[x] >= K_before && !have[ids[x] - K_before]) {
+          have[ids[x] - K_before] = true;
+          aa_of_store[ids[x]] = aa_hash[x];
+        }
+    }
+    const auto t3 = now();
+    std::vector<int> l;
+    for (std::size_t i = 0; i < m; ++i) {
+      for (std::size_t s = 0; s < S; ++s)
+        if (ids[i * S + s] >= 0)
+          Require(aa_hash[i * S + s] == aa_of_store[ids[i * S + s]],
+                  "lineage pipeline: equal sequences with different translation hashes at row " + std::to_string(off + i));
+      l.clear();
+      l.push_back(tab_of_store[ids[i * S + P]]);
+      for (std::size_t s = chain[i].size(); s-- > 0;) l.push_back(tab_of_store[ids[i * S + s]]);
+      l.push_back(seed_id);
+      tab.AddTree(l, (int)chain[i].size());
+    }
+    const auto t4 = now();
+    t_flat += secs(t0, t1);
+    t_dev += secs(t1, t2);
+    t_resolve += secs(t2, t3);
+    t_count += secs(t3, t4);
+  }
+  const auto t_w = now();
+  WriteLineageFiles(output_prefix, tab.Finish(seed_seq), collisions);
+  if (timing)
+    std::fprintf(stderr,
+                 "[RunLineagePipeline] %zu rows: read %.3f s, parse+schedule+paths %.3f s, device (K1 + K3 + K7, copies) "
+                 "%.3f s, resolve+read back (%d sequences) %.3f s, count %.3f s, write %.3f s; total %.3f s\n",
+                 rows.size(), secs(t_start, t_read), t_flat, t_dev, (int)K, t_resolve, t_count, secs(t_w, now()),
+                 secs(t_start, now()));
 }
 
 // src/PhyloHMM.cpp:461-471

@@ -136,6 +136,15 @@ class PhyloHMM : public HMM {
   /// ape::root(tree, "naive", resolve.root = TRUE) does, every node annotated [&ancestral="<L bases>"] (tips:
   /// their observed sequence).  Random numbers: Philox stream `seed`, sample number = row number.
   void RunAsr(const std::string& input_path, const std::string& output_path, uint64_t seed);
+  /// The lineage tables of the tip `seed_seq` (scripts/tabulate_lineage_probs.py) straight from a RunPipeline table:
+  /// RunAsr's input, parsing, batches and draws (Philox stream `seed`, sample number = row number), but the sampled
+  /// states stay on the device.  Per batch K3 + K7 (lh_lineage_batch) hand back two hashes per lineage node; the host
+  /// assigns sequence ids by hash, lh_lineage_resolve settles every assignment by the bases themselves, and only the
+  /// bases of sequences first seen are read back.  Writes <prefix>.fasta, .dnamap, .nodes.tsv, .edges.tsv and
+  /// .summary.tsv (Lineage.hpp): what TabulateLineageTrees makes of RunAsr's output for the same table and seed.
+  /// LH_LINEAGE_BATCH=n sets the rows per batch (default 1 024, RunAsr's).
+  void RunLineagePipeline(const std::string& input_path, const std::string& seed_seq, const std::string& output_prefix,
+                          uint64_t seed);
   /// One annotated tree (RunAsr's output line) from the sampled states anc[(T-2)][L] of a row.
   std::string AnnotatedNewick(const TreeArrays& tree, const std::string& naive_sequence, const uint8_t* anc) const;
 
@@ -179,6 +188,12 @@ class PhyloHMM : public HMM {
  private:
   TableBatch FlattenTable(const TsvTable& table, std::size_t r0, std::size_t r1, bool with_export, bool with_scalars,
                           const std::string& path) const;
+  struct AsrRow;
+  /// The rows of a RunPipeline table as RunAsr and RunLineagePipeline read them; *num_rates = the sr[] columns.
+  std::vector<AsrRow> ReadAsrRows(const std::string& input_path, int* num_rates) const;
+  /// lh_asr_batch's rates [m][R] and naive [m][L] of rows off .. off+m-1, and their tree samples.
+  void EncodeAsrRows(const std::vector<AsrRow>& rows, std::size_t off, std::size_t m, int num_rates,
+                     std::vector<TreeSample>* samples, std::vector<double>* rates, std::vector<uint8_t>* naive) const;
 };
 
 typedef std::shared_ptr<PhyloHMM> PhyloHMMPtr;

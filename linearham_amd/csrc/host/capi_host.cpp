@@ -10,6 +10,7 @@
 #include <random>
 #include <string>
 
+#include "Lineage.hpp"
 #include "NaiveProbs.hpp"
 #include "PhyloHMM.hpp"
 #include "SimpleHMM.hpp"
@@ -395,6 +396,16 @@ int lhh_run_pipeline(void* h, const char* input_path, const char* output_path, i
 }
 int lhh_run_asr(void* h, const char* input_path, const char* output_path, uint64_t seed) {
   return Guard([&] { dynamic_cast<PhyloHMM&>(*static_cast<HMM*>(h)).RunAsr(input_path, output_path, seed); });
+}
+int lhh_run_lineage_pipeline(void* h, const char* input_path, const char* seed_seq, const char* output_prefix,
+                             uint64_t seed) {
+  return Guard([&] {
+    dynamic_cast<PhyloHMM&>(*static_cast<HMM*>(h)).RunLineagePipeline(input_path, seed_seq, output_prefix, seed);
+  });
+}
+// TabulateLineageTrees: a file of RunAsr lines -> the lineage tables (no family, no GPU)
+int lhh_lineage_tabulate_trees(const char* trees_path, const char* seed_seq, const char* output_prefix) {
+  return Guard([&] { TabulateLineageTrees(trees_path, seed_seq, output_prefix); });
 }
 // what: bit 0 = state space + transitions, bit 1 = forward arrays, bit 2 = sample, bit 3 = xMSA structures
 

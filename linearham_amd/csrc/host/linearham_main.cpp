@@ -2,7 +2,8 @@
 // reference, without TCLAP): --compute-logl | --sample | --pipeline; plus --asr, the per-tree body of
 // scripts/run_bootstrap_asr_ess.R:48-104 on a --pipeline output table, and --marginals / --marginals-pipeline, the exact
 // posterior of the naive sequence (one tree / importance-weighted over a RevBayes table), and --naive-probs /
-// --naive-probs-pipeline, exact posterior probabilities of naive sequences (tabulate_naive_probs.py's table).
+// --naive-probs-pipeline, exact posterior probabilities of naive sequences (tabulate_naive_probs.py's table), and
+// --lineage-pipeline / --lineage-trees, the ancestral lineage tables of a seed sequence (tabulate_lineage_probs.py's).
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -14,6 +15,7 @@
 #include <thread>
 #include <vector>
 
+#include "Lineage.hpp"
 #include "NaiveProbs.hpp"
 #include "PhyloHMM.hpp"
 
@@ -58,7 +60,7 @@ int main(int argc, char** argv) {
   try {
     if (argc < 2 || std::string(argv[1]) == "-h" || std::string(argv[1]) == "--help") {
       std::cout << "A Phylo-HMM implementation for B cell receptor sequence analysis.\n"
-                   "USAGE: linearham {--compute-logl|--sample|--pipeline|--asr|--marginals|--marginals-pipeline|--naive-probs|--naive-probs-pipeline} --yaml-path <string> "
+                   "USAGE: linearham {--compute-logl|--sample|--pipeline|--asr|--marginals|--marginals-pipeline|--naive-probs|--naive-probs-pipeline|--lineage-pipeline} --yaml-path <string> "
                    "--cluster-ind <int> --hmm-param-dir <string> [--seed <int>] [--num-rates <int>] [--extended-range <0|1>] "
                    "[--devices <a,b,...>] ...\n"
                    "  --marginals: the arguments of --compute-logl; prints the per-site naive-base table and the gene table\n"
@@ -68,7 +70,11 @@ int main(int argc, char** argv) {
                    "    probability of every candidate naive sequence for that tree\n"
                    "  --naive-probs-pipeline --input-path <RevBayes table> --output-path <prefix> [--burnin-frac <f>]\n"
                    "    [--candidates-path <file>] [--max-candidates <n>]: writes <prefix>.naive.tsv, <prefix>.aa.fasta,\n"
-                   "    <prefix>.dnamap and <prefix>.summary.tsv (one device)\n";
+                   "    <prefix>.dnamap and <prefix>.summary.tsv (one device)\n"
+                   "  --lineage-pipeline --input-path <--pipeline table> --output-path <prefix> --seed-seq <name> [--seed <int>]:\n"
+                   "    the lineage tables of the sequence <name>: <prefix>.fasta, .dnamap, .nodes.tsv, .edges.tsv, .summary.tsv\n"
+                   "       linearham --lineage-trees --input-path <--asr trees> --output-path <prefix> --seed-seq <name>\n"
+                   "    the same tables from a file --asr wrote (no family, no device)\n";
       return argc < 2 ? EXIT_FAILURE : EXIT_SUCCESS;
     }
     const auto t_main = std::chrono::steady_clock::now();
@@ -76,9 +82,13 @@ int main(int argc, char** argv) {
     auto since_start = [&] { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t_main).count(); };
     const std::string subcmd = argv[1];
     const Args a = Parse(argc, argv, 2);
+    if (subcmd == "--lineage-trees") {
+      linearham::TabulateLineageTrees(a.one("input-path"), a.one("seed-seq"), a.one("output-path"));
+      return EXIT_SUCCESS;
+    }
     if (subcmd != "--compute-logl" && subcmd != "--sample" && subcmd != "--pipeline" && subcmd != "--asr" &&
         subcmd != "--marginals" && subcmd != "--marginals-pipeline" && subcmd != "--naive-probs" &&
-        subcmd != "--naive-probs-pipeline")
+        subcmd != "--naive-probs-pipeline" && subcmd != "--lineage-pipeline")
       throw std::invalid_argument("'" + subcmd + "' is not a valid subcommand.");
     const std::string yaml_path = a.one("yaml-path");
     const int cluster_ind = std::stoi(a.one("cluster-ind"));
@@ -141,6 +151,11 @@ int main(int argc, char** argv) {
       phylo_hmm_ptr->RunNaiveProbsPipeline(a.one("input-path"), a.one("output-path"), num_rates,
                                            std::stod(a.opt("burnin-frac", "0")), a.opt("candidates-path", ""),
                                            std::stoi(a.opt("max-candidates", "65536")));
+      return EXIT_SUCCESS;
+    }
+    if (subcmd == "--lineage-pipeline") {
+      phylo_hmm_ptr->RunLineagePipeline(a.one("input-path"), a.one("seed-seq"), a.one("output-path"),
+                                        (uint64_t)std::stoll(a.opt("seed", "0")));
       return EXIT_SUCCESS;
     }
     if (subcmd == "--asr") {

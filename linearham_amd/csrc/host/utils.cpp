@@ -104,6 +104,7 @@ const HostOptions& host_options() {
     o.host_sampling = std::getenv("LH_HOST_SAMPLING") != nullptr;
     if (const char* e = std::getenv("LH_HOST_THREADS")) o.host_threads = std::max(1, std::atoi(e));
     if (const char* e = std::getenv("LH_PIPELINE_BATCH")) o.pipeline_batch = std::max(1, std::atoi(e));
+    if (const char* e = std::getenv("LH_LINEAGE_BATCH")) o.lineage_batch = std::max(1, std::atoi(e));
     return o;
   }();
   return opts;

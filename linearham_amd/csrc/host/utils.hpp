@@ -75,6 +75,7 @@ struct HostOptions {
   bool host_sampling = false;    // LH_HOST_SAMPLING: HMM::SampleRow on the host even where the device sampler could run
   int host_threads = 0;          // LH_HOST_THREADS=<n>: worker threads per host stage (0: from the affinity mask)
   int pipeline_batch = 0;        // LH_PIPELINE_BATCH=<n>: rows per batch of RunNaiveProbsPipeline (0: 49 152)
+  int lineage_batch = 0;         // LH_LINEAGE_BATCH=<n>: rows per batch of RunLineagePipeline (0: 1 024, RunAsr's)
 };
 const HostOptions& host_options();
 

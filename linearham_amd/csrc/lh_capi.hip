@@ -195,6 +195,19 @@ struct CollectWs {
   size_t cap = 0;  // candidates store[cur] holds room for
 };
 
+// K7 (lh_lineage.hip): the last lineage batch (its arrays belong to the caller, or to the handle after lh_lineage_batch)
+// and the lineage store lh_lineage_resolve appends to (store[cur], K sequences; grown as CollectWs's is).
+struct LineageWs {
+  DevBuf naive, path, nt_hash, aa_hash;  // lh_lineage_batch's device copies
+  DevBuf ids, flag, pairs, gather_slots, gather_out;
+  DevBuf store[2];
+  int cur = 0;
+  int32_t K = 0;
+  size_t cap = 0;
+  lh::LineageBatch last{};  // last.n < 0: no batch
+  LineageWs() { last.n = -1; }
+};
+
 // Device copies of the host-pointer entry points' arrays.  The entry points share them on purpose: each waits for the device
 // before it fills them and before it returns, and a handle is driven by one thread at a time.
 struct HostInputs {
@@ -242,6 +255,7 @@ struct lh_family {
   PosteriorWs post;
   CandidateWs cand;
   CollectWs collect;
+  LineageWs lineage;
   // forward arrays that stay on the device, shared by K4 and K5 in both their forms: K4 draws from them, K5 overwrites
   // them with the posteriors (calls on a handle do not overlap: they also share the workspace)
   DevBuf forward_dev;
@@ -254,6 +268,7 @@ struct lh_family {
   KernelTimer<1> asr_timer, post_timer;
   KernelTimer<1> prior_timer, cand_timer;  // K6a, K6b
   KernelTimer<1> collect_timer;             // K6c
+  KernelTimer<1> lineage_timer;             // K7
   bool extended = false;  // lh_family_set_extended_range
   bool have_sampler = false;
   lh::DevSampler sampler{};  // device pointers inside (arena)
@@ -2087,6 +2102,204 @@ int lh_collect_profile_read(lh_family* f, double* ms, int64_t* n_launches) {
   if (!f) return fail("null family");
   DeviceGuard guard(f);
   return f->collect_timer.read(ms, n_launches);
+}
+
+}  // extern "C"
+
+// ---- K7: the lineage of a seed sequence, and the lineage store (lh_lineage.hip) ----
+
+extern "C" {
+
+int lh_lineage_collect_device(lh_family* f, int32_t n, int32_t T, const uint8_t* anc, const uint8_t* naive,
+                              const int32_t* path, int32_t P, uint64_t* nt_hash, uint64_t* aa_hash, void* hip_stream) {
+  const std::string W = "lh_lineage_collect_device";
+  if (!f) return fail(W + ": null family");
+  if (n < 0) return fail(W + ": negative batch size");
+  if (f->host.n_seqs < 1) return fail(W + ": family was created without an MSA (forward-only)");
+  if (T != f->host.n_seqs + 1 || T < 3) return fail(W + ": n_tips must equal n_seqs + 1 (naive), at least 3");
+  if (P < 1 || P > T - 2) return fail(W + ": path length must be in 1 .. n_tips - 2");
+  if ((size_t)n * (size_t)(P + 1) > (size_t)INT32_MAX) return fail(W + ": too many lineage slots for one batch");
+  DeviceGuard guard(f);
+  LineageWs& w = f->lineage;
+  w.last.n = -1;
+  if (n == 0) return 0;
+  if (!anc || !naive || !path || !nt_hash || !aa_hash) return fail(W + ": null array");
+  const int bits = lh::debug_options().collect_hash_bits;
+  const lh::LineageBatch b{n, T, f->host.n_sites, P, anc, naive, path, bits >= 64 ? ~0ull : ((1ull << bits) - 1)};
+  hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+  if (f->profile && f->lineage_timer.begin(stream)) return 1;
+  lh::launch_lineage(b, nt_hash, aa_hash, stream);
+  LH_HIP(hipGetLastError());
+  if (f->profile && f->lineage_timer.end(stream)) return 1;
+  w.last = b;
+  return 0;
+}
+
+int lh_lineage_batch(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops, const double* brlen,
+                     const double* er, const double* pi, const double* rates, int32_t R, const uint8_t* naive,
+                     uint64_t seed, uint64_t first_sample, const int32_t* path, int32_t P, uint64_t* nt_hash,
+                     uint64_t* aa_hash) {
+  const std::string W = "lh_lineage_batch";
+  if (int rc = check_batch(f, W, n, T, R, max_depth)) {
+    if (rc < 0) f->lineage.last.n = -1;
+    return rc > 0;
+  }
+  DeviceGuard guard(f);
+  f->lineage.last.n = -1;
+  if (!ops || !brlen || !er || !pi || !rates || !naive || !path || !nt_hash || !aa_hash) return fail(W + ": null array");
+  if (P < 1 || P > T - 2) return fail(W + ": path length must be in 1 .. n_tips - 2");
+  const size_t nodes = 2 * (size_t)T - 2, n_ops = (size_t)T - 2, L = f->host.n_sites;
+  // the whole batch's anc stays on the device for lh_lineage_resolve: no sub-batches here
+  const size_t most = std::min<size_t>(((size_t)1 << 30) / std::max<size_t>(n_ops * L, 1), (size_t)INT32_MAX / (P + 1));
+  if ((size_t)n > most)
+    return fail(W + ": batch too large to keep its sampled states on the device: at most " + std::to_string(most) +
+                " samples per call for this family");
+  if (!valid_schedules(ops, (size_t)n, T, (int)nodes, max_depth))
+    return fail(W + ": malformed schedule op (use lh_schedule_tree)");
+  for (size_t k = 0; k < (size_t)n * L; ++k)
+    if (naive[k] > 4) return fail(W + ": naive base out of range");
+  for (size_t i = 0; i < (size_t)n; ++i) {
+    bool ended = false;
+    for (int s = 0; s < P; ++s) {
+      const int32_t v = path[i * P + s];
+      if (v == -1) ended = true;
+      else if (ended || v < T || v >= (int32_t)nodes) return fail(W + ": path entries are inner nodes, then -1 padding");
+    }
+    if (path[i * P] == -1) return fail(W + ": empty path");
+  }
+  HostInputs& in = f->in;
+  HostOutputs& out = f->out;
+  LineageWs& w = f->lineage;
+  const size_t hb = sizeof(uint64_t) * n * (P + 1);
+  if (out.anc.ensure(n_ops * L * n) || out.rate_choice.ensure(L * n) || w.nt_hash.ensure(hb) || w.aa_hash.ensure(hb) ||
+      stage_inputs(f, {{ops, sizeof(int32_t) * 4 * n_ops * n, &in.ops},
+                       {brlen, sizeof(double) * nodes * n, &in.brlen},
+                       {er, sizeof(double) * 6 * n, &in.er},
+                       {pi, sizeof(double) * 4 * n, &in.pi},
+                       {rates, sizeof(double) * R * n, &in.rates},
+                       {naive, L * n, &w.naive},
+                       {path, sizeof(int32_t) * P * n, &w.path}}))
+    return 1;
+  if (lh_asr_batch_device(f, n, T, max_depth, in.ops.get<const int32_t>(), in.brlen.get<const double>(),
+                          in.er.get<const double>(), in.pi.get<const double>(), in.rates.get<const double>(), R,
+                          w.naive.get<const uint8_t>(), seed, first_sample, out.anc.get<uint8_t>(),
+                          out.rate_choice.get<uint8_t>(), nullptr))
+    return 1;
+  if (lh_lineage_collect_device(f, n, T, out.anc.get<const uint8_t>(), w.naive.get<const uint8_t>(),
+                                w.path.get<const int32_t>(), P, w.nt_hash.get<uint64_t>(), w.aa_hash.get<uint64_t>(),
+                                nullptr))
+    return 1;
+  if (copy_back(f, "lh_lineage_batch", {{nt_hash, w.nt_hash.get(), hb}, {aa_hash, w.aa_hash.get(), hb}})) {
+    w.last.n = -1;
+    return 1;
+  }
+  return 0;
+}
+
+int lh_lineage_resolve(lh_family* f, int32_t n_slots, const int32_t* ids, int32_t* n_mismatch, int32_t* mismatch_slots) {
+  const std::string W = "lh_lineage_resolve";
+  if (!f) return fail(W + ": null family");
+  DeviceGuard guard(f);
+  LineageWs& w = f->lineage;
+  const lh::LineageBatch& b = w.last;
+  if (b.n < 0) return fail(W + ": no lineage batch on the handle");
+  if (n_slots != b.n * (b.P + 1)) return fail(W + ": n_slots differs from the last batch's rows x (path length + 1)");
+  if (n_slots > 0 && !ids) return fail(W + ": null array");
+  const int L = b.L;
+  // new sequences: ids K .. K_new - 1, each with a first slot in this batch
+  int32_t K_new = w.K;
+  for (int32_t x = 0; x < n_slots; ++x) {
+    if (ids[x] < -1) return fail(W + ": sequence id below -1");
+    K_new = std::max(K_new, ids[x] + 1);
+  }
+  std::vector<int32_t> first((size_t)(K_new - w.K), -1), pairs;
+  for (int32_t x = 0; x < n_slots; ++x)
+    if (ids[x] >= w.K && first[ids[x] - w.K] < 0) first[ids[x] - w.K] = x;
+  for (size_t k = 0; k < first.size(); ++k) {
+    if (first[k] < 0) return fail(W + ": new sequence ids must be consecutive, each with a slot of the batch");
+    pairs.push_back(w.K + (int32_t)k);
+    pairs.push_back(first[k]);
+  }
+  LH_HIP(hipDeviceSynchronize());
+  if ((size_t)K_new > w.cap) {  // grow the store, keeping what it holds
+    const size_t cap = std::max<size_t>({(size_t)K_new, 2 * w.cap, 256});
+    DevBuf& nb = w.store[w.cur ^ 1];
+    if (nb.ensure(cap * L)) return 1;
+    if (w.K > 0) LH_HIP(hipMemcpy(nb.get(), w.store[w.cur].get(), (size_t)w.K * L, hipMemcpyDeviceToDevice));
+    w.cur ^= 1;
+    w.cap = cap;
+  }
+  if (n_slots == 0) {
+    if (n_mismatch) *n_mismatch = 0;
+    return 0;
+  }
+  if (w.ids.ensure(sizeof(int32_t) * n_slots) || w.flag.ensure(n_slots) || w.pairs.ensure(sizeof(int32_t) * pairs.size()))
+    return 1;
+  LH_HIP(hipMemcpy(w.ids.get(), ids, sizeof(int32_t) * n_slots, hipMemcpyHostToDevice));
+  if (!pairs.empty()) LH_HIP(hipMemcpy(w.pairs.get(), pairs.data(), sizeof(int32_t) * pairs.size(), hipMemcpyHostToDevice));
+  uint8_t* store = w.store[w.cur].get<uint8_t>();
+  lh::launch_lineage_append(b, (int)(pairs.size() / 2), K_new, w.pairs.get<const int32_t>(), store, nullptr);
+  lh::launch_lineage_verify(b, K_new, w.ids.get<const int32_t>(), store, w.flag.get<uint8_t>(), nullptr);
+  LH_HIP(hipGetLastError());
+  std::vector<uint8_t> flag(n_slots);
+  LH_HIP(hipMemcpy(flag.data(), w.flag.get(), n_slots, hipMemcpyDeviceToHost));
+  w.K = K_new;
+  int32_t m = 0;
+  for (int32_t x = 0; x < n_slots; ++x)
+    if (flag[x]) {
+      if (mismatch_slots) mismatch_slots[m] = x;
+      ++m;
+    }
+  if (n_mismatch) *n_mismatch = m;
+  return 0;
+}
+
+int lh_lineage_rows_read(lh_family* f, int32_t n_slots, const int32_t* slots, uint8_t* seqs) {
+  const std::string W = "lh_lineage_rows_read";
+  if (!f) return fail(W + ": null family");
+  DeviceGuard guard(f);
+  LineageWs& w = f->lineage;
+  const lh::LineageBatch& b = w.last;
+  if (b.n < 0) return fail(W + ": no lineage batch on the handle");
+  if (n_slots > 0 && (!slots || !seqs)) return fail(W + ": null array");
+  for (int32_t k = 0; k < n_slots; ++k)
+    if (slots[k] < 0 || slots[k] >= b.n * (b.P + 1)) return fail(W + ": slot outside the last batch");
+  if (n_slots <= 0) return 0;
+  const size_t bytes = (size_t)n_slots * b.L;
+  if (w.gather_slots.ensure(sizeof(int32_t) * n_slots) || w.gather_out.ensure(bytes)) return 1;
+  LH_HIP(hipDeviceSynchronize());
+  LH_HIP(hipMemcpy(w.gather_slots.get(), slots, sizeof(int32_t) * n_slots, hipMemcpyHostToDevice));
+  lh::launch_lineage_gather(b, n_slots, w.gather_slots.get<const int32_t>(), w.gather_out.get<uint8_t>(), nullptr);
+  LH_HIP(hipGetLastError());
+  LH_HIP(hipMemcpy(seqs, w.gather_out.get(), bytes, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int lh_lineage_store_read(lh_family* f, int32_t first, int32_t count, int32_t* K, uint8_t* seqs) {
+  const std::string W = "lh_lineage_store_read";
+  if (!f) return fail(W + ": null family");
+  DeviceGuard guard(f);
+  LineageWs& w = f->lineage;
+  if (K) *K = w.K;
+  if (!seqs || count == 0) return 0;
+  if (first < 0 || count < 0 || first > w.K || count > w.K - first) return fail(W + ": ids outside the store");
+  const size_t L = f->host.n_sites;
+  LH_HIP(hipDeviceSynchronize());
+  LH_HIP(hipMemcpy(seqs, w.store[w.cur].get<uint8_t>() + (size_t)first * L, (size_t)count * L, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int lh_lineage_reset(lh_family* f) {
+  if (!f) return fail("lh_lineage_reset: null family");
+  f->lineage.K = 0;
+  f->lineage.last.n = -1;
+  return 0;
+}
+
+int lh_lineage_profile_read(lh_family* f, double* ms, int64_t* n_launches) {
+  if (!f) return fail("null family");
+  DeviceGuard guard(f);
+  return f->lineage_timer.read(ms, n_launches);
 }
 
 }  // extern "C"

@@ -24,12 +24,6 @@ namespace {
 constexpr int kThreads = 256;
 constexpr int kRowsPerBlock = kThreads / 64;
 
-__device__ inline uint64_t mix64(uint64_t z) {  // the splitmix64 finaliser
-  z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
-  z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
-  return z ^ (z >> 31);
-}
-
 __device__ inline void put(const CollectTables& t, uint8_t* s, int col) {
   if (col < 0 || col >= t.n_cols) return;
   const int site = t.col_site[col];
@@ -102,7 +96,7 @@ __global__ void __launch_bounds__(kThreads)
     uint64_t word = 0;
 #pragma unroll
     for (int b = 0; b < 8; ++b) word |= (uint64_t)s[q * 8 + b] << (8 * b);
-    h ^= mix64(word + 0x9e3779b97f4a7c15ull * (uint64_t)(q + 1));
+    h ^= hash_word(word, q);
   }
   uint32_t lo = (uint32_t)h, hi = (uint32_t)(h >> 32);
 #pragma unroll
@@ -112,7 +106,7 @@ __global__ void __launch_bounds__(kThreads)
   }
   uint8_t* out = seqs + (size_t)r * t.L;
   for (int j = lane; j < t.L; j += 64) out[j] = s[j];
-  if (lane == 0) hash[r] = mix64((((uint64_t)hi << 32) | lo) ^ (uint64_t)t.L) & t.hash_mask;
+  if (lane == 0) hash[r] = hash_finish(((uint64_t)hi << 32) | lo, t.L) & t.hash_mask;
 }
 
 // flag[i] = 1 where row i's bytes differ from those of candidate cand[i] (0 for rows with cand[i] < 0)

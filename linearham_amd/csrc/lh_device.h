@@ -233,6 +233,18 @@ struct CollectTables {
   uint64_t hash_mask;  // ~0, or the low LH_COLLECT_HASH_BITS bits (DebugOptions)
 };
 // seqs[n][L] (A,C,G,T,N = 0..4) and hash[n] of states[n][states_per_sample]
+// The sequence hash K6c and K7 share: XOR over the sequence's 8-byte words (little-endian, padded to a whole word) of a
+// 64-bit mix of (word, position), then one more mix with the length.  XOR is exact and order-free.
+__host__ __device__ inline uint64_t mix64(uint64_t z) {  // the splitmix64 finaliser
+  z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+  z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+  return z ^ (z >> 31);
+}
+__host__ __device__ inline uint64_t hash_word(uint64_t word, int q) {
+  return mix64(word + 0x9e3779b97f4a7c15ull * (uint64_t)(q + 1));
+}
+__host__ __device__ inline uint64_t hash_finish(uint64_t h, int length) { return mix64(h ^ (uint64_t)length); }
+
 void launch_collect(const CollectTables& t, int n, const int32_t* states, uint8_t* seqs, uint64_t* hash, hipStream_t stream);
 size_t collect_lds_bytes(int L);
 // flag[n]: 1 where row i differs from store[cand[i]] (cand[i] < 0: 0; cand[i] >= K: 1)
@@ -244,6 +256,27 @@ void launch_collect_append(int n_pairs, int n, int L, int K, const int32_t* pair
 // out[q][..] = seqs[rows[q]][..] for q < n_rows (rows outside 0..n-1 read as N)
 void launch_collect_gather(int n_rows, int n, int L, const int32_t* rows, const uint8_t* seqs, uint8_t* out,
                            hipStream_t stream);
+
+// K7 (lh_lineage.hip): the lineage slots of a batch.  Slot s < P of sample i is the row anc[i][path[i*P + s] - T][0..L)
+// of K3's output (path entries outside T .. 2T-3 are padding), slot P the row naive[i][0..L).  A flat slot is i*(P+1)+s.
+struct LineageBatch {
+  int32_t n, T, L, P;
+  const uint8_t* anc;    // [n][T-2][L]
+  const uint8_t* naive;  // [n][L]
+  const int32_t* path;   // [n][P]
+  uint64_t hash_mask;
+};
+constexpr uint64_t kLineagePadHash = 0;  // LH_LINEAGE_PAD_HASH
+// nt_hash, aa_hash [n][P+1]
+void launch_lineage(const LineageBatch& b, uint64_t* nt_hash, uint64_t* aa_hash, hipStream_t stream);
+// flag[x] = 1 where flat slot x differs from store[ids[x]] (ids[x] < 0: 0; ids[x] >= K or a padding slot: 1)
+void launch_lineage_verify(const LineageBatch& b, int K, const int32_t* ids, const uint8_t* store, uint8_t* flag,
+                           hipStream_t stream);
+// store[pairs[2p]] = flat slot pairs[2p + 1] for p < n_pairs
+void launch_lineage_append(const LineageBatch& b, int n_pairs, int K, const int32_t* pairs, uint8_t* store,
+                           hipStream_t stream);
+// out[q][..] = flat slot slots[q] for q < n_slots (padding slots read as N)
+void launch_lineage_gather(const LineageBatch& b, int n_slots, const int32_t* slots, uint8_t* out, hipStream_t stream);
 
 // P = I + U expm1(lambda * t*r) Uinv, clamped at 0 (K1's prologue).
 // e: lambda[4] | U[4][4] | Uinv[4][4]

@@ -1,0 +1,200 @@
+// K7: the lineage of a seed sequence, collected on the device (gfx950).
+//
+// A tree sample's lineage is the chain of inner nodes from the seed tip's parent up to the tree's root (naive's
+// neighbour), then naive itself.  K3 leaves the sampled states of every inner node in anc[n][T-2][L]; the lineage needs
+// only the P or fewer rows on that chain, and the host needs of each row only whether it has seen the sequence before.
+// So the rows stay where they are and two 64-bit hashes per row come back: one of the bases, one of their translation.
+//
+// lineage_kernel: one wave per (sample, slot).  A lane takes 24 consecutive bases: three 8-byte words of the base hash
+// and, translated codon by codon (standard code, frame 0, a codon with N = the one symbol all its resolutions give,
+// else X: TranslateDna), one 8-byte word of the amino-acid hash.  The hash is K6c's (lh_device.h: XOR over the words
+// of a mix of (word, position), a final mix with the length), so its bits depend on the sequence alone and a naive
+// sequence hashes here as it does there.  Padding slots get kLineagePadHash; a sample whose schedule K3 refused (0xff in
+// its anc rows) gets all-ones in every slot.
+// verify / append / gather: lh_collect.hip's three, with a row found through the path instead of a row number.
+// No atomics anywhere; every output element has one writer.  Path entries are checked before they index anything.
+#include <algorithm>
+
+#include "lh_device.h"
+
+namespace lh {
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kSlotsPerBlock = kThreads / 64;
+constexpr int kChunk = 24;  // bases per lane and step: 3 base words, 8 codons
+
+// amino acid of the codon (a, b, c), bases A,C,G,T,N = 0..4, at [a*25 + b*5 + c]
+struct CodonTable {
+  uint8_t aa[125];
+};
+constexpr CodonTable make_codon_table() {
+  // the standard code over T, C, A, G (first base slowest)
+  const char code[] = "FFLLSSSSYY**CC*WLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG";
+  const int tcag[4] = {2, 1, 3, 0};  // A, C, G, T -> position in TCAG
+  CodonTable t{};
+  for (int a = 0; a < 5; ++a)
+    for (int b = 0; b < 5; ++b)
+      for (int c = 0; c < 5; ++c) {
+        char aa = 0;
+        for (int x = 0; x < 4; ++x)
+          for (int y = 0; y < 4; ++y)
+            for (int z = 0; z < 4; ++z) {
+              if ((a < 4 && x != a) || (b < 4 && y != b) || (c < 4 && z != c)) continue;
+              const char r = code[tcag[x] * 16 + tcag[y] * 4 + tcag[z]];
+              aa = (aa == 0 || aa == r) ? r : 'X';
+            }
+        t.aa[a * 25 + b * 5 + c] = (uint8_t)aa;
+      }
+  return t;
+}
+__device__ const CodonTable kCodons = make_codon_table();
+
+__device__ inline uint8_t translate(uint8_t a, uint8_t b, uint8_t c) {
+  return (a > 4 || b > 4 || c > 4) ? (uint8_t)'X' : kCodons.aa[a * 25 + b * 5 + c];
+}
+
+// the row of flat slot (i, s), null for a padding slot
+__device__ inline const uint8_t* slot_row(const LineageBatch& b, int i, int s) {
+  if (s == b.P) return b.naive + (size_t)i * b.L;
+  const int v = b.path[(size_t)i * b.P + s];
+  if (v < b.T || v >= 2 * b.T - 2) return nullptr;
+  return b.anc + ((size_t)i * (b.T - 2) + (v - b.T)) * b.L;
+}
+
+__device__ inline uint64_t wave_xor(uint64_t h) {
+  uint32_t lo = (uint32_t)h, hi = (uint32_t)(h >> 32);
+#pragma unroll
+  for (int m = 1; m < 64; m <<= 1) {
+    lo ^= (uint32_t)__shfl_xor((int)lo, m, 64);
+    hi ^= (uint32_t)__shfl_xor((int)hi, m, 64);
+  }
+  return ((uint64_t)hi << 32) | lo;
+}
+
+__global__ void __launch_bounds__(kThreads)
+    lineage_kernel(LineageBatch b, uint64_t* __restrict__ nt_hash, uint64_t* __restrict__ aa_hash) {
+  const int lane = threadIdx.x & 63;
+  const size_t x = (size_t)blockIdx.x * kSlotsPerBlock + (threadIdx.x >> 6);
+  if (x >= (size_t)b.n * (b.P + 1)) return;
+  const int i = (int)(x / (b.P + 1)), s = (int)(x % (b.P + 1));
+  const int L = b.L;
+  const uint8_t* row = slot_row(b, i, s);
+  // (K3 writes 0xff into every anc byte of a sample whose schedule it refuses; sampled states are 0..3)
+  const bool refused = L > 0 && b.anc[(size_t)i * (b.T - 2) * L] == 0xff;
+  if (refused || !row) {
+    if (lane == 0) nt_hash[x] = aa_hash[x] = refused ? ~0ull : kLineagePadHash;
+    return;
+  }
+  const int n_words = (L + 7) / 8, n_aa = L / 3, n_aa_words = (n_aa + 7) / 8;
+  const int n_chunks = (L + kChunk - 1) / kChunk;  // covers both: 3 * n_chunks >= n_words, n_chunks >= n_aa_words
+  uint64_t h_nt = 0, h_aa = 0;
+  for (int c = lane; c < n_chunks; c += 64) {
+    uint8_t base[kChunk];
+#pragma unroll
+    for (int k = 0; k < kChunk; ++k) {
+      const int j = c * kChunk + k;
+      base[k] = j < L ? row[j] : (uint8_t)4;  // (K6c pads its last word with N)
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const int q = 3 * c + k;
+      uint64_t word = 0;
+#pragma unroll
+      for (int m = 0; m < 8; ++m) word |= (uint64_t)base[8 * k + m] << (8 * m);
+      if (q < n_words) h_nt ^= hash_word(word, q);
+    }
+    if (c < n_aa_words) {
+      uint64_t word = 0;
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        const uint8_t aa = 8 * c + k < n_aa ? translate(base[3 * k], base[3 * k + 1], base[3 * k + 2]) : (uint8_t)0;
+        word |= (uint64_t)aa << (8 * k);
+      }
+      h_aa ^= hash_word(word, c);
+    }
+  }
+  h_nt = wave_xor(h_nt);
+  h_aa = wave_xor(h_aa);
+  if (lane == 0) {
+    nt_hash[x] = hash_finish(h_nt, L) & b.hash_mask;
+    aa_hash[x] = hash_finish(h_aa, n_aa) & b.hash_mask;
+  }
+}
+
+__global__ void __launch_bounds__(kThreads)
+    lineage_verify_kernel(LineageBatch b, int K, const int32_t* __restrict__ ids, const uint8_t* __restrict__ store,
+                          uint8_t* __restrict__ flag) {
+  const int lane = threadIdx.x & 63;
+  const size_t x = (size_t)blockIdx.x * kSlotsPerBlock + (threadIdx.x >> 6);
+  if (x >= (size_t)b.n * (b.P + 1)) return;
+  const int k = ids[x];
+  const uint8_t* row = k >= 0 ? slot_row(b, (int)(x / (b.P + 1)), (int)(x % (b.P + 1))) : nullptr;
+  bool diff = false;
+  if (row && k < K) {
+    const uint8_t* st = store + (size_t)k * b.L;
+    for (int j = lane; j < b.L; j += 64) diff |= row[j] != st[j];
+  }
+  const bool any = __any(diff);
+  if (lane == 0) flag[x] = k >= 0 && (k >= K || !row || any) ? 1 : 0;
+}
+
+__global__ void __launch_bounds__(kThreads)
+    lineage_append_kernel(LineageBatch b, int n_pairs, int K, const int32_t* __restrict__ pairs,
+                          uint8_t* __restrict__ store) {
+  const size_t total = (size_t)n_pairs * b.L, slots = (size_t)b.n * (b.P + 1);
+  for (size_t x = (size_t)blockIdx.x * kThreads + threadIdx.x; x < total; x += (size_t)gridDim.x * kThreads) {
+    const size_t p = x / b.L, j = x % b.L;
+    const int k = pairs[2 * p], y = pairs[2 * p + 1];
+    if (k < 0 || k >= K || y < 0 || (size_t)y >= slots) continue;
+    const uint8_t* row = slot_row(b, y / (b.P + 1), y % (b.P + 1));
+    if (row) store[(size_t)k * b.L + j] = row[j];
+  }
+}
+
+__global__ void __launch_bounds__(kThreads)
+    lineage_gather_kernel(LineageBatch b, int n_slots, const int32_t* __restrict__ slots_in, uint8_t* __restrict__ out) {
+  const size_t total = (size_t)n_slots * b.L, slots = (size_t)b.n * (b.P + 1);
+  for (size_t x = (size_t)blockIdx.x * kThreads + threadIdx.x; x < total; x += (size_t)gridDim.x * kThreads) {
+    const size_t q = x / b.L, j = x % b.L;
+    const int y = slots_in[q];
+    const uint8_t* row = (y >= 0 && (size_t)y < slots) ? slot_row(b, y / (b.P + 1), y % (b.P + 1)) : nullptr;
+    out[x] = row ? row[j] : (uint8_t)4;
+  }
+}
+
+unsigned slot_blocks(const LineageBatch& b) {
+  return (unsigned)(((size_t)b.n * (b.P + 1) + kSlotsPerBlock - 1) / kSlotsPerBlock);
+}
+unsigned byte_blocks(size_t total) {
+  return (unsigned)std::max<size_t>(1, std::min<size_t>((total + kThreads - 1) / kThreads, 4096));
+}
+
+}  // namespace
+
+void launch_lineage(const LineageBatch& b, uint64_t* nt_hash, uint64_t* aa_hash, hipStream_t stream) {
+  if (b.n <= 0) return;
+  hipLaunchKernelGGL(lineage_kernel, dim3(slot_blocks(b)), dim3(kThreads), 0, stream, b, nt_hash, aa_hash);
+}
+
+void launch_lineage_verify(const LineageBatch& b, int K, const int32_t* ids, const uint8_t* store, uint8_t* flag,
+                           hipStream_t stream) {
+  if (b.n <= 0) return;
+  hipLaunchKernelGGL(lineage_verify_kernel, dim3(slot_blocks(b)), dim3(kThreads), 0, stream, b, K, ids, store, flag);
+}
+
+void launch_lineage_append(const LineageBatch& b, int n_pairs, int K, const int32_t* pairs, uint8_t* store,
+                           hipStream_t stream) {
+  if (n_pairs <= 0 || b.n <= 0) return;
+  hipLaunchKernelGGL(lineage_append_kernel, dim3(byte_blocks((size_t)n_pairs * b.L)), dim3(kThreads), 0, stream, b,
+                     n_pairs, K, pairs, store);
+}
+
+void launch_lineage_gather(const LineageBatch& b, int n_slots, const int32_t* slots, uint8_t* out, hipStream_t stream) {
+  if (n_slots <= 0 || b.n <= 0) return;
+  hipLaunchKernelGGL(lineage_gather_kernel, dim3(byte_blocks((size_t)n_slots * b.L)), dim3(kThreads), 0, stream, b,
+                     n_slots, slots, out);
+}
+
+}  // namespace lh

@@ -131,6 +131,38 @@ def _parse_summary(text):
     return out
 
 
+def read_lineage(prefix):
+    """The files RunLineagePipeline / tabulate_lineage_trees write: dict(fasta = [(name, aa)] of <prefix>.fasta,
+    dnamap = {name: [(fraction, dna)]} of <prefix>.dnamap, nodes = [dict(name, kind, count, fraction)] of
+    <prefix>.nodes.tsv, edges = [dict(parent, child, count, fraction, parent_fraction, mutations = list)] of
+    <prefix>.edges.tsv, summary = {key: int} of <prefix>.summary.tsv), all in file order."""
+    fa = open(prefix + ".fasta").read().strip("\n").split("\n")
+    fasta = [(fa[i][1:], fa[i + 1]) for i in range(0, len(fa) - 1, 2)]
+
+    def table(path):
+        lines = open(path).read().strip("\n").split("\n")
+        head = lines[0].split("\t")
+        return [dict(zip(head, ln.split("\t") + [""] * (len(head) - len(ln.split("\t"))))) for ln in lines[1:]]
+
+    nodes = [dict(name=d["name"], kind=d["kind"], count=int(d["count"]), fraction=float(d["fraction"]))
+             for d in table(prefix + ".nodes.tsv")]
+    edges = [dict(parent=d["parent"], child=d["child"], count=int(d["count"]), fraction=float(d["fraction"]),
+                  parent_fraction=float(d["parent_fraction"]), mutations=d["mutations"].split())
+             for d in table(prefix + ".edges.tsv")]
+    summary = {d["key"]: int(d["value"]) for d in table(prefix + ".summary.tsv")}
+    return dict(fasta=fasta, dnamap=_parse_dnamap(open(prefix + ".dnamap").read()), nodes=nodes, edges=edges,
+                summary=summary)
+
+
+def tabulate_lineage_trees(trees_path, seed_seq, output_prefix):
+    """Lineage.hpp TabulateLineageTrees (tabulate_lineage_probs.py on a file PhyloHMM.run_asr wrote; no family, no
+    GPU); returns read_lineage(output_prefix)."""
+    lib = load_host()
+    lib.lhh_lineage_tabulate_trees.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p]
+    _check(lib.lhh_lineage_tabulate_trees(trees_path.encode(), seed_seq.encode(), output_prefix.encode()))
+    return read_lineage(output_prefix)
+
+
 def translate(dna):
     """The host's translation (NaiveProbs.hpp TranslateDna)."""
     out = C.c_char_p()
@@ -316,6 +348,13 @@ class PhyloHMM(_HMM):
 
     def run_pipeline(self, input_path, output_path, num_rates):
         _check(self.lib.lhh_run_pipeline(self.h, input_path.encode(), output_path.encode(), num_rates))
+
+    def run_lineage_pipeline(self, input_path, seed_seq, output_prefix, seed):
+        """PhyloHMM::RunLineagePipeline; returns read_lineage(output_prefix)."""
+        self.lib.lhh_run_lineage_pipeline.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint64]
+        _check(self.lib.lhh_run_lineage_pipeline(self.h, input_path.encode(), seed_seq.encode(), output_prefix.encode(),
+                                                 seed))
+        return read_lineage(output_prefix)
 
     def run_asr(self, input_path, output_path, seed):
         lib = load_host()
