@@ -15,9 +15,23 @@ namespace lh {
 // (fast_rcp, lh_device.h: the series and the continued fraction below are chains of dependent divisions, and the
 // IEEE division sequence is four times as long.)
 
+// x^a e^-x / Gamma(a), the factor in front of both expansions below.  Term by term its exponent -x + a log x - lgamma(a) is a
+// difference of numbers of size a log a -- 9e4 at a = 1e4 -- that cancel to a few units: 1e-11 relative in the factor, and as
+// much in the category means (a column of log-likelihood -560 multiplies a rate's error by 560: 5.7e-9 on an emission at
+// alpha = 1e4, tests/test_gpu_extreme_parameters.py).  From a = 24 on the large parts are cancelled on paper: with
+// x = a (1 + mu) and Stirling's series lgamma(a) = (a - 1/2) log a - a + log(2 pi) / 2 + delta(a),
+//   x^a e^-x / Gamma(a) = sqrt(a / 2 pi) exp(-delta(a) - a (mu - log1p(mu))),
+// delta(a) = 1/(12 a) - 1/(360 a^3) + 1/(1260 a^5) - 1/(1680 a^7) (the next term is below 3e-16 at a = 24).
+__device__ static double gamma_prefactor(double a, double x, double lga) {
+  if (a < 24.0) return exp(-x + a * log(x) - lga);
+  const double mu = (x - a) / a, ia = 1.0 / a, ia2 = ia * ia;
+  const double delta = ia * (1.0 / 12.0 - ia2 * (1.0 / 360.0 - ia2 * (1.0 / 1260.0 - ia2 * (1.0 / 1680.0))));
+  return sqrt(a * 0.15915494309189535) * exp(-delta - a * (mu - log1p(mu)));
+}
+
 __device__ static double gamma_p(double a, double x, double lga) {
   if (!(x > 0.0)) return 0.0;
-  const double pre = exp(-x + a * log(x) - lga);
+  const double pre = gamma_prefactor(a, x, lga);
   if (x < a + 1.0) {  // series
     double ap = a, del = fast_rcp(a), sum = del;
     for (int n = 0; n < 2000; ++n) {

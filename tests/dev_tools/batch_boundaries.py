@@ -1,6 +1,7 @@
 """Batch sizes around every boundary of lh_eval_batch (host pointers: staging sub-chunks of 12 288 through two pinned slots, launch
 groups of 49 152, launch parts): a small family whose eight distinct tree samples are cycled to n rows; every row's log-likelihood
-and rates must carry the bits of its tree sample's in the 8-row call, whatever n (builder-run).
+and rates must carry the bits of its tree sample's in the 8-row call, whatever n (builder-run; sixteen of these sizes, on eight
+extreme parameter sets, are in the suite: tests/test_gpu_extreme_parameters.py::test_batch_boundaries).
 usage (GPU box, repo root): python tests/dev_tools/batch_boundaries.py"""
 import os
 import shutil

@@ -4,6 +4,10 @@ branch lengths scaled by 1e-2 .. 1e2 -- K0a's eigen-decomposition and discrete-G
 from the generator's comfortable ranges.  What to expect (profiles/r04_extreme_parameters.txt): rates to 1e-11 everywhere; with base
 frequencies of 1e-6 the two CPU restatements themselves differ by up to 5e-9 on the log-likelihood (the eigen-decomposition of the
 symmetrised rate matrix: LAPACK's eigh in numpy, cyclic Jacobi in C), and the kernels -- Jacobi too -- side with the C one to 1e-15.
+The suite now holds this region itself, on a fixed stratified list of rows and against an exact (arbitrary-precision) reference
+instead of one double-precision restatement against the other: tests/test_gpu_extreme_parameters.py (every K1 form),
+tests/test_exact_model_oracle.py and profiles/r06_extreme_parameters_cpu.txt (which restatement is how far from exact).  This
+script stays as the random stream next to that list.
 usage (GPU box, repo root): python tests/dev_tools/extreme_parameters.py [seed] [n_rows]"""
 import os
 import re
