@@ -89,6 +89,31 @@ int HostThreads(int cap) {
   return std::max(1, std::min(avail, cap));
 }
 
+// fn(w, lo, hi) for every worker w < n_threads with its share [lo, hi) of 0 .. total: inline when there is one worker,
+// on threads of their own otherwise.  All are joined; then the first exception in worker order is rethrown here.
+template <class Fn>
+void ForRanges(int n_threads, std::size_t total, Fn&& fn) {
+  std::vector<std::exception_ptr> errors(n_threads);
+  std::vector<std::thread> pool;
+  for (int w = 0; w < n_threads; ++w) {
+    const std::size_t lo = total * w / n_threads, hi = total * (w + 1) / n_threads;
+    auto body = [&, w, lo, hi] {
+      try {
+        fn(w, lo, hi);
+      } catch (...) {
+        errors[w] = std::current_exception();
+      }
+    };
+    if (n_threads == 1)
+      body();
+    else
+      pool.emplace_back(body);
+  }
+  for (std::thread& th : pool) th.join();
+  for (const std::exception_ptr& e : errors)
+    if (e) std::rethrow_exception(e);
+}
+
 SegmentTables MakeSegments(const GeneRanges& ranges, const VectorXi& inds) {
   SegmentTables s;
   s.offsets.push_back(0);
@@ -264,27 +289,11 @@ PhyloHMM::DeviceBatch PhyloHMM::FlattenBatch(const std::vector<TreeSample>& samp
   };
   const int hw = HostThreads(16);
   const int n_threads = std::max(1, std::min(hw, b.n / 64));
-  if (n_threads == 1) {
-    flatten_rows(0, b.n, &b.max_depth);
-  } else {
-    std::vector<std::thread> pool;
-    std::vector<int> depths(n_threads, 0);
-    std::vector<std::exception_ptr> errors(n_threads);
-    for (int t = 0; t < n_threads; ++t) {
-      const int lo = (int)((long long)b.n * t / n_threads), hi = (int)((long long)b.n * (t + 1) / n_threads);
-      pool.emplace_back([&, t, lo, hi] {
-        try {
-          flatten_rows(lo, hi, &depths[t]);
-        } catch (...) {
-          errors[t] = std::current_exception();
-        }
-      });
-    }
-    for (std::thread& th : pool) th.join();
-    for (const std::exception_ptr& e : errors)
-      if (e) std::rethrow_exception(e);  // the first failing row range, in file order
-    for (int d : depths) b.max_depth = std::max(b.max_depth, d);
-  }
+  std::vector<int> depths(n_threads, 0);
+  // (an error: the first failing row range, in file order)
+  ForRanges(n_threads, (std::size_t)b.n,
+            [&](int w, std::size_t lo, std::size_t hi) { flatten_rows((int)lo, (int)hi, &depths[w]); });
+  for (int d : depths) b.max_depth = std::max(b.max_depth, d);
   return b;
 }
 
@@ -750,6 +759,15 @@ struct PhyloHMM::TsvTable {
     return t;
   }
 
+  // a RevBayes output table with the columns of RunPipeline's fifteen fields located
+  static TsvTable OpenRevBayesTable(const std::string& path) {
+    TsvTable t = Read(path, "RevBayes output file");
+    const char* names[15] = {"Iteration", "Likelihood", "Prior", "alpha", "er[1]", "er[2]", "er[3]", "er[4]",
+                             "er[5]",     "er[6]",      "pi[1]", "pi[2]", "pi[3]", "pi[4]", "tree"};
+    t.Locate(names, 15, t.col, path);
+    return t;
+  }
+
   void Locate(const char* const* names, int n, int* out, const std::string& path) const {
     for (int k = 0; k < n; ++k) {
       const auto it = std::find(header.begin(), header.end(), names[k]);
@@ -805,7 +823,7 @@ struct PhyloHMM::TableBatch {
 
 PhyloHMM::TableBatch PhyloHMM::FlattenTable(const TsvTable& t, std::size_t r0, std::size_t r1, bool with_export,
                                             bool with_scalars, const std::string& path) const {
-  const auto t_begin = std::chrono::steady_clock::now();
+  const auto t_begin = SteadyNow();
   TableBatch tb;
   DeviceBatch& b = tb.dev;
   const int T = (int)xmsa_labels_.size();
@@ -874,39 +892,21 @@ PhyloHMM::TableBatch PhyloHMM::FlattenTable(const TsvTable& t, std::size_t r0, s
   };
   const int hw = HostThreads(16);
   const int n_threads = (int)std::max<std::size_t>(1, std::min<std::size_t>(hw, m / 32));
-  std::vector<std::thread> pool;
   std::vector<int> depths(n_threads, 0);
-  std::vector<std::exception_ptr> errors(n_threads);
-  for (int w = 0; w < n_threads; ++w) {
-    const std::size_t lo = m * w / n_threads, hi = m * (w + 1) / n_threads;
-    auto body = [&, w, lo, hi] {
-      try {
-        work(lo, hi, &depths[w]);
-      } catch (...) {
-        errors[w] = std::current_exception();
-      }
-    };
-    if (n_threads == 1)
-      body();
-    else
-      pool.emplace_back(body);
-  }
-  for (std::thread& th : pool) th.join();
-  for (const std::exception_ptr& e : errors)
-    if (e) std::rethrow_exception(e);  // the first failing row range, in file order
+  // (an error: the first failing row range, in file order)
+  ForRanges(n_threads, m, [&](int w, std::size_t lo, std::size_t hi) { work(lo, hi, &depths[w]); });
   for (int d : depths) b.max_depth = std::max(b.max_depth, d);
   if (host_options().pipeline_timing)
     std::fprintf(stderr, "[FlattenTable] %zu rows on %d threads: %.3f s\n", m, n_threads,
-                 std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count());
+                 Seconds(t_begin, SteadyNow()));
   return tb;
 }
 
 PhyloHMM::DeviceBatch PhyloHMM::FlattenTsv(const std::string& path, int* n_rows) const {
-  const auto t0 = std::chrono::steady_clock::now();
+  const auto t0 = SteadyNow();
   TsvTable t = TsvTable::Read(path, "RevBayes output file");
   if (host_options().pipeline_timing)
-    std::fprintf(stderr, "[FlattenTsv] read + line index %.3f s\n",
-                 std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+    std::fprintf(stderr, "[FlattenTsv] read + line index %.3f s\n", Seconds(t0, SteadyNow()));
   const char* names[15] = {"alpha", "alpha", "alpha", "alpha", "er[1]", "er[2]", "er[3]", "er[4]",
                            "er[5]", "er[6]",  "pi[1]", "pi[2]", "pi[3]", "pi[4]", "tree"};
   t.Locate(names, 15, t.col, path);
@@ -946,17 +946,10 @@ PhyloHMM::DeviceBatch PhyloHMM::FlattenTsvRows(const std::string& path, const in
 // in the state the reference's loop leaves behind.
 void PhyloHMM::RunPipeline(const std::string& input_path, const std::string& output_path, int num_rates) {
   const bool timing = host_options().pipeline_timing;
-  auto now = [] { return std::chrono::steady_clock::now(); };
-  auto secs = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
-    return std::chrono::duration<double>(b - a).count();
-  };
-  const auto t_start = now();
-  TsvTable table = TsvTable::Read(input_path, "RevBayes output file");
-  const char* names[15] = {"Iteration", "Likelihood", "Prior", "alpha", "er[1]", "er[2]", "er[3]", "er[4]",
-                           "er[5]",     "er[6]",      "pi[1]", "pi[2]", "pi[3]", "pi[4]", "tree"};
-  table.Locate(names, 15, table.col, input_path);
+  const auto t_start = SteadyNow();
+  TsvTable table = TsvTable::OpenRevBayesTable(input_path);
   const std::size_t N = table.rows.size();
-  const auto t_read = now();
+  const auto t_read = SteadyNow();
 
   StageTimer stage;
   CreateFamily();
@@ -1024,9 +1017,9 @@ void PhyloHMM::RunPipeline(const std::string& input_path, const std::string& out
     try {
       for (std::size_t off = 0; off < N; off += kBatch) {
         const std::size_t m = std::min(kBatch, N - off);
-        const auto t0 = now();
+        const auto t0 = SteadyNow();
         TableBatch tb = FlattenTable(table, off, off + m, true, true, input_path);
-        t_flat += secs(t0, now());
+        t_flat += Seconds(t0, SteadyNow());
         std::unique_lock<std::mutex> lock(mu);
         cv.wait(lock, [&] { return parsed.size() < 2 || cancel; });
         if (cancel) return;
@@ -1050,10 +1043,10 @@ void PhyloHMM::RunPipeline(const std::string& input_path, const std::string& out
       std::mt19937 word_rng = rng_;
       for (std::size_t off = 0; off < N; off += kBatch) {
         const std::size_t m = std::min(kBatch, N - off);
-        const auto t0 = now();
+        const auto t0 = SteadyNow();
         std::vector<uint32_t> w(m * (std::size_t)raw_per_sample);
         for (uint32_t& x : w) x = (uint32_t)word_rng();
-        t_words += secs(t0, now());
+        t_words += Seconds(t0, SteadyNow());
         std::unique_lock<std::mutex> lock(mu);
         cv.wait(lock, [&] { return drawn.size() < 2 || cancel; });
         if (cancel) return;
@@ -1091,7 +1084,7 @@ void PhyloHMM::RunPipeline(const std::string& input_path, const std::string& out
         s.off = off;
         s.m = m;
         const DeviceBatch& b = s.tb.dev;
-        const auto t2 = now();
+        const auto t2 = SteadyNow();
         if (dev_sampling) {
           {
             std::unique_lock<std::mutex> lock(mu);
@@ -1112,45 +1105,36 @@ void PhyloHMM::RunPipeline(const std::string& input_path, const std::string& out
             const std::size_t D = 1 + more_families_.size();
             const std::size_t n_ops4 = (std::size_t)(b.n_tips - 2) * 4, nodes = 2 * (std::size_t)b.n_tips - 2;
             const std::size_t W = (std::size_t)raw_per_sample;
-            std::vector<std::exception_ptr> errs(D);
-            std::vector<std::thread> pool;
-            for (std::size_t d = 0; d < D; ++d)
-              pool.emplace_back([&, d] {
-                try {
-                  std::vector<std::size_t> idx;
-                  for (std::size_t i = 0; i < m; ++i)
-                    if ((off + i) % D == d) idx.push_back(i);
-                  const std::size_t q = idx.size();
-                  if (q == 0) return;
-                  std::vector<int32_t> ops(q * n_ops4), states(q * NS);
-                  std::vector<double> brlen(q * nodes), er(q * 6), pi(q * 4), alpha(q), ll(q), rates(q * (std::size_t)num_rates);
-                  std::vector<uint32_t> words(q * W);
-                  for (std::size_t j = 0; j < q; ++j) {
-                    const std::size_t i = idx[j];
-                    std::copy_n(b.ops.data() + i * n_ops4, n_ops4, ops.data() + j * n_ops4);
-                    std::copy_n(b.brlen.data() + i * nodes, nodes, brlen.data() + j * nodes);
-                    std::copy_n(b.er.data() + i * 6, 6, er.data() + j * 6);
-                    std::copy_n(b.pi.data() + i * 4, 4, pi.data() + j * 4);
-                    alpha[j] = b.alpha[i];
-                    std::copy_n(s.words.data() + i * W, W, words.data() + j * W);
-                  }
-                  lh_family* fam = d == 0 ? family_ : more_families_[d - 1];
-                  if (lh_eval_sample_batch(fam, (int32_t)q, b.n_tips, b.max_depth, ops.data(), brlen.data(), er.data(), pi.data(),
-                                           alpha.data(), num_rates, words.data(), ll.data(), rates.data(), states.data()))
-                    throw std::runtime_error(std::string("lh_eval_sample_batch: ") + lh_last_error());
-                  for (std::size_t j = 0; j < q; ++j) {
-                    const std::size_t i = idx[j];
-                    s.ll[i] = ll[j];
-                    std::copy_n(rates.data() + j * (std::size_t)num_rates, (std::size_t)num_rates, s.rates + i * (std::size_t)num_rates);
-                    std::copy_n(states.data() + j * NS, NS, s.states + i * NS);
-                  }
-                } catch (...) {
-                  errs[d] = std::current_exception();
-                }
-              });
-            for (std::thread& th : pool) th.join();
-            for (const std::exception_ptr& e : errs)
-              if (e) std::rethrow_exception(e);
+            ForRanges((int)D, D, [&](int w, std::size_t, std::size_t) {  // (D >= 2: one thread per device)
+              const std::size_t d = (std::size_t)w;
+              std::vector<std::size_t> idx;
+              for (std::size_t i = 0; i < m; ++i)
+                if ((off + i) % D == d) idx.push_back(i);
+              const std::size_t q = idx.size();
+              if (q == 0) return;
+              std::vector<int32_t> ops(q * n_ops4), states(q * NS);
+              std::vector<double> brlen(q * nodes), er(q * 6), pi(q * 4), alpha(q), ll(q), rates(q * (std::size_t)num_rates);
+              std::vector<uint32_t> words(q * W);
+              for (std::size_t j = 0; j < q; ++j) {
+                const std::size_t i = idx[j];
+                std::copy_n(b.ops.data() + i * n_ops4, n_ops4, ops.data() + j * n_ops4);
+                std::copy_n(b.brlen.data() + i * nodes, nodes, brlen.data() + j * nodes);
+                std::copy_n(b.er.data() + i * 6, 6, er.data() + j * 6);
+                std::copy_n(b.pi.data() + i * 4, 4, pi.data() + j * 4);
+                alpha[j] = b.alpha[i];
+                std::copy_n(s.words.data() + i * W, W, words.data() + j * W);
+              }
+              lh_family* fam = d == 0 ? family_ : more_families_[d - 1];
+              if (lh_eval_sample_batch(fam, (int32_t)q, b.n_tips, b.max_depth, ops.data(), brlen.data(), er.data(), pi.data(),
+                                       alpha.data(), num_rates, words.data(), ll.data(), rates.data(), states.data()))
+                throw std::runtime_error(std::string("lh_eval_sample_batch: ") + lh_last_error());
+              for (std::size_t j = 0; j < q; ++j) {
+                const std::size_t i = idx[j];
+                s.ll[i] = ll[j];
+                std::copy_n(rates.data() + j * (std::size_t)num_rates, (std::size_t)num_rates, s.rates + i * (std::size_t)num_rates);
+                std::copy_n(states.data() + j * NS, NS, s.states + i * NS);
+              }
+            });
           }
           auto one_row = [&](std::size_t i, int k_fwd) {  // forward arrays of one row, for the host-side checks
             const std::size_t n_ops = (std::size_t)(b.n_tips - 2) * 4, nodes = 2 * (std::size_t)b.n_tips - 2;
@@ -1168,8 +1152,8 @@ void PhyloHMM::RunPipeline(const std::string& input_path, const std::string& out
                                  b.pi.data(), b.alpha.data(), num_rates, s.ll, &outs),
                    "lh_eval_batch");
         }
-        const auto t3 = now();
-        t_eval += secs(t2, t3);
+        const auto t3 = SteadyNow();
+        t_eval += Seconds(t2, t3);
         {
           std::lock_guard<std::mutex> lock(mu);
           s.state = 1;
@@ -1206,7 +1190,7 @@ void PhyloHMM::RunPipeline(const std::string& input_path, const std::string& out
   int k = 0;
   for (std::size_t off = 0; off < N; off += kBatch, k ^= 1) {
     Slot& slot = slots[k];
-    const auto tw = now();
+    const auto tw = SteadyNow();
     {
       std::unique_lock<std::mutex> lock(mu);
       cv.wait(lock, [&] { return slot.state == 1 || producer_error; });
@@ -1217,61 +1201,44 @@ void PhyloHMM::RunPipeline(const std::string& input_path, const std::string& out
     const DeviceBatch& b = tb.dev;
     const double *ll = slot.ll, *rates = slot.rates, *fwd = slot.fwd;
     const int32_t* sco = slot.sco;
-    const auto t2 = now();
-    t_wait += secs(tw, t2);
+    const auto t2 = SteadyNow();
+    t_wait += Seconds(tw, t2);
     // rows of this batch except the table's very last one: sampled and formatted by the workers
     const std::size_t m_par = (off + m == N) ? m - 1 : m;
     const int hw = HostThreads(16);
     const int n_threads = (int)std::max<std::size_t>(1, std::min<std::size_t>(hw, m_par / 8));
     std::vector<std::string> chunks(n_threads);
-    std::vector<std::exception_ptr> errors(n_threads);
     auto sample_rows = [&](int w, std::size_t lo, std::size_t hi) {
-      try {
-        RowSampler s;
-        std::mt19937 rng = rng_;
-        if (!dev_sampling) rng.discard((unsigned long long)(off + lo) * (unsigned long long)raw_per_sample);
-        std::string& o = chunks[w];
-        o.reserve((hi - lo) * (tb.exported.empty() ? 512 : tb.exported[lo].size() + 1024));
-        for (std::size_t i = lo; i < hi; ++i) {
-          if (dev_sampling) {
-            ApplySampledStates(s, slot.states + i * NS);
-            if (off + i == 0) {  // the device's draws against the host sampler's, where it is cheap
-              RowSampler h;
-              SampleRow(h, fwd, rng);
-              if (h.naive_seq != s.naive_seq || h.vd_junction_state_inds != s.vd_junction_state_inds ||
-                  h.dj_junction_state_inds != s.dj_junction_state_inds || h.vgerm_state_ind != s.vgerm_state_ind ||
-                  h.dgerm_state_ind != s.dgerm_state_ind || h.jgerm_state_ind != s.jgerm_state_ind)
-                throw std::runtime_error("RunPipeline: the device sampler and the host sampler disagree on the first row");
-            }
-          } else if (off + i == 0) {  // the bookkeeping above rests on this count: check it where it is cheap
-            std::mt19937 expect = rng;
-            SampleRow(s, fwd + i * FS, rng);
-            expect.discard((unsigned long long)raw_per_sample);
-            if (!(expect == rng)) throw std::runtime_error("RunPipeline: a sample consumed an unexpected number of random numbers");
-          } else {
-            SampleRow(s, fwd + i * FS, rng);
+      RowSampler s;
+      std::mt19937 rng = rng_;
+      if (!dev_sampling) rng.discard((unsigned long long)(off + lo) * (unsigned long long)raw_per_sample);
+      std::string& o = chunks[w];
+      o.reserve((hi - lo) * (tb.exported.empty() ? 512 : tb.exported[lo].size() + 1024));
+      for (std::size_t i = lo; i < hi; ++i) {
+        if (dev_sampling) {
+          ApplySampledStates(s, slot.states + i * NS);
+          if (off + i == 0) {  // the device's draws against the host sampler's, where it is cheap
+            RowSampler h;
+            SampleRow(h, fwd, rng);
+            if (h.naive_seq != s.naive_seq || h.vd_junction_state_inds != s.vd_junction_state_inds ||
+                h.dj_junction_state_inds != s.dj_junction_state_inds || h.vgerm_state_ind != s.vgerm_state_ind ||
+                h.dgerm_state_ind != s.dgerm_state_ind || h.jgerm_state_ind != s.jgerm_state_ind)
+              throw std::runtime_error("RunPipeline: the device sampler and the host sampler disagree on the first row");
           }
-          FormatOutputLine(o, tb.iteration[i], tb.lik[i], tb.prior[i], b.alpha[i], b.er.data() + i * 6,
-                           b.pi.data() + i * 4, tb.exported[i], rates + i * num_rates, num_rates, ll[i], s);
+        } else if (off + i == 0) {  // the bookkeeping above rests on this count: check it where it is cheap
+          std::mt19937 expect = rng;
+          SampleRow(s, fwd + i * FS, rng);
+          expect.discard((unsigned long long)raw_per_sample);
+          if (!(expect == rng)) throw std::runtime_error("RunPipeline: a sample consumed an unexpected number of random numbers");
+        } else {
+          SampleRow(s, fwd + i * FS, rng);
         }
-      } catch (...) {
-        errors[w] = std::current_exception();
+        FormatOutputLine(o, tb.iteration[i], tb.lik[i], tb.prior[i], b.alpha[i], b.er.data() + i * 6,
+                         b.pi.data() + i * 4, tb.exported[i], rates + i * num_rates, num_rates, ll[i], s);
       }
     };
-    {
-      std::vector<std::thread> pool;
-      for (int w = 0; w < n_threads; ++w) {
-        const std::size_t lo = m_par * w / n_threads, hi = m_par * (w + 1) / n_threads;
-        if (n_threads == 1)
-          sample_rows(w, lo, hi);
-        else
-          pool.emplace_back(sample_rows, w, lo, hi);
-      }
-      for (std::thread& th : pool) th.join();
-      for (const std::exception_ptr& e : errors)
-        if (e) std::rethrow_exception(e);
-    }
-    const auto t3 = now();
+    ForRanges(n_threads, m_par, sample_rows);
+    const auto t3 = SteadyNow();
     if (!header_written) {
       WriteOutputHeaders(outfile);
       header_written = true;
@@ -1319,9 +1286,9 @@ void PhyloHMM::RunPipeline(const std::string& input_path, const std::string& out
       WriteOutputLine(outfile);
       pending_newick_ = nullptr;
     }
-    const auto t4 = now();
-    t_samp += secs(t2, t3);
-    t_write += secs(t3, t4);
+    const auto t4 = SteadyNow();
+    t_samp += Seconds(t2, t3);
+    t_write += Seconds(t3, t4);
     {
       std::lock_guard<std::mutex> lock(mu);
       slot.state = 0;
@@ -1334,9 +1301,9 @@ void PhyloHMM::RunPipeline(const std::string& input_path, const std::string& out
     std::fprintf(stderr,
                  "[RunPipeline] %zu rows: read %.3f s; producer: parse+schedule %.3f s, device (incl. copies%s) %.3f s; "
                  "consumer (%s): waiting %.3f s, sample+format %.3f s, write %.3f s; total %.3f s\n",
-                 N, secs(t_start, t_read), t_flat, dev_sampling ? (", engine words " + std::to_string(t_words) + " s").c_str() : "",
+                 N, Seconds(t_start, t_read), t_flat, dev_sampling ? (", engine words " + std::to_string(t_words) + " s").c_str() : "",
                  t_eval, dev_sampling ? "device sampler" : "host sampler", t_wait, t_samp,
-                 t_write, secs(t_start, now()));
+                 t_write, Seconds(t_start, SteadyNow()));
 }
 
 // scripts/run_bootstrap_asr_ess.R:86-101: the tree rooted on the naive branch (the added root node sits at
@@ -1354,8 +1321,7 @@ std::string PhyloHMM::AnnotatedNewick(const TreeArrays& tr, const std::string& n
     } else if (v < T) {
       for (int j = 0; j < L; ++j) s.push_back(alphabet_[msa_(v - 1, j)]);
     } else {
-      const uint8_t* a = anc + (std::size_t)(v - T) * L;
-      for (int j = 0; j < L; ++j) s.push_back(alphabet_[a[j]]);
+      s += DecodeBases(anc + (std::size_t)(v - T) * L, (std::size_t)L, alphabet_);
     }
     return s + "\"]";
   };
@@ -1487,18 +1453,10 @@ void PhyloHMM::RunAsr(const std::string& input_path, const std::string& output_p
     std::vector<std::string> lines(m);
     const int hw = HostThreads(16);
     const int n_threads = std::max(1, std::min(hw, (int)(m / 16)));
-    auto format_rows = [&](std::size_t lo, std::size_t hi) {
+    ForRanges(n_threads, m, [&](int, std::size_t lo, std::size_t hi) {
       for (std::size_t i = lo; i < hi; ++i)
         lines[i] = AnnotatedNewick(trees[i], rows[off + i].naive, anc.data() + i * (std::size_t)(T - 2) * L);
-    };
-    if (n_threads == 1) {
-      format_rows(0, m);
-    } else {
-      std::vector<std::thread> pool;
-      for (int t = 0; t < n_threads; ++t)
-        pool.emplace_back(format_rows, m * t / n_threads, m * (t + 1) / n_threads);
-      for (std::thread& th : pool) th.join();
-    }
+    });
     for (std::size_t i = 0; i < m; ++i) outfile << lines[i] << "\n";
   }
 }
@@ -1512,37 +1470,25 @@ void PhyloHMM::RunLineagePipeline(const std::string& input_path, const std::stri
     if (xmsa_labels_[v] == seed_seq) seed_tip = v;
   Require(seed_tip > 0, "the seed sequence '" + seed_seq + "' is not a sequence of this clonal family");
   const bool timing = host_options().pipeline_timing;
-  auto now = [] { return std::chrono::steady_clock::now(); };
-  auto secs = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
-    return std::chrono::duration<double>(b - a).count();
-  };
-  const auto t_start = now();
+  const auto t_start = SteadyNow();
   double t_flat = 0, t_dev = 0, t_resolve = 0, t_count = 0;
   int R = 0;
   const std::vector<AsrRow> rows = ReadAsrRows(input_path, &R);
-  const auto t_read = now();
+  const auto t_read = SteadyNow();
   const int L = (int)msa_.cols();
   CreateFamily();
   CheckHip(lh_lineage_reset(family_), "lh_lineage_reset");
-  auto decode = [&](const uint8_t* b) {
-    std::string s((std::size_t)L, 'N');
-    for (int j = 0; j < L; ++j) s[j] = alphabet_[std::min<std::size_t>(b[j], alphabet_.size() - 1)];
-    return s;
-  };
   LineageTabulator tab;
   std::string seed_nt((std::size_t)L, 'N');
   for (int j = 0; j < L; ++j) seed_nt[j] = alphabet_[msa_(seed_tip - 1, j)];
   const int seed_id = tab.AddSequence(seed_nt);  // (tips keep their observed characters: one sequence for every tree)
-  std::unordered_map<uint64_t, int32_t> by_hash;   // base hash -> store id of the first sequence seen with it
-  std::unordered_map<std::string, int32_t> exact;  // store ids made by resolving collisions, by their bases
-  std::vector<int> tab_of_store;                   // store id -> tabulator id
-  std::vector<uint64_t> aa_of_store;               // store id -> translation hash of its first slot
-  int32_t K = 0;
-  int64_t collisions = 0;
+  SeqInterner interner(family_, lh_lineage_resolve, lh_lineage_rows_read, L, "lineage pipeline");  // by base hash
+  std::vector<int> tab_of_store;      // store id -> tabulator id
+  std::vector<uint64_t> aa_of_store;  // store id -> translation hash of its first slot
   const std::size_t kBatch = host_options().lineage_batch > 0 ? (std::size_t)host_options().lineage_batch : 1024;
   for (std::size_t off = 0; off < rows.size(); off += kBatch) {
     const std::size_t m = std::min(kBatch, rows.size() - off);
-    const auto t0 = now();
+    const auto t0 = SteadyNow();
     std::vector<TreeSample> samples;
     std::vector<double> rates;
     std::vector<uint8_t> naive;
@@ -1570,44 +1516,25 @@ void PhyloHMM::RunLineagePipeline(const std::string& input_path, const std::stri
     for (std::size_t i = 0; i < m; ++i) std::copy(chain[i].begin(), chain[i].end(), path.begin() + i * P);
     const std::size_t S = P + 1;
     std::vector<uint64_t> nt_hash(m * S), aa_hash(m * S);
-    const auto t1 = now();
+    const auto t1 = SteadyNow();
     CheckHip(lh_lineage_batch(family_, b.n, b.n_tips, b.max_depth, b.ops.data(), b.brlen.data(), b.er.data(), b.pi.data(),
                               rates.data(), R, naive.data(), seed, (uint64_t)off, path.data(), (int32_t)P,
                               nt_hash.data(), aa_hash.data()),
              "lh_lineage_batch");
-    const auto t2 = now();
-    // ids by hash; lh_lineage_resolve then compares every slot with its id's bases, so no hash decides alone
-    std::vector<int32_t> ids(m * S, -1);
-    const int32_t K_before = K;
-    for (std::size_t i = 0; i < m; ++i)
-      for (std::size_t s = 0; s < S; ++s) {
-        if (s < P && s >= chain[i].size()) continue;
-        const auto r = by_hash.emplace(nt_hash[i * S + s], K);
-        if (r.second) ++K;
-        ids[i * S + s] = r.first->second;
-      }
-    std::vector<int32_t> mism(m * S);
+    const auto t2 = SteadyNow();
+    // every slot but the padding ones takes part
+    std::vector<uint8_t> take(m * S, 1);
+    for (std::size_t i = 0; i < m; ++i) std::fill(take.begin() + i * S + chain[i].size(), take.begin() + i * S + P, 0);
+    std::vector<int32_t> ids(m * S);
+    const int32_t K_before = interner.K();
+    const int32_t K = K_before + interner.Assign(m * S, nt_hash.data(), take.data(), ids.data());
     std::vector<uint8_t> bytes;
-    for (int round = 0;; ++round) {
-      int32_t nm = 0;
-      CheckHip(lh_lineage_resolve(family_, (int32_t)(m * S), ids.data(), &nm, mism.data()), "lh_lineage_resolve");
-      if (nm == 0) break;
-      Require(round == 0, "lineage pipeline: slots still differ from their sequences after resolution");
-      collisions += nm;
-      bytes.resize((std::size_t)nm * L);
-      CheckHip(lh_lineage_rows_read(family_, nm, mism.data(), bytes.data()), "lh_lineage_rows_read");
-      for (int32_t q = 0; q < nm; ++q) {
-        const auto r = exact.emplace(decode(bytes.data() + (std::size_t)q * L), K);
-        if (r.second) ++K;
-        ids[mism[q]] = r.first->second;
-      }
-    }
     // only the bases of the sequences first seen in this batch come back
     if (K > K_before) {
       bytes.resize((std::size_t)(K - K_before) * L);
       CheckHip(lh_lineage_store_read(family_, K_before, K - K_before, nullptr, bytes.data()), "lh_lineage_store_read");
       for (int32_t k = K_before; k < K; ++k)
-        tab_of_store.push_back(tab.AddSequence(decode(bytes.data() + (std::size_t)(k - K_before) * L)));
+        tab_of_store.push_back(tab.AddSequence(DecodeBases(bytes.data() + (std::size_t)(k - K_before) * L, (std::size_t)L, alphabet_)));
       aa_of_store.resize(K);
       std::vector<bool> have(K - K_before, false);
       for (std::size_t x = 0; x < m * S; ++x)
@@ -1616,7 +1543,7 @@ void PhyloHMM::RunLineagePipeline(const std::string& input_path, const std::stri
           aa_of_store[ids[x]] = aa_hash[x];
         }
     }
-    const auto t3 = now();
+    const auto t3 = SteadyNow();
     std::vector<int> l;
     for (std::size_t i = 0; i < m; ++i) {
       for (std::size_t s = 0; s < S; ++s)
@@ -1629,20 +1556,20 @@ void PhyloHMM::RunLineagePipeline(const std::string& input_path, const std::stri
       l.push_back(seed_id);
       tab.AddTree(l, (int)chain[i].size());
     }
-    const auto t4 = now();
-    t_flat += secs(t0, t1);
-    t_dev += secs(t1, t2);
-    t_resolve += secs(t2, t3);
-    t_count += secs(t3, t4);
+    const auto t4 = SteadyNow();
+    t_flat += Seconds(t0, t1);
+    t_dev += Seconds(t1, t2);
+    t_resolve += Seconds(t2, t3);
+    t_count += Seconds(t3, t4);
   }
-  const auto t_w = now();
-  WriteLineageFiles(output_prefix, tab.Finish(seed_seq), collisions);
+  const auto t_w = SteadyNow();
+  WriteLineageFiles(output_prefix, tab.Finish(seed_seq), interner.collisions());
   if (timing)
     std::fprintf(stderr,
                  "[RunLineagePipeline] %zu rows: read %.3f s, parse+schedule+paths %.3f s, device (K1 + K3 + K7, copies) "
                  "%.3f s, resolve+read back (%d sequences) %.3f s, count %.3f s, write %.3f s; total %.3f s\n",
-                 rows.size(), secs(t_start, t_read), t_flat, t_dev, (int)K, t_resolve, t_count, secs(t_w, now()),
-                 secs(t_start, now()));
+                 rows.size(), Seconds(t_start, t_read), t_flat, t_dev, (int)interner.K(), t_resolve, t_count, Seconds(t_w, SteadyNow()),
+                 Seconds(t_start, SteadyNow()));
 }
 
 // src/PhyloHMM.cpp:461-471
@@ -1689,17 +1616,14 @@ void PhyloHMM::RunMarginalsPipeline(const std::string& input_path, const std::st
   Require(burnin_frac >= 0.0 && burnin_frac < 1.0, "burn-in fraction must be in [0, 1)");
   CreateFamily();
   Require(device_sampler_, "the family has no device sampler tables (needed by the posterior kernel)");
-  TsvTable table = TsvTable::Read(input_path, "RevBayes output file");
-  const char* names[15] = {"Iteration", "Likelihood", "Prior", "alpha", "er[1]", "er[2]", "er[3]", "er[4]",
-                           "er[5]", "er[6]",  "pi[1]", "pi[2]", "pi[3]", "pi[4]", "tree"};
-  table.Locate(names, 15, table.col, input_path);
+  TsvTable table = TsvTable::OpenRevBayesTable(input_path);
   const std::size_t N = table.rows.size();
   const std::size_t first = (std::size_t)std::floor(burnin_frac * (double)N);
   const std::size_t FS = (std::size_t)lh_forward_size(family_);
   constexpr std::size_t kBatch = 49152;
   // running combination of the batches' (sum w pi, max lw, sum w, sum w^2), each relative to the running max
-  std::vector<double> total(FS, 0.0), wsum(FS);
-  double mx = -INFINITY, s1 = 0.0, s2 = 0.0;
+  WeightedSums acc(FS);
+  std::vector<double> wsum(FS);
   std::size_t skipped = 0;
   for (std::size_t off = first; off < N; off += kBatch) {
     const std::size_t m = std::min(kBatch, N - off);
@@ -1713,24 +1637,18 @@ void PhyloHMM::RunMarginalsPipeline(const std::string& input_path, const std::st
              "lh_eval_posterior_batch");
     for (std::size_t i = 0; i < m; ++i)
       if (!std::isfinite(ll[i] - tb.lik[i])) ++skipped;
-    if (!std::isfinite(st[0])) continue;
-    const double nm = std::max(mx, st[0]);
-    const double fo = std::isfinite(mx) ? std::exp(mx - nm) : 0.0, fn = std::exp(st[0] - nm);
-    for (std::size_t j = 0; j < FS; ++j) total[j] = total[j] * fo + wsum[j] * fn;
-    s1 = s1 * fo + st[1] * fn;
-    s2 = s2 * fo * fo + st[2] * fn * fn;
-    mx = nm;
+    acc.Add(wsum.data(), st);
   }
-  Require(s1 > 0.0, "marginals pipeline: no row with a finite weight");
-  for (double& v : total) v /= s1;
-  const NaiveMarginalsResult res = MapPosterior(total.data());
+  Require(acc.s1 > 0.0, "marginals pipeline: no row with a finite weight");
+  acc.Normalise();
+  const NaiveMarginalsResult res = MapPosterior(acc.total.data());
   std::ofstream sites(output_prefix + ".sites.tsv"), genes(output_prefix + ".genes.tsv"),
       summary(output_prefix + ".summary.tsv");
   Require(sites.good() && genes.good() && summary.good(), "Can't write " + output_prefix + ".*.tsv");
   WriteSiteTable(sites, res);
   WriteGeneTable(genes, res);
   char buf[64];
-  std::snprintf(buf, sizeof buf, "%.17g", s1 * s1 / s2);
+  std::snprintf(buf, sizeof buf, "%.17g", acc.KishEss());
   summary << "key\tvalue\nrows_used\t" << (N - first - skipped) << "\nrows_skipped_nonfinite\t" << skipped
           << "\nkish_ess\t" << buf << "\n";
 }
@@ -1792,15 +1710,8 @@ void PhyloHMM::RunNaiveProbsPipeline(const std::string& input_path, const std::s
   CreateFamily();
   // stage times on stderr (LH_PIPELINE_TIMING): table parsing, device calls, host collection, per pass
   const bool timing = host_options().pipeline_timing;
-  auto now = [] { return std::chrono::steady_clock::now(); };
-  auto secs = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
-    return std::chrono::duration<double>(b - a).count();
-  };
   double p1_parse = 0, p1_dev = 0, p1_collect = 0, p1_total = 0, p2_prior = 0, p2_parse = 0, p2_dev = 0, p2_total = 0;
-  TsvTable table = TsvTable::Read(input_path, "RevBayes output file");
-  const char* names[15] = {"Iteration", "Likelihood", "Prior", "alpha", "er[1]", "er[2]", "er[3]", "er[4]",
-                           "er[5]", "er[6]",  "pi[1]", "pi[2]", "pi[3]", "pi[4]", "tree"};
-  table.Locate(names, 15, table.col, input_path);
+  TsvTable table = TsvTable::OpenRevBayesTable(input_path);
   const std::size_t N = table.rows.size();
   const std::size_t first = (std::size_t)std::floor(burnin_frac * (double)N);
   const std::size_t U = N - first;  // rows after the burn-in
@@ -1810,7 +1721,7 @@ void PhyloHMM::RunNaiveProbsPipeline(const std::string& input_path, const std::s
   std::vector<int32_t> row_id;  // pass 1: candidate of every row after the burn-in (-1: non-finite row or dropped)
   std::vector<double> ll1;
   int64_t draws_distinct = -1, dropped = 0;
-  const auto t_p1 = now();
+  const auto t_p1 = SteadyNow();
   if (candidates_path.empty()) {
     const int raw = RawDrawsPerSample();
     row_id.assign(U, -1);
@@ -1818,18 +1729,16 @@ void PhyloHMM::RunNaiveProbsPipeline(const std::string& input_path, const std::s
     std::vector<std::string> distinct;  // by pass-1 id
     if (device_sampler_) {
       CheckHip(lh_draws_reset(family_), "lh_draws_reset");
-      std::unordered_map<uint64_t, int32_t> by_hash;  // hash -> store id of the first sequence seen with it
-      std::unordered_map<std::string, int32_t> exact;  // store ids made by resolving collisions, by their bytes
-      int32_t K = 0;
+      SeqInterner interner(family_, lh_draws_resolve, lh_draws_rows_read, L, "naive-probabilities pipeline");
       std::mt19937 word_rng = rng_;
       word_rng.discard((unsigned long long)first * (unsigned long long)raw);
       for (std::size_t off = first; off < N; off += kBatch) {
         const std::size_t m = std::min(kBatch, N - off);
-        const auto t0 = now();
+        const auto t0 = SteadyNow();
         TableBatch tb = FlattenTable(table, off, off + m, false, true, input_path);
         const DeviceBatch& b = tb.dev;
-        const auto t1 = now();
-        p1_parse += secs(t0, t1);
+        const auto t1 = SteadyNow();
+        p1_parse += Seconds(t0, t1);
         std::vector<uint32_t> words(m * (std::size_t)raw);
         for (uint32_t& x : words) x = (uint32_t)word_rng();
         std::vector<uint64_t> hash(m);
@@ -1837,33 +1746,12 @@ void PhyloHMM::RunNaiveProbsPipeline(const std::string& input_path, const std::s
         CheckHip(lh_eval_draw_batch(family_, b.n, b.n_tips, b.max_depth, b.ops.data(), b.brlen.data(), b.er.data(),
                                     b.pi.data(), b.alpha.data(), num_rates, words.data(), ll, hash.data(), nullptr),
                  "lh_eval_draw_batch");
-        const auto t2 = now();
-        p1_dev += secs(t1, t2);
-        int32_t* cand = row_id.data() + (off - first);
-        for (std::size_t i = 0; i < m; ++i) {
-          if (!std::isfinite(ll[i] - tb.lik[i])) continue;
-          const auto r = by_hash.emplace(hash[i], K);
-          if (r.second) ++K;
-          cand[i] = r.first->second;
-        }
-        std::vector<int32_t> mism(m);
-        std::vector<uint8_t> bytes;
-        for (int round = 0;; ++round) {
-          int32_t nm = 0;
-          CheckHip(lh_draws_resolve(family_, (int32_t)m, cand, &nm, mism.data()), "lh_draws_resolve");
-          if (nm == 0) break;
-          Require(round == 0, "naive-probabilities pipeline: rows still differ from their candidates after resolution");
-          bytes.resize((std::size_t)nm * L);
-          CheckHip(lh_draws_rows_read(family_, nm, mism.data(), bytes.data()), "lh_draws_rows_read");
-          for (int32_t q = 0; q < nm; ++q) {
-            std::string s((std::size_t)L, 'N');
-            for (int j = 0; j < L; ++j) s[j] = alphabet_[bytes[(std::size_t)q * L + j]];
-            const auto r = exact.emplace(s, K);
-            if (r.second) ++K;
-            cand[mism[q]] = r.first->second;
-          }
-        }
-        p1_collect += secs(t2, now());
+        const auto t2 = SteadyNow();
+        p1_dev += Seconds(t1, t2);
+        std::vector<uint8_t> finite(m);
+        for (std::size_t i = 0; i < m; ++i) finite[i] = std::isfinite(ll[i] - tb.lik[i]);
+        interner.Assign(m, hash.data(), finite.data(), row_id.data() + (off - first));
+        p1_collect += Seconds(t2, SteadyNow());
       }
       int32_t Ks = 0;
       CheckHip(lh_draws_candidates_read(family_, &Ks, nullptr), "lh_draws_candidates_read");
@@ -1875,9 +1763,7 @@ void PhyloHMM::RunNaiveProbsPipeline(const std::string& input_path, const std::s
         if (id < 0) continue;
         if (remap[id] < 0) {
           remap[id] = (int32_t)distinct.size();
-          std::string s((std::size_t)L, 'N');
-          for (int j = 0; j < L; ++j) s[j] = alphabet_[store[(std::size_t)id * L + j]];
-          distinct.push_back(s);
+          distinct.push_back(DecodeBases(store.data() + (std::size_t)id * L, (std::size_t)L, alphabet_));
         }
         id = remap[id];
       }
@@ -1894,18 +1780,18 @@ void PhyloHMM::RunNaiveProbsPipeline(const std::string& input_path, const std::s
       RowSampler s;
       for (std::size_t off = first; off < N; off += kSub) {
         const std::size_t m = std::min(kSub, N - off);
-        const auto t0 = now();
+        const auto t0 = SteadyNow();
         TableBatch tb = FlattenTable(table, off, off + m, false, true, input_path);
         const DeviceBatch& b = tb.dev;
-        const auto t1 = now();
-        p1_parse += secs(t0, t1);
+        const auto t1 = SteadyNow();
+        p1_parse += Seconds(t0, t1);
         double* ll = ll1.data() + (off - first);
         lh_eval_outputs outs{nullptr, nullptr, fwd.data(), sco.data()};
         CheckHip(lh_eval_batch(family_, b.n, b.n_tips, b.max_depth, b.ops.data(), b.brlen.data(), b.er.data(), b.pi.data(),
                                b.alpha.data(), num_rates, ll, &outs),
                  "lh_eval_batch");
-        const auto t2 = now();
-        p1_dev += secs(t1, t2);
+        const auto t2 = SteadyNow();
+        p1_dev += Seconds(t1, t2);
         for (std::size_t i = 0; i < m; ++i) {
           if (!std::isfinite(ll[i] - tb.lik[i])) {
             rng.discard((unsigned long long)raw);
@@ -1916,7 +1802,7 @@ void PhyloHMM::RunNaiveProbsPipeline(const std::string& input_path, const std::s
           if (r.second) distinct.push_back(s.naive_seq);
           row_id[off - first + i] = r.first->second;
         }
-        p1_collect += secs(t2, now());
+        p1_collect += Seconds(t2, SteadyNow());
       }
     }
     // counts, and the limit: the most drawn, ties by first appearance, kept in first-appearance order
@@ -1946,31 +1832,31 @@ void PhyloHMM::RunNaiveProbsPipeline(const std::string& input_path, const std::s
     t.seqs = ReadCandidateFile(candidates_path, L);
   }
 
-  p1_total = secs(t_p1, now());
+  p1_total = Seconds(t_p1, SteadyNow());
   // pass 2: exact probabilities
-  const auto t_p2 = now();
+  const auto t_p2 = SteadyNow();
   const int K = (int)t.seqs.size();
   const std::vector<uint8_t> bytes = EncodeSeqs(t.seqs, alphabet_, L);
   t.log_prior.assign(K, 0.0);
   CheckHip(lh_family_set_candidates(family_, K, bytes.data(), t.log_prior.data()), "lh_family_set_candidates");
-  p2_prior = secs(t_p2, now());
-  std::vector<double> total(K, 0.0), wsum(K), lw(U);
-  double mx = -INFINITY, s1 = 0.0, s2 = 0.0;
+  p2_prior = Seconds(t_p2, SteadyNow());
+  WeightedSums acc((std::size_t)K);
+  std::vector<double> wsum(K), lw(U);
   std::size_t skipped = 0;
   for (std::size_t off = first; off < N; off += kBatch) {
     const std::size_t m = std::min(kBatch, N - off);
-    const auto t0 = now();
+    const auto t0 = SteadyNow();
     TableBatch tb = FlattenTable(table, off, off + m, false, true, input_path);
     const DeviceBatch& b = tb.dev;
-    const auto t1 = now();
-    p2_parse += secs(t0, t1);
+    const auto t1 = SteadyNow();
+    p2_parse += Seconds(t0, t1);
     std::vector<double> ll(m);
     double st[3];
     lh_candidate_outputs outs{tb.lik.data(), ll.data(), nullptr, wsum.data(), st};
     CheckHip(lh_eval_candidates_batch(family_, b.n, b.n_tips, b.max_depth, b.ops.data(), b.brlen.data(), b.er.data(),
                                       b.pi.data(), b.alpha.data(), num_rates, &outs),
              "lh_eval_candidates_batch");
-    p2_dev += secs(t1, now());
+    p2_dev += Seconds(t1, SteadyNow());
     for (std::size_t i = 0; i < m; ++i) {
       lw[off - first + i] = ll[i] - tb.lik[i];
       if (!std::isfinite(lw[off - first + i])) ++skipped;
@@ -1978,28 +1864,20 @@ void PhyloHMM::RunNaiveProbsPipeline(const std::string& input_path, const std::s
         throw std::runtime_error("naive-probabilities pipeline: the two passes' log-likelihoods differ at row " +
                                  std::to_string(off + i));
     }
-    if (!std::isfinite(st[0])) continue;
-    const double nm = std::max(mx, st[0]);
-    const double fo = std::isfinite(mx) ? std::exp(mx - nm) : 0.0, fn = std::exp(st[0] - nm);
-    for (int k = 0; k < K; ++k) total[k] = total[k] * fo + wsum[k] * fn;
-    s1 = s1 * fo + st[1] * fn;
-    s2 = s2 * fo * fo + st[2] * fn * fn;
-    mx = nm;
+    acc.Add(wsum.data(), st);
   }
-  Require(s1 > 0.0, "naive-probabilities pipeline: no row with a finite weight");
-  p2_total = secs(t_p2, now());
+  Require(acc.s1 > 0.0, "naive-probabilities pipeline: no row with a finite weight");
+  acc.Normalise();
+  p2_total = Seconds(t_p2, SteadyNow());
   if (timing)
     std::fprintf(stderr,
                  "[RunNaiveProbsPipeline] %zu rows; pass 1 (%s): parse %.4f s, device %.4f s, collect %.4f s, total %.4f s; "
                  "pass 2 (%d candidates): priors %.4f s, parse %.4f s, device %.4f s, total %.4f s\n",
                  U, !candidates_path.empty() ? "skipped" : device_sampler_ ? "device draws" : "host draws", p1_parse, p1_dev,
                  p1_collect, p1_total, K, p2_prior, p2_parse, p2_dev, p2_total);
-  t.prob.resize(K);
+  t.prob = acc.total;
   double covered = 0.0;
-  for (int k = 0; k < K; ++k) {
-    t.prob[k] = total[k] / s1;
-    covered += t.prob[k];
-  }
+  for (int k = 0; k < K; ++k) covered += t.prob[k];
   if (t.sampled) {  // self-normalised sampled frequencies, weights as K5 / K6b form them, summed in row order
     double lmax = -INFINITY;
     for (double x : lw)
@@ -2022,7 +1900,7 @@ void PhyloHMM::RunNaiveProbsPipeline(const std::string& input_path, const std::s
   WriteAaFasta(aa, t);
   WriteDnaMap(dnamap, t);
   char buf[64], cov[64];
-  std::snprintf(buf, sizeof buf, "%.17g", s1 * s1 / s2);
+  std::snprintf(buf, sizeof buf, "%.17g", acc.KishEss());
   std::snprintf(cov, sizeof cov, "%.17g", covered);
   summary << "key\tvalue\nrows_used\t" << (U - skipped) << "\nrows_skipped_nonfinite\t" << skipped << "\nkish_ess\t" << buf
           << "\ndraws_distinct\t" << (draws_distinct < 0 ? std::string("NA") : std::to_string(draws_distinct))

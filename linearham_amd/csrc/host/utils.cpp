@@ -1,5 +1,7 @@
 #include "utils.hpp"
 
+#include "linearham_amd.h"
+
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -119,6 +121,43 @@ void StageTimer::Mark(const char* what) {
   const double t = Now();
   std::fprintf(stderr, "[host] %-28s %.3f s\n", what, t - t0);
   t0 = t;
+}
+
+std::string DecodeBases(const uint8_t* bytes, std::size_t n, const std::string& alphabet) {
+  std::string s(n, 'N');
+  for (std::size_t j = 0; j < n; ++j) s[j] = alphabet[std::min<std::size_t>(bytes[j], alphabet.size() - 1)];
+  return s;
+}
+
+int32_t SeqInterner::Assign(std::size_t m, const uint64_t* hash, const uint8_t* take, int32_t* ids) {
+  auto check = [&](int rc, const char* step) {
+    if (rc != 0) throw std::runtime_error(who_ + ": " + step + ": " + lh_last_error());
+  };
+  const int32_t K_before = K_;
+  for (std::size_t x = 0; x < m; ++x) {
+    ids[x] = -1;
+    if (!take[x]) continue;
+    const auto r = by_hash_.emplace(hash[x], K_);
+    if (r.second) ++K_;
+    ids[x] = r.first->second;
+  }
+  std::vector<int32_t> mism(m);
+  std::vector<uint8_t> bytes;
+  for (int round = 0;; ++round) {
+    int32_t nm = 0;
+    check(resolve_(family_, (int32_t)m, ids, &nm, mism.data()), "resolve");
+    if (nm == 0) break;
+    Require(round == 0, who_ + ": slots still differ from their sequences after resolution");
+    collisions_ += nm;
+    bytes.resize((std::size_t)nm * L_);
+    check(rows_read_(family_, nm, mism.data(), bytes.data()), "rows_read");
+    for (int32_t q = 0; q < nm; ++q) {
+      const auto r = exact_.emplace(std::string(reinterpret_cast<const char*>(bytes.data()) + (std::size_t)q * L_, L_), K_);
+      if (r.second) ++K_;
+      ids[mism[q]] = r.first->second;
+    }
+  }
+  return K_ - K_before;
 }
 
 }  // namespace linearham

@@ -3,13 +3,19 @@
 #ifndef LINEARHAM_UTILS_
 #define LINEARHAM_UTILS_
 
+#include <algorithm>
+#include <chrono>
 #include <cmath>
+#include <cstdint>
 #include <stdexcept>
 #include <string>
+#include <unordered_map>
 #include <utility>
 #include <vector>
 
 #include "yaml_lite.hpp"
+
+struct lh_family;
 
 namespace linearham {
 
@@ -62,6 +68,8 @@ std::pair<int, int> FindGermlineStartEnd(const yaml_lite::Node& root, const std:
 VectorXi ConvertSeqToInts(const std::string& seq_str, const std::string& alphabet);
 std::string ConvertIntsToSeq(const VectorXi& seq, const std::string& alphabet);
 std::string FixGeneName(std::string name);
+/// Bytes 0 .. alphabet.size() - 1 -> characters (the device's sequences; a larger byte reads as the last character, N).
+std::string DecodeBases(const uint8_t* bytes, std::size_t n, const std::string& alphabet);
 
 /// assert() of the reference is live in its release build (no -DNDEBUG, SConstruct:266); here format
 /// violations throw so that a library user gets a message instead of an abort.
@@ -86,6 +94,62 @@ struct StageTimer {
   static double Now();
   StageTimer();
   void Mark(const char* what);
+};
+
+/// Steady-clock readings and the seconds between two of them (the pipelines' stage times).
+using SteadyTime = std::chrono::steady_clock::time_point;
+inline SteadyTime SteadyNow() { return std::chrono::steady_clock::now(); }
+inline double Seconds(SteadyTime a, SteadyTime b) { return std::chrono::duration<double>(b - a).count(); }
+
+/// The running weighted combination of a table's batches.  A batch hands in wsum[j] = sum_i w_i x_ij and
+/// st = (max log weight, sum w, sum w^2), its weights taken relative to its own maximum; the running sums are kept
+/// relative to the running maximum.  A batch without a finite weight (st[0] not finite) adds nothing.
+struct WeightedSums {
+  std::vector<double> total;
+  double mx = -INFINITY, s1 = 0.0, s2 = 0.0;
+  explicit WeightedSums(std::size_t n) : total(n, 0.0) {}
+  void Add(const double* wsum, const double* st) {
+    if (!std::isfinite(st[0])) return;
+    const double nm = std::max(mx, st[0]);
+    const double fo = std::isfinite(mx) ? std::exp(mx - nm) : 0.0, fn = std::exp(st[0] - nm);
+    for (std::size_t j = 0; j < total.size(); ++j) total[j] = total[j] * fo + wsum[j] * fn;
+    s1 = s1 * fo + st[1] * fn;
+    s2 = s2 * fo * fo + st[2] * fn * fn;
+    mx = nm;
+  }
+  void Normalise() {  // total -> weighted means (s1 > 0: some row had a finite weight)
+    for (double& v : total) v /= s1;
+  }
+  double KishEss() const { return s1 * s1 / s2; }
+};
+
+/// The host side of a device sequence store (lh_draws_* or lh_lineage_*, which share their signatures): ids for the slots
+/// of the handle's last batch from their 64-bit hashes, verified by the device against the stored bytes, so that no hash
+/// decides alone.  Two sequences that share a hash are told apart by their bytes.
+class SeqInterner {
+ public:
+  using ResolveFn = int (*)(lh_family*, int32_t, const int32_t*, int32_t*, int32_t*);
+  using RowsReadFn = int (*)(lh_family*, int32_t, const int32_t*, uint8_t*);
+  /// L: bytes per sequence; who: the pipeline's name, for error texts
+  SeqInterner(lh_family* family, ResolveFn resolve, RowsReadFn rows_read, int L, std::string who)
+      : family_(family), resolve_(resolve), rows_read_(rows_read), L_(L), who_(std::move(who)) {}
+  /// ids[x] = the store id of slot x < m of the last batch (hash[x]; -1 where take[x] is 0), in slot order.  Slots that
+  /// differ from their id's bytes are read back and interned by their bytes; one more round must then find none.
+  /// Returns how many ids are new: the store appended K() - that .. K() - 1.
+  int32_t Assign(std::size_t m, const uint64_t* hash, const uint8_t* take, int32_t* ids);
+  int32_t K() const { return K_; }
+  int64_t collisions() const { return collisions_; }  // slots that went through the second round
+
+ private:
+  lh_family* family_;
+  ResolveFn resolve_;
+  RowsReadFn rows_read_;
+  int L_;
+  std::string who_;
+  std::unordered_map<uint64_t, int32_t> by_hash_;   // hash -> store id of the first sequence seen with it
+  std::unordered_map<std::string, int32_t> exact_;  // store ids made by resolving collisions, by their bytes
+  int32_t K_ = 0;
+  int64_t collisions_ = 0;
 };
 
 }  // namespace linearham

@@ -184,27 +184,31 @@ struct CandidateWs {
   DevBuf loglik, weights, stats, partial, lem, base;  // K6b's arrays the caller does not hand in
 };
 
-// K6c (lh_collect.hip): the naive sequences of the last lh_eval_draw_batch / lh_naive_sequences batch, and the
-// candidate store lh_draws_resolve appends to (store[cur], K candidates; grown by copying into the other buffer).
-struct CollectWs {
-  DevBuf seqs, hash, flag, cand, pairs, states;
-  DevBuf gather_rows, gather_out;  // lh_draws_rows_read
-  DevBuf store[2];
-  int cur = 0;
-  int32_t K = 0, n_last = -1;
-  size_t cap = 0;  // candidates store[cur] holds room for
-};
-
-// K7 (lh_lineage.hip): the last lineage batch (its arrays belong to the caller, or to the handle after lh_lineage_batch)
-// and the lineage store lh_lineage_resolve appends to (store[cur], K sequences; grown as CollectWs's is).
-struct LineageWs {
-  DevBuf naive, path, nt_hash, aa_hash;  // lh_lineage_batch's device copies
-  DevBuf ids, flag, pairs, gather_slots, gather_out;
+// The sequence store (lh_device.h) on a handle: store[cur] holds K distinct sequences and room for cap, and grows by
+// copying into the other buffer.  The rest is the scratch of store_resolve and store_rows_read.
+struct SeqStore {
+  DevBuf ids, flag, pairs;
+  DevBuf gather_slots, gather_out;
   DevBuf store[2];
   int cur = 0;
   int32_t K = 0;
-  size_t cap = 0;
+  size_t cap = 0;  // sequences store[cur] holds room for
+};
+
+// K6c (lh_collect.hip): the naive sequences of the last lh_eval_draw_batch / lh_naive_sequences batch, and the
+// candidate store lh_draws_resolve appends to.
+struct CollectWs {
+  DevBuf seqs, hash, states;
+  int32_t n_last = -1;
+  SeqStore store;
+};
+
+// K7 (lh_lineage.hip): the last lineage batch (its arrays belong to the caller, or to the handle after lh_lineage_batch)
+// and the lineage store lh_lineage_resolve appends to.
+struct LineageWs {
+  DevBuf naive, path, nt_hash, aa_hash;  // lh_lineage_batch's device copies
   lh::LineageBatch last{};  // last.n < 0: no batch
+  SeqStore store;
   LineageWs() { last.n = -1; }
 };
 
@@ -1937,6 +1941,96 @@ int collect_launch(lh_family* f, const lh::CollectTables& t, int n, const int32_
   return 0;
 }
 
+
+// The sequence store's operations, once for both features: `src` is the last batch's row source with n slots (the entry
+// point has checked that there is one), W the entry point's name.
+// ids[x] of slot x: -1 leaves it out, below s.K names a stored sequence, from s.K on a new one.  New ids must be
+// consecutive, each with a slot of the batch, whose first is appended.  Every slot with an id is then compared with its
+// stored sequence: the mismatching slots come back in ascending order.
+template <class Rows>
+int store_resolve(const std::string& W, SeqStore& s, const Rows& src, int32_t n, const int32_t* ids, int32_t* n_mismatch,
+                  int32_t* mismatch) {
+  if (n > 0 && !ids) return fail(W + ": null array");
+  const int L = src.L;
+  int32_t K_new = s.K;
+  for (int32_t x = 0; x < n; ++x) {
+    if (ids[x] < -1) return fail(W + ": id below -1");
+    K_new = std::max(K_new, ids[x] + 1);
+  }
+  std::vector<int32_t> first((size_t)(K_new - s.K), -1), pairs;
+  for (int32_t x = 0; x < n; ++x)
+    if (ids[x] >= s.K && first[ids[x] - s.K] < 0) first[ids[x] - s.K] = x;
+  for (size_t k = 0; k < first.size(); ++k) {
+    if (first[k] < 0) return fail(W + ": new ids must be consecutive, each with a row of the batch");
+    pairs.push_back(s.K + (int32_t)k);
+    pairs.push_back(first[k]);
+  }
+  LH_HIP(hipDeviceSynchronize());
+  if ((size_t)K_new > s.cap) {  // grow the store, keeping what it holds
+    const size_t cap = std::max<size_t>({(size_t)K_new, 2 * s.cap, 256});
+    DevBuf& nb = s.store[s.cur ^ 1];
+    if (nb.ensure(cap * L)) return 1;
+    if (s.K > 0) LH_HIP(hipMemcpy(nb.get(), s.store[s.cur].get(), (size_t)s.K * L, hipMemcpyDeviceToDevice));
+    s.cur ^= 1;
+    s.cap = cap;
+  }
+  if (n == 0) {
+    if (n_mismatch) *n_mismatch = 0;
+    return 0;
+  }
+  if (s.ids.ensure(sizeof(int32_t) * n) || s.flag.ensure(n) || s.pairs.ensure(sizeof(int32_t) * pairs.size())) return 1;
+  LH_HIP(hipMemcpy(s.ids.get(), ids, sizeof(int32_t) * n, hipMemcpyHostToDevice));
+  if (!pairs.empty()) LH_HIP(hipMemcpy(s.pairs.get(), pairs.data(), sizeof(int32_t) * pairs.size(), hipMemcpyHostToDevice));
+  uint8_t* store = s.store[s.cur].get<uint8_t>();
+  lh::launch_store_append(src, K_new, (int)(pairs.size() / 2), s.pairs.get<const int32_t>(), store, nullptr);
+  lh::launch_store_verify(src, K_new, s.ids.get<const int32_t>(), store, s.flag.get<uint8_t>(), nullptr);
+  LH_HIP(hipGetLastError());
+  std::vector<uint8_t> flag(n);
+  LH_HIP(hipMemcpy(flag.data(), s.flag.get(), n, hipMemcpyDeviceToHost));
+  s.K = K_new;
+  int32_t m = 0;
+  for (int32_t x = 0; x < n; ++x)
+    if (flag[x]) {
+      if (mismatch) mismatch[m] = x;
+      ++m;
+    }
+  if (n_mismatch) *n_mismatch = m;
+  return 0;
+}
+
+// seqs[q][0..L) = the bytes of slot slots[q] of the last batch (a padding slot reads as N)
+template <class Rows>
+int store_rows_read(const std::string& W, SeqStore& s, const Rows& src, int32_t n, int32_t n_out, const int32_t* slots,
+                    uint8_t* seqs) {
+  if (n_out > 0 && (!slots || !seqs)) return fail(W + ": null array");
+  for (int32_t q = 0; q < n_out; ++q)
+    if (slots[q] < 0 || slots[q] >= n) return fail(W + ": row outside the last batch");
+  if (n_out <= 0) return 0;
+  const size_t bytes = (size_t)n_out * src.L;
+  if (s.gather_slots.ensure(sizeof(int32_t) * n_out) || s.gather_out.ensure(bytes)) return 1;
+  LH_HIP(hipDeviceSynchronize());
+  LH_HIP(hipMemcpy(s.gather_slots.get(), slots, sizeof(int32_t) * n_out, hipMemcpyHostToDevice));
+  lh::launch_store_gather(src, n_out, s.gather_slots.get<const int32_t>(), s.gather_out.get<uint8_t>(), nullptr);
+  LH_HIP(hipGetLastError());
+  LH_HIP(hipMemcpy(seqs, s.gather_out.get(), bytes, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// *K = the store's count; seqs[count][L] = its sequences first .. first + count - 1
+int store_read(const std::string& W, const SeqStore& s, size_t L, int32_t first, int32_t count, int32_t* K, uint8_t* seqs) {
+  if (K) *K = s.K;
+  if (!seqs || count == 0) return 0;
+  if (first < 0 || count < 0 || first > s.K || count > s.K - first) return fail(W + ": ids outside the store");
+  LH_HIP(hipDeviceSynchronize());
+  LH_HIP(hipMemcpy(seqs, s.store[s.cur].get<uint8_t>() + first * L, count * L, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// the rows of the last K6c batch
+lh::FlatRows draw_rows(const lh_family* f) {
+  return lh::FlatRows{f->collect.n_last, f->host.n_sites, f->collect.seqs.get<const uint8_t>()};
+}
+
 }  // namespace
 
 extern "C" {
@@ -2006,94 +2100,27 @@ int lh_draws_resolve(lh_family* f, int32_t n, const int32_t* cand, int32_t* n_mi
   const std::string W = "lh_draws_resolve";
   if (!f) return fail(W + ": null family");
   DeviceGuard guard(f);
-  CollectWs& c = f->collect;
-  if (n != c.n_last) return fail(W + ": n differs from the last batch's row count");
-  if (n > 0 && !cand) return fail(W + ": null array");
-  const int L = f->host.n_sites;
-  // new candidates: ids K .. K_new - 1, each with a first row in this batch
-  int32_t K_new = c.K;
-  for (int32_t i = 0; i < n; ++i) {
-    if (cand[i] < -1) return fail(W + ": candidate id below -1");
-    K_new = std::max(K_new, cand[i] + 1);
-  }
-  std::vector<int32_t> first((size_t)(K_new - c.K), -1), pairs;
-  for (int32_t i = 0; i < n; ++i)
-    if (cand[i] >= c.K && first[cand[i] - c.K] < 0) first[cand[i] - c.K] = i;
-  for (size_t k = 0; k < first.size(); ++k) {
-    if (first[k] < 0) return fail(W + ": new candidate ids must be consecutive, each with a row of the batch");
-    pairs.push_back(c.K + (int32_t)k);
-    pairs.push_back(first[k]);
-  }
-  LH_HIP(hipDeviceSynchronize());
-  if ((size_t)K_new > c.cap) {  // grow the store, keeping what it holds
-    const size_t cap = std::max<size_t>({(size_t)K_new, 2 * c.cap, 256});
-    DevBuf& nb = c.store[c.cur ^ 1];
-    if (nb.ensure(cap * L)) return 1;
-    if (c.K > 0) LH_HIP(hipMemcpy(nb.get(), c.store[c.cur].get(), (size_t)c.K * L, hipMemcpyDeviceToDevice));
-    c.cur ^= 1;
-    c.cap = cap;
-  }
-  if (n == 0) {
-    if (n_mismatch) *n_mismatch = 0;
-    return 0;
-  }
-  if (c.cand.ensure(sizeof(int32_t) * n) || c.flag.ensure(n) || c.pairs.ensure(sizeof(int32_t) * pairs.size())) return 1;
-  LH_HIP(hipMemcpy(c.cand.get(), cand, sizeof(int32_t) * n, hipMemcpyHostToDevice));
-  if (!pairs.empty()) LH_HIP(hipMemcpy(c.pairs.get(), pairs.data(), sizeof(int32_t) * pairs.size(), hipMemcpyHostToDevice));
-  uint8_t* store = c.store[c.cur].get<uint8_t>();
-  lh::launch_collect_append((int)(pairs.size() / 2), n, L, K_new, c.pairs.get<const int32_t>(), c.seqs.get<const uint8_t>(),
-                            store, nullptr);
-  lh::launch_collect_verify(n, L, K_new, c.seqs.get<const uint8_t>(), c.cand.get<const int32_t>(), store,
-                            c.flag.get<uint8_t>(), nullptr);
-  LH_HIP(hipGetLastError());
-  std::vector<uint8_t> flag(n);
-  LH_HIP(hipMemcpy(flag.data(), c.flag.get(), n, hipMemcpyDeviceToHost));
-  c.K = K_new;
-  int32_t m = 0;
-  for (int32_t i = 0; i < n; ++i)
-    if (flag[i]) {
-      if (mismatch_rows) mismatch_rows[m] = i;
-      ++m;
-    }
-  if (n_mismatch) *n_mismatch = m;
-  return 0;
+  if (n != f->collect.n_last) return fail(W + ": n differs from the last batch's row count");
+  return store_resolve(W, f->collect.store, draw_rows(f), n, cand, n_mismatch, mismatch_rows);
 }
 
 int lh_draws_rows_read(lh_family* f, int32_t n_rows, const int32_t* rows, uint8_t* seqs) {
   const std::string W = "lh_draws_rows_read";
   if (!f) return fail(W + ": null family");
   DeviceGuard guard(f);
-  CollectWs& c = f->collect;
-  const size_t L = f->host.n_sites;
-  if (n_rows > 0 && (!rows || !seqs)) return fail(W + ": null array");
-  for (int32_t k = 0; k < n_rows; ++k)
-    if (rows[k] < 0 || rows[k] >= c.n_last) return fail(W + ": row outside the last batch");
-  if (n_rows <= 0) return 0;
-  if (c.gather_rows.ensure(sizeof(int32_t) * n_rows) || c.gather_out.ensure((size_t)n_rows * L)) return 1;
-  LH_HIP(hipDeviceSynchronize());
-  LH_HIP(hipMemcpy(c.gather_rows.get(), rows, sizeof(int32_t) * n_rows, hipMemcpyHostToDevice));
-  lh::launch_collect_gather(n_rows, c.n_last, (int)L, c.gather_rows.get<const int32_t>(), c.seqs.get<const uint8_t>(),
-                            c.gather_out.get<uint8_t>(), nullptr);
-  LH_HIP(hipGetLastError());
-  LH_HIP(hipMemcpy(seqs, c.gather_out.get(), (size_t)n_rows * L, hipMemcpyDeviceToHost));
-  return 0;
+  return store_rows_read(W, f->collect.store, draw_rows(f), f->collect.n_last, n_rows, rows, seqs);
 }
 
 int lh_draws_candidates_read(lh_family* f, int32_t* K, uint8_t* seqs) {
-  if (!f) return fail("lh_draws_candidates_read: null family");
+  const std::string W = "lh_draws_candidates_read";
+  if (!f) return fail(W + ": null family");
   DeviceGuard guard(f);
-  CollectWs& c = f->collect;
-  if (K) *K = c.K;
-  if (seqs && c.K > 0) {
-    LH_HIP(hipDeviceSynchronize());
-    LH_HIP(hipMemcpy(seqs, c.store[c.cur].get(), (size_t)c.K * f->host.n_sites, hipMemcpyDeviceToHost));
-  }
-  return 0;
+  return store_read(W, f->collect.store, f->host.n_sites, 0, f->collect.store.K, K, seqs);
 }
 
 int lh_draws_reset(lh_family* f) {
   if (!f) return fail("lh_draws_reset: null family");
-  f->collect.K = 0;
+  f->collect.store.K = 0;
   f->collect.n_last = -1;
   return 0;
 }
@@ -2200,98 +2227,31 @@ int lh_lineage_resolve(lh_family* f, int32_t n_slots, const int32_t* ids, int32_
   const std::string W = "lh_lineage_resolve";
   if (!f) return fail(W + ": null family");
   DeviceGuard guard(f);
-  LineageWs& w = f->lineage;
-  const lh::LineageBatch& b = w.last;
+  const lh::LineageBatch& b = f->lineage.last;
   if (b.n < 0) return fail(W + ": no lineage batch on the handle");
   if (n_slots != b.n * (b.P + 1)) return fail(W + ": n_slots differs from the last batch's rows x (path length + 1)");
-  if (n_slots > 0 && !ids) return fail(W + ": null array");
-  const int L = b.L;
-  // new sequences: ids K .. K_new - 1, each with a first slot in this batch
-  int32_t K_new = w.K;
-  for (int32_t x = 0; x < n_slots; ++x) {
-    if (ids[x] < -1) return fail(W + ": sequence id below -1");
-    K_new = std::max(K_new, ids[x] + 1);
-  }
-  std::vector<int32_t> first((size_t)(K_new - w.K), -1), pairs;
-  for (int32_t x = 0; x < n_slots; ++x)
-    if (ids[x] >= w.K && first[ids[x] - w.K] < 0) first[ids[x] - w.K] = x;
-  for (size_t k = 0; k < first.size(); ++k) {
-    if (first[k] < 0) return fail(W + ": new sequence ids must be consecutive, each with a slot of the batch");
-    pairs.push_back(w.K + (int32_t)k);
-    pairs.push_back(first[k]);
-  }
-  LH_HIP(hipDeviceSynchronize());
-  if ((size_t)K_new > w.cap) {  // grow the store, keeping what it holds
-    const size_t cap = std::max<size_t>({(size_t)K_new, 2 * w.cap, 256});
-    DevBuf& nb = w.store[w.cur ^ 1];
-    if (nb.ensure(cap * L)) return 1;
-    if (w.K > 0) LH_HIP(hipMemcpy(nb.get(), w.store[w.cur].get(), (size_t)w.K * L, hipMemcpyDeviceToDevice));
-    w.cur ^= 1;
-    w.cap = cap;
-  }
-  if (n_slots == 0) {
-    if (n_mismatch) *n_mismatch = 0;
-    return 0;
-  }
-  if (w.ids.ensure(sizeof(int32_t) * n_slots) || w.flag.ensure(n_slots) || w.pairs.ensure(sizeof(int32_t) * pairs.size()))
-    return 1;
-  LH_HIP(hipMemcpy(w.ids.get(), ids, sizeof(int32_t) * n_slots, hipMemcpyHostToDevice));
-  if (!pairs.empty()) LH_HIP(hipMemcpy(w.pairs.get(), pairs.data(), sizeof(int32_t) * pairs.size(), hipMemcpyHostToDevice));
-  uint8_t* store = w.store[w.cur].get<uint8_t>();
-  lh::launch_lineage_append(b, (int)(pairs.size() / 2), K_new, w.pairs.get<const int32_t>(), store, nullptr);
-  lh::launch_lineage_verify(b, K_new, w.ids.get<const int32_t>(), store, w.flag.get<uint8_t>(), nullptr);
-  LH_HIP(hipGetLastError());
-  std::vector<uint8_t> flag(n_slots);
-  LH_HIP(hipMemcpy(flag.data(), w.flag.get(), n_slots, hipMemcpyDeviceToHost));
-  w.K = K_new;
-  int32_t m = 0;
-  for (int32_t x = 0; x < n_slots; ++x)
-    if (flag[x]) {
-      if (mismatch_slots) mismatch_slots[m] = x;
-      ++m;
-    }
-  if (n_mismatch) *n_mismatch = m;
-  return 0;
+  return store_resolve(W, f->lineage.store, b, n_slots, ids, n_mismatch, mismatch_slots);
 }
 
 int lh_lineage_rows_read(lh_family* f, int32_t n_slots, const int32_t* slots, uint8_t* seqs) {
   const std::string W = "lh_lineage_rows_read";
   if (!f) return fail(W + ": null family");
   DeviceGuard guard(f);
-  LineageWs& w = f->lineage;
-  const lh::LineageBatch& b = w.last;
+  const lh::LineageBatch& b = f->lineage.last;
   if (b.n < 0) return fail(W + ": no lineage batch on the handle");
-  if (n_slots > 0 && (!slots || !seqs)) return fail(W + ": null array");
-  for (int32_t k = 0; k < n_slots; ++k)
-    if (slots[k] < 0 || slots[k] >= b.n * (b.P + 1)) return fail(W + ": slot outside the last batch");
-  if (n_slots <= 0) return 0;
-  const size_t bytes = (size_t)n_slots * b.L;
-  if (w.gather_slots.ensure(sizeof(int32_t) * n_slots) || w.gather_out.ensure(bytes)) return 1;
-  LH_HIP(hipDeviceSynchronize());
-  LH_HIP(hipMemcpy(w.gather_slots.get(), slots, sizeof(int32_t) * n_slots, hipMemcpyHostToDevice));
-  lh::launch_lineage_gather(b, n_slots, w.gather_slots.get<const int32_t>(), w.gather_out.get<uint8_t>(), nullptr);
-  LH_HIP(hipGetLastError());
-  LH_HIP(hipMemcpy(seqs, w.gather_out.get(), bytes, hipMemcpyDeviceToHost));
-  return 0;
+  return store_rows_read(W, f->lineage.store, b, b.n * (b.P + 1), n_slots, slots, seqs);
 }
 
 int lh_lineage_store_read(lh_family* f, int32_t first, int32_t count, int32_t* K, uint8_t* seqs) {
   const std::string W = "lh_lineage_store_read";
   if (!f) return fail(W + ": null family");
   DeviceGuard guard(f);
-  LineageWs& w = f->lineage;
-  if (K) *K = w.K;
-  if (!seqs || count == 0) return 0;
-  if (first < 0 || count < 0 || first > w.K || count > w.K - first) return fail(W + ": ids outside the store");
-  const size_t L = f->host.n_sites;
-  LH_HIP(hipDeviceSynchronize());
-  LH_HIP(hipMemcpy(seqs, w.store[w.cur].get<uint8_t>() + (size_t)first * L, (size_t)count * L, hipMemcpyDeviceToHost));
-  return 0;
+  return store_read(W, f->lineage.store, f->host.n_sites, first, count, K, seqs);
 }
 
 int lh_lineage_reset(lh_family* f) {
   if (!f) return fail("lh_lineage_reset: null family");
-  f->lineage.K = 0;
+  f->lineage.store.K = 0;
   f->lineage.last.n = -1;
   return 0;
 }

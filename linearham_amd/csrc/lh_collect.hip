@@ -10,8 +10,10 @@
 // barrier between regions, then hashed and written out as bytes seqs[n][L] (A,C,G,T,N = 0..4).  The hash is an XOR over
 // the row's 8-byte words of a 64-bit mix of (word, position): XOR is exact and order-free, so the bits do not depend
 // on the lane split, the batch or the run.
-// verify_kernel: one wave per row compares the row's bytes with the stored candidate the host assigned to it.
-// append_kernel: copies the first row of each new candidate into the candidate store; gather_kernel: rows to read back.
+// verify_kernel, append_kernel, gather_kernel: the sequence store's three (lh_device.h), written once over a row source
+// and instantiated for K6c's rows (slot x = row x of seqs) and K7's (slot x = a row of anc or naive, found through the
+// path).  verify: one wave per slot compares its bytes with the stored sequence the host assigned to it; append copies
+// the first slot of each new id into the store; gather: the slots a host reads back.
 // No atomics anywhere; every output element has one writer.
 #include <algorithm>
 
@@ -109,46 +111,58 @@ __global__ void __launch_bounds__(kThreads)
   if (lane == 0) hash[r] = hash_finish(((uint64_t)hi << 32) | lo, t.L) & t.hash_mask;
 }
 
-// flag[i] = 1 where row i's bytes differ from those of candidate cand[i] (0 for rows with cand[i] < 0)
+// The sequence store's three kernels (lh_device.h), generic over the row source.
+// flag[x] = 1 where slot x's bytes differ from those of store[ids[x]], or it has no row, or the store does not hold that
+// id (0 for slots with ids[x] < 0).  One wave per slot.
+template <class Rows>
 __global__ void __launch_bounds__(kThreads)
-    verify_kernel(int n, int L, int K, const uint8_t* __restrict__ seqs, const int32_t* __restrict__ cand,
-                  const uint8_t* __restrict__ store, uint8_t* __restrict__ flag) {
+    verify_kernel(Rows src, int K, const int32_t* __restrict__ ids, const uint8_t* __restrict__ store,
+                  uint8_t* __restrict__ flag) {
   const int lane = threadIdx.x & 63;
-  const int r = blockIdx.x * kRowsPerBlock + (threadIdx.x >> 6);
-  if (r >= n) return;
-  const int k = cand[r];
+  const size_t x = (size_t)blockIdx.x * kRowsPerBlock + (threadIdx.x >> 6);
+  if (x >= n_slots(src)) return;
+  const int k = ids[x], L = src.L;
+  const uint8_t* row = k >= 0 ? slot_row(src, (int)x) : nullptr;
   bool diff = false;
-  if (k >= 0 && k < K) {
-    const uint8_t* a = seqs + (size_t)r * L;
-    const uint8_t* b = store + (size_t)k * L;
-    for (int j = lane; j < L; j += 64) diff |= a[j] != b[j];
+  if (row && k < K) {
+    const uint8_t* st = store + (size_t)k * L;
+    for (int j = lane; j < L; j += 64) diff |= row[j] != st[j];
   }
   const bool any = __any(diff);
-  if (lane == 0) flag[r] = (k >= K) || any ? 1 : 0;  // (an id the store does not hold is a mismatch too)
+  if (lane == 0) flag[x] = k >= 0 && (k >= K || !row || any) ? 1 : 0;
 }
 
-// store[pairs[2p]][..] = seqs[pairs[2p + 1]][..]
+// store[pairs[2p]][..] = slot pairs[2p + 1]
+template <class Rows>
 __global__ void __launch_bounds__(kThreads)
-    append_kernel(int n_pairs, int n, int L, int K, const int32_t* __restrict__ pairs, const uint8_t* __restrict__ seqs,
-                  uint8_t* __restrict__ store) {
-  const size_t total = (size_t)n_pairs * L;
+    append_kernel(Rows src, int K, int n_pairs, const int32_t* __restrict__ pairs, uint8_t* __restrict__ store) {
+  const int L = src.L;
+  const size_t total = (size_t)n_pairs * L, slots = n_slots(src);
   for (size_t x = (size_t)blockIdx.x * kThreads + threadIdx.x; x < total; x += (size_t)gridDim.x * kThreads) {
     const size_t p = x / L, j = x % L;
-    const int k = pairs[2 * p], r = pairs[2 * p + 1];
-    if (k >= 0 && k < K && r >= 0 && r < n) store[(size_t)k * L + j] = seqs[(size_t)r * L + j];
+    const int k = pairs[2 * p], y = pairs[2 * p + 1];
+    if (k < 0 || k >= K || y < 0 || (size_t)y >= slots) continue;
+    const uint8_t* row = slot_row(src, y);
+    if (row) store[(size_t)k * L + j] = row[j];
   }
 }
 
-// out[q][..] = seqs[rows[q]][..] (the rows a host reads back: collisions to resolve)
+// out[q][..] = slot slots_in[q] (the rows a host reads back: collisions to resolve)
+template <class Rows>
 __global__ void __launch_bounds__(kThreads)
-    gather_kernel(int n_rows, int n, int L, const int32_t* __restrict__ rows, const uint8_t* __restrict__ seqs,
-                  uint8_t* __restrict__ out) {
-  const size_t total = (size_t)n_rows * L;
+    gather_kernel(Rows src, int n_out, const int32_t* __restrict__ slots_in, uint8_t* __restrict__ out) {
+  const int L = src.L;
+  const size_t total = (size_t)n_out * L, slots = n_slots(src);
   for (size_t x = (size_t)blockIdx.x * kThreads + threadIdx.x; x < total; x += (size_t)gridDim.x * kThreads) {
     const size_t q = x / L, j = x % L;
-    const int r = rows[q];
-    out[x] = (r >= 0 && r < n) ? seqs[(size_t)r * L + j] : (uint8_t)4;
+    const int y = slots_in[q];
+    const uint8_t* row = (y >= 0 && (size_t)y < slots) ? slot_row(src, y) : nullptr;
+    out[x] = row ? row[j] : (uint8_t)4;
   }
+}
+
+unsigned byte_blocks(size_t total) {
+  return (unsigned)std::max<size_t>(1, std::min<size_t>((total + kThreads - 1) / kThreads, 4096));
 }
 
 }  // namespace
@@ -166,27 +180,35 @@ void launch_collect(const CollectTables& t, int n, const int32_t* states, uint8_
   hipLaunchKernelGGL(assemble_kernel, dim3(blocks), dim3(kThreads), lds, stream, t, n, states, seqs, hash);
 }
 
-void launch_collect_verify(int n, int L, int K, const uint8_t* seqs, const int32_t* cand, const uint8_t* store,
-                           uint8_t* flag, hipStream_t stream) {
-  if (n <= 0) return;
-  hipLaunchKernelGGL(verify_kernel, dim3((n + kRowsPerBlock - 1) / kRowsPerBlock), dim3(kThreads), 0, stream, n, L, K,
-                     seqs, cand, store, flag);
+template <class Rows>
+void launch_store_verify(const Rows& src, int K, const int32_t* ids, const uint8_t* store, uint8_t* flag,
+                         hipStream_t stream) {
+  const size_t slots = n_slots(src);
+  if (slots == 0) return;
+  hipLaunchKernelGGL(verify_kernel<Rows>, dim3((unsigned)((slots + kRowsPerBlock - 1) / kRowsPerBlock)), dim3(kThreads), 0,
+                     stream, src, K, ids, store, flag);
 }
 
-void launch_collect_append(int n_pairs, int n, int L, int K, const int32_t* pairs, const uint8_t* seqs, uint8_t* store,
-                           hipStream_t stream) {
-  if (n_pairs <= 0) return;
-  const size_t total = (size_t)n_pairs * L;
-  const unsigned blocks = (unsigned)std::max<size_t>(1, std::min<size_t>((total + kThreads - 1) / kThreads, 4096));
-  hipLaunchKernelGGL(append_kernel, dim3(blocks), dim3(kThreads), 0, stream, n_pairs, n, L, K, pairs, seqs, store);
+template <class Rows>
+void launch_store_append(const Rows& src, int K, int n_pairs, const int32_t* pairs, uint8_t* store, hipStream_t stream) {
+  if (n_pairs <= 0 || n_slots(src) == 0) return;
+  hipLaunchKernelGGL(append_kernel<Rows>, dim3(byte_blocks((size_t)n_pairs * src.L)), dim3(kThreads), 0, stream, src, K,
+                     n_pairs, pairs, store);
 }
 
-void launch_collect_gather(int n_rows, int n, int L, const int32_t* rows, const uint8_t* seqs, uint8_t* out,
-                           hipStream_t stream) {
-  if (n_rows <= 0) return;
-  const size_t total = (size_t)n_rows * L;
-  const unsigned blocks = (unsigned)std::max<size_t>(1, std::min<size_t>((total + kThreads - 1) / kThreads, 4096));
-  hipLaunchKernelGGL(gather_kernel, dim3(blocks), dim3(kThreads), 0, stream, n_rows, n, L, rows, seqs, out);
+template <class Rows>
+void launch_store_gather(const Rows& src, int n_out, const int32_t* slots, uint8_t* out, hipStream_t stream) {
+  if (n_out <= 0 || n_slots(src) == 0) return;
+  hipLaunchKernelGGL(gather_kernel<Rows>, dim3(byte_blocks((size_t)n_out * src.L)), dim3(kThreads), 0, stream, src, n_out,
+                     slots, out);
 }
+
+#define LH_STORE_KERNELS(Rows)                                                                                          \
+  template void launch_store_verify<Rows>(const Rows&, int, const int32_t*, const uint8_t*, uint8_t*, hipStream_t);     \
+  template void launch_store_append<Rows>(const Rows&, int, int, const int32_t*, uint8_t*, hipStream_t);                \
+  template void launch_store_gather<Rows>(const Rows&, int, const int32_t*, uint8_t*, hipStream_t);
+LH_STORE_KERNELS(FlatRows)
+LH_STORE_KERNELS(LineageBatch)
+#undef LH_STORE_KERNELS
 
 }  // namespace lh

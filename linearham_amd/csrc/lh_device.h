@@ -247,15 +247,17 @@ __host__ __device__ inline uint64_t hash_finish(uint64_t h, int length) { return
 
 void launch_collect(const CollectTables& t, int n, const int32_t* states, uint8_t* seqs, uint64_t* hash, hipStream_t stream);
 size_t collect_lds_bytes(int L);
-// flag[n]: 1 where row i differs from store[cand[i]] (cand[i] < 0: 0; cand[i] >= K: 1)
-void launch_collect_verify(int n, int L, int K, const uint8_t* seqs, const int32_t* cand, const uint8_t* store,
-                           uint8_t* flag, hipStream_t stream);
-// store[pairs[2p]] = seqs[pairs[2p + 1]] for p < n_pairs (candidate, row)
-void launch_collect_append(int n_pairs, int n, int L, int K, const int32_t* pairs, const uint8_t* seqs, uint8_t* store,
-                           hipStream_t stream);
-// out[q][..] = seqs[rows[q]][..] for q < n_rows (rows outside 0..n-1 read as N)
-void launch_collect_gather(int n_rows, int n, int L, const int32_t* rows, const uint8_t* seqs, uint8_t* out,
-                           hipStream_t stream);
+
+// The sequence store (lh_collect.hip): a growable device array of distinct byte sequences, store[K][L], behind three
+// kernels that are generic over where a batch's rows lie.  A row source answers two questions: n_slots(src), how many
+// flat slots the batch has (at most INT32_MAX), and slot_row(src, x), the src.L bytes of slot x or null for a slot without
+// a row.  K6c's source is FlatRows, K7's is LineageBatch.
+struct FlatRows {
+  int32_t n, L;
+  const uint8_t* seqs;  // [n][L]
+};
+__host__ __device__ inline size_t n_slots(const FlatRows& r) { return r.n > 0 ? (size_t)r.n : 0; }
+__device__ inline const uint8_t* slot_row(const FlatRows& r, int x) { return r.seqs + (size_t)x * r.L; }
 
 // K7 (lh_lineage.hip): the lineage slots of a batch.  Slot s < P of sample i is the row anc[i][path[i*P + s] - T][0..L)
 // of K3's output (path entries outside T .. 2T-3 are padding), slot P the row naive[i][0..L).  A flat slot is i*(P+1)+s.
@@ -266,17 +268,30 @@ struct LineageBatch {
   const int32_t* path;   // [n][P]
   uint64_t hash_mask;
 };
+__host__ __device__ inline size_t n_slots(const LineageBatch& b) { return b.n > 0 ? (size_t)b.n * (b.P + 1) : 0; }
+// the row of slot (i, s), null for a padding slot
+__device__ inline const uint8_t* slot_row(const LineageBatch& b, int i, int s) {
+  if (s == b.P) return b.naive + (size_t)i * b.L;
+  const int v = b.path[(size_t)i * b.P + s];
+  if (v < b.T || v >= 2 * b.T - 2) return nullptr;
+  return b.anc + ((size_t)i * (b.T - 2) + (v - b.T)) * b.L;
+}
+__device__ inline const uint8_t* slot_row(const LineageBatch& b, int x) { return slot_row(b, x / (b.P + 1), x % (b.P + 1)); }
 constexpr uint64_t kLineagePadHash = 0;  // LH_LINEAGE_PAD_HASH
 // nt_hash, aa_hash [n][P+1]
 void launch_lineage(const LineageBatch& b, uint64_t* nt_hash, uint64_t* aa_hash, hipStream_t stream);
-// flag[x] = 1 where flat slot x differs from store[ids[x]] (ids[x] < 0: 0; ids[x] >= K or a padding slot: 1)
-void launch_lineage_verify(const LineageBatch& b, int K, const int32_t* ids, const uint8_t* store, uint8_t* flag,
-                           hipStream_t stream);
-// store[pairs[2p]] = flat slot pairs[2p + 1] for p < n_pairs
-void launch_lineage_append(const LineageBatch& b, int n_pairs, int K, const int32_t* pairs, uint8_t* store,
-                           hipStream_t stream);
-// out[q][..] = flat slot slots[q] for q < n_slots (padding slots read as N)
-void launch_lineage_gather(const LineageBatch& b, int n_slots, const int32_t* slots, uint8_t* out, hipStream_t stream);
+
+// The store's kernels, instantiated for FlatRows and LineageBatch (a slot outside the batch counts as one without a row).
+// flag[x] = 1 where slot x differs from store[ids[x]] (ids[x] < 0: 0; ids[x] >= K or no row: 1)
+template <class Rows>
+void launch_store_verify(const Rows& src, int K, const int32_t* ids, const uint8_t* store, uint8_t* flag,
+                         hipStream_t stream);
+// store[pairs[2p]] = slot pairs[2p + 1] for p < n_pairs (pairs outside the store or the batch, or without a row: skipped)
+template <class Rows>
+void launch_store_append(const Rows& src, int K, int n_pairs, const int32_t* pairs, uint8_t* store, hipStream_t stream);
+// out[q][..] = slot slots[q] for q < n_out (slots without a row read as N)
+template <class Rows>
+void launch_store_gather(const Rows& src, int n_out, const int32_t* slots, uint8_t* out, hipStream_t stream);
 
 // P = I + U expm1(lambda * t*r) Uinv, clamped at 0 (K1's prologue).
 // e: lambda[4] | U[4][4] | Uinv[4][4]

@@ -11,7 +11,6 @@
 // of a mix of (word, position), a final mix with the length), so its bits depend on the sequence alone and a naive
 // sequence hashes here as it does there.  Padding slots get kLineagePadHash; a sample whose schedule K3 refused (0xff in
 // its anc rows) gets all-ones in every slot.
-// verify / append / gather: lh_collect.hip's three, with a row found through the path instead of a row number.
 // No atomics anywhere; every output element has one writer.  Path entries are checked before they index anything.
 #include <algorithm>
 
@@ -53,14 +52,6 @@ __device__ const CodonTable kCodons = make_codon_table();
 
 __device__ inline uint8_t translate(uint8_t a, uint8_t b, uint8_t c) {
   return (a > 4 || b > 4 || c > 4) ? (uint8_t)'X' : kCodons.aa[a * 25 + b * 5 + c];
-}
-
-// the row of flat slot (i, s), null for a padding slot
-__device__ inline const uint8_t* slot_row(const LineageBatch& b, int i, int s) {
-  if (s == b.P) return b.naive + (size_t)i * b.L;
-  const int v = b.path[(size_t)i * b.P + s];
-  if (v < b.T || v >= 2 * b.T - 2) return nullptr;
-  return b.anc + ((size_t)i * (b.T - 2) + (v - b.T)) * b.L;
 }
 
 __device__ inline uint64_t wave_xor(uint64_t h) {
@@ -123,52 +114,8 @@ __global__ void __launch_bounds__(kThreads)
   }
 }
 
-__global__ void __launch_bounds__(kThreads)
-    lineage_verify_kernel(LineageBatch b, int K, const int32_t* __restrict__ ids, const uint8_t* __restrict__ store,
-                          uint8_t* __restrict__ flag) {
-  const int lane = threadIdx.x & 63;
-  const size_t x = (size_t)blockIdx.x * kSlotsPerBlock + (threadIdx.x >> 6);
-  if (x >= (size_t)b.n * (b.P + 1)) return;
-  const int k = ids[x];
-  const uint8_t* row = k >= 0 ? slot_row(b, (int)(x / (b.P + 1)), (int)(x % (b.P + 1))) : nullptr;
-  bool diff = false;
-  if (row && k < K) {
-    const uint8_t* st = store + (size_t)k * b.L;
-    for (int j = lane; j < b.L; j += 64) diff |= row[j] != st[j];
-  }
-  const bool any = __any(diff);
-  if (lane == 0) flag[x] = k >= 0 && (k >= K || !row || any) ? 1 : 0;
-}
-
-__global__ void __launch_bounds__(kThreads)
-    lineage_append_kernel(LineageBatch b, int n_pairs, int K, const int32_t* __restrict__ pairs,
-                          uint8_t* __restrict__ store) {
-  const size_t total = (size_t)n_pairs * b.L, slots = (size_t)b.n * (b.P + 1);
-  for (size_t x = (size_t)blockIdx.x * kThreads + threadIdx.x; x < total; x += (size_t)gridDim.x * kThreads) {
-    const size_t p = x / b.L, j = x % b.L;
-    const int k = pairs[2 * p], y = pairs[2 * p + 1];
-    if (k < 0 || k >= K || y < 0 || (size_t)y >= slots) continue;
-    const uint8_t* row = slot_row(b, y / (b.P + 1), y % (b.P + 1));
-    if (row) store[(size_t)k * b.L + j] = row[j];
-  }
-}
-
-__global__ void __launch_bounds__(kThreads)
-    lineage_gather_kernel(LineageBatch b, int n_slots, const int32_t* __restrict__ slots_in, uint8_t* __restrict__ out) {
-  const size_t total = (size_t)n_slots * b.L, slots = (size_t)b.n * (b.P + 1);
-  for (size_t x = (size_t)blockIdx.x * kThreads + threadIdx.x; x < total; x += (size_t)gridDim.x * kThreads) {
-    const size_t q = x / b.L, j = x % b.L;
-    const int y = slots_in[q];
-    const uint8_t* row = (y >= 0 && (size_t)y < slots) ? slot_row(b, y / (b.P + 1), y % (b.P + 1)) : nullptr;
-    out[x] = row ? row[j] : (uint8_t)4;
-  }
-}
-
 unsigned slot_blocks(const LineageBatch& b) {
   return (unsigned)(((size_t)b.n * (b.P + 1) + kSlotsPerBlock - 1) / kSlotsPerBlock);
-}
-unsigned byte_blocks(size_t total) {
-  return (unsigned)std::max<size_t>(1, std::min<size_t>((total + kThreads - 1) / kThreads, 4096));
 }
 
 }  // namespace
@@ -176,25 +123,6 @@ unsigned byte_blocks(size_t total) {
 void launch_lineage(const LineageBatch& b, uint64_t* nt_hash, uint64_t* aa_hash, hipStream_t stream) {
   if (b.n <= 0) return;
   hipLaunchKernelGGL(lineage_kernel, dim3(slot_blocks(b)), dim3(kThreads), 0, stream, b, nt_hash, aa_hash);
-}
-
-void launch_lineage_verify(const LineageBatch& b, int K, const int32_t* ids, const uint8_t* store, uint8_t* flag,
-                           hipStream_t stream) {
-  if (b.n <= 0) return;
-  hipLaunchKernelGGL(lineage_verify_kernel, dim3(slot_blocks(b)), dim3(kThreads), 0, stream, b, K, ids, store, flag);
-}
-
-void launch_lineage_append(const LineageBatch& b, int n_pairs, int K, const int32_t* pairs, uint8_t* store,
-                           hipStream_t stream) {
-  if (n_pairs <= 0 || b.n <= 0) return;
-  hipLaunchKernelGGL(lineage_append_kernel, dim3(byte_blocks((size_t)n_pairs * b.L)), dim3(kThreads), 0, stream, b,
-                     n_pairs, K, pairs, store);
-}
-
-void launch_lineage_gather(const LineageBatch& b, int n_slots, const int32_t* slots, uint8_t* out, hipStream_t stream) {
-  if (n_slots <= 0 || b.n <= 0) return;
-  hipLaunchKernelGGL(lineage_gather_kernel, dim3(byte_blocks((size_t)n_slots * b.L)), dim3(kThreads), 0, stream, b,
-                     n_slots, slots, out);
 }
 
 }  // namespace lh
