@@ -45,6 +45,7 @@
 #include <cstdlib>
 
 #include <cstdio>
+#include <type_traits>
 
 #include "lh_device.h"
 
@@ -436,11 +437,12 @@ typedef __attribute__((address_space(3))) const char* lds_ptr;
 // fetches 32 bytes per tip and op with a scalar load.
 // kN: alignments that mix N with bases -- a third plane per site set flags the lanes whose state is N (6 masks per tip and
 // block instead of 4), and such a tip reads the four ones at `ones` (LDS) instead of a column; lh_prune_walk_asm_s2n.inc.
+// Leaves the root's vector a and the scaler counts; the caller closes the naive branch (close_naive_branch), with operands
+// it reads AFTER this statement: the statement clobbers all but a dozen scalar registers.
 template <int kDepth, bool kN, int S>
 __device__ __forceinline__ void prune_wave_asm(int block128, const uint64_t* __restrict__ planes, int n_blocks, int n_w,
                                                const WalkOp* __restrict__ wops, pmat_ptr pm, unsigned ctoff,
-                                               const double* tiptab, const double* naive_tab, const double* ones,
-                                               const double* __restrict__ p4, double (&lik)[S][5], int (&scl)[S]) {
+                                               const double* tiptab, const double* ones, double (&a)[S][4], int (&scal)[S]) {
   static_assert(S == 1 || S == 2, "one or two sites per lane");
   __attribute__((aligned(16))) double out_mem[4 * S + 2];                                   // a[S][4], then the packed scaler counts
   __attribute__((aligned(16))) double deep_mem[(kDepth > 2 ? kDepth - 2 : 1) * 4 * S];     // stack slots 2.. : [slot][site][4] (0 and 1: registers)
@@ -491,8 +493,6 @@ __device__ __forceinline__ void prune_wave_asm(int block128, const uint64_t* __r
 #include "lh_prune_walk_clobbers_s1.inc"
     );
   }
-  double a[S][4];
-  int scal[S];
 #pragma unroll
   for (int s = 0; s < S; ++s)
 #pragma unroll
@@ -500,7 +500,6 @@ __device__ __forceinline__ void prune_wave_asm(int block128, const uint64_t* __r
   const unsigned* packed = reinterpret_cast<const unsigned*>(out_mem + 4 * S);
 #pragma unroll
   for (int s = 0; s < S; ++s) scal[s] = (int)((packed[s / 2] >> (16 * (s & 1))) & 0xffffu);
-  close_naive_branch<S>(a, scal, naive_tab, p4, lik, scl);
 }
 
 template <int kDepth, int S, bool kN>
@@ -1133,47 +1132,119 @@ __global__ void __launch_bounds__(64) schedule_stack_check_kernel(int T, int slo
   }
 }
 
+// The cherry-table kernels' arguments: ONE block at the start of the kernel-argument segment, read field by field with
+// scalar loads where a field is used (what K2a does with its descriptor).  As twenty-one separate
+// parameters they were fetched at the kernel's entry and held in scalar registers to its end -- beside the 56 registers
+// of the eigen-system, and across a walk statement that leaves a dozen -- and the compiler parked them in vector lanes:
+// 248 v_writelane_b32 / v_readlane_b32 in the default kernel.
+// The kernels declare the block as their only parameter and never name it: they read it through
+// __builtin_amdgcn_kernarg_segment_ptr (ct_args), so host and device must agree on this one layout; launch_prune fills it
+// field by field, by name.
+struct PruneCtArgs {
+  int n2, tile, R, wpr;
+  int L, T, tabs_stride, pad_;
+  const uint8_t* msa;
+  const uint64_t* planes;
+  const int2* wops;
+  const double* wlen;
+  const int4* tabs;
+  const int4* hdr;
+  const double* brlen;
+  const double* rates;
+  const double* eig;
+  double* pmat_w;
+  size_t rate_stride;
+  const double* pi;
+  double* site_lik;
+  int32_t* site_scal;
+};
+typedef const PruneCtArgs __attribute__((address_space(4)))* ct_args_ptr;
+typedef int __attribute__((ext_vector_type(4))) ct_int4;
+
+// The block as the kernel sees it (its only parameter: the segment starts with it).  The pointer is the OUTPUT of a
+// volatile asm statement: loads through the result of one call are never merged with loads through another's, so a
+// phase of the kernel that calls this anew reads its fields anew -- scalar loads, no vector issue -- instead of
+// holding the earlier phase's copies in registers (ct_args_again: the next phase's view of the same block).
+// (This statement, the one in front of the eigen-system's loads and the v_mov_b32 copies of the thread index around the
+// walk do nothing at run time; they steer this compiler's common-subexpression elimination and register coalescing.
+// Another compiler version may need them elsewhere: what holds them in place is tests/test_k1_scalar_spills.py, which
+// counts the lane moves, scratch operations and vector instructions of every instantiation.)
+__device__ __forceinline__ ct_args_ptr ct_args_again(ct_args_ptr p) {
+  uint64_t v = reinterpret_cast<uint64_t>(p);
+  asm volatile("; lh: kernel arguments at %0, read again from here" : "+s"(v));
+  return (ct_args_ptr)v;
+}
+__device__ __forceinline__ ct_args_ptr ct_args() { return ct_args_again((ct_args_ptr)__builtin_amdgcn_kernarg_segment_ptr()); }
+
+// An input of the launch that earlier kernels wrote and this one only reads, through the constant address space: a
+// wave-uniform address is then a scalar load, whatever the pointer's own history.
+template <class T, class U>
+__device__ __forceinline__ const T __attribute__((address_space(4)))* ct_ro(const U* p) {
+  return (const T __attribute__((address_space(4)))*)reinterpret_cast<uint64_t>(p);
+}
+
+// A wave's place in its workgroup: rate category, wave and thread within the rate, threads per rate.  Fused, the rate is
+// wave / wpr: counted out in scalar registers (at most 15 steps; a division of wave-uniform integers goes through the
+// vector unit's float reciprocal).
+struct CtWave {
+  int rate, wave, nthr, rtid;
+};
+// What launch_prune lets a fused workgroup be, and what the kernels rely on: at most 16 waves (ct_wave counts a rate below
+// 16 out), and tip tables -- R * T * 128 bytes -- within 80 KB of LDS, so R * T <= 640; the pooled round's items per rate
+// stay below 3 T (matrices, tables and tips), and its float-reciprocal quotient is exact for R * rem < 2^21.
+constexpr int kCtFusedMaxWaves = 16;
+constexpr size_t kCtFusedMaxLds = 80 * 1024;
+static_assert(kCtFusedMaxWaves <= 16, "ct_wave counts at most 15 steps");
+static_assert(53 * 1024 <= kCtFusedMaxLds, "the limit of fused workgroups of up to eight waves (launch_prune) lies within it");
+static_assert(3 * (kCtFusedMaxLds / 128) < (1u << 21), "prune_body_ct: c / rem through v_rcp_f32 needs R * rem < 2^21");
+// threads of the workgroup (what the launcher makes blockDim.x; from the arguments, no second pointer into the segment)
+template <bool kFused>
+__device__ __forceinline__ int ct_block_threads(int R, int wpr) {
+  return (kFused ? R : 1) * wpr * 64;
+}
+template <bool kFused>
+__device__ __forceinline__ CtWave ct_wave(int tid, int wpr) {
+  const int wave_all = __builtin_amdgcn_readfirstlane(tid >> 6);
+  if constexpr (kFused) {
+    int rate = 0, wave = wave_all;
+    for (; wave >= wpr && rate < 15; ++rate) wave -= wpr;
+    return CtWave{rate, wave, wpr * 64, tid - rate * wpr * 64};
+  } else {
+    return CtWave{(int)blockIdx.y, wave_all, wpr * 64, tid};
+  }
+}
+
 // The workgroup of the cherry-table form.  Block layout as prune_body (n2 two-site waves + n1 one-site waves per rate;
 // kFused: all R rates of the sample in one workgroup, mixed at the end).  scratch: this (sample, rate)'s region of
 // rate_stride doubles: [n_mat + n_tab][16] P-matrices | [n_tab][E][4] tables.
+// The kernel has three phases -- the P-matrices, the cherry tables and the walk, the epilogue -- and each reads the
+// arguments (ct_args) and derives what it needs from them for itself: the first phase's scalars do not sit in registers
+// beside the eigen-system, and nothing but the walk's results, the thread index and the workgroup's coordinates crosses
+// the walk statement.
 template <int kDepth, bool kN, bool kFused, bool kAsm = false>
-__device__ __forceinline__ void prune_body_ct(int n2, int tile, int R, int wpr, const uint8_t* __restrict__ msa,
-                                              const uint64_t* __restrict__ planes, int L,
-                                              int T, const int2* __restrict__ wops, const double* __restrict__ wlen,
-                                              const int4* __restrict__ tabs, int tabs_stride,
-                                              const int4* __restrict__ hdr, const double* __restrict__ brlen,
-                                              const double* __restrict__ rates, const double* __restrict__ eig,
-                                              double* pmat_w, size_t rate_stride, const double* __restrict__ pi,
-                                              double* __restrict__ site_lik, int32_t* __restrict__ site_scal) {
+__device__ __forceinline__ void prune_body_ct() {
   extern __shared__ double2 smem2[];
   constexpr int SY = kN ? 5 : 4, E = SY * SY;
-  const int tid = threadIdx.x;
-  const int wave_all = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int rate = kFused ? wave_all / wpr : (int)blockIdx.y;
-  const int wave = kFused ? wave_all - rate * wpr : wave_all;
-  const int nthr = kFused ? wpr * 64 : (int)blockDim.x;
-  const int rtid = kFused ? tid - rate * nthr : tid;
-  const int sample = blockIdx.z;
-  const int n_ops = T - 2;
-  const int4 h = hdr[sample];
-  const int n_w = __builtin_amdgcn_readfirstlane(h.x);
-  const int n_mat = __builtin_amdgcn_readfirstlane(h.y), n_tab = __builtin_amdgcn_readfirstlane(h.z);
-  const bool malformed = h.w != 0;
-  double* pw = pmat_w + ((size_t)sample * R + rate) * rate_stride;
-  double* ctab = pw + (size_t)(T - 3 > 0 ? T - 3 : 0) * 16;
   constexpr int kS = 2;  // sites per lane of the multi-site waves
-  double* tiptab = reinterpret_cast<double*>(smem2) + (kFused ? (size_t)rate * T * 16 : 0);  // LDS tip table [T][4][4]
-  const double* naive_tab = tiptab;
-  // kN: four ones behind the table(s) -- what a tip whose state is N contributes (tip_column)
-  double* ones = reinterpret_cast<double*>(smem2) + (size_t)(kFused ? R : 1) * T * 16;
-  const int ones_off = (int)(ones - tiptab);
-  if (kN && tid < 4) ones[tid] = 1.0;
-  const int4* __restrict__ tl = tabs + (size_t)sample * tabs_stride;
-  // the walk descriptors go to LDS behind the tip tables (one copy per workgroup) for the waves that run the C++ walk
-  WalkOp* desc = reinterpret_cast<WalkOp*>(reinterpret_cast<double*>(smem2) + (size_t)(kFused ? R : 1) * T * 16 + (kN ? 4 : 0));
-  // (the assembly walk fetches its descriptors from global memory with scalar loads: this copy also brings their
-  // lines into L2 before the walk asks for them -- without it every eighth op waited for HBM)
-  for (int i = tid; i < n_w; i += blockDim.x) desc[i] = wops[(size_t)sample * n_ops + i];
+  const int tid = threadIdx.x;
+  const int sample = blockIdx.z;
+  const ct_args_ptr a0 = ct_args();
+  const CtWave g = ct_wave<kFused>(tid, a0->wpr);
+  const int rate = g.rate, wave = g.wave, nthr = g.nthr, rtid = g.rtid;
+  {
+    const ct_args_ptr a = a0;
+    const int T = a->T, R = a->R;
+    const int n_w = ct_ro<int>(a->hdr)[(size_t)sample * 4];
+    if (kN && tid < 4) reinterpret_cast<double*>(smem2)[(kFused ? R : 1) * T * 16 + tid] = 1.0;  // `ones`, see below
+    const WalkOp* wops = a->wops + (size_t)sample * (T - 2);
+    // the walk descriptors go to LDS behind the tip tables (one copy per workgroup) for the waves that run the C++ walk
+    WalkOp* desc = reinterpret_cast<WalkOp*>(reinterpret_cast<double*>(smem2) + (size_t)(kFused ? R : 1) * T * 16 + (kN ? 4 : 0));
+    // (the assembly walk fetches its descriptors from global memory with scalar loads: this copy also brings their
+    // lines into L2 before the walk asks for them -- without it every eighth op waited for HBM)
+    // (scalar base + 32-bit byte offset: no 64-bit copy of the thread index)
+    for (int i = tid; i < n_w; i += ct_block_threads<kFused>(R, a->wpr))
+      desc[i] = *reinterpret_cast<const WalkOp*>(reinterpret_cast<const char*>(wops) + (unsigned)i * 8u);
+  }
 
   // Prologue, first half: the P-matrices of this (sample, rate), one thread per matrix (K0c left every matrix's
   // branch length in the order they are stored): the walk's inner-branch matrices to the scratch area, the tip
@@ -1183,17 +1254,23 @@ __device__ __forceinline__ void prune_body_ct(int n2, int tile, int R, int wpr, 
   // not through memory (tables beyond nthr / 4 take the path through the scratch area).  With N in the alignment a
   // table has a fifth row and column: the quad's lanes share the fifth row's entries (round 4; such tables all took
   // the scratch path before).
-  const int n_q = min(n_tab, nthr >> 2);
-  const bool pc_lane = (rtid & 3) == 0 && (rtid >> 2) < n_q;
   int4 tcell = make_int4(1, 1, 0, 0);
-  if ((rtid >> 2) < n_q) tcell = tl[rtid >> 2];  // the quad's table: requested now, used after the barrier
+  // the matrix of round 0, kept: on a quad's first lane the quad's cherry matrix (no other lane's copy is ever read)
   double pcq[16];
-#pragma unroll
-  for (int i = 0; i < 16; ++i) pcq[i] = 0.0;
   {
-    const double* __restrict__ e = eig + (size_t)sample * 36;
-    const double* __restrict__ bl = brlen + (size_t)sample * (2 * (size_t)T - 2);
-    const double* __restrict__ wl = wlen + (size_t)sample * n_ops;
+    const ct_args_ptr a = a0;
+    const int T = a->T, R = a->R, n_ops = T - 2;
+    const int n_mat = ct_ro<int>(a->hdr)[(size_t)sample * 4 + 1], n_tab = ct_ro<int>(a->hdr)[(size_t)sample * 4 + 2];
+    const size_t rate_stride = a->rate_stride;
+    const int n_q = min(n_tab, nthr >> 2);
+    const bool in_quad = (rtid >> 2) < n_q;
+    const bool pc_lane = (rtid & 3) == 0 && in_quad;
+    if (in_quad) tcell = (a->tabs + (size_t)sample * a->tabs_stride)[rtid >> 2];  // the quad's table: requested now, used after the barrier
+    const double* bl = a->brlen + (size_t)sample * (2 * (size_t)T - 2);
+    const double* wl = a->wlen + (size_t)sample * n_ops;
+    // the sample's scratch regions, addressed as scalar base + 32-bit byte offset (R regions of a few hundred KB)
+    char* pw_s = reinterpret_cast<char*>(a->pmat_w + (size_t)sample * R * rate_stride);
+    const unsigned rate_bytes = (unsigned)rate_stride * 8u;
     // One matrix per thread and round.  Round 0: a quad's first lane takes its cherry matrix, every other thread the
     // item of its rank in the common list of its rate (walk matrices | cherry matrices n_q.. (scratch path) | tips).
     // The rest of the lists -- with all rates in one workgroup -- is POOLED over the workgroup's threads (round 4: 71
@@ -1201,32 +1278,34 @@ __device__ __forceinline__ void prune_body_ct(int n2, int tile, int R, int wpr, 
     // five of the eight waves busy and three skip the round).  The pooled part runs FIRST: the quads' matrices (sixteen
     // registers each) are then not live across another compute_pmatrix.
     const int n_rest = n_tab - n_q;
-    const int n_list = n_mat + n_rest + T;
+    const int n_in = n_mat + n_rest;  // matrices that go to the scratch area
+    const int n_list = n_in + T;
     const int round1 = nthr - n_q;  // list items of a rate taken in round 0
-    auto item = [&](bool is_pc, int it, int rr, int quad) {
-      double P[4][4];
-      const bool in_list = !is_pc && it < n_list;
-      const bool inner = in_list && it < n_mat + n_rest;
+    // listed: `it` is known to be an item of the list (the pooled round); otherwise it is tested, and a quad's first
+    // lane (is_pc) takes table `quad`'s matrix instead
+    auto item = [&](bool listed, bool is_pc, int it, int rr, int quad, double (&P)[4][4]) {
+      const bool in_list = listed || (!is_pc && it < n_list);
+      const bool inner = in_list && it < n_in;
       const int slot = it < n_mat ? it : it + n_q;  // matrix slot in the scratch area ([n_mat + c] for table c)
-      const int j = it - (n_mat + n_rest);          // tip
+      const int j = it - n_in;                      // tip
       double t = 0.0;
-      if (is_pc) t = wl[n_mat + quad];
-      else if (inner) t = wl[slot];
+      if (is_pc || inner) t = wl[is_pc ? n_mat + quad : slot];
       else if (in_list) t = bl[j];
-      compute_pmatrix(e, t * rates[(size_t)sample * R + rr], P);
-      if (is_pc) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-          for (int q = 0; q < 4; ++q) pcq[i * 4 + q] = P[i][q];
-      } else if (inner) {
-        double* o = pmat_w + ((size_t)sample * R + rr) * rate_stride + (size_t)slot * 16;
+      // The eigen-system's 28 doubles are scalar operands of compute_pmatrix.  Their loads are issued per item, behind
+      // a statement the compiler cannot move them across: they hit the scalar cache and cost no vector issue, and 56
+      // scalar registers are not pinned across the pooled loop and round 0.
+      uint64_t ev = reinterpret_cast<uint64_t>(a->eig + (size_t)sample * 36);
+      asm volatile("; lh: eigen-system at %0" : "+s"(ev));
+      const double* e = (const double*)(const double __attribute__((address_space(4)))*)ev;
+      compute_pmatrix(e, t * ct_ro<double>(a->rates)[(size_t)sample * R + rr], P);
+      if (inner) {
+        double* o = reinterpret_cast<double*>(pw_s + ((unsigned)rr * rate_bytes + (unsigned)slot * 128u));
 #pragma unroll
         for (int i = 0; i < 4; ++i)
 #pragma unroll
           for (int q = 0; q < 4; ++q) o[i * 4 + q] = P[i][q];
       } else if (in_list) {
-        double* o = reinterpret_cast<double*>(smem2) + (kFused ? (size_t)rr * T * 16 : 0) + j * 16;
+        double* o = reinterpret_cast<double*>(smem2) + (kFused ? rr * T * 16 : 0) + j * 16;
 #pragma unroll
         for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -1235,30 +1314,63 @@ __device__ __forceinline__ void prune_body_ct(int n2, int tile, int R, int wpr, 
     };
     const int rem = n_list - round1;  // items of a rate beyond round 0
     if (rem > 0) {
+      double P[4][4];
       if constexpr (kFused) {
-        const float inv_rem = 1.0f / (float)rem;
-        for (int c = tid; c < R * rem; c += blockDim.x) {
-          int rr = min((int)(((float)c + 0.5f) * inv_rem), R - 1);  // c / rem
-          rr -= rr * rem > c ? 1 : 0;
-          rr += (rr + 1) * rem <= c ? 1 : 0;
-          item(false, round1 + c - rr * rem, rr, 0);
+        // c / rem through the float reciprocal, exact here: the quotient is below R, (c + 0.5) / rem is at least 0.5 / rem
+        // away from an integer, and the reciprocal's and the product's rounding move it by less than R * 2^-22 -- enough
+        // for R * rem < 2^21; a fused workgroup's tip tables fit 80 KB of LDS, which holds R * rem below 2000
+        // (kCtFusedMaxLds and its static_assert: the launcher's limit and this bound are tied together there).
+        const float inv_rem = __builtin_amdgcn_rcpf((float)rem);
+        for (int c = tid; c < R * rem; c += ct_block_threads<kFused>(R, a->wpr)) {
+          const int rr = (int)(((float)c + 0.5f) * inv_rem);
+          item(true, false, round1 + c - rr * rem, rr, 0, P);
         }
       } else {
-        for (int it = round1 + rtid; it < n_list; it += nthr) item(false, it, rate, 0);
+        for (int it = round1 + rtid; it < n_list; it += nthr) item(true, false, it, rate, 0, P);
       }
     }
-    item(pc_lane, rtid - min(n_q, (rtid + 3) >> 2), rate, rtid >> 2);
+    double P[4][4];
+    item(false, pc_lane, rtid - min(n_q, (rtid + 3) >> 2), rate, rtid >> 2, P);
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) pcq[i * 4 + q] = P[i][q];
+    // the tip tables are complete (LDS); the scratch-area stores need to have landed only if a table goes that way
+    if (n_tab > n_q) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   }
-  // the tip tables are complete (LDS); the scratch-area stores need to have landed only if a table goes that way
-  if (n_tab > n_q) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+  // Second phase: its own reading of the arguments
+  const ct_args_ptr a = ct_args_again(a0);
+  // (the thread index likewise: a value of its own per phase.  One value from the kernel's entry to its end was kept in
+  // scratch memory for all of it, because the walk statement leaves five vector registers.)
+  int tid2 = tid;
+  asm volatile("" : "+v"(tid2));
+  const int rtid2 = kFused ? tid2 - rate * nthr : tid2;
+  const int T = a->T, R = a->R;
+  const int n_w = ct_ro<int>(a->hdr)[(size_t)sample * 4];
+  const int n_mat = ct_ro<int>(a->hdr)[(size_t)sample * 4 + 1], n_tab = ct_ro<int>(a->hdr)[(size_t)sample * 4 + 2];
+  const int n_q = min(n_tab, nthr >> 2);
+  const bool in_quad = (rtid2 >> 2) < n_q;
+  double* pw = a->pmat_w + ((size_t)sample * R + rate) * a->rate_stride;
+  double* ctab = pw + (size_t)(T - 3 > 0 ? T - 3 : 0) * 16;
+  double* tiptab = reinterpret_cast<double*>(smem2) + (kFused ? (size_t)rate * T * 16 : 0);  // LDS tip table [T][4][4]
+  // kN: four ones behind the table(s) -- what a tip whose state is N contributes (tip_column)
+  double* ones = reinterpret_cast<double*>(smem2) + (size_t)(kFused ? R : 1) * T * 16;
+  const int ones_off = (int)(ones - tiptab);
+  const int4* tl = a->tabs + (size_t)sample * a->tabs_stride;
+  const WalkOp* wops = a->wops + (size_t)sample * (T - 2);
+  const WalkOp* desc = reinterpret_cast<const WalkOp*>(ones + (kN ? 4 : 0));
   // Second half: the cherry tables, one thread per (table, state of the first tip): P_c (tipcol_y o tipcol_z) for
   // every state of the second tip -- the very operations the unfused walk performs per lane, done once per state pair.
-  auto build_rows = [&](const double (&pc)[16], int c, int sy, int ty, int tz) {
+  // (kRolled: the states of the second tip one after the other.  The loop over the tables beyond the quads holds its
+  // matrix in 32 registers; unrolled, the scheduler overlapped the states' LDS reads and the loop spilled to scratch.)
+  auto build_rows = [&](auto rolled, const double (&pc)[16], int c, int sy, int ty, int tz) {
+    constexpr int kUnroll = decltype(rolled)::value ? 1 : SY;
     double py[4];
     tip_column<kN>(tiptab, ty, sy, py, ones_off);
-    double2* o = reinterpret_cast<double2*>(ctab) + ((size_t)c * E + (size_t)sy * SY) * 2;
-#pragma unroll
+    // (scalar base + 32-bit byte offset, here and below: a 64-bit address per lane costs two registers the loop lacks)
+    double2* o = reinterpret_cast<double2*>(reinterpret_cast<char*>(ctab) + ((unsigned)c * E + (unsigned)sy * SY) * 32u);
+#pragma unroll kUnroll
     for (int sz = 0; sz < SY; ++sz) {
       double pz[4], pr[4], x[4];
       tip_column<kN>(tiptab, tz, sz, pz, ones_off);
@@ -1269,8 +1381,9 @@ __device__ __forceinline__ void prune_body_ct(int n2, int tile, int R, int wpr, 
       o[2 * sz + 1] = make_double2(x[2], x[3]);
     }
   };
-  {
-    // every lane of the wave takes part in the DPP moves (quad_perm [0,0,0,0]: the quad's first lane to all four)
+  // A wave's quads are its first ones (rtid2 >> 2 < n_q): a wave whose first quad has no table has none and skips the DPP
+  // moves; in the others every lane takes part in them (quad_perm [0,0,0,0]: the quad's first lane to all four).
+  if (wave * 16 < n_q) {
     double pc[16];
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
@@ -1278,13 +1391,13 @@ __device__ __forceinline__ void prune_body_ct(int n2, int tile, int R, int wpr, 
       const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(pcq[i]), 0, 0xf, 0xf, true);
       pc[i] = __hiloint2double(hi, lo);
     }
-    if ((rtid >> 2) < n_q) {
-      build_rows(pc, rtid >> 2, rtid & 3, tcell.x, tcell.y);
+    if (in_quad) {
+      build_rows(std::false_type(), pc, rtid2 >> 2, rtid2 & 3, tcell.x, tcell.y);
       if constexpr (kN) {
         // the fifth row (first tip N: a vector of ones): its entries go to the quad's four lanes one each, the corner to
         // the last lane -- the very operations build_rows performs for sy = 4
-        const int sz = rtid & 3;
-        double2* o = reinterpret_cast<double2*>(ctab) + ((size_t)(rtid >> 2) * E + 4 * SY) * 2;
+        const int sz = rtid2 & 3;
+        double2* o = reinterpret_cast<double2*>(reinterpret_cast<char*>(ctab) + ((unsigned)(rtid2 >> 2) * E + 4 * SY) * 32u);
         for (int k = sz; k < SY; k += 4) {
           double pz[4], pr[4], x[4];
           tip_column<kN>(tiptab, tcell.y, k, pz, ones_off);
@@ -1297,134 +1410,161 @@ __device__ __forceinline__ void prune_body_ct(int n2, int tile, int R, int wpr, 
       }
     }
   }
-  for (int it = rtid; it < (n_tab - n_q) * SY; it += nthr) {
+  for (int it = rtid2; it < (n_tab - n_q) * SY; it += nthr) {
     const int c = n_q + it / SY, sy = it - (it / SY) * SY;
     const int4 t = tl[c];
     double pc[16];
-    const double2* q = reinterpret_cast<const double2*>(pw + (size_t)(n_mat + c) * 16);
+    const double2* q = reinterpret_cast<const double2*>(reinterpret_cast<const char*>(pw) + (unsigned)(n_mat + c) * 128u);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const double2 v = q[j];
       pc[2 * j] = v.x;
       pc[2 * j + 1] = v.y;
     }
-    build_rows(pc, c, sy, t.x, t.y);
+    build_rows(std::true_type(), pc, c, sy, t.x, t.y);
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __threadfence_block();
   __syncthreads();
 
-  const pmat_ptr pm = pmat_after_barrier(pw);
-  const int lane = tid & 63;
-  const int tile0 = blockIdx.x * tile;
-  const int site_end = min(tile0 + tile, L);
-  const double* __restrict__ p4 = pi + (size_t)sample * 4;
-  // n2 waves carry kS sites per lane (64 apart), the others one site per lane
+  // The walk.  n2 waves carry kS sites per lane (64 apart), the others one site per lane.
   double lik[kS][5];
   int scl[kS];
 #pragma unroll
   for (int s = 0; s < kS; ++s) scl[s] = 0;
-  int site0, n_own;
-  const bool two_sites = wave < n2;
-  if (two_sites) {
-    site0 = tile0 + wave * (64 * kS) + lane;
-    n_own = kS;
-    if constexpr (kAsm)
-      prune_wave_asm<kDepth, kN, kS>((tile0 + wave * (64 * kS)) >> 7, planes, (L + 127) >> 7, n_w, wops + (size_t)sample * n_ops, pm,
-                                     (unsigned)((T - 3 > 0 ? T - 3 : 0) * 128), tiptab, naive_tab, ones, p4, lik, scl);
-    else
-      prune_wave_ct<kDepth, kS, kN>(site0, site_end, msa, L, n_w, desc, pm, tiptab, ctab, naive_tab, ones_off, p4, lik, scl);
-  } else {
-    site0 = tile0 + n2 * (64 * kS) + (wave - n2) * 64 + lane;
-    n_own = 1;
-    double lik1[1][5];
-    int scl1[1];
-    if constexpr (kAsm)
-      prune_wave_asm<kDepth, kN, 1>((tile0 + n2 * (64 * kS)) >> 7, planes, (L + 127) >> 7, n_w,   // (at most one such wave)
-                                    wops + (size_t)sample * n_ops, pm, (unsigned)((T - 3 > 0 ? T - 3 : 0) * 128), tiptab, naive_tab,
-                                    ones, p4, lik1, scl1);
-    else
-      prune_wave_ct<kDepth, 1, kN>(site0, site_end, msa, L, n_w, desc, pm, tiptab, ctab, naive_tab, ones_off, p4, lik1, scl1);
+  double root[kS][4];  // the assembly walk's results: the root's vector and the scaler counts
+  int root_scal[kS];
+  // the thread index that crosses the walk statement: a copy made by an instruction, or the register allocator joins it
+  // to the 64-bit indices formed from it before and after, and spills the pair
+  int tid_w = tid2;
+  if constexpr (kAsm) asm volatile("v_mov_b32 %0, %1" : "=v"(tid_w) : "v"(tid2));
+  {
+    const pmat_ptr pm = pmat_after_barrier(pw);
+    const int L = a->L, n2 = a->n2;
+    const int tile0 = blockIdx.x * a->tile;
+    if (wave < n2) {
+      if constexpr (kAsm)
+        prune_wave_asm<kDepth, kN, kS>((tile0 + wave * (64 * kS)) >> 7, a->planes, (L + 127) >> 7, n_w, wops, pm,
+                                       (unsigned)((T - 3 > 0 ? T - 3 : 0) * 128), tiptab, ones, root, root_scal);
+      else
+        prune_wave_ct<kDepth, kS, kN>(tile0 + wave * (64 * kS) + (tid2 & 63), min(tile0 + a->tile, L), a->msa, L, n_w, desc, pm,
+                                      tiptab, ctab, tiptab, ones_off, (const double*)(ct_ro<double>(a->pi) + (size_t)sample * 4), lik, scl);
+    } else {
+      double lik1[1][5], root1[1][4];
+      int scl1[1], root_scal1[1];
+      if constexpr (kAsm) {
+        prune_wave_asm<kDepth, kN, 1>((tile0 + n2 * (64 * kS)) >> 7, a->planes, (L + 127) >> 7, n_w, wops, pm,  // (at most one such wave)
+                                      (unsigned)((T - 3 > 0 ? T - 3 : 0) * 128), tiptab, ones, root1, root_scal1);
 #pragma unroll
-    for (int b = 0; b < 5; ++b) lik[0][b] = lik1[0][b];
-    scl[0] = scl1[0];
+        for (int i = 0; i < 4; ++i) root[0][i] = root1[0][i];
+        root_scal[0] = root_scal1[0];
+      } else {
+        prune_wave_ct<kDepth, 1, kN>(tile0 + n2 * (64 * kS) + (wave - n2) * 64 + (tid2 & 63), min(tile0 + a->tile, L), a->msa, L, n_w,
+                                     desc, pm, tiptab, ctab, tiptab, ones_off, (const double*)(ct_ro<double>(a->pi) + (size_t)sample * 4), lik1, scl1);
+#pragma unroll
+        for (int b = 0; b < 5; ++b) lik[0][b] = lik1[0][b];
+        scl[0] = scl1[0];
+      }
+    }
   }
-  if (malformed) {  // K0c rejected the schedule: no number may look like a result
+
+  // After the walk: its statement clobbers all but a dozen scalar registers, so this phase reads the arguments and
+  // derives the wave's geometry again (scalar loads and scalar arithmetic) instead of carrying them through vector lanes.
+  const ct_args_ptr b = ct_args_again(a);
+  int tid_b = tid_w;
+  if constexpr (kAsm) asm volatile("v_mov_b32 %0, %1" : "=v"(tid_b) : "v"(tid_w));
+  const CtWave gb = ct_wave<kFused>(tid_b, b->wpr);
+  const int rate_b = gb.rate, wave_b = gb.wave;
+  const int R_b = b->R, L_b = b->L, n2_b = b->n2;
+  const int lane = tid_b & 63;
+  const int tile0 = blockIdx.x * b->tile;
+  const int site_end = min(tile0 + b->tile, L_b);
+  const bool two_sites = wave_b < n2_b;
+  const int site0 = two_sites ? tile0 + wave_b * (64 * kS) + lane : tile0 + n2_b * (64 * kS) + (wave_b - n2_b) * 64 + lane;
+  const int n_own = two_sites ? kS : 1;
+  if constexpr (kAsm) {
+    const double* naive_tab = reinterpret_cast<const double*>(smem2) + (kFused ? (size_t)rate_b * b->T * 16 : 0);
+    const double* p4 = (const double*)(ct_ro<double>(b->pi) + (size_t)sample * 4);
+    if (two_sites) {
+      close_naive_branch<kS>(root, root_scal, naive_tab, p4, lik, scl);
+    } else {
+      double lik1[1][5], root1[1][4];
+      int scl1[1], root_scal1[1];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) root1[0][i] = root[0][i];
+      root_scal1[0] = root_scal[0];
+      close_naive_branch<1>(root1, root_scal1, naive_tab, p4, lik1, scl1);
+#pragma unroll
+      for (int q = 0; q < 5; ++q) lik[0][q] = lik1[0][q];
+      scl[0] = scl1[0];
+    }
+  }
+  if (ct_ro<ct_int4>(b->hdr)[sample].w != 0) {  // K0c rejected the schedule: no number may look like a result
 #pragma unroll
     for (int s = 0; s < kS; ++s)
 #pragma unroll
-      for (int b = 0; b < 5; ++b) lik[s][b] = __builtin_nan("");
+      for (int q = 0; q < 5; ++q) lik[s][q] = __builtin_nan("");
   }
 
   if constexpr (!kFused) {
-    double* lik_out = site_lik + (((size_t)sample * R + rate) * 5) * (size_t)L;
-    int32_t* scal_out = site_scal + ((size_t)sample * R + rate) * (size_t)L;
+    double* lik_out = b->site_lik + (((size_t)sample * R_b + rate_b) * 5) * (size_t)L_b;
+    int32_t* scal_out = b->site_scal + ((size_t)sample * R_b + rate_b) * (size_t)L_b;
 #pragma unroll
     for (int s = 0; s < kS; ++s) {
       const int site = site0 + 64 * s;
       if (s < n_own && site < site_end) {
 #pragma unroll
-        for (int b = 0; b < 5; ++b) lik_out[(size_t)b * L + site] = lik[s][b];
+        for (int q = 0; q < 5; ++q) lik_out[(size_t)q * L_b + site] = lik[s][q];
         scal_out[site] = scl[s];
       }
     }
   } else {
     // exchange through LDS (over the tip tables, which no wave needs any more), then mix the rates (as prune_body)
-    const int pad = n2 * (64 * kS) + (wpr - n2) * 64;
+    const int pad = n2_b * (64 * kS) + (b->wpr - n2_b) * 64;
     __syncthreads();
     double* X = reinterpret_cast<double*>(smem2);
-    int* SC = reinterpret_cast<int*>(X + (size_t)R * 5 * pad);
+    int* SC = reinterpret_cast<int*>(X + (size_t)R_b * 5 * pad);
 #pragma unroll
     for (int s = 0; s < kS; ++s) {
       const int idx = site0 + 64 * s - tile0;
       if (s < n_own && idx < pad) {
 #pragma unroll
-        for (int b = 0; b < 5; ++b) X[((size_t)rate * 5 + b) * pad + idx] = lik[s][b];
-        SC[rate * pad + idx] = scl[s];
+        for (int q = 0; q < 5; ++q) X[((size_t)rate_b * 5 + q) * pad + idx] = lik[s][q];
+        SC[rate_b * pad + idx] = scl[s];
       }
     }
     __syncthreads();
     const int n_tile = site_end - tile0;
-    const double w = 1.0 / R;
-    double* lik_out = site_lik + ((size_t)sample * 5) * (size_t)L;
-    int32_t* scal_out = site_scal + (size_t)sample * (size_t)L;
+    const double w = 1.0 / R_b;
+    double* lik_out = b->site_lik + ((size_t)sample * 5) * (size_t)L_b;
+    int32_t* scal_out = b->site_scal + (size_t)sample * (size_t)L_b;
     // a thread per pattern, its five naive states together (round 4: a thread per (state, pattern) cost an integer division
     // by the tile size per item and read the R scaler counts five times over -- ~250 vector instructions per wave against ~40)
-    for (int p = tid; p < n_tile; p += blockDim.x) {
+    for (int p = tid_b; p < n_tile; p += ct_block_threads<kFused>(R_b, b->wpr)) {
       int smin = 0x7fffffff;
-      for (int r = 0; r < R; ++r) smin = min(smin, SC[r * pad + p]);
+      for (int r = 0; r < R_b; ++r) smin = min(smin, SC[r * pad + p]);
       double acc[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-      for (int r = 0; r < R; ++r) {
+      for (int r = 0; r < R_b; ++r) {
         const int d = SC[r * pad + p] - smin;
 #pragma unroll
-        for (int b = 0; b < 5; ++b) {
-          double v = X[((size_t)r * 5 + b) * pad + p];
-          for (int q = 0; q < d && v != 0.0; ++q) v *= kScaleThreshold;
-          acc[b] += w * v;
+        for (int q = 0; q < 5; ++q) {
+          double v = X[((size_t)r * 5 + q) * pad + p];
+          for (int k = 0; k < d && v != 0.0; ++k) v *= kScaleThreshold;
+          acc[q] += w * v;
         }
       }
 #pragma unroll
-      for (int b = 0; b < 5; ++b) lik_out[(size_t)b * L + tile0 + p] = acc[b];
+      for (int q = 0; q < 5; ++q) lik_out[(size_t)q * L_b + tile0 + p] = acc[q];
       scal_out[tile0 + p] = smin;
     }
   }
 }
 
-#define LH_PRUNE_CT_PARAMS                                                                                          \
-  int n2, int tile, int R, int wpr, const uint8_t *__restrict__ msa, const uint64_t *__restrict__ planes, int L,    \
-      int T, const int2 *__restrict__ wops,                                                                         \
-      const double *__restrict__ wlen, const int4 *__restrict__ tabs, int tabs_stride,                              \
-      const int4 *__restrict__ hdr, const double *__restrict__ brlen, const double *__restrict__ rates,            \
-      const double *__restrict__ eig, double *pmat_w, size_t rate_stride, const double *__restrict__ pi,           \
-      double *__restrict__ site_lik, int32_t *__restrict__ site_scal
-#define LH_PRUNE_CT_ARGS \
-  n2, tile, R, wpr, msa, planes, L, T, wops, wlen, tabs, tabs_stride, hdr, brlen, rates, eig, pmat_w, rate_stride, pi, site_lik, \
-      site_scal
 #define LH_PRUNE_CT_KERNEL(NAME, WAVES)                                                              \
   template <int kDepth, bool kN, bool kFused, bool kAsm>                                             \
   __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES))) NAME(   \
-      LH_PRUNE_CT_PARAMS) {                                                                          \
-    prune_body_ct<kDepth, kN, kFused, kAsm>(LH_PRUNE_CT_ARGS);                                       \
+      const PruneCtArgs args /* read through ct_args() */) {                                         \
+    prune_body_ct<kDepth, kN, kFused, kAsm>();                                                       \
   }
 LH_PRUNE_CT_KERNEL(prune_kernel_ct6, 6)
 LH_PRUNE_CT_KERNEL(prune_kernel_ct5, 5)
@@ -1535,7 +1675,8 @@ int launch_prune(const DevFamily& fam, int n, int R, int T, int max_depth, const
   //     registers, deeper ones in scratch memory: any depth up to 16; the walk in assembly) for everything else.
   const bool fused = allow_fused && !dbg.k1_no_fuse && !dbg.k1_segments &&
                      ((R * wpr <= 8 && fused_lds <= 53 * 1024) ||    // three workgroups of up to eight waves per CU
-                      (R * wpr > 8 && R * wpr <= 16 && fused_lds <= 80 * 1024));     // two of nine to sixteen
+                      (R * wpr > 8 && R * wpr <= kCtFusedMaxWaves && fused_lds <= kCtFusedMaxLds));     // two of nine to sixteen
+  // (both limits are relied on inside the cherry-table kernels: see kCtFusedMaxWaves)
   const bool big = !fused && ((160 * 1024 / tip_bytes) * wpr / 4 < 5 || dbg.k1_segments);
   const bool tables_hook = dbg.k1_tables || dbg.k1_no_tables;
   const bool use_asm = !dbg.k1_cxx_walk;  // (both kinds of alignment: 2-bit state planes, or 2 bits + an N flag)
@@ -1584,11 +1725,16 @@ int launch_prune(const DevFamily& fam, int n, int R, int T, int max_depth, const
     if (lds > 64 * 1024)                                                                                         \
       attr_rc = hipFuncSetAttribute(reinterpret_cast<const void*>(K), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
     snprintf(g_prune_form, sizeof(g_prune_form), "%s", NAME);                                                    \
-    if (attr_rc == hipSuccess)                                                                                   \
-      hipLaunchKernelGGL(K, grid, block, lds, stream, n2, tile, R, wpr, fam.msa, fam.msa_planes, L, T, ws.wops, ws.wlen, ws.tabs, \
-                         (int)sizes.tabs_per_sample, ws.hdr, brlen, rates, eig, pmat, rate_stride, pi, site_lik, \
-                         site_scal);                                                                             \
+    if (attr_rc == hipSuccess) hipLaunchKernelGGL(K, grid, block, lds, stream, ct_args);                        \
   }
+  PruneCtArgs ct_args = {};
+  ct_args.n2 = n2, ct_args.tile = tile, ct_args.R = R, ct_args.wpr = wpr;
+  ct_args.L = L, ct_args.T = T, ct_args.tabs_stride = (int)sizes.tabs_per_sample;
+  ct_args.msa = fam.msa, ct_args.planes = fam.msa_planes;
+  ct_args.wops = ws.wops, ct_args.wlen = ws.wlen, ct_args.tabs = ws.tabs, ct_args.hdr = ws.hdr;
+  ct_args.brlen = brlen, ct_args.rates = rates, ct_args.eig = eig;
+  ct_args.pmat_w = pmat, ct_args.rate_stride = rate_stride;
+  ct_args.pi = pi, ct_args.site_lik = site_lik, ct_args.site_scal = site_scal;
   // waves per SIMD that the LDS of the resident workgroups allows (160 KB per CU, 4 SIMDs)
   const int lds_waves = lds == 0 ? 8 : (int)((160 * 1024 / lds) * wg_waves / 4);
   if (stack_fused) {
