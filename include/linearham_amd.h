@@ -355,7 +355,7 @@ int lh_collect_profile_read(lh_family* fam, double* ms, int64_t* n_launches);
  * The lineage of tree sample i is the chain of inner nodes from the seed tip's parent up to the tree's root (naive's
  * neighbour): path[i][0..P) in lh_schedule_tree numbering (T + k), padded with -1; P = the batch's longest chain.  Its
  * slots are s < P: row anc[i][path[i][s] - T][0..L) of the sampled states; s = P: the sample's naive sequence.  A flat
- * slot is i * (P + 1) + s.  Per slot the kernel writes a 64-bit hash of the bases and one of their translation
+ * slot is i * (P + 1) + s (with lh_eval_lineage_batch's draws: (i * draws + d) * (P + 1) + s).  Per slot the kernel writes a 64-bit hash of the bases and one of their translation
  * (standard code, frame 0, truncated to whole codons, stop = '*', a codon with N = the one symbol all its resolutions
  * give, else 'X').  Hash bits depend on the sequence alone -- a naive sequence gets lh_naive_sequences' hash -- and
  * LH_COLLECT_HASH_BITS masks them too.  Padding slots get LH_LINEAGE_PAD_HASH; a sample whose (device-resident)
@@ -393,6 +393,46 @@ int lh_lineage_store_read(lh_family* fam, int32_t first, int32_t count, int32_t*
 int lh_lineage_reset(lh_family* fam);
 /* Time of K7 over the lineage calls made while profiling was enabled (HIP events); resets the counters. */
 int lh_lineage_profile_read(lh_family* fam, double* ms, int64_t* n_launches);
+
+/* ---- the chain: evaluation, naive draw, ancestral draws and lineage hashes in one pass ----
+ * What lh_eval_batch (rates), lh_eval_draw_batch, lh_draws_rows_read and lh_lineage_batch give when composed, without the
+ * host round trips and with one pruning launch per group: K0a (rates kept on the device), K0c, K1 once with unmixed rate
+ * planes, K2 on those planes, K4 with `words`, K6c (naive bases and hash), K3 with `draws` ancestral draws per row reading
+ * K6c's bases and K0a's full-precision rates, K7.  Draw d of row i is virtual sample i * draws + d; its Philox sample
+ * number is first_sample + i + (d << 32), so draw 0 is lh_lineage_batch's draw (with draws > 1, first_sample + n must not
+ * exceed 2^32).  The flat lineage slot is ((i * draws) + d) * (P + 1) + s; slot s = P is the row's naive sequence, the same
+ * for every d, with lh_naive_sequences' hash.  The batch becomes the handle's last lineage batch (lh_lineage_resolve,
+ * _rows_read and _store_read work on its n * draws * (P + 1) slots) and its last draw batch.  Refused: what
+ * lh_lineage_batch and lh_eval_draw_batch refuse (the 1 GiB bound on resident sampled states applies to n * draws samples;
+ * the message names the largest n), and draws outside 1 .. 64.  A row whose log-likelihood is not finite has unspecified
+ * hashes (its naive bytes are still 0 .. 4); a row whose schedule is rejected has a NaN log-likelihood and all-ones hashes
+ * in all its draws.  Honours lh_family_set_extended_range. */
+typedef struct {
+  double* loglik;       /* [n]                       required */
+  double* rates;        /* [n][R]                    or NULL  */
+  int32_t* states;      /* [n][lh_sample_states()]   or NULL  */
+  uint8_t* naive;       /* [n][L]  A,C,G,T,N = 0..4  or NULL  */
+  uint64_t* naive_hash; /* [n]                       or NULL  */
+  uint64_t* nt_hash;    /* [n][draws][P+1]           required */
+  uint64_t* aa_hash;    /* [n][draws][P+1]           required */
+} lh_lineage_eval_outputs;
+
+int lh_eval_lineage_batch(lh_family* fam, int32_t n, int32_t n_tips, int32_t max_depth, const int32_t* ops,
+                          const double* brlen, const double* er, const double* pi, const double* alpha,
+                          int32_t num_rates, const uint32_t* words, uint64_t seed, uint64_t first_sample, int32_t draws,
+                          const int32_t* path, int32_t path_len, const lh_lineage_eval_outputs* outs);
+
+/* The same with every array (outs' members included) resident on the handle's device; enqueued on `hip_stream` without
+ * synchronising.  `path` must stay as it is while the batch is resolved. */
+int lh_eval_lineage_batch_device(lh_family* fam, int32_t n, int32_t n_tips, int32_t max_depth, const int32_t* ops,
+                                 const double* brlen, const double* er, const double* pi, const double* alpha,
+                                 int32_t num_rates, const uint32_t* words, uint64_t seed, uint64_t first_sample,
+                                 int32_t draws, const int32_t* path, int32_t path_len,
+                                 const lh_lineage_eval_outputs* outs, void* hip_stream);
+
+/* Times of the chain's stages over the lh_eval_lineage_batch[_device] calls made while profiling was enabled (HIP events):
+ * ms[5] = K0a, K0c + K1, K2 + K4 + K6c, K3, K7; resets the counters. */
+int lh_lineage_eval_profile_read(lh_family* fam, double* ms, int64_t* n_launches);
 
 /* Tree in rooted-at-naive form: tips are nodes 0..T-1 (0 = `naive`, i = MSA row i-1), inner nodes
  * T..2T-3.  children[2*(v-T)+{0,1}] are the two children of inner node v when the tree is rooted at

@@ -62,6 +62,9 @@ LINEAGE_EXPORTS = ["lh_lineage_batch", "lh_lineage_collect_device", "lh_lineage_
                    "lh_lineage_store_read", "lh_lineage_reset", "lh_lineage_profile_read"]
 EXPORTS += LINEAGE_EXPORTS
 LINEAGE_PAD_HASH = 0  # LH_LINEAGE_PAD_HASH
+# the chain: evaluation, naive draw, D ancestral draws and lineage hashes in one pass
+LINEAGE_EVAL_EXPORTS = ["lh_eval_lineage_batch", "lh_eval_lineage_batch_device", "lh_lineage_eval_profile_read"]
+EXPORTS += LINEAGE_EVAL_EXPORTS
 
 
 class _PosteriorOutputs(C.Structure):
@@ -72,6 +75,16 @@ class _PosteriorOutputs(C.Structure):
 class _CandidateOutputs(C.Structure):
     _fields_ = [("log_offset", c_f64p), ("loglik", c_f64p), ("log_cand", c_f64p), ("weighted_sum", c_f64p),
                 ("weight_stats", c_f64p)]
+
+
+class _LineageEvalOutputs(C.Structure):
+    _fields_ = [("loglik", c_f64p), ("rates", c_f64p), ("states", c_i32p), ("naive", c_u8p),
+                ("naive_hash", C.POINTER(C.c_uint64)), ("nt_hash", C.POINTER(C.c_uint64)),
+                ("aa_hash", C.POINTER(C.c_uint64))]
+
+
+class _LineageEvalOutputsDevice(C.Structure):  # the same members as device addresses
+    _fields_ = [(k, C.c_void_p) for k in ("loglik", "rates", "states", "naive", "naive_hash", "nt_hash", "aa_hash")]
 
 
 def library_path():
@@ -163,6 +176,15 @@ class HipLibrary:
             lib.lh_lineage_store_read.argtypes = [C.c_void_p, C.c_int32, C.c_int32, c_i32p, c_u8p]
             lib.lh_lineage_reset.argtypes = [C.c_void_p]
             lib.lh_lineage_profile_read.argtypes = [C.c_void_p, c_f64p, C.POINTER(C.c_int64)]
+        if hasattr(lib, "lh_eval_lineage_batch"):
+            lib.lh_eval_lineage_batch.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, c_i32p, c_f64p, c_f64p,
+                                                  c_f64p, c_f64p, C.c_int32, C.POINTER(C.c_uint32), C.c_uint64,
+                                                  C.c_uint64, C.c_int32, c_i32p, C.c_int32,
+                                                  C.POINTER(_LineageEvalOutputs)]
+            lib.lh_eval_lineage_batch_device.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + \
+                [C.c_void_p] * 5 + [C.c_int32, C.c_void_p, C.c_uint64, C.c_uint64, C.c_int32, C.c_void_p, C.c_int32,
+                                    C.POINTER(_LineageEvalOutputsDevice), C.c_void_p]
+            lib.lh_lineage_eval_profile_read.argtypes = [C.c_void_p, c_f64p, C.POINTER(C.c_int64)]
         if hasattr(lib, "lh_set_device"):      # (absent from round-2 builds loaded through LH_LIB_DIR for comparisons)
             lib.lh_set_device.argtypes = [C.c_int32]
             lib.lh_family_status.argtypes = [C.c_void_p]
@@ -471,9 +493,23 @@ class Family:
         self.n_xmsa = desc.n_xmsa
         self.consensus_sets = self.hip.lib.lh_family_consensus_sets(h)
 
+    @classmethod
+    def borrow(cls, handle, lib=None):
+        """A wrapper of a handle somebody else owns (host.PhyloHMM's family, which has the sampler tables): the same
+        methods, close() leaves the handle alone."""
+        self = cls.__new__(cls)
+        self.hip = lib or load_library()
+        self.desc = None
+        self.handle = C.c_void_p(handle) if isinstance(handle, int) else handle
+        self.owned = False
+        self.forward_size = self.hip.lib.lh_forward_size(self.handle)
+        self.scaler_size = self.hip.lib.lh_scaler_size(self.handle)
+        return self
+
     def close(self):
         if self.handle:
-            self.hip.lib.lh_family_destroy(self.handle)
+            if getattr(self, "owned", True):
+                self.hip.lib.lh_family_destroy(self.handle)
             self.handle = None
 
     def __del__(self):
@@ -579,6 +615,50 @@ class Family:
             aa.ctypes.data_as(u64)))
         self._lineage_sites = L
         return nt, aa
+
+    def eval_lineage_batch(self, n_tips, max_depth, ops, brlen, er, pi, alpha, num_rates, words, seed, path, draws=1,
+                           first_sample=0):
+        """lh_eval_lineage_batch (the chain K0-K2, K4, K6c, K3 with `draws` ancestral draws per row, K7): a dict of
+        loglik [n], rates [n][R], states [n][S], naive [n][L] uint8, naive_hash [n], nt_hash and aa_hash [n][draws][P+1]
+        uint64.  The batch becomes the handle's last lineage batch: flat slot ((i * draws) + d) * (P + 1) + s."""
+        ops, brlen, er, pi, alpha = _i32(ops), _f64(brlen), _f64(er), _f64(pi), _f64(alpha)
+        words = np.ascontiguousarray(words, dtype=np.uint32)
+        path = _i32(path)
+        n = ops.shape[0]
+        assert ops.shape == (n, n_tips - 2, 4) and brlen.shape == (n, 2 * n_tips - 2)
+        assert er.shape == (n, 6) and pi.shape == (n, 4) and alpha.shape == (n,) and path.shape[0] == n
+        P = path.shape[1]
+        lib = self.hip.lib
+        _, L = self.hip.candidates_info(self.handle)
+        d = max(int(draws), 0)
+        res = {"loglik": np.zeros(n), "rates": np.zeros((n, num_rates)),
+               "states": np.zeros((n, lib.lh_sample_states(self.handle)), dtype=np.int32),
+               "naive": np.zeros((n, L), dtype=np.uint8), "naive_hash": np.zeros(n, dtype=np.uint64),
+               "nt_hash": np.zeros((n, d, P + 1), dtype=np.uint64), "aa_hash": np.zeros((n, d, P + 1), dtype=np.uint64)}
+        outs = _LineageEvalOutputs(*[res[k].ctypes.data_as(t) for k, t in _LineageEvalOutputs._fields_])
+        self.hip.check(lib.lh_eval_lineage_batch(
+            self.handle, n, n_tips, max_depth, ops.ctypes.data_as(c_i32p), brlen.ctypes.data_as(c_f64p),
+            er.ctypes.data_as(c_f64p), pi.ctypes.data_as(c_f64p), alpha.ctypes.data_as(c_f64p), num_rates,
+            words.ctypes.data_as(C.POINTER(C.c_uint32)), seed, first_sample, draws, path.ctypes.data_as(c_i32p), P,
+            C.byref(outs)))
+        self._lineage_sites = L
+        return res
+
+    def eval_lineage_batch_device(self, n, n_tips, max_depth, ops_ptr, brlen_ptr, er_ptr, pi_ptr, alpha_ptr, num_rates,
+                                  words_ptr, seed, first_sample, draws, path_ptr, path_len, outs, stream=0):
+        """lh_eval_lineage_batch_device on device addresses; outs: dict of the output members' addresses (loglik,
+        nt_hash, aa_hash required)."""
+        o = _LineageEvalOutputsDevice(**{k: int(v) for k, v in outs.items() if v})
+        self.hip.check(self.hip.lib.lh_eval_lineage_batch_device(
+            self.handle, n, n_tips, max_depth, ops_ptr, brlen_ptr, er_ptr, pi_ptr, alpha_ptr, num_rates, words_ptr, seed,
+            first_sample, draws, path_ptr, path_len, C.byref(o), stream))
+        _, self._lineage_sites = self.hip.candidates_info(self.handle)
+
+    def lineage_eval_profile_read(self):
+        """({k0_ms, k1_ms, k2_k4_k6c_ms, k3_ms, k7_ms}, launch groups) of the chain since the last read."""
+        ms, k = (C.c_double * 5)(), C.c_int64()
+        self.hip.check(self.hip.lib.lh_lineage_eval_profile_read(self.handle, ms, C.byref(k)))
+        return dict(zip(("k0_ms", "k1_ms", "k2_k4_k6c_ms", "k3_ms", "k7_ms"), list(ms))), k.value
 
     def lineage_collect_device(self, n, n_tips, anc_ptr, naive_ptr, path_ptr, path_len, nt_hash_ptr, aa_hash_ptr,
                                stream=0):

@@ -1,6 +1,9 @@
 #include "Lineage.hpp"
 
 #include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
 #include <fstream>
 #include <numeric>
 #include <stdexcept>
@@ -14,19 +17,30 @@ namespace {
 // str(float(count) / denominator), remembered: a table has few distinct counts and ReprDouble searches for its digits
 class Fractions {
  public:
-  const std::string& operator()(int64_t count, int64_t denominator) {
+  const std::string& operator()(double count, double denominator) {
     const auto r = text_.emplace(std::make_pair(count, denominator), std::string());
-    if (r.second) r.first->second = ReprDouble((double)count / (double)denominator);
+    if (r.second) r.first->second = ReprDouble(count / denominator);
     return r.first->second;
   }
 
  private:
-  std::map<std::pair<int64_t, int64_t>, std::string> text_;
+  std::map<std::pair<double, double>, std::string> text_;
 };
+
+// a count: the integer it is when no tree had a weight of its own, else str(float)
+std::string CountText(const LineageTables& t, double count) {
+  return t.weighted ? ReprDouble(count) : std::to_string((int64_t)count);
+}
+
+std::string G17(double v) {
+  char b[40];
+  std::snprintf(b, sizeof b, "%.17g", v);
+  return b;
+}
 
 }  // namespace
 
-void LineageTabulator::Counted::Add(int key) {
+void LineageTabulator::Counted::Add(int key, double weight) {
   int pos = -1;
   if (keys.size() <= kLinear) {  // most counters hold a key or two: no index until there are many
     for (std::size_t k = 0; k < keys.size() && pos < 0; ++k)
@@ -43,7 +57,7 @@ void LineageTabulator::Counted::Add(int key) {
     counts.push_back(0);
     if (!at.empty()) at.emplace(key, pos);
   }
-  ++counts[pos];
+  counts[pos] += weight;
 }
 
 std::vector<int> LineageTabulator::Counted::MostCommon() const {
@@ -65,17 +79,20 @@ int LineageTabulator::AddSequence(const std::string& nt) {
   return r.first->second;
 }
 
-void LineageTabulator::AddTree(const std::vector<std::string>& seqs, int path_len) {
+void LineageTabulator::AddTree(const std::vector<std::string>& seqs, int path_len, double weight) {
   std::vector<int> ids;
   for (const std::string& s : seqs) ids.push_back(AddSequence(s));
-  AddTree(ids, path_len);
+  AddTree(ids, path_len, weight);
 }
 
-void LineageTabulator::AddTree(const std::vector<int>& ids, int path_len) {
+void LineageTabulator::AddTree(const std::vector<int>& ids, int path_len, double weight) {
   if (ids.size() < 2) throw std::runtime_error("lineage: a tree's lineage holds at least naive and the seed");
   for (int id : ids)
     if (id < 0 || id >= (int)nt_.size()) throw std::runtime_error("lineage: unknown sequence id");
+  if (!(weight > 0.0) || !std::isfinite(weight)) throw std::runtime_error("lineage: a tree's weight must be positive and finite");
   ++num_trees_;
+  total_ += weight;
+  if (weight != 1.0) weighted_ = true;
   longest_path_ = std::max<int64_t>(longest_path_, path_len);
   std::vector<int> l;
   for (int id : ids) l.push_back(aa_of_nt_[id]);
@@ -86,12 +103,12 @@ void LineageTabulator::AddTree(const std::vector<int>& ids, int path_len) {
     if (node_dt_.size() < aa_.size()) node_dt_.resize(aa_.size());
     Counted& c = node_dt_[l[lo]];
     for (std::size_t k = lo; k < hi; ++k)
-      if (std::find(ids.begin() + lo, ids.begin() + k, ids[k]) == ids.begin() + k) c.Add(ids[k]);
+      if (std::find(ids.begin() + lo, ids.begin() + k, ids[k]) == ids.begin() + k) c.Add(ids[k], weight);
     lo = hi;
   }
   // node_c: frozenset(l)
   for (std::size_t k = 0; k < l.size(); ++k)
-    if (std::find(l.begin(), l.begin() + k, l[k]) == l.begin() + k) node_c_.Add(l[k]);
+    if (std::find(l.begin(), l.begin() + k, l[k]) == l.begin() + k) node_c_.Add(l[k], weight);
   // edge_c: zip(l[:-1], l[1:]) without the pairs the script never shows
   for (std::size_t k = 0; k + 1 < l.size(); ++k) {
     if (l[k] == l[k + 1]) continue;
@@ -101,9 +118,9 @@ void LineageTabulator::AddTree(const std::vector<int>& ids, int path_len) {
       edge_keys_.push_back(e);
       edge_counts_.push_back(0);
     }
-    ++edge_counts_[r.first->second];
+    edge_counts_[r.first->second] += weight;
   }
-  naive_c_.Add(l.front());
+  naive_c_.Add(l.front(), weight);
   if (std::find(seed_aa_.begin(), seed_aa_.end(), l.back()) == seed_aa_.end()) seed_aa_.push_back(l.back());
 }
 
@@ -114,6 +131,8 @@ LineageTables LineageTabulator::Finish(const std::string& seed_name) const {
                              " different translations over the trees");
   LineageTables t;
   t.num_trees = num_trees_;
+  t.total = total_;
+  t.weighted = weighted_;
   t.distinct_nt = (int64_t)nt_.size();
   t.distinct_aa = (int64_t)aa_.size();
   t.longest_path = longest_path_;
@@ -123,7 +142,7 @@ LineageTables LineageTabulator::Finish(const std::string& seed_name) const {
     int i = 0;
     for (int p : naive_c_.MostCommon())
       naive_name[naive_c_.keys[p]] =
-          "naive_" + std::to_string(i++) + "_" + frac(naive_c_.counts[p], num_trees_);
+          "naive_" + std::to_string(i++) + "_" + frac(naive_c_.counts[p], total_);
   }
   std::unordered_map<int, int> node_of_aa;
   int n_inter = 0;
@@ -140,7 +159,7 @@ LineageTables LineageTabulator::Finish(const std::string& seed_name) const {
       nd.name = nn->second;
       nd.kind = "naive";
     } else {
-      nd.name = "intermediate_" + std::to_string(n_inter++) + "_" + frac(nd.count, num_trees_);
+      nd.name = "intermediate_" + std::to_string(n_inter++) + "_" + frac(nd.count, total_);
       nd.kind = "intermediate";
     }
     const Counted& dt = node_dt_[aa];
@@ -174,14 +193,14 @@ void WriteLineageDnaMap(std::ostream& o, const LineageTables& t) {
   Fractions frac;
   for (const auto& n : t.nodes) {
     o << ">" << n.name << "\n";
-    for (const auto& d : n.dna) o << frac(d.first, t.num_trees) << "," << d.second << "\n";
+    for (const auto& d : n.dna) o << frac(d.first, t.total) << "," << d.second << "\n";
   }
 }
 
 void WriteLineageNodes(std::ostream& o, const LineageTables& t) {
   Fractions frac;
   o << "name\tkind\tcount\tfraction\n";
-  for (const auto& n : t.nodes) o << n.name << "\t" << n.kind << "\t" << n.count << "\t" << frac(n.count, t.num_trees) << "\n";
+  for (const auto& n : t.nodes) o << n.name << "\t" << n.kind << "\t" << CountText(t, n.count) << "\t" << frac(n.count, t.total) << "\n";
 }
 
 void WriteLineageEdges(std::ostream& o, const LineageTables& t) {
@@ -189,17 +208,42 @@ void WriteLineageEdges(std::ostream& o, const LineageTables& t) {
   o << "parent\tchild\tcount\tfraction\tparent_fraction\tmutations\n";
   for (const auto& e : t.edges) {
     const auto &a = t.nodes[e.parent], &b = t.nodes[e.child];
-    o << a.name << "\t" << b.name << "\t" << e.count << "\t" << frac(e.count, t.num_trees) << "\t"
+    o << a.name << "\t" << b.name << "\t" << CountText(t, e.count) << "\t" << frac(e.count, t.total) << "\t"
       << frac(e.count, a.count) << "\t" << FindMuts(a.aa, b.aa) << "\n";
   }
 }
 
-void WriteLineageSummary(std::ostream& o, const LineageTables& t, int64_t collisions) {
+void WriteLineageSummary(std::ostream& o, const LineageTables& t, int64_t collisions, const LineageWeightSummary* ws) {
   o << "key\tvalue\nrows\t" << t.num_trees << "\ndistinct_nt\t" << t.distinct_nt << "\ndistinct_aa\t" << t.distinct_aa
     << "\nlongest_path\t" << t.longest_path << "\nhash_collisions_resolved\t" << collisions << "\n";
+  if (ws)
+    o << "rows_used\t" << ws->rows_used << "\nrows_skipped_nonfinite\t" << ws->rows_skipped_nonfinite << "\ndraws_per_row\t"
+      << ws->draws_per_row << "\nkish_ess\t" << G17(ws->kish_ess) << "\n";
 }
 
-void WriteLineageFiles(const std::string& prefix, const LineageTables& t, int64_t collisions) {
+std::vector<double> LineageWeights(const std::vector<double>& lw, LineageWeightSummary* ws) {
+  double top = -INFINITY;
+  for (double x : lw)
+    if (std::isfinite(x)) top = std::max(top, x);
+  if (!std::isfinite(top)) throw std::runtime_error("lineage: no row with a finite weight");
+  std::vector<double> w(lw.size(), 0.0);
+  double s1 = 0, s2 = 0;
+  ws->rows_used = ws->rows_skipped_nonfinite = 0;
+  for (std::size_t i = 0; i < lw.size(); ++i) {
+    if (!std::isfinite(lw[i])) {
+      ++ws->rows_skipped_nonfinite;
+      continue;
+    }
+    w[i] = std::exp(lw[i] - top);
+    ++ws->rows_used;
+    s1 += w[i];
+    s2 += w[i] * w[i];
+  }
+  ws->kish_ess = s1 * s1 / s2;
+  return w;
+}
+
+void WriteLineageFiles(const std::string& prefix, const LineageTables& t, int64_t collisions, const LineageWeightSummary* ws) {
   std::ofstream fasta(prefix + ".fasta"), dnamap(prefix + ".dnamap"), nodes(prefix + ".nodes.tsv"),
       edges(prefix + ".edges.tsv"), summary(prefix + ".summary.tsv");
   if (!fasta || !dnamap || !nodes || !edges || !summary) throw std::runtime_error("Can't write " + prefix + ".*");
@@ -207,7 +251,7 @@ void WriteLineageFiles(const std::string& prefix, const LineageTables& t, int64_
   WriteLineageDnaMap(dnamap, t);
   WriteLineageNodes(nodes, t);
   WriteLineageEdges(edges, t);
-  WriteLineageSummary(summary, t, collisions);
+  WriteLineageSummary(summary, t, collisions, ws);
 }
 
 std::vector<std::string> LineageOfAnnotatedTree(const std::string& s, const std::string& seed_seq) {
@@ -293,16 +337,44 @@ std::vector<std::string> LineageOfAnnotatedTree(const std::string& s, const std:
   return l;
 }
 
-void TabulateLineageTrees(const std::string& trees_path, const std::string& seed_seq, const std::string& prefix) {
+void TabulateLineageTrees(const std::string& trees_path, const std::string& seed_seq, const std::string& prefix,
+                          const std::string& weights_path) {
   if (seed_seq == "naive") throw std::runtime_error("the seed sequence cannot be 'naive': the lineage ends there");
   std::ifstream in(trees_path);
   if (!in) throw std::runtime_error("Can't open trees file " + trees_path);
-  LineageTabulator tab;
   std::string line;
-  std::size_t n_line = 0;
+  // the weights first: a tree's weight needs the largest log-weight
+  const bool weighted = !weights_path.empty();
+  std::vector<double> lw, w;
+  LineageWeightSummary ws;
+  if (weighted) {
+    std::ifstream win(weights_path);
+    if (!win) throw std::runtime_error("Can't open weights file " + weights_path);
+    while (std::getline(win, line)) {
+      const std::size_t a = line.find_first_not_of(" \t\r");
+      if (a == std::string::npos) continue;
+      const char* b = line.c_str() + a;
+      char* end = nullptr;
+      const double v = std::strtod(b, &end);
+      if (end == b || std::string(end).find_first_not_of(" \t\r") != std::string::npos)
+        throw std::runtime_error(weights_path + " line " + std::to_string(lw.size() + 1) + ": not a number: " + line);
+      lw.push_back(v);
+    }
+  }
+  LineageTabulator tab;
+  if (weighted) tab.SetWeighted();
+  std::size_t n_line = 0, n_trees = 0;
+  bool have_weights = false;
   while (std::getline(in, line)) {
     ++n_line;
     if (line.find_first_not_of(" \t\r") == std::string::npos) continue;
+    const std::size_t k = n_trees++;
+    if (weighted && k >= lw.size()) continue;  // (counted on: the error below names both counts)
+    if (weighted && !have_weights) {
+      w = LineageWeights(lw, &ws);
+      have_weights = true;
+    }
+    if (weighted && !std::isfinite(lw[k])) continue;  // skipped and counted
     std::vector<std::string> l;
     try {
       l = LineageOfAnnotatedTree(line, seed_seq);
@@ -310,9 +382,12 @@ void TabulateLineageTrees(const std::string& trees_path, const std::string& seed
       throw std::runtime_error(trees_path + " line " + std::to_string(n_line) + ": " + e.what());
     }
     // naive, the root RunAsr adds on the naive branch, naive's neighbour .. seed's parent, seed
-    tab.AddTree(l, std::max(0, (int)l.size() - 3));
+    tab.AddTree(l, std::max(0, (int)l.size() - 3), weighted ? w[k] : 1.0);
   }
-  WriteLineageFiles(prefix, tab.Finish(seed_seq), 0);
+  if (weighted && lw.size() != n_trees)
+    throw std::runtime_error("the weights file " + weights_path + " has " + std::to_string(lw.size()) + " lines, the trees file " +
+                             trees_path + " has " + std::to_string(n_trees) + " trees");
+  WriteLineageFiles(prefix, tab.Finish(seed_seq), 0, weighted ? &ws : nullptr);
 }
 
 }  // namespace linearham

@@ -14,20 +14,30 @@
 namespace linearham {
 
 /// The finished tables.  Nodes are in node_c.most_common() order (descending count, ties by first appearance), edges
-/// likewise; fractions are count / num_trees.
+/// likewise; a count is the sum of the weights of the trees that count (whole numbers when every tree weighs 1, the
+/// script's case), fractions are count / total, total = the sum of all trees' weights.
 struct LineageTables {
   struct Node {
     std::string name, kind, aa;  // kind: seed / naive / intermediate
-    int64_t count = 0;
-    std::vector<std::pair<int64_t, std::string>> dna;  // node_dt[aa].most_common(): (count, nucleotide sequence)
+    double count = 0;
+    std::vector<std::pair<double, std::string>> dna;  // node_dt[aa].most_common(): (count, nucleotide sequence)
   };
   struct Edge {
     int parent = 0, child = 0;  // indices into nodes; never equal
-    int64_t count = 0;
+    double count = 0;
   };
   std::vector<Node> nodes;
   std::vector<Edge> edges;
   int64_t num_trees = 0, distinct_nt = 0, distinct_aa = 0, longest_path = 0;
+  double total = 0;       // sum of the trees' weights (= num_trees when none was given)
+  bool weighted = false;  // some tree was added with a weight of its own: counts print as doubles
+};
+
+/// What the weighted entry points add to .summary.tsv.
+struct LineageWeightSummary {
+  int64_t rows_used = 0, rows_skipped_nonfinite = 0;
+  int draws_per_row = 1;
+  double kish_ess = 0;  // (sum w)^2 / sum w^2 over the used rows
 };
 
 /// The script's counting.  A tree is its lineage as a list of nucleotide sequences naive, root, ..., seed's parent,
@@ -41,9 +51,12 @@ class LineageTabulator {
  public:
   /// Registers a nucleotide sequence (translated once) and returns its id; equal sequences share an id.
   int AddSequence(const std::string& nt);
-  /// One tree, as ids from AddSequence; `path_len` (inner nodes between seed and naive) feeds longest_path.
-  void AddTree(const std::vector<int>& ids, int path_len);
-  void AddTree(const std::vector<std::string>& seqs, int path_len);
+  /// One tree, as ids from AddSequence; `path_len` (inner nodes between seed and naive) feeds longest_path.  The tree
+  /// counts `weight` wherever the script counts 1 (sums of ones are exact: the unweighted tables are the script's).
+  void AddTree(const std::vector<int>& ids, int path_len, double weight = 1.0);
+  void AddTree(const std::vector<std::string>& seqs, int path_len, double weight = 1.0);
+  /// The tables' counts are to print as doubles even if every weight was 1 (the weighted entry points).
+  void SetWeighted() { weighted_ = true; }
   /// Names as the script gives them: the seed's translation is `seed_name`; a translation that is some tree's naive
   /// translation is naive_<i>_<fraction> as tabulate_naive_probs.py:57-60 numbers them over these trees' naive
   /// sequences; every other is intermediate_<i>_<fraction>.  Throws if no tree was added or the seeds' translations
@@ -53,10 +66,10 @@ class LineageTabulator {
  private:
   struct Counted {  // a Counter: insertion-ordered keys with counts
     std::vector<int> keys;
-    std::vector<int64_t> counts;
+    std::vector<double> counts;
     std::unordered_map<int, int> at;  // key -> position, kept once there are more than kLinear keys
     static constexpr std::size_t kLinear = 8;
-    void Add(int key);
+    void Add(int key, double weight);
     std::vector<int> MostCommon() const;  // positions into keys
   };
   std::vector<std::string> nt_, aa_;
@@ -65,10 +78,12 @@ class LineageTabulator {
   Counted node_c_, naive_c_;
   std::vector<Counted> node_dt_;  // aa -> Counter of nt
   std::vector<std::pair<int, int>> edge_keys_;
-  std::vector<int64_t> edge_counts_;
+  std::vector<double> edge_counts_;
   std::map<std::pair<int, int>, int> edge_at_;
   std::vector<int> seed_aa_;  // distinct seed translations
   int64_t num_trees_ = 0, longest_path_ = 0;
+  double total_ = 0;
+  bool weighted_ = false;
 };
 
 /// find_muts: "<orig><1-based position><mutated>" for every differing position, space-separated.
@@ -76,13 +91,20 @@ std::string FindMuts(const std::string& orig, const std::string& mutated);
 
 /// <prefix>.fasta and .dnamap byte for byte as the script writes them; .nodes.tsv (name, kind, count, fraction),
 /// .edges.tsv (parent, child, count, fraction, parent_fraction, mutations) and .summary.tsv (rows, distinct_nt,
-/// distinct_aa, longest_path, hash_collisions_resolved).  Fractions print as Python's str(float).
+/// distinct_aa, longest_path, hash_collisions_resolved; with `ws` also rows_used, rows_skipped_nonfinite, draws_per_row and
+/// kish_ess, %.17g).  Fractions print as Python's str(float); counts as integers, or -- weighted tables -- as str(float).
 void WriteLineageFasta(std::ostream& o, const LineageTables& t);
 void WriteLineageDnaMap(std::ostream& o, const LineageTables& t);
 void WriteLineageNodes(std::ostream& o, const LineageTables& t);
 void WriteLineageEdges(std::ostream& o, const LineageTables& t);
-void WriteLineageSummary(std::ostream& o, const LineageTables& t, int64_t collisions);
-void WriteLineageFiles(const std::string& prefix, const LineageTables& t, int64_t collisions);
+void WriteLineageSummary(std::ostream& o, const LineageTables& t, int64_t collisions,
+                         const LineageWeightSummary* ws = nullptr);
+void WriteLineageFiles(const std::string& prefix, const LineageTables& t, int64_t collisions,
+                       const LineageWeightSummary* ws = nullptr);
+
+/// Importance weights of rows from their log-weights: w_i = exp(lw_i - max lw) over the finite lw_i, 0 for the others
+/// (which `ws` counts as skipped); ws->kish_ess = (sum w)^2 / sum w^2.  Throws if no log-weight is finite.
+std::vector<double> LineageWeights(const std::vector<double>& log_weights, LineageWeightSummary* ws);
 
 /// One line of PhyloHMM::RunAsr's output (annotated Newick): the [&ancestral="..."] strings on the way seed, its
 /// ancestors up to the top node, then the tip `naive`, as seqs_of_tree collects them, reversed (naive first).
@@ -90,7 +112,11 @@ void WriteLineageFiles(const std::string& prefix, const LineageTables& t, int64_
 std::vector<std::string> LineageOfAnnotatedTree(const std::string& newick, const std::string& seed_seq);
 
 /// tabulate_lineage_probs.py for a file of RunAsr lines: needs no family and no device.  Writes the five files.
-void TabulateLineageTrees(const std::string& trees_path, const std::string& seed_seq, const std::string& prefix);
+/// `weights_path` (optional): one log-weight per tree line (a table's LogWeight column); tree k then counts
+/// exp(lw_k - max lw), lines whose log-weight is not finite are skipped and counted, and the summary gains the weighted
+/// keys.  The two files must have the same number of lines.
+void TabulateLineageTrees(const std::string& trees_path, const std::string& seed_seq, const std::string& prefix,
+                          const std::string& weights_path = "");
 
 }  // namespace linearham
 

@@ -819,10 +819,11 @@ struct PhyloHMM::TableBatch {
   std::vector<int> iteration;
   std::vector<double> lik, prior;
   std::vector<std::string> exported;  // per row: the output table's tree column (with_export)
+  std::vector<int32_t> children, root;  // per row: the child lists lh_schedule_tree got and the root (with_children)
 };
 
 PhyloHMM::TableBatch PhyloHMM::FlattenTable(const TsvTable& t, std::size_t r0, std::size_t r1, bool with_export,
-                                            bool with_scalars, const std::string& path) const {
+                                            bool with_scalars, const std::string& path, bool with_children) const {
   const auto t_begin = SteadyNow();
   TableBatch tb;
   DeviceBatch& b = tb.dev;
@@ -836,6 +837,10 @@ PhyloHMM::TableBatch PhyloHMM::FlattenTable(const TsvTable& t, std::size_t r0, s
   b.pi.resize(m * 4);
   b.alpha.resize(m);
   if (with_export) tb.exported.resize(m);
+  if (with_children) {
+    tb.children.resize(m * 2 * (std::size_t)(T - 2));
+    tb.root.resize(m);
+  }
   if (with_scalars) {
     tb.iteration.resize(m);
     tb.lik.resize(m);
@@ -887,6 +892,10 @@ PhyloHMM::TableBatch PhyloHMM::FlattenTable(const TsvTable& t, std::size_t r0, s
                       b.brlen.data() + i * (std::size_t)(2 * T - 2), with_export ? &tb.exported[i] : nullptr);
       CheckHip(lh_schedule_tree(T, children.data(), root, b.ops.data() + i * (std::size_t)(T - 2) * 4, &depth),
                "lh_schedule_tree");
+      if (with_children) {
+        std::copy(children.begin(), children.end(), tb.children.begin() + i * children.size());
+        tb.root[i] = root;
+      }
       *max_depth = std::max(*max_depth, (int)depth);
     }
   };
@@ -1570,6 +1579,190 @@ void PhyloHMM::RunLineagePipeline(const std::string& input_path, const std::stri
                  "%.3f s, resolve+read back (%d sequences) %.3f s, count %.3f s, write %.3f s; total %.3f s\n",
                  rows.size(), Seconds(t_start, t_read), t_flat, t_dev, (int)interner.K(), t_resolve, t_count, Seconds(t_w, SteadyNow()),
                  Seconds(t_start, SteadyNow()));
+}
+
+// The weighted lineage tables in one pass over the RevBayes table.  Per batch the chain lh_eval_lineage_batch evaluates the
+// rows, draws each row's naive sequence from RunPipeline's std::mt19937 words, draws `draws_per_row` sets of ancestral
+// sequences (Philox stream `seed`, sample number = table row, draw d in the upper half) and hashes the lineage slots; the
+// host interns the sequences as RunLineagePipeline does.  A tree's weight needs the largest log-weight of the table, so
+// the batches' id lists are kept and counted after the last batch: the result does not depend on the batch size.
+void PhyloHMM::RunWeightedLineagePipeline(const std::string& input_path, const std::string& seed_seq,
+                                          const std::string& output_prefix, int num_rates, double burnin_frac,
+                                          int draws_per_row, uint64_t seed) {
+  Require(devices_.size() <= 1, "the weighted lineage pipeline runs on one device: --devices may list only one");
+  Require(burnin_frac >= 0.0 && burnin_frac < 1.0, "burn-in fraction must be in [0, 1)");
+  Require(draws_per_row >= 1 && draws_per_row <= 64, "draws-per-row must be in 1 .. 64");
+  Require(seed_seq != "naive", "the seed sequence cannot be 'naive': the lineage ends there");
+  const int T = (int)xmsa_labels_.size();
+  int seed_tip = -1;
+  for (int v = 1; v < T; ++v)
+    if (xmsa_labels_[v] == seed_seq) seed_tip = v;
+  Require(seed_tip > 0, "the seed sequence '" + seed_seq + "' is not a sequence of this clonal family");
+  CreateFamily();
+  Require(device_sampler_, "the weighted lineage pipeline draws the naive sequences on the device: this family has no "
+                           "device sampler tables (or LH_HOST_SAMPLING is set)");
+  const bool timing = host_options().pipeline_timing;
+  const auto t_start = SteadyNow();
+  double t_flat = 0, t_dev = 0, t_resolve = 0;
+  TsvTable table = TsvTable::OpenRevBayesTable(input_path);
+  const std::size_t N = table.rows.size();
+  const std::size_t first = (std::size_t)std::floor(burnin_frac * (double)N);
+  const std::size_t U = N - first;  // rows after the burn-in
+  const std::size_t D = (std::size_t)draws_per_row;
+  const int L = (int)msa_.cols();
+  // the id lists of every (row, draw) wait for the last batch: at most T ids each; 1 GiB of them is the limit
+  const std::size_t kHeldLimit = (std::size_t)1 << 30;
+  Require(U * D * (std::size_t)T * sizeof(int32_t) <= kHeldLimit,
+          "weighted lineage pipeline: " + std::to_string(U) + " rows x " + std::to_string(D) + " draws x " + std::to_string(T) +
+              " lineage nodes exceed the 1 GiB the pipeline keeps until the weights are known; at most " +
+              std::to_string(kHeldLimit / (D * (std::size_t)T * sizeof(int32_t))) + " rows for this family and draws-per-row");
+  const auto t_read = SteadyNow();
+  CheckHip(lh_lineage_reset(family_), "lh_lineage_reset");
+  LineageTabulator tab;
+  tab.SetWeighted();
+  std::string seed_nt((std::size_t)L, 'N');
+  for (int j = 0; j < L; ++j) seed_nt[j] = alphabet_[msa_(seed_tip - 1, j)];
+  const int seed_id = tab.AddSequence(seed_nt);  // (tips keep their observed characters: one sequence for every tree)
+  SeqInterner interner(family_, lh_lineage_resolve, lh_lineage_rows_read, L, "weighted lineage pipeline");
+  std::vector<int> tab_of_store;      // store id -> tabulator id
+  std::vector<uint64_t> aa_of_store;  // store id -> translation hash of its first slot
+  const int raw = RawDrawsPerSample();
+  std::mt19937 word_rng = rng_;
+  word_rng.discard((unsigned long long)first * (unsigned long long)raw);
+  std::vector<double> ll(U), lw(U);
+  std::vector<int32_t> path_len(U, 0), naive_tab(U, -1);
+  std::vector<int32_t> held;              // per used (row, draw): naive, root .. seed's parent (tabulator ids)
+  std::vector<std::size_t> held_at(U + 1, 0);  // row -> its first entry in held (D lists of path_len + 1 ids)
+  const std::size_t kBatch = host_options().lineage_batch > 0 ? (std::size_t)host_options().lineage_batch : 1024;
+  for (std::size_t off = first; off < N; off += kBatch) {
+    const std::size_t m = std::min(kBatch, N - off);
+    const auto t0 = SteadyNow();
+    TableBatch tb = FlattenTable(table, off, off + m, false, true, input_path, true);
+    const DeviceBatch& b = tb.dev;
+    // the seed tip's ancestors up to naive's neighbour
+    std::vector<std::vector<int32_t>> chain(m);
+    std::size_t P = 1;
+    std::vector<int> parent(2 * (std::size_t)T - 2);
+    for (std::size_t i = 0; i < m; ++i) {
+      const int32_t* ch = tb.children.data() + i * 2 * (std::size_t)(T - 2);
+      const int root = tb.root[i];
+      std::fill(parent.begin(), parent.end(), -1);
+      for (int v = T; v < 2 * T - 2; ++v)
+        for (int c = 0; c < 2; ++c) parent[ch[2 * (std::size_t)(v - T) + c]] = v;
+      for (int v = parent[seed_tip]; v >= T; v = parent[v]) {
+        chain[i].push_back(v);
+        if (v == root || (int)chain[i].size() > T) break;
+      }
+      Require(!chain[i].empty() && chain[i].back() == root,
+              "row " + std::to_string(off + i) + ": the seed sequence '" + seed_seq + "' does not descend from the root");
+      P = std::max(P, chain[i].size());
+    }
+    std::vector<int32_t> path(m * P, -1);
+    for (std::size_t i = 0; i < m; ++i) std::copy(chain[i].begin(), chain[i].end(), path.begin() + i * P);
+    const std::size_t S = P + 1;
+    std::vector<uint32_t> words(m * (std::size_t)raw);
+    for (uint32_t& x : words) x = (uint32_t)word_rng();
+    std::vector<uint64_t> nt_hash(m * D * S), aa_hash(m * D * S);
+    double* ll_b = ll.data() + (off - first);
+    lh_lineage_eval_outputs outs{};
+    outs.loglik = ll_b;
+    outs.nt_hash = nt_hash.data();
+    outs.aa_hash = aa_hash.data();
+    const auto t1 = SteadyNow();
+    CheckHip(lh_eval_lineage_batch(family_, b.n, b.n_tips, b.max_depth, b.ops.data(), b.brlen.data(), b.er.data(),
+                                   b.pi.data(), b.alpha.data(), num_rates, words.data(), seed, (uint64_t)off,
+                                   draws_per_row, path.data(), (int32_t)P, &outs),
+             "lh_eval_lineage_batch");
+    const auto t2 = SteadyNow();
+    // every slot of a used row but the padding ones takes part
+    std::vector<uint8_t> take(m * D * S, 0);
+    for (std::size_t i = 0; i < m; ++i) {
+      const std::size_t u = off - first + i;
+      lw[u] = ll_b[i] - tb.lik[i];
+      path_len[u] = (int32_t)chain[i].size();
+      if (!std::isfinite(lw[u])) continue;
+      for (std::size_t d = 0; d < D; ++d) {
+        uint8_t* tk = take.data() + (i * D + d) * S;
+        std::fill(tk, tk + chain[i].size(), 1);
+        tk[P] = 1;
+      }
+    }
+    std::vector<int32_t> ids(m * D * S);
+    const int32_t K_before = interner.K();
+    const int32_t K = K_before + interner.Assign(m * D * S, nt_hash.data(), take.data(), ids.data());
+    if (K > K_before) {  // only the bases of the sequences first seen in this batch come back
+      std::vector<uint8_t> bytes((std::size_t)(K - K_before) * L);
+      CheckHip(lh_lineage_store_read(family_, K_before, K - K_before, nullptr, bytes.data()), "lh_lineage_store_read");
+      for (int32_t k = K_before; k < K; ++k)
+        tab_of_store.push_back(tab.AddSequence(DecodeBases(bytes.data() + (std::size_t)(k - K_before) * L, (std::size_t)L, alphabet_)));
+      aa_of_store.resize(K);
+      std::vector<bool> have(K - K_before, false);
+      for (std::size_t x = 0; x < m * D * S; ++x)
+        if (ids[x] >= K_before && !have[ids[x] - K_before]) {
+          have[ids[x] - K_before] = true;
+          aa_of_store[ids[x]] = aa_hash[x];
+        }
+    }
+    for (std::size_t i = 0; i < m; ++i) {
+      const std::size_t u = off - first + i;
+      held_at[u] = held.size();
+      if (!std::isfinite(lw[u])) continue;
+      for (std::size_t d = 0; d < D; ++d) {
+        const std::size_t x0 = (i * D + d) * S;
+        for (std::size_t s = 0; s < S; ++s)
+          if (ids[x0 + s] >= 0)
+            Require(aa_hash[x0 + s] == aa_of_store[ids[x0 + s]],
+                    "weighted lineage pipeline: equal sequences with different translation hashes at row " + std::to_string(off + i));
+        held.push_back(tab_of_store[ids[x0 + P]]);
+        for (std::size_t s = chain[i].size(); s-- > 0;) held.push_back(tab_of_store[ids[x0 + s]]);
+      }
+      naive_tab[u] = tab_of_store[ids[i * D * S + P]];
+    }
+    const auto t3 = SteadyNow();
+    t_flat += Seconds(t0, t1);
+    t_dev += Seconds(t1, t2);
+    t_resolve += Seconds(t2, t3);
+  }
+  held_at[U] = held.size();
+  // the weights, then every (row, draw) as one tree of its row's weight, in (row, draw) order
+  const auto t_c = SteadyNow();
+  LineageWeightSummary ws;
+  const std::vector<double> w = LineageWeights(lw, &ws);
+  ws.draws_per_row = draws_per_row;
+  std::vector<int> l;
+  for (std::size_t u = 0; u < U; ++u) {
+    if (!std::isfinite(lw[u])) continue;
+    const std::size_t len = (std::size_t)path_len[u] + 1;
+    for (std::size_t d = 0; d < D; ++d) {
+      const int32_t* h = held.data() + held_at[u] + d * len;
+      l.assign(h, h + len);
+      l.push_back(seed_id);
+      tab.AddTree(l, path_len[u], w[u]);
+    }
+  }
+  const auto t_w = SteadyNow();
+  WriteLineageFiles(output_prefix, tab.Finish(seed_seq), interner.collisions(), &ws);
+  {
+    // per row after the burn-in: what upstream's .log subset was for.  naive_id numbers the used rows' naive sequences by
+    // first appearance (-1: a skipped row)
+    std::ofstream rows(output_prefix + ".rows.tsv");
+    if (!rows) throw std::runtime_error("Can't write " + output_prefix + ".rows.tsv");
+    rows << "row\tlh_loglik\tlog_weight\tweight\tnaive_id\tpath_len\n";
+    std::unordered_map<int32_t, int32_t> naive_id;
+    char buf[160];
+    for (std::size_t u = 0; u < U; ++u) {
+      int32_t id = -1;
+      if (std::isfinite(lw[u])) id = naive_id.emplace(naive_tab[u], (int32_t)naive_id.size()).first->second;
+      std::snprintf(buf, sizeof buf, "%zu\t%.17g\t%.17g\t%.17g\t%d\t%d\n", first + u, ll[u], lw[u], w[u], (int)id, (int)path_len[u]);
+      rows << buf;
+    }
+  }
+  if (timing)
+    std::fprintf(stderr,
+                 "[RunWeightedLineagePipeline] %zu rows x %zu draws: read %.3f s, parse+schedule+paths %.3f s, device (the chain, "
+                 "copies) %.3f s, resolve+read back (%d sequences) %.3f s, count %.3f s, write %.3f s; total %.3f s\n",
+                 U, D, Seconds(t_start, t_read), t_flat, t_dev, (int)interner.K(), t_resolve, Seconds(t_c, t_w),
+                 Seconds(t_w, SteadyNow()), Seconds(t_start, SteadyNow()));
 }
 
 // src/PhyloHMM.cpp:461-471

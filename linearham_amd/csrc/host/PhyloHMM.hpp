@@ -145,6 +145,19 @@ class PhyloHMM : public HMM {
   /// LH_LINEAGE_BATCH=n sets the rows per batch (default 1 024, RunAsr's).
   void RunLineagePipeline(const std::string& input_path, const std::string& seed_seq, const std::string& output_prefix,
                           uint64_t seed);
+  /// Importance-weighted lineage tables straight from the RevBayes table, in one pass: RunNaiveProbsPipeline's burn-in
+  /// (the first floor(burnin_frac * rows) rows), weights (lw_i = LHLogLikelihood_i - Likelihood_i, w_i = exp(lw_i - max lw),
+  /// rows with a non-finite lw skipped and counted) and one-device rule; per row the naive sequence `--pipeline --seed s`
+  /// prints for it (the same std::mt19937 words) and `draws_per_row` (1 .. 64) ancestral draws on K0a's full-precision
+  /// rates (Philox stream `seed`, sample number = table row, draw d in the upper 32 bits: lh_eval_lineage_batch).  Every
+  /// (row, draw) is one tree of weight w_i, counted in (row, draw) order after the last batch (the id lists wait until
+  /// the largest log-weight is known: the result does not depend on LH_LINEAGE_BATCH; more than 1 GiB of them is
+  /// refused).  Writes the five lineage files -- counts are weighted sums, fractions sum / (draws x sum w), the summary
+  /// gains rows_used, rows_skipped_nonfinite, draws_per_row and kish_ess -- and <prefix>.rows.tsv (row, lh_loglik,
+  /// log_weight, weight, naive_id, path_len per row after the burn-in).
+  void RunWeightedLineagePipeline(const std::string& input_path, const std::string& seed_seq,
+                                  const std::string& output_prefix, int num_rates, double burnin_frac, int draws_per_row,
+                                  uint64_t seed);
   /// One annotated tree (RunAsr's output line) from the sampled states anc[(T-2)][L] of a row.
   std::string AnnotatedNewick(const TreeArrays& tree, const std::string& naive_sequence, const uint8_t* anc) const;
 
@@ -187,7 +200,7 @@ class PhyloHMM : public HMM {
 
  private:
   TableBatch FlattenTable(const TsvTable& table, std::size_t r0, std::size_t r1, bool with_export, bool with_scalars,
-                          const std::string& path) const;
+                          const std::string& path, bool with_children = false) const;
   struct AsrRow;
   /// The rows of a RunPipeline table as RunAsr and RunLineagePipeline read them; *num_rates = the sr[] columns.
   std::vector<AsrRow> ReadAsrRows(const std::string& input_path, int* num_rates) const;

@@ -403,9 +403,21 @@ int lhh_run_lineage_pipeline(void* h, const char* input_path, const char* seed_s
     dynamic_cast<PhyloHMM&>(*static_cast<HMM*>(h)).RunLineagePipeline(input_path, seed_seq, output_prefix, seed);
   });
 }
+int lhh_run_weighted_lineage_pipeline(void* h, const char* input_path, const char* seed_seq, const char* output_prefix,
+                                      int num_rates, double burnin_frac, int draws_per_row, uint64_t seed) {
+  return Guard([&] {
+    dynamic_cast<PhyloHMM&>(*static_cast<HMM*>(h)).RunWeightedLineagePipeline(input_path, seed_seq, output_prefix, num_rates,
+                                                                             burnin_frac, draws_per_row, seed);
+  });
+}
 // TabulateLineageTrees: a file of RunAsr lines -> the lineage tables (no family, no GPU)
 int lhh_lineage_tabulate_trees(const char* trees_path, const char* seed_seq, const char* output_prefix) {
   return Guard([&] { TabulateLineageTrees(trees_path, seed_seq, output_prefix); });
+}
+// the same with one log-weight per tree line (weights_path NULL or empty: none)
+int lhh_lineage_tabulate_trees_weighted(const char* trees_path, const char* seed_seq, const char* output_prefix,
+                                        const char* weights_path) {
+  return Guard([&] { TabulateLineageTrees(trees_path, seed_seq, output_prefix, weights_path ? weights_path : ""); });
 }
 // what: bit 0 = state space + transitions, bit 1 = forward arrays, bit 2 = sample, bit 3 = xMSA structures
 

@@ -60,7 +60,7 @@ int main(int argc, char** argv) {
   try {
     if (argc < 2 || std::string(argv[1]) == "-h" || std::string(argv[1]) == "--help") {
       std::cout << "A Phylo-HMM implementation for B cell receptor sequence analysis.\n"
-                   "USAGE: linearham {--compute-logl|--sample|--pipeline|--asr|--marginals|--marginals-pipeline|--naive-probs|--naive-probs-pipeline|--lineage-pipeline} --yaml-path <string> "
+                   "USAGE: linearham {--compute-logl|--sample|--pipeline|--asr|--marginals|--marginals-pipeline|--naive-probs|--naive-probs-pipeline|--lineage-pipeline|--weighted-lineage-pipeline} --yaml-path <string> "
                    "--cluster-ind <int> --hmm-param-dir <string> [--seed <int>] [--num-rates <int>] [--extended-range <0|1>] "
                    "[--devices <a,b,...>] ...\n"
                    "  --marginals: the arguments of --compute-logl; prints the per-site naive-base table and the gene table\n"
@@ -74,7 +74,15 @@ int main(int argc, char** argv) {
                    "  --lineage-pipeline --input-path <--pipeline table> --output-path <prefix> --seed-seq <name> [--seed <int>]:\n"
                    "    the lineage tables of the sequence <name>: <prefix>.fasta, .dnamap, .nodes.tsv, .edges.tsv, .summary.tsv\n"
                    "       linearham --lineage-trees --input-path <--asr trees> --output-path <prefix> --seed-seq <name>\n"
-                   "    the same tables from a file --asr wrote (no family, no device)\n";
+                   "         [--weights-path <file>]\n"
+                   "    the same tables from a file --asr wrote (no family, no device); --weights-path: one log-weight per tree\n"
+                   "    line (the table's LogWeight column), tree k then counts exp(lw_k - max lw)\n"
+                   "  --weighted-lineage-pipeline --input-path <RevBayes table> --output-path <prefix> --seed-seq <name>\n"
+                   "    [--burnin-frac <f>] [--draws-per-row <1..64>] [--seed <int>]: the importance-weighted lineage tables in\n"
+                   "    one pass (one device): rows after the burn-in weighted by exp(LHLogLikelihood - Likelihood), per row the\n"
+                   "    naive sequence --pipeline --seed <int> prints and <draws-per-row> ancestral draws; writes the five lineage\n"
+                   "    files (counts are weighted sums; the summary gains rows_used, rows_skipped_nonfinite, draws_per_row,\n"
+                   "    kish_ess) and <prefix>.rows.tsv\n";
       return argc < 2 ? EXIT_FAILURE : EXIT_SUCCESS;
     }
     const auto t_main = std::chrono::steady_clock::now();
@@ -83,12 +91,12 @@ int main(int argc, char** argv) {
     const std::string subcmd = argv[1];
     const Args a = Parse(argc, argv, 2);
     if (subcmd == "--lineage-trees") {
-      linearham::TabulateLineageTrees(a.one("input-path"), a.one("seed-seq"), a.one("output-path"));
+      linearham::TabulateLineageTrees(a.one("input-path"), a.one("seed-seq"), a.one("output-path"), a.opt("weights-path", ""));
       return EXIT_SUCCESS;
     }
     if (subcmd != "--compute-logl" && subcmd != "--sample" && subcmd != "--pipeline" && subcmd != "--asr" &&
         subcmd != "--marginals" && subcmd != "--marginals-pipeline" && subcmd != "--naive-probs" &&
-        subcmd != "--naive-probs-pipeline" && subcmd != "--lineage-pipeline")
+        subcmd != "--naive-probs-pipeline" && subcmd != "--lineage-pipeline" && subcmd != "--weighted-lineage-pipeline")
       throw std::invalid_argument("'" + subcmd + "' is not a valid subcommand.");
     const std::string yaml_path = a.one("yaml-path");
     const int cluster_ind = std::stoi(a.one("cluster-ind"));
@@ -106,7 +114,8 @@ int main(int argc, char** argv) {
         device_list.push_back(std::stoi(devs.substr(pos, comma - pos)));
         pos = comma + 1;
       }
-      if (device_list.size() > 1 && (subcmd == "--marginals-pipeline" || subcmd == "--naive-probs-pipeline"))
+      if (device_list.size() > 1 && (subcmd == "--marginals-pipeline" || subcmd == "--naive-probs-pipeline" ||
+                                     subcmd == "--weighted-lineage-pipeline"))
         throw std::invalid_argument(subcmd + " runs on one device: --devices may list only one");
       if (device_list.size() > 1 && subcmd != "--pipeline")
         std::fprintf(stderr, "linearham: %s evaluates on one device; of --devices only device %d is used\n", subcmd.c_str(),
@@ -156,6 +165,12 @@ int main(int argc, char** argv) {
     if (subcmd == "--lineage-pipeline") {
       phylo_hmm_ptr->RunLineagePipeline(a.one("input-path"), a.one("seed-seq"), a.one("output-path"),
                                         (uint64_t)std::stoll(a.opt("seed", "0")));
+      return EXIT_SUCCESS;
+    }
+    if (subcmd == "--weighted-lineage-pipeline") {
+      phylo_hmm_ptr->RunWeightedLineagePipeline(a.one("input-path"), a.one("seed-seq"), a.one("output-path"), num_rates,
+                                                std::stod(a.opt("burnin-frac", "0")), std::stoi(a.opt("draws-per-row", "1")),
+                                                (uint64_t)std::stoll(a.opt("seed", "0")));
       return EXIT_SUCCESS;
     }
     if (subcmd == "--asr") {

@@ -128,13 +128,15 @@ __global__ void __launch_bounds__(256) asr_rate_kernel(int n, int R, int L, int 
                                                        const double* __restrict__ site_lik,
                                                        const int32_t* __restrict__ site_scal,
                                                        const uint8_t* __restrict__ naive, uint64_t seed,
-                                                       uint64_t sample0, uint8_t* __restrict__ choice) {
+                                                       uint64_t sample0, uint8_t* __restrict__ choice, int D) {
   const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (gid >= (long long)n * L) return;
-  const int sample = (int)(gid / L), j = (int)(gid - (long long)sample * L);
+  if (gid >= (long long)n * D * L) return;
+  // virtual sample v = (tree sample, draw): the planes and the naive bases are the tree sample's
+  const int v = (int)(gid / L), j = (int)(gid - (long long)v * L);
+  const int sample = v / D, draw = v - sample * D;
   const int pat = site_pat[j];
-  const int b = naive[gid];
-  const double u = asr_uniform(seed, sample0 + (uint64_t)sample, (uint32_t)j, 0u);
+  const int b = min((int)naive[(size_t)sample * L + j], 4);  // (a byte above 4 reads as N)
+  const double u = asr_uniform(seed, sample0 + (uint64_t)sample + ((uint64_t)draw << 32), (uint32_t)j, 0u);
   int pick = R - 1;
   if (pat >= n_prune) {  // all-N column: every category has the same likelihood
     const double t = u * (double)R;
@@ -249,16 +251,20 @@ __global__ void __launch_bounds__(256) asr_kernel(int R, int T, int L, int n_pru
                                                   uint8_t* __restrict__ choice_g,
                                                   const uint8_t* __restrict__ naive, uint64_t seed, uint64_t sample0,
                                                   double2* clv, int Lp, uint8_t* __restrict__ anc,
-                                                  const int4* __restrict__ hdr) {
+                                                  const int4* __restrict__ hdr, int D) {
   extern __shared__ double2 asr_smem[];
   const int n_ops = T - 2;
-  if (hdr[blockIdx.y].w != 0) {
+  // blockIdx.y is the virtual sample (tree sample, draw): `sample` indexes what belongs to the tree sample, `vs` what
+  // the draw owns (choice, CLV area, anc)
+  const int vs = blockIdx.y;
+  const int sample = vs / D;
+  if (hdr[sample].w != 0) {
     // malformed schedule (reported through lh_family_status): states are bytes and have no NaN, so the sample's rows get
     // the sentinel 0xff -- no stale byte of the caller's buffers may look like a draw (include/linearham_amd.h)
     if (blockIdx.x == 0) {
-      uint8_t* a = anc + (size_t)blockIdx.y * n_ops * (size_t)L;
+      uint8_t* a = anc + (size_t)vs * n_ops * (size_t)L;
       for (size_t i = threadIdx.x; i < (size_t)n_ops * L; i += blockDim.x) a[i] = 0xff;
-      for (int i = threadIdx.x; i < L; i += blockDim.x) choice_g[(size_t)blockIdx.y * L + i] = 0xff;
+      for (int i = threadIdx.x; i < L; i += blockDim.x) choice_g[(size_t)vs * L + i] = 0xff;
     }
     return;
   }
@@ -277,10 +283,9 @@ __global__ void __launch_bounds__(256) asr_kernel(int R, int T, int L, int n_pru
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int n_waves = blockDim.x >> 6;
   const int rate = blockIdx.x;
-  const int sample = blockIdx.y;
-  const uint64_t sample_id = sample0 + (uint64_t)sample;
+  const uint64_t sample_id = sample0 + (uint64_t)sample + ((uint64_t)(vs - sample * D) << 32);
   const AsrOp* __restrict__ dsc = desc + (size_t)sample * n_ops;
-  const uint8_t* __restrict__ ch = choice_g + (size_t)sample * L;
+  const uint8_t* __restrict__ ch = choice_g + (size_t)vs * L;
 
   for (int i = tid; i < R * NP; i += blockDim.x) flags[i] = 0;
   __syncthreads();
@@ -362,8 +367,8 @@ __global__ void __launch_bounds__(256) asr_kernel(int R, int T, int L, int n_pru
   // CLV area of the sample: [op][2][Lp] double2 -- components (0,1) and (2,3) of a slot are 16-byte entries of
   // two planes, so a wave's store is one contiguous run of whole 128-byte lines per plane.
   const size_t plane = (size_t)Lp;
-  double2* clv_s = clv + (size_t)sample * n_ops * 2 * plane;
-  uint8_t* anc_s = anc + (size_t)sample * n_ops * (size_t)L;
+  double2* clv_s = clv + (size_t)vs * n_ops * 2 * plane;
+  uint8_t* anc_s = anc + (size_t)vs * n_ops * (size_t)L;
   uint8_t* my_stack = st_stack + tid;
 
   // ---- upward pass over the category's distinct patterns, full waves first.
@@ -539,21 +544,22 @@ size_t asr_desc_bytes(int T) { return sizeof(AsrOp) * (size_t)(T - 2); }
 int launch_asr(const DevFamily& fam, int n, int R, int T, const int32_t* ops, const double* brlen, const double* rates,
                const double* eig, const double* pi, const double* site_lik, const int32_t* site_scal,
                const uint8_t* naive, uint64_t seed, uint64_t sample0, double* clv, void* desc, uint8_t* anc,
-               uint8_t* rate_choice, const int4* hdr, hipStream_t stream) {
+               uint8_t* rate_choice, const int4* hdr, hipStream_t stream, int draws) {
   const int L = fam.n_sites;
+  if (draws < 1 || (long long)n * draws > 65535) return 1;  // (one grid row per virtual sample)
   const size_t lds = asr_lds_bytes(T, L, R, fam.n_prune);
   if (lds > 160 * 1024 || L < 1) return 1;
   if (lds > 64 * 1024)
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(asr_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)lds);
-  const long long cells = (long long)n * L;
+  const long long cells = (long long)n * draws * L;
   hipLaunchKernelGGL(asr_rate_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, stream, n, R, L,
-                     fam.n_prune, fam.site_pat, site_lik, site_scal, naive, seed, sample0, rate_choice);
+                     fam.n_prune, fam.site_pat, site_lik, site_scal, naive, seed, sample0, rate_choice, draws);
   const size_t sched_lds = (size_t)(T - 2) * (sizeof(int4) + 2 * sizeof(int32_t));
   hipLaunchKernelGGL(asr_sched_kernel, dim3(n), dim3(64), sched_lds, stream, T, ops, hdr, static_cast<AsrOp*>(desc));
-  hipLaunchKernelGGL(asr_kernel, dim3(R, n), dim3(256), lds, stream, R, T, L, fam.n_prune, fam.msa, fam.site_pat,
+  hipLaunchKernelGGL(asr_kernel, dim3(R, n * draws), dim3(256), lds, stream, R, T, L, fam.n_prune, fam.msa, fam.site_pat,
                      static_cast<const AsrOp*>(desc), brlen, rates, eig, pi, rate_choice, naive, seed,
-                     sample0, reinterpret_cast<double2*>(clv), (int)asr_slots(L, R), anc, hdr);
+                     sample0, reinterpret_cast<double2*>(clv), (int)asr_slots(L, R), anc, hdr, draws);
   return 0;
 }
 

@@ -163,6 +163,7 @@ struct ForwardWs {  // K2a -> K2b hand-off (run_forward)
 
 struct AsrWs {  // K3's scratch
   DevBuf clv;
+  DevBuf rates;   // lh_eval_lineage_batch: K0a's rates of the whole batch when the caller does not ask for them
   DevBuf choice;  // K3a -> K3b when the caller does not ask for the rate categories
   DevBuf desc;    // K3s -> K3b schedule descriptors
 };
@@ -273,6 +274,7 @@ struct lh_family {
   KernelTimer<1> prior_timer, cand_timer;  // K6a, K6b
   KernelTimer<1> collect_timer;             // K6c
   KernelTimer<1> lineage_timer;             // K7
+  KernelTimer<5> chain_timer;               // lh_eval_lineage_batch: K0, K1, K2 + K4 + K6c, K3, K7
   bool extended = false;  // lh_family_set_extended_range
   bool have_sampler = false;
   lh::DevSampler sampler{};  // device pointers inside (arena)
@@ -2229,7 +2231,8 @@ int lh_lineage_resolve(lh_family* f, int32_t n_slots, const int32_t* ids, int32_
   DeviceGuard guard(f);
   const lh::LineageBatch& b = f->lineage.last;
   if (b.n < 0) return fail(W + ": no lineage batch on the handle");
-  if (n_slots != b.n * (b.P + 1)) return fail(W + ": n_slots differs from the last batch's rows x (path length + 1)");
+  if ((size_t)n_slots != lh::n_slots(b))
+    return fail(W + ": n_slots differs from the last batch's rows x draws x (path length + 1)");
   return store_resolve(W, f->lineage.store, b, n_slots, ids, n_mismatch, mismatch_slots);
 }
 
@@ -2239,7 +2242,7 @@ int lh_lineage_rows_read(lh_family* f, int32_t n_slots, const int32_t* slots, ui
   DeviceGuard guard(f);
   const lh::LineageBatch& b = f->lineage.last;
   if (b.n < 0) return fail(W + ": no lineage batch on the handle");
-  return store_rows_read(W, f->lineage.store, b, b.n * (b.P + 1), n_slots, slots, seqs);
+  return store_rows_read(W, f->lineage.store, b, (int32_t)lh::n_slots(b), n_slots, slots, seqs);
 }
 
 int lh_lineage_store_read(lh_family* f, int32_t first, int32_t count, int32_t* K, uint8_t* seqs) {
@@ -2260,6 +2263,194 @@ int lh_lineage_profile_read(lh_family* f, double* ms, int64_t* n_launches) {
   if (!f) return fail("null family");
   DeviceGuard guard(f);
   return f->lineage_timer.read(ms, n_launches);
+}
+
+}  // extern "C"
+
+// ---- the chain: evaluation, naive draw, ancestral draws and lineage hashes of a batch in one pass ----
+
+namespace {
+
+// The shape checks lh_eval_lineage_batch[_device] share (everything that needs no array): lh_lineage_batch's and
+// lh_eval_draw_batch's refusals, the draws, and the bound on the sampled states that stay on the device.
+int lineage_eval_check(lh_family* f, const std::string& W, int32_t n, int32_t T, int32_t R, int32_t max_depth,
+                       uint64_t first_sample, int32_t D, int32_t P, lh::CollectTables* t) {
+  if (int rc = check_batch(f, W, n, T, R, max_depth, true)) {
+    if (rc < 0) f->lineage.last.n = -1;
+    return rc;
+  }
+  f->lineage.last.n = -1;
+  if (D < 1 || D > 64) return fail(W + ": draws must be in 1 .. 64");
+  if (P < 1 || P > T - 2) return fail(W + ": path length must be in 1 .. n_tips - 2");
+  if (D > 1 && (first_sample > ((uint64_t)1 << 32) || first_sample + (uint64_t)n > ((uint64_t)1 << 32)))
+    return fail(W + ": with more than one draw per row the sample numbers first_sample .. first_sample + n - 1 must lie "
+                    "below 2^32 (the draw number takes the upper half)");
+  const size_t n_ops = (size_t)T - 2, L = f->host.n_sites;
+  // the whole batch's anc stays on the device for lh_lineage_resolve: n * draws samples of it
+  const size_t most = std::min<size_t>(((size_t)1 << 30) / std::max<size_t>(n_ops * L, 1), (size_t)INT32_MAX / (P + 1)) / (size_t)D;
+  if ((size_t)n > most)
+    return fail(W + ": batch too large to keep its sampled states on the device: at most " + std::to_string(most) +
+                " samples per call for this family with " + std::to_string(D) + " draws each");
+  DeviceGuard guard(f);
+  if (collect_tables(f, W, t)) return 1;
+  if (lh::asr_lds_bytes(T, f->host.n_sites, R, f->host.n_prune) > 160 * 1024)
+    return fail(W + ": tree / alignment too large for the sampling kernel's LDS tables");
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int lh_eval_lineage_batch_device(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops,
+                                 const double* brlen, const double* er, const double* pi, const double* alpha, int32_t R,
+                                 const uint32_t* words, uint64_t seed, uint64_t first_sample, int32_t D,
+                                 const int32_t* path, int32_t P, const lh_lineage_eval_outputs* outs, void* hip_stream) {
+  const std::string W = "lh_eval_lineage_batch_device";
+  lh::CollectTables t;
+  if (int rc = lineage_eval_check(f, W, n, T, R, max_depth, first_sample, D, P, &t)) return rc > 0;
+  DeviceGuard guard(f);
+  if (!ops || !brlen || !er || !pi || !alpha || !words || !path || !outs || !outs->loglik || !outs->nt_hash || !outs->aa_hash)
+    return fail(W + ": null array");
+  hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+  const size_t nodes = 2 * (size_t)T - 2, n_ops = (size_t)T - 2, L = f->host.n_sites, FS = f->host.forward_size;
+  const size_t NS = t.states_per_sample, NW = f->sampler.words_per_sample, S = (size_t)P + 1;
+  // launch groups: the smaller of the evaluation's limit and the sampling kernel's (whose CLV area and grid count
+  // virtual samples); one K1 launch, unmixed, serves K2 and K3 of the group, so its planes outlive K2
+  const size_t clv_per_sample = sizeof(double) * n_ops * 4 * lh::asr_slots((int)L, R);
+  const size_t k1_per_sample = k1_bytes_per_sample(f, T, R) + sizeof(double) * R * 6 * (size_t)std::max(f->host.n_prune, 1);
+  const size_t eval_limit = std::min<size_t>(kChunk, std::max<size_t>(1024, ((size_t)16 << 30) / k1_per_sample));
+  const size_t asr_limit =
+      std::max<size_t>(1, std::min<size_t>(8192, std::max<size_t>(64, ((size_t)8 << 30) / (clv_per_sample + k1_per_sample))) / (size_t)D);
+  const int chunk = (int)std::min<size_t>((size_t)n, std::min(eval_limit, asr_limit));
+  if (ensure_workspace(f, chunk, R, T)) return 1;
+  AsrWs& aw = f->asr;
+  CollectWs& c = f->collect;
+  HostOutputs& out = f->out;
+  if (aw.clv.ensure(clv_per_sample * chunk * D) || aw.desc.ensure(lh::asr_desc_bytes(T) * chunk) ||
+      out.anc.ensure(n_ops * L * n * D) || out.rate_choice.ensure(L * (size_t)n * D) ||
+      f->forward_dev.ensure(sizeof(double) * FS * n) || c.seqs.ensure((size_t)n * L) || c.hash.ensure(sizeof(uint64_t) * n) ||
+      (!outs->states && c.states.ensure(sizeof(int32_t) * NS * n)) || (!outs->rates && aw.rates.ensure(sizeof(double) * R * n)))
+    return 1;
+  Workspace& w = f->ws;
+  double *eig = w.eig.get<double>(), *site_lik = w.site_lik.get<double>(), *fwd = f->forward_dev.get<double>();
+  int32_t* site_scal = w.site_scal.get<int32_t>();
+  double* rates = outs->rates ? outs->rates : aw.rates.get<double>();
+  int32_t* states = outs->states ? outs->states : c.states.get<int32_t>();
+  uint8_t *naive = c.seqs.get<uint8_t>(), *anc = out.anc.get<uint8_t>(), *choice = out.rate_choice.get<uint8_t>();
+  uint64_t* naive_hash = c.hash.get<uint64_t>();
+  const int bits = lh::debug_options().collect_hash_bits;
+  const uint64_t mask = bits >= 64 ? ~0ull : ((1ull << bits) - 1);
+  const lh_eval_outputs fwd_outs{nullptr, nullptr, fwd, nullptr};
+  c.n_last = -1;
+  for (int off = 0; off < n; off += chunk) {
+    const int m = std::min(chunk, n - off);
+    const double* pi_m = pi + (size_t)off * 4;
+    const int32_t* ops_m = ops + (size_t)off * n_ops * 4;
+    const double* bl_m = brlen + (size_t)off * nodes;
+    double* r_m = rates + (size_t)off * R;
+    if (f->profile && f->chain_timer.begin(stream)) return 1;
+    lh::launch_model_setup(m, R, er + (size_t)off * 6, pi_m, alpha + off, r_m, eig, stream);
+    if (f->profile && f->chain_timer.mark(1, stream)) return 1;
+    const int planes = lh::launch_prune(f->host, m, R, T, max_depth, ops_m, bl_m, r_m, eig, w.prune, pi_m, site_lik, site_scal,
+                                        stream, false);
+    if (planes < 0) return fail(W + ": " + lh::prune_last_error());
+    f->k1_form = lh::prune_last_form();
+    if (planes != R && f->host.n_prune > 0) return fail(W + ": internal error (rate planes were mixed)");
+    if (f->profile && f->chain_timer.mark(2, stream)) return 1;
+    if (run_forward(f, m, planes, site_lik, site_scal, pi_m, nullptr, nullptr, outs->loglik + off, &fwd_outs, off, stream)) return 1;
+    lh::launch_sample(f->sampler, f->sampler_dev, m, fwd + (size_t)off * FS, FS, words + (size_t)off * NW, (int)NW,
+                      states + (size_t)off * NS, stream);
+    lh::launch_collect(t, m, states + (size_t)off * NS, naive + (size_t)off * L, naive_hash + off, stream);
+    LH_HIP(hipGetLastError());
+    if (f->profile && f->chain_timer.mark(3, stream)) return 1;
+    uint8_t* anc_m = anc + (size_t)off * D * n_ops * L;
+    if (lh::launch_asr(f->host, m, R, T, ops_m, bl_m, r_m, eig, pi_m, site_lik, site_scal, naive + (size_t)off * L, seed,
+                       first_sample + (uint64_t)off, aw.clv.get<double>(), aw.desc.get(), anc_m, choice + (size_t)off * D * L,
+                       w.prune.hdr, stream, D))
+      return fail(W + ": launch failed");
+    LH_HIP(hipGetLastError());
+    if (f->profile && f->chain_timer.mark(4, stream)) return 1;
+    const lh::LineageBatch g{m, T, (int32_t)L, P, anc_m, naive + (size_t)off * L, path + (size_t)off * P, mask, D};
+    lh::launch_lineage(g, outs->nt_hash + (size_t)off * D * S, outs->aa_hash + (size_t)off * D * S, stream);
+    LH_HIP(hipGetLastError());
+    if (f->profile && f->chain_timer.end(stream)) return 1;
+  }
+  if (outs->naive) LH_HIP(hipMemcpyAsync(outs->naive, naive, (size_t)n * L, hipMemcpyDeviceToDevice, stream));
+  if (outs->naive_hash)
+    LH_HIP(hipMemcpyAsync(outs->naive_hash, naive_hash, sizeof(uint64_t) * n, hipMemcpyDeviceToDevice, stream));
+  c.n_last = n;
+  f->lineage.last = lh::LineageBatch{n, T, (int32_t)L, P, anc, naive, path, mask, D};
+  return 0;
+}
+
+int lh_eval_lineage_batch(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops, const double* brlen,
+                          const double* er, const double* pi, const double* alpha, int32_t R, const uint32_t* words,
+                          uint64_t seed, uint64_t first_sample, int32_t D, const int32_t* path, int32_t P,
+                          const lh_lineage_eval_outputs* outs) {
+  const std::string W = "lh_eval_lineage_batch";
+  lh::CollectTables t;
+  if (int rc = lineage_eval_check(f, W, n, T, R, max_depth, first_sample, D, P, &t)) return rc > 0;
+  DeviceGuard guard(f);
+  if (!ops || !brlen || !er || !pi || !alpha || !words || !path || !outs || !outs->loglik || !outs->nt_hash || !outs->aa_hash)
+    return fail(W + ": null array");
+  const size_t nodes = 2 * (size_t)T - 2, n_ops = (size_t)T - 2, L = f->host.n_sites;
+  const size_t NS = t.states_per_sample, NW = f->sampler.words_per_sample;
+  for (size_t i = 0; i < (size_t)n; ++i) {
+    bool ended = false;
+    for (int s = 0; s < P; ++s) {
+      const int32_t v = path[i * P + s];
+      if (v == -1) ended = true;
+      else if (ended || v < T || v >= (int32_t)nodes) return fail(W + ": path entries are inner nodes, then -1 padding");
+    }
+    if (path[i * P] == -1) return fail(W + ": empty path");
+  }
+  HostInputs& in = f->in;
+  HostOutputs& out = f->out;
+  LineageWs& lw = f->lineage;
+  const size_t hb = sizeof(uint64_t) * n * D * (P + 1);
+  lh_lineage_eval_outputs d{};
+  if (out.loglik.ensure(sizeof(double) * n) || out_buf(outs->rates, out.rates, sizeof(double) * R * n, &d.rates) ||
+      out_buf(outs->states, out.states, sizeof(int32_t) * NS * n, &d.states) || lw.nt_hash.ensure(hb) || lw.aa_hash.ensure(hb) ||
+      stage_inputs(f, {{ops, sizeof(int32_t) * 4 * n_ops * n, &in.ops},
+                       {brlen, sizeof(double) * nodes * n, &in.brlen},
+                       {er, sizeof(double) * 6 * n, &in.er},
+                       {pi, sizeof(double) * 4 * n, &in.pi},
+                       {alpha, sizeof(double) * n, &in.alpha},
+                       {words, sizeof(uint32_t) * NW * n, &in.words},
+                       {path, sizeof(int32_t) * P * n, &lw.path}}))
+    return 1;
+  d.loglik = out.loglik.get<double>();
+  d.nt_hash = lw.nt_hash.get<uint64_t>();
+  d.aa_hash = lw.aa_hash.get<uint64_t>();
+  if (lh_eval_lineage_batch_device(f, n, T, max_depth, in.ops.get<const int32_t>(), in.brlen.get<const double>(),
+                                   in.er.get<const double>(), in.pi.get<const double>(), in.alpha.get<const double>(), R,
+                                   in.words.get<const uint32_t>(), seed, first_sample, D, lw.path.get<const int32_t>(), P, &d,
+                                   nullptr))
+    return 1;
+  // (the schedules are checked on the host beside the device, as in lh_eval_draw_batch)
+  int rc = 0;
+  if (!valid_schedules(ops, (size_t)n, T, (int)nodes, max_depth)) rc = refuse_schedules(f, W.c_str());
+  if (!rc)
+    rc = copy_back(f, W.c_str(),
+                   {{outs->loglik, d.loglik, sizeof(double) * n},
+                    {outs->rates, d.rates, sizeof(double) * R * n},
+                    {outs->states, d.states, sizeof(int32_t) * NS * n},
+                    {outs->naive, f->collect.seqs.get(), (size_t)n * L},
+                    {outs->naive_hash, f->collect.hash.get(), sizeof(uint64_t) * n},
+                    {outs->nt_hash, d.nt_hash, hb},
+                    {outs->aa_hash, d.aa_hash, hb}});
+  if (rc) {
+    lw.last.n = -1;
+    f->collect.n_last = -1;
+  }
+  return rc;
+}
+
+int lh_lineage_eval_profile_read(lh_family* f, double* ms, int64_t* n_launches) {
+  if (!f) return fail("null family");
+  DeviceGuard guard(f);
+  return f->chain_timer.read(ms, n_launches);
 }
 
 }  // extern "C"

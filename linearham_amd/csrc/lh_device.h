@@ -259,26 +259,32 @@ struct FlatRows {
 __host__ __device__ inline size_t n_slots(const FlatRows& r) { return r.n > 0 ? (size_t)r.n : 0; }
 __device__ inline const uint8_t* slot_row(const FlatRows& r, int x) { return r.seqs + (size_t)x * r.L; }
 
-// K7 (lh_lineage.hip): the lineage slots of a batch.  Slot s < P of sample i is the row anc[i][path[i*P + s] - T][0..L)
-// of K3's output (path entries outside T .. 2T-3 are padding), slot P the row naive[i][0..L).  A flat slot is i*(P+1)+s.
+// K7 (lh_lineage.hip): the lineage slots of a batch.  A batch holds n tree samples with `draws` ancestral draws each: n * draws
+// virtual samples, v standing for row v / draws and draw v % draws.  Slot s < P of virtual sample v is the row
+// anc[v][path[row*P + s] - T][0..L) of K3's output (path entries outside T .. 2T-3 are padding), slot P the row
+// naive[row][0..L), the same for every draw of the row.  A flat slot is v*(P+1)+s.
 struct LineageBatch {
   int32_t n, T, L, P;
-  const uint8_t* anc;    // [n][T-2][L]
+  const uint8_t* anc;    // [n * draws][T-2][L]
   const uint8_t* naive;  // [n][L]
   const int32_t* path;   // [n][P]
   uint64_t hash_mask;
+  int32_t draws = 1;
 };
-__host__ __device__ inline size_t n_slots(const LineageBatch& b) { return b.n > 0 ? (size_t)b.n * (b.P + 1) : 0; }
-// the row of slot (i, s), null for a padding slot
-__device__ inline const uint8_t* slot_row(const LineageBatch& b, int i, int s) {
+__host__ __device__ inline size_t n_slots(const LineageBatch& b) {
+  return b.n > 0 ? (size_t)b.n * (size_t)b.draws * (b.P + 1) : 0;
+}
+// the row of slot (v, s), null for a padding slot
+__device__ inline const uint8_t* slot_row(const LineageBatch& b, int v, int s) {
+  const int i = b.draws > 1 ? v / b.draws : v;
   if (s == b.P) return b.naive + (size_t)i * b.L;
-  const int v = b.path[(size_t)i * b.P + s];
-  if (v < b.T || v >= 2 * b.T - 2) return nullptr;
-  return b.anc + ((size_t)i * (b.T - 2) + (v - b.T)) * b.L;
+  const int node = b.path[(size_t)i * b.P + s];
+  if (node < b.T || node >= 2 * b.T - 2) return nullptr;
+  return b.anc + ((size_t)v * (b.T - 2) + (node - b.T)) * b.L;
 }
 __device__ inline const uint8_t* slot_row(const LineageBatch& b, int x) { return slot_row(b, x / (b.P + 1), x % (b.P + 1)); }
 constexpr uint64_t kLineagePadHash = 0;  // LH_LINEAGE_PAD_HASH
-// nt_hash, aa_hash [n][P+1]
+// nt_hash, aa_hash [n * draws][P+1]
 void launch_lineage(const LineageBatch& b, uint64_t* nt_hash, uint64_t* aa_hash, hipStream_t stream);
 
 // The store's kernels, instantiated for FlatRows and LineageBatch (a slot outside the batch counts as one without a row).
@@ -338,13 +344,17 @@ const char* prune_last_error();
 void launch_gtr_setup(int n, const double* er, const double* pi, double* eig, hipStream_t stream);
 
 // K3: ancestral-sequence sampling (lh_asr.hip).  site_lik / site_scal are K1's UNMIXED per-rate planes
-// (launch_prune with allow_fused = false); clv[n][T-2][2][asr_slots(L, R)][2] is scratch; anc[n][T-2][n_sites] receives the
-// sampled state of inner node T + i at every site, rate_choice[n][n_sites] the drawn category (K3a -> K3b).
-// Returns nonzero if the tree is too large for the kernel's LDS tables.
+// (launch_prune with allow_fused = false).  With `draws` = D the launch covers n * D virtual samples, v standing for tree
+// sample v / D and draw v % D: what belongs to the tree sample (ops, brlen, rates, eig, pi, hdr, the planes, naive) is
+// read at the row, what a draw owns lies at v: clv[n*D][T-2][2][asr_slots(L, R)][2] is scratch; anc[n*D][T-2][n_sites]
+// receives the sampled state of inner node T + i at every site, rate_choice[n*D][n_sites] the drawn category (K3a ->
+// K3b).  The Philox sample number of (row, d) is sample0 + row + (d << 32): draw 0 is the single draw of D = 1.
+// K3s runs once per row (desc[n]).  Returns nonzero if the tree is too large for the kernel's LDS tables.
 int launch_asr(const DevFamily& fam, int n, int R, int T, const int32_t* ops, const double* brlen, const double* rates,
                const double* eig, const double* pi, const double* site_lik, const int32_t* site_scal,
                const uint8_t* naive, uint64_t seed, uint64_t sample0, double* clv, void* desc, uint8_t* anc,
-               uint8_t* rate_choice, const int4* hdr /* K0c's verdicts, PruneWs::hdr */, hipStream_t stream);
+               uint8_t* rate_choice, const int4* hdr /* K0c's verdicts, PruneWs::hdr */, hipStream_t stream,
+               int draws = 1);
 size_t asr_desc_bytes(int T);  // per sample, of the schedule descriptors `desc` (scratch, K3s -> K3b)
 size_t asr_lds_bytes(int T, int L, int R, int n_prune);
 size_t asr_slots(int L, int R);  // slots per sample in K3's CLV area: clv[n][T-2][2][asr_slots] double2

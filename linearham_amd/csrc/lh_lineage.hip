@@ -11,6 +11,8 @@
 // of a mix of (word, position), a final mix with the length), so its bits depend on the sequence alone and a naive
 // sequence hashes here as it does there.  Padding slots get kLineagePadHash; a sample whose schedule K3 refused (0xff in
 // its anc rows) gets all-ones in every slot.
+// With D ancestral draws per tree sample (LineageBatch::draws) the batch has n * D virtual samples: anc and the hashes lie
+// at the virtual sample, path and naive at its tree sample.
 // No atomics anywhere; every output element has one writer.  Path entries are checked before they index anything.
 #include <algorithm>
 
@@ -68,8 +70,8 @@ __global__ void __launch_bounds__(kThreads)
     lineage_kernel(LineageBatch b, uint64_t* __restrict__ nt_hash, uint64_t* __restrict__ aa_hash) {
   const int lane = threadIdx.x & 63;
   const size_t x = (size_t)blockIdx.x * kSlotsPerBlock + (threadIdx.x >> 6);
-  if (x >= (size_t)b.n * (b.P + 1)) return;
-  const int i = (int)(x / (b.P + 1)), s = (int)(x % (b.P + 1));
+  if (x >= n_slots(b)) return;
+  const int i = (int)(x / (b.P + 1)), s = (int)(x % (b.P + 1));  // i: the virtual sample (tree sample, draw)
   const int L = b.L;
   const uint8_t* row = slot_row(b, i, s);
   // (K3 writes 0xff into every anc byte of a sample whose schedule it refuses; sampled states are 0..3)
@@ -115,7 +117,7 @@ __global__ void __launch_bounds__(kThreads)
 }
 
 unsigned slot_blocks(const LineageBatch& b) {
-  return (unsigned)(((size_t)b.n * (b.P + 1) + kSlotsPerBlock - 1) / kSlotsPerBlock);
+  return (unsigned)((n_slots(b) + kSlotsPerBlock - 1) / kSlotsPerBlock);
 }
 
 }  // namespace

@@ -132,10 +132,12 @@ def _parse_summary(text):
 
 
 def read_lineage(prefix):
-    """The files RunLineagePipeline / tabulate_lineage_trees write: dict(fasta = [(name, aa)] of <prefix>.fasta,
-    dnamap = {name: [(fraction, dna)]} of <prefix>.dnamap, nodes = [dict(name, kind, count, fraction)] of
-    <prefix>.nodes.tsv, edges = [dict(parent, child, count, fraction, parent_fraction, mutations = list)] of
-    <prefix>.edges.tsv, summary = {key: int} of <prefix>.summary.tsv), all in file order."""
+    """The files RunLineagePipeline / RunWeightedLineagePipeline / tabulate_lineage_trees write: dict(fasta = [(name, aa)]
+    of <prefix>.fasta, dnamap = {name: [(fraction, dna)]} of <prefix>.dnamap, nodes = [dict(name, kind, count, fraction)]
+    of <prefix>.nodes.tsv, edges = [dict(parent, child, count, fraction, parent_fraction, mutations = list)] of
+    <prefix>.edges.tsv, summary = {key: int, kish_ess: float} of <prefix>.summary.tsv), all in file order.  Counts are
+    ints, or floats in weighted tables.  With <prefix>.rows.tsv (the weighted pipeline) also rows = [dict(row, lh_loglik,
+    log_weight, weight, naive_id, path_len)]."""
     fa = open(prefix + ".fasta").read().strip("\n").split("\n")
     fasta = [(fa[i][1:], fa[i + 1]) for i in range(0, len(fa) - 1, 2)]
 
@@ -144,22 +146,37 @@ def read_lineage(prefix):
         head = lines[0].split("\t")
         return [dict(zip(head, ln.split("\t") + [""] * (len(head) - len(ln.split("\t"))))) for ln in lines[1:]]
 
-    nodes = [dict(name=d["name"], kind=d["kind"], count=int(d["count"]), fraction=float(d["fraction"]))
+    def count(text):
+        return int(text) if text.lstrip("-").isdigit() else float(text)
+
+    nodes = [dict(name=d["name"], kind=d["kind"], count=count(d["count"]), fraction=float(d["fraction"]))
              for d in table(prefix + ".nodes.tsv")]
-    edges = [dict(parent=d["parent"], child=d["child"], count=int(d["count"]), fraction=float(d["fraction"]),
+    edges = [dict(parent=d["parent"], child=d["child"], count=count(d["count"]), fraction=float(d["fraction"]),
                   parent_fraction=float(d["parent_fraction"]), mutations=d["mutations"].split())
              for d in table(prefix + ".edges.tsv")]
-    summary = {d["key"]: int(d["value"]) for d in table(prefix + ".summary.tsv")}
-    return dict(fasta=fasta, dnamap=_parse_dnamap(open(prefix + ".dnamap").read()), nodes=nodes, edges=edges,
-                summary=summary)
+    summary = {d["key"]: float(d["value"]) if d["key"] == "kish_ess" else int(d["value"])
+               for d in table(prefix + ".summary.tsv")}
+    out = dict(fasta=fasta, dnamap=_parse_dnamap(open(prefix + ".dnamap").read()), nodes=nodes, edges=edges,
+               summary=summary)
+    if os.path.exists(prefix + ".rows.tsv"):
+        out["rows"] = [dict(row=int(d["row"]), lh_loglik=float(d["lh_loglik"]), log_weight=float(d["log_weight"]),
+                            weight=float(d["weight"]), naive_id=int(d["naive_id"]), path_len=int(d["path_len"]))
+                       for d in table(prefix + ".rows.tsv")]
+    return out
 
 
-def tabulate_lineage_trees(trees_path, seed_seq, output_prefix):
+def tabulate_lineage_trees(trees_path, seed_seq, output_prefix, weights_path=None):
     """Lineage.hpp TabulateLineageTrees (tabulate_lineage_probs.py on a file PhyloHMM.run_asr wrote; no family, no
-    GPU); returns read_lineage(output_prefix)."""
+    GPU); weights_path: one log-weight per tree line (tree k counts exp(lw_k - max lw)).  Returns
+    read_lineage(output_prefix)."""
     lib = load_host()
-    lib.lhh_lineage_tabulate_trees.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p]
-    _check(lib.lhh_lineage_tabulate_trees(trees_path.encode(), seed_seq.encode(), output_prefix.encode()))
+    if weights_path is None:
+        lib.lhh_lineage_tabulate_trees.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p]
+        _check(lib.lhh_lineage_tabulate_trees(trees_path.encode(), seed_seq.encode(), output_prefix.encode()))
+    else:
+        lib.lhh_lineage_tabulate_trees_weighted.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p]
+        _check(lib.lhh_lineage_tabulate_trees_weighted(trees_path.encode(), seed_seq.encode(), output_prefix.encode(),
+                                                       weights_path.encode()))
     return read_lineage(output_prefix)
 
 
@@ -354,6 +371,17 @@ class PhyloHMM(_HMM):
         self.lib.lhh_run_lineage_pipeline.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint64]
         _check(self.lib.lhh_run_lineage_pipeline(self.h, input_path.encode(), seed_seq.encode(), output_prefix.encode(),
                                                  seed))
+        return read_lineage(output_prefix)
+
+    def run_weighted_lineage_pipeline(self, input_path, seed_seq, output_prefix, num_rates, burnin_frac=0.0,
+                                      draws_per_row=1, seed=0):
+        """PhyloHMM::RunWeightedLineagePipeline on a RevBayes table: importance-weighted lineage tables in one pass;
+        returns read_lineage(output_prefix) (with the weighted summary keys and the rows table)."""
+        self.lib.lhh_run_weighted_lineage_pipeline.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int,
+                                                               C.c_double, C.c_int, C.c_uint64]
+        _check(self.lib.lhh_run_weighted_lineage_pipeline(self.h, input_path.encode(), seed_seq.encode(),
+                                                          output_prefix.encode(), num_rates, C.c_double(burnin_frac),
+                                                          draws_per_row, seed))
         return read_lineage(output_prefix)
 
     def run_asr(self, input_path, output_path, seed):
