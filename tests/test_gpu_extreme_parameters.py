@@ -266,8 +266,8 @@ def test_asr_on_extreme_rows(hip, which):
 
 def test_batch_boundaries(hip, tmp_path):
     """Batch sizes around every boundary of lh_eval_batch with host pointers (staging sub-chunks of 12 288 through two pinned
-    slots, launch groups of 49 152): eight distinct rows cycled to n; every row's log-likelihood and rates must carry the BITS
-    of its row in the 8-row call.  The eight rows take eight of ROWS' parameter sets (those with R = 4 on unscaled branches), so
+    slots, launch groups of 49 152): eight distinct rows cycled to n; every row's log-likelihood, rates and scaler counts must
+    carry the BITS of its row in the 8-row call (the forward arrays: tests/test_gpu_batch_boundaries.py).  The eight rows take eight of ROWS' parameter sets (those with R = 4 on unscaled branches), so
     that a line left over from a neighbour shows as another number."""
     import linearham_amd
     from oracle import linearham_oracle as orc
@@ -294,13 +294,16 @@ def test_batch_boundaries(hip, tmp_path):
     er, pi = np.array([p[0] for p in par]), np.array([p[1] for p in par])
     al = np.array([float(ROWS[i][3]) for i in picked])
     assert len(set(map(tuple, pi))) + len(set(al)) > 8          # the rows are different models
-    ll8, res8 = fam.eval_batch(T, depth, ops, brl, er, pi, al, 4, want=("rates",))
+    ll8, res8 = fam.eval_batch(T, depth, ops, brl, er, pi, al, 4, want=("rates", "scaler_counts"))
     assert np.all(np.isfinite(ll8)) and len(set(ll8)) == 8
     bad = []
     for n in [1, 63, 64, 65, 6143, 6144, 6145, 12287, 12288, 12289, 24577, 49151, 49152, 49153, 61441, 98305]:
         idx = np.arange(n) % 8
-        ll, res = fam.eval_batch(T, depth, ops[idx], brl[idx], er[idx], pi[idx], al[idx], 4, want=("rates",))
+        ll, res = fam.eval_batch(T, depth, ops[idx], brl[idx], er[idx], pi[idx], al[idx], 4, want=("rates", "scaler_counts"))
         if not (np.array_equal(ll, ll8[idx]) and np.array_equal(res["rates"], res8["rates"][idx])):
             bad.append((n, np.nonzero(ll != ll8[idx])[0][:8].tolist()))
+        sc = (res["scaler_counts"] != res8["scaler_counts"][idx]).any(axis=1)
+        if sc.any():
+            bad.append((n, "scaler_counts", np.nonzero(sc)[0][:8].tolist()))
     fam.close()
     assert not bad, bad
