@@ -150,6 +150,18 @@ int lh_family_consensus_sets(const lh_family* fam);
  * oracle.  The string lives as long as the handle and changes with the next evaluation. */
 const char* lh_family_prune_form(const lh_family* fam);
 
+/* Diagnostic: the K2 kernels the handle's last forward sweep ran (every entry point that evaluates, lh_forward_batch
+ * included), as "emission<slots,site|caller,byte|index[,ext][,lem]> cons=<sets> small=wave|block | <K2b kernels>" --
+ * e.g. "emission<1,site,byte> cons=2 small=wave | vd2<4>+dj" -- or "" before the first one.  K2a: gene slots per thread,
+ * emissions from the site likelihoods or from the caller, column byte offsets or indices, extended-range mode, log
+ * emissions requested; the sets it runs in consensus form (bits as lh_family_consensus_sets; 0 in the extended-range
+ * mode) and whether the small sets (D, J, J padding) walk a wave each or on the whole workgroup -- both for a sample
+ * whose emissions all lie in (0, 1]; any other sample walks every set factor by factor.  K2b: "vd2<GA>+dj" (two
+ * samples per wave on both junctions), "vd<GA>+dj" (one sample per V-D wave: more than 256 V alleles) or
+ * "junction<GA,GB>" (one wave per sample: light chains, more than 32 D or J alleles); GA, GB = 64-gene register
+ * chunks of the V side and of the D / J sides.  Lives and changes like lh_family_prune_form's string. */
+const char* lh_family_forward_form(const lh_family* fam);
+
 /* Opt-in extended-range mode (default off = the reference's arithmetic, overflows included).  The reference
  * loses a tree sample in two places: exp(lnL - log pi) underflows to 0 when a column's likelihood is below
  * 1e-308 (src/PhyloHMM.cpp:237), and the 2^(256 d) equalisation of a region's emission products to the LARGEST

@@ -282,6 +282,7 @@ struct lh_family {
   int32_t n_ucol_used = 0;  // (naive base, pattern) pairs some xMSA column has (lh_family_info)
   int32_t* err_flag = nullptr;  // device word (arena): K0c sets it when a schedule is malformed (lh_family_status)
   std::string k1_form;          // the K1 kernel form of the last evaluation (lh_family_prune_form)
+  std::string k2_form;          // the K2 kernels of the last forward sweep (lh_family_forward_form)
 };
 
 namespace {
@@ -591,6 +592,7 @@ int run_forward(lh_family* f, int n, int R, const double* site_lik, const int32_
   lh::launch_forward(f->host, f->dev, n, R, site_lik, site_scal, pi, em_in, em_out, w.gem.get<double>(), w.gcnt.get<int32_t>(),
                      w.jem.get<double>(), w.jrs.get<int32_t>(), w.dxf.get<double>(), w.dxc.get<int32_t>(), loglik_dev, fwd, sco,
                      f->extended, stream, lem);
+  f->k2_form = lh::forward_last_form();
   LH_HIP(hipGetLastError());
   return 0;
 }
@@ -1029,6 +1031,8 @@ void lh_family_destroy(lh_family* f) {
 int64_t lh_forward_size(const lh_family* f) { return f ? f->host.forward_size : 0; }
 
 const char* lh_family_prune_form(const lh_family* f) { return f ? f->k1_form.c_str() : ""; }
+
+const char* lh_family_forward_form(const lh_family* f) { return f ? f->k2_form.c_str() : ""; }
 
 int lh_family_consensus_sets(const lh_family* f) {
   if (!f) return 0;

@@ -381,6 +381,11 @@ void launch_forward(const DevFamily& fam, const DevFamily* fam_dev, int n, int R
                     int32_t* jrs, double* dxf, int32_t* dxc, double* loglik, double* forward_out, int32_t* scaler_out,
                     bool extended, hipStream_t stream, const LogEmRequest& lem = LogEmRequest{});
 size_t forward_lds_bytes(const DevFamily& fam);
+// what the calling thread's last launch_forward ran: "emission<1,site,byte> cons=2 small=wave | vd2<4>+dj" -- K2a's
+// instantiation <gene slots per thread, site likelihoods or caller's emissions, byte offsets or indices[, ext][, lem]>,
+// the sets it runs in consensus form (bits as lh_family_consensus_sets), whether the small sets walk a wave each
+// (fill_segments_wave) or on the whole block, and K2b's kernels: vd2<GA>+dj, vd<GA>+dj or junction<GA,GB>
+const char* forward_last_form();
 
 // Every environment switch of the device library in one place: hooks that tests/ use to push a family onto a kernel
 // form another shape takes by itself (timing experiments are built from a copy of csrc/, tools/build_asm_variant.sh);

@@ -41,6 +41,9 @@ constexpr int kFwdThreads = 256;
 constexpr int kFwdWaves = kFwdThreads / 64;
 constexpr int kJunctionWaves = 4;  // samples per K2b workgroup
 
+// what the calling thread's last launch_forward ran (forward_last_form): the launchers below write the two halves
+thread_local char g_k2a_form[64] = "", g_k2b_form[32] = "", g_forward_form[160] = "";
+
 // Block-wide maximum: shuffles inside the wave, one LDS exchange, one barrier (red holds
 // 2 * kFwdWaves ints; `phase` alternates its halves so that a reduction never overwrites values
 // another wave is still reading).
@@ -264,6 +267,14 @@ __host__ __device__ static inline int cons_capacity(const DevFamily& fam) {
   m = m > fam.jgerm.cons_sites ? m : fam.jgerm.cons_sites;
   m = m > fam.jpadding.cons_sites ? m : fam.jpadding.cons_sites;
   return m > 0 ? (m + 3) & ~1 : 0;
+}
+
+// Whether K2a walks the small sets (D, J, J padding; light chains: J, J padding) a wave each, side by side
+// (fill_segments_wave): never in the extended-range mode, and only when none of them is in consensus form -- or the
+// sample has left that form (`direct`: an emission outside (0, 1]).
+__host__ __device__ static inline bool small_sets_by_wave(const DevFamily& fam, bool ext, bool direct) {
+  return !ext && fam.dgerm.n_genes <= 64 && fam.jgerm.n_genes <= 64 &&
+         (direct || (fam.dgerm.cons_sites == 0 && fam.jgerm.cons_sites == 0 && fam.jpadding.cons_sites == 0));
 }
 
 // (v, k) = the reference's running product after ScaleMatrix: value v * 2^(-256 k), v kept in [2^-256, 1]
@@ -588,8 +599,7 @@ __global__ void __launch_bounds__(kFwdThreads) __attribute__((amdgpu_num_sgpr(80
   int cv = fill(fam.vpadding, gem, 0);
   cv += fill(fam.vgerm, gem + nV, 1);
   int cd = 0, cj;
-  if (!kExt && nD <= 64 && nJ <= 64 &&
-      (direct || (fam.dgerm.cons_sites == 0 && fam.jgerm.cons_sites == 0 && fam.jpadding.cons_sites == 0))) {
+  if (small_sets_by_wave(fam, kExt, direct)) {
     // the small sets (D, J, J padding; light chains: J, J padding), a wave each, side by side (fill_segments_wave);
     // the counts meet in LDS
     const int wave = tid >> 6, lane = tid & 63;
@@ -1646,6 +1656,8 @@ static void launch_emission_l(const DevFamily& fam, const DevFamily* fam_dev, in
                               double* gem, int32_t* gcnt, double* jem, int32_t* jrs, const LogEmRequest& lem,
                               hipStream_t stream) {
   const size_t lds = emission_lds_bytes(fam, kExt);
+  snprintf(g_k2a_form, sizeof(g_k2a_form), "emission<%d,%s,%s%s%s>", kG, kSite ? "site" : "caller",
+           kByteOff ? "byte" : "index", kExt ? ",ext" : "", kLem ? ",lem" : "");
   if (lds > 64 * 1024)
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(emission_kernel<kG, kSite, kByteOff, kExt, kLem>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -1713,6 +1725,7 @@ static void launch_junction_g(const DevFamily& fam, int n, const double* gem, co
     if (!vd_single && GA <= 4) {  // (beyond 256 V alleles the second sample's left-gene registers no longer fit)
       const size_t lds_vd2 = ((size_t)2 * kVdPairWaves * (fam.n_jcols + 1) + 16 * (size_t)fam.vd.right_pad) * sizeof(double);
       const dim3 grid_vd2(((n + 1) / 2 + kVdPairWaves - 1) / kVdPairWaves);
+      snprintf(g_k2b_form, sizeof(g_k2b_form), "vd2<%d>+dj", GA);
 #define LH_PAIR2_LAUNCH(E)                                                                                            \
   {                                                                                                                   \
     if (lds_vd2 > 64 * 1024)                                                                                          \
@@ -1733,6 +1746,7 @@ static void launch_junction_g(const DevFamily& fam, int n, const double* gem, co
 #undef LH_PAIR2_LAUNCH
       return;
     }
+    snprintf(g_k2b_form, sizeof(g_k2b_form), "vd<%d>+dj", GA);
 #define LH_PAIR_LAUNCH(E)                                                                                             \
   {                                                                                                                   \
     if (lds_vd > 64 * 1024)                                                                                           \
@@ -1755,6 +1769,7 @@ static void launch_junction_g(const DevFamily& fam, int n, const double* gem, co
   }
   const size_t lds = junction_lds_bytes(fam);
   const dim3 grid((n + kJunctionWaves - 1) / kJunctionWaves), block(64 * kJunctionWaves);
+  snprintf(g_k2b_form, sizeof(g_k2b_form), "junction<%d,%d>", GA, GB);
   if (ext) {
     if (lds > 64 * 1024)
       (void)hipFuncSetAttribute(reinterpret_cast<const void*>(junction_kernel<GA, GB, true>),
@@ -1815,6 +1830,16 @@ void launch_forward(const DevFamily& fam, const DevFamily* fam_dev, int n, int R
   else
     launch_junction_a<16>(LH_ARGS);
 #undef LH_ARGS
+  // the sets K2a runs in consensus form (bits as lh_family_consensus_sets; none in the extended-range mode, which
+  // walks every set with its counts) and how it walks the small ones -- for a sample whose emissions all lie in
+  // (0, 1]; any other sample walks every set factor by factor (emission_kernel, em_bad)
+  const int cons = ext ? 0
+                       : (fam.vpadding.cons_sites > 0) | (fam.vgerm.cons_sites > 0) << 1 | (fam.dgerm.cons_sites > 0) << 2 |
+                             (fam.jgerm.cons_sites > 0) << 3 | (fam.jpadding.cons_sites > 0) << 4;
+  snprintf(g_forward_form, sizeof(g_forward_form), "%s cons=%d small=%s | %s", g_k2a_form, cons,
+           small_sets_by_wave(fam, ext, false) ? "wave" : "block", g_k2b_form);
 }
+
+const char* forward_last_form() { return g_forward_form; }
 
 }  // namespace lh
