@@ -521,6 +521,52 @@ int lh_profile_read(lh_family* fam, double* ms_model, double* ms_prune, double* 
  * enabled (HIP events on the launch stream); resets the counters. */
 int lh_asr_profile_read(lh_family* fam, double* ms_sampling, int64_t* n_launches);
 
+/* ---- K8: the most probable state path (Viterbi), exact annotation probabilities ----
+ * The max-product counterpart of the forward sweep: per tree sample the most probable V(D)J state path a* given the
+ * data and the tree, and log P(data, a* | t).  Needs lh_family_set_sampler (the path is written in K4's layout).
+ *   log_offset   [n]      as in lh_posterior_outputs; may be NULL
+ *   loglik       [n]      the sample's log-likelihood (may be NULL)
+ *   states       [n][lh_sample_states()]  the path in lh_eval_sample_batch's layout and encoding: J gene | D-J rows |
+ *                         D gene | V-D rows | V gene, dense state indices (may be NULL)
+ *   log_path     [n]      log P(data, a* | t); log_path - loglik <= 0 is the path's posterior given the tree (may be NULL)
+ *   weight_stats [3]      max lw, sum w_i, sum w_i^2 as in lh_posterior_outputs; may be NULL
+ * A sample whose log-likelihood is NaN or +inf in the active range mode, or whose schedule the device rejected (which
+ * raises the handle's error word as everywhere else), gets states = -1 and log_path = NaN.  A sample no path of which
+ * has positive probability (log-likelihood -inf) gets states = -1 and log_path = -inf.
+ * Ties are broken by the values alone, so a row's result does not depend on its place in a batch or on the range mode:
+ * the lowest left gene in a junction's cross-gene term; among a state's predecessors the cross-gene term before the
+ * gene's own NTI states A, C, G, T before its own previous germline position; the lowest gene of the last J vector. */
+typedef struct {
+  const double* log_offset;
+  double* loglik;
+  int32_t* states;
+  double* log_path;
+  double* weight_stats;
+} lh_viterbi_outputs;
+
+/* Host pointers. */
+int lh_eval_viterbi_batch(lh_family* fam, int32_t n, int32_t n_tips, int32_t max_depth, const int32_t* ops,
+                          const double* brlen, const double* er, const double* pi, const double* alpha,
+                          int32_t num_rates, const lh_viterbi_outputs* outs);
+/* Every array resident on the handle's device; enqueued on `hip_stream` without synchronising. */
+int lh_eval_viterbi_batch_device(lh_family* fam, int32_t n, int32_t n_tips, int32_t max_depth, const int32_t* ops,
+                                 const double* brlen, const double* er, const double* pi, const double* alpha,
+                                 int32_t num_rates, const lh_viterbi_outputs* outs, void* hip_stream);
+
+/* K8 on caller-supplied per-column emissions em[n][C] (host pointers), beside lh_forward_batch:
+ * log_path[n] and states[n][lh_sample_states()] (either may be NULL). */
+int lh_viterbi_forward_batch(lh_family* fam, int32_t n, const double* em, double* log_path, int32_t* states);
+
+/* Registers K state paths states[K][lh_sample_states()] as the handle's candidates, in the slot lh_family_set_candidates
+ * fills: their naive sequences (K6c) with log P_HMM(a_k) -- the path's weight with every emission 1, returned in
+ * log_prior[K] (may be NULL) -- as the candidates' priors.  lh_eval_candidates_batch[_device] then returns
+ * log P(a_k | data, t_i) and the weighted sums.  A vector that is not a path of the model (an index out of range, a
+ * transition of probability 0) is refused and leaves the handle without candidates. */
+int lh_family_set_candidate_paths(lh_family* fam, int32_t K, const int32_t* states, double* log_prior);
+
+/* Time of K8 over the lh_eval_viterbi_batch[_device] launch groups made while profiling was enabled. */
+int lh_viterbi_profile_read(lh_family* fam, double* ms, int64_t* n_launches);
+
 #ifdef __cplusplus
 }
 #endif

@@ -65,6 +65,32 @@ LINEAGE_PAD_HASH = 0  # LH_LINEAGE_PAD_HASH
 # the chain: evaluation, naive draw, D ancestral draws and lineage hashes in one pass
 LINEAGE_EVAL_EXPORTS = ["lh_eval_lineage_batch", "lh_eval_lineage_batch_device", "lh_lineage_eval_profile_read"]
 EXPORTS += LINEAGE_EVAL_EXPORTS
+# K8 (the most probable state path, candidate paths)
+VITERBI_EXPORTS = ["lh_eval_viterbi_batch", "lh_eval_viterbi_batch_device", "lh_viterbi_forward_batch",
+                   "lh_family_set_candidate_paths", "lh_viterbi_profile_read"]
+EXPORTS += VITERBI_EXPORTS
+
+
+class _ViterbiOutputs(C.Structure):
+    _fields_ = [("log_offset", c_f64p), ("loglik", c_f64p), ("states", c_i32p), ("log_path", c_f64p),
+                ("weight_stats", c_f64p)]
+
+
+class _ViterbiOutputsDevice(C.Structure):  # the same members as device addresses
+    _fields_ = [(k, C.c_void_p) for k in ("log_offset", "loglik", "states", "log_path", "weight_stats")]
+
+
+class _SamplerJunction(C.Structure):
+    _fields_ = [("n_rows", C.c_int32), ("n_left", C.c_int32), ("n_right", C.c_int32), ("n_states", C.c_int32),
+                ("left_rows", c_i32p), ("left_dense", c_i32p), ("left_lo", c_f64p), ("left_trans", c_f64p),
+                ("enter_lo", c_f64p), ("right_dense", c_i32p), ("right_first", c_i32p), ("gene_prob", c_f64p),
+                ("nti_landing_in", c_f64p), ("nti_transition", c_f64p), ("nti_landing_out", c_f64p),
+                ("landing_in", c_f64p), ("right_trans", c_f64p), ("exit_nlo", c_f64p), ("exit_trans", c_f64p),
+                ("exit_li", c_f64p), ("prod", c_f64p)]
+
+
+class _SamplerDesc(C.Structure):
+    _fields_ = [("vd", _SamplerJunction), ("dj", _SamplerJunction)]
 
 
 class _PosteriorOutputs(C.Structure):
@@ -187,6 +213,15 @@ class HipLibrary:
                 [C.c_void_p] * 5 + [C.c_int32, C.c_void_p, C.c_uint64, C.c_uint64, C.c_int32, C.c_void_p, C.c_int32,
                                     C.POINTER(_LineageEvalOutputsDevice), C.c_void_p]
             lib.lh_lineage_eval_profile_read.argtypes = [C.c_void_p, c_f64p, C.POINTER(C.c_int64)]
+        if hasattr(lib, "lh_eval_viterbi_batch"):
+            lib.lh_family_set_sampler.argtypes = [C.c_void_p, C.POINTER(_SamplerDesc)]
+            lib.lh_eval_viterbi_batch.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, c_i32p, c_f64p, c_f64p,
+                                                  c_f64p, c_f64p, C.c_int32, C.POINTER(_ViterbiOutputs)]
+            lib.lh_eval_viterbi_batch_device.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + \
+                [C.c_void_p] * 5 + [C.c_int32, C.POINTER(_ViterbiOutputsDevice), C.c_void_p]
+            lib.lh_viterbi_forward_batch.argtypes = [C.c_void_p, C.c_int32, c_f64p, c_f64p, c_i32p]
+            lib.lh_family_set_candidate_paths.argtypes = [C.c_void_p, C.c_int32, c_i32p, c_f64p]
+            lib.lh_viterbi_profile_read.argtypes = [C.c_void_p, c_f64p, C.POINTER(C.c_int64)]
         if hasattr(lib, "lh_set_device"):      # (absent from round-2 builds loaded through LH_LIB_DIR for comparisons)
             lib.lh_set_device.argtypes = [C.c_int32]
             lib.lh_family_status.argtypes = [C.c_void_p]
@@ -307,6 +342,75 @@ class HipLibrary:
         ms, k = (C.c_double * 2)(), C.c_int64()
         self.check(self.lib.lh_candidates_profile_read(h, ms, C.byref(k)))
         return ms[0], ms[1], k.value
+
+    # ---- K8: the most probable state path, candidate paths ----
+    def sample_states(self, family):
+        """ints per sample of a state path in K4's layout (lh_sample_states; 0 without sampler tables)."""
+        h = family.handle if isinstance(family, Family) else family
+        return int(self.lib.lh_sample_states(h))
+
+    def eval_viterbi_batch(self, family, n_tips, max_depth, ops, brlen, er, pi, alpha, num_rates, log_offset=None,
+                           want=("loglik", "states", "log_path")):
+        """K0-K2 + K8 on a handle with sampler tables.  Returns a dict with the members of `want`: loglik [n], states
+        [n, lh_sample_states] (the most probable state path in K4's layout; -1 where there is none), log_path [n]
+        (log P(data, path | tree)), weight_stats [3]."""
+        h = family.handle if isinstance(family, Family) else family
+        ops = np.ascontiguousarray(ops, dtype=np.int32)
+        n = ops.shape[0]
+        brlen, er, pi, alpha = _f64(brlen), _f64(er), _f64(pi), _f64(alpha)
+        if ops.ndim != 3 or any(np.asarray(a).shape[0] != n for a in (brlen, er, pi, alpha)) or \
+                (log_offset is not None and np.asarray(log_offset).shape != (n,)):
+            raise ValueError("lh_eval_viterbi_batch: the per-row arrays must all have n rows")
+        shapes = {"loglik": ((n,), np.float64), "states": ((n, self.sample_states(h)), np.int32),
+                  "log_path": ((n,), np.float64), "weight_stats": ((3,), np.float64)}
+        res = {k: np.zeros(shapes[k][0], dtype=shapes[k][1]) for k in want}
+        lo = None if log_offset is None else _f64(log_offset)
+
+        def ptr(a, t=c_f64p):
+            return a.ctypes.data_as(t) if a is not None else None
+        outs = _ViterbiOutputs(ptr(lo), ptr(res.get("loglik")), ptr(res.get("states"), c_i32p), ptr(res.get("log_path")),
+                               ptr(res.get("weight_stats")))
+        self.check(self.lib.lh_eval_viterbi_batch(h, n, n_tips, max_depth, ops.ctypes.data_as(c_i32p), ptr(brlen),
+                                                  ptr(er), ptr(pi), ptr(alpha), num_rates, C.byref(outs)))
+        return res
+
+    def eval_viterbi_batch_device(self, family, n, n_tips, max_depth, ops_ptr, brlen_ptr, er_ptr, pi_ptr, alpha_ptr,
+                                  num_rates, outs, stream=0):
+        """lh_eval_viterbi_batch_device on device addresses; outs: dict of the output members' addresses."""
+        h = family.handle if isinstance(family, Family) else family
+        o = _ViterbiOutputsDevice(**{k: int(v) for k, v in outs.items() if v})
+        self.check(self.lib.lh_eval_viterbi_batch_device(h, n, n_tips, max_depth, ops_ptr, brlen_ptr, er_ptr, pi_ptr,
+                                                         alpha_ptr, num_rates, C.byref(o), stream))
+
+    def viterbi_forward_batch(self, family, em):
+        """K2a + K8 on caller emissions em [n][C]: (log_path [n], states [n, lh_sample_states])."""
+        h = family.handle if isinstance(family, Family) else family
+        em = _f64(em)
+        n = em.shape[0]
+        lp = np.zeros(n)
+        st = np.zeros((n, self.sample_states(h)), dtype=np.int32)
+        self.check(self.lib.lh_viterbi_forward_batch(h, n, em.ctypes.data_as(c_f64p), lp.ctypes.data_as(c_f64p),
+                                                     st.ctypes.data_as(c_i32p)))
+        return lp, st
+
+    def set_candidate_paths(self, family, states):
+        """Registers state paths states [K][lh_sample_states] as the handle's candidates (their naive sequences, with
+        the paths' HMM priors) and returns log P_HMM(a_k) [K]; eval_candidates_batch then scores the paths."""
+        h = family.handle if isinstance(family, Family) else family
+        states = np.ascontiguousarray(states, dtype=np.int32)
+        if states.ndim != 2 or states.shape[0] < 1 or states.shape[1] != self.sample_states(h):
+            raise ValueError("lh_family_set_candidate_paths: paths must be a non-empty [K][lh_sample_states] array")
+        out = np.zeros(states.shape[0])
+        self.check(self.lib.lh_family_set_candidate_paths(h, states.shape[0], states.ctypes.data_as(c_i32p),
+                                                          out.ctypes.data_as(c_f64p)))
+        return out
+
+    def viterbi_profile_read(self, family):
+        """(K8 ms, launch groups) since the last read."""
+        h = family.handle if isinstance(family, Family) else family
+        ms, k = C.c_double(), C.c_int64()
+        self.check(self.lib.lh_viterbi_profile_read(h, C.byref(ms), C.byref(k)))
+        return ms.value, k.value
 
     # ---- K6c: naive sequences of sampled states and the candidate store ----
     def naive_sequences(self, family, states):
@@ -431,6 +535,29 @@ class JunctionTables:
     def c(self):
         j = _Junction()
         j.n_rows, j.n_left, j.n_right = self.n_rows, self.n_left, self.n_right
+        for k in self.F64:
+            setattr(j, k, getattr(self, k).ctypes.data_as(c_f64p))
+        for k in self.I32:
+            setattr(j, k, getattr(self, k).ctypes.data_as(c_i32p))
+        return j
+
+
+class SamplerJunction:
+    """Host-side arrays of lh_sampler_junction (keeps the numpy buffers alive)."""
+    F64 = ["left_lo", "left_trans", "enter_lo", "gene_prob", "nti_landing_in", "nti_transition", "nti_landing_out",
+           "landing_in", "right_trans", "exit_nlo", "exit_trans", "exit_li", "prod"]
+    I32 = ["left_rows", "left_dense", "right_dense", "right_first"]
+
+    def __init__(self, n_rows, n_left, n_right, n_states, **arrays):
+        self.n_rows, self.n_left, self.n_right, self.n_states = n_rows, n_left, n_right, n_states
+        for k in self.F64:
+            setattr(self, k, _f64(arrays[k]))
+        for k in self.I32:
+            setattr(self, k, _i32(arrays[k]))
+
+    def c(self):
+        j = _SamplerJunction()
+        j.n_rows, j.n_left, j.n_right, j.n_states = self.n_rows, self.n_left, self.n_right, self.n_states
         for k in self.F64:
             setattr(j, k, getattr(self, k).ctypes.data_as(c_f64p))
         for k in self.I32:
@@ -710,6 +837,19 @@ class Family:
 
     def set_extended_range(self, on=True):
         self.hip.check(self.hip.lib.lh_family_set_extended_range(self.handle, int(on)))
+
+    def set_sampler(self, vd, dj=None):
+        """lh_family_set_sampler from SamplerJunction tables (dj: igh only)."""
+        d = _SamplerDesc()
+        d.vd = vd.c()
+        if dj is not None:
+            d.dj = dj.c()
+        self.hip.check(self.hip.lib.lh_family_set_sampler(self.handle, C.byref(d)))
+
+    def viterbi_forward_batch(self, em):
+        """(log_path [n], states [n][S]) of caller emissions em [n][C] (set_sampler first)."""
+        assert _f64(em).shape[1] == self.n_xmsa
+        return self.hip.viterbi_forward_batch(self.handle, em)
 
     def profile_enable(self, on=True):
         self.hip.check(self.hip.lib.lh_profile_enable(self.handle, int(on)))

@@ -790,6 +790,28 @@ HMM::SamplerJunction HMM::BuildSamplerJunction(const RegionStates& J, const Regi
   return t;
 }
 
+bool HMM::RegisterDeviceSampler(lh_family* family) const {
+  const bool igh = locus_ == "igh";
+  SamplerJunction svd, sdj;
+  lh_sampler_desc sd{};
+  if (igh) {
+    svd = BuildSamplerJunction(vd_junction_, vgerm_, dgerm_, flexbounds_.at("v_r"), flexbounds_.at("d_l"));
+    sdj = BuildSamplerJunction(dj_junction_, dgerm_, jgerm_, flexbounds_.at("d_r"), flexbounds_.at("j_l"));
+    sd.dj = sdj.c();
+  } else {
+    svd = BuildSamplerJunction(vd_junction_, vgerm_, jgerm_, flexbounds_.at("v_r"), flexbounds_.at("j_l"));
+  }
+  sd.vd = svd.c();
+  return lh_family_set_sampler(family, &sd) == 0;
+}
+
+std::vector<int32_t> HMM::ViterbiStates(int n, const double* em, double* log_path) const {
+  Require(family_ != nullptr && lh_sample_states(family_) > 0, "ViterbiStates: the family has no device sampler tables");
+  std::vector<int32_t> states((std::size_t)std::max(n, 0) * (std::size_t)lh_sample_states(family_));
+  CheckHip(lh_viterbi_forward_batch(family_, n, em, log_path, states.data()), "lh_viterbi_forward_batch");
+  return states;
+}
+
 namespace {
 
 // What SampleJunctionStates (src/HMM.cpp:1222-1278) does with the drawn states, in its order (last row first).

@@ -149,6 +149,10 @@ class HMM {
   };
   SamplerJunction BuildSamplerJunction(const RegionStates& J, const RegionStates& G_left, const RegionStates& G_right,
                                        std::pair<int, int> left_fb, std::pair<int, int> right_fb) const;
+  /// K8 on caller emissions (lh_viterbi_forward_batch): the most probable state path of each of the n emission vectors
+  /// em[n][columns of the family], in ApplySampledStates' layout (-1: no path), and log P(data, path) in log_path[n]
+  /// (may be null).  The family must exist and have its sampler tables.
+  std::vector<int32_t> ViterbiStates(int n, const double* em, double* log_path) const;
 
  protected:
   /// Runs the device forward pass if needed (pure virtual: the derived class knows how the
@@ -156,6 +160,9 @@ class HMM {
   virtual void RunForwardAlgorithm() = 0;
   void UnpackForward(const double* fwd, const int32_t* sco);
   void SampleInitialState();
+  /// Builds the junctions' sampler tables and registers them on `family` (lh_family_set_sampler); false if the library
+  /// refuses them (genes that do not form two blocks of a junction's state vector).
+  bool RegisterDeviceSampler(lh_family* family) const;
 
   /// Structured junction tables for the C ABI. `xmsa_inds` is the W x S index matrix of the junction
   /// (row-major), or empty when the caller fills the *_xmsa arrays itself.

@@ -408,6 +408,29 @@ std::vector<double> PhyloHMM::NaivePosterior(double* loglik) {
   return post;
 }
 
+HMM::RowSampler PhyloHMM::ViterbiAnnotation(double* log_path, double* loglik) {
+  Require(have_tree_, "InitializePhyloParameters must be called first");
+  CreateFamily();
+  Require(device_sampler_, "the family has no device sampler tables (needed by the Viterbi kernel)");
+  const int T = tree_.n_tips;
+  std::vector<int32_t> ops((std::size_t)(T - 2) * 4);
+  int32_t depth = 0;
+  CheckHip(lh_schedule_tree(T, tree_.children.data(), tree_.root, ops.data(), &depth), "lh_schedule_tree");
+  std::vector<int32_t> states(lh_sample_states(family_));
+  double lp = 0, ll = 0;
+  lh_viterbi_outputs outs{nullptr, &ll, states.data(), &lp, nullptr};
+  CheckHip(lh_eval_viterbi_batch(family_, 1, T, depth, ops.data(), tree_.brlen.data(), er_.data(), pi_.data(), &alpha_,
+                                 num_rates_, &outs),
+           "lh_eval_viterbi_batch");
+  Require(std::isfinite(ll), "ViterbiAnnotation: the log-likelihood is not finite");
+  Require(states[0] >= 0, "ViterbiAnnotation: no state path has positive probability");
+  if (log_path) *log_path = lp;
+  if (loglik) *loglik = ll;
+  RowSampler s;
+  ApplySampledStates(s, states.data());
+  return s;
+}
+
 // One walk over the compact posterior layout (lh_eval_outputs.forward: V | V-D rows | D | D-J rows | J): calls
 // germ(region letter, gene name, index in the region, value, region) for every germline-region gene and
 // junc(junction, row, dense state, site, naive base, value) for every junction state.  (Dense state posteriors in the
@@ -568,6 +591,11 @@ void PhyloHMM::FormatOutputLine(std::string& o, int iteration, double rb_loglike
   o.push_back('\t');
   AppendG(o, lh_loglikelihood - rb_loglikelihood);
   o.push_back('\t');
+  AppendAnnotationColumns(o, s);
+  o.push_back('\n');
+}
+
+void PhyloHMM::AppendAnnotationColumns(std::string& o, const RowSampler& s) const {
   o += s.naive_seq;
   o.push_back('\t');
   o += s.vgerm_state_str;
@@ -597,7 +625,12 @@ void PhyloHMM::FormatOutputLine(std::string& o, int iteration, double rb_loglike
   AppendInt(o, s.jgerm_right_del);
   o.push_back('\t');
   o += s.jgerm_right_insertion;
-  o.push_back('\n');
+}
+
+std::string PhyloHMM::AnnotationHeader() const {
+  std::string h = "NaiveSequence\tVGene\tV5pDel\tV3pDel\tVFwkInsertion\t";
+  h += locus_ == "igh" ? "VDInsertion\tDGene\tD5pDel\tD3pDel\tDJInsertion\t" : "VJInsertion\t";
+  return h + "JGene\tJ5pDel\tJ3pDel\tJFwkInsertion";
 }
 
 // src/PhyloHMM.cpp:288-327
@@ -2098,6 +2131,171 @@ void PhyloHMM::RunNaiveProbsPipeline(const std::string& input_path, const std::s
   summary << "key\tvalue\nrows_used\t" << (U - skipped) << "\nrows_skipped_nonfinite\t" << skipped << "\nkish_ess\t" << buf
           << "\ndraws_distinct\t" << (draws_distinct < 0 ? std::string("NA") : std::to_string(draws_distinct))
           << "\ncandidates\t" << K << "\ncandidates_dropped\t" << dropped << "\ncovered_mass\t" << cov << "\n";
+}
+
+// Pass 1: K8 per batch; the host interns the rows' state vectors.  Pass 2: the kept paths are registered as candidates
+// with their path priors and scored on every row by K6b; the host adds w_i exp(log_cand[i][k]) up in row order against the
+// largest log-weight of the whole table (known from pass 1), so no sum depends on how the table was cut into batches.
+void PhyloHMM::RunAnnotationsPipeline(const std::string& input_path, const std::string& output_prefix, int num_rates,
+                                      double burnin_frac, int max_candidates) {
+  Require(devices_.size() <= 1, "the annotations pipeline runs on one device: --devices may list only one");
+  Require(burnin_frac >= 0.0 && burnin_frac < 1.0, "burn-in fraction must be in [0, 1)");
+  Require(max_candidates >= 1 && max_candidates <= 65536, "max-candidates must be in 1 .. 65536");
+  CreateFamily();
+  Require(device_sampler_, "the family has no device sampler tables (needed by the Viterbi kernel)");
+  TsvTable table = TsvTable::OpenRevBayesTable(input_path);
+  const std::size_t N = table.rows.size();
+  const std::size_t first = (std::size_t)std::floor(burnin_frac * (double)N);
+  const std::size_t U = N - first;  // rows after the burn-in
+  const std::size_t S = (std::size_t)lh_sample_states(family_);
+  const std::size_t kBatch = host_options().pipeline_batch > 0 ? (std::size_t)host_options().pipeline_batch : 49152;
+
+  // pass 1
+  std::vector<double> ll1(U), lw(U), post(U);
+  std::vector<int32_t> row_path(U, -1);            // the row's MAP path by first appearance (-1: skipped row)
+  std::vector<std::vector<int32_t>> paths;         // distinct paths in first-appearance order
+  std::unordered_map<std::string, int32_t> ids;    // by the bytes of the state vector
+  std::size_t skipped = 0;
+  for (std::size_t off = first; off < N; off += kBatch) {
+    const std::size_t m = std::min(kBatch, N - off);
+    TableBatch tb = FlattenTable(table, off, off + m, false, true, input_path);
+    const DeviceBatch& b = tb.dev;
+    std::vector<int32_t> states(m * S);
+    std::vector<double> lp(m);
+    lh_viterbi_outputs outs{nullptr, ll1.data() + (off - first), states.data(), lp.data(), nullptr};
+    CheckHip(lh_eval_viterbi_batch(family_, b.n, b.n_tips, b.max_depth, b.ops.data(), b.brlen.data(), b.er.data(),
+                                   b.pi.data(), b.alpha.data(), num_rates, &outs),
+             "lh_eval_viterbi_batch");
+    for (std::size_t i = 0; i < m; ++i) {
+      const std::size_t u = off - first + i;
+      lw[u] = ll1[u] - tb.lik[i];
+      post[u] = lp[i] - ll1[u];
+      if (!std::isfinite(lw[u]) || states[i * S] < 0) {  // (no path without a finite log-likelihood, and the reverse)
+        ++skipped;
+        continue;
+      }
+      const std::string key(reinterpret_cast<const char*>(states.data() + i * S), S * sizeof(int32_t));
+      const auto r = ids.emplace(key, (int32_t)paths.size());
+      if (r.second) paths.emplace_back(states.begin() + i * S, states.begin() + (i + 1) * S);
+      row_path[u] = r.first->second;
+    }
+  }
+  Require(!paths.empty(), "annotations pipeline: no row with a finite weight");
+  double lmax = -INFINITY;
+  for (std::size_t u = 0; u < U; ++u)
+    if (row_path[u] >= 0) lmax = std::max(lmax, lw[u]);
+  std::vector<double> w(U, 0.0), map_weight(paths.size(), 0.0);
+  std::vector<int64_t> map_rows(paths.size(), 0);
+  double s1 = 0.0, s2 = 0.0;
+  for (std::size_t u = 0; u < U; ++u) {
+    if (row_path[u] < 0) continue;
+    w[u] = std::exp(lw[u] - lmax);
+    s1 += w[u];
+    s2 += w[u] * w[u];
+    map_weight[row_path[u]] += w[u];
+    ++map_rows[row_path[u]];
+  }
+  // the paths of largest MAP weight, ties by first appearance, kept in first-appearance order
+  std::vector<int32_t> keep(paths.size());
+  for (std::size_t k = 0; k < keep.size(); ++k) keep[k] = (int32_t)k;
+  if ((int64_t)paths.size() > max_candidates) {
+    std::stable_sort(keep.begin(), keep.end(), [&](int32_t a, int32_t b) { return map_weight[a] > map_weight[b]; });
+    keep.resize(max_candidates);
+    std::sort(keep.begin(), keep.end());
+  }
+  const int K = (int)keep.size();
+  std::vector<int32_t> cand_of_path(paths.size(), -1), cand_states((std::size_t)K * S);
+  for (int k = 0; k < K; ++k) {
+    cand_of_path[keep[k]] = k;
+    std::copy(paths[keep[k]].begin(), paths[keep[k]].end(), cand_states.begin() + (std::size_t)k * S);
+  }
+
+  // pass 2
+  std::vector<double> log_prior(K), prob(K, 0.0);
+  CheckHip(lh_family_set_candidate_paths(family_, K, cand_states.data(), log_prior.data()), "lh_family_set_candidate_paths");
+  const std::size_t kScore = std::max<std::size_t>(1, std::min(kBatch, ((std::size_t)32 << 20) / (std::size_t)K));  // rows per call: 256 MB of log_cand
+  std::vector<double> lc;
+  for (std::size_t off = first; off < N; off += kScore) {
+    const std::size_t m = std::min(kScore, N - off);
+    TableBatch tb = FlattenTable(table, off, off + m, false, true, input_path);
+    const DeviceBatch& b = tb.dev;
+    std::vector<double> ll(m);
+    lc.resize(m * (std::size_t)K);
+    lh_candidate_outputs outs{nullptr, ll.data(), lc.data(), nullptr, nullptr};
+    CheckHip(lh_eval_candidates_batch(family_, b.n, b.n_tips, b.max_depth, b.ops.data(), b.brlen.data(), b.er.data(),
+                                      b.pi.data(), b.alpha.data(), num_rates, &outs),
+             "lh_eval_candidates_batch");
+    for (std::size_t i = 0; i < m; ++i) {
+      const std::size_t u = off - first + i;
+      if (std::memcmp(&ll[i], &ll1[u], sizeof(double)) != 0)
+        throw std::runtime_error("annotations pipeline: the two passes' log-likelihoods differ at row " + std::to_string(off + i));
+      if (row_path[u] < 0) continue;
+      const double* row = lc.data() + i * (std::size_t)K;
+      for (int k = 0; k < K; ++k) prob[k] += w[u] * std::exp(row[k]);
+    }
+  }
+  for (double& v : prob) v /= s1;
+
+  // paths whose annotation columns format alike are one annotation
+  struct Annotation {
+    std::string columns;
+    double prob = 0.0, prior = 0.0, weight = 0.0;
+    int64_t rows = 0;
+  };
+  std::vector<Annotation> ann;
+  std::unordered_map<std::string, int32_t> ann_ids;
+  std::vector<int32_t> ann_of_cand(K);
+  RowSampler rs;
+  for (int k = 0; k < K; ++k) {
+    ApplySampledStates(rs, cand_states.data() + (std::size_t)k * S);
+    std::string cols;
+    AppendAnnotationColumns(cols, rs);
+    const auto r = ann_ids.emplace(cols, (int32_t)ann.size());
+    if (r.second) {
+      ann.emplace_back();
+      ann.back().columns = cols;
+    }
+    Annotation& a = ann[r.first->second];
+    a.prob += prob[k];
+    a.prior += std::exp(log_prior[k]);
+    a.weight += map_weight[keep[k]];
+    a.rows += map_rows[keep[k]];
+    ann_of_cand[k] = r.first->second;
+  }
+  std::vector<int32_t> order(ann.size()), rank_of(ann.size());
+  for (std::size_t k = 0; k < order.size(); ++k) order[k] = (int32_t)k;
+  std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return ann[a].prob > ann[b].prob; });
+  for (std::size_t r = 0; r < order.size(); ++r) rank_of[order[r]] = (int32_t)r + 1;
+  char buf[64];
+  auto num = [&](double v) {
+    std::snprintf(buf, sizeof buf, "%.17g", v);
+    return std::string(buf);
+  };
+  std::ofstream all(output_prefix + ".annotations.tsv"), best(output_prefix + ".best.tsv"), rows(output_prefix + ".rows.tsv"),
+      summary(output_prefix + ".summary.tsv");
+  Require(all.good() && best.good() && rows.good() && summary.good(), "Can't write " + output_prefix + ".*.tsv");
+  const std::string head = "rank\tprobability\tlog_probability\tlog_prior\tmap_rows\tmap_weight_share\t" + AnnotationHeader() + "\n";
+  all << head;
+  best << head;
+  double covered = 0.0;
+  for (std::size_t r = 0; r < order.size(); ++r) {
+    const Annotation& a = ann[order[r]];
+    covered += a.prob;
+    const std::string line = std::to_string(r + 1) + '\t' + num(a.prob) + '\t' + num(std::log(a.prob)) + '\t' +
+                             num(std::log(a.prior)) + '\t' + std::to_string(a.rows) + '\t' + num(a.weight / s1) + '\t' +
+                             a.columns + '\n';
+    all << line;
+    if (r == 0) best << line;
+  }
+  rows << "row\tlh_loglik\tlog_weight\tlog_path_posterior\tannotation\n";
+  for (std::size_t u = 0; u < U; ++u) {
+    const int32_t c = row_path[u] >= 0 ? cand_of_path[row_path[u]] : -1;
+    rows << (first + u) << '\t' << num(ll1[u]) << '\t' << num(lw[u]) << '\t' << num(post[u]) << '\t'
+         << (c >= 0 ? std::to_string(rank_of[ann_of_cand[c]]) : std::string("NA")) << '\n';
+  }
+  summary << "key\tvalue\nrows_used\t" << (U - skipped) << "\nrows_skipped_nonfinite\t" << skipped << "\ndistinct_paths\t"
+          << paths.size() << "\npaths_scored\t" << K << "\nannotations\t" << ann.size() << "\ncovered_mass\t" << num(covered)
+          << "\nkish_ess\t" << num(s1 * s1 / s2) << "\n";
 }
 
 }  // namespace linearham

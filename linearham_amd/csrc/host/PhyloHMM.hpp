@@ -124,6 +124,22 @@ class PhyloHMM : public HMM {
   /// .dnamap and .summary.tsv.
   void RunNaiveProbsPipeline(const std::string& input_path, const std::string& output_prefix, int num_rates,
                              double burnin_frac, const std::string& candidates_path, int max_candidates = 65536);
+  /// The most probable annotation of the current tree (K8, lh_eval_viterbi_batch), spelled out as ApplySampledStates
+  /// spells a draw: after InitializePhyloParameters.  *log_path = log P(data, annotation's state path | tree), *loglik the
+  /// tree's log-likelihood (either may be null); their difference is the path's posterior given the tree.  Throws if the
+  /// log-likelihood is not finite or no path has positive probability.
+  RowSampler ViterbiAnnotation(double* log_path, double* loglik);
+  /// The annotation columns of an output line (WriteOutputHeaders from NaiveSequence on), tab-separated, no line end.
+  std::string AnnotationHeader() const;
+  void AppendAnnotationColumns(std::string& line, const RowSampler& sample) const;
+  /// Exact posterior probabilities of annotations (state paths) over a RevBayes table, with RunNaiveProbsPipeline's
+  /// burn-in, weights, skipped-row accounting and one-device rule.  Pass 1 runs K8 on every used row and interns the rows'
+  /// most probable paths; pass 2 registers the `max_candidates` paths of largest MAP weight (ties: the first row seen) and
+  /// scores them exactly on every row (lh_family_set_candidate_paths + K6b); the rows' scores are added up on the host in
+  /// row order, so the files do not depend on LH_PIPELINE_BATCH.  Writes <prefix>.annotations.tsv (one line per distinct
+  /// annotation, paths that format alike collapsed), .best.tsv, .rows.tsv and .summary.tsv.
+  void RunAnnotationsPipeline(const std::string& input_path, const std::string& output_prefix, int num_rates,
+                              double burnin_frac, int max_candidates = 65536);
   static void WriteSiteTable(std::ostream& o, const NaiveMarginalsResult& m);
   static void WriteGeneTable(std::ostream& o, const NaiveMarginalsResult& m);
   void SampleStatesWithWords(const uint32_t* words, int n_words, std::vector<int32_t>& device_states,

@@ -146,6 +146,21 @@ void SimpleHMM::CreateFamily() {
   CheckHip(lh_family_create(&d, &family_), "lh_family_create");
 }
 
+HMM::RowSampler SimpleHMM::ViterbiPath(double* log_path) {
+  CreateFamily();
+  if (!device_sampler_) {
+    device_sampler_ = RegisterDeviceSampler(family_);
+    Require(device_sampler_, "ViterbiPath: the family's junctions have no device sampler tables");
+  }
+  double lp = 0;
+  const std::vector<int32_t> states = ViterbiStates(1, em_.data(), &lp);
+  Require(!states.empty() && states[0] >= 0, "ViterbiPath: no state path has positive probability");
+  if (log_path) *log_path = lp;
+  RowSampler s;
+  ApplySampledStates(s, states.data());
+  return s;
+}
+
 void SimpleHMM::RunForwardAlgorithm() {
   CreateFamily();
   std::vector<double> fwd(lh_forward_size(family_));

@@ -24,6 +24,9 @@ class SimpleHMM : public HMM {
 
  public:
   SimpleHMM(const std::string& yaml_path, int cluster_ind, const std::string& hmm_param_dir, int seed);
+  /// The most probable annotation under the star-tree emissions (K8, lh_viterbi_forward_batch) as ApplySampledStates
+  /// spells it out; *log_path (optional) = log P(data, path).  Throws if no path has positive probability.
+  RowSampler ViterbiPath(double* log_path = nullptr);
 };
 
 typedef std::shared_ptr<SimpleHMM> SimpleHMMPtr;

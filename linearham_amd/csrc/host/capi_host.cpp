@@ -332,6 +332,51 @@ int lhh_phylo_apply_states_map(void* h, int n, const int32_t* states, int* n_dis
   });
 }
 
+// PhyloHMM::ViterbiAnnotation: *out = "header line\nvalue line" of the annotation columns (tab-separated); *log_path,
+// *loglik.  states (optional, cap ints): the path in lh_eval_sample_batch's layout, *n_states its length.
+int lhh_phylo_viterbi_annotation(void* h, double* log_path, double* loglik, const char** out) {
+  return Guard([&] {
+    PhyloHMM& p = dynamic_cast<PhyloHMM&>(*static_cast<HMM*>(h));
+    const HMM::RowSampler s = p.ViterbiAnnotation(log_path, loglik);
+    g_out = p.AnnotationHeader() + "\n";
+    p.AppendAnnotationColumns(g_out, s);
+    *out = g_out.c_str();
+  });
+}
+
+// The annotation columns (PhyloHMM::AppendAnnotationColumns) of n state vectors states [n][lh_sample_states()], one line
+// each in *out; no device work.
+int lhh_phylo_annotation_columns(void* h, int n, int n_states, const int32_t* states, const char** out) {
+  return Guard([&] {
+    PhyloHMM& p = dynamic_cast<PhyloHMM&>(*static_cast<HMM*>(h));
+    HMM::RowSampler s;
+    g_out.clear();
+    for (int i = 0; i < n; ++i) {
+      p.ApplySampledStates(s, states + (std::size_t)i * n_states);
+      p.AppendAnnotationColumns(g_out, s);
+      g_out.push_back('\n');
+    }
+    *out = g_out.c_str();
+  });
+}
+
+// SimpleHMM::ViterbiPath: the naive sequence of the most probable path in *out, log P(data, path) in *log_path.
+int lhh_simple_viterbi_path(void* h, double* log_path, const char** out) {
+  return Guard([&] {
+    const HMM::RowSampler s = dynamic_cast<SimpleHMM&>(*static_cast<HMM*>(h)).ViterbiPath(log_path);
+    g_out = s.naive_seq;
+    *out = g_out.c_str();
+  });
+}
+
+int lhh_run_annotations_pipeline(void* h, const char* input_path, const char* output_prefix, int num_rates,
+                                 double burnin_frac, int max_candidates) {
+  return Guard([&] {
+    dynamic_cast<PhyloHMM&>(*static_cast<HMM*>(h))
+        .RunAnnotationsPipeline(input_path, output_prefix, num_rates, burnin_frac, max_candidates);
+  });
+}
+
 int lhh_run_naive_probs_pipeline(void* h, const char* input_path, const char* output_prefix, int num_rates,
                                  double burnin_frac, const char* candidates_path, int max_candidates) {
   return Guard([&] {

@@ -3,7 +3,9 @@
 // scripts/run_bootstrap_asr_ess.R:48-104 on a --pipeline output table, and --marginals / --marginals-pipeline, the exact
 // posterior of the naive sequence (one tree / importance-weighted over a RevBayes table), and --naive-probs /
 // --naive-probs-pipeline, exact posterior probabilities of naive sequences (tabulate_naive_probs.py's table), and
-// --lineage-pipeline / --lineage-trees, the ancestral lineage tables of a seed sequence (tabulate_lineage_probs.py's).
+// --lineage-pipeline / --lineage-trees, the ancestral lineage tables of a seed sequence (tabulate_lineage_probs.py's), and
+// --viterbi / --annotations-pipeline, the most probable annotation of one tree and the exact posterior probabilities of
+// annotations over a RevBayes table (write_lh_annotations.py's counting, without the sampling).
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -60,7 +62,7 @@ int main(int argc, char** argv) {
   try {
     if (argc < 2 || std::string(argv[1]) == "-h" || std::string(argv[1]) == "--help") {
       std::cout << "A Phylo-HMM implementation for B cell receptor sequence analysis.\n"
-                   "USAGE: linearham {--compute-logl|--sample|--pipeline|--asr|--marginals|--marginals-pipeline|--naive-probs|--naive-probs-pipeline|--lineage-pipeline|--weighted-lineage-pipeline} --yaml-path <string> "
+                   "USAGE: linearham {--compute-logl|--sample|--pipeline|--asr|--marginals|--marginals-pipeline|--naive-probs|--naive-probs-pipeline|--lineage-pipeline|--weighted-lineage-pipeline|--viterbi|--annotations-pipeline} --yaml-path <string> "
                    "--cluster-ind <int> --hmm-param-dir <string> [--seed <int>] [--num-rates <int>] [--extended-range <0|1>] "
                    "[--devices <a,b,...>] ...\n"
                    "  --marginals: the arguments of --compute-logl; prints the per-site naive-base table and the gene table\n"
@@ -71,6 +73,11 @@ int main(int argc, char** argv) {
                    "  --naive-probs-pipeline --input-path <RevBayes table> --output-path <prefix> [--burnin-frac <f>]\n"
                    "    [--candidates-path <file>] [--max-candidates <n>]: writes <prefix>.naive.tsv, <prefix>.aa.fasta,\n"
                    "    <prefix>.dnamap and <prefix>.summary.tsv (one device)\n"
+                   "  --viterbi: the arguments of --compute-logl; prints the most probable annotation of that tree, the log joint\n"
+                   "    probability of its state path, that path's log posterior and the tree's log-likelihood\n"
+                   "  --annotations-pipeline --input-path <RevBayes table> --output-path <prefix> [--burnin-frac <f>]\n"
+                   "    [--max-candidates <n>]: exact posterior probabilities of annotations; writes <prefix>.annotations.tsv,\n"
+                   "    <prefix>.best.tsv, <prefix>.rows.tsv and <prefix>.summary.tsv (one device)\n"
                    "  --lineage-pipeline --input-path <--pipeline table> --output-path <prefix> --seed-seq <name> [--seed <int>]:\n"
                    "    the lineage tables of the sequence <name>: <prefix>.fasta, .dnamap, .nodes.tsv, .edges.tsv, .summary.tsv\n"
                    "       linearham --lineage-trees --input-path <--asr trees> --output-path <prefix> --seed-seq <name>\n"
@@ -96,7 +103,8 @@ int main(int argc, char** argv) {
     }
     if (subcmd != "--compute-logl" && subcmd != "--sample" && subcmd != "--pipeline" && subcmd != "--asr" &&
         subcmd != "--marginals" && subcmd != "--marginals-pipeline" && subcmd != "--naive-probs" &&
-        subcmd != "--naive-probs-pipeline" && subcmd != "--lineage-pipeline" && subcmd != "--weighted-lineage-pipeline")
+        subcmd != "--naive-probs-pipeline" && subcmd != "--lineage-pipeline" && subcmd != "--weighted-lineage-pipeline" &&
+        subcmd != "--viterbi" && subcmd != "--annotations-pipeline")
       throw std::invalid_argument("'" + subcmd + "' is not a valid subcommand.");
     const std::string yaml_path = a.one("yaml-path");
     const int cluster_ind = std::stoi(a.one("cluster-ind"));
@@ -115,7 +123,7 @@ int main(int argc, char** argv) {
         pos = comma + 1;
       }
       if (device_list.size() > 1 && (subcmd == "--marginals-pipeline" || subcmd == "--naive-probs-pipeline" ||
-                                     subcmd == "--weighted-lineage-pipeline"))
+                                     subcmd == "--weighted-lineage-pipeline" || subcmd == "--annotations-pipeline"))
         throw std::invalid_argument(subcmd + " runs on one device: --devices may list only one");
       if (device_list.size() > 1 && subcmd != "--pipeline")
         std::fprintf(stderr, "linearham: %s evaluates on one device; of --devices only device %d is used\n", subcmd.c_str(),
@@ -162,6 +170,11 @@ int main(int argc, char** argv) {
                                            std::stoi(a.opt("max-candidates", "65536")));
       return EXIT_SUCCESS;
     }
+    if (subcmd == "--annotations-pipeline") {
+      phylo_hmm_ptr->RunAnnotationsPipeline(a.one("input-path"), a.one("output-path"), num_rates,
+                                            std::stod(a.opt("burnin-frac", "0")), std::stoi(a.opt("max-candidates", "65536")));
+      return EXIT_SUCCESS;
+    }
     if (subcmd == "--lineage-pipeline") {
       phylo_hmm_ptr->RunLineagePipeline(a.one("input-path"), a.one("seed-seq"), a.one("output-path"),
                                         (uint64_t)std::stoll(a.opt("seed", "0")));
@@ -189,6 +202,14 @@ int main(int argc, char** argv) {
       const std::vector<double> lc = phylo_hmm_ptr->CandidatePosterior(t.seqs, &ll, &t.log_prior);
       for (double x : lc) t.prob.push_back(std::exp(x));
       linearham::WriteNaiveTable(std::cout, t, false);
+    } else if (subcmd == "--viterbi") {
+      double lp = 0, ll = 0;
+      const linearham::HMM::RowSampler s = phylo_hmm_ptr->ViterbiAnnotation(&lp, &ll);
+      char buf[128];
+      std::snprintf(buf, sizeof buf, "%.17g\t%.17g\t%.17g\t", lp, lp - ll, ll);
+      std::string line = buf;
+      phylo_hmm_ptr->AppendAnnotationColumns(line, s);
+      std::cout << "log_path\tlog_path_posterior\tlh_loglik\t" << phylo_hmm_ptr->AnnotationHeader() << "\n" << line << "\n";
     } else if (subcmd == "--marginals") {
       const linearham::PhyloHMM::NaiveMarginalsResult m = phylo_hmm_ptr->NaiveMarginals();
       linearham::PhyloHMM::WriteSiteTable(std::cout, m);

@@ -5,6 +5,7 @@
 #include <map>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <atomic>
 #include <chrono>
 #include <string>
@@ -175,6 +176,11 @@ struct PosteriorWs {  // K5's arrays that the caller of lh_eval_posterior_batch_
 // K6 (lh_naive_probs.hip).  The prior P_HMM(s) of a candidate is the forward sweep over indicator emissions, one per
 // caller column: `twin` is the family created once more without its alignment (lh_family_create), whose columns are
 // the caller's one to one; col_site / col_base are the caller's column -> (site, naive base) map.
+struct ViterbiWs {  // K8 (lh_viterbi.hip): the back-pointers, and the arrays the caller does not hand in
+  DevBuf bp, loglik, states, log_path, weights, stats;
+  DevBuf paths, first_bad;  // lh_family_set_candidate_paths
+};
+
 struct CandidateWs {
   lh_family* twin = nullptr;
   std::string twin_error;  // why there is no twin
@@ -228,6 +234,7 @@ struct HostOutputs {
   DevBuf anc, rate_choice;           // lh_asr_batch
   DevBuf weighted_sum, weight_stats;  // lh_eval_posterior_batch, lh_eval_candidates_batch
   DevBuf log_cand, log_prior;         // lh_eval_candidates_batch, lh_family_set_candidates
+  DevBuf log_path;                    // lh_eval_viterbi_batch, lh_viterbi_forward_batch
 };
 
 // lh_eval_batch's host -> device pipeline: two pinned staging slots, a copy stream and a compute stream
@@ -259,6 +266,7 @@ struct lh_family {
   AsrWs asr;
   PosteriorWs post;
   CandidateWs cand;
+  ViterbiWs vit;
   CollectWs collect;
   LineageWs lineage;
   // forward arrays that stay on the device, shared by K4 and K5 in both their forms: K4 draws from them, K5 overwrites
@@ -273,6 +281,7 @@ struct lh_family {
   KernelTimer<1> asr_timer, post_timer;
   KernelTimer<1> prior_timer, cand_timer;  // K6a, K6b
   KernelTimer<1> collect_timer;             // K6c
+  KernelTimer<1> vit_timer;                 // K8
   KernelTimer<1> lineage_timer;             // K7
   KernelTimer<5> chain_timer;               // lh_eval_lineage_batch: K0, K1, K2 + K4 + K6c, K3, K7
   bool extended = false;  // lh_family_set_extended_range
@@ -1281,9 +1290,12 @@ int lh_asr_profile_read(lh_family* f, double* ms_sampling, int64_t* n_launches) 
 namespace {
 
 // lh_eval_batch_device's body; lem: K6b's log emissions of every sample (lem.out[n][lem.n]), or none.
+// after(off, m): enqueued behind the forward sweep of every launch group (samples off .. off + m), while K2a's hand-off
+// buffers still hold that group (K8 reads them); nonzero fails the call.
 int eval_device(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops, const double* brlen,
                 const double* er, const double* pi, const double* alpha, int32_t R, double* loglik,
-                const lh_eval_outputs* outs, void* hip_stream, const lh::LogEmRequest& lem) {
+                const lh_eval_outputs* outs, void* hip_stream, const lh::LogEmRequest& lem,
+                const std::function<int(int, int)>* after = nullptr) {
   if (int rc = check_batch(f, "lh_eval_batch", n, T, R, max_depth)) return rc > 0;
   DeviceGuard guard(f);
   if (!ops || !brlen || !er || !pi || !alpha || !loglik) return fail("lh_eval_batch: null array");
@@ -1316,6 +1328,7 @@ int eval_device(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int
       return 1;
     if (f->profile && f->eval_timer.end(stream)) return 1;
     LH_HIP(hipGetLastError());
+    if (after && (*after)(off, m)) return 1;
   }
   return 0;
 }
@@ -2455,6 +2468,168 @@ int lh_lineage_eval_profile_read(lh_family* f, double* ms, int64_t* n_launches) 
   if (!f) return fail("null family");
   DeviceGuard guard(f);
   return f->chain_timer.read(ms, n_launches);
+}
+
+}  // extern "C"
+
+// ---- K8: the most probable state path, candidate paths (lh_viterbi.hip) ----
+
+namespace {
+
+// K8 for the m samples K2a's hand-off buffers hold (run_forward has just been enqueued on `stream` for them)
+int viterbi_launch(lh_family* f, int m, const double* loglik, int32_t* states, double* log_path, hipStream_t stream) {
+  ForwardWs& w = f->fws;
+  if (f->vit.bp.ensure(lh::viterbi_bp_bytes(f->host) * (size_t)m)) return 1;
+  lh::launch_viterbi(f->host, f->sampler_dev, m, w.gem.get<const double>(), w.gcnt.get<const int32_t>(),
+                     w.jem.get<const double>(), w.jrs.get<const int32_t>(), loglik, f->vit.bp.get<uint8_t>(), states, log_path,
+                     f->extended, stream);
+  LH_HIP(hipGetLastError());
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int lh_eval_viterbi_batch_device(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops,
+                                 const double* brlen, const double* er, const double* pi, const double* alpha, int32_t R,
+                                 const lh_viterbi_outputs* outs, void* hip_stream) {
+  const std::string W = "lh_eval_viterbi_batch_device";
+  if (int rc = check_batch(f, W, n, T, R, max_depth, true)) return rc > 0;
+  DeviceGuard guard(f);
+  if (lh::viterbi_lds_bytes(f->host) > 160 * 1024) return fail(W + ": the junction tables do not fit K8's LDS");
+  hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+  const lh_viterbi_outputs none{nullptr, nullptr, nullptr, nullptr, nullptr};
+  const lh_viterbi_outputs& o = outs ? *outs : none;
+  ViterbiWs& vw = f->vit;
+  const size_t S = f->sampler.states_per_sample;
+  double *ll = o.loglik, *lp = o.log_path, *w = nullptr, *stats = o.weight_stats;
+  int32_t* states = o.states;
+  auto own = [](double*& p, DevBuf& b, size_t bytes) {
+    if (!p && b.ensure(bytes)) return 1;
+    if (!p) p = b.get<double>();
+    return 0;
+  };
+  if (own(ll, vw.loglik, sizeof(double) * n) || own(lp, vw.log_path, sizeof(double) * n) ||
+      (!states && vw.states.ensure(sizeof(int32_t) * S * n)) ||
+      (stats && own(w, vw.weights, sizeof(double) * n)) ||
+      vw.bp.ensure(lh::viterbi_bp_bytes(f->host) * (size_t)std::min(n, kChunk)))
+    return 1;
+  if (!states) states = vw.states.get<int32_t>();
+  const std::function<int(int, int)> after = [&](int off, int m) {
+    if (f->profile && f->vit_timer.begin(stream)) return 1;
+    if (viterbi_launch(f, m, ll + off, states + (size_t)off * S, lp + off, stream)) return 1;
+    if (f->profile && f->vit_timer.end(stream)) return 1;
+    return 0;
+  };
+  if (eval_device(f, n, T, max_depth, ops, brlen, er, pi, alpha, R, ll, nullptr, hip_stream, lh::LogEmRequest{}, &after))
+    return 1;
+  if (stats) lh::launch_posterior_reduce(n, 0, nullptr, ll, o.log_offset, w, nullptr, nullptr, stats, stream);
+  LH_HIP(hipGetLastError());
+  return 0;
+}
+
+int lh_eval_viterbi_batch(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops, const double* brlen,
+                          const double* er, const double* pi, const double* alpha, int32_t R,
+                          const lh_viterbi_outputs* outs) {
+  const std::string W = "lh_eval_viterbi_batch";
+  if (int rc = check_batch(f, W, n, T, R, max_depth, true)) return rc > 0;
+  DeviceGuard guard(f);
+  if (!ops || !brlen || !er || !pi || !alpha) return fail(W + ": null array");
+  const lh_viterbi_outputs none{nullptr, nullptr, nullptr, nullptr, nullptr};
+  const lh_viterbi_outputs& o = outs ? *outs : none;
+  if (!o.loglik && !o.states && !o.log_path && !o.weight_stats) return 0;  // nothing asked for
+  const size_t nodes = 2 * (size_t)T - 2, n_ops = (size_t)T - 2, S = f->sampler.states_per_sample;
+  HostInputs& in = f->in;
+  HostOutputs& out = f->out;
+  lh_viterbi_outputs dev{nullptr, nullptr, nullptr, nullptr, nullptr};
+  if (out.loglik.ensure(sizeof(double) * n) || out.states.ensure(sizeof(int32_t) * S * n) ||
+      out.log_path.ensure(sizeof(double) * n) ||
+      out_buf(o.weight_stats, out.weight_stats, sizeof(double) * 3, &dev.weight_stats) ||
+      stage_inputs(f, {{ops, sizeof(int32_t) * 4 * n_ops * n, &in.ops},
+                       {brlen, sizeof(double) * nodes * n, &in.brlen},
+                       {er, sizeof(double) * 6 * n, &in.er},
+                       {pi, sizeof(double) * 4 * n, &in.pi},
+                       {alpha, sizeof(double) * n, &in.alpha},
+                       {o.log_offset, sizeof(double) * n, &in.log_offset}}))
+    return 1;
+  dev.log_offset = o.log_offset ? in.log_offset.get<const double>() : nullptr;
+  dev.loglik = out.loglik.get<double>();
+  dev.states = out.states.get<int32_t>();
+  dev.log_path = out.log_path.get<double>();
+  if (lh_eval_viterbi_batch_device(f, n, T, max_depth, in.ops.get<const int32_t>(), in.brlen.get<const double>(),
+                                   in.er.get<const double>(), in.pi.get<const double>(), in.alpha.get<const double>(), R, &dev,
+                                   nullptr))
+    return 1;
+  if (!valid_schedules(ops, (size_t)n, T, (int)nodes, max_depth)) return refuse_schedules(f, W.c_str());
+  return copy_back(f, W.c_str(),
+                   {{o.loglik, dev.loglik, sizeof(double) * n},
+                    {o.states, dev.states, sizeof(int32_t) * S * n},
+                    {o.log_path, dev.log_path, sizeof(double) * n},
+                    {o.weight_stats, dev.weight_stats, sizeof(double) * 3}});
+}
+
+int lh_viterbi_forward_batch(lh_family* f, int32_t n, const double* em, double* log_path, int32_t* states) {
+  const std::string W = "lh_viterbi_forward_batch";
+  if (!f) return fail(W + ": null family");
+  DeviceGuard guard(f);
+  if (!f->have_sampler) return fail(W + ": lh_family_set_sampler has not been called");
+  if (n <= 0) return n == 0 ? 0 : fail(W + ": negative batch size");
+  if (!em) return fail(W + ": null array");
+  if (lh::viterbi_lds_bytes(f->host) > 160 * 1024) return fail(W + ": the junction tables do not fit K8's LDS");
+  const size_t C = f->host.n_xmsa, S = f->sampler.states_per_sample;
+  HostOutputs& out = f->out;
+  if (out.loglik.ensure(sizeof(double) * n) || out.states.ensure(sizeof(int32_t) * S * n) ||
+      out.log_path.ensure(sizeof(double) * n) || stage_inputs(f, {{em, sizeof(double) * C * n, &f->in.em}}))
+    return 1;
+  if (run_forward(f, n, 1, nullptr, nullptr, nullptr, f->in.em.get<const double>(), nullptr, out.loglik.get<double>(), nullptr,
+                  0, nullptr))
+    return 1;
+  if (viterbi_launch(f, n, out.loglik.get<const double>(), out.states.get<int32_t>(), out.log_path.get<double>(), nullptr))
+    return 1;
+  return copy_back(f, nullptr,
+                   {{log_path, out.log_path.get(), sizeof(double) * n}, {states, out.states.get(), sizeof(int32_t) * S * n}});
+}
+
+int lh_family_set_candidate_paths(lh_family* f, int32_t K, const int32_t* states, double* log_prior) {
+  const std::string W = "lh_family_set_candidate_paths";
+  if (!f) return fail(W + ": null family");
+  DeviceGuard guard(f);
+  lh::CollectTables t;
+  if (collect_tables(f, W, &t)) return 1;
+  if (K < 1 || K > 65536) return fail(W + ": K must be 1 .. 65536 paths");
+  if (!states) return fail(W + ": null array");
+  ViterbiWs& vw = f->vit;
+  CandidateWs& cw = f->cand;
+  const size_t S = f->sampler.states_per_sample;
+  const int32_t none = INT32_MAX;
+  cw.tab.K = 0;  // a call that fails leaves the handle without candidates
+  // the priors first: they also decide whether every vector is a path (K6c is given nothing else)
+  if (vw.log_path.ensure(sizeof(double) * K) || vw.first_bad.ensure(sizeof(int32_t)) ||
+      stage_inputs(f, {{states, sizeof(int32_t) * S * K, &vw.paths}, {&none, sizeof(none), &vw.first_bad}}))
+    return 1;
+  lh::launch_path_prior(f->host, f->sampler_dev, K, vw.paths.get<const int32_t>(), vw.log_path.get<double>(),
+                        vw.first_bad.get<int32_t>(), nullptr);
+  LH_HIP(hipGetLastError());
+  int32_t bad = none;
+  LH_HIP(hipMemcpy(&bad, vw.first_bad.get(), sizeof(bad), hipMemcpyDeviceToHost));
+  if (bad != none)
+    return fail(W + ": vector " + std::to_string(bad) +
+                " is not a path of the model (a state index out of range or a transition of probability 0)");
+  // their naive sequences, registered as lh_family_set_candidates registers sequences; then the paths' priors replace the
+  // sequences' in the tables
+  std::vector<uint8_t> seqs((size_t)K * t.L);
+  if (collect_launch(f, t, K, vw.paths.get<const int32_t>(), nullptr)) return 1;
+  if (copy_back(f, nullptr, {{seqs.data(), f->collect.seqs.get(), seqs.size()}})) return 1;
+  if (lh_family_set_candidates(f, K, seqs.data(), nullptr)) return 1;
+  LH_HIP(hipMemcpy(cw.prior.get(), vw.log_path.get(), sizeof(double) * K, hipMemcpyDeviceToDevice));
+  return copy_back(f, nullptr, {{log_prior, cw.prior.get(), sizeof(double) * K}});
+}
+
+int lh_viterbi_profile_read(lh_family* f, double* ms, int64_t* n_launches) {
+  if (!f) return fail("null family");
+  DeviceGuard guard(f);
+  return f->vit_timer.read(ms, n_launches);
 }
 
 }  // extern "C"

@@ -387,6 +387,21 @@ size_t forward_lds_bytes(const DevFamily& fam);
 // (fill_segments_wave) or on the whole block, and K2b's kernels: vd2<GA>+dj, vd<GA>+dj or junction<GA,GB>
 const char* forward_last_form();
 
+// K8 (lh_viterbi.hip): the most probable state path of each sample, from K2a's hand-off buffers as launch_forward has just
+// left them (gem, gcnt, jem, jrs) and the log-likelihoods K2b wrote.  states[n][states_per_sample] in K4's layout,
+// log_path[n] = log P(data, best path | tree); a sample whose loglik is NaN or +inf: states -1, log_path NaN; no path of
+// positive probability (loglik -inf): states -1, log_path -inf.  bp[n][viterbi_bp_bytes] is scratch (the back-pointers).
+size_t viterbi_bp_bytes(const DevFamily& fam);
+size_t viterbi_lds_bytes(const DevFamily& fam);
+void launch_viterbi(const DevFamily& fam, const DevSampler* smp_dev, int n, const double* gem, const int32_t* gcnt,
+                    const double* jem, const int32_t* jrs, const double* loglik, uint8_t* bp, int32_t* states,
+                    double* log_path, bool extended, hipStream_t stream);
+// log_prior[K] = log P_HMM of the paths states[K][states_per_sample] (their weight with every emission 1), one thread per
+// path; a vector that is not a path of the model (an index out of range, a transition of probability 0) gets NaN and
+// lowers *first_bad (which the caller sets to INT32_MAX) to its index.
+void launch_path_prior(const DevFamily& fam, const DevSampler* smp_dev, int K, const int32_t* states, double* log_prior,
+                       int32_t* first_bad, hipStream_t stream);
+
 // Every environment switch of the device library in one place: hooks that tests/ use to push a family onto a kernel
 // form another shape takes by itself (timing experiments are built from a copy of csrc/, tools/build_asm_variant.sh);
 // none of them part of the C ABI.  Read once per process (the first call of debug_options(), lh_capi.hip); a switch that is not set leaves the

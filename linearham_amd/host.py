@@ -131,6 +131,33 @@ def _parse_summary(text):
     return out
 
 
+def read_annotations(prefix):
+    """The files RunAnnotationsPipeline writes: dict(annotations = list of row dicts of <prefix>.annotations.tsv in rank
+    order (rank, map_rows ints; probability, log_probability, log_prior, map_weight_share floats; the annotation columns
+    as strings), best = the one row of <prefix>.best.tsv, rows = [dict(row, lh_loglik, log_weight, log_path_posterior,
+    annotation = rank or None)] of <prefix>.rows.tsv, summary = dict of <prefix>.summary.tsv)."""
+    def table(path):
+        lines = open(path).read().strip("\n").split("\n")
+        head = lines[0].split("\t")
+        return [dict(zip(head, ln.split("\t") + [""] * (len(head) - len(ln.split("\t"))))) for ln in lines[1:]]
+
+    def annotation(d):
+        d = dict(d)
+        for k in ("rank", "map_rows"):
+            d[k] = int(d[k])
+        for k in ("probability", "log_probability", "log_prior", "map_weight_share"):
+            d[k] = float(d[k])
+        return d
+    ann = [annotation(d) for d in table(prefix + ".annotations.tsv")]
+    best = [annotation(d) for d in table(prefix + ".best.tsv")]
+    rows = [dict(row=int(d["row"]), lh_loglik=float(d["lh_loglik"]), log_weight=float(d["log_weight"]),
+                 log_path_posterior=float(d["log_path_posterior"]),
+                 annotation=None if d["annotation"] == "NA" else int(d["annotation"])) for d in table(prefix + ".rows.tsv")]
+    summary = {d["key"]: float(d["value"]) if d["key"] in ("kish_ess", "covered_mass") else int(d["value"])
+               for d in table(prefix + ".summary.tsv")}
+    return dict(annotations=ann, best=best[0] if best else None, rows=rows, summary=summary)
+
+
 def read_lineage(prefix):
     """The files RunLineagePipeline / RunWeightedLineagePipeline / tabulate_lineage_trees write: dict(fasta = [(name, aa)]
     of <prefix>.fasta, dnamap = {name: [(fraction, dna)]} of <prefix>.dnamap, nodes = [dict(name, kind, count, fraction)]
@@ -260,6 +287,13 @@ class SimpleHMM(_HMM):
                                              C.byref(h)))
         super().__init__(h)
 
+    def viterbi_path(self):
+        """(naive sequence of the most probable state path, log P(data, path)): SimpleHMM::ViterbiPath (K8)."""
+        lp, out = C.c_double(), C.c_char_p()
+        self.lib.lhh_simple_viterbi_path.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_char_p)]
+        _check(self.lib.lhh_simple_viterbi_path(self.h, C.byref(lp), C.byref(out)))
+        return out.value.decode(), lp.value
+
 
 class PhyloHMM(_HMM):
     def __init__(self, yaml_path, cluster_ind, hmm_param_dir, seed):
@@ -326,6 +360,34 @@ class PhyloHMM(_HMM):
         _check(self.lib.lhh_run_marginals_pipeline(self.h, input_path.encode(), output_prefix.encode(), num_rates,
                                                    C.c_double(burnin_frac)))
         return read_marginals(output_prefix)
+
+    def viterbi_annotation(self):
+        """The most probable annotation of the current tree (PhyloHMM::ViterbiAnnotation, K8): (dict of the annotation
+        columns NaiveSequence, VGene, ... as strings, log P(data, path | tree), log-likelihood)."""
+        lp, ll, out = C.c_double(), C.c_double(), C.c_char_p()
+        self.lib.lhh_phylo_viterbi_annotation.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                                          C.POINTER(C.c_char_p)]
+        _check(self.lib.lhh_phylo_viterbi_annotation(self.h, C.byref(lp), C.byref(ll), C.byref(out)))
+        head, vals = out.value.decode().split("\n")
+        vals = vals.split("\t")
+        head = head.split("\t")
+        return dict(zip(head, vals + [""] * (len(head) - len(vals)))), lp.value, ll.value
+
+    def annotation_columns(self, states):
+        """The annotation columns (NaiveSequence, VGene, ... tab-separated, as the annotation files print them) of state
+        vectors states [n][S] in lh_eval_sample_batch's layout: HMM::ApplySampledStates on the host."""
+        st = np.ascontiguousarray(states, dtype=np.int32)
+        out = C.c_char_p()
+        self.lib.lhh_phylo_annotation_columns.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_char_p)]
+        _check(self.lib.lhh_phylo_annotation_columns(self.h, st.shape[0], st.shape[1], st.ctypes.data, C.byref(out)))
+        return out.value.decode().split("\n")[:st.shape[0]]
+
+    def run_annotations_pipeline(self, input_path, output_prefix, num_rates, burnin_frac=0.0, max_candidates=65536):
+        """PhyloHMM::RunAnnotationsPipeline; returns read_annotations(output_prefix)."""
+        self.lib.lhh_run_annotations_pipeline.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_int, C.c_double, C.c_int]
+        _check(self.lib.lhh_run_annotations_pipeline(self.h, input_path.encode(), output_prefix.encode(), num_rates,
+                                                     C.c_double(burnin_frac), max_candidates))
+        return read_annotations(output_prefix)
 
     def candidate_posterior(self, seqs):
         """(log P(s | data, tree) [K], log-likelihood, log P_HMM(s) [K]) of ACGTN candidate strings for the current tree
