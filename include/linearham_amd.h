@@ -567,6 +567,60 @@ int lh_family_set_candidate_paths(lh_family* fam, int32_t K, const int32_t* stat
 /* Time of K8 over the lh_eval_viterbi_batch[_device] launch groups made while profiling was enabled. */
 int lh_viterbi_profile_read(lh_family* fam, double* ms, int64_t* n_launches);
 
+/* ---- K9: exact posterior distributions of the naive sequence's codons ----
+ * For a reading frame f, codon c covers alignment sites f + 3c .. f + 3c + 2, c = 0 .. floor((L - f) / 3) - 1.  The three
+ * bases of a codon are dependent wherever a junction is involved, so per-site marginals (K5) do not give the codon's
+ * distribution: K9 forms the joint posterior of the (at most three) consecutive chain positions -- V genes | V-D rows |
+ * D genes | D-J rows | J genes -- that write the codon's sites and pushes it forward onto (b1, b2, b3) in {A,C,G,T,N}^3,
+ * 125 entries per codon, index 25 b1 + 5 b2 + b3.  The device writes the "window" codons, those with a site in a junction
+ * row, and the sample's gene posteriors; a codon that lies inside one germline region is a linear map of that region's
+ * gene posterior, which the host applies (linearham_amd/posterior.py codon_table, PhyloHMM::ExpandCodons).
+ *
+ * lh_family_set_codons fixes the frame and builds the window tables on the device (replacing an earlier frame's).  Needs
+ * lh_family_set_sampler and a family with an MSA.  Refused: a frame outside 0 .. 2, and a family whose D region has no
+ * alignment site of its own between the two junctions (a codon would then span more than three chain positions). */
+int lh_family_set_codons(lh_family* fam, int32_t frame);
+
+/* The layout lh_family_set_codons built: the number of codons of the frame, the number of window codons, their codon
+ * indices window_codon[n_window] (ascending) and the number of gene posteriors nV + nD + nJ.  Any pointer may be NULL. */
+int lh_codon_layout(const lh_family* fam, int32_t* n_codons, int32_t* n_window, int32_t* window_codon, int32_t* n_genes);
+
+/* Every member may be NULL.  log_offset is an input, as in lh_posterior_outputs.
+ *   loglik           [n]
+ *   windows          [n][n_window][125]  the window codons' distributions; NaN for a sample whose loglik is not finite
+ *                                        (an overflowed row in the active mode, or a rejected schedule)
+ *   genes            [n][n_genes]        V | D | J gene posteriors, as in the forward layout; NaN likewise
+ *   weighted_windows [n_window][125]     sum_i w_i windows_i, in a fixed order; samples with w_i = 0 are left out
+ *   weighted_genes   [n_genes]           sum_i w_i genes_i
+ *   weight_stats     [3]                 max lw, sum w_i, sum w_i^2, as lh_eval_posterior_batch's for the same rows
+ * Batches combine exactly: rescale each one's sums by exp(max_b - max). */
+typedef struct {
+  const double* log_offset;
+  double* loglik;
+  double* windows;
+  double* genes;
+  double* weighted_windows;
+  double* weighted_genes;
+  double* weight_stats;
+} lh_codon_outputs;
+
+/* lh_eval_batch followed by K9 (lh_family_set_codons first).  Host pointers; a malformed schedule fails the call as in
+ * lh_eval_posterior_batch. */
+int lh_eval_codons_batch(lh_family* fam, int32_t n, int32_t n_tips, int32_t max_depth, const int32_t* ops,
+                         const double* brlen, const double* er, const double* pi, const double* alpha,
+                         int32_t num_rates, const lh_codon_outputs* outs);
+
+/* The same with every array (outs' members included) resident on the handle's device; enqueued on `hip_stream` without
+ * synchronising.  A schedule K0c rejects gives that sample NaN, leaves it out of the weighted sums and raises the
+ * handle's error word (lh_family_status). */
+int lh_eval_codons_batch_device(lh_family* fam, int32_t n, int32_t n_tips, int32_t max_depth, const int32_t* ops,
+                                const double* brlen, const double* er, const double* pi, const double* alpha,
+                                int32_t num_rates, const lh_codon_outputs* outs, void* hip_stream);
+
+/* Time of K9 (smoothing and reduction) over the lh_eval_codons_batch[_device] calls made while profiling was enabled
+ * (HIP events on the launch stream); resets the counters. */
+int lh_codon_profile_read(lh_family* fam, double* ms, int64_t* n_launches);
+
 #ifdef __cplusplus
 }
 #endif

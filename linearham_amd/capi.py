@@ -69,6 +69,20 @@ EXPORTS += LINEAGE_EVAL_EXPORTS
 VITERBI_EXPORTS = ["lh_eval_viterbi_batch", "lh_eval_viterbi_batch_device", "lh_viterbi_forward_batch",
                    "lh_family_set_candidate_paths", "lh_viterbi_profile_read"]
 EXPORTS += VITERBI_EXPORTS
+# K9 (exact posterior distributions of the naive sequence's codons)
+CODON_EXPORTS = ["lh_family_set_codons", "lh_codon_layout", "lh_eval_codons_batch", "lh_eval_codons_batch_device",
+                 "lh_codon_profile_read"]
+EXPORTS += CODON_EXPORTS
+
+
+class _CodonOutputs(C.Structure):
+    _fields_ = [("log_offset", c_f64p), ("loglik", c_f64p), ("windows", c_f64p), ("genes", c_f64p),
+                ("weighted_windows", c_f64p), ("weighted_genes", c_f64p), ("weight_stats", c_f64p)]
+
+
+class _CodonOutputsDevice(C.Structure):  # the same members as device addresses
+    _fields_ = [(k, C.c_void_p) for k in ("log_offset", "loglik", "windows", "genes", "weighted_windows",
+                                          "weighted_genes", "weight_stats")]
 
 
 class _ViterbiOutputs(C.Structure):
@@ -222,6 +236,14 @@ class HipLibrary:
             lib.lh_viterbi_forward_batch.argtypes = [C.c_void_p, C.c_int32, c_f64p, c_f64p, c_i32p]
             lib.lh_family_set_candidate_paths.argtypes = [C.c_void_p, C.c_int32, c_i32p, c_f64p]
             lib.lh_viterbi_profile_read.argtypes = [C.c_void_p, c_f64p, C.POINTER(C.c_int64)]
+        if hasattr(lib, "lh_family_set_codons"):
+            lib.lh_family_set_codons.argtypes = [C.c_void_p, C.c_int32]
+            lib.lh_codon_layout.argtypes = [C.c_void_p, c_i32p, c_i32p, c_i32p, c_i32p]
+            lib.lh_eval_codons_batch.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, c_i32p, c_f64p, c_f64p,
+                                                 c_f64p, c_f64p, C.c_int32, C.POINTER(_CodonOutputs)]
+            lib.lh_eval_codons_batch_device.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + \
+                [C.c_void_p] * 5 + [C.c_int32, C.POINTER(_CodonOutputsDevice), C.c_void_p]
+            lib.lh_codon_profile_read.argtypes = [C.c_void_p, c_f64p, C.POINTER(C.c_int64)]
         if hasattr(lib, "lh_set_device"):      # (absent from round-2 builds loaded through LH_LIB_DIR for comparisons)
             lib.lh_set_device.argtypes = [C.c_int32]
             lib.lh_family_status.argtypes = [C.c_void_p]
@@ -269,6 +291,52 @@ class HipLibrary:
         h = family.handle if isinstance(family, Family) else family
         ms, k = C.c_double(), C.c_int64()
         self.check(self.lib.lh_posterior_profile_read(h, C.byref(ms), C.byref(k)))
+        return ms.value, k.value
+
+    def set_codons(self, family, frame=0):
+        """Fixes the reading frame of K9 on a family handle that has sampler tables and returns its layout:
+        dict(frame, n_codons, window_codon [n_window], n_genes)."""
+        h = family.handle if isinstance(family, Family) else family
+        self.check(self.lib.lh_family_set_codons(h, frame))
+        return self.codon_layout(h, frame)
+
+    def codon_layout(self, family, frame):
+        """The layout of the handle's window tables; `frame` is the one set_codons fixed (the C ABI does not report it)."""
+        h = family.handle if isinstance(family, Family) else family
+        nc, nw, ng = C.c_int32(), C.c_int32(), C.c_int32()
+        self.check(self.lib.lh_codon_layout(h, C.byref(nc), C.byref(nw), None, C.byref(ng)))
+        wc = np.zeros(max(nw.value, 1), dtype=np.int32)
+        self.check(self.lib.lh_codon_layout(h, None, None, wc.ctypes.data_as(c_i32p), None))
+        return dict(frame=frame, n_codons=nc.value, window_codon=wc[:nw.value].tolist(), n_genes=ng.value)
+
+    def eval_codons_batch(self, family, n_tips, max_depth, ops, brlen, er, pi, alpha, num_rates, log_offset=None,
+                          want=("loglik", "windows", "genes", "weighted_windows", "weighted_genes", "weight_stats")):
+        """K0-K2 + K9 on a family handle after set_codons.  Returns a dict with the members of `want`: loglik [n],
+        windows [n, n_window, 125], genes [n, n_genes], weighted_windows [n_window, 125], weighted_genes [n_genes],
+        weight_stats [3] (max lw, sum w, sum w^2 with lw = loglik - log_offset)."""
+        h = family.handle if isinstance(family, Family) else family
+        ops = np.ascontiguousarray(ops, dtype=np.int32)
+        n = ops.shape[0]
+        brlen, er, pi, alpha = _f64(brlen), _f64(er), _f64(pi), _f64(alpha)
+        nw, ng = C.c_int32(), C.c_int32()
+        self.check(self.lib.lh_codon_layout(h, None, C.byref(nw), None, C.byref(ng)))
+        shapes = dict(loglik=(n,), windows=(n, nw.value, 125), genes=(n, ng.value), weighted_windows=(nw.value, 125),
+                      weighted_genes=(ng.value,), weight_stats=(3,))
+        res = {k: np.zeros(shapes[k]) for k in shapes if k in want}
+        lo = None if log_offset is None else _f64(log_offset)
+
+        def ptr(a):
+            return a.ctypes.data_as(c_f64p) if a is not None else None
+        outs = _CodonOutputs(ptr(lo), *[ptr(res.get(k)) for k in ("loglik", "windows", "genes", "weighted_windows",
+                                                                  "weighted_genes", "weight_stats")])
+        self.check(self.lib.lh_eval_codons_batch(h, n, n_tips, max_depth, ops.ctypes.data_as(c_i32p), ptr(brlen),
+                                                 ptr(er), ptr(pi), ptr(alpha), num_rates, C.byref(outs)))
+        return res
+
+    def codon_profile_read(self, family):
+        h = family.handle if isinstance(family, Family) else family
+        ms, k = C.c_double(), C.c_int64()
+        self.check(self.lib.lh_codon_profile_read(h, C.byref(ms), C.byref(k)))
         return ms.value, k.value
 
     def candidates_info(self, family):

@@ -1880,6 +1880,171 @@ void PhyloHMM::RunMarginalsPipeline(const std::string& input_path, const std::st
 }
 
 
+// ---- K9: codon and amino-acid marginals ----
+
+namespace {
+
+// the layout lh_family_set_codons built
+struct CodonLayout {
+  int32_t n_codons = 0, n_window = 0, n_genes = 0;
+  std::vector<int32_t> window_codon;
+};
+
+CodonLayout SetCodons(lh_family* fam, int frame) {
+  if (lh_family_set_codons(fam, frame)) throw std::runtime_error(lh_last_error());
+  CodonLayout lay;
+  if (lh_codon_layout(fam, &lay.n_codons, &lay.n_window, nullptr, &lay.n_genes)) throw std::runtime_error(lh_last_error());
+  lay.window_codon.resize(lay.n_window);
+  if (lh_codon_layout(fam, nullptr, nullptr, lay.window_codon.data(), nullptr)) throw std::runtime_error(lh_last_error());
+  return lay;
+}
+
+}  // namespace
+
+PhyloHMM::CodonMarginalsResult PhyloHMM::ExpandCodons(int frame, const std::vector<int32_t>& window_codon,
+                                                      const double* windows, const double* genes) const {
+  const int L = (int)msa_.cols();
+  const bool igh = locus_ == "igh";
+  CodonMarginalsResult m;
+  m.frame = frame;
+  std::array<double, 125> zero;
+  zero.fill(0.0);
+  m.codons.assign(L >= frame ? (L - frame) / 3 : 0, zero);
+  std::vector<char> is_window(m.codons.size(), 0);
+  for (std::size_t i = 0; i < window_codon.size(); ++i) {
+    const std::size_t c = (std::size_t)window_codon.at(i);
+    Require(c < m.codons.size(), "ExpandCodons: window codon out of range");
+    is_window[c] = 1;
+    std::copy(windows + i * 125, windows + (i + 1) * 125, m.codons[c].begin());
+  }
+  // per region: first gene posterior, and every gene's base per site (N where it writes none)
+  struct Region {
+    const RegionStates* R;
+    std::size_t off;
+    std::vector<uint8_t> base;  // [genes][L]
+  };
+  std::vector<Region> regions;
+  std::size_t off = 0;
+  for (const RegionStates* R : {&vgerm_, igh ? &dgerm_ : nullptr, &jgerm_}) {
+    if (!R) continue;
+    Region r{R, off, std::vector<uint8_t>(R->ggene_ranges.size() * (std::size_t)L, 4)};
+    std::size_t g = 0;
+    for (const auto& kv : R->ggene_ranges) {
+      for (int k = kv.second.first; k < kv.second.second; ++k) r.base[g * L + R->site_inds[k]] = (uint8_t)R->naive_bases[k];
+      ++g;
+    }
+    off += g;
+    regions.push_back(std::move(r));
+  }
+  const int v_end = flexbounds_.at("v_r").first;
+  const int d_end = igh ? flexbounds_.at("d_r").first : v_end;
+  for (std::size_t c = 0; c < m.codons.size(); ++c) {
+    if (is_window[c]) continue;
+    const int s0 = frame + 3 * (int)c;
+    const Region& r = s0 < v_end ? regions.front() : (igh && s0 < d_end) ? regions[1] : regions.back();
+    const std::size_t n = r.R->ggene_ranges.size();
+    for (std::size_t g = 0; g < n; ++g) {
+      const uint8_t* b = r.base.data() + g * L + s0;
+      m.codons[c][25 * b[0] + 5 * b[1] + b[2]] += genes[r.off + g];
+    }
+  }
+  return m;
+}
+
+PhyloHMM::CodonMarginalsResult PhyloHMM::NaiveCodonMarginals(int frame) {
+  Require(have_tree_, "InitializePhyloParameters must be called first");
+  CreateFamily();
+  Require(device_sampler_, "the family has no device sampler tables (needed by the codon kernel)");
+  const CodonLayout lay = SetCodons(family_, frame);
+  const int T = tree_.n_tips;
+  std::vector<int32_t> ops((std::size_t)(T - 2) * 4);
+  int32_t depth = 0;
+  CheckHip(lh_schedule_tree(T, tree_.children.data(), tree_.root, ops.data(), &depth), "lh_schedule_tree");
+  std::vector<double> windows((std::size_t)lay.n_window * 125), genes(lay.n_genes);
+  double ll = 0;
+  lh_codon_outputs outs{nullptr, &ll, windows.data(), genes.data(), nullptr, nullptr, nullptr};
+  CheckHip(lh_eval_codons_batch(family_, 1, T, depth, ops.data(), tree_.brlen.data(), er_.data(), pi_.data(), &alpha_,
+                                num_rates_, &outs),
+           "lh_eval_codons_batch");
+  return ExpandCodons(frame, lay.window_codon, windows.data(), genes.data());
+}
+
+void PhyloHMM::WriteCodonTable(std::ostream& o, const CodonMarginalsResult& m) {
+  static const char kBases[] = "ACGTN";
+  o << "codon\tfirst_site\tbases\tprobability\n";
+  for (std::size_t c = 0; c < m.codons.size(); ++c)
+    for (int i = 0; i < 125; ++i)
+      if (m.codons[c][i] > 0.0)
+        o << c << '\t' << (m.frame + 3 * c) << '\t' << kBases[i / 25] << kBases[(i / 5) % 5] << kBases[i % 5] << '\t'
+          << ReprDouble(m.codons[c][i]) << '\n';
+}
+
+void PhyloHMM::WriteAminoAcidTable(std::ostream& o, const CodonMarginalsResult& m) {
+  static const std::string aa_of = [] {
+    static const char kBases[] = "ACGTN";
+    std::string dna;
+    for (int i = 0; i < 125; ++i) dna += {kBases[i / 25], kBases[(i / 5) % 5], kBases[i % 5]};
+    return TranslateDna(dna);
+  }();
+  o << "codon\taa\tprobability\n";
+  for (std::size_t c = 0; c < m.codons.size(); ++c) {
+    std::map<char, double> p;
+    for (int i = 0; i < 125; ++i)
+      if (m.codons[c][i] > 0.0) p[aa_of[i]] += m.codons[c][i];
+    for (const auto& kv : p) o << c << '\t' << kv.first << '\t' << ReprDouble(kv.second) << '\n';
+  }
+}
+
+void PhyloHMM::RunCodonMarginalsPipeline(const std::string& input_path, const std::string& output_prefix, int num_rates,
+                                         double burnin_frac, int frame) {
+  Require(devices_.size() <= 1, "the codon marginals pipeline runs on one device: --devices may list only one");
+  Require(burnin_frac >= 0.0 && burnin_frac < 1.0, "burn-in fraction must be in [0, 1)");
+  CreateFamily();
+  Require(device_sampler_, "the family has no device sampler tables (needed by the codon kernel)");
+  const CodonLayout lay = SetCodons(family_, frame);
+  TsvTable table = TsvTable::OpenRevBayesTable(input_path);
+  const std::size_t N = table.rows.size();
+  const std::size_t first = (std::size_t)std::floor(burnin_frac * (double)N);
+  const std::size_t NW = (std::size_t)lay.n_window * 125, NG = (std::size_t)lay.n_genes;
+  // the rows' windows and genes come back whole: a batch is bounded by their size (NW + NG doubles per row)
+  const std::size_t kBatch = host_options().pipeline_batch > 0 ? (std::size_t)host_options().pipeline_batch : 8192;
+  WeightedSums acc(NW + NG);
+  std::vector<double> windows, genes, row(NW + NG);
+  std::size_t skipped = 0;
+  for (std::size_t off = first; off < N; off += kBatch) {
+    const std::size_t m = std::min(kBatch, N - off);
+    TableBatch tb = FlattenTable(table, off, off + m, false, true, input_path);
+    const DeviceBatch& b = tb.dev;
+    std::vector<double> ll(m);
+    windows.resize(m * NW);
+    genes.resize(m * NG);
+    lh_codon_outputs outs{nullptr, ll.data(), windows.data(), genes.data(), nullptr, nullptr, nullptr};
+    CheckHip(lh_eval_codons_batch(family_, b.n, b.n_tips, b.max_depth, b.ops.data(), b.brlen.data(), b.er.data(),
+                                  b.pi.data(), b.alpha.data(), num_rates, &outs),
+             "lh_eval_codons_batch");
+    for (std::size_t i = 0; i < m; ++i) {
+      const double st[3] = {ll[i] - tb.lik[i], 1.0, 1.0};  // one row, its weight relative to itself
+      if (!std::isfinite(st[0])) {
+        ++skipped;
+        continue;
+      }
+      std::copy(windows.begin() + i * NW, windows.begin() + (i + 1) * NW, row.begin());
+      std::copy(genes.begin() + i * NG, genes.begin() + (i + 1) * NG, row.begin() + NW);
+      acc.Add(row.data(), st);
+    }
+  }
+  Require(acc.s1 > 0.0, "codon marginals pipeline: no row with a finite weight");
+  acc.Normalise();
+  const CodonMarginalsResult res = ExpandCodons(frame, lay.window_codon, acc.total.data(), acc.total.data() + NW);
+  std::ofstream codons(output_prefix + ".codons.tsv"), aa(output_prefix + ".aa.tsv"), summary(output_prefix + ".summary.tsv");
+  Require(codons.good() && aa.good() && summary.good(), "Can't write " + output_prefix + ".*.tsv");
+  WriteCodonTable(codons, res);
+  WriteAminoAcidTable(aa, res);
+  summary << "key\tvalue\nrows_used\t" << (N - first - skipped) << "\nrows_skipped_nonfinite\t" << skipped << "\nkish_ess\t"
+          << ReprDouble(acc.KishEss()) << "\nframe\t" << frame << "\n";
+}
+
+
 namespace {
 
 // ACGTN strings -> bytes 0..4 (the naive-base alphabet)

@@ -140,6 +140,29 @@ class PhyloHMM : public HMM {
   /// annotation, paths that format alike collapsed), .best.tsv, .rows.tsv and .summary.tsv.
   void RunAnnotationsPipeline(const std::string& input_path, const std::string& output_prefix, int num_rates,
                               double burnin_frac, int max_candidates = 65536);
+  /// The exact posterior distribution of every codon of the naive sequence in reading frame `frame` (K9,
+  /// lh_eval_codons_batch): codon c covers sites frame + 3c .. frame + 3c + 2; its 125 entries are indexed
+  /// 25 b1 + 5 b2 + b3 over A, C, G, T, N.
+  struct CodonMarginalsResult {
+    int frame = 0;
+    std::vector<std::array<double, 125>> codons;
+  };
+  /// The full table from what the device writes -- the window codons' distributions and the V | D | J gene posteriors:
+  /// a codon inside one germline region gets every gene's three bases there (N where the gene writes none) with the
+  /// gene's posterior.
+  CodonMarginalsResult ExpandCodons(int frame, const std::vector<int32_t>& window_codon, const double* windows,
+                                    const double* genes) const;
+  /// After InitializePhyloParameters: the codon table of the current tree.
+  CodonMarginalsResult NaiveCodonMarginals(int frame);
+  /// The importance-weighted codon table over a RevBayes table, with RunMarginalsPipeline's reader, burn-in and weights.
+  /// The rows' tables are added up on the host in row order, every row rescaled to the running largest log weight, so the
+  /// files do not depend on LH_PIPELINE_BATCH.  Writes <prefix>.codons.tsv, .aa.tsv and .summary.tsv.
+  void RunCodonMarginalsPipeline(const std::string& input_path, const std::string& output_prefix, int num_rates,
+                                 double burnin_frac, int frame);
+  /// codon, first_site, bases, probability: the entries above 0, numbers as ReprDouble prints them
+  static void WriteCodonTable(std::ostream& o, const CodonMarginalsResult& m);
+  /// codon, aa, probability: the codon table folded with TranslateDna's table (its N-codon rule included)
+  static void WriteAminoAcidTable(std::ostream& o, const CodonMarginalsResult& m);
   static void WriteSiteTable(std::ostream& o, const NaiveMarginalsResult& m);
   static void WriteGeneTable(std::ostream& o, const NaiveMarginalsResult& m);
   void SampleStatesWithWords(const uint32_t* words, int n_words, std::vector<int32_t>& device_states,

@@ -281,6 +281,33 @@ int lhh_run_marginals_pipeline(void* h, const char* input_path, const char* outp
   });
 }
 
+// PhyloHMM::NaiveCodonMarginals: table [cap_codons][125]; *n_codons receives the count; the amino-acid table
+// (WriteAminoAcidTable) in *aa.  table == NULL: only *n_codons, nothing is evaluated.
+int lhh_phylo_codon_marginals(void* h, int frame, double* table, int cap_codons, int* n_codons, const char** aa) {
+  return Guard([&] {
+    PhyloHMM& p = dynamic_cast<PhyloHMM&>(*static_cast<HMM*>(h));
+    if (frame < 0 || frame > 2) throw std::runtime_error("frame must be 0, 1 or 2");
+    const int L = (int)p.msa().cols();
+    *n_codons = L >= frame ? (L - frame) / 3 : 0;
+    if (!table) return;
+    const PhyloHMM::CodonMarginalsResult m = p.NaiveCodonMarginals(frame);
+    if ((int)m.codons.size() > cap_codons) throw std::runtime_error("lhh_phylo_codon_marginals: output too small");
+    for (std::size_t c = 0; c < m.codons.size(); ++c) std::copy(m.codons[c].begin(), m.codons[c].end(), table + c * 125);
+    std::ostringstream o;
+    PhyloHMM::WriteAminoAcidTable(o, m);
+    g_out = o.str();
+    *aa = g_out.c_str();
+  });
+}
+
+int lhh_run_codon_marginals_pipeline(void* h, const char* input_path, const char* output_prefix, int num_rates,
+                                     double burnin_frac, int frame) {
+  return Guard([&] {
+    dynamic_cast<PhyloHMM&>(*static_cast<HMM*>(h)).RunCodonMarginalsPipeline(input_path, output_prefix, num_rates,
+                                                                             burnin_frac, frame);
+  });
+}
+
 // PhyloHMM::CandidatePosterior: seqs = K candidates of n_sites characters, back to back; log_post [K], log_prior [K]
 // (may be NULL), *loglik.
 int lhh_phylo_candidate_posterior(void* h, int K, const char* seqs, double* log_post, double* log_prior, double* loglik) {

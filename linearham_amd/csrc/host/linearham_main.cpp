@@ -5,7 +5,9 @@
 // --naive-probs-pipeline, exact posterior probabilities of naive sequences (tabulate_naive_probs.py's table), and
 // --lineage-pipeline / --lineage-trees, the ancestral lineage tables of a seed sequence (tabulate_lineage_probs.py's), and
 // --viterbi / --annotations-pipeline, the most probable annotation of one tree and the exact posterior probabilities of
-// annotations over a RevBayes table (write_lh_annotations.py's counting, without the sampling).
+// annotations over a RevBayes table (write_lh_annotations.py's counting, without the sampling), and --codon-marginals /
+// --codon-marginals-pipeline, the exact codon and amino-acid distributions of the naive sequence (the logo
+// tabulate_naive_probs.py draws from sampled sequences).
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -62,7 +64,7 @@ int main(int argc, char** argv) {
   try {
     if (argc < 2 || std::string(argv[1]) == "-h" || std::string(argv[1]) == "--help") {
       std::cout << "A Phylo-HMM implementation for B cell receptor sequence analysis.\n"
-                   "USAGE: linearham {--compute-logl|--sample|--pipeline|--asr|--marginals|--marginals-pipeline|--naive-probs|--naive-probs-pipeline|--lineage-pipeline|--weighted-lineage-pipeline|--viterbi|--annotations-pipeline} --yaml-path <string> "
+                   "USAGE: linearham {--compute-logl|--sample|--pipeline|--asr|--marginals|--marginals-pipeline|--naive-probs|--naive-probs-pipeline|--lineage-pipeline|--weighted-lineage-pipeline|--viterbi|--annotations-pipeline|--codon-marginals|--codon-marginals-pipeline} --yaml-path <string> "
                    "--cluster-ind <int> --hmm-param-dir <string> [--seed <int>] [--num-rates <int>] [--extended-range <0|1>] "
                    "[--devices <a,b,...>] ...\n"
                    "  --marginals: the arguments of --compute-logl; prints the per-site naive-base table and the gene table\n"
@@ -78,6 +80,10 @@ int main(int argc, char** argv) {
                    "  --annotations-pipeline --input-path <RevBayes table> --output-path <prefix> [--burnin-frac <f>]\n"
                    "    [--max-candidates <n>]: exact posterior probabilities of annotations; writes <prefix>.annotations.tsv,\n"
                    "    <prefix>.best.tsv, <prefix>.rows.tsv and <prefix>.summary.tsv (one device)\n"
+                   "  --codon-marginals [--frame <0|1|2>]: the arguments of --marginals; prints the codon table and the amino-acid\n"
+                   "    table of the naive sequence for that tree\n"
+                   "  --codon-marginals-pipeline --input-path <RevBayes table> --output-path <prefix> [--burnin-frac <f>]\n"
+                   "    [--frame <0|1|2>]: writes <prefix>.codons.tsv, <prefix>.aa.tsv and <prefix>.summary.tsv (one device)\n"
                    "  --lineage-pipeline --input-path <--pipeline table> --output-path <prefix> --seed-seq <name> [--seed <int>]:\n"
                    "    the lineage tables of the sequence <name>: <prefix>.fasta, .dnamap, .nodes.tsv, .edges.tsv, .summary.tsv\n"
                    "       linearham --lineage-trees --input-path <--asr trees> --output-path <prefix> --seed-seq <name>\n"
@@ -104,7 +110,8 @@ int main(int argc, char** argv) {
     if (subcmd != "--compute-logl" && subcmd != "--sample" && subcmd != "--pipeline" && subcmd != "--asr" &&
         subcmd != "--marginals" && subcmd != "--marginals-pipeline" && subcmd != "--naive-probs" &&
         subcmd != "--naive-probs-pipeline" && subcmd != "--lineage-pipeline" && subcmd != "--weighted-lineage-pipeline" &&
-        subcmd != "--viterbi" && subcmd != "--annotations-pipeline")
+        subcmd != "--viterbi" && subcmd != "--annotations-pipeline" && subcmd != "--codon-marginals" &&
+        subcmd != "--codon-marginals-pipeline")
       throw std::invalid_argument("'" + subcmd + "' is not a valid subcommand.");
     const std::string yaml_path = a.one("yaml-path");
     const int cluster_ind = std::stoi(a.one("cluster-ind"));
@@ -123,7 +130,8 @@ int main(int argc, char** argv) {
         pos = comma + 1;
       }
       if (device_list.size() > 1 && (subcmd == "--marginals-pipeline" || subcmd == "--naive-probs-pipeline" ||
-                                     subcmd == "--weighted-lineage-pipeline" || subcmd == "--annotations-pipeline"))
+                                     subcmd == "--weighted-lineage-pipeline" || subcmd == "--annotations-pipeline" ||
+                                     subcmd == "--codon-marginals-pipeline"))
         throw std::invalid_argument(subcmd + " runs on one device: --devices may list only one");
       if (device_list.size() > 1 && subcmd != "--pipeline")
         std::fprintf(stderr, "linearham: %s evaluates on one device; of --devices only device %d is used\n", subcmd.c_str(),
@@ -162,6 +170,11 @@ int main(int argc, char** argv) {
     if (subcmd == "--marginals-pipeline") {
       phylo_hmm_ptr->RunMarginalsPipeline(a.one("input-path"), a.one("output-path"), num_rates,
                                           std::stod(a.opt("burnin-frac", "0")));
+      return EXIT_SUCCESS;
+    }
+    if (subcmd == "--codon-marginals-pipeline") {
+      phylo_hmm_ptr->RunCodonMarginalsPipeline(a.one("input-path"), a.one("output-path"), num_rates,
+                                               std::stod(a.opt("burnin-frac", "0")), std::stoi(a.opt("frame", "0")));
       return EXIT_SUCCESS;
     }
     if (subcmd == "--naive-probs-pipeline") {
@@ -210,6 +223,11 @@ int main(int argc, char** argv) {
       std::string line = buf;
       phylo_hmm_ptr->AppendAnnotationColumns(line, s);
       std::cout << "log_path\tlog_path_posterior\tlh_loglik\t" << phylo_hmm_ptr->AnnotationHeader() << "\n" << line << "\n";
+    } else if (subcmd == "--codon-marginals") {
+      const linearham::PhyloHMM::CodonMarginalsResult m = phylo_hmm_ptr->NaiveCodonMarginals(std::stoi(a.opt("frame", "0")));
+      linearham::PhyloHMM::WriteCodonTable(std::cout, m);
+      std::cout << "\n";
+      linearham::PhyloHMM::WriteAminoAcidTable(std::cout, m);
     } else if (subcmd == "--marginals") {
       const linearham::PhyloHMM::NaiveMarginalsResult m = phylo_hmm_ptr->NaiveMarginals();
       linearham::PhyloHMM::WriteSiteTable(std::cout, m);

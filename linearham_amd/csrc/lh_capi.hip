@@ -34,6 +34,7 @@ const DebugOptions& debug_options() {
     o.k1_segments = set("LH_K1_SEGMENTS");
     o.k1_seg_waves = num("LH_K1_SEG_WAVES", o.k1_seg_waves);
     o.k1_no_fuse = set("LH_K1_NO_FUSE");
+    o.codon_blocks = std::max(1, num("LH_CODON_BLOCKS", o.codon_blocks));
     o.collect_hash_bits = std::min(64, std::max(1, num("LH_COLLECT_HASH_BITS", o.collect_hash_bits)));
     return o;
   }();
@@ -181,6 +182,32 @@ struct ViterbiWs {  // K8 (lh_viterbi.hip): the back-pointers, and the arrays th
   DevBuf paths, first_bad;  // lh_family_set_candidate_paths
 };
 
+// K9 (lh_codon.hip).  CodonSource: what lh_family_set_codons needs of the caller's descriptor (the bases and sites the
+// states write), kept on the host by lh_family_create.
+struct CodonSegments {
+  std::vector<int32_t> offsets, inds;
+};
+struct CodonSourceJunction {
+  std::vector<int32_t> left_xmsa, right_xmsa, nti_xmsa;  // [W][nL], [W][nR], [W][nR][4] caller columns
+};
+struct CodonSource {
+  bool have = false;
+  std::vector<int32_t> site;  // [n_xmsa]
+  std::vector<uint8_t> base;  // [n_xmsa]
+  CodonSegments v, d, j;
+  CodonSourceJunction vd, dj;
+};
+struct CodonWs {
+  int32_t frame = -1;  // -1: lh_family_set_codons has not been called (or its last call failed)
+  int32_t n_codons = 0;
+  std::vector<int32_t> window_codon;
+  lh::CodonTables tab{};
+  DevBuf win, codes;                              // the tables
+  DevBuf scratch, fwd, loglik, windows, genes;    // K9's arrays the caller does not hand in
+  DevBuf weights, stats, partial_w, partial_g;
+  DevBuf out_wsum, out_gsum;                      // lh_eval_codons_batch's device copies of the weighted sums
+};
+
 struct CandidateWs {
   lh_family* twin = nullptr;
   std::string twin_error;  // why there is no twin
@@ -267,6 +294,8 @@ struct lh_family {
   PosteriorWs post;
   CandidateWs cand;
   ViterbiWs vit;
+  CodonSource codon_src;
+  CodonWs codon;
   CollectWs collect;
   LineageWs lineage;
   // forward arrays that stay on the device, shared by K4 and K5 in both their forms: K4 draws from them, K5 overwrites
@@ -282,6 +311,7 @@ struct lh_family {
   KernelTimer<1> prior_timer, cand_timer;  // K6a, K6b
   KernelTimer<1> collect_timer;             // K6c
   KernelTimer<1> vit_timer;                 // K8
+  KernelTimer<1> codon_timer;               // K9
   KernelTimer<1> lineage_timer;             // K7
   KernelTimer<5> chain_timer;               // lh_eval_lineage_batch: K0, K1, K2 + K4 + K6c, K3, K7
   bool extended = false;  // lh_family_set_extended_range
@@ -1008,6 +1038,30 @@ int lh_family_create(const lh_family_desc* desc, lh_family** out) {
       f->dev = static_cast<lh::DevFamily*>(p);
       f->allocs.push_back(p);
     }
+  }
+  if (!rc && desc->n_seqs > 0) {
+    // K9's source tables (lh_family_set_codons)
+    CodonSource& cs = f->codon_src;
+    cs.site.assign(desc->xmsa_site, desc->xmsa_site + C);
+    cs.base.assign(desc->xmsa_naive_base, desc->xmsa_naive_base + C);
+    auto seg = [](const lh_segments& s, CodonSegments* o) {
+      o->offsets.assign(s.offsets, s.offsets + s.n_genes + 1);
+      o->inds.assign(s.xmsa_inds, s.xmsa_inds + s.offsets[s.n_genes]);
+    };
+    auto junc = [](const lh_junction& j, CodonSourceJunction* o) {
+      const size_t W = j.n_rows, nL = j.n_left, nR = j.n_right;
+      o->left_xmsa.assign(j.left_xmsa, j.left_xmsa + W * nL);
+      o->right_xmsa.assign(j.right_xmsa, j.right_xmsa + W * nR);
+      o->nti_xmsa.assign(j.nti_xmsa, j.nti_xmsa + W * nR * 4);
+    };
+    seg(desc->vgerm, &cs.v);
+    seg(desc->jgerm, &cs.j);
+    junc(desc->vd, &cs.vd);
+    if (h.has_d) {
+      seg(desc->dgerm, &cs.d);
+      junc(desc->dj, &cs.dj);
+    }
+    cs.have = true;
   }
   if (!rc && desc->n_seqs > 0) {
     // K6a's twin (CandidateWs); a family it cannot be made for still evaluates, and lh_family_set_candidates says why
@@ -2630,6 +2684,248 @@ int lh_viterbi_profile_read(lh_family* f, double* ms, int64_t* n_launches) {
   if (!f) return fail("null family");
   DeviceGuard guard(f);
   return f->vit_timer.read(ms, n_launches);
+}
+
+// ---- K9: exact posterior distributions of the naive sequence's codons (lh_codon.hip) ----
+
+int lh_family_set_codons(lh_family* f, int32_t frame) {
+  const std::string W = "lh_family_set_codons";
+  if (!f) return fail(W + ": null family");
+  DeviceGuard guard(f);
+  if (frame < 0 || frame > 2) return fail(W + ": frame must be 0, 1 or 2");
+  if (!f->have_sampler) return fail(W + ": lh_family_set_sampler has not been called");
+  const CodonSource& cs = f->codon_src;
+  if (!cs.have) return fail(W + ": family was created without an MSA (forward-only)");
+  const lh::DevFamily& h = f->host;
+  const bool has_d = h.has_d != 0;
+  const int L = h.n_sites, nV = h.vgerm.n_genes, nD = has_d ? h.dgerm.n_genes : 0, nJ = h.jgerm.n_genes;
+  const int Wvd = h.vd.n_rows, Wdj = has_d ? h.dj.n_rows : 0;
+  // the alignment site of every junction row (the NTI states have a column on each)
+  auto row_sites = [&](const CodonSourceJunction& j, int rows, int nR, int* site0) {
+    for (int i = 0; i < rows; ++i) {
+      const int32_t c = j.nti_xmsa[(size_t)i * nR * 4];
+      if (c < 0) return fail(W + ": a junction row without an NTI column");
+      if (i == 0) *site0 = cs.site[c];
+      else if (cs.site[c] != *site0 + i) return fail(W + ": the rows of a junction are not on consecutive sites");
+    }
+    return *site0 < 0 || *site0 + rows > L ? fail(W + ": junction rows outside the alignment") : 0;
+  };
+  int vs0 = 0, ds0 = 0;
+  if (row_sites(cs.vd, Wvd, h.vd.n_right, &vs0)) return 1;
+  if (has_d) {
+    if (row_sites(cs.dj, Wdj, h.dj.n_right, &ds0)) return 1;
+    if (ds0 < vs0 + Wvd) return fail(W + ": the junctions overlap");
+    if (ds0 == vs0 + Wvd)
+      return fail(W + ": the D region has no alignment site of its own between the two junctions (d_l[1] == d_r[0]): a codon "
+                      "would span more than three chain positions");
+  }
+  // chain positions: V | V-D rows | D | D-J rows | J
+  const int n_pos = has_d ? Wvd + Wdj + 3 : Wvd + 2;
+  const int q_d = Wvd + 1, q_j = n_pos - 1;
+  std::vector<int32_t> pos(std::max(L, 1));
+  for (int s = 0; s < L; ++s) {
+    if (s < vs0) pos[s] = 0;
+    else if (s < vs0 + Wvd) pos[s] = 1 + (s - vs0);
+    else if (!has_d) pos[s] = q_j;
+    else if (s < ds0) pos[s] = q_d;
+    else if (s < ds0 + Wdj) pos[s] = q_d + 1 + (s - ds0);
+    else pos[s] = q_j;
+  }
+  // the base every gene of a region writes on every site (N where it writes none)
+  auto gene_bases = [&](const CodonSegments& g, int n_genes, int q, std::vector<uint8_t>* gb) {
+    gb->assign((size_t)n_genes * std::max(L, 1), 4);
+    for (int k = 0; k < n_genes; ++k)
+      for (int x = g.offsets[k]; x < g.offsets[k + 1]; ++x) {
+        const int s = cs.site[g.inds[x]];
+        if (pos[s] != q) return fail(W + ": a germline gene writes a site outside its region");
+        (*gb)[(size_t)k * L + s] = cs.base[g.inds[x]];
+      }
+    return 0;
+  };
+  std::vector<uint8_t> gb_v, gb_d, gb_j;
+  if (gene_bases(cs.v, nV, 0, &gb_v) || (has_d && gene_bases(cs.d, nD, q_d, &gb_d)) || gene_bases(cs.j, nJ, q_j, &gb_j))
+    return 1;
+  // the code pool: first the base every compact entry of every junction row writes
+  std::vector<uint8_t> codes;
+  auto row_codes = [&](const CodonSourceJunction& j, int rows, int nL, int nR, std::vector<int32_t>* off) {
+    for (int i = 0; i < rows; ++i) {
+      off->push_back((int32_t)codes.size());
+      for (int l = 0; l < nL; ++l) {
+        const int32_t c = j.left_xmsa[(size_t)i * nL + l];
+        codes.push_back(c >= 0 ? cs.base[c] : 4);
+      }
+      for (int r = 0; r < nR; ++r)
+        for (int a = 0; a < 4; ++a) codes.push_back((uint8_t)a);
+      for (int r = 0; r < nR; ++r) {
+        const int32_t c = j.right_xmsa[(size_t)i * nR + r];
+        codes.push_back(c >= 0 ? cs.base[c] : 4);
+      }
+    }
+  };
+  std::vector<int32_t> off_vd, off_dj;
+  row_codes(cs.vd, Wvd, h.vd.n_left, h.vd.n_right, &off_vd);
+  if (has_d) row_codes(cs.dj, Wdj, h.dj.n_left, h.dj.n_right, &off_dj);
+  auto is_row = [&](int q) { return (q >= 1 && q <= Wvd) || (has_d && q > q_d && q < q_j); };
+  const int n_codons = L >= frame ? (L - frame) / 3 : 0;
+  std::vector<lh::CodonWindow> wins;
+  std::vector<int32_t> window_codon;
+  static const int kPow5[3] = {1, 5, 25};
+  for (int c = 0; c < n_codons; ++c) {
+    const int s0 = frame + 3 * c;
+    if (!is_row(pos[s0]) && !is_row(pos[s0 + 1]) && !is_row(pos[s0 + 2])) continue;
+    lh::CodonWindow w{};
+    for (int o = 0; o < 3;) {
+      const int q = pos[s0 + o];
+      int o_last = o;
+      while (o_last + 1 < 3 && pos[s0 + o_last + 1] == q) ++o_last;
+      const int k = o_last - o + 1, slot = w.npos;
+      if (slot >= 3 || k > 2 || (slot > 0 && q != w.top + 1)) return fail(W + ": internal error (codon window)");
+      w.top = q;
+      w.mult[slot] = kPow5[2 - o_last];
+      w.ncodes[slot] = kPow5[k];
+      if (is_row(q)) {
+        w.code_off[slot] = q <= Wvd ? off_vd[q - 1] : off_dj[q - q_d - 1];
+      } else {
+        const std::vector<uint8_t>& gb = q == 0 ? gb_v : q == q_j ? gb_j : gb_d;
+        const int ng = q == 0 ? nV : q == q_j ? nJ : nD;
+        w.code_off[slot] = (int32_t)codes.size();
+        for (int g = 0; g < ng; ++g) {
+          const uint8_t* b = gb.data() + (size_t)g * L + s0;
+          codes.push_back(k == 1 ? b[o] : (uint8_t)(5 * b[o] + b[o + 1]));
+        }
+      }
+      ++w.npos;
+      o = o_last + 1;
+    }
+    if (w.npos < 2) return fail(W + ": internal error (codon window of one position)");
+    w.out = (int32_t)window_codon.size();
+    window_codon.push_back(c);
+    wins.push_back(w);
+  }
+  std::reverse(wins.begin(), wins.end());  // by top, descending: the order the backward recursion meets them
+  CodonWs& cw = f->codon;
+  cw.frame = -1;
+  if (cw.win.ensure(sizeof(lh::CodonWindow) * wins.size()) || cw.codes.ensure(codes.size())) return 1;
+  LH_HIP(hipDeviceSynchronize());  // queued work may still read the old tables
+  if (!wins.empty())
+    LH_HIP(hipMemcpy(cw.win.get(), wins.data(), sizeof(lh::CodonWindow) * wins.size(), hipMemcpyHostToDevice));
+  if (!codes.empty()) LH_HIP(hipMemcpy(cw.codes.get(), codes.data(), codes.size(), hipMemcpyHostToDevice));
+  cw.tab = lh::CodonTables{};
+  cw.tab.n_window = (int32_t)wins.size();
+  cw.tab.n_genes = nV + nD + nJ;
+  cw.tab.n_pos = n_pos;
+  cw.tab.max_vec = std::max({nV, nD, nJ, h.vd.n_left + 5 * h.vd.n_right, has_d ? h.dj.n_left + 5 * h.dj.n_right : 0});
+  cw.tab.win = cw.win.get<const lh::CodonWindow>();
+  cw.tab.codes = cw.codes.get<const uint8_t>();
+  cw.n_codons = n_codons;
+  cw.window_codon = window_codon;
+  cw.frame = frame;
+  return 0;
+}
+
+int lh_codon_layout(const lh_family* f, int32_t* n_codons, int32_t* n_window, int32_t* window_codon, int32_t* n_genes) {
+  if (!f) return fail("lh_codon_layout: null family");
+  const CodonWs& cw = f->codon;
+  if (cw.frame < 0) return fail("lh_codon_layout: lh_family_set_codons has not been called");
+  if (n_codons) *n_codons = cw.n_codons;
+  if (n_window) *n_window = cw.tab.n_window;
+  if (window_codon) std::copy(cw.window_codon.begin(), cw.window_codon.end(), window_codon);
+  if (n_genes) *n_genes = cw.tab.n_genes;
+  return 0;
+}
+
+int lh_eval_codons_batch_device(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops,
+                                const double* brlen, const double* er, const double* pi, const double* alpha, int32_t R,
+                                const lh_codon_outputs* outs, void* hip_stream) {
+  const std::string W = "lh_eval_codons_batch_device";
+  if (f && f->have_sampler && f->codon.frame < 0) return fail(W + ": lh_family_set_codons has not been called");
+  if (int rc = check_batch(f, W, n, T, R, max_depth, true)) return rc > 0;
+  DeviceGuard guard(f);
+  hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+  const lh_codon_outputs none{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  const lh_codon_outputs& o = outs ? *outs : none;
+  CodonWs& cw = f->codon;
+  const lh::CodonTables& tab = cw.tab;
+  const size_t FS = f->host.forward_size, NW = (size_t)tab.n_window * 125, NG = tab.n_genes;
+  auto own = [](double*& p, DevBuf& b, size_t bytes) {
+    if (!p && b.ensure(bytes)) return 1;
+    if (!p) p = b.get<double>();
+    return 0;
+  };
+  double *ll = o.loglik, *win = o.windows, *gen = o.genes, *w = nullptr, *stats = o.weight_stats, *pw = nullptr, *pg = nullptr;
+  const bool reduce = o.weighted_windows || o.weighted_genes || o.weight_stats;
+  const size_t slabs = lh::posterior_slabs(n);
+  // the forward arrays stay in the handle's buffer: K9 only reads them
+  if (f->forward_dev.ensure(sizeof(double) * FS * n) || own(ll, cw.loglik, sizeof(double) * n) ||
+      own(win, cw.windows, sizeof(double) * NW * n) || own(gen, cw.genes, sizeof(double) * NG * n) ||
+      cw.scratch.ensure(sizeof(double) * 4 * (size_t)tab.max_vec * lh::codon_slots(n)) ||
+      (reduce && (own(w, cw.weights, sizeof(double) * n) || own(stats, cw.stats, sizeof(double) * 3) ||
+                  (o.weighted_windows && own(pw, cw.partial_w, sizeof(double) * NW * slabs)) ||
+                  (o.weighted_genes && own(pg, cw.partial_g, sizeof(double) * NG * slabs)))))
+    return 1;
+  double* fwd = f->forward_dev.get<double>();
+  lh_eval_outputs eo{nullptr, nullptr, fwd, nullptr};
+  if (lh_eval_batch_device(f, n, T, max_depth, ops, brlen, er, pi, alpha, R, ll, &eo, hip_stream)) return 1;
+  if (f->profile && f->codon_timer.begin(stream)) return 1;
+  lh::launch_codons(f->sampler_dev, tab, n, fwd, FS, ll, cw.scratch.get<double>(), win, gen, stream);
+  if (reduce) {
+    lh::launch_posterior_reduce(n, 0, nullptr, ll, o.log_offset, w, nullptr, nullptr, stats, stream);
+    if (o.weighted_windows) lh::launch_weighted_slabs(n, NW, win, w, pw, o.weighted_windows, stream);
+    if (o.weighted_genes) lh::launch_weighted_slabs(n, NG, gen, w, pg, o.weighted_genes, stream);
+  }
+  if (f->profile && f->codon_timer.end(stream)) return 1;
+  LH_HIP(hipGetLastError());
+  return 0;
+}
+
+int lh_eval_codons_batch(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops, const double* brlen,
+                         const double* er, const double* pi, const double* alpha, int32_t R, const lh_codon_outputs* outs) {
+  const std::string W = "lh_eval_codons_batch";
+  if (f && f->have_sampler && f->codon.frame < 0) return fail(W + ": lh_family_set_codons has not been called");
+  if (int rc = check_batch(f, W, n, T, R, max_depth, true)) return rc > 0;
+  DeviceGuard guard(f);
+  if (!ops || !brlen || !er || !pi || !alpha) return fail(W + ": null array");
+  const lh_codon_outputs none{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  const lh_codon_outputs& o = outs ? *outs : none;
+  if (!o.loglik && !o.windows && !o.genes && !o.weighted_windows && !o.weighted_genes && !o.weight_stats) return 0;
+  CodonWs& cw = f->codon;
+  const size_t nodes = 2 * (size_t)T - 2, n_ops = (size_t)T - 2;
+  const size_t NW = (size_t)cw.tab.n_window * 125, NG = cw.tab.n_genes;
+  HostInputs& in = f->in;
+  HostOutputs& out = f->out;
+  lh_codon_outputs dev{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  if (out.loglik.ensure(sizeof(double) * n) || out_buf(o.windows, cw.windows, sizeof(double) * NW * n, &dev.windows) ||
+      out_buf(o.genes, cw.genes, sizeof(double) * NG * n, &dev.genes) ||
+      out_buf(o.weighted_windows, cw.out_wsum, sizeof(double) * NW, &dev.weighted_windows) ||
+      out_buf(o.weighted_genes, cw.out_gsum, sizeof(double) * NG, &dev.weighted_genes) ||
+      out_buf(o.weight_stats, out.weight_stats, sizeof(double) * 3, &dev.weight_stats) ||
+      stage_inputs(f, {{ops, sizeof(int32_t) * 4 * n_ops * n, &in.ops},
+                       {brlen, sizeof(double) * nodes * n, &in.brlen},
+                       {er, sizeof(double) * 6 * n, &in.er},
+                       {pi, sizeof(double) * 4 * n, &in.pi},
+                       {alpha, sizeof(double) * n, &in.alpha},
+                       {o.log_offset, sizeof(double) * n, &in.log_offset}}))
+    return 1;
+  dev.log_offset = o.log_offset ? in.log_offset.get<const double>() : nullptr;
+  dev.loglik = out.loglik.get<double>();
+  if (lh_eval_codons_batch_device(f, n, T, max_depth, in.ops.get<const int32_t>(), in.brlen.get<const double>(),
+                                  in.er.get<const double>(), in.pi.get<const double>(), in.alpha.get<const double>(), R, &dev,
+                                  nullptr))
+    return 1;
+  if (!valid_schedules(ops, (size_t)n, T, (int)nodes, max_depth)) return refuse_schedules(f, "lh_eval_codons_batch");
+  return copy_back(f, "lh_eval_codons_batch",
+                   {{o.loglik, dev.loglik, sizeof(double) * n},
+                    {o.windows, dev.windows, sizeof(double) * NW * n},
+                    {o.genes, dev.genes, sizeof(double) * NG * n},
+                    {o.weighted_windows, dev.weighted_windows, sizeof(double) * NW},
+                    {o.weighted_genes, dev.weighted_genes, sizeof(double) * NG},
+                    {o.weight_stats, dev.weight_stats, sizeof(double) * 3}});
+}
+
+int lh_codon_profile_read(lh_family* f, double* ms, int64_t* n_launches) {
+  if (!f) return fail("null family");
+  DeviceGuard guard(f);
+  return f->codon_timer.read(ms, n_launches);
 }
 
 }  // extern "C"

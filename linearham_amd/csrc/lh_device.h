@@ -186,6 +186,32 @@ void launch_posterior_reduce(int n, size_t forward_size, const double* post, con
                              double* w, double* partial, double* weighted_sum, double* stats, hipStream_t stream);
 // out[j] = sum over k < n_slabs, in order, of partial[k][j] (K5's last reduction step; K6b's too)
 void launch_slab_sum(int n_slabs, size_t size, const double* partial, double* out, hipStream_t stream);
+// K5's slab reduction alone, for weights launch_posterior_reduce has already written: weighted_sum[size] = sum_i w_i
+// rows[i][0..size) through partial[posterior_slabs(n)][size] (K9 reduces two arrays with one set of weights)
+void launch_weighted_slabs(int n, size_t size, const double* rows, const double* w, double* partial, double* weighted_sum,
+                           hipStream_t stream);
+
+// K9 (lh_codon.hip): exact posterior distributions of the naive sequence's codons that touch a junction row ("window
+// codons"), and the sample's V / D / J gene posteriors, from the compact forward arrays (read only).
+// Chain positions: 0 = V genes, 1 .. W_vd = V-D rows, then (igh) D genes, D-J rows, J genes; light chains V | rows | J.
+// A window covers npos = 2 or 3 consecutive positions, slot 0 the lowest.  A position's entries (the compact layout's: genes of
+// a region, or left | NTI x 4 | right of a row) carry a local code each, codes[code_off[slot] + entry] < ncodes[slot] (5: one
+// base; 25: 5 * first base + second base of a germline gene that writes two of the codon's sites); the codon index
+// 25 b1 + 5 b2 + b3 of a triple of entries is sum_slot mult[slot] * code.
+struct CodonWindow {
+  int32_t npos, top, out;  // top: chain position of the highest slot; out: index of the window in the output
+  int32_t mult[3], ncodes[3], code_off[3];
+};
+struct CodonTables {
+  int32_t n_window, n_genes, n_pos;
+  int32_t max_vec;             // entries of the largest position vector
+  const CodonWindow* win;      // [n_window], by `top` descending
+  const uint8_t* codes;        // the code pool
+};
+int codon_slots(int n);  // samples that are in flight at once: scratch[codon_slots(n)][4][max_vec] doubles
+// windows[n][n_window][125], genes[n][n_genes] (V | D | J); NaN for a sample whose loglik is not finite
+void launch_codons(const DevSampler* smp_dev, const CodonTables& t, int n, const double* fwd, size_t forward_size,
+                   const double* loglik, double* scratch, double* windows, double* genes, hipStream_t stream);
 
 // K6 (lh_naive_probs.hip): exact posterior probabilities of candidate naive sequences.
 // K6a: em[k][c] = 1 where candidate k has the naive base of the caller's column c at its site, else 0 (the
@@ -422,6 +448,7 @@ struct DebugOptions {
   bool k1_segments = false;    // LH_K1_SEGMENTS: the segmented tip table (large trees) on small trees too
   int k1_seg_waves = 4;        // LH_K1_SEG_WAVES=<4|5>: register budget of the segmented kernels
   bool k1_no_fuse = false;     // LH_K1_NO_FUSE: one workgroup per (sample, rate)
+  int codon_blocks = 2048;     // LH_CODON_BLOCKS=<n>: K9's workgroup cap (tests: a lane group walks several samples in a small call)
   int collect_hash_bits = 64;  // LH_COLLECT_HASH_BITS=<n>: K6c's row hashes masked to n bits (tests: collisions common,
                                // the exact resolution runs; results unchanged)
 };

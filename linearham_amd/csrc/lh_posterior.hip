@@ -45,6 +45,8 @@ __device__ inline double group_sum(double v) {
 // the ratio pi / Z of one successor, 0 where pi is 0 (Z may be 0 there)
 __device__ inline double ratio(double p, double z) { return p != 0.0 ? p / z : 0.0; }
 
+// (K9, lh_codon.hip, carries out-of-place, masked twins of the three step forms below -- step_row, step_last, step_left:
+// a change of the transition arithmetic here belongs there too.)
 // Junction row i = 0 .. W-2: post_row holds the forward row i on entry and pi_i on exit; next = pi_{i+1}.
 __device__ void smooth_row(const DevSampleJunction& J, int i, double* __restrict__ row, const double* __restrict__ next,
                            int gl) {
@@ -292,14 +294,19 @@ void launch_slab_sum(int n_slabs, size_t size, const double* partial, double* ou
                      n_slabs, size, partial, out);
 }
 
+void launch_weighted_slabs(int n, size_t size, const double* rows, const double* w, double* partial, double* weighted_sum,
+                           hipStream_t stream) {
+  if (size == 0) return;
+  const int slabs = posterior_slabs(n);
+  const unsigned bx = (unsigned)((size + kRedThreads - 1) / kRedThreads);
+  hipLaunchKernelGGL(slab_kernel, dim3(bx, slabs), dim3(kRedThreads), 0, stream, n, size, rows, w, partial);
+  hipLaunchKernelGGL(slab_sum_kernel, dim3(bx), dim3(kRedThreads), 0, stream, slabs, size, partial, weighted_sum);
+}
+
 void launch_posterior_reduce(int n, size_t forward_size, const double* post, const double* loglik, const double* log_offset,
                              double* w, double* partial, double* weighted_sum, double* stats, hipStream_t stream) {
   hipLaunchKernelGGL(weight_kernel, dim3(1), dim3(kRedThreads), 0, stream, n, loglik, log_offset, w, stats);
-  if (!weighted_sum) return;
-  const int slabs = posterior_slabs(n);
-  const unsigned bx = (unsigned)((forward_size + kRedThreads - 1) / kRedThreads);
-  hipLaunchKernelGGL(slab_kernel, dim3(bx, slabs), dim3(kRedThreads), 0, stream, n, forward_size, post, w, partial);
-  hipLaunchKernelGGL(slab_sum_kernel, dim3(bx), dim3(kRedThreads), 0, stream, slabs, forward_size, partial, weighted_sum);
+  if (weighted_sum) launch_weighted_slabs(n, forward_size, post, w, partial, weighted_sum, stream);
 }
 
 }  // namespace lh

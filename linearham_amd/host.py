@@ -82,6 +82,37 @@ def read_marginals(prefix):
     return sb, genes, summary
 
 
+def _parse_aa_table(text, n_codons):
+    aa = [dict() for _ in range(n_codons)]
+    for ln in text.strip("\n").split("\n")[1:]:
+        c, a, p = ln.split("\t")
+        aa[int(c)][a] = float(p)
+    return aa
+
+
+def parse_codon_tables(codon_text, aa_text):
+    """(table [n_codons][125], [per codon {amino acid: p}]) from the texts WriteCodonTable / WriteAminoAcidTable print
+    (every codon has an entry above 0, so the last line names the last codon)."""
+    from . import posterior
+    rows = [ln.split("\t") for ln in codon_text.strip("\n").split("\n")[1:]]
+    n_codons = int(rows[-1][0]) + 1 if rows else 0
+    table = np.zeros((n_codons, 125))
+    for c, site, bases, p in rows:
+        i = [posterior.BASES.index(b) for b in bases]
+        table[int(c), 25 * i[0] + 5 * i[1] + i[2]] = float(p)
+    return table, _parse_aa_table(aa_text, n_codons)
+
+
+def read_codon_marginals(prefix):
+    """(table [n_codons][125], [per codon {amino acid: p}], summary dict) from the files RunCodonMarginalsPipeline writes."""
+    table, aa = parse_codon_tables(open(prefix + ".codons.tsv").read(), open(prefix + ".aa.tsv").read())
+    summary = {}
+    for ln in open(prefix + ".summary.tsv").read().strip().split("\n")[1:]:
+        k, v = ln.split("\t")
+        summary[k] = float(v) if k == "kish_ess" else int(v)
+    return table, aa, summary
+
+
 def read_naive_probs(prefix):
     """The files RunNaiveProbsPipeline writes: dict(naive = list of row dicts of <prefix>.naive.tsv in rank order
     (probability / log_prior floats, sampled_count int or None, sampled_frequency float or None), aa = [(name, p, aa)]
@@ -360,6 +391,25 @@ class PhyloHMM(_HMM):
         _check(self.lib.lhh_run_marginals_pipeline(self.h, input_path.encode(), output_prefix.encode(), num_rates,
                                                    C.c_double(burnin_frac)))
         return read_marginals(output_prefix)
+
+    def naive_codon_marginals(self, frame=0):
+        """(table [n_codons][125] over 25 b1 + 5 b2 + b3, [per codon {amino acid: p}]) of the current tree
+        (PhyloHMM::NaiveCodonMarginals, K9)."""
+        f = self.lib.lhh_phylo_codon_marginals
+        f.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_char_p)]
+        n, out = C.c_int(), C.c_char_p()
+        _check(f(self.h, frame, None, 0, C.byref(n), C.byref(out)))
+        table = np.zeros((n.value, 125))
+        _check(f(self.h, frame, table.ctypes.data, n.value, C.byref(n), C.byref(out)))
+        return table, _parse_aa_table(out.value.decode(), n.value)
+
+    def run_codon_marginals_pipeline(self, input_path, output_prefix, num_rates, burnin_frac=0.0, frame=0):
+        """PhyloHMM::RunCodonMarginalsPipeline: importance-weighted exact codon and amino-acid tables over a RevBayes
+        table.  Writes <prefix>.codons.tsv, .aa.tsv and .summary.tsv and returns read_codon_marginals(prefix)."""
+        f = self.lib.lhh_run_codon_marginals_pipeline
+        f.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_int, C.c_double, C.c_int]
+        _check(f(self.h, input_path.encode(), output_prefix.encode(), num_rates, C.c_double(burnin_frac), frame))
+        return read_codon_marginals(output_prefix)
 
     def viterbi_annotation(self):
         """The most probable annotation of the current tree (PhyloHMM::ViterbiAnnotation, K8): (dict of the annotation

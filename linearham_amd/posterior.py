@@ -153,3 +153,116 @@ def combine(parts):
 
 def kish_ess(s1, s2):
     return s1 * s1 / s2 if s2 > 0 else 0.0
+
+
+# ---- K9: codon and amino-acid tables ----
+# A codon's 125 entries are indexed 25 b1 + 5 b2 + b3 over BASES.  The device writes the codons that have a site in a
+# junction row (the "window" codons) and the gene posteriors; a codon inside one germline region is a linear map of that
+# region's gene posterior (each gene writes its three bases there, N where it writes none).
+
+def _site_regions(ss):
+    """Per alignment site the germline region that owns it ("vgerm" / "dgerm" / "jgerm"), or None for a junction row."""
+    L = len(ss["msa"][0])
+    juncs = _junctions(ss)
+    out = [None] * L
+    bounds = []
+    for jname, gl, gr, site0, W in juncs:
+        bounds.append((site0, site0 + W, gl, gr))
+    for s in range(L):
+        reg = bounds[0][2]
+        for lo, hi, gl, gr in bounds:
+            if s >= hi:
+                reg = gr
+            elif s >= lo:
+                reg = None
+                break
+        out[s] = reg
+    return out
+
+
+def codon_layout(ss, frame):
+    """The layout lh_codon_layout reports, from the state space alone: dict(frame, n_codons, window_codon, n_genes)."""
+    if frame not in (0, 1, 2):
+        raise ValueError("frame must be 0, 1 or 2")
+    L = len(ss["msa"][0])
+    reg = _site_regions(ss)
+    n_codons = (L - frame) // 3 if L >= frame else 0
+    window = [c for c in range(n_codons) if any(reg[frame + 3 * c + o] is None for o in range(3))]
+    blocks, _ = layout(ss)
+    n_genes = sum(len(info) for kind, _, _, info in blocks if kind == "germ")
+    return dict(frame=frame, n_codons=n_codons, window_codon=window, n_genes=n_genes)
+
+
+def _gene_site_bases(ss, region):
+    """[n_genes][L] base each gene of a germline region writes on each site (4 = N where it writes none), genes in the
+    compact layout's (sorted) order."""
+    L = len(ss["msa"][0])
+    ranges, sites, bases = (ss[region + "_" + f] for f in ("ggene_ranges", "site_inds", "naive_bases"))
+    names = sorted(ranges)
+    out = np.full((len(names), L), 4, dtype=np.int64)
+    for g, name in enumerate(names):
+        rs, re_ = ranges[name]
+        for k in range(rs, re_):
+            out[g, sites[k]] = bases[k]
+    return out
+
+
+def codon_table(ss, windows, genes, lay):
+    """[n_codons][125] from the device's windows [n_window][125] and gene posteriors [n_genes] (V | D | J) under the layout
+    `lay` (codon_layout, or capi's codon_layout of the handle plus its frame)."""
+    windows = np.asarray(windows, dtype=np.float64).reshape(-1, 125)
+    genes = np.asarray(genes, dtype=np.float64)
+    frame, n_codons = lay["frame"], lay["n_codons"]
+    wc = list(lay["window_codon"])
+    assert windows.shape[0] == len(wc) and genes.shape[-1] == lay["n_genes"]
+    table = np.zeros((n_codons, 125))
+    reg = _site_regions(ss)
+    regions = ["vgerm"] + (["dgerm"] if ss["locus"] == "igh" else []) + ["jgerm"]
+    off, gb, goff = 0, {}, {}
+    for r in regions:
+        gb[r] = _gene_site_bases(ss, r)
+        goff[r] = off
+        off += gb[r].shape[0]
+    is_window = set(wc)
+    for i, c in enumerate(wc):
+        table[c] = windows[i]
+    for c in range(n_codons):
+        if c in is_window:
+            continue
+        s0 = frame + 3 * c
+        r = reg[s0]
+        assert r is not None and reg[s0 + 1] == r and reg[s0 + 2] == r
+        b = gb[r][:, s0:s0 + 3]
+        np.add.at(table[c], 25 * b[:, 0] + 5 * b[:, 1] + b[:, 2], genes[goff[r]:goff[r] + b.shape[0]])
+    return table
+
+
+def codon_site_base(table, frame, L):
+    """The [L][5] per-site marginals a codon table implies on the sites its codons cover (other sites: NaN)."""
+    t = np.asarray(table).reshape(-1, 5, 5, 5)
+    sb = np.full((L, 5), np.nan)
+    for c in range(t.shape[0]):
+        sb[frame + 3 * c] = t[c].sum(axis=(1, 2))
+        sb[frame + 3 * c + 1] = t[c].sum(axis=(0, 2))
+        sb[frame + 3 * c + 2] = t[c].sum(axis=(0, 1))
+    return sb
+
+
+def codon_amino_acids():
+    """The amino acid of each of the 125 codons over BASES: the host library's TranslateDna (its N-codon rule included)."""
+    from . import host
+    aa = host.translate("".join(BASES[i // 25] + BASES[(i // 5) % 5] + BASES[i % 5] for i in range(125)))
+    assert len(aa) == 125
+    return aa
+
+
+def aa_table(table, aa_of_codon=None):
+    """Per codon {amino acid: probability} (entries above 0 only), folding a codon table with codon_amino_acids()."""
+    aa = aa_of_codon or codon_amino_acids()
+    out = []
+    for row in np.asarray(table).reshape(-1, 125):
+        d = {}
+        for i in np.nonzero(row)[0]:
+            d[aa[i]] = d.get(aa[i], 0.0) + float(row[i])
+        out.append(d)
+    return out

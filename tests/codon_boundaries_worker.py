@@ -1,0 +1,66 @@
+"""Helper of tests/test_gpu_codons_batch_boundaries.py: tests/batch_boundaries_worker.py's scheme for
+lh_eval_codons_batch, one case per child process (LH_CHUNK and LH_HOST_SUB are read once per process).
+
+    python -m tests.codon_boundaries_worker <case> <directory> key=value ...
+
+Prints one JSON line: {"failures": [...], "info": {...}}."""
+import os
+import sys
+
+import numpy as np
+
+from tests import batch_boundaries_worker as bw
+
+FRAME = 1  # a frame whose windows include every kind the family has
+
+
+def codons(F, pk, R=4):
+    ops, brl, er, pi, alpha = F.inputs(pk)
+    return F.hip.eval_codons_batch(F.fam, F.T, F.depth, ops, brl, er, pi, alpha, R,
+                                   log_offset=np.ascontiguousarray(F.rb[pk]))
+
+
+def build_anchors(d):
+    """The 23 anchor rows as one call: writes d/codon_anchors.npz and returns its contents with the layout."""
+    F = bw.Fam(d, "igh")
+    lay = F.hip.set_codons(F.fam, FRAME)
+    res = codons(F, np.arange(bw.N_SETS))
+    F.close()
+    out = {k: res[k] for k in ("loglik", "windows", "genes")}
+    np.savez(os.path.join(d, "codon_anchors.npz"), **out)
+    return out, lay
+
+
+def case_codons(d, rep, ns, G):
+    """lh_eval_codons_batch; group (LH_CHUNK) and slab (256) edges that coincide and miss."""
+    F = bw.Fam(d)
+    F.hip.set_codons(F.fam, FRAME)
+    A = np.load(os.path.join(d, "codon_anchors.npz"))
+    for n in ns:
+        pk = bw.pick(n, G)
+        what = "lh_eval_codons_batch n=%d" % n
+        res = codons(F, pk)
+        for k in ("windows", "genes", "loglik"):
+            rep.bits(what, k, res[k], A[k][pk], G)
+        for rows, key in ((res["windows"].reshape(n, -1), "weighted_windows"), (res["genes"], "weighted_genes")):
+            bw._check_reduction(rep, what + " " + key, n, dict(res, weighted_sum=res[key].reshape(-1)), rows, F.rb[pk])
+        again = codons(F, pk)
+        for k in ("weighted_windows", "weighted_genes", "weight_stats"):
+            rep.check(np.array_equal(again[k], res[k]), "%s %s: the same call twice gives different bits" % (what, k))
+    F.close()
+
+
+def main(argv):
+    case, d = argv[0], argv[1]
+    kw = {}
+    for a in argv[2:]:
+        k, v = a.split("=")
+        kw[k] = [int(x) for x in v.split(",")] if k == "ns" else int(v)
+    rep = bw.Report()
+    {"codons": case_codons}[case](d, rep, **kw)
+    rep.done()
+
+
+if __name__ == "__main__":
+    sys.path.insert(0, bw.ROOT)
+    main(sys.argv[1:])
