@@ -133,6 +133,13 @@ def library_path():
     return os.path.join(os.environ.get("LH_LIB_DIR") or os.path.join(_HERE, "lib"), "liblinearham_hip.so")
 
 
+# what every lh_*_batch (host pointers) / lh_*_batch_device (device addresses) entry point begins with: the handle, n,
+# n_tips, max_depth, ops, brlen, er, pi, alpha or rates, num_rates
+_HOST_TREE = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, c_i32p, c_f64p, c_f64p, c_f64p, c_f64p, C.c_int32]
+_DEV_TREE = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 5 + [C.c_int32]
+_PROFILE_READ = [C.c_void_p, c_f64p, C.POINTER(C.c_int64)]
+
+
 class HipLibrary:
     def __init__(self, path=None):
         path = path or library_path()
@@ -140,6 +147,7 @@ class HipLibrary:
             raise RuntimeError("HIP library %s is missing: run `python -c 'import __graft_entry__ as g; "
                                "g.build()'` (there is no CPU fallback)" % path)
         self.lib = lib = C.CDLL(path)
+        c_u32p, c_u64p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
         lib.lh_last_error.restype = C.c_char_p
         lib.lh_device_count.restype = C.c_int
         lib.lh_family_create.argtypes = [C.POINTER(_FamilyDesc), C.POINTER(C.c_void_p)]
@@ -158,92 +166,68 @@ class HipLibrary:
         lib.lh_family_forward_form.argtypes = [C.c_void_p]
         lib.lh_family_forward_form.restype = C.c_char_p
         lib.lh_schedule_tree.argtypes = [C.c_int32, c_i32p, C.c_int32, c_i32p, c_i32p]
-        lib.lh_eval_batch.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, c_i32p, c_f64p, c_f64p,
-                                      c_f64p, c_f64p, C.c_int32, c_f64p, C.POINTER(_EvalOutputs)]
-        lib.lh_eval_batch_device.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
-                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
-                                             C.c_void_p, C.POINTER(_EvalOutputs), C.c_void_p]
+        lib.lh_eval_batch.argtypes = _HOST_TREE + [c_f64p, C.POINTER(_EvalOutputs)]
+        lib.lh_eval_batch_device.argtypes = _DEV_TREE + [C.c_void_p, C.POINTER(_EvalOutputs), C.c_void_p]
         lib.lh_forward_batch.argtypes = [C.c_void_p, C.c_int32, c_f64p, c_f64p, C.POINTER(_EvalOutputs)]
-        lib.lh_asr_batch.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, c_i32p, c_f64p, c_f64p, c_f64p,
-                                     c_f64p, C.c_int32, c_u8p, C.c_uint64, C.c_uint64, c_u8p, c_u8p]
-        lib.lh_asr_batch_device.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
-                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_uint64,
-                                            C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
-        lib.lh_asr_profile_read.argtypes = [C.c_void_p, c_f64p, C.POINTER(C.c_int64)]
+        lib.lh_asr_batch.argtypes = _HOST_TREE + [c_u8p, C.c_uint64, C.c_uint64, c_u8p, c_u8p]
+        lib.lh_asr_batch_device.argtypes = _DEV_TREE + [C.c_void_p, C.c_uint64, C.c_uint64] + [C.c_void_p] * 3
+        lib.lh_asr_profile_read.argtypes = _PROFILE_READ
         lib.lh_profile_enable.argtypes = [C.c_void_p, C.c_int]
         lib.lh_family_set_extended_range.argtypes = [C.c_void_p, C.c_int]
         lib.lh_profile_read.argtypes = [C.c_void_p, c_f64p, c_f64p, c_f64p, C.POINTER(C.c_int64)]
         if hasattr(lib, "lh_eval_sample_batch_device"):
-            lib.lh_eval_sample_batch_device.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 5 + \
-                [C.c_int32] + [C.c_void_p] * 5
+            lib.lh_eval_sample_batch_device.argtypes = _DEV_TREE + [C.c_void_p] * 5
             lib.lh_sample_words.argtypes = [C.c_void_p]
             lib.lh_sample_states.argtypes = [C.c_void_p]
         if hasattr(lib, "lh_eval_posterior_batch"):
-            lib.lh_eval_posterior_batch.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, c_i32p, c_f64p, c_f64p,
-                                                    c_f64p, c_f64p, C.c_int32, C.POINTER(_PosteriorOutputs)]
-            lib.lh_eval_posterior_batch_device.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + \
-                [C.c_void_p] * 5 + [C.c_int32, C.POINTER(_PosteriorOutputs), C.c_void_p]
-            lib.lh_posterior_profile_read.argtypes = [C.c_void_p, c_f64p, C.POINTER(C.c_int64)]
-            lib.lh_forward_size.argtypes = [C.c_void_p]
+            lib.lh_eval_posterior_batch.argtypes = _HOST_TREE + [C.POINTER(_PosteriorOutputs)]
+            lib.lh_eval_posterior_batch_device.argtypes = _DEV_TREE + [C.POINTER(_PosteriorOutputs), C.c_void_p]
+            lib.lh_posterior_profile_read.argtypes = _PROFILE_READ
         if hasattr(lib, "lh_family_set_candidates"):
             lib.lh_family_set_candidates.argtypes = [C.c_void_p, C.c_int32, c_u8p, c_f64p]
-            lib.lh_eval_candidates_batch.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, c_i32p, c_f64p, c_f64p,
-                                                     c_f64p, c_f64p, C.c_int32, C.POINTER(_CandidateOutputs)]
-            lib.lh_eval_candidates_batch_device.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + \
-                [C.c_void_p] * 5 + [C.c_int32, C.POINTER(_CandidateOutputs), C.c_void_p]
-            lib.lh_candidates_profile_read.argtypes = [C.c_void_p, c_f64p, C.POINTER(C.c_int64)]
+            lib.lh_eval_candidates_batch.argtypes = _HOST_TREE + [C.POINTER(_CandidateOutputs)]
+            lib.lh_eval_candidates_batch_device.argtypes = _DEV_TREE + [C.POINTER(_CandidateOutputs), C.c_void_p]
+            lib.lh_candidates_profile_read.argtypes = _PROFILE_READ
             lib.lh_candidates_info.argtypes = [C.c_void_p, c_i32p, c_i32p]
             lib.lh_candidates_layout.argtypes = [C.c_void_p, c_i32p, c_i32p, c_i32p]
         if hasattr(lib, "lh_naive_sequences"):
-            c_u64p = C.POINTER(C.c_uint64)
-            lib.lh_eval_draw_batch.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, c_i32p, c_f64p, c_f64p,
-                                               c_f64p, c_f64p, C.c_int32, C.POINTER(C.c_uint32), c_f64p, c_u64p, c_i32p]
-            lib.lh_eval_draw_batch_device.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 5 + \
-                [C.c_int32] + [C.c_void_p] * 5
+            lib.lh_eval_draw_batch.argtypes = _HOST_TREE + [c_u32p, c_f64p, c_u64p, c_i32p]
+            lib.lh_eval_draw_batch_device.argtypes = _DEV_TREE + [C.c_void_p] * 5
             lib.lh_naive_sequences.argtypes = [C.c_void_p, C.c_int32, c_i32p, c_u8p, c_u64p]
             lib.lh_draws_resolve.argtypes = [C.c_void_p, C.c_int32, c_i32p, c_i32p, c_i32p]
             lib.lh_draws_rows_read.argtypes = [C.c_void_p, C.c_int32, c_i32p, c_u8p]
             lib.lh_draws_candidates_read.argtypes = [C.c_void_p, c_i32p, c_u8p]
             lib.lh_draws_reset.argtypes = [C.c_void_p]
-            lib.lh_collect_profile_read.argtypes = [C.c_void_p, c_f64p, C.POINTER(C.c_int64)]
+            lib.lh_collect_profile_read.argtypes = _PROFILE_READ
         if hasattr(lib, "lh_lineage_batch"):
-            c_u64p = C.POINTER(C.c_uint64)
-            lib.lh_lineage_batch.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, c_i32p, c_f64p, c_f64p, c_f64p,
-                                             c_f64p, C.c_int32, c_u8p, C.c_uint64, C.c_uint64, c_i32p, C.c_int32,
-                                             c_u64p, c_u64p]
+            lib.lh_lineage_batch.argtypes = _HOST_TREE + [c_u8p, C.c_uint64, C.c_uint64, c_i32p, C.c_int32, c_u64p, c_u64p]
             lib.lh_lineage_collect_device.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                                       C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
             lib.lh_lineage_resolve.argtypes = [C.c_void_p, C.c_int32, c_i32p, c_i32p, c_i32p]
             lib.lh_lineage_rows_read.argtypes = [C.c_void_p, C.c_int32, c_i32p, c_u8p]
             lib.lh_lineage_store_read.argtypes = [C.c_void_p, C.c_int32, C.c_int32, c_i32p, c_u8p]
             lib.lh_lineage_reset.argtypes = [C.c_void_p]
-            lib.lh_lineage_profile_read.argtypes = [C.c_void_p, c_f64p, C.POINTER(C.c_int64)]
+            lib.lh_lineage_profile_read.argtypes = _PROFILE_READ
         if hasattr(lib, "lh_eval_lineage_batch"):
-            lib.lh_eval_lineage_batch.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, c_i32p, c_f64p, c_f64p,
-                                                  c_f64p, c_f64p, C.c_int32, C.POINTER(C.c_uint32), C.c_uint64,
-                                                  C.c_uint64, C.c_int32, c_i32p, C.c_int32,
-                                                  C.POINTER(_LineageEvalOutputs)]
-            lib.lh_eval_lineage_batch_device.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + \
-                [C.c_void_p] * 5 + [C.c_int32, C.c_void_p, C.c_uint64, C.c_uint64, C.c_int32, C.c_void_p, C.c_int32,
-                                    C.POINTER(_LineageEvalOutputsDevice), C.c_void_p]
-            lib.lh_lineage_eval_profile_read.argtypes = [C.c_void_p, c_f64p, C.POINTER(C.c_int64)]
+            lib.lh_eval_lineage_batch.argtypes = _HOST_TREE + [c_u32p, C.c_uint64, C.c_uint64, C.c_int32, c_i32p, C.c_int32,
+                                                               C.POINTER(_LineageEvalOutputs)]
+            lib.lh_eval_lineage_batch_device.argtypes = _DEV_TREE + [
+                C.c_void_p, C.c_uint64, C.c_uint64, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(_LineageEvalOutputsDevice),
+                C.c_void_p]
+            lib.lh_lineage_eval_profile_read.argtypes = _PROFILE_READ
         if hasattr(lib, "lh_eval_viterbi_batch"):
             lib.lh_family_set_sampler.argtypes = [C.c_void_p, C.POINTER(_SamplerDesc)]
-            lib.lh_eval_viterbi_batch.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, c_i32p, c_f64p, c_f64p,
-                                                  c_f64p, c_f64p, C.c_int32, C.POINTER(_ViterbiOutputs)]
-            lib.lh_eval_viterbi_batch_device.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + \
-                [C.c_void_p] * 5 + [C.c_int32, C.POINTER(_ViterbiOutputsDevice), C.c_void_p]
+            lib.lh_eval_viterbi_batch.argtypes = _HOST_TREE + [C.POINTER(_ViterbiOutputs)]
+            lib.lh_eval_viterbi_batch_device.argtypes = _DEV_TREE + [C.POINTER(_ViterbiOutputsDevice), C.c_void_p]
             lib.lh_viterbi_forward_batch.argtypes = [C.c_void_p, C.c_int32, c_f64p, c_f64p, c_i32p]
             lib.lh_family_set_candidate_paths.argtypes = [C.c_void_p, C.c_int32, c_i32p, c_f64p]
-            lib.lh_viterbi_profile_read.argtypes = [C.c_void_p, c_f64p, C.POINTER(C.c_int64)]
+            lib.lh_viterbi_profile_read.argtypes = _PROFILE_READ
         if hasattr(lib, "lh_family_set_codons"):
             lib.lh_family_set_codons.argtypes = [C.c_void_p, C.c_int32]
             lib.lh_codon_layout.argtypes = [C.c_void_p, c_i32p, c_i32p, c_i32p, c_i32p]
-            lib.lh_eval_codons_batch.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, c_i32p, c_f64p, c_f64p,
-                                                 c_f64p, c_f64p, C.c_int32, C.POINTER(_CodonOutputs)]
-            lib.lh_eval_codons_batch_device.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + \
-                [C.c_void_p] * 5 + [C.c_int32, C.POINTER(_CodonOutputsDevice), C.c_void_p]
-            lib.lh_codon_profile_read.argtypes = [C.c_void_p, c_f64p, C.POINTER(C.c_int64)]
+            lib.lh_eval_codons_batch.argtypes = _HOST_TREE + [C.POINTER(_CodonOutputs)]
+            lib.lh_eval_codons_batch_device.argtypes = _DEV_TREE + [C.POINTER(_CodonOutputsDevice), C.c_void_p]
+            lib.lh_codon_profile_read.argtypes = _PROFILE_READ
         if hasattr(lib, "lh_set_device"):      # (absent from round-2 builds loaded through LH_LIB_DIR for comparisons)
             lib.lh_set_device.argtypes = [C.c_int32]
             lib.lh_family_status.argtypes = [C.c_void_p]
@@ -258,51 +242,38 @@ class HipLibrary:
     def device_count(self):
         return self.lib.lh_device_count()
 
+    def _profile_read(self, name, family, n_ms=1):
+        """lh_<name>_profile_read: (the n_ms kernel times in ms ..., launch groups) since the last read."""
+        ms, k = (C.c_double * n_ms)(), C.c_int64()
+        self.check(getattr(self.lib, name)(_handle(family), ms, C.byref(k)))
+        return tuple(ms) + (k.value,)
+
     def eval_posterior_batch(self, family, n_tips, max_depth, ops, brlen, er, pi, alpha, num_rates, log_offset=None,
                              want=("loglik", "posterior", "weighted_sum", "weight_stats")):
         """K0-K2 + K5 on a family handle (a raw lh_family* or a Family) that has sampler tables.  Returns a dict with the
         members of `want`: loglik [n], posterior [n, forward_size], weighted_sum [forward_size], weight_stats [3]
         (max lw, sum w, sum w^2 with lw = loglik - log_offset)."""
-        h = family.handle if isinstance(family, Family) else family
-        ops = np.ascontiguousarray(ops, dtype=np.int32)
-        n = ops.shape[0]
-        brlen, er, pi, alpha = _f64(brlen), _f64(er), _f64(pi), _f64(alpha)
+        h = _handle(family)
+        n, arrays = _tree_args(ops, brlen, er, pi, alpha)
         fs = self.lib.lh_forward_size(h)
-        res = {}
-        if "loglik" in want:
-            res["loglik"] = np.zeros(n)
-        if "posterior" in want:
-            res["posterior"] = np.zeros((n, fs))
-        if "weighted_sum" in want:
-            res["weighted_sum"] = np.zeros(fs)
-        if "weight_stats" in want:
-            res["weight_stats"] = np.zeros(3)
-        lo = None if log_offset is None else _f64(log_offset)
-
-        def ptr(a):
-            return a.ctypes.data_as(c_f64p) if a is not None else None
-        outs = _PosteriorOutputs(ptr(lo), ptr(res.get("loglik")), ptr(res.get("posterior")), ptr(res.get("weighted_sum")),
-                                 ptr(res.get("weight_stats")))
-        self.check(self.lib.lh_eval_posterior_batch(h, n, n_tips, max_depth, ops.ctypes.data_as(c_i32p), ptr(brlen),
-                                                    ptr(er), ptr(pi), ptr(alpha), num_rates, C.byref(outs)))
+        res, outs = _outputs(_PosteriorOutputs, want, log_offset, loglik=(n,), posterior=(n, fs), weighted_sum=(fs,),
+                             weight_stats=(3,))
+        self.check(self.lib.lh_eval_posterior_batch(h, n, n_tips, max_depth, *_tree_ptrs(arrays), num_rates, C.byref(outs)))
         return res
 
     def posterior_profile_read(self, family):
-        h = family.handle if isinstance(family, Family) else family
-        ms, k = C.c_double(), C.c_int64()
-        self.check(self.lib.lh_posterior_profile_read(h, C.byref(ms), C.byref(k)))
-        return ms.value, k.value
+        return self._profile_read("lh_posterior_profile_read", family)
 
     def set_codons(self, family, frame=0):
         """Fixes the reading frame of K9 on a family handle that has sampler tables and returns its layout:
         dict(frame, n_codons, window_codon [n_window], n_genes)."""
-        h = family.handle if isinstance(family, Family) else family
+        h = _handle(family)
         self.check(self.lib.lh_family_set_codons(h, frame))
         return self.codon_layout(h, frame)
 
     def codon_layout(self, family, frame):
         """The layout of the handle's window tables; `frame` is the one set_codons fixed (the C ABI does not report it)."""
-        h = family.handle if isinstance(family, Family) else family
+        h = _handle(family)
         nc, nw, ng = C.c_int32(), C.c_int32(), C.c_int32()
         self.check(self.lib.lh_codon_layout(h, C.byref(nc), C.byref(nw), None, C.byref(ng)))
         wc = np.zeros(max(nw.value, 1), dtype=np.int32)
@@ -314,51 +285,36 @@ class HipLibrary:
         """K0-K2 + K9 on a family handle after set_codons.  Returns a dict with the members of `want`: loglik [n],
         windows [n, n_window, 125], genes [n, n_genes], weighted_windows [n_window, 125], weighted_genes [n_genes],
         weight_stats [3] (max lw, sum w, sum w^2 with lw = loglik - log_offset)."""
-        h = family.handle if isinstance(family, Family) else family
-        ops = np.ascontiguousarray(ops, dtype=np.int32)
-        n = ops.shape[0]
-        brlen, er, pi, alpha = _f64(brlen), _f64(er), _f64(pi), _f64(alpha)
+        h = _handle(family)
+        n, arrays = _tree_args(ops, brlen, er, pi, alpha)
         nw, ng = C.c_int32(), C.c_int32()
         self.check(self.lib.lh_codon_layout(h, None, C.byref(nw), None, C.byref(ng)))
-        shapes = dict(loglik=(n,), windows=(n, nw.value, 125), genes=(n, ng.value), weighted_windows=(nw.value, 125),
-                      weighted_genes=(ng.value,), weight_stats=(3,))
-        res = {k: np.zeros(shapes[k]) for k in shapes if k in want}
-        lo = None if log_offset is None else _f64(log_offset)
-
-        def ptr(a):
-            return a.ctypes.data_as(c_f64p) if a is not None else None
-        outs = _CodonOutputs(ptr(lo), *[ptr(res.get(k)) for k in ("loglik", "windows", "genes", "weighted_windows",
-                                                                  "weighted_genes", "weight_stats")])
-        self.check(self.lib.lh_eval_codons_batch(h, n, n_tips, max_depth, ops.ctypes.data_as(c_i32p), ptr(brlen),
-                                                 ptr(er), ptr(pi), ptr(alpha), num_rates, C.byref(outs)))
+        res, outs = _outputs(_CodonOutputs, want, log_offset, loglik=(n,), windows=(n, nw.value, 125), genes=(n, ng.value),
+                             weighted_windows=(nw.value, 125), weighted_genes=(ng.value,), weight_stats=(3,))
+        self.check(self.lib.lh_eval_codons_batch(h, n, n_tips, max_depth, *_tree_ptrs(arrays), num_rates, C.byref(outs)))
         return res
 
     def codon_profile_read(self, family):
-        h = family.handle if isinstance(family, Family) else family
-        ms, k = C.c_double(), C.c_int64()
-        self.check(self.lib.lh_codon_profile_read(h, C.byref(ms), C.byref(k)))
-        return ms.value, k.value
+        return self._profile_read("lh_codon_profile_read", family)
 
     def candidates_info(self, family):
         """(candidates registered on the handle, sites every candidate has): lh_candidates_info."""
-        h = family.handle if isinstance(family, Family) else family
         k, L = C.c_int32(), C.c_int32()
-        self.check(self.lib.lh_candidates_info(h, C.byref(k), C.byref(L)))
+        self.check(self.lib.lh_candidates_info(_handle(family), C.byref(k), C.byref(L)))
         return k.value, L.value
 
     def candidates_layout(self, family):
         """(variable sites V, log-emission u-columns n_lem, of which the variable sites' n_vlem) of the registered
         candidate tables: lh_candidates_layout."""
-        h = family.handle if isinstance(family, Family) else family
         v, a, b = C.c_int32(), C.c_int32(), C.c_int32()
-        self.check(self.lib.lh_candidates_layout(h, C.byref(v), C.byref(a), C.byref(b)))
+        self.check(self.lib.lh_candidates_layout(_handle(family), C.byref(v), C.byref(a), C.byref(b)))
         return v.value, a.value, b.value
 
     def set_candidates(self, family, seqs, n_sites=None):
         """K6a: registers candidate naive sequences seqs [K][L] (A,C,G,T,N = 0..4) on a family handle (a raw lh_family* or
         a Family) and returns log P_HMM(s_k) [K] (-inf: no state path produces the candidate).  L must be the family's
         alignment length (n_sites, if given, must be too)."""
-        h = family.handle if isinstance(family, Family) else family
+        h = _handle(family)
         seqs = np.asarray(seqs)
         if seqs.ndim != 2 or seqs.shape[0] < 1:
             raise ValueError("lh_family_set_candidates: candidates must be a non-empty [K][L] array")
@@ -380,79 +336,54 @@ class HipLibrary:
         """K0-K2 + K6b on a handle with candidates (set_candidates).  Returns a dict with the members of `want`:
         loglik [n], log_cand [n, K] (log P(s_k | data, t_i)), weighted_sum [K], weight_stats [3], K = the candidates
         registered on the handle (n_candidates, if given, must equal it)."""
-        h = family.handle if isinstance(family, Family) else family
-        ops = np.ascontiguousarray(ops, dtype=np.int32)
-        n = ops.shape[0]
-        brlen, er, pi, alpha = _f64(brlen), _f64(er), _f64(pi), _f64(alpha)
+        h = _handle(family)
+        n, arrays = _tree_args(ops, brlen, er, pi, alpha)
         K, _ = self.candidates_info(h)
         if n_candidates is not None and n_candidates != K:
             raise ValueError("lh_eval_candidates_batch: %d candidates expected, the handle has %d" % (n_candidates, K))
         if K == 0:
             raise RuntimeError("linearham_hip: lh_eval_candidates_batch: lh_family_set_candidates has not been called")
-        if ops.ndim != 3 or n < 1 or any(np.asarray(a).shape[0] != n for a in (brlen, er, pi, alpha)) or \
-                (log_offset is not None and np.asarray(log_offset).shape != (n,)):
+        if n < 1 or not _n_rows(n, arrays, log_offset):
             raise ValueError("lh_eval_candidates_batch: the per-row arrays must all have n rows")
-        shapes = {"loglik": (n,), "log_cand": (n, K), "weighted_sum": (K,), "weight_stats": (3,)}
-        res = {k: np.zeros(shapes[k]) for k in want}
-        lo = None if log_offset is None else _f64(log_offset)
-
-        def ptr(a):
-            return a.ctypes.data_as(c_f64p) if a is not None else None
-        outs = _CandidateOutputs(ptr(lo), ptr(res.get("loglik")), ptr(res.get("log_cand")), ptr(res.get("weighted_sum")),
-                                 ptr(res.get("weight_stats")))
-        self.check(self.lib.lh_eval_candidates_batch(h, n, n_tips, max_depth, ops.ctypes.data_as(c_i32p), ptr(brlen),
-                                                     ptr(er), ptr(pi), ptr(alpha), num_rates, C.byref(outs)))
+        res, outs = _outputs(_CandidateOutputs, want, log_offset, loglik=(n,), log_cand=(n, K), weighted_sum=(K,),
+                             weight_stats=(3,))
+        self.check(self.lib.lh_eval_candidates_batch(h, n, n_tips, max_depth, *_tree_ptrs(arrays), num_rates,
+                                                     C.byref(outs)))
         return res
 
     def candidates_profile_read(self, family):
         """(K6a ms, K6b ms, evaluation calls) since the last read."""
-        h = family.handle if isinstance(family, Family) else family
-        ms, k = (C.c_double * 2)(), C.c_int64()
-        self.check(self.lib.lh_candidates_profile_read(h, ms, C.byref(k)))
-        return ms[0], ms[1], k.value
+        return self._profile_read("lh_candidates_profile_read", family, 2)
 
     # ---- K8: the most probable state path, candidate paths ----
     def sample_states(self, family):
         """ints per sample of a state path in K4's layout (lh_sample_states; 0 without sampler tables)."""
-        h = family.handle if isinstance(family, Family) else family
-        return int(self.lib.lh_sample_states(h))
+        return int(self.lib.lh_sample_states(_handle(family)))
 
     def eval_viterbi_batch(self, family, n_tips, max_depth, ops, brlen, er, pi, alpha, num_rates, log_offset=None,
                            want=("loglik", "states", "log_path")):
         """K0-K2 + K8 on a handle with sampler tables.  Returns a dict with the members of `want`: loglik [n], states
         [n, lh_sample_states] (the most probable state path in K4's layout; -1 where there is none), log_path [n]
         (log P(data, path | tree)), weight_stats [3]."""
-        h = family.handle if isinstance(family, Family) else family
-        ops = np.ascontiguousarray(ops, dtype=np.int32)
-        n = ops.shape[0]
-        brlen, er, pi, alpha = _f64(brlen), _f64(er), _f64(pi), _f64(alpha)
-        if ops.ndim != 3 or any(np.asarray(a).shape[0] != n for a in (brlen, er, pi, alpha)) or \
-                (log_offset is not None and np.asarray(log_offset).shape != (n,)):
+        h = _handle(family)
+        n, arrays = _tree_args(ops, brlen, er, pi, alpha)
+        if not _n_rows(n, arrays, log_offset):
             raise ValueError("lh_eval_viterbi_batch: the per-row arrays must all have n rows")
-        shapes = {"loglik": ((n,), np.float64), "states": ((n, self.sample_states(h)), np.int32),
-                  "log_path": ((n,), np.float64), "weight_stats": ((3,), np.float64)}
-        res = {k: np.zeros(shapes[k][0], dtype=shapes[k][1]) for k in want}
-        lo = None if log_offset is None else _f64(log_offset)
-
-        def ptr(a, t=c_f64p):
-            return a.ctypes.data_as(t) if a is not None else None
-        outs = _ViterbiOutputs(ptr(lo), ptr(res.get("loglik")), ptr(res.get("states"), c_i32p), ptr(res.get("log_path")),
-                               ptr(res.get("weight_stats")))
-        self.check(self.lib.lh_eval_viterbi_batch(h, n, n_tips, max_depth, ops.ctypes.data_as(c_i32p), ptr(brlen),
-                                                  ptr(er), ptr(pi), ptr(alpha), num_rates, C.byref(outs)))
+        res, outs = _outputs(_ViterbiOutputs, want, log_offset, loglik=(n,), states=((n, self.sample_states(h)), np.int32),
+                             log_path=(n,), weight_stats=(3,))
+        self.check(self.lib.lh_eval_viterbi_batch(h, n, n_tips, max_depth, *_tree_ptrs(arrays), num_rates, C.byref(outs)))
         return res
 
     def eval_viterbi_batch_device(self, family, n, n_tips, max_depth, ops_ptr, brlen_ptr, er_ptr, pi_ptr, alpha_ptr,
                                   num_rates, outs, stream=0):
         """lh_eval_viterbi_batch_device on device addresses; outs: dict of the output members' addresses."""
-        h = family.handle if isinstance(family, Family) else family
         o = _ViterbiOutputsDevice(**{k: int(v) for k, v in outs.items() if v})
-        self.check(self.lib.lh_eval_viterbi_batch_device(h, n, n_tips, max_depth, ops_ptr, brlen_ptr, er_ptr, pi_ptr,
-                                                         alpha_ptr, num_rates, C.byref(o), stream))
+        self.check(self.lib.lh_eval_viterbi_batch_device(_handle(family), n, n_tips, max_depth, ops_ptr, brlen_ptr, er_ptr,
+                                                         pi_ptr, alpha_ptr, num_rates, C.byref(o), stream))
 
     def viterbi_forward_batch(self, family, em):
         """K2a + K8 on caller emissions em [n][C]: (log_path [n], states [n, lh_sample_states])."""
-        h = family.handle if isinstance(family, Family) else family
+        h = _handle(family)
         em = _f64(em)
         n = em.shape[0]
         lp = np.zeros(n)
@@ -464,7 +395,7 @@ class HipLibrary:
     def set_candidate_paths(self, family, states):
         """Registers state paths states [K][lh_sample_states] as the handle's candidates (their naive sequences, with
         the paths' HMM priors) and returns log P_HMM(a_k) [K]; eval_candidates_batch then scores the paths."""
-        h = family.handle if isinstance(family, Family) else family
+        h = _handle(family)
         states = np.ascontiguousarray(states, dtype=np.int32)
         if states.ndim != 2 or states.shape[0] < 1 or states.shape[1] != self.sample_states(h):
             raise ValueError("lh_family_set_candidate_paths: paths must be a non-empty [K][lh_sample_states] array")
@@ -475,15 +406,12 @@ class HipLibrary:
 
     def viterbi_profile_read(self, family):
         """(K8 ms, launch groups) since the last read."""
-        h = family.handle if isinstance(family, Family) else family
-        ms, k = C.c_double(), C.c_int64()
-        self.check(self.lib.lh_viterbi_profile_read(h, C.byref(ms), C.byref(k)))
-        return ms.value, k.value
+        return self._profile_read("lh_viterbi_profile_read", family)
 
     # ---- K6c: naive sequences of sampled states and the candidate store ----
     def naive_sequences(self, family, states):
         """K6c on states [n][lh_sample_states()]: (seqs [n][L] uint8, A,C,G,T,N = 0..4; hash [n] uint64)."""
-        h = family.handle if isinstance(family, Family) else family
+        h = _handle(family)
         states = np.ascontiguousarray(states, dtype=np.int32)
         n = states.shape[0]
         _, L = self.candidates_info(h)
@@ -495,34 +423,28 @@ class HipLibrary:
 
     def eval_draw_batch(self, family, n_tips, max_depth, ops, brlen, er, pi, alpha, num_rates, words, want_states=False):
         """lh_eval_draw_batch: (loglik [n], hash [n], states [n][S] or None); the sequences stay on the handle."""
-        h = family.handle if isinstance(family, Family) else family
-        ops = np.ascontiguousarray(ops, dtype=np.int32)
-        n = ops.shape[0]
-        brlen, er, pi, alpha = _f64(brlen), _f64(er), _f64(pi), _f64(alpha)
+        h = _handle(family)
+        n, arrays = _tree_args(ops, brlen, er, pi, alpha)
         words = np.ascontiguousarray(words, dtype=np.uint32)
         ll = np.zeros(n)
         hsh = np.zeros(n, dtype=np.uint64)
         st = np.zeros((n, self.lib.lh_sample_states(h)), dtype=np.int32) if want_states else None
-        self.check(self.lib.lh_eval_draw_batch(h, n, n_tips, max_depth, ops.ctypes.data_as(c_i32p),
-                                               brlen.ctypes.data_as(c_f64p), er.ctypes.data_as(c_f64p),
-                                               pi.ctypes.data_as(c_f64p), alpha.ctypes.data_as(c_f64p), num_rates,
-                                               words.ctypes.data_as(C.POINTER(C.c_uint32)), ll.ctypes.data_as(c_f64p),
-                                               hsh.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                               st.ctypes.data_as(c_i32p) if st is not None else None))
+        self.check(self.lib.lh_eval_draw_batch(h, n, n_tips, max_depth, *_tree_ptrs(arrays), num_rates,
+                                               _ptr(words, C.POINTER(C.c_uint32)), _ptr(ll),
+                                               _ptr(hsh, C.POINTER(C.c_uint64)), _ptr(st, c_i32p)))
         return ll, hsh, st
 
     def draws_resolve(self, family, cand):
         """lh_draws_resolve: the rows of the last batch whose bytes differ from their candidate's."""
-        h = family.handle if isinstance(family, Family) else family
         cand = np.ascontiguousarray(cand, dtype=np.int32)
         rows = np.zeros(max(len(cand), 1), dtype=np.int32)
         nm = C.c_int32()
-        self.check(self.lib.lh_draws_resolve(h, len(cand), cand.ctypes.data_as(c_i32p), C.byref(nm),
+        self.check(self.lib.lh_draws_resolve(_handle(family), len(cand), cand.ctypes.data_as(c_i32p), C.byref(nm),
                                              rows.ctypes.data_as(c_i32p)))
         return rows[:nm.value].copy()
 
     def draws_rows_read(self, family, rows):
-        h = family.handle if isinstance(family, Family) else family
+        h = _handle(family)
         rows = np.ascontiguousarray(rows, dtype=np.int32)
         _, L = self.candidates_info(h)
         out = np.zeros((len(rows), L), dtype=np.uint8)
@@ -531,7 +453,7 @@ class HipLibrary:
 
     def draws_candidates_read(self, family):
         """The candidate store: [K][L] uint8."""
-        h = family.handle if isinstance(family, Family) else family
+        h = _handle(family)
         k = C.c_int32()
         self.check(self.lib.lh_draws_candidates_read(h, C.byref(k), None))
         _, L = self.candidates_info(h)
@@ -540,15 +462,11 @@ class HipLibrary:
         return out
 
     def draws_reset(self, family):
-        h = family.handle if isinstance(family, Family) else family
-        self.check(self.lib.lh_draws_reset(h))
+        self.check(self.lib.lh_draws_reset(_handle(family)))
 
     def collect_profile_read(self, family):
         """(K6c ms, launches) since the last read."""
-        h = family.handle if isinstance(family, Family) else family
-        ms, k = C.c_double(), C.c_int64()
-        self.check(self.lib.lh_collect_profile_read(h, C.byref(ms), C.byref(k)))
-        return ms.value, k.value
+        return self._profile_read("lh_collect_profile_read", family)
 
     def schedule_tree(self, n_tips, children, root):
         """children: int32 [(T-2)*2]; returns (ops [T-2,4] int32, max_depth)."""
@@ -576,6 +494,48 @@ def _f64(a):
 
 def _i32(a):
     return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def _handle(family):
+    """The lh_family* of a Family, or the raw handle itself."""
+    return family.handle if isinstance(family, Family) else family
+
+
+def _ptr(a, t=c_f64p):
+    return a.ctypes.data_as(t) if a is not None else None
+
+
+def _tree_args(ops, brlen, er, pi, alpha):
+    """The per-row inputs of a batch of trees (alpha: or rates) as the C ABI reads them: (n, the five arrays)."""
+    ops = _i32(ops)
+    return ops.shape[0], (ops, _f64(brlen), _f64(er), _f64(pi), _f64(alpha))
+
+
+def _tree_ptrs(arrays):
+    return [_ptr(arrays[0], c_i32p)] + [_ptr(a) for a in arrays[1:]]
+
+
+def _n_rows(n, arrays, log_offset):
+    """Whether ops is [n][T-2][4] and every other per-row array has n rows."""
+    return arrays[0].ndim == 3 and all(a.shape[0] == n for a in arrays[1:]) and \
+        (log_offset is None or np.asarray(log_offset).shape == (n,))
+
+
+def _outputs(struct, want, log_offset=None, **shapes):
+    """The outputs of an evaluation: (res, outs) with res[k] a zeroed array of shapes[k] -- a shape, or (shape, dtype) --
+    for every k of `want`, and `outs` the filled output struct: its members point at res and at log_offset (if it has
+    one), the others stay null."""
+    res = {}
+    for k, v in shapes.items():
+        if k in want:
+            shape, dtype = v if isinstance(v[0], tuple) else (v, np.float64)
+            res[k] = np.zeros(shape, dtype=dtype)
+    outs = struct()
+    outs.arrays = dict(res, log_offset=None if log_offset is None else _f64(log_offset))  # (keeps log_offset alive)
+    for k, t in struct._fields_:
+        if outs.arrays.get(k) is not None:
+            setattr(outs, k, _ptr(outs.arrays[k], t))
+    return res, outs
 
 
 class Segments:
@@ -716,33 +676,22 @@ class Family:
             pass
 
     def _outs(self, n, R, want):
-        outs = _EvalOutputs()
-        res = {}
-        if "rates" in want:
-            res["rates"] = np.zeros((n, R))
-            outs.rates = res["rates"].ctypes.data_as(c_f64p)
-        if "xmsa_emission" in want:
-            res["xmsa_emission"] = np.zeros((n, self.n_xmsa))
-            outs.xmsa_emission = res["xmsa_emission"].ctypes.data_as(c_f64p)
-        if "forward" in want:
-            res["forward"] = np.zeros((n, self.forward_size))
-            outs.forward = res["forward"].ctypes.data_as(c_f64p)
-        if "scaler_counts" in want:
-            res["scaler_counts"] = np.zeros((n, self.scaler_size), dtype=np.int32)
-            outs.scaler_counts = res["scaler_counts"].ctypes.data_as(c_i32p)
+        shapes = dict(rates=(n, R), forward=(n, self.forward_size), scaler_counts=((n, self.scaler_size), np.int32))
+        if "xmsa_emission" in want:  # (a borrowed handle knows n_xmsa only if its owner has set it)
+            shapes["xmsa_emission"] = (n, self.n_xmsa)
+        res, outs = _outputs(_EvalOutputs, want, **shapes)
         return outs, res
 
     def eval_batch(self, n_tips, max_depth, ops, brlen, er, pi, alpha, num_rates, want=()):
-        ops, brlen, er, pi, alpha = _i32(ops), _f64(brlen), _f64(er), _f64(pi), _f64(alpha)
+        _, arrays = _tree_args(ops, brlen, er, pi, alpha)
+        ops, brlen, er, pi, alpha = arrays
         n = alpha.shape[0]
         assert ops.shape == (n, n_tips - 2, 4) and brlen.shape == (n, 2 * n_tips - 2)
         assert er.shape == (n, 6) and pi.shape == (n, 4)
         ll = np.zeros(n)
         outs, res = self._outs(n, num_rates, want)
-        self.hip.check(self.hip.lib.lh_eval_batch(
-            self.handle, n, n_tips, max_depth, ops.ctypes.data_as(c_i32p), brlen.ctypes.data_as(c_f64p),
-            er.ctypes.data_as(c_f64p), pi.ctypes.data_as(c_f64p), alpha.ctypes.data_as(c_f64p), num_rates,
-            ll.ctypes.data_as(c_f64p), C.byref(outs)))
+        self.hip.check(self.hip.lib.lh_eval_batch(self.handle, n, n_tips, max_depth, *_tree_ptrs(arrays), num_rates,
+                                                  _ptr(ll), C.byref(outs)))
         return ll, res
 
     def eval_batch_device(self, n, n_tips, max_depth, ops_ptr, brlen_ptr, er_ptr, pi_ptr, alpha_ptr,
@@ -781,17 +730,17 @@ class Family:
 
     def asr_batch(self, n_tips, max_depth, ops, brlen, er, pi, rates, naive, seed, first_sample=0):
         """lh_asr_batch: returns (anc [n][T-2][L] uint8, rate_choice [n][L] uint8)."""
-        ops, brlen, er, pi, rates = _i32(ops), _f64(brlen), _f64(er), _f64(pi), _f64(rates)
+        _, arrays = _tree_args(ops, brlen, er, pi, rates)
+        ops, brlen, er, pi, rates = arrays
         naive = np.ascontiguousarray(naive, dtype=np.uint8)
         n, L = naive.shape
         assert ops.shape == (n, n_tips - 2, 4) and brlen.shape == (n, 2 * n_tips - 2)
         assert er.shape == (n, 6) and pi.shape == (n, 4) and rates.shape[0] == n
         anc = np.zeros((n, n_tips - 2, L), dtype=np.uint8)
         choice = np.zeros((n, L), dtype=np.uint8)
-        self.hip.check(self.hip.lib.lh_asr_batch(
-            self.handle, n, n_tips, max_depth, ops.ctypes.data_as(c_i32p), brlen.ctypes.data_as(c_f64p),
-            er.ctypes.data_as(c_f64p), pi.ctypes.data_as(c_f64p), rates.ctypes.data_as(c_f64p), rates.shape[1],
-            naive.ctypes.data_as(c_u8p), seed, first_sample, anc.ctypes.data_as(c_u8p), choice.ctypes.data_as(c_u8p)))
+        self.hip.check(self.hip.lib.lh_asr_batch(self.handle, n, n_tips, max_depth, *_tree_ptrs(arrays), rates.shape[1],
+                                                 _ptr(naive, c_u8p), seed, first_sample, _ptr(anc, c_u8p),
+                                                 _ptr(choice, c_u8p)))
         return anc, choice
 
     # ---- K7: the lineage of a seed sequence and the lineage store ----
@@ -799,7 +748,8 @@ class Family:
         """lh_lineage_batch: lh_asr_batch's inputs and path [n][P] (inner nodes seed's parent .. root, -1 padding);
         returns (nt_hash, aa_hash), each [n][P+1] uint64, slot P = the naive sequence.  The sampled states stay on the
         handle for lineage_resolve / lineage_rows_read."""
-        ops, brlen, er, pi, rates = _i32(ops), _f64(brlen), _f64(er), _f64(pi), _f64(rates)
+        _, arrays = _tree_args(ops, brlen, er, pi, rates)
+        ops, brlen, er, pi, rates = arrays
         naive = np.ascontiguousarray(naive, dtype=np.uint8)
         path = _i32(path)
         n, L = naive.shape
@@ -810,10 +760,8 @@ class Family:
         aa = np.zeros((n, P + 1), dtype=np.uint64)
         u64 = C.POINTER(C.c_uint64)
         self.hip.check(self.hip.lib.lh_lineage_batch(
-            self.handle, n, n_tips, max_depth, ops.ctypes.data_as(c_i32p), brlen.ctypes.data_as(c_f64p),
-            er.ctypes.data_as(c_f64p), pi.ctypes.data_as(c_f64p), rates.ctypes.data_as(c_f64p), rates.shape[1],
-            naive.ctypes.data_as(c_u8p), seed, first_sample, path.ctypes.data_as(c_i32p), P, nt.ctypes.data_as(u64),
-            aa.ctypes.data_as(u64)))
+            self.handle, n, n_tips, max_depth, *_tree_ptrs(arrays), rates.shape[1], _ptr(naive, c_u8p), seed, first_sample,
+            _ptr(path, c_i32p), P, _ptr(nt, u64), _ptr(aa, u64)))
         self._lineage_sites = L
         return nt, aa
 
@@ -822,26 +770,23 @@ class Family:
         """lh_eval_lineage_batch (the chain K0-K2, K4, K6c, K3 with `draws` ancestral draws per row, K7): a dict of
         loglik [n], rates [n][R], states [n][S], naive [n][L] uint8, naive_hash [n], nt_hash and aa_hash [n][draws][P+1]
         uint64.  The batch becomes the handle's last lineage batch: flat slot ((i * draws) + d) * (P + 1) + s."""
-        ops, brlen, er, pi, alpha = _i32(ops), _f64(brlen), _f64(er), _f64(pi), _f64(alpha)
+        n, arrays = _tree_args(ops, brlen, er, pi, alpha)
+        ops, brlen, er, pi, alpha = arrays
         words = np.ascontiguousarray(words, dtype=np.uint32)
         path = _i32(path)
-        n = ops.shape[0]
         assert ops.shape == (n, n_tips - 2, 4) and brlen.shape == (n, 2 * n_tips - 2)
         assert er.shape == (n, 6) and pi.shape == (n, 4) and alpha.shape == (n,) and path.shape[0] == n
         P = path.shape[1]
         lib = self.hip.lib
         _, L = self.hip.candidates_info(self.handle)
         d = max(int(draws), 0)
-        res = {"loglik": np.zeros(n), "rates": np.zeros((n, num_rates)),
-               "states": np.zeros((n, lib.lh_sample_states(self.handle)), dtype=np.int32),
-               "naive": np.zeros((n, L), dtype=np.uint8), "naive_hash": np.zeros(n, dtype=np.uint64),
-               "nt_hash": np.zeros((n, d, P + 1), dtype=np.uint64), "aa_hash": np.zeros((n, d, P + 1), dtype=np.uint64)}
-        outs = _LineageEvalOutputs(*[res[k].ctypes.data_as(t) for k, t in _LineageEvalOutputs._fields_])
+        shapes = dict(loglik=(n,), rates=(n, num_rates), states=((n, lib.lh_sample_states(self.handle)), np.int32),
+                      naive=((n, L), np.uint8), naive_hash=((n,), np.uint64), nt_hash=((n, d, P + 1), np.uint64),
+                      aa_hash=((n, d, P + 1), np.uint64))
+        res, outs = _outputs(_LineageEvalOutputs, shapes, **shapes)
         self.hip.check(lib.lh_eval_lineage_batch(
-            self.handle, n, n_tips, max_depth, ops.ctypes.data_as(c_i32p), brlen.ctypes.data_as(c_f64p),
-            er.ctypes.data_as(c_f64p), pi.ctypes.data_as(c_f64p), alpha.ctypes.data_as(c_f64p), num_rates,
-            words.ctypes.data_as(C.POINTER(C.c_uint32)), seed, first_sample, draws, path.ctypes.data_as(c_i32p), P,
-            C.byref(outs)))
+            self.handle, n, n_tips, max_depth, *_tree_ptrs(arrays), num_rates, _ptr(words, C.POINTER(C.c_uint32)), seed,
+            first_sample, draws, _ptr(path, c_i32p), P, C.byref(outs)))
         self._lineage_sites = L
         return res
 
@@ -857,9 +802,8 @@ class Family:
 
     def lineage_eval_profile_read(self):
         """({k0_ms, k1_ms, k2_k4_k6c_ms, k3_ms, k7_ms}, launch groups) of the chain since the last read."""
-        ms, k = (C.c_double * 5)(), C.c_int64()
-        self.hip.check(self.hip.lib.lh_lineage_eval_profile_read(self.handle, ms, C.byref(k)))
-        return dict(zip(("k0_ms", "k1_ms", "k2_k4_k6c_ms", "k3_ms", "k7_ms"), list(ms))), k.value
+        r = self.hip._profile_read("lh_lineage_eval_profile_read", self.handle, 5)
+        return dict(zip(("k0_ms", "k1_ms", "k2_k4_k6c_ms", "k3_ms", "k7_ms"), r[:5])), r[5]
 
     def lineage_collect_device(self, n, n_tips, anc_ptr, naive_ptr, path_ptr, path_len, nt_hash_ptr, aa_hash_ptr,
                                stream=0):
@@ -899,9 +843,7 @@ class Family:
 
     def lineage_profile_read(self):
         """(K7 ms, launches) since the last read."""
-        ms, k = C.c_double(), C.c_int64()
-        self.hip.check(self.hip.lib.lh_lineage_profile_read(self.handle, C.byref(ms), C.byref(k)))
-        return ms.value, k.value
+        return self.hip._profile_read("lh_lineage_profile_read", self.handle)
 
     def set_extended_range(self, on=True):
         self.hip.check(self.hip.lib.lh_family_set_extended_range(self.handle, int(on)))

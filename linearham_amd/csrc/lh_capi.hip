@@ -648,9 +648,39 @@ int check_async_error(lh_family* f, const char* who) {
   return 0;
 }
 
+// A batch of trees as every evaluating entry point takes it, in the order of their signatures: n samples of T tips, each
+// with its schedule, branch lengths and model.  `model` is alpha[n], or (per_rate) rates[n][R].  The arrays are the
+// host's or the device's; only this struct knows their strides.
+struct TreeBatch {
+  int32_t n, T, max_depth;
+  const int32_t* ops;   // [n][T - 2][4]
+  const double* brlen;  // [n][2 T - 2]
+  const double* er;     // [n][6]
+  const double* pi;     // [n][4]
+  const double* model;
+  int32_t R;
+  bool per_rate = false;
+  size_t nodes() const { return 2 * (size_t)T - 2; }
+  size_t n_ops() const { return (size_t)T - 2; }
+  size_t model_stride() const { return per_rate ? (size_t)R : 1; }
+  bool has_arrays() const { return ops && brlen && er && pi && model; }
+  const int32_t* schedule(size_t i) const { return ops + i * n_ops() * 4; }
+  // samples off .. off + m
+  TreeBatch slice(size_t off, int32_t m) const {
+    return {m, T, max_depth, schedule(off), brlen + off * nodes(), er + off * 6, pi + off * 4, model + off * model_stride(),
+            R, per_rate};
+  }
+  // bytes per sample of ops, brlen, er, pi and model
+  std::array<size_t, 5> sample_bytes() const {
+    return {sizeof(int32_t) * 4 * n_ops(), sizeof(double) * nodes(), sizeof(double) * 6, sizeof(double) * 4,
+            sizeof(double) * model_stride()};
+  }
+};
+
 // The argument checks of every entry point that evaluates trees, `w` naming it in the messages.  Returns 1 (error set) for
 // a malformed call, -1 for an empty batch and 0 otherwise: `if (int rc = check_batch(...)) return rc > 0;`
-int check_batch(const lh_family* f, const std::string& w, int n, int T, int R, int max_depth, bool needs_sampler = false) {
+int check_batch(const lh_family* f, const std::string& w, const TreeBatch& b, bool needs_sampler = false) {
+  const int n = b.n, T = b.T, R = b.R, max_depth = b.max_depth;
   if (!f) return fail(w + ": null family");
   if (needs_sampler && !f->have_sampler) return fail(w + ": lh_family_set_sampler has not been called");
   if (n < 0) return fail(w + ": negative batch size");
@@ -662,6 +692,35 @@ int check_batch(const lh_family* f, const std::string& w, int n, int T, int R, i
   if (max_depth < 0 || max_depth > 16) return fail(w + ": max_depth out of range");
   // (launch_prune checks the LDS need of the form it takes -- trees this large with a stack deeper than four slots do not fit)
   if ((size_t)T * 128 > 160 * 1024) return fail(w + ": too many tips for the LDS tip table");
+  return 0;
+}
+
+// bytes per sample of an evaluation's launch group: K1's workspace and its planes
+size_t eval_bytes_per_sample(const lh_family* f, int T, int R) {
+  return k1_bytes_per_sample(f, T, R) + sizeof(double) * R * 6 * (size_t)std::max(f->host.n_prune, 1);
+}
+
+// launch groups of an evaluation: at most kChunk samples and at most ~16 GB of per-sample workspace
+size_t eval_group(const lh_family* f, int T, int R) {
+  return std::min<size_t>(kChunk, std::max<size_t>(1024, ((size_t)16 << 30) / eval_bytes_per_sample(f, T, R)));
+}
+
+// launch groups of the sampling kernel: at most ~8 GB of CLV area (clv_per_sample: 32 B per inner node and site) plus K1's
+// workspace
+size_t asr_group(const lh_family* f, int T, int R, size_t clv_per_sample) {
+  return std::min<size_t>(8192, std::max<size_t>(64, ((size_t)8 << 30) / (clv_per_sample + eval_bytes_per_sample(f, T, R))));
+}
+
+// K1 for the launch group g with the given rates, into the workspace's planes (ensure_workspace has sized them), and what
+// every caller makes of its outcome.  mix == false: per-rate planes, K1 must not mix the categories.
+int prune_group(lh_family* f, const std::string& who, const TreeBatch& g, const double* rates, bool mix, hipStream_t stream,
+                int* planes) {
+  Workspace& w = f->ws;
+  *planes = lh::launch_prune(f->host, g.n, g.R, g.T, g.max_depth, g.ops, g.brlen, rates, w.eig.get<double>(), w.prune, g.pi,
+                             w.site_lik.get<double>(), w.site_scal.get<int32_t>(), stream, mix);
+  if (*planes < 0) return fail(who + ": " + lh::prune_last_error());
+  f->k1_form = lh::prune_last_form();
+  if (!mix && *planes != g.R && f->host.n_prune > 0) return fail(who + ": internal error (rate planes were mixed)");
   return 0;
 }
 
@@ -714,15 +773,35 @@ void in_threads(size_t n, int nw, Fn&& fn) {
 
 // All schedules of a batch; a few threads when the batch is large (0.19 us per op on one core: 0.4 ms per 2048 samples of
 // a 101-tip tree, as much as the device then needs for K0-K2).
-bool valid_schedules(const int32_t* ops, size_t n, int T, int nodes, int max_depth) {
-  const size_t n_ops = (size_t)T - 2;
-  const int nw = (int)std::max<size_t>(1, std::min<size_t>({(size_t)std::thread::hardware_concurrency(), (size_t)8, n * n_ops / 65536}));
+bool valid_schedules(const TreeBatch& b) {
+  const size_t n = b.n;
+  const int nw = (int)std::max<size_t>(1, std::min<size_t>({(size_t)std::thread::hardware_concurrency(), (size_t)8, n * b.n_ops() / 65536}));
   std::atomic<bool> bad{false};
   in_threads(n, nw, [&](size_t lo, size_t hi) {
     for (size_t i = lo; i < hi && !bad; ++i)
-      if (!valid_schedule(ops + i * n_ops * 4, T, nodes, max_depth)) bad = true;
+      if (!valid_schedule(b.schedule(i), b.T, (int)b.nodes(), b.max_depth)) bad = true;
   });
   return !bad;
+}
+
+// Every row of the batch's path[n][P]: inner nodes, then -1 padding, and not empty
+int valid_paths(const std::string& W, const int32_t* path, int P, const TreeBatch& b) {
+  for (size_t i = 0; i < (size_t)b.n; ++i) {
+    bool ended = false;
+    for (int s = 0; s < P; ++s) {
+      const int32_t v = path[i * P + s];
+      if (v == -1) ended = true;
+      else if (ended || v < b.T || v >= (int32_t)b.nodes()) return fail(W + ": path entries are inner nodes, then -1 padding");
+    }
+    if (path[i * P] == -1) return fail(W + ": empty path");
+  }
+  return 0;
+}
+
+int valid_naive(const std::string& W, const uint8_t* naive, size_t count) {
+  for (size_t k = 0; k < count; ++k)
+    if (naive[k] > 4) return fail(W + ": naive base out of range");
+  return 0;
 }
 
 struct HostIn { const void* src; size_t bytes; DevBuf* dst; };  // a host array to copy in (src null: none)
@@ -732,7 +811,7 @@ struct HostOut { void* dst; const void* src; size_t bytes; };    // a device res
 // copied from there, every transfer has the driver lock and unlock their pages, which stalls for milliseconds whenever
 // other threads of the process are busy allocating (RunPipeline's formatting workers are).  One memcpy each into the
 // handle's page-locked slot (64-byte aligned) costs a fraction of that; the copies go on the default stream.
-int stage_inputs(lh_family* f, std::initializer_list<HostIn> in) {
+int stage_inputs(lh_family* f, const std::vector<HostIn>& in) {
   auto padded = [](size_t b) { return (b + 63) & ~(size_t)63; };
   size_t total = 0;
   for (const HostIn& a : in)
@@ -751,6 +830,51 @@ int stage_inputs(lh_family* f, std::initializer_list<HostIn> in) {
     }
   return 0;
 }
+
+// stage_inputs for a batch of trees on the host and the entry point's further arrays: *dev is the batch over the handle's
+// device copies (f->in), as the _device forms take it.
+int stage_batch(lh_family* f, const TreeBatch& host, std::initializer_list<HostIn> extras, TreeBatch* dev) {
+  HostInputs& in = f->in;
+  DevBuf& model = host.per_rate ? in.rates : in.alpha;
+  const std::array<size_t, 5> bytes = host.sample_bytes();
+  const size_t n = host.n;
+  std::vector<HostIn> all{{host.ops, bytes[0] * n, &in.ops},
+                          {host.brlen, bytes[1] * n, &in.brlen},
+                          {host.er, bytes[2] * n, &in.er},
+                          {host.pi, bytes[3] * n, &in.pi},
+                          {host.model, bytes[4] * n, &model}};
+  all.insert(all.end(), extras);
+  if (stage_inputs(f, all)) return 1;
+  *dev = host;
+  dev->ops = in.ops.get<const int32_t>();
+  dev->brlen = in.brlen.get<const double>();
+  dev->er = in.er.get<const double>();
+  dev->pi = in.pi.get<const double>();
+  dev->model = model.get<const double>();
+  return 0;
+}
+
+// what the caller does not hand in comes from the handle's buffers
+int own(double*& p, DevBuf& b, size_t bytes) {
+  if (!p && b.ensure(bytes)) return 1;
+  if (!p) p = b.get<double>();
+  return 0;
+}
+
+// The importance weights of a batch, w_i = exp(lw_i - max lw) with lw = loglik - log_offset, and their statistics (max lw,
+// sum w, sum w^2).  prepare() takes the buffers before the evaluation is enqueued (one that grows waits for the device):
+// the weights from the handle's, the statistics from the handle's unless the caller hands an array in.  launch() enqueues
+// the reduction behind the evaluation.
+struct WeightReduce {
+  double *w = nullptr, *stats = nullptr;
+  int prepare(size_t n, DevBuf& weights, DevBuf& stats_buf, double* caller_stats) {
+    stats = caller_stats;
+    return own(w, weights, sizeof(double) * n) || own(stats, stats_buf, sizeof(double) * 3);
+  }
+  void launch(int n, const double* loglik, const double* log_offset, hipStream_t stream) const {
+    lh::launch_posterior_reduce(n, 0, nullptr, loglik, log_offset, w, nullptr, nullptr, stats, stream);
+  }
+};
 
 // `want` (a host output the caller asked for) gets device buffer b, `bytes` long, as *d; else *d is null.
 template <typename T>
@@ -777,6 +901,20 @@ int copy_back(lh_family* f, const char* who, std::initializer_list<HostOut> out)
   for (const HostOut& o : out)
     if (o.dst) LH_HIP(hipMemcpy(o.dst, o.src, o.bytes, hipMemcpyDeviceToHost));
   return 0;
+}
+
+// The end of a host-pointer call that evaluated `host`: its schedules checked beside the device, then copy_back.
+int finish_batch(lh_family* f, const char* who, const TreeBatch& host, std::initializer_list<HostOut> out) {
+  if (!valid_schedules(host)) return refuse_schedules(f, who);
+  return copy_back(f, who, out);
+}
+
+// lh_*_profile_read: the times of one of the handle's timers since the last read
+template <int Stages>
+int profile_read(lh_family* f, KernelTimer<Stages> lh_family::*timer, double* ms, int64_t* launches) {
+  if (!f) return fail("null family");
+  DeviceGuard guard(f);
+  return (f->*timer).read(ms, launches);
 }
 
 }  // namespace
@@ -1325,10 +1463,8 @@ int lh_profile_enable(lh_family* f, int enable) {
 }
 
 int lh_profile_read(lh_family* f, double* ms_model, double* ms_prune, double* ms_forward, int64_t* n_launches) {
-  if (!f) return fail("null family");
-  DeviceGuard guard(f);
   double ms[3];
-  if (f->eval_timer.read(ms, n_launches)) return 1;
+  if (profile_read(f, &lh_family::eval_timer, ms, n_launches)) return 1;
   if (ms_model) *ms_model = ms[0];
   if (ms_prune) *ms_prune = ms[1];
   if (ms_forward) *ms_forward = ms[2];
@@ -1336,9 +1472,7 @@ int lh_profile_read(lh_family* f, double* ms_model, double* ms_prune, double* ms
 }
 
 int lh_asr_profile_read(lh_family* f, double* ms_sampling, int64_t* n_launches) {
-  if (!f) return fail("null family");
-  DeviceGuard guard(f);
-  return f->asr_timer.read(ms_sampling, n_launches);
+  return profile_read(f, &lh_family::asr_timer, ms_sampling, n_launches);
 }
 
 namespace {
@@ -1346,39 +1480,32 @@ namespace {
 // lh_eval_batch_device's body; lem: K6b's log emissions of every sample (lem.out[n][lem.n]), or none.
 // after(off, m): enqueued behind the forward sweep of every launch group (samples off .. off + m), while K2a's hand-off
 // buffers still hold that group (K8 reads them); nonzero fails the call.
-int eval_device(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops, const double* brlen,
-                const double* er, const double* pi, const double* alpha, int32_t R, double* loglik,
-                const lh_eval_outputs* outs, void* hip_stream, const lh::LogEmRequest& lem,
-                const std::function<int(int, int)>* after = nullptr) {
-  if (int rc = check_batch(f, "lh_eval_batch", n, T, R, max_depth)) return rc > 0;
+int eval_device(lh_family* f, const TreeBatch& b, double* loglik, const lh_eval_outputs* outs, void* hip_stream,
+                const lh::LogEmRequest& lem = lh::LogEmRequest{}, const std::function<int(int, int)>* after = nullptr) {
+  if (int rc = check_batch(f, "lh_eval_batch", b)) return rc > 0;
   DeviceGuard guard(f);
-  if (!ops || !brlen || !er || !pi || !alpha || !loglik) return fail("lh_eval_batch: null array");
+  if (!b.has_arrays() || !loglik) return fail("lh_eval_batch: null array");
   hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-  // launch groups of at most kChunk samples and at most ~16 GB of per-sample workspace
-  const size_t per_sample = k1_bytes_per_sample(f, T, R) + sizeof(double) * R * 6 * (size_t)std::max(f->host.n_prune, 1);
-  const int by_memory = (int)std::max<size_t>(1024, ((size_t)16 << 30) / per_sample);
-  const int chunk = std::min<int>(n, std::min(kChunk, by_memory));
-  if (ensure_workspace(f, chunk, R, T)) return 1;
+  const int n = b.n, R = b.R;
+  const int chunk = (int)std::min<size_t>(n, eval_group(f, b.T, R));
+  if (ensure_workspace(f, chunk, R, b.T)) return 1;
   Workspace& w = f->ws;
   double *eig = w.eig.get<double>(), *site_lik = w.site_lik.get<double>();
   int32_t* site_scal = w.site_scal.get<int32_t>();
-  const size_t nodes = 2 * (size_t)T - 2, n_ops = (size_t)T - 2, C = f->host.n_xmsa;
+  const size_t C = f->host.n_xmsa;
   for (int off = 0; off < n; off += chunk) {
     const int m = std::min(chunk, n - off);
+    const TreeBatch g = b.slice(off, m);
     if (f->profile && f->eval_timer.begin(stream)) return 1;
     double* rates = (outs && outs->rates) ? outs->rates + (size_t)off * R : w.rates.get<double>();
     double* em_out = (outs && outs->xmsa_emission) ? outs->xmsa_emission + (size_t)off * C : nullptr;
-    lh::launch_model_setup(m, R, er + (size_t)off * 6, pi + (size_t)off * 4, alpha + off, rates, eig, stream);
+    lh::launch_model_setup(m, R, g.er, g.pi, g.model, rates, eig, stream);
     if (f->profile && f->eval_timer.mark(1, stream)) return 1;
-    const int planes = lh::launch_prune(f->host, m, R, T, max_depth, ops + (size_t)off * n_ops * 4,
-                                        brlen + (size_t)off * nodes, rates, eig, w.prune, pi + (size_t)off * 4, site_lik,
-                                        site_scal, stream);
-    if (planes < 0) return fail(std::string("lh_eval_batch: ") + lh::prune_last_error());
-    f->k1_form = lh::prune_last_form();
+    int planes = 0;
+    if (prune_group(f, "lh_eval_batch", g, rates, true, stream, &planes)) return 1;
     if (f->profile && f->eval_timer.mark(2, stream)) return 1;
     const lh::LogEmRequest lem_m{lem.cols, lem.n, lem.out ? lem.out + (size_t)off * lem.n : nullptr};
-    if (run_forward(f, m, planes, site_lik, site_scal, pi + (size_t)off * 4, nullptr, em_out, loglik + off, outs, off, stream,
-                    lem_m))
+    if (run_forward(f, m, planes, site_lik, site_scal, g.pi, nullptr, em_out, loglik + off, outs, off, stream, lem_m))
       return 1;
     if (f->profile && f->eval_timer.end(stream)) return 1;
     LH_HIP(hipGetLastError());
@@ -1392,7 +1519,7 @@ int eval_device(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int
 int lh_eval_batch_device(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops,
                          const double* brlen, const double* er, const double* pi, const double* alpha,
                          int32_t R, double* loglik, const lh_eval_outputs* outs, void* hip_stream) {
-  return eval_device(f, n, T, max_depth, ops, brlen, er, pi, alpha, R, loglik, outs, hip_stream, lh::LogEmRequest{});
+  return eval_device(f, {n, T, max_depth, ops, brlen, er, pi, alpha, R}, loglik, outs, hip_stream);
 }
 
 // Host pointers in, host pointers out.  The batch moves in sub-chunks through two pinned staging slots:
@@ -1401,15 +1528,15 @@ int lh_eval_batch_device(lh_family* f, int32_t n, int32_t T, int32_t max_depth, 
 int lh_eval_batch(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops,
                   const double* brlen, const double* er, const double* pi, const double* alpha, int32_t R,
                   double* loglik, const lh_eval_outputs* outs) {
-  if (int rc = check_batch(f, "lh_eval_batch", n, T, R, max_depth)) return rc > 0;
+  const TreeBatch host{n, T, max_depth, ops, brlen, er, pi, alpha, R};
+  if (int rc = check_batch(f, "lh_eval_batch", host)) return rc > 0;
   DeviceGuard guard(f);
-  if (!ops || !brlen || !er || !pi || !alpha || !loglik) return fail("lh_eval_batch: null array");
-  const size_t nodes = 2 * (size_t)T - 2, n_ops = (size_t)T - 2;
+  if (!host.has_arrays() || !loglik) return fail("lh_eval_batch: null array");
   const size_t C = f->host.n_xmsa, FS = f->host.forward_size, SS = f->host.scaler_size;
-  const lh_eval_outputs none{nullptr, nullptr, nullptr, nullptr};
+  const lh_eval_outputs none{};
   const lh_eval_outputs& o = outs ? *outs : none;
   HostOutputs& out = f->out;
-  lh_eval_outputs d_outs{nullptr, nullptr, nullptr, nullptr};
+  lh_eval_outputs d_outs{};
   if (out.loglik.ensure(sizeof(double) * n) || out_buf(o.rates, out.rates, sizeof(double) * R * n, &d_outs.rates) ||
       out_buf(o.xmsa_emission, out.xmsa_emission, sizeof(double) * C * n, &d_outs.xmsa_emission) ||
       out_buf(o.forward, out.forward, sizeof(double) * FS * n, &d_outs.forward) ||
@@ -1418,8 +1545,7 @@ int lh_eval_batch(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const i
   double* d_ll = out.loglik.get<double>();
 
   // per-sample bytes of the five input arrays, in the order they sit in a staging slot
-  const size_t bytes[5] = {sizeof(int32_t) * 4 * n_ops, sizeof(double) * nodes, sizeof(double) * 6,
-                           sizeof(double) * 4, sizeof(double)};
+  const std::array<size_t, 5> bytes = host.sample_bytes();
   const char* src[5] = {(const char*)ops, (const char*)brlen, (const char*)er, (const char*)pi, (const char*)alpha};
   DevBuf* in[5] = {&f->in.ops, &f->in.brlen, &f->in.er, &f->in.pi, &f->in.alpha};
   char* dst[5];
@@ -1429,6 +1555,8 @@ int lh_eval_batch(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const i
     dst[a] = in[a]->get<char>();
     per_sample += bytes[a];
   }
+  const TreeBatch dev{n, T, max_depth, (const int32_t*)dst[0], (const double*)dst[1], (const double*)dst[2],
+                      (const double*)dst[3], (const double*)dst[4], R};
   const int kSub = lh::debug_options().host_sub;  // (default 12 288: whole rounds of all kernels for configs[2]-like shapes)
   const int sub = std::min<int>(n, kSub);
   HostPipe& hp = f->pipe;
@@ -1467,15 +1595,12 @@ int lh_eval_batch(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const i
                              d_outs.xmsa_emission ? d_outs.xmsa_emission + (size_t)off * C : nullptr,
                              d_outs.forward ? d_outs.forward + (size_t)off * FS : nullptr,
                              d_outs.scaler_counts ? d_outs.scaler_counts + (size_t)off * SS : nullptr};
-    rc = lh_eval_batch_device(f, m, T, max_depth, (const int32_t*)(dst[0] + bytes[0] * off),
-                              (const double*)(dst[1] + bytes[1] * off), (const double*)(dst[2] + bytes[2] * off),
-                              (const double*)(dst[3] + bytes[3] * off), (const double*)(dst[4] + bytes[4] * off), R,
-                              d_ll + off, &sub_outs, hp.comp);
+    rc = eval_device(f, dev.slice(off, m), d_ll + off, &sub_outs, hp.comp);
     if (rc) break;
     // ... and its schedules checked on the host while the device works on them
     in_threads(m, nw, [&](size_t lo, size_t hi) {
       for (size_t i = lo; i < hi && !bad; ++i)
-        if (!valid_schedule(ops + (off + i) * n_ops * 4, T, (int)nodes, max_depth)) bad = true;
+        if (!valid_schedule(host.schedule(off + i), T, (int)host.nodes(), max_depth)) bad = true;
     });
     if (bad) rc = refuse_schedules(f, "lh_eval_batch");
   }
@@ -1492,7 +1617,8 @@ int lh_eval_batch(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const i
 int lh_eval_sample_batch_device(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops,
                                 const double* brlen, const double* er, const double* pi, const double* alpha, int32_t R,
                                 const uint32_t* words, double* loglik, double* rates, int32_t* states, void* hip_stream) {
-  if (int rc = check_batch(f, "lh_eval_sample_batch_device", n, T, R, max_depth, true)) return rc > 0;
+  const TreeBatch b{n, T, max_depth, ops, brlen, er, pi, alpha, R};
+  if (int rc = check_batch(f, "lh_eval_sample_batch_device", b, true)) return rc > 0;
   DeviceGuard guard(f);
   if (!words || !states) return fail("lh_eval_sample_batch_device: null array");
   hipStream_t stream = static_cast<hipStream_t>(hip_stream);
@@ -1500,7 +1626,7 @@ int lh_eval_sample_batch_device(lh_family* f, int32_t n, int32_t T, int32_t max_
   if (f->forward_dev.ensure(sizeof(double) * FS * n)) return 1;
   double* fwd = f->forward_dev.get<double>();
   lh_eval_outputs outs{rates, nullptr, fwd, nullptr};
-  if (lh_eval_batch_device(f, n, T, max_depth, ops, brlen, er, pi, alpha, R, loglik, &outs, hip_stream)) return 1;
+  if (eval_device(f, b, loglik, &outs, hip_stream)) return 1;
   lh::launch_sample(f->sampler, f->sampler_dev, n, fwd, FS, words, f->sampler.words_per_sample, states, stream);
   LH_HIP(hipGetLastError());
   return 0;
@@ -1514,34 +1640,24 @@ namespace {
 // the device (rates into out.rates when want_rates), K4's draws into out.states, loglik into out.loglik.  With `sync` the
 // device is waited for after the evaluation and after the sampling; stamps[4] receive the times after the buffers, the
 // copies in, the evaluation and the sampling.
-int sample_host_batch(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops, const double* brlen,
-                      const double* er, const double* pi, const double* alpha, int32_t R, const uint32_t* words,
-                      bool want_rates, bool sync, std::chrono::steady_clock::time_point* stamps) {
-  const size_t nodes = 2 * (size_t)T - 2, n_ops = (size_t)T - 2, FS = f->host.forward_size;
+int sample_host_batch(lh_family* f, const TreeBatch& host, const uint32_t* words, bool want_rates, bool sync,
+                      std::chrono::steady_clock::time_point* stamps) {
+  const size_t n = host.n, FS = f->host.forward_size;
   const lh::DevSampler& smp = f->sampler;
-  HostInputs& in = f->in;
   HostOutputs& out = f->out;
-  if (out.loglik.ensure(sizeof(double) * n) || (want_rates && out.rates.ensure(sizeof(double) * R * n)) ||
-      out.states.ensure(sizeof(int32_t) * smp.states_per_sample * (size_t)n) || f->forward_dev.ensure(sizeof(double) * FS * n))
+  if (out.loglik.ensure(sizeof(double) * n) || (want_rates && out.rates.ensure(sizeof(double) * host.R * n)) ||
+      out.states.ensure(sizeof(int32_t) * smp.states_per_sample * n) || f->forward_dev.ensure(sizeof(double) * FS * n))
     return 1;
   stamps[0] = std::chrono::steady_clock::now();
-  if (stage_inputs(f, {{ops, sizeof(int32_t) * 4 * n_ops * n, &in.ops},
-                       {brlen, sizeof(double) * nodes * n, &in.brlen},
-                       {er, sizeof(double) * 6 * n, &in.er},
-                       {pi, sizeof(double) * 4 * n, &in.pi},
-                       {alpha, sizeof(double) * n, &in.alpha},
-                       {words, sizeof(uint32_t) * smp.words_per_sample * (size_t)n, &in.words}}))
-    return 1;
+  TreeBatch dev;
+  if (stage_batch(f, host, {{words, sizeof(uint32_t) * smp.words_per_sample * n, &f->in.words}}, &dev)) return 1;
   stamps[1] = std::chrono::steady_clock::now();
   double* fwd = f->forward_dev.get<double>();
   lh_eval_outputs outs{want_rates ? out.rates.get<double>() : nullptr, nullptr, fwd, nullptr};
-  if (lh_eval_batch_device(f, n, T, max_depth, in.ops.get<const int32_t>(), in.brlen.get<const double>(),
-                           in.er.get<const double>(), in.pi.get<const double>(), in.alpha.get<const double>(), R,
-                           out.loglik.get<double>(), &outs, nullptr))
-    return 1;
+  if (eval_device(f, dev, out.loglik.get<double>(), &outs, nullptr)) return 1;
   if (sync) LH_HIP(hipDeviceSynchronize());
   stamps[2] = std::chrono::steady_clock::now();
-  lh::launch_sample(smp, f->sampler_dev, n, fwd, FS, in.words.get<const uint32_t>(), smp.words_per_sample,
+  lh::launch_sample(smp, f->sampler_dev, host.n, fwd, FS, f->in.words.get<const uint32_t>(), smp.words_per_sample,
                     out.states.get<int32_t>(), nullptr);
   LH_HIP(hipGetLastError());
   if (sync) LH_HIP(hipDeviceSynchronize());
@@ -1556,17 +1672,18 @@ extern "C" {
 int lh_eval_sample_batch(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops,
                          const double* brlen, const double* er, const double* pi, const double* alpha, int32_t R,
                          const uint32_t* words, double* loglik, double* rates, int32_t* states) {
-  if (int rc = check_batch(f, "lh_eval_sample_batch", n, T, R, max_depth, true)) return rc > 0;
+  const TreeBatch host{n, T, max_depth, ops, brlen, er, pi, alpha, R};
+  if (int rc = check_batch(f, "lh_eval_sample_batch", host, true)) return rc > 0;
   DeviceGuard guard(f);
-  if (!ops || !brlen || !er || !pi || !alpha || !words || !loglik || !states) return fail("lh_eval_sample_batch: null array");
-  const size_t nodes = 2 * (size_t)T - 2;
+  if (!host.has_arrays() || !words || !loglik || !states) return fail("lh_eval_sample_batch: null array");
   static const bool timing = lh::debug_options().sample_timing;  // stage times of every call, on stderr
   auto now = [] { return std::chrono::steady_clock::now(); };
   auto t0 = now();
   std::chrono::steady_clock::time_point st[4];
-  if (sample_host_batch(f, n, T, max_depth, ops, brlen, er, pi, alpha, R, words, true, timing, st)) return 1;
+  if (sample_host_batch(f, host, words, true, timing, st)) return 1;
   const auto t2 = st[0], t3 = st[1], t4 = st[2], t5 = st[3];
-  if (!valid_schedules(ops, (size_t)n, T, (int)nodes, max_depth)) return refuse_schedules(f, "lh_eval_sample_batch");
+  // (not finish_batch: the stage times want a stamp between the check and the copies)
+  if (!valid_schedules(host)) return refuse_schedules(f, "lh_eval_sample_batch");
   auto t6 = now();
   HostOutputs& out = f->out;
   const size_t ll_bytes = sizeof(double) * n, rates_bytes = sizeof(double) * R * n,
@@ -1591,18 +1708,16 @@ int lh_asr_batch_device(lh_family* f, int32_t n, int32_t T, int32_t max_depth, c
                         const double* brlen, const double* er, const double* pi, const double* rates, int32_t R,
                         const uint8_t* naive, uint64_t seed, uint64_t first_sample, uint8_t* anc,
                         uint8_t* rate_choice, void* hip_stream) {
-  if (int rc = check_batch(f, "lh_asr_batch", n, T, R, max_depth)) return rc > 0;
+  const TreeBatch b{n, T, max_depth, ops, brlen, er, pi, rates, R, true};
+  if (int rc = check_batch(f, "lh_asr_batch", b)) return rc > 0;
   DeviceGuard guard(f);
   if (lh::asr_lds_bytes(T, f->host.n_sites, R, f->host.n_prune) > 160 * 1024)
     return fail("lh_asr_batch: tree / alignment too large for the sampling kernel's LDS tables");
-  if (!ops || !brlen || !er || !pi || !rates || !naive || !anc) return fail("lh_asr_batch: null array");
+  if (!b.has_arrays() || !naive || !anc) return fail("lh_asr_batch: null array");
   hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-  const size_t nodes = 2 * (size_t)T - 2, n_ops = (size_t)T - 2, L = f->host.n_sites;
-  // launch groups: at most ~8 GB of CLV area (32 B per inner node and site) plus K1's workspace
+  const size_t n_ops = b.n_ops(), L = f->host.n_sites;
   const size_t clv_per_sample = sizeof(double) * n_ops * 4 * lh::asr_slots((int)L, R);
-  const size_t k1_per_sample = k1_bytes_per_sample(f, T, R) + sizeof(double) * R * 6 * (size_t)std::max(f->host.n_prune, 1);
-  const int by_memory = (int)std::max<size_t>(64, ((size_t)8 << 30) / (clv_per_sample + k1_per_sample));
-  const int chunk = std::min<int>(n, std::min(8192, by_memory));
+  const int chunk = (int)std::min<size_t>(n, asr_group(f, T, R, clv_per_sample));
   if (ensure_workspace(f, chunk, R, T)) return 1;
   AsrWs& aw = f->asr;
   if (aw.clv.ensure(clv_per_sample * chunk) || aw.desc.ensure(lh::asr_desc_bytes(T) * chunk) ||
@@ -1613,19 +1728,12 @@ int lh_asr_batch_device(lh_family* f, int32_t n, int32_t T, int32_t max_depth, c
   int32_t* site_scal = w.site_scal.get<int32_t>();
   for (int off = 0; off < n; off += chunk) {
     const int m = std::min(chunk, n - off);
-    const double* r_m = rates + (size_t)off * R;
-    const double* pi_m = pi + (size_t)off * 4;
-    const int32_t* ops_m = ops + (size_t)off * n_ops * 4;
-    const double* bl_m = brlen + (size_t)off * nodes;
-    lh::launch_gtr_setup(m, er + (size_t)off * 6, pi_m, eig, stream);
-    // per-rate planes: K1 must not mix the categories here
-    const int planes = lh::launch_prune(f->host, m, R, T, max_depth, ops_m, bl_m, r_m, eig, w.prune, pi_m, site_lik,
-                                        site_scal, stream, false);
-    if (planes < 0) return fail(std::string("lh_asr_batch: ") + lh::prune_last_error());
-    f->k1_form = lh::prune_last_form();
-    if (planes != R && f->host.n_prune > 0) return fail("lh_asr_batch: internal error (rate planes were mixed)");
+    const TreeBatch g = b.slice(off, m);
+    lh::launch_gtr_setup(m, g.er, g.pi, eig, stream);
+    int planes = 0;
+    if (prune_group(f, "lh_asr_batch", g, g.model, false, stream, &planes)) return 1;
     if (f->profile && f->asr_timer.begin(stream)) return 1;
-    if (lh::launch_asr(f->host, m, R, T, ops_m, bl_m, r_m, eig, pi_m, site_lik, site_scal, naive + (size_t)off * L, seed,
+    if (lh::launch_asr(f->host, m, R, T, g.ops, g.brlen, g.model, eig, g.pi, site_lik, site_scal, naive + (size_t)off * L, seed,
                        first_sample + (uint64_t)off, aw.clv.get<double>(), aw.desc.get(), anc + (size_t)off * n_ops * L,
                        rate_choice ? rate_choice + (size_t)off * L : aw.choice.get<uint8_t>(), w.prune.hdr, stream))
       return fail("lh_asr_batch: launch failed");
@@ -1638,33 +1746,25 @@ int lh_asr_batch_device(lh_family* f, int32_t n, int32_t T, int32_t max_depth, c
 int lh_asr_batch(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops, const double* brlen,
                  const double* er, const double* pi, const double* rates, int32_t R, const uint8_t* naive,
                  uint64_t seed, uint64_t first_sample, uint8_t* anc, uint8_t* rate_choice) {
-  if (int rc = check_batch(f, "lh_asr_batch", n, T, R, max_depth)) return rc > 0;
+  const TreeBatch host{n, T, max_depth, ops, brlen, er, pi, rates, R, true};
+  if (int rc = check_batch(f, "lh_asr_batch", host)) return rc > 0;
   DeviceGuard guard(f);
-  if (!ops || !brlen || !er || !pi || !rates || !naive || !anc) return fail("lh_asr_batch: null array");
-  const size_t nodes = 2 * (size_t)T - 2, n_ops = (size_t)T - 2, L = f->host.n_sites;
-  if (!valid_schedules(ops, (size_t)n, T, (int)nodes, max_depth))
-    return fail("lh_asr_batch: malformed schedule op (use lh_schedule_tree)");
-  for (size_t k = 0; k < (size_t)n * L; ++k)
-    if (naive[k] > 4) return fail("lh_asr_batch: naive base out of range");
-  HostInputs& in = f->in;
+  if (!host.has_arrays() || !naive || !anc) return fail("lh_asr_batch: null array");
+  const size_t n_ops = host.n_ops(), L = f->host.n_sites;
+  if (!valid_schedules(host)) return fail("lh_asr_batch: malformed schedule op (use lh_schedule_tree)");
+  if (valid_naive("lh_asr_batch", naive, (size_t)n * L)) return 1;
   HostOutputs& out = f->out;
   // sub-batches bound the device copy of the output (anc: (T-2) * L bytes per sample)
   const int sub = (int)std::max<size_t>(1, std::min<size_t>(n, ((size_t)1 << 30) / std::max<size_t>(n_ops * L, 1)));
   for (int off = 0; off < n; off += sub) {
     const int m = std::min(sub, n - off);
     const size_t anc_bytes = n_ops * L * m, choice_bytes = L * m;
+    TreeBatch dev;
     if (out.anc.ensure(anc_bytes) || out.rate_choice.ensure(choice_bytes) ||
-        stage_inputs(f, {{ops + (size_t)off * n_ops * 4, sizeof(int32_t) * 4 * n_ops * m, &in.ops},
-                         {brlen + (size_t)off * nodes, sizeof(double) * nodes * m, &in.brlen},
-                         {er + (size_t)off * 6, sizeof(double) * 6 * m, &in.er},
-                         {pi + (size_t)off * 4, sizeof(double) * 4 * m, &in.pi},
-                         {rates + (size_t)off * R, sizeof(double) * R * m, &in.rates},
-                         {naive + (size_t)off * L, L * m, &in.naive}}))
+        stage_batch(f, host.slice(off, m), {{naive + (size_t)off * L, L * m, &f->in.naive}}, &dev))
       return 1;
-    if (lh_asr_batch_device(f, m, T, max_depth, in.ops.get<const int32_t>(), in.brlen.get<const double>(),
-                            in.er.get<const double>(), in.pi.get<const double>(), in.rates.get<const double>(), R,
-                            in.naive.get<const uint8_t>(), seed, first_sample + (uint64_t)off, out.anc.get<uint8_t>(),
-                            out.rate_choice.get<uint8_t>(), nullptr))
+    if (lh_asr_batch_device(f, m, T, max_depth, dev.ops, dev.brlen, dev.er, dev.pi, dev.model, R, f->in.naive.get<const uint8_t>(), seed,
+                            first_sample + (uint64_t)off, out.anc.get<uint8_t>(), out.rate_choice.get<uint8_t>(), nullptr))
       return 1;
     if (copy_back(f, "lh_asr_batch",
                   {{anc + (size_t)off * n_ops * L, out.anc.get(), anc_bytes},
@@ -1680,10 +1780,10 @@ int lh_forward_batch(lh_family* f, int32_t n, const double* em, double* loglik, 
   if (n <= 0) return n == 0 ? 0 : fail("lh_forward_batch: negative batch size");
   if (!em || !loglik) return fail("lh_forward_batch: null array");
   const size_t C = f->host.n_xmsa, FS = f->host.forward_size, SS = f->host.scaler_size;
-  const lh_eval_outputs none{nullptr, nullptr, nullptr, nullptr};
+  const lh_eval_outputs none{};
   const lh_eval_outputs& o = outs ? *outs : none;
   HostOutputs& out = f->out;
-  lh_eval_outputs d_outs{nullptr, nullptr, nullptr, nullptr};
+  lh_eval_outputs d_outs{};
   if (out.loglik.ensure(sizeof(double) * n) || out_buf(o.forward, out.forward, sizeof(double) * FS * n, &d_outs.forward) ||
       out_buf(o.scaler_counts, out.scaler_counts, sizeof(int32_t) * SS * n, &d_outs.scaler_counts) ||
       stage_inputs(f, {{em, sizeof(double) * C * n, &f->in.em}}))
@@ -1700,19 +1800,14 @@ int lh_forward_batch(lh_family* f, int32_t n, const double* em, double* loglik, 
 int lh_eval_posterior_batch_device(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops,
                                    const double* brlen, const double* er, const double* pi, const double* alpha, int32_t R,
                                    const lh_posterior_outputs* outs, void* hip_stream) {
-  if (int rc = check_batch(f, "lh_eval_posterior_batch_device", n, T, R, max_depth, true)) return rc > 0;
+  const TreeBatch b{n, T, max_depth, ops, brlen, er, pi, alpha, R};
+  if (int rc = check_batch(f, "lh_eval_posterior_batch_device", b, true)) return rc > 0;
   DeviceGuard guard(f);
   hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-  const lh_posterior_outputs none{nullptr, nullptr, nullptr, nullptr, nullptr};
+  const lh_posterior_outputs none{};
   const lh_posterior_outputs& o = outs ? *outs : none;
   const size_t FS = f->host.forward_size;
   PosteriorWs& pw = f->post;
-  // what the caller does not hand in comes from the handle's buffers
-  auto own = [](double*& p, DevBuf& b, size_t bytes) {
-    if (!p && b.ensure(bytes)) return 1;
-    if (!p) p = b.get<double>();
-    return 0;
-  };
   // the forward arrays go where the posteriors are wanted: K5 overwrites them in place
   double *post = o.posterior, *ll = o.loglik, *w = nullptr, *stats = o.weight_stats, *partial = nullptr;
   const bool reduce = o.weighted_sum || o.weight_stats;
@@ -1721,9 +1816,10 @@ int lh_eval_posterior_batch_device(lh_family* f, int32_t n, int32_t T, int32_t m
                   (o.weighted_sum && own(partial, pw.partial, sizeof(double) * FS * lh::posterior_slabs(n))))))
     return 1;
   lh_eval_outputs eo{nullptr, nullptr, post, nullptr};
-  if (lh_eval_batch_device(f, n, T, max_depth, ops, brlen, er, pi, alpha, R, ll, &eo, hip_stream)) return 1;
+  if (eval_device(f, b, ll, &eo, hip_stream)) return 1;
   if (f->profile && f->post_timer.begin(stream)) return 1;
   lh::launch_posterior(f->sampler_dev, n, post, FS, ll, stream);
+  // (not WeightReduce: K5's reduction also sums the posteriors, through its slab partials)
   if (reduce) lh::launch_posterior_reduce(n, FS, post, ll, o.log_offset, w, partial, o.weighted_sum, stats, stream);
   if (f->profile && f->post_timer.end(stream)) return 1;
   LH_HIP(hipGetLastError());
@@ -1733,45 +1829,35 @@ int lh_eval_posterior_batch_device(lh_family* f, int32_t n, int32_t T, int32_t m
 int lh_eval_posterior_batch(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops,
                             const double* brlen, const double* er, const double* pi, const double* alpha, int32_t R,
                             const lh_posterior_outputs* outs) {
-  if (int rc = check_batch(f, "lh_eval_posterior_batch", n, T, R, max_depth, true)) return rc > 0;
+  const TreeBatch host{n, T, max_depth, ops, brlen, er, pi, alpha, R};
+  if (int rc = check_batch(f, "lh_eval_posterior_batch", host, true)) return rc > 0;
   DeviceGuard guard(f);
-  if (!ops || !brlen || !er || !pi || !alpha) return fail("lh_eval_posterior_batch: null array");
-  const lh_posterior_outputs none{nullptr, nullptr, nullptr, nullptr, nullptr};
+  if (!host.has_arrays()) return fail("lh_eval_posterior_batch: null array");
+  const lh_posterior_outputs none{};
   const lh_posterior_outputs& o = outs ? *outs : none;
   if (!o.posterior && !o.weighted_sum && !o.weight_stats && !o.loglik) return 0;  // nothing asked for
-  const size_t nodes = 2 * (size_t)T - 2, n_ops = (size_t)T - 2, FS = f->host.forward_size;
-  HostInputs& in = f->in;
+  const size_t FS = f->host.forward_size;
   HostOutputs& out = f->out;
-  lh_posterior_outputs dev{nullptr, nullptr, nullptr, nullptr, nullptr};
+  lh_posterior_outputs d{};
+  TreeBatch dev;
   if (f->forward_dev.ensure(sizeof(double) * FS * n) || out.loglik.ensure(sizeof(double) * n) ||
-      out_buf(o.weighted_sum, out.weighted_sum, sizeof(double) * FS, &dev.weighted_sum) ||
-      out_buf(o.weight_stats, out.weight_stats, sizeof(double) * 3, &dev.weight_stats) ||
-      stage_inputs(f, {{ops, sizeof(int32_t) * 4 * n_ops * n, &in.ops},
-                       {brlen, sizeof(double) * nodes * n, &in.brlen},
-                       {er, sizeof(double) * 6 * n, &in.er},
-                       {pi, sizeof(double) * 4 * n, &in.pi},
-                       {alpha, sizeof(double) * n, &in.alpha},
-                       {o.log_offset, sizeof(double) * n, &in.log_offset}}))
+      out_buf(o.weighted_sum, out.weighted_sum, sizeof(double) * FS, &d.weighted_sum) ||
+      out_buf(o.weight_stats, out.weight_stats, sizeof(double) * 3, &d.weight_stats) ||
+      stage_batch(f, host, {{o.log_offset, sizeof(double) * n, &f->in.log_offset}}, &dev))
     return 1;
-  dev.log_offset = o.log_offset ? in.log_offset.get<const double>() : nullptr;
-  dev.loglik = out.loglik.get<double>();
-  dev.posterior = f->forward_dev.get<double>();
-  if (lh_eval_posterior_batch_device(f, n, T, max_depth, in.ops.get<const int32_t>(), in.brlen.get<const double>(),
-                                     in.er.get<const double>(), in.pi.get<const double>(), in.alpha.get<const double>(), R,
-                                     &dev, nullptr))
-    return 1;
-  if (!valid_schedules(ops, (size_t)n, T, (int)nodes, max_depth)) return refuse_schedules(f, "lh_eval_posterior_batch");
-  return copy_back(f, "lh_eval_posterior_batch",
-                   {{o.loglik, dev.loglik, sizeof(double) * n},
-                    {o.posterior, dev.posterior, sizeof(double) * FS * n},
-                    {o.weighted_sum, dev.weighted_sum, sizeof(double) * FS},
-                    {o.weight_stats, dev.weight_stats, sizeof(double) * 3}});
+  d.log_offset = o.log_offset ? f->in.log_offset.get<const double>() : nullptr;
+  d.loglik = out.loglik.get<double>();
+  d.posterior = f->forward_dev.get<double>();
+  if (lh_eval_posterior_batch_device(f, n, T, max_depth, dev.ops, dev.brlen, dev.er, dev.pi, dev.model, R, &d, nullptr)) return 1;
+  return finish_batch(f, "lh_eval_posterior_batch", host,
+                      {{o.loglik, d.loglik, sizeof(double) * n},
+                       {o.posterior, d.posterior, sizeof(double) * FS * n},
+                       {o.weighted_sum, d.weighted_sum, sizeof(double) * FS},
+                       {o.weight_stats, d.weight_stats, sizeof(double) * 3}});
 }
 
 int lh_posterior_profile_read(lh_family* f, double* ms_posterior, int64_t* n_launches) {
-  if (!f) return fail("null family");
-  DeviceGuard guard(f);
-  return f->post_timer.read(ms_posterior, n_launches);
+  return profile_read(f, &lh_family::post_timer, ms_posterior, n_launches);
 }
 
 // ---- K6: posterior probabilities of candidate naive sequences (lh_naive_probs.hip) ----
@@ -1860,34 +1946,31 @@ int lh_family_set_candidates(lh_family* f, int32_t K, const uint8_t* seqs, doubl
 int lh_eval_candidates_batch_device(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops,
                                     const double* brlen, const double* er, const double* pi, const double* alpha, int32_t R,
                                     const lh_candidate_outputs* outs, void* hip_stream) {
+  const TreeBatch b{n, T, max_depth, ops, brlen, er, pi, alpha, R};
   const std::string W = "lh_eval_candidates_batch_device";
-  if (int rc = check_batch(f, W, n, T, R, max_depth)) return rc > 0;
+  if (int rc = check_batch(f, W, b)) return rc > 0;
   DeviceGuard guard(f);
   CandidateWs& cw = f->cand;
   const lh::CandidateTables& tab = cw.tab;
   if (tab.K == 0) return fail(W + ": lh_family_set_candidates has not been called");
   hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-  const lh_candidate_outputs none{nullptr, nullptr, nullptr, nullptr, nullptr};
+  const lh_candidate_outputs none{};
   const lh_candidate_outputs& o = outs ? *outs : none;
-  auto own = [](double*& p, DevBuf& b, size_t bytes) {
-    if (!p && b.ensure(bytes)) return 1;
-    if (!p) p = b.get<double>();
-    return 0;
-  };
-  double *ll = o.loglik, *w = nullptr, *stats = o.weight_stats, *partial = nullptr;
+  double *ll = o.loglik, *partial = nullptr;
+  WeightReduce wr;
   const bool reduce = o.weighted_sum || o.weight_stats;
   const int slabs = lh::candidate_slabs(n);
   if (own(ll, cw.loglik, sizeof(double) * n) || cw.lem.ensure(sizeof(double) * n * (size_t)tab.n_lem) ||
       cw.base.ensure(sizeof(double) * n) ||
-      (reduce && (own(w, cw.weights, sizeof(double) * n) || own(stats, cw.stats, sizeof(double) * 3) ||
+      (reduce && (wr.prepare(n, cw.weights, cw.stats, o.weight_stats) ||
                   (o.weighted_sum && own(partial, cw.partial, sizeof(double) * slabs * (size_t)tab.K)))))
     return 1;
   const lh::LogEmRequest lem{cw.lem_cols.get<const int32_t>(), tab.n_lem, cw.lem.get<double>()};
-  if (eval_device(f, n, T, max_depth, ops, brlen, er, pi, alpha, R, ll, nullptr, hip_stream, lem)) return 1;
+  if (eval_device(f, b, ll, nullptr, hip_stream, lem)) return 1;
   if (f->profile && f->cand_timer.begin(stream)) return 1;
-  if (reduce) lh::launch_posterior_reduce(n, 0, nullptr, ll, o.log_offset, w, nullptr, nullptr, stats, stream);
+  if (reduce) wr.launch(n, ll, o.log_offset, stream);
   if (o.log_cand || o.weighted_sum)
-    lh::launch_candidates(tab, n, cw.lem.get<const double>(), ll, o.weighted_sum ? w : nullptr, cw.base.get<double>(),
+    lh::launch_candidates(tab, n, cw.lem.get<const double>(), ll, o.weighted_sum ? wr.w : nullptr, cw.base.get<double>(),
                           o.log_cand, partial, stream);
   if (o.weighted_sum) lh::launch_slab_sum(slabs, tab.K, partial, o.weighted_sum, stream);
   if (f->profile && f->cand_timer.end(stream)) return 1;
@@ -1899,39 +1982,31 @@ int lh_eval_candidates_batch(lh_family* f, int32_t n, int32_t T, int32_t max_dep
                              const double* brlen, const double* er, const double* pi, const double* alpha, int32_t R,
                              const lh_candidate_outputs* outs) {
   const std::string W = "lh_eval_candidates_batch";
-  if (int rc = check_batch(f, W, n, T, R, max_depth)) return rc > 0;
+  const TreeBatch host{n, T, max_depth, ops, brlen, er, pi, alpha, R};
+  if (int rc = check_batch(f, W, host)) return rc > 0;
   DeviceGuard guard(f);
-  if (!ops || !brlen || !er || !pi || !alpha) return fail(W + ": null array");
+  if (!host.has_arrays()) return fail(W + ": null array");
   if (f->cand.tab.K == 0) return fail(W + ": lh_family_set_candidates has not been called");
-  const lh_candidate_outputs none{nullptr, nullptr, nullptr, nullptr, nullptr};
+  const lh_candidate_outputs none{};
   const lh_candidate_outputs& o = outs ? *outs : none;
   if (!o.log_cand && !o.weighted_sum && !o.weight_stats && !o.loglik) return 0;  // nothing asked for
-  const size_t nodes = 2 * (size_t)T - 2, n_ops = (size_t)T - 2, K = f->cand.tab.K;
-  HostInputs& in = f->in;
+  const size_t K = f->cand.tab.K;
   HostOutputs& out = f->out;
-  lh_candidate_outputs dev{nullptr, nullptr, nullptr, nullptr, nullptr};
-  if (out.loglik.ensure(sizeof(double) * n) || out_buf(o.log_cand, out.log_cand, sizeof(double) * K * n, &dev.log_cand) ||
-      out_buf(o.weighted_sum, out.weighted_sum, sizeof(double) * K, &dev.weighted_sum) ||
-      out_buf(o.weight_stats, out.weight_stats, sizeof(double) * 3, &dev.weight_stats) ||
-      stage_inputs(f, {{ops, sizeof(int32_t) * 4 * n_ops * n, &in.ops},
-                       {brlen, sizeof(double) * nodes * n, &in.brlen},
-                       {er, sizeof(double) * 6 * n, &in.er},
-                       {pi, sizeof(double) * 4 * n, &in.pi},
-                       {alpha, sizeof(double) * n, &in.alpha},
-                       {o.log_offset, sizeof(double) * n, &in.log_offset}}))
+  lh_candidate_outputs d{};
+  TreeBatch dev;
+  if (out.loglik.ensure(sizeof(double) * n) || out_buf(o.log_cand, out.log_cand, sizeof(double) * K * n, &d.log_cand) ||
+      out_buf(o.weighted_sum, out.weighted_sum, sizeof(double) * K, &d.weighted_sum) ||
+      out_buf(o.weight_stats, out.weight_stats, sizeof(double) * 3, &d.weight_stats) ||
+      stage_batch(f, host, {{o.log_offset, sizeof(double) * n, &f->in.log_offset}}, &dev))
     return 1;
-  dev.log_offset = o.log_offset ? in.log_offset.get<const double>() : nullptr;
-  dev.loglik = out.loglik.get<double>();
-  if (lh_eval_candidates_batch_device(f, n, T, max_depth, in.ops.get<const int32_t>(), in.brlen.get<const double>(),
-                                      in.er.get<const double>(), in.pi.get<const double>(), in.alpha.get<const double>(), R,
-                                      &dev, nullptr))
-    return 1;
-  if (!valid_schedules(ops, (size_t)n, T, (int)nodes, max_depth)) return refuse_schedules(f, W.c_str());
-  return copy_back(f, W.c_str(),
-                   {{o.loglik, dev.loglik, sizeof(double) * n},
-                    {o.log_cand, dev.log_cand, sizeof(double) * K * n},
-                    {o.weighted_sum, dev.weighted_sum, sizeof(double) * K},
-                    {o.weight_stats, dev.weight_stats, sizeof(double) * 3}});
+  d.log_offset = o.log_offset ? f->in.log_offset.get<const double>() : nullptr;
+  d.loglik = out.loglik.get<double>();
+  if (lh_eval_candidates_batch_device(f, n, T, max_depth, dev.ops, dev.brlen, dev.er, dev.pi, dev.model, R, &d, nullptr)) return 1;
+  return finish_batch(f, W.c_str(), host,
+                      {{o.loglik, d.loglik, sizeof(double) * n},
+                       {o.log_cand, d.log_cand, sizeof(double) * K * n},
+                       {o.weighted_sum, d.weighted_sum, sizeof(double) * K},
+                       {o.weight_stats, d.weight_stats, sizeof(double) * 3}});
 }
 
 int lh_candidates_info(const lh_family* f, int32_t* n_candidates, int32_t* n_sites) {
@@ -1951,10 +2026,9 @@ int lh_candidates_layout(const lh_family* f, int32_t* n_var_sites, int32_t* n_le
 }
 
 int lh_candidates_profile_read(lh_family* f, double* ms, int64_t* n_launches) {
-  if (!f) return fail("null family");
-  DeviceGuard guard(f);
   double a = 0.0, b = 0.0;
-  if (f->prior_timer.read(&a, nullptr) || f->cand_timer.read(&b, n_launches)) return 1;
+  if (profile_read(f, &lh_family::prior_timer, &a, nullptr) || profile_read(f, &lh_family::cand_timer, &b, n_launches))
+    return 1;
   if (ms) {
     ms[0] = a;
     ms[1] = b;
@@ -2112,7 +2186,8 @@ int lh_eval_draw_batch_device(lh_family* f, int32_t n, int32_t T, int32_t max_de
                               const double* brlen, const double* er, const double* pi, const double* alpha, int32_t R,
                               const uint32_t* words, double* loglik, uint64_t* hash, int32_t* states, void* hip_stream) {
   const std::string W = "lh_eval_draw_batch_device";
-  if (int rc = check_batch(f, W, n, T, R, max_depth, true)) return rc > 0;
+  const TreeBatch b{n, T, max_depth, ops, brlen, er, pi, alpha, R};
+  if (int rc = check_batch(f, W, b, true)) return rc > 0;
   DeviceGuard guard(f);
   lh::CollectTables t;
   if (collect_tables(f, W, &t)) return 1;
@@ -2135,20 +2210,20 @@ int lh_eval_draw_batch(lh_family* f, int32_t n, int32_t T, int32_t max_depth, co
                        const double* er, const double* pi, const double* alpha, int32_t R, const uint32_t* words,
                        double* loglik, uint64_t* hash, int32_t* states) {
   const std::string W = "lh_eval_draw_batch";
-  if (int rc = check_batch(f, W, n, T, R, max_depth, true)) return rc > 0;
+  const TreeBatch host{n, T, max_depth, ops, brlen, er, pi, alpha, R};
+  if (int rc = check_batch(f, W, host, true)) return rc > 0;
   DeviceGuard guard(f);
   lh::CollectTables t;
   if (collect_tables(f, W, &t)) return 1;
-  if (!ops || !brlen || !er || !pi || !alpha || !words || !loglik || !hash) return fail(W + ": null array");
+  if (!host.has_arrays() || !words || !loglik || !hash) return fail(W + ": null array");
   std::chrono::steady_clock::time_point st[4];
-  if (sample_host_batch(f, n, T, max_depth, ops, brlen, er, pi, alpha, R, words, false, false, st)) return 1;
+  if (sample_host_batch(f, host, words, false, false, st)) return 1;
   HostOutputs& out = f->out;
   if (collect_launch(f, t, n, out.states.get<const int32_t>(), nullptr)) return 1;
-  if (!valid_schedules(ops, (size_t)n, T, 2 * T - 2, max_depth)) return refuse_schedules(f, W.c_str());
-  return copy_back(f, W.c_str(),
-                   {{loglik, out.loglik.get(), sizeof(double) * n},
-                    {hash, f->collect.hash.get(), sizeof(uint64_t) * n},
-                    {states, out.states.get(), sizeof(int32_t) * f->sampler.states_per_sample * (size_t)n}});
+  return finish_batch(f, W.c_str(), host,
+                      {{loglik, out.loglik.get(), sizeof(double) * n},
+                       {hash, f->collect.hash.get(), sizeof(uint64_t) * n},
+                       {states, out.states.get(), sizeof(int32_t) * f->sampler.states_per_sample * (size_t)n}});
 }
 
 int lh_naive_sequences(lh_family* f, int32_t n, const int32_t* states, uint8_t* seqs, uint64_t* hash) {
@@ -2199,9 +2274,7 @@ int lh_draws_reset(lh_family* f) {
 }
 
 int lh_collect_profile_read(lh_family* f, double* ms, int64_t* n_launches) {
-  if (!f) return fail("null family");
-  DeviceGuard guard(f);
-  return f->collect_timer.read(ms, n_launches);
+  return profile_read(f, &lh_family::collect_timer, ms, n_launches);
 }
 
 }  // extern "C"
@@ -2240,50 +2313,32 @@ int lh_lineage_batch(lh_family* f, int32_t n, int32_t T, int32_t max_depth, cons
                      uint64_t seed, uint64_t first_sample, const int32_t* path, int32_t P, uint64_t* nt_hash,
                      uint64_t* aa_hash) {
   const std::string W = "lh_lineage_batch";
-  if (int rc = check_batch(f, W, n, T, R, max_depth)) {
+  const TreeBatch host{n, T, max_depth, ops, brlen, er, pi, rates, R, true};
+  if (int rc = check_batch(f, W, host)) {
     if (rc < 0) f->lineage.last.n = -1;
     return rc > 0;
   }
   DeviceGuard guard(f);
   f->lineage.last.n = -1;
-  if (!ops || !brlen || !er || !pi || !rates || !naive || !path || !nt_hash || !aa_hash) return fail(W + ": null array");
+  if (!host.has_arrays() || !naive || !path || !nt_hash || !aa_hash) return fail(W + ": null array");
   if (P < 1 || P > T - 2) return fail(W + ": path length must be in 1 .. n_tips - 2");
-  const size_t nodes = 2 * (size_t)T - 2, n_ops = (size_t)T - 2, L = f->host.n_sites;
+  const size_t n_ops = host.n_ops(), L = f->host.n_sites;
   // the whole batch's anc stays on the device for lh_lineage_resolve: no sub-batches here
   const size_t most = std::min<size_t>(((size_t)1 << 30) / std::max<size_t>(n_ops * L, 1), (size_t)INT32_MAX / (P + 1));
   if ((size_t)n > most)
     return fail(W + ": batch too large to keep its sampled states on the device: at most " + std::to_string(most) +
                 " samples per call for this family");
-  if (!valid_schedules(ops, (size_t)n, T, (int)nodes, max_depth))
-    return fail(W + ": malformed schedule op (use lh_schedule_tree)");
-  for (size_t k = 0; k < (size_t)n * L; ++k)
-    if (naive[k] > 4) return fail(W + ": naive base out of range");
-  for (size_t i = 0; i < (size_t)n; ++i) {
-    bool ended = false;
-    for (int s = 0; s < P; ++s) {
-      const int32_t v = path[i * P + s];
-      if (v == -1) ended = true;
-      else if (ended || v < T || v >= (int32_t)nodes) return fail(W + ": path entries are inner nodes, then -1 padding");
-    }
-    if (path[i * P] == -1) return fail(W + ": empty path");
-  }
-  HostInputs& in = f->in;
+  if (!valid_schedules(host)) return fail(W + ": malformed schedule op (use lh_schedule_tree)");
+  if (valid_naive(W, naive, (size_t)n * L) || valid_paths(W, path, P, host)) return 1;
   HostOutputs& out = f->out;
   LineageWs& w = f->lineage;
   const size_t hb = sizeof(uint64_t) * n * (P + 1);
+  TreeBatch dev;
   if (out.anc.ensure(n_ops * L * n) || out.rate_choice.ensure(L * n) || w.nt_hash.ensure(hb) || w.aa_hash.ensure(hb) ||
-      stage_inputs(f, {{ops, sizeof(int32_t) * 4 * n_ops * n, &in.ops},
-                       {brlen, sizeof(double) * nodes * n, &in.brlen},
-                       {er, sizeof(double) * 6 * n, &in.er},
-                       {pi, sizeof(double) * 4 * n, &in.pi},
-                       {rates, sizeof(double) * R * n, &in.rates},
-                       {naive, L * n, &w.naive},
-                       {path, sizeof(int32_t) * P * n, &w.path}}))
+      stage_batch(f, host, {{naive, L * n, &w.naive}, {path, sizeof(int32_t) * P * n, &w.path}}, &dev))
     return 1;
-  if (lh_asr_batch_device(f, n, T, max_depth, in.ops.get<const int32_t>(), in.brlen.get<const double>(),
-                          in.er.get<const double>(), in.pi.get<const double>(), in.rates.get<const double>(), R,
-                          w.naive.get<const uint8_t>(), seed, first_sample, out.anc.get<uint8_t>(),
-                          out.rate_choice.get<uint8_t>(), nullptr))
+  if (lh_asr_batch_device(f, n, T, max_depth, dev.ops, dev.brlen, dev.er, dev.pi, dev.model, R, w.naive.get<const uint8_t>(), seed, first_sample,
+                          out.anc.get<uint8_t>(), out.rate_choice.get<uint8_t>(), nullptr))
     return 1;
   if (lh_lineage_collect_device(f, n, T, out.anc.get<const uint8_t>(), w.naive.get<const uint8_t>(),
                                 w.path.get<const int32_t>(), P, w.nt_hash.get<uint64_t>(), w.aa_hash.get<uint64_t>(),
@@ -2331,9 +2386,7 @@ int lh_lineage_reset(lh_family* f) {
 }
 
 int lh_lineage_profile_read(lh_family* f, double* ms, int64_t* n_launches) {
-  if (!f) return fail("null family");
-  DeviceGuard guard(f);
-  return f->lineage_timer.read(ms, n_launches);
+  return profile_read(f, &lh_family::lineage_timer, ms, n_launches);
 }
 
 }  // extern "C"
@@ -2344,9 +2397,10 @@ namespace {
 
 // The shape checks lh_eval_lineage_batch[_device] share (everything that needs no array): lh_lineage_batch's and
 // lh_eval_draw_batch's refusals, the draws, and the bound on the sampled states that stay on the device.
-int lineage_eval_check(lh_family* f, const std::string& W, int32_t n, int32_t T, int32_t R, int32_t max_depth,
-                       uint64_t first_sample, int32_t D, int32_t P, lh::CollectTables* t) {
-  if (int rc = check_batch(f, W, n, T, R, max_depth, true)) {
+int lineage_eval_check(lh_family* f, const std::string& W, const TreeBatch& b, uint64_t first_sample, int32_t D, int32_t P,
+                       lh::CollectTables* t) {
+  const int n = b.n, T = b.T, R = b.R;
+  if (int rc = check_batch(f, W, b, true)) {
     if (rc < 0) f->lineage.last.n = -1;
     return rc;
   }
@@ -2356,7 +2410,7 @@ int lineage_eval_check(lh_family* f, const std::string& W, int32_t n, int32_t T,
   if (D > 1 && (first_sample > ((uint64_t)1 << 32) || first_sample + (uint64_t)n > ((uint64_t)1 << 32)))
     return fail(W + ": with more than one draw per row the sample numbers first_sample .. first_sample + n - 1 must lie "
                     "below 2^32 (the draw number takes the upper half)");
-  const size_t n_ops = (size_t)T - 2, L = f->host.n_sites;
+  const size_t n_ops = b.n_ops(), L = f->host.n_sites;
   // the whole batch's anc stays on the device for lh_lineage_resolve: n * draws samples of it
   const size_t most = std::min<size_t>(((size_t)1 << 30) / std::max<size_t>(n_ops * L, 1), (size_t)INT32_MAX / (P + 1)) / (size_t)D;
   if ((size_t)n > most)
@@ -2377,23 +2431,21 @@ int lh_eval_lineage_batch_device(lh_family* f, int32_t n, int32_t T, int32_t max
                                  const double* brlen, const double* er, const double* pi, const double* alpha, int32_t R,
                                  const uint32_t* words, uint64_t seed, uint64_t first_sample, int32_t D,
                                  const int32_t* path, int32_t P, const lh_lineage_eval_outputs* outs, void* hip_stream) {
+  const TreeBatch b{n, T, max_depth, ops, brlen, er, pi, alpha, R};
   const std::string W = "lh_eval_lineage_batch_device";
   lh::CollectTables t;
-  if (int rc = lineage_eval_check(f, W, n, T, R, max_depth, first_sample, D, P, &t)) return rc > 0;
+  if (int rc = lineage_eval_check(f, W, b, first_sample, D, P, &t)) return rc > 0;
   DeviceGuard guard(f);
-  if (!ops || !brlen || !er || !pi || !alpha || !words || !path || !outs || !outs->loglik || !outs->nt_hash || !outs->aa_hash)
+  if (!b.has_arrays() || !words || !path || !outs || !outs->loglik || !outs->nt_hash || !outs->aa_hash)
     return fail(W + ": null array");
   hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-  const size_t nodes = 2 * (size_t)T - 2, n_ops = (size_t)T - 2, L = f->host.n_sites, FS = f->host.forward_size;
+  const size_t n_ops = b.n_ops(), L = f->host.n_sites, FS = f->host.forward_size;
   const size_t NS = t.states_per_sample, NW = f->sampler.words_per_sample, S = (size_t)P + 1;
   // launch groups: the smaller of the evaluation's limit and the sampling kernel's (whose CLV area and grid count
   // virtual samples); one K1 launch, unmixed, serves K2 and K3 of the group, so its planes outlive K2
   const size_t clv_per_sample = sizeof(double) * n_ops * 4 * lh::asr_slots((int)L, R);
-  const size_t k1_per_sample = k1_bytes_per_sample(f, T, R) + sizeof(double) * R * 6 * (size_t)std::max(f->host.n_prune, 1);
-  const size_t eval_limit = std::min<size_t>(kChunk, std::max<size_t>(1024, ((size_t)16 << 30) / k1_per_sample));
-  const size_t asr_limit =
-      std::max<size_t>(1, std::min<size_t>(8192, std::max<size_t>(64, ((size_t)8 << 30) / (clv_per_sample + k1_per_sample))) / (size_t)D);
-  const int chunk = (int)std::min<size_t>((size_t)n, std::min(eval_limit, asr_limit));
+  const size_t asr_limit = std::max<size_t>(1, asr_group(f, T, R, clv_per_sample) / (size_t)D);
+  const int chunk = (int)std::min<size_t>((size_t)n, std::min(eval_group(f, T, R), asr_limit));
   if (ensure_workspace(f, chunk, R, T)) return 1;
   AsrWs& aw = f->asr;
   CollectWs& c = f->collect;
@@ -2416,34 +2468,29 @@ int lh_eval_lineage_batch_device(lh_family* f, int32_t n, int32_t T, int32_t max
   c.n_last = -1;
   for (int off = 0; off < n; off += chunk) {
     const int m = std::min(chunk, n - off);
-    const double* pi_m = pi + (size_t)off * 4;
-    const int32_t* ops_m = ops + (size_t)off * n_ops * 4;
-    const double* bl_m = brlen + (size_t)off * nodes;
+    const TreeBatch g = b.slice(off, m);
     double* r_m = rates + (size_t)off * R;
     if (f->profile && f->chain_timer.begin(stream)) return 1;
-    lh::launch_model_setup(m, R, er + (size_t)off * 6, pi_m, alpha + off, r_m, eig, stream);
+    lh::launch_model_setup(m, R, g.er, g.pi, g.model, r_m, eig, stream);
     if (f->profile && f->chain_timer.mark(1, stream)) return 1;
-    const int planes = lh::launch_prune(f->host, m, R, T, max_depth, ops_m, bl_m, r_m, eig, w.prune, pi_m, site_lik, site_scal,
-                                        stream, false);
-    if (planes < 0) return fail(W + ": " + lh::prune_last_error());
-    f->k1_form = lh::prune_last_form();
-    if (planes != R && f->host.n_prune > 0) return fail(W + ": internal error (rate planes were mixed)");
+    int planes = 0;
+    if (prune_group(f, W, g, r_m, false, stream, &planes)) return 1;
     if (f->profile && f->chain_timer.mark(2, stream)) return 1;
-    if (run_forward(f, m, planes, site_lik, site_scal, pi_m, nullptr, nullptr, outs->loglik + off, &fwd_outs, off, stream)) return 1;
+    if (run_forward(f, m, planes, site_lik, site_scal, g.pi, nullptr, nullptr, outs->loglik + off, &fwd_outs, off, stream)) return 1;
     lh::launch_sample(f->sampler, f->sampler_dev, m, fwd + (size_t)off * FS, FS, words + (size_t)off * NW, (int)NW,
                       states + (size_t)off * NS, stream);
     lh::launch_collect(t, m, states + (size_t)off * NS, naive + (size_t)off * L, naive_hash + off, stream);
     LH_HIP(hipGetLastError());
     if (f->profile && f->chain_timer.mark(3, stream)) return 1;
     uint8_t* anc_m = anc + (size_t)off * D * n_ops * L;
-    if (lh::launch_asr(f->host, m, R, T, ops_m, bl_m, r_m, eig, pi_m, site_lik, site_scal, naive + (size_t)off * L, seed,
+    if (lh::launch_asr(f->host, m, R, T, g.ops, g.brlen, r_m, eig, g.pi, site_lik, site_scal, naive + (size_t)off * L, seed,
                        first_sample + (uint64_t)off, aw.clv.get<double>(), aw.desc.get(), anc_m, choice + (size_t)off * D * L,
                        w.prune.hdr, stream, D))
       return fail(W + ": launch failed");
     LH_HIP(hipGetLastError());
     if (f->profile && f->chain_timer.mark(4, stream)) return 1;
-    const lh::LineageBatch g{m, T, (int32_t)L, P, anc_m, naive + (size_t)off * L, path + (size_t)off * P, mask, D};
-    lh::launch_lineage(g, outs->nt_hash + (size_t)off * D * S, outs->aa_hash + (size_t)off * D * S, stream);
+    const lh::LineageBatch lg{m, T, (int32_t)L, P, anc_m, naive + (size_t)off * L, path + (size_t)off * P, mask, D};
+    lh::launch_lineage(lg, outs->nt_hash + (size_t)off * D * S, outs->aa_hash + (size_t)off * D * S, stream);
     LH_HIP(hipGetLastError());
     if (f->profile && f->chain_timer.end(stream)) return 1;
   }
@@ -2460,57 +2507,38 @@ int lh_eval_lineage_batch(lh_family* f, int32_t n, int32_t T, int32_t max_depth,
                           uint64_t seed, uint64_t first_sample, int32_t D, const int32_t* path, int32_t P,
                           const lh_lineage_eval_outputs* outs) {
   const std::string W = "lh_eval_lineage_batch";
+  const TreeBatch host{n, T, max_depth, ops, brlen, er, pi, alpha, R};
   lh::CollectTables t;
-  if (int rc = lineage_eval_check(f, W, n, T, R, max_depth, first_sample, D, P, &t)) return rc > 0;
+  if (int rc = lineage_eval_check(f, W, host, first_sample, D, P, &t)) return rc > 0;
   DeviceGuard guard(f);
-  if (!ops || !brlen || !er || !pi || !alpha || !words || !path || !outs || !outs->loglik || !outs->nt_hash || !outs->aa_hash)
+  if (!host.has_arrays() || !words || !path || !outs || !outs->loglik || !outs->nt_hash || !outs->aa_hash)
     return fail(W + ": null array");
-  const size_t nodes = 2 * (size_t)T - 2, n_ops = (size_t)T - 2, L = f->host.n_sites;
-  const size_t NS = t.states_per_sample, NW = f->sampler.words_per_sample;
-  for (size_t i = 0; i < (size_t)n; ++i) {
-    bool ended = false;
-    for (int s = 0; s < P; ++s) {
-      const int32_t v = path[i * P + s];
-      if (v == -1) ended = true;
-      else if (ended || v < T || v >= (int32_t)nodes) return fail(W + ": path entries are inner nodes, then -1 padding");
-    }
-    if (path[i * P] == -1) return fail(W + ": empty path");
-  }
-  HostInputs& in = f->in;
+  const size_t L = f->host.n_sites, NS = t.states_per_sample, NW = f->sampler.words_per_sample;
+  if (valid_paths(W, path, P, host)) return 1;
   HostOutputs& out = f->out;
   LineageWs& lw = f->lineage;
   const size_t hb = sizeof(uint64_t) * n * D * (P + 1);
   lh_lineage_eval_outputs d{};
+  TreeBatch dev;
   if (out.loglik.ensure(sizeof(double) * n) || out_buf(outs->rates, out.rates, sizeof(double) * R * n, &d.rates) ||
       out_buf(outs->states, out.states, sizeof(int32_t) * NS * n, &d.states) || lw.nt_hash.ensure(hb) || lw.aa_hash.ensure(hb) ||
-      stage_inputs(f, {{ops, sizeof(int32_t) * 4 * n_ops * n, &in.ops},
-                       {brlen, sizeof(double) * nodes * n, &in.brlen},
-                       {er, sizeof(double) * 6 * n, &in.er},
-                       {pi, sizeof(double) * 4 * n, &in.pi},
-                       {alpha, sizeof(double) * n, &in.alpha},
-                       {words, sizeof(uint32_t) * NW * n, &in.words},
-                       {path, sizeof(int32_t) * P * n, &lw.path}}))
+      stage_batch(f, host, {{words, sizeof(uint32_t) * NW * n, &f->in.words}, {path, sizeof(int32_t) * P * n, &lw.path}}, &dev))
     return 1;
   d.loglik = out.loglik.get<double>();
   d.nt_hash = lw.nt_hash.get<uint64_t>();
   d.aa_hash = lw.aa_hash.get<uint64_t>();
-  if (lh_eval_lineage_batch_device(f, n, T, max_depth, in.ops.get<const int32_t>(), in.brlen.get<const double>(),
-                                   in.er.get<const double>(), in.pi.get<const double>(), in.alpha.get<const double>(), R,
-                                   in.words.get<const uint32_t>(), seed, first_sample, D, lw.path.get<const int32_t>(), P, &d,
-                                   nullptr))
+  if (lh_eval_lineage_batch_device(f, n, T, max_depth, dev.ops, dev.brlen, dev.er, dev.pi, dev.model, R, f->in.words.get<const uint32_t>(), seed, first_sample, D,
+                                   lw.path.get<const int32_t>(), P, &d, nullptr))
     return 1;
   // (the schedules are checked on the host beside the device, as in lh_eval_draw_batch)
-  int rc = 0;
-  if (!valid_schedules(ops, (size_t)n, T, (int)nodes, max_depth)) rc = refuse_schedules(f, W.c_str());
-  if (!rc)
-    rc = copy_back(f, W.c_str(),
-                   {{outs->loglik, d.loglik, sizeof(double) * n},
-                    {outs->rates, d.rates, sizeof(double) * R * n},
-                    {outs->states, d.states, sizeof(int32_t) * NS * n},
-                    {outs->naive, f->collect.seqs.get(), (size_t)n * L},
-                    {outs->naive_hash, f->collect.hash.get(), sizeof(uint64_t) * n},
-                    {outs->nt_hash, d.nt_hash, hb},
-                    {outs->aa_hash, d.aa_hash, hb}});
+  const int rc = finish_batch(f, W.c_str(), host,
+                              {{outs->loglik, d.loglik, sizeof(double) * n},
+                               {outs->rates, d.rates, sizeof(double) * R * n},
+                               {outs->states, d.states, sizeof(int32_t) * NS * n},
+                               {outs->naive, f->collect.seqs.get(), (size_t)n * L},
+                               {outs->naive_hash, f->collect.hash.get(), sizeof(uint64_t) * n},
+                               {outs->nt_hash, d.nt_hash, hb},
+                               {outs->aa_hash, d.aa_hash, hb}});
   if (rc) {
     lw.last.n = -1;
     f->collect.n_last = -1;
@@ -2519,9 +2547,7 @@ int lh_eval_lineage_batch(lh_family* f, int32_t n, int32_t T, int32_t max_depth,
 }
 
 int lh_lineage_eval_profile_read(lh_family* f, double* ms, int64_t* n_launches) {
-  if (!f) return fail("null family");
-  DeviceGuard guard(f);
-  return f->chain_timer.read(ms, n_launches);
+  return profile_read(f, &lh_family::chain_timer, ms, n_launches);
 }
 
 }  // extern "C"
@@ -2548,25 +2574,22 @@ extern "C" {
 int lh_eval_viterbi_batch_device(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops,
                                  const double* brlen, const double* er, const double* pi, const double* alpha, int32_t R,
                                  const lh_viterbi_outputs* outs, void* hip_stream) {
+  const TreeBatch b{n, T, max_depth, ops, brlen, er, pi, alpha, R};
   const std::string W = "lh_eval_viterbi_batch_device";
-  if (int rc = check_batch(f, W, n, T, R, max_depth, true)) return rc > 0;
+  if (int rc = check_batch(f, W, b, true)) return rc > 0;
   DeviceGuard guard(f);
   if (lh::viterbi_lds_bytes(f->host) > 160 * 1024) return fail(W + ": the junction tables do not fit K8's LDS");
   hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-  const lh_viterbi_outputs none{nullptr, nullptr, nullptr, nullptr, nullptr};
+  const lh_viterbi_outputs none{};
   const lh_viterbi_outputs& o = outs ? *outs : none;
   ViterbiWs& vw = f->vit;
   const size_t S = f->sampler.states_per_sample;
-  double *ll = o.loglik, *lp = o.log_path, *w = nullptr, *stats = o.weight_stats;
+  double *ll = o.loglik, *lp = o.log_path;
+  WeightReduce wr;
   int32_t* states = o.states;
-  auto own = [](double*& p, DevBuf& b, size_t bytes) {
-    if (!p && b.ensure(bytes)) return 1;
-    if (!p) p = b.get<double>();
-    return 0;
-  };
   if (own(ll, vw.loglik, sizeof(double) * n) || own(lp, vw.log_path, sizeof(double) * n) ||
       (!states && vw.states.ensure(sizeof(int32_t) * S * n)) ||
-      (stats && own(w, vw.weights, sizeof(double) * n)) ||
+      (o.weight_stats && wr.prepare(n, vw.weights, vw.stats, o.weight_stats)) ||
       vw.bp.ensure(lh::viterbi_bp_bytes(f->host) * (size_t)std::min(n, kChunk)))
     return 1;
   if (!states) states = vw.states.get<int32_t>();
@@ -2576,9 +2599,8 @@ int lh_eval_viterbi_batch_device(lh_family* f, int32_t n, int32_t T, int32_t max
     if (f->profile && f->vit_timer.end(stream)) return 1;
     return 0;
   };
-  if (eval_device(f, n, T, max_depth, ops, brlen, er, pi, alpha, R, ll, nullptr, hip_stream, lh::LogEmRequest{}, &after))
-    return 1;
-  if (stats) lh::launch_posterior_reduce(n, 0, nullptr, ll, o.log_offset, w, nullptr, nullptr, stats, stream);
+  if (eval_device(f, b, ll, nullptr, hip_stream, lh::LogEmRequest{}, &after)) return 1;
+  if (o.weight_stats) wr.launch(n, ll, o.log_offset, stream);
   LH_HIP(hipGetLastError());
   return 0;
 }
@@ -2587,40 +2609,32 @@ int lh_eval_viterbi_batch(lh_family* f, int32_t n, int32_t T, int32_t max_depth,
                           const double* er, const double* pi, const double* alpha, int32_t R,
                           const lh_viterbi_outputs* outs) {
   const std::string W = "lh_eval_viterbi_batch";
-  if (int rc = check_batch(f, W, n, T, R, max_depth, true)) return rc > 0;
+  const TreeBatch host{n, T, max_depth, ops, brlen, er, pi, alpha, R};
+  if (int rc = check_batch(f, W, host, true)) return rc > 0;
   DeviceGuard guard(f);
-  if (!ops || !brlen || !er || !pi || !alpha) return fail(W + ": null array");
-  const lh_viterbi_outputs none{nullptr, nullptr, nullptr, nullptr, nullptr};
+  if (!host.has_arrays()) return fail(W + ": null array");
+  const lh_viterbi_outputs none{};
   const lh_viterbi_outputs& o = outs ? *outs : none;
   if (!o.loglik && !o.states && !o.log_path && !o.weight_stats) return 0;  // nothing asked for
-  const size_t nodes = 2 * (size_t)T - 2, n_ops = (size_t)T - 2, S = f->sampler.states_per_sample;
-  HostInputs& in = f->in;
+  const size_t S = f->sampler.states_per_sample;
   HostOutputs& out = f->out;
-  lh_viterbi_outputs dev{nullptr, nullptr, nullptr, nullptr, nullptr};
+  lh_viterbi_outputs d{};
+  TreeBatch dev;
   if (out.loglik.ensure(sizeof(double) * n) || out.states.ensure(sizeof(int32_t) * S * n) ||
       out.log_path.ensure(sizeof(double) * n) ||
-      out_buf(o.weight_stats, out.weight_stats, sizeof(double) * 3, &dev.weight_stats) ||
-      stage_inputs(f, {{ops, sizeof(int32_t) * 4 * n_ops * n, &in.ops},
-                       {brlen, sizeof(double) * nodes * n, &in.brlen},
-                       {er, sizeof(double) * 6 * n, &in.er},
-                       {pi, sizeof(double) * 4 * n, &in.pi},
-                       {alpha, sizeof(double) * n, &in.alpha},
-                       {o.log_offset, sizeof(double) * n, &in.log_offset}}))
+      out_buf(o.weight_stats, out.weight_stats, sizeof(double) * 3, &d.weight_stats) ||
+      stage_batch(f, host, {{o.log_offset, sizeof(double) * n, &f->in.log_offset}}, &dev))
     return 1;
-  dev.log_offset = o.log_offset ? in.log_offset.get<const double>() : nullptr;
-  dev.loglik = out.loglik.get<double>();
-  dev.states = out.states.get<int32_t>();
-  dev.log_path = out.log_path.get<double>();
-  if (lh_eval_viterbi_batch_device(f, n, T, max_depth, in.ops.get<const int32_t>(), in.brlen.get<const double>(),
-                                   in.er.get<const double>(), in.pi.get<const double>(), in.alpha.get<const double>(), R, &dev,
-                                   nullptr))
-    return 1;
-  if (!valid_schedules(ops, (size_t)n, T, (int)nodes, max_depth)) return refuse_schedules(f, W.c_str());
-  return copy_back(f, W.c_str(),
-                   {{o.loglik, dev.loglik, sizeof(double) * n},
-                    {o.states, dev.states, sizeof(int32_t) * S * n},
-                    {o.log_path, dev.log_path, sizeof(double) * n},
-                    {o.weight_stats, dev.weight_stats, sizeof(double) * 3}});
+  d.log_offset = o.log_offset ? f->in.log_offset.get<const double>() : nullptr;
+  d.loglik = out.loglik.get<double>();
+  d.states = out.states.get<int32_t>();
+  d.log_path = out.log_path.get<double>();
+  if (lh_eval_viterbi_batch_device(f, n, T, max_depth, dev.ops, dev.brlen, dev.er, dev.pi, dev.model, R, &d, nullptr)) return 1;
+  return finish_batch(f, W.c_str(), host,
+                      {{o.loglik, d.loglik, sizeof(double) * n},
+                       {o.states, d.states, sizeof(int32_t) * S * n},
+                       {o.log_path, d.log_path, sizeof(double) * n},
+                       {o.weight_stats, d.weight_stats, sizeof(double) * 3}});
 }
 
 int lh_viterbi_forward_batch(lh_family* f, int32_t n, const double* em, double* log_path, int32_t* states) {
@@ -2681,9 +2695,7 @@ int lh_family_set_candidate_paths(lh_family* f, int32_t K, const int32_t* states
 }
 
 int lh_viterbi_profile_read(lh_family* f, double* ms, int64_t* n_launches) {
-  if (!f) return fail("null family");
-  DeviceGuard guard(f);
-  return f->vit_timer.read(ms, n_launches);
+  return profile_read(f, &lh_family::vit_timer, ms, n_launches);
 }
 
 // ---- K9: exact posterior distributions of the naive sequence's codons (lh_codon.hip) ----
@@ -2837,41 +2849,38 @@ int lh_codon_layout(const lh_family* f, int32_t* n_codons, int32_t* n_window, in
 int lh_eval_codons_batch_device(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops,
                                 const double* brlen, const double* er, const double* pi, const double* alpha, int32_t R,
                                 const lh_codon_outputs* outs, void* hip_stream) {
+  const TreeBatch b{n, T, max_depth, ops, brlen, er, pi, alpha, R};
   const std::string W = "lh_eval_codons_batch_device";
   if (f && f->have_sampler && f->codon.frame < 0) return fail(W + ": lh_family_set_codons has not been called");
-  if (int rc = check_batch(f, W, n, T, R, max_depth, true)) return rc > 0;
+  if (int rc = check_batch(f, W, b, true)) return rc > 0;
   DeviceGuard guard(f);
   hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-  const lh_codon_outputs none{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  const lh_codon_outputs none{};
   const lh_codon_outputs& o = outs ? *outs : none;
   CodonWs& cw = f->codon;
   const lh::CodonTables& tab = cw.tab;
   const size_t FS = f->host.forward_size, NW = (size_t)tab.n_window * 125, NG = tab.n_genes;
-  auto own = [](double*& p, DevBuf& b, size_t bytes) {
-    if (!p && b.ensure(bytes)) return 1;
-    if (!p) p = b.get<double>();
-    return 0;
-  };
-  double *ll = o.loglik, *win = o.windows, *gen = o.genes, *w = nullptr, *stats = o.weight_stats, *pw = nullptr, *pg = nullptr;
+  double *ll = o.loglik, *win = o.windows, *gen = o.genes, *pw = nullptr, *pg = nullptr;
+  WeightReduce wr;
   const bool reduce = o.weighted_windows || o.weighted_genes || o.weight_stats;
   const size_t slabs = lh::posterior_slabs(n);
   // the forward arrays stay in the handle's buffer: K9 only reads them
   if (f->forward_dev.ensure(sizeof(double) * FS * n) || own(ll, cw.loglik, sizeof(double) * n) ||
       own(win, cw.windows, sizeof(double) * NW * n) || own(gen, cw.genes, sizeof(double) * NG * n) ||
       cw.scratch.ensure(sizeof(double) * 4 * (size_t)tab.max_vec * lh::codon_slots(n)) ||
-      (reduce && (own(w, cw.weights, sizeof(double) * n) || own(stats, cw.stats, sizeof(double) * 3) ||
+      (reduce && (wr.prepare(n, cw.weights, cw.stats, o.weight_stats) ||
                   (o.weighted_windows && own(pw, cw.partial_w, sizeof(double) * NW * slabs)) ||
                   (o.weighted_genes && own(pg, cw.partial_g, sizeof(double) * NG * slabs)))))
     return 1;
   double* fwd = f->forward_dev.get<double>();
   lh_eval_outputs eo{nullptr, nullptr, fwd, nullptr};
-  if (lh_eval_batch_device(f, n, T, max_depth, ops, brlen, er, pi, alpha, R, ll, &eo, hip_stream)) return 1;
+  if (eval_device(f, b, ll, &eo, hip_stream)) return 1;
   if (f->profile && f->codon_timer.begin(stream)) return 1;
   lh::launch_codons(f->sampler_dev, tab, n, fwd, FS, ll, cw.scratch.get<double>(), win, gen, stream);
   if (reduce) {
-    lh::launch_posterior_reduce(n, 0, nullptr, ll, o.log_offset, w, nullptr, nullptr, stats, stream);
-    if (o.weighted_windows) lh::launch_weighted_slabs(n, NW, win, w, pw, o.weighted_windows, stream);
-    if (o.weighted_genes) lh::launch_weighted_slabs(n, NG, gen, w, pg, o.weighted_genes, stream);
+    wr.launch(n, ll, o.log_offset, stream);
+    if (o.weighted_windows) lh::launch_weighted_slabs(n, NW, win, wr.w, pw, o.weighted_windows, stream);
+    if (o.weighted_genes) lh::launch_weighted_slabs(n, NG, gen, wr.w, pg, o.weighted_genes, stream);
   }
   if (f->profile && f->codon_timer.end(stream)) return 1;
   LH_HIP(hipGetLastError());
@@ -2881,51 +2890,40 @@ int lh_eval_codons_batch_device(lh_family* f, int32_t n, int32_t T, int32_t max_
 int lh_eval_codons_batch(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops, const double* brlen,
                          const double* er, const double* pi, const double* alpha, int32_t R, const lh_codon_outputs* outs) {
   const std::string W = "lh_eval_codons_batch";
+  const TreeBatch host{n, T, max_depth, ops, brlen, er, pi, alpha, R};
   if (f && f->have_sampler && f->codon.frame < 0) return fail(W + ": lh_family_set_codons has not been called");
-  if (int rc = check_batch(f, W, n, T, R, max_depth, true)) return rc > 0;
+  if (int rc = check_batch(f, W, host, true)) return rc > 0;
   DeviceGuard guard(f);
-  if (!ops || !brlen || !er || !pi || !alpha) return fail(W + ": null array");
-  const lh_codon_outputs none{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  if (!host.has_arrays()) return fail(W + ": null array");
+  const lh_codon_outputs none{};
   const lh_codon_outputs& o = outs ? *outs : none;
   if (!o.loglik && !o.windows && !o.genes && !o.weighted_windows && !o.weighted_genes && !o.weight_stats) return 0;
   CodonWs& cw = f->codon;
-  const size_t nodes = 2 * (size_t)T - 2, n_ops = (size_t)T - 2;
   const size_t NW = (size_t)cw.tab.n_window * 125, NG = cw.tab.n_genes;
-  HostInputs& in = f->in;
   HostOutputs& out = f->out;
-  lh_codon_outputs dev{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  if (out.loglik.ensure(sizeof(double) * n) || out_buf(o.windows, cw.windows, sizeof(double) * NW * n, &dev.windows) ||
-      out_buf(o.genes, cw.genes, sizeof(double) * NG * n, &dev.genes) ||
-      out_buf(o.weighted_windows, cw.out_wsum, sizeof(double) * NW, &dev.weighted_windows) ||
-      out_buf(o.weighted_genes, cw.out_gsum, sizeof(double) * NG, &dev.weighted_genes) ||
-      out_buf(o.weight_stats, out.weight_stats, sizeof(double) * 3, &dev.weight_stats) ||
-      stage_inputs(f, {{ops, sizeof(int32_t) * 4 * n_ops * n, &in.ops},
-                       {brlen, sizeof(double) * nodes * n, &in.brlen},
-                       {er, sizeof(double) * 6 * n, &in.er},
-                       {pi, sizeof(double) * 4 * n, &in.pi},
-                       {alpha, sizeof(double) * n, &in.alpha},
-                       {o.log_offset, sizeof(double) * n, &in.log_offset}}))
+  lh_codon_outputs d{};
+  TreeBatch dev;
+  if (out.loglik.ensure(sizeof(double) * n) || out_buf(o.windows, cw.windows, sizeof(double) * NW * n, &d.windows) ||
+      out_buf(o.genes, cw.genes, sizeof(double) * NG * n, &d.genes) ||
+      out_buf(o.weighted_windows, cw.out_wsum, sizeof(double) * NW, &d.weighted_windows) ||
+      out_buf(o.weighted_genes, cw.out_gsum, sizeof(double) * NG, &d.weighted_genes) ||
+      out_buf(o.weight_stats, out.weight_stats, sizeof(double) * 3, &d.weight_stats) ||
+      stage_batch(f, host, {{o.log_offset, sizeof(double) * n, &f->in.log_offset}}, &dev))
     return 1;
-  dev.log_offset = o.log_offset ? in.log_offset.get<const double>() : nullptr;
-  dev.loglik = out.loglik.get<double>();
-  if (lh_eval_codons_batch_device(f, n, T, max_depth, in.ops.get<const int32_t>(), in.brlen.get<const double>(),
-                                  in.er.get<const double>(), in.pi.get<const double>(), in.alpha.get<const double>(), R, &dev,
-                                  nullptr))
-    return 1;
-  if (!valid_schedules(ops, (size_t)n, T, (int)nodes, max_depth)) return refuse_schedules(f, "lh_eval_codons_batch");
-  return copy_back(f, "lh_eval_codons_batch",
-                   {{o.loglik, dev.loglik, sizeof(double) * n},
-                    {o.windows, dev.windows, sizeof(double) * NW * n},
-                    {o.genes, dev.genes, sizeof(double) * NG * n},
-                    {o.weighted_windows, dev.weighted_windows, sizeof(double) * NW},
-                    {o.weighted_genes, dev.weighted_genes, sizeof(double) * NG},
-                    {o.weight_stats, dev.weight_stats, sizeof(double) * 3}});
+  d.log_offset = o.log_offset ? f->in.log_offset.get<const double>() : nullptr;
+  d.loglik = out.loglik.get<double>();
+  if (lh_eval_codons_batch_device(f, n, T, max_depth, dev.ops, dev.brlen, dev.er, dev.pi, dev.model, R, &d, nullptr)) return 1;
+  return finish_batch(f, W.c_str(), host,
+                      {{o.loglik, d.loglik, sizeof(double) * n},
+                       {o.windows, d.windows, sizeof(double) * NW * n},
+                       {o.genes, d.genes, sizeof(double) * NG * n},
+                       {o.weighted_windows, d.weighted_windows, sizeof(double) * NW},
+                       {o.weighted_genes, d.weighted_genes, sizeof(double) * NG},
+                       {o.weight_stats, d.weight_stats, sizeof(double) * 3}});
 }
 
 int lh_codon_profile_read(lh_family* f, double* ms, int64_t* n_launches) {
-  if (!f) return fail("null family");
-  DeviceGuard guard(f);
-  return f->codon_timer.read(ms, n_launches);
+  return profile_read(f, &lh_family::codon_timer, ms, n_launches);
 }
 
 }  // extern "C"

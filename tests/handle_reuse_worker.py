@@ -2,10 +2,14 @@
 entry points take torch tensors, and torch brings its own HIP runtime, which has to come up first).
 
 One family handle, with profiling on, runs every entry point of the C ABI in turn -- lh_eval_batch (all four outputs),
-lh_forward_batch, lh_eval_sample_batch, lh_eval_posterior_batch (all outputs), lh_asr_batch, then the _device forms --
-for batch sizes that grow and then shrink.  Every result is compared with the same call on a fresh handle, and every
-profile counter is read after each call and once more.  Prints one JSON line: the mismatches and the profile readings
-that were not what the call implies (both lists empty when all is well)."""
+lh_forward_batch, lh_eval_sample_batch, lh_eval_viterbi_batch, lh_viterbi_forward_batch, lh_eval_draw_batch,
+lh_eval_posterior_batch (all outputs), lh_family_set_codons + lh_eval_codons_batch, lh_family_set_candidates +
+lh_eval_candidates_batch, lh_asr_batch, lh_lineage_batch, lh_eval_lineage_batch, then the _device forms -- for batch
+sizes that grow and then shrink.  Within a size, neighbours share a buffer of the handle: K4, K8 and the draws
+out.states, K5, K9 and K6 the forward arrays, the weights and log_offset, the ancestral draws, the lineages and the
+chain out.anc.  Every result is compared with the same call on a fresh handle, and every profile counter is read after
+each call and once more.  Prints one JSON line: the mismatches and the profile readings that were not what the call
+implies (both lists empty when all is well)."""
 import ctypes as C
 import json
 import os
@@ -24,7 +28,9 @@ def main():
     import numpy as np
     import torch
     from linearham_amd import host
-    from linearham_amd.capi import _EvalOutputs, _PosteriorOutputs, load_library
+    from linearham_amd.capi import (Family, _CandidateOutputs, _CodonOutputsDevice, _EvalOutputs, _PosteriorOutputs,
+                                    load_library)
+    from oracle import linearham_oracle as orc
     from tools import synth_family as sf
     dev = torch.device("cuda", 0)
     torch.zeros(1, device=dev)
@@ -53,6 +59,23 @@ def main():
     naive = rng.integers(0, 5, size=(N, L)).astype(np.uint8)
     log_offset = rng.normal(-50.0, 5.0, size=N)
     asr_rates = np.ascontiguousarray(np.tile([0.3, 0.7, 1.2, 1.8], (N, 1)))
+    # the lineage path of the last tip of every tree (as tests/batch_boundaries_worker.py's Fam builds it)
+    labels = list(orc.PhyloHMM(yaml_path, 0, pdir, 0).xmsa_labels)
+    chains = []
+    for i, s in enumerate(sf.read_trees_tsv(tsv)[:N]):
+        children, root, _ = host.newick_arrays(s["tree"], labels)
+        assert np.array_equal(hip.schedule_tree(T, children, root)[0], fl["ops"][i])  # flatten_tsv's node numbers
+        parent = {}
+        for v in range(T, 2 * T - 2):
+            parent[int(children[2 * (v - T)])] = parent[int(children[2 * (v - T) + 1])] = v
+        chains.append([parent[T - 1]])
+        while chains[-1][-1] != root:
+            chains[-1].append(parent[chains[-1][-1]])
+    PL = max(len(c) for c in chains)
+    path = np.full((N, PL), -1, dtype=np.int32)
+    for i, c in enumerate(chains):
+        path[i, :len(c)] = c
+    DRAWS, K = 2, 5
     p = lambda a, t: a.ctypes.data_as(C.POINTER(t))
     d = lambda a: C.c_void_p(a.data_ptr())
     P = lambda a: C.cast(d(a), C.POINTER(C.c_double))
@@ -105,6 +128,37 @@ def main():
                                    p(anc, C.c_uint8), p(choice, C.c_uint8)))
         return [anc, choice]
 
+    def viterbi_batch(f, n):
+        keys = ("loglik", "states", "log_path", "weight_stats")
+        res = hip.eval_viterbi_batch(f.value, T, depth, *inputs(n), R, log_offset=log_offset[:n], want=keys)
+        return [res[k] for k in keys]
+
+    def viterbi_forward(f, n):
+        return list(hip.viterbi_forward_batch(f.value, emissions[n]))
+
+    def draw_batch(f, n):
+        ll, hsh, st = hip.eval_draw_batch(f.value, T, depth, *inputs(n), R, words[:n], want_states=True)
+        return [ll, hsh, st, hip.draws_rows_read(f.value, np.arange(n))]
+
+    def codons_batch(f, n):
+        hip.set_codons(f.value, 0)
+        res = hip.eval_codons_batch(f.value, T, depth, *inputs(n), R, log_offset=log_offset[:n])
+        return [res[k] for k in ("loglik", "windows", "genes", "weighted_windows", "weighted_genes", "weight_stats")]
+
+    def candidates_batch(f, n):
+        prior = hip.set_candidates(f.value, cands)
+        res = hip.eval_candidates_batch(f.value, T, depth, *inputs(n), R, log_offset=log_offset[:n])
+        return [prior] + [res[k] for k in ("loglik", "log_cand", "weighted_sum", "weight_stats")]
+
+    def lineage_batch(f, n):
+        ops, brlen, er, pi, _ = inputs(n)
+        return list(Family.borrow(f.value, hip).lineage_batch(T, depth, ops, brlen, er, pi, asr_rates[:n], naive[:n], 17,
+                                                              path[:n], 3))
+
+    def lineage_eval_batch(f, n):
+        res = Family.borrow(f.value, hip).eval_lineage_batch(T, depth, *inputs(n), R, words[:n], 17, path[:n], DRAWS, 3)
+        return [res[k] for k in sorted(res)]
+
     def zeros(*shape, dtype=torch.float64):
         return torch.zeros(shape, dtype=dtype, device=dev)
 
@@ -142,12 +196,85 @@ def main():
         torch.cuda.synchronize()
         return [t.cpu().numpy() for t in (anc, choice)]
 
-    # entry point -> (call, launch groups it records in lh_profile_read / lh_asr_profile_read / lh_posterior_profile_read)
-    calls = [("lh_eval_batch", eval_batch, (1, 0, 0)), ("lh_forward_batch", forward_batch, (0, 0, 0)),
-             ("lh_eval_sample_batch", sample_batch, (1, 0, 0)), ("lh_eval_posterior_batch", posterior_batch, (1, 0, 1)),
-             ("lh_asr_batch", asr_batch, (0, 1, 0)), ("lh_eval_batch_device", eval_device, (1, 0, 0)),
-             ("lh_eval_sample_batch_device", sample_device, (1, 0, 0)),
-             ("lh_eval_posterior_batch_device", posterior_device, (1, 0, 1)), ("lh_asr_batch_device", asr_device, (0, 1, 0))]
+    def log_offset_device(n):
+        return torch.from_numpy(np.ascontiguousarray(log_offset[:n])).to(dev)
+
+    def words_device(n):
+        return torch.from_numpy(np.ascontiguousarray(words[:n]).view(np.int32)).to(dev)
+
+    def viterbi_device(f, n):
+        ptrs, _keep = dev_inputs(n)
+        lo = log_offset_device(n)
+        out = dict(loglik=zeros(n), states=zeros(n, NS, dtype=torch.int32), log_path=zeros(n), weight_stats=zeros(3))
+        hip.eval_viterbi_batch_device(f.value, n, T, depth, *ptrs, R,
+                                      dict({k: v.data_ptr() for k, v in out.items()}, log_offset=lo.data_ptr()), stream)
+        torch.cuda.synchronize()
+        return [t.cpu().numpy() for t in out.values()]
+
+    def draw_device(f, n):
+        ptrs, _keep = dev_inputs(n)
+        w = words_device(n)
+        ll, hsh, st = zeros(n), zeros(n, dtype=torch.int64), zeros(n, NS, dtype=torch.int32)
+        hip.check(lib.lh_eval_draw_batch_device(f, n, T, depth, *ptrs, R, d(w), d(ll), d(hsh), d(st), stream))
+        torch.cuda.synchronize()
+        return [ll.cpu().numpy(), hsh.cpu().numpy().view(np.uint64), st.cpu().numpy(),
+                hip.draws_rows_read(f.value, np.arange(n))]
+
+    def codons_device(f, n):
+        lay = hip.set_codons(f.value, 0)
+        nw, ng = len(lay["window_codon"]), lay["n_genes"]
+        ptrs, _keep = dev_inputs(n)
+        lo = log_offset_device(n)
+        out = [zeros(n), zeros(n, nw, 125), zeros(n, ng), zeros(nw, 125), zeros(ng), zeros(3)]
+        outs = _CodonOutputsDevice(lo.data_ptr(), *[t.data_ptr() for t in out])
+        hip.check(lib.lh_eval_codons_batch_device(f, n, T, depth, *ptrs, R, C.byref(outs), stream))
+        torch.cuda.synchronize()
+        return [t.cpu().numpy() for t in out]
+
+    def candidates_device(f, n):
+        prior = hip.set_candidates(f.value, cands)
+        ptrs, _keep = dev_inputs(n)
+        lo = log_offset_device(n)
+        out = [zeros(n), zeros(n, K), zeros(K), zeros(3)]
+        outs = _CandidateOutputs(P(lo), *[P(t) for t in out])
+        hip.check(lib.lh_eval_candidates_batch_device(f, n, T, depth, *ptrs, R, C.byref(outs), stream))
+        torch.cuda.synchronize()
+        return [prior] + [t.cpu().numpy() for t in out]
+
+    def lineage_eval_device(f, n):
+        _ptrs, ts = dev_inputs(n)
+        w, pth = words_device(n), torch.from_numpy(np.ascontiguousarray(path[:n])).to(dev)
+        u64 = lambda *shape: zeros(*shape, dtype=torch.int64)
+        out = dict(aa_hash=u64(n, DRAWS, PL + 1), loglik=zeros(n), naive=zeros(n, L, dtype=torch.uint8), naive_hash=u64(n),
+                   nt_hash=u64(n, DRAWS, PL + 1), rates=zeros(n, R), states=zeros(n, NS, dtype=torch.int32))
+        Family.borrow(f.value, hip).eval_lineage_batch_device(
+            n, T, depth, *[t.data_ptr() for t in ts], R, w.data_ptr(), 17, 3, DRAWS, pth.data_ptr(), PL,
+            {k: v.data_ptr() for k, v in out.items()}, stream)
+        torch.cuda.synchronize()
+        return [v.cpu().numpy().view(np.uint64) if v.dtype == torch.int64 else v.cpu().numpy() for v in out.values()]
+
+    # entry point -> (call, launch groups it records in each of READERS' counters)
+    READERS = ("eval", "asr", "posterior", "candidates", "collect", "lineage", "lineage_eval", "viterbi", "codon")
+    calls = [("lh_eval_batch", eval_batch, {"eval": 1}), ("lh_forward_batch", forward_batch, {}),
+             ("lh_eval_sample_batch", sample_batch, {"eval": 1}),
+             ("lh_eval_viterbi_batch", viterbi_batch, {"eval": 1, "viterbi": 1}),
+             ("lh_viterbi_forward_batch", viterbi_forward, {}),
+             ("lh_eval_draw_batch", draw_batch, {"eval": 1, "collect": 1}),
+             ("lh_eval_posterior_batch", posterior_batch, {"eval": 1, "posterior": 1}),
+             ("lh_eval_codons_batch", codons_batch, {"eval": 1, "codon": 1}),
+             ("lh_eval_candidates_batch", candidates_batch, {"eval": 1, "candidates": 1}),
+             ("lh_asr_batch", asr_batch, {"asr": 1}), ("lh_lineage_batch", lineage_batch, {"asr": 1, "lineage": 1}),
+             ("lh_eval_lineage_batch", lineage_eval_batch, {"lineage_eval": 1}),
+             ("lh_eval_sample_batch after the chain", sample_batch, {"eval": 1}),
+             ("lh_eval_batch_device", eval_device, {"eval": 1}), ("lh_eval_sample_batch_device", sample_device, {"eval": 1}),
+             ("lh_eval_viterbi_batch_device", viterbi_device, {"eval": 1, "viterbi": 1}),
+             ("lh_eval_draw_batch_device", draw_device, {"eval": 1, "collect": 1}),
+             ("lh_eval_posterior_batch_device", posterior_device, {"eval": 1, "posterior": 1}),
+             ("lh_eval_codons_batch_device", codons_device, {"eval": 1, "codon": 1}),
+             ("lh_eval_candidates_batch_device", candidates_device, {"eval": 1, "candidates": 1}),
+             ("lh_asr_batch_device", asr_device, {"asr": 1}),
+             ("lh_eval_lineage_batch_device", lineage_eval_device, {"lineage_eval": 1})]
+    calls = [(name, call, tuple(groups.get(r, 0) for r in READERS)) for name, call, groups in calls]
 
     def profile():
         ms, k = [C.c_double() for _ in range(3)], C.c_int64()
@@ -155,7 +282,19 @@ def main():
         a_ms, a_k, p_ms, p_k = C.c_double(), C.c_int64(), C.c_double(), C.c_int64()
         hip.check(lib.lh_asr_profile_read(fam, C.byref(a_ms), C.byref(a_k)))
         hip.check(lib.lh_posterior_profile_read(fam, C.byref(p_ms), C.byref(p_k)))
-        return [(k.value, [x.value for x in ms]), (a_k.value, [a_ms.value]), (p_k.value, [p_ms.value])]
+        chain_ms, chain_k = Family.borrow(fam.value, hip).lineage_eval_profile_read()
+        rest = [hip.candidates_profile_read(fam.value), hip.collect_profile_read(fam.value),
+                Family.borrow(fam.value, hip).lineage_profile_read(), tuple(chain_ms.values()) + (chain_k,),
+                hip.viterbi_profile_read(fam.value), hip.codon_profile_read(fam.value)]
+        return [(k.value, [x.value for x in ms]), (a_k.value, [a_ms.value]), (p_k.value, [p_ms.value])] + \
+            [(r[-1], list(r[:-1])) for r in rest]
+
+    # K6's candidates: five distinct naive sequences the family itself draws (on a handle of their own)
+    cand_h, cand_fl = handle()
+    cand_f = C.c_void_p(cand_fl["family"])
+    cands = np.unique(hip.naive_sequences(cand_f.value, sample_batch(cand_f, N)[2])[0], axis=0)[:K]
+    cand_h.close()
+    assert cands.shape == (K, L)
 
     hip.check(lib.lh_profile_enable(fam, 1))
     emissions = {}
@@ -165,10 +304,10 @@ def main():
         profile()
         for name, call, groups in calls:
             got = call(fam, n)
-            for (k, ms), want_k, reader in zip(profile(), groups, ("eval", "asr", "posterior")):
+            for (k, ms), want_k, reader in zip(profile(), groups, READERS):
                 if k != want_k or (k > 0 and not (sum(ms) > 0 and min(ms) >= 0)) or (k == 0 and any(ms)):
                     bad_profile.append([name, n, reader, k, ms])
-            for (k, ms), reader in zip(profile(), ("eval", "asr", "posterior")):
+            for (k, ms), reader in zip(profile(), READERS):
                 if k != 0 or any(ms):
                     bad_profile.append([name, n, reader + " (second read)", k, ms])
             fresh_h, fresh_fl = handle()

@@ -354,15 +354,15 @@ def test_extended_range_overflow_row(tmp_path):
 
 
 def test_one_handle_through_every_entry_point():
-    """One family handle, profiling on, through lh_eval_batch (all outputs), lh_forward_batch, lh_eval_sample_batch,
-    lh_eval_posterior_batch (all outputs), lh_asr_batch and the _device forms, in turn, for batch sizes that grow and then
-    shrink: every result is bit-identical to the same call on a fresh handle, and every *_profile_read reports the launch
-    groups of the call just made with a positive time, then zero (tests/handle_reuse_worker.py, its own process)."""
+    """One family handle, profiling on, through every batched entry point -- the evaluation, the forward sweep, K3 to K9,
+    the lineages and the chain, and their _device forms -- in turn, neighbours sharing a buffer, for batch sizes that grow
+    and then shrink: every result is bit-identical to the same call on a fresh handle, and every *_profile_read reports the
+    launch groups of the call just made with a positive time, then zero (tests/handle_reuse_worker.py, its own process)."""
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "tests", "handle_reuse_worker.py")], capture_output=True,
                        text=True, timeout=600, cwd=root)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     res = json.loads(r.stdout.strip().splitlines()[-1])
-    assert res["calls"] == 45
+    assert res["calls"] == 110
     assert res["mismatches"] == []
     assert res["bad_profile"] == []
