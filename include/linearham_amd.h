@@ -621,6 +621,65 @@ int lh_eval_codons_batch_device(lh_family* fam, int32_t n, int32_t n_tips, int32
  * (HIP events on the launch stream); resets the counters. */
 int lh_codon_profile_read(lh_family* fam, double* ms, int64_t* n_launches);
 
+/* ---- K10: exact posteriors of the recombination events (deletion and insertion lengths) ----
+ * Every state path of non-zero probability reads  left germline* NTI* right germline*  on a junction's W rows (the rows
+ * of lh_forward_layout).  For a path let  a = the number of junction rows its left gene l occupies (0 .. W)  and
+ * b = the first row that holds a germline state of its right gene r (W: none);  a <= b, and b - a is the insertion's
+ * length.  Per tree sample and junction K10 writes three tables, each summing to 1:
+ *   exit [nL][W+1]   P(l, a | data, tree)
+ *   enter[nR][W+1]   P(r, b | data, tree)
+ *   span [W+1][W+1]  P(a, b | data, tree): zero below the diagonal; its row and column sums are the gene sums of exit and
+ *                    enter; its k-th diagonal sums to P(insertion length = k)
+ * as one flat row of lh_events_size doubles: the V-D junction's  exit | enter | span,  then (heavy chains) the D-J
+ * junction's.  exit and enter are differences of K5's posteriors; span comes from a backward chain through K5's
+ * conditional steps.  Only ratios inside one forward row appear: the results do not depend on the range mode.
+ *
+ * lh_events_layout: per junction j < *n_junctions (1 or 2) the arrays receive rows[j] = W, n_left[j], n_right[j] and
+ * the offsets of its three tables in the row; *size the row's length, *n_genes = nV + nD + nJ.  Every array holds two
+ * entries; any pointer may be NULL.  Needs lh_family_set_sampler. */
+int lh_events_layout(const lh_family* fam, int32_t* n_junctions, int32_t* rows, int32_t* n_left, int32_t* n_right,
+                     int64_t* exit_off, int64_t* enter_off, int64_t* span_off, int64_t* size, int32_t* n_genes);
+
+/* Every member may be NULL.  log_offset is an input, as in lh_posterior_outputs.
+ *   loglik          [n]
+ *   events          [n][size]     the tables; NaN for a sample whose loglik is not finite (an overflowed row in the active
+ *                                 mode, or a rejected schedule)
+ *   genes           [n][n_genes]  V | D | J gene posteriors (K5's); NaN likewise
+ *   weighted_events [size]        sum_i w_i events_i, in a fixed order; samples with w_i = 0 are left out
+ *   weighted_genes  [n_genes]     sum_i w_i genes_i
+ *   weight_stats    [3]           max lw, sum w_i, sum w_i^2, as lh_eval_posterior_batch's for the same rows
+ * Batches combine exactly: rescale each one's sums by exp(max_b - max). */
+typedef struct {
+  const double* log_offset;
+  double* loglik;
+  double* events;
+  double* genes;
+  double* weighted_events;
+  double* weighted_genes;
+  double* weight_stats;
+} lh_events_outputs;
+
+/* lh_eval_batch followed by K5 (on a copy of the forward arrays) and K10.  Host pointers; a malformed schedule fails the
+ * call as in lh_eval_posterior_batch. */
+int lh_eval_events_batch(lh_family* fam, int32_t n, int32_t n_tips, int32_t max_depth, const int32_t* ops,
+                         const double* brlen, const double* er, const double* pi, const double* alpha,
+                         int32_t num_rates, const lh_events_outputs* outs);
+
+/* The same with every array (outs' members included) resident on the handle's device; enqueued on `hip_stream` without
+ * synchronising.  A schedule K0c rejects gives that sample NaN, leaves it out of the weighted sums and raises the
+ * handle's error word (lh_family_status). */
+int lh_eval_events_batch_device(lh_family* fam, int32_t n, int32_t n_tips, int32_t max_depth, const int32_t* ops,
+                                const double* brlen, const double* er, const double* pi, const double* alpha,
+                                int32_t num_rates, const lh_events_outputs* outs, void* hip_stream);
+
+/* K10 on caller-supplied emissions em[n][n_xmsa] (lh_forward_batch's), without a tree: loglik[n] and events[n][size]
+ * (either may be NULL).  The twin of lh_viterbi_forward_batch. */
+int lh_events_forward_batch(lh_family* fam, int32_t n, const double* em, double* loglik, double* events);
+
+/* Times of K5's pass and of K10 (with the reduction) over the lh_eval_events_batch[_device] calls made while profiling
+ * was enabled: ms[2] = smoothing, events; resets the counters. */
+int lh_events_profile_read(lh_family* fam, double* ms, int64_t* n_launches);
+
 #ifdef __cplusplus
 }
 #endif

@@ -73,6 +73,10 @@ EXPORTS += VITERBI_EXPORTS
 CODON_EXPORTS = ["lh_family_set_codons", "lh_codon_layout", "lh_eval_codons_batch", "lh_eval_codons_batch_device",
                  "lh_codon_profile_read"]
 EXPORTS += CODON_EXPORTS
+# K10 (exact posteriors of the recombination events: deletion and insertion lengths)
+EVENTS_EXPORTS = ["lh_events_layout", "lh_eval_events_batch", "lh_eval_events_batch_device", "lh_events_forward_batch",
+                  "lh_events_profile_read"]
+EXPORTS += EVENTS_EXPORTS
 
 
 class _CodonOutputs(C.Structure):
@@ -83,6 +87,16 @@ class _CodonOutputs(C.Structure):
 class _CodonOutputsDevice(C.Structure):  # the same members as device addresses
     _fields_ = [(k, C.c_void_p) for k in ("log_offset", "loglik", "windows", "genes", "weighted_windows",
                                           "weighted_genes", "weight_stats")]
+
+
+class _EventsOutputs(C.Structure):
+    _fields_ = [("log_offset", c_f64p), ("loglik", c_f64p), ("events", c_f64p), ("genes", c_f64p),
+                ("weighted_events", c_f64p), ("weighted_genes", c_f64p), ("weight_stats", c_f64p)]
+
+
+class _EventsOutputsDevice(C.Structure):  # the same members as device addresses
+    _fields_ = [(k, C.c_void_p) for k in ("log_offset", "loglik", "events", "genes", "weighted_events", "weighted_genes",
+                                          "weight_stats")]
 
 
 class _ViterbiOutputs(C.Structure):
@@ -228,6 +242,14 @@ class HipLibrary:
             lib.lh_eval_codons_batch.argtypes = _HOST_TREE + [C.POINTER(_CodonOutputs)]
             lib.lh_eval_codons_batch_device.argtypes = _DEV_TREE + [C.POINTER(_CodonOutputsDevice), C.c_void_p]
             lib.lh_codon_profile_read.argtypes = _PROFILE_READ
+        if hasattr(lib, "lh_events_layout"):
+            c_i64p = C.POINTER(C.c_int64)
+            lib.lh_events_layout.argtypes = [C.c_void_p, c_i32p, c_i32p, c_i32p, c_i32p, c_i64p, c_i64p, c_i64p, c_i64p,
+                                             c_i32p]
+            lib.lh_eval_events_batch.argtypes = _HOST_TREE + [C.POINTER(_EventsOutputs)]
+            lib.lh_eval_events_batch_device.argtypes = _DEV_TREE + [C.POINTER(_EventsOutputsDevice), C.c_void_p]
+            lib.lh_events_forward_batch.argtypes = [C.c_void_p, C.c_int32, c_f64p, c_f64p, c_f64p]
+            lib.lh_events_profile_read.argtypes = _PROFILE_READ
         if hasattr(lib, "lh_set_device"):      # (absent from round-2 builds loaded through LH_LIB_DIR for comparisons)
             lib.lh_set_device.argtypes = [C.c_int32]
             lib.lh_family_status.argtypes = [C.c_void_p]
@@ -296,6 +318,48 @@ class HipLibrary:
 
     def codon_profile_read(self, family):
         return self._profile_read("lh_codon_profile_read", family)
+
+    def events_layout(self, family):
+        """The layout of K10's flat row on a family handle that has sampler tables: dict(size, n_genes, junctions =
+        [dict(rows, n_left, n_right, exit, enter, span)]), the last three the offsets of exit [n_left][rows + 1],
+        enter [n_right][rows + 1] and span [rows + 1][rows + 1] in the row."""
+        h = _handle(family)
+        nj, ng, size = C.c_int32(), C.c_int32(), C.c_int64()
+        i32 = [(C.c_int32 * 2)() for _ in range(3)]
+        i64 = [(C.c_int64 * 2)() for _ in range(3)]
+        self.check(self.lib.lh_events_layout(h, C.byref(nj), *i32, *i64, C.byref(size), C.byref(ng)))
+        keys = ("rows", "n_left", "n_right", "exit", "enter", "span")
+        return dict(size=size.value, n_genes=ng.value,
+                    junctions=[dict(zip(keys, [int(a[j]) for a in i32 + i64])) for j in range(nj.value)])
+
+    def eval_events_batch(self, family, n_tips, max_depth, ops, brlen, er, pi, alpha, num_rates, log_offset=None,
+                          want=("loglik", "events", "genes", "weighted_events", "weighted_genes", "weight_stats")):
+        """K0-K2 + K5 + K10 on a family handle that has sampler tables.  Returns a dict with the members of `want`:
+        loglik [n], events [n, size], genes [n, n_genes], weighted_events [size], weighted_genes [n_genes],
+        weight_stats [3] (max lw, sum w, sum w^2 with lw = loglik - log_offset).  split_events() cuts a row up."""
+        h = _handle(family)
+        n, arrays = _tree_args(ops, brlen, er, pi, alpha)
+        lay = self.events_layout(h)
+        ne, ng = lay["size"], lay["n_genes"]
+        res, outs = _outputs(_EventsOutputs, want, log_offset, loglik=(n,), events=(n, ne), genes=(n, ng),
+                             weighted_events=(ne,), weighted_genes=(ng,), weight_stats=(3,))
+        self.check(self.lib.lh_eval_events_batch(h, n, n_tips, max_depth, *_tree_ptrs(arrays), num_rates, C.byref(outs)))
+        return res
+
+    def events_forward_batch(self, family, em):
+        """K2 + K5 + K10 on caller emissions em [n][C]: (loglik [n], events [n, size])."""
+        h = _handle(family)
+        em = _f64(em)
+        n = em.shape[0]
+        ll = np.zeros(n)
+        ev = np.zeros((n, self.events_layout(h)["size"]))
+        self.check(self.lib.lh_events_forward_batch(h, n, em.ctypes.data_as(c_f64p), ll.ctypes.data_as(c_f64p),
+                                                    ev.ctypes.data_as(c_f64p)))
+        return ll, ev
+
+    def events_profile_read(self, family):
+        """(ms of K5's pass on the copy, ms of K10 and its reduction, calls) since the last read."""
+        return self._profile_read("lh_events_profile_read", family, 2)
 
     def candidates_info(self, family):
         """(candidates registered on the handle, sites every candidate has): lh_candidates_info."""
@@ -519,6 +583,18 @@ def _n_rows(n, arrays, log_offset):
     """Whether ops is [n][T-2][4] and every other per-row array has n rows."""
     return arrays[0].ndim == 3 and all(a.shape[0] == n for a in arrays[1:]) and \
         (log_offset is None or np.asarray(log_offset).shape == (n,))
+
+
+def split_events(layout, row):
+    """[(exit, enter, span)] per junction: views of one flat K10 row under HipLibrary.events_layout's layout."""
+    row = np.asarray(row)
+    out = []
+    for j in layout["junctions"]:
+        W1 = j["rows"] + 1
+        out.append((row[j["exit"]:j["exit"] + j["n_left"] * W1].reshape(j["n_left"], W1),
+                    row[j["enter"]:j["enter"] + j["n_right"] * W1].reshape(j["n_right"], W1),
+                    row[j["span"]:j["span"] + W1 * W1].reshape(W1, W1)))
+    return out
 
 
 def _outputs(struct, want, log_offset=None, **shapes):

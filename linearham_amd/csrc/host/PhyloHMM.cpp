@@ -23,6 +23,7 @@
 #include <mutex>
 #include <sstream>
 #include <thread>
+#include <tuple>
 #include <unordered_map>
 
 namespace linearham {
@@ -2042,6 +2043,234 @@ void PhyloHMM::RunCodonMarginalsPipeline(const std::string& input_path, const st
   WriteAminoAcidTable(aa, res);
   summary << "key\tvalue\nrows_used\t" << (N - first - skipped) << "\nrows_skipped_nonfinite\t" << skipped << "\nkish_ess\t"
           << ReprDouble(acc.KishEss()) << "\nframe\t" << frame << "\n";
+}
+
+
+// ---- K10: posteriors of deletion and insertion lengths ----
+
+namespace {
+
+// one junction of the events row, as the host's state space describes it
+struct EventsJunctionView {
+  const RegionStates *J, *GL, *GR;
+  int site0, W;
+  const char *left_column, *right_column, *name;
+};
+
+std::string Fmt17(double v) {
+  char buf[64];
+  std::snprintf(buf, sizeof buf, "%.17g", v);
+  return buf;
+}
+
+std::vector<EventsJunctionView> EventsJunctions(const std::string& locus, const std::map<std::string, std::pair<int, int>>& fb,
+                                                const RegionStates& vgerm, const RegionStates& vd, const RegionStates& dgerm,
+                                                const RegionStates& dj, const RegionStates& jgerm) {
+  const int v0 = fb.at("v_r").first;
+  if (locus == "igh")
+    return {{&vd, &vgerm, &dgerm, v0, fb.at("d_l").second - v0, "V3pDel", "D5pDel", "VD"},
+            {&dj, &dgerm, &jgerm, fb.at("d_r").first, fb.at("j_l").second - fb.at("d_r").first, "D3pDel", "J5pDel", "DJ"}};
+  return {{&vd, &vgerm, &jgerm, v0, fb.at("j_l").second - v0, "V3pDel", "J5pDel", "VJ"}};
+}
+
+}  // namespace
+
+std::size_t PhyloHMM::EventsGenes() const {
+  return vgerm_.ggene_ranges.size() + (locus_ == "igh" ? dgerm_.ggene_ranges.size() : 0) + jgerm_.ggene_ranges.size();
+}
+
+std::size_t PhyloHMM::EventsSize() const {
+  std::size_t size = 0;
+  for (const EventsJunctionView& j : EventsJunctions(locus_, flexbounds_, vgerm_, vd_junction_, dgerm_, dj_junction_, jgerm_))
+    size += (j.GL->ggene_ranges.size() + j.GR->ggene_ranges.size() + (std::size_t)j.W + 1) * ((std::size_t)j.W + 1);
+  return size;
+}
+
+PhyloHMM::EventsResult PhyloHMM::MapEvents(const double* events, const double* genes) const {
+  // (column, gene, length) -> probability, in the order of the files: the columns as the annotation prints them, "*"
+  // (every gene) before the genes
+  static const char* const kColumns[] = {"V5pDel", "V3pDel", "D5pDel", "D3pDel", "J5pDel", "J3pDel"};
+  auto column_rank = [](const std::string& c) {
+    for (int k = 0; k < 6; ++k)
+      if (c == kColumns[k]) return k;
+    throw std::runtime_error("MapEvents: unknown column " + c);
+  };
+  std::map<std::tuple<int, std::string, int>, double> del;
+  auto add = [&](const std::string& column, const std::string& gene, int length, double p) {
+    if (!(p > 0.0)) return;  // (also leaves out a NaN)
+    del[{column_rank(column), gene, length}] += p;
+    del[{column_rank(column), "*", length}] += p;
+  };
+  auto state_index = [](const RegionStates& G) {
+    std::map<std::string, int> ix;
+    for (std::size_t k = 0; k < G.state_strs.size(); ++k) ix[G.state_strs[k]] = (int)k;
+    return ix;
+  };
+  EventsResult res;
+  const double* t = events;
+  for (const EventsJunctionView& j : EventsJunctions(locus_, flexbounds_, vgerm_, vd_junction_, dgerm_, dj_junction_, jgerm_)) {
+    const int W = j.W, W1 = W + 1;
+    const std::size_t nL = j.GL->ggene_ranges.size(), nR = j.GR->ggene_ranges.size();
+    const double *exit_t = t, *enter_t = exit_t + nL * W1, *span = enter_t + nR * W1;
+    t = span + (std::size_t)W1 * W1;
+    const std::map<std::string, int> ixL = state_index(*j.GL), ixR = state_index(*j.GR);
+    std::size_t l = 0;
+    for (const auto& kv : j.GL->ggene_ranges) {  // (a std::map: the genes by name, the compact layout's order)
+      const auto jr = j.J->ggene_ranges.find(kv.first);
+      const int rows = jr == j.J->ggene_ranges.end() ? 0 : jr->second.second - jr->second.first;
+      for (int a = 0; a <= W; ++a) {
+        const double p = exit_t[l * W1 + a];
+        if (!(p > 0.0)) continue;
+        if (a == 0) {
+          add(j.left_column, kv.first, j.GL->right_del[ixL.at(kv.first)], p);
+          continue;
+        }
+        Require(a <= rows, "MapEvents: weight on a junction row the left gene " + kv.first + " has no state on");
+        const int k = jr->second.first + (a - 1);
+        Require(j.J->site_inds[k] - j.site0 == a - 1, "MapEvents: the left gene's junction states are not on consecutive rows");
+        add(j.left_column, kv.first, j.J->del[k], p);
+      }
+      ++l;
+    }
+    std::size_t r = 0;
+    for (const auto& kv : j.GR->ggene_ranges) {
+      const auto jr = j.J->ggene_ranges.find(kv.first);
+      Require(jr != j.J->ggene_ranges.end(), "MapEvents: the right gene " + kv.first + " has no junction states");
+      const int g0 = jr->second.first + 4, g1 = jr->second.second;  // its germline states (after the four NTI states)
+      const int first = g0 < g1 ? j.J->site_inds[g0] - j.site0 : W;
+      for (int b = 0; b <= W; ++b) {
+        const double p = enter_t[r * W1 + b];
+        if (!(p > 0.0)) continue;
+        if (b == W) {
+          add(j.right_column, kv.first, j.GR->left_del[ixR.at(kv.first)], p);
+          continue;
+        }
+        Require(b >= first && g0 + (b - first) < g1, "MapEvents: weight on a junction row the right gene " + kv.first + " has no state on");
+        const int k = g0 + (b - first);
+        Require(j.J->site_inds[k] - j.site0 == b, "MapEvents: the right gene's junction states are not on consecutive rows");
+        add(j.right_column, kv.first, j.J->del[k], p);
+      }
+      ++r;
+    }
+    for (int k = 0; k <= W; ++k) {  // the k-th diagonal, from the top
+      double p = 0.0;
+      for (int a = 0; a + k <= W; ++a) p += span[(std::size_t)a * W1 + a + k];
+      if (p > 0.0) res.insertions.push_back({j.name, k, p});
+    }
+    for (int a = 0; a <= W; ++a)
+      for (int b = a; b <= W; ++b)
+        if (span[(std::size_t)a * W1 + b] > 0.0) res.spans.push_back({j.name, a, b, span[(std::size_t)a * W1 + b]});
+  }
+  // the outer ends are functions of the gene alone
+  {
+    std::size_t g = 0;
+    for (const auto& kv : vgerm_.ggene_ranges) add("V5pDel", kv.first, vgerm_.left_del[state_index(vgerm_).at(kv.first)], genes[g++]);
+    g = EventsGenes() - jgerm_.ggene_ranges.size();
+    for (const auto& kv : jgerm_.ggene_ranges) add("J3pDel", kv.first, jgerm_.right_del[state_index(jgerm_).at(kv.first)], genes[g++]);
+  }
+  for (const auto& kv : del)
+    res.deletions.push_back({kColumns[std::get<0>(kv.first)], std::get<1>(kv.first), std::get<2>(kv.first), kv.second});
+  return res;
+}
+
+PhyloHMM::EventsResult PhyloHMM::RearrangementEvents() {
+  Require(have_tree_, "InitializePhyloParameters must be called first");
+  CreateFamily();
+  Require(device_sampler_, "the family has no device sampler tables (needed by the events kernel)");
+  int64_t size = 0;
+  int32_t n_genes = 0;
+  CheckHip(lh_events_layout(family_, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &size, &n_genes),
+           "lh_events_layout");
+  Require((std::size_t)size == EventsSize() && (std::size_t)n_genes == EventsGenes(),
+          "the device's events layout differs from the host's state space");
+  const int T = tree_.n_tips;
+  std::vector<int32_t> ops((std::size_t)(T - 2) * 4);
+  int32_t depth = 0;
+  CheckHip(lh_schedule_tree(T, tree_.children.data(), tree_.root, ops.data(), &depth), "lh_schedule_tree");
+  std::vector<double> events((std::size_t)size), genes((std::size_t)n_genes);
+  double ll = 0;
+  lh_events_outputs outs{nullptr, &ll, events.data(), genes.data(), nullptr, nullptr, nullptr};
+  CheckHip(lh_eval_events_batch(family_, 1, T, depth, ops.data(), tree_.brlen.data(), er_.data(), pi_.data(), &alpha_,
+                                num_rates_, &outs),
+           "lh_eval_events_batch");
+  Require(std::isfinite(ll), "RearrangementEvents: the log-likelihood is not finite");
+  return MapEvents(events.data(), genes.data());
+}
+
+void PhyloHMM::WriteDeletionTable(std::ostream& o, const EventsResult& m) {
+  o << "column\tgene\tlength\tprobability\n";
+  for (const EventsResult::Deletion& d : m.deletions)
+    o << d.column << '\t' << d.gene << '\t' << d.length << '\t' << Fmt17(d.p) << '\n';
+}
+
+void PhyloHMM::WriteInsertionTable(std::ostream& o, const EventsResult& m) {
+  o << "junction\tlength\tprobability\n";
+  for (const EventsResult::Insertion& d : m.insertions) o << d.junction << '\t' << d.length << '\t' << Fmt17(d.p) << '\n';
+}
+
+void PhyloHMM::WriteSpanTable(std::ostream& o, const EventsResult& m) {
+  o << "junction\tleft_rows\tright_first\tprobability\n";
+  for (const EventsResult::Span& d : m.spans)
+    o << d.junction << '\t' << d.left_rows << '\t' << d.right_first << '\t' << Fmt17(d.p) << '\n';
+}
+
+void PhyloHMM::RunEventsPipeline(const std::string& input_path, const std::string& output_prefix, int num_rates,
+                                 double burnin_frac) {
+  Require(devices_.size() <= 1, "the events pipeline runs on one device: --devices may list only one");
+  Require(burnin_frac >= 0.0 && burnin_frac < 1.0, "burn-in fraction must be in [0, 1)");
+  CreateFamily();
+  Require(device_sampler_, "the family has no device sampler tables (needed by the events kernel)");
+  const std::size_t NE = EventsSize(), NG = EventsGenes();
+  {
+    int64_t size = 0;
+    int32_t n_genes = 0;
+    CheckHip(lh_events_layout(family_, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &size, &n_genes),
+             "lh_events_layout");
+    Require((std::size_t)size == NE && (std::size_t)n_genes == NG, "the device's events layout differs from the host's state space");
+  }
+  TsvTable table = TsvTable::OpenRevBayesTable(input_path);
+  const std::size_t N = table.rows.size();
+  const std::size_t first = (std::size_t)std::floor(burnin_frac * (double)N);
+  // the rows' tables come back whole: a batch is bounded by their size (at most 512 MiB of them)
+  const std::size_t fit = std::max<std::size_t>(1, ((std::size_t)512 << 20) / (sizeof(double) * (NE + NG)));
+  const std::size_t kBatch = host_options().pipeline_batch > 0 ? (std::size_t)host_options().pipeline_batch
+                                                                : std::min<std::size_t>(8192, fit);
+  WeightedSums acc(NE + NG);
+  std::vector<double> events, genes, row(NE + NG);
+  std::size_t skipped = 0;
+  for (std::size_t off = first; off < N; off += kBatch) {
+    const std::size_t m = std::min(kBatch, N - off);
+    TableBatch tb = FlattenTable(table, off, off + m, false, true, input_path);
+    const DeviceBatch& b = tb.dev;
+    std::vector<double> ll(m);
+    events.resize(m * NE);
+    genes.resize(m * NG);
+    lh_events_outputs outs{nullptr, ll.data(), events.data(), genes.data(), nullptr, nullptr, nullptr};
+    CheckHip(lh_eval_events_batch(family_, b.n, b.n_tips, b.max_depth, b.ops.data(), b.brlen.data(), b.er.data(),
+                                  b.pi.data(), b.alpha.data(), num_rates, &outs),
+             "lh_eval_events_batch");
+    for (std::size_t i = 0; i < m; ++i) {
+      const double st[3] = {ll[i] - tb.lik[i], 1.0, 1.0};  // one row, its weight relative to itself
+      if (!std::isfinite(st[0])) {
+        ++skipped;
+        continue;
+      }
+      std::copy(events.begin() + i * NE, events.begin() + (i + 1) * NE, row.begin());
+      std::copy(genes.begin() + i * NG, genes.begin() + (i + 1) * NG, row.begin() + NE);
+      acc.Add(row.data(), st);
+    }
+  }
+  Require(acc.s1 > 0.0, "events pipeline: no row with a finite weight");
+  acc.Normalise();
+  const EventsResult res = MapEvents(acc.total.data(), acc.total.data() + NE);
+  std::ofstream dels(output_prefix + ".deletions.tsv"), ins(output_prefix + ".insertions.tsv"),
+      spans(output_prefix + ".spans.tsv"), summary(output_prefix + ".summary.tsv");
+  Require(dels.good() && ins.good() && spans.good() && summary.good(), "Can't write " + output_prefix + ".*.tsv");
+  WriteDeletionTable(dels, res);
+  WriteInsertionTable(ins, res);
+  WriteSpanTable(spans, res);
+  summary << "key\tvalue\nrows_used\t" << (N - first - skipped) << "\nrows_skipped_nonfinite\t" << skipped << "\nkish_ess\t"
+          << Fmt17(acc.KishEss()) << "\n";
 }
 
 

@@ -163,6 +163,50 @@ class PhyloHMM : public HMM {
   static void WriteCodonTable(std::ostream& o, const CodonMarginalsResult& m);
   /// codon, aa, probability: the codon table folded with TranslateDna's table (its N-codon rule included)
   static void WriteAminoAcidTable(std::ostream& o, const CodonMarginalsResult& m);
+  /// The exact posteriors of the recombination events (K10, lh_eval_events_batch) in the units of the annotation columns.
+  /// deletions: P(column = length, gene) for V5pDel, V3pDel, D5pDel, D3pDel, J5pDel, J3pDel (light chains: no D columns),
+  /// the gene-summed rows under gene "*"; insertions: P(length) per junction ("VD", "DJ"; light chains "VJ"); spans:
+  /// P(rows the left gene occupies, first row of the right gene) per junction.  Entries above 0 only.
+  struct EventsResult {
+    struct Deletion {
+      std::string column, gene;
+      int length;
+      double p;
+    };
+    struct Insertion {
+      std::string junction;
+      int length;
+      double p;
+    };
+    struct Span {
+      std::string junction;
+      int left_rows, right_first;
+      double p;
+    };
+    std::vector<Deletion> deletions;
+    std::vector<Insertion> insertions;
+    std::vector<Span> spans;
+  };
+  /// The length of K10's flat row for this family (lh_events_layout's, derived from the state space alone) and the
+  /// number of gene posteriors nV + nD + nJ.
+  std::size_t EventsSize() const;
+  std::size_t EventsGenes() const;
+  /// Maps one flat row (per junction exit | enter | span) and the V | D | J gene posteriors to the columns' units.  The
+  /// deletion length comes from the members the sampler reads (SampleJunctionStates / SampleGermlineState): the junction
+  /// state's `del` on row a - 1 or row b, the germline region's right_del for a = 0 and left_del for b = W; V5pDel and
+  /// J3pDel are functions of the gene alone and are folded from the gene posteriors.  No device is needed.
+  EventsResult MapEvents(const double* events, const double* genes) const;
+  /// After InitializePhyloParameters: the tables of the current tree.
+  EventsResult RearrangementEvents();
+  /// The importance-weighted tables over a RevBayes table, with RunMarginalsPipeline's reader, burn-in, weights and Kish
+  /// ESS.  The rows' tables are added up on the host in row order, so the files do not depend on LH_PIPELINE_BATCH.
+  /// Writes <prefix>.deletions.tsv, .insertions.tsv, .spans.tsv and .summary.tsv.
+  void RunEventsPipeline(const std::string& input_path, const std::string& output_prefix, int num_rates, double burnin_frac);
+  /// column, gene, length, probability / junction, length, probability / junction, left_rows, right_first, probability;
+  /// numbers printed with %.17g
+  static void WriteDeletionTable(std::ostream& o, const EventsResult& m);
+  static void WriteInsertionTable(std::ostream& o, const EventsResult& m);
+  static void WriteSpanTable(std::ostream& o, const EventsResult& m);
   static void WriteSiteTable(std::ostream& o, const NaiveMarginalsResult& m);
   static void WriteGeneTable(std::ostream& o, const NaiveMarginalsResult& m);
   void SampleStatesWithWords(const uint32_t* words, int n_words, std::vector<int32_t>& device_states,

@@ -308,6 +308,43 @@ int lhh_run_codon_marginals_pipeline(void* h, const char* input_path, const char
   });
 }
 
+// The three tables of an EventsResult, separated by blank lines (WriteDeletionTable, WriteInsertionTable, WriteSpanTable).
+static const char* EventsText(const PhyloHMM::EventsResult& m) {
+  std::ostringstream o;
+  PhyloHMM::WriteDeletionTable(o, m);
+  o << "\n";
+  PhyloHMM::WriteInsertionTable(o, m);
+  o << "\n";
+  PhyloHMM::WriteSpanTable(o, m);
+  g_out = o.str();
+  return g_out.c_str();
+}
+
+// PhyloHMM::EventsSize / EventsGenes: the lengths MapEvents expects (no device).
+int lhh_phylo_events_sizes(void* h, int64_t* size, int* n_genes) {
+  return Guard([&] {
+    const PhyloHMM& p = dynamic_cast<PhyloHMM&>(*static_cast<HMM*>(h));
+    *size = (int64_t)p.EventsSize();
+    *n_genes = (int)p.EventsGenes();
+  });
+}
+
+// PhyloHMM::MapEvents on a caller's row events[EventsSize] and genes[EventsGenes] (no device): the tables' text in *text.
+int lhh_phylo_map_events(void* h, const double* events, const double* genes, const char** text) {
+  return Guard([&] { *text = EventsText(dynamic_cast<PhyloHMM&>(*static_cast<HMM*>(h)).MapEvents(events, genes)); });
+}
+
+// PhyloHMM::RearrangementEvents of the current tree: the tables' text in *text.
+int lhh_phylo_events(void* h, const char** text) {
+  return Guard([&] { *text = EventsText(dynamic_cast<PhyloHMM&>(*static_cast<HMM*>(h)).RearrangementEvents()); });
+}
+
+int lhh_run_events_pipeline(void* h, const char* input_path, const char* output_prefix, int num_rates, double burnin_frac) {
+  return Guard([&] {
+    dynamic_cast<PhyloHMM&>(*static_cast<HMM*>(h)).RunEventsPipeline(input_path, output_prefix, num_rates, burnin_frac);
+  });
+}
+
 // PhyloHMM::CandidatePosterior: seqs = K candidates of n_sites characters, back to back; log_post [K], log_prior [K]
 // (may be NULL), *loglik.
 int lhh_phylo_candidate_posterior(void* h, int K, const char* seqs, double* log_post, double* log_prior, double* loglik) {

@@ -7,7 +7,8 @@
 // --viterbi / --annotations-pipeline, the most probable annotation of one tree and the exact posterior probabilities of
 // annotations over a RevBayes table (write_lh_annotations.py's counting, without the sampling), and --codon-marginals /
 // --codon-marginals-pipeline, the exact codon and amino-acid distributions of the naive sequence (the logo
-// tabulate_naive_probs.py draws from sampled sequences).
+// tabulate_naive_probs.py draws from sampled sequences), and --events / --events-pipeline, the exact posteriors of the
+// deletion and insertion lengths (the annotation's event columns).
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -64,7 +65,7 @@ int main(int argc, char** argv) {
   try {
     if (argc < 2 || std::string(argv[1]) == "-h" || std::string(argv[1]) == "--help") {
       std::cout << "A Phylo-HMM implementation for B cell receptor sequence analysis.\n"
-                   "USAGE: linearham {--compute-logl|--sample|--pipeline|--asr|--marginals|--marginals-pipeline|--naive-probs|--naive-probs-pipeline|--lineage-pipeline|--weighted-lineage-pipeline|--viterbi|--annotations-pipeline|--codon-marginals|--codon-marginals-pipeline} --yaml-path <string> "
+                   "USAGE: linearham {--compute-logl|--sample|--pipeline|--asr|--marginals|--marginals-pipeline|--naive-probs|--naive-probs-pipeline|--lineage-pipeline|--weighted-lineage-pipeline|--viterbi|--annotations-pipeline|--codon-marginals|--codon-marginals-pipeline|--events|--events-pipeline} --yaml-path <string> "
                    "--cluster-ind <int> --hmm-param-dir <string> [--seed <int>] [--num-rates <int>] [--extended-range <0|1>] "
                    "[--devices <a,b,...>] ...\n"
                    "  --marginals: the arguments of --compute-logl; prints the per-site naive-base table and the gene table\n"
@@ -84,6 +85,10 @@ int main(int argc, char** argv) {
                    "    table of the naive sequence for that tree\n"
                    "  --codon-marginals-pipeline --input-path <RevBayes table> --output-path <prefix> [--burnin-frac <f>]\n"
                    "    [--frame <0|1|2>]: writes <prefix>.codons.tsv, <prefix>.aa.tsv and <prefix>.summary.tsv (one device)\n"
+                   "  --events: the arguments of --marginals; prints the exact posteriors of the deletion lengths (column, gene,\n"
+                   "    length), of the insertion lengths and of the junction spans for that tree\n"
+                   "  --events-pipeline --input-path <RevBayes table> --output-path <prefix> [--burnin-frac <f>]: writes\n"
+                   "    <prefix>.deletions.tsv, <prefix>.insertions.tsv, <prefix>.spans.tsv and <prefix>.summary.tsv (one device)\n"
                    "  --lineage-pipeline --input-path <--pipeline table> --output-path <prefix> --seed-seq <name> [--seed <int>]:\n"
                    "    the lineage tables of the sequence <name>: <prefix>.fasta, .dnamap, .nodes.tsv, .edges.tsv, .summary.tsv\n"
                    "       linearham --lineage-trees --input-path <--asr trees> --output-path <prefix> --seed-seq <name>\n"
@@ -111,7 +116,7 @@ int main(int argc, char** argv) {
         subcmd != "--marginals" && subcmd != "--marginals-pipeline" && subcmd != "--naive-probs" &&
         subcmd != "--naive-probs-pipeline" && subcmd != "--lineage-pipeline" && subcmd != "--weighted-lineage-pipeline" &&
         subcmd != "--viterbi" && subcmd != "--annotations-pipeline" && subcmd != "--codon-marginals" &&
-        subcmd != "--codon-marginals-pipeline")
+        subcmd != "--codon-marginals-pipeline" && subcmd != "--events" && subcmd != "--events-pipeline")
       throw std::invalid_argument("'" + subcmd + "' is not a valid subcommand.");
     const std::string yaml_path = a.one("yaml-path");
     const int cluster_ind = std::stoi(a.one("cluster-ind"));
@@ -131,7 +136,7 @@ int main(int argc, char** argv) {
       }
       if (device_list.size() > 1 && (subcmd == "--marginals-pipeline" || subcmd == "--naive-probs-pipeline" ||
                                      subcmd == "--weighted-lineage-pipeline" || subcmd == "--annotations-pipeline" ||
-                                     subcmd == "--codon-marginals-pipeline"))
+                                     subcmd == "--codon-marginals-pipeline" || subcmd == "--events-pipeline"))
         throw std::invalid_argument(subcmd + " runs on one device: --devices may list only one");
       if (device_list.size() > 1 && subcmd != "--pipeline")
         std::fprintf(stderr, "linearham: %s evaluates on one device; of --devices only device %d is used\n", subcmd.c_str(),
@@ -175,6 +180,10 @@ int main(int argc, char** argv) {
     if (subcmd == "--codon-marginals-pipeline") {
       phylo_hmm_ptr->RunCodonMarginalsPipeline(a.one("input-path"), a.one("output-path"), num_rates,
                                                std::stod(a.opt("burnin-frac", "0")), std::stoi(a.opt("frame", "0")));
+      return EXIT_SUCCESS;
+    }
+    if (subcmd == "--events-pipeline") {
+      phylo_hmm_ptr->RunEventsPipeline(a.one("input-path"), a.one("output-path"), num_rates, std::stod(a.opt("burnin-frac", "0")));
       return EXIT_SUCCESS;
     }
     if (subcmd == "--naive-probs-pipeline") {
@@ -228,6 +237,13 @@ int main(int argc, char** argv) {
       linearham::PhyloHMM::WriteCodonTable(std::cout, m);
       std::cout << "\n";
       linearham::PhyloHMM::WriteAminoAcidTable(std::cout, m);
+    } else if (subcmd == "--events") {
+      const linearham::PhyloHMM::EventsResult m = phylo_hmm_ptr->RearrangementEvents();
+      linearham::PhyloHMM::WriteDeletionTable(std::cout, m);
+      std::cout << "\n";
+      linearham::PhyloHMM::WriteInsertionTable(std::cout, m);
+      std::cout << "\n";
+      linearham::PhyloHMM::WriteSpanTable(std::cout, m);
     } else if (subcmd == "--marginals") {
       const linearham::PhyloHMM::NaiveMarginalsResult m = phylo_hmm_ptr->NaiveMarginals();
       linearham::PhyloHMM::WriteSiteTable(std::cout, m);

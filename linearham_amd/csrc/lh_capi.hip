@@ -35,6 +35,7 @@ const DebugOptions& debug_options() {
     o.k1_seg_waves = num("LH_K1_SEG_WAVES", o.k1_seg_waves);
     o.k1_no_fuse = set("LH_K1_NO_FUSE");
     o.codon_blocks = std::max(1, num("LH_CODON_BLOCKS", o.codon_blocks));
+    o.events_blocks = std::max(1, num("LH_EVENTS_BLOCKS", o.events_blocks));
     o.collect_hash_bits = std::min(64, std::max(1, num("LH_COLLECT_HASH_BITS", o.collect_hash_bits)));
     return o;
   }();
@@ -208,6 +209,14 @@ struct CodonWs {
   DevBuf out_wsum, out_gsum;                      // lh_eval_codons_batch's device copies of the weighted sums
 };
 
+// K10 (lh_events.hip)
+struct EventsWs {
+  DevBuf post, scratch;                         // K5's copy of the forward arrays, the per-slot normaliser tables
+  DevBuf loglik, events, genes;                 // K10's arrays the caller does not hand in
+  DevBuf weights, stats, partial_e, partial_g;
+  DevBuf out_esum, out_gsum;                    // lh_eval_events_batch's device copies of the weighted sums
+};
+
 struct CandidateWs {
   lh_family* twin = nullptr;
   std::string twin_error;  // why there is no twin
@@ -296,6 +305,7 @@ struct lh_family {
   ViterbiWs vit;
   CodonSource codon_src;
   CodonWs codon;
+  EventsWs events;
   CollectWs collect;
   LineageWs lineage;
   // forward arrays that stay on the device, shared by K4 and K5 in both their forms: K4 draws from them, K5 overwrites
@@ -312,6 +322,7 @@ struct lh_family {
   KernelTimer<1> collect_timer;             // K6c
   KernelTimer<1> vit_timer;                 // K8
   KernelTimer<1> codon_timer;               // K9
+  KernelTimer<2> events_timer;              // K10: K5's pass on the copy, K10 and its reduction
   KernelTimer<1> lineage_timer;             // K7
   KernelTimer<5> chain_timer;               // lh_eval_lineage_batch: K0, K1, K2 + K4 + K6c, K3, K7
   bool extended = false;  // lh_family_set_extended_range
@@ -2924,6 +2935,183 @@ int lh_eval_codons_batch(lh_family* f, int32_t n, int32_t T, int32_t max_depth, 
 
 int lh_codon_profile_read(lh_family* f, double* ms, int64_t* n_launches) {
   return profile_read(f, &lh_family::codon_timer, ms, n_launches);
+}
+
+}  // extern "C"
+
+// ---- K10: exact posteriors of the recombination events (lh_events.hip) ----
+
+namespace {
+
+struct EventsLayout {
+  int32_t n_junctions = 0, n_genes = 0;
+  int32_t rows[2] = {0, 0}, n_left[2] = {0, 0}, n_right[2] = {0, 0};
+  int64_t exit_off[2] = {0, 0}, enter_off[2] = {0, 0}, span_off[2] = {0, 0}, size = 0;
+};
+
+EventsLayout events_layout(const lh_family* f) {
+  const lh::DevSampler& smp = f->sampler;
+  EventsLayout lay;
+  lay.n_junctions = smp.has_d ? 2 : 1;
+  lay.n_genes = smp.n_v + (smp.has_d ? smp.n_d : 0) + smp.n_j;
+  for (int j = 0; j < lay.n_junctions; ++j) {
+    const lh::DevSampleJunction& J = j == 0 ? smp.vd : smp.dj;
+    const int64_t W1 = (int64_t)J.n_rows + 1;
+    lay.rows[j] = J.n_rows;
+    lay.n_left[j] = J.n_left;
+    lay.n_right[j] = J.n_right;
+    lay.exit_off[j] = lay.size;
+    lay.enter_off[j] = lay.exit_off[j] + J.n_left * W1;
+    lay.span_off[j] = lay.enter_off[j] + J.n_right * W1;
+    lay.size = lay.span_off[j] + W1 * W1;
+  }
+  return lay;
+}
+
+// K5 on a copy of the forward arrays fwd[m][FS] (it smooths in place; K10 reads both), then K10
+int events_launch(lh_family* f, int m, const double* fwd, const double* loglik, double* events, double* genes,
+                  hipStream_t stream, bool timed) {
+  EventsWs& ew = f->events;
+  const size_t FS = f->host.forward_size;
+  double* post = ew.post.get<double>();
+  if (timed && f->events_timer.begin(stream)) return 1;
+  LH_HIP(hipMemcpyAsync(post, fwd, sizeof(double) * FS * m, hipMemcpyDeviceToDevice, stream));
+  lh::launch_posterior(f->sampler_dev, m, post, FS, loglik, stream);
+  if (timed && f->events_timer.mark(1, stream)) return 1;
+  lh::launch_events(f->sampler, f->sampler_dev, m, fwd, post, FS, loglik, ew.scratch.get<double>(), events,
+                    (size_t)events_layout(f).size, genes, stream);
+  LH_HIP(hipGetLastError());
+  return 0;
+}
+
+int events_buffers(lh_family* f, int n) {
+  EventsWs& ew = f->events;
+  return ew.post.ensure(sizeof(double) * f->host.forward_size * n) ||
+         ew.scratch.ensure(sizeof(double) * lh::events_scratch_doubles(f->sampler) * lh::events_slots(n));
+}
+
+}  // namespace
+
+extern "C" {
+
+int lh_events_layout(const lh_family* f, int32_t* n_junctions, int32_t* rows, int32_t* n_left, int32_t* n_right,
+                     int64_t* exit_off, int64_t* enter_off, int64_t* span_off, int64_t* size, int32_t* n_genes) {
+  if (!f) return fail("lh_events_layout: null family");
+  if (!f->have_sampler) return fail("lh_events_layout: lh_family_set_sampler has not been called");
+  const EventsLayout lay = events_layout(f);
+  if (n_junctions) *n_junctions = lay.n_junctions;
+  for (int j = 0; j < 2; ++j) {
+    if (rows) rows[j] = lay.rows[j];
+    if (n_left) n_left[j] = lay.n_left[j];
+    if (n_right) n_right[j] = lay.n_right[j];
+    if (exit_off) exit_off[j] = lay.exit_off[j];
+    if (enter_off) enter_off[j] = lay.enter_off[j];
+    if (span_off) span_off[j] = lay.span_off[j];
+  }
+  if (size) *size = lay.size;
+  if (n_genes) *n_genes = lay.n_genes;
+  return 0;
+}
+
+int lh_eval_events_batch_device(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops,
+                                const double* brlen, const double* er, const double* pi, const double* alpha, int32_t R,
+                                const lh_events_outputs* outs, void* hip_stream) {
+  const TreeBatch b{n, T, max_depth, ops, brlen, er, pi, alpha, R};
+  const std::string W = "lh_eval_events_batch_device";
+  if (int rc = check_batch(f, W, b, true)) return rc > 0;
+  DeviceGuard guard(f);
+  hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+  const lh_events_outputs none{};
+  const lh_events_outputs& o = outs ? *outs : none;
+  EventsWs& ew = f->events;
+  const EventsLayout lay = events_layout(f);
+  const size_t FS = f->host.forward_size, NE = (size_t)lay.size, NG = lay.n_genes;
+  double *ll = o.loglik, *ev = o.events, *gen = o.genes, *pe = nullptr, *pg = nullptr;
+  WeightReduce wr;
+  const bool reduce = o.weighted_events || o.weighted_genes || o.weight_stats;
+  const size_t slabs = lh::posterior_slabs(n);
+  // the forward arrays stay in the handle's buffer (K10 reads them); K5 smooths a copy
+  if (f->forward_dev.ensure(sizeof(double) * FS * n) || events_buffers(f, n) || own(ll, ew.loglik, sizeof(double) * n) ||
+      own(ev, ew.events, sizeof(double) * NE * n) || own(gen, ew.genes, sizeof(double) * NG * n) ||
+      (reduce && (wr.prepare(n, ew.weights, ew.stats, o.weight_stats) ||
+                  (o.weighted_events && own(pe, ew.partial_e, sizeof(double) * NE * slabs)) ||
+                  (o.weighted_genes && own(pg, ew.partial_g, sizeof(double) * NG * slabs)))))
+    return 1;
+  double* fwd = f->forward_dev.get<double>();
+  lh_eval_outputs eo{nullptr, nullptr, fwd, nullptr};
+  if (eval_device(f, b, ll, &eo, hip_stream)) return 1;
+  if (events_launch(f, n, fwd, ll, ev, gen, stream, f->profile)) return 1;
+  if (reduce) {
+    wr.launch(n, ll, o.log_offset, stream);
+    if (o.weighted_events) lh::launch_weighted_slabs(n, NE, ev, wr.w, pe, o.weighted_events, stream);
+    if (o.weighted_genes) lh::launch_weighted_slabs(n, NG, gen, wr.w, pg, o.weighted_genes, stream);
+  }
+  if (f->profile && f->events_timer.end(stream)) return 1;
+  LH_HIP(hipGetLastError());
+  return 0;
+}
+
+int lh_eval_events_batch(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops, const double* brlen,
+                         const double* er, const double* pi, const double* alpha, int32_t R, const lh_events_outputs* outs) {
+  const std::string W = "lh_eval_events_batch";
+  const TreeBatch host{n, T, max_depth, ops, brlen, er, pi, alpha, R};
+  if (int rc = check_batch(f, W, host, true)) return rc > 0;
+  DeviceGuard guard(f);
+  if (!host.has_arrays()) return fail(W + ": null array");
+  const lh_events_outputs none{};
+  const lh_events_outputs& o = outs ? *outs : none;
+  if (!o.loglik && !o.events && !o.genes && !o.weighted_events && !o.weighted_genes && !o.weight_stats) return 0;
+  EventsWs& ew = f->events;
+  const EventsLayout lay = events_layout(f);
+  const size_t NE = (size_t)lay.size, NG = lay.n_genes;
+  HostOutputs& out = f->out;
+  lh_events_outputs d{};
+  TreeBatch dev;
+  if (out.loglik.ensure(sizeof(double) * n) || out_buf(o.events, ew.events, sizeof(double) * NE * n, &d.events) ||
+      out_buf(o.genes, ew.genes, sizeof(double) * NG * n, &d.genes) ||
+      out_buf(o.weighted_events, ew.out_esum, sizeof(double) * NE, &d.weighted_events) ||
+      out_buf(o.weighted_genes, ew.out_gsum, sizeof(double) * NG, &d.weighted_genes) ||
+      out_buf(o.weight_stats, out.weight_stats, sizeof(double) * 3, &d.weight_stats) ||
+      stage_batch(f, host, {{o.log_offset, sizeof(double) * n, &f->in.log_offset}}, &dev))
+    return 1;
+  d.log_offset = o.log_offset ? f->in.log_offset.get<const double>() : nullptr;
+  d.loglik = out.loglik.get<double>();
+  if (lh_eval_events_batch_device(f, n, T, max_depth, dev.ops, dev.brlen, dev.er, dev.pi, dev.model, R, &d, nullptr)) return 1;
+  return finish_batch(f, W.c_str(), host,
+                      {{o.loglik, d.loglik, sizeof(double) * n},
+                       {o.events, d.events, sizeof(double) * NE * n},
+                       {o.genes, d.genes, sizeof(double) * NG * n},
+                       {o.weighted_events, d.weighted_events, sizeof(double) * NE},
+                       {o.weighted_genes, d.weighted_genes, sizeof(double) * NG},
+                       {o.weight_stats, d.weight_stats, sizeof(double) * 3}});
+}
+
+int lh_events_forward_batch(lh_family* f, int32_t n, const double* em, double* loglik, double* events) {
+  const std::string W = "lh_events_forward_batch";
+  if (!f) return fail(W + ": null family");
+  DeviceGuard guard(f);
+  if (!f->have_sampler) return fail(W + ": lh_family_set_sampler has not been called");
+  if (n <= 0) return n == 0 ? 0 : fail(W + ": negative batch size");
+  if (!em) return fail(W + ": null array");
+  const size_t C = f->host.n_xmsa, FS = f->host.forward_size, NE = (size_t)events_layout(f).size;
+  HostOutputs& out = f->out;
+  EventsWs& ew = f->events;
+  if (out.loglik.ensure(sizeof(double) * n) || f->forward_dev.ensure(sizeof(double) * FS * n) || events_buffers(f, n) ||
+      ew.events.ensure(sizeof(double) * NE * n) || stage_inputs(f, {{em, sizeof(double) * C * n, &f->in.em}}))
+    return 1;
+  lh_eval_outputs eo{nullptr, nullptr, f->forward_dev.get<double>(), nullptr};
+  if (run_forward(f, n, 1, nullptr, nullptr, nullptr, f->in.em.get<const double>(), nullptr, out.loglik.get<double>(), &eo, 0,
+                  nullptr))
+    return 1;
+  if (events_launch(f, n, f->forward_dev.get<const double>(), out.loglik.get<const double>(), ew.events.get<double>(), nullptr,
+                    nullptr, false))
+    return 1;
+  return copy_back(f, nullptr,
+                   {{loglik, out.loglik.get(), sizeof(double) * n}, {events, ew.events.get(), sizeof(double) * NE * n}});
+}
+
+int lh_events_profile_read(lh_family* f, double* ms, int64_t* n_launches) {
+  return profile_read(f, &lh_family::events_timer, ms, n_launches);
 }
 
 }  // extern "C"

@@ -213,6 +213,16 @@ int codon_slots(int n);  // samples that are in flight at once: scratch[codon_sl
 void launch_codons(const DevSampler* smp_dev, const CodonTables& t, int n, const double* fwd, size_t forward_size,
                    const double* loglik, double* scratch, double* windows, double* genes, hipStream_t stream);
 
+// K10 (lh_events.hip): exact posteriors of the recombination events, from the compact forward arrays fwd and K5's
+// posteriors of the same entries post (both read only).  Per sample one flat row events[events_size]: per junction (V-D,
+// then D-J)  exit[nL][W+1] | enter[nR][W+1] | span[W+1][W+1]  (include/linearham_amd.h, lh_events_layout); genes[n][nV +
+// nD + nJ] (may be null) are K5's gene posteriors.  NaN for a sample whose loglik is not finite.
+int events_slots(int n);  // samples that are in flight at once: scratch[events_slots(n)][events_scratch_doubles(smp)]
+size_t events_scratch_doubles(const DevSampler& smp);
+void launch_events(const DevSampler& smp, const DevSampler* smp_dev, int n, const double* fwd, const double* post,
+                   size_t forward_size, const double* loglik, double* scratch, double* events, size_t events_size,
+                   double* genes, hipStream_t stream);
+
 // K6 (lh_naive_probs.hip): exact posterior probabilities of candidate naive sequences.
 // K6a: em[k][c] = 1 where candidate k has the naive base of the caller's column c at its site, else 0 (the
 // indicator emissions of the constrained forward sweep), for K candidates of L sites and C columns.
@@ -449,6 +459,7 @@ struct DebugOptions {
   int k1_seg_waves = 4;        // LH_K1_SEG_WAVES=<4|5>: register budget of the segmented kernels
   bool k1_no_fuse = false;     // LH_K1_NO_FUSE: one workgroup per (sample, rate)
   int codon_blocks = 2048;     // LH_CODON_BLOCKS=<n>: K9's workgroup cap (tests: a lane group walks several samples in a small call)
+  int events_blocks = 1024;    // LH_EVENTS_BLOCKS=<n>: K10's workgroup cap (as LH_CODON_BLOCKS)
   int collect_hash_bits = 64;  // LH_COLLECT_HASH_BITS=<n>: K6c's row hashes masked to n bits (tests: collisions common,
                                // the exact resolution runs; results unchanged)
 };

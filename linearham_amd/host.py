@@ -113,6 +113,27 @@ def read_codon_marginals(prefix):
     return table, aa, summary
 
 
+def parse_events(deletions_text, insertions_text, spans_text):
+    """dict(deletions = {(column, gene, length): p}, insertions = {(column, length): p}, spans = {(junction, left rows,
+    right first row): p}) from the texts WriteDeletionTable / WriteInsertionTable / WriteSpanTable print.  gene "*" names
+    the gene-summed rows; an insertion's column is the annotation's (VDInsertion, DJInsertion, VJInsertion)."""
+    def rows(text):
+        return [ln.split("\t") for ln in text.strip("\n").split("\n")[1:] if ln]
+    return dict(deletions={(c, g, int(k)): float(p) for c, g, k, p in rows(deletions_text)},
+                insertions={(j + "Insertion", int(k)): float(p) for j, k, p in rows(insertions_text)},
+                spans={(j, int(a), int(b)): float(p) for j, a, b, p in rows(spans_text)})
+
+
+def read_events(prefix):
+    """(parse_events' dict, summary dict) from the files RunEventsPipeline writes."""
+    tables = parse_events(*[open(prefix + ext).read() for ext in (".deletions.tsv", ".insertions.tsv", ".spans.tsv")])
+    summary = {}
+    for ln in open(prefix + ".summary.tsv").read().strip().split("\n")[1:]:
+        k, v = ln.split("\t")
+        summary[k] = float(v) if k == "kish_ess" else int(v)
+    return tables, summary
+
+
 def read_naive_probs(prefix):
     """The files RunNaiveProbsPipeline writes: dict(naive = list of row dicts of <prefix>.naive.tsv in rank order
     (probability / log_prior floats, sampled_count int or None, sampled_frequency float or None), aa = [(name, p, aa)]
@@ -410,6 +431,44 @@ class PhyloHMM(_HMM):
         f.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_int, C.c_double, C.c_int]
         _check(f(self.h, input_path.encode(), output_prefix.encode(), num_rates, C.c_double(burnin_frac), frame))
         return read_codon_marginals(output_prefix)
+
+    def events_sizes(self):
+        """(length of K10's flat row, number of gene posteriors nV + nD + nJ) for this family; no device."""
+        f = self.lib.lhh_phylo_events_sizes
+        f.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int)]
+        size, ng = C.c_int64(), C.c_int()
+        _check(f(self.h, C.byref(size), C.byref(ng)))
+        return size.value, ng.value
+
+    def map_events(self, events, genes):
+        """PhyloHMM::MapEvents on one flat row and the V | D | J gene posteriors (no device): parse_events' dict."""
+        size, ng = self.events_sizes()
+        events, genes = np.ascontiguousarray(events, dtype=np.float64), np.ascontiguousarray(genes, dtype=np.float64)
+        if events.shape != (size,) or genes.shape != (ng,):
+            raise ValueError("map_events: the row must hold %d entries and the genes %d" % (size, ng))
+        f = self.lib.lhh_phylo_map_events
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_char_p)]
+        out = C.c_char_p()
+        _check(f(self.h, events.ctypes.data, genes.ctypes.data, C.byref(out)))
+        return parse_events(*out.value.decode().split("\n\n"))
+
+    def rearrangement_events(self):
+        """parse_events' dict for the current tree (PhyloHMM::RearrangementEvents, K10): exact posteriors of the deletion
+        lengths per gene, of the insertion lengths and of the junction spans."""
+        f = self.lib.lhh_phylo_events
+        f.argtypes = [C.c_void_p, C.POINTER(C.c_char_p)]
+        out = C.c_char_p()
+        _check(f(self.h, C.byref(out)))
+        return parse_events(*out.value.decode().split("\n\n"))
+
+    def run_events_pipeline(self, input_path, output_prefix, num_rates, burnin_frac=0.0):
+        """PhyloHMM::RunEventsPipeline: importance-weighted exact deletion, insertion and span tables over a RevBayes
+        table.  Writes <prefix>.deletions.tsv, .insertions.tsv, .spans.tsv and .summary.tsv and returns
+        read_events(prefix)."""
+        f = self.lib.lhh_run_events_pipeline
+        f.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_int, C.c_double]
+        _check(f(self.h, input_path.encode(), output_prefix.encode(), num_rates, C.c_double(burnin_frac)))
+        return read_events(output_prefix)
 
     def viterbi_annotation(self):
         """The most probable annotation of the current tree (PhyloHMM::ViterbiAnnotation, K8): (dict of the annotation
