@@ -723,12 +723,15 @@ size_t asr_group(const lh_family* f, int T, int R, size_t clv_per_sample) {
 }
 
 // K1 for the launch group g with the given rates, into the workspace's planes (ensure_workspace has sized them), and what
-// every caller makes of its outcome.  mix == false: per-rate planes, K1 must not mix the categories.
+// every caller makes of its outcome.  mix == false: per-rate planes, K1 must not mix the categories.  The walk that tests
+// for rescaling after every op (launch_prune, test_every_op) for a handle in the extended-range mode and for the unmixed
+// planes: K3 draws a site's rate category from them, and a category the assembly walk has zeroed between two of its tests
+// leaves the draw to the dead ones (tests/test_gpu_rescaling_cadence.py).
 int prune_group(lh_family* f, const std::string& who, const TreeBatch& g, const double* rates, bool mix, hipStream_t stream,
                 int* planes) {
   Workspace& w = f->ws;
   *planes = lh::launch_prune(f->host, g.n, g.R, g.T, g.max_depth, g.ops, g.brlen, rates, w.eig.get<double>(), w.prune, g.pi,
-                             w.site_lik.get<double>(), w.site_scal.get<int32_t>(), stream, mix);
+                             w.site_lik.get<double>(), w.site_scal.get<int32_t>(), stream, mix, f->extended || !mix);
   if (*planes < 0) return fail(who + ": " + lh::prune_last_error());
   f->k1_form = lh::prune_last_form();
   if (!mix && *planes != g.R && f->host.n_prune > 0) return fail(who + ": internal error (rate planes were mixed)");

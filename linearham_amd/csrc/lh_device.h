@@ -366,11 +366,14 @@ void launch_model_setup(int n, int R, const double* er, const double* pi, const 
 // matrix of the child whose CLV is in the accumulator, [1] = matrix of the popped child), tip-branch
 // matrices into its LDS tip table.
 // site_lik[n][R][5][n_prune], site_scal[n][R][n_prune]
+// test_every_op: the cherry-table form runs its C++ walk (a rescaling test after every op) where it would run the assembly
+// walk (a test after every fourth): the extended-range mode asks for it (lh_prune.hip, launch_prune).
 // Returns the number of rate planes left in site_lik / site_scal: R, or 1 if the rates were mixed in K1
 // (site_lik[n][1][5][n_prune], site_scal[n][1][n_prune]); K2a is to be run with that count.
 int launch_prune(const DevFamily& fam, int n, int R, int T, int max_depth, const int32_t* ops,
                  const double* brlen, const double* rates, const double* eig, const PruneWs& ws, const double* pi,
-                 double* site_lik, int32_t* site_scal, hipStream_t stream, bool allow_fused = true);
+                 double* site_lik, int32_t* site_scal, hipStream_t stream, bool allow_fused = true,
+                 bool test_every_op = false);
 // the kernel form the calling thread's last launch_prune chose ("w6<3,false>", "seg4<4,true>", "ct6<16,false,false,true>":
 // kernel<depth, N-aware, all rates in one workgroup, assembly walk>) and, after a -1, why it failed
 const char* prune_last_form();

@@ -1623,7 +1623,7 @@ PruneWsSizes prune_ws_sizes(int T, bool mixed_n) {
 // the rate categories themselves (the count K2a must then be run with); -1 when the launch failed (prune_last_error).
 int launch_prune(const DevFamily& fam, int n, int R, int T, int max_depth, const int32_t* ops,
                  const double* brlen, const double* rates, const double* eig, const PruneWs& ws, const double* pi,
-                 double* site_lik, int32_t* site_scal, hipStream_t stream, bool allow_fused) {
+                 double* site_lik, int32_t* site_scal, hipStream_t stream, bool allow_fused, bool test_every_op) {
   const int L = fam.n_prune;  // distinct alignment columns; identical ones are pruned once
   const PruneWsSizes sizes = prune_ws_sizes(T, fam.msa_mixed_n != 0);
   if (L == 0) {  // nothing but all-N padding (K2a reads no plane at all): the schedules still get checked
@@ -1672,14 +1672,21 @@ int launch_prune(const DevFamily& fam, int n, int R, int T, int max_depth, const
   //     workgroups of 12 or 16 waves per CU, used to fall to a workgroup per (sample, rate) at twice the time.)
   //  2. big: with a whole tip table in LDS fewer than five waves per SIMD would be resident -> segmented tip table.
   //  3. the register-stack form (stack depth <= 4: slots in registers) for big shapes; the cherry-table form (two slots in
-  //     registers, deeper ones in scratch memory: any depth up to 16; the walk in assembly) for everything else.
+  //     registers, deeper ones in scratch memory: any depth up to 16; the walk in assembly, or in C++ with a rescaling test
+  //     after every op where the caller asks for it) for everything else.
   const bool fused = allow_fused && !dbg.k1_no_fuse && !dbg.k1_segments &&
                      ((R * wpr <= 8 && fused_lds <= 53 * 1024) ||    // three workgroups of up to eight waves per CU
                       (R * wpr > 8 && R * wpr <= kCtFusedMaxWaves && fused_lds <= kCtFusedMaxLds));     // two of nine to sixteen
   // (both limits are relied on inside the cherry-table kernels: see kCtFusedMaxWaves)
   const bool big = !fused && ((160 * 1024 / tip_bytes) * wpr / 4 < 5 || dbg.k1_segments);
   const bool tables_hook = dbg.k1_tables || dbg.k1_no_tables;
-  const bool use_asm = !dbg.k1_cxx_walk;  // (both kinds of alignment: 2-bit state planes, or 2 bits + an N flag)
+  // (both kinds of alignment: 2-bit state planes, or 2 bits + an N flag.)  test_every_op: the caller's results must hold on
+  // columns below 2^-1074 (the extended-range mode).  The assembly walk tests for the 2^256 rescaling after every fourth op,
+  // on the largest entry; on such a column a SMALLER entry of a live rate category -- the state the next mutated tip needs --
+  // can fall through the subnormals between two tests and take the column's best path with it (tests/cadence_cases.py:
+  // 2 to 100 % off, finite and plausible).  The C++ walk of the same form tests after every op.  In the default mode such a
+  // column's emission is below 1e-308 and 0 whichever walk runs, so the benchmarked path keeps the assembly walk.
+  const bool use_asm = !dbg.k1_cxx_walk && !test_every_op;
   // Fused shapes take the cherry-table form (round 4, after the assembly walk got its tip states through the scalar path,
   // a rescaling test every fourth op and a lane-parallel K0c): against the compiler's register-stack walk it is 17-33 %
   // ahead on families of at most 128 patterns (one wave per rate, three waves per SIMD: latency-bound -- 115 patterns 5.22

@@ -19,6 +19,7 @@ P = I + U expm1(lambda t r) U^-1 -- at model parameters where that form is ill-c
                         the exact P-matrices rounded to double in linearham_oracle.gtr_pmatrices' shape [branches, R, 4, 4].
 * four_op_drop:         from the exact per-rate conditional likelihoods, the largest fall in binades over four consecutive
                         ops of a lh_schedule_tree schedule (see its docstring for what is counted).
+* entry_window_drop:    the same windows, for EVERY entry of the vectors that can still reach the result, not the largest alone.
 
 mpmath comes with torch's sympy.  Where it does not import, BACKEND is "decimal": the same algorithms run on the standard
 library's decimal module at the same number of digits, except the category means, for which scipy's gammaincinv / gammainc (as
@@ -223,12 +224,14 @@ class ExactModel:
                 out[b, r] = [[float(x) for x in row] for row in self.p(t, r)]
         return out
 
-    def prune(self, T, children, root, brlen, xmsa, columns):
+    def prune(self, T, children, root, brlen, xmsa, columns, entries=False):
         """Exact per-column likelihoods of the tree in lh_schedule_tree's rooted-at-naive form (tests/desc_builder.py
         tree_arrays): tips 0..T-1 (0 = naive), inner nodes T..2T-3, brlen[v] the branch above node v.
         xmsa [T, C] states 0..3, 4 = N; columns: the xmsa columns wanted.
         Returns dict(emission [n] doubles, log2_emission [n], per_rate_log2 [R, n] (log2 of the unmixed per-rate site
-        likelihood, before the division by pi[naive]), node_log2max {inner node: [R, n_patterns]}, pattern_of [n])."""
+        likelihood, before the division by pi[naive]), node_log2max {inner node: [R, n_patterns]}, pattern_of [n]);
+        entries=True adds node_log2 {inner node: [R, n_patterns, 4]}, every entry of the conditional-likelihood vectors
+        (entry_window_drop reads them)."""
         R = len(self.rates)
         children = np.asarray(children).reshape(-1, 2)
         with _Work(self.dps) as w:
@@ -245,6 +248,7 @@ class ExactModel:
                 stack.extend(int(c) for c in children[v - T] if c >= T)
             root_clv = [[None] * len(pat_list) for _ in range(R)]
             node_log2max = {v: np.zeros((R, len(pat_list))) for v in order}
+            node_log2 = {v: np.zeros((R, len(pat_list), 4)) for v in order} if entries else None
             for r in range(R):
                 Pm = {}
                 for v in range(1, 2 * T - 2):
@@ -267,6 +271,8 @@ class ExactModel:
                             acc = [acc[i] * m[i] for i in range(4)]
                         clv[v] = acc
                         node_log2max[v][r, pi_] = w.log2(max(acc))
+                        if entries:
+                            node_log2[v][r, pi_] = [w.log2(x) for x in acc]
                     root_clv[r][pi_] = clv[root]
             # the naive branch: emission(c) = mean_r sum_i pi_i clv_root_i P_naive[i, s] / pi_s   (s = N: row sums, no division)
             n = len(columns)
@@ -288,8 +294,11 @@ class ExactModel:
                 if s != 4:
                     tot = tot / self.pi[s]
                 em[k], l2[k] = float(tot), w.log2(tot)
-        return {"emission": em, "log2_emission": l2, "per_rate_log2": per_rate, "node_log2max": node_log2max,
-                "pattern_of": np.array(pattern_of)}
+        out = {"emission": em, "log2_emission": l2, "per_rate_log2": per_rate, "node_log2max": node_log2max,
+               "pattern_of": np.array(pattern_of)}
+        if entries:
+            out["node_log2"] = node_log2
+        return out
 
 
 def branch_order(tree):
@@ -361,3 +370,39 @@ def four_op_drop(T, children, ops, node_log2max, window=4, live_within=None):
     for k in range(len(nodes)):
         worst = min(worst, float(falls[k:k + window].sum(axis=0)[live].min()))
     return worst
+
+
+def entry_window_drop(T, children, ops, node_log2, window=4, matters_within=60):
+    """four_op_drop for EVERY entry of the conditional-likelihood vectors: [ops, R, patterns, 4], for each op k and entry i
+    how far entry i of op k's result lies below where the largest entry stood `window` ops earlier,
+        (sum over the window's earlier ops of their falls as four_op_drop counts them) + (entry i's own fall in op k),
+    an entry's own fall being log2 result_i - sum over the op's inner-node operands of log2 max(operand).
+
+    Why the largest entry is not enough.  A walk that tests for the 2^256 rescaling only after every `window`-th op looks at
+    the largest entry (so does K1's assembly walk).  Between two tests the vector is multiplied down unscaled, and an entry
+    that lies d binades below the largest reaches the subnormals (2^-1022, bits lost) or zero (2^-1074) when the largest is
+    still d binades clear of them.  That smaller entry may be the one the column's best path runs through -- a state that
+    is unlikely here and exactly right for the tips joined next -- so the result is finite, plausible and wrong while
+    four_op_drop reports a fall far from anything.  A test after every op leaves at most one op's fall between tests.
+
+    Entries that cannot reach the result are nan: every factor still to come is a probability, so an entry contributes at
+    most its own value, and one more than 2^-matters_within below the root's largest entry (per category and pattern)
+    changes nothing in any arithmetic.  node_log2: ExactModel.prune(..., entries=True)'s."""
+    children = np.asarray(children).reshape(-1, 2)
+    nodes = op_nodes(T, children, ops)
+    top, own = [], []
+    for v in nodes:
+        below = np.zeros(node_log2[v].shape[:2])
+        for c in children[v - T]:
+            if c >= T:
+                below = below + node_log2[int(c)].max(axis=2)
+        top.append(node_log2[v].max(axis=2) - below)
+        own.append(node_log2[v] - below[..., None])
+    top, own = np.stack(top), np.stack(own)                 # [ops, R, patterns], [ops, R, patterns, 4]
+    at_root = node_log2[nodes[-1]].max(axis=2)
+    out = np.full(own.shape, np.nan)
+    for k, v in enumerate(nodes):
+        before = top[max(k - window + 1, 0):k].sum(axis=0)
+        fall = before[..., None] + own[k]
+        out[k] = np.where(node_log2[v] >= at_root[..., None] - matters_within, fall, np.nan)
+    return out
