@@ -23,6 +23,8 @@ const DebugOptions& debug_options() {
     auto num = [](const char* name, int dflt) { const char* e = std::getenv(name); return e ? std::atoi(e) : dflt; };
     o.chunk = std::max(256, num("LH_CHUNK", o.chunk));
     o.host_sub = std::max(256, num("LH_HOST_SUB", o.host_sub));
+    o.eval_split = std::min(8, std::max(0, num("LH_EVAL_SPLIT", o.eval_split)));
+    o.eval_fwd_priority = std::min(1, num("LH_EVAL_FWD_PRIORITY", o.eval_fwd_priority));
     o.k2b_no_pair = set("LH_K2B_NO_PAIR");
     o.k2b_vd_single = set("LH_K2B_VD_SINGLE");
     o.sample_timing = set("LH_SAMPLE_TIMING");
@@ -96,7 +98,9 @@ using DevBuf = Buffer<false>;
 using PinnedBuf = Buffer<true>;
 
 // lh_profile_enable's kernel times: HIP events at the Stages + 1 boundaries of every profiled launch group, summed and
-// reset by a read.
+// reset by a read.  A launch group that runs in sub-batches on several streams (eval_group_split) is recorded as spans
+// instead: a pair of events around every piece of a stage, on the stream that piece runs on; a stage's time is then the
+// sum of its spans, and the stages' times overlap.
 template <int Stages>
 class KernelTimer {
  public:
@@ -106,6 +110,8 @@ class KernelTimer {
   ~KernelTimer() {
     for (Events& es : done_) destroy(es);
     destroy(open_);
+    destroy(done_spans_);
+    destroy(open_spans_);
   }
   // begin() records boundary 0 on `s`, mark(k) boundary k, end() the last one
   int begin(hipStream_t s) {
@@ -122,11 +128,41 @@ class KernelTimer {
     done_.push_back(std::exchange(open_, Events{}));
     return 0;
   }
+  // The span form of one launch group: begin_spans(), then span_begin(stage, s) ... span_end(s) around every piece,
+  // end_spans().
+  void begin_spans() {
+    destroy(open_);
+    destroy(open_spans_);
+  }
+  int span_begin(int stage, hipStream_t s) {
+    Span sp{stage, nullptr, nullptr};
+    LH_HIP(hipEventCreate(&sp.a));
+    open_spans_.push_back(sp);
+    LH_HIP(hipEventCreate(&open_spans_.back().b));
+    LH_HIP(hipEventRecord(sp.a, s));
+    return 0;
+  }
+  int span_end(hipStream_t s) {
+    LH_HIP(hipEventRecord(open_spans_.back().b, s));
+    return 0;
+  }
+  void end_spans() {
+    done_spans_.insert(done_spans_.end(), open_spans_.begin(), open_spans_.end());
+    open_spans_.clear();
+    ++span_groups_;
+  }
   // Waits for the launch groups recorded since the last read and hands out their times per stage (ms[Stages]) and their
   // number; either may be null.
   int read(double* ms, int64_t* launches) {
     double sum[Stages] = {};
     hipError_t e = hipSuccess;
+    for (Span& sp : done_spans_) {
+      if (e == hipSuccess) e = hipEventSynchronize(sp.b);
+      float t = 0;
+      if (e == hipSuccess) e = hipEventElapsedTime(&t, sp.a, sp.b);
+      sum[sp.stage] += t;
+    }
+    destroy(done_spans_);
     for (Events& es : done_) {
       if (e == hipSuccess) e = hipEventSynchronize(es[Stages]);
       for (int k = 0; k < Stages && e == hipSuccess; ++k) {
@@ -136,7 +172,7 @@ class KernelTimer {
       }
       destroy(es);
     }
-    const int64_t n = (int64_t)done_.size();
+    const int64_t n = (int64_t)done_.size() + std::exchange(span_groups_, 0);
     done_.clear();
     LH_HIP(e);
     if (ms) std::copy(sum, sum + Stages, ms);
@@ -150,8 +186,21 @@ class KernelTimer {
     for (hipEvent_t& e : es)
       if (e) (void)hipEventDestroy(std::exchange(e, nullptr));
   }
+  struct Span {
+    int stage;
+    hipEvent_t a, b;
+  };
+  static void destroy(std::vector<Span>& v) {
+    for (Span& sp : v) {
+      if (sp.a) (void)hipEventDestroy(sp.a);
+      if (sp.b) (void)hipEventDestroy(sp.b);
+    }
+    v.clear();
+  }
   std::vector<Events> done_;
   Events open_{};
+  std::vector<Span> done_spans_, open_spans_;
+  int64_t span_groups_ = 0;
 };
 
 struct Workspace {  // K0-K2's scratch (ensure_workspace)
@@ -286,6 +335,39 @@ struct HostPipe {
   }
 };
 
+// An evaluation's launch group in sub-batches (eval_group_split): K0a and every sub-batch's K0c + K1 on `prune`, every
+// sub-batch's K2 on `fwd`; the events order the two against each other and against the caller's stream.  Created by the
+// first launch group that is split; an event is recorded again by every group (a wait holds the record that was the last
+// one when the wait was enqueued).
+struct OverlapPipe {
+  static constexpr int kMaxSplit = 8;  // LH_EVAL_SPLIT's range
+  hipStream_t prune = nullptr, fwd = nullptr;
+  hipEvent_t fork = nullptr, join_prune = nullptr, join_fwd = nullptr;
+  hipEvent_t pruned[kMaxSplit] = {};
+  bool ready = false;
+  int ensure(bool fwd_high) {
+    if (ready) return 0;
+    int least = 0, greatest = 0;
+    LH_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
+    if (!prune) LH_HIP(hipStreamCreateWithFlags(&prune, hipStreamNonBlocking));
+    if (!fwd) LH_HIP(hipStreamCreateWithPriority(&fwd, hipStreamNonBlocking, fwd_high ? greatest : 0));
+    for (hipEvent_t* e : {&fork, &join_prune, &join_fwd})
+      if (!*e) LH_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
+    for (hipEvent_t& e : pruned)
+      if (!e) LH_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    ready = true;
+    return 0;
+  }
+  ~OverlapPipe() {
+    for (hipEvent_t e : {fork, join_prune, join_fwd})
+      if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : pruned)
+      if (e) (void)hipEventDestroy(e);
+    if (prune) (void)hipStreamDestroy(prune);
+    if (fwd) (void)hipStreamDestroy(fwd);
+  }
+};
+
 }  // namespace
 
 // Everything a handle owns.  Its buffers, events and streams release themselves; lh_family_destroy deletes the handle with
@@ -315,6 +397,7 @@ struct lh_family {
   HostOutputs out;
   PinnedBuf staging;  // stage_inputs' page-locked slot
   HostPipe pipe;
+  OverlapPipe overlap;
   bool profile = false;
   KernelTimer<3> eval_timer;  // model, prune, forward
   KernelTimer<1> asr_timer, post_timer;
@@ -628,20 +711,27 @@ static const int kChunk = lh::debug_options().chunk;
 
 int run_forward(lh_family* f, int n, int R, const double* site_lik, const int32_t* site_scal, const double* pi,
                 const double* em_in, double* em_out, double* loglik_dev, const lh_eval_outputs* outs,
-                size_t sample_offset, hipStream_t stream, const lh::LogEmRequest& lem = lh::LogEmRequest{}) {
+                size_t sample_offset, hipStream_t stream, const lh::LogEmRequest& lem = lh::LogEmRequest{}, size_t row0 = 0,
+                size_t rows = 0) {
   double* fwd = (outs && outs->forward) ? outs->forward + sample_offset * f->host.forward_size : nullptr;
   int32_t* sco =
       (outs && outs->scaler_counts) ? outs->scaler_counts + sample_offset * f->host.scaler_size : nullptr;
   ForwardWs& w = f->fws;
-  const size_t m = n;
+  // A sub-batch (eval_group_split) is rows row0 .. row0 + n of a launch group of `rows` samples: the hand-off buffers are
+  // sized for the group (growing one would wait for the device and drop the other sub-batches' rows), and every one of
+  // them is indexed by sample alone (lh_forward.hip: gem [gem_size], gcnt [3], jem [n_jcols], jrs [junction rows],
+  // dxf [32], dxc [1] per sample), so the sub-batch works on its own rows of them.
+  const size_t m = std::max(rows, row0 + (size_t)n);
+  const size_t jrows = f->host.vd.n_rows + (f->host.has_d ? f->host.dj.n_rows : 0);
   if (w.jrs.ensure(sizeof(int32_t) * m * std::max(f->host.vd.n_rows + f->host.dj.n_rows, 1)) ||
       w.dxf.ensure(sizeof(double) * m * 32) || w.dxc.ensure(sizeof(int32_t) * m) ||
       w.gem.ensure(sizeof(double) * m * std::max<int64_t>(f->host.gem_size, 1)) ||
       w.jem.ensure(sizeof(double) * m * std::max(f->host.n_jcols, 1)) || w.gcnt.ensure(sizeof(int32_t) * m * 3))
     return 1;
-  lh::launch_forward(f->host, f->dev, n, R, site_lik, site_scal, pi, em_in, em_out, w.gem.get<double>(), w.gcnt.get<int32_t>(),
-                     w.jem.get<double>(), w.jrs.get<int32_t>(), w.dxf.get<double>(), w.dxc.get<int32_t>(), loglik_dev, fwd, sco,
-                     f->extended, stream, lem);
+  lh::launch_forward(f->host, f->dev, n, R, site_lik, site_scal, pi, em_in, em_out, w.gem.get<double>() + row0 * f->host.gem_size,
+                     w.gcnt.get<int32_t>() + row0 * 3, w.jem.get<double>() + row0 * f->host.n_jcols,
+                     w.jrs.get<int32_t>() + row0 * jrows, w.dxf.get<double>() + row0 * 32, w.dxc.get<int32_t>() + row0, loglik_dev,
+                     fwd, sco, f->extended, stream, lem);
   f->k2_form = lh::forward_last_form();
   LH_HIP(hipGetLastError());
   return 0;
@@ -727,14 +817,29 @@ size_t asr_group(const lh_family* f, int T, int R, size_t clv_per_sample) {
 // for rescaling after every op (launch_prune, test_every_op) for a handle in the extended-range mode and for the unmixed
 // planes: K3 draws a site's rate category from them, and a category the assembly walk has zeroed between two of its tests
 // leaves the draw to the dead ones (tests/test_gpu_rescaling_cadence.py).
+// row0 > 0: g is a sub-batch (eval_group_split) that starts at row row0 of its launch group, and works on its own rows of
+// the workspace -- every array is indexed by sample alone (lh_prune.hip: eig [36], the scratch area [R][rate_stride], wops and
+// wlen [T - 2], tabs [tabs_stride], hdr [1], the planes [planes][5 | 1][n_prune] per sample); `rates` is the sub-batch's.
+// The planes' stride needs the plane count, which the shape and not the batch size decides: row0_planes is what the
+// group's first sub-batch got.
 int prune_group(lh_family* f, const std::string& who, const TreeBatch& g, const double* rates, bool mix, hipStream_t stream,
-                int* planes) {
+                int* planes, size_t row0 = 0, int row0_planes = 0) {
   Workspace& w = f->ws;
-  *planes = lh::launch_prune(f->host, g.n, g.R, g.T, g.max_depth, g.ops, g.brlen, rates, w.eig.get<double>(), w.prune, g.pi,
-                             w.site_lik.get<double>(), w.site_scal.get<int32_t>(), stream, mix, f->extended || !mix);
+  const lh::PruneWsSizes z = lh::prune_ws_sizes(g.T, f->host.msa_mixed_n != 0);
+  const size_t L = (size_t)std::max(f->host.n_prune, 0), pl = (size_t)row0_planes;
+  lh::PruneWs p = w.prune;
+  p.scratch += row0 * g.R * z.scratch_doubles_per_rate;
+  p.wops += row0 * g.n_ops();
+  p.wlen += row0 * g.n_ops();
+  p.tabs += row0 * z.tabs_per_sample;
+  p.hdr += row0;
+  *planes = lh::launch_prune(f->host, g.n, g.R, g.T, g.max_depth, g.ops, g.brlen, rates, w.eig.get<double>() + row0 * 36, p, g.pi,
+                             w.site_lik.get<double>() + row0 * pl * 5 * L, w.site_scal.get<int32_t>() + row0 * pl * L, stream,
+                             mix, f->extended || !mix);
   if (*planes < 0) return fail(who + ": " + lh::prune_last_error());
   f->k1_form = lh::prune_last_form();
   if (!mix && *planes != g.R && f->host.n_prune > 0) return fail(who + ": internal error (rate planes were mixed)");
+  if (row0 > 0 && *planes != row0_planes) return fail(who + ": internal error (sub-batches with different rate planes)");
   return 0;
 }
 
@@ -1491,6 +1596,77 @@ int lh_asr_profile_read(lh_family* f, double* ms_sampling, int64_t* n_launches) 
 
 namespace {
 
+// Samples per sub-batch of a launch group of m samples (m or more: the group runs whole, on the caller's stream).
+// LH_EVAL_SPLIT=S forces S equal sub-batches, however small (tests, measurements).  The product's choice is kEvalSplit = 1,
+// no split: on configs[2] every split measured at or below the single stream (profiles/r12_k1_k2_overlap.txt -- 56 to 79 %
+// of K2's time ran inside a K1 interval, and K1 paid more for the company than K2's hidden time returned: three K1
+// workgroups fill a CU's LDS and registers, so a K2 workgroup takes the place of a K1 workgroup instead of the idle issue
+// slots beside it).  A kEvalSplit above 1 would cut whole blocks of 6144 samples (whole rounds of K1 and of all three K2
+// kernels on 256 CUs for configs[2]-like shapes, as the launch group's own size) and leave a group too small for two such
+// blocks whole: a K1 that no longer fills the chip loses more to its tail than an overlap could return.
+constexpr int kEvalSplit = 1;
+constexpr bool kEvalFwdHigh = false;
+static_assert(kEvalSplit >= 1 && kEvalSplit <= OverlapPipe::kMaxSplit, "one `pruned` event per sub-batch");
+int eval_sub_batch(int m) {
+  const int forced = lh::debug_options().eval_split;
+  if (forced > 0) return (m + forced - 1) / forced;
+  constexpr int kBlock = 6144;
+  if (kEvalSplit <= 1 || m < 2 * kBlock) return m;
+  return ((m + kEvalSplit - 1) / kEvalSplit + kBlock - 1) / kBlock * kBlock;
+}
+
+// One launch group of eval_device (samples off .. off + g.n of the call) in sub-batches of `per` samples: K2 of sub-batch i
+// runs on the handle's forward stream while K1 of sub-batch i + 1 runs on its pruning stream -- neither kernel fills the
+// vector units by itself.  A sub-batch is its own rows of the group's workspace (prune_group, run_forward): no second
+// workspace, no copies.  Both streams fork from the caller's stream and join it again before this returns, whatever
+// the outcome, so everything the caller enqueues next -- the next group, K8 on the hand-off buffers, the next call --
+// finds the group complete in stream order.
+int eval_group_split(lh_family* f, const TreeBatch& g, int off, int per, double* rates, double* em_out, double* loglik,
+                     const lh_eval_outputs* outs, const lh::LogEmRequest& lem, hipStream_t stream) {
+  OverlapPipe& op = f->overlap;
+  const int fwd_priority = lh::debug_options().eval_fwd_priority;
+  if (op.ensure(fwd_priority < 0 ? kEvalFwdHigh : fwd_priority > 0)) return 1;
+  Workspace& w = f->ws;
+  const int m = g.n, R = g.R;
+  const size_t C = f->host.n_xmsa, L = (size_t)std::max(f->host.n_prune, 0);
+  KernelTimer<3>* timer = f->profile ? &f->eval_timer : nullptr;
+  LH_HIP(hipEventRecord(op.fork, stream));
+  LH_HIP(hipStreamWaitEvent(op.prune, op.fork, 0));
+  LH_HIP(hipStreamWaitEvent(op.fwd, op.fork, 0));
+  auto enqueue = [&]() -> int {
+    if (timer) timer->begin_spans();
+    if (timer && timer->span_begin(0, op.prune)) return 1;
+    lh::launch_model_setup(m, R, g.er, g.pi, g.model, rates, w.eig.get<double>(), op.prune);
+    if (timer && timer->span_end(op.prune)) return 1;
+    int planes = 0;
+    for (int r0 = 0, j = 0; r0 < m; r0 += per, ++j) {
+      const int k = std::min(per, m - r0);
+      const TreeBatch sub = g.slice(r0, k);
+      if (timer && timer->span_begin(1, op.prune)) return 1;
+      if (prune_group(f, "lh_eval_batch", sub, rates + (size_t)r0 * R, true, op.prune, &planes, r0, planes)) return 1;
+      if (timer && timer->span_end(op.prune)) return 1;
+      LH_HIP(hipEventRecord(op.pruned[j], op.prune));
+      LH_HIP(hipStreamWaitEvent(op.fwd, op.pruned[j], 0));
+      if (timer && timer->span_begin(2, op.fwd)) return 1;
+      const size_t s0 = (size_t)off + r0;
+      const lh::LogEmRequest lem_k{lem.cols, lem.n, lem.out ? lem.out + s0 * lem.n : nullptr};
+      if (run_forward(f, k, planes, w.site_lik.get<double>() + (size_t)r0 * planes * 5 * L,
+                      w.site_scal.get<int32_t>() + (size_t)r0 * planes * L, sub.pi, nullptr,
+                      em_out ? em_out + (size_t)r0 * C : nullptr, loglik + s0, outs, s0, op.fwd, lem_k, r0, m))
+        return 1;
+      if (timer && timer->span_end(op.fwd)) return 1;
+    }
+    if (timer) timer->end_spans();
+    return 0;
+  };
+  const int rc = enqueue();
+  LH_HIP(hipEventRecord(op.join_prune, op.prune));
+  LH_HIP(hipEventRecord(op.join_fwd, op.fwd));
+  LH_HIP(hipStreamWaitEvent(stream, op.join_prune, 0));
+  LH_HIP(hipStreamWaitEvent(stream, op.join_fwd, 0));
+  return rc;
+}
+
 // lh_eval_batch_device's body; lem: K6b's log emissions of every sample (lem.out[n][lem.n]), or none.
 // after(off, m): enqueued behind the forward sweep of every launch group (samples off .. off + m), while K2a's hand-off
 // buffers still hold that group (K8 reads them); nonzero fails the call.
@@ -1510,9 +1686,15 @@ int eval_device(lh_family* f, const TreeBatch& b, double* loglik, const lh_eval_
   for (int off = 0; off < n; off += chunk) {
     const int m = std::min(chunk, n - off);
     const TreeBatch g = b.slice(off, m);
-    if (f->profile && f->eval_timer.begin(stream)) return 1;
     double* rates = (outs && outs->rates) ? outs->rates + (size_t)off * R : w.rates.get<double>();
     double* em_out = (outs && outs->xmsa_emission) ? outs->xmsa_emission + (size_t)off * C : nullptr;
+    if (const int per = eval_sub_batch(m); per < m) {
+      if (eval_group_split(f, g, off, per, rates, em_out, loglik, outs, lem, stream)) return 1;
+      LH_HIP(hipGetLastError());
+      if (after && (*after)(off, m)) return 1;
+      continue;
+    }
+    if (f->profile && f->eval_timer.begin(stream)) return 1;
     lh::launch_model_setup(m, R, g.er, g.pi, g.model, rates, eig, stream);
     if (f->profile && f->eval_timer.mark(1, stream)) return 1;
     int planes = 0;

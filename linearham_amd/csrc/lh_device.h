@@ -450,6 +450,11 @@ struct DebugOptions {
   int host_sub = 12288;        // LH_HOST_SUB=<n>: tree samples per staging sub-chunk of lh_eval_batch (host pointers)
   // (LH_K2A_DIRECT -- K2a walks every gene factor by factor, no consensus form -- is a property of a family and is read
   // when one is created: upload_consensus, lh_capi.hip)
+  int eval_split = 0;          // LH_EVAL_SPLIT=<1..8>: sub-batches of every launch group of an evaluation, K2 of one beside K1
+                               // of the next on the handle's two streams (1: the single-stream path; 0, unset: the
+                               // product's choice, eval_sub_batch in lh_capi.hip)
+  int eval_fwd_priority = -1;  // LH_EVAL_FWD_PRIORITY=<0|1>: the K2 stream at default / at the highest priority (-1, unset:
+                               // the product's choice)
   bool k2b_no_pair = false;    // LH_K2B_NO_PAIR: K2b with one sample per wave
   bool k2b_vd_single = false;  // LH_K2B_VD_SINGLE: one sample per V-D wave
   bool sample_timing = false;  // LH_SAMPLE_TIMING: stage times of every lh_eval_sample_batch call on stderr
