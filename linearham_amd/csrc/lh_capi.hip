@@ -247,23 +247,25 @@ struct CodonSource {
   CodonSegments v, d, j;
   CodonSourceJunction vd, dj;
 };
-struct CodonWs {
+// What K9's and K10's entry points share: a table per row (K9: the windows, K10: the events), the gene posteriors, and the
+// weighted sums of both.
+struct TableWs {
+  DevBuf loglik, table, genes;               // the arrays the caller does not hand in
+  DevBuf weights, stats, partial_t, partial_g;
+  DevBuf out_tsum, out_gsum;                 // the host-pointer form's device copies of the weighted sums
+};
+struct CodonWs : TableWs {
   int32_t frame = -1;  // -1: lh_family_set_codons has not been called (or its last call failed)
   int32_t n_codons = 0;
   std::vector<int32_t> window_codon;
   lh::CodonTables tab{};
-  DevBuf win, codes;                              // the tables
-  DevBuf scratch, fwd, loglik, windows, genes;    // K9's arrays the caller does not hand in
-  DevBuf weights, stats, partial_w, partial_g;
-  DevBuf out_wsum, out_gsum;                      // lh_eval_codons_batch's device copies of the weighted sums
+  DevBuf win, codes;  // the tables
+  DevBuf scratch;
 };
 
 // K10 (lh_events.hip)
-struct EventsWs {
-  DevBuf post, scratch;                         // K5's copy of the forward arrays, the per-slot normaliser tables
-  DevBuf loglik, events, genes;                 // K10's arrays the caller does not hand in
-  DevBuf weights, stats, partial_e, partial_g;
-  DevBuf out_esum, out_gsum;                    // lh_eval_events_batch's device copies of the weighted sums
+struct EventsWs : TableWs {
+  DevBuf post, scratch;  // K5's copy of the forward arrays, the per-slot normaliser tables
 };
 
 struct CandidateWs {
@@ -2894,6 +2896,112 @@ int lh_viterbi_profile_read(lh_family* f, double* ms, int64_t* n_launches) {
   return profile_read(f, &lh_family::vit_timer, ms, n_launches);
 }
 
+}  // extern "C"
+
+// ---- K9 and K10: a table per row, the gene posteriors and the weighted sums of both, behind one evaluation ----
+
+namespace {
+
+// lh_codon_outputs and lh_events_outputs, member for member (`table`: the windows or the events)
+struct TableOuts {
+  const double* log_offset;
+  double *loglik, *table, *genes, *weighted_table, *weighted_genes, *weight_stats;
+};
+
+// The _device form behind its argument checks: rows of NT table entries and NG genes.  launch(fwd, loglik, table, genes)
+// enqueues the kernels behind the evaluation and begins the timer's group when the handle profiles; the reduction joins
+// the group's last stage.  The caller has taken the kernel's own scratch.
+template <int Stages, class Launch>
+int table_batch_device(lh_family* f, const TreeBatch& b, TableWs& ws, size_t NT, size_t NG, const TableOuts& o,
+                       void* hip_stream, KernelTimer<Stages> lh_family::*timer, Launch&& launch) {
+  hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+  const int n = b.n;
+  double *ll = o.loglik, *tbl = o.table, *gen = o.genes, *pt = nullptr, *pg = nullptr;
+  WeightReduce wr;
+  const bool reduce = o.weighted_table || o.weighted_genes || o.weight_stats;
+  const size_t slabs = lh::posterior_slabs(n);
+  // the forward arrays stay in the handle's buffer: the kernels only read them
+  if (f->forward_dev.ensure(sizeof(double) * f->host.forward_size * n) || own(ll, ws.loglik, sizeof(double) * n) ||
+      own(tbl, ws.table, sizeof(double) * NT * n) || own(gen, ws.genes, sizeof(double) * NG * n) ||
+      (reduce && (wr.prepare(n, ws.weights, ws.stats, o.weight_stats) ||
+                  (o.weighted_table && own(pt, ws.partial_t, sizeof(double) * NT * slabs)) ||
+                  (o.weighted_genes && own(pg, ws.partial_g, sizeof(double) * NG * slabs)))))
+    return 1;
+  double* fwd = f->forward_dev.get<double>();
+  lh_eval_outputs eo{nullptr, nullptr, fwd, nullptr};
+  if (eval_device(f, b, ll, &eo, hip_stream)) return 1;
+  if (launch(fwd, ll, tbl, gen, stream)) return 1;
+  if (reduce) {
+    wr.launch(n, ll, o.log_offset, stream);
+    if (o.weighted_table) lh::launch_weighted_slabs(n, NT, tbl, wr.w, pt, o.weighted_table, stream);
+    if (o.weighted_genes) lh::launch_weighted_slabs(n, NG, gen, wr.w, pg, o.weighted_genes, stream);
+  }
+  if (f->profile && (f->*timer).end(stream)) return 1;
+  LH_HIP(hipGetLastError());
+  return 0;
+}
+
+// The host-pointer form W behind its argument checks: `device` is its _device form, run on the handle's device copies.
+using TableDevice = int(lh_family*, const std::string&, const TreeBatch&, const TableOuts&, void*, bool);
+int table_batch(lh_family* f, const std::string& W, const TreeBatch& host, TableWs& ws, size_t NT, size_t NG,
+                const TableOuts& o, TableDevice* device) {
+  if (!host.has_arrays()) return fail(W + ": null array");
+  if (!o.loglik && !o.table && !o.genes && !o.weighted_table && !o.weighted_genes && !o.weight_stats) return 0;
+  const int n = host.n;
+  HostOutputs& out = f->out;
+  TableOuts d{};
+  TreeBatch dev;
+  if (out.loglik.ensure(sizeof(double) * n) || out_buf(o.table, ws.table, sizeof(double) * NT * n, &d.table) ||
+      out_buf(o.genes, ws.genes, sizeof(double) * NG * n, &d.genes) ||
+      out_buf(o.weighted_table, ws.out_tsum, sizeof(double) * NT, &d.weighted_table) ||
+      out_buf(o.weighted_genes, ws.out_gsum, sizeof(double) * NG, &d.weighted_genes) ||
+      out_buf(o.weight_stats, out.weight_stats, sizeof(double) * 3, &d.weight_stats) ||
+      stage_batch(f, host, {{o.log_offset, sizeof(double) * n, &f->in.log_offset}}, &dev))
+    return 1;
+  d.log_offset = o.log_offset ? f->in.log_offset.get<const double>() : nullptr;
+  d.loglik = out.loglik.get<double>();
+  if (device(f, W + "_device", dev, d, nullptr, false)) return 1;
+  return finish_batch(f, W.c_str(), host,
+                      {{o.loglik, d.loglik, sizeof(double) * n},
+                       {o.table, d.table, sizeof(double) * NT * n},
+                       {o.genes, d.genes, sizeof(double) * NG * n},
+                       {o.weighted_table, d.weighted_table, sizeof(double) * NT},
+                       {o.weighted_genes, d.weighted_genes, sizeof(double) * NG},
+                       {o.weight_stats, d.weight_stats, sizeof(double) * 3}});
+}
+
+TableOuts table_outs(const lh_codon_outputs* o) {
+  if (!o) return {};
+  return {o->log_offset, o->loglik, o->windows, o->genes, o->weighted_windows, o->weighted_genes, o->weight_stats};
+}
+TableOuts table_outs(const lh_events_outputs* o) {
+  if (!o) return {};
+  return {o->log_offset, o->loglik, o->events, o->genes, o->weighted_events, o->weighted_genes, o->weight_stats};
+}
+
+// lh_eval_codons_batch_device; host (b's arrays are the host's): lh_eval_codons_batch, which comes back here once, staged
+int codons_batch(lh_family* f, const std::string& W, const TreeBatch& b, const TableOuts& o, void* hip_stream, bool host) {
+  if (f && f->have_sampler && f->codon.frame < 0) return fail(W + ": lh_family_set_codons has not been called");
+  if (int rc = check_batch(f, W, b, true)) return rc > 0;
+  DeviceGuard guard(f);
+  CodonWs& cw = f->codon;
+  const lh::CodonTables& tab = cw.tab;
+  const size_t NW = (size_t)tab.n_window * 125, NG = tab.n_genes;
+  if (host) return table_batch(f, W, b, cw, NW, NG, o, codons_batch);
+  if (cw.scratch.ensure(sizeof(double) * 4 * (size_t)tab.max_vec * lh::codon_slots(b.n))) return 1;
+  return table_batch_device(f, b, cw, NW, NG, o, hip_stream, &lh_family::codon_timer,
+                            [&](const double* fwd, const double* ll, double* win, double* gen, hipStream_t stream) {
+                              if (f->profile && f->codon_timer.begin(stream)) return 1;
+                              lh::launch_codons(f->sampler_dev, tab, b.n, fwd, f->host.forward_size, ll,
+                                                cw.scratch.get<double>(), win, gen, stream);
+                              return 0;
+                            });
+}
+
+}  // namespace
+
+extern "C" {
+
 // ---- K9: exact posterior distributions of the naive sequence's codons (lh_codon.hip) ----
 
 int lh_family_set_codons(lh_family* f, int32_t frame) {
@@ -3045,77 +3153,14 @@ int lh_codon_layout(const lh_family* f, int32_t* n_codons, int32_t* n_window, in
 int lh_eval_codons_batch_device(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops,
                                 const double* brlen, const double* er, const double* pi, const double* alpha, int32_t R,
                                 const lh_codon_outputs* outs, void* hip_stream) {
-  const TreeBatch b{n, T, max_depth, ops, brlen, er, pi, alpha, R};
-  const std::string W = "lh_eval_codons_batch_device";
-  if (f && f->have_sampler && f->codon.frame < 0) return fail(W + ": lh_family_set_codons has not been called");
-  if (int rc = check_batch(f, W, b, true)) return rc > 0;
-  DeviceGuard guard(f);
-  hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-  const lh_codon_outputs none{};
-  const lh_codon_outputs& o = outs ? *outs : none;
-  CodonWs& cw = f->codon;
-  const lh::CodonTables& tab = cw.tab;
-  const size_t FS = f->host.forward_size, NW = (size_t)tab.n_window * 125, NG = tab.n_genes;
-  double *ll = o.loglik, *win = o.windows, *gen = o.genes, *pw = nullptr, *pg = nullptr;
-  WeightReduce wr;
-  const bool reduce = o.weighted_windows || o.weighted_genes || o.weight_stats;
-  const size_t slabs = lh::posterior_slabs(n);
-  // the forward arrays stay in the handle's buffer: K9 only reads them
-  if (f->forward_dev.ensure(sizeof(double) * FS * n) || own(ll, cw.loglik, sizeof(double) * n) ||
-      own(win, cw.windows, sizeof(double) * NW * n) || own(gen, cw.genes, sizeof(double) * NG * n) ||
-      cw.scratch.ensure(sizeof(double) * 4 * (size_t)tab.max_vec * lh::codon_slots(n)) ||
-      (reduce && (wr.prepare(n, cw.weights, cw.stats, o.weight_stats) ||
-                  (o.weighted_windows && own(pw, cw.partial_w, sizeof(double) * NW * slabs)) ||
-                  (o.weighted_genes && own(pg, cw.partial_g, sizeof(double) * NG * slabs)))))
-    return 1;
-  double* fwd = f->forward_dev.get<double>();
-  lh_eval_outputs eo{nullptr, nullptr, fwd, nullptr};
-  if (eval_device(f, b, ll, &eo, hip_stream)) return 1;
-  if (f->profile && f->codon_timer.begin(stream)) return 1;
-  lh::launch_codons(f->sampler_dev, tab, n, fwd, FS, ll, cw.scratch.get<double>(), win, gen, stream);
-  if (reduce) {
-    wr.launch(n, ll, o.log_offset, stream);
-    if (o.weighted_windows) lh::launch_weighted_slabs(n, NW, win, wr.w, pw, o.weighted_windows, stream);
-    if (o.weighted_genes) lh::launch_weighted_slabs(n, NG, gen, wr.w, pg, o.weighted_genes, stream);
-  }
-  if (f->profile && f->codon_timer.end(stream)) return 1;
-  LH_HIP(hipGetLastError());
-  return 0;
+  return codons_batch(f, "lh_eval_codons_batch_device", {n, T, max_depth, ops, brlen, er, pi, alpha, R}, table_outs(outs),
+                      hip_stream, false);
 }
 
 int lh_eval_codons_batch(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops, const double* brlen,
                          const double* er, const double* pi, const double* alpha, int32_t R, const lh_codon_outputs* outs) {
-  const std::string W = "lh_eval_codons_batch";
-  const TreeBatch host{n, T, max_depth, ops, brlen, er, pi, alpha, R};
-  if (f && f->have_sampler && f->codon.frame < 0) return fail(W + ": lh_family_set_codons has not been called");
-  if (int rc = check_batch(f, W, host, true)) return rc > 0;
-  DeviceGuard guard(f);
-  if (!host.has_arrays()) return fail(W + ": null array");
-  const lh_codon_outputs none{};
-  const lh_codon_outputs& o = outs ? *outs : none;
-  if (!o.loglik && !o.windows && !o.genes && !o.weighted_windows && !o.weighted_genes && !o.weight_stats) return 0;
-  CodonWs& cw = f->codon;
-  const size_t NW = (size_t)cw.tab.n_window * 125, NG = cw.tab.n_genes;
-  HostOutputs& out = f->out;
-  lh_codon_outputs d{};
-  TreeBatch dev;
-  if (out.loglik.ensure(sizeof(double) * n) || out_buf(o.windows, cw.windows, sizeof(double) * NW * n, &d.windows) ||
-      out_buf(o.genes, cw.genes, sizeof(double) * NG * n, &d.genes) ||
-      out_buf(o.weighted_windows, cw.out_wsum, sizeof(double) * NW, &d.weighted_windows) ||
-      out_buf(o.weighted_genes, cw.out_gsum, sizeof(double) * NG, &d.weighted_genes) ||
-      out_buf(o.weight_stats, out.weight_stats, sizeof(double) * 3, &d.weight_stats) ||
-      stage_batch(f, host, {{o.log_offset, sizeof(double) * n, &f->in.log_offset}}, &dev))
-    return 1;
-  d.log_offset = o.log_offset ? f->in.log_offset.get<const double>() : nullptr;
-  d.loglik = out.loglik.get<double>();
-  if (lh_eval_codons_batch_device(f, n, T, max_depth, dev.ops, dev.brlen, dev.er, dev.pi, dev.model, R, &d, nullptr)) return 1;
-  return finish_batch(f, W.c_str(), host,
-                      {{o.loglik, d.loglik, sizeof(double) * n},
-                       {o.windows, d.windows, sizeof(double) * NW * n},
-                       {o.genes, d.genes, sizeof(double) * NG * n},
-                       {o.weighted_windows, d.weighted_windows, sizeof(double) * NW},
-                       {o.weighted_genes, d.weighted_genes, sizeof(double) * NG},
-                       {o.weight_stats, d.weight_stats, sizeof(double) * 3}});
+  return codons_batch(f, "lh_eval_codons_batch", {n, T, max_depth, ops, brlen, er, pi, alpha, R}, table_outs(outs), nullptr,
+                      true);
 }
 
 int lh_codon_profile_read(lh_family* f, double* ms, int64_t* n_launches) {
@@ -3175,6 +3220,20 @@ int events_buffers(lh_family* f, int n) {
          ew.scratch.ensure(sizeof(double) * lh::events_scratch_doubles(f->sampler) * lh::events_slots(n));
 }
 
+// lh_eval_events_batch_device, and (host) lh_eval_events_batch, as codons_batch
+int events_batch(lh_family* f, const std::string& W, const TreeBatch& b, const TableOuts& o, void* hip_stream, bool host) {
+  if (int rc = check_batch(f, W, b, true)) return rc > 0;
+  DeviceGuard guard(f);
+  const EventsLayout lay = events_layout(f);
+  const size_t NE = (size_t)lay.size, NG = lay.n_genes;
+  if (host) return table_batch(f, W, b, f->events, NE, NG, o, events_batch);
+  if (events_buffers(f, b.n)) return 1;  // K5 smooths a copy of the forward arrays: K10 reads both
+  return table_batch_device(f, b, f->events, NE, NG, o, hip_stream, &lh_family::events_timer,
+                            [&](const double* fwd, const double* ll, double* ev, double* gen, hipStream_t stream) {
+                              return events_launch(f, b.n, fwd, ll, ev, gen, stream, f->profile);
+                            });
+}
+
 }  // namespace
 
 extern "C" {
@@ -3201,74 +3260,14 @@ int lh_events_layout(const lh_family* f, int32_t* n_junctions, int32_t* rows, in
 int lh_eval_events_batch_device(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops,
                                 const double* brlen, const double* er, const double* pi, const double* alpha, int32_t R,
                                 const lh_events_outputs* outs, void* hip_stream) {
-  const TreeBatch b{n, T, max_depth, ops, brlen, er, pi, alpha, R};
-  const std::string W = "lh_eval_events_batch_device";
-  if (int rc = check_batch(f, W, b, true)) return rc > 0;
-  DeviceGuard guard(f);
-  hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-  const lh_events_outputs none{};
-  const lh_events_outputs& o = outs ? *outs : none;
-  EventsWs& ew = f->events;
-  const EventsLayout lay = events_layout(f);
-  const size_t FS = f->host.forward_size, NE = (size_t)lay.size, NG = lay.n_genes;
-  double *ll = o.loglik, *ev = o.events, *gen = o.genes, *pe = nullptr, *pg = nullptr;
-  WeightReduce wr;
-  const bool reduce = o.weighted_events || o.weighted_genes || o.weight_stats;
-  const size_t slabs = lh::posterior_slabs(n);
-  // the forward arrays stay in the handle's buffer (K10 reads them); K5 smooths a copy
-  if (f->forward_dev.ensure(sizeof(double) * FS * n) || events_buffers(f, n) || own(ll, ew.loglik, sizeof(double) * n) ||
-      own(ev, ew.events, sizeof(double) * NE * n) || own(gen, ew.genes, sizeof(double) * NG * n) ||
-      (reduce && (wr.prepare(n, ew.weights, ew.stats, o.weight_stats) ||
-                  (o.weighted_events && own(pe, ew.partial_e, sizeof(double) * NE * slabs)) ||
-                  (o.weighted_genes && own(pg, ew.partial_g, sizeof(double) * NG * slabs)))))
-    return 1;
-  double* fwd = f->forward_dev.get<double>();
-  lh_eval_outputs eo{nullptr, nullptr, fwd, nullptr};
-  if (eval_device(f, b, ll, &eo, hip_stream)) return 1;
-  if (events_launch(f, n, fwd, ll, ev, gen, stream, f->profile)) return 1;
-  if (reduce) {
-    wr.launch(n, ll, o.log_offset, stream);
-    if (o.weighted_events) lh::launch_weighted_slabs(n, NE, ev, wr.w, pe, o.weighted_events, stream);
-    if (o.weighted_genes) lh::launch_weighted_slabs(n, NG, gen, wr.w, pg, o.weighted_genes, stream);
-  }
-  if (f->profile && f->events_timer.end(stream)) return 1;
-  LH_HIP(hipGetLastError());
-  return 0;
+  return events_batch(f, "lh_eval_events_batch_device", {n, T, max_depth, ops, brlen, er, pi, alpha, R}, table_outs(outs),
+                      hip_stream, false);
 }
 
 int lh_eval_events_batch(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops, const double* brlen,
                          const double* er, const double* pi, const double* alpha, int32_t R, const lh_events_outputs* outs) {
-  const std::string W = "lh_eval_events_batch";
-  const TreeBatch host{n, T, max_depth, ops, brlen, er, pi, alpha, R};
-  if (int rc = check_batch(f, W, host, true)) return rc > 0;
-  DeviceGuard guard(f);
-  if (!host.has_arrays()) return fail(W + ": null array");
-  const lh_events_outputs none{};
-  const lh_events_outputs& o = outs ? *outs : none;
-  if (!o.loglik && !o.events && !o.genes && !o.weighted_events && !o.weighted_genes && !o.weight_stats) return 0;
-  EventsWs& ew = f->events;
-  const EventsLayout lay = events_layout(f);
-  const size_t NE = (size_t)lay.size, NG = lay.n_genes;
-  HostOutputs& out = f->out;
-  lh_events_outputs d{};
-  TreeBatch dev;
-  if (out.loglik.ensure(sizeof(double) * n) || out_buf(o.events, ew.events, sizeof(double) * NE * n, &d.events) ||
-      out_buf(o.genes, ew.genes, sizeof(double) * NG * n, &d.genes) ||
-      out_buf(o.weighted_events, ew.out_esum, sizeof(double) * NE, &d.weighted_events) ||
-      out_buf(o.weighted_genes, ew.out_gsum, sizeof(double) * NG, &d.weighted_genes) ||
-      out_buf(o.weight_stats, out.weight_stats, sizeof(double) * 3, &d.weight_stats) ||
-      stage_batch(f, host, {{o.log_offset, sizeof(double) * n, &f->in.log_offset}}, &dev))
-    return 1;
-  d.log_offset = o.log_offset ? f->in.log_offset.get<const double>() : nullptr;
-  d.loglik = out.loglik.get<double>();
-  if (lh_eval_events_batch_device(f, n, T, max_depth, dev.ops, dev.brlen, dev.er, dev.pi, dev.model, R, &d, nullptr)) return 1;
-  return finish_batch(f, W.c_str(), host,
-                      {{o.loglik, d.loglik, sizeof(double) * n},
-                       {o.events, d.events, sizeof(double) * NE * n},
-                       {o.genes, d.genes, sizeof(double) * NG * n},
-                       {o.weighted_events, d.weighted_events, sizeof(double) * NE},
-                       {o.weighted_genes, d.weighted_genes, sizeof(double) * NG},
-                       {o.weight_stats, d.weight_stats, sizeof(double) * 3}});
+  return events_batch(f, "lh_eval_events_batch", {n, T, max_depth, ops, brlen, er, pi, alpha, R}, table_outs(outs), nullptr,
+                      true);
 }
 
 int lh_events_forward_batch(lh_family* f, int32_t n, const double* em, double* loglik, double* events) {
@@ -3282,17 +3281,17 @@ int lh_events_forward_batch(lh_family* f, int32_t n, const double* em, double* l
   HostOutputs& out = f->out;
   EventsWs& ew = f->events;
   if (out.loglik.ensure(sizeof(double) * n) || f->forward_dev.ensure(sizeof(double) * FS * n) || events_buffers(f, n) ||
-      ew.events.ensure(sizeof(double) * NE * n) || stage_inputs(f, {{em, sizeof(double) * C * n, &f->in.em}}))
+      ew.table.ensure(sizeof(double) * NE * n) || stage_inputs(f, {{em, sizeof(double) * C * n, &f->in.em}}))
     return 1;
   lh_eval_outputs eo{nullptr, nullptr, f->forward_dev.get<double>(), nullptr};
   if (run_forward(f, n, 1, nullptr, nullptr, nullptr, f->in.em.get<const double>(), nullptr, out.loglik.get<double>(), &eo, 0,
                   nullptr))
     return 1;
-  if (events_launch(f, n, f->forward_dev.get<const double>(), out.loglik.get<const double>(), ew.events.get<double>(), nullptr,
+  if (events_launch(f, n, f->forward_dev.get<const double>(), out.loglik.get<const double>(), ew.table.get<double>(), nullptr,
                     nullptr, false))
     return 1;
   return copy_back(f, nullptr,
-                   {{loglik, out.loglik.get(), sizeof(double) * n}, {events, ew.events.get(), sizeof(double) * NE * n}});
+                   {{loglik, out.loglik.get(), sizeof(double) * n}, {events, ew.table.get(), sizeof(double) * NE * n}});
 }
 
 int lh_events_profile_read(lh_family* f, double* ms, int64_t* n_launches) {

@@ -25,31 +25,22 @@
 #include <cmath>
 
 #include "lh_device.h"
+#include "lh_smooth.h"
 
 namespace lh {
 
 namespace {
 
-constexpr int kG = 16;  // lanes per sample
-constexpr int kWaves = 4;
-constexpr int kPerWave = 64 / kG;
+using namespace smooth;  // the lane groups and the three step forms K5, K9 and K10 share
 
-__device__ inline double group_sum(double v) {
-#pragma unroll
-  for (int m = 1; m < kG; m <<= 1) v += __shfl_xor(v, m, kG);
-  return v;
-}
-
-__device__ inline double ratio(double p, double z) { return p != 0.0 ? p / z : 0.0; }
-
-// the entries of a vector that carry local code `want` (want < 0: all of them)
+// the entries of a vector that carry local code `want` (want < 0: all of them); the step forms' reader of `next`
 struct Mask {
   const uint8_t* code;
   int want;
+  __device__ double operator()(const double* __restrict__ v, size_t k) const {
+    return (want < 0 || code[k] == want) ? v[k] : 0.0;
+  }
 };
-__device__ inline double mv(const double* __restrict__ v, const Mask& m, size_t k) {
-  return (m.want < 0 || m.code[k] == m.want) ? v[k] : 0.0;
-}
 
 // A chain position: a germline region (J = the junction to its right, null for the J genes) or a junction row.
 struct Pos {
@@ -63,17 +54,14 @@ struct Pos {
 __device__ inline Pos position(const DevSampler& smp, int q) {
   const DevSampleJunction& VD = smp.vd;
   const DevSampleJunction& DJ = smp.dj;
-  const size_t svd = (size_t)VD.n_left + 5 * (size_t)VD.n_right;
-  if (q == 0) return Pos{0, &VD, 0, 0, smp.n_v};
-  if (q <= VD.n_rows) return Pos{1, &VD, q - 1, (size_t)smp.n_v + (size_t)(q - 1) * svd, 0};
-  size_t off = (size_t)smp.n_v + (size_t)VD.n_rows * svd;
+  const ForwardLayout lay = forward_layout(smp);
+  if (q == 0) return Pos{0, &VD, 0, lay.o_v, smp.n_v};
+  if (q <= VD.n_rows) return Pos{1, &VD, q - 1, lay.o_vd + (size_t)(q - 1) * row_stride(VD), 0};
   q -= VD.n_rows + 1;
-  if (!smp.has_d) return Pos{0, nullptr, 0, off, smp.n_j};
-  if (q == 0) return Pos{0, &DJ, 0, off, smp.n_d};
-  const size_t sdj = (size_t)DJ.n_left + 5 * (size_t)DJ.n_right;
-  off += smp.n_d;
-  if (q <= DJ.n_rows) return Pos{1, &DJ, q - 1, off + (size_t)(q - 1) * sdj, 0};
-  return Pos{0, nullptr, 0, off + (size_t)DJ.n_rows * sdj, smp.n_j};
+  if (!smp.has_d) return Pos{0, nullptr, 0, lay.o_j, smp.n_j};
+  if (q == 0) return Pos{0, &DJ, 0, lay.o_d, smp.n_d};
+  if (q <= DJ.n_rows) return Pos{1, &DJ, q - 1, lay.o_dj + (size_t)(q - 1) * row_stride(DJ), 0};
+  return Pos{0, nullptr, 0, lay.o_j, smp.n_j};
 }
 
 // f(entry) for every entry of the position's vector this lane owns
@@ -94,118 +82,13 @@ __device__ inline void for_owned(const Pos& p, int gl, F&& f) {
 
 __device__ inline double mass(const Pos& p, const double* __restrict__ v, const Mask& m, int gl) {
   double a = 0.0;
-  for_owned(p, gl, [&](size_t k) { a += mv(v, m, k); });
+  for_owned(p, gl, [&](size_t k) { a += m(v, k); });
   return group_sum(a);
 }
 
-// The three step forms below are K5's smooth_row, smooth_last_row and smooth_left_region (lh_posterior.hip) written out of
-// place and with a mask on the vector they are handed: the transition arithmetic is the same and must change together.
-// Junction row i = 0 .. W-2 (smooth_row of K5, out of place): out = one smoothing step from `next` = a (tagged) vector of
-// row i + 1, over the forward row f.
-__device__ void step_row(const DevSampleJunction& J, int i, const double* __restrict__ f, const double* __restrict__ next,
-                         const Mask& m, double* __restrict__ out, int gl) {
-  const int nL = J.n_left, nR = J.n_right;
-  const size_t oN = nL, oR = (size_t)nL + 4 * (size_t)nR;
-  const int i1 = i + 1;
-  double a = 0.0;
-  for (int l = gl; l < nL; l += kG)
-    if (i < J.left_rows[l]) a += J.left_lo[(size_t)i * nL + l] * f[l];
-  a = group_sum(a);
-  double b = 0.0;
-  for (int r = gl; r < nR; r += kG) {
-    const double gp = J.gp[r];
-    const double* ntt = J.ntt + (size_t)r * 16;  // [a][b]: a -> b
-    const double* nli = J.nli + (size_t)r * 4;
-    const double* nlo = J.nlo + ((size_t)i1 * nR + r) * 4;
-    const size_t kn = oN + (size_t)r * 4;
-    const double f0 = f[kn + 0], f1 = f[kn + 1], f2 = f[kn + 2], f3 = f[kn + 3];
-    const bool germ_here = i >= J.right_first[r];
-    const bool germ_next = i1 >= J.right_first[r];
-    const double fg = germ_here ? f[oR + r] : 0.0;
-    const double z0 = (gp * nli[0]) * a + (ntt[0] * f0 + ntt[4] * f1 + ntt[8] * f2 + ntt[12] * f3);
-    const double z1 = (gp * nli[1]) * a + (ntt[1] * f0 + ntt[5] * f1 + ntt[9] * f2 + ntt[13] * f3);
-    const double z2 = (gp * nli[2]) * a + (ntt[2] * f0 + ntt[6] * f1 + ntt[10] * f2 + ntt[14] * f3);
-    const double z3 = (gp * nli[3]) * a + (ntt[3] * f0 + ntt[7] * f1 + ntt[11] * f2 + ntt[15] * f3);
-    const double li = germ_next ? J.li[(size_t)i1 * nR + r] : 0.0;
-    const double rt = germ_next ? J.rtrans[(size_t)i1 * nR + r] : 0.0;
-    const double zg = (gp * li) * a + (nlo[0] * f0 + nlo[1] * f1 + nlo[2] * f2 + nlo[3] * f3) + rt * fg;
-    const double r0 = ratio(mv(next, m, kn + 0), z0), r1 = ratio(mv(next, m, kn + 1), z1);
-    const double r2 = ratio(mv(next, m, kn + 2), z2), r3 = ratio(mv(next, m, kn + 3), z3);
-    const double rg = germ_next ? ratio(mv(next, m, oR + r), zg) : 0.0;
-    out[kn + 0] = f0 * (ntt[0] * r0 + ntt[1] * r1 + ntt[2] * r2 + ntt[3] * r3 + nlo[0] * rg);
-    out[kn + 1] = f1 * (ntt[4] * r0 + ntt[5] * r1 + ntt[6] * r2 + ntt[7] * r3 + nlo[1] * rg);
-    out[kn + 2] = f2 * (ntt[8] * r0 + ntt[9] * r1 + ntt[10] * r2 + ntt[11] * r3 + nlo[2] * rg);
-    out[kn + 3] = f3 * (ntt[12] * r0 + ntt[13] * r1 + ntt[14] * r2 + ntt[15] * r3 + nlo[3] * rg);
-    out[oR + r] = fg * (rt * rg);
-    b += gp * (nli[0] * r0 + nli[1] * r1 + nli[2] * r2 + nli[3] * r3 + li * rg);
-  }
-  b = group_sum(b);
-  for (int l = gl; l < nL; l += kG) {
-    const bool here = i < J.left_rows[l];
-    const double own = i1 < J.left_rows[l] ? mv(next, m, (size_t)l) : 0.0;
-    out[l] = own + (here ? f[l] * (J.left_lo[(size_t)i * nL + l] * b) : 0.0);
-  }
-}
-
-// Junction row W-1: `next` is a (tagged) gene vector of the region right of the junction.
-__device__ void step_last(const DevSampleJunction& J, const double* __restrict__ f, const double* __restrict__ next,
-                          const Mask& m, double* __restrict__ out, int gl) {
-  const int nL = J.n_left, nR = J.n_right, i = J.n_rows - 1;
-  const size_t oN = nL, oR = (size_t)nL + 4 * (size_t)nR;
-  double a = 0.0;
-  for (int l = gl; l < nL; l += kG)
-    if (i < J.left_rows[l]) a += J.left_lo[(size_t)i * nL + l] * f[l];
-  a = group_sum(a);
-  double b = 0.0;
-  for (int r = gl; r < nR; r += kG) {
-    const double* xn = J.exit_nlo + (size_t)r * 4;
-    const size_t kn = oN + (size_t)r * 4;
-    const double f0 = f[kn + 0], f1 = f[kn + 1], f2 = f[kn + 2], f3 = f[kn + 3];
-    const double fg = i >= J.right_first[r] ? f[oR + r] : 0.0;
-    const double c = (J.gp[r] * J.exit_li[r]) * J.prod[r];
-    const double xt = J.exit_trans[r];
-    const double z = c * a + (xn[0] * f0 + xn[1] * f1 + xn[2] * f2 + xn[3] * f3) + xt * fg;
-    const double rho = ratio(mv(next, m, (size_t)r), z);
-    out[kn + 0] = f0 * (xn[0] * rho);
-    out[kn + 1] = f1 * (xn[1] * rho);
-    out[kn + 2] = f2 * (xn[2] * rho);
-    out[kn + 3] = f3 * (xn[3] * rho);
-    out[oR + r] = fg * (xt * rho);
-    b += c * rho;
-  }
-  b = group_sum(b);
-  for (int l = gl; l < nL; l += kG)
-    out[l] = i < J.left_rows[l] ? f[l] * (J.left_lo[(size_t)i * nL + l] * b) : 0.0;
-}
-
-// The germline region left of a junction: `next` is a (tagged) vector of the junction's row 0.
-__device__ void step_left(const DevSampleJunction& J, const double* __restrict__ f, const double* __restrict__ next,
-                          const Mask& m, double* __restrict__ out, int gl) {
-  const int nL = J.n_left, nR = J.n_right;
-  const size_t oN = nL, oR = (size_t)nL + 4 * (size_t)nR;
-  double e = 0.0;
-  for (int g = gl; g < nL; g += kG) e += J.enter_lo[g] * f[g];
-  e = group_sum(e);
-  double b = 0.0;
-  for (int r = gl; r < nR; r += kG) {
-    const double gp = J.gp[r];
-    const double* nli = J.nli + (size_t)r * 4;
-    const double li = J.right_first[r] == 0 ? J.li[r] : 0.0;
-    const size_t kn = oN + (size_t)r * 4;
-    b += ratio(mv(next, m, kn + 0), (gp * nli[0]) * e) * (gp * nli[0]);
-    b += ratio(mv(next, m, kn + 1), (gp * nli[1]) * e) * (gp * nli[1]);
-    b += ratio(mv(next, m, kn + 2), (gp * nli[2]) * e) * (gp * nli[2]);
-    b += ratio(mv(next, m, kn + 3), (gp * nli[3]) * e) * (gp * nli[3]);
-    if (li != 0.0) b += ratio(mv(next, m, oR + r), (gp * li) * e) * (gp * li);
-  }
-  b = group_sum(b);
-  for (int g = gl; g < nL; g += kG) {
-    const double own = J.left_rows[g] > 0 ? mv(next, m, (size_t)g) : 0.0;
-    out[g] = own + f[g] * (J.enter_lo[g] * b);
-  }
-}
-
-// out = the smoothing step from position p + 1 down to p (p is never the last position)
+// out = the smoothing step from position p + 1 down to p (p is never the last position), out of place and with a mask on
+// the vector it is handed.  The step forms promise nothing about their arrays: the __restrict__ here tells them that K9's
+// three are distinct.
 __device__ inline void step(const Pos& p, const double* __restrict__ F, const double* __restrict__ next, const Mask& m,
                             double* __restrict__ out, int gl) {
   const double* f = F + p.off;

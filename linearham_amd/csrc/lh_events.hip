@@ -31,21 +31,15 @@
 #include <cmath>
 
 #include "lh_device.h"
+#include "lh_smooth.h"
 
 namespace lh {
 
 namespace {
 
-constexpr int kG = 16;  // lanes per sample
-constexpr int kWaves = 4;
-constexpr int kPerWave = 64 / kG;
-constexpr int kTab = 6;  // doubles per (row, right gene) of the scratch table
+using namespace smooth;  // the lane groups and K5's normalisers
 
-__device__ inline double group_sum(double v) {
-#pragma unroll
-  for (int m = 1; m < kG; m <<= 1) v += __shfl_xor(v, m, kG);
-  return v;
-}
+constexpr int kTab = 6;  // doubles per (row, right gene) of the scratch table
 
 __device__ inline double recip(double z) { return z != 0.0 ? 1.0 / z : 0.0; }
 
@@ -53,41 +47,31 @@ __device__ inline double recip(double z) { return z != 0.0 ? 1.0 / z : 0.0; }
 // [5] = the weight of "every left gene's row-i state" into those successors, less the successor's own factor
 __device__ void tabulate(const DevSampleJunction& J, const double* __restrict__ F, double* __restrict__ tab, int gl) {
   const int nL = J.n_left, nR = J.n_right, W = J.n_rows;
-  const size_t stride = (size_t)nL + 5 * (size_t)nR;
+  const size_t stride = row_stride(J);
   for (int i = 0; i < W; ++i) {
-    const double* fL = F + (size_t)i * stride;
-    const double* fN = fL + nL;
-    const double* fR = fL + nL + 4 * (size_t)nR;
-    double a = 0.0;
-    for (int l = gl; l < nL; l += kG)
-      if (i < J.left_rows[l]) a += J.left_lo[(size_t)i * nL + l] * fL[l];
-    a = group_sum(a);
-    const int i1 = i + 1;
+    const double* f = F + (size_t)i * stride;
+    const double* fN = f + nL;
+    const double* fR = f + nL + 4 * (size_t)nR;
+    const double a = left_weight(J, i, J.left_lo + (size_t)i * nL, f, gl);
     for (int r = gl; r < nR; r += kG) {
       double* t = tab + ((size_t)i * nR + r) * kTab;
-      const double gp = J.gp[r];
       const double f0 = fN[(size_t)r * 4 + 0], f1 = fN[(size_t)r * 4 + 1], f2 = fN[(size_t)r * 4 + 2],
                    f3 = fN[(size_t)r * 4 + 3];
       const double fg = i >= J.right_first[r] ? fR[r] : 0.0;
-      if (i1 < W) {  // K5's smooth_row
-        const double* ntt = J.ntt + (size_t)r * 16;
-        const double* nli = J.nli + (size_t)r * 4;
-        const double* nlo = J.nlo + ((size_t)i1 * nR + r) * 4;
-        const bool germ_next = i1 >= J.right_first[r];
-        t[0] = recip((gp * nli[0]) * a + (ntt[0] * f0 + ntt[4] * f1 + ntt[8] * f2 + ntt[12] * f3));
-        t[1] = recip((gp * nli[1]) * a + (ntt[1] * f0 + ntt[5] * f1 + ntt[9] * f2 + ntt[13] * f3));
-        t[2] = recip((gp * nli[2]) * a + (ntt[2] * f0 + ntt[6] * f1 + ntt[10] * f2 + ntt[14] * f3));
-        t[3] = recip((gp * nli[3]) * a + (ntt[3] * f0 + ntt[7] * f1 + ntt[11] * f2 + ntt[15] * f3));
-        const double li = germ_next ? J.li[(size_t)i1 * nR + r] : 0.0;
-        const double rt = germ_next ? J.rtrans[(size_t)i1 * nR + r] : 0.0;
-        t[4] = germ_next ? recip((gp * li) * a + (nlo[0] * f0 + nlo[1] * f1 + nlo[2] * f2 + nlo[3] * f3) + rt * fg) : 0.0;
-        t[5] = gp * a;
-      } else {  // K5's smooth_last_row
-        const double* xn = J.exit_nlo + (size_t)r * 4;
-        const double c = (gp * J.exit_li[r]) * J.prod[r];
+      if (i + 1 < W) {
+        const RightGene g = right_gene(J, i + 1, r);
+        const RowNorm n = row_normalisers(J, i + 1, r, g, a, f0, f1, f2, f3, fg);
+        t[0] = recip(n.z0);
+        t[1] = recip(n.z1);
+        t[2] = recip(n.z2);
+        t[3] = recip(n.z3);
+        t[4] = n.germ_next ? recip(n.zg) : 0.0;
+        t[5] = g.gp * a;
+      } else {
+        const LastNorm n = last_normaliser(J, r, a, f0, f1, f2, f3, fg);
         t[0] = t[1] = t[2] = t[3] = 0.0;
-        t[4] = recip(c * a + (xn[0] * f0 + xn[1] * f1 + xn[2] * f2 + xn[3] * f3) + J.exit_trans[r] * fg);
-        t[5] = c * a;
+        t[4] = recip(n.z);
+        t[5] = n.c * a;
       }
     }
   }
@@ -111,7 +95,7 @@ __device__ void span_chains(const DevSampleJunction& J, const double* __restrict
                             const double* __restrict__ pg, const double* __restrict__ tab, double* __restrict__ span,
                             int gl) {
   const int nL = J.n_left, nR = J.n_right, W = J.n_rows, W1 = W + 1;
-  const size_t stride = (size_t)nL + 5 * (size_t)nR;
+  const size_t stride = row_stride(J);
   const size_t oN = nL, oR = (size_t)nL + 4 * (size_t)nR;
   for (int k = gl; k < W1 * W1; k += kG)
     if (k / W1 > k % W1) span[k] = 0.0;  // below the diagonal (no chain comes there)
@@ -183,7 +167,7 @@ __device__ void differences(const DevSampleJunction& J, const double* __restrict
                             const double* __restrict__ pg, double* __restrict__ exit_t, double* __restrict__ enter_t,
                             int gl) {
   const int nL = J.n_left, nR = J.n_right, W = J.n_rows, W1 = W + 1;
-  const size_t stride = (size_t)nL + 5 * (size_t)nR;
+  const size_t stride = row_stride(J);
   const size_t oR = (size_t)nL + 4 * (size_t)nR;
   for (int l = gl; l < nL; l += kG) {
     const int rows = J.left_rows[l];
@@ -230,9 +214,8 @@ __global__ void __launch_bounds__(64 * kWaves)
   const DevSampleJunction& VD = smp.vd;
   const DevSampleJunction& DJ = smp.dj;
   const int nV = smp.n_v, nD = smp.has_d ? smp.n_d : 0, nJ = smp.n_j;
-  const size_t vd_size = (size_t)VD.n_rows * (VD.n_left + 5 * (size_t)VD.n_right);
-  const size_t dj_size = smp.has_d ? (size_t)DJ.n_rows * (DJ.n_left + 5 * (size_t)DJ.n_right) : 0;
-  const size_t o_vd = nV, o_d = o_vd + vd_size, o_dj = o_d + nD, o_j = o_dj + dj_size;
+  const ForwardLayout lay = forward_layout(smp);
+  const size_t o_vd = lay.o_vd, o_d = lay.o_d, o_dj = lay.o_dj, o_j = lay.o_j;
   const size_t vd_out = ((size_t)VD.n_left + VD.n_right + VD.n_rows + 1) * (VD.n_rows + 1);
   const size_t vd_tab = (size_t)VD.n_rows * VD.n_right * kTab;  // each junction has its own table
   const int n_genes = nV + nD + nJ;

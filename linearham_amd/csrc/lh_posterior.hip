@@ -27,143 +27,35 @@
 #include <cmath>
 
 #include "lh_device.h"
+#include "lh_smooth.h"
 
 namespace lh {
 
 namespace {
 
-constexpr int kG = 16;  // lanes per sample
-constexpr int kWaves = 4;
-constexpr int kPerWave = 64 / kG;
+using namespace smooth;  // the lane groups and the three step forms K5, K9 and K10 share
 
-__device__ inline double group_sum(double v) {
-#pragma unroll
-  for (int m = 1; m < kG; m <<= 1) v += __shfl_xor(v, m, kG);
-  return v;
+// Row i = 0 .. W-2 in place: `row` holds the forward row i on entry and pi_i on exit; next = pi_{i+1}, another row.  The
+// step forms promise nothing about their arrays; these three forward to them only to carry __restrict__: `row` (read and
+// written) against `next` and the tables.
+__device__ inline void smooth_row(const DevSampleJunction& J, int i, double* __restrict__ row,
+                                  const double* __restrict__ next, int gl) {
+  step_row(J, i, row, next, Direct{}, row, gl);
 }
-
-// the ratio pi / Z of one successor, 0 where pi is 0 (Z may be 0 there)
-__device__ inline double ratio(double p, double z) { return p != 0.0 ? p / z : 0.0; }
-
-// (K9, lh_codon.hip, carries out-of-place, masked twins of the three step forms below -- step_row, step_last, step_left:
-// a change of the transition arithmetic here belongs there too.)
-// Junction row i = 0 .. W-2: post_row holds the forward row i on entry and pi_i on exit; next = pi_{i+1}.
-__device__ void smooth_row(const DevSampleJunction& J, int i, double* __restrict__ row, const double* __restrict__ next,
-                           int gl) {
-  const int nL = J.n_left, nR = J.n_right;
-  double* fL = row;
-  double* fN = row + nL;
-  double* fR = row + nL + 4 * (size_t)nR;
-  const double* pL = next;
-  const double* pN = next + nL;
-  const double* pR = next + nL + 4 * (size_t)nR;
-  const int i1 = i + 1;
-  double a = 0.0;
-  for (int l = gl; l < nL; l += kG)
-    if (i < J.left_rows[l]) a += J.left_lo[(size_t)i * nL + l] * fL[l];
-  a = group_sum(a);
-  double b = 0.0;
-  for (int r = gl; r < nR; r += kG) {
-    const double gp = J.gp[r];
-    const double* ntt = J.ntt + (size_t)r * 16;  // [a][b]: a -> b
-    const double* nli = J.nli + (size_t)r * 4;
-    const double* nlo = J.nlo + ((size_t)i1 * nR + r) * 4;
-    const double f0 = fN[(size_t)r * 4 + 0], f1 = fN[(size_t)r * 4 + 1], f2 = fN[(size_t)r * 4 + 2],
-                 f3 = fN[(size_t)r * 4 + 3];
-    const bool germ_here = i >= J.right_first[r];   // the gene has a germline state on row i
-    const bool germ_next = i1 >= J.right_first[r];  // ... and on row i + 1
-    const double fg = germ_here ? fR[r] : 0.0;
-    // successors: NTI b of row i + 1 (b = 0..3), germline state of row i + 1
-    const double z0 = (gp * nli[0]) * a + (ntt[0] * f0 + ntt[4] * f1 + ntt[8] * f2 + ntt[12] * f3);
-    const double z1 = (gp * nli[1]) * a + (ntt[1] * f0 + ntt[5] * f1 + ntt[9] * f2 + ntt[13] * f3);
-    const double z2 = (gp * nli[2]) * a + (ntt[2] * f0 + ntt[6] * f1 + ntt[10] * f2 + ntt[14] * f3);
-    const double z3 = (gp * nli[3]) * a + (ntt[3] * f0 + ntt[7] * f1 + ntt[11] * f2 + ntt[15] * f3);
-    const double li = germ_next ? J.li[(size_t)i1 * nR + r] : 0.0;
-    const double rt = germ_next ? J.rtrans[(size_t)i1 * nR + r] : 0.0;
-    const double zg = (gp * li) * a + (nlo[0] * f0 + nlo[1] * f1 + nlo[2] * f2 + nlo[3] * f3) + rt * fg;
-    const double r0 = ratio(pN[(size_t)r * 4 + 0], z0), r1 = ratio(pN[(size_t)r * 4 + 1], z1);
-    const double r2 = ratio(pN[(size_t)r * 4 + 2], z2), r3 = ratio(pN[(size_t)r * 4 + 3], z3);
-    const double rg = germ_next ? ratio(pR[r], zg) : 0.0;
-    fN[(size_t)r * 4 + 0] = f0 * (ntt[0] * r0 + ntt[1] * r1 + ntt[2] * r2 + ntt[3] * r3 + nlo[0] * rg);
-    fN[(size_t)r * 4 + 1] = f1 * (ntt[4] * r0 + ntt[5] * r1 + ntt[6] * r2 + ntt[7] * r3 + nlo[1] * rg);
-    fN[(size_t)r * 4 + 2] = f2 * (ntt[8] * r0 + ntt[9] * r1 + ntt[10] * r2 + ntt[11] * r3 + nlo[2] * rg);
-    fN[(size_t)r * 4 + 3] = f3 * (ntt[12] * r0 + ntt[13] * r1 + ntt[14] * r2 + ntt[15] * r3 + nlo[3] * rg);
-    fR[r] = fg * (rt * rg);
-    b += gp * (nli[0] * r0 + nli[1] * r1 + nli[2] * r2 + nli[3] * r3 + li * rg);
-  }
-  b = group_sum(b);
-  for (int l = gl; l < nL; l += kG) {
-    const bool here = i < J.left_rows[l];
-    const double own = i1 < J.left_rows[l] ? pL[l] : 0.0;
-    fL[l] = own + (here ? fL[l] * (J.left_lo[(size_t)i * nL + l] * b) : 0.0);
-  }
+// Row W-1: the successor is the gene of the region right of the junction, whose posterior is pg[nR].
+__device__ inline void smooth_last_row(const DevSampleJunction& J, double* __restrict__ row, const double* __restrict__ pg,
+                                       int gl) {
+  step_last(J, row, pg, Direct{}, row, gl);
 }
-
-// Junction row W-1: the successor is the gene of the region right of the junction, whose posterior is pg[nR].
-__device__ void smooth_last_row(const DevSampleJunction& J, double* __restrict__ row, const double* __restrict__ pg, int gl) {
-  const int nL = J.n_left, nR = J.n_right, i = J.n_rows - 1;
-  double* fL = row;
-  double* fN = row + nL;
-  double* fR = row + nL + 4 * (size_t)nR;
-  double a = 0.0;
-  for (int l = gl; l < nL; l += kG)
-    if (i < J.left_rows[l]) a += J.left_lo[(size_t)i * nL + l] * fL[l];
-  a = group_sum(a);
-  double b = 0.0;
-  for (int r = gl; r < nR; r += kG) {
-    const double* xn = J.exit_nlo + (size_t)r * 4;
-    const double f0 = fN[(size_t)r * 4 + 0], f1 = fN[(size_t)r * 4 + 1], f2 = fN[(size_t)r * 4 + 2],
-                 f3 = fN[(size_t)r * 4 + 3];
-    const bool germ_here = i >= J.right_first[r];
-    const double fg = germ_here ? fR[r] : 0.0;
-    const double c = (J.gp[r] * J.exit_li[r]) * J.prod[r];
-    const double xt = J.exit_trans[r];
-    const double z = c * a + (xn[0] * f0 + xn[1] * f1 + xn[2] * f2 + xn[3] * f3) + xt * fg;
-    const double rho = ratio(pg[r], z);
-    fN[(size_t)r * 4 + 0] = f0 * (xn[0] * rho);
-    fN[(size_t)r * 4 + 1] = f1 * (xn[1] * rho);
-    fN[(size_t)r * 4 + 2] = f2 * (xn[2] * rho);
-    fN[(size_t)r * 4 + 3] = f3 * (xn[3] * rho);
-    fR[r] = fg * (xt * rho);
-    b += c * rho;
-  }
-  b = group_sum(b);
-  for (int l = gl; l < nL; l += kG)
-    fL[l] = i < J.left_rows[l] ? fL[l] * (J.left_lo[(size_t)i * nL + l] * b) : 0.0;
-}
-
-// The germline region left of the junction (draw_left_region's expectation): f[nL] holds its forward vector on entry
-// and its gene posterior on exit; p0 = pi_0 of the junction.  Row 0's NTI and germline states have the region's
-// genes as their only predecessors, with weights enter_lo[g] * (gp nli[b] or gp li[0]) * f[g]: their posterior mass
-// is shared out in proportion to enter_lo[g] f[g].
-__device__ void smooth_left_region(const DevSampleJunction& J, double* __restrict__ f, const double* __restrict__ p0, int gl) {
-  const int nL = J.n_left, nR = J.n_right;
-  const double* pL = p0;
-  const double* pN = p0 + nL;
-  const double* pR = p0 + nL + 4 * (size_t)nR;
-  double e = 0.0;
-  for (int g = gl; g < nL; g += kG) e += J.enter_lo[g] * f[g];
-  e = group_sum(e);
-  double b = 0.0;
-  for (int r = gl; r < nR; r += kG) {
-    const double gp = J.gp[r];
-    const double* nli = J.nli + (size_t)r * 4;
-    const double li = J.right_first[r] == 0 ? J.li[r] : 0.0;
-    b += ratio(pN[(size_t)r * 4 + 0], (gp * nli[0]) * e) * (gp * nli[0]);
-    b += ratio(pN[(size_t)r * 4 + 1], (gp * nli[1]) * e) * (gp * nli[1]);
-    b += ratio(pN[(size_t)r * 4 + 2], (gp * nli[2]) * e) * (gp * nli[2]);
-    b += ratio(pN[(size_t)r * 4 + 3], (gp * nli[3]) * e) * (gp * nli[3]);
-    if (li != 0.0) b += ratio(pR[r], (gp * li) * e) * (gp * li);
-  }
-  b = group_sum(b);
-  for (int g = gl; g < nL; g += kG) {
-    const double own = J.left_rows[g] > 0 ? pL[g] : 0.0;
-    f[g] = own + f[g] * (J.enter_lo[g] * b);
-  }
+// The germline region left of the junction: f[nL] holds its forward vector on entry and its gene posterior on exit;
+// p0 = pi_0 of the junction.
+__device__ inline void smooth_left_region(const DevSampleJunction& J, double* __restrict__ f,
+                                          const double* __restrict__ p0, int gl) {
+  step_left(J, f, p0, Direct{}, f, gl);
 }
 
 __device__ void smooth_junction(const DevSampleJunction& J, double* __restrict__ rows, const double* __restrict__ pg, int gl) {
-  const size_t stride = (size_t)J.n_left + 5 * (size_t)J.n_right;
+  const size_t stride = row_stride(J);
   const int W = J.n_rows;
   smooth_last_row(J, rows + (size_t)(W - 1) * stride, pg, gl);
   for (int i = W - 2; i >= 0; --i) smooth_row(J, i, rows + (size_t)i * stride, rows + (size_t)(i + 1) * stride, gl);
@@ -183,14 +75,13 @@ __global__ void __launch_bounds__(64 * kWaves)
   }
   const DevSampleJunction& VD = smp.vd;
   const DevSampleJunction& DJ = smp.dj;
-  const int nV = smp.n_v, nD = smp.n_d, nJ = smp.n_j;
-  const size_t vd_size = (size_t)VD.n_rows * (VD.n_left + 5 * (size_t)VD.n_right);
-  const size_t dj_size = smp.has_d ? (size_t)DJ.n_rows * (DJ.n_left + 5 * (size_t)DJ.n_right) : 0;
-  double* p_v = p;
-  double* p_vd = p_v + nV;
-  double* p_d = p_vd + vd_size;
-  double* p_dj = p_d + (smp.has_d ? nD : 0);
-  double* p_j = p_dj + dj_size;
+  const int nJ = smp.n_j;
+  const ForwardLayout lay = forward_layout(smp);
+  double* p_v = p + lay.o_v;
+  double* p_vd = p + lay.o_vd;
+  double* p_d = p + lay.o_d;
+  double* p_dj = p + lay.o_dj;
+  double* p_j = p + lay.o_j;
   double tj = 0.0;
   for (int g = gl; g < nJ; g += kG) tj += p_j[g];
   tj = group_sum(tj);

@@ -57,3 +57,15 @@ def eigen_is_approx(a, b, prec):
     """Eigen isApprox: ||a-b||^2 <= prec^2 * min(||a||^2, ||b||^2)."""
     a, b = np.asarray(a, float).ravel(), np.asarray(b, float).ravel()
     return np.sum((a - b) ** 2) <= prec * prec * min(np.sum(a * a), np.sum(b * b))
+
+
+def gene_entries(lay, post):
+    """K5's V | D | J gene posteriors, cut out of its compact vector `post`; lay: the handle's events_layout()."""
+    j = lay["junctions"]
+    nV, st0 = j[0]["n_left"], j[0]["n_left"] + 5 * j[0]["n_right"]
+    o_d = nV + j[0]["rows"] * st0
+    if len(j) == 1:
+        return np.concatenate([post[:nV], post[o_d:o_d + j[0]["n_right"]]])
+    nD, st1 = j[1]["n_left"], j[1]["n_left"] + 5 * j[1]["n_right"]
+    o_j = o_d + nD + j[1]["rows"] * st1
+    return np.concatenate([post[:nV], post[o_d:o_d + nD], post[o_j:o_j + j[1]["n_right"]]])

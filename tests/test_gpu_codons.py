@@ -14,6 +14,7 @@ from linearham_amd import posterior as lp
 from oracle import linearham_oracle as orc
 from tests import codon_oracle as co
 from tests import posterior_oracle as po
+from tests.helpers import gene_entries
 
 pytestmark = pytest.mark.gpu
 
@@ -95,6 +96,10 @@ def test_golden_families(tmp_path, case):
     ss = h.dump(1)
     L = len(ss["msa"][0])
     sb, _ = h.naive_marginals()
+    # K5's posteriors of the same row: K9's untagged recursion runs the same smoothing steps (lh_smooth.h)
+    k5 = hip.eval_posterior_batch(fl["family"], fl["n_tips"], fl["max_depth"], fl["ops"], fl["brlen"], fl["er"], fl["pi"],
+                                  fl["alpha"], R, want=("posterior",))["posterior"]
+    k5_genes = gene_entries(hip.events_layout(fl["family"]), k5[0])
     for frame in (0, 1, 2):
         table, aa = h.naive_codon_marginals(frame)
         _oracle_row(o, row, R)
@@ -103,6 +108,7 @@ def test_golden_families(tmp_path, case):
         # the C++ expansion and fold against the Python ones, on the same device outputs
         lay = hip.set_codons(fl["family"], frame)
         res = _eval(hip, fl, R=R)
+        assert np.array_equal(res["genes"][0], k5_genes)
         py = lp.codon_table(ss, res["windows"][0], res["genes"][0], lay)
         assert np.max(np.abs(table - py)) < 1e-13
         pa = lp.aa_table(py)

@@ -17,6 +17,7 @@ from tests import events_oracle as eo
 from tests import k2_scaling_cases as kc
 from tests import viterbi_cases as vc
 from tests import viterbi_oracle as vo
+from tests.helpers import gene_entries
 
 pytestmark = pytest.mark.gpu
 
@@ -62,18 +63,6 @@ def _posterior(hip, fam, inp):
                                     inp["alpha"], inp["R"], want=("loglik", "posterior"))
 
 
-def _gene_entries(lay, S, post):
-    """K5's V | D | J gene posteriors, cut out of its compact vector."""
-    j = lay["junctions"]
-    nV, st0 = j[0]["n_left"], j[0]["n_left"] + 5 * j[0]["n_right"]
-    o_d = nV + j[0]["rows"] * st0
-    if len(j) == 1:
-        return np.concatenate([post[:nV], post[o_d:o_d + j[0]["n_right"]]])
-    nD, st1 = j[1]["n_left"], j[1]["n_left"] + 5 * j[1]["n_right"]
-    o_j = o_d + nD + j[1]["rows"] * st1
-    return np.concatenate([post[:nV], post[o_d:o_d + nD], post[o_j:o_j + j[1]["n_right"]]])
-
-
 def _diff(x, y):
     return max(float(np.max(np.abs(a - b))) for jx, jy in zip(x, y) for a, b in zip(jx, jy))
 
@@ -105,7 +94,7 @@ def test_families(hip, tmp_path, name):
         print(name, "row", i, "max deviation from the dense oracle", err, "difference identity", ident)
         assert err < BOUND
         assert ident < 1e-12
-        assert np.array_equal(res["genes"][i], _gene_entries(lay, S, post["posterior"][i]))
+        assert np.array_equal(res["genes"][i], gene_entries(lay, post["posterior"][i]))
         for ex, en, sp in got:
             W = sp.shape[0] - 1
             assert max(abs(ex.sum() - 1.0), abs(en.sum() - 1.0), abs(sp.sum() - 1.0)) < BOUND
