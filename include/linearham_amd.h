@@ -19,6 +19,7 @@
  *   lh_forward_batch      <- HMM::LogLikelihood on caller-supplied emissions (SimpleHMM,
  *                            src/SimpleHMM.cpp:26-39 + src/HMM.cpp:345-354).
  *   lh_asr_batch[_device] <- the per-tree body of scripts/run_bootstrap_asr_ess.R:48-104
+ *   lh_asr_marginals_batch[_device]  the same step's exact per-node marginals along a lineage (no counterpart)
  *                            (phylomd::phylo.likelihood per rate, rate draw, phylomd::asr.sim).
  *
  * All functions return 0 on success and a nonzero status otherwise; lh_last_error() gives the
@@ -510,6 +511,82 @@ int lh_asr_batch_device(lh_family* fam, int32_t n, int32_t n_tips, int32_t max_d
                         const double* brlen, const double* er, const double* pi, const double* rates,
                         int32_t num_rates, const uint8_t* naive, uint64_t seed, uint64_t first_sample,
                         uint8_t* anc, uint8_t* rate_choice, void* hip_stream);
+
+/* ---- K11: exact ancestral-state marginals along a seed's lineage ----
+ * What lh_asr_batch draws and the lineage tables count, as probabilities: per node of a lineage path and alignment site
+ * the posterior of the node's state, marginalised over the rate category and over the naive base,
+ *   marg[s][j][c] = sum_b naive_prob[j][b] sum_r [lik_r(j, b) / sum_r' lik_r'(j, b)] P(x_{v_s, j} = c | column j, naive_j = b, rate r)
+ * from one upward pass of the pruning recursion and one downward pass along the path (no random numbers).
+ *   ops, brlen, er, pi, rates   as for lh_asr_batch
+ *   naive_prob [n][L][5]  the distribution of the naive base at every site (A,C,G,T,N; rows sum to 1).  A one-hot row
+ *                         conditions on a fixed naive sequence: the tables are then the distributions lh_asr_batch draws
+ *                         from.  A base of probability 0 contributes nothing; a NaN row gives NaN at that site.
+ *   path  [n][P]          the lineage of a tip in lh_lineage_batch's convention: slot 0 the tip's parent, every entry
+ *                         the child of the next, the last one the root (naive's neighbour); entries outside T .. 2T-3
+ *                         (-1) are padding and come only after them.  1 <= P <= T - 2.
+ *   marg  [n][P][L][4]    the tables (may be NULL); a padding slot's tables are 0
+ *   rate_post [n][L][R]   the posterior of the site's rate category (may be NULL)
+ * The path is checked against the sample's own schedule.  The host-pointer form refuses a batch with a path that is not
+ * such a chain, as it refuses malformed schedules.  The device form gives that sample NaN in its whole marg row and raises
+ * the handle's error word (lh_family_status), as for a rejected schedule; no index is formed from an unchecked entry.
+ * The same sample gives the same bits whatever the batch around it. */
+int lh_asr_marginals_batch(lh_family* fam, int32_t n, int32_t n_tips, int32_t max_depth, const int32_t* ops,
+                           const double* brlen, const double* er, const double* pi, const double* rates,
+                           int32_t num_rates, const double* naive_prob, const int32_t* path, int32_t path_len,
+                           double* marg, double* rate_post);
+
+/* Same with every array resident on the handle's device; enqueued on `hip_stream` without synchronising. */
+int lh_asr_marginals_batch_device(lh_family* fam, int32_t n, int32_t n_tips, int32_t max_depth, const int32_t* ops,
+                                  const double* brlen, const double* er, const double* pi, const double* rates,
+                                  int32_t num_rates, const double* naive_prob, const int32_t* path, int32_t path_len,
+                                  double* marg, double* rate_post, void* hip_stream);
+
+/* The evaluation with the exact ancestral marginals behind it: lh_eval_posterior_batch's inputs plus path, and per tree
+ * sample K0-K2 (one unmixed K1 serves the forward sweep and K11), K5's posterior on the forward arrays, its push-forward
+ * onto the naive base of every site, and lh_asr_marginals_batch fed that distribution and the sample's rates.  Needs
+ * lh_family_set_sampler; honours lh_family_set_extended_range.  Every member may be NULL:
+ *   log_offset   [n]           (input) as in lh_posterior_outputs
+ *   loglik       [n]
+ *   site_base    [n][L][5]     posterior of the naive base (A,C,G,T,N); what no state writes stays N; NaN for a row
+ *                              without a posterior (non-finite log-likelihood, rejected schedule)
+ *   marg         [n][P][L][4]  as lh_asr_marginals_batch
+ *   rate_post    [n][L][R]
+ *   weighted_sum [2][L][4]     sum_i w_i marg_i of the two slots that mean the same in every tree: [0] the seed's parent
+ *                              (slot 0), [1] the MRCA (the sample's last slot); w_i = exp(loglik_i - log_offset_i - max)
+ *   weighted_rate [L][R]       sum_i w_i rate_post_i
+ *   weight_stats [3]           max, sum w, sum w^2 as in lh_posterior_outputs
+ * The sums run in sample order (K5's slab scheme: no atomics, bit-stable); rows with w = 0 or a non-finite
+ * log-likelihood are left out of the sums and of the statistics, so batches combine exactly as
+ * lh_eval_posterior_batch's do.  So are rows without a valid path (device form) whenever the call looks at the paths,
+ * which it does when marg or weighted_sum is asked for; a call for weighted_rate and weight_stats alone forms neither
+ * and weighs every row.  The host-pointer form refuses a batch whose device copies of site_base, marg and rate_post
+ * would exceed 4 GiB, naming the largest n. */
+typedef struct lh_ancestral_outputs {
+  const double* log_offset;
+  double* loglik;
+  double* site_base;
+  double* marg;
+  double* rate_post;
+  double* weighted_sum;
+  double* weighted_rate;
+  double* weight_stats;
+} lh_ancestral_outputs;
+
+int lh_eval_ancestral_batch(lh_family* fam, int32_t n, int32_t n_tips, int32_t max_depth, const int32_t* ops,
+                            const double* brlen, const double* er, const double* pi, const double* alpha,
+                            int32_t num_rates, const int32_t* path, int32_t path_len, const lh_ancestral_outputs* outs);
+
+/* Same with every array (the members of outs included) resident on the handle's device; enqueued on `hip_stream`
+ * without synchronising. */
+int lh_eval_ancestral_batch_device(lh_family* fam, int32_t n, int32_t n_tips, int32_t max_depth, const int32_t* ops,
+                                   const double* brlen, const double* er, const double* pi, const double* alpha,
+                                   int32_t num_rates, const int32_t* path, int32_t path_len,
+                                   const lh_ancestral_outputs* outs, void* hip_stream);
+
+/* Times of K11 over the launches made while profiling was enabled (HIP events on the launch stream), ms[3]: the
+ * naive-base posteriors, the marginals kernel with its rate weights, path check and rate combination, the weighted
+ * reduction (lh_asr_marginals_batch runs the second only); resets the counters. */
+int lh_ancestral_profile_read(lh_family* fam, double* ms, int64_t* n_launches);
 
 /* Timing of the kernels of the last lh_eval_batch_device call sequence, measured with HIP events
  * on the launch stream when enabled (ms per kernel family: model, prune, forward). */

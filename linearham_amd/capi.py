@@ -77,6 +77,10 @@ EXPORTS += CODON_EXPORTS
 EVENTS_EXPORTS = ["lh_events_layout", "lh_eval_events_batch", "lh_eval_events_batch_device", "lh_events_forward_batch",
                   "lh_events_profile_read"]
 EXPORTS += EVENTS_EXPORTS
+# K11 (exact ancestral-state marginals along a seed's lineage)
+ANCESTRAL_EXPORTS = ["lh_asr_marginals_batch", "lh_asr_marginals_batch_device", "lh_eval_ancestral_batch",
+                     "lh_eval_ancestral_batch_device", "lh_ancestral_profile_read"]
+EXPORTS += ANCESTRAL_EXPORTS
 
 
 class _CodonOutputs(C.Structure):
@@ -106,6 +110,18 @@ class _ViterbiOutputs(C.Structure):
 
 class _ViterbiOutputsDevice(C.Structure):  # the same members as device addresses
     _fields_ = [(k, C.c_void_p) for k in ("log_offset", "loglik", "states", "log_path", "weight_stats")]
+
+
+_ANCESTRAL_MEMBERS = ("log_offset", "loglik", "site_base", "marg", "rate_post", "weighted_sum", "weighted_rate",
+                      "weight_stats")
+
+
+class _AncestralOutputs(C.Structure):
+    _fields_ = [(k, c_f64p) for k in _ANCESTRAL_MEMBERS]
+
+
+class _AncestralOutputsDevice(C.Structure):  # the same members as device addresses
+    _fields_ = [(k, C.c_void_p) for k in _ANCESTRAL_MEMBERS]
 
 
 class _SamplerJunction(C.Structure):
@@ -250,6 +266,13 @@ class HipLibrary:
             lib.lh_eval_events_batch_device.argtypes = _DEV_TREE + [C.POINTER(_EventsOutputsDevice), C.c_void_p]
             lib.lh_events_forward_batch.argtypes = [C.c_void_p, C.c_int32, c_f64p, c_f64p, c_f64p]
             lib.lh_events_profile_read.argtypes = _PROFILE_READ
+        if hasattr(lib, "lh_asr_marginals_batch"):
+            lib.lh_asr_marginals_batch.argtypes = _HOST_TREE + [c_f64p, c_i32p, C.c_int32, c_f64p, c_f64p]
+            lib.lh_asr_marginals_batch_device.argtypes = _DEV_TREE + [C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 3
+            lib.lh_eval_ancestral_batch.argtypes = _HOST_TREE + [c_i32p, C.c_int32, C.POINTER(_AncestralOutputs)]
+            lib.lh_eval_ancestral_batch_device.argtypes = _DEV_TREE + [C.c_void_p, C.c_int32,
+                                                                       C.POINTER(_AncestralOutputsDevice), C.c_void_p]
+            lib.lh_ancestral_profile_read.argtypes = _PROFILE_READ
         if hasattr(lib, "lh_set_device"):      # (absent from round-2 builds loaded through LH_LIB_DIR for comparisons)
             lib.lh_set_device.argtypes = [C.c_int32]
             lib.lh_family_status.argtypes = [C.c_void_p]
@@ -282,6 +305,36 @@ class HipLibrary:
                              weight_stats=(3,))
         self.check(self.lib.lh_eval_posterior_batch(h, n, n_tips, max_depth, *_tree_ptrs(arrays), num_rates, C.byref(outs)))
         return res
+
+    def eval_ancestral_batch(self, family, n_tips, max_depth, ops, brlen, er, pi, alpha, num_rates, path, log_offset=None,
+                             want=("loglik", "site_base", "marg", "rate_post", "weighted_sum", "weighted_rate",
+                                   "weight_stats")):
+        """K0-K2 + K5 + K11 on a family handle that has sampler tables; path [n][P] (seed_path rows, -1 padding).  Returns a
+        dict with the members of `want`: loglik [n], site_base [n, L, 5], marg [n, P, L, 4], rate_post [n, L, R],
+        weighted_sum [2, L, 4] (the seed's parent, the MRCA), weighted_rate [L, R], weight_stats [3]."""
+        h = _handle(family)
+        n, arrays = _tree_args(ops, brlen, er, pi, alpha)
+        path = _i32(path)
+        assert path.ndim == 2 and path.shape[0] == n
+        P, R = path.shape[1], num_rates
+        _, L = self.candidates_info(h)
+        res, outs = _outputs(_AncestralOutputs, want, log_offset, loglik=(n,), site_base=(n, L, 5), marg=(n, P, L, 4),
+                             rate_post=(n, L, R), weighted_sum=(2, L, 4), weighted_rate=(L, R), weight_stats=(3,))
+        self.check(self.lib.lh_eval_ancestral_batch(h, n, n_tips, max_depth, *_tree_ptrs(arrays), num_rates,
+                                                    _ptr(path, c_i32p), P, C.byref(outs)))
+        return res
+
+    def eval_ancestral_batch_device(self, family, n, n_tips, max_depth, ops_ptr, brlen_ptr, er_ptr, pi_ptr, alpha_ptr,
+                                    num_rates, path_ptr, path_len, outs, stream=0):
+        """lh_eval_ancestral_batch_device on device addresses; outs: dict of the output members' addresses."""
+        o = _AncestralOutputsDevice(**{k: int(v) for k, v in outs.items() if v})
+        self.check(self.lib.lh_eval_ancestral_batch_device(_handle(family), n, n_tips, max_depth, ops_ptr, brlen_ptr, er_ptr,
+                                                           pi_ptr, alpha_ptr, num_rates, path_ptr, path_len, C.byref(o),
+                                                           stream))
+
+    def ancestral_profile_read(self, family):
+        """(k11a_ms, k11b_ms, reduce_ms, launch groups) of K11 since the last read."""
+        return self._profile_read("lh_ancestral_profile_read", family, 3)
 
     def posterior_profile_read(self, family):
         return self._profile_read("lh_posterior_profile_read", family)
@@ -585,6 +638,21 @@ def _n_rows(n, arrays, log_offset):
         (log_offset is None or np.asarray(log_offset).shape == (n,))
 
 
+def seed_path(n_tips, children, root, seed_tip):
+    """The `path` row of a tip: host.seed_path (the host library's walk, shared with the lineage pipelines)."""
+    from . import host
+    return host.seed_path(n_tips, children, root, seed_tip)
+
+
+def pad_paths(paths):
+    """[n][P] int32 from path rows of different lengths, -1 after each row's last entry."""
+    P = max(len(p) for p in paths)
+    out = np.full((len(paths), P), -1, dtype=np.int32)
+    for i, p in enumerate(paths):
+        out[i, :len(p)] = p
+    return out
+
+
 def split_events(layout, row):
     """[(exit, enter, span)] per junction: views of one flat K10 row under HipLibrary.events_layout's layout."""
     row = np.asarray(row)
@@ -818,6 +886,39 @@ class Family:
                                                  _ptr(naive, c_u8p), seed, first_sample, _ptr(anc, c_u8p),
                                                  _ptr(choice, c_u8p)))
         return anc, choice
+
+    # ---- K11: exact ancestral-state marginals along a lineage ----
+    def asr_marginals_batch(self, n_tips, max_depth, ops, brlen, er, pi, rates, naive_prob, path,
+                            want=("marg", "rate_post")):
+        """lh_asr_marginals_batch: lh_asr_batch's trees and rates, naive_prob [n][L][5] and path [n][P] (seed_path rows,
+        -1 padding); returns (marg [n][P][L][4], rate_post [n][L][R]), None for what `want` leaves out."""
+        _, arrays = _tree_args(ops, brlen, er, pi, rates)
+        ops, brlen, er, pi, rates = arrays
+        naive_prob = _f64(naive_prob)
+        path = _i32(path)
+        n, L = naive_prob.shape[:2]
+        assert naive_prob.shape == (n, L, 5) and path.ndim == 2 and path.shape[0] == n
+        assert ops.shape == (n, n_tips - 2, 4) and brlen.shape == (n, 2 * n_tips - 2)
+        assert er.shape == (n, 6) and pi.shape == (n, 4) and rates.shape[0] == n
+        P, R = path.shape[1], rates.shape[1]
+        marg = np.zeros((n, P, L, 4)) if "marg" in want else None
+        rate_post = np.zeros((n, L, R)) if "rate_post" in want else None
+        self.hip.check(self.hip.lib.lh_asr_marginals_batch(
+            self.handle, n, n_tips, max_depth, *_tree_ptrs(arrays), R, _ptr(naive_prob), _ptr(path, c_i32p), P,
+            _ptr(marg), _ptr(rate_post)))
+        return marg, rate_post
+
+    def asr_marginals_batch_device(self, n, n_tips, max_depth, ops_ptr, brlen_ptr, er_ptr, pi_ptr, rates_ptr, num_rates,
+                                   naive_prob_ptr, path_ptr, path_len, marg_ptr, rate_post_ptr, stream=0):
+        """lh_asr_marginals_batch_device on device addresses, enqueued on `stream`."""
+        self.hip.check(self.hip.lib.lh_asr_marginals_batch_device(
+            self.handle, n, n_tips, max_depth, ops_ptr, brlen_ptr, er_ptr, pi_ptr, rates_ptr, num_rates, naive_prob_ptr,
+            path_ptr, path_len, marg_ptr, rate_post_ptr, stream))
+
+    def ancestral_profile_read(self):
+        """({k11a_ms, k11b_ms, reduce_ms}, launch groups) of K11 since the last read."""
+        r = self.hip._profile_read("lh_ancestral_profile_read", self.handle, 3)
+        return dict(zip(("k11a_ms", "k11b_ms", "reduce_ms"), r[:3])), r[3]
 
     # ---- K7: the lineage of a seed sequence and the lineage store ----
     def lineage_batch(self, n_tips, max_depth, ops, brlen, er, pi, rates, naive, seed, path, first_sample=0):

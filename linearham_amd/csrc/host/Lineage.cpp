@@ -254,6 +254,23 @@ void WriteLineageFiles(const std::string& prefix, const LineageTables& t, int64_
   WriteLineageSummary(summary, t, collisions, ws);
 }
 
+std::vector<int32_t> SeedPath(const int32_t* children, int T, int root, int seed_tip) {
+  std::vector<int32_t> chain;
+  if (T < 3 || seed_tip < 1 || seed_tip >= T) return chain;
+  std::vector<int> parent(2 * (std::size_t)T - 2, -1);
+  for (int v = T; v < 2 * T - 2; ++v)
+    for (int c = 0; c < 2; ++c) {
+      const int k = children[2 * (std::size_t)(v - T) + c];
+      if (k >= 0 && k < 2 * T - 2) parent[k] = v;
+    }
+  for (int v = parent[seed_tip]; v >= T; v = parent[v]) {
+    chain.push_back(v);
+    if (v == root || (int)chain.size() > T) break;
+  }
+  if (chain.empty() || chain.back() != root) chain.clear();
+  return chain;
+}
+
 std::vector<std::string> LineageOfAnnotatedTree(const std::string& s, const std::string& seed_seq) {
   struct Node {
     int parent = -1;

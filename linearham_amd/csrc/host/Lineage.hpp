@@ -106,6 +106,12 @@ void WriteLineageFiles(const std::string& prefix, const LineageTables& t, int64_
 /// (which `ws` counts as skipped); ws->kish_ess = (sum w)^2 / sum w^2.  Throws if no log-weight is finite.
 std::vector<double> LineageWeights(const std::vector<double>& log_weights, LineageWeightSummary* ws);
 
+/// The `path` row of a tip under a tree in the C ABI's rooted-at-naive arrays (children [(T-2)*2] of the inner nodes
+/// T .. 2T-3, root = naive's neighbour): the inner nodes from the tip's parent up to the root, each the child of the next
+/// (lh_lineage_batch's and lh_asr_marginals_batch's convention).  Empty if the tip does not hang below the root or is not
+/// one of the tips 1 .. T-1.
+std::vector<int32_t> SeedPath(const int32_t* children, int n_tips, int root, int seed_tip);
+
 /// One line of PhyloHMM::RunAsr's output (annotated Newick): the [&ancestral="..."] strings on the way seed, its
 /// ancestors up to the top node, then the tip `naive`, as seqs_of_tree collects them, reversed (naive first).
 /// Throws when the tree has no tip `seed_seq` or `naive`, or a node on the way has no annotation.

@@ -1541,17 +1541,9 @@ void PhyloHMM::RunLineagePipeline(const std::string& input_path, const std::stri
     // the seed tip's ancestors up to naive's neighbour
     std::vector<std::vector<int32_t>> chain(m);
     std::size_t P = 1;
-    std::vector<int> parent(2 * (std::size_t)T - 2);
     for (std::size_t i = 0; i < m; ++i) {
-      const TreeArrays& tr = trees[i];
-      std::fill(parent.begin(), parent.end(), -1);
-      for (int v = T; v < 2 * T - 2; ++v)
-        for (int c = 0; c < 2; ++c) parent[tr.children[2 * (std::size_t)(v - T) + c]] = v;
-      for (int v = parent[seed_tip]; v >= T; v = parent[v]) {
-        chain[i].push_back(v);
-        if (v == tr.root || (int)chain[i].size() > T) break;
-      }
-      Require(!chain[i].empty() && chain[i].back() == tr.root,
+      chain[i] = SeedPath(trees[i].children.data(), T, trees[i].root, seed_tip);
+      Require(!chain[i].empty(),
               "row " + std::to_string(off + i) + ": the seed sequence '" + seed_seq + "' does not descend from the root");
       P = std::max(P, chain[i].size());
     }
@@ -1676,18 +1668,9 @@ void PhyloHMM::RunWeightedLineagePipeline(const std::string& input_path, const s
     // the seed tip's ancestors up to naive's neighbour
     std::vector<std::vector<int32_t>> chain(m);
     std::size_t P = 1;
-    std::vector<int> parent(2 * (std::size_t)T - 2);
     for (std::size_t i = 0; i < m; ++i) {
-      const int32_t* ch = tb.children.data() + i * 2 * (std::size_t)(T - 2);
-      const int root = tb.root[i];
-      std::fill(parent.begin(), parent.end(), -1);
-      for (int v = T; v < 2 * T - 2; ++v)
-        for (int c = 0; c < 2; ++c) parent[ch[2 * (std::size_t)(v - T) + c]] = v;
-      for (int v = parent[seed_tip]; v >= T; v = parent[v]) {
-        chain[i].push_back(v);
-        if (v == root || (int)chain[i].size() > T) break;
-      }
-      Require(!chain[i].empty() && chain[i].back() == root,
+      chain[i] = SeedPath(tb.children.data() + i * 2 * (std::size_t)(T - 2), T, tb.root[i], seed_tip);
+      Require(!chain[i].empty(),
               "row " + std::to_string(off + i) + ": the seed sequence '" + seed_seq + "' does not descend from the root");
       P = std::max(P, chain[i].size());
     }
@@ -1878,6 +1861,149 @@ void PhyloHMM::RunMarginalsPipeline(const std::string& input_path, const std::st
   std::snprintf(buf, sizeof buf, "%.17g", acc.KishEss());
   summary << "key\tvalue\nrows_used\t" << (N - first - skipped) << "\nrows_skipped_nonfinite\t" << skipped
           << "\nkish_ess\t" << buf << "\n";
+}
+
+
+// ---- K11: exact ancestral-state marginals along a seed's lineage ----
+
+namespace {
+std::string Fmt17(double v);  // (%.17g; defined with the codon tables below)
+}
+
+int PhyloHMM::SeedTip(const std::string& seed_seq) const {
+  Require(seed_seq != "naive", "the seed sequence cannot be 'naive': the lineage ends there");
+  const int T = (int)xmsa_labels_.size();
+  for (int v = 1; v < T; ++v)
+    if (xmsa_labels_[v] == seed_seq) return v;
+  throw std::runtime_error("the seed sequence '" + seed_seq + "' is not a sequence of this clonal family");
+}
+
+PhyloHMM::AncestralMarginalsResult PhyloHMM::AncestralMarginals(const std::string& seed_seq) {
+  Require(have_tree_, "InitializePhyloParameters must be called first");
+  const int seed_tip = SeedTip(seed_seq);
+  CreateFamily();
+  Require(device_sampler_, "the family has no device sampler tables (needed by the posterior kernel)");
+  const int T = tree_.n_tips, R = num_rates_;
+  const std::size_t L = (std::size_t)msa_.cols();
+  std::vector<int32_t> ops((std::size_t)(T - 2) * 4);
+  int32_t depth = 0;
+  CheckHip(lh_schedule_tree(T, tree_.children.data(), tree_.root, ops.data(), &depth), "lh_schedule_tree");
+  AncestralMarginalsResult res;
+  res.nodes = SeedPath(tree_.children.data(), T, tree_.root, seed_tip);
+  Require(!res.nodes.empty(), "the seed sequence '" + seed_seq + "' does not descend from the root");
+  const std::size_t P = res.nodes.size();
+  res.n_sites = (int)L;
+  res.num_rates = R;
+  res.marg.assign(P * L * 4, 0.0);
+  res.rate_post.assign(L * (std::size_t)R, 0.0);
+  lh_ancestral_outputs outs{};
+  outs.loglik = &res.loglik;
+  outs.marg = res.marg.data();
+  outs.rate_post = res.rate_post.data();
+  CheckHip(lh_eval_ancestral_batch(family_, 1, T, depth, ops.data(), tree_.brlen.data(), er_.data(), pi_.data(), &alpha_, R,
+                                   res.nodes.data(), (int32_t)P, &outs),
+           "lh_eval_ancestral_batch");
+  return res;
+}
+
+void PhyloHMM::WriteNodeTable(std::ostream& o, const double* table, std::size_t n_sites) {
+  static const char kBases[] = "ACGT";
+  o << "site\tA\tC\tG\tT\tmap_base\n";
+  for (std::size_t s = 0; s < n_sites; ++s) {
+    const double* p = table + s * 4;
+    o << s;
+    for (int c = 0; c < 4; ++c) o << '\t' << Fmt17(p[c]);
+    o << '\t' << kBases[std::max_element(p, p + 4) - p] << '\n';
+  }
+}
+
+void PhyloHMM::WriteRateTable(std::ostream& o, const double* rate_post, std::size_t n_sites, int num_rates) {
+  o << "site";
+  for (int k = 0; k < num_rates; ++k) o << "\trate" << k;
+  o << '\n';
+  for (std::size_t s = 0; s < n_sites; ++s) {
+    o << s;
+    for (int k = 0; k < num_rates; ++k) o << '\t' << Fmt17(rate_post[s * num_rates + k]);
+    o << '\n';
+  }
+}
+
+void PhyloHMM::RunAncestralMarginalsPipeline(const std::string& input_path, const std::string& seed_seq,
+                                             const std::string& output_prefix, int num_rates, double burnin_frac) {
+  Require(devices_.size() <= 1, "the ancestral marginals pipeline runs on one device: --devices may list only one");
+  Require(burnin_frac >= 0.0 && burnin_frac < 1.0, "burn-in fraction must be in [0, 1)");
+  const int seed_tip = SeedTip(seed_seq);
+  CreateFamily();
+  Require(device_sampler_, "the family has no device sampler tables (needed by the posterior kernel)");
+  const int T = (int)xmsa_labels_.size(), R = num_rates;
+  const std::size_t L = (std::size_t)msa_.cols();
+  TsvTable table = TsvTable::OpenRevBayesTable(input_path);
+  const std::size_t N = table.rows.size();
+  const std::size_t first = (std::size_t)std::floor(burnin_frac * (double)N);
+  // the rows' tables come back whole (32 P L bytes each, P <= T - 2): a batch is bounded by at most 512 MiB of them
+  const std::size_t NE = 2 * L * 4, NR = L * (std::size_t)R;
+  const std::size_t fit = std::max<std::size_t>(1, ((std::size_t)512 << 20) / (sizeof(double) * ((std::size_t)(T - 2) * L * 4 + NR)));
+  const std::size_t kBatch = host_options().pipeline_batch > 0 ? (std::size_t)host_options().pipeline_batch
+                                                                : std::min<std::size_t>(8192, fit);
+  // the rows' tables are added up on the host in row order: the files do not depend on the batch size
+  WeightedSums acc(NE + NR);
+  std::vector<double> marg, rate_post, row(NE + NR);
+  std::vector<double> lw(N - first);
+  std::vector<int32_t> path_len(N - first, 0);
+  std::size_t skipped = 0;
+  for (std::size_t off = first; off < N; off += kBatch) {
+    const std::size_t m = std::min(kBatch, N - off);
+    TableBatch tb = FlattenTable(table, off, off + m, false, true, input_path, true);
+    const DeviceBatch& b = tb.dev;
+    std::vector<std::vector<int32_t>> chain(m);
+    std::size_t P = 1;
+    for (std::size_t i = 0; i < m; ++i) {
+      chain[i] = SeedPath(tb.children.data() + i * 2 * (std::size_t)(T - 2), T, tb.root[i], seed_tip);
+      Require(!chain[i].empty(),
+              "row " + std::to_string(off + i) + ": the seed sequence '" + seed_seq + "' does not descend from the root");
+      P = std::max(P, chain[i].size());
+    }
+    std::vector<int32_t> path(m * P, -1);
+    for (std::size_t i = 0; i < m; ++i) std::copy(chain[i].begin(), chain[i].end(), path.begin() + i * P);
+    std::vector<double> ll(m);
+    marg.resize(m * P * L * 4);
+    rate_post.resize(m * NR);
+    lh_ancestral_outputs outs{};
+    outs.loglik = ll.data();
+    outs.marg = marg.data();
+    outs.rate_post = rate_post.data();
+    CheckHip(lh_eval_ancestral_batch(family_, b.n, b.n_tips, b.max_depth, b.ops.data(), b.brlen.data(), b.er.data(),
+                                     b.pi.data(), b.alpha.data(), R, path.data(), (int32_t)P, &outs),
+             "lh_eval_ancestral_batch");
+    for (std::size_t i = 0; i < m; ++i) {
+      const std::size_t u = off - first + i;
+      const double st[3] = {ll[i] - tb.lik[i], 1.0, 1.0};  // one row, its weight relative to itself
+      lw[u] = st[0];
+      path_len[u] = (int32_t)chain[i].size();
+      if (!std::isfinite(st[0])) {
+        ++skipped;
+        continue;
+      }
+      const double* mi = marg.data() + i * P * L * 4;
+      std::copy(mi, mi + L * 4, row.begin());                                                        // the seed's parent
+      std::copy(mi + (chain[i].size() - 1) * L * 4, mi + chain[i].size() * L * 4, row.begin() + L * 4);  // the MRCA
+      std::copy(rate_post.begin() + i * NR, rate_post.begin() + (i + 1) * NR, row.begin() + NE);
+      acc.Add(row.data(), st);
+    }
+  }
+  Require(acc.s1 > 0.0, "ancestral marginals pipeline: no row with a finite weight");
+  acc.Normalise();
+  std::ofstream parent(output_prefix + ".parent.tsv"), mrca(output_prefix + ".mrca.tsv"), rates(output_prefix + ".rates.tsv"),
+      rows(output_prefix + ".rows.tsv"), summary(output_prefix + ".summary.tsv");
+  Require(parent.good() && mrca.good() && rates.good() && rows.good() && summary.good(), "Can't write " + output_prefix + ".*.tsv");
+  WriteNodeTable(parent, acc.total.data(), L);
+  WriteNodeTable(mrca, acc.total.data() + L * 4, L);
+  WriteRateTable(rates, acc.total.data() + NE, L, R);
+  rows << "row\tweight\tchain_length\n";
+  for (std::size_t u = 0; u < lw.size(); ++u)
+    rows << (first + u) << '\t' << Fmt17(std::isfinite(lw[u]) ? std::exp(lw[u] - acc.mx) : 0.0) << '\t' << path_len[u] << '\n';
+  summary << "key\tvalue\nrows_used\t" << (N - first - skipped) << "\nrows_skipped_nonfinite\t" << skipped << "\nkish_ess\t"
+          << Fmt17(acc.KishEss()) << "\n";
 }
 
 

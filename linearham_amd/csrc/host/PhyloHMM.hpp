@@ -207,6 +207,30 @@ class PhyloHMM : public HMM {
   static void WriteDeletionTable(std::ostream& o, const EventsResult& m);
   static void WriteInsertionTable(std::ostream& o, const EventsResult& m);
   static void WriteSpanTable(std::ostream& o, const EventsResult& m);
+  /// K11: exact ancestral-state marginals along the lineage of the tip `seed_seq` (lh_eval_ancestral_batch).  Per lineage
+  /// slot -- slot 0 the seed's parent, the last one the MRCA (naive's neighbour) -- the node, its table [L][4] over
+  /// A, C, G, T, marginalised over the rate category and over the naive base, and the rate posterior [L][R].
+  struct AncestralMarginalsResult {
+    std::vector<int32_t> nodes;     // [P] the lineage: inner nodes in lh_schedule_tree's numbering
+    std::vector<double> marg;       // [P][L][4]
+    std::vector<double> rate_post;  // [L][R]
+    int n_sites = 0, num_rates = 0;
+    double loglik = 0.0;
+  };
+  /// After InitializePhyloParameters: the tables of the current tree.
+  AncestralMarginalsResult AncestralMarginals(const std::string& seed_seq);
+  /// The importance-weighted tables of the seed's parent and of the MRCA -- the two slots that mean the same in every
+  /// tree -- and of the rate posteriors over a RevBayes table, with RunMarginalsPipeline's reader, burn-in, weights
+  /// exp(LHLogLikelihood - Likelihood), Kish ESS and one-device rule.  The rows' tables are added up on the host in row
+  /// order, so the files do not depend on LH_PIPELINE_BATCH.  Writes <prefix>.parent.tsv and .mrca.tsv (site, four
+  /// probabilities, the arg-max base), .rates.tsv, .rows.tsv (row, weight, chain_length) and .summary.tsv.
+  void RunAncestralMarginalsPipeline(const std::string& input_path, const std::string& seed_seq,
+                                     const std::string& output_prefix, int num_rates, double burnin_frac);
+  /// site, A, C, G, T, map_base / site, rate0 ..; numbers printed with %.17g
+  static void WriteNodeTable(std::ostream& o, const double* table, std::size_t n_sites);
+  static void WriteRateTable(std::ostream& o, const double* rate_post, std::size_t n_sites, int num_rates);
+  /// The tip (1 .. T-1) of a sequence of the clonal family; throws for 'naive' and for names the family does not hold.
+  int SeedTip(const std::string& seed_seq) const;
   static void WriteSiteTable(std::ostream& o, const NaiveMarginalsResult& m);
   static void WriteGeneTable(std::ostream& o, const NaiveMarginalsResult& m);
   void SampleStatesWithWords(const uint32_t* words, int n_words, std::vector<int32_t>& device_states,

@@ -281,6 +281,42 @@ int lhh_run_marginals_pipeline(void* h, const char* input_path, const char* outp
   });
 }
 
+// linearham::SeedPath (no family, no device): path [cap >= n_tips - 2]; *n receives the length, 0 if the tip does not hang
+// below the root.
+int lhh_seed_path(const int32_t* children, int n_tips, int root, int seed_tip, int32_t* path, int cap, int* n) {
+  return Guard([&] {
+    const std::vector<int32_t> c = linearham::SeedPath(children, n_tips, root, seed_tip);
+    if ((int)c.size() > cap) throw std::runtime_error("lhh_seed_path: output too small");
+    std::copy(c.begin(), c.end(), path);
+    *n = (int)c.size();
+  });
+}
+
+// PhyloHMM::AncestralMarginals: nodes [cap_slots], marg [cap_slots][L][4], rate_post [L][R]; *n_slots receives the chain's
+// length, *num_rates R.  marg == NULL: only those two.
+int lhh_phylo_ancestral_marginals(void* h, const char* seed_seq, int32_t* nodes, double* marg, double* rate_post,
+                                  int cap_slots, int* n_slots, int* num_rates, double* loglik) {
+  return Guard([&] {
+    const PhyloHMM::AncestralMarginalsResult r = dynamic_cast<PhyloHMM&>(*static_cast<HMM*>(h)).AncestralMarginals(seed_seq);
+    *n_slots = (int)r.nodes.size();
+    *num_rates = r.num_rates;
+    if (!marg) return;
+    if ((int)r.nodes.size() > cap_slots) throw std::runtime_error("lhh_phylo_ancestral_marginals: output too small");
+    std::copy(r.nodes.begin(), r.nodes.end(), nodes);
+    std::copy(r.marg.begin(), r.marg.end(), marg);
+    if (rate_post) std::copy(r.rate_post.begin(), r.rate_post.end(), rate_post);
+    if (loglik) *loglik = r.loglik;
+  });
+}
+
+int lhh_run_ancestral_marginals_pipeline(void* h, const char* input_path, const char* seed_seq, const char* output_prefix,
+                                         int num_rates, double burnin_frac) {
+  return Guard([&] {
+    dynamic_cast<PhyloHMM&>(*static_cast<HMM*>(h)).RunAncestralMarginalsPipeline(input_path, seed_seq, output_prefix, num_rates,
+                                                                               burnin_frac);
+  });
+}
+
 // PhyloHMM::NaiveCodonMarginals: table [cap_codons][125]; *n_codons receives the count; the amino-acid table
 // (WriteAminoAcidTable) in *aa.  table == NULL: only *n_codons, nothing is evaluated.
 int lhh_phylo_codon_marginals(void* h, int frame, double* table, int cap_codons, int* n_codons, const char** aa) {

@@ -65,7 +65,7 @@ int main(int argc, char** argv) {
   try {
     if (argc < 2 || std::string(argv[1]) == "-h" || std::string(argv[1]) == "--help") {
       std::cout << "A Phylo-HMM implementation for B cell receptor sequence analysis.\n"
-                   "USAGE: linearham {--compute-logl|--sample|--pipeline|--asr|--marginals|--marginals-pipeline|--naive-probs|--naive-probs-pipeline|--lineage-pipeline|--weighted-lineage-pipeline|--viterbi|--annotations-pipeline|--codon-marginals|--codon-marginals-pipeline|--events|--events-pipeline} --yaml-path <string> "
+                   "USAGE: linearham {--compute-logl|--sample|--pipeline|--asr|--marginals|--marginals-pipeline|--naive-probs|--naive-probs-pipeline|--lineage-pipeline|--weighted-lineage-pipeline|--viterbi|--annotations-pipeline|--codon-marginals|--codon-marginals-pipeline|--events|--events-pipeline|--ancestral-marginals|--ancestral-marginals-pipeline} --yaml-path <string> "
                    "--cluster-ind <int> --hmm-param-dir <string> [--seed <int>] [--num-rates <int>] [--extended-range <0|1>] "
                    "[--devices <a,b,...>] ...\n"
                    "  --marginals: the arguments of --compute-logl; prints the per-site naive-base table and the gene table\n"
@@ -89,6 +89,12 @@ int main(int argc, char** argv) {
                    "    length), of the insertion lengths and of the junction spans for that tree\n"
                    "  --events-pipeline --input-path <RevBayes table> --output-path <prefix> [--burnin-frac <f>]: writes\n"
                    "    <prefix>.deletions.tsv, <prefix>.insertions.tsv, <prefix>.spans.tsv and <prefix>.summary.tsv (one device)\n"
+                   "  --ancestral-marginals --seed-seq <name>: the arguments of --marginals; prints, per node on the way from the\n"
+                   "    sequence <name> to naive (slot 0 its parent, the last slot the MRCA), the exact per-site table of the node's\n"
+                   "    base, then the per-site posterior of the rate category\n"
+                   "  --ancestral-marginals-pipeline --input-path <RevBayes table> --output-path <prefix> --seed-seq <name>\n"
+                   "    [--burnin-frac <f>]: writes <prefix>.parent.tsv, <prefix>.mrca.tsv, <prefix>.rates.tsv, <prefix>.rows.tsv\n"
+                   "    and <prefix>.summary.tsv (one device)\n"
                    "  --lineage-pipeline --input-path <--pipeline table> --output-path <prefix> --seed-seq <name> [--seed <int>]:\n"
                    "    the lineage tables of the sequence <name>: <prefix>.fasta, .dnamap, .nodes.tsv, .edges.tsv, .summary.tsv\n"
                    "       linearham --lineage-trees --input-path <--asr trees> --output-path <prefix> --seed-seq <name>\n"
@@ -116,7 +122,8 @@ int main(int argc, char** argv) {
         subcmd != "--marginals" && subcmd != "--marginals-pipeline" && subcmd != "--naive-probs" &&
         subcmd != "--naive-probs-pipeline" && subcmd != "--lineage-pipeline" && subcmd != "--weighted-lineage-pipeline" &&
         subcmd != "--viterbi" && subcmd != "--annotations-pipeline" && subcmd != "--codon-marginals" &&
-        subcmd != "--codon-marginals-pipeline" && subcmd != "--events" && subcmd != "--events-pipeline")
+        subcmd != "--codon-marginals-pipeline" && subcmd != "--events" && subcmd != "--events-pipeline" &&
+        subcmd != "--ancestral-marginals" && subcmd != "--ancestral-marginals-pipeline")
       throw std::invalid_argument("'" + subcmd + "' is not a valid subcommand.");
     const std::string yaml_path = a.one("yaml-path");
     const int cluster_ind = std::stoi(a.one("cluster-ind"));
@@ -136,7 +143,8 @@ int main(int argc, char** argv) {
       }
       if (device_list.size() > 1 && (subcmd == "--marginals-pipeline" || subcmd == "--naive-probs-pipeline" ||
                                      subcmd == "--weighted-lineage-pipeline" || subcmd == "--annotations-pipeline" ||
-                                     subcmd == "--codon-marginals-pipeline" || subcmd == "--events-pipeline"))
+                                     subcmd == "--codon-marginals-pipeline" || subcmd == "--events-pipeline" ||
+                                     subcmd == "--ancestral-marginals-pipeline"))
         throw std::invalid_argument(subcmd + " runs on one device: --devices may list only one");
       if (device_list.size() > 1 && subcmd != "--pipeline")
         std::fprintf(stderr, "linearham: %s evaluates on one device; of --devices only device %d is used\n", subcmd.c_str(),
@@ -184,6 +192,11 @@ int main(int argc, char** argv) {
     }
     if (subcmd == "--events-pipeline") {
       phylo_hmm_ptr->RunEventsPipeline(a.one("input-path"), a.one("output-path"), num_rates, std::stod(a.opt("burnin-frac", "0")));
+      return EXIT_SUCCESS;
+    }
+    if (subcmd == "--ancestral-marginals-pipeline") {
+      phylo_hmm_ptr->RunAncestralMarginalsPipeline(a.one("input-path"), a.one("seed-seq"), a.one("output-path"), num_rates,
+                                                   std::stod(a.opt("burnin-frac", "0")));
       return EXIT_SUCCESS;
     }
     if (subcmd == "--naive-probs-pipeline") {
@@ -244,6 +257,15 @@ int main(int argc, char** argv) {
       linearham::PhyloHMM::WriteInsertionTable(std::cout, m);
       std::cout << "\n";
       linearham::PhyloHMM::WriteSpanTable(std::cout, m);
+    } else if (subcmd == "--ancestral-marginals") {
+      const linearham::PhyloHMM::AncestralMarginalsResult m = phylo_hmm_ptr->AncestralMarginals(a.one("seed-seq"));
+      const std::size_t L = (std::size_t)m.n_sites;
+      for (std::size_t s = 0; s < m.nodes.size(); ++s) {
+        std::cout << "slot\t" << s << "\tnode\t" << m.nodes[s] << "\n";
+        linearham::PhyloHMM::WriteNodeTable(std::cout, m.marg.data() + s * L * 4, L);
+        std::cout << "\n";
+      }
+      linearham::PhyloHMM::WriteRateTable(std::cout, m.rate_post.data(), L, m.num_rates);
     } else if (subcmd == "--marginals") {
       const linearham::PhyloHMM::NaiveMarginalsResult m = phylo_hmm_ptr->NaiveMarginals();
       linearham::PhyloHMM::WriteSiteTable(std::cout, m);

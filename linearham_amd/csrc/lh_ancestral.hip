@@ -1,0 +1,483 @@
+// K11: exact ancestral-state marginals along a seed's lineage (gfx950).
+//
+// What K3 (lh_asr.hip) draws and K7 counts, as probabilities: for every node v_s of the lineage path (slot 0 = the seed's
+// parent, the last slot = the root, naive's neighbour) and every alignment site j
+//   marg[s][j][c] = P(x_{v_s, j} = c | data) = sum_b q_j(b) sum_r [lik_r(j, b) / Z_j(b)] P(x = c | column j, naive_j = b, rate r),
+// q_j = the posterior of the naive base (a one-hot row conditions on a fixed naive sequence, K3's setting), lik_r = K1's
+// unmixed per-rate planes, Z_j(b) = sum_r lik_r(j, b).  The joint P(x = c, column | b, r) is linear in the naive tip's
+// vector, so with t_j(b) = q_j(b) / Z_j(b) one down pass per (site, rate) serves all five naive bases:
+//   rho_r(j) = sum_b t_j(b) lik_r(j, b)                                   the rate posterior (sums to 1 over r)
+//   A_{P-1}(i) = pi_i (sum_{b<4} P_naive[i][b] t_j(b) + t_j(N) rowsum_i)  the message into the root from above
+//   post_s(c) = A_s(c) L_{v_s}(c)
+//   A_{s-1}(c) = sum_i A_s(i) (P_{w_s} L_{w_s})(i) P_{v_{s-1}}[i][c]      w_s = the child of v_s off the path
+//   marg[s][j][c] = sum_r rho_r(j) post_s^(r)(c) / sum_c' post_s^(r)(c')
+// Normalising per (slot, site, rate) before the weighting makes the result independent of every rescaling of the CLVs.
+//
+// Kernels:
+//  * K11a (site_base_kernel), a thread per (sample, site): K5's posterior (compact forward layout) pushed onto (site, base).
+//    Every compact entry writes its naive base on its sites (a germline gene on all of its sites, a junction entry on its
+//    row's site); the table, built once per family, lists per (site, base) the entries that write it, in ascending order,
+//    so a cell is a sum in a fixed order.  What no state writes stays N: N takes 1 - (the five sums).  A row without a
+//    posterior (non-finite log-likelihood) is NaN.
+//  * K11r (anc_rate_kernel), a thread per (sample, site): t_j[5] and rho_j[R] from the planes, scaler counts aligned to the
+//    smallest as K3a does.
+//  * K3s (lh_asr.hip) writes the schedule descriptors; K11c (anc_chain_kernel), a workgroup per sample, checks the path against
+//    them -- entries outside T .. 2T-3 are padding and come last, each entry is a child of the next, the last one is the
+//    root -- and writes per slot the op that produced the node and which of that op's children continues the path.  No index
+//    is formed from a path entry before it is checked.  A path that fails leaves length 0: the sample's row is NaN and the
+//    handle's error word is raised.
+//  * K11b (anc_kernel), a workgroup per (rate category, sample) so that P-matrices are wave-uniform: K3b's LDS tables (tip
+//    table, inner P-matrices by op), K3b's upward pass over ALL site patterns of the family (a lane per pattern, every
+//    inner CLV stored: clv[sample][rate][op][2][pattern] of 16-byte entries), then the downward pass along the path, a lane
+//    per site: P mat-vecs, not T - 2.  The message from above is divided by its largest entry after every step (a CLV's
+//    largest entry lies anywhere in [2^-256, 1], so a few unnormalised steps would underflow).  The lane writes
+//    rho_r * post / sum into part[sample][rate][slot][site][4].
+//  * K11m (anc_combine_kernel), a thread per (sample, slot, site): the R partial tables added in rate order -- fixed order,
+//    no atomics, the same bits whatever the batch.
+// No private array is reached by a dynamic index: 4-vectors are indexed by unrolled loops only.
+#include "lh_device.h"
+
+namespace lh {
+
+namespace {
+
+__device__ __forceinline__ void anc_tip_col(const double* tiptab, int tip, int st, double (&c)[4]) {
+  const double* t = tiptab + tip * 16;
+  if (st < 4) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) c[i] = t[st * 4 + i];
+  } else {  // N: row sums of P, as K3
+#pragma unroll
+    for (int i = 0; i < 4; ++i) c[i] = ((t[i] + t[4 + i]) + t[8 + i]) + t[12 + i];
+  }
+}
+
+// x = P a, P row-major in LDS at a wave-uniform address
+__device__ __forceinline__ void anc_matvec(const double* p, const double (&a)[4], double (&x)[4]) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) x[i] = fma(p[i * 4 + 3], a[3], fma(p[i * 4 + 2], a[2], fma(p[i * 4 + 1], a[1], p[i * 4] * a[0])));
+}
+
+// x = a^T P
+__device__ __forceinline__ void anc_vecmat(const double* p, const double (&a)[4], double (&x)[4]) {
+#pragma unroll
+  for (int c = 0; c < 4; ++c) x[c] = fma(p[12 + c], a[3], fma(p[8 + c], a[2], fma(p[4 + c], a[1], p[c] * a[0])));
+}
+
+__device__ __forceinline__ double anc_aligned(double v, int d) {
+  for (int q = 0; q < d && v != 0.0; ++q) v *= kScaleThreshold;
+  return v;
+}
+
+// K11a
+__global__ void __launch_bounds__(256) site_base_kernel(int n, int L, size_t forward_size, const int32_t* __restrict__ off,
+                                                        const int32_t* __restrict__ idx, const double* __restrict__ post,
+                                                        const double* __restrict__ loglik, double* __restrict__ out) {
+  const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (gid >= (long long)n * L) return;
+  const int sample = (int)(gid / L), j = (int)(gid - (long long)sample * L);
+  double* __restrict__ o = out + (size_t)gid * 5;
+  if (!isfinite(loglik[sample])) {
+#pragma unroll
+    for (int b = 0; b < 5; ++b) o[b] = __builtin_nan("");
+    return;
+  }
+  const double* __restrict__ p = post + (size_t)sample * forward_size;
+  const int32_t* __restrict__ oj = off + (size_t)j * 5;
+  double s[5];
+#pragma unroll
+  for (int b = 0; b < 5; ++b) {
+    double acc = 0.0;
+    for (int x = oj[b]; x < oj[b + 1]; ++x) acc += p[idx[x]];
+    s[b] = acc;
+  }
+  s[4] += 1.0 - ((((s[0] + s[1]) + s[2]) + s[3]) + s[4]);
+#pragma unroll
+  for (int b = 0; b < 5; ++b) o[b] = s[b];
+}
+
+// The two slots that mean the same in every tree, for the weighted reduction: ends[sample][0] = slot 0 (the seed's parent),
+// ends[sample][1] = the sample's last slot (the MRCA); and the log-likelihood the weights are formed from, NaN for a
+// sample without a path, so that its NaN row is left out.
+__global__ void __launch_bounds__(256) anc_ends_kernel(int n, int P, int L, const int32_t* __restrict__ plen,
+                                                       const double* __restrict__ marg, const double* __restrict__ loglik,
+                                                       double* __restrict__ ends, double* __restrict__ ll_used) {
+  const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long long per = 2ll * L * 4;
+  if (gid >= (long long)n * per) return;
+  const int sample = (int)(gid / per);
+  const int cell = (int)(gid - (long long)sample * per);
+  const int which = cell / (L * 4), rest = cell - which * (L * 4);
+  const int len = plen[sample];
+  const int slot = which == 0 ? 0 : max(len - 1, 0);
+  if (ends) ends[gid] = marg[((size_t)sample * P + slot) * L * 4 + rest];
+  if (cell == 0) ll_used[sample] = len == 0 ? __builtin_nan("") : loglik[sample];
+}
+
+// K11r.  t = q / Z where q != 0 (a NaN q stays NaN), 0 where q == 0 -- also where Z == 0.
+__global__ void __launch_bounds__(256) anc_rate_kernel(int n, int R, int L, int n_prune, const int32_t* __restrict__ site_pat,
+                                                       const double* __restrict__ site_lik,
+                                                       const int32_t* __restrict__ site_scal,
+                                                       const double* __restrict__ naive_prob,
+                                                       const double* __restrict__ pi, double* __restrict__ tvec,
+                                                       double* __restrict__ rho) {
+  const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (gid >= (long long)n * L) return;
+  const int sample = (int)(gid / L), j = (int)(gid - (long long)sample * L);
+  const int pat = site_pat[j];
+  const double* __restrict__ q = naive_prob + (size_t)gid * 5;
+  double* __restrict__ t_out = tvec + (size_t)gid * 5;
+  double* __restrict__ r_out = rho + (size_t)gid * R;
+  double t[5];
+  if (pat >= n_prune) {
+    // all-N column: K1 has no plane for it.  In the planes' units (sum_i pi_i L_root(i) P_naive[i][b], L_root all ones) its
+    // likelihood is pi_b under a naive base b, by stationarity, and sum_i pi_i under N (1 up to the digits pi was given
+    // with), whatever the category.
+    const double* __restrict__ p4 = pi + (size_t)sample * 4;
+    const double psum = ((p4[0] + p4[1]) + p4[2]) + p4[3];
+    double total = 0.0;
+#pragma unroll
+    for (int b = 0; b < 5; ++b) {
+      const double qb = q[b];
+      t[b] = qb == 0.0 ? 0.0 : qb / ((double)R * (b < 4 ? p4[b] : psum));
+      total += qb == 0.0 ? 0.0 : qb / (double)R;
+    }
+#pragma unroll
+    for (int b = 0; b < 5; ++b) t_out[b] = t[b];
+    for (int k = 0; k < R; ++k) r_out[k] = total;
+    return;
+  }
+  const int32_t* sc = site_scal + (size_t)sample * R * n_prune + pat;
+  const double* lk = site_lik + (size_t)sample * R * 5 * n_prune + pat;
+  int smin = 0x7fffffff;
+  for (int k = 0; k < R; ++k) smin = min(smin, sc[(size_t)k * n_prune]);
+  double z[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int k = 0; k < R; ++k) {
+    const int d = sc[(size_t)k * n_prune] - smin;
+#pragma unroll
+    for (int b = 0; b < 5; ++b) z[b] += anc_aligned(lk[((size_t)k * 5 + b) * n_prune], d);
+  }
+#pragma unroll
+  for (int b = 0; b < 5; ++b) {
+    const double qb = q[b];
+    t[b] = qb == 0.0 ? 0.0 : qb / z[b];
+    t_out[b] = t[b];
+  }
+  for (int k = 0; k < R; ++k) {
+    const int d = sc[(size_t)k * n_prune] - smin;
+    double acc = 0.0;
+#pragma unroll
+    for (int b = 0; b < 5; ++b) {
+      const double v = anc_aligned(lk[((size_t)k * 5 + b) * n_prune], d);
+      if (t[b] != 0.0) acc += t[b] * v;
+    }
+    r_out[k] = acc;
+  }
+}
+
+// K11c.  chain[sample][s] = op that produced v_s | (1 << 30 if v_{s-1} is the child that op popped, else its accumulator
+// child); plen[sample] = the path's length, 0 if the sample has no valid path (or K0c rejected its schedule).
+__global__ void __launch_bounds__(64) anc_chain_kernel(int T, int P, const AsrOp* __restrict__ desc,
+                                                       const int4* __restrict__ hdr, const int32_t* __restrict__ path,
+                                                       int32_t* __restrict__ chain, int32_t* __restrict__ plen,
+                                                       int32_t* err_flag) {
+  extern __shared__ int32_t chain_smem[];
+  const int sample = blockIdx.x, tid = threadIdx.x, n_ops = T - 2;
+  if (hdr[sample].w != 0) {  // (K0c has raised the error word)
+    if (tid == 0) plen[sample] = 0;
+    return;
+  }
+  int32_t* op_of_node = chain_smem;  // [n_ops]
+  const AsrOp* __restrict__ dsc = desc + (size_t)sample * n_ops;
+  for (int k = tid; k < n_ops; k += blockDim.x) op_of_node[k] = -1;
+  __syncthreads();
+  for (int k = tid; k < n_ops; k += blockDim.x) {
+    const int z = dsc[k].b.z;
+    if (z >= 0 && z < n_ops) op_of_node[z] = k;
+  }
+  __syncthreads();
+  if (tid != 0) return;
+  const int32_t* __restrict__ p = path + (size_t)sample * P;
+  int32_t* __restrict__ ch = chain + (size_t)sample * P;
+  bool ok = true, ended = false;
+  int len = 0;
+  for (int s = 0; s < P; ++s) {
+    const int v = p[s];
+    if (v < T || v > 2 * T - 3)
+      ended = true;
+    else if (ended)
+      ok = false;
+    else
+      ++len;
+  }
+  ok = ok && len >= 1;
+  int prev = -1;
+  for (int s = 0; s < len && ok; ++s) {
+    const int k = op_of_node[p[s] - T];
+    if (k < 0) {
+      ok = false;
+      break;
+    }
+    int word = k;
+    if (s > 0) {
+      const int4 a = dsc[k].a;
+      const int kind = a.x & 15;
+      if (kind != OP_CHERRY && prev == k - 1) {
+      } else if (kind == OP_POP_ACC && a.w == prev) {
+        word |= 1 << 30;
+      } else {
+        ok = false;
+      }
+    }
+    ch[s] = word;
+    prev = k;
+  }
+  ok = ok && prev == n_ops - 1;  // the last entry is the root
+  plen[sample] = ok ? len : 0;
+  if (!ok) atomicOr(err_flag, 2);  // bit 1: a path, bit 0: a schedule (K0c)
+}
+
+// K11b
+__global__ void __launch_bounds__(256) anc_kernel(int R, int T, int L, int n_prune, int P, const uint8_t* __restrict__ msa,
+                                                  const int32_t* __restrict__ site_pat, const AsrOp* __restrict__ desc,
+                                                  const double* __restrict__ brlen, const double* __restrict__ rates,
+                                                  const double* __restrict__ eig, const double* __restrict__ pi,
+                                                  const double* __restrict__ tvec, const double* __restrict__ rho,
+                                                  const int32_t* __restrict__ chain, const int32_t* __restrict__ plen,
+                                                  double2* clv, int Lp, double* __restrict__ part) {
+  extern __shared__ double2 anc_smem[];
+  const int n_ops = T - 2;
+  const int sample = blockIdx.y, rate = blockIdx.x;
+  const int len = plen[sample];
+  if (len == 0) return;  // K11m writes the row's NaN
+  const int NP = n_prune + 1;  // patterns, the all-N one (id n_prune) included
+  double* tiptab = reinterpret_cast<double*>(anc_smem);  // [T][4][4] columns of P
+  double* pin = tiptab + (size_t)T * 16;                 // [n_ops][4][4] row-major, by the op that produced the child
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int n_waves = blockDim.x >> 6;
+  const AsrOp* __restrict__ dsc = desc + (size_t)sample * n_ops;
+  const double* __restrict__ e = eig + (size_t)sample * 36;
+  const double rt = rates[(size_t)sample * R + rate];
+  const double* __restrict__ bl = brlen + (size_t)sample * (2 * (size_t)T - 2);
+  {
+    double Pm[4][4];
+    for (int j = tid; j < T + n_ops - 1; j += blockDim.x) {
+      if (j < T) {
+        compute_pmatrix(e, bl[j] * rt, Pm);
+        double* o = tiptab + j * 16;
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+          for (int st = 0; st < 4; ++st) o[st * 4 + i] = Pm[i][st];
+      } else {
+        const int k = j - T;  // op k < n_ops - 1 produced inner node T + b.z, whose branch this is
+        compute_pmatrix(e, bl[T + dsc[k].b.z] * rt, Pm);
+        double* o = pin + (size_t)k * 16;
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+          for (int q = 0; q < 4; ++q) o[i * 4 + q] = Pm[i][q];
+      }
+    }
+  }
+  __syncthreads();
+
+  // CLV area of this (sample, rate): [op][2][Lp] double2, components (0,1) and (2,3) of a pattern in two planes
+  const size_t plane = (size_t)Lp;
+  double2* clv_s = clv + ((size_t)sample * R + rate) * n_ops * 2 * plane;
+
+  // ---- upward pass, a lane per pattern (lanes past the last pattern repeat it: same values, no predicate)
+  for (int s0 = wave * 64; s0 < NP; s0 += n_waves * 64) {
+    const int pat = min(s0 + lane, NP - 1);
+    const bool all_n = pat >= n_prune;
+    double a[4] = {1.0, 1.0, 1.0, 1.0};
+    for (int k = 0; k < n_ops; ++k) {
+      const int4 da = dsc[k].a, db = dsc[k].b;
+      const int kind = da.x & 15;
+      double u[4], v[4];
+      if (kind == OP_CHERRY) {
+        const int sa = all_n ? 4 : (int)msa[(size_t)da.y * n_prune + pat];
+        const int sb = all_n ? 4 : (int)msa[(size_t)da.z * n_prune + pat];
+        anc_tip_col(tiptab, db.x, sa, u);
+        anc_tip_col(tiptab, db.y, sb, v);
+      } else {
+        anc_matvec(pin + (size_t)(k - 1) * 16, a, v);
+        if (kind == OP_TIP_ACC) {
+          const int sa = all_n ? 4 : (int)msa[(size_t)da.y * n_prune + pat];
+          anc_tip_col(tiptab, db.x, sa, u);
+        } else {
+          const double2* cq = clv_s + (size_t)da.w * 2 * plane + pat;
+          const double2 lo = cq[0], hi = cq[plane];
+          const double y[4] = {lo.x, lo.y, hi.x, hi.y};
+          anc_matvec(pin + (size_t)da.w * 16, y, u);
+        }
+      }
+#pragma unroll
+      for (int q = 0; q < 4; ++q) a[q] = u[q] * v[q];
+      if (fmax(fmax(a[0], a[1]), fmax(a[2], a[3])) < kScaleThreshold) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) a[q] *= kScaleFactor;
+      }
+      double2* ck = clv_s + (size_t)k * 2 * plane + pat;
+      ck[0] = make_double2(a[0], a[1]);
+      ck[plane] = make_double2(a[2], a[3]);
+    }
+  }
+  // the sites' lanes below read CLVs that other lanes and waves of this workgroup stored above
+  __threadfence_block();
+  __syncthreads();
+
+  // ---- downward pass along the path, a lane per site
+  const double* __restrict__ p4 = pi + (size_t)sample * 4;
+  const int32_t* __restrict__ ch = chain + (size_t)sample * P;
+  double* part_s = part + ((size_t)sample * R + rate) * (size_t)P * L * 4;
+  for (int s0 = wave * 64; s0 < L; s0 += n_waves * 64) {
+    const bool live = s0 + lane < L;
+    const int site = min(s0 + lane, L - 1);
+    const int pat = min(site_pat[site], n_prune);
+    const bool all_n = pat >= n_prune;
+    const double2* cbase = clv_s + pat;
+    const double* __restrict__ tj = tvec + ((size_t)sample * L + site) * 5;
+    const double rj = rho[((size_t)sample * L + site) * R + rate];
+    double A[4];
+    {
+      double n4[4];
+      anc_tip_col(tiptab, 0, 4, n4);
+      const double t0 = tj[0], t1 = tj[1], t2 = tj[2], t3 = tj[3], t4 = tj[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        A[i] = p4[i] * (t0 * tiptab[i] + t1 * tiptab[4 + i] + t2 * tiptab[8 + i] + t3 * tiptab[12 + i] + t4 * n4[i]);
+    }
+    for (int s = len - 1; s >= 0; --s) {
+      const int word = ch[s];
+      const int k = word & 0x3fffffff;
+      const double2* cv = cbase + (size_t)k * 2 * plane;
+      const double2 lo = cv[0], hi = cv[plane];
+      const double post[4] = {A[0] * lo.x, A[1] * lo.y, A[2] * hi.x, A[3] * hi.y};
+      const double sum = (post[0] + post[1]) + (post[2] + post[3]);
+      // a category with rho = 0 or an all-zero post contributes 0, not NaN
+      const double f = (sum == 0.0 || rj == 0.0) ? 0.0 : rj / sum;
+      if (live) {
+        double2* o = reinterpret_cast<double2*>(part_s + ((size_t)s * L + site) * 4);
+        o[0] = make_double2(f == 0.0 ? 0.0 : f * post[0], f == 0.0 ? 0.0 : f * post[1]);
+        o[1] = make_double2(f == 0.0 ? 0.0 : f * post[2], f == 0.0 ? 0.0 : f * post[3]);
+      }
+      if (s == 0) break;
+      // the message into v_{s-1}: the sibling off the path times the message from above, through v_{s-1}'s branch
+      const int4 da = dsc[k].a, db = dsc[k].b;
+      const int kind = da.x & 15;
+      const bool via_pop = (word >> 30) != 0;
+      double m[4];
+      int kc = k - 1;  // the op that produced v_{s-1}
+      if (kind == OP_TIP_ACC) {
+        const int sa = all_n ? 4 : (int)msa[(size_t)da.y * n_prune + pat];
+        anc_tip_col(tiptab, db.x, sa, m);
+      } else {
+        const int kw = via_pop ? k - 1 : da.w;  // the op that produced the sibling
+        kc = via_pop ? da.w : k - 1;
+        const double2* cw = cbase + (size_t)kw * 2 * plane;
+        const double2 wlo = cw[0], whi = cw[plane];
+        const double y[4] = {wlo.x, wlo.y, whi.x, whi.y};
+        anc_matvec(pin + (size_t)kw * 16, y, m);
+      }
+      double M[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) M[i] = A[i] * m[i];
+      anc_vecmat(pin + (size_t)kc * 16, M, A);
+      const double top = fmax(fmax(A[0], A[1]), fmax(A[2], A[3]));
+      if (top > 0.0 && top < INFINITY) {
+        const double inv = 1.0 / top;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) A[i] *= inv;
+      }
+    }
+  }
+}
+
+// K11m
+__global__ void __launch_bounds__(256) anc_combine_kernel(int n, int R, int P, int L, const int32_t* __restrict__ plen,
+                                                          const double* __restrict__ part, double* __restrict__ marg) {
+  const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long long per = (long long)P * L;
+  if (gid >= (long long)n * per) return;
+  const int sample = (int)(gid / per);
+  const long long cell = gid - (long long)sample * per;  // slot * L + site
+  const int s = (int)(cell / L);
+  const int len = plen[sample];
+  double2 lo = make_double2(0.0, 0.0), hi = lo;
+  if (len == 0) {
+    lo = hi = make_double2(__builtin_nan(""), __builtin_nan(""));
+  } else if (s < len) {
+    for (int k = 0; k < R; ++k) {
+      const double2* p = reinterpret_cast<const double2*>(part + (((size_t)sample * R + k) * per + cell) * 4);
+      const double2 a = p[0], b = p[1];
+      lo.x += a.x;
+      lo.y += a.y;
+      hi.x += b.x;
+      hi.y += b.y;
+    }
+  }
+  double2* o = reinterpret_cast<double2*>(marg + (size_t)gid * 4);
+  o[0] = lo;
+  o[1] = hi;
+}
+
+size_t anc_lp(int n_prune) { return ((size_t)n_prune + 1 + 7) & ~(size_t)7; }
+
+}  // namespace
+
+void launch_site_base(int n, int L, size_t forward_size, const int32_t* off, const int32_t* idx, const double* post,
+                      const double* loglik, double* site_base, hipStream_t stream) {
+  const long long cells = (long long)n * L;
+  hipLaunchKernelGGL(site_base_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, stream, n, L, forward_size, off,
+                     idx, post, loglik, site_base);
+}
+
+void launch_ancestral_ends(int n, int P, int L, const int32_t* plen, const double* marg, const double* loglik, double* ends,
+                           double* ll_used, hipStream_t stream) {
+  const long long cells = (long long)n * 2 * L * 4;
+  hipLaunchKernelGGL(anc_ends_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, stream, n, P, L, plen, marg, loglik,
+                     ends, ll_used);
+}
+
+size_t anc_lds_bytes(int T) { return ((size_t)T + (size_t)(T - 2)) * 16 * sizeof(double); }
+
+AncWsBytes anc_ws_bytes(int T, int L, int R, int n_prune, int P) {
+  AncWsBytes b;
+  b.clv = sizeof(double2) * (size_t)R * (T - 2) * 2 * anc_lp(n_prune);
+  b.part = sizeof(double) * (size_t)R * P * L * 4;
+  b.tvec = sizeof(double) * (size_t)L * 5;
+  b.rho = sizeof(double) * (size_t)L * R;
+  b.chain = sizeof(int32_t) * (size_t)P;
+  return b;
+}
+
+int launch_ancestral(const DevFamily& fam, int n, int R, int T, const int32_t* ops, const double* brlen, const double* rates,
+                     const double* eig, const double* pi, const double* site_lik, const int32_t* site_scal,
+                     const double* naive_prob, const int32_t* path, int P, const AncWs& ws, double* marg, double* rate_post,
+                     const int4* hdr, int32_t* err_flag, hipStream_t stream) {
+  const int L = fam.n_sites;
+  if (n < 1 || n > 65535 || L < 1 || P < 1) return 1;  // (one grid row per sample)
+  const size_t lds = anc_lds_bytes(T);
+  if (lds > 160 * 1024) return 1;
+  double* rho = rate_post ? rate_post : ws.rho;
+  const long long cells = (long long)n * L;
+  hipLaunchKernelGGL(anc_rate_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, stream, n, R, L, fam.n_prune,
+                     fam.site_pat, site_lik, site_scal, naive_prob, pi, ws.tvec, rho);
+  if (!marg) return 0;
+  launch_asr_sched(n, T, ops, hdr, ws.desc, stream);
+  hipLaunchKernelGGL(anc_chain_kernel, dim3(n), dim3(64), sizeof(int32_t) * (size_t)(T - 2), stream, T, P,
+                     static_cast<const AsrOp*>(ws.desc), hdr, path, ws.chain, ws.plen, err_flag);
+  if (lds > 64 * 1024)
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(anc_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL(anc_kernel, dim3(R, n), dim3(256), lds, stream, R, T, L, fam.n_prune, P, fam.msa, fam.site_pat,
+                     static_cast<const AsrOp*>(ws.desc), brlen, rates, eig, pi, ws.tvec, rho, ws.chain, ws.plen,
+                     reinterpret_cast<double2*>(ws.clv), (int)anc_lp(fam.n_prune), ws.part);
+  const long long out = (long long)n * P * L;
+  hipLaunchKernelGGL(anc_combine_kernel, dim3((unsigned)((out + 255) / 256)), dim3(256), 0, stream, n, R, P, L, ws.plen,
+                     ws.part, marg);
+  return 0;
+}
+
+}  // namespace lh

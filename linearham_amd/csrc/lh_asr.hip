@@ -110,17 +110,6 @@ size_t asr_lds_bytes(int T, int L, int R, int n_prune) {
   return b;
 }
 
-// One schedule op as the sampling kernel reads it (two int4, fetched with scalar loads): everything that K3b
-// would otherwise have to derive per op from the K1 schedule with dependent look-ups.
-//   a.x  kind | stack slot of the op << 4 | (slot + 1 the NEXT op pushes the accumulator to, or 0) << 8
-//   a.y  MSA row of tip child y (cherry, tip-acc), else 0        a.z  MSA row of tip child z (cherry), else 0
-//   a.w  op that produced the sibling a pop op takes from the stack, else 0
-//   b.x  tip id y (tip table row)   b.y  tip id z   b.z  inner node (minus T) this op produces
-//   b.w  inner node (minus T) of the popped sibling (pop), else 0
-struct AsrOp {
-  int4 a, b;
-};
-
 // K3a: the rate category of every (sample, site): one thread each.  Weights = K1's per-rate column
 // likelihoods for the site's naive base, scalers aligned to the smallest (the arithmetic of K2a's mixture).
 __global__ void __launch_bounds__(256) asr_rate_kernel(int n, int R, int L, int n_prune,
@@ -541,6 +530,11 @@ __global__ void __launch_bounds__(256) asr_kernel(int R, int T, int L, int n_pru
 
 size_t asr_desc_bytes(int T) { return sizeof(AsrOp) * (size_t)(T - 2); }
 
+void launch_asr_sched(int n, int T, const int32_t* ops, const int4* hdr, void* desc, hipStream_t stream) {
+  const size_t sched_lds = (size_t)(T - 2) * (sizeof(int4) + 2 * sizeof(int32_t));
+  hipLaunchKernelGGL(asr_sched_kernel, dim3(n), dim3(64), sched_lds, stream, T, ops, hdr, static_cast<AsrOp*>(desc));
+}
+
 int launch_asr(const DevFamily& fam, int n, int R, int T, const int32_t* ops, const double* brlen, const double* rates,
                const double* eig, const double* pi, const double* site_lik, const int32_t* site_scal,
                const uint8_t* naive, uint64_t seed, uint64_t sample0, double* clv, void* desc, uint8_t* anc,
@@ -555,8 +549,7 @@ int launch_asr(const DevFamily& fam, int n, int R, int T, const int32_t* ops, co
   const long long cells = (long long)n * draws * L;
   hipLaunchKernelGGL(asr_rate_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, stream, n, R, L,
                      fam.n_prune, fam.site_pat, site_lik, site_scal, naive, seed, sample0, rate_choice, draws);
-  const size_t sched_lds = (size_t)(T - 2) * (sizeof(int4) + 2 * sizeof(int32_t));
-  hipLaunchKernelGGL(asr_sched_kernel, dim3(n), dim3(64), sched_lds, stream, T, ops, hdr, static_cast<AsrOp*>(desc));
+  launch_asr_sched(n, T, ops, hdr, desc, stream);
   hipLaunchKernelGGL(asr_kernel, dim3(R, n * draws), dim3(256), lds, stream, R, T, L, fam.n_prune, fam.msa, fam.site_pat,
                      static_cast<const AsrOp*>(desc), brlen, rates, eig, pi, rate_choice, naive, seed,
                      sample0, reinterpret_cast<double2*>(clv), (int)asr_slots(L, R), anc, hdr, draws);

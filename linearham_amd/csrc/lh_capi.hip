@@ -38,6 +38,7 @@ const DebugOptions& debug_options() {
     o.k1_no_fuse = set("LH_K1_NO_FUSE");
     o.codon_blocks = std::max(1, num("LH_CODON_BLOCKS", o.codon_blocks));
     o.events_blocks = std::max(1, num("LH_EVENTS_BLOCKS", o.events_blocks));
+    o.anc_out_mb = std::max(1, num("LH_ANC_OUT_MB", o.anc_out_mb));
     o.collect_hash_bits = std::min(64, std::max(1, num("LH_COLLECT_HASH_BITS", o.collect_hash_bits)));
     return o;
   }();
@@ -220,6 +221,17 @@ struct AsrWs {  // K3's scratch
   DevBuf desc;    // K3s -> K3b schedule descriptors
 };
 
+struct AncestralWs {  // K11's scratch (lh::AncWs) and the arrays its callers do not hand in
+  DevBuf clv, part, tvec, rho, chain, plen, desc;
+  DevBuf naive_prob, path;  // the host-pointer forms' device copies
+  DevBuf marg, rate_post;
+  // lh_eval_ancestral_batch: K11a's table (built by the first call), its output, and the reduction's arrays
+  bool have_table = false;
+  DevBuf sb_off, sb_idx, site_base;
+  DevBuf loglik, rates, ends, ll_used, weights, stats, partial_e, partial_r;
+  DevBuf out_wsum, out_wrate;
+};
+
 struct PosteriorWs {  // K5's arrays that the caller of lh_eval_posterior_batch_device does not hand in
   DevBuf loglik, weights, stats, partial;
 };
@@ -392,6 +404,7 @@ struct lh_family {
   EventsWs events;
   CollectWs collect;
   LineageWs lineage;
+  AncestralWs anc;
   // forward arrays that stay on the device, shared by K4 and K5 in both their forms: K4 draws from them, K5 overwrites
   // them with the posteriors (calls on a handle do not overlap: they also share the workspace)
   DevBuf forward_dev;
@@ -409,6 +422,7 @@ struct lh_family {
   KernelTimer<1> codon_timer;               // K9
   KernelTimer<2> events_timer;              // K10: K5's pass on the copy, K10 and its reduction
   KernelTimer<1> lineage_timer;             // K7
+  KernelTimer<3> anc_timer;                 // K11: K11a, K11b (with K11r, K11c, K11m), the weighted reduction
   KernelTimer<5> chain_timer;               // lh_eval_lineage_batch: K0, K1, K2 + K4 + K6c, K3, K7
   bool extended = false;  // lh_family_set_extended_range
   bool have_sampler = false;
@@ -746,6 +760,8 @@ int check_async_error(lh_family* f, const char* who) {
   LH_HIP(hipMemcpy(&flag, f->err_flag, sizeof(flag), hipMemcpyDeviceToHost));
   if (flag) {
     LH_HIP(hipMemset(f->err_flag, 0, sizeof(flag)));
+    if (flag == 2)  // (K11c's bit alone)
+      return fail(std::string(who) + ": lineage path that is not a chain up to the root; the affected samples' results are NaN");
     return fail(std::string(who) + ": malformed schedule op (use lh_schedule_tree); the affected samples' results are NaN");
   }
   return 0;
@@ -1970,6 +1986,354 @@ int lh_asr_batch(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const in
       return 1;
   }
   return 0;
+}
+
+}  // extern "C"
+
+namespace {
+
+// The chain of a sample's path under its own schedule, as K11c checks it on the device: the non-padding entries are inner
+// nodes, each a child of the next, the last one the root; padding (anything outside T .. 2T-3) comes only after them.
+bool valid_chain(const int32_t* ops, int T, const int32_t* path, int P) {
+  const int n_ops = T - 2;
+  std::vector<int> parent_op(n_ops, -1), op_of_node(n_ops, -1), slot(16, -1);
+  long long named = 0;
+  auto name = [&](int op, int node) {
+    if (node >= T && node <= 2 * T - 3) op_of_node[node - T] = op;
+    named += node;
+  };
+  for (int k = 0; k < n_ops; ++k) {
+    const int32_t* op = ops + (size_t)k * 4;
+    const int kind = op[0] & 15;
+    if (op[0] & lh::OP_PUSH_FLAG) slot[op[3] & 15] = k - 1;
+    if (kind == lh::OP_TIP_ACC) {
+      parent_op[k - 1] = k;
+      name(k - 1, op[2]);
+    } else if (kind == lh::OP_POP_ACC) {
+      const int q = slot[op[3] & 15];
+      if (q < 0) return false;
+      parent_op[k - 1] = k;
+      parent_op[q] = k;
+      name(k - 1, op[2]);
+      name(q, op[1]);
+    }
+  }
+  const long long root = (long long)n_ops * T + (long long)n_ops * (n_ops - 1) / 2 - named;
+  if (root < T || root > 2 * T - 3) return false;
+  op_of_node[root - T] = n_ops - 1;
+  int prev = -1, len = 0;
+  bool ended = false;
+  for (int s = 0; s < P; ++s) {
+    const int v = path[s];
+    if (v < T || v > 2 * T - 3) {
+      ended = true;
+      continue;
+    }
+    if (ended) return false;
+    const int k = op_of_node[v - T];
+    if (k < 0 || (len > 0 && parent_op[prev] != k)) return false;
+    prev = k;
+    ++len;
+  }
+  return len >= 1 && prev == n_ops - 1;
+}
+
+int ancestral_check(const lh_family* f, const std::string& W, const TreeBatch& b, int P) {
+  if (P < 1 || P > b.T - 2) return fail(W + ": path length must be in 1 .. n_tips - 2");
+  if (lh::anc_lds_bytes(b.T) > 160 * 1024) return fail(W + ": tree too large for the kernel's LDS tables");
+  return 0;
+}
+
+// samples per launch group of K11: at most kChunk and 8192 samples and ~8 GB of K11's scratch plus K1's workspace (as asr_group
+// bounds K3's: a group size by memory, at least one sample)
+size_t ancestral_group(const lh_family* f, int T, int R, int P) {
+  const size_t per = lh::anc_ws_bytes(T, f->host.n_sites, R, f->host.n_prune, P).total() + lh::asr_desc_bytes(T) +
+                     eval_bytes_per_sample(f, T, R);
+  return std::max<size_t>(1, std::min<size_t>({(size_t)kChunk, (size_t)8192, ((size_t)8 << 30) / per}));
+}
+
+int ancestral_workspace(lh_family* f, int chunk, int T, int R, int P, bool own_rho, lh::AncWs* ws) {
+  AncestralWs& a = f->anc;
+  const lh::AncWsBytes z = lh::anc_ws_bytes(T, f->host.n_sites, R, f->host.n_prune, P);
+  const size_t m = chunk;
+  if (a.clv.ensure(z.clv * m) || a.part.ensure(z.part * m) || a.tvec.ensure(z.tvec * m) || (own_rho && a.rho.ensure(z.rho * m)) ||
+      a.chain.ensure(z.chain * m) || a.plen.ensure(sizeof(int32_t) * m) || a.desc.ensure(lh::asr_desc_bytes(T) * m))
+    return 1;
+  *ws = {a.clv.get<double>(), a.part.get<double>(), a.tvec.get<double>(), a.rho.get<double>(), a.chain.get<int32_t>(),
+         a.plen.get<int32_t>(), a.desc.get()};
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int lh_asr_marginals_batch_device(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops,
+                                  const double* brlen, const double* er, const double* pi, const double* rates, int32_t R,
+                                  const double* naive_prob, const int32_t* path, int32_t P, double* marg, double* rate_post,
+                                  void* hip_stream) {
+  const TreeBatch b{n, T, max_depth, ops, brlen, er, pi, rates, R, true};
+  const std::string W = "lh_asr_marginals_batch";
+  if (int rc = check_batch(f, W, b)) return rc > 0;
+  if (ancestral_check(f, W, b, P)) return 1;
+  DeviceGuard guard(f);
+  if (!b.has_arrays() || !naive_prob || !path) return fail(W + ": null array");
+  if (!marg && !rate_post) return 0;  // nothing asked for
+  hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+  const size_t L = f->host.n_sites;
+  const int chunk = (int)std::min<size_t>(n, ancestral_group(f, T, R, P));
+  lh::AncWs ws;
+  if (ensure_workspace(f, chunk, R, T) || ancestral_workspace(f, chunk, T, R, P, !rate_post, &ws)) return 1;
+  Workspace& w = f->ws;
+  double *eig = w.eig.get<double>(), *site_lik = w.site_lik.get<double>();
+  int32_t* site_scal = w.site_scal.get<int32_t>();
+  for (int off = 0; off < n; off += chunk) {
+    const int m = std::min(chunk, n - off);
+    const TreeBatch g = b.slice(off, m);
+    lh::launch_gtr_setup(m, g.er, g.pi, eig, stream);
+    int planes = 0;
+    if (prune_group(f, W, g, g.model, false, stream, &planes)) return 1;
+    if (f->profile && (f->anc_timer.begin(stream) || f->anc_timer.mark(1, stream))) return 1;
+    if (lh::launch_ancestral(f->host, m, R, T, g.ops, g.brlen, g.model, eig, g.pi, site_lik, site_scal,
+                             naive_prob + (size_t)off * L * 5, path + (size_t)off * P, P, ws,
+                             marg ? marg + (size_t)off * P * L * 4 : nullptr, rate_post ? rate_post + (size_t)off * L * R : nullptr,
+                             w.prune.hdr, f->err_flag, stream))
+      return fail(W + ": launch failed");
+    if (f->profile && (f->anc_timer.mark(2, stream) || f->anc_timer.end(stream))) return 1;
+    LH_HIP(hipGetLastError());
+  }
+  return 0;
+}
+
+int lh_asr_marginals_batch(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops, const double* brlen,
+                           const double* er, const double* pi, const double* rates, int32_t R, const double* naive_prob,
+                           const int32_t* path, int32_t P, double* marg, double* rate_post) {
+  const TreeBatch host{n, T, max_depth, ops, brlen, er, pi, rates, R, true};
+  const std::string W = "lh_asr_marginals_batch";
+  if (int rc = check_batch(f, W, host)) return rc > 0;
+  if (ancestral_check(f, W, host, P)) return 1;
+  DeviceGuard guard(f);
+  if (!host.has_arrays() || !naive_prob || !path) return fail(W + ": null array");
+  if (!marg && !rate_post) return 0;
+  const size_t L = f->host.n_sites;
+  if (!valid_schedules(host)) return fail(W + ": malformed schedule op (use lh_schedule_tree)");
+  for (size_t i = 0; i < (size_t)n; ++i)
+    if (!valid_chain(host.schedule(i), T, path + i * P, P))
+      return fail(W + ": path of sample " + std::to_string(i) +
+                  " is not a chain of inner nodes, each the child of the next, that ends at the root (padding after it)");
+  AncestralWs& a = f->anc;
+  // sub-batches bound the device copies of the outputs (marg: 32 P L bytes per sample)
+  const size_t per = sizeof(double) * L * ((size_t)P * 4 + R + 5);
+  const int sub = (int)std::max<size_t>(1, std::min<size_t>(n, ((size_t)1 << 30) / per));
+  for (int off = 0; off < n; off += sub) {
+    const int m = std::min(sub, n - off);
+    const size_t marg_bytes = sizeof(double) * P * L * 4 * m, rp_bytes = sizeof(double) * L * R * m;
+    double *d_marg = nullptr, *d_rp = nullptr;
+    TreeBatch dev;
+    if (out_buf(marg, a.marg, marg_bytes, &d_marg) || out_buf(rate_post, a.rate_post, rp_bytes, &d_rp) ||
+        stage_batch(f, host.slice(off, m),
+                    {{naive_prob + (size_t)off * L * 5, sizeof(double) * L * 5 * m, &a.naive_prob},
+                     {path + (size_t)off * P, sizeof(int32_t) * P * m, &a.path}},
+                    &dev))
+      return 1;
+    if (lh_asr_marginals_batch_device(f, m, T, max_depth, dev.ops, dev.brlen, dev.er, dev.pi, dev.model, R,
+                                      a.naive_prob.get<const double>(), a.path.get<const int32_t>(), P, d_marg, d_rp, nullptr))
+      return 1;
+    if (copy_back(f, W.c_str(),
+                  {{marg ? marg + (size_t)off * P * L * 4 : nullptr, d_marg, marg_bytes},
+                   {rate_post ? rate_post + (size_t)off * L * R : nullptr, d_rp, rp_bytes}}))
+      return 1;
+  }
+  return 0;
+}
+
+}  // extern "C"
+
+namespace {
+
+// K11a's table: per (site, base) the compact entries (lh_eval_outputs.forward's layout) whose state writes that base on
+// that site, in ascending order -- posterior.site_base's mapping and the host library's NaiveMarginals.
+int ancestral_table(lh_family* f, const std::string& W) {
+  AncestralWs& a = f->anc;
+  if (a.have_table) return 0;
+  const CodonSource& cs = f->codon_src;
+  if (!cs.have) return fail(W + ": family was created without an MSA (forward-only)");
+  const lh::DevFamily& h = f->host;
+  const bool has_d = h.has_d != 0;
+  const size_t L = h.n_sites;
+  std::vector<std::vector<int32_t>> cell(L * 5);
+  int32_t k = 0;
+  auto column = [&](int32_t c) {  // the entry k writes what the caller's column c says
+    if (c >= 0 && cs.site[c] >= 0 && (size_t)cs.site[c] < L && cs.base[c] <= 4) cell[(size_t)cs.site[c] * 5 + cs.base[c]].push_back(k);
+  };
+  auto germ = [&](const CodonSegments& g, int n_genes) {
+    for (int i = 0; i < n_genes; ++i, ++k)
+      for (int x = g.offsets[i]; x < g.offsets[i + 1]; ++x) column(g.inds[x]);
+  };
+  auto junction = [&](const CodonSourceJunction& j, const lh::DevJunction& d) {
+    const size_t nL = d.n_left, nR = d.n_right;
+    for (size_t i = 0; i < (size_t)d.n_rows; ++i) {
+      for (size_t l = 0; l < nL; ++l, ++k) column(j.left_xmsa[i * nL + l]);
+      for (size_t r = 0; r < nR; ++r)
+        for (int b = 0; b < 4; ++b, ++k) column(j.nti_xmsa[(i * nR + r) * 4 + b]);
+      for (size_t r = 0; r < nR; ++r, ++k) column(j.right_xmsa[i * nR + r]);
+    }
+  };
+  germ(cs.v, h.vgerm.n_genes);
+  junction(cs.vd, h.vd);
+  if (has_d) {
+    germ(cs.d, h.dgerm.n_genes);
+    junction(cs.dj, h.dj);
+  }
+  germ(cs.j, h.jgerm.n_genes);
+  if (k != (int32_t)h.forward_size) return fail(W + ": internal error (compact layout)");
+  std::vector<int32_t> off(L * 5 + 1, 0), idx;
+  for (size_t c = 0; c < cell.size(); ++c) {
+    idx.insert(idx.end(), cell[c].begin(), cell[c].end());
+    off[c + 1] = (int32_t)idx.size();
+  }
+  if (a.sb_off.ensure(sizeof(int32_t) * off.size()) || a.sb_idx.ensure(sizeof(int32_t) * idx.size())) return 1;
+  LH_HIP(hipMemcpy(a.sb_off.get(), off.data(), sizeof(int32_t) * off.size(), hipMemcpyHostToDevice));
+  if (!idx.empty()) LH_HIP(hipMemcpy(a.sb_idx.get(), idx.data(), sizeof(int32_t) * idx.size(), hipMemcpyHostToDevice));
+  a.have_table = true;
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int lh_eval_ancestral_batch_device(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops,
+                                   const double* brlen, const double* er, const double* pi, const double* alpha, int32_t R,
+                                   const int32_t* path, int32_t P, const lh_ancestral_outputs* outs, void* hip_stream) {
+  const TreeBatch b{n, T, max_depth, ops, brlen, er, pi, alpha, R};
+  const std::string W = "lh_eval_ancestral_batch";
+  if (int rc = check_batch(f, W, b, true)) return rc > 0;
+  if (ancestral_check(f, W, b, P)) return 1;
+  DeviceGuard guard(f);
+  if (!b.has_arrays() || !path) return fail(W + ": null array");
+  const lh_ancestral_outputs none{};
+  const lh_ancestral_outputs& o = outs ? *outs : none;
+  if (ancestral_table(f, W)) return 1;
+  hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+  const size_t L = f->host.n_sites, FS = f->host.forward_size;
+  const int chunk = (int)std::min<size_t>(n, std::min(ancestral_group(f, T, R, P), eval_group(f, T, R)));
+  AncestralWs& a = f->anc;
+  const bool reduce = o.weighted_sum || o.weighted_rate || o.weight_stats;
+  const bool want_marg = o.marg || o.weighted_sum;
+  const bool want_rp = o.rate_post || o.weighted_rate;
+  const size_t slabs = lh::posterior_slabs(n);
+  lh::AncWs ws;
+  double *ll = o.loglik, *sb = o.site_base, *marg = o.marg, *rp = o.rate_post, *ends = nullptr, *pe = nullptr, *pr = nullptr;
+  WeightReduce wr;
+  // what the caller does not take lives per launch group (site_base, marg) or, where the reduction reads it, per batch
+  const size_t sb_rows = o.site_base ? 0 : chunk, marg_rows = (o.marg || !want_marg) ? 0 : chunk;
+  if (ensure_workspace(f, chunk, R, T) || ancestral_workspace(f, chunk, T, R, P, !want_rp, &ws) ||
+      a.plen.ensure(sizeof(int32_t) * n) || a.rates.ensure(sizeof(double) * R * chunk) ||
+      f->forward_dev.ensure(sizeof(double) * FS * n) || own(ll, a.loglik, sizeof(double) * n) ||
+      own(sb, a.site_base, sizeof(double) * L * 5 * sb_rows) || (want_marg && own(marg, a.marg, sizeof(double) * P * L * 4 * marg_rows)) ||
+      (want_rp && own(rp, a.rate_post, sizeof(double) * L * R * n)) ||
+      (reduce && (a.ll_used.ensure(sizeof(double) * n) || wr.prepare(n, a.weights, a.stats, o.weight_stats) ||
+                  (o.weighted_sum && (own(ends, a.ends, sizeof(double) * 2 * L * 4 * n) || own(pe, a.partial_e, sizeof(double) * 2 * L * 4 * slabs))) ||
+                  (o.weighted_rate && own(pr, a.partial_r, sizeof(double) * L * R * slabs)))))
+    return 1;
+  ws.plen = a.plen.get<int32_t>();  // (the batch's, for the reduction; a.plen.ensure above may have moved it)
+  Workspace& w = f->ws;
+  double *eig = w.eig.get<double>(), *site_lik = w.site_lik.get<double>(), *fwd = f->forward_dev.get<double>();
+  double* rates = a.rates.get<double>();
+  int32_t* site_scal = w.site_scal.get<int32_t>();
+  const lh_eval_outputs fwd_outs{nullptr, nullptr, fwd, nullptr};
+  for (int off = 0; off < n; off += chunk) {
+    const int m = std::min(chunk, n - off);
+    const TreeBatch g = b.slice(off, m);
+    lh::launch_model_setup(m, R, g.er, g.pi, g.model, rates, eig, stream);
+    int planes = 0;
+    // one unmixed K1 serves K2 and K11b: its planes outlive K2
+    if (prune_group(f, W, g, rates, false, stream, &planes)) return 1;
+    if (run_forward(f, m, planes, site_lik, site_scal, g.pi, nullptr, nullptr, ll + off, &fwd_outs, off, stream)) return 1;
+    lh::launch_posterior(f->sampler_dev, m, fwd + (size_t)off * FS, FS, ll + off, stream);
+    if (f->profile && f->anc_timer.begin(stream)) return 1;
+    double* sb_g = o.site_base ? sb + (size_t)off * L * 5 : sb;
+    lh::launch_site_base(m, (int)L, FS, a.sb_off.get<const int32_t>(), a.sb_idx.get<const int32_t>(), fwd + (size_t)off * FS,
+                         ll + off, sb_g, stream);
+    if (f->profile && f->anc_timer.mark(1, stream)) return 1;
+    double* marg_g = !want_marg ? nullptr : o.marg ? marg + (size_t)off * P * L * 4 : marg;
+    lh::AncWs wg = ws;
+    wg.plen = ws.plen + off;
+    if (want_marg || want_rp) {
+      if (lh::launch_ancestral(f->host, m, R, T, g.ops, g.brlen, rates, eig, g.pi, site_lik, site_scal, sb_g, path + (size_t)off * P,
+                               P, wg, marg_g, want_rp ? rp + (size_t)off * L * R : nullptr, w.prune.hdr, f->err_flag, stream))
+        return fail(W + ": launch failed");
+    }
+    // the paths were checked wherever marg was formed: a row without one then gets no weight
+    if (reduce && want_marg)
+      lh::launch_ancestral_ends(m, P, (int)L, wg.plen, marg_g, ll + off, o.weighted_sum ? ends + (size_t)off * 2 * L * 4 : nullptr,
+                                a.ll_used.get<double>() + off, stream);
+    if (f->profile && f->anc_timer.mark(2, stream)) return 1;
+    if (reduce && off + m == n) {
+      // (without marg or weighted_sum no path was looked at: the weights are the rows' own)
+      wr.launch(n, want_marg ? a.ll_used.get<const double>() : ll, o.log_offset, stream);
+      if (o.weighted_sum) lh::launch_weighted_slabs(n, 2 * L * 4, ends, wr.w, pe, o.weighted_sum, stream);
+      if (o.weighted_rate) lh::launch_weighted_slabs(n, L * R, rp, wr.w, pr, o.weighted_rate, stream);
+    }
+    if (f->profile && f->anc_timer.end(stream)) return 1;
+    LH_HIP(hipGetLastError());
+  }
+  return 0;
+}
+
+int lh_eval_ancestral_batch(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops, const double* brlen,
+                            const double* er, const double* pi, const double* alpha, int32_t R, const int32_t* path, int32_t P,
+                            const lh_ancestral_outputs* outs) {
+  const TreeBatch host{n, T, max_depth, ops, brlen, er, pi, alpha, R};
+  const std::string W = "lh_eval_ancestral_batch";
+  if (int rc = check_batch(f, W, host, true)) return rc > 0;
+  if (ancestral_check(f, W, host, P)) return 1;
+  DeviceGuard guard(f);
+  if (!host.has_arrays() || !path) return fail(W + ": null array");
+  const lh_ancestral_outputs none{};
+  const lh_ancestral_outputs& o = outs ? *outs : none;
+  if (!o.loglik && !o.site_base && !o.marg && !o.rate_post && !o.weighted_sum && !o.weighted_rate && !o.weight_stats) return 0;
+  const size_t L = f->host.n_sites;
+  // the device copies of the per-row outputs bound the batch
+  const size_t per = sizeof(double) * L * ((o.marg ? (size_t)P * 4 : 0) + (o.rate_post ? R : 0) + (o.site_base ? 5 : 0));
+  const size_t most = per ? ((size_t)lh::debug_options().anc_out_mb << 20) / per : (size_t)INT32_MAX;
+  if ((size_t)n > most)
+    return fail(W + ": batch too large for the device copies of its per-row outputs: at most " + std::to_string(most) +
+                " samples per call for this family and path length");
+  for (size_t i = 0; i < (size_t)n; ++i)
+    if (valid_schedule(host.schedule(i), T, (int)host.nodes(), max_depth) && !valid_chain(host.schedule(i), T, path + i * P, P))
+      return fail(W + ": path of sample " + std::to_string(i) +
+                  " is not a chain of inner nodes, each the child of the next, that ends at the root (padding after it)");
+  AncestralWs& a = f->anc;
+  HostOutputs& out = f->out;
+  lh_ancestral_outputs d{};
+  TreeBatch dev;
+  if (out.loglik.ensure(sizeof(double) * n) || out_buf(o.site_base, a.site_base, sizeof(double) * L * 5 * n, &d.site_base) ||
+      out_buf(o.marg, a.marg, sizeof(double) * P * L * 4 * n, &d.marg) ||
+      out_buf(o.rate_post, a.rate_post, sizeof(double) * L * R * n, &d.rate_post) ||
+      out_buf(o.weighted_sum, a.out_wsum, sizeof(double) * 2 * L * 4, &d.weighted_sum) ||
+      out_buf(o.weighted_rate, a.out_wrate, sizeof(double) * L * R, &d.weighted_rate) ||
+      out_buf(o.weight_stats, out.weight_stats, sizeof(double) * 3, &d.weight_stats) ||
+      stage_batch(f, host, {{o.log_offset, sizeof(double) * n, &f->in.log_offset}, {path, sizeof(int32_t) * P * n, &a.path}}, &dev))
+    return 1;
+  d.log_offset = o.log_offset ? f->in.log_offset.get<const double>() : nullptr;
+  d.loglik = out.loglik.get<double>();
+  if (lh_eval_ancestral_batch_device(f, n, T, max_depth, dev.ops, dev.brlen, dev.er, dev.pi, dev.model, R, a.path.get<const int32_t>(), P,
+                                     &d, nullptr))
+    return 1;
+  return finish_batch(f, W.c_str(), host,
+                      {{o.loglik, d.loglik, sizeof(double) * n},
+                       {o.site_base, d.site_base, sizeof(double) * L * 5 * n},
+                       {o.marg, d.marg, sizeof(double) * P * L * 4 * n},
+                       {o.rate_post, d.rate_post, sizeof(double) * L * R * n},
+                       {o.weighted_sum, d.weighted_sum, sizeof(double) * 2 * L * 4},
+                       {o.weighted_rate, d.weighted_rate, sizeof(double) * L * R},
+                       {o.weight_stats, d.weight_stats, sizeof(double) * 3}});
+}
+
+int lh_ancestral_profile_read(lh_family* f, double* ms, int64_t* n_launches) {
+  return profile_read(f, &lh_family::anc_timer, ms, n_launches);
 }
 
 int lh_forward_batch(lh_family* f, int32_t n, const double* em, double* loglik, const lh_eval_outputs* outs) {

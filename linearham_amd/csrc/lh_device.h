@@ -398,6 +398,53 @@ size_t asr_desc_bytes(int T);  // per sample, of the schedule descriptors `desc`
 size_t asr_lds_bytes(int T, int L, int R, int n_prune);
 size_t asr_slots(int L, int R);  // slots per sample in K3's CLV area: clv[n][T-2][2][asr_slots] double2
 
+// One schedule op as the sampling kernel reads it (two int4, fetched with scalar loads): everything that K3b
+// would otherwise have to derive per op from the K1 schedule with dependent look-ups.
+//   a.x  kind | stack slot of the op << 4 | (slot + 1 the NEXT op pushes the accumulator to, or 0) << 8
+//   a.y  MSA row of tip child y (cherry, tip-acc), else 0        a.z  MSA row of tip child z (cherry), else 0
+//   a.w  op that produced the sibling a pop op takes from the stack, else 0
+//   b.x  tip id y (tip table row)   b.y  tip id z   b.z  inner node (minus T) this op produces
+//   b.w  inner node (minus T) of the popped sibling (pop), else 0
+struct AsrOp {
+  int4 a, b;
+};
+
+// K3s alone: desc[n][T - 2] from the schedules (K0c's verdicts in hdr: a rejected sample's descriptors are not written)
+void launch_asr_sched(int n, int T, const int32_t* ops, const int4* hdr, void* desc, hipStream_t stream);
+
+// K11: exact ancestral-state marginals along a lineage path (lh_ancestral.hip).  Inputs as launch_asr's, with
+// naive_prob[n][n_sites][5] in place of the naive sequences and path[n][P] (seed's parent .. root, padding after).  marg
+// [n][P][n_sites][4] (may be null: the rate posteriors alone) and rate_post [n][n_sites][R] (may be null).  A sample whose
+// path is not a chain under its own schedule, or whose schedule K0c rejected, gets NaN in its marg row; the first raises
+// *err_flag.  Scratch per sample: anc_ws_bytes.  Returns nonzero if the launch cannot be made (LDS tables, grid).
+struct AncWs {
+  double* clv;      // [n][R][T-2][2][patterns rounded up to 8] double2
+  double* part;     // [n][R][P][n_sites][4]
+  double* tvec;     // [n][n_sites][5]
+  double* rho;      // [n][n_sites][R], used when rate_post is null
+  int32_t* chain;   // [n][P]
+  int32_t* plen;    // [n]
+  void* desc;       // [n] asr_desc_bytes(T)
+};
+struct AncWsBytes {
+  size_t clv, part, tvec, rho, chain;  // per sample (desc: asr_desc_bytes)
+  size_t total() const { return clv + part + tvec + rho + chain; }
+};
+AncWsBytes anc_ws_bytes(int T, int L, int R, int n_prune, int P);
+size_t anc_lds_bytes(int T);
+int launch_ancestral(const DevFamily& fam, int n, int R, int T, const int32_t* ops, const double* brlen, const double* rates,
+                     const double* eig, const double* pi, const double* site_lik, const int32_t* site_scal,
+                     const double* naive_prob, const int32_t* path, int P, const AncWs& ws, double* marg, double* rate_post,
+                     const int4* hdr, int32_t* err_flag, hipStream_t stream);
+// K11a: site_base[n][L][5] from K5's posteriors post[n][forward_size]; off[5 L + 1] / idx: per (site, base) the compact
+// entries that write it.  A row whose loglik is not finite is NaN.
+void launch_site_base(int n, int L, size_t forward_size, const int32_t* off, const int32_t* idx, const double* post,
+                      const double* loglik, double* site_base, hipStream_t stream);
+// For the weighted reduction: ends[n][2][L][4] = slot 0 and the last slot of every sample's marg (ends null: not wanted);
+// ll_used[n] = loglik, NaN where plen is 0 (launch_ancestral found no path: the row's weight becomes 0).
+void launch_ancestral_ends(int n, int P, int L, const int32_t* plen, const double* marg, const double* loglik, double* ends,
+                           double* ll_used, hipStream_t stream);
+
 // K2a + K2b.  site_lik != null: emissions are assembled from K1's output (rate mix and naive
 // correction; optionally written to em_out[n][C]); site_lik == null: emissions are taken from
 // em_in[n][C].  K2a leaves the germline/padding emission products in gem[n][gem_size], their scaler
@@ -468,6 +515,8 @@ struct DebugOptions {
   bool k1_no_fuse = false;     // LH_K1_NO_FUSE: one workgroup per (sample, rate)
   int codon_blocks = 2048;     // LH_CODON_BLOCKS=<n>: K9's workgroup cap (tests: a lane group walks several samples in a small call)
   int events_blocks = 1024;    // LH_EVENTS_BLOCKS=<n>: K10's workgroup cap (as LH_CODON_BLOCKS)
+  int anc_out_mb = 4096;       // LH_ANC_OUT_MB=<n>: MiB of device copies of lh_eval_ancestral_batch's per-row outputs (host
+                               // pointers) above which a batch is refused with the largest n (tests: the refusal on a small family)
   int collect_hash_bits = 64;  // LH_COLLECT_HASH_BITS=<n>: K6c's row hashes masked to n bits (tests: collisions common,
                                // the exact resolution runs; results unchanged)
 };

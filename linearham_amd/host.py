@@ -62,6 +62,50 @@ def newick_arrays(newick, labels):
     return children, root.value, brlen
 
 
+def seed_path(n_tips, children, root, seed_tip):
+    """The `path` row of a tip under the tree (children [(T-2)*2], root) in lh_schedule_tree's numbering: the inner nodes
+    from the tip's parent up to the root (naive's neighbour), each the child of the next -- linearham::SeedPath, the walk
+    the lineage pipelines use.  No device needed."""
+    import numpy as np
+    children = np.ascontiguousarray(children, dtype=np.int32).ravel()
+    T = int(n_tips)
+    if children.size != 2 * (T - 2):
+        raise ValueError("seed_path: children must hold 2 (n_tips - 2) entries")
+    if not 1 <= seed_tip < T:
+        raise ValueError("seed_path: the seed is one of the tips 1 .. n_tips - 1 (0 is naive)")
+    path = np.zeros(max(T - 2, 1), dtype=np.int32)
+    n = C.c_int()
+    lib = load_host()
+    lib.lhh_seed_path.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+    _check(lib.lhh_seed_path(children.ctypes.data, T, int(root), int(seed_tip), path.ctypes.data, len(path), C.byref(n)))
+    if n.value == 0:
+        raise ValueError("seed_path: tip %d does not hang below the root" % seed_tip)
+    return [int(v) for v in path[:n.value]]
+
+
+def read_ancestral_marginals(prefix):
+    """The files of PhyloHMM::RunAncestralMarginalsPipeline: dict(parent [L][4], mrca [L][4], map_base {"parent", "mrca"},
+    rates [L][R], rows [(row, weight, chain_length)], summary)."""
+    import numpy as np
+
+    def table(path, last_is_text):
+        lines = open(path).read().strip().split("\n")
+        cells = [ln.split("\t") for ln in lines[1:]]
+        end = -1 if last_is_text else None
+        return lines[0].split("\t"), np.array([[float(x) for x in c[1:end]] for c in cells]), [c[-1] for c in cells]
+    out, maps = {}, {}
+    for name in ("parent", "mrca"):
+        header, out[name], maps[name] = table(prefix + "." + name + ".tsv", True)
+        assert header == ["site", "A", "C", "G", "T", "map_base"]
+    out["map_base"] = maps
+    _, out["rates"], _ = table(prefix + ".rates.tsv", False)
+    rows = [ln.split("\t") for ln in open(prefix + ".rows.tsv").read().strip().split("\n")]
+    assert rows[0] == ["row", "weight", "chain_length"]
+    out["rows"] = [(int(r[0]), float(r[1]), int(r[2])) for r in rows[1:]]
+    out["summary"] = _parse_summary(open(prefix + ".summary.tsv").read())
+    return out
+
+
 def _parse_gene_table(text):
     genes = {}
     for line in text.strip().split("\n")[1:]:
@@ -403,6 +447,33 @@ class PhyloHMM(_HMM):
         self.lib.lhh_phylo_naive_marginals.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_char_p)]
         _check(self.lib.lhh_phylo_naive_marginals(self.h, sb.ctypes.data, L, C.byref(out)))
         return sb, _parse_gene_table(out.value.decode())
+
+    def ancestral_marginals(self, seed_seq):
+        """PhyloHMM::AncestralMarginals of the current tree: dict(nodes [P] -- the lineage of the tip `seed_seq`, slot 0 its
+        parent, the last slot the MRCA --, marg [P][L][4], rate_post [L][R], loglik)."""
+        sz = self.sizes()
+        T, L = sz["n_tips"], sz["n_sites"]
+        lib = self.lib
+        lib.lhh_phylo_ancestral_marginals.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                                      C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double)]
+        n, r, ll = C.c_int(), C.c_int(), C.c_double()
+        _check(lib.lhh_phylo_ancestral_marginals(self.h, seed_seq.encode(), None, None, None, 0, C.byref(n), C.byref(r), None))
+        P, R = n.value, r.value
+        nodes = np.zeros(P, dtype=np.int32)
+        marg = np.zeros((P, L, 4))
+        rate_post = np.zeros((L, R))
+        _check(lib.lhh_phylo_ancestral_marginals(self.h, seed_seq.encode(), nodes.ctypes.data, marg.ctypes.data,
+                                                 rate_post.ctypes.data, P, C.byref(n), C.byref(r), C.byref(ll)))
+        return dict(nodes=nodes.tolist(), marg=marg, rate_post=rate_post, loglik=ll.value)
+
+    def run_ancestral_marginals_pipeline(self, input_path, seed_seq, output_prefix, num_rates, burnin_frac=0.0):
+        """PhyloHMM::RunAncestralMarginalsPipeline: importance-weighted exact tables of the seed's parent and of the MRCA and
+        the rate posteriors over a RevBayes table; returns read_ancestral_marginals(output_prefix)."""
+        self.lib.lhh_run_ancestral_marginals_pipeline.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int,
+                                                                  C.c_double]
+        _check(self.lib.lhh_run_ancestral_marginals_pipeline(self.h, input_path.encode(), seed_seq.encode(),
+                                                             output_prefix.encode(), num_rates, C.c_double(burnin_frac)))
+        return read_ancestral_marginals(output_prefix)
 
     def run_marginals_pipeline(self, input_path, output_prefix, num_rates, burnin_frac=0.0):
         """PhyloHMM::RunMarginalsPipeline: importance-weighted exact marginals over a RevBayes table (burn-in
