@@ -588,6 +588,98 @@ int lh_eval_ancestral_batch_device(lh_family* fam, int32_t n, int32_t n_tips, in
  * reduction (lh_asr_marginals_batch runs the second only); resets the counters. */
 int lh_ancestral_profile_read(lh_family* fam, double* ms, int64_t* n_launches);
 
+/* ---- K12: exact substitution posteriors along the edges of a seed's lineage ----
+ * The two ends of an edge are strongly dependent, so which substitution happened on which edge is not the product of two
+ * of K11's per-node tables.  For a sample with path v_0 (the seed's parent) .. v_{len-1} (the root, naive's neighbour) the
+ * lineage of seed tip u has len + 1 edges; every table is indexed [ancestor state][descendant state], naive the oldest node.
+ *   lh_asr_marginals_batch's inputs, plus
+ *   seed_tip              the seed's tip id, 1 .. T-1, one value per call; it must be a child of path[i][0] in every sample
+ * and an output struct, every member of which may be NULL:
+ *   edge [n][P][L][4][4]      edge[s][j][a][c] = P(x_{v_s, j} = a, x_{below, j} = c | data), below = v_{s-1} for s >= 1 and
+ *                             the seed tip for s = 0 (an N seed tip: what the model says about the unobserved base).
+ *                             A padding slot's tables are 0.
+ *   naive_edge [n][L][5][4]   P(naive_j = b, x_{root, j} = i | data), b over A,C,G,T,N
+ *   chain_counts [n][L][4][4] naive_edge (rows b < 4) + sum_s edge[s]: the expected number of lineage edges, naive to
+ *                             seed, on which site j goes from a to c.  An off-diagonal cell counts edges whose ends are a
+ *                             and c, not substitutions inside a branch.  The cells of a site sum to len + 1 - q_j(N).
+ *   edge_load [n][P+1]        the expected number of sites whose two ends differ on the edge: [s] slot s (padding slots 0),
+ *                             [P] the naive edge (rows b < 4)
+ *   rate_post [n][L][R]       as lh_asr_marginals_batch
+ * Margins: sum_c edge[s] = marg[s], sum_a edge[s] = marg[s-1], sum_i naive_edge = naive_prob, sum_b naive_edge = marg[len-1].
+ * chain_counts, edge_load and naive_edge have the same bits whether or not edge is asked for (without it a leaner kernel
+ * runs), and the same sample gives the same bits whatever the batch around it: every sum runs in a fixed order.
+ * The host-pointer form refuses a batch whose device copies of the per-row outputs would exceed 4 GiB, naming the largest n,
+ * a seed_tip outside 1 .. T-1, a path that is not a chain (as lh_asr_marginals_batch) and a
+ * seed_tip that is not a child of path[i][0].  The device form refuses only the first; for the other two the sample gets NaN
+ * in all its rows and the handle's error word is raised (bit 1), and no index is formed from an unchecked value. */
+typedef struct lh_edges_outputs {
+  double* edge;
+  double* naive_edge;
+  double* chain_counts;
+  double* edge_load;
+  double* rate_post;
+} lh_edges_outputs;
+
+int lh_asr_edges_batch(lh_family* fam, int32_t n, int32_t n_tips, int32_t max_depth, const int32_t* ops,
+                       const double* brlen, const double* er, const double* pi, const double* rates, int32_t num_rates,
+                       const double* naive_prob, const int32_t* path, int32_t path_len, int32_t seed_tip,
+                       const lh_edges_outputs* outs);
+
+/* Same with every array (the members of outs included) resident on the handle's device; enqueued on `hip_stream`
+ * without synchronising. */
+int lh_asr_edges_batch_device(lh_family* fam, int32_t n, int32_t n_tips, int32_t max_depth, const int32_t* ops,
+                              const double* brlen, const double* er, const double* pi, const double* rates,
+                              int32_t num_rates, const double* naive_prob, const int32_t* path, int32_t path_len,
+                              int32_t seed_tip, const lh_edges_outputs* outs, void* hip_stream);
+
+/* The evaluation with K12 behind it, K11's chain: lh_eval_ancestral_batch's inputs plus seed_tip, and per tree sample K0-K2
+ * (one unmixed K1 serves the forward sweep and K12), K5's posterior on the forward arrays, its push-forward onto the naive
+ * base of every site, and lh_asr_edges_batch fed that distribution and the sample's rates.  Needs lh_family_set_sampler;
+ * honours lh_family_set_extended_range.  Every member may be NULL:
+ *   log_offset, loglik, site_base            as in lh_ancestral_outputs
+ *   edge, naive_edge, chain_counts, edge_load, rate_post   as in lh_edges_outputs
+ *   seed_edge [n][L][4][4]                   slot 0 of edge, the edge above the seed tip, without the other slots
+ *   weighted_counts [L][4][4]                sum_i w_i chain_counts_i,  w_i = exp(loglik_i - log_offset_i - max)
+ *   weighted_seed_edge [L][4][4]             sum_i w_i seed_edge_i
+ *   weighted_naive_edge [L][5][4]            sum_i w_i naive_edge_i
+ *   weight_stats [3]                         max, sum w, sum w^2 as in lh_posterior_outputs
+ * The three weighted tables are of quantities that mean the same in every tree.  The sums run in sample order (K5's slab
+ * scheme: no atomics, bit-stable); rows with w = 0 or a non-finite log-likelihood are left out, and so are rows without a
+ * valid path (device form) whenever a table is asked for, so batches combine exactly as lh_eval_posterior_batch's do.
+ * Without edge the lean kernel runs.  The host-pointer form refuses as lh_asr_edges_batch does, and a batch whose device
+ * copies of the per-row outputs would exceed 4 GiB, naming the largest n. */
+typedef struct lh_eval_edges_outputs {
+  const double* log_offset;
+  double* loglik;
+  double* site_base;
+  double* edge;
+  double* naive_edge;
+  double* chain_counts;
+  double* seed_edge;
+  double* edge_load;
+  double* rate_post;
+  double* weighted_counts;
+  double* weighted_seed_edge;
+  double* weighted_naive_edge;
+  double* weight_stats;
+} lh_eval_edges_outputs;
+
+int lh_eval_edges_batch(lh_family* fam, int32_t n, int32_t n_tips, int32_t max_depth, const int32_t* ops,
+                        const double* brlen, const double* er, const double* pi, const double* alpha, int32_t num_rates,
+                        const int32_t* path, int32_t path_len, int32_t seed_tip, const lh_eval_edges_outputs* outs);
+
+/* Same with every array (the members of outs included) resident on the handle's device; enqueued on `hip_stream`
+ * without synchronising. */
+int lh_eval_edges_batch_device(lh_family* fam, int32_t n, int32_t n_tips, int32_t max_depth, const int32_t* ops,
+                               const double* brlen, const double* er, const double* pi, const double* alpha,
+                               int32_t num_rates, const int32_t* path, int32_t path_len, int32_t seed_tip,
+                               const lh_eval_edges_outputs* outs, void* hip_stream);
+
+/* Times of K12 over the launches made while profiling was enabled (HIP events on the launch stream), ms[3]: the
+ * naive-base posteriors (lh_eval_edges_batch only), the edge kernel with its rate weights, path and seed checks and rate
+ * combination, the weighted reduction (lh_eval_edges_batch only); resets the counters. */
+int lh_edges_profile_read(lh_family* fam, double* ms, int64_t* n_launches);
+
 /* Timing of the kernels of the last lh_eval_batch_device call sequence, measured with HIP events
  * on the launch stream when enabled (ms per kernel family: model, prune, forward). */
 int lh_profile_enable(lh_family* fam, int enable);

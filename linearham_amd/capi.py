@@ -81,6 +81,10 @@ EXPORTS += EVENTS_EXPORTS
 ANCESTRAL_EXPORTS = ["lh_asr_marginals_batch", "lh_asr_marginals_batch_device", "lh_eval_ancestral_batch",
                      "lh_eval_ancestral_batch_device", "lh_ancestral_profile_read"]
 EXPORTS += ANCESTRAL_EXPORTS
+# K12 (exact substitution posteriors along the edges of a seed's lineage)
+EDGES_EXPORTS = ["lh_asr_edges_batch", "lh_asr_edges_batch_device", "lh_eval_edges_batch", "lh_eval_edges_batch_device",
+                 "lh_edges_profile_read"]
+EXPORTS += EDGES_EXPORTS
 
 
 class _CodonOutputs(C.Structure):
@@ -122,6 +126,27 @@ class _AncestralOutputs(C.Structure):
 
 class _AncestralOutputsDevice(C.Structure):  # the same members as device addresses
     _fields_ = [(k, C.c_void_p) for k in _ANCESTRAL_MEMBERS]
+
+
+_EDGES_MEMBERS = ("edge", "naive_edge", "chain_counts", "edge_load", "rate_post")
+_EVAL_EDGES_MEMBERS = ("log_offset", "loglik", "site_base", "edge", "naive_edge", "chain_counts", "seed_edge", "edge_load",
+                       "rate_post", "weighted_counts", "weighted_seed_edge", "weighted_naive_edge", "weight_stats")
+
+
+class _EdgesOutputs(C.Structure):
+    _fields_ = [(k, c_f64p) for k in _EDGES_MEMBERS]
+
+
+class _EdgesOutputsDevice(C.Structure):  # the same members as device addresses
+    _fields_ = [(k, C.c_void_p) for k in _EDGES_MEMBERS]
+
+
+class _EvalEdgesOutputs(C.Structure):
+    _fields_ = [(k, c_f64p) for k in _EVAL_EDGES_MEMBERS]
+
+
+class _EvalEdgesOutputsDevice(C.Structure):  # the same members as device addresses
+    _fields_ = [(k, C.c_void_p) for k in _EVAL_EDGES_MEMBERS]
 
 
 class _SamplerJunction(C.Structure):
@@ -273,6 +298,14 @@ class HipLibrary:
             lib.lh_eval_ancestral_batch_device.argtypes = _DEV_TREE + [C.c_void_p, C.c_int32,
                                                                        C.POINTER(_AncestralOutputsDevice), C.c_void_p]
             lib.lh_ancestral_profile_read.argtypes = _PROFILE_READ
+        if hasattr(lib, "lh_asr_edges_batch"):
+            lib.lh_asr_edges_batch.argtypes = _HOST_TREE + [c_f64p, c_i32p, C.c_int32, C.c_int32, C.POINTER(_EdgesOutputs)]
+            lib.lh_asr_edges_batch_device.argtypes = _DEV_TREE + [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                                                  C.POINTER(_EdgesOutputsDevice), C.c_void_p]
+            lib.lh_eval_edges_batch.argtypes = _HOST_TREE + [c_i32p, C.c_int32, C.c_int32, C.POINTER(_EvalEdgesOutputs)]
+            lib.lh_eval_edges_batch_device.argtypes = _DEV_TREE + [C.c_void_p, C.c_int32, C.c_int32,
+                                                                   C.POINTER(_EvalEdgesOutputsDevice), C.c_void_p]
+            lib.lh_edges_profile_read.argtypes = _PROFILE_READ
         if hasattr(lib, "lh_set_device"):      # (absent from round-2 builds loaded through LH_LIB_DIR for comparisons)
             lib.lh_set_device.argtypes = [C.c_int32]
             lib.lh_family_status.argtypes = [C.c_void_p]
@@ -335,6 +368,39 @@ class HipLibrary:
     def ancestral_profile_read(self, family):
         """(k11a_ms, k11b_ms, reduce_ms, launch groups) of K11 since the last read."""
         return self._profile_read("lh_ancestral_profile_read", family, 3)
+
+    def eval_edges_batch(self, family, n_tips, max_depth, ops, brlen, er, pi, alpha, num_rates, path, seed_tip,
+                         log_offset=None, want=("loglik", "chain_counts", "seed_edge", "naive_edge", "edge_load")):
+        """K0-K2 + K5 + K12 on a family handle that has sampler tables; path [n][P] (seed_path rows, -1 padding) of tip
+        `seed_tip`.  Returns a dict with the members of `want`: loglik [n], site_base [n, L, 5], edge [n, P, L, 4, 4],
+        naive_edge [n, L, 5, 4], chain_counts [n, L, 4, 4], seed_edge [n, L, 4, 4], edge_load [n, P+1], rate_post [n, L, R],
+        weighted_counts [L, 4, 4], weighted_seed_edge [L, 4, 4], weighted_naive_edge [L, 5, 4], weight_stats [3].  Tables are
+        indexed [ancestor state][descendant state]; without "edge" the lean kernel runs."""
+        h = _handle(family)
+        n, arrays = _tree_args(ops, brlen, er, pi, alpha)
+        path = _i32(path)
+        assert path.ndim == 2 and path.shape[0] == n
+        P, R = path.shape[1], num_rates
+        _, L = self.candidates_info(h)
+        res, outs = _outputs(_EvalEdgesOutputs, want, log_offset, loglik=(n,), site_base=(n, L, 5), edge=(n, P, L, 4, 4),
+                             naive_edge=(n, L, 5, 4), chain_counts=(n, L, 4, 4), seed_edge=(n, L, 4, 4), edge_load=(n, P + 1),
+                             rate_post=(n, L, R), weighted_counts=(L, 4, 4), weighted_seed_edge=(L, 4, 4),
+                             weighted_naive_edge=(L, 5, 4), weight_stats=(3,))
+        self.check(self.lib.lh_eval_edges_batch(h, n, n_tips, max_depth, *_tree_ptrs(arrays), num_rates, _ptr(path, c_i32p), P,
+                                                int(seed_tip), C.byref(outs)))
+        return res
+
+    def eval_edges_batch_device(self, family, n, n_tips, max_depth, ops_ptr, brlen_ptr, er_ptr, pi_ptr, alpha_ptr, num_rates,
+                                path_ptr, path_len, seed_tip, outs, stream=0):
+        """lh_eval_edges_batch_device on device addresses; outs: dict of the output members' addresses."""
+        o = _EvalEdgesOutputsDevice(**{k: int(v) for k, v in outs.items() if v})
+        self.check(self.lib.lh_eval_edges_batch_device(_handle(family), n, n_tips, max_depth, ops_ptr, brlen_ptr, er_ptr, pi_ptr,
+                                                       alpha_ptr, num_rates, path_ptr, path_len, int(seed_tip), C.byref(o),
+                                                       stream))
+
+    def edges_profile_read(self, family):
+        """(k11a_ms, k12b_ms, reduce_ms, launch groups) of K12 since the last read."""
+        return self._profile_read("lh_edges_profile_read", family, 3)
 
     def posterior_profile_read(self, family):
         return self._profile_read("lh_posterior_profile_read", family)
@@ -919,6 +985,42 @@ class Family:
         """({k11a_ms, k11b_ms, reduce_ms}, launch groups) of K11 since the last read."""
         r = self.hip._profile_read("lh_ancestral_profile_read", self.handle, 3)
         return dict(zip(("k11a_ms", "k11b_ms", "reduce_ms"), r[:3])), r[3]
+
+    # ---- K12: exact substitution posteriors along the edges of a lineage ----
+    def asr_edges_batch(self, n_tips, max_depth, ops, brlen, er, pi, rates, naive_prob, path, seed_tip,
+                        want=_EDGES_MEMBERS):
+        """lh_asr_edges_batch: asr_marginals_batch's inputs and the seed's tip id (a child of every row's path[0]); returns
+        a dict with the members of `want`: edge [n][P][L][4][4], naive_edge [n][L][5][4], chain_counts [n][L][4][4],
+        edge_load [n][P+1], rate_post [n][L][R], tables indexed [ancestor state][descendant state].  Without "edge" the
+        lean kernel runs."""
+        _, arrays = _tree_args(ops, brlen, er, pi, rates)
+        ops, brlen, er, pi, rates = arrays
+        naive_prob = _f64(naive_prob)
+        path = _i32(path)
+        n, L = naive_prob.shape[:2]
+        assert naive_prob.shape == (n, L, 5) and path.ndim == 2 and path.shape[0] == n
+        assert ops.shape == (n, n_tips - 2, 4) and brlen.shape == (n, 2 * n_tips - 2)
+        assert er.shape == (n, 6) and pi.shape == (n, 4) and rates.shape[0] == n
+        P, R = path.shape[1], rates.shape[1]
+        res, outs = _outputs(_EdgesOutputs, want, edge=(n, P, L, 4, 4), naive_edge=(n, L, 5, 4), chain_counts=(n, L, 4, 4),
+                             edge_load=(n, P + 1), rate_post=(n, L, R))
+        self.hip.check(self.hip.lib.lh_asr_edges_batch(
+            self.handle, n, n_tips, max_depth, *_tree_ptrs(arrays), R, _ptr(naive_prob), _ptr(path, c_i32p), P, int(seed_tip),
+            C.byref(outs)))
+        return res
+
+    def asr_edges_batch_device(self, n, n_tips, max_depth, ops_ptr, brlen_ptr, er_ptr, pi_ptr, rates_ptr, num_rates,
+                               naive_prob_ptr, path_ptr, path_len, seed_tip, outs, stream=0):
+        """lh_asr_edges_batch_device on device addresses, enqueued on `stream`; outs: dict of the members' addresses."""
+        o = _EdgesOutputsDevice(**{k: int(v) for k, v in outs.items() if v})
+        self.hip.check(self.hip.lib.lh_asr_edges_batch_device(
+            self.handle, n, n_tips, max_depth, ops_ptr, brlen_ptr, er_ptr, pi_ptr, rates_ptr, num_rates, naive_prob_ptr,
+            path_ptr, path_len, int(seed_tip), C.byref(o), stream))
+
+    def edges_profile_read(self):
+        """({k11a_ms, k12b_ms, reduce_ms}, launch groups) of K12 since the last read."""
+        r = self.hip._profile_read("lh_edges_profile_read", self.handle, 3)
+        return dict(zip(("k11a_ms", "k12b_ms", "reduce_ms"), r[:3])), r[3]
 
     # ---- K7: the lineage of a seed sequence and the lineage store ----
     def lineage_batch(self, n_tips, max_depth, ops, brlen, er, pi, rates, naive, seed, path, first_sample=0):

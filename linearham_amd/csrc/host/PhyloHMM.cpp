@@ -2007,6 +2007,155 @@ void PhyloHMM::RunAncestralMarginalsPipeline(const std::string& input_path, cons
 }
 
 
+// ---- K12: exact substitution posteriors along the edges of a seed's lineage ----
+
+PhyloHMM::LineageSubstitutionsResult PhyloHMM::LineageSubstitutions(const std::string& seed_seq) {
+  Require(have_tree_, "InitializePhyloParameters must be called first");
+  const int seed_tip = SeedTip(seed_seq);
+  CreateFamily();
+  Require(device_sampler_, "the family has no device sampler tables (needed by the posterior kernel)");
+  const int T = tree_.n_tips, R = num_rates_;
+  const std::size_t L = (std::size_t)msa_.cols();
+  std::vector<int32_t> ops((std::size_t)(T - 2) * 4);
+  int32_t depth = 0;
+  CheckHip(lh_schedule_tree(T, tree_.children.data(), tree_.root, ops.data(), &depth), "lh_schedule_tree");
+  LineageSubstitutionsResult res;
+  res.nodes = SeedPath(tree_.children.data(), T, tree_.root, seed_tip);
+  Require(!res.nodes.empty(), "the seed sequence '" + seed_seq + "' does not descend from the root");
+  const std::size_t P = res.nodes.size();
+  res.n_sites = (int)L;
+  res.edge.assign(P * L * 16, 0.0);
+  res.naive_edge.assign(L * 20, 0.0);
+  res.chain_counts.assign(L * 16, 0.0);
+  std::vector<double> load(P + 1, 0.0);
+  lh_eval_edges_outputs outs{};
+  outs.loglik = &res.loglik;
+  outs.edge = res.edge.data();
+  outs.naive_edge = res.naive_edge.data();
+  outs.chain_counts = res.chain_counts.data();
+  outs.edge_load = load.data();
+  CheckHip(lh_eval_edges_batch(family_, 1, T, depth, ops.data(), tree_.brlen.data(), er_.data(), pi_.data(), &alpha_, R,
+                               res.nodes.data(), (int32_t)P, seed_tip, &outs),
+           "lh_eval_edges_batch");
+  res.edges.resize(P + 1);
+  for (std::size_t s = 0; s <= P; ++s) {
+    LineageSubstitutionsResult::Edge& e = res.edges[s];
+    e.upper = s < P ? res.nodes[s] : 0;
+    e.lower = s == P ? res.nodes[P - 1] : s == 0 ? seed_tip : res.nodes[s - 1];
+    e.brlen = tree_.brlen[s == P ? 0 : e.lower];
+    e.load = load[s];
+  }
+  return res;
+}
+
+void PhyloHMM::WritePairTable(std::ostream& o, const double* table, std::size_t n_sites, int n_rows, bool with_sum) {
+  static const char kBases[] = "ACGTN";
+  o << "site";
+  for (int a = 0; a < n_rows; ++a)
+    for (int c = 0; c < 4; ++c) o << '\t' << kBases[a] << kBases[c];
+  if (with_sum) o << "\tsubstitutions";
+  o << '\n';
+  for (std::size_t s = 0; s < n_sites; ++s) {
+    const double* p = table + s * (std::size_t)n_rows * 4;
+    o << s;
+    double off = 0.0;
+    for (int a = 0; a < n_rows; ++a)
+      for (int c = 0; c < 4; ++c) {
+        o << '\t' << Fmt17(p[a * 4 + c]);
+        if (a < 4 && a != c) off += p[a * 4 + c];
+      }
+    if (with_sum) o << '\t' << Fmt17(off);
+    o << '\n';
+  }
+}
+
+void PhyloHMM::RunLineageSubstitutionsPipeline(const std::string& input_path, const std::string& seed_seq,
+                                               const std::string& output_prefix, int num_rates, double burnin_frac) {
+  Require(devices_.size() <= 1, "the lineage substitutions pipeline runs on one device: --devices may list only one");
+  Require(burnin_frac >= 0.0 && burnin_frac < 1.0, "burn-in fraction must be in [0, 1)");
+  const int seed_tip = SeedTip(seed_seq);
+  CreateFamily();
+  Require(device_sampler_, "the family has no device sampler tables (needed by the posterior kernel)");
+  const int T = (int)xmsa_labels_.size(), R = num_rates;
+  const std::size_t L = (std::size_t)msa_.cols();
+  TsvTable table = TsvTable::OpenRevBayesTable(input_path);
+  const std::size_t N = table.rows.size();
+  const std::size_t first = (std::size_t)std::floor(burnin_frac * (double)N);
+  // only the rows' reductions come back (52 L + P + 1 doubles each): a batch is bounded by at most 512 MiB of them
+  const std::size_t NC = L * 16, NN = L * 20, NROW = 2 * NC + NN;
+  const std::size_t fit = std::max<std::size_t>(1, ((std::size_t)512 << 20) / (sizeof(double) * (NROW + (std::size_t)T)));
+  const std::size_t kBatch = host_options().pipeline_batch > 0 ? (std::size_t)host_options().pipeline_batch
+                                                                : std::min<std::size_t>(8192, fit);
+  // the rows' tables are added up on the host in row order: the files do not depend on the batch size
+  WeightedSums acc(NROW);
+  std::vector<double> cc, se, ne, load, row(NROW);
+  std::vector<double> lw(N - first), subs(N - first, 0.0);
+  std::vector<int32_t> path_len(N - first, 0);
+  std::size_t skipped = 0;
+  for (std::size_t off = first; off < N; off += kBatch) {
+    const std::size_t m = std::min(kBatch, N - off);
+    TableBatch tb = FlattenTable(table, off, off + m, false, true, input_path, true);
+    const DeviceBatch& b = tb.dev;
+    std::vector<std::vector<int32_t>> chain(m);
+    std::size_t P = 1;
+    for (std::size_t i = 0; i < m; ++i) {
+      chain[i] = SeedPath(tb.children.data() + i * 2 * (std::size_t)(T - 2), T, tb.root[i], seed_tip);
+      Require(!chain[i].empty(),
+              "row " + std::to_string(off + i) + ": the seed sequence '" + seed_seq + "' does not descend from the root");
+      P = std::max(P, chain[i].size());
+    }
+    std::vector<int32_t> path(m * P, -1);
+    for (std::size_t i = 0; i < m; ++i) std::copy(chain[i].begin(), chain[i].end(), path.begin() + i * P);
+    std::vector<double> ll(m);
+    cc.resize(m * NC);
+    se.resize(m * NC);
+    ne.resize(m * NN);
+    load.resize(m * (P + 1));
+    lh_eval_edges_outputs outs{};
+    outs.loglik = ll.data();
+    outs.chain_counts = cc.data();
+    outs.seed_edge = se.data();
+    outs.naive_edge = ne.data();
+    outs.edge_load = load.data();
+    CheckHip(lh_eval_edges_batch(family_, b.n, b.n_tips, b.max_depth, b.ops.data(), b.brlen.data(), b.er.data(), b.pi.data(),
+                                 b.alpha.data(), R, path.data(), (int32_t)P, seed_tip, &outs),
+             "lh_eval_edges_batch");
+    for (std::size_t i = 0; i < m; ++i) {
+      const std::size_t u = off - first + i;
+      const double st[3] = {ll[i] - tb.lik[i], 1.0, 1.0};  // one row, its weight relative to itself
+      lw[u] = st[0];
+      path_len[u] = (int32_t)chain[i].size();
+      const double* li = load.data() + i * (P + 1);
+      double total = li[P];  // the naive edge, then the slots from the MRCA down (padding slots hold 0)
+      for (std::size_t s = chain[i].size(); s-- > 0;) total += li[s];
+      subs[u] = total;
+      if (!std::isfinite(st[0])) {
+        ++skipped;
+        continue;
+      }
+      std::copy(cc.begin() + i * NC, cc.begin() + (i + 1) * NC, row.begin());
+      std::copy(se.begin() + i * NC, se.begin() + (i + 1) * NC, row.begin() + NC);
+      std::copy(ne.begin() + i * NN, ne.begin() + (i + 1) * NN, row.begin() + 2 * NC);
+      acc.Add(row.data(), st);
+    }
+  }
+  Require(acc.s1 > 0.0, "lineage substitutions pipeline: no row with a finite weight");
+  acc.Normalise();
+  std::ofstream counts(output_prefix + ".substitutions.tsv"), seed(output_prefix + ".seed_edge.tsv"),
+      naive(output_prefix + ".naive_edge.tsv"), rows(output_prefix + ".rows.tsv"), summary(output_prefix + ".summary.tsv");
+  Require(counts.good() && seed.good() && naive.good() && rows.good() && summary.good(), "Can't write " + output_prefix + ".*.tsv");
+  WritePairTable(counts, acc.total.data(), L, 4, true);
+  WritePairTable(seed, acc.total.data() + NC, L, 4, false);
+  WritePairTable(naive, acc.total.data() + 2 * NC, L, 5, false);
+  rows << "row\tweight\tchain_length\texpected_substitutions\n";
+  for (std::size_t u = 0; u < lw.size(); ++u)
+    rows << (first + u) << '\t' << Fmt17(std::isfinite(lw[u]) ? std::exp(lw[u] - acc.mx) : 0.0) << '\t' << path_len[u] << '\t'
+         << Fmt17(subs[u]) << '\n';
+  summary << "key\tvalue\nrows_used\t" << (N - first - skipped) << "\nrows_skipped_nonfinite\t" << skipped << "\nkish_ess\t"
+          << Fmt17(acc.KishEss()) << "\n";
+}
+
+
 // ---- K9: codon and amino-acid marginals ----
 
 namespace {

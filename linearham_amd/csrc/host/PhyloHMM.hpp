@@ -226,6 +226,35 @@ class PhyloHMM : public HMM {
   /// probabilities, the arg-max base), .rates.tsv, .rows.tsv (row, weight, chain_length) and .summary.tsv.
   void RunAncestralMarginalsPipeline(const std::string& input_path, const std::string& seed_seq,
                                      const std::string& output_prefix, int num_rates, double burnin_frac);
+  /// K12: exact substitution posteriors along the edges of the lineage of the tip `seed_seq` (lh_eval_edges_batch).  Tables
+  /// are indexed [ancestor state][descendant state], naive the oldest node.
+  struct LineageSubstitutionsResult {
+    struct Edge {
+      int32_t upper = 0, lower = 0;  // nodes in lh_schedule_tree's numbering (0 = naive, tips 1 .. T-1)
+      double brlen = 0.0;            // of the lower node's branch (the naive edge: naive's)
+      double load = 0.0;             // the expected number of sites whose two ends differ
+    };
+    std::vector<int32_t> nodes;        // [P] the lineage: slot 0 the seed's parent, the last one the MRCA
+    std::vector<Edge> edges;           // [P+1]: [s] the edge below slot s ([0] ends at the seed tip), [P] naive -> MRCA
+    std::vector<double> edge;          // [P][L][4][4]
+    std::vector<double> naive_edge;    // [L][5][4]
+    std::vector<double> chain_counts;  // [L][4][4] expected number of lineage edges on which the site goes from a to c
+    int n_sites = 0;
+    double loglik = 0.0;
+  };
+  /// After InitializePhyloParameters: the tables of the current tree.
+  LineageSubstitutionsResult LineageSubstitutions(const std::string& seed_seq);
+  /// The importance-weighted chain_counts, seed-edge and naive-edge tables -- the three that mean the same in every tree --
+  /// over a RevBayes table, with RunAncestralMarginalsPipeline's reader, burn-in, weights, Kish ESS and one-device rule.
+  /// Only the per-row reductions come back from the device (the lean kernel runs); they are added up on the host in row
+  /// order, so the files do not depend on LH_PIPELINE_BATCH.  Writes <prefix>.substitutions.tsv (site, the 16 weighted
+  /// counts, their off-diagonal sum), .seed_edge.tsv, .naive_edge.tsv, .rows.tsv (row, weight, chain_length, the row's
+  /// expected number of differing edge ends over all sites) and .summary.tsv.
+  void RunLineageSubstitutionsPipeline(const std::string& input_path, const std::string& seed_seq,
+                                       const std::string& output_prefix, int num_rates, double burnin_frac);
+  /// site, then one column per cell named <ancestor base><descendant base> (n_rows x 4 cells, rows over ACGTN), and with
+  /// `with_sum` the off-diagonal sum of the first four rows; numbers printed with %.17g
+  static void WritePairTable(std::ostream& o, const double* table, std::size_t n_sites, int n_rows, bool with_sum);
   /// site, A, C, G, T, map_base / site, rate0 ..; numbers printed with %.17g
   static void WriteNodeTable(std::ostream& o, const double* table, std::size_t n_sites);
   static void WriteRateTable(std::ostream& o, const double* rate_post, std::size_t n_sites, int num_rates);

@@ -317,6 +317,47 @@ int lhh_run_ancestral_marginals_pipeline(void* h, const char* input_path, const 
   });
 }
 
+// PhyloHMM::LineageSubstitutions: nodes [cap_slots], edge [cap_slots][L][16], naive_edge [L][20], chain_counts [L][16],
+// edges [cap_slots + 1][4] (upper node, lower node, branch length, load); *n_slots receives the chain's length.
+int lhh_phylo_lineage_substitutions(void* h, const char* seed_seq, int32_t* nodes, double* edge, double* naive_edge,
+                                    double* chain_counts, double* edges, int cap_slots, int* n_slots, double* loglik) {
+  return Guard([&] {
+    const PhyloHMM::LineageSubstitutionsResult r = dynamic_cast<PhyloHMM&>(*static_cast<HMM*>(h)).LineageSubstitutions(seed_seq);
+    if ((int)r.nodes.size() > cap_slots) throw std::runtime_error("lhh_phylo_lineage_substitutions: output too small");
+    *n_slots = (int)r.nodes.size();
+    std::copy(r.nodes.begin(), r.nodes.end(), nodes);
+    std::copy(r.edge.begin(), r.edge.end(), edge);
+    std::copy(r.naive_edge.begin(), r.naive_edge.end(), naive_edge);
+    std::copy(r.chain_counts.begin(), r.chain_counts.end(), chain_counts);
+    for (std::size_t e = 0; e < r.edges.size(); ++e) {
+      edges[e * 4] = r.edges[e].upper;
+      edges[e * 4 + 1] = r.edges[e].lower;
+      edges[e * 4 + 2] = r.edges[e].brlen;
+      edges[e * 4 + 3] = r.edges[e].load;
+    }
+    if (loglik) *loglik = r.loglik;
+  });
+}
+
+// PhyloHMM::WritePairTable's text of table [n_sites][n_rows][4]
+int lhh_write_pair_table(const double* table, int n_sites, int n_rows, int with_sum, const char** out) {
+  return Guard([&] {
+    if (n_sites < 0 || n_rows < 1 || n_rows > 5) throw std::runtime_error("lhh_write_pair_table: bad shape");
+    std::ostringstream o;
+    PhyloHMM::WritePairTable(o, table, (std::size_t)n_sites, n_rows, with_sum != 0);
+    g_out = o.str();
+    *out = g_out.c_str();
+  });
+}
+
+int lhh_run_lineage_substitutions_pipeline(void* h, const char* input_path, const char* seed_seq, const char* output_prefix,
+                                           int num_rates, double burnin_frac) {
+  return Guard([&] {
+    dynamic_cast<PhyloHMM&>(*static_cast<HMM*>(h)).RunLineageSubstitutionsPipeline(input_path, seed_seq, output_prefix, num_rates,
+                                                                                 burnin_frac);
+  });
+}
+
 // PhyloHMM::NaiveCodonMarginals: table [cap_codons][125]; *n_codons receives the count; the amino-acid table
 // (WriteAminoAcidTable) in *aa.  table == NULL: only *n_codons, nothing is evaluated.
 int lhh_phylo_codon_marginals(void* h, int frame, double* table, int cap_codons, int* n_codons, const char** aa) {

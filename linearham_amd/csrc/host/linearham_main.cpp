@@ -65,7 +65,7 @@ int main(int argc, char** argv) {
   try {
     if (argc < 2 || std::string(argv[1]) == "-h" || std::string(argv[1]) == "--help") {
       std::cout << "A Phylo-HMM implementation for B cell receptor sequence analysis.\n"
-                   "USAGE: linearham {--compute-logl|--sample|--pipeline|--asr|--marginals|--marginals-pipeline|--naive-probs|--naive-probs-pipeline|--lineage-pipeline|--weighted-lineage-pipeline|--viterbi|--annotations-pipeline|--codon-marginals|--codon-marginals-pipeline|--events|--events-pipeline|--ancestral-marginals|--ancestral-marginals-pipeline} --yaml-path <string> "
+                   "USAGE: linearham {--compute-logl|--sample|--pipeline|--asr|--marginals|--marginals-pipeline|--naive-probs|--naive-probs-pipeline|--lineage-pipeline|--weighted-lineage-pipeline|--viterbi|--annotations-pipeline|--codon-marginals|--codon-marginals-pipeline|--events|--events-pipeline|--ancestral-marginals|--ancestral-marginals-pipeline|--lineage-substitutions|--lineage-substitutions-pipeline} --yaml-path <string> "
                    "--cluster-ind <int> --hmm-param-dir <string> [--seed <int>] [--num-rates <int>] [--extended-range <0|1>] "
                    "[--devices <a,b,...>] ...\n"
                    "  --marginals: the arguments of --compute-logl; prints the per-site naive-base table and the gene table\n"
@@ -95,6 +95,13 @@ int main(int argc, char** argv) {
                    "  --ancestral-marginals-pipeline --input-path <RevBayes table> --output-path <prefix> --seed-seq <name>\n"
                    "    [--burnin-frac <f>]: writes <prefix>.parent.tsv, <prefix>.mrca.tsv, <prefix>.rates.tsv, <prefix>.rows.tsv\n"
                    "    and <prefix>.summary.tsv (one device)\n"
+                   "  --lineage-substitutions --seed-seq <name>: the arguments of --marginals; prints the edges of the lineage from\n"
+                   "    the sequence <name> up to naive (upper node, lower node, branch length, expected number of sites whose two\n"
+                   "    ends differ), the per-site expected number of lineage edges on which the site goes from one base to another,\n"
+                   "    then per edge the exact joint table of its two ends' bases ([ancestor][descendant]), the naive edge last\n"
+                   "  --lineage-substitutions-pipeline --input-path <RevBayes table> --output-path <prefix> --seed-seq <name>\n"
+                   "    [--burnin-frac <f>]: writes <prefix>.substitutions.tsv, <prefix>.seed_edge.tsv, <prefix>.naive_edge.tsv,\n"
+                   "    <prefix>.rows.tsv and <prefix>.summary.tsv (one device)\n"
                    "  --lineage-pipeline --input-path <--pipeline table> --output-path <prefix> --seed-seq <name> [--seed <int>]:\n"
                    "    the lineage tables of the sequence <name>: <prefix>.fasta, .dnamap, .nodes.tsv, .edges.tsv, .summary.tsv\n"
                    "       linearham --lineage-trees --input-path <--asr trees> --output-path <prefix> --seed-seq <name>\n"
@@ -123,7 +130,8 @@ int main(int argc, char** argv) {
         subcmd != "--naive-probs-pipeline" && subcmd != "--lineage-pipeline" && subcmd != "--weighted-lineage-pipeline" &&
         subcmd != "--viterbi" && subcmd != "--annotations-pipeline" && subcmd != "--codon-marginals" &&
         subcmd != "--codon-marginals-pipeline" && subcmd != "--events" && subcmd != "--events-pipeline" &&
-        subcmd != "--ancestral-marginals" && subcmd != "--ancestral-marginals-pipeline")
+        subcmd != "--ancestral-marginals" && subcmd != "--ancestral-marginals-pipeline" &&
+        subcmd != "--lineage-substitutions" && subcmd != "--lineage-substitutions-pipeline")
       throw std::invalid_argument("'" + subcmd + "' is not a valid subcommand.");
     const std::string yaml_path = a.one("yaml-path");
     const int cluster_ind = std::stoi(a.one("cluster-ind"));
@@ -144,7 +152,7 @@ int main(int argc, char** argv) {
       if (device_list.size() > 1 && (subcmd == "--marginals-pipeline" || subcmd == "--naive-probs-pipeline" ||
                                      subcmd == "--weighted-lineage-pipeline" || subcmd == "--annotations-pipeline" ||
                                      subcmd == "--codon-marginals-pipeline" || subcmd == "--events-pipeline" ||
-                                     subcmd == "--ancestral-marginals-pipeline"))
+                                     subcmd == "--ancestral-marginals-pipeline" || subcmd == "--lineage-substitutions-pipeline"))
         throw std::invalid_argument(subcmd + " runs on one device: --devices may list only one");
       if (device_list.size() > 1 && subcmd != "--pipeline")
         std::fprintf(stderr, "linearham: %s evaluates on one device; of --devices only device %d is used\n", subcmd.c_str(),
@@ -197,6 +205,11 @@ int main(int argc, char** argv) {
     if (subcmd == "--ancestral-marginals-pipeline") {
       phylo_hmm_ptr->RunAncestralMarginalsPipeline(a.one("input-path"), a.one("seed-seq"), a.one("output-path"), num_rates,
                                                    std::stod(a.opt("burnin-frac", "0")));
+      return EXIT_SUCCESS;
+    }
+    if (subcmd == "--lineage-substitutions-pipeline") {
+      phylo_hmm_ptr->RunLineageSubstitutionsPipeline(a.one("input-path"), a.one("seed-seq"), a.one("output-path"), num_rates,
+                                                     std::stod(a.opt("burnin-frac", "0")));
       return EXIT_SUCCESS;
     }
     if (subcmd == "--naive-probs-pipeline") {
@@ -266,6 +279,23 @@ int main(int argc, char** argv) {
         std::cout << "\n";
       }
       linearham::PhyloHMM::WriteRateTable(std::cout, m.rate_post.data(), L, m.num_rates);
+    } else if (subcmd == "--lineage-substitutions") {
+      const linearham::PhyloHMM::LineageSubstitutionsResult m = phylo_hmm_ptr->LineageSubstitutions(a.one("seed-seq"));
+      const std::size_t L = (std::size_t)m.n_sites, P = m.nodes.size();
+      char buf[96];
+      std::cout << "edge\tupper\tlower\tbrlen\texpected_substitutions\n";
+      for (std::size_t e = 0; e <= P; ++e) {
+        std::snprintf(buf, sizeof buf, "%.17g\t%.17g", m.edges[e].brlen, m.edges[e].load);
+        std::cout << e << '\t' << m.edges[e].upper << '\t' << m.edges[e].lower << '\t' << buf << "\n";
+      }
+      std::cout << "\n";
+      linearham::PhyloHMM::WritePairTable(std::cout, m.chain_counts.data(), L, 4, true);
+      for (std::size_t s = 0; s < P; ++s) {
+        std::cout << "\nedge\t" << s << "\tupper\t" << m.edges[s].upper << "\tlower\t" << m.edges[s].lower << "\n";
+        linearham::PhyloHMM::WritePairTable(std::cout, m.edge.data() + s * L * 16, L, 4, false);
+      }
+      std::cout << "\nedge\t" << P << "\tupper\t" << m.edges[P].upper << "\tlower\t" << m.edges[P].lower << "\n";
+      linearham::PhyloHMM::WritePairTable(std::cout, m.naive_edge.data(), L, 5, false);
     } else if (subcmd == "--marginals") {
       const linearham::PhyloHMM::NaiveMarginalsResult m = phylo_hmm_ptr->NaiveMarginals();
       linearham::PhyloHMM::WriteSiteTable(std::cout, m);

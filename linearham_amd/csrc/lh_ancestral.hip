@@ -41,29 +41,6 @@ namespace lh {
 
 namespace {
 
-__device__ __forceinline__ void anc_tip_col(const double* tiptab, int tip, int st, double (&c)[4]) {
-  const double* t = tiptab + tip * 16;
-  if (st < 4) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) c[i] = t[st * 4 + i];
-  } else {  // N: row sums of P, as K3
-#pragma unroll
-    for (int i = 0; i < 4; ++i) c[i] = ((t[i] + t[4 + i]) + t[8 + i]) + t[12 + i];
-  }
-}
-
-// x = P a, P row-major in LDS at a wave-uniform address
-__device__ __forceinline__ void anc_matvec(const double* p, const double (&a)[4], double (&x)[4]) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) x[i] = fma(p[i * 4 + 3], a[3], fma(p[i * 4 + 2], a[2], fma(p[i * 4 + 1], a[1], p[i * 4] * a[0])));
-}
-
-// x = a^T P
-__device__ __forceinline__ void anc_vecmat(const double* p, const double (&a)[4], double (&x)[4]) {
-#pragma unroll
-  for (int c = 0; c < 4; ++c) x[c] = fma(p[12 + c], a[3], fma(p[8 + c], a[2], fma(p[4 + c], a[1], p[c] * a[0])));
-}
-
 __device__ __forceinline__ double anc_aligned(double v, int d) {
   for (int q = 0; q < d && v != 0.0; ++q) v *= kScaleThreshold;
   return v;
@@ -250,7 +227,6 @@ __global__ void __launch_bounds__(256) anc_kernel(int R, int T, int L, int n_pru
   const int sample = blockIdx.y, rate = blockIdx.x;
   const int len = plen[sample];
   if (len == 0) return;  // K11m writes the row's NaN
-  const int NP = n_prune + 1;  // patterns, the all-N one (id n_prune) included
   double* tiptab = reinterpret_cast<double*>(anc_smem);  // [T][4][4] columns of P
   double* pin = tiptab + (size_t)T * 16;                 // [n_ops][4][4] row-major, by the op that produced the child
   const int tid = threadIdx.x, lane = tid & 63;
@@ -260,70 +236,15 @@ __global__ void __launch_bounds__(256) anc_kernel(int R, int T, int L, int n_pru
   const double* __restrict__ e = eig + (size_t)sample * 36;
   const double rt = rates[(size_t)sample * R + rate];
   const double* __restrict__ bl = brlen + (size_t)sample * (2 * (size_t)T - 2);
-  {
-    double Pm[4][4];
-    for (int j = tid; j < T + n_ops - 1; j += blockDim.x) {
-      if (j < T) {
-        compute_pmatrix(e, bl[j] * rt, Pm);
-        double* o = tiptab + j * 16;
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-          for (int st = 0; st < 4; ++st) o[st * 4 + i] = Pm[i][st];
-      } else {
-        const int k = j - T;  // op k < n_ops - 1 produced inner node T + b.z, whose branch this is
-        compute_pmatrix(e, bl[T + dsc[k].b.z] * rt, Pm);
-        double* o = pin + (size_t)k * 16;
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-          for (int q = 0; q < 4; ++q) o[i * 4 + q] = Pm[i][q];
-      }
-    }
-  }
+  anc_fill_tables(T, dsc, e, bl, rt, tiptab, pin);
   __syncthreads();
 
   // CLV area of this (sample, rate): [op][2][Lp] double2, components (0,1) and (2,3) of a pattern in two planes
   const size_t plane = (size_t)Lp;
   double2* clv_s = clv + ((size_t)sample * R + rate) * n_ops * 2 * plane;
 
-  // ---- upward pass, a lane per pattern (lanes past the last pattern repeat it: same values, no predicate)
-  for (int s0 = wave * 64; s0 < NP; s0 += n_waves * 64) {
-    const int pat = min(s0 + lane, NP - 1);
-    const bool all_n = pat >= n_prune;
-    double a[4] = {1.0, 1.0, 1.0, 1.0};
-    for (int k = 0; k < n_ops; ++k) {
-      const int4 da = dsc[k].a, db = dsc[k].b;
-      const int kind = da.x & 15;
-      double u[4], v[4];
-      if (kind == OP_CHERRY) {
-        const int sa = all_n ? 4 : (int)msa[(size_t)da.y * n_prune + pat];
-        const int sb = all_n ? 4 : (int)msa[(size_t)da.z * n_prune + pat];
-        anc_tip_col(tiptab, db.x, sa, u);
-        anc_tip_col(tiptab, db.y, sb, v);
-      } else {
-        anc_matvec(pin + (size_t)(k - 1) * 16, a, v);
-        if (kind == OP_TIP_ACC) {
-          const int sa = all_n ? 4 : (int)msa[(size_t)da.y * n_prune + pat];
-          anc_tip_col(tiptab, db.x, sa, u);
-        } else {
-          const double2* cq = clv_s + (size_t)da.w * 2 * plane + pat;
-          const double2 lo = cq[0], hi = cq[plane];
-          const double y[4] = {lo.x, lo.y, hi.x, hi.y};
-          anc_matvec(pin + (size_t)da.w * 16, y, u);
-        }
-      }
-#pragma unroll
-      for (int q = 0; q < 4; ++q) a[q] = u[q] * v[q];
-      if (fmax(fmax(a[0], a[1]), fmax(a[2], a[3])) < kScaleThreshold) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) a[q] *= kScaleFactor;
-      }
-      double2* ck = clv_s + (size_t)k * 2 * plane + pat;
-      ck[0] = make_double2(a[0], a[1]);
-      ck[plane] = make_double2(a[2], a[3]);
-    }
-  }
+  // ---- upward pass, a lane per pattern
+  anc_upward(n_ops, n_prune, msa, dsc, tiptab, pin, clv_s, plane, wave, n_waves, lane);
   // the sites' lanes below read CLVs that other lanes and waves of this workgroup stored above
   __threadfence_block();
   __syncthreads();
@@ -423,9 +344,9 @@ __global__ void __launch_bounds__(256) anc_combine_kernel(int n, int R, int P, i
   o[1] = hi;
 }
 
-size_t anc_lp(int n_prune) { return ((size_t)n_prune + 1 + 7) & ~(size_t)7; }
-
 }  // namespace
+
+size_t anc_lp(int n_prune) { return ((size_t)n_prune + 1 + 7) & ~(size_t)7; }
 
 void launch_site_base(int n, int L, size_t forward_size, const int32_t* off, const int32_t* idx, const double* post,
                       const double* loglik, double* site_base, hipStream_t stream) {
@@ -453,6 +374,20 @@ AncWsBytes anc_ws_bytes(int T, int L, int R, int n_prune, int P) {
   return b;
 }
 
+void launch_ancestral_front(const DevFamily& fam, int n, int R, int T, const int32_t* ops, const double* pi,
+                            const double* site_lik, const int32_t* site_scal, const double* naive_prob, const int32_t* path,
+                            int P, const AncWs& ws, double* rate_post, const int4* hdr, int32_t* err_flag, hipStream_t stream) {
+  const int L = fam.n_sites;
+  double* rho = rate_post ? rate_post : ws.rho;
+  const long long cells = (long long)n * L;
+  hipLaunchKernelGGL(anc_rate_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, stream, n, R, L, fam.n_prune,
+                     fam.site_pat, site_lik, site_scal, naive_prob, pi, ws.tvec, rho);
+  if (!path) return;
+  launch_asr_sched(n, T, ops, hdr, ws.desc, stream);
+  hipLaunchKernelGGL(anc_chain_kernel, dim3(n), dim3(64), sizeof(int32_t) * (size_t)(T - 2), stream, T, P,
+                     static_cast<const AsrOp*>(ws.desc), hdr, path, ws.chain, ws.plen, err_flag);
+}
+
 int launch_ancestral(const DevFamily& fam, int n, int R, int T, const int32_t* ops, const double* brlen, const double* rates,
                      const double* eig, const double* pi, const double* site_lik, const int32_t* site_scal,
                      const double* naive_prob, const int32_t* path, int P, const AncWs& ws, double* marg, double* rate_post,
@@ -462,13 +397,9 @@ int launch_ancestral(const DevFamily& fam, int n, int R, int T, const int32_t* o
   const size_t lds = anc_lds_bytes(T);
   if (lds > 160 * 1024) return 1;
   double* rho = rate_post ? rate_post : ws.rho;
-  const long long cells = (long long)n * L;
-  hipLaunchKernelGGL(anc_rate_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, stream, n, R, L, fam.n_prune,
-                     fam.site_pat, site_lik, site_scal, naive_prob, pi, ws.tvec, rho);
+  launch_ancestral_front(fam, n, R, T, ops, pi, site_lik, site_scal, naive_prob, marg ? path : nullptr, P, ws, rate_post, hdr,
+                         err_flag, stream);
   if (!marg) return 0;
-  launch_asr_sched(n, T, ops, hdr, ws.desc, stream);
-  hipLaunchKernelGGL(anc_chain_kernel, dim3(n), dim3(64), sizeof(int32_t) * (size_t)(T - 2), stream, T, P,
-                     static_cast<const AsrOp*>(ws.desc), hdr, path, ws.chain, ws.plen, err_flag);
   if (lds > 64 * 1024)
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(anc_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   hipLaunchKernelGGL(anc_kernel, dim3(R, n), dim3(256), lds, stream, R, T, L, fam.n_prune, P, fam.msa, fam.site_pat,

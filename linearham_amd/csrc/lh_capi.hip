@@ -39,6 +39,7 @@ const DebugOptions& debug_options() {
     o.codon_blocks = std::max(1, num("LH_CODON_BLOCKS", o.codon_blocks));
     o.events_blocks = std::max(1, num("LH_EVENTS_BLOCKS", o.events_blocks));
     o.anc_out_mb = std::max(1, num("LH_ANC_OUT_MB", o.anc_out_mb));
+    o.edge_out_mb = std::max(1, num("LH_EDGE_OUT_MB", o.edge_out_mb));
     o.collect_hash_bits = std::min(64, std::max(1, num("LH_COLLECT_HASH_BITS", o.collect_hash_bits)));
     return o;
   }();
@@ -232,6 +233,12 @@ struct AncestralWs {  // K11's scratch (lh::AncWs) and the arrays its callers do
   DevBuf out_wsum, out_wrate;
 };
 
+struct EdgesWs {  // K12's scratch beside K11's (lh::SubWs) and the outputs its callers do not take
+  DevBuf cc, ne, se, el, edge;
+  DevBuf out_edge, out_ne, out_cc, out_se, out_el, out_wcc, out_wse, out_wne;
+  DevBuf partial_c, partial_s, partial_n;  // the weighted reduction's slabs
+};
+
 struct PosteriorWs {  // K5's arrays that the caller of lh_eval_posterior_batch_device does not hand in
   DevBuf loglik, weights, stats, partial;
 };
@@ -405,6 +412,7 @@ struct lh_family {
   CollectWs collect;
   LineageWs lineage;
   AncestralWs anc;
+  EdgesWs edges;
   // forward arrays that stay on the device, shared by K4 and K5 in both their forms: K4 draws from them, K5 overwrites
   // them with the posteriors (calls on a handle do not overlap: they also share the workspace)
   DevBuf forward_dev;
@@ -423,6 +431,7 @@ struct lh_family {
   KernelTimer<2> events_timer;              // K10: K5's pass on the copy, K10 and its reduction
   KernelTimer<1> lineage_timer;             // K7
   KernelTimer<3> anc_timer;                 // K11: K11a, K11b (with K11r, K11c, K11m), the weighted reduction
+  KernelTimer<3> edges_timer;               // K12: K11a, K12b (with K11r, K11c, K12c, K12m), the weighted reduction
   KernelTimer<5> chain_timer;               // lh_eval_lineage_batch: K0, K1, K2 + K4 + K6c, K3, K7
   bool extended = false;  // lh_family_set_extended_range
   bool have_sampler = false;
@@ -760,8 +769,9 @@ int check_async_error(lh_family* f, const char* who) {
   LH_HIP(hipMemcpy(&flag, f->err_flag, sizeof(flag), hipMemcpyDeviceToHost));
   if (flag) {
     LH_HIP(hipMemset(f->err_flag, 0, sizeof(flag)));
-    if (flag == 2)  // (K11c's bit alone)
-      return fail(std::string(who) + ": lineage path that is not a chain up to the root; the affected samples' results are NaN");
+    if (flag == 2)  // (K11c's and K12c's bit alone)
+      return fail(std::string(who) + ": lineage path that is not a chain up to the root, or (edge tables) a seed tip that is not a "
+                                     "child of its first node; the affected samples' results are NaN");
     return fail(std::string(who) + ": malformed schedule op (use lh_schedule_tree); the affected samples' results are NaN");
   }
   return 0;
@@ -1994,7 +2004,8 @@ namespace {
 
 // The chain of a sample's path under its own schedule, as K11c checks it on the device: the non-padding entries are inner
 // nodes, each a child of the next, the last one the root; padding (anything outside T .. 2T-3) comes only after them.
-bool valid_chain(const int32_t* ops, int T, const int32_t* path, int P) {
+// With seed_tip > 0 also what K12c checks: that tip is a child of path[0] (of the cherry or tip-accumulate op behind it).
+bool valid_chain(const int32_t* ops, int T, const int32_t* path, int P, int seed_tip = 0) {
   const int n_ops = T - 2;
   std::vector<int> parent_op(n_ops, -1), op_of_node(n_ops, -1), slot(16, -1);
   long long named = 0;
@@ -2021,7 +2032,7 @@ bool valid_chain(const int32_t* ops, int T, const int32_t* path, int P) {
   const long long root = (long long)n_ops * T + (long long)n_ops * (n_ops - 1) / 2 - named;
   if (root < T || root > 2 * T - 3) return false;
   op_of_node[root - T] = n_ops - 1;
-  int prev = -1, len = 0;
+  int prev = -1, len = 0, first = -1;
   bool ended = false;
   for (int s = 0; s < P; ++s) {
     const int v = path[s];
@@ -2032,10 +2043,18 @@ bool valid_chain(const int32_t* ops, int T, const int32_t* path, int P) {
     if (ended) return false;
     const int k = op_of_node[v - T];
     if (k < 0 || (len > 0 && parent_op[prev] != k)) return false;
+    if (len == 0) first = k;
     prev = k;
     ++len;
   }
-  return len >= 1 && prev == n_ops - 1;
+  if (len < 1 || prev != n_ops - 1) return false;
+  if (seed_tip > 0) {
+    const int32_t* op = ops + (size_t)first * 4;
+    const int kind = op[0] & 15;
+    if (!((kind == lh::OP_CHERRY && (op[1] == seed_tip || op[2] == seed_tip)) || (kind == lh::OP_TIP_ACC && op[1] == seed_tip)))
+      return false;
+  }
+  return true;
 }
 
 int ancestral_check(const lh_family* f, const std::string& W, const TreeBatch& b, int P) {
@@ -2334,6 +2353,300 @@ int lh_eval_ancestral_batch(lh_family* f, int32_t n, int32_t T, int32_t max_dept
 
 int lh_ancestral_profile_read(lh_family* f, double* ms, int64_t* n_launches) {
   return profile_read(f, &lh_family::anc_timer, ms, n_launches);
+}
+
+}  // extern "C"
+
+namespace {
+
+int edges_check(const lh_family* f, const std::string& W, const TreeBatch& b, int P, int seed_tip) {
+  if (ancestral_check(f, W, b, P)) return 1;
+  if (seed_tip < 1 || seed_tip > b.T - 1) return fail(W + ": seed_tip must be a tip other than naive, 1 .. n_tips - 1");
+  if (lh::sub_lds_bytes(b.T, P) > 160 * 1024) return fail(W + ": tree too large for the kernel's LDS tables");
+  return 0;
+}
+
+// samples per launch group of K12, by memory as ancestral_group: K11's scratch without its partials, K12's with the
+// per-slot partials (four times K11's) only where edge is asked for
+size_t edges_group(const lh_family* f, int T, int R, int P, bool with_edge) {
+  const lh::AncWsBytes z = lh::anc_ws_bytes(T, f->host.n_sites, R, f->host.n_prune, P);
+  const size_t per = z.total() - z.part + lh::sub_ws_bytes(f->host.n_sites, R, P).total(with_edge) + lh::asr_desc_bytes(T) +
+                     eval_bytes_per_sample(f, T, R);
+  return std::max<size_t>(1, std::min<size_t>({(size_t)kChunk, (size_t)8192, ((size_t)8 << 30) / per}));
+}
+
+int edges_workspace(lh_family* f, int chunk, int T, int R, int P, bool own_rho, bool with_edge, bool with_seed, lh::AncWs* ws,
+                    lh::SubWs* sws) {
+  AncestralWs& a = f->anc;
+  EdgesWs& e = f->edges;
+  const lh::AncWsBytes z = lh::anc_ws_bytes(T, f->host.n_sites, R, f->host.n_prune, P);
+  const lh::SubWsBytes y = lh::sub_ws_bytes(f->host.n_sites, R, P);
+  const size_t m = chunk;
+  if (a.clv.ensure(z.clv * m) || a.tvec.ensure(z.tvec * m) || (own_rho && a.rho.ensure(z.rho * m)) || a.chain.ensure(z.chain * m) ||
+      a.plen.ensure(sizeof(int32_t) * m) || a.desc.ensure(lh::asr_desc_bytes(T) * m) || e.cc.ensure(y.cc * m) ||
+      e.ne.ensure(y.ne * m) || (with_seed && e.se.ensure(y.se * m)) || e.el.ensure(y.el * m) ||
+      (with_edge && e.edge.ensure(y.edge * m)))
+    return 1;
+  *ws = {a.clv.get<double>(), nullptr, a.tvec.get<double>(), a.rho.get<double>(), a.chain.get<int32_t>(), a.plen.get<int32_t>(),
+         a.desc.get()};
+  *sws = {e.cc.get<double>(), e.ne.get<double>(), e.se.get<double>(), e.el.get<double>(), e.edge.get<double>()};
+  return 0;
+}
+
+bool edges_wanted(const lh_edges_outputs& o) { return o.edge || o.naive_edge || o.chain_counts || o.edge_load || o.rate_post; }
+
+}  // namespace
+
+extern "C" {
+
+int lh_asr_edges_batch_device(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops, const double* brlen,
+                              const double* er, const double* pi, const double* rates, int32_t R, const double* naive_prob,
+                              const int32_t* path, int32_t P, int32_t seed_tip, const lh_edges_outputs* outs, void* hip_stream) {
+  const TreeBatch b{n, T, max_depth, ops, brlen, er, pi, rates, R, true};
+  const std::string W = "lh_asr_edges_batch";
+  if (int rc = check_batch(f, W, b)) return rc > 0;
+  if (edges_check(f, W, b, P, seed_tip)) return 1;
+  DeviceGuard guard(f);
+  if (!b.has_arrays() || !naive_prob || !path) return fail(W + ": null array");
+  if (!outs || !edges_wanted(*outs)) return 0;  // nothing asked for
+  const lh_edges_outputs& o = *outs;
+  hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+  const size_t L = f->host.n_sites;
+  const int chunk = (int)std::min<size_t>(n, edges_group(f, T, R, P, o.edge != nullptr));
+  lh::AncWs ws;
+  lh::SubWs sws;
+  if (ensure_workspace(f, chunk, R, T) || edges_workspace(f, chunk, T, R, P, !o.rate_post, o.edge != nullptr, false, &ws, &sws))
+    return 1;
+  Workspace& w = f->ws;
+  double *eig = w.eig.get<double>(), *site_lik = w.site_lik.get<double>();
+  int32_t* site_scal = w.site_scal.get<int32_t>();
+  auto at = [](double* p, size_t off) { return p ? p + off : nullptr; };
+  for (int off = 0; off < n; off += chunk) {
+    const int m = std::min(chunk, n - off);
+    const TreeBatch g = b.slice(off, m);
+    lh::launch_gtr_setup(m, g.er, g.pi, eig, stream);
+    int planes = 0;
+    if (prune_group(f, W, g, g.model, false, stream, &planes)) return 1;
+    if (f->profile && (f->edges_timer.begin(stream) || f->edges_timer.mark(1, stream))) return 1;
+    const lh::SubOut so{at(o.edge, (size_t)off * P * L * 16), at(o.naive_edge, (size_t)off * L * 20),
+                        at(o.chain_counts, (size_t)off * L * 16), nullptr, at(o.edge_load, (size_t)off * (P + 1)),
+                        at(o.rate_post, (size_t)off * L * R)};
+    if (lh::launch_substitutions(f->host, m, R, T, g.ops, g.brlen, g.model, eig, g.pi, site_lik, site_scal,
+                                 naive_prob + (size_t)off * L * 5, path + (size_t)off * P, P, seed_tip, ws, sws, so, w.prune.hdr,
+                                 f->err_flag, stream))
+      return fail(W + ": launch failed");
+    if (f->profile && (f->edges_timer.mark(2, stream) || f->edges_timer.end(stream))) return 1;
+    LH_HIP(hipGetLastError());
+  }
+  return 0;
+}
+
+int lh_asr_edges_batch(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops, const double* brlen,
+                       const double* er, const double* pi, const double* rates, int32_t R, const double* naive_prob,
+                       const int32_t* path, int32_t P, int32_t seed_tip, const lh_edges_outputs* outs) {
+  const TreeBatch host{n, T, max_depth, ops, brlen, er, pi, rates, R, true};
+  const std::string W = "lh_asr_edges_batch";
+  if (int rc = check_batch(f, W, host)) return rc > 0;
+  if (edges_check(f, W, host, P, seed_tip)) return 1;
+  DeviceGuard guard(f);
+  if (!host.has_arrays() || !naive_prob || !path) return fail(W + ": null array");
+  if (!outs || !edges_wanted(*outs)) return 0;
+  const lh_edges_outputs& o = *outs;
+  const size_t L = f->host.n_sites;
+  // the device copies of the per-row outputs bound the batch (K11's rule)
+  const size_t per = sizeof(double) * ((o.edge ? (size_t)P * L * 16 : 0) + (o.naive_edge ? L * 20 : 0) + (o.chain_counts ? L * 16 : 0) +
+                                       (o.edge_load ? (size_t)P + 1 : 0) + (o.rate_post ? L * R : 0));
+  const size_t most = per ? ((size_t)lh::debug_options().edge_out_mb << 20) / per : (size_t)INT32_MAX;
+  if ((size_t)n > most)
+    return fail(W + ": batch too large for the device copies of its per-row outputs: at most " + std::to_string(most) +
+                " samples per call for this family and path length");
+  if (!valid_schedules(host)) return fail(W + ": malformed schedule op (use lh_schedule_tree)");
+  for (size_t i = 0; i < (size_t)n; ++i) {
+    if (!valid_chain(host.schedule(i), T, path + i * P, P))
+      return fail(W + ": path of sample " + std::to_string(i) +
+                  " is not a chain of inner nodes, each the child of the next, that ends at the root (padding after it)");
+    if (!valid_chain(host.schedule(i), T, path + i * P, P, seed_tip))
+      return fail(W + ": seed_tip " + std::to_string(seed_tip) + " is not a child of path[0] of sample " + std::to_string(i));
+  }
+  AncestralWs& a = f->anc;
+  EdgesWs& e = f->edges;
+  lh_edges_outputs d{};
+  TreeBatch dev;
+  const size_t edge_b = sizeof(double) * P * L * 16 * n, ne_b = sizeof(double) * L * 20 * n, cc_b = sizeof(double) * L * 16 * n,
+               el_b = sizeof(double) * ((size_t)P + 1) * n, rp_b = sizeof(double) * L * R * n;
+  if (out_buf(o.edge, e.out_edge, edge_b, &d.edge) || out_buf(o.naive_edge, e.out_ne, ne_b, &d.naive_edge) ||
+      out_buf(o.chain_counts, e.out_cc, cc_b, &d.chain_counts) || out_buf(o.edge_load, e.out_el, el_b, &d.edge_load) ||
+      out_buf(o.rate_post, a.rate_post, rp_b, &d.rate_post) ||
+      stage_batch(f, host, {{naive_prob, sizeof(double) * L * 5 * n, &a.naive_prob}, {path, sizeof(int32_t) * P * n, &a.path}}, &dev))
+    return 1;
+  if (lh_asr_edges_batch_device(f, n, T, max_depth, dev.ops, dev.brlen, dev.er, dev.pi, dev.model, R, a.naive_prob.get<const double>(),
+                                a.path.get<const int32_t>(), P, seed_tip, &d, nullptr))
+    return 1;
+  return copy_back(f, W.c_str(),
+                   {{o.edge, d.edge, edge_b},
+                    {o.naive_edge, d.naive_edge, ne_b},
+                    {o.chain_counts, d.chain_counts, cc_b},
+                    {o.edge_load, d.edge_load, el_b},
+                    {o.rate_post, d.rate_post, rp_b}});
+}
+
+int lh_eval_edges_batch_device(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops, const double* brlen,
+                               const double* er, const double* pi, const double* alpha, int32_t R, const int32_t* path, int32_t P,
+                               int32_t seed_tip, const lh_eval_edges_outputs* outs, void* hip_stream) {
+  const TreeBatch b{n, T, max_depth, ops, brlen, er, pi, alpha, R};
+  const std::string W = "lh_eval_edges_batch";
+  if (int rc = check_batch(f, W, b, true)) return rc > 0;
+  if (edges_check(f, W, b, P, seed_tip)) return 1;
+  DeviceGuard guard(f);
+  if (!b.has_arrays() || !path) return fail(W + ": null array");
+  const lh_eval_edges_outputs none{};
+  const lh_eval_edges_outputs& o = outs ? *outs : none;
+  if (ancestral_table(f, W)) return 1;
+  hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+  const size_t L = f->host.n_sites, FS = f->host.forward_size;
+  const bool with_edge = o.edge != nullptr;
+  const int chunk = (int)std::min<size_t>(n, std::min(edges_group(f, T, R, P, with_edge), eval_group(f, T, R)));
+  AncestralWs& a = f->anc;
+  EdgesWs& e = f->edges;
+  const bool reduce = o.weighted_counts || o.weighted_seed_edge || o.weighted_naive_edge || o.weight_stats;
+  // the reduction reads its rows of the whole batch; what the caller does not take then lives on the handle
+  const bool want_cc = o.chain_counts || o.weighted_counts, want_se = o.seed_edge || o.weighted_seed_edge,
+             want_ne = o.naive_edge || o.weighted_naive_edge;
+  const bool tables = with_edge || want_cc || want_se || want_ne || o.edge_load;
+  const size_t slabs = lh::posterior_slabs(n);
+  lh::AncWs ws;
+  lh::SubWs sws;
+  double *ll = o.loglik, *sb = o.site_base, *cc = o.chain_counts, *se = o.seed_edge, *ne = o.naive_edge;
+  double *pc = nullptr, *ps = nullptr, *pn = nullptr;
+  WeightReduce wr;
+  const size_t sb_rows = o.site_base ? 0 : chunk;
+  if (ensure_workspace(f, chunk, R, T) || edges_workspace(f, chunk, T, R, P, !o.rate_post, with_edge, want_se, &ws, &sws) ||
+      a.plen.ensure(sizeof(int32_t) * n) || a.rates.ensure(sizeof(double) * R * chunk) ||
+      f->forward_dev.ensure(sizeof(double) * FS * n) || own(ll, a.loglik, sizeof(double) * n) ||
+      own(sb, a.site_base, sizeof(double) * L * 5 * sb_rows) || (want_cc && own(cc, e.out_cc, sizeof(double) * L * 16 * n)) ||
+      (want_se && own(se, e.out_se, sizeof(double) * L * 16 * n)) || (want_ne && own(ne, e.out_ne, sizeof(double) * L * 20 * n)) ||
+      (reduce && (a.ll_used.ensure(sizeof(double) * n) || wr.prepare(n, a.weights, a.stats, o.weight_stats) ||
+                  (o.weighted_counts && own(pc, e.partial_c, sizeof(double) * L * 16 * slabs)) ||
+                  (o.weighted_seed_edge && own(ps, e.partial_s, sizeof(double) * L * 16 * slabs)) ||
+                  (o.weighted_naive_edge && own(pn, e.partial_n, sizeof(double) * L * 20 * slabs)))))
+    return 1;
+  ws.plen = a.plen.get<int32_t>();  // (the batch's, for the reduction; a.plen.ensure above may have moved it)
+  Workspace& w = f->ws;
+  double *eig = w.eig.get<double>(), *site_lik = w.site_lik.get<double>(), *fwd = f->forward_dev.get<double>();
+  double* rates = a.rates.get<double>();
+  int32_t* site_scal = w.site_scal.get<int32_t>();
+  const lh_eval_outputs fwd_outs{nullptr, nullptr, fwd, nullptr};
+  auto at = [](double* p, size_t off) { return p ? p + off : nullptr; };
+  for (int off = 0; off < n; off += chunk) {
+    const int m = std::min(chunk, n - off);
+    const TreeBatch g = b.slice(off, m);
+    lh::launch_model_setup(m, R, g.er, g.pi, g.model, rates, eig, stream);
+    int planes = 0;
+    // one unmixed K1 serves K2 and K12b: its planes outlive K2
+    if (prune_group(f, W, g, rates, false, stream, &planes)) return 1;
+    if (run_forward(f, m, planes, site_lik, site_scal, g.pi, nullptr, nullptr, ll + off, &fwd_outs, off, stream)) return 1;
+    lh::launch_posterior(f->sampler_dev, m, fwd + (size_t)off * FS, FS, ll + off, stream);
+    if (f->profile && f->edges_timer.begin(stream)) return 1;
+    double* sb_g = o.site_base ? sb + (size_t)off * L * 5 : sb;
+    lh::launch_site_base(m, (int)L, FS, a.sb_off.get<const int32_t>(), a.sb_idx.get<const int32_t>(), fwd + (size_t)off * FS,
+                         ll + off, sb_g, stream);
+    if (f->profile && f->edges_timer.mark(1, stream)) return 1;
+    lh::AncWs wg = ws;
+    wg.plen = ws.plen + off;
+    if (tables || o.rate_post) {
+      const lh::SubOut so{at(o.edge, (size_t)off * P * L * 16), want_ne ? ne + (size_t)off * L * 20 : nullptr,
+                          want_cc ? cc + (size_t)off * L * 16 : nullptr, want_se ? se + (size_t)off * L * 16 : nullptr,
+                          at(o.edge_load, (size_t)off * (P + 1)), at(o.rate_post, (size_t)off * L * R)};
+      if (lh::launch_substitutions(f->host, m, R, T, g.ops, g.brlen, rates, eig, g.pi, site_lik, site_scal, sb_g,
+                                   path + (size_t)off * P, P, seed_tip, wg, sws, so, w.prune.hdr, f->err_flag, stream))
+        return fail(W + ": launch failed");
+    }
+    // the paths were checked wherever a table was formed: a row without one then gets no weight
+    if (reduce && tables)
+      lh::launch_ancestral_ends(m, P, (int)L, wg.plen, nullptr, ll + off, nullptr, a.ll_used.get<double>() + off, stream);
+    if (f->profile && f->edges_timer.mark(2, stream)) return 1;
+    if (reduce && off + m == n) {
+      wr.launch(n, tables ? a.ll_used.get<const double>() : ll, o.log_offset, stream);
+      if (o.weighted_counts) lh::launch_weighted_slabs(n, L * 16, cc, wr.w, pc, o.weighted_counts, stream);
+      if (o.weighted_seed_edge) lh::launch_weighted_slabs(n, L * 16, se, wr.w, ps, o.weighted_seed_edge, stream);
+      if (o.weighted_naive_edge) lh::launch_weighted_slabs(n, L * 20, ne, wr.w, pn, o.weighted_naive_edge, stream);
+    }
+    if (f->profile && f->edges_timer.end(stream)) return 1;
+    LH_HIP(hipGetLastError());
+  }
+  return 0;
+}
+
+int lh_eval_edges_batch(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops, const double* brlen,
+                        const double* er, const double* pi, const double* alpha, int32_t R, const int32_t* path, int32_t P,
+                        int32_t seed_tip, const lh_eval_edges_outputs* outs) {
+  const TreeBatch host{n, T, max_depth, ops, brlen, er, pi, alpha, R};
+  const std::string W = "lh_eval_edges_batch";
+  if (int rc = check_batch(f, W, host, true)) return rc > 0;
+  if (edges_check(f, W, host, P, seed_tip)) return 1;
+  DeviceGuard guard(f);
+  if (!host.has_arrays() || !path) return fail(W + ": null array");
+  const lh_eval_edges_outputs none{};
+  const lh_eval_edges_outputs& o = outs ? *outs : none;
+  if (!o.loglik && !o.site_base && !o.edge && !o.naive_edge && !o.chain_counts && !o.seed_edge && !o.edge_load && !o.rate_post &&
+      !o.weighted_counts && !o.weighted_seed_edge && !o.weighted_naive_edge && !o.weight_stats)
+    return 0;
+  const size_t L = f->host.n_sites;
+  // the device copies of the per-row outputs bound the batch (K11's rule)
+  const size_t per = sizeof(double) * ((o.edge ? (size_t)P * L * 16 : 0) + (o.naive_edge ? L * 20 : 0) + (o.chain_counts ? L * 16 : 0) +
+                                       (o.seed_edge ? L * 16 : 0) + (o.edge_load ? (size_t)P + 1 : 0) + (o.rate_post ? L * R : 0) +
+                                       (o.site_base ? L * 5 : 0));
+  const size_t most = per ? ((size_t)lh::debug_options().edge_out_mb << 20) / per : (size_t)INT32_MAX;
+  if ((size_t)n > most)
+    return fail(W + ": batch too large for the device copies of its per-row outputs: at most " + std::to_string(most) +
+                " samples per call for this family and path length");
+  for (size_t i = 0; i < (size_t)n; ++i) {
+    if (!valid_schedule(host.schedule(i), T, (int)host.nodes(), max_depth)) continue;  // (finish_batch refuses it)
+    if (!valid_chain(host.schedule(i), T, path + i * P, P))
+      return fail(W + ": path of sample " + std::to_string(i) +
+                  " is not a chain of inner nodes, each the child of the next, that ends at the root (padding after it)");
+    if (!valid_chain(host.schedule(i), T, path + i * P, P, seed_tip))
+      return fail(W + ": seed_tip " + std::to_string(seed_tip) + " is not a child of path[0] of sample " + std::to_string(i));
+  }
+  AncestralWs& a = f->anc;
+  EdgesWs& e = f->edges;
+  HostOutputs& out = f->out;
+  lh_eval_edges_outputs d{};
+  TreeBatch dev;
+  const size_t t16 = sizeof(double) * L * 16, t20 = sizeof(double) * L * 20;
+  if (out.loglik.ensure(sizeof(double) * n) || out_buf(o.site_base, a.site_base, sizeof(double) * L * 5 * n, &d.site_base) ||
+      out_buf(o.edge, e.out_edge, t16 * P * n, &d.edge) || out_buf(o.naive_edge, e.out_ne, t20 * n, &d.naive_edge) ||
+      out_buf(o.chain_counts, e.out_cc, t16 * n, &d.chain_counts) || out_buf(o.seed_edge, e.out_se, t16 * n, &d.seed_edge) ||
+      out_buf(o.edge_load, e.out_el, sizeof(double) * ((size_t)P + 1) * n, &d.edge_load) ||
+      out_buf(o.rate_post, a.rate_post, sizeof(double) * L * R * n, &d.rate_post) ||
+      out_buf(o.weighted_counts, e.out_wcc, t16, &d.weighted_counts) ||
+      out_buf(o.weighted_seed_edge, e.out_wse, t16, &d.weighted_seed_edge) ||
+      out_buf(o.weighted_naive_edge, e.out_wne, t20, &d.weighted_naive_edge) ||
+      out_buf(o.weight_stats, out.weight_stats, sizeof(double) * 3, &d.weight_stats) ||
+      stage_batch(f, host, {{o.log_offset, sizeof(double) * n, &f->in.log_offset}, {path, sizeof(int32_t) * P * n, &a.path}}, &dev))
+    return 1;
+  d.log_offset = o.log_offset ? f->in.log_offset.get<const double>() : nullptr;
+  d.loglik = out.loglik.get<double>();
+  if (lh_eval_edges_batch_device(f, n, T, max_depth, dev.ops, dev.brlen, dev.er, dev.pi, dev.model, R, a.path.get<const int32_t>(), P,
+                                 seed_tip, &d, nullptr))
+    return 1;
+  return finish_batch(f, W.c_str(), host,
+                      {{o.loglik, d.loglik, sizeof(double) * n},
+                       {o.site_base, d.site_base, sizeof(double) * L * 5 * n},
+                       {o.edge, d.edge, t16 * P * n},
+                       {o.naive_edge, d.naive_edge, t20 * n},
+                       {o.chain_counts, d.chain_counts, t16 * n},
+                       {o.seed_edge, d.seed_edge, t16 * n},
+                       {o.edge_load, d.edge_load, sizeof(double) * ((size_t)P + 1) * n},
+                       {o.rate_post, d.rate_post, sizeof(double) * L * R * n},
+                       {o.weighted_counts, d.weighted_counts, t16},
+                       {o.weighted_seed_edge, d.weighted_seed_edge, t16},
+                       {o.weighted_naive_edge, d.weighted_naive_edge, t20},
+                       {o.weight_stats, d.weight_stats, sizeof(double) * 3}});
+}
+
+int lh_edges_profile_read(lh_family* f, double* ms, int64_t* n_launches) {
+  return profile_read(f, &lh_family::edges_timer, ms, n_launches);
 }
 
 int lh_forward_batch(lh_family* f, int32_t n, const double* em, double* loglik, const lh_eval_outputs* outs) {

@@ -444,6 +444,135 @@ void launch_site_base(int n, int L, size_t forward_size, const int32_t* off, con
 // ll_used[n] = loglik, NaN where plen is 0 (launch_ancestral found no path: the row's weight becomes 0).
 void launch_ancestral_ends(int n, int P, int L, const int32_t* plen, const double* marg, const double* loglik, double* ends,
                            double* ll_used, hipStream_t stream);
+// K11r, K3s and K11c alone: ws.tvec, rho (rate_post, or ws.rho where that is null), ws.desc, ws.chain, ws.plen.  What
+// launch_ancestral runs in front of K11b; K12 (lh_substitutions.hip) runs its own kernels behind it.
+void launch_ancestral_front(const DevFamily& fam, int n, int R, int T, const int32_t* ops, const double* pi,
+                            const double* site_lik, const int32_t* site_scal, const double* naive_prob, const int32_t* path,
+                            int P, const AncWs& ws, double* rate_post, const int4* hdr, int32_t* err_flag, hipStream_t stream);
+size_t anc_lp(int n_prune);  // patterns per CLV plane: n_prune + 1 rounded up to 8
+
+// What K11b and K12b share, inlined into each: the 4-vector helpers, the LDS tables and the upward pass.
+__device__ static __forceinline__ void anc_tip_col(const double* tiptab, int tip, int st, double (&c)[4]) {
+  const double* t = tiptab + tip * 16;
+  if (st < 4) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) c[i] = t[st * 4 + i];
+  } else {  // N: row sums of P, as K3
+#pragma unroll
+    for (int i = 0; i < 4; ++i) c[i] = ((t[i] + t[4 + i]) + t[8 + i]) + t[12 + i];
+  }
+}
+
+// x = P a, P row-major in LDS at a wave-uniform address
+__device__ static __forceinline__ void anc_matvec(const double* p, const double (&a)[4], double (&x)[4]) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) x[i] = fma(p[i * 4 + 3], a[3], fma(p[i * 4 + 2], a[2], fma(p[i * 4 + 1], a[1], p[i * 4] * a[0])));
+}
+
+// x = a^T P
+__device__ static __forceinline__ void anc_vecmat(const double* p, const double (&a)[4], double (&x)[4]) {
+#pragma unroll
+  for (int c = 0; c < 4; ++c) x[c] = fma(p[12 + c], a[3], fma(p[8 + c], a[2], fma(p[4 + c], a[1], p[c] * a[0])));
+}
+
+// The LDS tables of a (sample, rate): tiptab[T][4][4] columns of the tip branches' P, pin[T-2][4][4] row-major P of the
+// inner branches, by the op that produced the child.  The caller synchronises the workgroup behind it.
+__device__ static __forceinline__ void anc_fill_tables(int T, const AsrOp* __restrict__ dsc, const double* __restrict__ e,
+                                                       const double* __restrict__ bl, double rt, double* tiptab, double* pin) {
+  const int n_ops = T - 2;
+  double Pm[4][4];
+  for (int j = threadIdx.x; j < T + n_ops - 1; j += blockDim.x) {
+    if (j < T) {
+      compute_pmatrix(e, bl[j] * rt, Pm);
+      double* o = tiptab + j * 16;
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int st = 0; st < 4; ++st) o[st * 4 + i] = Pm[i][st];
+    } else {
+      const int k = j - T;  // op k < n_ops - 1 produced inner node T + b.z, whose branch this is
+      compute_pmatrix(e, bl[T + dsc[k].b.z] * rt, Pm);
+      double* o = pin + (size_t)k * 16;
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) o[i * 4 + q] = Pm[i][q];
+    }
+  }
+}
+
+// K3b's upward pass over all NP = n_prune + 1 patterns (the all-N one last), a lane per pattern (lanes past the last
+// pattern repeat it: same values, no predicate); every inner CLV stored: clv_s[op][2][plane] double2, components (0,1) and
+// (2,3) of a pattern in two planes.
+__device__ static __forceinline__ void anc_upward(int n_ops, int n_prune, const uint8_t* __restrict__ msa,
+                                                  const AsrOp* __restrict__ dsc, const double* tiptab, const double* pin,
+                                                  double2* clv_s, size_t plane, int wave, int n_waves, int lane) {
+  const int NP = n_prune + 1;
+  for (int s0 = wave * 64; s0 < NP; s0 += n_waves * 64) {
+    const int pat = min(s0 + lane, NP - 1);
+    const bool all_n = pat >= n_prune;
+    double a[4] = {1.0, 1.0, 1.0, 1.0};
+    for (int k = 0; k < n_ops; ++k) {
+      const int4 da = dsc[k].a, db = dsc[k].b;
+      const int kind = da.x & 15;
+      double u[4], v[4];
+      if (kind == OP_CHERRY) {
+        const int sa = all_n ? 4 : (int)msa[(size_t)da.y * n_prune + pat];
+        const int sb = all_n ? 4 : (int)msa[(size_t)da.z * n_prune + pat];
+        anc_tip_col(tiptab, db.x, sa, u);
+        anc_tip_col(tiptab, db.y, sb, v);
+      } else {
+        anc_matvec(pin + (size_t)(k - 1) * 16, a, v);
+        if (kind == OP_TIP_ACC) {
+          const int sa = all_n ? 4 : (int)msa[(size_t)da.y * n_prune + pat];
+          anc_tip_col(tiptab, db.x, sa, u);
+        } else {
+          const double2* cq = clv_s + (size_t)da.w * 2 * plane + pat;
+          const double2 lo = cq[0], hi = cq[plane];
+          const double y[4] = {lo.x, lo.y, hi.x, hi.y};
+          anc_matvec(pin + (size_t)da.w * 16, y, u);
+        }
+      }
+#pragma unroll
+      for (int q = 0; q < 4; ++q) a[q] = u[q] * v[q];
+      if (fmax(fmax(a[0], a[1]), fmax(a[2], a[3])) < kScaleThreshold) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) a[q] *= kScaleFactor;
+      }
+      double2* ck = clv_s + (size_t)k * 2 * plane + pat;
+      ck[0] = make_double2(a[0], a[1]);
+      ck[plane] = make_double2(a[2], a[3]);
+    }
+  }
+}
+
+// K12 (lh_substitutions.hip): exact joint posteriors of the two ends of every edge of a seed's lineage.  Inputs as
+// launch_ancestral's plus seed_tip (1 .. T-1, the same for every sample): the tip must be a child of path[0] under the
+// sample's own schedule, else the sample is treated as one with a bad path (NaN rows, *err_flag bit 1).  Every output may
+// be null: edge[n][P][n_sites][4][4] (padding slots 0), naive_edge[n][n_sites][5][4], chain_counts[n][n_sites][4][4],
+// seed_edge[n][n_sites][4][4] (slot 0 of edge), edge_load[n][P+1], rate_post[n][n_sites][R]; plen_out[n] (null: ws.plen)
+// receives the path lengths, 0 for a sample without a valid path.  Tables are indexed [ancestor state][descendant state].
+// Scratch per sample: sub_ws_bytes on top of anc_ws_bytes' clv, tvec, rho and chain (AncWs::part is not used).
+struct SubWs {
+  double* cc;    // [n][R][n_sites][16]
+  double* ne;    // [n][R][n_sites][20]
+  double* se;    // [n][R][n_sites][16]
+  double* el;    // [n][R][P+1]
+  double* edge;  // [n][R][P][n_sites][16], only where edge is asked for
+};
+struct SubWsBytes {
+  size_t cc, ne, se, el, edge;  // per sample
+  size_t total(bool with_edge) const { return cc + ne + se + el + (with_edge ? edge : 0); }
+};
+SubWsBytes sub_ws_bytes(int L, int R, int P);
+size_t sub_lds_bytes(int T, int P);
+struct SubOut {
+  double *edge, *naive_edge, *chain_counts, *seed_edge, *edge_load, *rate_post;
+};
+int launch_substitutions(const DevFamily& fam, int n, int R, int T, const int32_t* ops, const double* brlen, const double* rates,
+                         const double* eig, const double* pi, const double* site_lik, const int32_t* site_scal,
+                         const double* naive_prob, const int32_t* path, int P, int seed_tip, const AncWs& ws, const SubWs& sws,
+                         const SubOut& out, const int4* hdr, int32_t* err_flag, hipStream_t stream);
 
 // K2a + K2b.  site_lik != null: emissions are assembled from K1's output (rate mix and naive
 // correction; optionally written to em_out[n][C]); site_lik == null: emissions are taken from
@@ -517,6 +646,7 @@ struct DebugOptions {
   int events_blocks = 1024;    // LH_EVENTS_BLOCKS=<n>: K10's workgroup cap (as LH_CODON_BLOCKS)
   int anc_out_mb = 4096;       // LH_ANC_OUT_MB=<n>: MiB of device copies of lh_eval_ancestral_batch's per-row outputs (host
                                // pointers) above which a batch is refused with the largest n (tests: the refusal on a small family)
+  int edge_out_mb = 4096;      // LH_EDGE_OUT_MB=<n>: the same bound for lh_asr_edges_batch and lh_eval_edges_batch
   int collect_hash_bits = 64;  // LH_COLLECT_HASH_BITS=<n>: K6c's row hashes masked to n bits (tests: collisions common,
                                // the exact resolution runs; results unchanged)
 };

@@ -106,6 +106,29 @@ def read_ancestral_marginals(prefix):
     return out
 
 
+def read_lineage_substitutions(prefix):
+    """The files of PhyloHMM::RunLineageSubstitutionsPipeline: dict(counts [L][4][4], substitutions [L] (the off-diagonal sum
+    the file carries), seed_edge [L][4][4], naive_edge [L][5][4], rows [(row, weight, chain_length, expected_substitutions)],
+    summary).  Tables are indexed [ancestor base][descendant base]."""
+    import numpy as np
+
+    def table(path, n_rows, with_sum):
+        lines = open(path).read().strip().split("\n")
+        want = ["site"] + [a + c for a in "ACGTN"[:n_rows] for c in "ACGT"] + (["substitutions"] if with_sum else [])
+        assert lines[0].split("\t") == want, lines[0]
+        return np.array([[float(x) for x in ln.split("\t")[1:]] for ln in lines[1:]])
+    out = {}
+    counts = table(prefix + ".substitutions.tsv", 4, True)
+    out["counts"], out["substitutions"] = counts[:, :16].reshape(-1, 4, 4), counts[:, 16]
+    out["seed_edge"] = table(prefix + ".seed_edge.tsv", 4, False).reshape(-1, 4, 4)
+    out["naive_edge"] = table(prefix + ".naive_edge.tsv", 5, False).reshape(-1, 5, 4)
+    rows = [ln.split("\t") for ln in open(prefix + ".rows.tsv").read().strip().split("\n")]
+    assert rows[0] == ["row", "weight", "chain_length", "expected_substitutions"]
+    out["rows"] = [(int(r[0]), float(r[1]), int(r[2]), float(r[3])) for r in rows[1:]]
+    out["summary"] = _parse_summary(open(prefix + ".summary.tsv").read())
+    return out
+
+
 def _parse_gene_table(text):
     genes = {}
     for line in text.strip().split("\n")[1:]:
@@ -474,6 +497,35 @@ class PhyloHMM(_HMM):
         _check(self.lib.lhh_run_ancestral_marginals_pipeline(self.h, input_path.encode(), seed_seq.encode(),
                                                              output_prefix.encode(), num_rates, C.c_double(burnin_frac)))
         return read_ancestral_marginals(output_prefix)
+
+    def lineage_substitutions(self, seed_seq):
+        """PhyloHMM::LineageSubstitutions of the current tree: dict(nodes [P] -- the lineage of the tip `seed_seq`, slot 0 its
+        parent, the last slot the MRCA --, edges [(upper node, lower node, branch length, expected differing sites)] of
+        length P + 1 ([s] the edge below slot s, [P] naive -> MRCA), edge [P][L][4][4], naive_edge [L][5][4],
+        chain_counts [L][4][4], loglik); tables indexed [ancestor base][descendant base]."""
+        sz = self.sizes()
+        T, L = sz["n_tips"], sz["n_sites"]
+        lib = self.lib
+        lib.lhh_phylo_lineage_substitutions.argtypes = [C.c_void_p, C.c_char_p] + [C.c_void_p] * 5 + \
+            [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double)]
+        cap = T - 2
+        nodes = np.zeros(cap, dtype=np.int32)
+        edge, ne, cc, edges = np.zeros((cap, L, 4, 4)), np.zeros((L, 5, 4)), np.zeros((L, 4, 4)), np.zeros((cap + 1, 4))
+        n, ll = C.c_int(), C.c_double()
+        _check(lib.lhh_phylo_lineage_substitutions(self.h, seed_seq.encode(), nodes.ctypes.data, edge.ctypes.data, ne.ctypes.data,
+                                                   cc.ctypes.data, edges.ctypes.data, cap, C.byref(n), C.byref(ll)))
+        P = n.value
+        return dict(nodes=nodes[:P].tolist(), edges=[(int(e[0]), int(e[1]), float(e[2]), float(e[3])) for e in edges[:P + 1]],
+                    edge=edge[:P].copy(), naive_edge=ne, chain_counts=cc, loglik=ll.value)
+
+    def run_lineage_substitutions_pipeline(self, input_path, seed_seq, output_prefix, num_rates, burnin_frac=0.0):
+        """PhyloHMM::RunLineageSubstitutionsPipeline: importance-weighted exact substitution tables of the seed's lineage over
+        a RevBayes table; returns read_lineage_substitutions(output_prefix)."""
+        self.lib.lhh_run_lineage_substitutions_pipeline.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int,
+                                                                    C.c_double]
+        _check(self.lib.lhh_run_lineage_substitutions_pipeline(self.h, input_path.encode(), seed_seq.encode(),
+                                                               output_prefix.encode(), num_rates, C.c_double(burnin_frac)))
+        return read_lineage_substitutions(output_prefix)
 
     def run_marginals_pipeline(self, input_path, output_prefix, num_rates, burnin_frac=0.0):
         """PhyloHMM::RunMarginalsPipeline: importance-weighted exact marginals over a RevBayes table (burn-in
