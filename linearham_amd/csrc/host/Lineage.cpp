@@ -9,6 +9,7 @@
 #include <stdexcept>
 
 #include "NaiveProbs.hpp"
+#include "utils.hpp"
 
 namespace linearham {
 
@@ -30,12 +31,6 @@ class Fractions {
 // a count: the integer it is when no tree had a weight of its own, else str(float)
 std::string CountText(const LineageTables& t, double count) {
   return t.weighted ? ReprDouble(count) : std::to_string((int64_t)count);
-}
-
-std::string G17(double v) {
-  char b[40];
-  std::snprintf(b, sizeof b, "%.17g", v);
-  return b;
 }
 
 }  // namespace
@@ -218,7 +213,7 @@ void WriteLineageSummary(std::ostream& o, const LineageTables& t, int64_t collis
     << "\nlongest_path\t" << t.longest_path << "\nhash_collisions_resolved\t" << collisions << "\n";
   if (ws)
     o << "rows_used\t" << ws->rows_used << "\nrows_skipped_nonfinite\t" << ws->rows_skipped_nonfinite << "\ndraws_per_row\t"
-      << ws->draws_per_row << "\nkish_ess\t" << G17(ws->kish_ess) << "\n";
+      << ws->draws_per_row << "\nkish_ess\t" << Fmt17(ws->kish_ess) << "\n";
 }
 
 std::vector<double> LineageWeights(const std::vector<double>& lw, LineageWeightSummary* ws) {

@@ -1820,15 +1820,84 @@ void PhyloHMM::SetExtendedRange(bool on) {
     if (lh_family_set_extended_range(f, on ? 1 : 0)) throw std::runtime_error(lh_last_error());
 }
 
+// ---- what the pipelines over a RevBayes table share ----
+
+int PhyloHMM::BeginPipeline(const std::string& what, const std::string& kernel, double burnin_frac, const std::string* seed_seq) {
+  Require(devices_.size() <= 1, "the " + what + " pipeline runs on one device: --devices may list only one");
+  Require(burnin_frac >= 0.0 && burnin_frac < 1.0, "burn-in fraction must be in [0, 1)");
+  const int seed_tip = seed_seq ? SeedTip(*seed_seq) : 0;
+  CreateFamily();
+  Require(device_sampler_, "the family has no device sampler tables (needed by the " + kernel + " kernel)");
+  return seed_tip;
+}
+
+namespace {
+
+// the first row after the burn-in
+std::size_t FirstUsedRow(std::size_t n_rows, double burnin_frac) {
+  return (std::size_t)std::floor(burnin_frac * (double)n_rows);
+}
+
+// rows per batch where LH_PIPELINE_BATCH does not say: at most 8192, and `fit` where the rows' tables bound it
+std::size_t PipelineBatch(std::size_t fit) {
+  return host_options().pipeline_batch > 0 ? (std::size_t)host_options().pipeline_batch : std::min<std::size_t>(8192, fit);
+}
+
+// summary.tsv's common lines; `kish_ess` as the pipeline prints its numbers
+void WriteSummary(std::ostream& summary, std::size_t used, std::size_t skipped, const std::string& kish_ess) {
+  summary << "key\tvalue\nrows_used\t" << used << "\nrows_skipped_nonfinite\t" << skipped << "\nkish_ess\t" << kish_ess << "\n";
+}
+
+}  // namespace
+
+// What SumWeightedRows hands the writers: the weighted means, and per row after the burn-in its log weight
+struct PhyloHMM::WeightedRows {
+  WeightedSums acc;
+  std::size_t skipped = 0;
+  std::vector<double> lw;
+  std::size_t used() const { return lw.size() - skipped; }
+  double weight(std::size_t u) const { return std::isfinite(lw[u]) ? std::exp(lw[u] - acc.mx) : 0.0; }
+};
+
+// The importance-weighted mean of a table per row, over the rows from `first` on in batches of `batch_rows`:
+// pack = batch(tb, off, ll) runs the C entry point on rows off .. off + tb.dev.n - 1 (ll: their log-likelihoods) and
+// pack(i, row) lays row i's `width` doubles out.  The rows' tables are added up on the host in row order, each with its
+// weight relative to itself: the result does not depend on the batch size.  Rows with a non-finite weight are skipped
+// and counted.
+template <class Batch>
+PhyloHMM::WeightedRows PhyloHMM::SumWeightedRows(const std::string& what, const TsvTable& table, const std::string& input_path,
+                                                 std::size_t first, std::size_t batch_rows, std::size_t width,
+                                                 bool with_children, Batch&& batch) const {
+  const std::size_t N = table.rows.size();
+  WeightedRows r{WeightedSums(width), 0, std::vector<double>(N - first)};
+  std::vector<double> row(width);
+  for (std::size_t off = first; off < N; off += batch_rows) {
+    const std::size_t m = std::min(batch_rows, N - off);
+    const TableBatch tb = FlattenTable(table, off, off + m, false, true, input_path, with_children);
+    std::vector<double> ll(m);
+    const auto pack = batch(tb, off, ll.data());
+    for (std::size_t i = 0; i < m; ++i) {
+      const double st[3] = {ll[i] - tb.lik[i], 1.0, 1.0};  // one row, its weight relative to itself
+      r.lw[off - first + i] = st[0];
+      if (!std::isfinite(st[0])) {
+        ++r.skipped;
+        continue;
+      }
+      pack(i, row.data());
+      r.acc.Add(row.data(), st);
+    }
+  }
+  Require(r.acc.s1 > 0.0, what + " pipeline: no row with a finite weight");
+  r.acc.Normalise();
+  return r;
+}
+
 void PhyloHMM::RunMarginalsPipeline(const std::string& input_path, const std::string& output_prefix, int num_rates,
                                     double burnin_frac) {
-  Require(devices_.size() <= 1, "the marginals pipeline runs on one device: --devices may list only one");
-  Require(burnin_frac >= 0.0 && burnin_frac < 1.0, "burn-in fraction must be in [0, 1)");
-  CreateFamily();
-  Require(device_sampler_, "the family has no device sampler tables (needed by the posterior kernel)");
+  BeginPipeline("marginals", "posterior", burnin_frac);
   TsvTable table = TsvTable::OpenRevBayesTable(input_path);
   const std::size_t N = table.rows.size();
-  const std::size_t first = (std::size_t)std::floor(burnin_frac * (double)N);
+  const std::size_t first = FirstUsedRow(table.rows.size(), burnin_frac);
   const std::size_t FS = (std::size_t)lh_forward_size(family_);
   constexpr std::size_t kBatch = 49152;
   // running combination of the batches' (sum w pi, max lw, sum w, sum w^2), each relative to the running max
@@ -1857,18 +1926,11 @@ void PhyloHMM::RunMarginalsPipeline(const std::string& input_path, const std::st
   Require(sites.good() && genes.good() && summary.good(), "Can't write " + output_prefix + ".*.tsv");
   WriteSiteTable(sites, res);
   WriteGeneTable(genes, res);
-  char buf[64];
-  std::snprintf(buf, sizeof buf, "%.17g", acc.KishEss());
-  summary << "key\tvalue\nrows_used\t" << (N - first - skipped) << "\nrows_skipped_nonfinite\t" << skipped
-          << "\nkish_ess\t" << buf << "\n";
+  WriteSummary(summary, N - first - skipped, skipped, Fmt17(acc.KishEss()));
 }
 
 
 // ---- K11: exact ancestral-state marginals along a seed's lineage ----
-
-namespace {
-std::string Fmt17(double v);  // (%.17g; defined with the codon tables below)
-}
 
 int PhyloHMM::SeedTip(const std::string& seed_seq) const {
   Require(seed_seq != "naive", "the seed sequence cannot be 'naive': the lineage ends there");
@@ -1878,19 +1940,33 @@ int PhyloHMM::SeedTip(const std::string& seed_seq) const {
   throw std::runtime_error("the seed sequence '" + seed_seq + "' is not a sequence of this clonal family");
 }
 
-PhyloHMM::AncestralMarginalsResult PhyloHMM::AncestralMarginals(const std::string& seed_seq) {
+// The current tree as K11's and K12's entry points take it: its schedule and the seed's chain of ancestors
+struct PhyloHMM::SeedLineage {
+  int seed_tip = 0;
+  std::vector<int32_t> ops, nodes;
+  int32_t depth = 0;
+};
+
+PhyloHMM::SeedLineage PhyloHMM::OpenSeedLineage(const std::string& seed_seq) {
   Require(have_tree_, "InitializePhyloParameters must be called first");
-  const int seed_tip = SeedTip(seed_seq);
+  SeedLineage s;
+  s.seed_tip = SeedTip(seed_seq);
   CreateFamily();
   Require(device_sampler_, "the family has no device sampler tables (needed by the posterior kernel)");
+  const int T = tree_.n_tips;
+  s.ops.resize((std::size_t)(T - 2) * 4);
+  CheckHip(lh_schedule_tree(T, tree_.children.data(), tree_.root, s.ops.data(), &s.depth), "lh_schedule_tree");
+  s.nodes = SeedPath(tree_.children.data(), T, tree_.root, s.seed_tip);
+  Require(!s.nodes.empty(), "the seed sequence '" + seed_seq + "' does not descend from the root");
+  return s;
+}
+
+PhyloHMM::AncestralMarginalsResult PhyloHMM::AncestralMarginals(const std::string& seed_seq) {
+  SeedLineage s = OpenSeedLineage(seed_seq);
   const int T = tree_.n_tips, R = num_rates_;
   const std::size_t L = (std::size_t)msa_.cols();
-  std::vector<int32_t> ops((std::size_t)(T - 2) * 4);
-  int32_t depth = 0;
-  CheckHip(lh_schedule_tree(T, tree_.children.data(), tree_.root, ops.data(), &depth), "lh_schedule_tree");
   AncestralMarginalsResult res;
-  res.nodes = SeedPath(tree_.children.data(), T, tree_.root, seed_tip);
-  Require(!res.nodes.empty(), "the seed sequence '" + seed_seq + "' does not descend from the root");
+  res.nodes = std::move(s.nodes);
   const std::size_t P = res.nodes.size();
   res.n_sites = (int)L;
   res.num_rates = R;
@@ -1900,7 +1976,7 @@ PhyloHMM::AncestralMarginalsResult PhyloHMM::AncestralMarginals(const std::strin
   outs.loglik = &res.loglik;
   outs.marg = res.marg.data();
   outs.rate_post = res.rate_post.data();
-  CheckHip(lh_eval_ancestral_batch(family_, 1, T, depth, ops.data(), tree_.brlen.data(), er_.data(), pi_.data(), &alpha_, R,
+  CheckHip(lh_eval_ancestral_batch(family_, 1, T, s.depth, s.ops.data(), tree_.brlen.data(), er_.data(), pi_.data(), &alpha_, R,
                                    res.nodes.data(), (int32_t)P, &outs),
            "lh_eval_ancestral_batch");
   return res;
@@ -1928,100 +2004,97 @@ void PhyloHMM::WriteRateTable(std::ostream& o, const double* rate_post, std::siz
   }
 }
 
+// The seed's chains of a batch of table rows (FlattenTable with the children), padded with -1 into path[m][P]
+struct PhyloHMM::SeedChains {
+  std::vector<std::vector<int32_t>> chain;
+  std::size_t P = 1;
+  std::vector<int32_t> path;
+};
+
+// *path_len: the lengths of the chains of rows off .. off + m - 1
+PhyloHMM::SeedChains PhyloHMM::SeedChainsOf(const TableBatch& tb, std::size_t off, int seed_tip, const std::string& seed_seq,
+                                            int32_t* path_len) const {
+  const int T = (int)xmsa_labels_.size();
+  const std::size_t m = (std::size_t)tb.dev.n;
+  SeedChains c;
+  c.chain.resize(m);
+  for (std::size_t i = 0; i < m; ++i) {
+    c.chain[i] = SeedPath(tb.children.data() + i * 2 * (std::size_t)(T - 2), T, tb.root[i], seed_tip);
+    Require(!c.chain[i].empty(),
+            "row " + std::to_string(off + i) + ": the seed sequence '" + seed_seq + "' does not descend from the root");
+    c.P = std::max(c.P, c.chain[i].size());
+    path_len[i] = (int32_t)c.chain[i].size();
+  }
+  c.path.assign(m * c.P, -1);
+  for (std::size_t i = 0; i < m; ++i) std::copy(c.chain[i].begin(), c.chain[i].end(), c.path.begin() + i * c.P);
+  return c;
+}
+
+// rows.tsv of K11's and K12's pipelines: row, weight, chain_length, and the column `extra_name` where there is one
+void PhyloHMM::WriteSeedRows(std::ostream& rows, std::size_t first, const WeightedRows& w, const std::vector<int32_t>& path_len,
+                             const char* extra_name, const std::vector<double>* extra) {
+  rows << "row\tweight\tchain_length" << (extra ? "\t" : "") << (extra ? extra_name : "") << '\n';
+  for (std::size_t u = 0; u < w.lw.size(); ++u) {
+    rows << (first + u) << '\t' << Fmt17(w.weight(u)) << '\t' << path_len[u];
+    if (extra) rows << '\t' << Fmt17((*extra)[u]);
+    rows << '\n';
+  }
+}
+
 void PhyloHMM::RunAncestralMarginalsPipeline(const std::string& input_path, const std::string& seed_seq,
                                              const std::string& output_prefix, int num_rates, double burnin_frac) {
-  Require(devices_.size() <= 1, "the ancestral marginals pipeline runs on one device: --devices may list only one");
-  Require(burnin_frac >= 0.0 && burnin_frac < 1.0, "burn-in fraction must be in [0, 1)");
-  const int seed_tip = SeedTip(seed_seq);
-  CreateFamily();
-  Require(device_sampler_, "the family has no device sampler tables (needed by the posterior kernel)");
+  const int seed_tip = BeginPipeline("ancestral marginals", "posterior", burnin_frac, &seed_seq);
   const int T = (int)xmsa_labels_.size(), R = num_rates;
   const std::size_t L = (std::size_t)msa_.cols();
   TsvTable table = TsvTable::OpenRevBayesTable(input_path);
-  const std::size_t N = table.rows.size();
-  const std::size_t first = (std::size_t)std::floor(burnin_frac * (double)N);
+  const std::size_t first = FirstUsedRow(table.rows.size(), burnin_frac);
   // the rows' tables come back whole (32 P L bytes each, P <= T - 2): a batch is bounded by at most 512 MiB of them
   const std::size_t NE = 2 * L * 4, NR = L * (std::size_t)R;
   const std::size_t fit = std::max<std::size_t>(1, ((std::size_t)512 << 20) / (sizeof(double) * ((std::size_t)(T - 2) * L * 4 + NR)));
-  const std::size_t kBatch = host_options().pipeline_batch > 0 ? (std::size_t)host_options().pipeline_batch
-                                                                : std::min<std::size_t>(8192, fit);
-  // the rows' tables are added up on the host in row order: the files do not depend on the batch size
-  WeightedSums acc(NE + NR);
-  std::vector<double> marg, rate_post, row(NE + NR);
-  std::vector<double> lw(N - first);
-  std::vector<int32_t> path_len(N - first, 0);
-  std::size_t skipped = 0;
-  for (std::size_t off = first; off < N; off += kBatch) {
-    const std::size_t m = std::min(kBatch, N - off);
-    TableBatch tb = FlattenTable(table, off, off + m, false, true, input_path, true);
-    const DeviceBatch& b = tb.dev;
-    std::vector<std::vector<int32_t>> chain(m);
-    std::size_t P = 1;
-    for (std::size_t i = 0; i < m; ++i) {
-      chain[i] = SeedPath(tb.children.data() + i * 2 * (std::size_t)(T - 2), T, tb.root[i], seed_tip);
-      Require(!chain[i].empty(),
-              "row " + std::to_string(off + i) + ": the seed sequence '" + seed_seq + "' does not descend from the root");
-      P = std::max(P, chain[i].size());
-    }
-    std::vector<int32_t> path(m * P, -1);
-    for (std::size_t i = 0; i < m; ++i) std::copy(chain[i].begin(), chain[i].end(), path.begin() + i * P);
-    std::vector<double> ll(m);
-    marg.resize(m * P * L * 4);
-    rate_post.resize(m * NR);
-    lh_ancestral_outputs outs{};
-    outs.loglik = ll.data();
-    outs.marg = marg.data();
-    outs.rate_post = rate_post.data();
-    CheckHip(lh_eval_ancestral_batch(family_, b.n, b.n_tips, b.max_depth, b.ops.data(), b.brlen.data(), b.er.data(),
-                                     b.pi.data(), b.alpha.data(), R, path.data(), (int32_t)P, &outs),
-             "lh_eval_ancestral_batch");
-    for (std::size_t i = 0; i < m; ++i) {
-      const std::size_t u = off - first + i;
-      const double st[3] = {ll[i] - tb.lik[i], 1.0, 1.0};  // one row, its weight relative to itself
-      lw[u] = st[0];
-      path_len[u] = (int32_t)chain[i].size();
-      if (!std::isfinite(st[0])) {
-        ++skipped;
-        continue;
-      }
-      const double* mi = marg.data() + i * P * L * 4;
-      std::copy(mi, mi + L * 4, row.begin());                                                        // the seed's parent
-      std::copy(mi + (chain[i].size() - 1) * L * 4, mi + chain[i].size() * L * 4, row.begin() + L * 4);  // the MRCA
-      std::copy(rate_post.begin() + i * NR, rate_post.begin() + (i + 1) * NR, row.begin() + NE);
-      acc.Add(row.data(), st);
-    }
-  }
-  Require(acc.s1 > 0.0, "ancestral marginals pipeline: no row with a finite weight");
-  acc.Normalise();
+  std::vector<double> marg, rate_post;
+  std::vector<int32_t> path_len(table.rows.size() - first, 0);
+  SeedChains sc;
+  const WeightedRows w = SumWeightedRows(
+      "ancestral marginals", table, input_path, first, PipelineBatch(fit), NE + NR, true,
+      [&](const TableBatch& tb, std::size_t off, double* ll) {
+        const DeviceBatch& b = tb.dev;
+        sc = SeedChainsOf(tb, off, seed_tip, seed_seq, path_len.data() + (off - first));
+        marg.resize((std::size_t)b.n * sc.P * L * 4);
+        rate_post.resize((std::size_t)b.n * NR);
+        lh_ancestral_outputs outs{};
+        outs.loglik = ll;
+        outs.marg = marg.data();
+        outs.rate_post = rate_post.data();
+        CheckHip(lh_eval_ancestral_batch(family_, b.n, b.n_tips, b.max_depth, b.ops.data(), b.brlen.data(), b.er.data(),
+                                         b.pi.data(), b.alpha.data(), R, sc.path.data(), (int32_t)sc.P, &outs),
+                 "lh_eval_ancestral_batch");
+        return [&](std::size_t i, double* row) {
+          const std::size_t len = sc.chain[i].size();
+          const double* mi = marg.data() + i * sc.P * L * 4;
+          std::copy(mi, mi + L * 4, row);                                    // the seed's parent
+          std::copy(mi + (len - 1) * L * 4, mi + len * L * 4, row + L * 4);  // the MRCA
+          std::copy(rate_post.begin() + i * NR, rate_post.begin() + (i + 1) * NR, row + NE);
+        };
+      });
   std::ofstream parent(output_prefix + ".parent.tsv"), mrca(output_prefix + ".mrca.tsv"), rates(output_prefix + ".rates.tsv"),
       rows(output_prefix + ".rows.tsv"), summary(output_prefix + ".summary.tsv");
   Require(parent.good() && mrca.good() && rates.good() && rows.good() && summary.good(), "Can't write " + output_prefix + ".*.tsv");
-  WriteNodeTable(parent, acc.total.data(), L);
-  WriteNodeTable(mrca, acc.total.data() + L * 4, L);
-  WriteRateTable(rates, acc.total.data() + NE, L, R);
-  rows << "row\tweight\tchain_length\n";
-  for (std::size_t u = 0; u < lw.size(); ++u)
-    rows << (first + u) << '\t' << Fmt17(std::isfinite(lw[u]) ? std::exp(lw[u] - acc.mx) : 0.0) << '\t' << path_len[u] << '\n';
-  summary << "key\tvalue\nrows_used\t" << (N - first - skipped) << "\nrows_skipped_nonfinite\t" << skipped << "\nkish_ess\t"
-          << Fmt17(acc.KishEss()) << "\n";
+  WriteNodeTable(parent, w.acc.total.data(), L);
+  WriteNodeTable(mrca, w.acc.total.data() + L * 4, L);
+  WriteRateTable(rates, w.acc.total.data() + NE, L, R);
+  WriteSeedRows(rows, first, w, path_len);
+  WriteSummary(summary, w.used(), w.skipped, Fmt17(w.acc.KishEss()));
 }
 
 
 // ---- K12: exact substitution posteriors along the edges of a seed's lineage ----
 
 PhyloHMM::LineageSubstitutionsResult PhyloHMM::LineageSubstitutions(const std::string& seed_seq) {
-  Require(have_tree_, "InitializePhyloParameters must be called first");
-  const int seed_tip = SeedTip(seed_seq);
-  CreateFamily();
-  Require(device_sampler_, "the family has no device sampler tables (needed by the posterior kernel)");
-  const int T = tree_.n_tips, R = num_rates_;
+  SeedLineage lin = OpenSeedLineage(seed_seq);
+  const int T = tree_.n_tips, R = num_rates_, seed_tip = lin.seed_tip;
   const std::size_t L = (std::size_t)msa_.cols();
-  std::vector<int32_t> ops((std::size_t)(T - 2) * 4);
-  int32_t depth = 0;
-  CheckHip(lh_schedule_tree(T, tree_.children.data(), tree_.root, ops.data(), &depth), "lh_schedule_tree");
   LineageSubstitutionsResult res;
-  res.nodes = SeedPath(tree_.children.data(), T, tree_.root, seed_tip);
-  Require(!res.nodes.empty(), "the seed sequence '" + seed_seq + "' does not descend from the root");
+  res.nodes = std::move(lin.nodes);
   const std::size_t P = res.nodes.size();
   res.n_sites = (int)L;
   res.edge.assign(P * L * 16, 0.0);
@@ -2034,7 +2107,7 @@ PhyloHMM::LineageSubstitutionsResult PhyloHMM::LineageSubstitutions(const std::s
   outs.naive_edge = res.naive_edge.data();
   outs.chain_counts = res.chain_counts.data();
   outs.edge_load = load.data();
-  CheckHip(lh_eval_edges_batch(family_, 1, T, depth, ops.data(), tree_.brlen.data(), er_.data(), pi_.data(), &alpha_, R,
+  CheckHip(lh_eval_edges_batch(family_, 1, T, lin.depth, lin.ops.data(), tree_.brlen.data(), er_.data(), pi_.data(), &alpha_, R,
                                res.nodes.data(), (int32_t)P, seed_tip, &outs),
            "lh_eval_edges_batch");
   res.edges.resize(P + 1);
@@ -2071,88 +2144,56 @@ void PhyloHMM::WritePairTable(std::ostream& o, const double* table, std::size_t 
 
 void PhyloHMM::RunLineageSubstitutionsPipeline(const std::string& input_path, const std::string& seed_seq,
                                                const std::string& output_prefix, int num_rates, double burnin_frac) {
-  Require(devices_.size() <= 1, "the lineage substitutions pipeline runs on one device: --devices may list only one");
-  Require(burnin_frac >= 0.0 && burnin_frac < 1.0, "burn-in fraction must be in [0, 1)");
-  const int seed_tip = SeedTip(seed_seq);
-  CreateFamily();
-  Require(device_sampler_, "the family has no device sampler tables (needed by the posterior kernel)");
+  const int seed_tip = BeginPipeline("lineage substitutions", "posterior", burnin_frac, &seed_seq);
   const int T = (int)xmsa_labels_.size(), R = num_rates;
   const std::size_t L = (std::size_t)msa_.cols();
   TsvTable table = TsvTable::OpenRevBayesTable(input_path);
-  const std::size_t N = table.rows.size();
-  const std::size_t first = (std::size_t)std::floor(burnin_frac * (double)N);
+  const std::size_t first = FirstUsedRow(table.rows.size(), burnin_frac);
   // only the rows' reductions come back (52 L + P + 1 doubles each): a batch is bounded by at most 512 MiB of them
   const std::size_t NC = L * 16, NN = L * 20, NROW = 2 * NC + NN;
   const std::size_t fit = std::max<std::size_t>(1, ((std::size_t)512 << 20) / (sizeof(double) * (NROW + (std::size_t)T)));
-  const std::size_t kBatch = host_options().pipeline_batch > 0 ? (std::size_t)host_options().pipeline_batch
-                                                                : std::min<std::size_t>(8192, fit);
-  // the rows' tables are added up on the host in row order: the files do not depend on the batch size
-  WeightedSums acc(NROW);
-  std::vector<double> cc, se, ne, load, row(NROW);
-  std::vector<double> lw(N - first), subs(N - first, 0.0);
-  std::vector<int32_t> path_len(N - first, 0);
-  std::size_t skipped = 0;
-  for (std::size_t off = first; off < N; off += kBatch) {
-    const std::size_t m = std::min(kBatch, N - off);
-    TableBatch tb = FlattenTable(table, off, off + m, false, true, input_path, true);
-    const DeviceBatch& b = tb.dev;
-    std::vector<std::vector<int32_t>> chain(m);
-    std::size_t P = 1;
-    for (std::size_t i = 0; i < m; ++i) {
-      chain[i] = SeedPath(tb.children.data() + i * 2 * (std::size_t)(T - 2), T, tb.root[i], seed_tip);
-      Require(!chain[i].empty(),
-              "row " + std::to_string(off + i) + ": the seed sequence '" + seed_seq + "' does not descend from the root");
-      P = std::max(P, chain[i].size());
-    }
-    std::vector<int32_t> path(m * P, -1);
-    for (std::size_t i = 0; i < m; ++i) std::copy(chain[i].begin(), chain[i].end(), path.begin() + i * P);
-    std::vector<double> ll(m);
-    cc.resize(m * NC);
-    se.resize(m * NC);
-    ne.resize(m * NN);
-    load.resize(m * (P + 1));
-    lh_eval_edges_outputs outs{};
-    outs.loglik = ll.data();
-    outs.chain_counts = cc.data();
-    outs.seed_edge = se.data();
-    outs.naive_edge = ne.data();
-    outs.edge_load = load.data();
-    CheckHip(lh_eval_edges_batch(family_, b.n, b.n_tips, b.max_depth, b.ops.data(), b.brlen.data(), b.er.data(), b.pi.data(),
-                                 b.alpha.data(), R, path.data(), (int32_t)P, seed_tip, &outs),
-             "lh_eval_edges_batch");
-    for (std::size_t i = 0; i < m; ++i) {
-      const std::size_t u = off - first + i;
-      const double st[3] = {ll[i] - tb.lik[i], 1.0, 1.0};  // one row, its weight relative to itself
-      lw[u] = st[0];
-      path_len[u] = (int32_t)chain[i].size();
-      const double* li = load.data() + i * (P + 1);
-      double total = li[P];  // the naive edge, then the slots from the MRCA down (padding slots hold 0)
-      for (std::size_t s = chain[i].size(); s-- > 0;) total += li[s];
-      subs[u] = total;
-      if (!std::isfinite(st[0])) {
-        ++skipped;
-        continue;
-      }
-      std::copy(cc.begin() + i * NC, cc.begin() + (i + 1) * NC, row.begin());
-      std::copy(se.begin() + i * NC, se.begin() + (i + 1) * NC, row.begin() + NC);
-      std::copy(ne.begin() + i * NN, ne.begin() + (i + 1) * NN, row.begin() + 2 * NC);
-      acc.Add(row.data(), st);
-    }
-  }
-  Require(acc.s1 > 0.0, "lineage substitutions pipeline: no row with a finite weight");
-  acc.Normalise();
+  std::vector<double> cc, se, ne, load, subs(table.rows.size() - first, 0.0);
+  std::vector<int32_t> path_len(table.rows.size() - first, 0);
+  const WeightedRows w = SumWeightedRows(
+      "lineage substitutions", table, input_path, first, PipelineBatch(fit), NROW, true,
+      [&](const TableBatch& tb, std::size_t off, double* ll) {
+        const DeviceBatch& b = tb.dev;
+        const std::size_t m = (std::size_t)b.n;
+        const SeedChains sc = SeedChainsOf(tb, off, seed_tip, seed_seq, path_len.data() + (off - first));
+        const std::size_t P = sc.P;
+        cc.resize(m * NC);
+        se.resize(m * NC);
+        ne.resize(m * NN);
+        load.resize(m * (P + 1));
+        lh_eval_edges_outputs outs{};
+        outs.loglik = ll;
+        outs.chain_counts = cc.data();
+        outs.seed_edge = se.data();
+        outs.naive_edge = ne.data();
+        outs.edge_load = load.data();
+        CheckHip(lh_eval_edges_batch(family_, b.n, b.n_tips, b.max_depth, b.ops.data(), b.brlen.data(), b.er.data(), b.pi.data(),
+                                     b.alpha.data(), R, sc.path.data(), (int32_t)P, seed_tip, &outs),
+                 "lh_eval_edges_batch");
+        for (std::size_t i = 0; i < m; ++i) {
+          const double* li = load.data() + i * (P + 1);
+          double total = li[P];  // the naive edge, then the slots from the MRCA down (padding slots hold 0)
+          for (std::size_t s = sc.chain[i].size(); s-- > 0;) total += li[s];
+          subs[off - first + i] = total;
+        }
+        return [&](std::size_t i, double* row) {
+          std::copy(cc.begin() + i * NC, cc.begin() + (i + 1) * NC, row);
+          std::copy(se.begin() + i * NC, se.begin() + (i + 1) * NC, row + NC);
+          std::copy(ne.begin() + i * NN, ne.begin() + (i + 1) * NN, row + 2 * NC);
+        };
+      });
   std::ofstream counts(output_prefix + ".substitutions.tsv"), seed(output_prefix + ".seed_edge.tsv"),
       naive(output_prefix + ".naive_edge.tsv"), rows(output_prefix + ".rows.tsv"), summary(output_prefix + ".summary.tsv");
   Require(counts.good() && seed.good() && naive.good() && rows.good() && summary.good(), "Can't write " + output_prefix + ".*.tsv");
-  WritePairTable(counts, acc.total.data(), L, 4, true);
-  WritePairTable(seed, acc.total.data() + NC, L, 4, false);
-  WritePairTable(naive, acc.total.data() + 2 * NC, L, 5, false);
-  rows << "row\tweight\tchain_length\texpected_substitutions\n";
-  for (std::size_t u = 0; u < lw.size(); ++u)
-    rows << (first + u) << '\t' << Fmt17(std::isfinite(lw[u]) ? std::exp(lw[u] - acc.mx) : 0.0) << '\t' << path_len[u] << '\t'
-         << Fmt17(subs[u]) << '\n';
-  summary << "key\tvalue\nrows_used\t" << (N - first - skipped) << "\nrows_skipped_nonfinite\t" << skipped << "\nkish_ess\t"
-          << Fmt17(acc.KishEss()) << "\n";
+  WritePairTable(counts, w.acc.total.data(), L, 4, true);
+  WritePairTable(seed, w.acc.total.data() + NC, L, 4, false);
+  WritePairTable(naive, w.acc.total.data() + 2 * NC, L, 5, false);
+  WriteSeedRows(rows, first, w, path_len, "expected_substitutions", &subs);
+  WriteSummary(summary, w.used(), w.skipped, Fmt17(w.acc.KishEss()));
 }
 
 
@@ -2273,51 +2314,35 @@ void PhyloHMM::WriteAminoAcidTable(std::ostream& o, const CodonMarginalsResult& 
 
 void PhyloHMM::RunCodonMarginalsPipeline(const std::string& input_path, const std::string& output_prefix, int num_rates,
                                          double burnin_frac, int frame) {
-  Require(devices_.size() <= 1, "the codon marginals pipeline runs on one device: --devices may list only one");
-  Require(burnin_frac >= 0.0 && burnin_frac < 1.0, "burn-in fraction must be in [0, 1)");
-  CreateFamily();
-  Require(device_sampler_, "the family has no device sampler tables (needed by the codon kernel)");
+  BeginPipeline("codon marginals", "codon", burnin_frac);
   const CodonLayout lay = SetCodons(family_, frame);
   TsvTable table = TsvTable::OpenRevBayesTable(input_path);
-  const std::size_t N = table.rows.size();
-  const std::size_t first = (std::size_t)std::floor(burnin_frac * (double)N);
+  const std::size_t first = FirstUsedRow(table.rows.size(), burnin_frac);
   const std::size_t NW = (std::size_t)lay.n_window * 125, NG = (std::size_t)lay.n_genes;
   // the rows' windows and genes come back whole: a batch is bounded by their size (NW + NG doubles per row)
-  const std::size_t kBatch = host_options().pipeline_batch > 0 ? (std::size_t)host_options().pipeline_batch : 8192;
-  WeightedSums acc(NW + NG);
-  std::vector<double> windows, genes, row(NW + NG);
-  std::size_t skipped = 0;
-  for (std::size_t off = first; off < N; off += kBatch) {
-    const std::size_t m = std::min(kBatch, N - off);
-    TableBatch tb = FlattenTable(table, off, off + m, false, true, input_path);
-    const DeviceBatch& b = tb.dev;
-    std::vector<double> ll(m);
-    windows.resize(m * NW);
-    genes.resize(m * NG);
-    lh_codon_outputs outs{nullptr, ll.data(), windows.data(), genes.data(), nullptr, nullptr, nullptr};
-    CheckHip(lh_eval_codons_batch(family_, b.n, b.n_tips, b.max_depth, b.ops.data(), b.brlen.data(), b.er.data(),
-                                  b.pi.data(), b.alpha.data(), num_rates, &outs),
-             "lh_eval_codons_batch");
-    for (std::size_t i = 0; i < m; ++i) {
-      const double st[3] = {ll[i] - tb.lik[i], 1.0, 1.0};  // one row, its weight relative to itself
-      if (!std::isfinite(st[0])) {
-        ++skipped;
-        continue;
-      }
-      std::copy(windows.begin() + i * NW, windows.begin() + (i + 1) * NW, row.begin());
-      std::copy(genes.begin() + i * NG, genes.begin() + (i + 1) * NG, row.begin() + NW);
-      acc.Add(row.data(), st);
-    }
-  }
-  Require(acc.s1 > 0.0, "codon marginals pipeline: no row with a finite weight");
-  acc.Normalise();
-  const CodonMarginalsResult res = ExpandCodons(frame, lay.window_codon, acc.total.data(), acc.total.data() + NW);
+  std::vector<double> windows, genes;
+  const WeightedRows w = SumWeightedRows(
+      "codon marginals", table, input_path, first, PipelineBatch(8192), NW + NG, false,
+      [&](const TableBatch& tb, std::size_t, double* ll) {
+        const DeviceBatch& b = tb.dev;
+        windows.resize((std::size_t)b.n * NW);
+        genes.resize((std::size_t)b.n * NG);
+        lh_codon_outputs outs{nullptr, ll, windows.data(), genes.data(), nullptr, nullptr, nullptr};
+        CheckHip(lh_eval_codons_batch(family_, b.n, b.n_tips, b.max_depth, b.ops.data(), b.brlen.data(), b.er.data(),
+                                      b.pi.data(), b.alpha.data(), num_rates, &outs),
+                 "lh_eval_codons_batch");
+        return [&](std::size_t i, double* row) {
+          std::copy(windows.begin() + i * NW, windows.begin() + (i + 1) * NW, row);
+          std::copy(genes.begin() + i * NG, genes.begin() + (i + 1) * NG, row + NW);
+        };
+      });
+  const CodonMarginalsResult res = ExpandCodons(frame, lay.window_codon, w.acc.total.data(), w.acc.total.data() + NW);
   std::ofstream codons(output_prefix + ".codons.tsv"), aa(output_prefix + ".aa.tsv"), summary(output_prefix + ".summary.tsv");
   Require(codons.good() && aa.good() && summary.good(), "Can't write " + output_prefix + ".*.tsv");
   WriteCodonTable(codons, res);
   WriteAminoAcidTable(aa, res);
-  summary << "key\tvalue\nrows_used\t" << (N - first - skipped) << "\nrows_skipped_nonfinite\t" << skipped << "\nkish_ess\t"
-          << ReprDouble(acc.KishEss()) << "\nframe\t" << frame << "\n";
+  WriteSummary(summary, w.used(), w.skipped, ReprDouble(w.acc.KishEss()));
+  summary << "frame\t" << frame << "\n";
 }
 
 
@@ -2331,12 +2356,6 @@ struct EventsJunctionView {
   int site0, W;
   const char *left_column, *right_column, *name;
 };
-
-std::string Fmt17(double v) {
-  char buf[64];
-  std::snprintf(buf, sizeof buf, "%.17g", v);
-  return buf;
-}
 
 std::vector<EventsJunctionView> EventsJunctions(const std::string& locus, const std::map<std::string, std::pair<int, int>>& fb,
                                                 const RegionStates& vgerm, const RegionStates& vd, const RegionStates& dgerm,
@@ -2491,10 +2510,7 @@ void PhyloHMM::WriteSpanTable(std::ostream& o, const EventsResult& m) {
 
 void PhyloHMM::RunEventsPipeline(const std::string& input_path, const std::string& output_prefix, int num_rates,
                                  double burnin_frac) {
-  Require(devices_.size() <= 1, "the events pipeline runs on one device: --devices may list only one");
-  Require(burnin_frac >= 0.0 && burnin_frac < 1.0, "burn-in fraction must be in [0, 1)");
-  CreateFamily();
-  Require(device_sampler_, "the family has no device sampler tables (needed by the events kernel)");
+  BeginPipeline("events", "events", burnin_frac);
   const std::size_t NE = EventsSize(), NG = EventsGenes();
   {
     int64_t size = 0;
@@ -2504,48 +2520,33 @@ void PhyloHMM::RunEventsPipeline(const std::string& input_path, const std::strin
     Require((std::size_t)size == NE && (std::size_t)n_genes == NG, "the device's events layout differs from the host's state space");
   }
   TsvTable table = TsvTable::OpenRevBayesTable(input_path);
-  const std::size_t N = table.rows.size();
-  const std::size_t first = (std::size_t)std::floor(burnin_frac * (double)N);
+  const std::size_t first = FirstUsedRow(table.rows.size(), burnin_frac);
   // the rows' tables come back whole: a batch is bounded by their size (at most 512 MiB of them)
   const std::size_t fit = std::max<std::size_t>(1, ((std::size_t)512 << 20) / (sizeof(double) * (NE + NG)));
-  const std::size_t kBatch = host_options().pipeline_batch > 0 ? (std::size_t)host_options().pipeline_batch
-                                                                : std::min<std::size_t>(8192, fit);
-  WeightedSums acc(NE + NG);
-  std::vector<double> events, genes, row(NE + NG);
-  std::size_t skipped = 0;
-  for (std::size_t off = first; off < N; off += kBatch) {
-    const std::size_t m = std::min(kBatch, N - off);
-    TableBatch tb = FlattenTable(table, off, off + m, false, true, input_path);
-    const DeviceBatch& b = tb.dev;
-    std::vector<double> ll(m);
-    events.resize(m * NE);
-    genes.resize(m * NG);
-    lh_events_outputs outs{nullptr, ll.data(), events.data(), genes.data(), nullptr, nullptr, nullptr};
-    CheckHip(lh_eval_events_batch(family_, b.n, b.n_tips, b.max_depth, b.ops.data(), b.brlen.data(), b.er.data(),
-                                  b.pi.data(), b.alpha.data(), num_rates, &outs),
-             "lh_eval_events_batch");
-    for (std::size_t i = 0; i < m; ++i) {
-      const double st[3] = {ll[i] - tb.lik[i], 1.0, 1.0};  // one row, its weight relative to itself
-      if (!std::isfinite(st[0])) {
-        ++skipped;
-        continue;
-      }
-      std::copy(events.begin() + i * NE, events.begin() + (i + 1) * NE, row.begin());
-      std::copy(genes.begin() + i * NG, genes.begin() + (i + 1) * NG, row.begin() + NE);
-      acc.Add(row.data(), st);
-    }
-  }
-  Require(acc.s1 > 0.0, "events pipeline: no row with a finite weight");
-  acc.Normalise();
-  const EventsResult res = MapEvents(acc.total.data(), acc.total.data() + NE);
+  std::vector<double> events, genes;
+  const WeightedRows w = SumWeightedRows(
+      "events", table, input_path, first, PipelineBatch(fit), NE + NG, false,
+      [&](const TableBatch& tb, std::size_t, double* ll) {
+        const DeviceBatch& b = tb.dev;
+        events.resize((std::size_t)b.n * NE);
+        genes.resize((std::size_t)b.n * NG);
+        lh_events_outputs outs{nullptr, ll, events.data(), genes.data(), nullptr, nullptr, nullptr};
+        CheckHip(lh_eval_events_batch(family_, b.n, b.n_tips, b.max_depth, b.ops.data(), b.brlen.data(), b.er.data(),
+                                      b.pi.data(), b.alpha.data(), num_rates, &outs),
+                 "lh_eval_events_batch");
+        return [&](std::size_t i, double* row) {
+          std::copy(events.begin() + i * NE, events.begin() + (i + 1) * NE, row);
+          std::copy(genes.begin() + i * NG, genes.begin() + (i + 1) * NG, row + NE);
+        };
+      });
+  const EventsResult res = MapEvents(w.acc.total.data(), w.acc.total.data() + NE);
   std::ofstream dels(output_prefix + ".deletions.tsv"), ins(output_prefix + ".insertions.tsv"),
       spans(output_prefix + ".spans.tsv"), summary(output_prefix + ".summary.tsv");
   Require(dels.good() && ins.good() && spans.good() && summary.good(), "Can't write " + output_prefix + ".*.tsv");
   WriteDeletionTable(dels, res);
   WriteInsertionTable(ins, res);
   WriteSpanTable(spans, res);
-  summary << "key\tvalue\nrows_used\t" << (N - first - skipped) << "\nrows_skipped_nonfinite\t" << skipped << "\nkish_ess\t"
-          << Fmt17(acc.KishEss()) << "\n";
+  WriteSummary(summary, w.used(), w.skipped, Fmt17(w.acc.KishEss()));
 }
 
 

@@ -337,6 +337,20 @@ class PhyloHMM : public HMM {
  private:
   TableBatch FlattenTable(const TsvTable& table, std::size_t r0, std::size_t r1, bool with_export, bool with_scalars,
                           const std::string& path, bool with_children = false) const;
+  /// What the pipelines over a RevBayes table refuse before any file is opened, in this order: more than one device
+  /// ("the <what> pipeline ..."), the burn-in fraction, the seed sequence (returns its tip; 0 without one), then a
+  /// family without sampler tables ("needed by the <kernel> kernel").
+  int BeginPipeline(const std::string& what, const std::string& kernel, double burnin_frac, const std::string* seed_seq = nullptr);
+  struct WeightedRows;
+  template <class Batch>
+  WeightedRows SumWeightedRows(const std::string& what, const TsvTable& table, const std::string& input_path, std::size_t first,
+                               std::size_t batch_rows, std::size_t width, bool with_children, Batch&& batch) const;
+  struct SeedLineage;
+  SeedLineage OpenSeedLineage(const std::string& seed_seq);
+  struct SeedChains;
+  SeedChains SeedChainsOf(const TableBatch& tb, std::size_t off, int seed_tip, const std::string& seed_seq, int32_t* path_len) const;
+  static void WriteSeedRows(std::ostream& rows, std::size_t first, const WeightedRows& w, const std::vector<int32_t>& path_len,
+                            const char* extra_name = nullptr, const std::vector<double>* extra = nullptr);
   struct AsrRow;
   /// The rows of a RunPipeline table as RunAsr and RunLineagePipeline read them; *num_rates = the sr[] columns.
   std::vector<AsrRow> ReadAsrRows(const std::string& input_path, int* num_rates) const;

@@ -7,6 +7,7 @@
 #include <chrono>
 #include <cmath>
 #include <cstdint>
+#include <cstdio>
 #include <stdexcept>
 #include <string>
 #include <unordered_map>
@@ -75,6 +76,13 @@ std::string DecodeBases(const uint8_t* bytes, std::size_t n, const std::string& 
 /// violations throw so that a library user gets a message instead of an abort.
 inline void Require(bool cond, const std::string& what) {
   if (!cond) throw std::runtime_error("linearham: requirement failed: " + what);
+}
+
+/// %.17g: enough digits for a double to read back as the same bits (the numbers of the pipelines' tables)
+inline std::string Fmt17(double v) {
+  char buf[40];
+  std::snprintf(buf, sizeof buf, "%.17g", v);
+  return buf;
 }
 
 /// The environment switches of the host library (test hooks; read once per process).

@@ -1042,7 +1042,7 @@ int refuse_schedules(lh_family* f, const char* who) {
 
 // The end of a host-pointer call: waits for the device, reads K0c's verdict on the schedules as the device saw them (`who`
 // null: the call ran none), and copies the results back.
-int copy_back(lh_family* f, const char* who, std::initializer_list<HostOut> out) {
+int copy_back(lh_family* f, const char* who, const std::vector<HostOut>& out) {
   if (!who) LH_HIP(hipDeviceSynchronize());
   if (who && check_async_error(f, who)) return 1;
   for (const HostOut& o : out)
@@ -1051,7 +1051,7 @@ int copy_back(lh_family* f, const char* who, std::initializer_list<HostOut> out)
 }
 
 // The end of a host-pointer call that evaluated `host`: its schedules checked beside the device, then copy_back.
-int finish_batch(lh_family* f, const char* who, const TreeBatch& host, std::initializer_list<HostOut> out) {
+int finish_batch(lh_family* f, const char* who, const TreeBatch& host, const std::vector<HostOut>& out) {
   if (!valid_schedules(host)) return refuse_schedules(f, who);
   return copy_back(f, who, out);
 }
@@ -2005,7 +2005,9 @@ namespace {
 // The chain of a sample's path under its own schedule, as K11c checks it on the device: the non-padding entries are inner
 // nodes, each a child of the next, the last one the root; padding (anything outside T .. 2T-3) comes only after them.
 // With seed_tip > 0 also what K12c checks: that tip is a child of path[0] (of the cherry or tip-accumulate op behind it).
-bool valid_chain(const int32_t* ops, int T, const int32_t* path, int P, int seed_tip = 0) {
+// One pass over the schedule tells which of the two failed.
+enum ChainFault { kChain = 0, kNotChain, kNotChild };
+ChainFault chain_fault(const int32_t* ops, int T, const int32_t* path, int P, int seed_tip) {
   const int n_ops = T - 2;
   std::vector<int> parent_op(n_ops, -1), op_of_node(n_ops, -1), slot(16, -1);
   long long named = 0;
@@ -2022,7 +2024,7 @@ bool valid_chain(const int32_t* ops, int T, const int32_t* path, int P, int seed
       name(k - 1, op[2]);
     } else if (kind == lh::OP_POP_ACC) {
       const int q = slot[op[3] & 15];
-      if (q < 0) return false;
+      if (q < 0) return kNotChain;
       parent_op[k - 1] = k;
       parent_op[q] = k;
       name(k - 1, op[2]);
@@ -2030,7 +2032,7 @@ bool valid_chain(const int32_t* ops, int T, const int32_t* path, int P, int seed
     }
   }
   const long long root = (long long)n_ops * T + (long long)n_ops * (n_ops - 1) / 2 - named;
-  if (root < T || root > 2 * T - 3) return false;
+  if (root < T || root > 2 * T - 3) return kNotChain;
   op_of_node[root - T] = n_ops - 1;
   int prev = -1, len = 0, first = -1;
   bool ended = false;
@@ -2040,21 +2042,21 @@ bool valid_chain(const int32_t* ops, int T, const int32_t* path, int P, int seed
       ended = true;
       continue;
     }
-    if (ended) return false;
+    if (ended) return kNotChain;
     const int k = op_of_node[v - T];
-    if (k < 0 || (len > 0 && parent_op[prev] != k)) return false;
+    if (k < 0 || (len > 0 && parent_op[prev] != k)) return kNotChain;
     if (len == 0) first = k;
     prev = k;
     ++len;
   }
-  if (len < 1 || prev != n_ops - 1) return false;
+  if (len < 1 || prev != n_ops - 1) return kNotChain;
   if (seed_tip > 0) {
     const int32_t* op = ops + (size_t)first * 4;
     const int kind = op[0] & 15;
     if (!((kind == lh::OP_CHERRY && (op[1] == seed_tip || op[2] == seed_tip)) || (kind == lh::OP_TIP_ACC && op[1] == seed_tip)))
-      return false;
+      return kNotChild;
   }
-  return true;
+  return kChain;
 }
 
 int ancestral_check(const lh_family* f, const std::string& W, const TreeBatch& b, int P) {
@@ -2082,93 +2084,6 @@ int ancestral_workspace(lh_family* f, int chunk, int T, int R, int P, bool own_r
          a.plen.get<int32_t>(), a.desc.get()};
   return 0;
 }
-
-}  // namespace
-
-extern "C" {
-
-int lh_asr_marginals_batch_device(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops,
-                                  const double* brlen, const double* er, const double* pi, const double* rates, int32_t R,
-                                  const double* naive_prob, const int32_t* path, int32_t P, double* marg, double* rate_post,
-                                  void* hip_stream) {
-  const TreeBatch b{n, T, max_depth, ops, brlen, er, pi, rates, R, true};
-  const std::string W = "lh_asr_marginals_batch";
-  if (int rc = check_batch(f, W, b)) return rc > 0;
-  if (ancestral_check(f, W, b, P)) return 1;
-  DeviceGuard guard(f);
-  if (!b.has_arrays() || !naive_prob || !path) return fail(W + ": null array");
-  if (!marg && !rate_post) return 0;  // nothing asked for
-  hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-  const size_t L = f->host.n_sites;
-  const int chunk = (int)std::min<size_t>(n, ancestral_group(f, T, R, P));
-  lh::AncWs ws;
-  if (ensure_workspace(f, chunk, R, T) || ancestral_workspace(f, chunk, T, R, P, !rate_post, &ws)) return 1;
-  Workspace& w = f->ws;
-  double *eig = w.eig.get<double>(), *site_lik = w.site_lik.get<double>();
-  int32_t* site_scal = w.site_scal.get<int32_t>();
-  for (int off = 0; off < n; off += chunk) {
-    const int m = std::min(chunk, n - off);
-    const TreeBatch g = b.slice(off, m);
-    lh::launch_gtr_setup(m, g.er, g.pi, eig, stream);
-    int planes = 0;
-    if (prune_group(f, W, g, g.model, false, stream, &planes)) return 1;
-    if (f->profile && (f->anc_timer.begin(stream) || f->anc_timer.mark(1, stream))) return 1;
-    if (lh::launch_ancestral(f->host, m, R, T, g.ops, g.brlen, g.model, eig, g.pi, site_lik, site_scal,
-                             naive_prob + (size_t)off * L * 5, path + (size_t)off * P, P, ws,
-                             marg ? marg + (size_t)off * P * L * 4 : nullptr, rate_post ? rate_post + (size_t)off * L * R : nullptr,
-                             w.prune.hdr, f->err_flag, stream))
-      return fail(W + ": launch failed");
-    if (f->profile && (f->anc_timer.mark(2, stream) || f->anc_timer.end(stream))) return 1;
-    LH_HIP(hipGetLastError());
-  }
-  return 0;
-}
-
-int lh_asr_marginals_batch(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops, const double* brlen,
-                           const double* er, const double* pi, const double* rates, int32_t R, const double* naive_prob,
-                           const int32_t* path, int32_t P, double* marg, double* rate_post) {
-  const TreeBatch host{n, T, max_depth, ops, brlen, er, pi, rates, R, true};
-  const std::string W = "lh_asr_marginals_batch";
-  if (int rc = check_batch(f, W, host)) return rc > 0;
-  if (ancestral_check(f, W, host, P)) return 1;
-  DeviceGuard guard(f);
-  if (!host.has_arrays() || !naive_prob || !path) return fail(W + ": null array");
-  if (!marg && !rate_post) return 0;
-  const size_t L = f->host.n_sites;
-  if (!valid_schedules(host)) return fail(W + ": malformed schedule op (use lh_schedule_tree)");
-  for (size_t i = 0; i < (size_t)n; ++i)
-    if (!valid_chain(host.schedule(i), T, path + i * P, P))
-      return fail(W + ": path of sample " + std::to_string(i) +
-                  " is not a chain of inner nodes, each the child of the next, that ends at the root (padding after it)");
-  AncestralWs& a = f->anc;
-  // sub-batches bound the device copies of the outputs (marg: 32 P L bytes per sample)
-  const size_t per = sizeof(double) * L * ((size_t)P * 4 + R + 5);
-  const int sub = (int)std::max<size_t>(1, std::min<size_t>(n, ((size_t)1 << 30) / per));
-  for (int off = 0; off < n; off += sub) {
-    const int m = std::min(sub, n - off);
-    const size_t marg_bytes = sizeof(double) * P * L * 4 * m, rp_bytes = sizeof(double) * L * R * m;
-    double *d_marg = nullptr, *d_rp = nullptr;
-    TreeBatch dev;
-    if (out_buf(marg, a.marg, marg_bytes, &d_marg) || out_buf(rate_post, a.rate_post, rp_bytes, &d_rp) ||
-        stage_batch(f, host.slice(off, m),
-                    {{naive_prob + (size_t)off * L * 5, sizeof(double) * L * 5 * m, &a.naive_prob},
-                     {path + (size_t)off * P, sizeof(int32_t) * P * m, &a.path}},
-                    &dev))
-      return 1;
-    if (lh_asr_marginals_batch_device(f, m, T, max_depth, dev.ops, dev.brlen, dev.er, dev.pi, dev.model, R,
-                                      a.naive_prob.get<const double>(), a.path.get<const int32_t>(), P, d_marg, d_rp, nullptr))
-      return 1;
-    if (copy_back(f, W.c_str(),
-                  {{marg ? marg + (size_t)off * P * L * 4 : nullptr, d_marg, marg_bytes},
-                   {rate_post ? rate_post + (size_t)off * L * R : nullptr, d_rp, rp_bytes}}))
-      return 1;
-  }
-  return 0;
-}
-
-}  // extern "C"
-
-namespace {
 
 // K11a's table: per (site, base) the compact entries (lh_eval_outputs.forward's layout) whose state writes that base on
 // that site, in ascending order -- posterior.site_base's mapping and the host library's NaiveMarginals.
@@ -2218,147 +2133,6 @@ int ancestral_table(lh_family* f, const std::string& W) {
   return 0;
 }
 
-}  // namespace
-
-extern "C" {
-
-int lh_eval_ancestral_batch_device(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops,
-                                   const double* brlen, const double* er, const double* pi, const double* alpha, int32_t R,
-                                   const int32_t* path, int32_t P, const lh_ancestral_outputs* outs, void* hip_stream) {
-  const TreeBatch b{n, T, max_depth, ops, brlen, er, pi, alpha, R};
-  const std::string W = "lh_eval_ancestral_batch";
-  if (int rc = check_batch(f, W, b, true)) return rc > 0;
-  if (ancestral_check(f, W, b, P)) return 1;
-  DeviceGuard guard(f);
-  if (!b.has_arrays() || !path) return fail(W + ": null array");
-  const lh_ancestral_outputs none{};
-  const lh_ancestral_outputs& o = outs ? *outs : none;
-  if (ancestral_table(f, W)) return 1;
-  hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-  const size_t L = f->host.n_sites, FS = f->host.forward_size;
-  const int chunk = (int)std::min<size_t>(n, std::min(ancestral_group(f, T, R, P), eval_group(f, T, R)));
-  AncestralWs& a = f->anc;
-  const bool reduce = o.weighted_sum || o.weighted_rate || o.weight_stats;
-  const bool want_marg = o.marg || o.weighted_sum;
-  const bool want_rp = o.rate_post || o.weighted_rate;
-  const size_t slabs = lh::posterior_slabs(n);
-  lh::AncWs ws;
-  double *ll = o.loglik, *sb = o.site_base, *marg = o.marg, *rp = o.rate_post, *ends = nullptr, *pe = nullptr, *pr = nullptr;
-  WeightReduce wr;
-  // what the caller does not take lives per launch group (site_base, marg) or, where the reduction reads it, per batch
-  const size_t sb_rows = o.site_base ? 0 : chunk, marg_rows = (o.marg || !want_marg) ? 0 : chunk;
-  if (ensure_workspace(f, chunk, R, T) || ancestral_workspace(f, chunk, T, R, P, !want_rp, &ws) ||
-      a.plen.ensure(sizeof(int32_t) * n) || a.rates.ensure(sizeof(double) * R * chunk) ||
-      f->forward_dev.ensure(sizeof(double) * FS * n) || own(ll, a.loglik, sizeof(double) * n) ||
-      own(sb, a.site_base, sizeof(double) * L * 5 * sb_rows) || (want_marg && own(marg, a.marg, sizeof(double) * P * L * 4 * marg_rows)) ||
-      (want_rp && own(rp, a.rate_post, sizeof(double) * L * R * n)) ||
-      (reduce && (a.ll_used.ensure(sizeof(double) * n) || wr.prepare(n, a.weights, a.stats, o.weight_stats) ||
-                  (o.weighted_sum && (own(ends, a.ends, sizeof(double) * 2 * L * 4 * n) || own(pe, a.partial_e, sizeof(double) * 2 * L * 4 * slabs))) ||
-                  (o.weighted_rate && own(pr, a.partial_r, sizeof(double) * L * R * slabs)))))
-    return 1;
-  ws.plen = a.plen.get<int32_t>();  // (the batch's, for the reduction; a.plen.ensure above may have moved it)
-  Workspace& w = f->ws;
-  double *eig = w.eig.get<double>(), *site_lik = w.site_lik.get<double>(), *fwd = f->forward_dev.get<double>();
-  double* rates = a.rates.get<double>();
-  int32_t* site_scal = w.site_scal.get<int32_t>();
-  const lh_eval_outputs fwd_outs{nullptr, nullptr, fwd, nullptr};
-  for (int off = 0; off < n; off += chunk) {
-    const int m = std::min(chunk, n - off);
-    const TreeBatch g = b.slice(off, m);
-    lh::launch_model_setup(m, R, g.er, g.pi, g.model, rates, eig, stream);
-    int planes = 0;
-    // one unmixed K1 serves K2 and K11b: its planes outlive K2
-    if (prune_group(f, W, g, rates, false, stream, &planes)) return 1;
-    if (run_forward(f, m, planes, site_lik, site_scal, g.pi, nullptr, nullptr, ll + off, &fwd_outs, off, stream)) return 1;
-    lh::launch_posterior(f->sampler_dev, m, fwd + (size_t)off * FS, FS, ll + off, stream);
-    if (f->profile && f->anc_timer.begin(stream)) return 1;
-    double* sb_g = o.site_base ? sb + (size_t)off * L * 5 : sb;
-    lh::launch_site_base(m, (int)L, FS, a.sb_off.get<const int32_t>(), a.sb_idx.get<const int32_t>(), fwd + (size_t)off * FS,
-                         ll + off, sb_g, stream);
-    if (f->profile && f->anc_timer.mark(1, stream)) return 1;
-    double* marg_g = !want_marg ? nullptr : o.marg ? marg + (size_t)off * P * L * 4 : marg;
-    lh::AncWs wg = ws;
-    wg.plen = ws.plen + off;
-    if (want_marg || want_rp) {
-      if (lh::launch_ancestral(f->host, m, R, T, g.ops, g.brlen, rates, eig, g.pi, site_lik, site_scal, sb_g, path + (size_t)off * P,
-                               P, wg, marg_g, want_rp ? rp + (size_t)off * L * R : nullptr, w.prune.hdr, f->err_flag, stream))
-        return fail(W + ": launch failed");
-    }
-    // the paths were checked wherever marg was formed: a row without one then gets no weight
-    if (reduce && want_marg)
-      lh::launch_ancestral_ends(m, P, (int)L, wg.plen, marg_g, ll + off, o.weighted_sum ? ends + (size_t)off * 2 * L * 4 : nullptr,
-                                a.ll_used.get<double>() + off, stream);
-    if (f->profile && f->anc_timer.mark(2, stream)) return 1;
-    if (reduce && off + m == n) {
-      // (without marg or weighted_sum no path was looked at: the weights are the rows' own)
-      wr.launch(n, want_marg ? a.ll_used.get<const double>() : ll, o.log_offset, stream);
-      if (o.weighted_sum) lh::launch_weighted_slabs(n, 2 * L * 4, ends, wr.w, pe, o.weighted_sum, stream);
-      if (o.weighted_rate) lh::launch_weighted_slabs(n, L * R, rp, wr.w, pr, o.weighted_rate, stream);
-    }
-    if (f->profile && f->anc_timer.end(stream)) return 1;
-    LH_HIP(hipGetLastError());
-  }
-  return 0;
-}
-
-int lh_eval_ancestral_batch(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops, const double* brlen,
-                            const double* er, const double* pi, const double* alpha, int32_t R, const int32_t* path, int32_t P,
-                            const lh_ancestral_outputs* outs) {
-  const TreeBatch host{n, T, max_depth, ops, brlen, er, pi, alpha, R};
-  const std::string W = "lh_eval_ancestral_batch";
-  if (int rc = check_batch(f, W, host, true)) return rc > 0;
-  if (ancestral_check(f, W, host, P)) return 1;
-  DeviceGuard guard(f);
-  if (!host.has_arrays() || !path) return fail(W + ": null array");
-  const lh_ancestral_outputs none{};
-  const lh_ancestral_outputs& o = outs ? *outs : none;
-  if (!o.loglik && !o.site_base && !o.marg && !o.rate_post && !o.weighted_sum && !o.weighted_rate && !o.weight_stats) return 0;
-  const size_t L = f->host.n_sites;
-  // the device copies of the per-row outputs bound the batch
-  const size_t per = sizeof(double) * L * ((o.marg ? (size_t)P * 4 : 0) + (o.rate_post ? R : 0) + (o.site_base ? 5 : 0));
-  const size_t most = per ? ((size_t)lh::debug_options().anc_out_mb << 20) / per : (size_t)INT32_MAX;
-  if ((size_t)n > most)
-    return fail(W + ": batch too large for the device copies of its per-row outputs: at most " + std::to_string(most) +
-                " samples per call for this family and path length");
-  for (size_t i = 0; i < (size_t)n; ++i)
-    if (valid_schedule(host.schedule(i), T, (int)host.nodes(), max_depth) && !valid_chain(host.schedule(i), T, path + i * P, P))
-      return fail(W + ": path of sample " + std::to_string(i) +
-                  " is not a chain of inner nodes, each the child of the next, that ends at the root (padding after it)");
-  AncestralWs& a = f->anc;
-  HostOutputs& out = f->out;
-  lh_ancestral_outputs d{};
-  TreeBatch dev;
-  if (out.loglik.ensure(sizeof(double) * n) || out_buf(o.site_base, a.site_base, sizeof(double) * L * 5 * n, &d.site_base) ||
-      out_buf(o.marg, a.marg, sizeof(double) * P * L * 4 * n, &d.marg) ||
-      out_buf(o.rate_post, a.rate_post, sizeof(double) * L * R * n, &d.rate_post) ||
-      out_buf(o.weighted_sum, a.out_wsum, sizeof(double) * 2 * L * 4, &d.weighted_sum) ||
-      out_buf(o.weighted_rate, a.out_wrate, sizeof(double) * L * R, &d.weighted_rate) ||
-      out_buf(o.weight_stats, out.weight_stats, sizeof(double) * 3, &d.weight_stats) ||
-      stage_batch(f, host, {{o.log_offset, sizeof(double) * n, &f->in.log_offset}, {path, sizeof(int32_t) * P * n, &a.path}}, &dev))
-    return 1;
-  d.log_offset = o.log_offset ? f->in.log_offset.get<const double>() : nullptr;
-  d.loglik = out.loglik.get<double>();
-  if (lh_eval_ancestral_batch_device(f, n, T, max_depth, dev.ops, dev.brlen, dev.er, dev.pi, dev.model, R, a.path.get<const int32_t>(), P,
-                                     &d, nullptr))
-    return 1;
-  return finish_batch(f, W.c_str(), host,
-                      {{o.loglik, d.loglik, sizeof(double) * n},
-                       {o.site_base, d.site_base, sizeof(double) * L * 5 * n},
-                       {o.marg, d.marg, sizeof(double) * P * L * 4 * n},
-                       {o.rate_post, d.rate_post, sizeof(double) * L * R * n},
-                       {o.weighted_sum, d.weighted_sum, sizeof(double) * 2 * L * 4},
-                       {o.weighted_rate, d.weighted_rate, sizeof(double) * L * R},
-                       {o.weight_stats, d.weight_stats, sizeof(double) * 3}});
-}
-
-int lh_ancestral_profile_read(lh_family* f, double* ms, int64_t* n_launches) {
-  return profile_read(f, &lh_family::anc_timer, ms, n_launches);
-}
-
-}  // extern "C"
-
-namespace {
-
 int edges_check(const lh_family* f, const std::string& W, const TreeBatch& b, int P, int seed_tip) {
   if (ancestral_check(f, W, b, P)) return 1;
   if (seed_tip < 1 || seed_tip > b.T - 1) return fail(W + ": seed_tip must be a tip other than naive, 1 .. n_tips - 1");
@@ -2393,11 +2167,388 @@ int edges_workspace(lh_family* f, int chunk, int T, int R, int P, bool own_rho, 
   return 0;
 }
 
-bool edges_wanted(const lh_edges_outputs& o) { return o.edge || o.naive_edge || o.chain_counts || o.edge_load || o.rate_post; }
+// ---- the skeleton under K11's and K12's entry points: tables per row along a seed's lineage and their weighted sums ----
+
+// One per-row output of an entry point.  Each family states its outputs once (ancestral_rows, edges_rows); every size,
+// offset, buffer and copy below is read from there.
+struct RowOut {
+  double* p;         // the caller's array (null: not taken)
+  size_t width;      // doubles per row
+  DevBuf* copy;      // the host-pointer form's device copy (null: no caller takes it)
+  DevBuf* fallback;  // the device form's array when the caller does not take it (null: formed only for the caller)
+  bool need = false;      // formed although not taken: another member is made from it
+  double* sum = nullptr;  // the caller's weighted sum over the rows (null: none), its slab partials, its host-form copy
+  DevBuf *partial = nullptr, *sum_copy = nullptr;
+  double* slabs = nullptr;
+  size_t step = width;  // doubles from one launch group's rows to the next (0: the array holds one group)
+  bool wanted() const { return p || sum || need; }
+  size_t bytes(size_t rows) const { return sizeof(double) * width * rows; }
+  double* group(size_t off) const { return p ? p + off * step : nullptr; }
+  // The device form's arrays: what the caller does not take lives per launch group or, where the reduction reads it, per
+  // batch.
+  int settle(size_t n, size_t chunk, size_t n_slabs) {
+    if (!p) step = sum ? width : 0;
+    return (!p && own(p, *fallback, bytes(sum ? n : chunk))) || (sum && own(slabs, *partial, bytes(n_slabs)));
+  }
+  // The host-pointer form's: *d is this member over the handle's device copies, `rows` rows of it
+  int stage(size_t rows, RowOut* d) const {
+    *d = *this;
+    d->p = d->sum = nullptr;
+    return (p && out_buf(p, *copy, bytes(rows), &d->p)) || (sum && out_buf(sum, *sum_copy, bytes(1), &d->sum));
+  }
+};
+
+// An entry point's arguments beside its batch of trees
+struct LineageCall {
+  const double* naive_prob;  // the asr forms' input, a row of rows[kSiteBase].width (null: an eval form makes it, K11a)
+  const int32_t* path;
+  int P, seed_tip;  // seed_tip 0: K11
+  std::vector<RowOut> rows;
+  const double* log_offset = nullptr;  // the eval forms' (lh_posterior_outputs' members)
+  double *loglik = nullptr, *weight_stats = nullptr;
+  bool asked() const {
+    return loglik || weight_stats || std::any_of(rows.begin(), rows.end(), [](const RowOut& r) { return r.p || r.sum; });
+  }
+  // bytes per sample of the host-pointer form's device copies: of what it takes, or (all) of whatever a caller can take
+  size_t copy_bytes(bool all) const {
+    size_t per = 0;
+    for (const RowOut& r : rows) per += (all ? r.copy != nullptr : r.p != nullptr) ? r.bytes(1) : 0;
+    return per;
+  }
+};
+enum { kSiteBase = 0 };  // K11a's output leads both families' rows
+
+// the device copies of the per-row outputs bound the batch
+int refuse_oversize(const std::string& W, size_t n, const LineageCall& c, int out_mb) {
+  const size_t per = c.copy_bytes(false);
+  const size_t most = per ? ((size_t)out_mb << 20) / per : (size_t)INT32_MAX;
+  if (n > most)
+    return fail(W + ": batch too large for the device copies of its per-row outputs: at most " + std::to_string(most) +
+                " samples per call for this family and path length");
+  return 0;
+}
+
+// The asr _device forms behind their argument checks and their kernel's scratch: per launch group of `chunk` samples K0a's
+// eigensystems, one unmixed K1 and launch(group, first sample, rates, naive_prob, scratch, stream), K11b or K12b.
+template <class Launch>
+int lineage_asr_device(lh_family* f, const std::string& W, const TreeBatch& b, const LineageCall& c, int chunk, const lh::AncWs& ws,
+                       KernelTimer<3> lh_family::*timer, void* hip_stream, Launch&& launch) {
+  hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+  KernelTimer<3>& t = f->*timer;
+  for (int off = 0; off < b.n; off += chunk) {
+    const TreeBatch g = b.slice(off, std::min(chunk, b.n - off));
+    lh::launch_gtr_setup(g.n, g.er, g.pi, f->ws.eig.get<double>(), stream);
+    int planes = 0;
+    if (prune_group(f, W, g, g.model, false, stream, &planes)) return 1;
+    if (f->profile && (t.begin(stream) || t.mark(1, stream))) return 1;
+    if (launch(g, off, g.model, c.naive_prob + (size_t)off * c.rows[kSiteBase].width, ws, stream)) return fail(W + ": launch failed");
+    if (f->profile && (t.mark(2, stream) || t.end(stream))) return 1;
+    LH_HIP(hipGetLastError());
+  }
+  return 0;
+}
+
+// The eval _device forms behind theirs: per launch group K0, one unmixed K1 that serves K2 and the kernel (its planes
+// outlive K2), K2 forward, K5, K11a and `launch` as above on K11a's output; then K11c's `ends` where the kernel looked at
+// the paths (`checked`), from c.rows[marg] into c.rows[ends] where the family has them (-1: it only settles the weights);
+// behind the last group the weights and the slabs of every member with a sum.
+template <class Launch>
+int lineage_eval_device(lh_family* f, const std::string& W, const TreeBatch& b, LineageCall& c, int chunk, lh::AncWs ws,
+                        KernelTimer<3> lh_family::*timer, bool checked, int marg, int ends, void* hip_stream, Launch&& launch) {
+  hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+  KernelTimer<3>& t = f->*timer;
+  const int n = b.n, P = c.P, R = b.R;
+  const size_t L = f->host.n_sites, FS = f->host.forward_size, n_slabs = lh::posterior_slabs(n);
+  AncestralWs& a = f->anc;
+  RowOut& site_base = c.rows[kSiteBase];
+  site_base.need = true;
+  const bool run = std::any_of(c.rows.begin() + 1, c.rows.end(), [](const RowOut& r) { return r.wanted(); });
+  const bool reduce = c.weight_stats || std::any_of(c.rows.begin(), c.rows.end(), [](const RowOut& r) { return r.sum != nullptr; });
+  double* ll = c.loglik;
+  WeightReduce wr;
+  if (a.plen.ensure(sizeof(int32_t) * n) || a.rates.ensure(sizeof(double) * R * chunk) ||
+      f->forward_dev.ensure(sizeof(double) * FS * n) || own(ll, a.loglik, sizeof(double) * n) ||
+      (reduce && (a.ll_used.ensure(sizeof(double) * n) || wr.prepare(n, a.weights, a.stats, c.weight_stats))))
+    return 1;
+  for (RowOut& r : c.rows)
+    if (r.wanted() && r.settle(n, chunk, n_slabs)) return 1;
+  ws.plen = a.plen.get<int32_t>();  // (the batch's, for the reduction; a.plen.ensure above may have moved it)
+  Workspace& w = f->ws;
+  double *eig = w.eig.get<double>(), *site_lik = w.site_lik.get<double>(), *fwd = f->forward_dev.get<double>();
+  double* rates = a.rates.get<double>();
+  int32_t* site_scal = w.site_scal.get<int32_t>();
+  const lh_eval_outputs fwd_outs{nullptr, nullptr, fwd, nullptr};
+  for (int off = 0; off < n; off += chunk) {
+    const int m = std::min(chunk, n - off);
+    const TreeBatch g = b.slice(off, m);
+    lh::launch_model_setup(m, R, g.er, g.pi, g.model, rates, eig, stream);
+    int planes = 0;
+    if (prune_group(f, W, g, rates, false, stream, &planes)) return 1;
+    if (run_forward(f, m, planes, site_lik, site_scal, g.pi, nullptr, nullptr, ll + off, &fwd_outs, off, stream)) return 1;
+    lh::launch_posterior(f->sampler_dev, m, fwd + (size_t)off * FS, FS, ll + off, stream);
+    if (f->profile && t.begin(stream)) return 1;
+    lh::launch_site_base(m, (int)L, FS, a.sb_off.get<const int32_t>(), a.sb_idx.get<const int32_t>(), fwd + (size_t)off * FS,
+                         ll + off, site_base.group(off), stream);
+    if (f->profile && t.mark(1, stream)) return 1;
+    lh::AncWs wg = ws;
+    wg.plen = ws.plen + off;
+    if (run && launch(g, off, rates, site_base.group(off), wg, stream)) return fail(W + ": launch failed");
+    // the paths were checked wherever the kernel formed a table: a row without one then gets no weight
+    if (reduce && checked)
+      lh::launch_ancestral_ends(m, P, (int)L, wg.plen, marg < 0 ? nullptr : c.rows[marg].group(off), ll + off,
+                                ends < 0 ? nullptr : c.rows[ends].group(off), a.ll_used.get<double>() + off, stream);
+    if (f->profile && t.mark(2, stream)) return 1;
+    if (reduce && off + m == n) {
+      // (where no path was looked at, the weights are the rows' own)
+      wr.launch(n, checked ? a.ll_used.get<const double>() : ll, c.log_offset, stream);
+      for (const RowOut& r : c.rows)
+        if (r.sum) lh::launch_weighted_slabs(n, r.width, r.p, wr.w, r.slabs, r.sum, stream);
+    }
+    if (f->profile && t.end(stream)) return 1;
+    LH_HIP(hipGetLastError());
+  }
+  return 0;
+}
+
+// The host-pointer form W behind its argument checks and output bound: the paths validated, then per sub-batch of `sub`
+// samples the arrays staged, device(batch, call), its _device form's body on the handle's device copies, and the copy
+// back.  A batch that is evaluated (alpha, not rates) has K0c check its schedules beside the host: finish_batch reads the
+// verdict, and a row with a malformed schedule has no chain to check here.
+template <class Device>
+int lineage_batch(lh_family* f, const std::string& W, const TreeBatch& host, const LineageCall& c, size_t sub, Device&& device) {
+  const bool evaluated = !host.per_rate;
+  const int n = host.n, P = c.P;
+  if (!evaluated && !valid_schedules(host)) return fail(W + ": malformed schedule op (use lh_schedule_tree)");
+  for (size_t i = 0; i < (size_t)n; ++i) {
+    if (evaluated && !valid_schedule(host.schedule(i), host.T, (int)host.nodes(), host.max_depth)) continue;
+    const ChainFault bad = chain_fault(host.schedule(i), host.T, c.path + i * P, P, c.seed_tip);
+    if (bad == kNotChain)
+      return fail(W + ": path of sample " + std::to_string(i) +
+                  " is not a chain of inner nodes, each the child of the next, that ends at the root (padding after it)");
+    if (bad == kNotChild)
+      return fail(W + ": seed_tip " + std::to_string(c.seed_tip) + " is not a child of path[0] of sample " + std::to_string(i));
+  }
+  AncestralWs& a = f->anc;
+  HostOutputs& out = f->out;
+  const size_t NP = c.rows[kSiteBase].width;
+  for (size_t off = 0; off < (size_t)n; off += sub) {
+    const size_t m = std::min(sub, n - off);
+    LineageCall d = c;
+    TreeBatch dev;
+    std::vector<HostOut> back;
+    if (evaluated && out.loglik.ensure(sizeof(double) * m)) return 1;
+    d.loglik = evaluated ? out.loglik.get<double>() : nullptr;
+    back.push_back({c.loglik ? c.loglik + off : nullptr, d.loglik, sizeof(double) * m});
+    for (size_t k = 0; k < c.rows.size(); ++k) {
+      const RowOut& h = c.rows[k];
+      if (h.stage(m, &d.rows[k])) return 1;
+      back.push_back({h.group(off), d.rows[k].p, h.bytes(m)});
+      back.push_back({h.sum, d.rows[k].sum, h.bytes(1)});
+    }
+    if (out_buf(c.weight_stats, out.weight_stats, sizeof(double) * 3, &d.weight_stats) ||
+        stage_batch(f, host.slice((int)off, (int)m),
+                    {{c.naive_prob ? c.naive_prob + off * NP : nullptr, sizeof(double) * NP * m, &a.naive_prob},
+                     {c.log_offset ? c.log_offset + off : nullptr, sizeof(double) * m, &f->in.log_offset},
+                     {c.path + off * P, sizeof(int32_t) * P * m, &a.path}},
+                    &dev))
+      return 1;
+    back.push_back({c.weight_stats, d.weight_stats, sizeof(double) * 3});
+    d.naive_prob = c.naive_prob ? a.naive_prob.get<const double>() : nullptr;
+    d.log_offset = c.log_offset ? f->in.log_offset.get<const double>() : nullptr;
+    d.path = a.path.get<const int32_t>();
+    if (device(dev, d)) return 1;
+    if (evaluated ? finish_batch(f, W.c_str(), host.slice((int)off, (int)m), back) : copy_back(f, W.c_str(), back)) return 1;
+  }
+  return 0;
+}
+
+// ---- K11: exact ancestral-state marginals along a seed's lineage (lh_ancestral.hip) ----
+
+// K11's per-row outputs; `ends` are the two slots of marg that mean the same in every tree, which weighted_sum sums
+enum { kMarg = 1, kEnds, kRatePost };
+std::vector<RowOut> ancestral_rows(lh_family* f, int P, int R, double* site_base, double* marg, double* rate_post,
+                                   double* weighted_sum, double* weighted_rate) {
+  AncestralWs& a = f->anc;
+  const size_t L = f->host.n_sites;
+  return {{site_base, L * 5, &a.site_base, &a.site_base},
+          {marg, (size_t)P * L * 4, &a.marg, &a.marg, weighted_sum != nullptr},
+          {nullptr, 2 * L * 4, nullptr, &a.ends, false, weighted_sum, &a.partial_e, &a.out_wsum},
+          {rate_post, L * R, &a.rate_post, &a.rate_post, false, weighted_rate, &a.partial_r, &a.out_wrate}};
+}
+
+// K11b on a launch group, as both skeletons call it
+auto ancestral_launch(lh_family* f, const LineageCall& c) {
+  return [f, &c](const TreeBatch& g, size_t off, const double* rates, const double* naive_prob, const lh::AncWs& ws, hipStream_t stream) {
+    Workspace& w = f->ws;
+    return lh::launch_ancestral(f->host, g.n, g.R, g.T, g.ops, g.brlen, rates, w.eig.get<double>(), g.pi, w.site_lik.get<double>(),
+                                w.site_scal.get<int32_t>(), naive_prob, c.path + off * c.P, c.P, ws, c.rows[kMarg].group(off),
+                                c.rows[kRatePost].group(off), w.prune.hdr, f->err_flag, stream);
+  };
+}
+
+int asr_marginals_device(lh_family* f, const std::string& W, const TreeBatch& b, const LineageCall& c, void* hip_stream) {
+  const int chunk = (int)std::min<size_t>(b.n, ancestral_group(f, b.T, b.R, c.P));
+  lh::AncWs ws;
+  if (ensure_workspace(f, chunk, b.R, b.T) || ancestral_workspace(f, chunk, b.T, b.R, c.P, !c.rows[kRatePost].p, &ws)) return 1;
+  return lineage_asr_device(f, W, b, c, chunk, ws, &lh_family::anc_timer, hip_stream, ancestral_launch(f, c));
+}
+
+int eval_ancestral_device(lh_family* f, const std::string& W, const TreeBatch& b, LineageCall& c, void* hip_stream) {
+  if (ancestral_table(f, W)) return 1;
+  const int chunk = (int)std::min<size_t>(b.n, std::min(ancestral_group(f, b.T, b.R, c.P), eval_group(f, b.T, b.R)));
+  lh::AncWs ws;
+  if (ensure_workspace(f, chunk, b.R, b.T) || ancestral_workspace(f, chunk, b.T, b.R, c.P, !c.rows[kRatePost].wanted(), &ws))
+    return 1;
+  // (without marg or weighted_sum no path is looked at)
+  return lineage_eval_device(f, W, b, c, chunk, ws, &lh_family::anc_timer, c.rows[kMarg].wanted(), kMarg, kEnds, hip_stream,
+                             ancestral_launch(f, c));
+}
+
+LineageCall ancestral_call(lh_family* f, int P, int R, const int32_t* path, const lh_ancestral_outputs* outs) {
+  const lh_ancestral_outputs o = outs ? *outs : lh_ancestral_outputs{};
+  return {nullptr, path, P, 0, ancestral_rows(f, P, R, o.site_base, o.marg, o.rate_post, o.weighted_sum, o.weighted_rate),
+          o.log_offset, o.loglik, o.weight_stats};
+}
+
+// ---- K12: exact substitution posteriors along the edges of a seed's lineage (lh_substitutions.hip) ----
+
+// K12's per-row outputs (lh_edges_outputs has no seed_edge and no sums)
+enum { kEdge = 1, kChainCounts, kSeedEdge, kNaiveEdge, kEdgeLoad, kEdgeRatePost };
+std::vector<RowOut> edges_rows(lh_family* f, int P, int R, const lh_eval_edges_outputs& o) {
+  AncestralWs& a = f->anc;
+  EdgesWs& e = f->edges;
+  const size_t L = f->host.n_sites;
+  return {{o.site_base, L * 5, &a.site_base, &a.site_base},
+          {o.edge, (size_t)P * L * 16, &e.out_edge, nullptr},
+          {o.chain_counts, L * 16, &e.out_cc, &e.out_cc, false, o.weighted_counts, &e.partial_c, &e.out_wcc},
+          {o.seed_edge, L * 16, &e.out_se, &e.out_se, false, o.weighted_seed_edge, &e.partial_s, &e.out_wse},
+          {o.naive_edge, L * 20, &e.out_ne, &e.out_ne, false, o.weighted_naive_edge, &e.partial_n, &e.out_wne},
+          {o.edge_load, (size_t)P + 1, &e.out_el, nullptr},
+          {o.rate_post, L * R, &a.rate_post, nullptr}};
+}
+
+// K12b on a launch group, as both skeletons call it
+auto edges_launch(lh_family* f, const LineageCall& c, const lh::SubWs& sws) {
+  return [f, &c, sws](const TreeBatch& g, size_t off, const double* rates, const double* naive_prob, const lh::AncWs& ws, hipStream_t stream) {
+    Workspace& w = f->ws;
+    const std::vector<RowOut>& r = c.rows;
+    const lh::SubOut so{r[kEdge].group(off),     r[kNaiveEdge].group(off), r[kChainCounts].group(off),
+                        r[kSeedEdge].group(off), r[kEdgeLoad].group(off),  r[kEdgeRatePost].group(off)};
+    return lh::launch_substitutions(f->host, g.n, g.R, g.T, g.ops, g.brlen, rates, w.eig.get<double>(), g.pi, w.site_lik.get<double>(),
+                                    w.site_scal.get<int32_t>(), naive_prob, c.path + off * c.P, c.P, c.seed_tip, ws, sws, so,
+                                    w.prune.hdr, f->err_flag, stream);
+  };
+}
+
+int asr_edges_device(lh_family* f, const std::string& W, const TreeBatch& b, const LineageCall& c, void* hip_stream) {
+  const bool with_edge = c.rows[kEdge].p != nullptr;
+  const int chunk = (int)std::min<size_t>(b.n, edges_group(f, b.T, b.R, c.P, with_edge));
+  lh::AncWs ws;
+  lh::SubWs sws;
+  if (ensure_workspace(f, chunk, b.R, b.T) ||
+      edges_workspace(f, chunk, b.T, b.R, c.P, !c.rows[kEdgeRatePost].p, with_edge, false, &ws, &sws))
+    return 1;
+  return lineage_asr_device(f, W, b, c, chunk, ws, &lh_family::edges_timer, hip_stream, edges_launch(f, c, sws));
+}
+
+int eval_edges_device(lh_family* f, const std::string& W, const TreeBatch& b, LineageCall& c, void* hip_stream) {
+  if (ancestral_table(f, W)) return 1;
+  const bool with_edge = c.rows[kEdge].p != nullptr;
+  const int chunk = (int)std::min<size_t>(b.n, std::min(edges_group(f, b.T, b.R, c.P, with_edge), eval_group(f, b.T, b.R)));
+  lh::AncWs ws;
+  lh::SubWs sws;
+  if (ensure_workspace(f, chunk, b.R, b.T) ||
+      edges_workspace(f, chunk, b.T, b.R, c.P, !c.rows[kEdgeRatePost].p, with_edge, c.rows[kSeedEdge].wanted(), &ws, &sws))
+    return 1;
+  // K12c checks the paths wherever a table is formed; rate_post alone forms none
+  const bool tables = std::any_of(c.rows.begin() + kEdge, c.rows.begin() + kEdgeRatePost, [](const RowOut& r) { return r.wanted(); });
+  return lineage_eval_device(f, W, b, c, chunk, ws, &lh_family::edges_timer, tables, -1, -1, hip_stream, edges_launch(f, c, sws));
+}
+
+LineageCall edges_call(lh_family* f, int P, int R, const double* naive_prob, const int32_t* path, int seed_tip,
+                       const lh_eval_edges_outputs& o) {
+  return {naive_prob, path, P, seed_tip, edges_rows(f, P, R, o), o.log_offset, o.loglik, o.weight_stats};
+}
+LineageCall edges_call(lh_family* f, int P, int R, const double* naive_prob, const int32_t* path, int seed_tip,
+                       const lh_edges_outputs* outs) {
+  lh_eval_edges_outputs o{};
+  if (outs) {
+    o.edge = outs->edge;
+    o.naive_edge = outs->naive_edge;
+    o.chain_counts = outs->chain_counts;
+    o.edge_load = outs->edge_load;
+    o.rate_post = outs->rate_post;
+  }
+  return edges_call(f, P, R, naive_prob, path, seed_tip, o);
+}
 
 }  // namespace
 
 extern "C" {
+
+int lh_asr_marginals_batch_device(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops,
+                                  const double* brlen, const double* er, const double* pi, const double* rates, int32_t R,
+                                  const double* naive_prob, const int32_t* path, int32_t P, double* marg, double* rate_post,
+                                  void* hip_stream) {
+  const TreeBatch b{n, T, max_depth, ops, brlen, er, pi, rates, R, true};
+  const std::string W = "lh_asr_marginals_batch";
+  if (int rc = check_batch(f, W, b)) return rc > 0;
+  if (ancestral_check(f, W, b, P)) return 1;
+  DeviceGuard guard(f);
+  if (!b.has_arrays() || !naive_prob || !path) return fail(W + ": null array");
+  const LineageCall c{naive_prob, path, P, 0, ancestral_rows(f, P, R, nullptr, marg, rate_post, nullptr, nullptr)};
+  if (!c.asked()) return 0;  // nothing asked for
+  return asr_marginals_device(f, W, b, c, hip_stream);
+}
+
+int lh_asr_marginals_batch(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops, const double* brlen,
+                           const double* er, const double* pi, const double* rates, int32_t R, const double* naive_prob,
+                           const int32_t* path, int32_t P, double* marg, double* rate_post) {
+  const TreeBatch host{n, T, max_depth, ops, brlen, er, pi, rates, R, true};
+  const std::string W = "lh_asr_marginals_batch";
+  if (int rc = check_batch(f, W, host)) return rc > 0;
+  if (ancestral_check(f, W, host, P)) return 1;
+  DeviceGuard guard(f);
+  if (!host.has_arrays() || !naive_prob || !path) return fail(W + ": null array");
+  const LineageCall c{naive_prob, path, P, 0, ancestral_rows(f, P, R, nullptr, marg, rate_post, nullptr, nullptr)};
+  if (!c.asked()) return 0;
+  // no refusal here: sub-batches bound the device copies of the inputs and outputs (marg: 32 P L bytes per sample)
+  const size_t sub = std::max<size_t>(1, std::min<size_t>(n, ((size_t)1 << 30) / c.copy_bytes(true)));
+  return lineage_batch(f, W, host, c, sub,
+                       [&](const TreeBatch& dev, const LineageCall& d) { return asr_marginals_device(f, W, dev, d, nullptr); });
+}
+
+int lh_eval_ancestral_batch_device(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops,
+                                   const double* brlen, const double* er, const double* pi, const double* alpha, int32_t R,
+                                   const int32_t* path, int32_t P, const lh_ancestral_outputs* outs, void* hip_stream) {
+  const TreeBatch b{n, T, max_depth, ops, brlen, er, pi, alpha, R};
+  const std::string W = "lh_eval_ancestral_batch";
+  if (int rc = check_batch(f, W, b, true)) return rc > 0;
+  if (ancestral_check(f, W, b, P)) return 1;
+  DeviceGuard guard(f);
+  if (!b.has_arrays() || !path) return fail(W + ": null array");
+  LineageCall c = ancestral_call(f, P, R, path, outs);
+  return eval_ancestral_device(f, W, b, c, hip_stream);
+}
+
+int lh_eval_ancestral_batch(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops, const double* brlen,
+                            const double* er, const double* pi, const double* alpha, int32_t R, const int32_t* path, int32_t P,
+                            const lh_ancestral_outputs* outs) {
+  const TreeBatch host{n, T, max_depth, ops, brlen, er, pi, alpha, R};
+  const std::string W = "lh_eval_ancestral_batch";
+  if (int rc = check_batch(f, W, host, true)) return rc > 0;
+  if (ancestral_check(f, W, host, P)) return 1;
+  DeviceGuard guard(f);
+  if (!host.has_arrays() || !path) return fail(W + ": null array");
+  const LineageCall c = ancestral_call(f, P, R, path, outs);
+  if (!c.asked()) return 0;
+  if (refuse_oversize(W, n, c, lh::debug_options().anc_out_mb)) return 1;
+  return lineage_batch(f, W, host, c, n, [&](const TreeBatch& dev, LineageCall d) { return eval_ancestral_device(f, W, dev, d, nullptr); });
+}
+
+int lh_ancestral_profile_read(lh_family* f, double* ms, int64_t* n_launches) {
+  return profile_read(f, &lh_family::anc_timer, ms, n_launches);
+}
 
 int lh_asr_edges_batch_device(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops, const double* brlen,
                               const double* er, const double* pi, const double* rates, int32_t R, const double* naive_prob,
@@ -2408,37 +2559,9 @@ int lh_asr_edges_batch_device(lh_family* f, int32_t n, int32_t T, int32_t max_de
   if (edges_check(f, W, b, P, seed_tip)) return 1;
   DeviceGuard guard(f);
   if (!b.has_arrays() || !naive_prob || !path) return fail(W + ": null array");
-  if (!outs || !edges_wanted(*outs)) return 0;  // nothing asked for
-  const lh_edges_outputs& o = *outs;
-  hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-  const size_t L = f->host.n_sites;
-  const int chunk = (int)std::min<size_t>(n, edges_group(f, T, R, P, o.edge != nullptr));
-  lh::AncWs ws;
-  lh::SubWs sws;
-  if (ensure_workspace(f, chunk, R, T) || edges_workspace(f, chunk, T, R, P, !o.rate_post, o.edge != nullptr, false, &ws, &sws))
-    return 1;
-  Workspace& w = f->ws;
-  double *eig = w.eig.get<double>(), *site_lik = w.site_lik.get<double>();
-  int32_t* site_scal = w.site_scal.get<int32_t>();
-  auto at = [](double* p, size_t off) { return p ? p + off : nullptr; };
-  for (int off = 0; off < n; off += chunk) {
-    const int m = std::min(chunk, n - off);
-    const TreeBatch g = b.slice(off, m);
-    lh::launch_gtr_setup(m, g.er, g.pi, eig, stream);
-    int planes = 0;
-    if (prune_group(f, W, g, g.model, false, stream, &planes)) return 1;
-    if (f->profile && (f->edges_timer.begin(stream) || f->edges_timer.mark(1, stream))) return 1;
-    const lh::SubOut so{at(o.edge, (size_t)off * P * L * 16), at(o.naive_edge, (size_t)off * L * 20),
-                        at(o.chain_counts, (size_t)off * L * 16), nullptr, at(o.edge_load, (size_t)off * (P + 1)),
-                        at(o.rate_post, (size_t)off * L * R)};
-    if (lh::launch_substitutions(f->host, m, R, T, g.ops, g.brlen, g.model, eig, g.pi, site_lik, site_scal,
-                                 naive_prob + (size_t)off * L * 5, path + (size_t)off * P, P, seed_tip, ws, sws, so, w.prune.hdr,
-                                 f->err_flag, stream))
-      return fail(W + ": launch failed");
-    if (f->profile && (f->edges_timer.mark(2, stream) || f->edges_timer.end(stream))) return 1;
-    LH_HIP(hipGetLastError());
-  }
-  return 0;
+  const LineageCall c = edges_call(f, P, R, naive_prob, path, seed_tip, outs);
+  if (!c.asked()) return 0;  // nothing asked for
+  return asr_edges_device(f, W, b, c, hip_stream);
 }
 
 int lh_asr_edges_batch(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops, const double* brlen,
@@ -2450,44 +2573,10 @@ int lh_asr_edges_batch(lh_family* f, int32_t n, int32_t T, int32_t max_depth, co
   if (edges_check(f, W, host, P, seed_tip)) return 1;
   DeviceGuard guard(f);
   if (!host.has_arrays() || !naive_prob || !path) return fail(W + ": null array");
-  if (!outs || !edges_wanted(*outs)) return 0;
-  const lh_edges_outputs& o = *outs;
-  const size_t L = f->host.n_sites;
-  // the device copies of the per-row outputs bound the batch (K11's rule)
-  const size_t per = sizeof(double) * ((o.edge ? (size_t)P * L * 16 : 0) + (o.naive_edge ? L * 20 : 0) + (o.chain_counts ? L * 16 : 0) +
-                                       (o.edge_load ? (size_t)P + 1 : 0) + (o.rate_post ? L * R : 0));
-  const size_t most = per ? ((size_t)lh::debug_options().edge_out_mb << 20) / per : (size_t)INT32_MAX;
-  if ((size_t)n > most)
-    return fail(W + ": batch too large for the device copies of its per-row outputs: at most " + std::to_string(most) +
-                " samples per call for this family and path length");
-  if (!valid_schedules(host)) return fail(W + ": malformed schedule op (use lh_schedule_tree)");
-  for (size_t i = 0; i < (size_t)n; ++i) {
-    if (!valid_chain(host.schedule(i), T, path + i * P, P))
-      return fail(W + ": path of sample " + std::to_string(i) +
-                  " is not a chain of inner nodes, each the child of the next, that ends at the root (padding after it)");
-    if (!valid_chain(host.schedule(i), T, path + i * P, P, seed_tip))
-      return fail(W + ": seed_tip " + std::to_string(seed_tip) + " is not a child of path[0] of sample " + std::to_string(i));
-  }
-  AncestralWs& a = f->anc;
-  EdgesWs& e = f->edges;
-  lh_edges_outputs d{};
-  TreeBatch dev;
-  const size_t edge_b = sizeof(double) * P * L * 16 * n, ne_b = sizeof(double) * L * 20 * n, cc_b = sizeof(double) * L * 16 * n,
-               el_b = sizeof(double) * ((size_t)P + 1) * n, rp_b = sizeof(double) * L * R * n;
-  if (out_buf(o.edge, e.out_edge, edge_b, &d.edge) || out_buf(o.naive_edge, e.out_ne, ne_b, &d.naive_edge) ||
-      out_buf(o.chain_counts, e.out_cc, cc_b, &d.chain_counts) || out_buf(o.edge_load, e.out_el, el_b, &d.edge_load) ||
-      out_buf(o.rate_post, a.rate_post, rp_b, &d.rate_post) ||
-      stage_batch(f, host, {{naive_prob, sizeof(double) * L * 5 * n, &a.naive_prob}, {path, sizeof(int32_t) * P * n, &a.path}}, &dev))
-    return 1;
-  if (lh_asr_edges_batch_device(f, n, T, max_depth, dev.ops, dev.brlen, dev.er, dev.pi, dev.model, R, a.naive_prob.get<const double>(),
-                                a.path.get<const int32_t>(), P, seed_tip, &d, nullptr))
-    return 1;
-  return copy_back(f, W.c_str(),
-                   {{o.edge, d.edge, edge_b},
-                    {o.naive_edge, d.naive_edge, ne_b},
-                    {o.chain_counts, d.chain_counts, cc_b},
-                    {o.edge_load, d.edge_load, el_b},
-                    {o.rate_post, d.rate_post, rp_b}});
+  const LineageCall c = edges_call(f, P, R, naive_prob, path, seed_tip, outs);
+  if (!c.asked()) return 0;
+  if (refuse_oversize(W, n, c, lh::debug_options().edge_out_mb)) return 1;  // (K11's rule)
+  return lineage_batch(f, W, host, c, n, [&](const TreeBatch& dev, const LineageCall& d) { return asr_edges_device(f, W, dev, d, nullptr); });
 }
 
 int lh_eval_edges_batch_device(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops, const double* brlen,
@@ -2499,82 +2588,8 @@ int lh_eval_edges_batch_device(lh_family* f, int32_t n, int32_t T, int32_t max_d
   if (edges_check(f, W, b, P, seed_tip)) return 1;
   DeviceGuard guard(f);
   if (!b.has_arrays() || !path) return fail(W + ": null array");
-  const lh_eval_edges_outputs none{};
-  const lh_eval_edges_outputs& o = outs ? *outs : none;
-  if (ancestral_table(f, W)) return 1;
-  hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-  const size_t L = f->host.n_sites, FS = f->host.forward_size;
-  const bool with_edge = o.edge != nullptr;
-  const int chunk = (int)std::min<size_t>(n, std::min(edges_group(f, T, R, P, with_edge), eval_group(f, T, R)));
-  AncestralWs& a = f->anc;
-  EdgesWs& e = f->edges;
-  const bool reduce = o.weighted_counts || o.weighted_seed_edge || o.weighted_naive_edge || o.weight_stats;
-  // the reduction reads its rows of the whole batch; what the caller does not take then lives on the handle
-  const bool want_cc = o.chain_counts || o.weighted_counts, want_se = o.seed_edge || o.weighted_seed_edge,
-             want_ne = o.naive_edge || o.weighted_naive_edge;
-  const bool tables = with_edge || want_cc || want_se || want_ne || o.edge_load;
-  const size_t slabs = lh::posterior_slabs(n);
-  lh::AncWs ws;
-  lh::SubWs sws;
-  double *ll = o.loglik, *sb = o.site_base, *cc = o.chain_counts, *se = o.seed_edge, *ne = o.naive_edge;
-  double *pc = nullptr, *ps = nullptr, *pn = nullptr;
-  WeightReduce wr;
-  const size_t sb_rows = o.site_base ? 0 : chunk;
-  if (ensure_workspace(f, chunk, R, T) || edges_workspace(f, chunk, T, R, P, !o.rate_post, with_edge, want_se, &ws, &sws) ||
-      a.plen.ensure(sizeof(int32_t) * n) || a.rates.ensure(sizeof(double) * R * chunk) ||
-      f->forward_dev.ensure(sizeof(double) * FS * n) || own(ll, a.loglik, sizeof(double) * n) ||
-      own(sb, a.site_base, sizeof(double) * L * 5 * sb_rows) || (want_cc && own(cc, e.out_cc, sizeof(double) * L * 16 * n)) ||
-      (want_se && own(se, e.out_se, sizeof(double) * L * 16 * n)) || (want_ne && own(ne, e.out_ne, sizeof(double) * L * 20 * n)) ||
-      (reduce && (a.ll_used.ensure(sizeof(double) * n) || wr.prepare(n, a.weights, a.stats, o.weight_stats) ||
-                  (o.weighted_counts && own(pc, e.partial_c, sizeof(double) * L * 16 * slabs)) ||
-                  (o.weighted_seed_edge && own(ps, e.partial_s, sizeof(double) * L * 16 * slabs)) ||
-                  (o.weighted_naive_edge && own(pn, e.partial_n, sizeof(double) * L * 20 * slabs)))))
-    return 1;
-  ws.plen = a.plen.get<int32_t>();  // (the batch's, for the reduction; a.plen.ensure above may have moved it)
-  Workspace& w = f->ws;
-  double *eig = w.eig.get<double>(), *site_lik = w.site_lik.get<double>(), *fwd = f->forward_dev.get<double>();
-  double* rates = a.rates.get<double>();
-  int32_t* site_scal = w.site_scal.get<int32_t>();
-  const lh_eval_outputs fwd_outs{nullptr, nullptr, fwd, nullptr};
-  auto at = [](double* p, size_t off) { return p ? p + off : nullptr; };
-  for (int off = 0; off < n; off += chunk) {
-    const int m = std::min(chunk, n - off);
-    const TreeBatch g = b.slice(off, m);
-    lh::launch_model_setup(m, R, g.er, g.pi, g.model, rates, eig, stream);
-    int planes = 0;
-    // one unmixed K1 serves K2 and K12b: its planes outlive K2
-    if (prune_group(f, W, g, rates, false, stream, &planes)) return 1;
-    if (run_forward(f, m, planes, site_lik, site_scal, g.pi, nullptr, nullptr, ll + off, &fwd_outs, off, stream)) return 1;
-    lh::launch_posterior(f->sampler_dev, m, fwd + (size_t)off * FS, FS, ll + off, stream);
-    if (f->profile && f->edges_timer.begin(stream)) return 1;
-    double* sb_g = o.site_base ? sb + (size_t)off * L * 5 : sb;
-    lh::launch_site_base(m, (int)L, FS, a.sb_off.get<const int32_t>(), a.sb_idx.get<const int32_t>(), fwd + (size_t)off * FS,
-                         ll + off, sb_g, stream);
-    if (f->profile && f->edges_timer.mark(1, stream)) return 1;
-    lh::AncWs wg = ws;
-    wg.plen = ws.plen + off;
-    if (tables || o.rate_post) {
-      const lh::SubOut so{at(o.edge, (size_t)off * P * L * 16), want_ne ? ne + (size_t)off * L * 20 : nullptr,
-                          want_cc ? cc + (size_t)off * L * 16 : nullptr, want_se ? se + (size_t)off * L * 16 : nullptr,
-                          at(o.edge_load, (size_t)off * (P + 1)), at(o.rate_post, (size_t)off * L * R)};
-      if (lh::launch_substitutions(f->host, m, R, T, g.ops, g.brlen, rates, eig, g.pi, site_lik, site_scal, sb_g,
-                                   path + (size_t)off * P, P, seed_tip, wg, sws, so, w.prune.hdr, f->err_flag, stream))
-        return fail(W + ": launch failed");
-    }
-    // the paths were checked wherever a table was formed: a row without one then gets no weight
-    if (reduce && tables)
-      lh::launch_ancestral_ends(m, P, (int)L, wg.plen, nullptr, ll + off, nullptr, a.ll_used.get<double>() + off, stream);
-    if (f->profile && f->edges_timer.mark(2, stream)) return 1;
-    if (reduce && off + m == n) {
-      wr.launch(n, tables ? a.ll_used.get<const double>() : ll, o.log_offset, stream);
-      if (o.weighted_counts) lh::launch_weighted_slabs(n, L * 16, cc, wr.w, pc, o.weighted_counts, stream);
-      if (o.weighted_seed_edge) lh::launch_weighted_slabs(n, L * 16, se, wr.w, ps, o.weighted_seed_edge, stream);
-      if (o.weighted_naive_edge) lh::launch_weighted_slabs(n, L * 20, ne, wr.w, pn, o.weighted_naive_edge, stream);
-    }
-    if (f->profile && f->edges_timer.end(stream)) return 1;
-    LH_HIP(hipGetLastError());
-  }
-  return 0;
+  LineageCall c = edges_call(f, P, R, nullptr, path, seed_tip, outs ? *outs : lh_eval_edges_outputs{});
+  return eval_edges_device(f, W, b, c, hip_stream);
 }
 
 int lh_eval_edges_batch(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops, const double* brlen,
@@ -2586,63 +2601,10 @@ int lh_eval_edges_batch(lh_family* f, int32_t n, int32_t T, int32_t max_depth, c
   if (edges_check(f, W, host, P, seed_tip)) return 1;
   DeviceGuard guard(f);
   if (!host.has_arrays() || !path) return fail(W + ": null array");
-  const lh_eval_edges_outputs none{};
-  const lh_eval_edges_outputs& o = outs ? *outs : none;
-  if (!o.loglik && !o.site_base && !o.edge && !o.naive_edge && !o.chain_counts && !o.seed_edge && !o.edge_load && !o.rate_post &&
-      !o.weighted_counts && !o.weighted_seed_edge && !o.weighted_naive_edge && !o.weight_stats)
-    return 0;
-  const size_t L = f->host.n_sites;
-  // the device copies of the per-row outputs bound the batch (K11's rule)
-  const size_t per = sizeof(double) * ((o.edge ? (size_t)P * L * 16 : 0) + (o.naive_edge ? L * 20 : 0) + (o.chain_counts ? L * 16 : 0) +
-                                       (o.seed_edge ? L * 16 : 0) + (o.edge_load ? (size_t)P + 1 : 0) + (o.rate_post ? L * R : 0) +
-                                       (o.site_base ? L * 5 : 0));
-  const size_t most = per ? ((size_t)lh::debug_options().edge_out_mb << 20) / per : (size_t)INT32_MAX;
-  if ((size_t)n > most)
-    return fail(W + ": batch too large for the device copies of its per-row outputs: at most " + std::to_string(most) +
-                " samples per call for this family and path length");
-  for (size_t i = 0; i < (size_t)n; ++i) {
-    if (!valid_schedule(host.schedule(i), T, (int)host.nodes(), max_depth)) continue;  // (finish_batch refuses it)
-    if (!valid_chain(host.schedule(i), T, path + i * P, P))
-      return fail(W + ": path of sample " + std::to_string(i) +
-                  " is not a chain of inner nodes, each the child of the next, that ends at the root (padding after it)");
-    if (!valid_chain(host.schedule(i), T, path + i * P, P, seed_tip))
-      return fail(W + ": seed_tip " + std::to_string(seed_tip) + " is not a child of path[0] of sample " + std::to_string(i));
-  }
-  AncestralWs& a = f->anc;
-  EdgesWs& e = f->edges;
-  HostOutputs& out = f->out;
-  lh_eval_edges_outputs d{};
-  TreeBatch dev;
-  const size_t t16 = sizeof(double) * L * 16, t20 = sizeof(double) * L * 20;
-  if (out.loglik.ensure(sizeof(double) * n) || out_buf(o.site_base, a.site_base, sizeof(double) * L * 5 * n, &d.site_base) ||
-      out_buf(o.edge, e.out_edge, t16 * P * n, &d.edge) || out_buf(o.naive_edge, e.out_ne, t20 * n, &d.naive_edge) ||
-      out_buf(o.chain_counts, e.out_cc, t16 * n, &d.chain_counts) || out_buf(o.seed_edge, e.out_se, t16 * n, &d.seed_edge) ||
-      out_buf(o.edge_load, e.out_el, sizeof(double) * ((size_t)P + 1) * n, &d.edge_load) ||
-      out_buf(o.rate_post, a.rate_post, sizeof(double) * L * R * n, &d.rate_post) ||
-      out_buf(o.weighted_counts, e.out_wcc, t16, &d.weighted_counts) ||
-      out_buf(o.weighted_seed_edge, e.out_wse, t16, &d.weighted_seed_edge) ||
-      out_buf(o.weighted_naive_edge, e.out_wne, t20, &d.weighted_naive_edge) ||
-      out_buf(o.weight_stats, out.weight_stats, sizeof(double) * 3, &d.weight_stats) ||
-      stage_batch(f, host, {{o.log_offset, sizeof(double) * n, &f->in.log_offset}, {path, sizeof(int32_t) * P * n, &a.path}}, &dev))
-    return 1;
-  d.log_offset = o.log_offset ? f->in.log_offset.get<const double>() : nullptr;
-  d.loglik = out.loglik.get<double>();
-  if (lh_eval_edges_batch_device(f, n, T, max_depth, dev.ops, dev.brlen, dev.er, dev.pi, dev.model, R, a.path.get<const int32_t>(), P,
-                                 seed_tip, &d, nullptr))
-    return 1;
-  return finish_batch(f, W.c_str(), host,
-                      {{o.loglik, d.loglik, sizeof(double) * n},
-                       {o.site_base, d.site_base, sizeof(double) * L * 5 * n},
-                       {o.edge, d.edge, t16 * P * n},
-                       {o.naive_edge, d.naive_edge, t20 * n},
-                       {o.chain_counts, d.chain_counts, t16 * n},
-                       {o.seed_edge, d.seed_edge, t16 * n},
-                       {o.edge_load, d.edge_load, sizeof(double) * ((size_t)P + 1) * n},
-                       {o.rate_post, d.rate_post, sizeof(double) * L * R * n},
-                       {o.weighted_counts, d.weighted_counts, t16},
-                       {o.weighted_seed_edge, d.weighted_seed_edge, t16},
-                       {o.weighted_naive_edge, d.weighted_naive_edge, t20},
-                       {o.weight_stats, d.weight_stats, sizeof(double) * 3}});
+  const LineageCall c = edges_call(f, P, R, nullptr, path, seed_tip, outs ? *outs : lh_eval_edges_outputs{});
+  if (!c.asked()) return 0;
+  if (refuse_oversize(W, n, c, lh::debug_options().edge_out_mb)) return 1;  // (K11's rule)
+  return lineage_batch(f, W, host, c, n, [&](const TreeBatch& dev, LineageCall d) { return eval_edges_device(f, W, dev, d, nullptr); });
 }
 
 int lh_edges_profile_read(lh_family* f, double* ms, int64_t* n_launches) {
