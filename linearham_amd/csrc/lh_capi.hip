@@ -24,6 +24,7 @@ const DebugOptions& debug_options() {
     o.chunk = std::max(256, num("LH_CHUNK", o.chunk));
     o.host_sub = std::max(256, num("LH_HOST_SUB", o.host_sub));
     o.eval_split = std::min(8, std::max(0, num("LH_EVAL_SPLIT", o.eval_split)));
+    o.k0_serial = set("LH_K0_SERIAL");
     o.eval_fwd_priority = std::min(1, num("LH_EVAL_FWD_PRIORITY", o.eval_fwd_priority));
     o.k2b_no_pair = set("LH_K2B_NO_PAIR");
     o.k2b_vd_single = set("LH_K2B_VD_SINGLE");
@@ -358,12 +359,15 @@ struct HostPipe {
 
 // An evaluation's launch group in sub-batches (eval_group_split): K0a and every sub-batch's K0c + K1 on `prune`, every
 // sub-batch's K2 on `fwd`; the events order the two against each other and against the caller's stream.  Created by the
-// first launch group that is split; an event is recorded again by every group (a wait holds the record that was the last
+// handle's first evaluation; an event is recorded again by every group (a wait holds the record that was the last
 // one when the wait was enqueued).
+// The same streams run K0a beside K0c in front of every launch group's K1 (eval_device: K0a on `prune` behind `fork`,
+// joined by `join_prune` into the caller's stream, where K0c and K1 run; eval_group_split: K0a on `fwd` beside the first
+// sub-batch's K0c on `prune`, whose K1 waits for `k0a`).
 struct OverlapPipe {
   static constexpr int kMaxSplit = 8;  // LH_EVAL_SPLIT's range
   hipStream_t prune = nullptr, fwd = nullptr;
-  hipEvent_t fork = nullptr, join_prune = nullptr, join_fwd = nullptr;
+  hipEvent_t fork = nullptr, join_prune = nullptr, join_fwd = nullptr, k0a = nullptr;
   hipEvent_t pruned[kMaxSplit] = {};
   bool ready = false;
   int ensure(bool fwd_high) {
@@ -372,7 +376,7 @@ struct OverlapPipe {
     LH_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
     if (!prune) LH_HIP(hipStreamCreateWithFlags(&prune, hipStreamNonBlocking));
     if (!fwd) LH_HIP(hipStreamCreateWithPriority(&fwd, hipStreamNonBlocking, fwd_high ? greatest : 0));
-    for (hipEvent_t* e : {&fork, &join_prune, &join_fwd})
+    for (hipEvent_t* e : {&fork, &join_prune, &join_fwd, &k0a})
       if (!*e) LH_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
     for (hipEvent_t& e : pruned)
       if (!e) LH_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
@@ -380,7 +384,7 @@ struct OverlapPipe {
     return 0;
   }
   ~OverlapPipe() {
-    for (hipEvent_t e : {fork, join_prune, join_fwd})
+    for (hipEvent_t e : {fork, join_prune, join_fwd, k0a})
       if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : pruned)
       if (e) (void)hipEventDestroy(e);
@@ -849,9 +853,9 @@ size_t asr_group(const lh_family* f, int T, int R, size_t clv_per_sample) {
 // the workspace -- every array is indexed by sample alone (lh_prune.hip: eig [36], the scratch area [R][rate_stride], wops and
 // wlen [T - 2], tabs [tabs_stride], hdr [1], the planes [planes][5 | 1][n_prune] per sample); `rates` is the sub-batch's.
 // The planes' stride needs the plane count, which the shape and not the batch size decides: row0_planes is what the
-// group's first sub-batch got.
+// group's first sub-batch got.  fork: the schedule kernel on another stream, joined in front of K1 (lh::PruneFork).
 int prune_group(lh_family* f, const std::string& who, const TreeBatch& g, const double* rates, bool mix, hipStream_t stream,
-                int* planes, size_t row0 = 0, int row0_planes = 0) {
+                int* planes, size_t row0 = 0, int row0_planes = 0, const lh::PruneFork* fork = nullptr) {
   Workspace& w = f->ws;
   const lh::PruneWsSizes z = lh::prune_ws_sizes(g.T, f->host.msa_mixed_n != 0);
   const size_t L = (size_t)std::max(f->host.n_prune, 0), pl = (size_t)row0_planes;
@@ -863,7 +867,7 @@ int prune_group(lh_family* f, const std::string& who, const TreeBatch& g, const 
   p.hdr += row0;
   *planes = lh::launch_prune(f->host, g.n, g.R, g.T, g.max_depth, g.ops, g.brlen, rates, w.eig.get<double>() + row0 * 36, p, g.pi,
                              w.site_lik.get<double>() + row0 * pl * 5 * L, w.site_scal.get<int32_t>() + row0 * pl * L, stream,
-                             mix, f->extended || !mix);
+                             mix, f->extended || !mix, fork);
   if (*planes < 0) return fail(who + ": " + lh::prune_last_error());
   f->k1_form = lh::prune_last_form();
   if (!mix && *planes != g.R && f->host.n_prune > 0) return fail(who + ": internal error (rate planes were mixed)");
@@ -1643,6 +1647,12 @@ int eval_sub_batch(int m) {
   return ((m + kEvalSplit - 1) / kEvalSplit + kBlock - 1) / kBlock * kBlock;
 }
 
+// the handle's two internal streams and their events, created by the first evaluation
+int ensure_overlap(lh_family* f) {
+  const int fwd_priority = lh::debug_options().eval_fwd_priority;
+  return f->overlap.ensure(fwd_priority < 0 ? kEvalFwdHigh : fwd_priority > 0);
+}
+
 // One launch group of eval_device (samples off .. off + g.n of the call) in sub-batches of `per` samples: K2 of sub-batch i
 // runs on the handle's forward stream while K1 of sub-batch i + 1 runs on its pruning stream -- neither kernel fills the
 // vector units by itself.  A sub-batch is its own rows of the group's workspace (prune_group, run_forward): no second
@@ -1652,8 +1662,7 @@ int eval_sub_batch(int m) {
 int eval_group_split(lh_family* f, const TreeBatch& g, int off, int per, double* rates, double* em_out, double* loglik,
                      const lh_eval_outputs* outs, const lh::LogEmRequest& lem, hipStream_t stream) {
   OverlapPipe& op = f->overlap;
-  const int fwd_priority = lh::debug_options().eval_fwd_priority;
-  if (op.ensure(fwd_priority < 0 ? kEvalFwdHigh : fwd_priority > 0)) return 1;
+  if (ensure_overlap(f)) return 1;
   Workspace& w = f->ws;
   const int m = g.n, R = g.R;
   const size_t C = f->host.n_xmsa, L = (size_t)std::max(f->host.n_prune, 0);
@@ -1661,17 +1670,30 @@ int eval_group_split(lh_family* f, const TreeBatch& g, int off, int per, double*
   LH_HIP(hipEventRecord(op.fork, stream));
   LH_HIP(hipStreamWaitEvent(op.prune, op.fork, 0));
   LH_HIP(hipStreamWaitEvent(op.fwd, op.fork, 0));
+  // K0a runs once, beside the first sub-batch's K0c: K0a on the forward stream (idle until the first K2), K0c where it was,
+  // and that sub-batch's K1 behind both.  The K0 span then runs from K0a's start to that join and holds the first K0c;
+  // the later sub-batches' K0c stay in their K1 spans.  (LH_K0_SERIAL: K0a -> K0c -> K1 in a row on the pruning stream.)
+  const bool beside = !lh::debug_options().k0_serial;
+  hipStream_t k0a_stream = beside ? op.fwd : op.prune;
+  const lh::PruneFork k0_fork{op.prune, [&]() -> int {
+                                LH_HIP(hipStreamWaitEvent(op.prune, op.k0a, 0));
+                                if (timer && (timer->span_end(op.prune) || timer->span_begin(1, op.prune))) return 1;
+                                return 0;
+                              }};
   auto enqueue = [&]() -> int {
     if (timer) timer->begin_spans();
-    if (timer && timer->span_begin(0, op.prune)) return 1;
-    lh::launch_model_setup(m, R, g.er, g.pi, g.model, rates, w.eig.get<double>(), op.prune);
-    if (timer && timer->span_end(op.prune)) return 1;
+    if (timer && timer->span_begin(0, k0a_stream)) return 1;
+    lh::launch_model_setup(m, R, g.er, g.pi, g.model, rates, w.eig.get<double>(), k0a_stream);
+    if (beside) LH_HIP(hipEventRecord(op.k0a, op.fwd));
+    if (!beside && timer && timer->span_end(op.prune)) return 1;
     int planes = 0;
     for (int r0 = 0, j = 0; r0 < m; r0 += per, ++j) {
       const int k = std::min(per, m - r0);
       const TreeBatch sub = g.slice(r0, k);
-      if (timer && timer->span_begin(1, op.prune)) return 1;
-      if (prune_group(f, "lh_eval_batch", sub, rates + (size_t)r0 * R, true, op.prune, &planes, r0, planes)) return 1;
+      const bool forked = beside && r0 == 0;  // (its join opens the K1 span)
+      if (!forked && timer && timer->span_begin(1, op.prune)) return 1;
+      if (prune_group(f, "lh_eval_batch", sub, rates + (size_t)r0 * R, true, op.prune, &planes, r0, planes, forked ? &k0_fork : nullptr))
+        return 1;
       if (timer && timer->span_end(op.prune)) return 1;
       LH_HIP(hipEventRecord(op.pruned[j], op.prune));
       LH_HIP(hipStreamWaitEvent(op.fwd, op.pruned[j], 0));
@@ -1711,6 +1733,8 @@ int eval_device(lh_family* f, const TreeBatch& b, double* loglik, const lh_eval_
   double *eig = w.eig.get<double>(), *site_lik = w.site_lik.get<double>();
   int32_t* site_scal = w.site_scal.get<int32_t>();
   const size_t C = f->host.n_xmsa;
+  const bool serial_k0 = lh::debug_options().k0_serial;  // LH_K0_SERIAL: K0a -> K0c -> K1 in a row on the caller's stream
+  if (!serial_k0 && ensure_overlap(f)) return 1;
   for (int off = 0; off < n; off += chunk) {
     const int m = std::min(chunk, n - off);
     const TreeBatch g = b.slice(off, m);
@@ -1723,10 +1747,35 @@ int eval_device(lh_family* f, const TreeBatch& b, double* loglik, const lh_eval_
       continue;
     }
     if (f->profile && f->eval_timer.begin(stream)) return 1;
-    lh::launch_model_setup(m, R, g.er, g.pi, g.model, rates, eig, stream);
-    if (f->profile && f->eval_timer.mark(1, stream)) return 1;
     int planes = 0;
-    if (prune_group(f, "lh_eval_batch", g, rates, true, stream, &planes)) return 1;
+    if (serial_k0) {
+      lh::launch_model_setup(m, R, g.er, g.pi, g.model, rates, eig, stream);
+      if (f->profile && f->eval_timer.mark(1, stream)) return 1;
+      if (prune_group(f, "lh_eval_batch", g, rates, true, stream, &planes)) return 1;
+    } else {
+      // K0a (er / pi / alpha -> rates / eig) beside K0c (ops / brlen -> wops / wlen / tabs / hdr): neither reads what the
+      // other writes, and a thread respectively a wave per sample leaves both bound by latency, so the step pays the
+      // longer one instead of their sum (as far as they leave each other room: side by side K0a takes 119 instead of 65 us
+      // on configs[2] and K0c 130 instead of 96; profiles/r17_outside_k1.txt).  The K0 pair of events spans fork to join,
+      // K1's starts behind the join.
+      // K0c stays on the caller's stream, where K1 follows it without a wait between two queues (such a wait measured
+      // 20 us between K0c's end and K1's start, most of what running the two side by side saves); K0a, the shorter one,
+      // goes to the handle's pruning stream and has ended when K0c does.
+      OverlapPipe& op = f->overlap;
+      LH_HIP(hipEventRecord(op.fork, stream));
+      LH_HIP(hipStreamWaitEvent(op.prune, op.fork, 0));
+      lh::launch_model_setup(m, R, g.er, g.pi, g.model, rates, eig, op.prune);
+      LH_HIP(hipEventRecord(op.join_prune, op.prune));
+      bool joined = false;
+      const lh::PruneFork k0_fork{stream, [&]() -> int {
+                                    joined = true;
+                                    LH_HIP(hipStreamWaitEvent(stream, op.join_prune, 0));
+                                    return f->profile ? f->eval_timer.mark(1, stream) : 0;
+                                  }};
+      const int rc = prune_group(f, "lh_eval_batch", g, rates, true, stream, &planes, 0, 0, &k0_fork);
+      if (!joined) LH_HIP(hipStreamWaitEvent(stream, op.join_prune, 0));  // (K1 was refused before K0c went out)
+      if (rc) return 1;
+    }
     if (f->profile && f->eval_timer.mark(2, stream)) return 1;
     const lh::LogEmRequest lem_m{lem.cols, lem.n, lem.out ? lem.out + (size_t)off * lem.n : nullptr};
     if (run_forward(f, m, planes, site_lik, site_scal, g.pi, nullptr, em_out, loglik + off, outs, off, stream, lem_m))

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <functional>
+
 #include "linearham_amd.h"
 
 namespace lh {
@@ -40,6 +42,13 @@ struct PruneWsSizes {
   size_t tabs_per_sample;
 };
 PruneWsSizes prune_ws_sizes(int T, bool mixed_n);
+// K0c beside K0a (eval_device, lh_capi.hip): launch_prune puts the schedule kernel (K0c, or the register-stack forms' stack
+// check) on `sched` instead of its own stream and calls join() between that launch and K1's.  join() must order
+// launch_prune's stream behind `sched` (and behind whatever else K1 has to wait for); nonzero fails the launch.
+struct PruneFork {
+  hipStream_t sched;
+  std::function<int()> join;
+};
 
 // Device copy of lh_segments / lh_junction / family constants (all pointers are device pointers).
 struct DevSegments {
@@ -373,7 +382,7 @@ void launch_model_setup(int n, int R, const double* er, const double* pi, const 
 int launch_prune(const DevFamily& fam, int n, int R, int T, int max_depth, const int32_t* ops,
                  const double* brlen, const double* rates, const double* eig, const PruneWs& ws, const double* pi,
                  double* site_lik, int32_t* site_scal, hipStream_t stream, bool allow_fused = true,
-                 bool test_every_op = false);
+                 bool test_every_op = false, const PruneFork* fork = nullptr);
 // the kernel form the calling thread's last launch_prune chose ("w6<3,false>", "seg4<4,true>", "ct6<16,false,false,true>":
 // kernel<depth, N-aware, all rates in one workgroup, assembly walk>) and, after a -1, why it failed
 const char* prune_last_form();
@@ -629,6 +638,8 @@ struct DebugOptions {
   int eval_split = 0;          // LH_EVAL_SPLIT=<1..8>: sub-batches of every launch group of an evaluation, K2 of one beside K1
                                // of the next on the handle's two streams (1: the single-stream path; 0, unset: the
                                // product's choice, eval_sub_batch in lh_capi.hip)
+  bool k0_serial = false;      // LH_K0_SERIAL: an evaluation's K0a -> K0c -> K1 in a row on one stream, not K0a beside K0c on the
+                               // handle's two streams (eval_device in lh_capi.hip; tests compare the two bit for bit)
   int eval_fwd_priority = -1;  // LH_EVAL_FWD_PRIORITY=<0|1>: the K2 stream at default / at the highest priority (-1, unset:
                                // the product's choice)
   bool k2b_no_pair = false;    // LH_K2B_NO_PAIR: K2b with one sample per wave

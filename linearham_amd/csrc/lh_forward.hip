@@ -300,6 +300,10 @@ __device__ static inline ScaledProd sp_from(double e) {  // e in (0, 1]
   return r;
 }
 
+// high words of the doubles 2^-256, 2^-64, 2^64 and 2^256 (fill_consensus' test of a round of departures)
+constexpr uint32_t kHi2m256 = (1023u - 256u) << 20, kHi2m64 = (1023u - 64u) << 20;
+constexpr uint32_t kHi2p64 = (1023u + 64u) << 20, kHi2p256 = (1023u + 256u) << 20;
+
 // FillGermlinePaddingEmission through the set's consensus (DevSegments::cons_*).  All emissions are in (0, 1]
 // here (checked by the caller), so a gene's running product falls monotonically and the reference's pair
 // (value, ScaleMatrix count) is a function of the product alone: count = the fewest 2^256 factors that bring it
@@ -310,7 +314,7 @@ __device__ static inline ScaledProd sp_from(double e) {  // e in (0, 1]
 // candidates of one rearrangement.  lds: cons_inv[cap] | cons_pv[cap + 4] | cons_pk[cap + 4], cap = the largest
 // set's sites + 2, even (emission_lds_bytes).
 template <int kG, bool kByteOff>
-__device__ static int fill_consensus(const DevSegments& seg, const double* em, int tid, double* __restrict__ out,
+__device__ static __forceinline__ int fill_consensus(const DevSegments& seg, const double* em, int tid, double* __restrict__ out,
                                      int* redi, int phase, double* cons_inv, double* cons_pv, int* cons_pk,
                                      int cap) {  // cap: capacity of the prefix arrays; 4 more slots follow
   const int ns = seg.cons_sites, n = seg.n_genes;
@@ -391,16 +395,43 @@ __device__ static int fill_consensus(const DevSegments& seg, const double* em, i
         double fct[8];
 #pragma unroll
         for (int i = 0; i < 8; ++i) fct[i] = em_at(w[i] >> 16) * cons_inv[w[i] & 0xffffu];
+        // A round is safe when r starts within [2^-256, 2^256) and every factor lies within [2^-64, 2^64): every prefix
+        // of the round then stays within [2^-768, 2^768], so the eight multiplications run bare and (r, k) is settled
+        // once behind them -- the corrections are exact powers of two and commute bit for bit with the other factors
+        // while nothing leaves the normal range.  Positive doubles order as their high words do (a sign bit or a NaN
+        // reads as a large word), so the test is two integer min / max chains.  Decided for the whole wave, as
+        // fill_segments does; padding entries are factors of exactly 1.
+        uint32_t lo = (uint32_t)__double2hiint(fct[0]), hi = lo;
 #pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          r *= fct[i];
-          // keep r within [2^-256, 2^256): a ratio of two emissions can be far from 1
-          if (r < kScaleThreshold) {
+        for (int i = 1; i < 8; ++i) {
+          const uint32_t h = (uint32_t)__double2hiint(fct[i]);
+          lo = min(lo, h);
+          hi = max(hi, h);
+        }
+        const bool safe = lo >= kHi2m64 && hi < kHi2p64 && (uint32_t)__double2hiint(r) - kHi2m256 < kHi2p256 - kHi2m256;
+        if (__ballot(!safe) == 0) {
+#pragma unroll
+          for (int i = 0; i < 8; ++i) r *= fct[i];
+          while (r < kScaleThreshold) {
             r *= kScaleFactor;
             ++k;
-          } else if (r >= kScaleFactor) {
+          }
+          while (r >= kScaleFactor) {
             r *= kScaleThreshold;
             --k;
+          }
+        } else {  // a ratio of two emissions far from 1 somewhere in this wave: factor by factor
+#pragma unroll
+          for (int i = 0; i < 8; ++i) {
+            r *= fct[i];
+            // keep r within [2^-256, 2^256)
+            if (r < kScaleThreshold) {
+              r *= kScaleFactor;
+              ++k;
+            } else if (r >= kScaleFactor) {
+              r *= kScaleThreshold;
+              --k;
+            }
           }
         }
       }

@@ -1623,12 +1623,20 @@ PruneWsSizes prune_ws_sizes(int T, bool mixed_n) {
 // the rate categories themselves (the count K2a must then be run with); -1 when the launch failed (prune_last_error).
 int launch_prune(const DevFamily& fam, int n, int R, int T, int max_depth, const int32_t* ops,
                  const double* brlen, const double* rates, const double* eig, const PruneWs& ws, const double* pi,
-                 double* site_lik, int32_t* site_scal, hipStream_t stream, bool allow_fused, bool test_every_op) {
+                 double* site_lik, int32_t* site_scal, hipStream_t stream, bool allow_fused, bool test_every_op,
+                 const PruneFork* fork) {
+  // the schedule kernel's stream, and the caller's join behind it (K0c beside K0a)
+  hipStream_t sched = fork ? fork->sched : stream;
+  auto joined = [&]() {
+    if (!fork || fork->join() == 0) return true;
+    snprintf(g_prune_error, sizeof(g_prune_error), "K1: the schedule kernel's stream could not be joined");
+    return false;
+  };
   const int L = fam.n_prune;  // distinct alignment columns; identical ones are pruned once
   const PruneWsSizes sizes = prune_ws_sizes(T, fam.msa_mixed_n != 0);
   if (L == 0) {  // nothing but all-N padding (K2a reads no plane at all): the schedules still get checked
-    hipLaunchKernelGGL(schedule_stack_check_kernel, dim3(n), dim3(64), 0, stream, T, std::max(max_depth, 1), 0, ops, ws.hdr, ws.err_flag);
-    return R;
+    hipLaunchKernelGGL(schedule_stack_check_kernel, dim3(n), dim3(64), 0, sched, T, std::max(max_depth, 1), 0, ops, ws.hdr, ws.err_flag);
+    return joined() ? R : -1;
   }
   double* pmat = ws.scratch;
   const size_t rate_stride = sizes.scratch_doubles_per_rate;
@@ -1708,12 +1716,13 @@ int launch_prune(const DevFamily& fam, int n, int R, int T, int max_depth, const
   // the register-stack kernels run behind the stack check (fields, discipline, ranks when fused), the cherry-table kernels
   // behind K0c (the same checks, plus the rewrite)
   if (stack_fused || seg) {
-    hipLaunchKernelGGL(schedule_stack_check_kernel, dim3(n), dim3(64), 0, stream, T, stack_fused && max_depth <= 3 ? 3 : 4,
+    hipLaunchKernelGGL(schedule_stack_check_kernel, dim3(n), dim3(64), 0, sched, T, stack_fused && max_depth <= 3 ? 3 : 4,
                        stack_fused ? 1 : 0, ops, ws.hdr, ws.err_flag);
   } else {
-    hipLaunchKernelGGL(schedule_rewrite_kernel, dim3(n), dim3(64), (sizes.tabs_per_sample + 16) * sizeof(int), stream, T, max_depth,
+    hipLaunchKernelGGL(schedule_rewrite_kernel, dim3(n), dim3(64), (sizes.tabs_per_sample + 16) * sizeof(int), sched, T, max_depth,
                        (int)sizes.tabs_per_sample, dbg.k1_no_tables ? 0 : 1, ops, brlen, ws.wops, ws.wlen, ws.tabs, ws.hdr, ws.err_flag);
   }
+  if (!joined()) return -1;
   const int wg_waves = fused ? R * wpr : wpr;
   dim3 grid(tiles, fused ? 1 : R, n), block(64 * wg_waves);
   const int n_ops = T - 2;
