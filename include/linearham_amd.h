@@ -680,6 +680,61 @@ int lh_eval_edges_batch_device(lh_family* fam, int32_t n, int32_t n_tips, int32_
  * combination, the weighted reduction (lh_eval_edges_batch only); resets the counters. */
 int lh_edges_profile_read(lh_family* fam, double* ms, int64_t* n_launches);
 
+/* ---- K13: exact posterior probabilities of candidate ancestral sequences ----
+ * K11's per-site tables cannot give the probability of a whole sequence at a node of the lineage: the node's sites are
+ * coupled through the naive sequence, whose sites the HMM couples.  For a tree sample t, a node v and a candidate x
+ *   P(X_v = x | data, t) = sum_paths prior(path) prod_j E_t[b_j, j] G_t[j][b_j][x_j] / P(data | t),
+ * b_j the naive base the path writes on site j, E_t the xMSA emission and G_t[j][b][c] = P(x_{v,j} = c | column j,
+ * naive_j = b), K11's table for a one-hot naive distribution.  Every (row, candidate) pair takes one forward sweep.
+ *
+ * lh_family_set_ancestral_candidates registers K candidates (1 <= K <= 65536) of n_sites bytes each: 0..3 = A, C, G, T,
+ * 4 = the site is left open (any base).  They are kept apart from lh_family_set_candidates' naive candidates, which stay
+ * registered.  A call that fails leaves no candidates.  Refused for a family without an MSA or without the constrained
+ * forward sweep (as lh_family_set_candidates). */
+int lh_family_set_ancestral_candidates(lh_family* fam, int32_t K, const uint8_t* seqs);
+
+/* (candidates registered, sites each has) */
+int lh_ancestral_candidates_info(const lh_family* fam, int32_t* n_candidates, int32_t* n_sites);
+
+/* The evaluation with K13 behind it: lh_eval_ancestral_batch's inputs plus node, 0 = the seed's parent (slot 0 of the
+ * path), 1 = the MRCA (the sample's last slot).  Needs lh_family_set_sampler and lh_family_set_ancestral_candidates; a handle
+ * in the extended-range mode is refused (the candidates' sweeps run on plain doubles).  Every member may be NULL:
+ *   log_offset   [n]           (input) as in lh_posterior_outputs
+ *   loglik       [n]
+ *   cond         [n][L][5][4]  G: P(x_{node,j} = c | column j, naive_j = b), b = A,C,G,T,N
+ *   log_cand     [n][K]        log P(X_node = x_k | data, t_i); an all-open candidate gives exactly 0
+ *   weighted_sum [K]           sum_i w_i P(x_k | data, t_i), w_i = exp(loglik_i - log_offset_i - max)
+ *   weight_stats [3]           max, sum w, sum w^2 as in lh_posterior_outputs
+ * A row with a non-finite log-likelihood, a rejected schedule or (device form) a bad path gets NaN in cond and log_cand
+ * and no weight; the path is checked, the error word raised and the host-pointer form's device copies of cond and
+ * log_cand bounded (4 GiB) as for lh_eval_ancestral_batch.  The sums run in sample order (K5's slab scheme); the same
+ * sample gives the same bits whatever the batch around it. */
+typedef struct lh_ancestral_candidates_outputs {
+  const double* log_offset;
+  double* loglik;
+  double* cond;
+  double* log_cand;
+  double* weighted_sum;
+  double* weight_stats;
+} lh_ancestral_candidates_outputs;
+
+int lh_eval_ancestral_candidates_batch(lh_family* fam, int32_t n, int32_t n_tips, int32_t max_depth, const int32_t* ops,
+                                       const double* brlen, const double* er, const double* pi, const double* alpha,
+                                       int32_t num_rates, const int32_t* path, int32_t path_len, int32_t node,
+                                       const lh_ancestral_candidates_outputs* outs);
+
+/* Same with every array (the members of outs included) resident on the handle's device; enqueued on `hip_stream`
+ * without synchronising. */
+int lh_eval_ancestral_candidates_batch_device(lh_family* fam, int32_t n, int32_t n_tips, int32_t max_depth,
+                                              const int32_t* ops, const double* brlen, const double* er, const double* pi,
+                                              const double* alpha, int32_t num_rates, const int32_t* path, int32_t path_len,
+                                              int32_t node, const lh_ancestral_candidates_outputs* outs, void* hip_stream);
+
+/* Times of K13 over the launches made while profiling was enabled (HIP events on the launch stream), ms[3]: the tables
+ * (rate weights, path check, K13b, rate combination), the pair emissions with their sweeps, the weighted reduction; resets
+ * the counters. */
+int lh_ancestral_candidates_profile_read(lh_family* fam, double* ms, int64_t* n_launches);
+
 /* Timing of the kernels of the last lh_eval_batch_device call sequence, measured with HIP events
  * on the launch stream when enabled (ms per kernel family: model, prune, forward). */
 int lh_profile_enable(lh_family* fam, int enable);

@@ -85,6 +85,12 @@ EXPORTS += ANCESTRAL_EXPORTS
 EDGES_EXPORTS = ["lh_asr_edges_batch", "lh_asr_edges_batch_device", "lh_eval_edges_batch", "lh_eval_edges_batch_device",
                  "lh_edges_profile_read"]
 EXPORTS += EDGES_EXPORTS
+# K13 (exact posterior probabilities of candidate ancestral sequences)
+ANCESTRAL_PROBS_EXPORTS = ["lh_family_set_ancestral_candidates", "lh_ancestral_candidates_info",
+                           "lh_eval_ancestral_candidates_batch", "lh_eval_ancestral_candidates_batch_device",
+                           "lh_ancestral_candidates_profile_read"]
+EXPORTS += ANCESTRAL_PROBS_EXPORTS
+NODE_PARENT, NODE_MRCA = 0, 1  # lh_eval_ancestral_candidates_batch's `node`
 
 
 class _CodonOutputs(C.Structure):
@@ -147,6 +153,17 @@ class _EvalEdgesOutputs(C.Structure):
 
 class _EvalEdgesOutputsDevice(C.Structure):  # the same members as device addresses
     _fields_ = [(k, C.c_void_p) for k in _EVAL_EDGES_MEMBERS]
+
+
+_ANCESTRAL_PROBS_MEMBERS = ("log_offset", "loglik", "cond", "log_cand", "weighted_sum", "weight_stats")
+
+
+class _AncestralProbsOutputs(C.Structure):
+    _fields_ = [(k, c_f64p) for k in _ANCESTRAL_PROBS_MEMBERS]
+
+
+class _AncestralProbsOutputsDevice(C.Structure):  # the same members as device addresses
+    _fields_ = [(k, C.c_void_p) for k in _ANCESTRAL_PROBS_MEMBERS]
 
 
 class _SamplerJunction(C.Structure):
@@ -306,6 +323,14 @@ class HipLibrary:
             lib.lh_eval_edges_batch_device.argtypes = _DEV_TREE + [C.c_void_p, C.c_int32, C.c_int32,
                                                                    C.POINTER(_EvalEdgesOutputsDevice), C.c_void_p]
             lib.lh_edges_profile_read.argtypes = _PROFILE_READ
+        if hasattr(lib, "lh_family_set_ancestral_candidates"):
+            lib.lh_family_set_ancestral_candidates.argtypes = [C.c_void_p, C.c_int32, c_u8p]
+            lib.lh_ancestral_candidates_info.argtypes = [C.c_void_p, c_i32p, c_i32p]
+            lib.lh_eval_ancestral_candidates_batch.argtypes = _HOST_TREE + [c_i32p, C.c_int32, C.c_int32,
+                                                                            C.POINTER(_AncestralProbsOutputs)]
+            lib.lh_eval_ancestral_candidates_batch_device.argtypes = _DEV_TREE + [
+                C.c_void_p, C.c_int32, C.c_int32, C.POINTER(_AncestralProbsOutputsDevice), C.c_void_p]
+            lib.lh_ancestral_candidates_profile_read.argtypes = _PROFILE_READ
         if hasattr(lib, "lh_set_device"):      # (absent from round-2 builds loaded through LH_LIB_DIR for comparisons)
             lib.lh_set_device.argtypes = [C.c_int32]
             lib.lh_family_status.argtypes = [C.c_void_p]
@@ -368,6 +393,57 @@ class HipLibrary:
     def ancestral_profile_read(self, family):
         """(k11a_ms, k11b_ms, reduce_ms, launch groups) of K11 since the last read."""
         return self._profile_read("lh_ancestral_profile_read", family, 3)
+
+    def ancestral_candidates_info(self, family):
+        """(ancestral candidates registered on the handle, sites each has): lh_ancestral_candidates_info."""
+        k, L = C.c_int32(), C.c_int32()
+        self.check(self.lib.lh_ancestral_candidates_info(_handle(family), C.byref(k), C.byref(L)))
+        return k.value, L.value
+
+    def set_ancestral_candidates(self, family, seqs):
+        """K13: registers candidate ancestral sequences seqs [K][L] on a family handle: A,C,G,T = 0..3, 4 = the site is
+        left open.  The naive candidates of set_candidates stay registered."""
+        h = _handle(family)
+        seqs = np.asarray(seqs)
+        if seqs.ndim != 2 or seqs.dtype.kind not in "iu":
+            raise ValueError("lh_family_set_ancestral_candidates: candidates must be an integer [K][L] array")
+        L = self.ancestral_candidates_info(h)[1]
+        if seqs.shape[1] != L:
+            raise ValueError("lh_family_set_ancestral_candidates: candidates have %d sites, the family's alignment %d"
+                             % (seqs.shape[1], L))
+        if seqs.size and (seqs.min() < 0 or seqs.max() > 255):
+            raise ValueError("lh_family_set_ancestral_candidates: bases must be bytes")
+        seqs = np.ascontiguousarray(seqs, dtype=np.uint8)
+        self.check(self.lib.lh_family_set_ancestral_candidates(h, seqs.shape[0], seqs.ctypes.data_as(c_u8p)))
+
+    def eval_ancestral_candidates_batch(self, family, n_tips, max_depth, ops, brlen, er, pi, alpha, num_rates, path, node,
+                                        log_offset=None, want=("loglik", "cond", "log_cand", "weighted_sum",
+                                                               "weight_stats")):
+        """K0-K2 + K5 + K13 on a family handle that has sampler tables and ancestral candidates; path [n][P] (seed_path
+        rows, -1 padding), node NODE_PARENT or NODE_MRCA.  Returns a dict with the members of `want`: loglik [n], cond
+        [n, L, 5, 4] (P(x_node = c | column, naive base b)), log_cand [n, K], weighted_sum [K], weight_stats [3]."""
+        h = _handle(family)
+        n, arrays = _tree_args(ops, brlen, er, pi, alpha)
+        path = _i32(path)
+        assert path.ndim == 2 and path.shape[0] == n
+        K, L = self.ancestral_candidates_info(h)
+        res, outs = _outputs(_AncestralProbsOutputs, want, log_offset, loglik=(n,), cond=(n, L, 5, 4), log_cand=(n, K),
+                             weighted_sum=(K,), weight_stats=(3,))
+        self.check(self.lib.lh_eval_ancestral_candidates_batch(h, n, n_tips, max_depth, *_tree_ptrs(arrays), num_rates,
+                                                               _ptr(path, c_i32p), path.shape[1], node, C.byref(outs)))
+        return res
+
+    def eval_ancestral_candidates_batch_device(self, family, n, n_tips, max_depth, ops_ptr, brlen_ptr, er_ptr, pi_ptr,
+                                               alpha_ptr, num_rates, path_ptr, path_len, node, outs, stream=0):
+        """lh_eval_ancestral_candidates_batch_device on device addresses; outs: dict of the output members' addresses."""
+        o = _AncestralProbsOutputsDevice(**{k: int(v) for k, v in outs.items() if v})
+        self.check(self.lib.lh_eval_ancestral_candidates_batch_device(
+            _handle(family), n, n_tips, max_depth, ops_ptr, brlen_ptr, er_ptr, pi_ptr, alpha_ptr, num_rates, path_ptr,
+            path_len, node, C.byref(o), stream))
+
+    def ancestral_candidates_profile_read(self, family):
+        """(tables ms, pair emissions and sweeps ms, reduction ms, launch groups) of K13 since the last read."""
+        return self._profile_read("lh_ancestral_candidates_profile_read", family, 3)
 
     def eval_edges_batch(self, family, n_tips, max_depth, ops, brlen, er, pi, alpha, num_rates, path, seed_tip,
                          log_offset=None, want=("loglik", "chain_counts", "seed_edge", "naive_edge", "edge_load")):

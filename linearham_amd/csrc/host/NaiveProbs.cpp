@@ -131,12 +131,15 @@ std::string ReprDouble(double v) {
   return out;
 }
 
-std::vector<std::string> ReadCandidateFile(const std::string& path, int n_sites) {
+namespace {
+
+// names: the candidates' names too (ReadNamedCandidateFile), or null
+std::vector<std::string> ReadCandidates(const std::string& path, int n_sites, std::vector<std::string>* names) {
   std::ifstream in(path);
   if (!in) throw std::runtime_error("Can't read candidate file " + path);
   std::vector<std::string> seqs;
   std::vector<int> line_of;
-  std::string line, cur;
+  std::string line, cur, cur_name;
   int ln = 0, cur_line = 0, header_line = 0;
   bool fasta = false;
   auto refuse_empty_record = [&] {
@@ -147,7 +150,9 @@ std::vector<std::string> ReadCandidateFile(const std::string& path, int n_sites)
     if (cur.empty()) return;
     seqs.push_back(cur);
     line_of.push_back(cur_line);
+    if (names) names->push_back(cur_name.empty() ? "candidate_" + std::to_string(seqs.size()) : cur_name);
     cur.clear();
+    cur_name.clear();
   };
   while (std::getline(in, line)) {
     ++ln;
@@ -158,6 +163,7 @@ std::vector<std::string> ReadCandidateFile(const std::string& path, int n_sites)
       fasta = true;
       flush();
       header_line = ln;
+      cur_name = line.substr(1, std::min(line.find_first_of(" \t", 1), line.size()) - 1);
       continue;
     }
     for (char& ch : line) {
@@ -192,11 +198,45 @@ std::vector<std::string> ReadCandidateFile(const std::string& path, int n_sites)
   return seqs;
 }
 
-std::vector<std::size_t> RankCandidates(const NaiveProbsTable& t) {
-  std::vector<std::size_t> idx(t.seqs.size());
+std::vector<std::size_t> RankByProbability(const std::vector<double>& prob) {
+  std::vector<std::size_t> idx(prob.size());
   for (std::size_t k = 0; k < idx.size(); ++k) idx[k] = k;
-  std::stable_sort(idx.begin(), idx.end(), [&](std::size_t a, std::size_t b) { return t.prob[a] > t.prob[b]; });
+  std::stable_sort(idx.begin(), idx.end(), [&](std::size_t a, std::size_t b) { return prob[a] > prob[b]; });
   return idx;
+}
+
+}  // namespace
+
+std::vector<std::string> ReadCandidateFile(const std::string& path, int n_sites) { return ReadCandidates(path, n_sites, nullptr); }
+
+NamedCandidates ReadNamedCandidateFile(const std::string& path, int n_sites) {
+  NamedCandidates c;
+  c.seqs = ReadCandidates(path, n_sites, &c.names);
+  return c;
+}
+
+std::vector<std::size_t> RankCandidates(const NaiveProbsTable& t) { return RankByProbability(t.prob); }
+
+void WriteAncestralProbsTable(std::ostream& o, const AncestralProbsTable& t) {
+  char buf[64];
+  o << "name\tsequence\tprobability\n";
+  for (std::size_t k : RankByProbability(t.prob)) {
+    std::snprintf(buf, sizeof buf, "%.17g", t.prob[k]);
+    o << t.names[k] << '\t' << t.seqs[k] << '\t' << buf << '\n';
+  }
+}
+
+double CoveredMass(const AncestralProbsTable& t) {
+  double mass = 0.0;
+  for (std::size_t k = 0; k < t.seqs.size(); ++k)
+    if (t.seqs[k].find('N') == std::string::npos) mass += t.prob[k];
+  return mass;
+}
+
+int ParseLineageNode(const std::string& name) {
+  if (name == "parent") return 0;
+  if (name == "mrca") return 1;
+  throw std::runtime_error("--node must be 'parent' (the seed's parent) or 'mrca', not '" + name + "'");
 }
 
 void WriteNaiveTable(std::ostream& o, const NaiveProbsTable& t, bool with_sampled) {

@@ -32,6 +32,24 @@ std::string ReprDouble(double v);
 /// and every FASTA header must be followed by sequence lines.  Throws with the line number otherwise, and for a file
 /// without sequences.
 std::vector<std::string> ReadCandidateFile(const std::string& path, int n_sites);
+/// The same file with the candidates' names, by the same rules: a FASTA record's name is its header up to the first
+/// blank, a plain line's is "candidate_<k>", k counting the sequences from 1.
+struct NamedCandidates {
+  std::vector<std::string> names, seqs;
+};
+NamedCandidates ReadNamedCandidateFile(const std::string& path, int n_sites);
+/// Candidate ancestral sequences (PhyloHMM::AncestralCandidatePosterior, RunAncestralProbsPipeline) with their exact
+/// posterior probability, in file order.  N leaves a site open.
+struct AncestralProbsTable {
+  std::vector<std::string> names, seqs;
+  std::vector<double> prob;
+};
+/// <prefix>.probs.tsv: name, sequence, probability ("%.17g"), ranked as RankCandidates ranks.
+void WriteAncestralProbsTable(std::ostream& o, const AncestralProbsTable& t);
+/// The sum of the probabilities of the candidates without an open site: distinct ones cover at most 1.
+double CoveredMass(const AncestralProbsTable& t);
+/// --node's values: "parent" -> 0 (the seed's parent), "mrca" -> 1; throws otherwise.
+int ParseLineageNode(const std::string& name);
 /// Candidate order sorted by probability, descending, ties by candidate order.
 std::vector<std::size_t> RankCandidates(const NaiveProbsTable& t);
 /// <prefix>.naive.tsv: rank, NaiveSequence, probability, log_prior[, sampled_count, sampled_frequency] ("%.17g";

@@ -2592,6 +2592,79 @@ std::vector<double> PhyloHMM::CandidatePosterior(const std::vector<std::string>&
   return lc;
 }
 
+// ---- K13: exact posterior probabilities of candidate ancestral sequences ----
+
+PhyloHMM::AncestralCandidateResult PhyloHMM::AncestralCandidatePosterior(const std::string& seed_seq, int node,
+                                                                         const std::vector<std::string>& candidates) {
+  Require(node == 0 || node == 1, "AncestralCandidatePosterior: node must be 0 (the seed's parent) or 1 (the MRCA)");
+  Require(!candidates.empty(), "AncestralCandidatePosterior: no candidates");
+  const int L = msa_.cols(), K = (int)candidates.size();
+  const std::vector<uint8_t> bytes = EncodeSeqs(candidates, alphabet_, L);
+  SeedLineage s = OpenSeedLineage(seed_seq);
+  CheckHip(lh_family_set_ancestral_candidates(family_, K, bytes.data()), "lh_family_set_ancestral_candidates");
+  AncestralCandidateResult res;
+  res.node = node == 0 ? s.nodes.front() : s.nodes.back();
+  res.log_cand.assign(K, 0.0);
+  lh_ancestral_candidates_outputs outs{};
+  outs.loglik = &res.loglik;
+  outs.log_cand = res.log_cand.data();
+  CheckHip(lh_eval_ancestral_candidates_batch(family_, 1, tree_.n_tips, s.depth, s.ops.data(), tree_.brlen.data(), er_.data(),
+                                              pi_.data(), &alpha_, num_rates_, s.nodes.data(), (int32_t)s.nodes.size(), node, &outs),
+           "lh_eval_ancestral_candidates_batch");
+  return res;
+}
+
+void PhyloHMM::RunAncestralProbsPipeline(const std::string& input_path, const std::string& seed_seq, int node,
+                                         const std::string& candidates_path, const std::string& output_prefix, int num_rates,
+                                         double burnin_frac) {
+  // what can be refused without a device is refused first: the node, the candidate file, then BeginPipeline's checks
+  Require(node == 0 || node == 1, "the ancestral-probabilities pipeline: node must be 0 (the seed's parent) or 1 (the MRCA)");
+  const int L = msa_.cols();
+  AncestralProbsTable t;
+  {
+    NamedCandidates c = ReadNamedCandidateFile(candidates_path, L);
+    t.names = std::move(c.names);
+    t.seqs = std::move(c.seqs);
+  }
+  const std::size_t K = t.seqs.size();
+  const std::vector<uint8_t> bytes = EncodeSeqs(t.seqs, alphabet_, L);
+  const int seed_tip = BeginPipeline("ancestral probabilities", "posterior", burnin_frac, &seed_seq);
+  CheckHip(lh_family_set_ancestral_candidates(family_, (int32_t)K, bytes.data()), "lh_family_set_ancestral_candidates");
+  TsvTable table = TsvTable::OpenRevBayesTable(input_path);
+  const std::size_t first = FirstUsedRow(table.rows.size(), burnin_frac);
+  // the rows' log_cand come back whole (K doubles each): a batch is bounded by at most 512 MiB of them
+  const std::size_t fit = std::max<std::size_t>(1, ((std::size_t)512 << 20) / (sizeof(double) * K));
+  std::vector<double> log_cand;
+  std::vector<int32_t> path_len(table.rows.size() - first, 0);
+  const WeightedRows w = SumWeightedRows(
+      "ancestral probabilities", table, input_path, first, PipelineBatch(fit), K, true,
+      [&](const TableBatch& tb, std::size_t off, double* ll) {
+        const DeviceBatch& b = tb.dev;
+        const SeedChains sc = SeedChainsOf(tb, off, seed_tip, seed_seq, path_len.data() + (off - first));
+        log_cand.resize((std::size_t)b.n * K);
+        lh_ancestral_candidates_outputs outs{};
+        outs.loglik = ll;
+        outs.log_cand = log_cand.data();
+        CheckHip(lh_eval_ancestral_candidates_batch(family_, b.n, b.n_tips, b.max_depth, b.ops.data(), b.brlen.data(),
+                                                    b.er.data(), b.pi.data(), b.alpha.data(), num_rates, sc.path.data(),
+                                                    (int32_t)sc.P, node, &outs),
+                 "lh_eval_ancestral_candidates_batch");
+        return [&](std::size_t i, double* row) {
+          for (std::size_t k = 0; k < K; ++k) row[k] = std::exp(log_cand[i * K + k]);
+        };
+      });
+  t.prob = w.acc.total;
+  std::ofstream probs(output_prefix + ".probs.tsv"), rows(output_prefix + ".rows.tsv"), summary(output_prefix + ".summary.tsv");
+  Require(probs.good() && rows.good() && summary.good(), "Can't write " + output_prefix + ".*.tsv");
+  WriteAncestralProbsTable(probs, t);
+  WriteSeedRows(rows, first, w, path_len);
+  WriteSummary(summary, w.used(), w.skipped, Fmt17(w.acc.KishEss()));
+  std::size_t constrained = 0;
+  for (const std::string& q : t.seqs) constrained += q.find('N') == std::string::npos;
+  summary << "candidates\t" << K << "\ncandidates_constrained\t" << constrained << "\ncovered_mass\t" << Fmt17(CoveredMass(t))
+          << "\n";
+}
+
 // Pass 1 draws every used row's naive sequence with the std::mt19937 words RunPipeline gives that row (row r: words
 // r * RawDrawsPerSample() on), on the device where the family has its sampler tables: K4's states become bytes and a
 // hash there (K6c), the host maps hashes to candidate ids in row order and the device checks every row's bytes against

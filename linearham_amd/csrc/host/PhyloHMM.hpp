@@ -252,6 +252,26 @@ class PhyloHMM : public HMM {
   /// expected number of differing edge ends over all sites) and .summary.tsv.
   void RunLineageSubstitutionsPipeline(const std::string& input_path, const std::string& seed_seq,
                                        const std::string& output_prefix, int num_rates, double burnin_frac);
+  /// K13: exact posterior probabilities of whole candidate sequences at a node of the lineage of the tip `seed_seq`
+  /// (lh_eval_ancestral_candidates_batch): node 0 = the seed's parent, 1 = the MRCA; candidates of the alignment's length
+  /// over ACGTN, N leaving the site open.
+  struct AncestralCandidateResult {
+    std::vector<double> log_cand;  // [K] log P(X_node = x_k | data, tree)
+    int32_t node = 0;              // the node in lh_schedule_tree's numbering
+    double loglik = 0.0;
+  };
+  /// After InitializePhyloParameters: the candidates' log probabilities under the current tree.
+  AncestralCandidateResult AncestralCandidatePosterior(const std::string& seed_seq, int node,
+                                                       const std::vector<std::string>& candidates);
+  /// The importance-weighted probabilities of the candidates of `candidates_path` (ReadNamedCandidateFile) over a RevBayes
+  /// table, with RunAncestralMarginalsPipeline's reader, burn-in, weights, Kish ESS and one-device rule.  The node and the
+  /// candidate file are checked first, before any device work.  The rows' probabilities are added up on the host in row
+  /// order, so the files do not depend on LH_PIPELINE_BATCH.  Writes <prefix>.probs.tsv (name, sequence, probability,
+  /// ranked), .rows.tsv (row, weight, chain_length) and .summary.tsv (rows used and skipped, Kish ESS, the candidates,
+  /// those without an open site and the posterior mass these cover).
+  void RunAncestralProbsPipeline(const std::string& input_path, const std::string& seed_seq, int node,
+                                 const std::string& candidates_path, const std::string& output_prefix, int num_rates,
+                                 double burnin_frac);
   /// site, then one column per cell named <ancestor base><descendant base> (n_rows x 4 cells, rows over ACGTN), and with
   /// `with_sum` the off-diagonal sum of the first four rows; numbers printed with %.17g
   static void WritePairTable(std::ostream& o, const double* table, std::size_t n_sites, int n_rows, bool with_sum);

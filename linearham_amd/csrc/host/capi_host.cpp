@@ -350,6 +350,63 @@ int lhh_write_pair_table(const double* table, int n_sites, int n_rows, int with_
   });
 }
 
+// PhyloHMM::AncestralCandidatePosterior: candidates = K sequences joined by '\n'; log_cand [K]
+int lhh_phylo_ancestral_candidate_posterior(void* h, const char* seed_seq, int node, const char* candidates, int K,
+                                            double* log_cand, int* node_id, double* loglik) {
+  return Guard([&] {
+    std::vector<std::string> seqs;
+    std::istringstream in(candidates);
+    for (std::string line; std::getline(in, line);) seqs.push_back(line);
+    if ((int)seqs.size() != K) throw std::runtime_error("lhh_phylo_ancestral_candidate_posterior: K does not match the candidates");
+    const PhyloHMM::AncestralCandidateResult r =
+        dynamic_cast<PhyloHMM&>(*static_cast<HMM*>(h)).AncestralCandidatePosterior(seed_seq, node, seqs);
+    std::copy(r.log_cand.begin(), r.log_cand.end(), log_cand);
+    if (node_id) *node_id = r.node;
+    if (loglik) *loglik = r.loglik;
+  });
+}
+
+int lhh_run_ancestral_probs_pipeline(void* h, const char* input_path, const char* seed_seq, int node, const char* candidates_path,
+                                     const char* output_prefix, int num_rates, double burnin_frac) {
+  return Guard([&] {
+    dynamic_cast<PhyloHMM&>(*static_cast<HMM*>(h)).RunAncestralProbsPipeline(input_path, seed_seq, node, candidates_path,
+                                                                           output_prefix, num_rates, burnin_frac);
+  });
+}
+
+// WriteAncestralProbsTable's text of K candidates: names and seqs joined by '\n'; *covered receives CoveredMass
+int lhh_write_ancestral_probs_table(const char* names, const char* seqs, const double* prob, int K, const char** out,
+                                    double* covered) {
+  return Guard([&] {
+    linearham::AncestralProbsTable t;
+    std::istringstream a(names), b(seqs);
+    for (std::string line; std::getline(a, line);) t.names.push_back(line);
+    for (std::string line; std::getline(b, line);) t.seqs.push_back(line);
+    if ((int)t.names.size() != K || (int)t.seqs.size() != K) throw std::runtime_error("lhh_write_ancestral_probs_table: bad shape");
+    t.prob.assign(prob, prob + K);
+    std::ostringstream o;
+    linearham::WriteAncestralProbsTable(o, t);
+    g_out = o.str();
+    *out = g_out.c_str();
+    if (covered) *covered = linearham::CoveredMass(t);
+  });
+}
+
+// ReadNamedCandidateFile: "name\tsequence" lines
+int lhh_read_named_candidates(const char* path, int n_sites, const char** out) {
+  return Guard([&] {
+    const linearham::NamedCandidates c = linearham::ReadNamedCandidateFile(path, n_sites);
+    std::string s;
+    for (std::size_t k = 0; k < c.seqs.size(); ++k) s += c.names[k] + "\t" + c.seqs[k] + "\n";
+    g_out = s;
+    *out = g_out.c_str();
+  });
+}
+
+int lhh_parse_lineage_node(const char* name, int* node) {
+  return Guard([&] { *node = linearham::ParseLineageNode(name); });
+}
+
 int lhh_run_lineage_substitutions_pipeline(void* h, const char* input_path, const char* seed_seq, const char* output_prefix,
                                            int num_rates, double burnin_frac) {
   return Guard([&] {

@@ -65,7 +65,7 @@ int main(int argc, char** argv) {
   try {
     if (argc < 2 || std::string(argv[1]) == "-h" || std::string(argv[1]) == "--help") {
       std::cout << "A Phylo-HMM implementation for B cell receptor sequence analysis.\n"
-                   "USAGE: linearham {--compute-logl|--sample|--pipeline|--asr|--marginals|--marginals-pipeline|--naive-probs|--naive-probs-pipeline|--lineage-pipeline|--weighted-lineage-pipeline|--viterbi|--annotations-pipeline|--codon-marginals|--codon-marginals-pipeline|--events|--events-pipeline|--ancestral-marginals|--ancestral-marginals-pipeline|--lineage-substitutions|--lineage-substitutions-pipeline} --yaml-path <string> "
+                   "USAGE: linearham {--compute-logl|--sample|--pipeline|--asr|--marginals|--marginals-pipeline|--naive-probs|--naive-probs-pipeline|--lineage-pipeline|--weighted-lineage-pipeline|--viterbi|--annotations-pipeline|--codon-marginals|--codon-marginals-pipeline|--events|--events-pipeline|--ancestral-marginals|--ancestral-marginals-pipeline|--lineage-substitutions|--lineage-substitutions-pipeline|--ancestral-probs|--ancestral-probs-pipeline} --yaml-path <string> "
                    "--cluster-ind <int> --hmm-param-dir <string> [--seed <int>] [--num-rates <int>] [--extended-range <0|1>] "
                    "[--devices <a,b,...>] ...\n"
                    "  --marginals: the arguments of --compute-logl; prints the per-site naive-base table and the gene table\n"
@@ -102,6 +102,12 @@ int main(int argc, char** argv) {
                    "  --lineage-substitutions-pipeline --input-path <RevBayes table> --output-path <prefix> --seed-seq <name>\n"
                    "    [--burnin-frac <f>]: writes <prefix>.substitutions.tsv, <prefix>.seed_edge.tsv, <prefix>.naive_edge.tsv,\n"
                    "    <prefix>.rows.tsv and <prefix>.summary.tsv (one device)\n"
+                   "  --ancestral-probs --seed-seq <name> --node <parent|mrca> --candidates <fasta>: the arguments of --marginals;\n"
+                   "    prints the exact posterior probability of every candidate sequence at the parent of the sequence <name>\n"
+                   "    or at its MRCA with naive (name, sequence, probability, ranked; N leaves a site open)\n"
+                   "  --ancestral-probs-pipeline --input-path <RevBayes table> --output-path <prefix> --seed-seq <name>\n"
+                   "    --node <parent|mrca> --candidates <fasta> [--burnin-frac <f>]: writes <prefix>.probs.tsv, <prefix>.rows.tsv\n"
+                   "    and <prefix>.summary.tsv (one device)\n"
                    "  --lineage-pipeline --input-path <--pipeline table> --output-path <prefix> --seed-seq <name> [--seed <int>]:\n"
                    "    the lineage tables of the sequence <name>: <prefix>.fasta, .dnamap, .nodes.tsv, .edges.tsv, .summary.tsv\n"
                    "       linearham --lineage-trees --input-path <--asr trees> --output-path <prefix> --seed-seq <name>\n"
@@ -131,7 +137,8 @@ int main(int argc, char** argv) {
         subcmd != "--viterbi" && subcmd != "--annotations-pipeline" && subcmd != "--codon-marginals" &&
         subcmd != "--codon-marginals-pipeline" && subcmd != "--events" && subcmd != "--events-pipeline" &&
         subcmd != "--ancestral-marginals" && subcmd != "--ancestral-marginals-pipeline" &&
-        subcmd != "--lineage-substitutions" && subcmd != "--lineage-substitutions-pipeline")
+        subcmd != "--lineage-substitutions" && subcmd != "--lineage-substitutions-pipeline" &&
+        subcmd != "--ancestral-probs" && subcmd != "--ancestral-probs-pipeline")
       throw std::invalid_argument("'" + subcmd + "' is not a valid subcommand.");
     const std::string yaml_path = a.one("yaml-path");
     const int cluster_ind = std::stoi(a.one("cluster-ind"));
@@ -152,7 +159,8 @@ int main(int argc, char** argv) {
       if (device_list.size() > 1 && (subcmd == "--marginals-pipeline" || subcmd == "--naive-probs-pipeline" ||
                                      subcmd == "--weighted-lineage-pipeline" || subcmd == "--annotations-pipeline" ||
                                      subcmd == "--codon-marginals-pipeline" || subcmd == "--events-pipeline" ||
-                                     subcmd == "--ancestral-marginals-pipeline" || subcmd == "--lineage-substitutions-pipeline"))
+                                     subcmd == "--ancestral-marginals-pipeline" || subcmd == "--lineage-substitutions-pipeline" ||
+                                     subcmd == "--ancestral-probs-pipeline"))
         throw std::invalid_argument(subcmd + " runs on one device: --devices may list only one");
       if (device_list.size() > 1 && subcmd != "--pipeline")
         std::fprintf(stderr, "linearham: %s evaluates on one device; of --devices only device %d is used\n", subcmd.c_str(),
@@ -212,6 +220,12 @@ int main(int argc, char** argv) {
                                                      std::stod(a.opt("burnin-frac", "0")));
       return EXIT_SUCCESS;
     }
+    if (subcmd == "--ancestral-probs-pipeline") {
+      phylo_hmm_ptr->RunAncestralProbsPipeline(a.one("input-path"), a.one("seed-seq"), linearham::ParseLineageNode(a.one("node")),
+                                               a.one("candidates"), a.one("output-path"), num_rates,
+                                               std::stod(a.opt("burnin-frac", "0")));
+      return EXIT_SUCCESS;
+    }
     if (subcmd == "--naive-probs-pipeline") {
       phylo_hmm_ptr->RunNaiveProbsPipeline(a.one("input-path"), a.one("output-path"), num_rates,
                                            std::stod(a.opt("burnin-frac", "0")), a.opt("candidates-path", ""),
@@ -237,6 +251,15 @@ int main(int argc, char** argv) {
     if (subcmd == "--asr") {
       phylo_hmm_ptr->RunAsr(a.one("input-path"), a.one("output-path"), (uint64_t)std::stoll(a.opt("seed", "0")));
       return EXIT_SUCCESS;
+    }
+    // --ancestral-probs: the node and the candidate file are refused before anything is evaluated
+    int probs_node = 0;
+    linearham::AncestralProbsTable probs;
+    if (subcmd == "--ancestral-probs") {
+      probs_node = linearham::ParseLineageNode(a.one("node"));
+      linearham::NamedCandidates c = linearham::ReadNamedCandidateFile(a.one("candidates"), (int)phylo_hmm_ptr->msa().cols());
+      probs.names = std::move(c.names);
+      probs.seqs = std::move(c.seqs);
     }
     phylo_hmm_ptr->InitializePhyloParameters(a.one("newick-path"), a.multi("er"), a.multi("pi"),
                                              std::stod(a.opt("alpha", "1.0")), num_rates);
@@ -279,6 +302,10 @@ int main(int argc, char** argv) {
         std::cout << "\n";
       }
       linearham::PhyloHMM::WriteRateTable(std::cout, m.rate_post.data(), L, m.num_rates);
+    } else if (subcmd == "--ancestral-probs") {
+      for (double x : phylo_hmm_ptr->AncestralCandidatePosterior(a.one("seed-seq"), probs_node, probs.seqs).log_cand)
+        probs.prob.push_back(std::exp(x));
+      linearham::WriteAncestralProbsTable(std::cout, probs);
     } else if (subcmd == "--lineage-substitutions") {
       const linearham::PhyloHMM::LineageSubstitutionsResult m = phylo_hmm_ptr->LineageSubstitutions(a.one("seed-seq"));
       const std::size_t L = (std::size_t)m.n_sites, P = m.nodes.size();

@@ -41,11 +41,6 @@ namespace lh {
 
 namespace {
 
-__device__ __forceinline__ double anc_aligned(double v, int d) {
-  for (int q = 0; q < d && v != 0.0; ++q) v *= kScaleThreshold;
-  return v;
-}
-
 // K11a
 __global__ void __launch_bounds__(256) site_base_kernel(int n, int L, size_t forward_size, const int32_t* __restrict__ off,
                                                         const int32_t* __restrict__ idx, const double* __restrict__ post,

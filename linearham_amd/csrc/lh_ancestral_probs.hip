@@ -1,0 +1,315 @@
+// K13: exact posterior probabilities of candidate ancestral sequences at a node of a seed's lineage (gfx950).
+//
+// What K3 draws and K7 counts for whole sequences, as probabilities.  For a tree sample t, a node v of the seed's path (the
+// seed's parent, slot 0, or the MRCA, the last slot) and a candidate x of L bytes (A, C, G, T, or 4 = the site is left open)
+//   P(X_v = x | data, t) = sum_paths prior(path) prod_j E_t[b_j, j] G_t[j][b_j][x_j] / P(data | t),
+// b_j the naive base the path writes on site j, E_t the xMSA emission of the evaluation and
+//   G_t[j][b][c] = P(x_{v,j} = c | column j, naive_j = b) = sum_r [lik_r(j, b) / Z_j(b)] P(x_{v,j} = c | column j, b, rate r),
+// G = 1 at an open site.  G is K11's marg for a one-hot naive distribution at b; it depends on the site only through its
+// pattern.  The sites of a node are coupled through the naive sequence, so the sum over paths does not factorise: every
+// (row, candidate) pair takes a forward sweep, K2a + K2b on the family's caller-column twin (K6a's) with the emissions
+// em'[col] = em[col] G[site(col)][base(col)][x[site(col)]].
+//
+// Kernels:
+//  * K11r, K3s and K11c (launch_ancestral_front) run in front: the path is checked against the sample's own schedule.
+//  * K13b (cond_kernel), a workgroup per (rate category, sample) as K11b, with K11b's LDS tables and upward pass; a lane
+//    per PATTERN in both passes, so a lane reads back only the CLVs it stored itself.  The joint P(x = c, column | b, r) is
+//    linear in the naive tip's vector: the down pass carries the message from above for the five basis vectors (A, C, G,
+//    T, N) at once, a 4 x 5 block, each column divided by its own largest entry after every step.  At the node the table
+//    is normalised per (basis, rate) and weighted by lik_r(j, b) / Z_j(b) from K1's unmixed planes (scaler counts aligned
+//    to the smallest, as K11r): part[sample][rate][pattern][5][4].  Z = 0, a dead category or an all-zero table gives 0.
+//    The all-N pattern takes K11's convention: likelihood pi_b under base b, sum pi under N, so the weight is 1 / R.
+//    The node is a template switch.  kMrca: no down step, the root's CLV stays in the lane's registers and the upward
+//    pass stores only what a later op pops from its stack.  Otherwise (the seed's parent): K11b's walk down the chain.
+//  * K13m (cond_combine_kernel), a thread per (sample, pattern, basis): the R partial tables added in rate order (K11m's
+//    rule: fixed order, no atomics); NaN for a sample without a valid path.  cond_sites_kernel spreads the patterns'
+//    tables over the sites for a caller who takes them: cond[n][L][5][4].
+//  * K13e (pair_emission_kernel), a thread per (pair, caller column) of a group of (row, candidate) pairs, pair q = row * K
+//    + candidate: the emissions above.  Rows without a path get 0 (row_mask_kernel does the same to the rows' own
+//    emissions), so the sweeps see what K6a's see; pair_finish_kernel turns the sweeps' log-likelihoods into
+//    log_cand = ll'(x) - ll'(open), the denominator being the twin's own sweep of the row's unmodified emissions: both
+//    terms share their arithmetic, and an all-open candidate gives exactly 0.
+// No private array is reached by a dynamic index: 4-vectors and the 4 x 5 block are indexed by unrolled loops only.
+#include <algorithm>
+
+#include "lh_device.h"
+
+namespace lh {
+
+namespace {
+
+template <bool kMrca>
+__global__ void __launch_bounds__(256) cond_kernel(int R, int T, int n_prune, int P, const uint8_t* __restrict__ msa,
+                                                   const AsrOp* __restrict__ desc, const double* __restrict__ brlen,
+                                                   const double* __restrict__ rates, const double* __restrict__ eig,
+                                                   const double* __restrict__ pi, const double* __restrict__ site_lik,
+                                                   const int32_t* __restrict__ site_scal, const int32_t* __restrict__ chain,
+                                                   const int32_t* __restrict__ plen, double2* clv, int Lp,
+                                                   double* __restrict__ part) {
+  extern __shared__ double2 cond_smem[];
+  const int n_ops = T - 2, NP = n_prune + 1;
+  const int sample = blockIdx.y, rate = blockIdx.x;
+  const int len = plen[sample];
+  if (len == 0) return;  // K13m writes the row's NaN
+  double* tiptab = reinterpret_cast<double*>(cond_smem);  // [T][4][4] columns of P
+  double* pin = tiptab + (size_t)T * 16;                  // [n_ops][4][4] row-major, by the op that produced the child
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int n_waves = blockDim.x >> 6;
+  const AsrOp* __restrict__ dsc = desc + (size_t)sample * n_ops;
+  const double rt = rates[(size_t)sample * R + rate];
+  anc_fill_tables(T, dsc, eig + (size_t)sample * 36, brlen + (size_t)sample * (2 * (size_t)T - 2), rt, tiptab, pin);
+  __syncthreads();
+
+  const size_t plane = (size_t)Lp;
+  double2* clv_s = clv + ((size_t)sample * R + rate) * n_ops * 2 * plane;
+  const double* __restrict__ p4 = pi + (size_t)sample * 4;
+  const int32_t* __restrict__ ch = chain + (size_t)sample * P;
+  double* part_s = part + ((size_t)sample * R + rate) * (size_t)NP * 20;
+  const int32_t* sc_s = site_scal + (size_t)sample * R * n_prune;
+  const double* lk_s = site_lik + (size_t)sample * R * 5 * n_prune;
+
+  for (int s0 = wave * 64; s0 < NP; s0 += n_waves * 64) {
+    const bool live = s0 + lane < NP;
+    const int pat = min(s0 + lane, NP - 1);
+    const bool all_n = pat >= n_prune;
+    double node[4];  // the node's CLV
+    anc_upward_pattern<!kMrca>(n_ops, n_prune, pat, msa, dsc, tiptab, pin, clv_s, plane, node);
+
+    // the weight of this category under each naive base
+    double w[5];
+    if (all_n) {
+#pragma unroll
+      for (int b = 0; b < 5; ++b) w[b] = 1.0 / (double)R;
+    } else {
+      const int32_t* sc = sc_s + pat;
+      const double* lk = lk_s + pat;
+      int smin = 0x7fffffff;
+      for (int k = 0; k < R; ++k) smin = min(smin, sc[(size_t)k * n_prune]);
+      double z[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+      for (int k = 0; k < R; ++k) {
+        const int d = sc[(size_t)k * n_prune] - smin;
+#pragma unroll
+        for (int b = 0; b < 5; ++b) z[b] += anc_aligned(lk[((size_t)k * 5 + b) * n_prune], d);
+      }
+      const int d = sc[(size_t)rate * n_prune] - smin;
+#pragma unroll
+      for (int b = 0; b < 5; ++b) {
+        const double v = anc_aligned(lk[((size_t)rate * 5 + b) * n_prune], d);
+        w[b] = (z[b] == 0.0 || v == 0.0) ? 0.0 : v / z[b];
+      }
+    }
+
+    // the message into the root from above, per basis vector of the naive tip
+    double A[5][4];
+    {
+      double n4[4];
+      anc_tip_col(tiptab, 0, 4, n4);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+#pragma unroll
+        for (int b = 0; b < 4; ++b) A[b][i] = p4[i] * tiptab[b * 4 + i];
+        A[4][i] = p4[i] * n4[i];
+      }
+    }
+    if (!kMrca) {
+      const double2* cbase = clv_s + pat;
+      for (int s = len - 1; s >= 1; --s) {
+        // the message into v_{s-1}: the sibling off the path times the message from above, through v_{s-1}'s branch
+        const int word = ch[s];
+        const int k = word & 0x3fffffff;
+        const int4 da = dsc[k].a, db = dsc[k].b;
+        const int kind = da.x & 15;
+        const bool via_pop = (word >> 30) != 0;
+        double m[4];
+        int kc = k - 1;  // the op that produced v_{s-1}
+        if (kind == OP_TIP_ACC) {
+          const int sa = all_n ? 4 : (int)msa[(size_t)da.y * n_prune + pat];
+          anc_tip_col(tiptab, db.x, sa, m);
+        } else {
+          const int kw = via_pop ? k - 1 : da.w;  // the op that produced the sibling
+          kc = via_pop ? da.w : k - 1;
+          const double2* cw = cbase + (size_t)kw * 2 * plane;
+          const double2 wlo = cw[0], whi = cw[plane];
+          const double y[4] = {wlo.x, wlo.y, whi.x, whi.y};
+          anc_matvec(pin + (size_t)kw * 16, y, m);
+        }
+#pragma unroll
+        for (int b = 0; b < 5; ++b) {
+          double M[4];
+#pragma unroll
+          for (int i = 0; i < 4; ++i) M[i] = A[b][i] * m[i];
+          anc_vecmat(pin + (size_t)kc * 16, M, A[b]);
+          const double top = fmax(fmax(A[b][0], A[b][1]), fmax(A[b][2], A[b][3]));
+          if (top > 0.0 && top < INFINITY) {
+            const double inv = 1.0 / top;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) A[b][i] *= inv;
+          }
+        }
+      }
+      const double2* cv = cbase + (size_t)(ch[0] & 0x3fffffff) * 2 * plane;
+      const double2 lo = cv[0], hi = cv[plane];
+      node[0] = lo.x;
+      node[1] = lo.y;
+      node[2] = hi.x;
+      node[3] = hi.y;
+    }
+    if (live) {
+      double2* o = reinterpret_cast<double2*>(part_s + (size_t)pat * 20);
+#pragma unroll
+      for (int b = 0; b < 5; ++b) {
+        const double post[4] = {A[b][0] * node[0], A[b][1] * node[1], A[b][2] * node[2], A[b][3] * node[3]};
+        const double sum = (post[0] + post[1]) + (post[2] + post[3]);
+        // a category of weight 0 or an all-zero table contributes 0, not NaN
+        const double f = (sum == 0.0 || w[b] == 0.0) ? 0.0 : w[b] / sum;
+        o[2 * b] = make_double2(f == 0.0 ? 0.0 : f * post[0], f == 0.0 ? 0.0 : f * post[1]);
+        o[2 * b + 1] = make_double2(f == 0.0 ? 0.0 : f * post[2], f == 0.0 ? 0.0 : f * post[3]);
+      }
+    }
+  }
+}
+
+// K13m
+__global__ void __launch_bounds__(256) cond_combine_kernel(int n, int R, int NP, const int32_t* __restrict__ plen,
+                                                           const double* __restrict__ part, double* __restrict__ table) {
+  const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long long per = (long long)NP * 5;
+  if (gid >= (long long)n * per) return;
+  const int sample = (int)(gid / per);
+  const long long cell = gid - (long long)sample * per;  // pattern * 5 + basis
+  double2 lo = make_double2(0.0, 0.0), hi = lo;
+  if (plen[sample] == 0) {
+    lo = hi = make_double2(__builtin_nan(""), __builtin_nan(""));
+  } else {
+    for (int k = 0; k < R; ++k) {
+      const double2* p = reinterpret_cast<const double2*>(part + (((size_t)sample * R + k) * per + cell) * 4);
+      const double2 a = p[0], b = p[1];
+      lo.x += a.x;
+      lo.y += a.y;
+      hi.x += b.x;
+      hi.y += b.y;
+    }
+  }
+  double2* o = reinterpret_cast<double2*>(table + (size_t)gid * 4);
+  o[0] = lo;
+  o[1] = hi;
+}
+
+__global__ void __launch_bounds__(256) cond_sites_kernel(int n, int L, int n_prune, const int32_t* __restrict__ site_pat,
+                                                         const double* __restrict__ table, double* __restrict__ cond) {
+  const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long long per = (long long)L * 5;
+  if (gid >= (long long)n * per) return;
+  const int sample = (int)(gid / per);
+  const long long cell = gid - (long long)sample * per;
+  const int site = (int)(cell / 5), b = (int)(cell - (long long)site * 5);
+  const int pat = min(site_pat[site], n_prune);
+  const double2* t = reinterpret_cast<const double2*>(table + (((size_t)sample * (n_prune + 1) + pat) * 5 + b) * 4);
+  double2* o = reinterpret_cast<double2*>(cond + (size_t)gid * 4);
+  o[0] = t[0];
+  o[1] = t[1];
+}
+
+__global__ void __launch_bounds__(256) row_mask_kernel(int n, int C, const int32_t* __restrict__ plen, double* __restrict__ em) {
+  const size_t total = (size_t)n * C;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256)
+    if (plen[i / C] == 0) em[i] = 0.0;
+}
+
+// K13e
+__global__ void __launch_bounds__(256) pair_emission_kernel(int K, int L, int C, int n_prune, long long q0, int count,
+                                                            const uint8_t* __restrict__ seqs,
+                                                            const int32_t* __restrict__ col_site,
+                                                            const uint8_t* __restrict__ col_base,
+                                                            const int32_t* __restrict__ site_pat,
+                                                            const int32_t* __restrict__ plen, const double* __restrict__ em,
+                                                            const double* __restrict__ table, double* __restrict__ out) {
+  const size_t total = (size_t)count * C;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+    const size_t p = i / C, c = i - p * C;
+    const long long q = q0 + (long long)p;
+    const size_t row = (size_t)(q / K), k = (size_t)(q - (long long)row * K);
+    const int site = col_site[c];
+    const int x = seqs[k * L + site];
+    double v = 0.0;
+    if (plen[row] != 0) {
+      v = em[row * C + c];
+      if (x < 4) v *= table[((row * (size_t)(n_prune + 1) + min(site_pat[site], n_prune)) * 5 + col_base[c]) * 4 + x];
+    }
+    out[i] = v;
+  }
+}
+
+__global__ void __launch_bounds__(256) pair_finish_kernel(int K, long long q0, int count, const double* __restrict__ pair_ll,
+                                                          const double* __restrict__ open_ll, const int32_t* __restrict__ plen,
+                                                          double* log_cand, double* prob) {
+  const int p = blockIdx.x * 256 + threadIdx.x;
+  if (p >= count) return;
+  const long long q = q0 + p;
+  const size_t row = (size_t)(q / K);
+  const double den = open_ll[row];
+  const double v = (plen[row] == 0 || !isfinite(den)) ? __builtin_nan("") : pair_ll[p] - den;
+  if (log_cand) log_cand[q] = v;
+  if (prob) prob[q] = exp(v);
+}
+
+unsigned strided_blocks(size_t total) { return (unsigned)std::min<size_t>((total + 255) / 256, 8192); }
+
+}  // namespace
+
+CondWsBytes cond_ws_bytes(int R, int n_prune) {
+  return {sizeof(double) * (size_t)R * (n_prune + 1) * 20, sizeof(double) * (size_t)(n_prune + 1) * 20};
+}
+
+int launch_ancestral_cond(const DevFamily& fam, int n, int R, int T, const int32_t* ops, const double* brlen,
+                          const double* rates, const double* eig, const double* pi, const double* site_lik,
+                          const int32_t* site_scal, const double* naive_prob, const int32_t* path, int P, int node,
+                          const AncWs& ws, double* table, double* cond, const int4* hdr, int32_t* err_flag,
+                          hipStream_t stream) {
+  const int L = fam.n_sites, NP = fam.n_prune + 1;
+  if (n < 1 || n > 65535 || L < 1 || P < 1 || node < 0 || node > 1) return 1;  // (one grid row per sample)
+  const size_t lds = anc_lds_bytes(T);
+  if (lds > 160 * 1024) return 1;
+  launch_ancestral_front(fam, n, R, T, ops, pi, site_lik, site_scal, naive_prob, path, P, ws, nullptr, hdr, err_flag, stream);
+  auto run = [&](auto kernel) {
+    if (lds > 64 * 1024)
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(kernel, dim3(R, n), dim3(256), lds, stream, R, T, fam.n_prune, P, fam.msa,
+                       static_cast<const AsrOp*>(ws.desc), brlen, rates, eig, pi, site_lik, site_scal, ws.chain, ws.plen,
+                       reinterpret_cast<double2*>(ws.clv), (int)anc_lp(fam.n_prune), ws.part);
+  };
+  if (node == 1)
+    run(cond_kernel<true>);
+  else
+    run(cond_kernel<false>);
+  const long long cells = (long long)n * NP * 5;
+  hipLaunchKernelGGL(cond_combine_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, stream, n, R, NP, ws.plen,
+                     ws.part, table);
+  if (cond) {
+    const long long out = (long long)n * L * 5;
+    hipLaunchKernelGGL(cond_sites_kernel, dim3((unsigned)((out + 255) / 256)), dim3(256), 0, stream, n, L, fam.n_prune,
+                       fam.site_pat, table, cond);
+  }
+  return 0;
+}
+
+void launch_row_mask(int n, int C, const int32_t* plen, double* em, hipStream_t stream) {
+  hipLaunchKernelGGL(row_mask_kernel, dim3(strided_blocks((size_t)n * C)), dim3(256), 0, stream, n, C, plen, em);
+}
+
+void launch_pair_emissions(const DevFamily& fam, int K, long long q0, int count, const uint8_t* seqs, const int32_t* col_site,
+                           const uint8_t* col_base, const int32_t* plen, const double* em, const double* table, double* out,
+                           hipStream_t stream) {
+  hipLaunchKernelGGL(pair_emission_kernel, dim3(strided_blocks((size_t)count * fam.n_xmsa)), dim3(256), 0, stream, K,
+                     fam.n_sites, fam.n_xmsa, fam.n_prune, q0, count, seqs, col_site, col_base, fam.site_pat, plen, em, table,
+                     out);
+}
+
+void launch_pair_finish(int K, long long q0, int count, const double* pair_ll, const double* open_ll, const int32_t* plen,
+                        double* log_cand, double* prob, hipStream_t stream) {
+  hipLaunchKernelGGL(pair_finish_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, stream, K, q0, count, pair_ll,
+                     open_ll, plen, log_cand, prob);
+}
+
+}  // namespace lh

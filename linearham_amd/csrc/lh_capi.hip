@@ -41,6 +41,7 @@ const DebugOptions& debug_options() {
     o.events_blocks = std::max(1, num("LH_EVENTS_BLOCKS", o.events_blocks));
     o.anc_out_mb = std::max(1, num("LH_ANC_OUT_MB", o.anc_out_mb));
     o.edge_out_mb = std::max(1, num("LH_EDGE_OUT_MB", o.edge_out_mb));
+    o.anc_pairs = std::max(0, num("LH_ANC_PAIRS", o.anc_pairs));
     o.collect_hash_bits = std::min(64, std::max(1, num("LH_COLLECT_HASH_BITS", o.collect_hash_bits)));
     return o;
   }();
@@ -240,6 +241,16 @@ struct EdgesWs {  // K12's scratch beside K11's (lh::SubWs) and the outputs its 
   DevBuf partial_c, partial_s, partial_n;  // the weighted reduction's slabs
 };
 
+struct AncProbsWs {  // K13 (lh_ancestral_probs.hip)
+  int32_t K = 0;               // 0: lh_family_set_ancestral_candidates has not been called (or its last call failed)
+  DevBuf seqs;                 // [K][L]
+  DevBuf part, table;          // K13b's partial tables and K13m's tables of a launch group
+  DevBuf em;                   // the group's emissions in caller columns, K2a's em_out
+  DevBuf pair_em, pair_ll, open_ll;  // a group of pairs: its emissions and sweeps; the rows' own sweeps
+  DevBuf prob, partial;        // exp(log_cand) of the batch and the weighted reduction's slabs
+  DevBuf out_cond, out_log_cand, out_wsum;  // the host-pointer form's device copies
+};
+
 struct PosteriorWs {  // K5's arrays that the caller of lh_eval_posterior_batch_device does not hand in
   DevBuf loglik, weights, stats, partial;
 };
@@ -417,6 +428,7 @@ struct lh_family {
   LineageWs lineage;
   AncestralWs anc;
   EdgesWs edges;
+  AncProbsWs probs;
   // forward arrays that stay on the device, shared by K4 and K5 in both their forms: K4 draws from them, K5 overwrites
   // them with the posteriors (calls on a handle do not overlap: they also share the workspace)
   DevBuf forward_dev;
@@ -436,6 +448,8 @@ struct lh_family {
   KernelTimer<1> lineage_timer;             // K7
   KernelTimer<3> anc_timer;                 // K11: K11a, K11b (with K11r, K11c, K11m), the weighted reduction
   KernelTimer<3> edges_timer;               // K12: K11a, K12b (with K11r, K11c, K12c, K12m), the weighted reduction
+  KernelTimer<3> probs_timer;               // K13's skeleton: K11a, K13b + K13e with their sweeps, the weighted reduction
+  KernelTimer<2> probs_stage_timer;         // inside its second stage: the tables (K11r, K11c, K13b, K13m), the pairs (K13e, K2)
   KernelTimer<5> chain_timer;               // lh_eval_lineage_batch: K0, K1, K2 + K4 + K6c, K3, K7
   bool extended = false;  // lh_family_set_extended_range
   bool have_sampler = false;
@@ -2255,6 +2269,7 @@ struct LineageCall {
   std::vector<RowOut> rows;
   const double* log_offset = nullptr;  // the eval forms' (lh_posterior_outputs' members)
   double *loglik = nullptr, *weight_stats = nullptr;
+  double* em_out = nullptr;  // the eval forms': a launch group's emissions in caller columns, [chunk][n_xmsa] (null: not formed)
   bool asked() const {
     return loglik || weight_stats || std::any_of(rows.begin(), rows.end(), [](const RowOut& r) { return r.p || r.sum; });
   }
@@ -2333,7 +2348,7 @@ int lineage_eval_device(lh_family* f, const std::string& W, const TreeBatch& b, 
     lh::launch_model_setup(m, R, g.er, g.pi, g.model, rates, eig, stream);
     int planes = 0;
     if (prune_group(f, W, g, rates, false, stream, &planes)) return 1;
-    if (run_forward(f, m, planes, site_lik, site_scal, g.pi, nullptr, nullptr, ll + off, &fwd_outs, off, stream)) return 1;
+    if (run_forward(f, m, planes, site_lik, site_scal, g.pi, nullptr, c.em_out, ll + off, &fwd_outs, off, stream)) return 1;
     lh::launch_posterior(f->sampler_dev, m, fwd + (size_t)off * FS, FS, ll + off, stream);
     if (f->profile && t.begin(stream)) return 1;
     lh::launch_site_base(m, (int)L, FS, a.sb_off.get<const int32_t>(), a.sb_idx.get<const int32_t>(), fwd + (size_t)off * FS,
@@ -2531,6 +2546,119 @@ LineageCall edges_call(lh_family* f, int P, int R, const double* naive_prob, con
   return edges_call(f, P, R, naive_prob, path, seed_tip, o);
 }
 
+// ---- K13: exact posterior probabilities of candidate ancestral sequences (lh_ancestral_probs.hip) ----
+
+// K13's per-row outputs; the rows' exp(log_cand) are formed only for weighted_sum
+enum { kCond = 1, kLogCand, kCandProb };
+std::vector<RowOut> probs_rows(lh_family* f, const lh_ancestral_candidates_outputs& o) {
+  AncestralWs& a = f->anc;
+  AncProbsWs& p = f->probs;
+  const size_t L = f->host.n_sites, K = p.K;
+  return {{nullptr, L * 5, nullptr, &a.site_base},
+          {o.cond, L * 20, &p.out_cond, nullptr},
+          {o.log_cand, K, &p.out_log_cand, nullptr},
+          {nullptr, K, nullptr, &p.prob, false, o.weighted_sum, &p.partial, &p.out_wsum}};
+}
+
+LineageCall probs_call(lh_family* f, int P, const int32_t* path, const lh_ancestral_candidates_outputs* outs) {
+  const lh_ancestral_candidates_outputs o = outs ? *outs : lh_ancestral_candidates_outputs{};
+  return {nullptr, path, P, 0, probs_rows(f, o), o.log_offset, o.loglik, o.weight_stats};
+}
+
+int probs_check(const lh_family* f, const std::string& W, const TreeBatch& b, int P, int node) {
+  if (ancestral_check(f, W, b, P)) return 1;
+  if (node != 0 && node != 1) return fail(W + ": node must be 0 (the seed's parent) or 1 (the MRCA)");
+  if (f->probs.K == 0) return fail(W + ": lh_family_set_ancestral_candidates has not been called");
+  if (f->extended)
+    return fail(W + ": not available on a handle in the extended-range mode: the candidates' sweeps run on plain doubles, and the "
+                    "emissions they start from underflow exactly where that mode is needed");
+  return 0;
+}
+
+// samples per launch group of K13, by memory as ancestral_group: K11's scratch with K13b's partials in place of K11b's, the
+// tables and the rows' emissions
+size_t probs_group(const lh_family* f, int T, int R, int P) {
+  const lh::AncWsBytes z = lh::anc_ws_bytes(T, f->host.n_sites, R, f->host.n_prune, P);
+  const lh::CondWsBytes y = lh::cond_ws_bytes(R, f->host.n_prune);
+  const size_t per = z.total() - z.part + y.part + y.table + sizeof(double) * (size_t)f->host.n_xmsa + lh::asr_desc_bytes(T) +
+                     eval_bytes_per_sample(f, T, R);
+  return std::max<size_t>(1, std::min<size_t>({(size_t)kChunk, (size_t)8192, ((size_t)8 << 30) / per}));
+}
+
+// (row, candidate) pairs per sweep: 256 MiB of emissions, C doubles a pair, at most 32 768 pairs (LH_ANC_PAIRS: test hook)
+size_t probs_pairs(const lh_family* f, size_t chunk) {
+  const size_t hook = lh::debug_options().anc_pairs;
+  const size_t by_memory = std::max<size_t>(1, ((size_t)256 << 20) / (sizeof(double) * (size_t)f->host.n_xmsa));
+  return std::min<size_t>(hook ? hook : std::min<size_t>(by_memory, 32768), chunk * (size_t)f->probs.K);
+}
+
+int probs_workspace(lh_family* f, int chunk, int T, int R, int P, size_t pairs, bool sweeps, lh::AncWs* ws) {
+  AncestralWs& a = f->anc;
+  AncProbsWs& p = f->probs;
+  const lh::AncWsBytes z = lh::anc_ws_bytes(T, f->host.n_sites, R, f->host.n_prune, P);
+  const lh::CondWsBytes y = lh::cond_ws_bytes(R, f->host.n_prune);
+  const size_t m = chunk, C = f->host.n_xmsa;
+  if (a.clv.ensure(z.clv * m) || a.tvec.ensure(z.tvec * m) || a.rho.ensure(z.rho * m) || a.chain.ensure(z.chain * m) ||
+      a.plen.ensure(sizeof(int32_t) * m) || a.desc.ensure(lh::asr_desc_bytes(T) * m) || p.part.ensure(y.part * m) ||
+      p.table.ensure(y.table * m) ||
+      (sweeps && (p.em.ensure(sizeof(double) * C * m) || p.open_ll.ensure(sizeof(double) * m) ||
+                  p.pair_em.ensure(sizeof(double) * C * pairs) || p.pair_ll.ensure(sizeof(double) * pairs))))
+    return 1;
+  *ws = {a.clv.get<double>(), p.part.get<double>(), a.tvec.get<double>(), a.rho.get<double>(), a.chain.get<int32_t>(),
+         a.plen.get<int32_t>(), a.desc.get()};
+  return 0;
+}
+
+// K13b on a launch group, then (sweeps) the twin's sweep of the rows' own emissions and, `pairs` pairs at a time, K13e, the
+// twin's sweep and the pairs' log_cand
+auto probs_launch(lh_family* f, const LineageCall& c, int node, size_t pairs, bool sweeps) {
+  return [f, &c, node, pairs, sweeps](const TreeBatch& g, size_t off, const double* rates, const double* naive_prob,
+                                      const lh::AncWs& ws, hipStream_t stream) -> int {
+    Workspace& w = f->ws;
+    AncProbsWs& p = f->probs;
+    CandidateWs& cw = f->cand;
+    KernelTimer<2>& t = f->probs_stage_timer;
+    if (f->profile && t.begin(stream)) return 1;
+    if (lh::launch_ancestral_cond(f->host, g.n, g.R, g.T, g.ops, g.brlen, rates, w.eig.get<double>(), g.pi,
+                                  w.site_lik.get<double>(), w.site_scal.get<int32_t>(), naive_prob, c.path + off * c.P, c.P, node,
+                                  ws, p.table.get<double>(), c.rows[kCond].group(off), w.prune.hdr, f->err_flag, stream))
+      return 1;
+    if (f->profile && t.mark(1, stream)) return 1;
+    if (sweeps) {
+      const int K = p.K;
+      double *pair_em = p.pair_em.get<double>(), *pair_ll = p.pair_ll.get<double>(), *open_ll = p.open_ll.get<double>();
+      lh::launch_row_mask(g.n, f->host.n_xmsa, ws.plen, c.em_out, stream);
+      if (run_forward(cw.twin, g.n, 1, nullptr, nullptr, nullptr, c.em_out, nullptr, open_ll, nullptr, 0, stream)) return 1;
+      const long long total = (long long)g.n * K;
+      for (long long q0 = 0; q0 < total; q0 += (long long)pairs) {
+        const int count = (int)std::min<long long>((long long)pairs, total - q0);
+        lh::launch_pair_emissions(f->host, K, q0, count, p.seqs.get<const uint8_t>(), cw.col_site, cw.col_base, ws.plen, c.em_out,
+                                  p.table.get<const double>(), pair_em, stream);
+        if (run_forward(cw.twin, count, 1, nullptr, nullptr, nullptr, pair_em, nullptr, pair_ll, nullptr, 0, stream)) return 1;
+        lh::launch_pair_finish(K, q0, count, pair_ll, open_ll, ws.plen, c.rows[kLogCand].group(off),
+                               c.rows[kCandProb].group(off), stream);
+      }
+    }
+    if (f->profile && t.end(stream)) return 1;
+    return 0;
+  };
+}
+
+int eval_probs_device(lh_family* f, const std::string& W, const TreeBatch& b, LineageCall& c, int node, void* hip_stream) {
+  if (ancestral_table(f, W)) return 1;
+  AncProbsWs& p = f->probs;
+  const bool sweeps = c.rows[kLogCand].wanted() || c.rows[kCandProb].wanted();
+  const int chunk = (int)std::min<size_t>(b.n, std::min(probs_group(f, b.T, b.R, c.P), eval_group(f, b.T, b.R)));
+  const size_t pairs = probs_pairs(f, chunk);
+  lh::AncWs ws;
+  if (ensure_workspace(f, chunk, b.R, b.T) || probs_workspace(f, chunk, b.T, b.R, c.P, pairs, sweeps, &ws)) return 1;
+  c.em_out = sweeps ? p.em.get<double>() : nullptr;
+  // K11c checks the paths wherever a table is formed
+  const bool tables = sweeps || c.rows[kCond].wanted();
+  return lineage_eval_device(f, W, b, c, chunk, ws, &lh_family::probs_timer, tables, -1, -1, hip_stream,
+                             probs_launch(f, c, node, pairs, sweeps));
+}
+
 }  // namespace
 
 extern "C" {
@@ -2658,6 +2786,78 @@ int lh_eval_edges_batch(lh_family* f, int32_t n, int32_t T, int32_t max_depth, c
 
 int lh_edges_profile_read(lh_family* f, double* ms, int64_t* n_launches) {
   return profile_read(f, &lh_family::edges_timer, ms, n_launches);
+}
+
+int lh_family_set_ancestral_candidates(lh_family* f, int32_t K, const uint8_t* seqs) {
+  const std::string W = "lh_family_set_ancestral_candidates";
+  if (!f) return fail(W + ": null family");
+  DeviceGuard guard(f);
+  AncProbsWs& p = f->probs;
+  p.K = 0;  // a call that fails leaves no candidates
+  if (f->host.n_seqs < 1) return fail(W + ": family was created without an MSA (forward-only)");
+  if (!f->cand.twin) return fail(W + ": no constrained forward sweep for this family: " + f->cand.twin_error);
+  if (K < 1 || K > 65536) return fail(W + ": K must be 1 .. 65536 candidates");
+  if (!seqs) return fail(W + ": null array");
+  const size_t L = f->host.n_sites;
+  for (size_t i = 0; i < (size_t)K * L; ++i)
+    if (seqs[i] > 4)
+      return fail(W + ": candidate " + std::to_string(i / L) + ", site " + std::to_string(i % L) + ": base " +
+                  std::to_string(seqs[i]) + " is not one of A,C,G,T = 0..3 or 4 (the site is left open)");
+  if (p.seqs.ensure((size_t)K * L) || stage_inputs(f, {{seqs, (size_t)K * L, &p.seqs}})) return 1;
+  LH_HIP(hipDeviceSynchronize());
+  p.K = K;
+  return 0;
+}
+
+int lh_ancestral_candidates_info(const lh_family* f, int32_t* n_candidates, int32_t* n_sites) {
+  if (!f) return fail("lh_ancestral_candidates_info: null family");
+  if (n_candidates) *n_candidates = f->probs.K;
+  if (n_sites) *n_sites = f->host.n_sites;
+  return 0;
+}
+
+int lh_eval_ancestral_candidates_batch_device(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops,
+                                              const double* brlen, const double* er, const double* pi, const double* alpha,
+                                              int32_t R, const int32_t* path, int32_t P, int32_t node,
+                                              const lh_ancestral_candidates_outputs* outs, void* hip_stream) {
+  const TreeBatch b{n, T, max_depth, ops, brlen, er, pi, alpha, R};
+  const std::string W = "lh_eval_ancestral_candidates_batch";
+  if (int rc = check_batch(f, W, b, true)) return rc > 0;
+  if (probs_check(f, W, b, P, node)) return 1;
+  DeviceGuard guard(f);
+  if (!b.has_arrays() || !path) return fail(W + ": null array");
+  LineageCall c = probs_call(f, P, path, outs);
+  return eval_probs_device(f, W, b, c, node, hip_stream);
+}
+
+int lh_eval_ancestral_candidates_batch(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops,
+                                       const double* brlen, const double* er, const double* pi, const double* alpha, int32_t R,
+                                       const int32_t* path, int32_t P, int32_t node,
+                                       const lh_ancestral_candidates_outputs* outs) {
+  const TreeBatch host{n, T, max_depth, ops, brlen, er, pi, alpha, R};
+  const std::string W = "lh_eval_ancestral_candidates_batch";
+  if (int rc = check_batch(f, W, host, true)) return rc > 0;
+  if (probs_check(f, W, host, P, node)) return 1;
+  DeviceGuard guard(f);
+  if (!host.has_arrays() || !path) return fail(W + ": null array");
+  const LineageCall c = probs_call(f, P, path, outs);
+  if (!c.asked()) return 0;
+  if (refuse_oversize(W, n, c, lh::debug_options().anc_out_mb)) return 1;  // (K11's rule)
+  return lineage_batch(f, W, host, c, n,
+                       [&](const TreeBatch& dev, LineageCall d) { return eval_probs_device(f, W, dev, d, node, nullptr); });
+}
+
+int lh_ancestral_candidates_profile_read(lh_family* f, double* ms, int64_t* n_launches) {
+  double skeleton[3] = {}, stage[2] = {};
+  if (profile_read(f, &lh_family::probs_timer, skeleton, n_launches) ||
+      profile_read(f, &lh_family::probs_stage_timer, stage, nullptr))
+    return 1;
+  if (ms) {
+    ms[0] = stage[0];
+    ms[1] = stage[1];
+    ms[2] = skeleton[2];
+  }
+  return 0;
 }
 
 int lh_forward_batch(lh_family* f, int32_t n, const double* em, double* loglik, const lh_eval_outputs* outs) {

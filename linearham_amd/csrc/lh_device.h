@@ -460,7 +460,13 @@ void launch_ancestral_front(const DevFamily& fam, int n, int R, int T, const int
                             int P, const AncWs& ws, double* rate_post, const int4* hdr, int32_t* err_flag, hipStream_t stream);
 size_t anc_lp(int n_prune);  // patterns per CLV plane: n_prune + 1 rounded up to 8
 
-// What K11b and K12b share, inlined into each: the 4-vector helpers, the LDS tables and the upward pass.
+// What K11b, K12b and K13b share, inlined into each: the 4-vector helpers, the LDS tables and the upward pass.
+// a plane value whose scaler count lies d above the site's smallest, on that one's scale (K11r, K13b)
+__device__ static __forceinline__ double anc_aligned(double v, int d) {
+  for (int q = 0; q < d && v != 0.0; ++q) v *= kScaleThreshold;
+  return v;
+}
+
 __device__ static __forceinline__ void anc_tip_col(const double* tiptab, int tip, int st, double (&c)[4]) {
   const double* t = tiptab + tip * 16;
   if (st < 4) {
@@ -510,48 +516,60 @@ __device__ static __forceinline__ void anc_fill_tables(int T, const AsrOp* __res
   }
 }
 
-// K3b's upward pass over all NP = n_prune + 1 patterns (the all-N one last), a lane per pattern (lanes past the last
-// pattern repeat it: same values, no predicate); every inner CLV stored: clv_s[op][2][plane] double2, components (0,1) and
-// (2,3) of a pattern in two planes.
+// K3b's upward pass of one pattern (n_prune: the all-N one), the lane's: every inner CLV stored: clv_s[op][2][plane]
+// double2, components (0,1) and (2,3) of a pattern in two planes.  kStoreAll = false (K13b's MRCA form) stores only what a
+// later op pops from the stack, which the lane itself reads back.  `a` leaves as the root's CLV.
+template <bool kStoreAll = true>
+__device__ static __forceinline__ void anc_upward_pattern(int n_ops, int n_prune, int pat, const uint8_t* __restrict__ msa,
+                                                          const AsrOp* __restrict__ dsc, const double* tiptab,
+                                                          const double* pin, double2* clv_s, size_t plane, double (&a)[4]) {
+  const bool all_n = pat >= n_prune;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) a[q] = 1.0;
+  for (int k = 0; k < n_ops; ++k) {
+    const int4 da = dsc[k].a, db = dsc[k].b;
+    const int kind = da.x & 15;
+    double u[4], v[4];
+    if (kind == OP_CHERRY) {
+      const int sa = all_n ? 4 : (int)msa[(size_t)da.y * n_prune + pat];
+      const int sb = all_n ? 4 : (int)msa[(size_t)da.z * n_prune + pat];
+      anc_tip_col(tiptab, db.x, sa, u);
+      anc_tip_col(tiptab, db.y, sb, v);
+    } else {
+      anc_matvec(pin + (size_t)(k - 1) * 16, a, v);
+      if (kind == OP_TIP_ACC) {
+        const int sa = all_n ? 4 : (int)msa[(size_t)da.y * n_prune + pat];
+        anc_tip_col(tiptab, db.x, sa, u);
+      } else {
+        const double2* cq = clv_s + (size_t)da.w * 2 * plane + pat;
+        const double2 lo = cq[0], hi = cq[plane];
+        const double y[4] = {lo.x, lo.y, hi.x, hi.y};
+        anc_matvec(pin + (size_t)da.w * 16, y, u);
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) a[q] = u[q] * v[q];
+    if (fmax(fmax(a[0], a[1]), fmax(a[2], a[3])) < kScaleThreshold) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) a[q] *= kScaleFactor;
+    }
+    if (kStoreAll || (da.x >> 8) != 0) {
+      double2* ck = clv_s + (size_t)k * 2 * plane + pat;
+      ck[0] = make_double2(a[0], a[1]);
+      ck[plane] = make_double2(a[2], a[3]);
+    }
+  }
+}
+
+// The pass over all NP = n_prune + 1 patterns (the all-N one last), a lane per pattern (lanes past the last pattern repeat
+// it: same values, no predicate).
 __device__ static __forceinline__ void anc_upward(int n_ops, int n_prune, const uint8_t* __restrict__ msa,
                                                   const AsrOp* __restrict__ dsc, const double* tiptab, const double* pin,
                                                   double2* clv_s, size_t plane, int wave, int n_waves, int lane) {
   const int NP = n_prune + 1;
   for (int s0 = wave * 64; s0 < NP; s0 += n_waves * 64) {
-    const int pat = min(s0 + lane, NP - 1);
-    const bool all_n = pat >= n_prune;
-    double a[4] = {1.0, 1.0, 1.0, 1.0};
-    for (int k = 0; k < n_ops; ++k) {
-      const int4 da = dsc[k].a, db = dsc[k].b;
-      const int kind = da.x & 15;
-      double u[4], v[4];
-      if (kind == OP_CHERRY) {
-        const int sa = all_n ? 4 : (int)msa[(size_t)da.y * n_prune + pat];
-        const int sb = all_n ? 4 : (int)msa[(size_t)da.z * n_prune + pat];
-        anc_tip_col(tiptab, db.x, sa, u);
-        anc_tip_col(tiptab, db.y, sb, v);
-      } else {
-        anc_matvec(pin + (size_t)(k - 1) * 16, a, v);
-        if (kind == OP_TIP_ACC) {
-          const int sa = all_n ? 4 : (int)msa[(size_t)da.y * n_prune + pat];
-          anc_tip_col(tiptab, db.x, sa, u);
-        } else {
-          const double2* cq = clv_s + (size_t)da.w * 2 * plane + pat;
-          const double2 lo = cq[0], hi = cq[plane];
-          const double y[4] = {lo.x, lo.y, hi.x, hi.y};
-          anc_matvec(pin + (size_t)da.w * 16, y, u);
-        }
-      }
-#pragma unroll
-      for (int q = 0; q < 4; ++q) a[q] = u[q] * v[q];
-      if (fmax(fmax(a[0], a[1]), fmax(a[2], a[3])) < kScaleThreshold) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) a[q] *= kScaleFactor;
-      }
-      double2* ck = clv_s + (size_t)k * 2 * plane + pat;
-      ck[0] = make_double2(a[0], a[1]);
-      ck[plane] = make_double2(a[2], a[3]);
-    }
+    double a[4];
+    anc_upward_pattern<true>(n_ops, n_prune, min(s0 + lane, NP - 1), msa, dsc, tiptab, pin, clv_s, plane, a);
   }
 }
 
@@ -582,6 +600,33 @@ int launch_substitutions(const DevFamily& fam, int n, int R, int T, const int32_
                          const double* eig, const double* pi, const double* site_lik, const int32_t* site_scal,
                          const double* naive_prob, const int32_t* path, int P, int seed_tip, const AncWs& ws, const SubWs& sws,
                          const SubOut& out, const int4* hdr, int32_t* err_flag, hipStream_t stream);
+
+// K13 (lh_ancestral_probs.hip): exact posterior probabilities of candidate ancestral sequences at one node of a seed's
+// lineage, node 0 = the seed's parent (slot 0), 1 = the MRCA (the sample's last slot).
+// K13b + K13m behind launch_ancestral_front (which takes naive_prob for K11r; its tvec and rho are not read here): table
+// [n][n_prune + 1][5][4], P(x_node = c | column of the pattern, naive base b), NaN for a sample without a valid path (*err_flag
+// raised, ws.plen 0); cond[n][n_sites][5][4] (may be null) is the same table per site.  Scratch: AncWs with `part` sized by
+// cond_ws_bytes.  Returns nonzero if the launch cannot be made (LDS tables, grid).
+struct CondWsBytes {
+  size_t part, table;  // per sample
+};
+CondWsBytes cond_ws_bytes(int R, int n_prune);
+int launch_ancestral_cond(const DevFamily& fam, int n, int R, int T, const int32_t* ops, const double* brlen,
+                          const double* rates, const double* eig, const double* pi, const double* site_lik,
+                          const int32_t* site_scal, const double* naive_prob, const int32_t* path, int P, int node,
+                          const AncWs& ws, double* table, double* cond, const int4* hdr, int32_t* err_flag,
+                          hipStream_t stream);
+// em[n][C] = 0 in the rows whose plen is 0
+void launch_row_mask(int n, int C, const int32_t* plen, double* em, hipStream_t stream);
+// K13e for the pairs q0 .. q0 + count of a launch group, pair q = row * K + candidate: out[count][C] from the group's
+// emissions em[rows][C] (caller columns), its tables and path lengths, seqs[K][L] and K6a's column -> (site, base) map
+void launch_pair_emissions(const DevFamily& fam, int K, long long q0, int count, const uint8_t* seqs, const int32_t* col_site,
+                           const uint8_t* col_base, const int32_t* plen, const double* em, const double* table, double* out,
+                           hipStream_t stream);
+// log_cand[q] = pair_ll[q - q0] - open_ll[row], NaN where the row has no path or open_ll is not finite; prob[q] = exp of it
+// (either may be null)
+void launch_pair_finish(int K, long long q0, int count, const double* pair_ll, const double* open_ll, const int32_t* plen,
+                        double* log_cand, double* prob, hipStream_t stream);
 
 // K2a + K2b.  site_lik != null: emissions are assembled from K1's output (rate mix and naive
 // correction; optionally written to em_out[n][C]); site_lik == null: emissions are taken from
@@ -658,6 +703,8 @@ struct DebugOptions {
   int anc_out_mb = 4096;       // LH_ANC_OUT_MB=<n>: MiB of device copies of lh_eval_ancestral_batch's per-row outputs (host
                                // pointers) above which a batch is refused with the largest n (tests: the refusal on a small family)
   int edge_out_mb = 4096;      // LH_EDGE_OUT_MB=<n>: the same bound for lh_asr_edges_batch and lh_eval_edges_batch
+  int anc_pairs = 0;           // LH_ANC_PAIRS=<n>: (row, candidate) pairs per sweep of lh_eval_ancestral_candidates_batch (0,
+                               // unset: by memory; tests: a group cuts rows and candidates in a small call)
   int collect_hash_bits = 64;  // LH_COLLECT_HASH_BITS=<n>: K6c's row hashes masked to n bits (tests: collisions common,
                                // the exact resolution runs; results unchanged)
 };

@@ -106,6 +106,37 @@ def read_ancestral_marginals(prefix):
     return out
 
 
+def read_ancestral_probs(prefix):
+    """The files of PhyloHMM::RunAncestralProbsPipeline: dict(names, seqs, prob [K] in the file's (ranked) order, rows [(row,
+    weight, chain_length)], summary)."""
+    import numpy as np
+    lines = [ln.split("\t") for ln in open(prefix + ".probs.tsv").read().strip("\n").split("\n")]
+    assert lines[0] == ["name", "sequence", "probability"], lines[0]
+    rows = [ln.split("\t") for ln in open(prefix + ".rows.tsv").read().strip().split("\n")]
+    assert rows[0] == ["row", "weight", "chain_length"]
+    return dict(names=[c[0] for c in lines[1:]], seqs=[c[1] for c in lines[1:]], prob=np.array([float(c[2]) for c in lines[1:]]),
+                rows=[(int(r[0]), float(r[1]), int(r[2])) for r in rows[1:]],
+                summary=_parse_summary(open(prefix + ".summary.tsv").read()))
+
+
+def parse_lineage_node(name):
+    """--node's values: "parent" -> 0 (the seed's parent), "mrca" -> 1 (linearham::ParseLineageNode)."""
+    lib = load_host()
+    lib.lhh_parse_lineage_node.argtypes = [C.c_char_p, C.POINTER(C.c_int)]
+    node = C.c_int()
+    _check(lib.lhh_parse_lineage_node(name.encode(), C.byref(node)))
+    return node.value
+
+
+def read_named_candidates(path, n_sites):
+    """linearham::ReadNamedCandidateFile: [(name, sequence)] in file order."""
+    lib = load_host()
+    lib.lhh_read_named_candidates.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_char_p)]
+    out = C.c_char_p()
+    _check(lib.lhh_read_named_candidates(path.encode(), n_sites, C.byref(out)))
+    return [tuple(ln.split("\t")) for ln in out.value.decode().strip("\n").split("\n")]
+
+
 def read_lineage_substitutions(prefix):
     """The files of PhyloHMM::RunLineageSubstitutionsPipeline: dict(counts [L][4][4], substitutions [L] (the off-diagonal sum
     the file carries), seed_edge [L][4][4], naive_edge [L][5][4], rows [(row, weight, chain_length, expected_substitutions)],
@@ -497,6 +528,33 @@ class PhyloHMM(_HMM):
         _check(self.lib.lhh_run_ancestral_marginals_pipeline(self.h, input_path.encode(), seed_seq.encode(),
                                                              output_prefix.encode(), num_rates, C.c_double(burnin_frac)))
         return read_ancestral_marginals(output_prefix)
+
+    def ancestral_candidate_posterior(self, seed_seq, node, candidates):
+        """PhyloHMM::AncestralCandidatePosterior of the current tree: dict(log_cand [K], node, loglik) for candidate strings
+        over ACGTN (N leaves the site open) at node 0 / "parent" (the seed's parent) or 1 / "mrca"."""
+        if isinstance(node, str):
+            node = parse_lineage_node(node)
+        lib = self.lib
+        lib.lhh_phylo_ancestral_candidate_posterior.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_char_p, C.c_int, C.c_void_p,
+                                                                C.POINTER(C.c_int), C.POINTER(C.c_double)]
+        lc = np.zeros(len(candidates))
+        v, ll = C.c_int(), C.c_double()
+        _check(lib.lhh_phylo_ancestral_candidate_posterior(self.h, seed_seq.encode(), node, "\n".join(candidates).encode(),
+                                                           len(candidates), lc.ctypes.data, C.byref(v), C.byref(ll)))
+        return dict(log_cand=lc, node=v.value, loglik=ll.value)
+
+    def run_ancestral_probs_pipeline(self, input_path, seed_seq, node, candidates_path, output_prefix, num_rates,
+                                     burnin_frac=0.0):
+        """PhyloHMM::RunAncestralProbsPipeline: importance-weighted exact probabilities of the candidate sequences of a file
+        at the seed's parent or MRCA over a RevBayes table; returns read_ancestral_probs(output_prefix)."""
+        if isinstance(node, str):
+            node = parse_lineage_node(node)
+        self.lib.lhh_run_ancestral_probs_pipeline.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_int, C.c_char_p, C.c_char_p,
+                                                              C.c_int, C.c_double]
+        _check(self.lib.lhh_run_ancestral_probs_pipeline(self.h, input_path.encode(), seed_seq.encode(), node,
+                                                         candidates_path.encode(), output_prefix.encode(), num_rates,
+                                                         C.c_double(burnin_frac)))
+        return read_ancestral_probs(output_prefix)
 
     def lineage_substitutions(self, seed_seq):
         """PhyloHMM::LineageSubstitutions of the current tree: dict(nodes [P] -- the lineage of the tip `seed_seq`, slot 0 its
