@@ -163,6 +163,12 @@ const char* lh_family_prune_form(const lh_family* fam);
  * chunks of the V side and of the D / J sides.  Lives and changes like lh_family_prune_form's string. */
 const char* lh_family_forward_form(const lh_family* fam);
 
+/* Diagnostic: samples per wave of the D-J kernel in the handle's last forward sweep, where K2b ran in the pair form
+ * ("vd2<GA>+dj" / "vd<GA>+dj"): 4 (one DPP row of 16 lanes per sample: at most 32 D and 16 J alleles, and LDS for four
+ * emission slices per wave at the pair form's occupancy) or 2 (lanes 0-31 / 32-63); 0 for "junction<GA,GB>" and before
+ * the first sweep.  Both layouts compute the same bits. */
+int lh_family_forward_dj_samples(const lh_family* fam);
+
 /* Opt-in extended-range mode (default off = the reference's arithmetic, overflows included).  The reference
  * loses a tree sample in two places: exp(lnL - log pi) underflows to 0 when a column's likelihood is below
  * 1e-308 (src/PhyloHMM.cpp:237), and the 2^(256 d) equalisation of a region's emission products to the LARGEST

@@ -28,6 +28,7 @@ const DebugOptions& debug_options() {
     o.eval_fwd_priority = std::min(1, num("LH_EVAL_FWD_PRIORITY", o.eval_fwd_priority));
     o.k2b_no_pair = set("LH_K2B_NO_PAIR");
     o.k2b_vd_single = set("LH_K2B_VD_SINGLE");
+    o.k2b_dj_pair = set("LH_K2B_DJ_PAIR");
     o.sample_timing = set("LH_SAMPLE_TIMING");
     o.k1_tile_cap = num("LH_K1_TILE_CAP", 0);
     o.k1_cxx_walk = set("LH_K1_CXX_WALK");
@@ -459,6 +460,7 @@ struct lh_family {
   int32_t* err_flag = nullptr;  // device word (arena): K0c sets it when a schedule is malformed (lh_family_status)
   std::string k1_form;          // the K1 kernel form of the last evaluation (lh_family_prune_form)
   std::string k2_form;          // the K2 kernels of the last forward sweep (lh_family_forward_form)
+  int k2_dj_samples = 0;        // samples per wave of its D-J kernel (lh_family_forward_dj_samples)
 };
 
 namespace {
@@ -776,6 +778,7 @@ int run_forward(lh_family* f, int n, int R, const double* site_lik, const int32_
                      w.jrs.get<int32_t>() + row0 * jrows, w.dxf.get<double>() + row0 * 32, w.dxc.get<int32_t>() + row0, loglik_dev,
                      fwd, sco, f->extended, stream, lem);
   f->k2_form = lh::forward_last_form();
+  f->k2_dj_samples = lh::forward_last_dj_samples();
   LH_HIP(hipGetLastError());
   return 0;
 }
@@ -1399,6 +1402,7 @@ int64_t lh_forward_size(const lh_family* f) { return f ? f->host.forward_size : 
 const char* lh_family_prune_form(const lh_family* f) { return f ? f->k1_form.c_str() : ""; }
 
 const char* lh_family_forward_form(const lh_family* f) { return f ? f->k2_form.c_str() : ""; }
+int lh_family_forward_dj_samples(const lh_family* f) { return f ? f->k2_dj_samples : 0; }
 
 int lh_family_consensus_sets(const lh_family* f) {
   if (!f) return 0;

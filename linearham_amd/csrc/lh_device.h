@@ -655,6 +655,9 @@ size_t forward_lds_bytes(const DevFamily& fam);
 // the sets it runs in consensus form (bits as lh_family_consensus_sets), whether the small sets walk a wave each
 // (fill_segments_wave) or on the whole block, and K2b's kernels: vd2<GA>+dj, vd<GA>+dj or junction<GA,GB>
 const char* forward_last_form();
+// samples per wave of the D-J kernel that launch_forward ran: 4 (junction_dj4_kernel), 2 (junction_dj_kernel), 0 (K2b not
+// in the pair form)
+int forward_last_dj_samples();
 
 // K8 (lh_viterbi.hip): the most probable state path of each sample, from K2a's hand-off buffers as launch_forward has just
 // left them (gem, gcnt, jem, jrs) and the log-likelihoods K2b wrote.  states[n][states_per_sample] in K4's layout,
@@ -689,6 +692,7 @@ struct DebugOptions {
                                // the product's choice)
   bool k2b_no_pair = false;    // LH_K2B_NO_PAIR: K2b with one sample per wave
   bool k2b_vd_single = false;  // LH_K2B_VD_SINGLE: one sample per V-D wave
+  bool k2b_dj_pair = false;    // LH_K2B_DJ_PAIR: two samples per D-J wave (junction_dj_kernel) where four would run
   bool sample_timing = false;  // LH_SAMPLE_TIMING: stage times of every lh_eval_sample_batch call on stderr
   int k1_tile_cap = 0;         // LH_K1_TILE_CAP=<sites>: small K1 tiles, so that small families run the multi-tile path
   bool k1_cxx_walk = false;    // LH_K1_CXX_WALK: the cherry-table form with its C++ walk instead of the assembly one

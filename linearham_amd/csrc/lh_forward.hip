@@ -43,6 +43,7 @@ constexpr int kJunctionWaves = 4;  // samples per K2b workgroup
 
 // what the calling thread's last launch_forward ran (forward_last_form): the launchers below write the two halves
 thread_local char g_k2a_form[64] = "", g_k2b_form[32] = "", g_forward_form[160] = "";
+thread_local int g_k2b_dj_samples = 0;  // samples per wave of the pair form's D-J kernel (forward_last_dj_samples)
 
 // Block-wide maximum: shuffles inside the wave, one LDS exchange, one barrier (red holds
 // 2 * kFwdWaves ints; `phase` alternates its halves so that a reduction never overwrites values
@@ -1536,6 +1537,243 @@ __global__ void __launch_bounds__(64 * kPairWaves)
   if (valid && g == 0) loglik[s2] = log(part) - jcount * kLogScaleFactor;
 }
 
+// ---- four samples per wave on the D-J junction (at most 32 D and 16 J alleles) -----------------------------------
+// The right genes carry most of a row's arithmetic (five states per gene) and the pair form keeps 12 of a half's 32
+// lanes busy on them (configs[2]: 12 J genes).  The quad form gives a sample ONE DPP row: lane = 16 * (sample in
+// wave) + l, right gene l, left genes l and 16 + l (register slots q = 0, 1; GL = 1 for at most 16 D genes).  Per
+// sample the operations and their order are those of junction_pair:
+//   * half_sums adds the total of lanes 0-15 to that of lanes 16-31; here the same tree runs over the q = 0 products
+//     and over the q = 1 products (same positions in the row, same DPP controls), then T0 + T1 (+ 0.0 with GL = 1 and
+//     for the J genes, whose lanes 16-31 hold zeros in the pair form).  The first step of a tree over products is
+//     contracted into an fma whose addend is the NEIGHBOUR's rounded product, so the lanes of a row do not end on
+//     the same bits; the pair form reads lanes 0 and 16, and the quad form takes the sum its row's first lane formed
+//     (one more DPP move, row_newbcast:0), not its own.
+//   * minima and maxima are exact in any order: a lane's keys are combined over q, then one tree per row leaves the
+//     row's key in all sixteen lanes.
+//   * one compare of the row key against the rescaling threshold and a wave-level branch; inside it each lane derives
+//     its row's RowScale from the key it holds (a row that does not rescale multiplies by 1.0, as the other half of a
+//     pair does).
+constexpr int kDppRowFirst = 0x150;  // row_newbcast:0 -- every lane reads the first lane of its row of 16
+
+__device__ static inline double row_tree_sum(double v) {  // lane 0 of each row: what half_sums reads at lanes 0 / 16
+  v += dpp_move<kDppQuadSwap1>(v);
+  v += dpp_move<kDppQuadSwap2>(v);
+  v += dpp_move<kDppHalfMirror>(v);
+  v += dpp_move<kDppMirror>(v);
+  return v;
+}
+
+template <int GL>
+__device__ static inline double row_sums(const double (&p)[GL]) {
+  double t = row_tree_sum(p[0]);
+  if constexpr (GL == 2)
+    t = t + row_tree_sum(p[1]);
+  else
+    t = t + 0.0;  // the pair form's total of lanes 16-31 (not folded: -0.0 + 0.0 is +0.0)
+  return dpp_move<kDppRowFirst>(t);
+}
+
+// The row's scale key as row_scale takes it: the smallest scale_key, or (kExt) the largest high word less one.
+template <bool kExt>
+__device__ static inline unsigned row_key(unsigned v) {
+  if (kExt) {
+    v = dpp_max_u32<kDppQuadSwap1>(v);
+    v = dpp_max_u32<kDppQuadSwap2>(v);
+    v = dpp_max_u32<kDppHalfMirror>(v);
+    v = dpp_max_u32<kDppMirror>(v);
+    return v - 1u;
+  }
+  v = dpp_min_u32<kDppQuadSwap1>(v);
+  v = dpp_min_u32<kDppQuadSwap2>(v);
+  v = dpp_min_u32<kDppHalfMirror>(v);
+  v = dpp_min_u32<kDppMirror>(v);
+  return v;
+}
+
+// row_scale(key).k != 0 for every key below this one: the high word key + 1 is not zero and its exponent field is
+// below 767 (every entry is >= 0, see scale_key: no sign bit).
+constexpr unsigned kRescaleKeyEnd = (767u << 20) - 1u;
+
+// The D-J junction sweep and the hand-off into the J germline region for the four samples of a wave.  l = lane & 15;
+// every pointer is the lane's own sample's.  Returns the lane's sample's J scaler count; g_out = forward probability
+// of J gene l.
+template <int GL, bool kExt>
+__device__ static int junction_quad(const DevJunction& J, const double* jem, const double* ntt_lds, unsigned l,
+                                    const double (&f_in)[GL], int count_in, const double* __restrict__ germ_em,
+                                    const double* __restrict__ pad_trans, const double* __restrict__ pad_em,
+                                    double& g_out, double* __restrict__ fwd_out, int32_t* __restrict__ scal_out,
+                                    const int32_t* __restrict__ jrs, bool valid) {
+  const int W = J.n_rows, nL = J.n_left, nR = J.n_right;
+  int count = count_in;
+  double fL[GL], fR = 0.0, fN[4] = {0.0, 0.0, 0.0, 0.0}, nli[4];
+#pragma unroll
+  for (int q = 0; q < GL; ++q) fL[q] = f_in[q];
+  {
+    const double2* p = reinterpret_cast<const double2*>(J.right_gp_nli) + 2u * l;
+    const double2 a = p[0], b = p[1];
+    nli[0] = a.x, nli[1] = a.y, nli[2] = b.x, nli[3] = b.y;
+  }
+  const size_t row_stride = (size_t)nL + 5 * (size_t)nR;
+  double A;
+  {
+    double part[GL];
+#pragma unroll
+    for (int q = 0; q < GL; ++q) part[q] = f_in[q] * J.enter_lo[l + 16u * q];
+    A = row_sums<GL>(part);
+  }
+  for (int i = 0; i < W; ++i) {
+    const size_t ol = (size_t)i * J.left_pad, orr = (size_t)i * J.right_pad;
+    double ltr[GL], llo[GL];
+    int lidx[GL];
+#pragma unroll
+    for (int q = 0; q < GL; ++q) {
+      ltr[q] = J.left_trans[ol + l + 16u * q];
+      llo[q] = J.left_lo[ol + l + 16u * q];
+      lidx[q] = J.left_xmsa[ol + l + 16u * q];
+    }
+    const double2* pn = reinterpret_cast<const double2*>(J.right_nlo) + 2 * (orr + l);
+    const double2 n01 = pn[0], n23 = pn[1];
+    const int4 nx = reinterpret_cast<const int4*>(J.nti_xmsa)[orr + l];
+    const double rtr = J.right_trans[orr + l], rli = J.right_gp_li[orr + l];
+    const int ridx = J.right_xmsa[orr + l];
+
+    unsigned key = key_start<kExt>();
+    double part[GL];
+#pragma unroll
+    for (int q = 0; q < GL; ++q) {
+      const double v = (fL[q] * ltr[q]) * jem[lidx[q]];
+      fL[q] = v;
+      key = key_add<kExt>(key, v);
+      part[q] = fL[q] * llo[q];
+    }
+    const double n0 = fN[0], n1 = fN[1], n2 = fN[2], n3 = fN[3];
+    const double2* tt = reinterpret_cast<const double2*>(ntt_lds) + 8u * l;
+    const int nxs[4] = {nx.x, nx.y, nx.z, nx.w};
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      const double2 t01 = tt[2 * b], t23 = tt[2 * b + 1];
+      double sacc = ((n0 * t01.x + n1 * t01.y) + n2 * t23.x) + n3 * t23.y;
+      sacc += A * nli[b];
+      const double v = sacc * jem[nxs[b]];
+      fN[b] = v;
+      key = key_add<kExt>(key, v);
+    }
+    {
+      double sacc = ((n0 * n01.x + n1 * n01.y) + n2 * n23.x) + n3 * n23.y;
+      sacc += fR * rtr;
+      sacc += A * rli;
+      const double v = sacc * jem[ridx];
+      fR = v;
+      key = key_add<kExt>(key, v);
+    }
+    A = row_sums<GL>(part);
+    const unsigned rk = row_key<kExt>(key);
+    if constexpr (kExt) count += jrs[i];
+    if (__builtin_amdgcn_ballot_w64(rk < kRescaleKeyEnd) != 0) {  // some row of the wave rescales: a few rows per junction
+      const RowScale sc = row_scale(rk);  // per lane, equal across a row
+      A = sc.apply(A);
+#pragma unroll
+      for (int q = 0; q < GL; ++q) fL[q] = sc.apply(fL[q]);
+      fR = sc.apply(fR);
+#pragma unroll
+      for (int b = 0; b < 4; ++b) fN[b] = sc.apply(fN[b]);
+      count += sc.k;
+    }
+    if (fwd_out && valid) {
+      double* o = fwd_out + (size_t)i * row_stride;
+#pragma unroll
+      for (int q = 0; q < GL; ++q)
+        if ((int)(l + 16u * q) < nL) o[l + 16u * q] = fL[q];
+      if ((int)l < nR) {
+        o[nL + 4 * (size_t)l + 0] = fN[0];
+        o[nL + 4 * (size_t)l + 1] = fN[1];
+        o[nL + 4 * (size_t)l + 2] = fN[2];
+        o[nL + 4 * (size_t)l + 3] = fN[3];
+        o[nL + 4 * (size_t)nR + l] = fR;
+      }
+    }
+    if (scal_out && valid && l == 0) scal_out[i] = count;
+  }
+  unsigned key = key_start<kExt>();
+  {
+    const double2* xn = reinterpret_cast<const double2*>(J.exit_nlo) + 2u * l;
+    const double2 x01 = xn[0], x23 = xn[1];
+    double sacc = ((fN[0] * x01.x + fN[1] * x01.y) + fN[2] * x23.x) + fN[3] * x23.y;
+    sacc += fR * J.exit_trans[l];
+    sacc += A * J.exit_gp_li[l];
+    double v = 0.0;
+    if ((int)l < nR) {
+      v = sacc * germ_em[l];
+      if (pad_trans) v *= pad_trans[l];
+      if (pad_em) v *= pad_em[l];
+    }
+    key = key_add<kExt>(key, v);
+    g_out = v;
+  }
+  const RowScale last = row_scale(row_key<kExt>(key));
+  g_out = last.apply(g_out);
+  return count + last.k;
+}
+
+// (waves per workgroup chosen by the launcher, dj4_waves: blockDim.x / 64; 1024 threads bound the kernel to 128 VGPRs)
+template <int GL, bool kExt>
+__global__ void __launch_bounds__(1024)
+    junction_dj4_kernel(const DevFamily fam, int n, const double* __restrict__ gem_all,
+                        const int32_t* __restrict__ gcnt_all, const double* __restrict__ jem_all,
+                        const int32_t* __restrict__ jrs_all, const double* __restrict__ dxf,
+                        const int32_t* __restrict__ dxc, double* __restrict__ loglik, double* __restrict__ fwd_all,
+                        int32_t* __restrict__ scal_all) {
+  extern __shared__ double jlds[];  // [NTI->NTI blocks of the 16 dj right genes a row of lanes owns | 4 * waves jem slices]
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, waves = blockDim.x >> 6;
+  const int NJ = fam.n_jcols;
+  double* ntt_dj = jlds;
+  double* jem0 = ntt_dj + 16 * 16 + (size_t)(4 * wave) * (NJ + 1);
+  for (int t = threadIdx.x; t < 16 * 16; t += blockDim.x) ntt_dj[t] = fam.dj.right_ntt[t];
+  __syncthreads();
+  // this wave's four samples: lanes 16 h .. 16 h + 15 -> sample 4 p + h
+  const int p = blockIdx.x * waves + wave;
+  if (4 * p >= n) return;  // none of the four exists
+  const int sub = lane >> 4;
+  const unsigned l = lane & 15;
+  const int s4 = 4 * p + sub;
+  const bool valid = s4 < n;
+  const int sr = valid ? s4 : n - 1;  // an absent sample reads the last one's inputs and writes nothing
+  for (int h = 0; h < 4; ++h) {
+    const int sh = min(4 * p + h, n - 1);
+    const double* src = jem_all + (size_t)sh * NJ;
+    double* dst = jem0 + (size_t)h * (NJ + 1);
+    for (int j = lane; j < NJ; j += 64) dst[j] = src[j];
+    if (lane == 0) dst[NJ] = 0.0;
+  }
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  const int nV = fam.vgerm.n_genes, nD = fam.dgerm.n_genes, nJ = fam.jgerm.n_genes;
+  const size_t vd_fwd = (size_t)fam.vd.n_rows * (fam.vd.n_left + 5 * (size_t)fam.vd.n_right);
+  const double* gem = gem_all + (size_t)sr * fam.gem_size;
+  const double* jgerm_em = gem + 2 * (size_t)nV + nD;
+  const double* jpad_em = jgerm_em + nJ;
+  const int cj = gcnt_all[(size_t)sr * 3 + 2];
+  double* fwd = fwd_all ? fwd_all + (size_t)sr * fam.forward_size + nV + vd_fwd + nD : nullptr;
+  int32_t* sco = scal_all ? scal_all + (size_t)sr * fam.scaler_size + 2 + fam.vd.n_rows : nullptr;
+  double f_in[GL];
+#pragma unroll
+  for (int q = 0; q < GL; ++q) f_in[q] = valid ? dxf[(size_t)s4 * 32 + l + 16u * q] : 0.0;
+  const int dcount = valid ? dxc[s4] : 0;
+  double gJ;
+  const int jcount =
+      cj + junction_quad<GL, kExt>(fam.dj, jem0 + (size_t)sub * (NJ + 1), ntt_dj, l, f_in, dcount, jgerm_em,
+                                   fam.jpadding_transition, jpad_em, gJ, fwd, sco,
+                                   kExt ? jrs_all + (size_t)sr * (fam.vd.n_rows + fam.dj.n_rows) + fam.vd.n_rows : nullptr,
+                                   valid);
+  if (fwd && valid && (int)l < nJ) fwd[(size_t)fam.dj.n_rows * (fam.dj.n_left + 5 * (size_t)fam.dj.n_right) + l] = gJ;
+  if (sco && valid && l == 0) sco[fam.dj.n_rows] = jcount;
+  // HMM::LogLikelihood (src/HMM.cpp:352-353)
+  const double tot[1] = {gJ};  // zero beyond the last J gene
+  const double part = row_sums<1>(tot);
+  if (valid && l == 0) loglik[s4] = log(part) - jcount * kLogScaleFactor;
+}
+
 // GA: register slots for the V genes (ceil(nV / 64)); GB: slots for the D and J genes.
 template <int GA, int GB, bool kExt = false>
 __global__ void __launch_bounds__(64 * kJunctionWaves)
@@ -1669,6 +1907,24 @@ static bool junction_pair_form(const DevFamily& fam) {
   return !off && fam.has_d && fam.dgerm.n_genes <= 32 && fam.jgerm.n_genes <= 32;
 }
 
+static size_t dj4_lds_bytes(const DevFamily& fam, int waves) {
+  return ((size_t)4 * waves * (fam.n_jcols + 1) + 16 * 16) * sizeof(double);
+}
+
+// Waves per junction_dj4_kernel workgroup, or 0 where the family keeps junction_dj_kernel: more than 16 J or 32 D alleles,
+// or no workgroup size at which the four jem slices per wave leave a SIMD as many resident waves as the pair form has
+// (both kernels hold at most 128 VGPRs: four waves per SIMD by registers; 160 KB of LDS per CU).
+static int dj4_waves(const DevFamily& fam, size_t lds_pair) {
+  static const bool pair = debug_options().k2b_dj_pair;  // test hook: two samples per D-J wave
+  if (pair || fam.jgerm.n_genes > 16 || fam.dgerm.n_genes > 32) return 0;
+  constexpr size_t kCuLds = 160 * 1024;
+  auto per_simd = [](size_t lds, int waves) { return std::min<size_t>(4, lds > kCuLds ? 0 : kCuLds / lds * waves / 4); };
+  const size_t need = per_simd(lds_pair, kPairWaves);
+  for (int waves = 4; waves <= 16; waves *= 2)
+    if (per_simd(dj4_lds_bytes(fam, waves), waves) >= need && need > 0) return waves;
+  return 0;
+}
+
 static size_t emission_lds_bytes(const DevFamily& fam, bool ext) {
   const size_t cap = (size_t)cons_capacity(fam);
   return ((((size_t)fam.n_ucol + 2) & ~(size_t)1) + 6) * sizeof(double) + (2 * kFwdWaves + 2) * sizeof(int) +
@@ -1744,14 +2000,48 @@ static void launch_emission_g(const DevFamily& fam, const DevFamily* fam_dev, in
 #undef LH_ARGS
 }
 
+// The pair form's D-J kernel: four samples per wave where dj4_waves allows it, two otherwise.
+template <bool kExt>
+static void launch_dj(const DevFamily& fam, int n, const double* gem, const int32_t* gcnt, const double* jem,
+                      const int32_t* jrs, const double* dxf, const int32_t* dxc, double* loglik, double* forward_out,
+                      int32_t* scaler_out, hipStream_t stream) {
+  const size_t lds_dj = ((size_t)2 * kPairWaves * (fam.n_jcols + 1) + 16 * (size_t)fam.dj.right_pad) * sizeof(double);
+  const int waves = dj4_waves(fam, lds_dj);
+  if (waves == 0) {
+    g_k2b_dj_samples = 2;
+    if (lds_dj > 64 * 1024)
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(junction_dj_kernel<kExt>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_dj);
+    hipLaunchKernelGGL((junction_dj_kernel<kExt>), dim3(((n + 1) / 2 + kPairWaves - 1) / kPairWaves), dim3(64 * kPairWaves),
+                       lds_dj, stream, fam, n, gem, gcnt, jem, jrs, dxf, dxc, loglik, forward_out, scaler_out);
+    return;
+  }
+  g_k2b_dj_samples = 4;
+  const size_t lds = dj4_lds_bytes(fam, waves);
+  const dim3 grid(((n + 3) / 4 + waves - 1) / waves), block(64 * waves);
+  if (fam.dgerm.n_genes <= 16) {
+    if (lds > 64 * 1024)
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(junction_dj4_kernel<1, kExt>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL((junction_dj4_kernel<1, kExt>), grid, block, lds, stream, fam, n, gem, gcnt, jem, jrs, dxf, dxc,
+                       loglik, forward_out, scaler_out);
+  } else {
+    if (lds > 64 * 1024)
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(junction_dj4_kernel<2, kExt>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL((junction_dj4_kernel<2, kExt>), grid, block, lds, stream, fam, n, gem, gcnt, jem, jrs, dxf, dxc,
+                       loglik, forward_out, scaler_out);
+  }
+}
+
 template <int GA, int GB>
 static void launch_junction_g(const DevFamily& fam, int n, const double* gem, const int32_t* gcnt, const double* jem,
                               const int32_t* jrs, double* dxf, int32_t* dxc, double* loglik, double* forward_out,
                               int32_t* scaler_out, bool ext, hipStream_t stream) {
+  g_k2b_dj_samples = 0;
   if (GB == 1 && junction_pair_form(fam)) {
     const size_t lds_vd = ((size_t)kJunctionWaves * (fam.n_jcols + 1) + 16 * (size_t)fam.vd.right_pad) * sizeof(double);
-    const size_t lds_dj = ((size_t)2 * kPairWaves * (fam.n_jcols + 1) + 16 * (size_t)fam.dj.right_pad) * sizeof(double);
-    const dim3 grid_vd((n + kJunctionWaves - 1) / kJunctionWaves), grid_dj(((n + 1) / 2 + kPairWaves - 1) / kPairWaves);
+    const dim3 grid_vd((n + kJunctionWaves - 1) / kJunctionWaves);
     static const bool vd_single = debug_options().k2b_vd_single;  // test hook: one sample per V-D wave
     if (!vd_single && GA <= 4) {  // (beyond 256 V alleles the second sample's left-gene registers no longer fit)
       const size_t lds_vd2 = ((size_t)2 * kVdPairWaves * (fam.n_jcols + 1) + 16 * (size_t)fam.vd.right_pad) * sizeof(double);
@@ -1762,13 +2052,9 @@ static void launch_junction_g(const DevFamily& fam, int n, const double* gem, co
     if (lds_vd2 > 64 * 1024)                                                                                          \
       (void)hipFuncSetAttribute(reinterpret_cast<const void*>(junction_vd2_kernel<GA, E>),                            \
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_vd2);                            \
-    if (lds_dj > 64 * 1024)                                                                                           \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(junction_dj_kernel<E>),                                 \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_dj);                             \
     hipLaunchKernelGGL((junction_vd2_kernel<GA, E>), grid_vd2, dim3(64 * kVdPairWaves), lds_vd2, stream, fam, n, gem, \
                        gcnt, jem, jrs, forward_out, scaler_out, dxf, dxc);                                            \
-    hipLaunchKernelGGL((junction_dj_kernel<E>), grid_dj, dim3(64 * kPairWaves), lds_dj, stream, fam, n, gem, gcnt,    \
-                       jem, jrs, dxf, dxc, loglik, forward_out, scaler_out);                                          \
+    launch_dj<E>(fam, n, gem, gcnt, jem, jrs, dxf, dxc, loglik, forward_out, scaler_out, stream);                     \
   }
       if (ext)
         LH_PAIR2_LAUNCH(true)
@@ -1783,13 +2069,9 @@ static void launch_junction_g(const DevFamily& fam, int n, const double* gem, co
     if (lds_vd > 64 * 1024)                                                                                           \
       (void)hipFuncSetAttribute(reinterpret_cast<const void*>(junction_vd_kernel<GA, E>),                             \
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_vd);                             \
-    if (lds_dj > 64 * 1024)                                                                                           \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(junction_dj_kernel<E>),                                 \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_dj);                             \
     hipLaunchKernelGGL((junction_vd_kernel<GA, E>), grid_vd, dim3(64 * kJunctionWaves), lds_vd, stream, fam, n, gem,  \
                        gcnt, jem, jrs, forward_out, scaler_out, dxf, dxc);                                            \
-    hipLaunchKernelGGL((junction_dj_kernel<E>), grid_dj, dim3(64 * kPairWaves), lds_dj, stream, fam, n, gem, gcnt,    \
-                       jem, jrs, dxf, dxc, loglik, forward_out, scaler_out);                                          \
+    launch_dj<E>(fam, n, gem, gcnt, jem, jrs, dxf, dxc, loglik, forward_out, scaler_out, stream);                     \
   }
     if (ext)
       LH_PAIR_LAUNCH(true)
@@ -1872,5 +2154,6 @@ void launch_forward(const DevFamily& fam, const DevFamily* fam_dev, int n, int R
 }
 
 const char* forward_last_form() { return g_forward_form; }
+int forward_last_dj_samples() { return g_k2b_dj_samples; }
 
 }  // namespace lh
