@@ -395,11 +395,9 @@ int launch_ancestral(const DevFamily& fam, int n, int R, int T, const int32_t* o
   launch_ancestral_front(fam, n, R, T, ops, pi, site_lik, site_scal, naive_prob, marg ? path : nullptr, P, ws, rate_post, hdr,
                          err_flag, stream);
   if (!marg) return 0;
-  if (lds > 64 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(anc_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL(anc_kernel, dim3(R, n), dim3(256), lds, stream, R, T, L, fam.n_prune, P, fam.msa, fam.site_pat,
-                     static_cast<const AsrOp*>(ws.desc), brlen, rates, eig, pi, ws.tvec, rho, ws.chain, ws.plen,
-                     reinterpret_cast<double2*>(ws.clv), (int)anc_lp(fam.n_prune), ws.part);
+  launch_lds(anc_kernel, dim3(R, n), dim3(256), lds, stream, R, T, L, fam.n_prune, P, fam.msa, fam.site_pat,
+             static_cast<const AsrOp*>(ws.desc), brlen, rates, eig, pi, ws.tvec, rho, ws.chain, ws.plen,
+             reinterpret_cast<double2*>(ws.clv), (int)anc_lp(fam.n_prune), ws.part);
   const long long out = (long long)n * P * L;
   hipLaunchKernelGGL(anc_combine_kernel, dim3((unsigned)((out + 255) / 256)), dim3(256), 0, stream, n, R, P, L, ws.plen,
                      ws.part, marg);

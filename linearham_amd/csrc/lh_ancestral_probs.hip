@@ -273,11 +273,9 @@ int launch_ancestral_cond(const DevFamily& fam, int n, int R, int T, const int32
   if (lds > 160 * 1024) return 1;
   launch_ancestral_front(fam, n, R, T, ops, pi, site_lik, site_scal, naive_prob, path, P, ws, nullptr, hdr, err_flag, stream);
   auto run = [&](auto kernel) {
-    if (lds > 64 * 1024)
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(kernel, dim3(R, n), dim3(256), lds, stream, R, T, fam.n_prune, P, fam.msa,
-                       static_cast<const AsrOp*>(ws.desc), brlen, rates, eig, pi, site_lik, site_scal, ws.chain, ws.plen,
-                       reinterpret_cast<double2*>(ws.clv), (int)anc_lp(fam.n_prune), ws.part);
+    launch_lds(kernel, dim3(R, n), dim3(256), lds, stream, R, T, fam.n_prune, P, fam.msa,
+               static_cast<const AsrOp*>(ws.desc), brlen, rates, eig, pi, site_lik, site_scal, ws.chain, ws.plen,
+               reinterpret_cast<double2*>(ws.clv), (int)anc_lp(fam.n_prune), ws.part);
   };
   if (node == 1)
     run(cond_kernel<true>);

@@ -174,10 +174,7 @@ void launch_collect(const CollectTables& t, int n, const int32_t* states, uint8_
   if (n <= 0) return;
   const unsigned blocks = (unsigned)((n + kRowsPerBlock - 1) / kRowsPerBlock);
   const size_t lds = collect_lds_bytes(t.L);
-  if (lds > 64 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(assemble_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)lds);
-  hipLaunchKernelGGL(assemble_kernel, dim3(blocks), dim3(kThreads), lds, stream, t, n, states, seqs, hash);
+  launch_lds(assemble_kernel, dim3(blocks), dim3(kThreads), lds, stream, t, n, states, seqs, hash);
 }
 
 template <class Rows>

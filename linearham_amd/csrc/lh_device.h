@@ -13,6 +13,16 @@ constexpr double kScaleFactor = 0x1p256;      // SCALE_FACTOR, src/utils.hpp:22
 constexpr double kScaleThreshold = 0x1p-256;  // SCALE_THRESHOLD, src/utils.hpp:24
 constexpr double kLogScaleFactor = 177.445678223345993274;  // log(2^256)
 
+// Launch a kernel with `lds` bytes of dynamic LDS: beyond the 64 KB every kernel may ask for, the kernel's limit is
+// raised first (the result of that call is not looked at: a launch that cannot have its LDS fails as a launch).
+template <class... P, class... A>
+static inline void launch_lds(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t stream,
+                              const A&... args) {
+  if (lds > 64 * 1024)
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL(kernel, grid, block, lds, stream, args...);
+}
+
 // schedule op kinds (ops[4k] & 15); bit 4 = push the accumulator to stack slot ops[4k+3] first
 // bits 8..: for a tip-into-accumulator / pop op, the number of inner-branch P-matrices the earlier ops need (its own
 // one or two follow): K1's prologue packs its matrix work by it

@@ -32,6 +32,7 @@
 //       lazily, as an exact power-of-two factor, when the row is consumed and when it is written out.
 #include <cstdio>
 #include <cstdlib>
+#include <type_traits>
 
 #include "lh_device.h"
 
@@ -773,21 +774,44 @@ __device__ static inline RowScale wave_row_scale(unsigned key) {
   return row_scale(kExt ? wave_max_u32(key) - 1u : wave_min_key(key));
 }
 
+// per-lane choice between the scalings of a wave's two halves (each wave-uniform)
+__device__ static __forceinline__ RowScale pick(bool hi, const RowScale& sa, const RowScale& sb) {
+  return RowScale{hi ? sb.k : sa.k, hi ? sb.factor : sa.factor, hi ? sb.extra : sa.extra};
+}
+
 // One junction row's table entries for the genes a lane owns (family constants, independent of the
 // sample and of the HMM state).
+struct RightRow {  // one right gene's entries
+  double nlo[4], rtr, rli;
+  int ridx;
+  int4 nx;
+};
+
 template <int GL, int GR>
 struct RowTables {
   double ltr[GL], llo[GL];
   int lidx[GL];
-  double nlo[GR][4], rtr[GR], rli[GR];
-  int ridx[GR];
-  int4 nx[GR];
+  RightRow right[GR];
 };
+
+// (wave-uniform row base + an offset that fits the instruction's immediate: no vector address math)
+__device__ static __forceinline__ void load_right_row(const DevJunction& J, int i, unsigned r, RightRow& t) {
+  const size_t orr = (size_t)i * J.right_pad;
+  const double2* pn = reinterpret_cast<const double2*>(J.right_nlo) + 2 * orr;
+  const double2 a = pn[2u * r], b = pn[2u * r + 1u];
+  t.nlo[0] = a.x;
+  t.nlo[1] = a.y;
+  t.nlo[2] = b.x;
+  t.nlo[3] = b.y;
+  t.nx = (reinterpret_cast<const int4*>(J.nti_xmsa) + orr)[r];
+  t.rtr = (J.right_trans + orr)[r];
+  t.rli = (J.right_gp_li + orr)[r];
+  t.ridx = (J.right_xmsa + orr)[r];
+}
 
 template <int GL, int GR>
 __device__ static inline void load_row(const DevJunction& J, int i, unsigned lane, RowTables<GL, GR>& t) {
-  // wave-uniform row bases + a lane offset that fits the instruction's immediate: no vector address math
-  const size_t ol = (size_t)i * J.left_pad, orr = (size_t)i * J.right_pad;
+  const size_t ol = (size_t)i * J.left_pad;
   const double* lt = J.left_trans + ol;
   const double* ll = J.left_lo + ol;
   const int32_t* lx = J.left_xmsa + ol;
@@ -797,24 +821,83 @@ __device__ static inline void load_row(const DevJunction& J, int i, unsigned lan
     t.llo[q] = ll[lane + 64u * q];
     t.lidx[q] = lx[lane + 64u * q];
   }
-  const double2* pn = reinterpret_cast<const double2*>(J.right_nlo) + 2 * orr;
-  const int4* px = reinterpret_cast<const int4*>(J.nti_xmsa) + orr;
-  const double* rt = J.right_trans + orr;
-  const double* rl = J.right_gp_li + orr;
-  const int32_t* rx = J.right_xmsa + orr;
 #pragma unroll
-  for (int q = 0; q < GR; ++q) {
-    const unsigned r = lane + 64u * q;
-    const double2 a = pn[2u * r], b = pn[2u * r + 1u];
-    t.nlo[q][0] = a.x;
-    t.nlo[q][1] = a.y;
-    t.nlo[q][2] = b.x;
-    t.nlo[q][3] = b.y;
-    t.nx[q] = px[r];
-    t.rtr[q] = rt[r];
-    t.rli[q] = rl[r];
-    t.ridx[q] = rx[r];
+  for (int q = 0; q < GR; ++q) load_right_row(J, i, lane + 64u * q, t.right[q]);
+}
+
+// ---- what every form of the sweep does for a right gene r, defined once: the forms below differ in how lanes map to
+// genes and samples and in how the sums and keys are reduced, not in this arithmetic ----
+
+// row-invariant NTI landing table of right gene r
+__device__ static __forceinline__ void load_nli(const DevJunction& J, unsigned r, double (&nli)[4]) {
+  const double2* p = reinterpret_cast<const double2*>(J.right_gp_nli) + 2u * r;
+  const double2 a = p[0], b = p[1];
+  nli[0] = a.x, nli[1] = a.y, nli[2] = b.x, nli[3] = b.y;
+}
+
+// One row's step of right gene r: its four NTI states (fN) and its germline state (fR) from the previous row's, the
+// rank-one sum A and the row's table entries; returns the scale key with the five new values added.
+template <bool kExt>
+__device__ static __forceinline__ unsigned right_gene_step(unsigned key, double (&fN)[4], double& fR, double A,
+                                                           const double (&nli)[4], const double* ntt_lds, unsigned r,
+                                                           const RightRow& t, const double* jem) {
+  const double n0 = fN[0], n1 = fN[1], n2 = fN[2], n3 = fN[3];
+  // NTI->NTI block of gene r, transposed in LDS: [b * 4 + a] = transition a -> b
+  const double2* tt = reinterpret_cast<const double2*>(ntt_lds) + 8u * r;
+  const int nxs[4] = {t.nx.x, t.nx.y, t.nx.z, t.nx.w};
+#pragma unroll
+  for (int b = 0; b < 4; ++b) {
+    const double2 t01 = tt[2 * b], t23 = tt[2 * b + 1];
+    double s = ((n0 * t01.x + n1 * t01.y) + n2 * t23.x) + n3 * t23.y;
+    s += A * nli[b];
+    fN[b] = s * jem[nxs[b]];
   }
+  double s = ((n0 * t.nlo[0] + n1 * t.nlo[1]) + n2 * t.nlo[2]) + n3 * t.nlo[3];
+  s += fR * t.rtr;
+  s += A * t.rli;
+  fR = s * jem[t.ridx];
+  // (the key behind the arithmetic, not value by value: integer minima and maxima, exact in any order, and
+  // junction_vd2_kernel<4, true> stays within the 168 registers of three waves per SIMD)
+#pragma unroll
+  for (int b = 0; b < 4; ++b) key = key_add<kExt>(key, fN[b]);
+  return key_add<kExt>(key, fR);
+}
+
+// Right gene r's entry into the next germline region, before its rescaling (A: the last row's rank-one sum; pad_trans
+// and pad_em may be null); zero beyond the last right gene.
+__device__ static __forceinline__ double exit_handoff(const DevJunction& J, unsigned r, int nR, const double (&fN)[4],
+                                                      double fR, double A, const double* __restrict__ germ_em,
+                                                      const double* __restrict__ pad_trans,
+                                                      const double* __restrict__ pad_em) {
+  const double2* xn = reinterpret_cast<const double2*>(J.exit_nlo) + 2u * r;
+  const double2 x01 = xn[0], x23 = xn[1];
+  double s = ((fN[0] * x01.x + fN[1] * x01.y) + fN[2] * x23.x) + fN[3] * x23.y;
+  s += fR * J.exit_trans[r];
+  s += A * J.exit_gp_li[r];
+  double v = 0.0;
+  if ((int)r < nR) {
+    v = s * germ_em[r];
+    if (pad_trans) v *= pad_trans[r];
+    if (pad_em) v *= pad_em[r];
+  }
+  return v;
+}
+
+// right gene r's five states into row o of the forward array: [nL left | 4 nR NTI | nR right]
+__device__ static __forceinline__ void store_right(double* __restrict__ o, int nL, int nR, unsigned r,
+                                                   const double (&fN)[4], double fR) {
+  if ((int)r < nR) {
+    o[nL + 4 * (size_t)r + 0] = fN[0];
+    o[nL + 4 * (size_t)r + 1] = fN[1];
+    o[nL + 4 * (size_t)r + 2] = fN[2];
+    o[nL + 4 * (size_t)r + 3] = fN[3];
+    o[nL + 4 * (size_t)nR + r] = fR;
+  }
+}
+
+// doubles of a junction's rows in the forward array
+__device__ static __forceinline__ size_t junction_fwd_size(const DevJunction& J) {
+  return (size_t)J.n_rows * (J.n_left + 5 * (size_t)J.n_right);
 }
 
 // kExt (extended-range mode): row i's emissions carry the 2^-256 count jrs[i], added to the running count, and
@@ -835,12 +918,7 @@ __device__ static int junction_wave(const DevJunction& J, const double* jem, con
   for (int q = 0; q < GR; ++q) {
     fR[q] = 0.0;
     fN[q][0] = fN[q][1] = fN[q][2] = fN[q][3] = 0.0;
-    const double2* p = reinterpret_cast<const double2*>(J.right_gp_nli) + 2u * (lane + 64u * q);
-    const double2 a = p[0], b = p[1];
-    nli[q][0] = a.x;
-    nli[q][1] = a.y;
-    nli[q][2] = b.x;
-    nli[q][3] = b.y;
+    load_nli(J, lane + 64u * q, nli[q]);
   }
   const size_t row_stride = (size_t)nL + 5 * (size_t)nR;
   // rank-one term of row 0: A = sum_l f_in[l] * landing_out_l[last germline-region index]
@@ -865,27 +943,8 @@ __device__ static int junction_wave(const DevJunction& J, const double* jem, con
       part += v * t.llo[q];  // contribution to the next row's rank-one term
     }
 #pragma unroll
-    for (int q = 0; q < GR; ++q) {
-      const double n0 = fN[q][0], n1 = fN[q][1], n2 = fN[q][2], n3 = fN[q][3];
-      // NTI->NTI block of gene r, transposed in LDS: [b * 4 + a] = transition a -> b
-      const double2* tt = reinterpret_cast<const double2*>(ntt_lds) + 8u * (lane + 64u * q);
-      const int nxs[4] = {t.nx[q].x, t.nx[q].y, t.nx[q].z, t.nx[q].w};
-#pragma unroll
-      for (int b = 0; b < 4; ++b) {
-        const double2 t01 = tt[2 * b], t23 = tt[2 * b + 1];
-        double s = ((n0 * t01.x + n1 * t01.y) + n2 * t23.x) + n3 * t23.y;
-        s += A * nli[q][b];
-        const double v = s * jem[nxs[b]];
-        fN[q][b] = v;
-        key = key_add<kExt>(key, v);
-      }
-      double s = ((n0 * t.nlo[q][0] + n1 * t.nlo[q][1]) + n2 * t.nlo[q][2]) + n3 * t.nlo[q][3];
-      s += fR[q] * t.rtr[q];
-      s += A * t.rli[q];
-      const double v = s * jem[t.ridx[q]];
-      fR[q] = v;
-      key = key_add<kExt>(key, v);
-    }
+    for (int q = 0; q < GR; ++q)
+      key = right_gene_step<kExt>(key, fN[q], fR[q], A, nli[q], ntt_lds, lane + 64u * q, t.right[q], jem);
     A = wave_sum(part);
     const RowScale sc = wave_row_scale<kExt>(key);
     if constexpr (kExt) count += jrs[i];
@@ -909,16 +968,7 @@ __device__ static int junction_wave(const DevJunction& J, const double* jem, con
         if (g < nL) o[g] = fL[q];
       }
 #pragma unroll
-      for (int q = 0; q < GR; ++q) {
-        const int g = lane + 64 * q;
-        if (g < nR) {
-          o[nL + 4 * (size_t)g + 0] = fN[q][0];
-          o[nL + 4 * (size_t)g + 1] = fN[q][1];
-          o[nL + 4 * (size_t)g + 2] = fN[q][2];
-          o[nL + 4 * (size_t)g + 3] = fN[q][3];
-          o[nL + 4 * (size_t)nR + g] = fR[q];
-        }
-      }
+      for (int q = 0; q < GR; ++q) store_right(o, nL, nR, lane + 64u * q, fN[q], fR[q]);
     }
     if (scal_out && lane == 0) scal_out[i] = count;
   };
@@ -935,18 +985,7 @@ __device__ static int junction_wave(const DevJunction& J, const double* jem, con
   unsigned key = key_start<kExt>();
 #pragma unroll
   for (int q = 0; q < GR; ++q) {
-    const unsigned r = lane + 64u * q;
-    const double2* xn = reinterpret_cast<const double2*>(J.exit_nlo) + 2u * r;
-    const double2 x01 = xn[0], x23 = xn[1];
-    double s = ((fN[q][0] * x01.x + fN[q][1] * x01.y) + fN[q][2] * x23.x) + fN[q][3] * x23.y;
-    s += fR[q] * J.exit_trans[r];
-    s += A * J.exit_gp_li[r];
-    double v = 0.0;
-    if ((int)r < nR) {
-      v = s * germ_em[r];
-      if (pad_trans) v *= pad_trans[r];
-      if (pad_em) v *= pad_em[r];
-    }
+    const double v = exit_handoff(J, lane + 64u * q, nR, fN[q], fR[q], A, germ_em, pad_trans, pad_em);
     key = key_add<kExt>(key, v);
     g_out[q] = v;
   }
@@ -1011,23 +1050,16 @@ __device__ static int junction_pair(const DevJunction& J, const double* jem, con
   const unsigned g = lane & 31;  // gene of this lane, left and right alike
   int count = count_in;
   double fL = f_in, fR = 0.0, fN[4] = {0.0, 0.0, 0.0, 0.0}, nli[4];
-  {
-    const double2* p = reinterpret_cast<const double2*>(J.right_gp_nli) + 2u * g;
-    const double2 a = p[0], b = p[1];
-    nli[0] = a.x, nli[1] = a.y, nli[2] = b.x, nli[3] = b.y;
-  }
+  load_nli(J, g, nli);
   const size_t row_stride = (size_t)nL + 5 * (size_t)nR;
   auto mine = [&](const HalfPair& p) { return hi ? p.b : p.a; };
   double A = mine(half_sums(f_in * J.enter_lo[g]));
   for (int i = 0; i < W; ++i) {
-    const size_t ol = (size_t)i * J.left_pad, orr = (size_t)i * J.right_pad;
+    const size_t ol = (size_t)i * J.left_pad;
     const double ltr = J.left_trans[ol + g], llo = J.left_lo[ol + g];
     const int lidx = J.left_xmsa[ol + g];
-    const double2* pn = reinterpret_cast<const double2*>(J.right_nlo) + 2 * (orr + g);
-    const double2 n01 = pn[0], n23 = pn[1];
-    const int4 nx = reinterpret_cast<const int4*>(J.nti_xmsa)[orr + g];
-    const double rtr = J.right_trans[orr + g], rli = J.right_gp_li[orr + g];
-    const int ridx = J.right_xmsa[orr + g];
+    RightRow t;
+    load_right_row(J, i, g, t);
 
     unsigned key = key_start<kExt>();
     {
@@ -1036,83 +1068,31 @@ __device__ static int junction_pair(const DevJunction& J, const double* jem, con
       key = key_add<kExt>(key, v);
     }
     const double part = fL * llo;
-    const double n0 = fN[0], n1 = fN[1], n2 = fN[2], n3 = fN[3];
-    const double2* tt = reinterpret_cast<const double2*>(ntt_lds) + 8u * g;
-    const int nxs[4] = {nx.x, nx.y, nx.z, nx.w};
-#pragma unroll
-    for (int b = 0; b < 4; ++b) {
-      const double2 t01 = tt[2 * b], t23 = tt[2 * b + 1];
-      double sacc = ((n0 * t01.x + n1 * t01.y) + n2 * t23.x) + n3 * t23.y;
-      sacc += A * nli[b];
-      const double v = sacc * jem[nxs[b]];
-      fN[b] = v;
-      key = key_add<kExt>(key, v);
-    }
-    {
-      double sacc = ((n0 * n01.x + n1 * n01.y) + n2 * n23.x) + n3 * n23.y;
-      sacc += fR * rtr;
-      sacc += A * rli;
-      const double v = sacc * jem[ridx];
-      fR = v;
-      key = key_add<kExt>(key, v);
-    }
+    key = right_gene_step<kExt>(key, fN, fR, A, nli, ntt_lds, g, t, jem);
     A = mine(half_sums(part));
     const HalfKeys hk = half_keys<kExt>(key);
     const RowScale sa = row_scale(hk.a), sb = row_scale(hk.b);
     if constexpr (kExt) count += jrs[i];
     if ((sa.k | sb.k) != 0) {  // wave-uniform, a few rows per junction
-      const RowScale& sc = hi ? sb : sa;  // (per-lane choice between two wave-uniform scalings)
-      const double factor = hi ? sb.factor : sa.factor;
-      const bool extra = hi ? sb.extra : sa.extra;
-      auto apply = [&](double v) {
-        v *= factor;
-        if (extra) v *= kScaleFactor;
-        return v;
-      };
-      A = apply(A);
-      fL = apply(fL);
-      fR = apply(fR);
+      const RowScale sc = pick(hi, sa, sb);
+      A = sc.apply(A);
+      fL = sc.apply(fL);
+      fR = sc.apply(fR);
 #pragma unroll
-      for (int b = 0; b < 4; ++b) fN[b] = apply(fN[b]);
+      for (int b = 0; b < 4; ++b) fN[b] = sc.apply(fN[b]);
       count += sc.k;
     }
     if (fwd_out && valid) {
       double* o = fwd_out + (size_t)i * row_stride;
       if ((int)g < nL) o[g] = fL;
-      if ((int)g < nR) {
-        o[nL + 4 * (size_t)g + 0] = fN[0];
-        o[nL + 4 * (size_t)g + 1] = fN[1];
-        o[nL + 4 * (size_t)g + 2] = fN[2];
-        o[nL + 4 * (size_t)g + 3] = fN[3];
-        o[nL + 4 * (size_t)nR + g] = fR;
-      }
+      store_right(o, nL, nR, g, fN, fR);
     }
     if (scal_out && valid && g == 0) scal_out[i] = count;
   }
-  unsigned key = key_start<kExt>();
-  {
-    const double2* xn = reinterpret_cast<const double2*>(J.exit_nlo) + 2u * g;
-    const double2 x01 = xn[0], x23 = xn[1];
-    double sacc = ((fN[0] * x01.x + fN[1] * x01.y) + fN[2] * x23.x) + fN[3] * x23.y;
-    sacc += fR * J.exit_trans[g];
-    sacc += A * J.exit_gp_li[g];
-    double v = 0.0;
-    if ((int)g < nR) {
-      v = sacc * germ_em[g];
-      if (pad_trans) v *= pad_trans[g];
-      if (pad_em) v *= pad_em[g];
-    }
-    key = key_add<kExt>(key, v);
-    g_out = v;
-  }
-  const HalfKeys hk = half_keys<kExt>(key);
-  const RowScale sa = row_scale(hk.a), sb = row_scale(hk.b);
-  const RowScale& last = hi ? sb : sa;
-  {
-    double v = g_out * (hi ? sb.factor : sa.factor);
-    if (hi ? sb.extra : sa.extra) v *= kScaleFactor;
-    g_out = v;
-  }
+  g_out = exit_handoff(J, g, nR, fN, fR, A, germ_em, pad_trans, pad_em);
+  const HalfKeys hk = half_keys<kExt>(key_add<kExt>(key_start<kExt>(), g_out));
+  const RowScale last = pick(hi, row_scale(hk.a), row_scale(hk.b));
+  g_out = last.apply(g_out);
   return count + last.k;
 }
 
@@ -1142,11 +1122,7 @@ __device__ static void junction_vd_pair(const DevJunction& J, const double* jemA
     fA[q] = fA_in[q];
     fB[q] = fB_in[q];
   }
-  {
-    const double2* p = reinterpret_cast<const double2*>(J.right_gp_nli) + 2u * g;
-    const double2 a = p[0], b = p[1];
-    nli[0] = a.x, nli[1] = a.y, nli[2] = b.x, nli[3] = b.y;
-  }
+  load_nli(J, g, nli);
   const size_t row_stride = (size_t)nL + 5 * (size_t)nR;
   double AA, AB;
   {
@@ -1162,7 +1138,7 @@ __device__ static void junction_vd_pair(const DevJunction& J, const double* jemA
   }
   auto combine = [](unsigned a, unsigned b) { return kExt ? max(a, b) : min(a, b); };
   for (int i = 0; i < W; ++i) {
-    const size_t ol = (size_t)i * J.left_pad, orr = (size_t)i * J.right_pad;
+    const size_t ol = (size_t)i * J.left_pad;
     unsigned keyA = key_start<kExt>(), keyB = key_start<kExt>();
     double partA = 0.0, partB = 0.0;
     {
@@ -1184,33 +1160,9 @@ __device__ static void junction_vd_pair(const DevJunction& J, const double* jemA
       }
     }
     {
-      const double AM = hi ? AB : AA;
-      const double2* pn = reinterpret_cast<const double2*>(J.right_nlo) + 2 * (orr + g);
-      const double2 n01 = pn[0], n23 = pn[1];
-      const int4 nx = reinterpret_cast<const int4*>(J.nti_xmsa)[orr + g];
-      const double rtr = J.right_trans[orr + g], rli = J.right_gp_li[orr + g];
-      const int ridx = J.right_xmsa[orr + g];
-      unsigned keyR = key_start<kExt>();
-      const double n0 = fN[0], n1 = fN[1], n2 = fN[2], n3 = fN[3];
-      const double2* tt = reinterpret_cast<const double2*>(ntt_lds) + 8u * g;
-      const int nxs[4] = {nx.x, nx.y, nx.z, nx.w};
-#pragma unroll
-      for (int b = 0; b < 4; ++b) {
-        const double2 t01 = tt[2 * b], t23 = tt[2 * b + 1];
-        double sacc = ((n0 * t01.x + n1 * t01.y) + n2 * t23.x) + n3 * t23.y;
-        sacc += AM * nli[b];
-        const double v = sacc * jemM[nxs[b]];
-        fN[b] = v;
-        keyR = key_add<kExt>(keyR, v);
-      }
-      {
-        double sacc = ((n0 * n01.x + n1 * n01.y) + n2 * n23.x) + n3 * n23.y;
-        sacc += fR * rtr;
-        sacc += AM * rli;
-        const double v = sacc * jemM[ridx];
-        fR = v;
-        keyR = key_add<kExt>(keyR, v);
-      }
+      RightRow t;
+      load_right_row(J, i, g, t);
+      const unsigned keyR = right_gene_step<kExt>(key_start<kExt>(), fN, fR, hi ? AB : AA, nli, ntt_lds, g, t, jemM);
       if (hi)
         keyB = combine(keyB, keyR);
       else
@@ -1231,16 +1183,10 @@ __device__ static void junction_vd_pair(const DevJunction& J, const double* jemA
         fA[q] = sa.apply(fA[q]);
         fB[q] = sb.apply(fB[q]);
       }
-      const double factor = hi ? sb.factor : sa.factor;
-      const bool extra = hi ? sb.extra : sa.extra;
-      auto apply = [&](double v) {
-        v *= factor;
-        if (extra) v *= kScaleFactor;
-        return v;
-      };
-      fR = apply(fR);
+      const RowScale sm = pick(hi, sa, sb);
+      fR = sm.apply(fR);
 #pragma unroll
-      for (int b = 0; b < 4; ++b) fN[b] = apply(fN[b]);
+      for (int b = 0; b < 4; ++b) fN[b] = sm.apply(fN[b]);
       countA += sa.k;
       countB += sb.k;
     }
@@ -1256,13 +1202,7 @@ __device__ static void junction_vd_pair(const DevJunction& J, const double* jemA
         }
       }
       double* om = hi ? ob : oa;
-      if (om && (int)g < nR) {
-        om[nL + 4 * (size_t)g + 0] = fN[0];
-        om[nL + 4 * (size_t)g + 1] = fN[1];
-        om[nL + 4 * (size_t)g + 2] = fN[2];
-        om[nL + 4 * (size_t)g + 3] = fN[3];
-        om[nL + 4 * (size_t)nR + g] = fR;
-      }
+      if (om) store_right(om, nL, nR, g, fN, fR);
     }
     if (lane == 0) {
       if (scoA) scoA[i] = countA;
@@ -1270,68 +1210,43 @@ __device__ static void junction_vd_pair(const DevJunction& J, const double* jemA
     }
   }
   // hand-off into the D germline region, each half for its sample
-  unsigned key = key_start<kExt>();
-  {
-    const double AM = hi ? AB : AA;
-    const double2* xn = reinterpret_cast<const double2*>(J.exit_nlo) + 2u * g;
-    const double2 x01 = xn[0], x23 = xn[1];
-    double sacc = ((fN[0] * x01.x + fN[1] * x01.y) + fN[2] * x23.x) + fN[3] * x23.y;
-    sacc += fR * J.exit_trans[g];
-    sacc += AM * J.exit_gp_li[g];
-    double v = 0.0;
-    if ((int)g < nR) v = sacc * germ_em_mine[g];
-    key = key_add<kExt>(key, v);
-    g_out = v;
-  }
-  const HalfKeys hk = half_keys<kExt>(key);
-  const RowScale la = row_scale(hk.a), lb = row_scale(hk.b);
-  {
-    double v = g_out * (hi ? lb.factor : la.factor);
-    if (hi ? lb.extra : la.extra) v *= kScaleFactor;
-    g_out = v;
-  }
-  count_mine = (hi ? countB + lb.k : countA + la.k);
+  g_out = exit_handoff(J, g, nR, fN, fR, hi ? AB : AA, germ_em_mine, nullptr, nullptr);
+  const HalfKeys hk = half_keys<kExt>(key_add<kExt>(key_start<kExt>(), g_out));
+  const RowScale last = pick(hi, row_scale(hk.a), row_scale(hk.b));
+  g_out = last.apply(g_out);
+  count_mine = (hi ? countB : countA) + last.k;
 }
 
-// The pair form (igh families with at most 32 D and 32 J alleles) as two kernels, because the two halves want
-// different launch shapes: junction_vd_kernel sweeps the V-D junction with a wave per sample (the V genes fill
-// its lanes, 156 VGPRs, three waves per SIMD) and leaves the D-germline forward vector and its scaler count in
-// dxf / dxc; junction_dj_kernel sweeps the D-J junctions of TWO samples per wave (junction_pair; few registers,
-// every wave slot of the CU in use).  Run inside one kernel -- waves 2 and 3 of a workgroup retiring after the
-// V-D half -- the freed slots could not be refilled before the whole workgroup had finished (K2 0.81 -> 0.80 ms
-// only).
-// (113 VGPRs, four waves per SIMD; a 96-register budget for five waves: 0.28 -> 0.32 ms, 80 for six: 0.75 ms)
-template <int GA, bool kExt>
-__global__ void __launch_bounds__(64 * kJunctionWaves)
-    junction_vd_kernel(const DevFamily fam, int n, const double* __restrict__ gem_all,
-                       const int32_t* __restrict__ gcnt_all, const double* __restrict__ jem_all,
-                       const int32_t* __restrict__ jrs_all, double* __restrict__ fwd_all,
-                       int32_t* __restrict__ scal_all, double* __restrict__ dxf, int32_t* __restrict__ dxc) {
-  extern __shared__ double jlds[];  // [NTI->NTI blocks of the vd right genes | kJunctionWaves jem slices]
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int s = blockIdx.x * kJunctionWaves + wave;
-  const int NJ = fam.n_jcols;
-  double* ntt_vd = jlds;
-  double* jem = ntt_vd + 16 * (size_t)fam.vd.right_pad + (size_t)wave * (NJ + 1);
-  for (int t = threadIdx.x; t < 16 * fam.vd.right_pad; t += 64 * kJunctionWaves) ntt_vd[t] = fam.vd.right_ntt[t];
-  __syncthreads();
-  if (s >= n) return;  // whole waves leave; nothing below synchronises across waves
-  const int nV = fam.vgerm.n_genes, nD = fam.dgerm.n_genes;
-  const size_t vd_fwd = (size_t)fam.vd.n_rows * (fam.vd.n_left + 5 * (size_t)fam.vd.n_right);
-  {
-    const double* src = jem_all + (size_t)s * NJ;
-    for (int j = lane; j < NJ; j += 64) jem[j] = src[j];
-    if (lane == 0) jem[NJ] = 0.0;  // what a state that cannot emit at a site looks up
+// ---- kernel prologue and epilogue pieces shared by the K2b kernels -----------------------------------------------
+
+// a junction's NTI->NTI blocks into LDS, by a workgroup of `threads`; the caller's __syncthreads() follows
+__device__ static __forceinline__ void stage_ntt(double* dst, const double* __restrict__ src, int count, int threads) {
+  for (int t = threadIdx.x; t < count; t += threads) dst[t] = src[t];
+}
+
+// The jem slices of this wave's kSamples samples (first, first + 1, ...; one beyond the last sample, n - 1, reads
+// that one's) into LDS, NJ + 1 doubles apiece, and the wave's own fence: nothing else reads these slices.
+template <int kSamples>
+__device__ static __forceinline__ void stage_jem(double* jem0, const double* __restrict__ jem_all, int first, int n,
+                                                 int NJ, int lane) {
+  for (int h = 0; h < kSamples; ++h) {
+    const double* src = jem_all + (size_t)min(first + h, n - 1) * NJ;
+    double* dst = jem0 + (size_t)h * (NJ + 1);
+    for (int j = lane; j < NJ; j += 64) dst[j] = src[j];
+    if (lane == 0) dst[NJ] = 0.0;  // what a state that cannot emit at a site looks up
   }
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  const double* gem = gem_all + (size_t)s * fam.gem_size;
-  const int cv = gcnt_all[(size_t)s * 3 + 0], cd = gcnt_all[(size_t)s * 3 + 1];
-  double* fwd = fwd_all ? fwd_all + (size_t)s * fam.forward_size : nullptr;
-  int32_t* sco = scal_all ? scal_all + (size_t)s * fam.scaler_size : nullptr;
-  // initial forward over the V germline region (src/HMM.cpp:291-319)
-  double gV[GA];
+}
+
+// Initial forward over the V germline region (src/HMM.cpp:291-319) of one sample per wave: gV, rescaled; written to
+// fwd / sco[0] where those are asked for.  Returns the V scaler count (cv: K2a's).
+template <int GA, bool kExt>
+__device__ static __forceinline__ int initial_v_forward(const DevFamily& fam, const double* __restrict__ gem, int lane,
+                                                        int cv, double (&gV)[GA], double* __restrict__ fwd,
+                                                        int32_t* __restrict__ sco) {
+  const int nV = fam.vgerm.n_genes;
   unsigned key = key_start<kExt>();
 #pragma unroll
   for (int q = 0; q < GA; ++q) {
@@ -1347,19 +1262,51 @@ __global__ void __launch_bounds__(64 * kJunctionWaves)
     key = key_add<kExt>(key, v);
     gV[q] = v;
   }
-  int vcount = cv;
-  {
-    const RowScale sc = wave_row_scale<kExt>(key);
+  const RowScale sc = wave_row_scale<kExt>(key);
 #pragma unroll
-    for (int q = 0; q < GA; ++q) gV[q] = sc.apply(gV[q]);
-    vcount += sc.k;
-  }
+  for (int q = 0; q < GA; ++q) gV[q] = sc.apply(gV[q]);
+  const int vcount = cv + sc.k;
   if (fwd) {
 #pragma unroll
     for (int q = 0; q < GA; ++q)
       if (lane + 64 * q < nV) fwd[lane + 64 * q] = gV[q];
   }
   if (sco && lane == 0) sco[0] = vcount;
+  return vcount;
+}
+
+// The pair form (igh families with at most 32 D and 32 J alleles) as two kernels, because the two halves want
+// different launch shapes: junction_vd_kernel sweeps the V-D junction with a wave per sample (the V genes fill
+// its lanes) and leaves the D-germline forward vector and its scaler count in
+// dxf / dxc; junction_dj_kernel sweeps the D-J junctions of TWO samples per wave (junction_pair; few registers,
+// every wave slot of the CU in use).  Run inside one kernel -- waves 2 and 3 of a workgroup retiring after the
+// V-D half -- the freed slots could not be refilled before the whole workgroup had finished (K2 0.81 -> 0.80 ms
+// only).
+// (GA = 4: 106 VGPRs, four waves per SIMD; a 96-register budget for five waves: 0.28 -> 0.32 ms, 80 for six: 0.75 ms)
+template <int GA, bool kExt>
+__global__ void __launch_bounds__(64 * kJunctionWaves)
+    junction_vd_kernel(const DevFamily fam, int n, const double* __restrict__ gem_all,
+                       const int32_t* __restrict__ gcnt_all, const double* __restrict__ jem_all,
+                       const int32_t* __restrict__ jrs_all, double* __restrict__ fwd_all,
+                       int32_t* __restrict__ scal_all, double* __restrict__ dxf, int32_t* __restrict__ dxc) {
+  extern __shared__ double jlds[];  // [NTI->NTI blocks of the vd right genes | kJunctionWaves jem slices]
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int s = blockIdx.x * kJunctionWaves + wave;
+  const int NJ = fam.n_jcols;
+  double* ntt_vd = jlds;
+  double* jem = ntt_vd + 16 * (size_t)fam.vd.right_pad + (size_t)wave * (NJ + 1);
+  stage_ntt(ntt_vd, fam.vd.right_ntt, 16 * fam.vd.right_pad, 64 * kJunctionWaves);
+  __syncthreads();
+  if (s >= n) return;  // whole waves leave; nothing below synchronises across waves
+  const int nV = fam.vgerm.n_genes, nD = fam.dgerm.n_genes;
+  const size_t vd_fwd = junction_fwd_size(fam.vd);
+  stage_jem<1>(jem, jem_all, s, n, NJ, lane);
+  const double* gem = gem_all + (size_t)s * fam.gem_size;
+  const int cv = gcnt_all[(size_t)s * 3 + 0], cd = gcnt_all[(size_t)s * 3 + 1];
+  double* fwd = fwd_all ? fwd_all + (size_t)s * fam.forward_size : nullptr;
+  int32_t* sco = scal_all ? scal_all + (size_t)s * fam.scaler_size : nullptr;
+  double gV[GA];
+  const int vcount = initial_v_forward<GA, kExt>(fam, gem, lane, cv, gV, fwd, sco);
   double gD[1];
   const int dcount =
       cd + junction_wave<GA, 1, kExt>(fam.vd, jem, ntt_vd, lane, gV, vcount, gem + 2 * (size_t)nV, nullptr, nullptr, gD,
@@ -1373,7 +1320,7 @@ __global__ void __launch_bounds__(64 * kJunctionWaves)
 
 // V-D half of the pair form with two samples per wave (junction_vd_pair); same outputs as junction_vd_kernel.
 constexpr int kVdPairWaves = 4;  // waves per workgroup (eight samples)
-// (167 VGPRs, three waves = six samples per SIMD: 0.327 ms per 49 152 against 0.567 for junction_vd_kernel; forced to
+// (GA = 4: 162 VGPRs, three waves = six samples per SIMD: 0.327 ms per 49 152 against 0.567 for junction_vd_kernel; forced to
 // four waves it spills: 0.358, two waves: 0.393)
 template <int GA, bool kExt>
 __global__ void __launch_bounds__(64 * kVdPairWaves)
@@ -1386,31 +1333,23 @@ __global__ void __launch_bounds__(64 * kVdPairWaves)
   const int NJ = fam.n_jcols;
   double* ntt_vd = jlds;
   double* jem0 = ntt_vd + 16 * (size_t)fam.vd.right_pad + (size_t)(2 * wave) * (NJ + 1);
-  for (int t = threadIdx.x; t < 16 * fam.vd.right_pad; t += 64 * kVdPairWaves) ntt_vd[t] = fam.vd.right_ntt[t];
+  stage_ntt(ntt_vd, fam.vd.right_ntt, 16 * fam.vd.right_pad, 64 * kVdPairWaves);
   __syncthreads();
   const int p = blockIdx.x * kVdPairWaves + wave;
   if (2 * p >= n) return;  // neither sample exists; nothing below synchronises across waves
   const bool hi = lane >= 32;
   const int sA = 2 * p, sB = min(2 * p + 1, n - 1);
   const bool validB = 2 * p + 1 < n;  // an absent second sample reads the first one's inputs and writes nothing
-  for (int h = 0; h < 2; ++h) {
-    const double* src = jem_all + (size_t)(h ? sB : sA) * NJ;
-    double* dst = jem0 + (size_t)h * (NJ + 1);
-    for (int j = lane; j < NJ; j += 64) dst[j] = src[j];
-    if (lane == 0) dst[NJ] = 0.0;  // what a state that cannot emit at a site looks up
-  }
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  stage_jem<2>(jem0, jem_all, sA, n, NJ, lane);
   const int nV = fam.vgerm.n_genes, nD = fam.dgerm.n_genes;
-  const size_t vd_fwd = (size_t)fam.vd.n_rows * (fam.vd.n_left + 5 * (size_t)fam.vd.n_right);
+  const size_t vd_fwd = junction_fwd_size(fam.vd);
   const double* gemA = gem_all + (size_t)sA * fam.gem_size;
   const double* gemB = gem_all + (size_t)sB * fam.gem_size;
   double* fwdA = fwd_all ? fwd_all + (size_t)sA * fam.forward_size : nullptr;
   double* fwdB = fwd_all && validB ? fwd_all + (size_t)sB * fam.forward_size : nullptr;
   int32_t* scoA = scal_all ? scal_all + (size_t)sA * fam.scaler_size : nullptr;
   int32_t* scoB = scal_all && validB ? scal_all + (size_t)sB * fam.scaler_size : nullptr;
-  // initial forward over the V germline region (src/HMM.cpp:291-319), both samples
+  // initial_v_forward for both samples in one loop: the three family constants of a gene are loaded once
   double gA[GA], gB[GA];
   unsigned keyA = key_start<kExt>(), keyB = key_start<kExt>();
 #pragma unroll
@@ -1480,6 +1419,43 @@ __global__ void __launch_bounds__(64 * kVdPairWaves)
 
 constexpr int kPairWaves = 4;  // waves per junction_dj_kernel workgroup (eight samples)
 
+// What a lane of the D-J kernels holds of the sample it works for.
+struct DjSample {
+  const double *jgerm_em, *jpad_em;
+  int cj;              // K2a's J scaler count
+  double* fwd;         // the sample's D-J rows in the forward array, the J region behind them (null: not asked for)
+  int32_t* sco;        // the scaler counts of the same
+  const int32_t* jrs;  // the D-J rows' 2^-256 counts (extended-range mode)
+};
+
+template <bool kExt>
+__device__ static __forceinline__ DjSample dj_sample(const DevFamily& fam, int s, const double* __restrict__ gem_all,
+                                                     const int32_t* __restrict__ gcnt_all,
+                                                     const int32_t* __restrict__ jrs_all, double* __restrict__ fwd_all,
+                                                     int32_t* __restrict__ scal_all) {
+  const int nV = fam.vgerm.n_genes, nD = fam.dgerm.n_genes, nJ = fam.jgerm.n_genes;
+  DjSample d;
+  d.jgerm_em = gem_all + (size_t)s * fam.gem_size + 2 * (size_t)nV + nD;
+  d.jpad_em = d.jgerm_em + nJ;
+  d.cj = gcnt_all[(size_t)s * 3 + 2];
+  d.fwd = fwd_all ? fwd_all + (size_t)s * fam.forward_size + nV + junction_fwd_size(fam.vd) + nD : nullptr;
+  d.sco = scal_all ? scal_all + (size_t)s * fam.scaler_size + 2 + fam.vd.n_rows : nullptr;
+  d.jrs = kExt ? jrs_all + (size_t)s * (fam.vd.n_rows + fam.dj.n_rows) + fam.vd.n_rows : nullptr;
+  return d;
+}
+
+// Sample s's J-region forward vector (gJ: J gene g's entry), its count, and HMM::LogLikelihood (src/HMM.cpp:352-353);
+// total() = the sum of the sample's gJ by the form's reduction, called by every lane of the wave.  (Stores first, then
+// the sum: with the sum first junction_dj4_kernel no longer fits its 128 registers.)
+template <class Total>
+__device__ static __forceinline__ void dj_finish(const DevFamily& fam, const DjSample& d, int s, bool valid, unsigned g,
+                                                 double gJ, int jcount, Total&& total, double* __restrict__ loglik) {
+  if (d.fwd && valid && (int)g < fam.jgerm.n_genes) d.fwd[junction_fwd_size(fam.dj) + g] = gJ;
+  if (d.sco && valid && g == 0) d.sco[fam.dj.n_rows] = jcount;
+  const double part = total();  // zero beyond the last J gene
+  if (valid && g == 0) loglik[s] = log(part) - jcount * kLogScaleFactor;
+}
+
 // (122 VGPRs, four waves per SIMD: capped at 80 / 64 registers the kernel spills and takes 2.9x / 4.9x as long)
 template <bool kExt>
 __global__ void __launch_bounds__(64 * kPairWaves)
@@ -1493,7 +1469,7 @@ __global__ void __launch_bounds__(64 * kPairWaves)
   const int NJ = fam.n_jcols;
   double* ntt_dj = jlds;
   double* jem0 = ntt_dj + 16 * (size_t)fam.dj.right_pad + (size_t)(2 * wave) * (NJ + 1);
-  for (int t = threadIdx.x; t < 16 * fam.dj.right_pad; t += 64 * kPairWaves) ntt_dj[t] = fam.dj.right_ntt[t];
+  stage_ntt(ntt_dj, fam.dj.right_ntt, 16 * fam.dj.right_pad, 64 * kPairWaves);
   __syncthreads();
   // this wave's two samples: lanes 0-31 -> sample 2 p, lanes 32-63 -> sample 2 p + 1
   const int p = blockIdx.x * kPairWaves + wave;
@@ -1502,39 +1478,19 @@ __global__ void __launch_bounds__(64 * kPairWaves)
   const int s2 = 2 * p + (hi ? 1 : 0);
   const bool valid = s2 < n;
   const int sr = valid ? s2 : n - 1;  // an absent second sample reads the last one's inputs and writes nothing
-  for (int h = 0; h < 2; ++h) {
-    const int sh = min(2 * p + h, n - 1);
-    const double* src = jem_all + (size_t)sh * NJ;
-    double* dst = jem0 + (size_t)h * (NJ + 1);
-    for (int j = lane; j < NJ; j += 64) dst[j] = src[j];
-    if (lane == 0) dst[NJ] = 0.0;
-  }
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  const int nV = fam.vgerm.n_genes, nD = fam.dgerm.n_genes, nJ = fam.jgerm.n_genes;
-  const size_t vd_fwd = (size_t)fam.vd.n_rows * (fam.vd.n_left + 5 * (size_t)fam.vd.n_right);
+  stage_jem<2>(jem0, jem_all, 2 * p, n, NJ, lane);
   const unsigned g = lane & 31;
-  const double* gem = gem_all + (size_t)sr * fam.gem_size;
-  const double* jgerm_em = gem + 2 * (size_t)nV + nD;
-  const double* jpad_em = jgerm_em + nJ;
-  const int cj = gcnt_all[(size_t)sr * 3 + 2];
-  double* fwd = fwd_all ? fwd_all + (size_t)sr * fam.forward_size + nV + vd_fwd + nD : nullptr;
-  int32_t* sco = scal_all ? scal_all + (size_t)sr * fam.scaler_size + 2 + fam.vd.n_rows : nullptr;
+  const DjSample d = dj_sample<kExt>(fam, sr, gem_all, gcnt_all, jrs_all, fwd_all, scal_all);
   const double f_in = valid ? dxf[(size_t)s2 * 32 + g] : 0.0;
   const int dcount = valid ? dxc[s2] : 0;
   double gJ;
-  const int jcount =
-      cj + junction_pair<kExt>(fam.dj, jem0 + (size_t)(hi ? 1 : 0) * (NJ + 1), ntt_dj, lane, hi, f_in, dcount, jgerm_em,
-                               fam.jpadding_transition, jpad_em, gJ, fwd, sco,
-                               kExt ? jrs_all + (size_t)sr * (fam.vd.n_rows + fam.dj.n_rows) + fam.vd.n_rows : nullptr,
-                               valid);
-  if (fwd && valid && (int)g < nJ) fwd[(size_t)fam.dj.n_rows * (fam.dj.n_left + 5 * (size_t)fam.dj.n_right) + g] = gJ;
-  if (sco && valid && g == 0) sco[fam.dj.n_rows] = jcount;
-  // HMM::LogLikelihood (src/HMM.cpp:352-353)
-  const HalfPair tot = half_sums(gJ);  // zero beyond the last J gene
-  const double part = hi ? tot.b : tot.a;
-  if (valid && g == 0) loglik[s2] = log(part) - jcount * kLogScaleFactor;
+  const int jcount = d.cj + junction_pair<kExt>(fam.dj, jem0 + (size_t)(hi ? 1 : 0) * (NJ + 1), ntt_dj, lane, hi, f_in,
+                                                dcount, d.jgerm_em, fam.jpadding_transition, d.jpad_em, gJ, d.fwd,
+                                                d.sco, d.jrs, valid);
+  dj_finish(fam, d, s2, valid, g, gJ, jcount, [&] {
+    const HalfPair tot = half_sums(gJ);
+    return hi ? tot.b : tot.a;
+  }, loglik);
 }
 
 // ---- four samples per wave on the D-J junction (at most 32 D and 16 J alleles) -----------------------------------
@@ -1608,11 +1564,7 @@ __device__ static int junction_quad(const DevJunction& J, const double* jem, con
   double fL[GL], fR = 0.0, fN[4] = {0.0, 0.0, 0.0, 0.0}, nli[4];
 #pragma unroll
   for (int q = 0; q < GL; ++q) fL[q] = f_in[q];
-  {
-    const double2* p = reinterpret_cast<const double2*>(J.right_gp_nli) + 2u * l;
-    const double2 a = p[0], b = p[1];
-    nli[0] = a.x, nli[1] = a.y, nli[2] = b.x, nli[3] = b.y;
-  }
+  load_nli(J, l, nli);
   const size_t row_stride = (size_t)nL + 5 * (size_t)nR;
   double A;
   {
@@ -1622,7 +1574,7 @@ __device__ static int junction_quad(const DevJunction& J, const double* jem, con
     A = row_sums<GL>(part);
   }
   for (int i = 0; i < W; ++i) {
-    const size_t ol = (size_t)i * J.left_pad, orr = (size_t)i * J.right_pad;
+    const size_t ol = (size_t)i * J.left_pad;
     double ltr[GL], llo[GL];
     int lidx[GL];
 #pragma unroll
@@ -1631,11 +1583,8 @@ __device__ static int junction_quad(const DevJunction& J, const double* jem, con
       llo[q] = J.left_lo[ol + l + 16u * q];
       lidx[q] = J.left_xmsa[ol + l + 16u * q];
     }
-    const double2* pn = reinterpret_cast<const double2*>(J.right_nlo) + 2 * (orr + l);
-    const double2 n01 = pn[0], n23 = pn[1];
-    const int4 nx = reinterpret_cast<const int4*>(J.nti_xmsa)[orr + l];
-    const double rtr = J.right_trans[orr + l], rli = J.right_gp_li[orr + l];
-    const int ridx = J.right_xmsa[orr + l];
+    RightRow t;
+    load_right_row(J, i, l, t);
 
     unsigned key = key_start<kExt>();
     double part[GL];
@@ -1646,26 +1595,7 @@ __device__ static int junction_quad(const DevJunction& J, const double* jem, con
       key = key_add<kExt>(key, v);
       part[q] = fL[q] * llo[q];
     }
-    const double n0 = fN[0], n1 = fN[1], n2 = fN[2], n3 = fN[3];
-    const double2* tt = reinterpret_cast<const double2*>(ntt_lds) + 8u * l;
-    const int nxs[4] = {nx.x, nx.y, nx.z, nx.w};
-#pragma unroll
-    for (int b = 0; b < 4; ++b) {
-      const double2 t01 = tt[2 * b], t23 = tt[2 * b + 1];
-      double sacc = ((n0 * t01.x + n1 * t01.y) + n2 * t23.x) + n3 * t23.y;
-      sacc += A * nli[b];
-      const double v = sacc * jem[nxs[b]];
-      fN[b] = v;
-      key = key_add<kExt>(key, v);
-    }
-    {
-      double sacc = ((n0 * n01.x + n1 * n01.y) + n2 * n23.x) + n3 * n23.y;
-      sacc += fR * rtr;
-      sacc += A * rli;
-      const double v = sacc * jem[ridx];
-      fR = v;
-      key = key_add<kExt>(key, v);
-    }
+    key = right_gene_step<kExt>(key, fN, fR, A, nli, ntt_lds, l, t, jem);
     A = row_sums<GL>(part);
     const unsigned rk = row_key<kExt>(key);
     if constexpr (kExt) count += jrs[i];
@@ -1684,33 +1614,12 @@ __device__ static int junction_quad(const DevJunction& J, const double* jem, con
 #pragma unroll
       for (int q = 0; q < GL; ++q)
         if ((int)(l + 16u * q) < nL) o[l + 16u * q] = fL[q];
-      if ((int)l < nR) {
-        o[nL + 4 * (size_t)l + 0] = fN[0];
-        o[nL + 4 * (size_t)l + 1] = fN[1];
-        o[nL + 4 * (size_t)l + 2] = fN[2];
-        o[nL + 4 * (size_t)l + 3] = fN[3];
-        o[nL + 4 * (size_t)nR + l] = fR;
-      }
+      store_right(o, nL, nR, l, fN, fR);
     }
     if (scal_out && valid && l == 0) scal_out[i] = count;
   }
-  unsigned key = key_start<kExt>();
-  {
-    const double2* xn = reinterpret_cast<const double2*>(J.exit_nlo) + 2u * l;
-    const double2 x01 = xn[0], x23 = xn[1];
-    double sacc = ((fN[0] * x01.x + fN[1] * x01.y) + fN[2] * x23.x) + fN[3] * x23.y;
-    sacc += fR * J.exit_trans[l];
-    sacc += A * J.exit_gp_li[l];
-    double v = 0.0;
-    if ((int)l < nR) {
-      v = sacc * germ_em[l];
-      if (pad_trans) v *= pad_trans[l];
-      if (pad_em) v *= pad_em[l];
-    }
-    key = key_add<kExt>(key, v);
-    g_out = v;
-  }
-  const RowScale last = row_scale(row_key<kExt>(key));
+  g_out = exit_handoff(J, l, nR, fN, fR, A, germ_em, pad_trans, pad_em);
+  const RowScale last = row_scale(row_key<kExt>(key_add<kExt>(key_start<kExt>(), g_out)));
   g_out = last.apply(g_out);
   return count + last.k;
 }
@@ -1728,7 +1637,7 @@ __global__ void __launch_bounds__(1024)
   const int NJ = fam.n_jcols;
   double* ntt_dj = jlds;
   double* jem0 = ntt_dj + 16 * 16 + (size_t)(4 * wave) * (NJ + 1);
-  for (int t = threadIdx.x; t < 16 * 16; t += blockDim.x) ntt_dj[t] = fam.dj.right_ntt[t];
+  stage_ntt(ntt_dj, fam.dj.right_ntt, 16 * 16, blockDim.x);
   __syncthreads();
   // this wave's four samples: lanes 16 h .. 16 h + 15 -> sample 4 p + h
   const int p = blockIdx.x * waves + wave;
@@ -1738,40 +1647,17 @@ __global__ void __launch_bounds__(1024)
   const int s4 = 4 * p + sub;
   const bool valid = s4 < n;
   const int sr = valid ? s4 : n - 1;  // an absent sample reads the last one's inputs and writes nothing
-  for (int h = 0; h < 4; ++h) {
-    const int sh = min(4 * p + h, n - 1);
-    const double* src = jem_all + (size_t)sh * NJ;
-    double* dst = jem0 + (size_t)h * (NJ + 1);
-    for (int j = lane; j < NJ; j += 64) dst[j] = src[j];
-    if (lane == 0) dst[NJ] = 0.0;
-  }
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  const int nV = fam.vgerm.n_genes, nD = fam.dgerm.n_genes, nJ = fam.jgerm.n_genes;
-  const size_t vd_fwd = (size_t)fam.vd.n_rows * (fam.vd.n_left + 5 * (size_t)fam.vd.n_right);
-  const double* gem = gem_all + (size_t)sr * fam.gem_size;
-  const double* jgerm_em = gem + 2 * (size_t)nV + nD;
-  const double* jpad_em = jgerm_em + nJ;
-  const int cj = gcnt_all[(size_t)sr * 3 + 2];
-  double* fwd = fwd_all ? fwd_all + (size_t)sr * fam.forward_size + nV + vd_fwd + nD : nullptr;
-  int32_t* sco = scal_all ? scal_all + (size_t)sr * fam.scaler_size + 2 + fam.vd.n_rows : nullptr;
+  stage_jem<4>(jem0, jem_all, 4 * p, n, NJ, lane);
+  const DjSample d = dj_sample<kExt>(fam, sr, gem_all, gcnt_all, jrs_all, fwd_all, scal_all);
   double f_in[GL];
 #pragma unroll
   for (int q = 0; q < GL; ++q) f_in[q] = valid ? dxf[(size_t)s4 * 32 + l + 16u * q] : 0.0;
   const int dcount = valid ? dxc[s4] : 0;
   double gJ;
-  const int jcount =
-      cj + junction_quad<GL, kExt>(fam.dj, jem0 + (size_t)sub * (NJ + 1), ntt_dj, l, f_in, dcount, jgerm_em,
-                                   fam.jpadding_transition, jpad_em, gJ, fwd, sco,
-                                   kExt ? jrs_all + (size_t)sr * (fam.vd.n_rows + fam.dj.n_rows) + fam.vd.n_rows : nullptr,
-                                   valid);
-  if (fwd && valid && (int)l < nJ) fwd[(size_t)fam.dj.n_rows * (fam.dj.n_left + 5 * (size_t)fam.dj.n_right) + l] = gJ;
-  if (sco && valid && l == 0) sco[fam.dj.n_rows] = jcount;
-  // HMM::LogLikelihood (src/HMM.cpp:352-353)
-  const double tot[1] = {gJ};  // zero beyond the last J gene
-  const double part = row_sums<1>(tot);
-  if (valid && l == 0) loglik[s4] = log(part) - jcount * kLogScaleFactor;
+  const int jcount = d.cj + junction_quad<GL, kExt>(fam.dj, jem0 + (size_t)sub * (NJ + 1), ntt_dj, l, f_in, dcount,
+                                                    d.jgerm_em, fam.jpadding_transition, d.jpad_em, gJ, d.fwd, d.sco,
+                                                    d.jrs, valid);
+  dj_finish(fam, d, s4, valid, l, gJ, jcount, [&] { return row_sums<1>({gJ}); }, loglik);
 }
 
 // GA: register slots for the V genes (ceil(nV / 64)); GB: slots for the D and J genes.
@@ -1789,19 +1675,11 @@ __global__ void __launch_bounds__(64 * kJunctionWaves)
   double* ntt_vd = jlds;
   double* ntt_dj = ntt_vd + 16 * (size_t)fam.vd.right_pad;
   double* jem = ntt_dj + (fam.has_d ? 16 * (size_t)fam.dj.right_pad : 0) + (size_t)wave * (NJ + 1);
-  for (int t = threadIdx.x; t < 16 * fam.vd.right_pad; t += 64 * kJunctionWaves) ntt_vd[t] = fam.vd.right_ntt[t];
-  if (fam.has_d)
-    for (int t = threadIdx.x; t < 16 * fam.dj.right_pad; t += 64 * kJunctionWaves) ntt_dj[t] = fam.dj.right_ntt[t];
+  stage_ntt(ntt_vd, fam.vd.right_ntt, 16 * fam.vd.right_pad, 64 * kJunctionWaves);
+  if (fam.has_d) stage_ntt(ntt_dj, fam.dj.right_ntt, 16 * fam.dj.right_pad, 64 * kJunctionWaves);
   __syncthreads();
   if (s >= n) return;  // whole waves leave; nothing below synchronises across waves
-  {
-    const double* src = jem_all + (size_t)s * NJ;
-    for (int j = lane; j < NJ; j += 64) jem[j] = src[j];
-    if (lane == 0) jem[NJ] = 0.0;  // what a state that cannot emit at a site looks up
-  }
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  stage_jem<1>(jem, jem_all, s, n, NJ, lane);
 
   const int nV = fam.vgerm.n_genes, nD = fam.dgerm.n_genes, nJ = fam.jgerm.n_genes;
   const double* gem = gem_all + (size_t)s * fam.gem_size;
@@ -1809,41 +1687,11 @@ __global__ void __launch_bounds__(64 * kJunctionWaves)
   double* fwd = fwd_all ? fwd_all + (size_t)s * fam.forward_size : nullptr;
   int32_t* sco = scal_all ? scal_all + (size_t)s * fam.scaler_size : nullptr;
 
-  // initial forward over the V germline region (src/HMM.cpp:291-319)
   double gV[GA];
-  unsigned key = key_start<kExt>();
-#pragma unroll
-  for (int q = 0; q < GA; ++q) {
-    const int t = lane + 64 * q;
-    double v = 0.0;
-    if (t < nV) {
-      v = fam.vgerm_gene_prob[t];
-      v *= fam.vpadding_transition[t];
-      v *= gem[t];
-      v *= fam.vgerm_trans_prod[t];
-      v *= gem[nV + t];
-    }
-    key = key_add<kExt>(key, v);
-    gV[q] = v;
-  }
-  int vcount = cv;
+  const int vcount = initial_v_forward<GA, kExt>(fam, gem, lane, cv, gV, fwd, sco);
   const int32_t* jrs = kExt ? jrs_all + (size_t)s * (fam.vd.n_rows + (fam.has_d ? fam.dj.n_rows : 0)) : nullptr;
-  {
-    const RowScale sc = wave_row_scale<kExt>(key);
-#pragma unroll
-    for (int q = 0; q < GA; ++q) gV[q] = sc.apply(gV[q]);
-    vcount += sc.k;
-  }
-  if (fwd) {
-#pragma unroll
-    for (int q = 0; q < GA; ++q)
-      if (lane + 64 * q < nV) fwd[lane + 64 * q] = gV[q];
-    fwd += nV;
-  }
-  if (sco) {
-    if (lane == 0) sco[0] = vcount;
-    sco += 1;
-  }
+  if (fwd) fwd += nV;
+  if (sco) sco += 1;
 
   double gJ[GB];
   int jcount;
@@ -1855,7 +1703,7 @@ __global__ void __launch_bounds__(64 * kJunctionWaves)
     const int dcount = cd + junction_wave<GA, GB, kExt>(fam.vd, jem, ntt_vd, lane, gV, vcount, dgerm_em, nullptr,
                                                         nullptr, gD, fwd, sco, jrs);
     if (fwd) {
-      fwd += (size_t)fam.vd.n_rows * (fam.vd.n_left + 5 * (size_t)fam.vd.n_right);
+      fwd += junction_fwd_size(fam.vd);
 #pragma unroll
       for (int q = 0; q < GB; ++q)
         if (lane + 64 * q < nD) fwd[lane + 64 * q] = gD[q];
@@ -1869,14 +1717,14 @@ __global__ void __launch_bounds__(64 * kJunctionWaves)
     jcount = cj + junction_wave<GB, GB, kExt>(fam.dj, jem, ntt_dj, lane, gD, dcount, jgerm_em,
                                               fam.jpadding_transition, jpad_em, gJ, fwd, sco,
                                               kExt ? jrs + fam.vd.n_rows : nullptr);
-    if (fwd) fwd += (size_t)fam.dj.n_rows * (fam.dj.n_left + 5 * (size_t)fam.dj.n_right);
+    if (fwd) fwd += junction_fwd_size(fam.dj);
     if (sco) sco += fam.dj.n_rows;
   } else {
     const double* jgerm_em = gem + 2 * (size_t)nV;
     const double* jpad_em = jgerm_em + nJ;
     jcount = cj + junction_wave<GA, GB, kExt>(fam.vd, jem, ntt_vd, lane, gV, vcount, jgerm_em,
                                               fam.jpadding_transition, jpad_em, gJ, fwd, sco, jrs);
-    if (fwd) fwd += (size_t)fam.vd.n_rows * (fam.vd.n_left + 5 * (size_t)fam.vd.n_right);
+    if (fwd) fwd += junction_fwd_size(fam.vd);
     if (sco) sco += fam.vd.n_rows;
   }
   if (fwd) {
@@ -1901,7 +1749,8 @@ static size_t junction_lds_bytes(const DevFamily& fam) {
          sizeof(double);
 }
 
-// Two samples per wave on the D-J junction (junction_kernel_pair): igh families with at most 32 D and J alleles.
+// The pair form (junction_vd_kernel or junction_vd2_kernel, then junction_dj_kernel or junction_dj4_kernel): igh
+// families with at most 32 D and J alleles.
 static bool junction_pair_form(const DevFamily& fam) {
   static const bool off = debug_options().k2b_no_pair;  // test hook: the one-sample-per-wave form
   return !off && fam.has_d && fam.dgerm.n_genes <= 32 && fam.jgerm.n_genes <= 32;
@@ -1937,6 +1786,17 @@ size_t forward_lds_bytes(const DevFamily& fam) {
   return a > b ? a : b;
 }
 
+// a run-time bool as a template argument: f(std::true_type{}) or f(std::false_type{})
+template <class F>
+static void with_bool(bool b, F&& f) {
+  if (b)
+    f(std::true_type{});
+  else
+    f(std::false_type{});
+}
+template <int N>
+using slots_c = std::integral_constant<int, N>;  // likewise for a count of register slots
+
 template <int kG, bool kSite, bool kByteOff, bool kExt, bool kLem>
 static void launch_emission_l(const DevFamily& fam, const DevFamily* fam_dev, int n, int R, const double* site_lik,
                               const int32_t* site_scal, const double* pi, const double* em_in, double* em_out,
@@ -1945,11 +1805,8 @@ static void launch_emission_l(const DevFamily& fam, const DevFamily* fam_dev, in
   const size_t lds = emission_lds_bytes(fam, kExt);
   snprintf(g_k2a_form, sizeof(g_k2a_form), "emission<%d,%s,%s%s%s>", kG, kSite ? "site" : "caller",
            kByteOff ? "byte" : "index", kExt ? ",ext" : "", kLem ? ",lem" : "");
-  if (lds > 64 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(emission_kernel<kG, kSite, kByteOff, kExt, kLem>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL((emission_kernel<kG, kSite, kByteOff, kExt, kLem>), dim3(n), dim3(kFwdThreads), lds, stream, fam_dev,
-                     R, site_lik, site_scal, pi, em_in, em_out, gem, gcnt, jem, jrs, lem.cols, lem.n, lem.out);
+  launch_lds(emission_kernel<kG, kSite, kByteOff, kExt, kLem>, dim3(n), dim3(kFwdThreads), lds, stream, fam_dev, R,
+             site_lik, site_scal, pi, em_in, em_out, gem, gcnt, jem, jrs, lem.cols, lem.n, lem.out);
 }
 
 template <int kG, bool kSite, bool kByteOff, bool kExt>
@@ -1973,31 +1830,14 @@ static void launch_emission_g(const DevFamily& fam, const DevFamily* fam_dev, in
                               const int32_t* site_scal, const double* pi, const double* em_in, double* em_out,
                               double* gem, int32_t* gcnt, double* jem, int32_t* jrs, bool ext, const LogEmRequest& lem,
                               hipStream_t stream) {
-#define LH_ARGS fam, fam_dev, n, R, site_lik, site_scal, pi, em_in, em_out, gem, gcnt, jem, jrs, lem, stream
-  if (ext) {  // opt-in mode: one index form is enough
-    if (site_lik) {
-      if (fam.idx_byte_offsets)
-        launch_emission_k<kG, true, true, true>(LH_ARGS);
-      else
-        launch_emission_k<kG, true, false, true>(LH_ARGS);
-    } else {
-      if (fam.idx_byte_offsets)
-        launch_emission_k<kG, false, true, true>(LH_ARGS);
-      else
-        launch_emission_k<kG, false, false, true>(LH_ARGS);
-    }
-  } else if (site_lik) {
-    if (fam.idx_byte_offsets)
-      launch_emission_k<kG, true, true, false>(LH_ARGS);
-    else
-      launch_emission_k<kG, true, false, false>(LH_ARGS);
-  } else {
-    if (fam.idx_byte_offsets)
-      launch_emission_k<kG, false, true, false>(LH_ARGS);
-    else
-      launch_emission_k<kG, false, false, false>(LH_ARGS);
-  }
-#undef LH_ARGS
+  with_bool(site_lik != nullptr, [&](auto S) {
+    with_bool(fam.idx_byte_offsets != 0, [&](auto B) {
+      with_bool(ext, [&](auto E) {
+        launch_emission_k<kG, decltype(S)::value, decltype(B)::value, decltype(E)::value>(
+            fam, fam_dev, n, R, site_lik, site_scal, pi, em_in, em_out, gem, gcnt, jem, jrs, lem, stream);
+      });
+    });
+  });
 }
 
 // The pair form's D-J kernel: four samples per wave where dj4_waves allows it, two otherwise.
@@ -2007,31 +1847,17 @@ static void launch_dj(const DevFamily& fam, int n, const double* gem, const int3
                       int32_t* scaler_out, hipStream_t stream) {
   const size_t lds_dj = ((size_t)2 * kPairWaves * (fam.n_jcols + 1) + 16 * (size_t)fam.dj.right_pad) * sizeof(double);
   const int waves = dj4_waves(fam, lds_dj);
-  if (waves == 0) {
-    g_k2b_dj_samples = 2;
-    if (lds_dj > 64 * 1024)
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(junction_dj_kernel<kExt>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_dj);
-    hipLaunchKernelGGL((junction_dj_kernel<kExt>), dim3(((n + 1) / 2 + kPairWaves - 1) / kPairWaves), dim3(64 * kPairWaves),
-                       lds_dj, stream, fam, n, gem, gcnt, jem, jrs, dxf, dxc, loglik, forward_out, scaler_out);
-    return;
+  g_k2b_dj_samples = waves == 0 ? 2 : 4;
+  auto kernel = junction_dj_kernel<kExt>;  // (the three kernels take the same arguments)
+  size_t lds = lds_dj;
+  dim3 grid(((n + 1) / 2 + kPairWaves - 1) / kPairWaves), block(64 * kPairWaves);
+  if (waves != 0) {
+    kernel = fam.dgerm.n_genes <= 16 ? junction_dj4_kernel<1, kExt> : junction_dj4_kernel<2, kExt>;
+    lds = dj4_lds_bytes(fam, waves);
+    grid = dim3(((n + 3) / 4 + waves - 1) / waves);
+    block = dim3(64 * waves);
   }
-  g_k2b_dj_samples = 4;
-  const size_t lds = dj4_lds_bytes(fam, waves);
-  const dim3 grid(((n + 3) / 4 + waves - 1) / waves), block(64 * waves);
-  if (fam.dgerm.n_genes <= 16) {
-    if (lds > 64 * 1024)
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(junction_dj4_kernel<1, kExt>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL((junction_dj4_kernel<1, kExt>), grid, block, lds, stream, fam, n, gem, gcnt, jem, jrs, dxf, dxc,
-                       loglik, forward_out, scaler_out);
-  } else {
-    if (lds > 64 * 1024)
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(junction_dj4_kernel<2, kExt>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL((junction_dj4_kernel<2, kExt>), grid, block, lds, stream, fam, n, gem, gcnt, jem, jrs, dxf, dxc,
-                       loglik, forward_out, scaler_out);
-  }
+  launch_lds(kernel, grid, block, lds, stream, fam, n, gem, gcnt, jem, jrs, dxf, dxc, loglik, forward_out, scaler_out);
 }
 
 template <int GA, int GB>
@@ -2039,63 +1865,39 @@ static void launch_junction_g(const DevFamily& fam, int n, const double* gem, co
                               const int32_t* jrs, double* dxf, int32_t* dxc, double* loglik, double* forward_out,
                               int32_t* scaler_out, bool ext, hipStream_t stream) {
   g_k2b_dj_samples = 0;
-  if (GB == 1 && junction_pair_form(fam)) {
-    const size_t lds_vd = ((size_t)kJunctionWaves * (fam.n_jcols + 1) + 16 * (size_t)fam.vd.right_pad) * sizeof(double);
-    const dim3 grid_vd((n + kJunctionWaves - 1) / kJunctionWaves);
-    static const bool vd_single = debug_options().k2b_vd_single;  // test hook: one sample per V-D wave
-    if (!vd_single && GA <= 4) {  // (beyond 256 V alleles the second sample's left-gene registers no longer fit)
-      const size_t lds_vd2 = ((size_t)2 * kVdPairWaves * (fam.n_jcols + 1) + 16 * (size_t)fam.vd.right_pad) * sizeof(double);
-      const dim3 grid_vd2(((n + 1) / 2 + kVdPairWaves - 1) / kVdPairWaves);
-      snprintf(g_k2b_form, sizeof(g_k2b_form), "vd2<%d>+dj", GA);
-#define LH_PAIR2_LAUNCH(E)                                                                                            \
-  {                                                                                                                   \
-    if (lds_vd2 > 64 * 1024)                                                                                          \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(junction_vd2_kernel<GA, E>),                            \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_vd2);                            \
-    hipLaunchKernelGGL((junction_vd2_kernel<GA, E>), grid_vd2, dim3(64 * kVdPairWaves), lds_vd2, stream, fam, n, gem, \
-                       gcnt, jem, jrs, forward_out, scaler_out, dxf, dxc);                                            \
-    launch_dj<E>(fam, n, gem, gcnt, jem, jrs, dxf, dxc, loglik, forward_out, scaler_out, stream);                     \
-  }
-      if (ext)
-        LH_PAIR2_LAUNCH(true)
-      else
-        LH_PAIR2_LAUNCH(false)
-#undef LH_PAIR2_LAUNCH
+  if constexpr (GB == 1) {
+    if (junction_pair_form(fam)) {
+      const size_t jem_slice = (size_t)fam.n_jcols + 1, ntt_vd = 16 * (size_t)fam.vd.right_pad;
+      // two samples per V-D wave up to 256 V alleles (beyond, the second sample's left-gene registers no longer fit)
+      bool vd2 = false;
+      if constexpr (GA <= 4) {
+        static const bool vd_single = debug_options().k2b_vd_single;  // test hook: one sample per V-D wave
+        vd2 = !vd_single;
+      }
+      snprintf(g_k2b_form, sizeof(g_k2b_form), vd2 ? "vd2<%d>+dj" : "vd<%d>+dj", GA);
+      with_bool(ext, [&](auto E) {
+        constexpr bool kE = decltype(E)::value;
+        if constexpr (GA <= 4) {
+          if (vd2)
+            launch_lds(junction_vd2_kernel<GA, kE>, dim3(((n + 1) / 2 + kVdPairWaves - 1) / kVdPairWaves),
+                       dim3(64 * kVdPairWaves), (2 * kVdPairWaves * jem_slice + ntt_vd) * sizeof(double), stream, fam, n,
+                       gem, gcnt, jem, jrs, forward_out, scaler_out, dxf, dxc);
+        }
+        if (!vd2)
+          launch_lds(junction_vd_kernel<GA, kE>, dim3((n + kJunctionWaves - 1) / kJunctionWaves),
+                     dim3(64 * kJunctionWaves), (kJunctionWaves * jem_slice + ntt_vd) * sizeof(double), stream, fam, n,
+                     gem, gcnt, jem, jrs, forward_out, scaler_out, dxf, dxc);
+        launch_dj<kE>(fam, n, gem, gcnt, jem, jrs, dxf, dxc, loglik, forward_out, scaler_out, stream);
+      });
       return;
     }
-    snprintf(g_k2b_form, sizeof(g_k2b_form), "vd<%d>+dj", GA);
-#define LH_PAIR_LAUNCH(E)                                                                                             \
-  {                                                                                                                   \
-    if (lds_vd > 64 * 1024)                                                                                           \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(junction_vd_kernel<GA, E>),                             \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_vd);                             \
-    hipLaunchKernelGGL((junction_vd_kernel<GA, E>), grid_vd, dim3(64 * kJunctionWaves), lds_vd, stream, fam, n, gem,  \
-                       gcnt, jem, jrs, forward_out, scaler_out, dxf, dxc);                                            \
-    launch_dj<E>(fam, n, gem, gcnt, jem, jrs, dxf, dxc, loglik, forward_out, scaler_out, stream);                     \
   }
-    if (ext)
-      LH_PAIR_LAUNCH(true)
-    else
-      LH_PAIR_LAUNCH(false)
-#undef LH_PAIR_LAUNCH
-    return;
-  }
-  const size_t lds = junction_lds_bytes(fam);
-  const dim3 grid((n + kJunctionWaves - 1) / kJunctionWaves), block(64 * kJunctionWaves);
   snprintf(g_k2b_form, sizeof(g_k2b_form), "junction<%d,%d>", GA, GB);
-  if (ext) {
-    if (lds > 64 * 1024)
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(junction_kernel<GA, GB, true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL((junction_kernel<GA, GB, true>), grid, block, lds, stream, fam, n, gem, gcnt, jem, jrs, loglik,
-                       forward_out, scaler_out);
-  } else {
-    if (lds > 64 * 1024)
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(junction_kernel<GA, GB, false>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL((junction_kernel<GA, GB, false>), grid, block, lds, stream, fam, n, gem, gcnt, jem, jrs, loglik,
-                       forward_out, scaler_out);
-  }
+  with_bool(ext, [&](auto E) {
+    launch_lds(junction_kernel<GA, GB, decltype(E)::value>, dim3((n + kJunctionWaves - 1) / kJunctionWaves),
+               dim3(64 * kJunctionWaves), junction_lds_bytes(fam), stream, fam, n, gem, gcnt, jem, jrs, loglik,
+               forward_out, scaler_out);
+  });
 }
 
 template <int GA>
@@ -2121,28 +1923,32 @@ void launch_forward(const DevFamily& fam, const DevFamily* fam_dev, int n, int R
                     int32_t* gcnt, double* jem, int32_t* jrs, double* dxf, int32_t* dxc, double* loglik,
                     double* forward_out, int32_t* scaler_out, bool ext, hipStream_t stream, const LogEmRequest& lem) {
   const int slots = (fam.max_genes + kFwdThreads - 1) / kFwdThreads;
-#define LH_ARGS fam, fam_dev, n, R, site_lik, site_scal, pi, em_in, em_out, gem, gcnt, jem, jrs, ext, lem, stream
+  auto emission = [&](auto G) {
+    launch_emission_g<decltype(G)::value>(fam, fam_dev, n, R, site_lik, site_scal, pi, em_in, em_out, gem, gcnt, jem, jrs,
+                                          ext, lem, stream);
+  };
   if (slots <= 1)
-    launch_emission_g<1>(LH_ARGS);
+    emission(slots_c<1>{});
   else if (slots <= 2)
-    launch_emission_g<2>(LH_ARGS);
+    emission(slots_c<2>{});
   else
-    launch_emission_g<4>(LH_ARGS);
-#undef LH_ARGS
+    emission(slots_c<4>{});
   const int ga = (fam.vgerm.n_genes + 63) / 64;
   const int gb = (std::max(fam.dgerm.n_genes, fam.jgerm.n_genes) + 63) / 64;
-#define LH_ARGS gb, fam, n, gem, gcnt, jem, jrs, dxf, dxc, loglik, forward_out, scaler_out, ext, stream
+  auto junction = [&](auto G) {
+    launch_junction_a<decltype(G)::value>(gb, fam, n, gem, gcnt, jem, jrs, dxf, dxc, loglik, forward_out, scaler_out, ext,
+                                          stream);
+  };
   if (ga <= 1)
-    launch_junction_a<1>(LH_ARGS);
+    junction(slots_c<1>{});
   else if (ga <= 2)
-    launch_junction_a<2>(LH_ARGS);
+    junction(slots_c<2>{});
   else if (ga <= 4)
-    launch_junction_a<4>(LH_ARGS);
+    junction(slots_c<4>{});
   else if (ga <= 8)
-    launch_junction_a<8>(LH_ARGS);
+    junction(slots_c<8>{});
   else
-    launch_junction_a<16>(LH_ARGS);
-#undef LH_ARGS
+    junction(slots_c<16>{});
   // the sets K2a runs in consensus form (bits as lh_family_consensus_sets; none in the extended-range mode, which
   // walks every set with its counts) and how it walks the small ones -- for a sample whose emissions all lie in
   // (0, 1]; any other sample walks every set factor by factor (emission_kernel, em_bad)

@@ -130,10 +130,7 @@ void launch_candidates(const CandidateTables& t, int n, const double* lem, const
   if (lds8 <= 64 * 1024) {
     hipLaunchKernelGGL(score_kernel<8>, grid, dim3(kThreads), lds8, stream, t, n, lem, base, w, log_cand, partial);
   } else {
-    if (lds1 > 64 * 1024)
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(score_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lds1);
-    hipLaunchKernelGGL(score_kernel<1>, grid, dim3(kThreads), lds1, stream, t, n, lem, base, w, log_cand, partial);
+    launch_lds(score_kernel<1>, grid, dim3(kThreads), lds1, stream, t, n, lem, base, w, log_cand, partial);
   }
 }
 

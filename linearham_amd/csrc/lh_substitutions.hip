@@ -353,12 +353,10 @@ int launch_substitutions(const DevFamily& fam, int n, int R, int T, const int32_
   hipLaunchKernelGGL(sub_seed_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, n, T, P, seed_tip,
                      static_cast<const AsrOp*>(ws.desc), ws.chain, ws.plen, err_flag);
   auto run = [&](auto kernel, double* edge_part) {
-    if (lds > 64 * 1024)
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(kernel, dim3(R, n), dim3(kSubWaves * 64), lds, stream, R, T, L, fam.n_prune, P, seed_tip, fam.msa,
-                       fam.site_pat, static_cast<const AsrOp*>(ws.desc), brlen, rates, eig, pi, ws.tvec, rho, ws.chain, ws.plen,
-                       reinterpret_cast<double2*>(ws.clv), (int)anc_lp(fam.n_prune), sws.cc, sws.ne,
-                       out.seed_edge ? sws.se : nullptr, sws.el, edge_part);
+    launch_lds(kernel, dim3(R, n), dim3(kSubWaves * 64), lds, stream, R, T, L, fam.n_prune, P, seed_tip, fam.msa,
+               fam.site_pat, static_cast<const AsrOp*>(ws.desc), brlen, rates, eig, pi, ws.tvec, rho, ws.chain, ws.plen,
+               reinterpret_cast<double2*>(ws.clv), (int)anc_lp(fam.n_prune), sws.cc, sws.ne,
+               out.seed_edge ? sws.se : nullptr, sws.el, edge_part);
   };
   if (out.edge)
     run(sub_kernel<true>, sws.edge);

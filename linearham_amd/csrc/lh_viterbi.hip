@@ -392,12 +392,8 @@ template <int GA, int GB, bool kExt>
 void launch_viterbi_e(const DevFamily& fam, const DevSampler* smp_dev, int n, const double* gem, const int32_t* gcnt,
                       const double* jem, const int32_t* jrs, const double* loglik, uint8_t* bp, int32_t* states,
                       double* log_path, hipStream_t stream) {
-  const size_t lds = viterbi_lds(fam);
-  if (lds > 64 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(viterbi_kernel<GA, GB, kExt>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL((viterbi_kernel<GA, GB, kExt>), dim3((n + kVitWaves - 1) / kVitWaves), dim3(64 * kVitWaves), lds, stream,
-                     fam, smp_dev, n, gem, gcnt, jem, jrs, loglik, bp, viterbi_bp_bytes(fam), states, log_path);
+  launch_lds(viterbi_kernel<GA, GB, kExt>, dim3((n + kVitWaves - 1) / kVitWaves), dim3(64 * kVitWaves), viterbi_lds(fam),
+             stream, fam, smp_dev, n, gem, gcnt, jem, jrs, loglik, bp, viterbi_bp_bytes(fam), states, log_path);
 }
 
 template <int GA>
