@@ -169,6 +169,12 @@ const char* lh_family_forward_form(const lh_family* fam);
  * the first sweep.  Both layouts compute the same bits. */
 int lh_family_forward_dj_samples(const lh_family* fam);
 
+/* Diagnostic: waves per workgroup of that D-J kernel in the handle's last forward sweep: 4, 8 or 16 with four samples
+ * per wave (the smallest workgroup whose four emission slices per wave keep the pair form's occupancy within 160 KB of
+ * LDS per CU: it grows with the family's junction columns), the two-sample kernel's fixed workgroup otherwise; 0 for
+ * "junction<GA,GB>" and before the first sweep. */
+int lh_family_forward_dj_waves(const lh_family* fam);
+
 /* Opt-in extended-range mode (default off = the reference's arithmetic, overflows included).  The reference
  * loses a tree sample in two places: exp(lnL - log pi) underflows to 0 when a column's likelihood is below
  * 1e-308 (src/PhyloHMM.cpp:237), and the 2^(256 d) equalisation of a region's emission products to the LARGEST

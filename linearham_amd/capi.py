@@ -46,7 +46,7 @@ EXPORTS = ["lh_last_error", "lh_device_count", "lh_family_create", "lh_family_de
            "lh_profile_enable", "lh_profile_read", "lh_asr_profile_read", "lh_family_set_extended_range", "lh_warmup", "lh_host_alloc", "lh_host_free", "lh_family_set_sampler",
            "lh_sample_words", "lh_sample_states", "lh_eval_sample_batch", "lh_set_device", "lh_family_status",
            "lh_eval_sample_batch_device", "lh_family_prune_form", "lh_family_forward_form",
-           "lh_family_forward_dj_samples"]
+           "lh_family_forward_dj_samples", "lh_family_forward_dj_waves"]
 # K5 (exact posterior state marginals)
 POSTERIOR_EXPORTS = ["lh_eval_posterior_batch", "lh_eval_posterior_batch_device", "lh_posterior_profile_read"]
 EXPORTS += POSTERIOR_EXPORTS
@@ -241,6 +241,9 @@ class HipLibrary:
         if hasattr(lib, "lh_family_forward_dj_samples"):  # (absent from earlier builds loaded through LH_LIB_DIR)
             lib.lh_family_forward_dj_samples.argtypes = [C.c_void_p]
             lib.lh_family_forward_dj_samples.restype = C.c_int
+        if hasattr(lib, "lh_family_forward_dj_waves"):  # (likewise)
+            lib.lh_family_forward_dj_waves.argtypes = [C.c_void_p]
+            lib.lh_family_forward_dj_waves.restype = C.c_int
         lib.lh_schedule_tree.argtypes = [C.c_int32, c_i32p, C.c_int32, c_i32p, c_i32p]
         lib.lh_eval_batch.argtypes = _HOST_TREE + [c_f64p, C.POINTER(_EvalOutputs)]
         lib.lh_eval_batch_device.argtypes = _DEV_TREE + [C.c_void_p, C.POINTER(_EvalOutputs), C.c_void_p]
@@ -1008,6 +1011,11 @@ class Family:
         """Samples per wave of the last forward sweep's D-J kernel: 4 or 2 in the pair form, else 0
         (diagnostic, lh_family_forward_dj_samples)."""
         return int(self.hip.lib.lh_family_forward_dj_samples(self.handle))
+
+    def k2_dj_waves(self):
+        """Waves per workgroup of the last forward sweep's D-J kernel: 4, 8 or 16 with four samples per wave, the
+        two-sample kernel's own otherwise, 0 outside the pair form (diagnostic, lh_family_forward_dj_waves)."""
+        return int(self.hip.lib.lh_family_forward_dj_waves(self.handle))
 
     def status(self):
         """Synchronise the device and raise if a launch since the last call met a malformed (device-resident) schedule."""

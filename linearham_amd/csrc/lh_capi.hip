@@ -461,6 +461,7 @@ struct lh_family {
   std::string k1_form;          // the K1 kernel form of the last evaluation (lh_family_prune_form)
   std::string k2_form;          // the K2 kernels of the last forward sweep (lh_family_forward_form)
   int k2_dj_samples = 0;        // samples per wave of its D-J kernel (lh_family_forward_dj_samples)
+  int k2_dj_waves = 0;          // waves per workgroup of that kernel (lh_family_forward_dj_waves)
 };
 
 namespace {
@@ -779,6 +780,7 @@ int run_forward(lh_family* f, int n, int R, const double* site_lik, const int32_
                      fwd, sco, f->extended, stream, lem);
   f->k2_form = lh::forward_last_form();
   f->k2_dj_samples = lh::forward_last_dj_samples();
+  f->k2_dj_waves = lh::forward_last_dj_waves();
   LH_HIP(hipGetLastError());
   return 0;
 }
@@ -1403,6 +1405,7 @@ const char* lh_family_prune_form(const lh_family* f) { return f ? f->k1_form.c_s
 
 const char* lh_family_forward_form(const lh_family* f) { return f ? f->k2_form.c_str() : ""; }
 int lh_family_forward_dj_samples(const lh_family* f) { return f ? f->k2_dj_samples : 0; }
+int lh_family_forward_dj_waves(const lh_family* f) { return f ? f->k2_dj_waves : 0; }
 
 int lh_family_consensus_sets(const lh_family* f) {
   if (!f) return 0;

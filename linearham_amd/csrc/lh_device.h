@@ -668,6 +668,7 @@ const char* forward_last_form();
 // samples per wave of the D-J kernel that launch_forward ran: 4 (junction_dj4_kernel), 2 (junction_dj_kernel), 0 (K2b not
 // in the pair form)
 int forward_last_dj_samples();
+int forward_last_dj_waves();
 
 // K8 (lh_viterbi.hip): the most probable state path of each sample, from K2a's hand-off buffers as launch_forward has just
 // left them (gem, gcnt, jem, jrs) and the log-likelihoods K2b wrote.  states[n][states_per_sample] in K4's layout,

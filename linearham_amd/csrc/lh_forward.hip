@@ -45,6 +45,7 @@ constexpr int kJunctionWaves = 4;  // samples per K2b workgroup
 // what the calling thread's last launch_forward ran (forward_last_form): the launchers below write the two halves
 thread_local char g_k2a_form[64] = "", g_k2b_form[32] = "", g_forward_form[160] = "";
 thread_local int g_k2b_dj_samples = 0;  // samples per wave of the pair form's D-J kernel (forward_last_dj_samples)
+thread_local int g_k2b_dj_waves = 0;    // waves per workgroup of that kernel (forward_last_dj_waves)
 
 // Block-wide maximum: shuffles inside the wave, one LDS exchange, one barrier (red holds
 // 2 * kFwdWaves ints; `phase` alternates its halves so that a reduction never overwrites values
@@ -1848,6 +1849,7 @@ static void launch_dj(const DevFamily& fam, int n, const double* gem, const int3
   const size_t lds_dj = ((size_t)2 * kPairWaves * (fam.n_jcols + 1) + 16 * (size_t)fam.dj.right_pad) * sizeof(double);
   const int waves = dj4_waves(fam, lds_dj);
   g_k2b_dj_samples = waves == 0 ? 2 : 4;
+  g_k2b_dj_waves = waves == 0 ? kPairWaves : waves;
   auto kernel = junction_dj_kernel<kExt>;  // (the three kernels take the same arguments)
   size_t lds = lds_dj;
   dim3 grid(((n + 1) / 2 + kPairWaves - 1) / kPairWaves), block(64 * kPairWaves);
@@ -1864,7 +1866,7 @@ template <int GA, int GB>
 static void launch_junction_g(const DevFamily& fam, int n, const double* gem, const int32_t* gcnt, const double* jem,
                               const int32_t* jrs, double* dxf, int32_t* dxc, double* loglik, double* forward_out,
                               int32_t* scaler_out, bool ext, hipStream_t stream) {
-  g_k2b_dj_samples = 0;
+  g_k2b_dj_samples = g_k2b_dj_waves = 0;
   if constexpr (GB == 1) {
     if (junction_pair_form(fam)) {
       const size_t jem_slice = (size_t)fam.n_jcols + 1, ntt_vd = 16 * (size_t)fam.vd.right_pad;
@@ -1961,5 +1963,6 @@ void launch_forward(const DevFamily& fam, const DevFamily* fam_dev, int n, int R
 
 const char* forward_last_form() { return g_forward_form; }
 int forward_last_dj_samples() { return g_k2b_dj_samples; }
+int forward_last_dj_waves() { return g_k2b_dj_waves; }
 
 }  // namespace lh

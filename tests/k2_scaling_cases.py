@@ -25,6 +25,13 @@ COUNT_KEYS = ("vgerm_scaler_count", "vd_junction_scaler_counts", "dgerm_scaler_c
               "jgerm_scaler_count")
 BOUNDARY_RTOL = 1e-6       # condition (a)
 EXT_SPREAD_BITS = 900      # condition (c)
+# condition (c) for delta4: the extended-range mode equalises every set to its smallest count and keeps an allele down to
+# 2^-1024 below the set's best (fill_segments_ext; further down its product is a vanishing subnormal or 0).  delta4 puts
+# the counts of the V germline set four apart and those of the V padding set three: the alleles with the long padding
+# keep 2^-768 there and are the best of the germline set.  With BOTH sets four apart (their spreads then pass 1024 bits)
+# every V allele is 2^-1024 down in one of its two factors, the first forward vector holds zeros and subnormals only and
+# the mode returns -inf, as it says it does beyond that range.
+EXT_DELTA4_BITS = 1024
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -44,18 +51,41 @@ def family_specs():
         "igh_v260": sf.Spec.small(n_v=260, n_d=3, n_j=3, seed=62, **few),         # vd<8>+dj, K2a with two genes a thread
         # 24 V alleles on 296 sites: the V germline set in consensus form (test_consensus_products_equal_the_factor_walk)
         "igh_cons": sf.Spec(n_sites=400, n_v=24, n_d=6, n_j=4, seed=123, **few),
+        # the wide germline sets: GA = V alleles / 64 rounded up to 1, 2, 4, 8, 16; GB likewise (1, 2, 4) of the D / J sets
+        "igh_v70": sf.Spec.small(n_v=70, n_d=3, n_j=3, seed=63, **few),           # vd2<2>+dj
+        "igh_v130_d30_j12": sf.Spec.small(n_v=130, n_d=30, n_j=12, seed=64, **few),  # vd2<4>+dj, the benchmark's counts
+        "igh_v520": sf.Spec.small(n_v=520, n_d=3, n_j=3, seed=65, **few),         # vd<16>+dj, K2a with four genes a thread
+        "igh_d65": sf.Spec.small(n_v=5, n_d=65, n_j=5, seed=66, **few),           # junction<1,2>
+        "igh_j130": sf.Spec.small(n_v=5, n_d=3, n_j=130, seed=67, **few),         # junction<1,4>: GA < GB
+        "igh_v130_d70": sf.Spec.small(n_v=130, n_d=70, n_j=5, seed=68, **few),    # junction<4,2>
+        "igk_v70_j70": sf.Spec.small(locus="igk", n_v=70, n_j=70, seed=69, **few),   # junction<2,2>: light chain, GB > 1
+        "igh_v520_j130": sf.Spec.small(n_v=520, n_d=3, n_j=130, seed=70, **few),  # junction<16,4>
     }
 
 
 # seeds of (em0, k) per family, fixed so that conditions (a) to (d) hold (check_conditions)
-SEEDS = {"toy": 1, "small_igh": 1, "small_igk": 1, "igh_70_33_5": 1, "igh_v260": 1, "igh_cons": 1}
+SEEDS = {"toy": 1, "small_igh": 1, "small_igk": 1, "igh_70_33_5": 1, "igh_v260": 1, "igh_cons": 1,
+         # (igh_v130_d30_j12 at seed 1 and igh_v520 at seeds 1 to 6: the k that puts two counts four apart, 504 bits on
+         # either coverage site, brings one of the 130 / 520 running products within 1e-3 of a boundary; delta4's search
+         # goes on to 512 a site, and every V allele is then more than 2^-1024 below the best of its padding or of its
+         # germline set -- EXT_DELTA4_BITS)
+         "igh_v70": 1, "igh_v130_d30_j12": 2, "igh_v520": 7, "igh_d65": 1, "igh_j130": 1, "igh_v130_d70": 1,
+         "igk_v70_j70": 1, "igh_v520_j130": 1}
 
 
 # cases each family must be able to express (build_cases leaves out what a layout cannot: the toy family's V alleles have
 # fewer than eight germline factors and all start at the same site)
 _ALL = ("chunk_fast", "chunk_step", "chunk_fast_j", "chunk_step_j", "exact", "exact_below", "zero", "delta3", "delta4", "row3")
 NEED = {"toy": ("exact", "exact_below", "zero", "row3"), "small_igh": _ALL, "small_igk": _ALL, "igh_70_33_5": _ALL,
-        "igh_v260": _ALL, "igh_cons": _ALL}
+        "igh_v260": _ALL, "igh_cons": _ALL,
+        "igh_v70": _ALL, "igh_v130_d30_j12": _ALL, "igh_v520": _ALL, "igh_j130": _ALL,
+        # (no delta4, at any seed: its five V alleles differ in coverage on ONE site, and a single emission stays a normal
+        # number only to 2^-960 -- short of the 2^-1024 that puts two counts of a set four apart)
+        "igh_d65": tuple(n for n in _ALL if n != "delta4"),
+        "igh_v130_d70": _ALL, "igk_v70_j70": _ALL, "igh_v520_j130": _ALL}
+
+# the families of the wide germline sets (GA or GB above 1 in a form no other family reaches)
+WIDE = ("igh_v70", "igh_v130_d30_j12", "igh_v520", "igh_d65", "igh_j130", "igh_v130_d70", "igk_v70_j70", "igh_v520_j130")
 
 
 def load_family(name, workdir):
@@ -331,7 +361,9 @@ def build_cases(h, seed):
                                                                     and set_gap(w, "vgerm") == 3)):
                 both = set_gap(w, "vpadding") == 3 and set_gap(w, "vgerm") == 3
                 found[3] = k
-            if gap == 4 and w["near"] > 1e-3:
+            # (EXT_DELTA4_BITS: where the 16-bit step that first gives 4 is near a boundary, the next one puts BOTH V sets
+            # four apart and no allele is left for the extended-range mode; the family then has no delta4 at this seed)
+            if gap == 4 and w["near"] > 1e-3 and ext_spread_bits(w) < EXT_DELTA4_BITS:
                 found[4] = k
             if 4 in found:
                 break
@@ -348,19 +380,28 @@ def build_cases(h, seed):
 
     # row3: one junction row that needs three rescalings at once (row_scale k3 = 3).  2^-700 on the first junction site
     # whose row then falls below 2^-768 at its smallest entry; a little more where no row is that small at 700
-    done = False
-    for kk in (700, 720, 740, 760):
-        for s in _junction_sites(h):
-            k = zero_k.copy()
-            k[s] = kk
-            r = oracle_eval(h, np.ldexp(em0, -k[site]))
-            if any(n == 3 for _, n in r["rows"]) and all(lo >= 2.0 ** -1022 for lo, _ in r["rows"]):
-                cases.append(Case("row3", em0, k, site, base="base"))
-                done = True
-                break
-        if done:
-            break
+    def row3(name, sites, hit):
+        for kk in (700, 720, 740, 760):
+            for s in sites:
+                k = zero_k.copy()
+                k[s] = kk
+                r = oracle_eval(h, np.ldexp(em0, -k[site]))
+                if hit(r) and all(lo >= 2.0 ** -1022 for lo, _ in r["rows"]):
+                    cases.append(Case(name, em0, k, site, base="base"))
+                    return
+    row3("row3", _junction_sites(h), lambda r: any(n == 3 for _, n in r["rows"]))
+    # row3_dj: the same on a row of the D-J junction (the search above tries the V-D sites first and stops there on every
+    # family whose V-D junction has a row that small): the right-gene sweep of the D-J kernels with k3 = 3
+    if h.locus == "igh":
+        fb = h.flexbounds
+        row3("row3_dj", range(fb["d_r"][0], fb["j_l"][1]), lambda r: 3 in dj_increments(r))
     return site, cases
+
+
+def dj_increments(oracle):
+    """how often each D-J junction row rescaled: the steps of the cumulative count from the D germline region's on"""
+    c = [int(oracle["dgerm_scaler_count"])] + [int(x) for x in oracle["dj_junction_scaler_counts"]]
+    return [b - a for a, b in zip(c, c[1:])]
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -409,6 +450,8 @@ def check_conditions(h, cases, refs, need=()):
         #     is reported by ext_spread_bits and the extended-range check of that case stands on its own
         if c.name != "delta4":
             assert ext_spread_bits(w) <= EXT_SPREAD_BITS, (c.name, ext_spread_bits(w))
+        else:
+            assert ext_spread_bits(w) < EXT_DELTA4_BITS, (c.name, ext_spread_bits(w))
         # (d) overflow exactly on delta4
         assert np.isfinite(r["loglik"]) == (c.expect == "finite"), (c.name, r["loglik"])
         assert (max_gap(w) >= 4) == (c.expect == "overflow"), (c.name, max_gap(w))
@@ -445,6 +488,8 @@ def check_conditions(h, cases, refs, need=()):
         assert np.isfinite(refs["delta4_spread"]["oracle"]["loglik"])
     if "row3" in by:
         assert any(n == 3 for _, n in refs["row3"]["oracle"]["rows"])
+    if "row3_dj" in by:
+        assert 3 in dj_increments(refs["row3_dj"]["oracle"])
 
 
 def _check_chunk(h, by, refs, set_name, fast, step):

@@ -4,7 +4,12 @@ K2b picks among four launch shapes (launch_junction_g: junction_vd2_kernel + jun
 ScaleMatrix count per half; junction_vd_kernel + junction_dj_kernel beyond 256 V alleles; junction_kernel<GA, GB> for light
 chains and for more than 32 D or J alleles; the hooks LH_K2B_NO_PAIR and LH_K2B_VD_SINGLE), K2a among four product walks
 (fill_segments with its chunk fast path and its step-by-step path, fill_segments_wave, fill_consensus, fill_segments_ext)
-and a per-sample fallback out of the consensus form (em_bad).  Which branch a row takes depends on its emissions, and
+and a per-sample fallback out of the consensus form (em_bad).  The wide germline sets pick the register chunks: GA = 1, 2,
+4, 8, 16 for up to 64, 128, 256, 512, 1024 V alleles, GB = 1, 2, 4 for up to 64, 128, 256 D or J alleles, and K2a's gene
+slots per thread (1, 2, 4 for up to 256, 512, 1024 alleles in a set); K2B below names a family for every GA of the pair
+forms and of junction<GA,1>, for GB = 2 and 4 with GA below, equal to and above GB, and for a light chain with GB = 2.
+
+Which branch a row takes depends on its emissions, and
 lh_forward_batch takes the caller's: tests/k2_scaling_cases.py builds emission vectors that reach each branch, with a
 reference that shares nothing with ScaleMatrix -- multiplying every column of alignment site t by 2^-k_t moves the
 log-likelihood by exactly -ln 2 * sum(k) (checked on the oracle in tests/test_k2_scaling_cases_cpu.py).
@@ -47,13 +52,27 @@ K2B = {
     "igh_70_33_5": (r"junction<2,1>",) * 3,                                  # 33 D alleles: one wave per sample
     "igh_v260": (r"vd<8>\+dj", r"junction<8,1>", r"vd<8>\+dj"),              # more than 256 V alleles
     "igh_cons": (r"vd2<1>\+dj", r"junction<1,1>", r"vd<1>\+dj"),
+    # the wide germline sets; GB = ceil(max(D alleles, J alleles) / 64) rounded up to 1, 2, 4
+    "igh_v70": (r"vd2<2>\+dj", r"junction<2,1>", r"vd<2>\+dj"),
+    "igh_v130_d30_j12": (r"vd2<4>\+dj", r"junction<4,1>", r"vd<4>\+dj"),       # the benchmark workload's kernels
+    "igh_v520": (r"vd<16>\+dj", r"junction<16,1>", r"vd<16>\+dj"),
+    "igh_d65": (r"junction<1,2>",) * 3,
+    "igh_j130": (r"junction<1,4>",) * 3,                                      # GA < GB
+    "igh_v130_d70": (r"junction<4,2>",) * 3,
+    "igk_v70_j70": (r"junction<2,2>",) * 3,                                   # light chain with GB > 1
+    "igh_v520_j130": (r"junction<16,4>",) * 3,
 }
-K2A_SLOTS = {"igh_v260": 2}     # gene slots per K2a thread (more than 256 alleles in a set): 1 everywhere else
+# gene slots per K2a thread (more than 256, more than 512 alleles in a set): 1 everywhere else
+K2A_SLOTS = {"igh_v260": 2, "igh_v520": 4, "igh_v520_j130": 4}
+# more than 64 D or J alleles: the small sets walk on the whole workgroup, not a wave each
+SMALL_BY_BLOCK = ("igh_d65", "igh_j130", "igh_v130_d70", "igk_v70_j70", "igh_v520_j130")
 SETTINGS = {
     "default": ({}, list(K2B)),
-    "no_pair": ({"LH_K2B_NO_PAIR": "1"}, ["toy", "small_igh", "igh_v260", "igh_cons"]),
-    "vd_single": ({"LH_K2B_VD_SINGLE": "1"}, ["toy", "small_igh", "igh_cons"]),
-    "k2a_direct": ({"LH_K2A_DIRECT": "1"}, ["toy", "small_igh", "igh_70_33_5", "igh_cons"]),
+    "no_pair": ({"LH_K2B_NO_PAIR": "1"}, ["toy", "small_igh", "igh_v260", "igh_cons", "igh_v70", "igh_v130_d30_j12",
+                                          "igh_v520"]),
+    "vd_single": ({"LH_K2B_VD_SINGLE": "1"}, ["toy", "small_igh", "igh_cons", "igh_v70", "igh_v130_d30_j12"]),
+    "k2a_direct": ({"LH_K2A_DIRECT": "1"}, ["toy", "small_igh", "igh_70_33_5", "igh_cons", "igh_v130_d30_j12", "igh_j130",
+                                            "igk_v70_j70"]),
 }
 
 
@@ -99,11 +118,15 @@ def test_k2_forms_at_the_rescaling_edges(references, setting):
     for family in SETTINGS[setting][1]:
         for mode in ("default", "extended"):
             info = report[family][mode]
+            dev = info["deviation"]
+            print("%s %s %s: %s, log-likelihood against the identity %.2e, forward arrays against the oracle %.2e"
+                  % (setting, family, mode, info["form"], dev["loglik"], dev["forward"]))
             assert info["n"] >= 17 and info["n"] % 2 == 1
             ext = mode == "extended"
             # the extended-range mode walks every set with its counts (fill_segments_ext): no consensus form, no waves
             k2a = r"emission<%d,caller,(byte|index)%s> cons=%s small=%s" % (
-                K2A_SLOTS.get(family, 1), ",ext" if ext else "", "0" if ext else r"\d+", "block" if ext else r"(wave|block)")
+                K2A_SLOTS.get(family, 1), ",ext" if ext else "", "0" if ext else r"\d+",
+                "block" if ext or family in SMALL_BY_BLOCK else r"(wave|block)")
             pattern = k2a + r" \| " + K2B[family][col]
             assert re.fullmatch(pattern, info["form"]), (family, mode, info["form"], pattern)
             cons = int(re.search(r"cons=(\d+)", info["form"]).group(1))
@@ -112,8 +135,8 @@ def test_k2_forms_at_the_rescaling_edges(references, setting):
                 assert info["consensus_sets"] == 0 and cons == 0, (family, info)
             elif family == "igh_cons":
                 assert info["consensus_sets"] & 2, "the V germline set of this family should be in consensus form"
-            if not ext and info["consensus_sets"] == 0:
-                assert "small=wave" in info["form"], (family, info["form"])   # at most 64 D and J alleles everywhere here
+            if not ext and info["consensus_sets"] == 0 and family not in SMALL_BY_BLOCK:
+                assert "small=wave" in info["form"], (family, info["form"])   # at most 64 D and J alleles
 
 
 def test_k2_forms_agree_with_each_other(references):

@@ -96,7 +96,10 @@ def crafted(tmp_path_factory):
         if name not in cache:
             h = kc.load_family(name, work)
             _, cases = kc.build_cases(h, kc.SEEDS[name])
-            rng = np.random.default_rng(1000 + sorted(kc.family_specs()).index(name))
+            # (a family's random vectors go by its place among the sorted names; the wide germline sets, added later,
+            # stand behind the others so that no earlier family's vectors moved)
+            order = sorted(n for n in kc.family_specs() if n not in kc.WIDE) + sorted(kc.WIDE)
+            rng = np.random.default_rng(1000 + order.index(name))
             rand = rng.uniform(0.05, 1.0, size=(N_RANDOM, len(cases[0].em)))
             refs = {}
             for nm, em in [(c.name, c.em) for c in cases if c.sum_k == 0] + [("random%d" % i, e) for i, e in enumerate(rand)]:
@@ -108,7 +111,8 @@ def crafted(tmp_path_factory):
     return get
 
 
-@pytest.mark.parametrize("name", sorted(kc.family_specs()))
+# (every family but the two of 520 V alleles: the numpy Viterbi of their 26 vectors alone takes eleven seconds apiece)
+@pytest.mark.parametrize("name", sorted(n for n in kc.family_specs() if n not in ("igh_v520", "igh_v520_j130")))
 def test_crafted_emissions(hip, crafted, name):
     h, cases, rand, refs = crafted(name)
     for nm, ref in refs.items():
