@@ -496,6 +496,19 @@ int lh_family_status(lh_family* fam);
 int lh_forward_batch(lh_family* fam, int32_t n, const double* em, double* loglik,
                      const lh_eval_outputs* outs);
 
+/* K4 on caller-supplied per-column emissions em[n][C] (host pointers), beside lh_forward_batch: the forward sweep with the
+ * forward arrays kept on the device, then the draws of lh_eval_sample_batch from words [n][lh_sample_words()] into states
+ * [n][lh_sample_states()] (its layout and encoding).  loglik [n] may be NULL; outs may be NULL, and of its members forward
+ * and scaler_counts are written: the arrays K4 drew from.  Honours lh_family_set_extended_range; needs
+ * lh_family_set_sampler. */
+int lh_sample_forward_batch(lh_family* fam, int32_t n, const double* em, const uint32_t* words, double* loglik,
+                            int32_t* states, const lh_eval_outputs* outs);
+
+/* K5 on caller-supplied per-column emissions em[n][C] (host pointers): loglik [n] and posterior [n][lh_forward_size()] as
+ * lh_posterior_outputs describes them (either may be NULL).  The twin of lh_viterbi_forward_batch; honours
+ * lh_family_set_extended_range; needs lh_family_set_sampler. */
+int lh_posterior_forward_batch(lh_family* fam, int32_t n, const double* em, double* loglik, double* posterior);
+
 /* Ancestral-sequence sampling (scripts/run_bootstrap_asr_ess.R:48-104) for n tree samples of the family:
  * per alignment site, draw a rate category with the likelihoods of the column (naive base on the `naive`
  * tip) on the rate-scaled trees, then draw the states of all inner nodes jointly given the tips on the

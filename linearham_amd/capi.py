@@ -47,6 +47,9 @@ EXPORTS = ["lh_last_error", "lh_device_count", "lh_family_create", "lh_family_de
            "lh_sample_words", "lh_sample_states", "lh_eval_sample_batch", "lh_set_device", "lh_family_status",
            "lh_eval_sample_batch_device", "lh_family_prune_form", "lh_family_forward_form",
            "lh_family_forward_dj_samples", "lh_family_forward_dj_waves"]
+# K4 and K5 on caller-supplied emissions
+CRAFTED_EXPORTS = ["lh_sample_forward_batch", "lh_posterior_forward_batch"]
+EXPORTS += CRAFTED_EXPORTS
 # K5 (exact posterior state marginals)
 POSTERIOR_EXPORTS = ["lh_eval_posterior_batch", "lh_eval_posterior_batch_device", "lh_posterior_profile_read"]
 EXPORTS += POSTERIOR_EXPORTS
@@ -258,6 +261,10 @@ class HipLibrary:
             lib.lh_eval_sample_batch_device.argtypes = _DEV_TREE + [C.c_void_p] * 5
             lib.lh_sample_words.argtypes = [C.c_void_p]
             lib.lh_sample_states.argtypes = [C.c_void_p]
+        if hasattr(lib, "lh_sample_forward_batch"):
+            lib.lh_sample_forward_batch.argtypes = [C.c_void_p, C.c_int32, c_f64p, c_u32p, c_f64p, c_i32p,
+                                                    C.POINTER(_EvalOutputs)]
+            lib.lh_posterior_forward_batch.argtypes = [C.c_void_p, C.c_int32, c_f64p, c_f64p, c_f64p]
         if hasattr(lib, "lh_eval_posterior_batch"):
             lib.lh_eval_posterior_batch.argtypes = _HOST_TREE + [C.POINTER(_PosteriorOutputs)]
             lib.lh_eval_posterior_batch_device.argtypes = _DEV_TREE + [C.POINTER(_PosteriorOutputs), C.c_void_p]
@@ -657,6 +664,37 @@ class HipLibrary:
         self.check(self.lib.lh_viterbi_forward_batch(h, n, em.ctypes.data_as(c_f64p), lp.ctypes.data_as(c_f64p),
                                                      st.ctypes.data_as(c_i32p)))
         return lp, st
+
+    def sample_forward_batch(self, family, em, words, want=()):
+        """K2 + K4 on caller emissions em [n][C] and engine words [n][lh_sample_words]: (loglik [n], states
+        [n, lh_sample_states], dict with the members of `want`: forward [n, forward_size], scaler_counts [n, scaler_size] --
+        the arrays K4 drew from)."""
+        h = _handle(family)
+        em = _f64(em)
+        n = em.shape[0]
+        words = np.ascontiguousarray(words, dtype=np.uint32)
+        if words.shape != (n, int(self.lib.lh_sample_words(h))):
+            raise ValueError("lh_sample_forward_batch: words must be [n][lh_sample_words]")
+        ll = np.zeros(n)
+        st = np.zeros((n, self.sample_states(h)), dtype=np.int32)
+        res, outs = _outputs(_EvalOutputs, [w for w in want if w in ("forward", "scaler_counts")],
+                             forward=(n, self.lib.lh_forward_size(h)),
+                             scaler_counts=((n, self.lib.lh_scaler_size(h)), np.int32))
+        self.check(self.lib.lh_sample_forward_batch(h, n, em.ctypes.data_as(c_f64p),
+                                                    words.ctypes.data_as(C.POINTER(C.c_uint32)), ll.ctypes.data_as(c_f64p),
+                                                    st.ctypes.data_as(c_i32p), C.byref(outs)))
+        return ll, st, res
+
+    def posterior_forward_batch(self, family, em):
+        """K2 + K5 on caller emissions em [n][C]: (loglik [n], posterior [n, forward_size])."""
+        h = _handle(family)
+        em = _f64(em)
+        n = em.shape[0]
+        ll = np.zeros(n)
+        post = np.zeros((n, self.lib.lh_forward_size(h)))
+        self.check(self.lib.lh_posterior_forward_batch(h, n, em.ctypes.data_as(c_f64p), ll.ctypes.data_as(c_f64p),
+                                                       post.ctypes.data_as(c_f64p)))
+        return ll, post
 
     def set_candidate_paths(self, family, states):
         """Registers state paths states [K][lh_sample_states] as the handle's candidates (their naive sequences, with
@@ -1232,6 +1270,16 @@ class Family:
         """(log_path [n], states [n][S]) of caller emissions em [n][C] (set_sampler first)."""
         assert _f64(em).shape[1] == self.n_xmsa
         return self.hip.viterbi_forward_batch(self.handle, em)
+
+    def sample_forward_batch(self, em, words, want=()):
+        """(loglik [n], states [n][S], dict of `want`) of caller emissions em [n][C] and engine words (set_sampler first)."""
+        assert _f64(em).shape[1] == self.n_xmsa
+        return self.hip.sample_forward_batch(self.handle, em, words, want)
+
+    def posterior_forward_batch(self, em):
+        """(loglik [n], posterior [n][forward_size]) of caller emissions em [n][C] (set_sampler first)."""
+        assert _f64(em).shape[1] == self.n_xmsa
+        return self.hip.posterior_forward_batch(self.handle, em)
 
     def profile_enable(self, on=True):
         self.hip.check(self.hip.lib.lh_profile_enable(self.handle, int(on)))

@@ -30,6 +30,7 @@ const DebugOptions& debug_options() {
     o.k2b_vd_single = set("LH_K2B_VD_SINGLE");
     o.k2b_dj_pair = set("LH_K2B_DJ_PAIR");
     o.sample_timing = set("LH_SAMPLE_TIMING");
+    o.k4_no_save = set("LH_K4_NO_SAVE");
     o.k1_tile_cap = num("LH_K1_TILE_CAP", 0);
     o.k1_cxx_walk = set("LH_K1_CXX_WALK");
     o.k1_tables = set("LH_K1_TABLES");
@@ -2888,6 +2889,62 @@ int lh_forward_batch(lh_family* f, int32_t n, const double* em, double* loglik, 
                    {{loglik, out.loglik.get(), sizeof(double) * n},
                     {o.forward, d_outs.forward, sizeof(double) * FS * n},
                     {o.scaler_counts, d_outs.scaler_counts, sizeof(int32_t) * SS * n}});
+}
+
+int lh_sample_forward_batch(lh_family* f, int32_t n, const double* em, const uint32_t* words, double* loglik, int32_t* states,
+                            const lh_eval_outputs* outs) {
+  const std::string W = "lh_sample_forward_batch";
+  if (!f) return fail(W + ": null family");
+  DeviceGuard guard(f);
+  if (!f->have_sampler) return fail(W + ": lh_family_set_sampler has not been called");
+  if (n <= 0) return n == 0 ? 0 : fail(W + ": negative batch size");
+  if (!em || !words || !states) return fail(W + ": null array");
+  const size_t C = f->host.n_xmsa, FS = f->host.forward_size, SS = f->host.scaler_size;
+  const size_t NW = f->sampler.words_per_sample, S = f->sampler.states_per_sample;
+  const lh_eval_outputs none{};
+  const lh_eval_outputs& o = outs ? *outs : none;
+  HostOutputs& out = f->out;
+  // the forward arrays stay where K4 reads them (as in lh_eval_sample_batch); outs->forward is a copy of exactly those
+  lh_eval_outputs d_outs{};
+  if (out.loglik.ensure(sizeof(double) * n) || out.states.ensure(sizeof(int32_t) * S * n) ||
+      f->forward_dev.ensure(sizeof(double) * FS * n) ||
+      out_buf(o.scaler_counts, out.scaler_counts, sizeof(int32_t) * SS * n, &d_outs.scaler_counts) ||
+      stage_inputs(f, {{em, sizeof(double) * C * n, &f->in.em}, {words, sizeof(uint32_t) * NW * n, &f->in.words}}))
+    return 1;
+  d_outs.forward = f->forward_dev.get<double>();
+  if (run_forward(f, n, 1, nullptr, nullptr, nullptr, f->in.em.get<const double>(), nullptr, out.loglik.get<double>(),
+                  &d_outs, 0, nullptr))
+    return 1;
+  lh::launch_sample(f->sampler, f->sampler_dev, n, d_outs.forward, FS, f->in.words.get<const uint32_t>(), (int)NW,
+                    out.states.get<int32_t>(), nullptr);
+  LH_HIP(hipGetLastError());
+  return copy_back(f, nullptr,
+                   {{loglik, out.loglik.get(), sizeof(double) * n},
+                    {states, out.states.get(), sizeof(int32_t) * S * n},
+                    {o.forward, d_outs.forward, sizeof(double) * FS * n},
+                    {o.scaler_counts, d_outs.scaler_counts, sizeof(int32_t) * SS * n}});
+}
+
+int lh_posterior_forward_batch(lh_family* f, int32_t n, const double* em, double* loglik, double* posterior) {
+  const std::string W = "lh_posterior_forward_batch";
+  if (!f) return fail(W + ": null family");
+  DeviceGuard guard(f);
+  if (!f->have_sampler) return fail(W + ": lh_family_set_sampler has not been called");
+  if (n <= 0) return n == 0 ? 0 : fail(W + ": negative batch size");
+  if (!em) return fail(W + ": null array");
+  const size_t C = f->host.n_xmsa, FS = f->host.forward_size;
+  HostOutputs& out = f->out;
+  if (out.loglik.ensure(sizeof(double) * n) || f->forward_dev.ensure(sizeof(double) * FS * n) ||
+      stage_inputs(f, {{em, sizeof(double) * C * n, &f->in.em}}))
+    return 1;
+  double* post = f->forward_dev.get<double>();  // K5 overwrites the forward arrays in place
+  lh_eval_outputs eo{nullptr, nullptr, post, nullptr};
+  if (run_forward(f, n, 1, nullptr, nullptr, nullptr, f->in.em.get<const double>(), nullptr, out.loglik.get<double>(), &eo, 0,
+                  nullptr))
+    return 1;
+  lh::launch_posterior(f->sampler_dev, n, post, FS, out.loglik.get<const double>(), nullptr);
+  LH_HIP(hipGetLastError());
+  return copy_back(f, nullptr, {{loglik, out.loglik.get(), sizeof(double) * n}, {posterior, post, sizeof(double) * FS * n}});
 }
 
 int lh_eval_posterior_batch_device(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops,

@@ -705,6 +705,8 @@ struct DebugOptions {
   bool k2b_vd_single = false;  // LH_K2B_VD_SINGLE: one sample per V-D wave
   bool k2b_dj_pair = false;    // LH_K2B_DJ_PAIR: two samples per D-J wave (junction_dj_kernel) where four would run
   bool sample_timing = false;  // LH_SAMPLE_TIMING: stage times of every lh_eval_sample_batch call on stderr
+  bool k4_no_save = false;     // LH_K4_NO_SAVE: K4 forms a draw's weights again in each pass (the form of families wider than
+                               // 256 genes, launch_sample) whatever the family's width
   int k1_tile_cap = 0;         // LH_K1_TILE_CAP=<sites>: small K1 tiles, so that small families run the multi-tile path
   bool k1_cxx_walk = false;    // LH_K1_CXX_WALK: the cherry-table form with its C++ walk instead of the assembly one
   bool k1_tables = false;      // LH_K1_TABLES: the cherry-table form for large trees too (which take the segmented register-stack form)

@@ -425,7 +425,8 @@ void launch_sample(const DevSampler& smp, const DevSampler* smp_dev, int n, cons
   // per workgroup): 256 genes; wider families form them again in each pass
   int widest = std::max(std::max(smp.n_v, smp.n_j), std::max(smp.vd.n_left, smp.has_d ? std::max(smp.n_d, smp.dj.n_left) : 0));
   widest = (widest + kG - 1) / kG * kG;
-  const int save_cap = widest <= 256 ? widest : 0;
+  static const bool no_save = debug_options().k4_no_save;  // test hook: the recompute form for every width
+  const int save_cap = widest <= 256 && !no_save ? widest : 0;
   const size_t dyn = (size_t)per_block * save_cap * sizeof(double);
   hipLaunchKernelGGL(sample_kernel, dim3((n + per_block - 1) / per_block), dim3(64 * kSampleWaves), dyn, stream, smp_dev, n,
                      fwd, forward_size, words, words_per_sample, states, save_cap);

@@ -272,8 +272,19 @@ def generate_canonical(rng):
     return r
 
 
+def _ieee_div(x, y):
+    """x / y of two Python floats as IEEE 754 defines it (Python raises on a zero divisor)."""
+    if y != 0.0:
+        return x / y          # (NaN and inf operands propagate as in C)
+    if x != x or x == 0.0:
+        return math.nan       # NaN / 0, 0 / 0
+    return math.copysign(math.inf, x) * math.copysign(1.0, y)
+
+
 def discrete_distribution_draw(weights, rng):
-    """std::discrete_distribution<int>::operator() (bits/random.tcc:2656-2713)."""
+    """std::discrete_distribution<int>::operator() (bits/random.tcc:2656-2713).  The quotients are IEEE divisions, as in
+    C++: x / 0 is inf or NaN (a vector without a positive weight gives 0 / 0 throughout, no partial sum compares below
+    the uniform and lower_bound ends on element 0), never an exception."""
     w = [float(x) for x in weights]
     if len(w) < 2:
         return 0  # no RNG draw
@@ -283,7 +294,7 @@ def discrete_distribution_draw(weights, rng):
     cp = []
     acc = 0.0
     for x in w:
-        acc += x / total
+        acc += _ieee_div(x, total)
         cp.append(acc)
     cp[-1] = 1.0
     p = generate_canonical(rng)

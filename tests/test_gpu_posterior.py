@@ -353,6 +353,74 @@ def test_extended_range_overflow_row(tmp_path):
         assert np.max(np.abs(dense[region] - want[region])) < BOUND, region
 
 
+CRAFTED = ("toy", "small_igh", "small_igk", "igh_70_33_5", "igh_v130_d30_j12", "igh_v260", "igh_d65", "igk_v70_j70")
+
+
+@pytest.mark.parametrize("name", CRAFTED)
+def test_crafted_emissions(tmp_path, name):
+    """lh_posterior_forward_batch on the cases of tests/k2_scaling_cases.py, the rows of its batch_order, in both range modes
+    (as test_gpu_events.py::test_crafted_emissions does for K10): scaling every column of a site by 2^-k changes no
+    posterior, so every deep case's posterior equals its base's to 1e-12; base cases against posterior_oracle.smoothing on
+    the same emissions; site marginals sum to 1; delta4 overflows the default mode (log-likelihood not finite, posterior
+    NaN) and is finite and equal to its base in the extended-range mode; every row bit-equal alone, as row 1 of a call of
+    two, and in the full call."""
+    from linearham_amd.capi import load_library
+    from tests import k2_scaling_cases as kc
+    from tests import viterbi_cases as vc
+    from tests import viterbi_oracle as vo
+    hip = load_library()
+    h = kc.load_family(name, tmp_path)
+    _, cases = kc.build_cases(h, kc.SEEDS[name])
+    by = {c.name: c for c in cases}
+    want = {}
+    for c in cases:
+        if c.sum_k == 0:
+            vo.set_emissions(h, c.em)
+            h.cache_forward = True  # (new emissions: the forward arrays of the last vector are stale)
+            assert np.isfinite(h.log_likelihood())
+            want[c.name] = po.to_compact(h, po.smoothing(h))
+    assert "base" in want and all(c.base in want for c in cases)
+    order = kc.batch_order(cases)
+    assert set(order) == set(by) and len(order) >= 17 and len(order) % 2 == 1
+    em = np.stack([by[n].em for n in order])
+    ss = po.state_space(h)
+    lay = lp.layout(ss)
+    fam = vc.device_family(hip, h)
+    finite = {}
+    for ext in (False, True):
+        fam.set_extended_range(ext)
+        ll, post = fam.posterior_forward_batch(em)
+        assert post.shape == (len(order), fam.forward_size)
+        first = {}
+        for i, n in enumerate(order):
+            j = first.setdefault(n, i)
+            assert ll[i:i + 1].tobytes() + post[i].tobytes() == ll[j:j + 1].tobytes() + post[j].tobytes(), (n, i, j)
+        for n, i in first.items():
+            l1, p1 = fam.posterior_forward_batch(by[n].em[None])
+            l2, p2 = fam.posterior_forward_batch(np.stack([by["base"].em, by[n].em]))
+            mine = ll[i:i + 1].tobytes() + post[i].tobytes()
+            assert l1.tobytes() + p1[0].tobytes() == mine, (n, ext, "alone")
+            assert l2[1:2].tobytes() + p2[1].tobytes() == mine, (n, ext, "row 1 of a call of two")
+            if by[n].expect == "overflow" and not ext:
+                assert not np.isfinite(ll[i]) and np.all(np.isnan(post[i])), (n, ll[i])
+                continue
+            assert np.isfinite(ll[i]) and np.all(np.isfinite(post[i])), (n, ext)
+            d_base = np.max(np.abs(post[i] - post[first[by[n].base]]))
+            d_orc = np.max(np.abs(post[i] - want[by[n].base]))
+            d_sum = np.max(np.abs(lp.site_base(ss, post[i], lay).sum(axis=1) - 1.0))
+            print(name, "ext" if ext else "default", n, "vs base", d_base, "vs oracle", d_orc, "site sums", d_sum)
+            assert d_base < 1e-12, (n, ext, d_base)
+            assert d_orc < BOUND, (n, ext, d_orc)
+            assert d_sum < 1e-12, (n, ext, d_sum)
+        finite[ext] = {n: post[i] for n, i in first.items() if np.isfinite(ll[i])}
+    assert set(finite[True]) == set(by) and len(finite[False]) >= len(by) - 1
+    if "delta4" in by:
+        assert "delta4" not in finite[False]
+    for n in finite[False]:
+        assert np.max(np.abs(finite[False][n] - finite[True][n])) < 1e-12, n
+    fam.close()
+
+
 def test_one_handle_through_every_entry_point():
     """One family handle, profiling on, through every batched entry point -- the evaluation, the forward sweep, K3 to K9,
     the lineages and the chain, and their _device forms -- in turn, neighbours sharing a buffer, for batch sizes that grow
