@@ -20,7 +20,7 @@
 //    so a cell is a sum in a fixed order.  What no state writes stays N: N takes 1 - (the five sums).  A row without a
 //    posterior (non-finite log-likelihood) is NaN.
 //  * K11r (anc_rate_kernel), a thread per (sample, site): t_j[5] and rho_j[R] from the planes, scaler counts aligned to the
-//    smallest as K3a does.
+//    smallest (RatePlanes, lh_treepass.h).
 //  * K3s (lh_asr.hip) writes the schedule descriptors; K11c (anc_chain_kernel), a workgroup per sample, checks the path against
 //    them -- entries outside T .. 2T-3 are padding and come last, each entry is a child of the next, the last one is the
 //    root -- and writes per slot the op that produced the node and which of that op's children continues the path.  No index
@@ -29,13 +29,14 @@
 //  * K11b (anc_kernel), a workgroup per (rate category, sample) so that P-matrices are wave-uniform: K3b's LDS tables (tip
 //    table, inner P-matrices by op), K3b's upward pass over ALL site patterns of the family (a lane per pattern, every
 //    inner CLV stored: clv[sample][rate][op][2][pattern] of 16-byte entries), then the downward pass along the path, a lane
-//    per site: P mat-vecs, not T - 2.  The message from above is divided by its largest entry after every step (a CLV's
-//    largest entry lies anywhere in [2^-256, 1], so a few unnormalised steps would underflow).  The lane writes
-//    rho_r * post / sum into part[sample][rate][slot][site][4].
-//  * K11m (anc_combine_kernel), a thread per (sample, slot, site): the R partial tables added in rate order -- fixed order,
-//    no atomics, the same bits whatever the batch.
+//    per site: P mat-vecs, not T - 2.  The message from above is divided by its largest entry after every step.  The lane
+//    writes rho_r * post / sum into part[sample][rate][slot][site][4].  The kernel's prologue (tables, CLV area), the
+//    upward pass and the step down the lineage (sibling message, descent) are lh_treepass.h's, shared with K12b and K13b;
+//    the message into the root is written here (its sum may be contracted, and is in this kernel).
+//  * K11m (rate_sum_kernel, launch_rate_sum), a thread per output cell: the R partial tables added in rate order -- fixed
+//    order, no atomics, the same bits whatever the batch.  K12 and K13 sum their partial tables with the same kernel.
 // No private array is reached by a dynamic index: 4-vectors are indexed by unrolled loops only.
-#include "lh_device.h"
+#include "lh_treepass.h"
 
 namespace lh {
 
@@ -119,16 +120,9 @@ __global__ void __launch_bounds__(256) anc_rate_kernel(int n, int R, int L, int 
     for (int k = 0; k < R; ++k) r_out[k] = total;
     return;
   }
-  const int32_t* sc = site_scal + (size_t)sample * R * n_prune + pat;
-  const double* lk = site_lik + (size_t)sample * R * 5 * n_prune + pat;
-  int smin = 0x7fffffff;
-  for (int k = 0; k < R; ++k) smin = min(smin, sc[(size_t)k * n_prune]);
-  double z[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-  for (int k = 0; k < R; ++k) {
-    const int d = sc[(size_t)k * n_prune] - smin;
-#pragma unroll
-    for (int b = 0; b < 5; ++b) z[b] += anc_aligned(lk[((size_t)k * 5 + b) * n_prune], d);
-  }
+  const RatePlanes planes = rate_planes(site_scal, site_lik, sample, R, n_prune, pat);
+  double z[5];
+  planes.totals(R, z);
 #pragma unroll
   for (int b = 0; b < 5; ++b) {
     const double qb = q[b];
@@ -136,13 +130,12 @@ __global__ void __launch_bounds__(256) anc_rate_kernel(int n, int R, int L, int 
     t_out[b] = t[b];
   }
   for (int k = 0; k < R; ++k) {
-    const int d = sc[(size_t)k * n_prune] - smin;
+    double v[5];
+    planes.values(k, v);
     double acc = 0.0;
 #pragma unroll
-    for (int b = 0; b < 5; ++b) {
-      const double v = anc_aligned(lk[((size_t)k * 5 + b) * n_prune], d);
-      if (t[b] != 0.0) acc += t[b] * v;
-    }
+    for (int b = 0; b < 5; ++b)
+      if (t[b] != 0.0) acc += t[b] * v[b];
     r_out[k] = acc;
   }
 }
@@ -218,28 +211,18 @@ __global__ void __launch_bounds__(256) anc_kernel(int R, int T, int L, int n_pru
                                                   const int32_t* __restrict__ chain, const int32_t* __restrict__ plen,
                                                   double2* clv, int Lp, double* __restrict__ part) {
   extern __shared__ double2 anc_smem[];
-  const int n_ops = T - 2;
-  const int sample = blockIdx.y, rate = blockIdx.x;
-  const int len = plen[sample];
+  const TreeTables tt = tree_prologue(anc_smem, R, T, desc, brlen, rates, eig, plen, clv, Lp);
+  const int len = tt.len;
   if (len == 0) return;  // K11m writes the row's NaN
-  double* tiptab = reinterpret_cast<double*>(anc_smem);  // [T][4][4] columns of P
-  double* pin = tiptab + (size_t)T * 16;                 // [n_ops][4][4] row-major, by the op that produced the child
+  const int sample = blockIdx.y, rate = blockIdx.x;
+  const double* tiptab = tt.tiptab;
+  const size_t plane = tt.plane;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int n_waves = blockDim.x >> 6;
-  const AsrOp* __restrict__ dsc = desc + (size_t)sample * n_ops;
-  const double* __restrict__ e = eig + (size_t)sample * 36;
-  const double rt = rates[(size_t)sample * R + rate];
-  const double* __restrict__ bl = brlen + (size_t)sample * (2 * (size_t)T - 2);
-  anc_fill_tables(T, dsc, e, bl, rt, tiptab, pin);
-  __syncthreads();
-
-  // CLV area of this (sample, rate): [op][2][Lp] double2, components (0,1) and (2,3) of a pattern in two planes
-  const size_t plane = (size_t)Lp;
-  double2* clv_s = clv + ((size_t)sample * R + rate) * n_ops * 2 * plane;
 
   // ---- upward pass, a lane per pattern
-  anc_upward(n_ops, n_prune, msa, dsc, tiptab, pin, clv_s, plane, wave, n_waves, lane);
+  tree_upward(T - 2, n_prune, msa, tt.dsc, tiptab, tt.pin, tt.clv_s, plane, wave, n_waves, lane);
   // the sites' lanes below read CLVs that other lanes and waves of this workgroup stored above
   __threadfence_block();
   __syncthreads();
@@ -253,13 +236,13 @@ __global__ void __launch_bounds__(256) anc_kernel(int R, int T, int L, int n_pru
     const int site = min(s0 + lane, L - 1);
     const int pat = min(site_pat[site], n_prune);
     const bool all_n = pat >= n_prune;
-    const double2* cbase = clv_s + pat;
+    const double2* cbase = tt.clv_s + pat;
     const double* __restrict__ tj = tvec + ((size_t)sample * L + site) * 5;
     const double rj = rho[((size_t)sample * L + site) * R + rate];
     double A[4];
     {
       double n4[4];
-      anc_tip_col(tiptab, 0, 4, n4);
+      tree_tip_col(tiptab, 0, 4, n4);
       const double t0 = tj[0], t1 = tj[1], t2 = tj[2], t3 = tj[3], t4 = tj[4];
 #pragma unroll
       for (int i = 0; i < 4; ++i)
@@ -267,8 +250,7 @@ __global__ void __launch_bounds__(256) anc_kernel(int R, int T, int L, int n_pru
     }
     for (int s = len - 1; s >= 0; --s) {
       const int word = ch[s];
-      const int k = word & 0x3fffffff;
-      const double2* cv = cbase + (size_t)k * 2 * plane;
+      const double2* cv = cbase + (size_t)chain_op(word) * 2 * plane;
       const double2 lo = cv[0], hi = cv[plane];
       const double post[4] = {A[0] * lo.x, A[1] * lo.y, A[2] * hi.x, A[3] * hi.y};
       const double sum = (post[0] + post[1]) + (post[2] + post[3]);
@@ -281,65 +263,46 @@ __global__ void __launch_bounds__(256) anc_kernel(int R, int T, int L, int n_pru
       }
       if (s == 0) break;
       // the message into v_{s-1}: the sibling off the path times the message from above, through v_{s-1}'s branch
-      const int4 da = dsc[k].a, db = dsc[k].b;
-      const int kind = da.x & 15;
-      const bool via_pop = (word >> 30) != 0;
       double m[4];
-      int kc = k - 1;  // the op that produced v_{s-1}
-      if (kind == OP_TIP_ACC) {
-        const int sa = all_n ? 4 : (int)msa[(size_t)da.y * n_prune + pat];
-        anc_tip_col(tiptab, db.x, sa, m);
-      } else {
-        const int kw = via_pop ? k - 1 : da.w;  // the op that produced the sibling
-        kc = via_pop ? da.w : k - 1;
-        const double2* cw = cbase + (size_t)kw * 2 * plane;
-        const double2 wlo = cw[0], whi = cw[plane];
-        const double y[4] = {wlo.x, wlo.y, whi.x, whi.y};
-        anc_matvec(pin + (size_t)kw * 16, y, m);
-      }
-      double M[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) M[i] = A[i] * m[i];
-      anc_vecmat(pin + (size_t)kc * 16, M, A);
-      const double top = fmax(fmax(A[0], A[1]), fmax(A[2], A[3]));
-      if (top > 0.0 && top < INFINITY) {
-        const double inv = 1.0 / top;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) A[i] *= inv;
-      }
+      const int kc = tree_sibling_message(tt, word, msa, n_prune, pat, all_n, m);
+      tree_descend(tt.pin, kc, m, A);
     }
   }
 }
 
-// K11m
-__global__ void __launch_bounds__(256) anc_combine_kernel(int n, int R, int P, int L, const int32_t* __restrict__ plen,
-                                                          const double* __restrict__ part, double* __restrict__ marg) {
+// K11m, K12m, K13m.  part[n][R][slots][width], out[n][slots][width]; slot s of a sample is live if s < plen, or if it is
+// the last and last_live (edge_load's naive edge).
+__global__ void __launch_bounds__(256) rate_sum_kernel(int n, int R, int slots, long long width, bool last_live,
+                                                       const int32_t* __restrict__ plen, const double* __restrict__ part,
+                                                       double* __restrict__ out) {
   const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  const long long per = (long long)P * L;
+  const long long per = (long long)slots * width;
   if (gid >= (long long)n * per) return;
   const int sample = (int)(gid / per);
-  const long long cell = gid - (long long)sample * per;  // slot * L + site
-  const int s = (int)(cell / L);
+  const long long cell = gid - (long long)sample * per;
+  const int s = (int)(cell / width);
   const int len = plen[sample];
-  double2 lo = make_double2(0.0, 0.0), hi = lo;
+  double v = 0.0;
   if (len == 0) {
-    lo = hi = make_double2(__builtin_nan(""), __builtin_nan(""));
-  } else if (s < len) {
-    for (int k = 0; k < R; ++k) {
-      const double2* p = reinterpret_cast<const double2*>(part + (((size_t)sample * R + k) * per + cell) * 4);
-      const double2 a = p[0], b = p[1];
-      lo.x += a.x;
-      lo.y += a.y;
-      hi.x += b.x;
-      hi.y += b.y;
-    }
+    v = __builtin_nan("");
+  } else if (s < len || (last_live && s == slots - 1)) {
+    // (unrolled: four categories' loads in flight per thread, the sum still in rate order; with one 8-byte load in flight
+    // the kernel was 10 % slower on K11's tables, profiles/r22_treepass_shared.txt)
+#pragma unroll 4
+    for (int k = 0; k < R; ++k) v += part[((size_t)sample * R + k) * per + cell];
   }
-  double2* o = reinterpret_cast<double2*>(marg + (size_t)gid * 4);
-  o[0] = lo;
-  o[1] = hi;
+  out[gid] = v;
 }
 
 }  // namespace
+
+void launch_rate_sum(int n, int R, int slots, size_t width, bool last_live, const int32_t* plen, const double* part,
+                     double* out, hipStream_t stream) {
+  if (!out) return;
+  const long long cells = (long long)n * slots * (long long)width;
+  hipLaunchKernelGGL(rate_sum_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, stream, n, R, slots,
+                     (long long)width, last_live, plen, part, out);
+}
 
 size_t anc_lp(int n_prune) { return ((size_t)n_prune + 1 + 7) & ~(size_t)7; }
 
@@ -398,9 +361,7 @@ int launch_ancestral(const DevFamily& fam, int n, int R, int T, const int32_t* o
   launch_lds(anc_kernel, dim3(R, n), dim3(256), lds, stream, R, T, L, fam.n_prune, P, fam.msa, fam.site_pat,
              static_cast<const AsrOp*>(ws.desc), brlen, rates, eig, pi, ws.tvec, rho, ws.chain, ws.plen,
              reinterpret_cast<double2*>(ws.clv), (int)anc_lp(fam.n_prune), ws.part);
-  const long long out = (long long)n * P * L;
-  hipLaunchKernelGGL(anc_combine_kernel, dim3((unsigned)((out + 255) / 256)), dim3(256), 0, stream, n, R, P, L, ws.plen,
-                     ws.part, marg);
+  launch_rate_sum(n, R, P, (size_t)L * 4, false, ws.plen, ws.part, marg, stream);
   return 0;
 }
 

@@ -12,18 +12,19 @@
 //
 // Kernels:
 //  * K11r, K3s and K11c (launch_ancestral_front) run in front: the path is checked against the sample's own schedule.
-//  * K13b (cond_kernel), a workgroup per (rate category, sample) as K11b, with K11b's LDS tables and upward pass; a lane
-//    per PATTERN in both passes, so a lane reads back only the CLVs it stored itself.  The joint P(x = c, column | b, r) is
-//    linear in the naive tip's vector: the down pass carries the message from above for the five basis vectors (A, C, G,
-//    T, N) at once, a 4 x 5 block, each column divided by its own largest entry after every step.  At the node the table
-//    is normalised per (basis, rate) and weighted by lik_r(j, b) / Z_j(b) from K1's unmixed planes (scaler counts aligned
-//    to the smallest, as K11r): part[sample][rate][pattern][5][4].  Z = 0, a dead category or an all-zero table gives 0.
-//    The all-N pattern takes K11's convention: likelihood pi_b under base b, sum pi under N, so the weight is 1 / R.
+//  * K13b (cond_kernel), a workgroup per (rate category, sample) as K11b, with K11b's prologue, upward pass and step
+//    down the lineage (lh_treepass.h); a lane per PATTERN in both passes, so a lane reads back only the CLVs it stored
+//    itself.  The joint P(x = c, column | b, r) is linear in the naive tip's vector: the down pass carries the message
+//    from above for the five basis vectors (A, C, G, T, N) at once, a 4 x 5 block, each column divided by its own
+//    largest entry after every step.  At the node the table is normalised per (basis, rate) and weighted by lik_r(j, b)
+//    / Z_j(b) from K1's unmixed planes (scaler counts aligned to the smallest, RatePlanes as K11r):
+//    part[sample][rate][pattern][5][4].  Z = 0, a dead category or an all-zero table gives 0. The all-N pattern takes
+//    K11's convention: likelihood pi_b under base b, sum pi under N, so the weight is 1 / R.
 //    The node is a template switch.  kMrca: no down step, the root's CLV stays in the lane's registers and the upward
 //    pass stores only what a later op pops from its stack.  Otherwise (the seed's parent): K11b's walk down the chain.
-//  * K13m (cond_combine_kernel), a thread per (sample, pattern, basis): the R partial tables added in rate order (K11m's
-//    rule: fixed order, no atomics); NaN for a sample without a valid path.  cond_sites_kernel spreads the patterns'
-//    tables over the sites for a caller who takes them: cond[n][L][5][4].
+//  * K13m (K11m's rate_sum_kernel, lh_ancestral.hip), a thread per cell: the R partial tables added in rate order
+//    (fixed order, no atomics); NaN for a sample without a valid path.  cond_sites_kernel spreads the patterns' tables
+//    over the sites for a caller who takes them: cond[n][L][5][4].
 //  * K13e (pair_emission_kernel), a thread per (pair, caller column) of a group of (row, candidate) pairs, pair q = row * K
 //    + candidate: the emissions above.  Rows without a path get 0 (row_mask_kernel does the same to the rows' own
 //    emissions), so the sweeps see what K6a's see; pair_finish_kernel turns the sweeps' log-likelihoods into
@@ -32,7 +33,7 @@
 // No private array is reached by a dynamic index: 4-vectors and the 4 x 5 block are indexed by unrolled loops only.
 #include <algorithm>
 
-#include "lh_device.h"
+#include "lh_treepass.h"
 
 namespace lh {
 
@@ -47,34 +48,26 @@ __global__ void __launch_bounds__(256) cond_kernel(int R, int T, int n_prune, in
                                                    const int32_t* __restrict__ plen, double2* clv, int Lp,
                                                    double* __restrict__ part) {
   extern __shared__ double2 cond_smem[];
-  const int n_ops = T - 2, NP = n_prune + 1;
-  const int sample = blockIdx.y, rate = blockIdx.x;
-  const int len = plen[sample];
+  const TreeTables tt = tree_prologue(cond_smem, R, T, desc, brlen, rates, eig, plen, clv, Lp);
+  const int len = tt.len;
   if (len == 0) return;  // K13m writes the row's NaN
-  double* tiptab = reinterpret_cast<double*>(cond_smem);  // [T][4][4] columns of P
-  double* pin = tiptab + (size_t)T * 16;                  // [n_ops][4][4] row-major, by the op that produced the child
+  const int NP = n_prune + 1;
+  const int sample = blockIdx.y, rate = blockIdx.x;
+  const double* tiptab = tt.tiptab;
+  const size_t plane = tt.plane;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int n_waves = blockDim.x >> 6;
-  const AsrOp* __restrict__ dsc = desc + (size_t)sample * n_ops;
-  const double rt = rates[(size_t)sample * R + rate];
-  anc_fill_tables(T, dsc, eig + (size_t)sample * 36, brlen + (size_t)sample * (2 * (size_t)T - 2), rt, tiptab, pin);
-  __syncthreads();
-
-  const size_t plane = (size_t)Lp;
-  double2* clv_s = clv + ((size_t)sample * R + rate) * n_ops * 2 * plane;
   const double* __restrict__ p4 = pi + (size_t)sample * 4;
   const int32_t* __restrict__ ch = chain + (size_t)sample * P;
   double* part_s = part + ((size_t)sample * R + rate) * (size_t)NP * 20;
-  const int32_t* sc_s = site_scal + (size_t)sample * R * n_prune;
-  const double* lk_s = site_lik + (size_t)sample * R * 5 * n_prune;
 
   for (int s0 = wave * 64; s0 < NP; s0 += n_waves * 64) {
     const bool live = s0 + lane < NP;
     const int pat = min(s0 + lane, NP - 1);
     const bool all_n = pat >= n_prune;
     double node[4];  // the node's CLV
-    anc_upward_pattern<!kMrca>(n_ops, n_prune, pat, msa, dsc, tiptab, pin, clv_s, plane, node);
+    tree_upward_pattern<!kMrca>(T - 2, n_prune, pat, msa, tt.dsc, tiptab, tt.pin, tt.clv_s, plane, node);
 
     // the weight of this category under each naive base
     double w[5];
@@ -82,29 +75,19 @@ __global__ void __launch_bounds__(256) cond_kernel(int R, int T, int n_prune, in
 #pragma unroll
       for (int b = 0; b < 5; ++b) w[b] = 1.0 / (double)R;
     } else {
-      const int32_t* sc = sc_s + pat;
-      const double* lk = lk_s + pat;
-      int smin = 0x7fffffff;
-      for (int k = 0; k < R; ++k) smin = min(smin, sc[(size_t)k * n_prune]);
-      double z[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-      for (int k = 0; k < R; ++k) {
-        const int d = sc[(size_t)k * n_prune] - smin;
+      const RatePlanes planes = rate_planes(site_scal, site_lik, sample, R, n_prune, pat);
+      double z[5], v[5];
+      planes.totals(R, z);
+      planes.values(rate, v);
 #pragma unroll
-        for (int b = 0; b < 5; ++b) z[b] += anc_aligned(lk[((size_t)k * 5 + b) * n_prune], d);
-      }
-      const int d = sc[(size_t)rate * n_prune] - smin;
-#pragma unroll
-      for (int b = 0; b < 5; ++b) {
-        const double v = anc_aligned(lk[((size_t)rate * 5 + b) * n_prune], d);
-        w[b] = (z[b] == 0.0 || v == 0.0) ? 0.0 : v / z[b];
-      }
+      for (int b = 0; b < 5; ++b) w[b] = (z[b] == 0.0 || v[b] == 0.0) ? 0.0 : v[b] / z[b];
     }
 
     // the message into the root from above, per basis vector of the naive tip
     double A[5][4];
     {
       double n4[4];
-      anc_tip_col(tiptab, 0, 4, n4);
+      tree_tip_col(tiptab, 0, 4, n4);
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
 #pragma unroll
@@ -113,42 +96,15 @@ __global__ void __launch_bounds__(256) cond_kernel(int R, int T, int n_prune, in
       }
     }
     if (!kMrca) {
-      const double2* cbase = clv_s + pat;
+      const double2* cbase = tt.clv_s + pat;
       for (int s = len - 1; s >= 1; --s) {
         // the message into v_{s-1}: the sibling off the path times the message from above, through v_{s-1}'s branch
-        const int word = ch[s];
-        const int k = word & 0x3fffffff;
-        const int4 da = dsc[k].a, db = dsc[k].b;
-        const int kind = da.x & 15;
-        const bool via_pop = (word >> 30) != 0;
         double m[4];
-        int kc = k - 1;  // the op that produced v_{s-1}
-        if (kind == OP_TIP_ACC) {
-          const int sa = all_n ? 4 : (int)msa[(size_t)da.y * n_prune + pat];
-          anc_tip_col(tiptab, db.x, sa, m);
-        } else {
-          const int kw = via_pop ? k - 1 : da.w;  // the op that produced the sibling
-          kc = via_pop ? da.w : k - 1;
-          const double2* cw = cbase + (size_t)kw * 2 * plane;
-          const double2 wlo = cw[0], whi = cw[plane];
-          const double y[4] = {wlo.x, wlo.y, whi.x, whi.y};
-          anc_matvec(pin + (size_t)kw * 16, y, m);
-        }
+        const int kc = tree_sibling_message(tt, ch[s], msa, n_prune, pat, all_n, m);
 #pragma unroll
-        for (int b = 0; b < 5; ++b) {
-          double M[4];
-#pragma unroll
-          for (int i = 0; i < 4; ++i) M[i] = A[b][i] * m[i];
-          anc_vecmat(pin + (size_t)kc * 16, M, A[b]);
-          const double top = fmax(fmax(A[b][0], A[b][1]), fmax(A[b][2], A[b][3]));
-          if (top > 0.0 && top < INFINITY) {
-            const double inv = 1.0 / top;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) A[b][i] *= inv;
-          }
-        }
+        for (int b = 0; b < 5; ++b) tree_descend(tt.pin, kc, m, A[b]);
       }
-      const double2* cv = cbase + (size_t)(ch[0] & 0x3fffffff) * 2 * plane;
+      const double2* cv = cbase + (size_t)chain_op(ch[0]) * 2 * plane;
       const double2 lo = cv[0], hi = cv[plane];
       node[0] = lo.x;
       node[1] = lo.y;
@@ -168,32 +124,6 @@ __global__ void __launch_bounds__(256) cond_kernel(int R, int T, int n_prune, in
       }
     }
   }
-}
-
-// K13m
-__global__ void __launch_bounds__(256) cond_combine_kernel(int n, int R, int NP, const int32_t* __restrict__ plen,
-                                                           const double* __restrict__ part, double* __restrict__ table) {
-  const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  const long long per = (long long)NP * 5;
-  if (gid >= (long long)n * per) return;
-  const int sample = (int)(gid / per);
-  const long long cell = gid - (long long)sample * per;  // pattern * 5 + basis
-  double2 lo = make_double2(0.0, 0.0), hi = lo;
-  if (plen[sample] == 0) {
-    lo = hi = make_double2(__builtin_nan(""), __builtin_nan(""));
-  } else {
-    for (int k = 0; k < R; ++k) {
-      const double2* p = reinterpret_cast<const double2*>(part + (((size_t)sample * R + k) * per + cell) * 4);
-      const double2 a = p[0], b = p[1];
-      lo.x += a.x;
-      lo.y += a.y;
-      hi.x += b.x;
-      hi.y += b.y;
-    }
-  }
-  double2* o = reinterpret_cast<double2*>(table + (size_t)gid * 4);
-  o[0] = lo;
-  o[1] = hi;
 }
 
 __global__ void __launch_bounds__(256) cond_sites_kernel(int n, int L, int n_prune, const int32_t* __restrict__ site_pat,
@@ -281,9 +211,7 @@ int launch_ancestral_cond(const DevFamily& fam, int n, int R, int T, const int32
     run(cond_kernel<true>);
   else
     run(cond_kernel<false>);
-  const long long cells = (long long)n * NP * 5;
-  hipLaunchKernelGGL(cond_combine_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, stream, n, R, NP, ws.plen,
-                     ws.part, table);
+  launch_rate_sum(n, R, 1, (size_t)NP * 20, false, ws.plen, ws.part, table, stream);
   if (cond) {
     const long long out = (long long)n * L * 5;
     hipLaunchKernelGGL(cond_sites_kernel, dim3((unsigned)((out + 255) / 256)), dim3(256), 0, stream, n, L, fam.n_prune,

@@ -29,12 +29,14 @@
 //  * Downward pass: the schedule in reverse; a lane carries the state of the accumulator child in a
 //    register, states of popped siblings wait in a per-lane LDS byte stack (same slot numbers as K1's
 //    register stack).  CLVs are rescaled freely on the way up (only ratios within a node matter).
+//  * The 4-vector helpers, the aligned per-rate plane values and the fill of the LDS tables are lh_treepass.h's, shared
+//    with K11, K12 and K13; the two software-pipelined passes below are K3b's own.
 //  * Random numbers: Philox4x32-10, counter = (site, draw, sample), key = seed; draw 0 = rate category,
 //    1 = root, 2 + (v - T) = inner node v.  oracle/asr_oracle.py restates the same stream, so GPU and oracle
 //    agree draw by draw.
 #include <cstdlib>
 
-#include "lh_device.h"
+#include "lh_treepass.h"
 
 namespace lh {
 
@@ -73,23 +75,6 @@ __device__ __forceinline__ int draw4(const double (&w)[4], double u) {
   const double c0 = w[0], c1 = c0 + w[1], c2 = c1 + w[2], c3 = c2 + w[3];
   const double t = u * c3;
   return (int)(c0 <= t) + (int)(c1 <= t) + (int)(c2 <= t);
-}
-
-__device__ __forceinline__ void tip_col(const double* tiptab, int tip, int st, double (&c)[4]) {
-  const double* t = tiptab + tip * 16;
-  if (st < 4) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) c[i] = t[st * 4 + i];
-  } else {  // N: row sums of P
-#pragma unroll
-    for (int i = 0; i < 4; ++i) c[i] = ((t[i] + t[4 + i]) + t[8 + i]) + t[12 + i];
-  }
-}
-
-// x = P a, P row-major in LDS at a wave-uniform address
-__device__ __forceinline__ void matvec_lds(const double* p, const double (&a)[4], double (&x)[4]) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) x[i] = fma(p[i * 4 + 3], a[3], fma(p[i * 4 + 2], a[2], fma(p[i * 4 + 1], a[1], p[i * 4] * a[0])));
 }
 
 }  // namespace
@@ -132,25 +117,14 @@ __global__ void __launch_bounds__(256) asr_rate_kernel(int n, int R, int L, int 
     for (int k = R - 1; k >= 0; --k)
       if (t < (double)(k + 1)) pick = k;
   } else {
-    const int32_t* sc = site_scal + (size_t)sample * R * n_prune + pat;
-    const double* lk = site_lik + ((size_t)sample * R * 5 + b) * n_prune + pat;
-    int smin = 0x7fffffff;
-    for (int k = 0; k < R; ++k) smin = min(smin, sc[(size_t)k * n_prune]);
+    const RatePlanes planes = rate_planes(site_scal, site_lik, sample, R, n_prune, pat);
     double total = 0.0;
-    for (int k = 0; k < R; ++k) {
-      double v = lk[(size_t)k * 5 * n_prune];
-      const int d = sc[(size_t)k * n_prune] - smin;
-      for (int q = 0; q < d && v != 0.0; ++q) v *= kScaleThreshold;
-      total += v;
-    }
+    for (int k = 0; k < R; ++k) total += planes.value(k, b);
     const double t = u * total;
     double cum = 0.0;
     bool found = false;
     for (int k = 0; k < R; ++k) {
-      double v = lk[(size_t)k * 5 * n_prune];
-      const int d = sc[(size_t)k * n_prune] - smin;
-      for (int q = 0; q < d && v != 0.0; ++q) v *= kScaleThreshold;
-      cum += v;
+      cum += planes.value(k, b);
       if (!found && t < cum) {
         pick = k;
         found = true;
@@ -321,32 +295,11 @@ __global__ void __launch_bounds__(256) asr_kernel(int R, int T, int L, int n_pru
     }
   }
 
-  // ---- P-matrices of this (sample, rate): tip branches -> tip table (columns of P); inner branches row-major,
-  // indexed by the op that produced the child
+  // ---- P-matrices of this (sample, rate)
   const double* __restrict__ e = eig + (size_t)sample * 36;
   const double rt = rates[(size_t)sample * R + rate];
   const double* __restrict__ bl = brlen + (size_t)sample * (2 * (size_t)T - 2);
-  {
-    double P[4][4];
-    for (int j = tid; j < T + n_ops - 1; j += blockDim.x) {
-      if (j < T) {
-        compute_pmatrix(e, bl[j] * rt, P);
-        double* o = tiptab + j * 16;
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-          for (int st = 0; st < 4; ++st) o[st * 4 + i] = P[i][st];
-      } else {
-        const int k = j - T;  // op k < n_ops - 1 produced inner node T + b.z, whose branch this is
-        compute_pmatrix(e, bl[T + dsc[k].b.z] * rt, P);
-        double* o = pin + (size_t)k * 16;
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-          for (int q = 0; q < 4; ++q) o[i * 4 + q] = P[i][q];
-      }
-    }
-  }
+  tree_fill_tables(T, dsc, e, bl, rt, tiptab, pin);
   __syncthreads();
   const int cnt = misc[0], base = misc[1], cntp = misc[2];
   if (cnt == 0) return;  // no site of this sample drew this category (uniform)
@@ -417,15 +370,15 @@ __global__ void __launch_bounds__(256) asr_kernel(int R, int T, int L, int n_pru
             const int kind = c.da.x & 15;
             double u[4], v[4];
             if (kind == OP_CHERRY) {
-              tip_col(tiptab, c.db.x, all_n ? 4 : c.sa, u);
-              tip_col(tiptab, c.db.y, all_n ? 4 : c.sb, v);
+              tree_tip_col(tiptab, c.db.x, all_n ? 4 : c.sa, u);
+              tree_tip_col(tiptab, c.db.y, all_n ? 4 : c.sb, v);
             } else {
-              matvec_lds(pin + (size_t)(kk - 1) * 16, a, v);
+              tree_matvec(pin + (size_t)(kk - 1) * 16, a, v);
               if (kind == OP_TIP_ACC) {
-                tip_col(tiptab, c.db.x, all_n ? 4 : c.sa, u);
+                tree_tip_col(tiptab, c.db.x, all_n ? 4 : c.sa, u);
               } else {
                 const double y[4] = {ylo[i & 1].x, ylo[i & 1].y, yhi[i & 1].x, yhi[i & 1].y};
-                matvec_lds(pin + (size_t)c.da.w * 16, y, u);
+                tree_matvec(pin + (size_t)c.da.w * 16, y, u);
               }
             }
 #pragma unroll
@@ -491,7 +444,7 @@ __global__ void __launch_bounds__(256) asr_kernel(int R, int T, int L, int n_pru
         const double2* cr = cbase + (size_t)(n_ops - 1) * 2 * plane;
         const double2 rlo = cr[0], rhi = cr[plane];
         double down[4];
-        tip_col(tiptab, 0, b_naive, down);
+        tree_tip_col(tiptab, 0, b_naive, down);
         const double w[4] = {p4[0] * rlo.x * down[0], p4[1] * rlo.y * down[1], p4[2] * rhi.x * down[2],
                              p4[3] * rhi.y * down[3]};
         s_acc = draw4(w, asr_uniform(seed, sample_id, (uint32_t)site, 1u));
@@ -543,16 +496,13 @@ int launch_asr(const DevFamily& fam, int n, int R, int T, const int32_t* ops, co
   if (draws < 1 || (long long)n * draws > 65535) return 1;  // (one grid row per virtual sample)
   const size_t lds = asr_lds_bytes(T, L, R, fam.n_prune);
   if (lds > 160 * 1024 || L < 1) return 1;
-  if (lds > 64 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(asr_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)lds);
   const long long cells = (long long)n * draws * L;
   hipLaunchKernelGGL(asr_rate_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, stream, n, R, L,
                      fam.n_prune, fam.site_pat, site_lik, site_scal, naive, seed, sample0, rate_choice, draws);
   launch_asr_sched(n, T, ops, hdr, desc, stream);
-  hipLaunchKernelGGL(asr_kernel, dim3(R, n * draws), dim3(256), lds, stream, R, T, L, fam.n_prune, fam.msa, fam.site_pat,
-                     static_cast<const AsrOp*>(desc), brlen, rates, eig, pi, rate_choice, naive, seed,
-                     sample0, reinterpret_cast<double2*>(clv), (int)asr_slots(L, R), anc, hdr, draws);
+  launch_lds(asr_kernel, dim3(R, n * draws), dim3(256), lds, stream, R, T, L, fam.n_prune, fam.msa, fam.site_pat,
+             static_cast<const AsrOp*>(desc), brlen, rates, eig, pi, rate_choice, naive, seed, sample0,
+             reinterpret_cast<double2*>(clv), (int)asr_slots(L, R), anc, hdr, draws);
   return 0;
 }
 

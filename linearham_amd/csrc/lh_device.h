@@ -470,118 +470,12 @@ void launch_ancestral_front(const DevFamily& fam, int n, int R, int T, const int
                             int P, const AncWs& ws, double* rate_post, const int4* hdr, int32_t* err_flag, hipStream_t stream);
 size_t anc_lp(int n_prune);  // patterns per CLV plane: n_prune + 1 rounded up to 8
 
-// What K11b, K12b and K13b share, inlined into each: the 4-vector helpers, the LDS tables and the upward pass.
-// a plane value whose scaler count lies d above the site's smallest, on that one's scale (K11r, K13b)
-__device__ static __forceinline__ double anc_aligned(double v, int d) {
-  for (int q = 0; q < d && v != 0.0; ++q) v *= kScaleThreshold;
-  return v;
-}
-
-__device__ static __forceinline__ void anc_tip_col(const double* tiptab, int tip, int st, double (&c)[4]) {
-  const double* t = tiptab + tip * 16;
-  if (st < 4) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) c[i] = t[st * 4 + i];
-  } else {  // N: row sums of P, as K3
-#pragma unroll
-    for (int i = 0; i < 4; ++i) c[i] = ((t[i] + t[4 + i]) + t[8 + i]) + t[12 + i];
-  }
-}
-
-// x = P a, P row-major in LDS at a wave-uniform address
-__device__ static __forceinline__ void anc_matvec(const double* p, const double (&a)[4], double (&x)[4]) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) x[i] = fma(p[i * 4 + 3], a[3], fma(p[i * 4 + 2], a[2], fma(p[i * 4 + 1], a[1], p[i * 4] * a[0])));
-}
-
-// x = a^T P
-__device__ static __forceinline__ void anc_vecmat(const double* p, const double (&a)[4], double (&x)[4]) {
-#pragma unroll
-  for (int c = 0; c < 4; ++c) x[c] = fma(p[12 + c], a[3], fma(p[8 + c], a[2], fma(p[4 + c], a[1], p[c] * a[0])));
-}
-
-// The LDS tables of a (sample, rate): tiptab[T][4][4] columns of the tip branches' P, pin[T-2][4][4] row-major P of the
-// inner branches, by the op that produced the child.  The caller synchronises the workgroup behind it.
-__device__ static __forceinline__ void anc_fill_tables(int T, const AsrOp* __restrict__ dsc, const double* __restrict__ e,
-                                                       const double* __restrict__ bl, double rt, double* tiptab, double* pin) {
-  const int n_ops = T - 2;
-  double Pm[4][4];
-  for (int j = threadIdx.x; j < T + n_ops - 1; j += blockDim.x) {
-    if (j < T) {
-      compute_pmatrix(e, bl[j] * rt, Pm);
-      double* o = tiptab + j * 16;
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int st = 0; st < 4; ++st) o[st * 4 + i] = Pm[i][st];
-    } else {
-      const int k = j - T;  // op k < n_ops - 1 produced inner node T + b.z, whose branch this is
-      compute_pmatrix(e, bl[T + dsc[k].b.z] * rt, Pm);
-      double* o = pin + (size_t)k * 16;
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) o[i * 4 + q] = Pm[i][q];
-    }
-  }
-}
-
-// K3b's upward pass of one pattern (n_prune: the all-N one), the lane's: every inner CLV stored: clv_s[op][2][plane]
-// double2, components (0,1) and (2,3) of a pattern in two planes.  kStoreAll = false (K13b's MRCA form) stores only what a
-// later op pops from the stack, which the lane itself reads back.  `a` leaves as the root's CLV.
-template <bool kStoreAll = true>
-__device__ static __forceinline__ void anc_upward_pattern(int n_ops, int n_prune, int pat, const uint8_t* __restrict__ msa,
-                                                          const AsrOp* __restrict__ dsc, const double* tiptab,
-                                                          const double* pin, double2* clv_s, size_t plane, double (&a)[4]) {
-  const bool all_n = pat >= n_prune;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) a[q] = 1.0;
-  for (int k = 0; k < n_ops; ++k) {
-    const int4 da = dsc[k].a, db = dsc[k].b;
-    const int kind = da.x & 15;
-    double u[4], v[4];
-    if (kind == OP_CHERRY) {
-      const int sa = all_n ? 4 : (int)msa[(size_t)da.y * n_prune + pat];
-      const int sb = all_n ? 4 : (int)msa[(size_t)da.z * n_prune + pat];
-      anc_tip_col(tiptab, db.x, sa, u);
-      anc_tip_col(tiptab, db.y, sb, v);
-    } else {
-      anc_matvec(pin + (size_t)(k - 1) * 16, a, v);
-      if (kind == OP_TIP_ACC) {
-        const int sa = all_n ? 4 : (int)msa[(size_t)da.y * n_prune + pat];
-        anc_tip_col(tiptab, db.x, sa, u);
-      } else {
-        const double2* cq = clv_s + (size_t)da.w * 2 * plane + pat;
-        const double2 lo = cq[0], hi = cq[plane];
-        const double y[4] = {lo.x, lo.y, hi.x, hi.y};
-        anc_matvec(pin + (size_t)da.w * 16, y, u);
-      }
-    }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) a[q] = u[q] * v[q];
-    if (fmax(fmax(a[0], a[1]), fmax(a[2], a[3])) < kScaleThreshold) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q) a[q] *= kScaleFactor;
-    }
-    if (kStoreAll || (da.x >> 8) != 0) {
-      double2* ck = clv_s + (size_t)k * 2 * plane + pat;
-      ck[0] = make_double2(a[0], a[1]);
-      ck[plane] = make_double2(a[2], a[3]);
-    }
-  }
-}
-
-// The pass over all NP = n_prune + 1 patterns (the all-N one last), a lane per pattern (lanes past the last pattern repeat
-// it: same values, no predicate).
-__device__ static __forceinline__ void anc_upward(int n_ops, int n_prune, const uint8_t* __restrict__ msa,
-                                                  const AsrOp* __restrict__ dsc, const double* tiptab, const double* pin,
-                                                  double2* clv_s, size_t plane, int wave, int n_waves, int lane) {
-  const int NP = n_prune + 1;
-  for (int s0 = wave * 64; s0 < NP; s0 += n_waves * 64) {
-    double a[4];
-    anc_upward_pattern<true>(n_ops, n_prune, min(s0 + lane, NP - 1), msa, dsc, tiptab, pin, clv_s, plane, a);
-  }
-}
+// The R per-rate partial tables of every sample added in rate order, a thread per output cell (rate_sum_kernel,
+// lh_ancestral.hip: K11m, K12m, K13m) -- fixed order, no atomics, the same bits whatever the batch.  part[n][R][slots][width]
+// -> out[n][slots][width] (null: nothing is done).  Slot s of a sample is live if s < plen, or if it is the last and
+// last_live; every other slot gets 0, a sample whose plen is 0 NaN.
+void launch_rate_sum(int n, int R, int slots, size_t width, bool last_live, const int32_t* plen, const double* part,
+                     double* out, hipStream_t stream);
 
 // K12 (lh_substitutions.hip): exact joint posteriors of the two ends of every edge of a seed's lineage.  Inputs as
 // launch_ancestral's plus seed_tip (1 .. T-1, the same for every sample): the tip must be a child of path[0] under the

@@ -34,18 +34,19 @@
 //    child of the cherry or the tip of the tip-accumulate op that produced v_0).  It marks in the chain word of slot 0 which
 //    child it is; a failure leaves length 0 and raises bit 1 of the error word, as a bad path does.  seed_tip itself is
 //    checked on the host (1 .. T-1) and only compared, never used as an index, before this verdict.
-//  * K12b (sub_kernel<kWriteEdges>), a workgroup per (rate category, sample): K11b's LDS tables and upward pass (shared
-//    code, lh_device.h), then the down pass, a lane per site.  Per step: the 16 cells, their sum, the weight rho_r / sum.
+//  * K12b (sub_kernel<kWriteEdges>), a workgroup per (rate category, sample): K11b's prologue, upward pass and step down
+//    the lineage (shared code, lh_treepass.h; the seed edge at slot 0 and the message into the root are written here), a
+//    lane per site in the down pass.  Per step: the 16 cells, their sum, the weight rho_r / sum.
 //    The site's chain_counts partial lives in 16 registers; the step's off-diagonal mass is reduced across the wave with
 //    shuffles and added to the wave's row of an LDS table by one lane.  Only the kWriteEdges form writes [slot][site][16]
 //    per rate; the lean form writes [site][16] (chain_counts), [site][20] (naive edge), [P+1] (edge_load) and, where the
 //    caller wants the slot-0 table without the others, one more [site][16].
 //    Both forms do the same arithmetic in the same order (floating-point contraction is off in the down pass, fma is
 //    written where it is meant), so the reductions have the same bits in both.
-//  * K12m (sub_combine_kernel), a thread per output cell: the R partials added in rate order -- no atomics, the same bits
-//    whatever the batch.  NaN for a sample without a valid path, 0 in padding slots.
+//  * K12m (K11m's rate_sum_kernel, lh_ancestral.hip), a thread per output cell: the R partials added in rate order -- no
+//    atomics, the same bits whatever the batch.  NaN for a sample without a valid path, 0 in padding slots.
 // No private array is reached by a dynamic index: the 4- and 16-vectors are indexed by unrolled loops only.
-#include "lh_device.h"
+#include "lh_treepass.h"
 
 namespace lh {
 
@@ -61,7 +62,7 @@ __global__ void __launch_bounds__(256) sub_seed_kernel(int n, int T, int P, int 
   if (sample >= n) return;
   if (plen[sample] == 0) return;  // K11c (or K0c) has refused the sample
   int32_t* ch = chain + (size_t)sample * P;
-  const int k = ch[0] & 0x3fffffff;  // K11c took it from its own table: 0 <= k < T - 2
+  const int k = chain_op(ch[0]);  // K11c took it from its own table: 0 <= k < T - 2
   const AsrOp d = desc[(size_t)sample * (T - 2) + k];
   const int kind = d.a.x & 15;
   int which = -1;
@@ -132,27 +133,21 @@ __global__ void __launch_bounds__(kSubWaves * 64) sub_kernel(int R, int T, int L
                                                              double* __restrict__ se_part, double* __restrict__ el_part,
                                                              double* __restrict__ edge_part) {
   extern __shared__ double2 sub_smem[];
+  const TreeTables tt = tree_prologue(sub_smem, R, T, desc, brlen, rates, eig, plen, clv, Lp);
+  const int len = tt.len;
+  if (len == 0) return;  // K12m writes the row's NaN
   const int n_ops = T - 2;
   const int sample = blockIdx.y, rate = blockIdx.x;
-  const int len = plen[sample];
-  if (len == 0) return;  // K12m writes the row's NaN
-  double* tiptab = reinterpret_cast<double*>(sub_smem);  // [T][4][4] columns of P
-  double* pin = tiptab + (size_t)T * 16;                 // [n_ops][4][4] row-major, by the op that produced the child
-  double* load = pin + (size_t)n_ops * 16;               // [kSubWaves][P + 1] edge_load partials of the waves
+  const double *tiptab = tt.tiptab, *pin = tt.pin;
+  const AsrOp* __restrict__ dsc = tt.dsc;
+  const size_t plane = tt.plane;
+  double* load = tt.pin + (size_t)n_ops * 16;  // [kSubWaves][P + 1] edge_load partials of the waves
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const AsrOp* __restrict__ dsc = desc + (size_t)sample * n_ops;
-  const double* __restrict__ e = eig + (size_t)sample * 36;
-  const double rt = rates[(size_t)sample * R + rate];
-  const double* __restrict__ bl = brlen + (size_t)sample * (2 * (size_t)T - 2);
-  anc_fill_tables(T, dsc, e, bl, rt, tiptab, pin);
   for (int i = tid; i < kSubWaves * (P + 1); i += blockDim.x) load[i] = 0.0;
-  __syncthreads();
 
-  const size_t plane = (size_t)Lp;
-  double2* clv_s = clv + ((size_t)sample * R + rate) * n_ops * 2 * plane;
-  anc_upward(n_ops, n_prune, msa, dsc, tiptab, pin, clv_s, plane, wave, kSubWaves, lane);
-  // the sites' lanes below read CLVs that other lanes and waves of this workgroup stored above
+  tree_upward(n_ops, n_prune, msa, dsc, tiptab, pin, tt.clv_s, plane, wave, kSubWaves, lane);
+  // the sites' lanes below read CLVs that other lanes and waves of this workgroup stored above, and the zeroed load table
   __threadfence_block();
   __syncthreads();
 
@@ -167,7 +162,7 @@ __global__ void __launch_bounds__(kSubWaves * 64) sub_kernel(int R, int T, int L
     const int site = min(s0 + lane, L - 1);
     const int pat = min(site_pat[site], n_prune);
     const bool all_n = pat >= n_prune;
-    const double2* cbase = clv_s + pat;
+    const double2* cbase = tt.clv_s + pat;
     const double* __restrict__ tj = tvec + ((size_t)sample * L + site) * 5;
     const double rj = rho[((size_t)sample * L + site) * R + rate];
     double cc[16];
@@ -176,12 +171,12 @@ __global__ void __launch_bounds__(kSubWaves * 64) sub_kernel(int R, int T, int L
     double A[4];
     {
       // the naive edge: J(b, i) = t(b) pi_i P_naive[i][b] L_root(i), 20 cells; A(i) = sum_b of the first three factors
-      const int kr = ch[len - 1] & 0x3fffffff;
+      const int kr = chain_op(ch[len - 1]);
       const double2* cv = cbase + (size_t)kr * 2 * plane;
       const double2 lo = cv[0], hi = cv[plane];
       const double Lr[4] = {lo.x, lo.y, hi.x, hi.y};
       double n4[4];
-      anc_tip_col(tiptab, 0, 4, n4);
+      tree_tip_col(tiptab, 0, 4, n4);
       const double t[5] = {tj[0], tj[1], tj[2], tj[3], tj[4]};
       double J[20];
 #pragma unroll
@@ -218,65 +213,44 @@ __global__ void __launch_bounds__(kSubWaves * 64) sub_kernel(int R, int T, int L
     }
     for (int s = len - 1; s >= 0; --s) {
       const int word = ch[s];
-      const int k = word & 0x3fffffff;
-      const int4 da = dsc[k].a, db = dsc[k].b;
-      const int kind = da.x & 15;
-      const bool flag = (word >> 30) != 0;  // s > 0: v_{s-1} is the popped child; s = 0: the seed is the cherry's z child
       double m[4], M[4], J[16];
       double off;
       if (s == 0) {
+        const int k = chain_op(word);
+        const int4 da = dsc[k].a, db = dsc[k].b;
+        const bool flag = chain_flag(word);  // the seed is the cherry's z child
         // the seed edge: the sibling is the cherry's other tip, or the accumulator child of a tip-accumulate op
         int useed, srow;
-        if (kind == OP_CHERRY) {
+        if ((da.x & 15) == OP_CHERRY) {
           const int sib = flag ? db.x : db.y, sib_row = flag ? da.y : da.z;
           useed = flag ? db.y : db.x;
           srow = flag ? da.z : da.y;
           const int ss = all_n ? 4 : (int)msa[(size_t)sib_row * n_prune + pat];
-          anc_tip_col(tiptab, sib, ss, m);
+          tree_tip_col(tiptab, sib, ss, m);
         } else {
           useed = db.x;
           srow = da.y;
           const double2* cw = cbase + (size_t)(k - 1) * 2 * plane;
           const double2 wlo = cw[0], whi = cw[plane];
           const double y[4] = {wlo.x, wlo.y, whi.x, whi.y};
-          anc_matvec(pin + (size_t)(k - 1) * 16, y, m);
+          tree_matvec(pin + (size_t)(k - 1) * 16, y, m);
         }
         const int st = all_n ? 4 : (int)msa[(size_t)srow * n_prune + pat];
         double Lb[4];
 #pragma unroll
         for (int c = 0; c < 4; ++c) Lb[c] = (st >= 4 || st == c) ? 1.0 : 0.0;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) M[i] = A[i] * m[i];
+        tree_join(A, m, M);
         // the tip table holds columns: P_u[a][c] at [c * 4 + a]
         off = sub_edge<1, 4>(M, tiptab + (size_t)useed * 16, Lb, rj, J, cc);
         if (se_part && live) sub_store16(se_part + (sr * L + site) * 16, J);
       } else {
-        int kc = k - 1;  // the op that produced v_{s-1}
-        if (kind == OP_TIP_ACC) {
-          const int sa = all_n ? 4 : (int)msa[(size_t)da.y * n_prune + pat];
-          anc_tip_col(tiptab, db.x, sa, m);
-        } else {
-          const int kw = flag ? k - 1 : da.w;  // the op that produced the sibling
-          kc = flag ? da.w : k - 1;
-          const double2* cw = cbase + (size_t)kw * 2 * plane;
-          const double2 wlo = cw[0], whi = cw[plane];
-          const double y[4] = {wlo.x, wlo.y, whi.x, whi.y};
-          anc_matvec(pin + (size_t)kw * 16, y, m);
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) M[i] = A[i] * m[i];
+        const int kc = tree_sibling_message(tt, word, msa, n_prune, pat, all_n, m);
+        tree_join(A, m, M);
         const double2* cv = cbase + (size_t)kc * 2 * plane;
         const double2 lo = cv[0], hi = cv[plane];
         const double Lb[4] = {lo.x, lo.y, hi.x, hi.y};
         off = sub_edge<4, 1>(M, pin + (size_t)kc * 16, Lb, rj, J, cc);
-        // the message into v_{s-1}, as K11b forms it
-        anc_vecmat(pin + (size_t)kc * 16, M, A);
-        const double top = fmax(fmax(A[0], A[1]), fmax(A[2], A[3]));
-        if (top > 0.0 && top < INFINITY) {
-          const double inv = 1.0 / top;
-#pragma unroll
-          for (int i = 0; i < 4; ++i) A[i] *= inv;
-        }
+        tree_push_down(pin, kc, M, A);  // the message into v_{s-1}
       }
       if (kWriteEdges && live) sub_store16(edge_part + ((sr * P + s) * L + site) * 16, J);
       const double tot = sub_wave_sum(live ? off : 0.0);
@@ -292,35 +266,6 @@ __global__ void __launch_bounds__(kSubWaves * 64) sub_kernel(int R, int T, int L
     for (int w = 1; w < kSubWaves; ++w) v += load[(size_t)w * (P + 1) + s];
     el_part[sr * (P + 1) + s] = v;
   }
-}
-
-// K12m.  part[n][R][slots][width], out[n][slots][width]; slot s of a sample is live if s < plen, or if it is the last and
-// last_live (edge_load's naive edge).
-__global__ void __launch_bounds__(256) sub_combine_kernel(int n, int R, int slots, long long width, bool last_live,
-                                                          const int32_t* __restrict__ plen, const double* __restrict__ part,
-                                                          double* __restrict__ out) {
-  const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  const long long per = (long long)slots * width;
-  if (gid >= (long long)n * per) return;
-  const int sample = (int)(gid / per);
-  const long long cell = gid - (long long)sample * per;
-  const int s = (int)(cell / width);
-  const int len = plen[sample];
-  double v = 0.0;
-  if (len == 0) {
-    v = __builtin_nan("");
-  } else if (s < len || (last_live && s == slots - 1)) {
-    for (int k = 0; k < R; ++k) v += part[((size_t)sample * R + k) * per + cell];
-  }
-  out[gid] = v;
-}
-
-void combine(int n, int R, int slots, size_t width, bool last_live, const int32_t* plen, const double* part, double* out,
-             hipStream_t stream) {
-  if (!out) return;
-  const long long cells = (long long)n * slots * (long long)width;
-  hipLaunchKernelGGL(sub_combine_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, stream, n, R, slots,
-                     (long long)width, last_live, plen, part, out);
 }
 
 }  // namespace
@@ -363,11 +308,11 @@ int launch_substitutions(const DevFamily& fam, int n, int R, int T, const int32_
   else
     run(sub_kernel<false>, nullptr);
   const size_t l = (size_t)L;
-  combine(n, R, P, l * 16, false, ws.plen, sws.edge, out.edge, stream);
-  combine(n, R, 1, l * 20, false, ws.plen, sws.ne, out.naive_edge, stream);
-  combine(n, R, 1, l * 16, false, ws.plen, sws.cc, out.chain_counts, stream);
-  combine(n, R, 1, l * 16, false, ws.plen, sws.se, out.seed_edge, stream);
-  combine(n, R, P + 1, 1, true, ws.plen, sws.el, out.edge_load, stream);
+  launch_rate_sum(n, R, P, l * 16, false, ws.plen, sws.edge, out.edge, stream);
+  launch_rate_sum(n, R, 1, l * 20, false, ws.plen, sws.ne, out.naive_edge, stream);
+  launch_rate_sum(n, R, 1, l * 16, false, ws.plen, sws.cc, out.chain_counts, stream);
+  launch_rate_sum(n, R, 1, l * 16, false, ws.plen, sws.se, out.seed_edge, stream);
+  launch_rate_sum(n, R, P + 1, 1, true, ws.plen, sws.el, out.edge_load, stream);
   return 0;
 }
 
