@@ -383,10 +383,7 @@ __global__ void __launch_bounds__(256) asr_kernel(int R, int T, int L, int n_pru
             }
 #pragma unroll
             for (int q = 0; q < 4; ++q) a[q] = u[q] * v[q];
-            if (fmax(fmax(a[0], a[1]), fmax(a[2], a[3])) < kScaleThreshold) {
-#pragma unroll
-              for (int q = 0; q < 4; ++q) a[q] *= kScaleFactor;
-            }
+            tree_rescale(a);
             double2* ck = clv_s + (size_t)kk * 2 * plane + gslot;
             ck[0] = make_double2(a[0], a[1]);
             ck[plane] = make_double2(a[2], a[3]);

@@ -155,6 +155,16 @@ __device__ static inline double fast_rcp(double v) {
   return r;
 }
 
+// The 2^256 rescaling of a conditional-likelihood vector (entries >= 0) goes on until its largest entry is back at or
+// above 2^-256: a tip joining the accumulator falls by one mismatch, but the join of two subtrees that each sit up to 256
+// binades down leaves the product up to 512 and a mismatch further down.  How many multiplications by 2^256 that takes
+// (1 .. 3), from the high word hw < 0x2FF00000 of the largest entry: with its biased exponent E >= 1 the entry is
+// a < 2^-256 and a 2^(256 n) >= 2^-256 needs E + 256 n >= 767.  A subnormal largest entry (E = 0: bits are lost already)
+// gets the three of E = 1, and a vector with nothing left to bring back (hw = 0) is rescaled once, as it always was.
+__device__ static __forceinline__ int rescale_steps(unsigned hw) {
+  return hw == 0u ? 1 : (int)((1022u - (hw >> 20)) >> 8);
+}
+
 // K4 (lh_sample.hip): what a backward sampling step needs of one junction, in the unfused form FillTransition
 // multiplies it together (src/HMM.cpp:964-1089), so that every weight has the bits of the dense matrices.
 // Unpadded [W][nL] / [W][nR] tables; dense = index in the reference's junction state vector.

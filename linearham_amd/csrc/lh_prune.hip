@@ -307,6 +307,11 @@ __device__ __forceinline__ void prune_wave(int site0, int site_end, const uint8_
     // when that word is below 0x2FF00000 (integer compares instead of 7 FP64 max/compare).
     // (An all-zero CLV -- impossible data -- counts as small too: rescaling it changes nothing but its
     // counter, and K2a aligns the rates' counters before it mixes them.)
+    // The rescaling goes on until the largest entry is back at or above 2^-256, every 2^256 counted (rescale_steps: a
+    // join of two subtrees can leave the product more than 512 binades down); an all-zero vector is rescaled once.
+    // Here the first multiplication stands as it always did and the further ones, needed below 2^-512 only, sit in a
+    // branch of their own behind it: this walk's kernels run at their register limit, and in this form the
+    // allocation of the loop around it stays what it was.
     unsigned hw[S];
 #pragma unroll
     for (int s = 0; s < S; ++s)
@@ -324,6 +329,19 @@ __device__ __forceinline__ void prune_wave(int site0, int site_end, const uint8_
           a[s][2] *= kScaleFactor;
           a[s][3] *= kScaleFactor;
           ++scal[s];
+        }
+      }
+      if (__builtin_expect(__ballot(hmin < 0x1FF00000u) != 0, 0)) {
+#pragma unroll
+        for (int s = 0; s < S; ++s) {
+          if (hw[s] < 0x1FF00000u) {
+            const int n = rescale_steps(hw[s]) - 1;  // (0 for the all-zero vector)
+            a[s][0] = ldexp(a[s][0], n << 8);
+            a[s][1] = ldexp(a[s][1], n << 8);
+            a[s][2] = ldexp(a[s][2], n << 8);
+            a[s][3] = ldexp(a[s][3], n << 8);
+            scal[s] += n;
+          }
         }
       }
     }
@@ -659,11 +677,12 @@ __device__ __forceinline__ void prune_wave_ct(int site0, int site_end, const uin
 #pragma unroll
       for (int s = 0; s < S; ++s) {
         if (hw[s] < 0x2FF00000u) {
-          a[s][0] *= kScaleFactor;
-          a[s][1] *= kScaleFactor;
-          a[s][2] *= kScaleFactor;
-          a[s][3] *= kScaleFactor;
-          ++scal[s];
+          const int n = rescale_steps(hw[s]);
+          a[s][0] = ldexp(a[s][0], n << 8);
+          a[s][1] = ldexp(a[s][1], n << 8);
+          a[s][2] = ldexp(a[s][2], n << 8);
+          a[s][3] = ldexp(a[s][3], n << 8);
+          scal[s] += n;
         }
       }
     }

@@ -81,6 +81,17 @@ __device__ static __forceinline__ void tree_vecmat(const double* p, const double
   for (int c = 0; c < 4; ++c) x[c] = fma(p[12 + c], a[3], fma(p[8 + c], a[2], fma(p[4 + c], a[1], p[c] * a[0])));
 }
 
+// The 2^256 rescaling of an upward CLV after an op, until the largest entry is back at or above 2^-256 (rescale_steps;
+// the tree passes normalise per node, so no count is kept).
+__device__ static __forceinline__ void tree_rescale(double (&a)[4]) {
+  const double top = fmax(fmax(a[0], a[1]), fmax(a[2], a[3]));
+  if (__builtin_expect(top < kScaleThreshold, 0)) {
+    const int n = rescale_steps((unsigned)__double2hiint(top));
+#pragma unroll
+    for (int q = 0; q < 4; ++q) a[q] = ldexp(a[q], n << 8);
+  }
+}
+
 // The LDS tables of a (sample, rate): tiptab[T][4][4] columns of the tip branches' P (the K1 tip table), pin[T-2][4][4]
 // row-major P of the inner branches, by the op that produced the child (entry T-3 unused).  The caller synchronises the
 // workgroup behind it.
@@ -178,10 +189,7 @@ __device__ static __forceinline__ void tree_upward_pattern(int n_ops, int n_prun
     }
 #pragma unroll
     for (int q = 0; q < 4; ++q) a[q] = u[q] * v[q];
-    if (fmax(fmax(a[0], a[1]), fmax(a[2], a[3])) < kScaleThreshold) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q) a[q] *= kScaleFactor;
-    }
+    tree_rescale(a);
     if (kStoreAll || (da.x >> 8) != 0) {
       double2* ck = clv_s + (size_t)k * 2 * plane + pat;
       ck[0] = make_double2(a[0], a[1]);
@@ -235,8 +243,9 @@ __device__ static __forceinline__ void tree_join(const double (&A)[4], const dou
   for (int i = 0; i < 4; ++i) M[i] = A[i] * m[i];
 }
 
-// A = M^T P_kc, the message into v_{s-1} through its branch, divided by its largest entry (a CLV's largest entry lies
-// anywhere in [2^-256, 1], so a few unnormalised steps would underflow).
+// A = M^T P_kc, the message into v_{s-1} through its branch, divided by its largest entry (a stored CLV's largest entry
+// lies anywhere in [2^-256, 1] -- tree_rescale repeats until it does, as long as the op's own product stayed above the
+// subnormals --, so a few unnormalised steps would underflow).
 __device__ static __forceinline__ void tree_push_down(const double* pin, int kc, const double (&M)[4], double (&A)[4]) {
   tree_vecmat(pin + (size_t)kc * 16, M, A);
   const double top = fmax(fmax(A[0], A[1]), fmax(A[2], A[3]));

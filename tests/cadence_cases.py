@@ -30,6 +30,24 @@ and for every row: the every-op restatement is unchanged when every entry below 
 that matters goes subnormal in a correct every-op walk), and no allele lies more than 2^-900 below its set's best (the
 extended-range mode's documented reach).
 
+Joins (family cmp180, rows compound_*).  One 2^256 rescaling per op is enough on a ladder: a tip joining the accumulator falls
+by one mismatch.  The product of two subtrees that sit d_a and d_b binades down, with m more for a state mismatch, lies
+d_a + d_b + m down, and after ONE rescaling still d_a + d_b + m - 256: more than 256, and the next join doubles it.  The
+compound family's tree (compound_newick) is cad190's ladder of background tips, every branch 100, with one balanced block
+spliced in as an element: eight four-tip ladders joined pairwise, every branch of the block 1e-6.  On its four deep columns
+(V, both junctions, J) every tip holds the rare base A except the block's, whose ladders alternate between (A, A, A, Y) and
+(Z, Z, Z, W).  In the live slow category a ladder then sits one mismatch down (2^-222), a pair of ladders three (2^-666;
+2^-410 after one rescaling), four ladders 2^-820 (2^-564), and the eight multiply to 2^-1128: 0 in double, where the exact
+vector is 2^-2655 at state A with 12 substitutions.  Rescaling UNTIL the largest entry is back at or above 2^-256, each
+rescaling counted, keeps every stored vector within [2^-256, 1] and is exact as long as one op's own product stays above
+2^-1022 (d_a + d_b + m with both d <= 256: check_row asserts it through the flushed restatement).  Classes:
+  compound_control  the tree at alpha = 1 with every branch 1e-4 of its length, as `control`
+  compound_clear    tree "D": the same shape with the like ladders joined first, so that the unlike halves meet at the block's
+                    last join alone: no vector lies more than 256 down after its rescaling, and both restatements are exact
+  compound_lossy    block branches of 1.8e-5 (a mismatch costs 2^-218): with one rescaling per op the last join's product lands in
+                    (2^-1074, 2^-1022) and the live category is more than 1e-3 off, finitely; rescale-until is exact
+  compound_zeroed   block branches of 1e-6: with one rescaling per op the live category's whole vector is 0; rescale-until is exact
+
 The log-likelihood reference (reference_loglik): every path emits each site once.  The exact emissions E (ExactModel.prune's
 log2_emission per (naive base, site)) are brought to benign doubles by one integer k_t per site, the numpy oracle runs its
 forward sweep on E 2^k_t, and ln 2 * sum k_t is taken off again.  (The issue's window [2^-200, 1] for a site's five emissions
@@ -55,13 +73,23 @@ LIVE_BITS = 60
 DEEP_LOG2 = -1100.0
 EXT_SPREAD_BITS = 900
 SITE_WINDOW_BITS = 256
+LOSSY_BLOCK = 1.8e-5          # block branches of the compound_lossy row: a mismatch costs 2^-218 instead of SHORT's 2^-222
 
 # name -> (leaves, R, synth seed, elements of tree "A" as (first tip, tips) runs: 1 = ladder tips, 2 = cherry then tip
 # alternating, deep columns as (site, first mutated tip, mutated tips))
 FAMILIES = {
     "cad190": dict(n_leaves=190, R=2, seed=71, cherries=(120, 160),
                    deep=[(5, 20, 12), (9, 21, 12), (17, 22, 12), (23, 23, 12), (29, 120, 12), (40, 123, 12), (44, 61, 12)]),
+    # the compound family (module docstring, "Joins"): block = (first tip, four-tip ladders) of the balanced block; deep
+    # columns as (site, which of BLOCK_BASES the block's tips take)
+    "cmp180": dict(n_leaves=180, R=2, seed=72, block=(40, 8), deep=[(5, 0), (23, 1), (29, 2), (44, 3)]),
 }
+# (Y, Z, W) of a deep column of the compound family: ladder j of the block holds (A, A, A, Y) for even j, (Z, Z, Z, W) for odd
+BLOCK_BASES = [(1, 2, 3), (2, 3, 1), (3, 1, 2), (1, 3, 2)]
+# the block's ladders in the order the balanced tree joins them pairwise: tree "C" as they lie in the alignment (every join
+# pairs an (A, A, A, Y) subtree with a (Z, Z, Z, W) one or two like halves), tree "D" the even ladders first (unlike halves
+# meet at the block's last join alone)
+BLOCK_ORDER = {"C": (0, 1, 2, 3, 4, 5, 6, 7), "D": (0, 2, 4, 6, 1, 3, 5, 7)}
 
 # (name, family, class, tree, alpha, first and last tip of the stretch on short branches or None, length of those branches,
 #  factor on every branch)
@@ -73,7 +101,13 @@ ROWS = [
     ("lossy_long", "cad190", "lossy", "A", 0.005, None, SHORT, 1.0),
     ("lossy_scaled", "cad190", "lossy", "A", 0.005, (59, 75), 1e-4, 1.0),
     ("zeroed_cherries", "cad190", "zeroed", "A", 0.005, (118, 137), SHORT, 1.0),
+    # the compound family: trees "C" and "D" (compound_newick); the stretch is unused, the length is the block's branches'
+    ("compound_control", "cmp180", "compound_control", "C", 1.0, None, SHORT, 1e-4),
+    ("compound_clear", "cmp180", "compound_clear", "D", 0.005, None, SHORT, 1.0),
+    ("compound_lossy", "cmp180", "compound_lossy", "C", 0.005, None, LOSSY_BLOCK, 1.0),
+    ("compound_zeroed", "cmp180", "compound_zeroed", "C", 0.005, None, SHORT, 1.0),
 ]
+COMPOUND = ("compound_control", "compound_clear", "compound_lossy", "compound_zeroed")
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -103,12 +137,38 @@ def load_family(name, workdir):
     assert n == FAMILIES[name]["n_leaves"] and len(naive) == L
     base = np.array(["ACGTN".index(c) for c in naive], dtype=np.int32)
     msa = np.tile(base, (n, 1))
-    for site, first, count in FAMILIES[name]["deep"]:
-        msa[:, site] = 0
-        msa[first:first + count, site] = 1 + np.arange(count) % 3        # C, G, T, C, ...
+    if "block" in FAMILIES[name]:
+        first, ladders = FAMILIES[name]["block"]
+        for site, which in FAMILIES[name]["deep"]:
+            y, z, w = BLOCK_BASES[which]
+            msa[:, site] = 0
+            for j in range(ladders):
+                msa[first + 4 * j:first + 4 * j + 4, site] = (0, 0, 0, y) if j % 2 == 0 else (z, z, z, w)
+    else:
+        for site, first, count in FAMILIES[name]["deep"]:
+            msa[:, site] = 0
+            msa[first:first + count, site] = 1 + np.arange(count) % 3        # C, G, T, C, ...
     h.msa = msa
     h._initialize_xmsa_structs()
     return h
+
+
+def write_family_files(name, workdir, h):
+    """What the host library needs of a family that load_family(name, workdir) returned as `h`: a copy of its cluster file with
+    the replaced alignment written in, next to the generated one.  Returns (the copy's path, the parameter directory)."""
+    out = os.path.join(str(workdir), name)
+    with open(os.path.join(out, "cluster.yaml")) as f:
+        d = json.load(f)
+    ev = d["events"][0]
+    assert ev["unique_ids"] == list(h.xmsa_labels)[1:]
+    ev["input_seqs"] = ["".join("ACGTN"[int(b)] for b in row) for row in h.msa]
+    ev["indel_reversed_seqs"] = ["" for _ in ev["input_seqs"]]
+    path = os.path.join(out, "cluster_replaced.yaml")
+    with open(path, "w") as f:
+        json.dump(d, f)
+    again = orc.PhyloHMM(path, 0, os.path.join(out, "hmm_params"), 0)
+    assert np.array_equal(again.msa, h.msa) and np.array_equal(again.xmsa, h.xmsa) and list(again.xmsa_labels) == list(h.xmsa_labels)
+    return path, os.path.join(out, "hmm_params")
 
 
 def elements(name, tree):
@@ -149,9 +209,36 @@ def tree_newick(name, tree, short=None, short_len=SHORT, scale=1.0):
     return "(%s:%s,naive:%s,%s);" % (node, fmt(LONG), fmt(LONG), text(el[-1]))
 
 
+def compound_newick(name, tree, block_len=SHORT, scale=1.0):
+    """Newick of the compound family's tree: the ladder of tree_newick over the background tips, every branch LONG, with one
+    element that is the balanced block -- its four-tip ladders (((t0, t1), t2), t3), the tip that differs last, joined
+    pairwise in BLOCK_ORDER[tree]'s order; every branch inside the block and the one above it is block_len; all times
+    `scale`."""
+    n = FAMILIES[name]["n_leaves"]
+    first, ladders = FAMILIES[name]["block"]
+    fmt = lambda x: "%.12g" % max(x * scale, 1e-6)
+    b, long_ = fmt(block_len), fmt(LONG)
+    nodes = []
+    for j in BLOCK_ORDER[tree]:
+        t = first + 4 * j
+        nodes.append("(((s%d:%s,s%d:%s):%s,s%d:%s):%s,s%d:%s)" % (t, b, t + 1, b, b, t + 2, b, b, t + 3, b))
+    while len(nodes) > 1:
+        nodes = ["(%s:%s,%s:%s)" % (nodes[i], b, nodes[i + 1], b) for i in range(0, len(nodes), 2)]
+    el = ["s%d:%s" % (t, long_) for t in range(first)] + ["%s:%s" % (nodes[0], b)] + \
+         ["s%d:%s" % (t, long_) for t in range(first + 4 * ladders, n)]
+    node = "(%s,%s)" % (el[0], el[1])
+    for k in range(2, len(el) - 1):
+        node = "(%s:%s,%s)" % (node, long_, el[k])
+    return "(%s:%s,naive:%s,%s);" % (node, long_, long_, el[-1])
+
+
 def sample_of(row):
     name, fam, cls, tree, alpha, short, short_len, scale = row
-    return dict(tree=tree_newick(fam, tree, short, short_len, scale), er=ER, pi=PI, alpha=float(alpha)), FAMILIES[fam]["R"]
+    if tree in BLOCK_ORDER:
+        newick = compound_newick(fam, tree, short_len, scale)
+    else:
+        newick = tree_newick(fam, tree, short, short_len, scale)
+    return dict(tree=newick, er=ER, pi=PI, alpha=float(alpha)), FAMILIES[fam]["R"]
 
 
 def schedule(h, sample):
@@ -185,17 +272,25 @@ def walk_groups(ops, use_tables=True):
     return groups
 
 
-def restate_walk(T, ops, pats, P, pi, w, use_tables=True, flush=False):
+def restate_walk(T, ops, pats, P, pi, w, use_tables=True, flush=False, until=False):
     """K1's walk in numpy doubles over the schedule `ops`, all patterns at once.  pats [T-1, n] tip states (4 = N), P
     [2T-2, R, 4, 4] the P-matrix above every node.  The 2^256 test looks at the LARGEST entry, after every w-th walk op
     and after the last: w = 1 rescales once per test (the C++ walks), w > 1 until the largest entry is back above 2^-256
-    or has a zero high word (the assembly walk).  flush: every entry below 2^-1022 is set to 0 after each op.
+    or has a zero high word (the assembly walk); w = 1 with until: after every op, rescaled until the largest entry is back
+    at or above 2^-256, each rescale counted (what a join of two subtrees needs -- module docstring, "Joins").  This is the
+    device's arithmetic (lh_device.h rescale_steps) wherever the largest entry an op leaves is a normal number; where it is
+    subnormal -- bits are lost already: outside the mode's reach, and check_row asserts through `flush` that no row gets
+    there -- the device reads the count off the exponent field alone: three for [2^-1042, 2^-1022), where this loop makes
+    four below 2^-1024, and one for a zero high word, where this loop goes on unless the vector is 0.
+    flush: every entry below 2^-1022 is set to 0 after each op.
     Returns log2 [R, 5, n] of the per-rate site likelihood by naive state (counts taken off), zeroed [R, n]: the whole
-    vector was 0 after some op, low [R, n]: log2 of the smallest positive entry any op left."""
+    vector was 0 after some op, low [R, n]: log2 of the smallest positive entry any op left, top_low [R, n]: log2 of the
+    smallest positive LARGEST entry any op left (before its rescaling)."""
     R, n = P.shape[1], pats.shape[1]
     groups = walk_groups(ops, use_tables)
     onehot = np.concatenate([np.eye(4), np.ones((1, 4))], axis=0)
     out, zeroed, low = np.zeros((R, 5, n)), np.zeros((R, n), bool), np.full((R, n), np.inf)
+    top_low = np.full((R, n), np.inf)
     thr, fac = 2.0 ** -256, 2.0 ** 256
     with np.errstate(all="ignore"):
         for r in range(R):
@@ -218,12 +313,13 @@ def restate_walk(T, ops, pats, P, pi, w, use_tables=True, flush=False):
                 pos = np.where(acc > 0, acc, np.inf).min(axis=0)
                 low[r] = np.minimum(low[r], pos)
                 zeroed[r] |= acc.max(axis=0) == 0
+                top_low[r] = np.minimum(top_low[r], np.where(acc.max(axis=0) > 0, acc.max(axis=0), np.inf))
                 if wi % w == w - 1 or wi == len(groups) - 1:
                     need = acc.max(axis=0) < thr                     # (an all-zero vector is rescaled once and left)
                     while need.any():
                         acc = np.where(need, acc * fac, acc)
                         count += need
-                        if w == 1:
+                        if w == 1 and not until:
                             break
                         mx = acc.max(axis=0)
                         need = (mx < thr) & (mx >= 2.0 ** -1042)    # a zero high word counts as nothing left
@@ -231,7 +327,7 @@ def restate_walk(T, ops, pats, P, pi, w, use_tables=True, flush=False):
             for b in range(5):
                 lik = (wgt * (P[0, r] @ onehot[b])[:, None]).sum(axis=0)
                 out[r, b] = np.log2(lik) - 256.0 * count
-    return {"log2": out, "zeroed": zeroed, "low": np.log2(low)}
+    return {"log2": out, "zeroed": zeroed, "low": np.log2(low), "top_low": np.log2(top_low)}
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -352,9 +448,11 @@ def analyse_row(h, row, exact=None):
     pats = np.zeros((T - 1, int(x["pattern_of"].max()) + 1), dtype=np.int64)
     pats[:, x["pattern_of"]] = h.xmsa[1:]
     dev, zeroed, walks = {}, {}, {}
-    for tag, w, tables, flush in (("w1", 1, True, False), ("w4", 4, True, False), ("w4_no_tables", 4, False, False),
-                                  ("w1_flush", 1, True, True)):
-        rs = restate_walk(T, ops, pats, x["P"], sample["pi"], w, use_tables=tables, flush=flush)
+    for tag, w, tables, flush, until in (("w1", 1, True, False, False), ("w4", 4, True, False, False),
+                                         ("w4_no_tables", 4, False, False, False), ("w1_flush", 1, True, True, False),
+                                         ("u1", 1, True, False, True), ("u1_no_tables", 1, False, False, True),
+                                         ("u1_flush", 1, True, True, True)):
+        rs = restate_walk(T, ops, pats, x["P"], sample["pi"], w, use_tables=tables, flush=flush, until=until)
         got = rs["log2"][:, naive, x["pattern_of"]]                     # [R, C]
         d = np.where(live, relative_deviation(got, per_rate), 0.0)
         dev[tag] = d
@@ -369,6 +467,8 @@ def analyse_row(h, row, exact=None):
                live_slow=bool(live[0][deep_cols].all() and not live[1:][:, deep_cols].any()),
                dev={k: float(v.max()) for k, v in dev.items()}, dev_cols=dev, zeroed=zeroed,
                low_w1=float(np.where(live, walks["w1"]["low"][:, x["pattern_of"]], np.inf).min()),
+               join_low_w1=float(np.where(live, walks["w1"]["top_low"][:, x["pattern_of"]], np.inf).min()),
+               join_low_u1=float(np.where(live, walks["u1"]["top_low"][:, x["pattern_of"]], np.inf).min()),
                four_op_fall=float(top), entry_fall=float(np.nanmin(ent)) if np.isfinite(ent).any() else 0.0,
                spread=ext_spread_bits(h, x["log2_emission"]), walk_ops=len(walk_groups(ops)), live=live, exact=x)
     return out
@@ -378,10 +478,27 @@ def check_row(a):
     """The conditions of the row's class (module docstring)."""
     name, cls, dev = a["name"], a["cls"], a["dev"]
     assert a["depth"] <= 4, (name, "the default form must be the fused cherry-table kernel of depth <= 4", a["depth"])
+    assert a["spread"] <= EXT_SPREAD_BITS, (name, "an allele beyond the extended-range mode's reach", a["spread"])
+    # rescale-until is the arithmetic the device has: exact on every row, with and without cherry tables, and no entry that
+    # matters goes subnormal on the way (the residual reach: one op's own product stays above 2^-1022)
+    assert dev["u1"] <= 1e-12 and dev["u1_no_tables"] <= 1e-12, (name, "the rescale-until restatement is not the exact value", dev["u1"])
+    assert dev["u1_flush"] <= 1e-12 and not a["zeroed"]["u1"], (name, "an op's product goes subnormal in the rescale-until walk", dev["u1_flush"])
+    if cls in ("compound_lossy", "compound_zeroed"):
+        assert a["deepest"] < DEEP_LOG2, (name, "a deep column above 2^-1100", a["deepest"])
+        assert a["live_slow"], (name, "the slow category alone must be live on the deep columns")
+        if cls == "compound_zeroed":
+            assert a["zeroed"]["w1"], (name, "no live category's vector reaches 0 with one rescale per op")
+        else:
+            assert not a["zeroed"]["w1"] and 1e-3 < dev["w1"] < np.inf, (name, "one rescale per op is not finitely off", dev["w1"])
+            assert -1074 < a["join_low_w1"] < -1022, (name, "no join's product in (2^-1074, 2^-1022)", a["join_low_w1"])
+        return
     assert dev["w1"] <= 1e-12, (name, "the every-op restatement is not the exact value", dev["w1"])
     assert dev["w1_flush"] <= 1e-12 and not a["zeroed"]["w1"], (name, "an entry that matters goes subnormal in the every-op walk", dev["w1_flush"])
-    assert a["spread"] <= EXT_SPREAD_BITS, (name, "an allele beyond the extended-range mode's reach", a["spread"])
-    if cls == "control":
+    if cls == "compound_clear":                 # the tree's shape alone is harmless: one rescale per op is exact as well
+        assert a["deepest"] < DEEP_LOG2 and a["live_slow"], (name, a["deepest"])
+        assert a["join_low_w1"] > -1022, (name, a["join_low_w1"])
+        return
+    if cls in ("control", "compound_control"):
         assert dev["w4"] <= 1e-12 and a["log2_emission"].min() > -900, (name, dev["w4"], a["log2_emission"].min())
         return
     assert a["deepest"] < DEEP_LOG2, (name, "a deep column above 2^-1100", a["deepest"])
@@ -395,27 +512,46 @@ def check_row(a):
 
 
 def _analyse(args):
-    """One row in a pool process: the family is generated again there (deterministic, half a second)."""
+    """One row in a pool process: the family is generated again there (deterministic, half a second).  Returns the analysis
+    and the seconds it took (the exact side -- mpmath pruning -- and the restatements)."""
     import shutil
     import tempfile
+    import time
     name, row = args
     work = tempfile.mkdtemp(prefix="lh_cadence_")
     try:
-        return analyse_row(load_family(name, work), row)
+        h = load_family(name, work)
+        t0 = time.perf_counter()
+        a = analyse_row(h, row)
+        return a, time.perf_counter() - t0
     finally:
         shutil.rmtree(work, ignore_errors=True)
 
 
-def build_family(name, workdir, jobs=1):
-    """(h, [(row, analysis)]) of one family, every row checked; jobs > 1: the rows' exact sides on a pool of processes."""
-    h = load_family(name, workdir)
-    rows = [row for row in ROWS if row[1] == name]
+def build_families(names, workdir, jobs=1):
+    """{name: (h, [(row, analysis)], seconds)} of the families, every row checked; jobs > 1: the rows of all families on one
+    pool of processes.  seconds: the family's rows' analyses, summed."""
+    import time
+    hs = {name: load_family(name, workdir) for name in names}
+    todo = [(row[1], row) for row in ROWS if row[1] in names]
     if jobs > 1:
         import multiprocessing as mp
-        with mp.get_context("spawn").Pool(min(jobs, len(rows))) as pool:
-            done = pool.map(_analyse, [(name, row) for row in rows])
+        with mp.get_context("spawn").Pool(min(jobs, len(todo))) as pool:
+            done = pool.map(_analyse, todo)
     else:
-        done = [analyse_row(h, row) for row in rows]
-    for a in done:
+        done = []
+        for name, row in todo:
+            t0 = time.perf_counter()
+            done.append((analyse_row(hs[name], row), time.perf_counter() - t0))
+    out = {name: (hs[name], [], 0.0) for name in names}
+    for (name, row), (a, sec) in zip(todo, done):
         check_row(a)
-    return h, list(zip(rows, done))
+        h, rows, total = out[name]
+        out[name] = (h, rows + [(row, a)], total + sec)
+    return out
+
+
+def build_family(name, workdir, jobs=1):
+    """(h, [(row, analysis)]) of one family, every row checked."""
+    h, rows, _ = build_families([name], workdir, jobs)[name]
+    return h, rows

@@ -20,6 +20,11 @@ independent reference:
     numpy oracle's is, the control rows pass compare();
  d. every row bit-identical alone and as row 1 of a call of two, in extended range;
  e. K3 on the lossy and zeroed rows: every deep site draws the rate category the exact per-rate values make certain.
+The same five on the compound family (cmp180: a balanced block of eight four-tip ladders spliced into the ladder of
+background tips, schedule stack depth 4), where the join of two deep subtrees needs MORE THAN ONE 2^256 rescaling per op: the
+C++ walks and K3b's upward pass rescale until the largest entry is back at or above 2^-256, counting each (lh_device.h
+rescale_steps).  With one rescaling per op every form returned -8949.78 for -7742.19 on compound_zeroed and was 2.7e-6 off on
+compound_lossy, and K3 drew the dead category on all four deep sites of compound_zeroed (profiles/r23_compound_joins_gpu.txt).
 LH_CADENCE_DIR keeps the children's files and profile_gpu.txt, the figures per row and form."""
 import json
 import os
@@ -37,7 +42,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 WORKER = os.path.join(ROOT, "tests", "cadence_worker.py")
 CHILD_TIMEOUT = 120
 
-# The forms lh_family_prune_form must report for this family (191 tips, stack depth 1, 16 site patterns, R = 2; %N: whether
+# The forms lh_family_prune_form must report for both families (cad190: 191 tips, stack depth 1, 16 site patterns; cmp180: 181
+# tips, stack depth 4 -- still within the four register slots of the <4,...> kernels; R = 2; %N: whether
 # the alignment mixes N with bases -- it does not): (default mode, extended range, K3's unfused launch).  Fused, the shape
 # takes the cherry-table kernel; a workgroup per (sample, rate) would hold fewer than five waves per SIMD next to a whole tip
 # table, so unfused it takes the segmented register-stack kernel unless a tables hook asks for the cherry-table form.  In
@@ -48,6 +54,18 @@ SEG, STACK = r"seg4<4,false>", r"w[456]<[34],false>"
 EXPECT = {"default": (CT, CT_CXX, SEG), "stack": (STACK, STACK, SEG), "tables": (CT, CT_CXX, CT_UNFUSED_CXX),
           "tables_cxx": (CT_CXX, CT_CXX, CT_UNFUSED_CXX), "no_tables": (CT, CT_CXX, CT_UNFUSED_CXX), "no_fuse": (SEG, SEG, SEG),
           "segments": (SEG, SEG, SEG)}
+# Read off lh_family_prune_form on an MI355X and pinned, per family: (default mode, extended range, K3's unfused launch).  The
+# register-stack kernel's first template argument is its number of register slots: cad190 (stack depth 1) takes the three-slot
+# kernel, cmp180 (depth 4) the four-slot one; every other form has the same arguments for both.
+PINNED = {
+    "cad190": {"default": ("ct4<4,false,true,true>", "ct4<4,false,true,false>", "seg4<4,false>"),
+               "stack": ("w4<3,false>", "w4<3,false>", "seg4<4,false>"),
+               "tables": ("ct4<4,false,true,true>", "ct4<4,false,true,false>", "ct4<4,false,false,false>"),
+               "tables_cxx": ("ct4<4,false,true,false>", "ct4<4,false,true,false>", "ct4<4,false,false,false>"),
+               "no_tables": ("ct4<4,false,true,true>", "ct4<4,false,true,false>", "ct4<4,false,false,false>"),
+               "no_fuse": ("seg4<4,false>",) * 3, "segments": ("seg4<4,false>",) * 3},
+}
+PINNED["cmp180"] = dict(PINNED["cad190"], stack=("w4<4,false>", "w4<4,false>", "seg4<4,false>"))
 
 
 @pytest.fixture(scope="module")
@@ -71,10 +89,13 @@ def runs(tmp_path_factory):
     lines = ["Rescaling cadence rows on the device: relative deviation of the extended-range log-likelihood from the reference per "
              "row and K1 form (default mode / extended range / K3), largest |log_cand - prior + loglik - sum log E| over the candidates"]
     for tag, rep in reports.items():
-        lines.append("%s: %s / %s / %s" % (tag, rep["forms"]["default"], rep["forms"]["extended"], rep["forms"]["asr"]))
+        lines.append("%s: %s" % (tag, "; ".join("%s %s / %s / %s" % (fam, fo["default"], fo["extended"], fo["asr"])
+                                                for fam, fo in rep["forms"]["families"].items())))
         for f in rep["figures"]:
-            lines.append("  %-16s %-8s extended %.12f  reference %.12f  d %.2g (bound %.2g)  default mode %s  candidates %.2g" %
-                         (f["row"], f["cls"], f["loglik_ext"], f["reference"], f["d_ll_ext"], f["bound"], f["loglik_default"], f["d_candidates"]))
+            k3 = "  K3 wrong category on %d of %d deep sites" % (f["asr_wrong"], f["asr_sites"]) if "asr_sites" in f else ""
+            lines.append("  %-16s %-16s extended %.12f  reference %.12f  d %.2g (bound %.2g)  default mode %s  candidates %.2g%s" %
+                         (f["row"], f["cls"], f["loglik_ext"], f["reference"], f["d_ll_ext"], f["bound"], f["loglik_default"],
+                          f["d_candidates"], k3))
         for g, fl in rep["failures"].items():
             lines += ["  FAILED %s: %s" % (g, t) for t in fl]
     with open(os.path.join(out, "profile_gpu.txt"), "w") as f:
@@ -97,8 +118,11 @@ def test_forms_ran(runs, tag):
     _, reports, _ = runs
     rep = reports[tag]
     assert rep["rows"] == len(cc.ROWS) == len(rep["figures"])
-    for mode, pattern in zip(("default", "extended", "asr"), EXPECT[tag]):
-        assert re.fullmatch(pattern, rep["forms"][mode]), (tag, mode, rep["forms"][mode], pattern)
+    assert set(rep["forms"]["families"]) == set(cc.FAMILIES)
+    for family, forms in rep["forms"]["families"].items():
+        for mode, pattern, pinned in zip(("default", "extended", "asr"), EXPECT[tag], PINNED[family][tag]):
+            assert re.fullmatch(pattern, forms[mode]), (tag, family, mode, forms[mode], pattern)
+            assert forms[mode] == pinned, (tag, family, mode, forms[mode], pinned)
 
 
 @pytest.mark.parametrize("tag", list(FORMS))
@@ -112,11 +136,14 @@ def test_extended_range_against_the_reference(runs, tag):
 def test_forms_agree_in_extended_range(runs, tag):
     """(a): a hooked form against the default one in extended range: log-likelihood 1e-13, counts exactly."""
     out = runs[0]
+    from tests import cadence_cases as cc
     a, b = np.load(os.path.join(out, "gpu_default.npz")), np.load(os.path.join(out, "gpu_%s.npz" % tag))
-    assert np.all(np.isfinite(a["ll_ext"])) and np.all(np.isfinite(b["ll_ext"]))
-    d = np.abs(a["ll_ext"] - b["ll_ext"]) / np.abs(a["ll_ext"])
-    assert d.max() <= 1e-13, d.tolist()
-    assert np.array_equal(a["sc_ext"], b["sc_ext"])
+    for family in cc.FAMILIES:
+        la, lb = a["ll_ext_" + family], b["ll_ext_" + family]
+        assert np.all(np.isfinite(la)) and np.all(np.isfinite(lb)), family
+        d = np.abs(la - lb) / np.abs(la)
+        assert d.max() <= 1e-13, (family, d.tolist())
+        assert np.array_equal(a["sc_ext_" + family], b["sc_ext_" + family]), family
 
 
 @pytest.mark.parametrize("tag", list(FORMS))
