@@ -760,6 +760,74 @@ int lh_eval_ancestral_candidates_batch_device(lh_family* fam, int32_t n, int32_t
  * the counters. */
 int lh_ancestral_candidates_profile_read(lh_family* fam, double* ms, int64_t* n_launches);
 
+/* ---- K14: exact codon marginals of a node of a seed's lineage ----
+ * The three bases of a node's codon are coupled through the naive codon, whose bases the HMM couples in the junctions, so
+ * K11's per-site tables do not give the node's codon.  Given the naive base of a site the node's base there is independent
+ * of everything else, so with K9's naive codon posterior Q (125 entries, 25 b1 + 5 b2 + b3 over A,C,G,T,N) and K13's G
+ *   T_t[c][x1 x2 x3] = sum_b Q_t[c][b1 b2 b3] G_t[j1][b1][x1] G_t[j2][b2][x2] G_t[j3][b3][x3]
+ * for codon c over the sites j1, j2, j3 = frame + 3 c .. of lh_family_set_codons' frame; the node triple is indexed
+ * 16 x1 + 4 x2 + x3 over A,C,G,T.  change folds the joint P(b, x) per codon:
+ *   [0] the naive triple has no N and x equals it        [1] no N, x != b, the same translation
+ *   [2] no N, a different translation                    [3] the naive triple holds an N
+ * (the standard code, the stop codons a symbol of their own); the four sum to 1.
+ *
+ * The evaluation with K14 behind it: lh_eval_ancestral_candidates_batch's inputs (node 0 = the seed's parent, 1 = the
+ * MRCA).  Needs lh_family_set_sampler and lh_family_set_codons, no candidates; the extended-range mode is honoured.  With
+ * C = n_codons of lh_codon_layout, every member may be NULL:
+ *   log_offset      [n]         (input) as in lh_posterior_outputs
+ *   loglik          [n]
+ *   codons          [n][C][64]  T
+ *   change          [n][C][4]
+ *   weighted_codons [C][64]     sum_i w_i T_i, w_i = exp(loglik_i - log_offset_i - max)
+ *   weighted_change [C][4]
+ *   weight_stats    [3]         max, sum w, sum w^2 as in lh_posterior_outputs
+ * A row with a non-finite log-likelihood, a rejected schedule or (device form) a bad path gets NaN in codons and change
+ * and no weight; the path is checked, the error word raised and the host-pointer form's device copies of codons and change
+ * bounded (4 GiB) as for lh_eval_ancestral_batch.  The sums run in sample order (K5's slab scheme); the same sample gives
+ * the same bits whatever the batch around it. */
+typedef struct lh_node_codons_outputs {
+  const double* log_offset;
+  double* loglik;
+  double* codons;
+  double* change;
+  double* weighted_codons;
+  double* weighted_change;
+  double* weight_stats;
+} lh_node_codons_outputs;
+
+int lh_eval_node_codons_batch(lh_family* fam, int32_t n, int32_t n_tips, int32_t max_depth, const int32_t* ops,
+                              const double* brlen, const double* er, const double* pi, const double* alpha,
+                              int32_t num_rates, const int32_t* path, int32_t path_len, int32_t node,
+                              const lh_node_codons_outputs* outs);
+
+/* Same with every array (the members of outs included) resident on the handle's device; enqueued on `hip_stream`
+ * without synchronising. */
+int lh_eval_node_codons_batch_device(lh_family* fam, int32_t n, int32_t n_tips, int32_t max_depth, const int32_t* ops,
+                                     const double* brlen, const double* er, const double* pi, const double* alpha,
+                                     int32_t num_rates, const int32_t* path, int32_t path_len, int32_t node,
+                                     const lh_node_codons_outputs* outs, void* hip_stream);
+
+/* The contraction alone behind one pruning pass: lh_asr_marginals_batch's trees and given rates[n][num_rates], with the
+ * caller's naive codon posteriors naive_codons[n][C][125] in place of naive_prob; codons[n][C][64] and change[n][C][4]
+ * (either may be NULL).  Needs lh_family_set_codons (for the frame). */
+int lh_asr_node_codons_batch(lh_family* fam, int32_t n, int32_t n_tips, int32_t max_depth, const int32_t* ops,
+                             const double* brlen, const double* er, const double* pi, const double* rates,
+                             int32_t num_rates, const double* naive_codons, const int32_t* path, int32_t path_len,
+                             int32_t node, double* codons, double* change);
+int lh_asr_node_codons_batch_device(lh_family* fam, int32_t n, int32_t n_tips, int32_t max_depth, const int32_t* ops,
+                                    const double* brlen, const double* er, const double* pi, const double* rates,
+                                    int32_t num_rates, const double* naive_codons, const int32_t* path, int32_t path_len,
+                                    int32_t node, double* codons, double* change, void* hip_stream);
+
+/* classes[125][64]: the class 0 .. 3 (the entries of change) of every (naive triple, node triple) pair, as the kernel's
+ * compile-time table has it. */
+int lh_node_codon_classes(uint8_t* classes);
+
+/* Times of K14 over the launches made while profiling was enabled (HIP events on the launch stream), ms[3]: K9 with the
+ * tables (rate weights, path check, K13b, rate combination, the naive codons of every codon), the contraction, the
+ * weighted reduction (lh_eval_node_codons_batch only); resets the counters. */
+int lh_node_codons_profile_read(lh_family* fam, double* ms, int64_t* n_launches);
+
 /* Timing of the kernels of the last lh_eval_batch_device call sequence, measured with HIP events
  * on the launch stream when enabled (ms per kernel family: model, prune, forward). */
 int lh_profile_enable(lh_family* fam, int enable);

@@ -95,6 +95,10 @@ ANCESTRAL_PROBS_EXPORTS = ["lh_family_set_ancestral_candidates", "lh_ancestral_c
                            "lh_ancestral_candidates_profile_read"]
 EXPORTS += ANCESTRAL_PROBS_EXPORTS
 NODE_PARENT, NODE_MRCA = 0, 1  # lh_eval_ancestral_candidates_batch's `node`
+# K14 (exact codon marginals of a node of a seed's lineage)
+NODE_CODONS_EXPORTS = ["lh_eval_node_codons_batch", "lh_eval_node_codons_batch_device", "lh_asr_node_codons_batch",
+                       "lh_asr_node_codons_batch_device", "lh_node_codon_classes", "lh_node_codons_profile_read"]
+EXPORTS += NODE_CODONS_EXPORTS
 
 
 class _CodonOutputs(C.Structure):
@@ -168,6 +172,17 @@ class _AncestralProbsOutputs(C.Structure):
 
 class _AncestralProbsOutputsDevice(C.Structure):  # the same members as device addresses
     _fields_ = [(k, C.c_void_p) for k in _ANCESTRAL_PROBS_MEMBERS]
+
+
+_NODE_CODONS_MEMBERS = ("log_offset", "loglik", "codons", "change", "weighted_codons", "weighted_change", "weight_stats")
+
+
+class _NodeCodonsOutputs(C.Structure):
+    _fields_ = [(k, c_f64p) for k in _NODE_CODONS_MEMBERS]
+
+
+class _NodeCodonsOutputsDevice(C.Structure):  # the same members as device addresses
+    _fields_ = [(k, C.c_void_p) for k in _NODE_CODONS_MEMBERS]
 
 
 class _SamplerJunction(C.Structure):
@@ -345,6 +360,16 @@ class HipLibrary:
             lib.lh_eval_ancestral_candidates_batch_device.argtypes = _DEV_TREE + [
                 C.c_void_p, C.c_int32, C.c_int32, C.POINTER(_AncestralProbsOutputsDevice), C.c_void_p]
             lib.lh_ancestral_candidates_profile_read.argtypes = _PROFILE_READ
+        if hasattr(lib, "lh_eval_node_codons_batch"):
+            lib.lh_eval_node_codons_batch.argtypes = _HOST_TREE + [c_i32p, C.c_int32, C.c_int32,
+                                                                   C.POINTER(_NodeCodonsOutputs)]
+            lib.lh_eval_node_codons_batch_device.argtypes = _DEV_TREE + [
+                C.c_void_p, C.c_int32, C.c_int32, C.POINTER(_NodeCodonsOutputsDevice), C.c_void_p]
+            lib.lh_asr_node_codons_batch.argtypes = _HOST_TREE + [c_f64p, c_i32p, C.c_int32, C.c_int32, c_f64p, c_f64p]
+            lib.lh_asr_node_codons_batch_device.argtypes = _DEV_TREE + [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32] + \
+                [C.c_void_p] * 3
+            lib.lh_node_codon_classes.argtypes = [c_u8p]
+            lib.lh_node_codons_profile_read.argtypes = _PROFILE_READ
         if hasattr(lib, "lh_set_device"):      # (absent from round-2 builds loaded through LH_LIB_DIR for comparisons)
             lib.lh_set_device.argtypes = [C.c_int32]
             lib.lh_family_status.argtypes = [C.c_void_p]
@@ -458,6 +483,45 @@ class HipLibrary:
     def ancestral_candidates_profile_read(self, family):
         """(tables ms, pair emissions and sweeps ms, reduction ms, launch groups) of K13 since the last read."""
         return self._profile_read("lh_ancestral_candidates_profile_read", family, 3)
+
+    def eval_node_codons_batch(self, family, n_tips, max_depth, ops, brlen, er, pi, alpha, num_rates, path, node,
+                               log_offset=None, want=("loglik", "codons", "change", "weighted_codons", "weighted_change",
+                                                      "weight_stats")):
+        """K0-K2 + K9 + K13's tables + K14 on a family handle after set_codons; path [n][P] (seed_path rows, -1 padding),
+        node NODE_PARENT or NODE_MRCA.  Returns a dict with the members of `want`: loglik [n], codons [n, C, 64] (the node's
+        triple 16 x1 + 4 x2 + x3 over A,C,G,T), change [n, C, 4] (identical, synonymous, replacement, naive triple with an
+        N), weighted_codons [C, 64], weighted_change [C, 4], weight_stats [3]."""
+        h = _handle(family)
+        n, arrays = _tree_args(ops, brlen, er, pi, alpha)
+        path = _i32(path)
+        assert path.ndim == 2 and path.shape[0] == n
+        nc = C.c_int32()
+        self.check(self.lib.lh_codon_layout(h, C.byref(nc), None, None, None))
+        nc = nc.value
+        res, outs = _outputs(_NodeCodonsOutputs, want, log_offset, loglik=(n,), codons=(n, nc, 64), change=(n, nc, 4),
+                             weighted_codons=(nc, 64), weighted_change=(nc, 4), weight_stats=(3,))
+        self.check(self.lib.lh_eval_node_codons_batch(h, n, n_tips, max_depth, *_tree_ptrs(arrays), num_rates,
+                                                      _ptr(path, c_i32p), path.shape[1], node, C.byref(outs)))
+        return res
+
+    def eval_node_codons_batch_device(self, family, n, n_tips, max_depth, ops_ptr, brlen_ptr, er_ptr, pi_ptr, alpha_ptr,
+                                      num_rates, path_ptr, path_len, node, outs, stream=0):
+        """lh_eval_node_codons_batch_device on device addresses; outs: dict of the output members' addresses."""
+        o = _NodeCodonsOutputsDevice(**{k: int(v) for k, v in outs.items() if v})
+        self.check(self.lib.lh_eval_node_codons_batch_device(
+            _handle(family), n, n_tips, max_depth, ops_ptr, brlen_ptr, er_ptr, pi_ptr, alpha_ptr, num_rates, path_ptr,
+            path_len, node, C.byref(o), stream))
+
+    def node_codons_profile_read(self, family):
+        """(K9 + tables ms, contraction ms, reduction ms, launch groups) of K14 since the last read."""
+        return self._profile_read("lh_node_codons_profile_read", family, 3)
+
+    def node_codon_classes(self):
+        """[125, 64] uint8: the class (0 identical, 1 synonymous, 2 replacement, 3 naive triple with an N) of every (naive
+        triple, node triple) pair as the device's compile-time table has it."""
+        out = np.zeros((125, 64), dtype=np.uint8)
+        self.check(self.lib.lh_node_codon_classes(out.ctypes.data_as(c_u8p)))
+        return out
 
     def eval_edges_batch(self, family, n_tips, max_depth, ops, brlen, er, pi, alpha, num_rates, path, seed_tip,
                          log_offset=None, want=("loglik", "chain_counts", "seed_edge", "naive_edge", "edge_load")):
@@ -1116,6 +1180,31 @@ class Family:
         """({k11a_ms, k11b_ms, reduce_ms}, launch groups) of K11 since the last read."""
         r = self.hip._profile_read("lh_ancestral_profile_read", self.handle, 3)
         return dict(zip(("k11a_ms", "k11b_ms", "reduce_ms"), r[:3])), r[3]
+
+    # ---- K14: exact codon marginals of a node of a lineage ----
+    def asr_node_codons_batch(self, n_tips, max_depth, ops, brlen, er, pi, rates, naive_codons, path, node,
+                              want=("codons", "change")):
+        """lh_asr_node_codons_batch: asr_marginals_batch's trees and rates, the caller's naive codon posteriors
+        naive_codons [n][C][125] (C = n_codons of set_codons' frame) and path [n][P]; returns (codons [n][C][64], change
+        [n][C][4]), None for what `want` leaves out."""
+        _, arrays = _tree_args(ops, brlen, er, pi, rates)
+        ops, brlen, er, pi, rates = arrays
+        naive_codons = _f64(naive_codons)
+        path = _i32(path)
+        n, nc = naive_codons.shape[:2]
+        assert naive_codons.shape == (n, nc, 125) and path.ndim == 2 and path.shape[0] == n
+        assert ops.shape == (n, n_tips - 2, 4) and brlen.shape == (n, 2 * n_tips - 2)
+        assert er.shape == (n, 6) and pi.shape == (n, 4) and rates.shape[0] == n
+        have = C.c_int32()
+        self.hip.check(self.hip.lib.lh_codon_layout(self.handle, C.byref(have), None, None, None))
+        if have.value != nc:
+            raise ValueError("lh_asr_node_codons_batch: naive_codons has %d codons, the handle's frame %d" % (nc, have.value))
+        codons = np.zeros((n, nc, 64)) if "codons" in want else None
+        change = np.zeros((n, nc, 4)) if "change" in want else None
+        self.hip.check(self.hip.lib.lh_asr_node_codons_batch(
+            self.handle, n, n_tips, max_depth, *_tree_ptrs(arrays), rates.shape[1], _ptr(naive_codons), _ptr(path, c_i32p),
+            path.shape[1], node, _ptr(codons), _ptr(change)))
+        return codons, change
 
     # ---- K12: exact substitution posteriors along the edges of a lineage ----
     def asr_edges_batch(self, n_tips, max_depth, ops, brlen, er, pi, rates, naive_prob, path, seed_tip,

@@ -2665,6 +2665,135 @@ void PhyloHMM::RunAncestralProbsPipeline(const std::string& input_path, const st
           << "\n";
 }
 
+// ---- K14: exact codon marginals of a node of a seed's lineage ----
+
+namespace {
+
+void CheckNodeAndFrame(const std::string& who, int node, int frame) {
+  Require(node == 0 || node == 1, who + ": node must be 0 (the seed's parent) or 1 (the MRCA)");
+  Require(frame >= 0 && frame <= 2, who + ": frame must be 0, 1 or 2");
+}
+
+PhyloHMM::NodeCodonsResult UnpackNodeCodons(int frame, std::size_t C, const double* codons, const double* change) {
+  PhyloHMM::NodeCodonsResult r;
+  r.frame = frame;
+  r.node = -1;
+  r.codons.resize(C);
+  r.change.resize(C);
+  for (std::size_t c = 0; c < C; ++c) {
+    std::copy(codons + c * 64, codons + (c + 1) * 64, r.codons[c].begin());
+    std::copy(change + c * 4, change + (c + 1) * 4, r.change[c].begin());
+  }
+  return r;
+}
+
+}  // namespace
+
+PhyloHMM::NodeCodonsResult PhyloHMM::NodeCodonMarginals(const std::string& seed_seq, int node, int frame) {
+  CheckNodeAndFrame("NodeCodonMarginals", node, frame);
+  SeedLineage s = OpenSeedLineage(seed_seq);
+  const CodonLayout lay = SetCodons(family_, frame);
+  const std::size_t C = (std::size_t)lay.n_codons;
+  std::vector<double> codons(C * 64), change(C * 4);
+  double ll = 0.0;
+  lh_node_codons_outputs outs{};
+  outs.loglik = &ll;
+  outs.codons = codons.data();
+  outs.change = change.data();
+  CheckHip(lh_eval_node_codons_batch(family_, 1, tree_.n_tips, s.depth, s.ops.data(), tree_.brlen.data(), er_.data(), pi_.data(),
+                                     &alpha_, num_rates_, s.nodes.data(), (int32_t)s.nodes.size(), node, &outs),
+           "lh_eval_node_codons_batch");
+  NodeCodonsResult r = UnpackNodeCodons(frame, C, codons.data(), change.data());
+  r.node = node == 0 ? s.nodes.front() : s.nodes.back();
+  r.loglik = ll;
+  return r;
+}
+
+void PhyloHMM::WriteNodeCodonTable(std::ostream& o, const NodeCodonsResult& m) {
+  static const char kBases[] = "ACGT";
+  o << "codon\tfirst_site\tbases\tprobability\n";
+  for (std::size_t c = 0; c < m.codons.size(); ++c)
+    for (int i = 0; i < 64; ++i)
+      if (m.codons[c][i] > 0.0)
+        o << c << '\t' << (m.frame + 3 * c) << '\t' << kBases[i / 16] << kBases[(i / 4) % 4] << kBases[i % 4] << '\t'
+          << Fmt17(m.codons[c][i]) << '\n';
+}
+
+void PhyloHMM::WriteNodeAminoAcidTable(std::ostream& o, const NodeCodonsResult& m) {
+  static const std::string aa_of = [] {
+    static const char kBases[] = "ACGT";
+    std::string dna;
+    for (int i = 0; i < 64; ++i) dna += {kBases[i / 16], kBases[(i / 4) % 4], kBases[i % 4]};
+    return TranslateDna(dna);
+  }();
+  o << "codon\taa\tprobability\n";
+  for (std::size_t c = 0; c < m.codons.size(); ++c) {
+    std::map<char, double> p;
+    for (int i = 0; i < 64; ++i)
+      if (m.codons[c][i] > 0.0) p[aa_of[i]] += m.codons[c][i];
+    for (const auto& kv : p) o << c << '\t' << kv.first << '\t' << Fmt17(kv.second) << '\n';
+  }
+}
+
+void PhyloHMM::WriteChangeTable(std::ostream& o, const NodeCodonsResult& m) {
+  o << "codon\tidentical\tsynonymous\treplacement\tundetermined\n";
+  for (std::size_t c = 0; c < m.change.size(); ++c) {
+    o << c;
+    for (int k = 0; k < 4; ++k) o << '\t' << Fmt17(m.change[c][k]);
+    o << '\n';
+  }
+}
+
+void PhyloHMM::RunNodeCodonsPipeline(const std::string& input_path, const std::string& seed_seq, int node,
+                                     const std::string& output_prefix, int num_rates, double burnin_frac, int frame) {
+  // what can be refused without a device is refused first: the node and the frame, then BeginPipeline's checks
+  CheckNodeAndFrame("the node-codons pipeline", node, frame);
+  const int seed_tip = BeginPipeline("node codons", "codon", burnin_frac, &seed_seq);
+  const CodonLayout lay = SetCodons(family_, frame);
+  TsvTable table = TsvTable::OpenRevBayesTable(input_path);
+  const std::size_t first = FirstUsedRow(table.rows.size(), burnin_frac);
+  const std::size_t C = (std::size_t)lay.n_codons, NC = C * 64, NH = C * 4;
+  // the rows' tables come back whole (68 C doubles each): a batch is bounded by at most 512 MiB of them
+  const std::size_t fit = std::max<std::size_t>(1, ((std::size_t)512 << 20) / (sizeof(double) * std::max<std::size_t>(NC + NH, 1)));
+  std::vector<double> codons, change;
+  std::vector<int32_t> path_len(table.rows.size() - first, 0);
+  const WeightedRows w = SumWeightedRows(
+      "node codons", table, input_path, first, PipelineBatch(fit), NC + NH, true,
+      [&](const TableBatch& tb, std::size_t off, double* ll) {
+        const DeviceBatch& b = tb.dev;
+        const SeedChains sc = SeedChainsOf(tb, off, seed_tip, seed_seq, path_len.data() + (off - first));
+        codons.resize((std::size_t)b.n * NC);
+        change.resize((std::size_t)b.n * NH);
+        lh_node_codons_outputs outs{};
+        outs.loglik = ll;
+        outs.codons = codons.data();
+        outs.change = change.data();
+        CheckHip(lh_eval_node_codons_batch(family_, b.n, b.n_tips, b.max_depth, b.ops.data(), b.brlen.data(), b.er.data(),
+                                           b.pi.data(), b.alpha.data(), num_rates, sc.path.data(), (int32_t)sc.P, node, &outs),
+                 "lh_eval_node_codons_batch");
+        return [&](std::size_t i, double* row) {
+          std::copy(codons.begin() + i * NC, codons.begin() + (i + 1) * NC, row);
+          std::copy(change.begin() + i * NH, change.begin() + (i + 1) * NH, row + NC);
+        };
+      });
+  const NodeCodonsResult res = UnpackNodeCodons(frame, C, w.acc.total.data(), w.acc.total.data() + NC);
+  std::ofstream cod(output_prefix + ".codons.tsv"), aa(output_prefix + ".aa.tsv"), chg(output_prefix + ".changes.tsv"),
+      rows(output_prefix + ".rows.tsv"), summary(output_prefix + ".summary.tsv");
+  Require(cod.good() && aa.good() && chg.good() && rows.good() && summary.good(), "Can't write " + output_prefix + ".*.tsv");
+  WriteNodeCodonTable(cod, res);
+  WriteNodeAminoAcidTable(aa, res);
+  WriteChangeTable(chg, res);
+  WriteSeedRows(rows, first, w, path_len);
+  WriteSummary(summary, w.used(), w.skipped, Fmt17(w.acc.KishEss()));
+  double syn = 0.0, repl = 0.0;
+  for (const auto& h : res.change) {
+    syn += h[1];
+    repl += h[2];
+  }
+  summary << "frame\t" << frame << "\nnode\t" << (node == 0 ? "parent" : "mrca") << "\nexpected_synonymous\t" << Fmt17(syn)
+          << "\nexpected_replacement\t" << Fmt17(repl) << "\n";
+}
+
 // Pass 1 draws every used row's naive sequence with the std::mt19937 words RunPipeline gives that row (row r: words
 // r * RawDrawsPerSample() on), on the device where the family has its sampler tables: K4's states become bytes and a
 // hash there (K6c), the host maps hashes to candidate ids in row order and the device checks every row's bytes against

@@ -272,6 +272,32 @@ class PhyloHMM : public HMM {
   void RunAncestralProbsPipeline(const std::string& input_path, const std::string& seed_seq, int node,
                                  const std::string& candidates_path, const std::string& output_prefix, int num_rates,
                                  double burnin_frac);
+  /// K14: exact codon marginals of a node of the lineage of the tip `seed_seq` (lh_eval_node_codons_batch): node 0 = the
+  /// seed's parent, 1 = the MRCA; codon c covers the sites frame + 3 c ...  A node triple is indexed 16 x1 + 4 x2 + x3 over
+  /// ACGT; change = the probabilities that the node's codon is identical to the naive one, a synonymous change of it, an
+  /// amino-acid replacement, or undetermined (the naive triple holds an N).
+  struct NodeCodonsResult {
+    int frame = 0;
+    int32_t node = 0;  // the node in lh_schedule_tree's numbering (-1: a weighted mean over trees)
+    double loglik = 0.0;
+    std::vector<std::array<double, 64>> codons;
+    std::vector<std::array<double, 4>> change;
+  };
+  /// After InitializePhyloParameters: the tables of the current tree.  The node and the frame are checked first.
+  NodeCodonsResult NodeCodonMarginals(const std::string& seed_seq, int node, int frame);
+  /// The importance-weighted tables over a RevBayes table, with RunAncestralMarginalsPipeline's reader, burn-in, weights,
+  /// Kish ESS and one-device rule.  What needs no device (the node, the frame, the burn-in, the seed) is refused before the
+  /// family is created.  The rows' tables are added up on the host in row order, so the files do not depend on
+  /// LH_PIPELINE_BATCH.  Writes <prefix>.codons.tsv (codon, first site, node triple, probability), .aa.tsv (codon, amino
+  /// acid, probability), .changes.tsv (codon, identical, synonymous, replacement, undetermined), .rows.tsv (row, weight,
+  /// chain_length) and .summary.tsv (with frame, node, expected_synonymous and expected_replacement, the column sums of
+  /// the changes table).
+  void RunNodeCodonsPipeline(const std::string& input_path, const std::string& seed_seq, int node,
+                             const std::string& output_prefix, int num_rates, double burnin_frac, int frame);
+  /// numbers printed with %.17g; entries of probability 0 are left out of the first two
+  static void WriteNodeCodonTable(std::ostream& o, const NodeCodonsResult& m);
+  static void WriteNodeAminoAcidTable(std::ostream& o, const NodeCodonsResult& m);
+  static void WriteChangeTable(std::ostream& o, const NodeCodonsResult& m);
   /// site, then one column per cell named <ancestor base><descendant base> (n_rows x 4 cells, rows over ACGTN), and with
   /// `with_sum` the off-diagonal sum of the first four rows; numbers printed with %.17g
   static void WritePairTable(std::ostream& o, const double* table, std::size_t n_sites, int n_rows, bool with_sum);

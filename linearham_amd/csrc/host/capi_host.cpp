@@ -374,6 +374,67 @@ int lhh_run_ancestral_probs_pipeline(void* h, const char* input_path, const char
   });
 }
 
+// The three tables of a NodeCodonsResult, separated by blank lines (WriteNodeCodonTable, WriteNodeAminoAcidTable,
+// WriteChangeTable)
+static const char* NodeCodonsText(const PhyloHMM::NodeCodonsResult& m) {
+  std::ostringstream o;
+  PhyloHMM::WriteNodeCodonTable(o, m);
+  o << "\n";
+  PhyloHMM::WriteNodeAminoAcidTable(o, m);
+  o << "\n";
+  PhyloHMM::WriteChangeTable(o, m);
+  g_out = o.str();
+  return g_out.c_str();
+}
+
+// PhyloHMM::NodeCodonMarginals: codons [cap_codons][64], change [cap_codons][4]; *n_codons receives the count, *text the
+// three tables as the writers print them.  codons == NULL: only *n_codons (after the node and frame checks), nothing is
+// evaluated.
+int lhh_phylo_node_codon_marginals(void* h, const char* seed_seq, int node, int frame, double* codons, double* change,
+                                   int cap_codons, int* n_codons, int* node_id, double* loglik, const char** text) {
+  return Guard([&] {
+    PhyloHMM& p = dynamic_cast<PhyloHMM&>(*static_cast<HMM*>(h));
+    if (node != 0 && node != 1) throw std::runtime_error("NodeCodonMarginals: node must be 0 (the seed's parent) or 1 (the MRCA)");
+    if (frame < 0 || frame > 2) throw std::runtime_error("NodeCodonMarginals: frame must be 0, 1 or 2");
+    const int L = (int)p.msa().cols();
+    *n_codons = L >= frame ? (L - frame) / 3 : 0;
+    if (!codons) return;
+    const PhyloHMM::NodeCodonsResult m = p.NodeCodonMarginals(seed_seq, node, frame);
+    if ((int)m.codons.size() > cap_codons) throw std::runtime_error("lhh_phylo_node_codon_marginals: output too small");
+    for (std::size_t c = 0; c < m.codons.size(); ++c) {
+      std::copy(m.codons[c].begin(), m.codons[c].end(), codons + c * 64);
+      if (change) std::copy(m.change[c].begin(), m.change[c].end(), change + c * 4);
+    }
+    if (node_id) *node_id = m.node;
+    if (loglik) *loglik = m.loglik;
+    if (text) *text = NodeCodonsText(m);
+  });
+}
+
+int lhh_run_node_codons_pipeline(void* h, const char* input_path, const char* seed_seq, int node, const char* output_prefix,
+                                 int num_rates, double burnin_frac, int frame) {
+  return Guard([&] {
+    dynamic_cast<PhyloHMM&>(*static_cast<HMM*>(h)).RunNodeCodonsPipeline(input_path, seed_seq, node, output_prefix, num_rates,
+                                                                       burnin_frac, frame);
+  });
+}
+
+// The writers' text of caller tables: codons [n_codons][64], change [n_codons][4]
+int lhh_write_node_codons(const double* codons, const double* change, int n_codons, int frame, const char** out) {
+  return Guard([&] {
+    if (n_codons < 0 || frame < 0 || frame > 2) throw std::runtime_error("lhh_write_node_codons: bad shape");
+    PhyloHMM::NodeCodonsResult m;
+    m.frame = frame;
+    m.codons.resize(n_codons);
+    m.change.resize(n_codons);
+    for (int c = 0; c < n_codons; ++c) {
+      std::copy(codons + c * 64, codons + (c + 1) * 64, m.codons[c].begin());
+      std::copy(change + c * 4, change + (c + 1) * 4, m.change[c].begin());
+    }
+    *out = NodeCodonsText(m);
+  });
+}
+
 // WriteAncestralProbsTable's text of K candidates: names and seqs joined by '\n'; *covered receives CoveredMass
 int lhh_write_ancestral_probs_table(const char* names, const char* seqs, const double* prob, int K, const char** out,
                                     double* covered) {

@@ -65,7 +65,7 @@ int main(int argc, char** argv) {
   try {
     if (argc < 2 || std::string(argv[1]) == "-h" || std::string(argv[1]) == "--help") {
       std::cout << "A Phylo-HMM implementation for B cell receptor sequence analysis.\n"
-                   "USAGE: linearham {--compute-logl|--sample|--pipeline|--asr|--marginals|--marginals-pipeline|--naive-probs|--naive-probs-pipeline|--lineage-pipeline|--weighted-lineage-pipeline|--viterbi|--annotations-pipeline|--codon-marginals|--codon-marginals-pipeline|--events|--events-pipeline|--ancestral-marginals|--ancestral-marginals-pipeline|--lineage-substitutions|--lineage-substitutions-pipeline|--ancestral-probs|--ancestral-probs-pipeline} --yaml-path <string> "
+                   "USAGE: linearham {--compute-logl|--sample|--pipeline|--asr|--marginals|--marginals-pipeline|--naive-probs|--naive-probs-pipeline|--lineage-pipeline|--weighted-lineage-pipeline|--viterbi|--annotations-pipeline|--codon-marginals|--codon-marginals-pipeline|--events|--events-pipeline|--ancestral-marginals|--ancestral-marginals-pipeline|--lineage-substitutions|--lineage-substitutions-pipeline|--ancestral-probs|--ancestral-probs-pipeline|--node-codons|--node-codons-pipeline} --yaml-path <string> "
                    "--cluster-ind <int> --hmm-param-dir <string> [--seed <int>] [--num-rates <int>] [--extended-range <0|1>] "
                    "[--devices <a,b,...>] ...\n"
                    "  --marginals: the arguments of --compute-logl; prints the per-site naive-base table and the gene table\n"
@@ -108,6 +108,13 @@ int main(int argc, char** argv) {
                    "  --ancestral-probs-pipeline --input-path <RevBayes table> --output-path <prefix> --seed-seq <name>\n"
                    "    --node <parent|mrca> --candidates <fasta> [--burnin-frac <f>]: writes <prefix>.probs.tsv, <prefix>.rows.tsv\n"
                    "    and <prefix>.summary.tsv (one device)\n"
+                   "  --node-codons --seed-seq <name> --node <parent|mrca> [--frame <0|1|2>]: the arguments of --marginals; prints\n"
+                   "    the exact codon table of the parent of the sequence <name> or of its MRCA with naive for that tree, its\n"
+                   "    amino-acid table, and per codon the probabilities that it is identical to the naive codon, a synonymous\n"
+                   "    change of it, a replacement, or undetermined (the naive codon holds an N)\n"
+                   "  --node-codons-pipeline --input-path <RevBayes table> --output-path <prefix> --seed-seq <name>\n"
+                   "    --node <parent|mrca> [--frame <0|1|2>] [--burnin-frac <f>]: writes <prefix>.codons.tsv, <prefix>.aa.tsv,\n"
+                   "    <prefix>.changes.tsv, <prefix>.rows.tsv and <prefix>.summary.tsv (one device)\n"
                    "  --lineage-pipeline --input-path <--pipeline table> --output-path <prefix> --seed-seq <name> [--seed <int>]:\n"
                    "    the lineage tables of the sequence <name>: <prefix>.fasta, .dnamap, .nodes.tsv, .edges.tsv, .summary.tsv\n"
                    "       linearham --lineage-trees --input-path <--asr trees> --output-path <prefix> --seed-seq <name>\n"
@@ -138,7 +145,8 @@ int main(int argc, char** argv) {
         subcmd != "--codon-marginals-pipeline" && subcmd != "--events" && subcmd != "--events-pipeline" &&
         subcmd != "--ancestral-marginals" && subcmd != "--ancestral-marginals-pipeline" &&
         subcmd != "--lineage-substitutions" && subcmd != "--lineage-substitutions-pipeline" &&
-        subcmd != "--ancestral-probs" && subcmd != "--ancestral-probs-pipeline")
+        subcmd != "--ancestral-probs" && subcmd != "--ancestral-probs-pipeline" && subcmd != "--node-codons" &&
+        subcmd != "--node-codons-pipeline")
       throw std::invalid_argument("'" + subcmd + "' is not a valid subcommand.");
     const std::string yaml_path = a.one("yaml-path");
     const int cluster_ind = std::stoi(a.one("cluster-ind"));
@@ -160,7 +168,7 @@ int main(int argc, char** argv) {
                                      subcmd == "--weighted-lineage-pipeline" || subcmd == "--annotations-pipeline" ||
                                      subcmd == "--codon-marginals-pipeline" || subcmd == "--events-pipeline" ||
                                      subcmd == "--ancestral-marginals-pipeline" || subcmd == "--lineage-substitutions-pipeline" ||
-                                     subcmd == "--ancestral-probs-pipeline"))
+                                     subcmd == "--ancestral-probs-pipeline" || subcmd == "--node-codons-pipeline"))
         throw std::invalid_argument(subcmd + " runs on one device: --devices may list only one");
       if (device_list.size() > 1 && subcmd != "--pipeline")
         std::fprintf(stderr, "linearham: %s evaluates on one device; of --devices only device %d is used\n", subcmd.c_str(),
@@ -226,6 +234,12 @@ int main(int argc, char** argv) {
                                                std::stod(a.opt("burnin-frac", "0")));
       return EXIT_SUCCESS;
     }
+    if (subcmd == "--node-codons-pipeline") {
+      phylo_hmm_ptr->RunNodeCodonsPipeline(a.one("input-path"), a.one("seed-seq"), linearham::ParseLineageNode(a.one("node")),
+                                           a.one("output-path"), num_rates, std::stod(a.opt("burnin-frac", "0")),
+                                           std::stoi(a.opt("frame", "0")));
+      return EXIT_SUCCESS;
+    }
     if (subcmd == "--naive-probs-pipeline") {
       phylo_hmm_ptr->RunNaiveProbsPipeline(a.one("input-path"), a.one("output-path"), num_rates,
                                            std::stod(a.opt("burnin-frac", "0")), a.opt("candidates-path", ""),
@@ -260,6 +274,13 @@ int main(int argc, char** argv) {
       linearham::NamedCandidates c = linearham::ReadNamedCandidateFile(a.one("candidates"), (int)phylo_hmm_ptr->msa().cols());
       probs.names = std::move(c.names);
       probs.seqs = std::move(c.seqs);
+    }
+    // --node-codons: the node and the frame are refused before anything is evaluated
+    int codons_node = 0, codons_frame = 0;
+    if (subcmd == "--node-codons") {
+      codons_node = linearham::ParseLineageNode(a.one("node"));
+      codons_frame = std::stoi(a.opt("frame", "0"));
+      if (codons_frame < 0 || codons_frame > 2) throw std::invalid_argument("--frame must be 0, 1 or 2");
     }
     phylo_hmm_ptr->InitializePhyloParameters(a.one("newick-path"), a.multi("er"), a.multi("pi"),
                                              std::stod(a.opt("alpha", "1.0")), num_rates);
@@ -306,6 +327,13 @@ int main(int argc, char** argv) {
       for (double x : phylo_hmm_ptr->AncestralCandidatePosterior(a.one("seed-seq"), probs_node, probs.seqs).log_cand)
         probs.prob.push_back(std::exp(x));
       linearham::WriteAncestralProbsTable(std::cout, probs);
+    } else if (subcmd == "--node-codons") {
+      const linearham::PhyloHMM::NodeCodonsResult m = phylo_hmm_ptr->NodeCodonMarginals(a.one("seed-seq"), codons_node, codons_frame);
+      linearham::PhyloHMM::WriteNodeCodonTable(std::cout, m);
+      std::cout << "\n";
+      linearham::PhyloHMM::WriteNodeAminoAcidTable(std::cout, m);
+      std::cout << "\n";
+      linearham::PhyloHMM::WriteChangeTable(std::cout, m);
     } else if (subcmd == "--lineage-substitutions") {
       const linearham::PhyloHMM::LineageSubstitutionsResult m = phylo_hmm_ptr->LineageSubstitutions(a.one("seed-seq"));
       const std::size_t L = (std::size_t)m.n_sites, P = m.nodes.size();

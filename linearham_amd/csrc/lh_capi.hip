@@ -253,6 +253,16 @@ struct AncProbsWs {  // K13 (lh_ancestral_probs.hip)
   DevBuf out_cond, out_log_cand, out_wsum;  // the host-pointer form's device copies
 };
 
+struct NodeCodonsWs {  // K14 (lh_node_codon.hip)
+  bool have = false;  // the tables are built: by the first call after lh_family_set_codons
+  lh::NodeCodonTables tab{};
+  DevBuf codon_src, germ, codes;
+  DevBuf windows, genes, naive;  // a launch group's K9 outputs and the naive codon posteriors of every codon
+  DevBuf zero;                   // the given-rates form: the all-zero naive_prob K11r is handed (its output is not read)
+  DevBuf codons, change, partial_c, partial_h;  // the batch's rows where the caller does not take them; the reduction's slabs
+  DevBuf out_codons, out_change, out_wcodons, out_wchange;  // the host-pointer form's device copies
+};
+
 struct PosteriorWs {  // K5's arrays that the caller of lh_eval_posterior_batch_device does not hand in
   DevBuf loglik, weights, stats, partial;
 };
@@ -294,6 +304,11 @@ struct CodonWs : TableWs {
   lh::CodonTables tab{};
   DevBuf win, codes;  // the tables
   DevBuf scratch;
+  // what K14's tables are built from (host): the chain position of every site, the positions of the D and the J genes, and
+  // per region (V, D, J) the base every gene writes on every site (N where it writes none)
+  std::vector<int32_t> site_pos;
+  int32_t q_d = 0, q_j = 0;
+  std::vector<uint8_t> gene_base[3];
 };
 
 // K10 (lh_events.hip)
@@ -431,6 +446,7 @@ struct lh_family {
   AncestralWs anc;
   EdgesWs edges;
   AncProbsWs probs;
+  NodeCodonsWs node_codons;
   // forward arrays that stay on the device, shared by K4 and K5 in both their forms: K4 draws from them, K5 overwrites
   // them with the posteriors (calls on a handle do not overlap: they also share the workspace)
   DevBuf forward_dev;
@@ -452,6 +468,9 @@ struct lh_family {
   KernelTimer<3> edges_timer;               // K12: K11a, K12b (with K11r, K11c, K12c, K12m), the weighted reduction
   KernelTimer<3> probs_timer;               // K13's skeleton: K11a, K13b + K13e with their sweeps, the weighted reduction
   KernelTimer<2> probs_stage_timer;         // inside its second stage: the tables (K11r, K11c, K13b, K13m), the pairs (K13e, K2)
+  KernelTimer<3> node_codons_timer;         // K14's skeleton: K11a, the tables + the contraction, the weighted reduction
+  KernelTimer<2> node_codons_stage_timer;   // inside its second stage: the tables (K13's, the naive codons), the contraction
+  KernelTimer<1> node_codons_k9_timer;      // K9, in front of K5
   KernelTimer<5> chain_timer;               // lh_eval_lineage_batch: K0, K1, K2 + K4 + K6c, K3, K7
   bool extended = false;  // lh_family_set_extended_range
   bool have_sampler = false;
@@ -2278,6 +2297,9 @@ struct LineageCall {
   const double* log_offset = nullptr;  // the eval forms' (lh_posterior_outputs' members)
   double *loglik = nullptr, *weight_stats = nullptr;
   double* em_out = nullptr;  // the eval forms': a launch group's emissions in caller columns, [chunk][n_xmsa] (null: not formed)
+  // the eval forms': called per launch group with (samples, first sample, the group's forward arrays, its log-likelihoods,
+  // stream) before K5 overwrites the forward arrays (K14 runs K9 there); empty: nothing is called
+  std::function<int(int, size_t, const double*, const double*, hipStream_t)> before_smoothing;
   bool asked() const {
     return loglik || weight_stats || std::any_of(rows.begin(), rows.end(), [](const RowOut& r) { return r.p || r.sum; });
   }
@@ -2357,6 +2379,7 @@ int lineage_eval_device(lh_family* f, const std::string& W, const TreeBatch& b, 
     int planes = 0;
     if (prune_group(f, W, g, rates, false, stream, &planes)) return 1;
     if (run_forward(f, m, planes, site_lik, site_scal, g.pi, nullptr, c.em_out, ll + off, &fwd_outs, off, stream)) return 1;
+    if (c.before_smoothing && c.before_smoothing(m, off, fwd + (size_t)off * FS, ll + off, stream)) return 1;
     lh::launch_posterior(f->sampler_dev, m, fwd + (size_t)off * FS, FS, ll + off, stream);
     if (f->profile && t.begin(stream)) return 1;
     lh::launch_site_base(m, (int)L, FS, a.sb_off.get<const int32_t>(), a.sb_idx.get<const int32_t>(), fwd + (size_t)off * FS,
@@ -2667,6 +2690,177 @@ int eval_probs_device(lh_family* f, const std::string& W, const TreeBatch& b, Li
                              probs_launch(f, c, node, pairs, sweeps));
 }
 
+// ---- K14: exact codon marginals of a node of a seed's lineage (lh_node_codon.hip) ----
+
+// K14's per-row outputs.  Row 0 is what the skeletons lead with: the eval form's site_base (K11r reads it; nobody takes it), the
+// given-rates form's input, the caller's naive codon posteriors.
+enum { kNodeCodons = 1, kNodeChange };
+std::vector<RowOut> node_codons_rows(lh_family* f, bool given, const lh_node_codons_outputs& o) {
+  AncestralWs& a = f->anc;
+  NodeCodonsWs& k = f->node_codons;
+  const size_t L = f->host.n_sites, C = f->codon.n_codons;
+  return {{nullptr, given ? C * 125 : L * 5, nullptr, &a.site_base},
+          {o.codons, C * 64, &k.out_codons, &k.codons, false, o.weighted_codons, &k.partial_c, &k.out_wcodons},
+          {o.change, C * 4, &k.out_change, &k.change, false, o.weighted_change, &k.partial_h, &k.out_wchange}};
+}
+
+int node_codons_check(const lh_family* f, const std::string& W, const TreeBatch& b, int P, int node) {
+  if (ancestral_check(f, W, b, P)) return 1;
+  if (node != 0 && node != 1) return fail(W + ": node must be 0 (the seed's parent) or 1 (the MRCA)");
+  if (f->codon.frame < 0) return fail(W + ": lh_family_set_codons has not been called");
+  return 0;
+}
+
+// The tables that give every codon its naive posterior (lh::NodeCodonTables), from what lh_family_set_codons kept: for a
+// codon inside one germline region, the triple every gene of the region writes there.
+int node_codons_tables(lh_family* f, const std::string& W) {
+  NodeCodonsWs& k = f->node_codons;
+  if (k.have) return 0;
+  const CodonWs& cw = f->codon;
+  const lh::DevFamily& h = f->host;
+  const int L = h.n_sites, C = cw.n_codons, frame = cw.frame;
+  const int nV = h.vgerm.n_genes, nD = h.has_d ? h.dgerm.n_genes : 0, nJ = h.jgerm.n_genes;
+  std::vector<int32_t> codon_src(std::max(C, 1), 0);
+  std::vector<int4> germ;
+  std::vector<uint8_t> codes;
+  for (size_t i = 0; i < cw.window_codon.size(); ++i) codon_src[cw.window_codon[i]] = (int32_t)i + 1;  // (0: not a window)
+  int32_t n_germ = 0;
+  for (int c = 0; c < C; ++c) {
+    if (codon_src[c] > 0) {
+      codon_src[c] -= 1;
+      continue;
+    }
+    const int s0 = frame + 3 * c, q = cw.site_pos[s0];
+    if (cw.site_pos[s0 + 1] != q || cw.site_pos[s0 + 2] != q || (q != 0 && q != cw.q_j && !(h.has_d && q == cw.q_d)))
+      return fail(W + ": internal error (germline codon)");
+    const int region = q == 0 ? 0 : q == cw.q_j ? 2 : 1;
+    const int ng = region == 0 ? nV : region == 1 ? nD : nJ, g0 = region == 0 ? 0 : region == 1 ? nV : nV + nD;
+    const std::vector<uint8_t>& gb = cw.gene_base[region];
+    germ.push_back(make_int4((int)codes.size(), g0, ng, 0));
+    for (int g = 0; g < ng; ++g) {
+      const uint8_t* b = gb.data() + (size_t)g * L + s0;
+      codes.push_back((uint8_t)(25 * b[0] + 5 * b[1] + b[2]));
+    }
+    codon_src[c] = -1 - n_germ++;
+  }
+  auto put = [&](DevBuf& b, const void* v, size_t bytes) {
+    if (b.ensure(bytes)) return 1;
+    if (bytes) LH_HIP(hipMemcpy(b.get(), v, bytes, hipMemcpyHostToDevice));
+    return 0;
+  };
+  LH_HIP(hipDeviceSynchronize());  // queued work may still read the old tables
+  if (put(k.codon_src, codon_src.data(), sizeof(int32_t) * codon_src.size()) || put(k.germ, germ.data(), sizeof(int4) * germ.size()) ||
+      put(k.codes, codes.data(), codes.size()))
+    return 1;
+  k.tab = {C, cw.tab.n_window, cw.tab.n_genes, k.codon_src.get<const int32_t>(), k.germ.get<const int4>(),
+           k.codes.get<const uint8_t>()};
+  k.have = true;
+  return 0;
+}
+
+// bytes per sample of K14's own arrays in a launch group: K9's outputs, the naive codon posteriors, K13m's table
+size_t node_codons_bytes(const lh_family* f) {
+  const CodonWs& cw = f->codon;
+  return sizeof(double) * ((size_t)cw.tab.n_window * 125 + cw.tab.n_genes + (size_t)cw.n_codons * 125);
+}
+
+// samples per launch group of K14, by memory as probs_group
+size_t node_codons_group(const lh_family* f, int T, int R, int P) {
+  const lh::AncWsBytes z = lh::anc_ws_bytes(T, f->host.n_sites, R, f->host.n_prune, P);
+  const lh::CondWsBytes y = lh::cond_ws_bytes(R, f->host.n_prune);
+  const size_t per = z.total() - z.part + y.part + y.table + node_codons_bytes(f) + lh::asr_desc_bytes(T) +
+                     eval_bytes_per_sample(f, T, R);
+  return std::max<size_t>(1, std::min<size_t>({(size_t)kChunk, (size_t)8192, ((size_t)8 << 30) / per}));
+}
+
+// K13's scratch (probs_workspace without the sweeps) and K14's group arrays
+int node_codons_workspace(lh_family* f, int chunk, int T, int R, int P, bool given, lh::AncWs* ws) {
+  NodeCodonsWs& k = f->node_codons;
+  const CodonWs& cw = f->codon;
+  const size_t m = chunk;
+  if (probs_workspace(f, chunk, T, R, P, 0, false, ws)) return 1;
+  if (given) return k.zero.ensure(sizeof(double) * 5 * (size_t)f->host.n_sites * m);
+  return k.windows.ensure(sizeof(double) * 125 * (size_t)cw.tab.n_window * m) ||
+         k.genes.ensure(sizeof(double) * (size_t)cw.tab.n_genes * m) || k.naive.ensure(sizeof(double) * 125 * (size_t)cw.n_codons * m) ||
+         f->codon.scratch.ensure(sizeof(double) * 4 * (size_t)cw.tab.max_vec * lh::codon_slots(chunk));
+}
+
+// K13b + K13m on a launch group, the naive codon posteriors of every codon (eval form: from K9's outputs, which
+// before_smoothing left in the handle's arrays; given-rates form: the caller's, handed in as the skeleton's naive_prob) and
+// the contraction.  *group_ll: the group's log-likelihoods (eval form), null otherwise.
+auto node_codons_launch(lh_family* f, const LineageCall& c, int node, bool given, const double* const* group_ll) {
+  return [f, &c, node, given, group_ll](const TreeBatch& g, size_t off, const double* rates, const double* naive_prob,
+                                        const lh::AncWs& ws, hipStream_t stream) -> int {
+    Workspace& w = f->ws;
+    AncProbsWs& p = f->probs;
+    NodeCodonsWs& k = f->node_codons;
+    KernelTimer<2>& t = f->node_codons_stage_timer;
+    const double* site_base = naive_prob;
+    const double* Q = k.naive.get<const double>();
+    if (given) {
+      Q = naive_prob;
+      LH_HIP(hipMemsetAsync(k.zero.get(), 0, sizeof(double) * 5 * (size_t)f->host.n_sites * g.n, stream));
+      site_base = k.zero.get<const double>();
+    }
+    if (f->profile && t.begin(stream)) return 1;
+    if (lh::launch_ancestral_cond(f->host, g.n, g.R, g.T, g.ops, g.brlen, rates, w.eig.get<double>(), g.pi,
+                                  w.site_lik.get<double>(), w.site_scal.get<int32_t>(), site_base, c.path + off * c.P, c.P, node,
+                                  ws, p.table.get<double>(), nullptr, w.prune.hdr, f->err_flag, stream))
+      return 1;
+    if (!given)
+      lh::launch_naive_codons(k.tab, g.n, k.windows.get<const double>(), k.genes.get<const double>(), k.naive.get<double>(), stream);
+    if (f->profile && t.mark(1, stream)) return 1;
+    lh::launch_node_codons(f->host, g.n, f->codon.n_codons, f->codon.frame, p.table.get<const double>(), Q, ws.plen,
+                           group_ll ? *group_ll : nullptr, c.rows[kNodeCodons].group(off), c.rows[kNodeChange].group(off), stream);
+    if (f->profile && t.end(stream)) return 1;
+    return 0;
+  };
+}
+
+int eval_node_codons_device(lh_family* f, const std::string& W, const TreeBatch& b, LineageCall& c, int node, void* hip_stream) {
+  if (ancestral_table(f, W) || node_codons_tables(f, W)) return 1;
+  const int chunk = (int)std::min<size_t>(b.n, std::min(node_codons_group(f, b.T, b.R, c.P), eval_group(f, b.T, b.R)));
+  lh::AncWs ws;
+  if (ensure_workspace(f, chunk, b.R, b.T) || node_codons_workspace(f, chunk, b.T, b.R, c.P, false, &ws)) return 1;
+  const double* group_ll = nullptr;
+  // K9 reads the forward arrays before K5 smooths them in place
+  c.before_smoothing = [f, &group_ll](int m, size_t, const double* fwd, const double* ll, hipStream_t stream) -> int {
+    NodeCodonsWs& k = f->node_codons;
+    KernelTimer<1>& t = f->node_codons_k9_timer;
+    group_ll = ll;
+    if (f->profile && t.begin(stream)) return 1;
+    lh::launch_codons(f->sampler_dev, f->codon.tab, m, fwd, f->host.forward_size, ll, f->codon.scratch.get<double>(),
+                      k.windows.get<double>(), k.genes.get<double>(), stream);
+    if (f->profile && t.end(stream)) return 1;
+    return 0;
+  };
+  // K11c checks the paths wherever a table is formed
+  const bool tables = c.rows[kNodeCodons].wanted() || c.rows[kNodeChange].wanted();
+  const int rc = lineage_eval_device(f, W, b, c, chunk, ws, &lh_family::node_codons_timer, tables, -1, -1, hip_stream,
+                                     node_codons_launch(f, c, node, false, &group_ll));
+  c.before_smoothing = nullptr;
+  return rc;
+}
+
+int asr_node_codons_device(lh_family* f, const std::string& W, const TreeBatch& b, const LineageCall& c, int node, void* hip_stream) {
+  const int chunk = (int)std::min<size_t>(b.n, node_codons_group(f, b.T, b.R, c.P));
+  lh::AncWs ws;
+  if (ensure_workspace(f, chunk, b.R, b.T) || node_codons_workspace(f, chunk, b.T, b.R, c.P, true, &ws)) return 1;
+  return lineage_asr_device(f, W, b, c, chunk, ws, &lh_family::node_codons_timer, hip_stream,
+                            node_codons_launch(f, c, node, true, nullptr));
+}
+
+LineageCall node_codons_call(lh_family* f, int P, const int32_t* path, const lh_node_codons_outputs* outs) {
+  const lh_node_codons_outputs o = outs ? *outs : lh_node_codons_outputs{};
+  return {nullptr, path, P, 0, node_codons_rows(f, false, o), o.log_offset, o.loglik, o.weight_stats};
+}
+LineageCall node_codons_call(lh_family* f, int P, const double* naive_codons, const int32_t* path, double* codons, double* change) {
+  lh_node_codons_outputs o{};
+  o.codons = codons;
+  o.change = change;
+  return {naive_codons, path, P, 0, node_codons_rows(f, true, o)};
+}
+
 }  // namespace
 
 extern "C" {
@@ -2862,6 +3056,90 @@ int lh_ancestral_candidates_profile_read(lh_family* f, double* ms, int64_t* n_la
     return 1;
   if (ms) {
     ms[0] = stage[0];
+    ms[1] = stage[1];
+    ms[2] = skeleton[2];
+  }
+  return 0;
+}
+
+int lh_eval_node_codons_batch_device(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops,
+                                     const double* brlen, const double* er, const double* pi, const double* alpha, int32_t R,
+                                     const int32_t* path, int32_t P, int32_t node, const lh_node_codons_outputs* outs,
+                                     void* hip_stream) {
+  const TreeBatch b{n, T, max_depth, ops, brlen, er, pi, alpha, R};
+  const std::string W = "lh_eval_node_codons_batch";
+  if (int rc = check_batch(f, W, b, true)) return rc > 0;
+  if (node_codons_check(f, W, b, P, node)) return 1;
+  DeviceGuard guard(f);
+  if (!b.has_arrays() || !path) return fail(W + ": null array");
+  LineageCall c = node_codons_call(f, P, path, outs);
+  return eval_node_codons_device(f, W, b, c, node, hip_stream);
+}
+
+int lh_eval_node_codons_batch(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops, const double* brlen,
+                              const double* er, const double* pi, const double* alpha, int32_t R, const int32_t* path, int32_t P,
+                              int32_t node, const lh_node_codons_outputs* outs) {
+  const TreeBatch host{n, T, max_depth, ops, brlen, er, pi, alpha, R};
+  const std::string W = "lh_eval_node_codons_batch";
+  if (int rc = check_batch(f, W, host, true)) return rc > 0;
+  if (node_codons_check(f, W, host, P, node)) return 1;
+  DeviceGuard guard(f);
+  if (!host.has_arrays() || !path) return fail(W + ": null array");
+  const LineageCall c = node_codons_call(f, P, path, outs);
+  if (!c.asked()) return 0;
+  if (refuse_oversize(W, n, c, lh::debug_options().anc_out_mb)) return 1;  // (K11's rule)
+  return lineage_batch(f, W, host, c, n,
+                       [&](const TreeBatch& dev, LineageCall d) { return eval_node_codons_device(f, W, dev, d, node, nullptr); });
+}
+
+int lh_asr_node_codons_batch_device(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops,
+                                    const double* brlen, const double* er, const double* pi, const double* rates, int32_t R,
+                                    const double* naive_codons, const int32_t* path, int32_t P, int32_t node, double* codons,
+                                    double* change, void* hip_stream) {
+  const TreeBatch b{n, T, max_depth, ops, brlen, er, pi, rates, R, true};
+  const std::string W = "lh_asr_node_codons_batch";
+  if (int rc = check_batch(f, W, b)) return rc > 0;
+  if (node_codons_check(f, W, b, P, node)) return 1;
+  DeviceGuard guard(f);
+  if (!b.has_arrays() || !naive_codons || !path) return fail(W + ": null array");
+  const LineageCall c = node_codons_call(f, P, naive_codons, path, codons, change);
+  if (!c.asked()) return 0;  // nothing asked for
+  return asr_node_codons_device(f, W, b, c, node, hip_stream);
+}
+
+int lh_asr_node_codons_batch(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops, const double* brlen,
+                             const double* er, const double* pi, const double* rates, int32_t R, const double* naive_codons,
+                             const int32_t* path, int32_t P, int32_t node, double* codons, double* change) {
+  const TreeBatch host{n, T, max_depth, ops, brlen, er, pi, rates, R, true};
+  const std::string W = "lh_asr_node_codons_batch";
+  if (int rc = check_batch(f, W, host)) return rc > 0;
+  if (node_codons_check(f, W, host, P, node)) return 1;
+  DeviceGuard guard(f);
+  if (!host.has_arrays() || !naive_codons || !path) return fail(W + ": null array");
+  const LineageCall c = node_codons_call(f, P, naive_codons, path, codons, change);
+  if (!c.asked()) return 0;
+  // no refusal here: sub-batches bound the device copies of the inputs and outputs (as lh_asr_marginals_batch)
+  const size_t per = c.copy_bytes(true) + c.rows[kSiteBase].bytes(1);
+  const size_t sub = std::max<size_t>(1, std::min<size_t>(n, ((size_t)1 << 30) / std::max<size_t>(per, 1)));
+  return lineage_batch(f, W, host, c, sub, [&](const TreeBatch& dev, const LineageCall& d) {
+    return asr_node_codons_device(f, W, dev, d, node, nullptr);
+  });
+}
+
+int lh_node_codon_classes(uint8_t* classes) {
+  if (!classes) return fail("lh_node_codon_classes: null array");
+  lh::node_codon_classes(classes);
+  return 0;
+}
+
+int lh_node_codons_profile_read(lh_family* f, double* ms, int64_t* n_launches) {
+  double skeleton[3] = {}, stage[2] = {}, k9 = 0.0;
+  if (profile_read(f, &lh_family::node_codons_timer, skeleton, n_launches) ||
+      profile_read(f, &lh_family::node_codons_stage_timer, stage, nullptr) ||
+      profile_read(f, &lh_family::node_codons_k9_timer, &k9, nullptr))
+    return 1;
+  if (ms) {
+    ms[0] = k9 + stage[0];
     ms[1] = stage[1];
     ms[2] = skeleton[2];
   }
@@ -4087,6 +4365,13 @@ int lh_family_set_codons(lh_family* f, int32_t frame) {
   cw.tab.codes = cw.codes.get<const uint8_t>();
   cw.n_codons = n_codons;
   cw.window_codon = window_codon;
+  cw.site_pos = pos;
+  cw.q_d = q_d;
+  cw.q_j = q_j;
+  cw.gene_base[0] = gb_v;
+  cw.gene_base[1] = gb_d;
+  cw.gene_base[2] = gb_j;
+  f->node_codons.have = false;  // K14 builds its tables again
   cw.frame = frame;
   return 0;
 }

@@ -542,6 +542,29 @@ void launch_pair_emissions(const DevFamily& fam, int K, long long q0, int count,
 void launch_pair_finish(int K, long long q0, int count, const double* pair_ll, const double* open_ll, const int32_t* plen,
                         double* log_cand, double* prob, hipStream_t stream);
 
+// K14 (lh_node_codon.hip): exact codon marginals of a node of a seed's lineage, from K9's naive codon posteriors and K13b's
+// tables.  NodeCodonTables says where every codon's naive posterior comes from: codon_src[c] >= 0 is its window in K9's
+// output; -1 - k makes it germline codon k, a codon inside one germline region: germ[k] = (offset of its codes, the region's
+// first gene in K9's genes, the region's gene count, 0) and codes[offset + g] the triple 25 b1 + 5 b2 + b3 gene g of the
+// region writes on the codon's sites (N where it writes none).  Entry e of the codon is the sum of the posteriors of the
+// genes whose code is e, in ascending gene order.
+struct NodeCodonTables {
+  int32_t n_codons, n_window, n_genes;
+  const int32_t* codon_src;  // [n_codons]
+  const int4* germ;          // [germline codons]
+  const uint8_t* codes;
+};
+// Q[n][n_codons][125] from K9's windows[n][n_window][125] and genes[n][n_genes]
+void launch_naive_codons(const NodeCodonTables& t, int n, const double* windows, const double* genes, double* Q,
+                         hipStream_t stream);
+// codons[n][n_codons][64] and change[n][n_codons][4] (either may be null) from Q and K13m's table[n][n_prune + 1][5][4];
+// codon c covers the sites frame + 3 c ..; NaN for a row whose plen is 0 or whose loglik (null: not looked at) is not finite
+void launch_node_codons(const DevFamily& fam, int n, int n_codons, int frame, const double* table, const double* Q,
+                        const int32_t* plen, const double* loglik, double* codons, double* change, hipStream_t stream);
+// out[125][64]: the class (0 identical, 1 synonymous, 2 replacement, 3 the naive triple holds an N) of every (naive
+// triple, node triple) pair, from the kernel's compile-time relation
+void node_codon_classes(uint8_t* out);
+
 // K2a + K2b.  site_lik != null: emissions are assembled from K1's output (rate mix and naive
 // correction; optionally written to em_out[n][C]); site_lik == null: emissions are taken from
 // em_in[n][C].  K2a leaves the germline/padding emission products in gem[n][gem_size], their scaler

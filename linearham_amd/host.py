@@ -119,6 +119,56 @@ def read_ancestral_probs(prefix):
                 summary=_parse_summary(open(prefix + ".summary.tsv").read()))
 
 
+def parse_node_codons(text):
+    """dict(codons [n_codons][64], aa [per codon {amino acid: p}], change [n_codons][4]) from the three tables
+    WriteNodeCodonTable, WriteNodeAminoAcidTable and WriteChangeTable print, separated by blank lines.  The changes table has
+    a line per codon, so it gives the count."""
+    import numpy as np
+    cod, aa, chg = text.strip("\n").split("\n\n")
+    lines = [ln.split("\t") for ln in chg.strip("\n").split("\n")]
+    assert lines[0] == ["codon", "identical", "synonymous", "replacement", "undetermined"], lines[0]
+    change = np.array([[float(x) for x in ln[1:]] for ln in lines[1:]]).reshape(-1, 4)
+    assert [int(ln[0]) for ln in lines[1:]] == list(range(len(change)))
+    rows = [ln.split("\t") for ln in cod.strip("\n").split("\n")]
+    assert rows[0] == ["codon", "first_site", "bases", "probability"], rows[0]
+    codons = np.zeros((len(change), 64))
+    for c, _, bases, p in rows[1:]:
+        i = ["ACGT".index(b) for b in bases]
+        codons[int(c), 16 * i[0] + 4 * i[1] + i[2]] = float(p)
+    assert aa.split("\n")[0].split("\t") == ["codon", "aa", "probability"]
+    return dict(codons=codons, aa=_parse_aa_table(aa, len(change)), change=change)
+
+
+def read_node_codons(prefix):
+    """The files of PhyloHMM::RunNodeCodonsPipeline: parse_node_codons' dict plus rows [(row, weight, chain_length)] and
+    summary."""
+    res = parse_node_codons("\n".join(open(prefix + ext).read() for ext in (".codons.tsv", ".aa.tsv", ".changes.tsv")))
+    rows = [ln.split("\t") for ln in open(prefix + ".rows.tsv").read().strip().split("\n")]
+    assert rows[0] == ["row", "weight", "chain_length"]
+    res["rows"] = [(int(r[0]), float(r[1]), int(r[2])) for r in rows[1:]]
+    summary = {}
+    for ln in open(prefix + ".summary.tsv").read().strip().split("\n")[1:]:
+        k, v = ln.split("\t")
+        summary[k] = v if k == "node" else int(v) if k in ("rows_used", "rows_skipped_nonfinite", "frame") else float(v)
+    res["summary"] = summary
+    return res
+
+
+def node_codons_write(codons, change, frame=0):
+    """The host writers on caller tables codons [n_codons][64] and change [n_codons][4]: the three texts joined by blank
+    lines (parse_node_codons reads them back)."""
+    import numpy as np
+    codons = np.ascontiguousarray(codons, dtype=np.float64)
+    change = np.ascontiguousarray(change, dtype=np.float64)
+    n = codons.shape[0]
+    assert codons.shape == (n, 64) and change.shape == (n, 4)
+    lib = load_host()
+    lib.lhh_write_node_codons.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_char_p)]
+    out = C.c_char_p()
+    _check(lib.lhh_write_node_codons(codons.ctypes.data, change.ctypes.data, n, frame, C.byref(out)))
+    return out.value.decode()
+
+
 def parse_lineage_node(name):
     """--node's values: "parent" -> 0 (the seed's parent), "mrca" -> 1 (linearham::ParseLineageNode)."""
     lib = load_host()
@@ -555,6 +605,35 @@ class PhyloHMM(_HMM):
                                                          candidates_path.encode(), output_prefix.encode(), num_rates,
                                                          C.c_double(burnin_frac)))
         return read_ancestral_probs(output_prefix)
+
+    def node_codon_marginals(self, seed_seq, node, frame=0):
+        """PhyloHMM::NodeCodonMarginals of the current tree: dict(codons [n_codons][64], change [n_codons][4], aa, node,
+        loglik) at node 0 / "parent" (the seed's parent) or 1 / "mrca"; aa as the host's writer folds it."""
+        if isinstance(node, str):
+            node = parse_lineage_node(node)
+        lib = self.lib
+        lib.lhh_phylo_node_codon_marginals.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                                       C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double),
+                                                       C.POINTER(C.c_char_p)]
+        nc, v, ll, text = C.c_int(), C.c_int(), C.c_double(), C.c_char_p()
+        _check(lib.lhh_phylo_node_codon_marginals(self.h, seed_seq.encode(), node, frame, None, None, 0, C.byref(nc), None, None,
+                                                  None))
+        codons, change = np.zeros((nc.value, 64)), np.zeros((nc.value, 4))
+        _check(lib.lhh_phylo_node_codon_marginals(self.h, seed_seq.encode(), node, frame, codons.ctypes.data, change.ctypes.data,
+                                                  nc.value, C.byref(nc), C.byref(v), C.byref(ll), C.byref(text)))
+        return dict(codons=codons, change=change, aa=parse_node_codons(text.value.decode())["aa"], node=v.value,
+                    loglik=ll.value)
+
+    def run_node_codons_pipeline(self, input_path, seed_seq, node, output_prefix, num_rates, burnin_frac=0.0, frame=0):
+        """PhyloHMM::RunNodeCodonsPipeline: the importance-weighted codon, amino-acid and change tables of the seed's parent
+        or MRCA over a RevBayes table; returns read_node_codons(output_prefix)."""
+        if isinstance(node, str):
+            node = parse_lineage_node(node)
+        self.lib.lhh_run_node_codons_pipeline.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_int, C.c_char_p, C.c_int,
+                                                          C.c_double, C.c_int]
+        _check(self.lib.lhh_run_node_codons_pipeline(self.h, input_path.encode(), seed_seq.encode(), node, output_prefix.encode(),
+                                                     num_rates, C.c_double(burnin_frac), frame))
+        return read_node_codons(output_prefix)
 
     def lineage_substitutions(self, seed_seq):
         """PhyloHMM::LineageSubstitutions of the current tree: dict(nodes [P] -- the lineage of the tip `seed_seq`, slot 0 its

@@ -266,3 +266,42 @@ def aa_table(table, aa_of_codon=None):
             d[aa[i]] = d.get(aa[i], 0.0) + float(row[i])
         out.append(d)
     return out
+
+
+# ---- K14: codon and amino-acid tables of a node of a seed's lineage ----
+# A node's 64 entries are indexed 16 x1 + 4 x2 + x3 over A, C, G, T: node bases are never N.
+
+def node_codon_amino_acids():
+    """The amino acid of each of the 64 node triples (the host library's TranslateDna; '*' for the stop codons)."""
+    from . import host
+    aa = host.translate("".join(BASES[i // 16] + BASES[(i // 4) % 4] + BASES[i % 4] for i in range(64)))
+    assert len(aa) == 64
+    return aa
+
+
+def node_aa_table(table, aa_of_codon=None):
+    """Per codon {amino acid: probability} (entries above 0 only), folding a node's codon table [n_codons][64]."""
+    aa = aa_of_codon or node_codon_amino_acids()
+    out = []
+    for row in np.asarray(table).reshape(-1, 64):
+        d = {}
+        for i in np.nonzero(row)[0]:
+            d[aa[i]] = d.get(aa[i], 0.0) + float(row[i])
+        out.append(d)
+    return out
+
+
+def change_classes(aa_of_codon=None):
+    """[125][64] uint8, the class of a (naive triple, node triple) pair: 0 the naive triple has no N and the node's equals
+    it, 1 no N and another triple with the same translation, 2 no N and a different translation, 3 the naive triple holds
+    an N.  The device carries the same relation as a compile-time table (capi.HipLibrary.node_codon_classes)."""
+    aa = aa_of_codon or node_codon_amino_acids()
+    out = np.full((125, 64), 3, dtype=np.uint8)
+    for i in range(125):
+        b = (i // 25, (i // 5) % 5, i % 5)
+        if 4 in b:
+            continue
+        k = 16 * b[0] + 4 * b[1] + b[2]
+        for x in range(64):
+            out[i, x] = 0 if x == k else 1 if aa[x] == aa[k] else 2
+    return out
