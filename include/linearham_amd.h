@@ -828,6 +828,85 @@ int lh_node_codon_classes(uint8_t* classes);
  * weighted reduction (lh_eval_node_codons_batch only); resets the counters. */
 int lh_node_codons_profile_read(lh_family* fam, double* ms, int64_t* n_launches);
 
+/* ---- K15: exact amino-acid replacement posteriors along the edges of a seed's lineage ----
+ * Which residue was replaced on which step of the lineage.  Neither K12's per-site edge tables nor K14's node tables give
+ * it: a codon's three sites are coupled through the naive codon at both ends of an edge, and the two ends are dependent.
+ * Given the naive base b of a site everything at that site is independent of the rest, so with
+ *   H_s[j][b][a][c] = P(x_{v_s,j} = a, x_{below,j} = c | column j, naive_j = b)
+ * (path, seed tip and "below" as for lh_asr_edges_batch, tables [ancestor][descendant]) and K9's Q, the joint of codon c
+ * over the sites j1, j2, j3 = frame + 3 c .. at the two ends of edge s is
+ *   E_s[c][x][y] = sum_b Q[c][b1 b2 b3] H_s[j1][b1][x1][y1] H_s[j2][b2][x2][y2] H_s[j3][b3][x3][y3]
+ * and the naive edge is K14's joint at the MRCA.  An edge's classes: [0] the lower codon equals the upper, [1] another
+ * codon with the same translation, [2] a different translation (the standard code, the stop codons a symbol of their own:
+ * 21 symbols, lh_codon_edge_symbols); on the naive edge only the N-free naive triples count, [3] is the rest.
+ * With C = n_codons of lh_codon_layout and P = path_len, every member may be NULL:
+ *   log_offset            [n]             (input) as in lh_posterior_outputs
+ *   loglik                [n]
+ *   codon_counts          [n][C][4]       expected number of lineage edges, naive to seed, on which the codon stays, changes
+ *                                         silently, changes by replacement; [3] the naive-edge mass of naive triples with an N.
+ *                                         The four sum to the chain length + 1.
+ *   aa_counts             [n][C][21][21]  expected number of edges on which the translation goes from X (upper end) to Y
+ *                                         (lower end); trace = codon_counts [0] + [1], off-diagonal sum = [2]
+ *   seed_change           [n][C][3]       the three classes on the edge into the seed alone
+ *   edge_change           [n][P+1][C][3]  per edge (slot s: v_s to below; entry P: the naive edge, K14's change [0..2] at the
+ *                                         MRCA); padding slots 0
+ *   edge_load             [n][P+1][2]     expected number of codons changing silently / by replacement on each edge
+ *   weighted_codon_counts [C][4], weighted_aa_counts [C][21][21], weighted_seed_change [C][3]
+ *                                         sum_i w_i row_i, w_i = exp(loglik_i - log_offset_i - max)
+ *   weight_stats          [3]             max, sum w, sum w^2 as in lh_posterior_outputs
+ * Needs lh_family_set_sampler and lh_family_set_codons; the extended-range mode is honoured.  A row with a non-finite
+ * log-likelihood, a rejected schedule or (device form) a bad path or seed gets NaN and no weight; path and seed are checked,
+ * the error word raised and the host-pointer form's device copies bounded (4 GiB) as for lh_eval_edges_batch.  The sums run
+ * in sample order (K5's slab scheme); the same sample gives the same bits whatever the batch around it. */
+typedef struct lh_codon_edges_outputs {
+  const double* log_offset;
+  double* loglik;
+  double* codon_counts;
+  double* aa_counts;
+  double* seed_change;
+  double* edge_change;
+  double* edge_load;
+  double* weighted_codon_counts;
+  double* weighted_aa_counts;
+  double* weighted_seed_change;
+  double* weight_stats;
+} lh_codon_edges_outputs;
+
+int lh_eval_codon_edges_batch(lh_family* fam, int32_t n, int32_t n_tips, int32_t max_depth, const int32_t* ops,
+                              const double* brlen, const double* er, const double* pi, const double* alpha,
+                              int32_t num_rates, const int32_t* path, int32_t path_len, int32_t seed_tip,
+                              const lh_codon_edges_outputs* outs);
+
+/* Same with every array (the members of outs included) resident on the handle's device; enqueued on `hip_stream`
+ * without synchronising. */
+int lh_eval_codon_edges_batch_device(lh_family* fam, int32_t n, int32_t n_tips, int32_t max_depth, const int32_t* ops,
+                                     const double* brlen, const double* er, const double* pi, const double* alpha,
+                                     int32_t num_rates, const int32_t* path, int32_t path_len, int32_t seed_tip,
+                                     const lh_codon_edges_outputs* outs, void* hip_stream);
+
+/* The tables alone behind one pruning pass: lh_asr_node_codons_batch's trees, given rates[n][num_rates] and the caller's
+ * naive codon posteriors naive_codons[n][C][125], with seed_tip; the five per-row tables above (each may be NULL) and
+ * cond_edge[n][P][L][5][4][4] (may be NULL), H spread over the sites.  Needs lh_family_set_codons (for the frame). */
+int lh_asr_codon_edges_batch(lh_family* fam, int32_t n, int32_t n_tips, int32_t max_depth, const int32_t* ops,
+                             const double* brlen, const double* er, const double* pi, const double* rates,
+                             int32_t num_rates, const double* naive_codons, const int32_t* path, int32_t path_len,
+                             int32_t seed_tip, double* codon_counts, double* aa_counts, double* seed_change,
+                             double* edge_change, double* edge_load, double* cond_edge);
+int lh_asr_codon_edges_batch_device(lh_family* fam, int32_t n, int32_t n_tips, int32_t max_depth, const int32_t* ops,
+                                    const double* brlen, const double* er, const double* pi, const double* rates,
+                                    int32_t num_rates, const double* naive_codons, const int32_t* path, int32_t path_len,
+                                    int32_t seed_tip, double* codon_counts, double* aa_counts, double* seed_change,
+                                    double* edge_change, double* edge_load, double* cond_edge, void* hip_stream);
+
+/* sym[64]: the symbol 0 .. 20 (its position in "ACDEFGHIKLMNPQRSTVWY*") of every triple 16 x1 + 4 x2 + x3 over A,C,G,T,
+ * as the kernel's compile-time map has it. */
+int lh_codon_edge_symbols(uint8_t* sym);
+
+/* Times of K15 over the launches made while profiling was enabled (HIP events on the launch stream), ms[3]: K9 with the
+ * tables (rate weights, path and seed check, K15b, rate combination, the naive codons of every codon), the contraction, the
+ * weighted reduction (lh_eval_codon_edges_batch only); resets the counters. */
+int lh_codon_edges_profile_read(lh_family* fam, double* ms, int64_t* n_launches);
+
 /* Timing of the kernels of the last lh_eval_batch_device call sequence, measured with HIP events
  * on the launch stream when enabled (ms per kernel family: model, prune, forward). */
 int lh_profile_enable(lh_family* fam, int enable);

@@ -12,7 +12,7 @@ LIB = os.path.join(PKG, "lib")
 HIP_SOURCES = ["lh_model.hip", "lh_prune.hip", "lh_forward.hip", "lh_asr.hip", "lh_sample.hip", "lh_posterior.hip",
                "lh_naive_probs.hip", "lh_collect.hip", "lh_lineage.hip", "lh_viterbi.hip", "lh_codon.hip", "lh_events.hip",
                "lh_ancestral.hip", "lh_substitutions.hip", "lh_ancestral_probs.hip", "lh_node_codon.hip",
-               "lh_capi.hip"]
+               "lh_codon_edges.hip", "lh_capi.hip"]
 
 
 def _run(cmd, verbose):

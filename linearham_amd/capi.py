@@ -99,6 +99,11 @@ NODE_PARENT, NODE_MRCA = 0, 1  # lh_eval_ancestral_candidates_batch's `node`
 NODE_CODONS_EXPORTS = ["lh_eval_node_codons_batch", "lh_eval_node_codons_batch_device", "lh_asr_node_codons_batch",
                        "lh_asr_node_codons_batch_device", "lh_node_codon_classes", "lh_node_codons_profile_read"]
 EXPORTS += NODE_CODONS_EXPORTS
+# K15 (exact amino-acid replacement posteriors along the edges of a seed's lineage)
+CODON_EDGES_EXPORTS = ["lh_eval_codon_edges_batch", "lh_eval_codon_edges_batch_device", "lh_asr_codon_edges_batch",
+                       "lh_asr_codon_edges_batch_device", "lh_codon_edge_symbols", "lh_codon_edges_profile_read"]
+EXPORTS += CODON_EDGES_EXPORTS
+AA_SYMBOLS = "ACDEFGHIKLMNPQRSTVWY*"  # the 21 symbols of aa_counts, in lh_codon_edge_symbols' numbering
 
 
 class _CodonOutputs(C.Structure):
@@ -183,6 +188,24 @@ class _NodeCodonsOutputs(C.Structure):
 
 class _NodeCodonsOutputsDevice(C.Structure):  # the same members as device addresses
     _fields_ = [(k, C.c_void_p) for k in _NODE_CODONS_MEMBERS]
+
+
+_CODON_EDGES_MEMBERS = ("log_offset", "loglik", "codon_counts", "aa_counts", "seed_change", "edge_change", "edge_load",
+                        "weighted_codon_counts", "weighted_aa_counts", "weighted_seed_change", "weight_stats")
+_CODON_EDGES_TABLES = ("codon_counts", "aa_counts", "seed_change", "edge_change", "edge_load")
+
+
+class _CodonEdgesOutputs(C.Structure):
+    _fields_ = [(k, c_f64p) for k in _CODON_EDGES_MEMBERS]
+
+
+class _CodonEdgesOutputsDevice(C.Structure):  # the same members as device addresses
+    _fields_ = [(k, C.c_void_p) for k in _CODON_EDGES_MEMBERS]
+
+
+def _codon_edges_shapes(n, nc, P):
+    return dict(codon_counts=(n, nc, 4), aa_counts=(n, nc, 21, 21), seed_change=(n, nc, 3), edge_change=(n, P + 1, nc, 3),
+                edge_load=(n, P + 1, 2))
 
 
 class _SamplerJunction(C.Structure):
@@ -370,6 +393,16 @@ class HipLibrary:
                 [C.c_void_p] * 3
             lib.lh_node_codon_classes.argtypes = [c_u8p]
             lib.lh_node_codons_profile_read.argtypes = _PROFILE_READ
+        if hasattr(lib, "lh_eval_codon_edges_batch"):
+            lib.lh_eval_codon_edges_batch.argtypes = _HOST_TREE + [c_i32p, C.c_int32, C.c_int32,
+                                                                   C.POINTER(_CodonEdgesOutputs)]
+            lib.lh_eval_codon_edges_batch_device.argtypes = _DEV_TREE + [
+                C.c_void_p, C.c_int32, C.c_int32, C.POINTER(_CodonEdgesOutputsDevice), C.c_void_p]
+            lib.lh_asr_codon_edges_batch.argtypes = _HOST_TREE + [c_f64p, c_i32p, C.c_int32, C.c_int32] + [c_f64p] * 6
+            lib.lh_asr_codon_edges_batch_device.argtypes = _DEV_TREE + [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32] + \
+                [C.c_void_p] * 7
+            lib.lh_codon_edge_symbols.argtypes = [c_u8p]
+            lib.lh_codon_edges_profile_read.argtypes = _PROFILE_READ
         if hasattr(lib, "lh_set_device"):      # (absent from round-2 builds loaded through LH_LIB_DIR for comparisons)
             lib.lh_set_device.argtypes = [C.c_int32]
             lib.lh_family_status.argtypes = [C.c_void_p]
@@ -521,6 +554,47 @@ class HipLibrary:
         triple, node triple) pair as the device's compile-time table has it."""
         out = np.zeros((125, 64), dtype=np.uint8)
         self.check(self.lib.lh_node_codon_classes(out.ctypes.data_as(c_u8p)))
+        return out
+
+    def eval_codon_edges_batch(self, family, n_tips, max_depth, ops, brlen, er, pi, alpha, num_rates, path, seed_tip,
+                               log_offset=None, want=("loglik",) + _CODON_EDGES_TABLES):
+        """K0-K2 + K9 + K15 on a family handle after set_codons; path [n][P] (seed_path rows, -1 padding) of tip seed_tip.
+        Returns a dict with the members of `want`: loglik [n], codon_counts [n, C, 4] (expected lineage edges on which the
+        codon stays, changes silently, changes by replacement; naive triple with an N), aa_counts [n, C, 21, 21] (from the
+        upper end's symbol to the lower end's, AA_SYMBOLS), seed_change [n, C, 3], edge_change [n, P + 1, C, 3] (entry P the
+        naive edge), edge_load [n, P + 1, 2], weighted_codon_counts [C, 4], weighted_aa_counts [C, 21, 21],
+        weighted_seed_change [C, 3], weight_stats [3]."""
+        h = _handle(family)
+        n, arrays = _tree_args(ops, brlen, er, pi, alpha)
+        path = _i32(path)
+        assert path.ndim == 2 and path.shape[0] == n
+        nc = C.c_int32()
+        self.check(self.lib.lh_codon_layout(h, C.byref(nc), None, None, None))
+        nc = nc.value
+        res, outs = _outputs(_CodonEdgesOutputs, want, log_offset, loglik=(n,), weighted_codon_counts=(nc, 4),
+                             weighted_aa_counts=(nc, 21, 21), weighted_seed_change=(nc, 3), weight_stats=(3,),
+                             **_codon_edges_shapes(n, nc, path.shape[1]))
+        self.check(self.lib.lh_eval_codon_edges_batch(h, n, n_tips, max_depth, *_tree_ptrs(arrays), num_rates,
+                                                      _ptr(path, c_i32p), path.shape[1], seed_tip, C.byref(outs)))
+        return res
+
+    def eval_codon_edges_batch_device(self, family, n, n_tips, max_depth, ops_ptr, brlen_ptr, er_ptr, pi_ptr, alpha_ptr,
+                                      num_rates, path_ptr, path_len, seed_tip, outs, stream=0):
+        """lh_eval_codon_edges_batch_device on device addresses; outs: dict of the output members' addresses."""
+        o = _CodonEdgesOutputsDevice(**{k: int(v) for k, v in outs.items() if v})
+        self.check(self.lib.lh_eval_codon_edges_batch_device(
+            _handle(family), n, n_tips, max_depth, ops_ptr, brlen_ptr, er_ptr, pi_ptr, alpha_ptr, num_rates, path_ptr,
+            path_len, seed_tip, C.byref(o), stream))
+
+    def codon_edges_profile_read(self, family):
+        """(K9 + tables ms, contraction ms, reduction ms, launch groups) of K15 since the last read."""
+        return self._profile_read("lh_codon_edges_profile_read", family, 3)
+
+    def codon_edge_symbols(self):
+        """[64] uint8: the symbol (index into AA_SYMBOLS) of every triple 16 x1 + 4 x2 + x3 as the device's compile-time
+        map has it."""
+        out = np.zeros(64, dtype=np.uint8)
+        self.check(self.lib.lh_codon_edge_symbols(out.ctypes.data_as(c_u8p)))
         return out
 
     def eval_edges_batch(self, family, n_tips, max_depth, ops, brlen, er, pi, alpha, num_rates, path, seed_tip,
@@ -1205,6 +1279,35 @@ class Family:
             self.handle, n, n_tips, max_depth, *_tree_ptrs(arrays), rates.shape[1], _ptr(naive_codons), _ptr(path, c_i32p),
             path.shape[1], node, _ptr(codons), _ptr(change)))
         return codons, change
+
+    # ---- K15: exact amino-acid replacement posteriors along the edges of a lineage ----
+    def asr_codon_edges_batch(self, n_tips, max_depth, ops, brlen, er, pi, rates, naive_codons, path, seed_tip,
+                              want=_CODON_EDGES_TABLES, n_sites=None):
+        """lh_asr_codon_edges_batch: asr_node_codons_batch's trees, rates and naive codon posteriors naive_codons
+        [n][C][125], path [n][P] of tip seed_tip; returns a dict with the members of `want` among codon_counts, aa_counts,
+        seed_change, edge_change, edge_load (eval_codon_edges_batch's shapes) and cond_edge [n][P][L][5][4][4] (which needs
+        n_sites = L)."""
+        _, arrays = _tree_args(ops, brlen, er, pi, rates)
+        ops, brlen, er, pi, rates = arrays
+        naive_codons = _f64(naive_codons)
+        path = _i32(path)
+        n, nc = naive_codons.shape[:2]
+        assert naive_codons.shape == (n, nc, 125) and path.ndim == 2 and path.shape[0] == n
+        assert ops.shape == (n, n_tips - 2, 4) and brlen.shape == (n, 2 * n_tips - 2)
+        assert er.shape == (n, 6) and pi.shape == (n, 4) and rates.shape[0] == n
+        have = C.c_int32()
+        self.hip.check(self.hip.lib.lh_codon_layout(self.handle, C.byref(have), None, None, None))
+        if have.value != nc:
+            raise ValueError("lh_asr_codon_edges_batch: naive_codons has %d codons, the handle's frame %d" % (nc, have.value))
+        P = path.shape[1]
+        shapes = _codon_edges_shapes(n, nc, P)
+        assert "cond_edge" not in want or n_sites
+        shapes["cond_edge"] = (n, P, n_sites or 0, 5, 4, 4)
+        res = {k: (np.zeros(shapes[k]) if k in want else None) for k in _CODON_EDGES_TABLES + ("cond_edge",)}
+        self.hip.check(self.hip.lib.lh_asr_codon_edges_batch(
+            self.handle, n, n_tips, max_depth, *_tree_ptrs(arrays), rates.shape[1], _ptr(naive_codons), _ptr(path, c_i32p),
+            P, seed_tip, *[_ptr(res[k]) for k in _CODON_EDGES_TABLES + ("cond_edge",)]))
+        return {k: v for k, v in res.items() if v is not None}
 
     # ---- K12: exact substitution posteriors along the edges of a lineage ----
     def asr_edges_batch(self, n_tips, max_depth, ops, brlen, er, pi, rates, naive_prob, path, seed_tip,

@@ -2794,6 +2794,149 @@ void PhyloHMM::RunNodeCodonsPipeline(const std::string& input_path, const std::s
           << "\nexpected_replacement\t" << Fmt17(repl) << "\n";
 }
 
+// ---- K15: exact amino-acid replacement posteriors along the edges of a seed's lineage ----
+
+namespace {
+
+void CheckFrame(const std::string& who, int frame) { Require(frame >= 0 && frame <= 2, who + ": frame must be 0, 1 or 2"); }
+
+PhyloHMM::LineageReplacementsResult UnpackReplacements(int frame, std::size_t C, const double* cc, const double* aa, const double* sc) {
+  PhyloHMM::LineageReplacementsResult r;
+  r.frame = frame;
+  r.codon_counts.resize(C);
+  r.aa_counts.resize(C);
+  r.seed_change.resize(C);
+  for (std::size_t c = 0; c < C; ++c) {
+    std::copy(cc + c * 4, cc + (c + 1) * 4, r.codon_counts[c].begin());
+    std::copy(aa + c * 441, aa + (c + 1) * 441, r.aa_counts[c].begin());
+    std::copy(sc + c * 3, sc + (c + 1) * 3, r.seed_change[c].begin());
+  }
+  return r;
+}
+
+}  // namespace
+
+PhyloHMM::LineageReplacementsResult PhyloHMM::LineageReplacements(const std::string& seed_seq, int frame) {
+  CheckFrame("LineageReplacements", frame);
+  SeedLineage s = OpenSeedLineage(seed_seq);
+  const CodonLayout lay = SetCodons(family_, frame);
+  const std::size_t C = (std::size_t)lay.n_codons, P = s.nodes.size();
+  std::vector<double> cc(C * 4), aa(C * 441), sc(C * 3), ec((P + 1) * C * 3), el((P + 1) * 2);
+  double ll = 0.0;
+  lh_codon_edges_outputs outs{};
+  outs.loglik = &ll;
+  outs.codon_counts = cc.data();
+  outs.aa_counts = aa.data();
+  outs.seed_change = sc.data();
+  outs.edge_change = ec.data();
+  outs.edge_load = el.data();
+  CheckHip(lh_eval_codon_edges_batch(family_, 1, tree_.n_tips, s.depth, s.ops.data(), tree_.brlen.data(), er_.data(), pi_.data(),
+                                     &alpha_, num_rates_, s.nodes.data(), (int32_t)P, s.seed_tip, &outs),
+           "lh_eval_codon_edges_batch");
+  LineageReplacementsResult r = UnpackReplacements(frame, C, cc.data(), aa.data(), sc.data());
+  r.nodes = std::move(s.nodes);
+  r.loglik = ll;
+  r.edge_change = std::move(ec);
+  r.edge_load.resize(P + 1);
+  for (std::size_t e = 0; e <= P; ++e) r.edge_load[e] = {el[2 * e], el[2 * e + 1]};
+  return r;
+}
+
+void PhyloHMM::WriteReplacementTable(std::ostream& o, const LineageReplacementsResult& m) {
+  o << "codon\tfirst_site\tfrom\tto\texpected_edges\n";
+  for (std::size_t c = 0; c < m.aa_counts.size(); ++c)
+    for (int x = 0; x < 21; ++x)
+      for (int y = 0; y < 21; ++y)
+        if (x != y && m.aa_counts[c][x * 21 + y] > 0.0)
+          o << c << '\t' << (m.frame + 3 * c) << '\t' << kAaSymbols[x] << '\t' << kAaSymbols[y] << '\t'
+            << Fmt17(m.aa_counts[c][x * 21 + y]) << '\n';
+}
+
+void PhyloHMM::WriteCodonChangeTable(std::ostream& o, const LineageReplacementsResult& m) {
+  o << "codon\tunchanged\tsynonymous\treplacement\tundetermined\n";
+  for (std::size_t c = 0; c < m.codon_counts.size(); ++c) {
+    o << c;
+    for (int k = 0; k < 4; ++k) o << '\t' << Fmt17(m.codon_counts[c][k]);
+    o << '\n';
+  }
+}
+
+void PhyloHMM::WriteSeedChangeTable(std::ostream& o, const LineageReplacementsResult& m) {
+  o << "codon\tunchanged\tsynonymous\treplacement\n";
+  for (std::size_t c = 0; c < m.seed_change.size(); ++c) {
+    o << c;
+    for (int k = 0; k < 3; ++k) o << '\t' << Fmt17(m.seed_change[c][k]);
+    o << '\n';
+  }
+}
+
+void PhyloHMM::RunLineageReplacementsPipeline(const std::string& input_path, const std::string& seed_seq,
+                                              const std::string& output_prefix, int num_rates, double burnin_frac, int frame) {
+  // what can be refused without a device is refused first: the frame, then BeginPipeline's checks (burn-in, seed)
+  CheckFrame("the lineage-replacements pipeline", frame);
+  const int seed_tip = BeginPipeline("lineage replacements", "codon", burnin_frac, &seed_seq);
+  const CodonLayout lay = SetCodons(family_, frame);
+  TsvTable table = TsvTable::OpenRevBayesTable(input_path);
+  const std::size_t first = FirstUsedRow(table.rows.size(), burnin_frac);
+  const std::size_t C = (std::size_t)lay.n_codons, NC = C * 4, NA = C * 441, NS = C * 3, NROW = NC + NA + NS;
+  // the rows' tables come back whole (448 C doubles each): a batch is bounded by at most 512 MiB of them
+  const std::size_t fit = std::max<std::size_t>(1, ((std::size_t)512 << 20) / (sizeof(double) * std::max<std::size_t>(NROW, 1)));
+  std::vector<double> cc, aa, sc, syn(table.rows.size() - first, 0.0), repl(table.rows.size() - first, 0.0);
+  std::vector<int32_t> path_len(table.rows.size() - first, 0);
+  const WeightedRows w = SumWeightedRows(
+      "lineage replacements", table, input_path, first, PipelineBatch(fit), NROW, true,
+      [&](const TableBatch& tb, std::size_t off, double* ll) {
+        const DeviceBatch& b = tb.dev;
+        const std::size_t m = (std::size_t)b.n;
+        const SeedChains chains = SeedChainsOf(tb, off, seed_tip, seed_seq, path_len.data() + (off - first));
+        cc.resize(m * NC);
+        aa.resize(m * NA);
+        sc.resize(m * NS);
+        lh_codon_edges_outputs outs{};
+        outs.loglik = ll;
+        outs.codon_counts = cc.data();
+        outs.aa_counts = aa.data();
+        outs.seed_change = sc.data();
+        CheckHip(lh_eval_codon_edges_batch(family_, b.n, b.n_tips, b.max_depth, b.ops.data(), b.brlen.data(), b.er.data(),
+                                           b.pi.data(), b.alpha.data(), num_rates, chains.path.data(), (int32_t)chains.P, seed_tip,
+                                           &outs),
+                 "lh_eval_codon_edges_batch");
+        for (std::size_t i = 0; i < m; ++i) {  // the row's expected changes over its lineage, the codons in order
+          double s1 = 0.0, s2 = 0.0;
+          for (std::size_t c = 0; c < C; ++c) {
+            s1 += cc[i * NC + c * 4 + 1];
+            s2 += cc[i * NC + c * 4 + 2];
+          }
+          syn[off - first + i] = s1;
+          repl[off - first + i] = s2;
+        }
+        return [&](std::size_t i, double* row) {
+          std::copy(cc.begin() + i * NC, cc.begin() + (i + 1) * NC, row);
+          std::copy(aa.begin() + i * NA, aa.begin() + (i + 1) * NA, row + NC);
+          std::copy(sc.begin() + i * NS, sc.begin() + (i + 1) * NS, row + NC + NA);
+        };
+      });
+  const double* t = w.acc.total.data();
+  const LineageReplacementsResult res = UnpackReplacements(frame, C, t, t + NC, t + NC + NA);
+  std::ofstream rep(output_prefix + ".replacements.tsv"), chg(output_prefix + ".codon_changes.tsv"),
+      seed(output_prefix + ".seed_edge.tsv"), rows(output_prefix + ".rows.tsv"), summary(output_prefix + ".summary.tsv");
+  Require(rep.good() && chg.good() && seed.good() && rows.good() && summary.good(), "Can't write " + output_prefix + ".*.tsv");
+  WriteReplacementTable(rep, res);
+  WriteCodonChangeTable(chg, res);
+  WriteSeedChangeTable(seed, res);
+  rows << "row\tweight\tchain_length\texpected_synonymous\texpected_replacement\n";
+  for (std::size_t u = 0; u < w.lw.size(); ++u)
+    rows << (first + u) << '\t' << Fmt17(w.weight(u)) << '\t' << path_len[u] << '\t' << Fmt17(syn[u]) << '\t' << Fmt17(repl[u])
+         << '\n';
+  WriteSummary(summary, w.used(), w.skipped, Fmt17(w.acc.KishEss()));
+  double s1 = 0.0, s2 = 0.0;
+  for (const auto& h : res.codon_counts) {
+    s1 += h[1];
+    s2 += h[2];
+  }
+  summary << "frame\t" << frame << "\nexpected_synonymous\t" << Fmt17(s1) << "\nexpected_replacement\t" << Fmt17(s2) << "\n";
+}
+
 // Pass 1 draws every used row's naive sequence with the std::mt19937 words RunPipeline gives that row (row r: words
 // r * RawDrawsPerSample() on), on the device where the family has its sampler tables: K4's states become bytes and a
 // hash there (K6c), the host maps hashes to candidate ids in row order and the device checks every row's bytes against

@@ -298,6 +298,36 @@ class PhyloHMM : public HMM {
   static void WriteNodeCodonTable(std::ostream& o, const NodeCodonsResult& m);
   static void WriteNodeAminoAcidTable(std::ostream& o, const NodeCodonsResult& m);
   static void WriteChangeTable(std::ostream& o, const NodeCodonsResult& m);
+  /// K15: exact amino-acid replacement posteriors along the edges of the lineage of the tip `seed_seq`
+  /// (lh_eval_codon_edges_batch); codon c covers the sites frame + 3 c ...  The lineage has nodes.size() + 1 edges: slot s
+  /// from nodes[s] to nodes[s - 1] (slot 0: to the seed), the last entry the naive edge.  Amino acids are indexed by their
+  /// place in kAaSymbols, the stop codons a symbol of their own.
+  static constexpr const char* kAaSymbols = "ACDEFGHIKLMNPQRSTVWY*";
+  struct LineageReplacementsResult {
+    int frame = 0;
+    double loglik = 0.0;
+    std::vector<int32_t> nodes;                          // the chain, the seed's parent first (empty: a weighted mean)
+    std::vector<std::array<double, 4>> codon_counts;     // expected edges: unchanged, synonymous, replacement; naive triple with an N
+    std::vector<std::array<double, 441>> aa_counts;      // [from][to] expected edges
+    std::vector<std::array<double, 3>> seed_change;      // the edge into the seed alone
+    std::vector<double> edge_change;                     // [nodes.size() + 1][n_codons][3]
+    std::vector<std::array<double, 2>> edge_load;        // per edge: expected codons changing silently / by replacement
+  };
+  /// After InitializePhyloParameters: the tables of the current tree.  The frame is checked first.
+  LineageReplacementsResult LineageReplacements(const std::string& seed_seq, int frame);
+  /// The importance-weighted tables over a RevBayes table, with RunLineageSubstitutionsPipeline's reader, burn-in, weights,
+  /// Kish ESS and one-device rule.  The seed, the frame and the burn-in are refused before the family is created.  The rows'
+  /// tables are added up on the host in row order, so the files do not depend on LH_PIPELINE_BATCH.  Writes
+  /// <prefix>.replacements.tsv (codon, first site, from, to, expected edges: the non-zero off-diagonal cells),
+  /// .codon_changes.tsv (codon, unchanged, synonymous, replacement, undetermined), .seed_edge.tsv (codon, unchanged,
+  /// synonymous, replacement), .rows.tsv (row, weight, chain_length, expected_synonymous, expected_replacement) and
+  /// .summary.tsv (with frame, expected_synonymous and expected_replacement, the column sums of the codon changes).
+  void RunLineageReplacementsPipeline(const std::string& input_path, const std::string& seed_seq, const std::string& output_prefix,
+                                      int num_rates, double burnin_frac, int frame);
+  /// numbers printed with %.17g; the first leaves out the diagonal and the cells that are 0
+  static void WriteReplacementTable(std::ostream& o, const LineageReplacementsResult& m);
+  static void WriteCodonChangeTable(std::ostream& o, const LineageReplacementsResult& m);
+  static void WriteSeedChangeTable(std::ostream& o, const LineageReplacementsResult& m);
   /// site, then one column per cell named <ancestor base><descendant base> (n_rows x 4 cells, rows over ACGTN), and with
   /// `with_sum` the off-diagonal sum of the first four rows; numbers printed with %.17g
   static void WritePairTable(std::ostream& o, const double* table, std::size_t n_sites, int n_rows, bool with_sum);

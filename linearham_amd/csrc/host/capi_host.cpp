@@ -435,6 +435,78 @@ int lhh_write_node_codons(const double* codons, const double* change, int n_codo
   });
 }
 
+// The three tables of a LineageReplacementsResult, separated by blank lines (WriteReplacementTable, WriteCodonChangeTable,
+// WriteSeedChangeTable)
+static const char* LineageReplacementsText(const PhyloHMM::LineageReplacementsResult& m) {
+  std::ostringstream o;
+  PhyloHMM::WriteReplacementTable(o, m);
+  o << "\n";
+  PhyloHMM::WriteCodonChangeTable(o, m);
+  o << "\n";
+  PhyloHMM::WriteSeedChangeTable(o, m);
+  g_out = o.str();
+  return g_out.c_str();
+}
+
+// PhyloHMM::LineageReplacements: codon_counts [cap_codons][4], aa_counts [cap_codons][441], seed_change [cap_codons][3],
+// edge_change [cap_edges][cap_codons][3], edge_load [cap_edges][2], nodes [cap_edges]; *n_codons and *n_edges (the chain's
+// length + 1) receive the counts, *text the three tables as the writers print them.  codon_counts == NULL: only the frame
+// check and *n_codons, nothing is evaluated; cap_edges too small: *n_edges alone is set and nothing is copied.
+int lhh_phylo_lineage_replacements(void* h, const char* seed_seq, int frame, double* codon_counts, double* aa_counts,
+                                   double* seed_change, int cap_codons, double* edge_change, double* edge_load, int32_t* nodes,
+                                   int cap_edges, int* n_codons, int* n_edges, double* loglik, const char** text) {
+  return Guard([&] {
+    PhyloHMM& p = dynamic_cast<PhyloHMM&>(*static_cast<HMM*>(h));
+    if (frame < 0 || frame > 2) throw std::runtime_error("LineageReplacements: frame must be 0, 1 or 2");
+    const int L = (int)p.msa().cols();
+    *n_codons = L >= frame ? (L - frame) / 3 : 0;
+    if (!codon_counts) return;
+    const PhyloHMM::LineageReplacementsResult m = p.LineageReplacements(seed_seq, frame);
+    const std::size_t C = m.codon_counts.size(), E = m.nodes.size() + 1;
+    if ((int)C > cap_codons) throw std::runtime_error("lhh_phylo_lineage_replacements: output too small");
+    *n_edges = (int)E;
+    for (std::size_t c = 0; c < C; ++c) {
+      std::copy(m.codon_counts[c].begin(), m.codon_counts[c].end(), codon_counts + c * 4);
+      if (aa_counts) std::copy(m.aa_counts[c].begin(), m.aa_counts[c].end(), aa_counts + c * 441);
+      if (seed_change) std::copy(m.seed_change[c].begin(), m.seed_change[c].end(), seed_change + c * 3);
+    }
+    if ((int)E <= cap_edges) {
+      if (edge_change) std::copy(m.edge_change.begin(), m.edge_change.end(), edge_change);
+      for (std::size_t e = 0; e < E && edge_load; ++e) std::copy(m.edge_load[e].begin(), m.edge_load[e].end(), edge_load + 2 * e);
+      if (nodes) std::copy(m.nodes.begin(), m.nodes.end(), nodes);
+    }
+    if (loglik) *loglik = m.loglik;
+    if (text) *text = LineageReplacementsText(m);
+  });
+}
+
+int lhh_run_lineage_replacements_pipeline(void* h, const char* input_path, const char* seed_seq, const char* output_prefix,
+                                          int num_rates, double burnin_frac, int frame) {
+  return Guard([&] {
+    dynamic_cast<PhyloHMM&>(*static_cast<HMM*>(h)).RunLineageReplacementsPipeline(input_path, seed_seq, output_prefix, num_rates,
+                                                                                burnin_frac, frame);
+  });
+}
+
+// The writers' text of caller tables: codon_counts [n_codons][4], aa_counts [n_codons][441], seed_change [n_codons][3]
+int lhh_write_lineage_replacements(const double* codon_counts, const double* aa_counts, const double* seed_change, int n_codons,
+                                   int frame, const char** out) {
+  return Guard([&] {
+    if (n_codons < 0 || frame < 0 || frame > 2) throw std::runtime_error("lhh_write_lineage_replacements: bad shape");
+    PhyloHMM::LineageReplacementsResult m;
+    m.frame = frame;
+    m.codon_counts.resize(n_codons);
+    m.aa_counts.resize(n_codons);
+    m.seed_change.resize(n_codons);
+    for (int c = 0; c < n_codons; ++c) {
+      std::copy(codon_counts + c * 4, codon_counts + (c + 1) * 4, m.codon_counts[c].begin());
+      std::copy(aa_counts + c * 441, aa_counts + (c + 1) * 441, m.aa_counts[c].begin());
+      std::copy(seed_change + c * 3, seed_change + (c + 1) * 3, m.seed_change[c].begin());
+    }
+    *out = LineageReplacementsText(m);
+  });
+}
+
 // WriteAncestralProbsTable's text of K candidates: names and seqs joined by '\n'; *covered receives CoveredMass
 int lhh_write_ancestral_probs_table(const char* names, const char* seqs, const double* prob, int K, const char** out,
                                     double* covered) {

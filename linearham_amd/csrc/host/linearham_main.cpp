@@ -65,7 +65,7 @@ int main(int argc, char** argv) {
   try {
     if (argc < 2 || std::string(argv[1]) == "-h" || std::string(argv[1]) == "--help") {
       std::cout << "A Phylo-HMM implementation for B cell receptor sequence analysis.\n"
-                   "USAGE: linearham {--compute-logl|--sample|--pipeline|--asr|--marginals|--marginals-pipeline|--naive-probs|--naive-probs-pipeline|--lineage-pipeline|--weighted-lineage-pipeline|--viterbi|--annotations-pipeline|--codon-marginals|--codon-marginals-pipeline|--events|--events-pipeline|--ancestral-marginals|--ancestral-marginals-pipeline|--lineage-substitutions|--lineage-substitutions-pipeline|--ancestral-probs|--ancestral-probs-pipeline|--node-codons|--node-codons-pipeline} --yaml-path <string> "
+                   "USAGE: linearham {--compute-logl|--sample|--pipeline|--asr|--marginals|--marginals-pipeline|--naive-probs|--naive-probs-pipeline|--lineage-pipeline|--weighted-lineage-pipeline|--viterbi|--annotations-pipeline|--codon-marginals|--codon-marginals-pipeline|--events|--events-pipeline|--ancestral-marginals|--ancestral-marginals-pipeline|--lineage-substitutions|--lineage-substitutions-pipeline|--ancestral-probs|--ancestral-probs-pipeline|--node-codons|--node-codons-pipeline|--lineage-replacements|--lineage-replacements-pipeline} --yaml-path <string> "
                    "--cluster-ind <int> --hmm-param-dir <string> [--seed <int>] [--num-rates <int>] [--extended-range <0|1>] "
                    "[--devices <a,b,...>] ...\n"
                    "  --marginals: the arguments of --compute-logl; prints the per-site naive-base table and the gene table\n"
@@ -115,6 +115,13 @@ int main(int argc, char** argv) {
                    "  --node-codons-pipeline --input-path <RevBayes table> --output-path <prefix> --seed-seq <name>\n"
                    "    --node <parent|mrca> [--frame <0|1|2>] [--burnin-frac <f>]: writes <prefix>.codons.tsv, <prefix>.aa.tsv,\n"
                    "    <prefix>.changes.tsv, <prefix>.rows.tsv and <prefix>.summary.tsv (one device)\n"
+                   "  --lineage-replacements --seed-seq <name> [--frame <0|1|2>]: the arguments of --marginals; prints per codon the\n"
+                   "    expected number of lineage edges, naive to the sequence <name>, on which its amino acid goes from one residue\n"
+                   "    to another, the codon's expected unchanged / synonymous / replacement edges, the same on the edge into the\n"
+                   "    sequence alone, and per edge the expected number of codons changing silently and by replacement\n"
+                   "  --lineage-replacements-pipeline --input-path <RevBayes table> --output-path <prefix> --seed-seq <name>\n"
+                   "    [--frame <0|1|2>] [--burnin-frac <f>]: writes <prefix>.replacements.tsv, <prefix>.codon_changes.tsv,\n"
+                   "    <prefix>.seed_edge.tsv, <prefix>.rows.tsv and <prefix>.summary.tsv (one device)\n"
                    "  --lineage-pipeline --input-path <--pipeline table> --output-path <prefix> --seed-seq <name> [--seed <int>]:\n"
                    "    the lineage tables of the sequence <name>: <prefix>.fasta, .dnamap, .nodes.tsv, .edges.tsv, .summary.tsv\n"
                    "       linearham --lineage-trees --input-path <--asr trees> --output-path <prefix> --seed-seq <name>\n"
@@ -146,7 +153,7 @@ int main(int argc, char** argv) {
         subcmd != "--ancestral-marginals" && subcmd != "--ancestral-marginals-pipeline" &&
         subcmd != "--lineage-substitutions" && subcmd != "--lineage-substitutions-pipeline" &&
         subcmd != "--ancestral-probs" && subcmd != "--ancestral-probs-pipeline" && subcmd != "--node-codons" &&
-        subcmd != "--node-codons-pipeline")
+        subcmd != "--node-codons-pipeline" && subcmd != "--lineage-replacements" && subcmd != "--lineage-replacements-pipeline")
       throw std::invalid_argument("'" + subcmd + "' is not a valid subcommand.");
     const std::string yaml_path = a.one("yaml-path");
     const int cluster_ind = std::stoi(a.one("cluster-ind"));
@@ -168,7 +175,8 @@ int main(int argc, char** argv) {
                                      subcmd == "--weighted-lineage-pipeline" || subcmd == "--annotations-pipeline" ||
                                      subcmd == "--codon-marginals-pipeline" || subcmd == "--events-pipeline" ||
                                      subcmd == "--ancestral-marginals-pipeline" || subcmd == "--lineage-substitutions-pipeline" ||
-                                     subcmd == "--ancestral-probs-pipeline" || subcmd == "--node-codons-pipeline"))
+                                     subcmd == "--ancestral-probs-pipeline" || subcmd == "--node-codons-pipeline" ||
+                                     subcmd == "--lineage-replacements-pipeline"))
         throw std::invalid_argument(subcmd + " runs on one device: --devices may list only one");
       if (device_list.size() > 1 && subcmd != "--pipeline")
         std::fprintf(stderr, "linearham: %s evaluates on one device; of --devices only device %d is used\n", subcmd.c_str(),
@@ -240,6 +248,11 @@ int main(int argc, char** argv) {
                                            std::stoi(a.opt("frame", "0")));
       return EXIT_SUCCESS;
     }
+    if (subcmd == "--lineage-replacements-pipeline") {
+      phylo_hmm_ptr->RunLineageReplacementsPipeline(a.one("input-path"), a.one("seed-seq"), a.one("output-path"), num_rates,
+                                                    std::stod(a.opt("burnin-frac", "0")), std::stoi(a.opt("frame", "0")));
+      return EXIT_SUCCESS;
+    }
     if (subcmd == "--naive-probs-pipeline") {
       phylo_hmm_ptr->RunNaiveProbsPipeline(a.one("input-path"), a.one("output-path"), num_rates,
                                            std::stod(a.opt("burnin-frac", "0")), a.opt("candidates-path", ""),
@@ -281,6 +294,12 @@ int main(int argc, char** argv) {
       codons_node = linearham::ParseLineageNode(a.one("node"));
       codons_frame = std::stoi(a.opt("frame", "0"));
       if (codons_frame < 0 || codons_frame > 2) throw std::invalid_argument("--frame must be 0, 1 or 2");
+    }
+    // --lineage-replacements: the frame is refused before anything is evaluated
+    int replacements_frame = 0;
+    if (subcmd == "--lineage-replacements") {
+      replacements_frame = std::stoi(a.opt("frame", "0"));
+      if (replacements_frame < 0 || replacements_frame > 2) throw std::invalid_argument("--frame must be 0, 1 or 2");
     }
     phylo_hmm_ptr->InitializePhyloParameters(a.one("newick-path"), a.multi("er"), a.multi("pi"),
                                              std::stod(a.opt("alpha", "1.0")), num_rates);
@@ -334,6 +353,19 @@ int main(int argc, char** argv) {
       linearham::PhyloHMM::WriteNodeAminoAcidTable(std::cout, m);
       std::cout << "\n";
       linearham::PhyloHMM::WriteChangeTable(std::cout, m);
+    } else if (subcmd == "--lineage-replacements") {
+      const linearham::PhyloHMM::LineageReplacementsResult m = phylo_hmm_ptr->LineageReplacements(a.one("seed-seq"), replacements_frame);
+      linearham::PhyloHMM::WriteReplacementTable(std::cout, m);
+      std::cout << "\n";
+      linearham::PhyloHMM::WriteCodonChangeTable(std::cout, m);
+      std::cout << "\n";
+      linearham::PhyloHMM::WriteSeedChangeTable(std::cout, m);
+      std::cout << "\nedge\tupper\tlower\texpected_synonymous\texpected_replacement\n";
+      const std::size_t P = m.nodes.size();
+      for (std::size_t e = 0; e <= P; ++e)
+        std::cout << e << '\t' << (e < P ? std::to_string(m.nodes[e]) : std::string("naive")) << '\t'
+                  << (e == P ? std::to_string(m.nodes[P - 1]) : e == 0 ? a.one("seed-seq") : std::to_string(m.nodes[e - 1])) << '\t'
+                  << linearham::Fmt17(m.edge_load[e][0]) << '\t' << linearham::Fmt17(m.edge_load[e][1]) << '\n';
     } else if (subcmd == "--lineage-substitutions") {
       const linearham::PhyloHMM::LineageSubstitutionsResult m = phylo_hmm_ptr->LineageSubstitutions(a.one("seed-seq"));
       const std::size_t L = (std::size_t)m.n_sites, P = m.nodes.size();

@@ -44,6 +44,7 @@ const DebugOptions& debug_options() {
     o.anc_out_mb = std::max(1, num("LH_ANC_OUT_MB", o.anc_out_mb));
     o.edge_out_mb = std::max(1, num("LH_EDGE_OUT_MB", o.edge_out_mb));
     o.anc_pairs = std::max(0, num("LH_ANC_PAIRS", o.anc_pairs));
+    o.codon_edges_mb = std::max(0, num("LH_CODON_EDGES_MB", o.codon_edges_mb));
     o.collect_hash_bits = std::min(64, std::max(1, num("LH_COLLECT_HASH_BITS", o.collect_hash_bits)));
     return o;
   }();
@@ -263,6 +264,13 @@ struct NodeCodonsWs {  // K14 (lh_node_codon.hip)
   DevBuf out_codons, out_change, out_wcodons, out_wchange;  // the host-pointer form's device copies
 };
 
+struct CodonEdgesWs {  // K15 (lh_codon_edges.hip); K9's outputs and the naive codon posteriors live in NodeCodonsWs
+  DevBuf part, table;  // K15b's partials and K15m's tables of a launch group
+  DevBuf ec_tmp;       // a launch group's edge_change where only edge_load is taken
+  DevBuf cc, aa, sc, partial_c, partial_a, partial_s;  // the batch's rows where the caller does not take them; the slabs
+  DevBuf out_cc, out_aa, out_sc, out_ec, out_el, out_cond, out_wcc, out_waa, out_wsc;  // the host-pointer form's device copies
+};
+
 struct PosteriorWs {  // K5's arrays that the caller of lh_eval_posterior_batch_device does not hand in
   DevBuf loglik, weights, stats, partial;
 };
@@ -447,6 +455,7 @@ struct lh_family {
   EdgesWs edges;
   AncProbsWs probs;
   NodeCodonsWs node_codons;
+  CodonEdgesWs codon_edges;
   // forward arrays that stay on the device, shared by K4 and K5 in both their forms: K4 draws from them, K5 overwrites
   // them with the posteriors (calls on a handle do not overlap: they also share the workspace)
   DevBuf forward_dev;
@@ -471,6 +480,9 @@ struct lh_family {
   KernelTimer<3> node_codons_timer;         // K14's skeleton: K11a, the tables + the contraction, the weighted reduction
   KernelTimer<2> node_codons_stage_timer;   // inside its second stage: the tables (K13's, the naive codons), the contraction
   KernelTimer<1> node_codons_k9_timer;      // K9, in front of K5
+  KernelTimer<3> codon_edges_timer;         // K15's skeleton: K11a, the tables + the contraction, the weighted reduction
+  KernelTimer<2> codon_edges_stage_timer;   // inside its second stage: the tables (K15b, K15m, the naive codons), the contraction
+  KernelTimer<1> codon_edges_k9_timer;      // K9, in front of K5
   KernelTimer<5> chain_timer;               // lh_eval_lineage_batch: K0, K1, K2 + K4 + K6c, K3, K7
   bool extended = false;  // lh_family_set_extended_range
   bool have_sampler = false;
@@ -2861,6 +2873,149 @@ LineageCall node_codons_call(lh_family* f, int P, const double* naive_codons, co
   return {naive_codons, path, P, 0, node_codons_rows(f, true, o)};
 }
 
+// ---- K15: exact amino-acid replacement posteriors along the edges of a seed's lineage (lh_codon_edges.hip) ----
+
+// K15's per-row outputs.  Row 0 as K14's: the eval form's site_base, the given-rates form's naive codon posteriors.
+enum { kCeCounts = 1, kCeAa, kCeSeed, kCeEdgeChange, kCeEdgeLoad, kCeCond };
+std::vector<RowOut> codon_edges_rows(lh_family* f, bool given, int P, const lh_codon_edges_outputs& o, double* cond_edge) {
+  AncestralWs& a = f->anc;
+  CodonEdgesWs& k = f->codon_edges;
+  const size_t L = f->host.n_sites, C = f->codon.n_codons;
+  return {{nullptr, given ? C * 125 : L * 5, nullptr, &a.site_base},
+          {o.codon_counts, C * 4, &k.out_cc, &k.cc, false, o.weighted_codon_counts, &k.partial_c, &k.out_wcc},
+          {o.aa_counts, C * 441, &k.out_aa, &k.aa, false, o.weighted_aa_counts, &k.partial_a, &k.out_waa},
+          {o.seed_change, C * 3, &k.out_sc, &k.sc, false, o.weighted_seed_change, &k.partial_s, &k.out_wsc},
+          {o.edge_change, ((size_t)P + 1) * C * 3, &k.out_ec, nullptr},
+          {o.edge_load, ((size_t)P + 1) * 2, &k.out_el, nullptr},
+          {cond_edge, (size_t)P * L * 80, &k.out_cond, nullptr}};
+}
+
+int codon_edges_check(const lh_family* f, const std::string& W, const TreeBatch& b, int P, int seed_tip) {
+  if (edges_check(f, W, b, P, seed_tip)) return 1;
+  if (f->codon.frame < 0) return fail(W + ": lh_family_set_codons has not been called (no frame set)");
+  return 0;
+}
+
+// samples per launch group of K15, by memory as edges_group and node_codons_group: K11's scratch with K15b's per-slot
+// partials and K15m's tables in place of K11b's (LH_CODON_EDGES_MB: the budget, a test hook)
+size_t codon_edges_group(const lh_family* f, int T, int R, int P) {
+  const lh::AncWsBytes z = lh::anc_ws_bytes(T, f->host.n_sites, R, f->host.n_prune, P);
+  const lh::CondEdgeWsBytes y = lh::cond_edge_ws_bytes(R, f->host.n_prune, P);
+  const size_t per = z.total() - z.part + y.part + y.table + node_codons_bytes(f) + lh::asr_desc_bytes(T) +
+                     eval_bytes_per_sample(f, T, R);
+  const size_t hook = (size_t)lh::debug_options().codon_edges_mb;
+  const size_t budget = hook ? hook << 20 : (size_t)8 << 30;
+  return std::max<size_t>(1, std::min<size_t>({(size_t)kChunk, (size_t)8192, budget / per}));
+}
+
+int codon_edges_workspace(lh_family* f, int chunk, int T, int R, int P, bool given, bool ec_tmp, lh::AncWs* ws) {
+  AncestralWs& a = f->anc;
+  NodeCodonsWs& k = f->node_codons;
+  CodonEdgesWs& e = f->codon_edges;
+  const CodonWs& cw = f->codon;
+  const lh::AncWsBytes z = lh::anc_ws_bytes(T, f->host.n_sites, R, f->host.n_prune, P);
+  const lh::CondEdgeWsBytes y = lh::cond_edge_ws_bytes(R, f->host.n_prune, P);
+  const size_t m = chunk;
+  if (a.clv.ensure(z.clv * m) || a.tvec.ensure(z.tvec * m) || a.rho.ensure(z.rho * m) || a.chain.ensure(z.chain * m) ||
+      a.plen.ensure(sizeof(int32_t) * m) || a.desc.ensure(lh::asr_desc_bytes(T) * m) || e.part.ensure(y.part * m) ||
+      e.table.ensure(y.table * m) ||
+      (ec_tmp && e.ec_tmp.ensure(sizeof(double) * ((size_t)P + 1) * cw.n_codons * 3 * m)))
+    return 1;
+  *ws = {a.clv.get<double>(), e.part.get<double>(), a.tvec.get<double>(), a.rho.get<double>(), a.chain.get<int32_t>(),
+         a.plen.get<int32_t>(), a.desc.get()};
+  if (given) return k.zero.ensure(sizeof(double) * 5 * (size_t)f->host.n_sites * m);
+  return k.windows.ensure(sizeof(double) * 125 * (size_t)cw.tab.n_window * m) ||
+         k.genes.ensure(sizeof(double) * (size_t)cw.tab.n_genes * m) || k.naive.ensure(sizeof(double) * 125 * (size_t)cw.n_codons * m) ||
+         f->codon.scratch.ensure(sizeof(double) * 4 * (size_t)cw.tab.max_vec * lh::codon_slots(chunk));
+}
+
+// K15b + K15m on a launch group, the naive codon posteriors of every codon (as node_codons_launch) and the contraction
+auto codon_edges_launch(lh_family* f, const LineageCall& c, bool given, const double* const* group_ll) {
+  return [f, &c, given, group_ll](const TreeBatch& g, size_t off, const double* rates, const double* naive_prob,
+                                  const lh::AncWs& ws, hipStream_t stream) -> int {
+    Workspace& w = f->ws;
+    NodeCodonsWs& k = f->node_codons;
+    CodonEdgesWs& e = f->codon_edges;
+    KernelTimer<2>& t = f->codon_edges_stage_timer;
+    const std::vector<RowOut>& r = c.rows;
+    const double* site_base = naive_prob;
+    const double* Q = k.naive.get<const double>();
+    if (given) {
+      Q = naive_prob;
+      LH_HIP(hipMemsetAsync(k.zero.get(), 0, sizeof(double) * 5 * (size_t)f->host.n_sites * g.n, stream));
+      site_base = k.zero.get<const double>();
+    }
+    if (f->profile && t.begin(stream)) return 1;
+    if (lh::launch_cond_edges(f->host, g.n, g.R, g.T, g.ops, g.brlen, rates, w.eig.get<double>(), g.pi, w.site_lik.get<double>(),
+                              w.site_scal.get<int32_t>(), site_base, c.path + off * c.P, c.P, c.seed_tip, ws,
+                              e.table.get<double>(), r[kCeCond].group(off), w.prune.hdr, f->err_flag, stream))
+      return 1;
+    if (!given)
+      lh::launch_naive_codons(k.tab, g.n, k.windows.get<const double>(), k.genes.get<const double>(), k.naive.get<double>(), stream);
+    if (f->profile && t.mark(1, stream)) return 1;
+    double *load = r[kCeEdgeLoad].group(off), *ec = r[kCeEdgeChange].group(off);
+    if (load && !ec) ec = e.ec_tmp.get<double>();
+    lh::launch_codon_edges(f->host, g.n, f->codon.n_codons, f->codon.frame, c.P, e.table.get<const double>(), Q, ws.plen,
+                           group_ll ? *group_ll : nullptr, r[kCeCounts].group(off), r[kCeAa].group(off), r[kCeSeed].group(off),
+                           ec, load, stream);
+    if (f->profile && t.end(stream)) return 1;
+    return 0;
+  };
+}
+
+bool codon_edges_tmp(const LineageCall& c) { return c.rows[kCeEdgeLoad].p && !c.rows[kCeEdgeChange].p; }
+
+int eval_codon_edges_device(lh_family* f, const std::string& W, const TreeBatch& b, LineageCall& c, void* hip_stream) {
+  if (ancestral_table(f, W) || node_codons_tables(f, W)) return 1;
+  const int chunk = (int)std::min<size_t>(b.n, std::min(codon_edges_group(f, b.T, b.R, c.P), eval_group(f, b.T, b.R)));
+  lh::AncWs ws;
+  if (ensure_workspace(f, chunk, b.R, b.T) || codon_edges_workspace(f, chunk, b.T, b.R, c.P, false, codon_edges_tmp(c), &ws))
+    return 1;
+  const double* group_ll = nullptr;
+  // K9 reads the forward arrays before K5 smooths them in place
+  c.before_smoothing = [f, &group_ll](int m, size_t, const double* fwd, const double* ll, hipStream_t stream) -> int {
+    NodeCodonsWs& k = f->node_codons;
+    KernelTimer<1>& t = f->codon_edges_k9_timer;
+    group_ll = ll;
+    if (f->profile && t.begin(stream)) return 1;
+    lh::launch_codons(f->sampler_dev, f->codon.tab, m, fwd, f->host.forward_size, ll, f->codon.scratch.get<double>(),
+                      k.windows.get<double>(), k.genes.get<double>(), stream);
+    if (f->profile && t.end(stream)) return 1;
+    return 0;
+  };
+  // K11c and K12c check the paths wherever a table is formed
+  const bool tables = std::any_of(c.rows.begin() + 1, c.rows.end(), [](const RowOut& r) { return r.wanted(); });
+  const int rc = lineage_eval_device(f, W, b, c, chunk, ws, &lh_family::codon_edges_timer, tables, -1, -1, hip_stream,
+                                     codon_edges_launch(f, c, false, &group_ll));
+  c.before_smoothing = nullptr;
+  return rc;
+}
+
+int asr_codon_edges_device(lh_family* f, const std::string& W, const TreeBatch& b, const LineageCall& c, void* hip_stream) {
+  const int chunk = (int)std::min<size_t>(b.n, codon_edges_group(f, b.T, b.R, c.P));
+  lh::AncWs ws;
+  if (ensure_workspace(f, chunk, b.R, b.T) || codon_edges_workspace(f, chunk, b.T, b.R, c.P, true, codon_edges_tmp(c), &ws))
+    return 1;
+  return lineage_asr_device(f, W, b, c, chunk, ws, &lh_family::codon_edges_timer, hip_stream,
+                            codon_edges_launch(f, c, true, nullptr));
+}
+
+LineageCall codon_edges_call(lh_family* f, int P, const int32_t* path, int seed_tip, const lh_codon_edges_outputs* outs) {
+  const lh_codon_edges_outputs o = outs ? *outs : lh_codon_edges_outputs{};
+  return {nullptr, path, P, seed_tip, codon_edges_rows(f, false, P, o, nullptr), o.log_offset, o.loglik, o.weight_stats};
+}
+LineageCall codon_edges_call(lh_family* f, int P, const double* naive_codons, const int32_t* path, int seed_tip,
+                             double* codon_counts, double* aa_counts, double* seed_change, double* edge_change, double* edge_load,
+                             double* cond_edge) {
+  lh_codon_edges_outputs o{};
+  o.codon_counts = codon_counts;
+  o.aa_counts = aa_counts;
+  o.seed_change = seed_change;
+  o.edge_change = edge_change;
+  o.edge_load = edge_load;
+  return {naive_codons, path, P, seed_tip, codon_edges_rows(f, true, P, o, cond_edge)};
+}
+
 }  // namespace
 
 extern "C" {
@@ -3137,6 +3292,94 @@ int lh_node_codons_profile_read(lh_family* f, double* ms, int64_t* n_launches) {
   if (profile_read(f, &lh_family::node_codons_timer, skeleton, n_launches) ||
       profile_read(f, &lh_family::node_codons_stage_timer, stage, nullptr) ||
       profile_read(f, &lh_family::node_codons_k9_timer, &k9, nullptr))
+    return 1;
+  if (ms) {
+    ms[0] = k9 + stage[0];
+    ms[1] = stage[1];
+    ms[2] = skeleton[2];
+  }
+  return 0;
+}
+
+int lh_eval_codon_edges_batch_device(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops,
+                                     const double* brlen, const double* er, const double* pi, const double* alpha, int32_t R,
+                                     const int32_t* path, int32_t P, int32_t seed_tip, const lh_codon_edges_outputs* outs,
+                                     void* hip_stream) {
+  const TreeBatch b{n, T, max_depth, ops, brlen, er, pi, alpha, R};
+  const std::string W = "lh_eval_codon_edges_batch";
+  if (int rc = check_batch(f, W, b, true)) return rc > 0;
+  if (codon_edges_check(f, W, b, P, seed_tip)) return 1;
+  DeviceGuard guard(f);
+  if (!b.has_arrays() || !path) return fail(W + ": null array");
+  LineageCall c = codon_edges_call(f, P, path, seed_tip, outs);
+  return eval_codon_edges_device(f, W, b, c, hip_stream);
+}
+
+int lh_eval_codon_edges_batch(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops, const double* brlen,
+                              const double* er, const double* pi, const double* alpha, int32_t R, const int32_t* path, int32_t P,
+                              int32_t seed_tip, const lh_codon_edges_outputs* outs) {
+  const TreeBatch host{n, T, max_depth, ops, brlen, er, pi, alpha, R};
+  const std::string W = "lh_eval_codon_edges_batch";
+  if (int rc = check_batch(f, W, host, true)) return rc > 0;
+  if (codon_edges_check(f, W, host, P, seed_tip)) return 1;
+  DeviceGuard guard(f);
+  if (!host.has_arrays() || !path) return fail(W + ": null array");
+  const LineageCall c = codon_edges_call(f, P, path, seed_tip, outs);
+  if (!c.asked()) return 0;
+  if (refuse_oversize(W, n, c, lh::debug_options().edge_out_mb)) return 1;  // (K11's rule)
+  return lineage_batch(f, W, host, c, n,
+                       [&](const TreeBatch& dev, LineageCall d) { return eval_codon_edges_device(f, W, dev, d, nullptr); });
+}
+
+int lh_asr_codon_edges_batch_device(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops,
+                                    const double* brlen, const double* er, const double* pi, const double* rates, int32_t R,
+                                    const double* naive_codons, const int32_t* path, int32_t P, int32_t seed_tip,
+                                    double* codon_counts, double* aa_counts, double* seed_change, double* edge_change,
+                                    double* edge_load, double* cond_edge, void* hip_stream) {
+  const TreeBatch b{n, T, max_depth, ops, brlen, er, pi, rates, R, true};
+  const std::string W = "lh_asr_codon_edges_batch";
+  if (int rc = check_batch(f, W, b)) return rc > 0;
+  if (codon_edges_check(f, W, b, P, seed_tip)) return 1;
+  DeviceGuard guard(f);
+  if (!b.has_arrays() || !naive_codons || !path) return fail(W + ": null array");
+  const LineageCall c =
+      codon_edges_call(f, P, naive_codons, path, seed_tip, codon_counts, aa_counts, seed_change, edge_change, edge_load, cond_edge);
+  if (!c.asked()) return 0;  // nothing asked for
+  return asr_codon_edges_device(f, W, b, c, hip_stream);
+}
+
+int lh_asr_codon_edges_batch(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops, const double* brlen,
+                             const double* er, const double* pi, const double* rates, int32_t R, const double* naive_codons,
+                             const int32_t* path, int32_t P, int32_t seed_tip, double* codon_counts, double* aa_counts,
+                             double* seed_change, double* edge_change, double* edge_load, double* cond_edge) {
+  const TreeBatch host{n, T, max_depth, ops, brlen, er, pi, rates, R, true};
+  const std::string W = "lh_asr_codon_edges_batch";
+  if (int rc = check_batch(f, W, host)) return rc > 0;
+  if (codon_edges_check(f, W, host, P, seed_tip)) return 1;
+  DeviceGuard guard(f);
+  if (!host.has_arrays() || !naive_codons || !path) return fail(W + ": null array");
+  const LineageCall c =
+      codon_edges_call(f, P, naive_codons, path, seed_tip, codon_counts, aa_counts, seed_change, edge_change, edge_load, cond_edge);
+  if (!c.asked()) return 0;
+  // no refusal here: sub-batches bound the device copies of the inputs and outputs (as lh_asr_node_codons_batch)
+  const size_t per = c.copy_bytes(true) + c.rows[kSiteBase].bytes(1);
+  const size_t sub = std::max<size_t>(1, std::min<size_t>(n, ((size_t)1 << 30) / std::max<size_t>(per, 1)));
+  return lineage_batch(f, W, host, c, sub, [&](const TreeBatch& dev, const LineageCall& d) {
+    return asr_codon_edges_device(f, W, dev, d, nullptr);
+  });
+}
+
+int lh_codon_edge_symbols(uint8_t* sym) {
+  if (!sym) return fail("lh_codon_edge_symbols: null array");
+  lh::codon_edge_symbols(sym);
+  return 0;
+}
+
+int lh_codon_edges_profile_read(lh_family* f, double* ms, int64_t* n_launches) {
+  double skeleton[3] = {}, stage[2] = {}, k9 = 0.0;
+  if (profile_read(f, &lh_family::codon_edges_timer, skeleton, n_launches) ||
+      profile_read(f, &lh_family::codon_edges_stage_timer, stage, nullptr) ||
+      profile_read(f, &lh_family::codon_edges_k9_timer, &k9, nullptr))
     return 1;
   if (ms) {
     ms[0] = k9 + stage[0];

@@ -565,6 +565,36 @@ void launch_node_codons(const DevFamily& fam, int n, int n_codons, int frame, co
 // triple, node triple) pair, from the kernel's compile-time relation
 void node_codon_classes(uint8_t* out);
 
+// K12c alone (lh_substitutions.hip), behind launch_ancestral_front: the seed tip must be a child of v_0 under the sample's own
+// schedule; slot 0's chain word is marked with which child it is, a failure leaves plen 0 and raises bit 1 of *err_flag.
+void launch_sub_seed(int n, int T, int P, int seed_tip, const void* desc, int32_t* chain, int32_t* plen, int32_t* err_flag,
+                     hipStream_t stream);
+
+// K15 (lh_codon_edges.hip): exact joint posteriors of a codon at the two ends of every edge of a seed's lineage, folded to
+// amino-acid replacements.
+// K15b + K15m behind launch_ancestral_front and K12c: table[n][P][n_prune + 1][5][4][4], H_s[pattern][naive base b][a][c] =
+// P(x_{v_s} = a, x_below = c | column of the pattern, naive base b) (padding slots 0, NaN for a sample without a valid path
+// or seed: *err_flag raised, ws.plen 0); cond_edge[n][P][n_sites][5][4][4] (may be null) is the same per site.  Scratch:
+// AncWs with `part` sized by cond_edge_ws_bytes.  Returns nonzero if the launch cannot be made (LDS tables, grid).
+struct CondEdgeWsBytes {
+  size_t part, table;  // per sample
+};
+CondEdgeWsBytes cond_edge_ws_bytes(int R, int n_prune, int P);
+int launch_cond_edges(const DevFamily& fam, int n, int R, int T, const int32_t* ops, const double* brlen, const double* rates,
+                      const double* eig, const double* pi, const double* site_lik, const int32_t* site_scal,
+                      const double* naive_prob, const int32_t* path, int P, int seed_tip, const AncWs& ws, double* table,
+                      double* cond_edge, const int4* hdr, int32_t* err_flag, hipStream_t stream);
+// K15 from Q[n][n_codons][125] and K15m's table; every output may be null (edge_load needs edge_change):
+// codon_counts[n][n_codons][4], aa_counts[n][n_codons][21][21], seed_change[n][n_codons][3], edge_change[n][P+1][n_codons][3]
+// (entry P the naive edge, padding slots 0), edge_load[n][P+1][2].  NaN for a row whose plen is 0 or whose loglik (null: not
+// looked at) is not finite.
+void launch_codon_edges(const DevFamily& fam, int n, int n_codons, int frame, int P, const double* table, const double* Q,
+                        const int32_t* plen, const double* loglik, double* codon_counts, double* aa_counts,
+                        double* seed_change, double* edge_change, double* edge_load, hipStream_t stream);
+// out[64]: the symbol 0 .. 20 (position in "ACDEFGHIKLMNPQRSTVWY*") of every triple 16 x1 + 4 x2 + x3, the kernel's
+// compile-time map
+void codon_edge_symbols(uint8_t* out);
+
 // K2a + K2b.  site_lik != null: emissions are assembled from K1's output (rate mix and naive
 // correction; optionally written to em_out[n][C]); site_lik == null: emissions are taken from
 // em_in[n][C].  K2a leaves the germline/padding emission products in gem[n][gem_size], their scaler
@@ -649,6 +679,8 @@ struct DebugOptions {
   int edge_out_mb = 4096;      // LH_EDGE_OUT_MB=<n>: the same bound for lh_asr_edges_batch and lh_eval_edges_batch
   int anc_pairs = 0;           // LH_ANC_PAIRS=<n>: (row, candidate) pairs per sweep of lh_eval_ancestral_candidates_batch (0,
                                // unset: by memory; tests: a group cuts rows and candidates in a small call)
+  int codon_edges_mb = 0;      // LH_CODON_EDGES_MB=<n>: MiB of scratch a launch group of lh_eval_codon_edges_batch and
+                               // lh_asr_codon_edges_batch may take (0, unset: 8 GiB; tests: several groups in a small call)
   int collect_hash_bits = 64;  // LH_COLLECT_HASH_BITS=<n>: K6c's row hashes masked to n bits (tests: collisions common,
                                // the exact resolution runs; results unchanged)
 };

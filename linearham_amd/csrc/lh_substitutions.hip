@@ -282,6 +282,12 @@ SubWsBytes sub_ws_bytes(int L, int R, int P) {
   return b;
 }
 
+void launch_sub_seed(int n, int T, int P, int seed_tip, const void* desc, int32_t* chain, int32_t* plen, int32_t* err_flag,
+                     hipStream_t stream) {
+  hipLaunchKernelGGL(sub_seed_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, n, T, P, seed_tip,
+                     static_cast<const AsrOp*>(desc), chain, plen, err_flag);
+}
+
 int launch_substitutions(const DevFamily& fam, int n, int R, int T, const int32_t* ops, const double* brlen, const double* rates,
                          const double* eig, const double* pi, const double* site_lik, const int32_t* site_scal,
                          const double* naive_prob, const int32_t* path, int P, int seed_tip, const AncWs& ws, const SubWs& sws,

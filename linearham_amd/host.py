@@ -169,6 +169,60 @@ def node_codons_write(codons, change, frame=0):
     return out.value.decode()
 
 
+def parse_lineage_replacements(text):
+    """dict(aa_counts [n_codons][21][21] -- the off-diagonal cells, the diagonal is not written --, codon_counts
+    [n_codons][4], seed_change [n_codons][3]) from the three tables WriteReplacementTable, WriteCodonChangeTable and
+    WriteSeedChangeTable print, separated by blank lines.  Amino acids are indexed by posterior.AA_SYMBOLS."""
+    import numpy as np
+    from .posterior import AA_SYMBOLS
+    rep, chg, seed = text.strip("\n").split("\n\n")[:3]
+    lines = [ln.split("\t") for ln in chg.strip("\n").split("\n")]
+    assert lines[0] == ["codon", "unchanged", "synonymous", "replacement", "undetermined"], lines[0]
+    counts = np.array([[float(x) for x in ln[1:]] for ln in lines[1:]]).reshape(-1, 4)
+    assert [int(ln[0]) for ln in lines[1:]] == list(range(len(counts)))
+    lines = [ln.split("\t") for ln in seed.strip("\n").split("\n")]
+    assert lines[0] == ["codon", "unchanged", "synonymous", "replacement"], lines[0]
+    seed_change = np.array([[float(x) for x in ln[1:]] for ln in lines[1:]]).reshape(-1, 3)
+    rows = [ln.split("\t") for ln in rep.strip("\n").split("\n")]
+    assert rows[0] == ["codon", "first_site", "from", "to", "expected_edges"], rows[0]
+    aa = np.zeros((len(counts), 21, 21))
+    for c, _, x, y, v in rows[1:]:
+        aa[int(c), AA_SYMBOLS.index(x), AA_SYMBOLS.index(y)] = float(v)
+    return dict(aa_counts=aa, codon_counts=counts, seed_change=seed_change)
+
+
+def read_lineage_replacements(prefix):
+    """The files of PhyloHMM::RunLineageReplacementsPipeline: parse_lineage_replacements' dict plus rows [(row, weight,
+    chain_length, expected_synonymous, expected_replacement)] and summary."""
+    res = parse_lineage_replacements("\n".join(open(prefix + ext).read()
+                                               for ext in (".replacements.tsv", ".codon_changes.tsv", ".seed_edge.tsv")))
+    rows = [ln.split("\t") for ln in open(prefix + ".rows.tsv").read().strip().split("\n")]
+    assert rows[0] == ["row", "weight", "chain_length", "expected_synonymous", "expected_replacement"]
+    res["rows"] = [(int(r[0]), float(r[1]), int(r[2]), float(r[3]), float(r[4])) for r in rows[1:]]
+    summary = {}
+    for ln in open(prefix + ".summary.tsv").read().strip().split("\n")[1:]:
+        k, v = ln.split("\t")
+        summary[k] = int(v) if k in ("rows_used", "rows_skipped_nonfinite", "frame") else float(v)
+    res["summary"] = summary
+    return res
+
+
+def lineage_replacements_write(codon_counts, aa_counts, seed_change, frame=0):
+    """The host writers on caller tables codon_counts [n_codons][4], aa_counts [n_codons][21][21] and seed_change
+    [n_codons][3]: the three texts joined by blank lines (parse_lineage_replacements reads them back)."""
+    import numpy as np
+    cc = np.ascontiguousarray(codon_counts, dtype=np.float64)
+    aa = np.ascontiguousarray(aa_counts, dtype=np.float64)
+    sc = np.ascontiguousarray(seed_change, dtype=np.float64)
+    n = cc.shape[0]
+    assert cc.shape == (n, 4) and aa.shape == (n, 21, 21) and sc.shape == (n, 3)
+    lib = load_host()
+    lib.lhh_write_lineage_replacements.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_char_p)]
+    out = C.c_char_p()
+    _check(lib.lhh_write_lineage_replacements(cc.ctypes.data, aa.ctypes.data, sc.ctypes.data, n, frame, C.byref(out)))
+    return out.value.decode()
+
+
 def parse_lineage_node(name):
     """--node's values: "parent" -> 0 (the seed's parent), "mrca" -> 1 (linearham::ParseLineageNode)."""
     lib = load_host()
@@ -634,6 +688,42 @@ class PhyloHMM(_HMM):
         _check(self.lib.lhh_run_node_codons_pipeline(self.h, input_path.encode(), seed_seq.encode(), node, output_prefix.encode(),
                                                      num_rates, C.c_double(burnin_frac), frame))
         return read_node_codons(output_prefix)
+
+    def lineage_replacements(self, seed_seq, frame=0):
+        """PhyloHMM::LineageReplacements of the current tree: dict(nodes [P] -- the lineage of the tip `seed_seq`, slot 0 its
+        parent --, codon_counts [n_codons][4], aa_counts [n_codons][21][21], seed_change [n_codons][3], edge_change
+        [P + 1][n_codons][3] and edge_load [P + 1][2] (the last entry the naive edge), loglik, text as the writers print the
+        first three)."""
+        lib = self.lib
+        lib.lhh_phylo_lineage_replacements.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int),
+                                                       C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_char_p)]
+        nc, ne, ll, text = C.c_int(), C.c_int(), C.c_double(), C.c_char_p()
+        _check(lib.lhh_phylo_lineage_replacements(self.h, seed_seq.encode(), frame, None, None, None, 0, None, None, None, 0,
+                                                  C.byref(nc), C.byref(ne), None, None))
+        n = nc.value
+        cc, aa, sc = np.zeros((n, 4)), np.zeros((n, 21, 21)), np.zeros((n, 3))
+        cap = 64
+        while True:  # (the chain's length is known once the tree has been evaluated: a longer one is fetched again)
+            ec, el, nodes = np.zeros((cap, n, 3)), np.zeros((cap, 2)), np.zeros(cap, dtype=np.int32)
+            _check(lib.lhh_phylo_lineage_replacements(self.h, seed_seq.encode(), frame, cc.ctypes.data, aa.ctypes.data,
+                                                      sc.ctypes.data, n, ec.ctypes.data, el.ctypes.data, nodes.ctypes.data, cap,
+                                                      C.byref(nc), C.byref(ne), C.byref(ll), C.byref(text)))
+            if ne.value <= cap:
+                break
+            cap = ne.value
+        E = ne.value
+        return dict(nodes=nodes[:E - 1].tolist(), codon_counts=cc, aa_counts=aa, seed_change=sc, edge_change=ec[:E],
+                    edge_load=el[:E], loglik=ll.value, text=text.value.decode())
+
+    def run_lineage_replacements_pipeline(self, input_path, seed_seq, output_prefix, num_rates, burnin_frac=0.0, frame=0):
+        """PhyloHMM::RunLineageReplacementsPipeline: the importance-weighted amino-acid replacement, codon change and seed-edge
+        tables of the seed's lineage over a RevBayes table; returns read_lineage_replacements(output_prefix)."""
+        self.lib.lhh_run_lineage_replacements_pipeline.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int,
+                                                                   C.c_double, C.c_int]
+        _check(self.lib.lhh_run_lineage_replacements_pipeline(self.h, input_path.encode(), seed_seq.encode(),
+                                                              output_prefix.encode(), num_rates, C.c_double(burnin_frac), frame))
+        return read_lineage_replacements(output_prefix)
 
     def lineage_substitutions(self, seed_seq):
         """PhyloHMM::LineageSubstitutions of the current tree: dict(nodes [P] -- the lineage of the tip `seed_seq`, slot 0 its

@@ -305,3 +305,23 @@ def change_classes(aa_of_codon=None):
         for x in range(64):
             out[i, x] = 0 if x == k else 1 if aa[x] == aa[k] else 2
     return out
+
+
+# ---- K15: amino-acid replacements along the edges of a seed's lineage ----
+AA_SYMBOLS = "ACDEFGHIKLMNPQRSTVWY*"  # the 21 symbols of aa_counts (capi.AA_SYMBOLS), the stop codons a symbol of their own
+
+
+def aa_symbols(aa_of_codon=None):
+    """[64] uint8: the symbol (index into AA_SYMBOLS) of every triple 16 x1 + 4 x2 + x3, from the host library's
+    TranslateDna.  The device carries the same map as a compile-time table (capi.HipLibrary.codon_edge_symbols)."""
+    aa = aa_of_codon or node_codon_amino_acids()
+    return np.array([AA_SYMBOLS.index(a) for a in aa], dtype=np.uint8)
+
+
+def edge_classes(aa_of_codon=None):
+    """[64][64] uint8, the class of an inner edge by its (upper triple, lower triple): 0 the same triple, 1 another triple
+    with the same translation, 2 a different translation."""
+    sym = aa_symbols(aa_of_codon)
+    out = np.where(sym[:, None] == sym[None, :], 1, 2).astype(np.uint8)
+    out[np.arange(64), np.arange(64)] = 0
+    return out
