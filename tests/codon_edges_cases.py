@@ -42,6 +42,13 @@ class CodonEdgesCase(NodeCodonsCase):
         return ceo.cond_edges(children, root, brlen, self.T, self.o.msa, r["er"], pi, rates, path, tip, pre=pre)
 
 
+def dirichlet_codons(rng, shape):
+    """Naive codon posteriors [shape][125] for the given-rates forms: sparse Dirichlet rows, entries below 1e-3 set to 0."""
+    dq = rng.dirichlet(np.ones(125) * 0.05, size=shape)
+    dq[dq < 1e-3] = 0.0
+    return dq / dq.sum(axis=-1, keepdims=True)
+
+
 def compare(got, i, want):
     """The largest difference of row i of the device's five tables from the oracle's dict."""
     return max(np.abs(got[k][i] - want[k]).max() for k in TABLES)

@@ -19,6 +19,7 @@ from tests import ancestral_probs_oracle as apo
 from tests import codon_edge_oracle as ceo
 from tests.ancestral_cases import BOUND
 from tests.codon_edges_cases import TABLES, check, rules, synth, toy_case
+from tests.codon_edges_cases import dirichlet_codons as _dirichlet
 from tests.node_codons_cases import MRCA, PARENT
 
 pytestmark = pytest.mark.gpu
@@ -115,12 +116,6 @@ def test_many_allele_family(hip, tmp_path):
 
 
 # ---- the given-rates form ----
-
-def _dirichlet(rng, shape):
-    dq = rng.dirichlet(np.ones(125) * 0.05, size=shape)
-    dq[dq < 1e-3] = 0.0
-    return dq / dq.sum(axis=-1, keepdims=True)
-
 
 def test_more_than_256_patterns(hip, tmp_path):
     """A 20-leaf family of 340 sites with more than 256 site patterns, so K15b's pattern loop makes a second trip per wave;
