@@ -5,7 +5,11 @@ the MRCA), beside the forward sweep's time per evaluation (lh_profile_read) and 
 (lh_eval_ancestral_batch_device) in the same run.  Not the headline metric (bench.py is); prints one JSON line.
 
   python bench_ancestral_probs.py [--batch 4096] [--candidates 64] [--steps 3] [--warmup 1] [--preset config2|small]
-                                  [--seed-tip 1] [--out <file>]
+                                  [--seed-tip 1] [--with-tip <tip>] [--alternations 5] [--out <file>]
+
+--with-tip names a second tip: the run then also times the slot form (lh_eval_ancestral_candidates_at_batch_device) at the
+most recent common ancestor of the two tips, a slot of its own per row, and reports the table time of the three forms over
+--alternations rounds of parent, MRCA, slot in turn after the warm-up, with the mean and range of the slots.
 
 The candidates are distinct MRCA sequences of the family's own ancestral draws (lh_eval_draw_batch, lh_naive_sequences,
 lh_asr_batch).  Each step scores every candidate on `batch` distinct tree samples -- batch x candidates forward sweeps --
@@ -31,6 +35,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--preset", default="config2", choices=["config2", "small"])
     ap.add_argument("--seed-tip", type=int, default=1)
+    ap.add_argument("--with-tip", type=int, default=0, help="a second tip: also time K13 at its common ancestor with the seed")
+    ap.add_argument("--alternations", type=int, default=5, help="rounds of parent, MRCA, slot in turn (with --with-tip)")
     ap.add_argument("--check", type=int, default=2, help="candidates of row 0 checked against the oracle")
     ap.add_argument("--out", default="", help="also write the JSON line to this file")
     args = ap.parse_args()
@@ -57,13 +63,15 @@ def main():
     labels = list(o.xmsa_labels)
     T, R, L = len(labels), 4, o.msa.shape[1]
     rows = sf.read_trees_tsv(tsv)
-    ops, brl, paths, trees, depth = [], [], [], [], 0
+    ops, brl, paths, trees, depth, slots = [], [], [], [], 0, []
     for i in range(n):
         r = rows[i % len(rows)]
         children, root, brlen = host.newick_arrays(r["tree"], labels)
         op, dp = lib.schedule_tree(T, children, root)
         ops.append(op), brl.append(brlen), paths.append(capi.seed_path(T, children, root, args.seed_tip))
         trees.append((children, root, brlen))
+        if args.with_tip:
+            slots.append(capi.clade_slot(T, children, root, args.seed_tip, [args.with_tip])[1])
         depth = max(depth, dp)
     path = capi.pad_paths(paths)
     P = path.shape[1]
@@ -128,6 +136,34 @@ def main():
                           "ms_per_49152_pairs": pairs / args.steps / (n * K) * 49152,
                           "launch_groups_per_step": groups / args.steps,
                           "weighted_sum_total": float(outs["weighted_sum"].sum().item())}
+    # the three forms of the tables in turn: ms[0] of the profile reader, one step per reading
+    forms = None
+    if args.with_tip:
+        d["slot"] = t(slots, np.int32)
+        calls = {"parent": lambda: lib.eval_ancestral_candidates_batch_device(fam, n, T, depth, *tree_ptrs, R, d["path"].data_ptr(),
+                                                                             P, capi.NODE_PARENT, out_ptrs, stream),
+                 "mrca": lambda: lib.eval_ancestral_candidates_batch_device(fam, n, T, depth, *tree_ptrs, R, d["path"].data_ptr(),
+                                                                           P, capi.NODE_MRCA, out_ptrs, stream),
+                 "slot": lambda: lib.eval_ancestral_candidates_at_batch_device(fam, n, T, depth, *tree_ptrs, R,
+                                                                              d["path"].data_ptr(), P, d["slot"].data_ptr(),
+                                                                              out_ptrs, stream)}
+        for step in calls.values():
+            for _ in range(max(args.warmup, 1)):
+                step()
+        torch.cuda.synchronize()
+        lib.check(lib.lib.lh_family_status(fam))
+        forms = {k: [] for k in calls}
+        for _ in range(args.alternations):
+            for name, step in calls.items():
+                lib.check(lib.lib.lh_profile_enable(fam, 1))
+                step()
+                torch.cuda.synchronize()
+                lib.check(lib.lib.lh_profile_enable(fam, 0))
+                forms[name].append(lib.ancestral_candidates_profile_read(fam)[0])
+        lens = np.array([len(p) for p in paths])
+        forms = {"tables_ms": forms, "with_tip": args.with_tip,
+                 "slots": {"mean": float(np.mean(slots)), "min": int(min(slots)), "max": int(max(slots))},
+                 "down_steps_mean": {"parent": float(np.mean(lens - 1)), "mrca": 0.0, "slot": float(np.mean(lens - 1 - np.array(slots)))}}
     # the forward sweep of a plain evaluation of the same rows
     eo = capi._EvalOutputs()
     dt = timed(lambda: lib.check(lib.lib.lh_eval_batch_device(fam, n, T, depth, *tree_ptrs, R, outs["loglik"].data_ptr(),
@@ -170,6 +206,8 @@ def main():
            "k11b_ms_per_step": k11b / args.steps,
            "kish_ess": float(st[1] * st[1] / st[2]) if st[2] > 0 else 0.0,
            "parity": {"candidates": args.check, "max_abs_err": worst}}
+    if forms:
+        out["forms"] = forms
     line = json.dumps(out)
     print(line, flush=True)
     if args.out:

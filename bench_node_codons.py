@@ -6,7 +6,10 @@ contraction, the weighted reduction -- beside K9's own time on the same rows (lh
 sweep's (lh_profile_read) in the same run.  Not the headline metric (bench.py is); prints one JSON line.
 
   python bench_node_codons.py [--batch 4096] [--steps 3] [--warmup 1] [--preset config2|small] [--seed-tip 1] [--frame 0]
-                              [--out <file>]
+                              [--with-tip <tip>] [--out <file>]
+
+--with-tip names a second tip: the run then also times the slot form (lh_eval_node_codons_at_batch_device) at the most
+recent common ancestor of the two tips, a slot of its own per row, and reports it beside the two fixed nodes.
 
 One row is checked against tests/node_codon_oracle.py outside the timed loop."""
 import argparse
@@ -28,6 +31,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--preset", default="config2", choices=["config2", "small"])
     ap.add_argument("--seed-tip", type=int, default=1)
+    ap.add_argument("--with-tip", type=int, default=0, help="a second tip: also time K14 at its common ancestor with the seed")
     ap.add_argument("--frame", type=int, default=0)
     ap.add_argument("--out", default="", help="also write the JSON line to this file")
     args = ap.parse_args()
@@ -54,13 +58,15 @@ def main():
     labels = list(o.xmsa_labels)
     T, R, L = len(labels), 4, o.msa.shape[1]
     rows = sf.read_trees_tsv(tsv)
-    ops, brl, paths, trees, depth = [], [], [], [], 0
+    ops, brl, paths, trees, depth, slots = [], [], [], [], 0, []
     for i in range(n):
         r = rows[i % len(rows)]
         children, root, brlen = host.newick_arrays(r["tree"], labels)
         op, dp = lib.schedule_tree(T, children, root)
         ops.append(op), brl.append(brlen), paths.append(capi.seed_path(T, children, root, args.seed_tip))
         trees.append((children, root, brlen))
+        if args.with_tip:
+            slots.append(capi.clade_slot(T, children, root, args.seed_tip, [args.with_tip])[1])
         depth = max(depth, dp)
     path = capi.pad_paths(paths)
     P = path.shape[1]
@@ -96,9 +102,15 @@ def main():
         return dt
 
     per_node = {}
-    for name, node in (("parent", capi.NODE_PARENT), ("mrca", capi.NODE_MRCA)):
-        dt = timed(lambda: lib.eval_node_codons_batch_device(fam, n, T, depth, *tree_ptrs, R, d["path"].data_ptr(), P, node,
-                                                             out_ptrs, stream))
+    if args.with_tip:
+        d["slot"] = t(slots, np.int32)
+    for name, node in (("parent", capi.NODE_PARENT), ("mrca", capi.NODE_MRCA)) + ((("slot", None),) if args.with_tip else ()):
+        if node is None:
+            dt = timed(lambda: lib.eval_node_codons_at_batch_device(fam, n, T, depth, *tree_ptrs, R, d["path"].data_ptr(), P,
+                                                                    d["slot"].data_ptr(), out_ptrs, stream))
+        else:
+            dt = timed(lambda: lib.eval_node_codons_batch_device(fam, n, T, depth, *tree_ptrs, R, d["path"].data_ptr(), P, node,
+                                                                 out_ptrs, stream))
         tables, contraction, red, groups = lib.node_codons_profile_read(fam)
         per_node[name] = {"rows_per_s": n * args.steps / dt, "ms_per_step": dt / args.steps * 1e3,
                           "kernel_ms_per_step": {"K9 + tables": tables / args.steps, "contraction": contraction / args.steps,
@@ -152,6 +164,9 @@ def main():
            "k9_alone_ms_per_step": k9_ms, "forward_K2_ms_per_step": ms[2].value / args.steps,
            "kish_ess": float(st[1] * st[1] / st[2]) if st[2] > 0 else 0.0,
            "parity": {"max_abs_err": worst}}
+    if args.with_tip:
+        out["slot"] = dict(per_node["slot"], with_tip=args.with_tip,
+                           slots={"mean": float(np.mean(slots)), "min": int(min(slots)), "max": int(max(slots))})
     line = json.dumps(out)
     print(line, flush=True)
     if args.out:

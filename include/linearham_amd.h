@@ -488,8 +488,9 @@ int lh_eval_batch_device(lh_family* fam, int32_t n, int32_t n_tips, int32_t max_
                          const lh_eval_outputs* outs, void* hip_stream);
 
 /* Synchronises the handle's device, then reports and clears its asynchronous error state: nonzero (message in
- * lh_last_error) if a launch since the previous call met a malformed schedule.  The host-pointer entry points
- * call it themselves before they return. */
+ * lh_last_error) if a launch since the previous call met a malformed schedule, a lineage path that is not a chain, or
+ * (the `_at` entry points of K13 and K14) a slot outside its path: that message names the first such row of its call and
+ * takes the place of the path's.  The host-pointer entry points call it themselves before they return. */
 int lh_family_status(lh_family* fam);
 
 /* Forward pass only, on caller-supplied per-column emissions em[n][C] (host pointers). */
@@ -755,6 +756,23 @@ int lh_eval_ancestral_candidates_batch_device(lh_family* fam, int32_t n, int32_t
                                               const double* alpha, int32_t num_rates, const int32_t* path, int32_t path_len,
                                               int32_t node, const lh_ancestral_candidates_outputs* outs, void* hip_stream);
 
+/* The same at a node per row: slot[n] names, for every sample, the entry of its own path the tables are formed at,
+ * 0 <= slot[i] < the length of path i (0 is the seed's parent, the last one the MRCA; both give the bits of node 0 and 1).
+ * The use is a node that means the same in every tree sample though its slot does not: the most recent common ancestor of
+ * the seed and other tips (lhh_clade_slot gives the slot).  K13b's walk down the lineage stops at the row's slot.  The
+ * host-pointer form refuses a batch with a slot outside its path, naming the row; the device form gives that row NaN and
+ * no weight and raises a bit of its own in the handle's error word (lh_family_status names the first such row).
+ * Everything else, the refusal of an extended-range handle included, is lh_eval_ancestral_candidates_batch's. */
+int lh_eval_ancestral_candidates_at_batch(lh_family* fam, int32_t n, int32_t n_tips, int32_t max_depth, const int32_t* ops,
+                                          const double* brlen, const double* er, const double* pi, const double* alpha,
+                                          int32_t num_rates, const int32_t* path, int32_t path_len,
+                                          const int32_t* slot /* [n] */, const lh_ancestral_candidates_outputs* outs);
+int lh_eval_ancestral_candidates_at_batch_device(lh_family* fam, int32_t n, int32_t n_tips, int32_t max_depth,
+                                                 const int32_t* ops, const double* brlen, const double* er, const double* pi,
+                                                 const double* alpha, int32_t num_rates, const int32_t* path,
+                                                 int32_t path_len, const int32_t* slot /* [n] */,
+                                                 const lh_ancestral_candidates_outputs* outs, void* hip_stream);
+
 /* Times of K13 over the launches made while profiling was enabled (HIP events on the launch stream), ms[3]: the tables
  * (rate weights, path check, K13b, rate combination), the pair emissions with their sweeps, the weighted reduction; resets
  * the counters. */
@@ -818,6 +836,25 @@ int lh_asr_node_codons_batch_device(lh_family* fam, int32_t n, int32_t n_tips, i
                                     const double* brlen, const double* er, const double* pi, const double* rates,
                                     int32_t num_rates, const double* naive_codons, const int32_t* path, int32_t path_len,
                                     int32_t node, double* codons, double* change, void* hip_stream);
+
+/* K14 at a node per row, slot[n] as lh_eval_ancestral_candidates_at_batch takes it (the same checks and error word);
+ * everything else is the `node` forms'.  They honour lh_family_set_extended_range as those do. */
+int lh_eval_node_codons_at_batch(lh_family* fam, int32_t n, int32_t n_tips, int32_t max_depth, const int32_t* ops,
+                                 const double* brlen, const double* er, const double* pi, const double* alpha,
+                                 int32_t num_rates, const int32_t* path, int32_t path_len, const int32_t* slot /* [n] */,
+                                 const lh_node_codons_outputs* outs);
+int lh_eval_node_codons_at_batch_device(lh_family* fam, int32_t n, int32_t n_tips, int32_t max_depth, const int32_t* ops,
+                                        const double* brlen, const double* er, const double* pi, const double* alpha,
+                                        int32_t num_rates, const int32_t* path, int32_t path_len,
+                                        const int32_t* slot /* [n] */, const lh_node_codons_outputs* outs, void* hip_stream);
+int lh_asr_node_codons_at_batch(lh_family* fam, int32_t n, int32_t n_tips, int32_t max_depth, const int32_t* ops,
+                                const double* brlen, const double* er, const double* pi, const double* rates,
+                                int32_t num_rates, const double* naive_codons, const int32_t* path, int32_t path_len,
+                                const int32_t* slot /* [n] */, double* codons, double* change);
+int lh_asr_node_codons_at_batch_device(lh_family* fam, int32_t n, int32_t n_tips, int32_t max_depth, const int32_t* ops,
+                                       const double* brlen, const double* er, const double* pi, const double* rates,
+                                       int32_t num_rates, const double* naive_codons, const int32_t* path, int32_t path_len,
+                                       const int32_t* slot /* [n] */, double* codons, double* change, void* hip_stream);
 
 /* classes[125][64]: the class 0 .. 3 (the entries of change) of every (naive triple, node triple) pair, as the kernel's
  * compile-time table has it. */

@@ -92,12 +92,15 @@ EXPORTS += EDGES_EXPORTS
 # K13 (exact posterior probabilities of candidate ancestral sequences)
 ANCESTRAL_PROBS_EXPORTS = ["lh_family_set_ancestral_candidates", "lh_ancestral_candidates_info",
                            "lh_eval_ancestral_candidates_batch", "lh_eval_ancestral_candidates_batch_device",
-                           "lh_ancestral_candidates_profile_read"]
+                           "lh_ancestral_candidates_profile_read", "lh_eval_ancestral_candidates_at_batch",
+                           "lh_eval_ancestral_candidates_at_batch_device"]
 EXPORTS += ANCESTRAL_PROBS_EXPORTS
 NODE_PARENT, NODE_MRCA = 0, 1  # lh_eval_ancestral_candidates_batch's `node`
 # K14 (exact codon marginals of a node of a seed's lineage)
 NODE_CODONS_EXPORTS = ["lh_eval_node_codons_batch", "lh_eval_node_codons_batch_device", "lh_asr_node_codons_batch",
-                       "lh_asr_node_codons_batch_device", "lh_node_codon_classes", "lh_node_codons_profile_read"]
+                       "lh_asr_node_codons_batch_device", "lh_node_codon_classes", "lh_node_codons_profile_read",
+                       "lh_eval_node_codons_at_batch", "lh_eval_node_codons_at_batch_device", "lh_asr_node_codons_at_batch",
+                       "lh_asr_node_codons_at_batch_device"]
 EXPORTS += NODE_CODONS_EXPORTS
 # K15 (exact amino-acid replacement posteriors along the edges of a seed's lineage)
 CODON_EDGES_EXPORTS = ["lh_eval_codon_edges_batch", "lh_eval_codon_edges_batch_device", "lh_asr_codon_edges_batch",
@@ -383,6 +386,17 @@ class HipLibrary:
             lib.lh_eval_ancestral_candidates_batch_device.argtypes = _DEV_TREE + [
                 C.c_void_p, C.c_int32, C.c_int32, C.POINTER(_AncestralProbsOutputsDevice), C.c_void_p]
             lib.lh_ancestral_candidates_profile_read.argtypes = _PROFILE_READ
+        if hasattr(lib, "lh_eval_ancestral_candidates_at_batch"):  # (the slot array in the place of `node`)
+            lib.lh_eval_ancestral_candidates_at_batch.argtypes = _HOST_TREE + [c_i32p, C.c_int32, c_i32p,
+                                                                               C.POINTER(_AncestralProbsOutputs)]
+            lib.lh_eval_ancestral_candidates_at_batch_device.argtypes = _DEV_TREE + [
+                C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(_AncestralProbsOutputsDevice), C.c_void_p]
+            lib.lh_eval_node_codons_at_batch.argtypes = _HOST_TREE + [c_i32p, C.c_int32, c_i32p, C.POINTER(_NodeCodonsOutputs)]
+            lib.lh_eval_node_codons_at_batch_device.argtypes = _DEV_TREE + [
+                C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(_NodeCodonsOutputsDevice), C.c_void_p]
+            lib.lh_asr_node_codons_at_batch.argtypes = _HOST_TREE + [c_f64p, c_i32p, C.c_int32, c_i32p, c_f64p, c_f64p]
+            lib.lh_asr_node_codons_at_batch_device.argtypes = _DEV_TREE + [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p] + \
+                [C.c_void_p] * 3
         if hasattr(lib, "lh_eval_node_codons_batch"):
             lib.lh_eval_node_codons_batch.argtypes = _HOST_TREE + [c_i32p, C.c_int32, C.c_int32,
                                                                    C.POINTER(_NodeCodonsOutputs)]
@@ -494,6 +508,19 @@ class HipLibrary:
         """K0-K2 + K5 + K13 on a family handle that has sampler tables and ancestral candidates; path [n][P] (seed_path
         rows, -1 padding), node NODE_PARENT or NODE_MRCA.  Returns a dict with the members of `want`: loglik [n], cond
         [n, L, 5, 4] (P(x_node = c | column, naive base b)), log_cand [n, K], weighted_sum [K], weight_stats [3]."""
+        return self._eval_ancestral_candidates("lh_eval_ancestral_candidates_batch", family, n_tips, max_depth, ops, brlen,
+                                               er, pi, alpha, num_rates, path, node, log_offset, want)
+
+    def eval_ancestral_candidates_at_batch(self, family, n_tips, max_depth, ops, brlen, er, pi, alpha, num_rates, path, slot,
+                                           log_offset=None, want=("loglik", "cond", "log_cand", "weighted_sum",
+                                                                  "weight_stats")):
+        """eval_ancestral_candidates_batch at a node per row: slot [n], for every sample the entry of its own path the
+        tables are formed at (clade_slot gives it for the common ancestor of the seed and other tips)."""
+        return self._eval_ancestral_candidates("lh_eval_ancestral_candidates_at_batch", family, n_tips, max_depth, ops,
+                                               brlen, er, pi, alpha, num_rates, path, _slots(slot), log_offset, want)
+
+    def _eval_ancestral_candidates(self, entry, family, n_tips, max_depth, ops, brlen, er, pi, alpha, num_rates, path, node,
+                                   log_offset, want):
         h = _handle(family)
         n, arrays = _tree_args(ops, brlen, er, pi, alpha)
         path = _i32(path)
@@ -501,8 +528,8 @@ class HipLibrary:
         K, L = self.ancestral_candidates_info(h)
         res, outs = _outputs(_AncestralProbsOutputs, want, log_offset, loglik=(n,), cond=(n, L, 5, 4), log_cand=(n, K),
                              weighted_sum=(K,), weight_stats=(3,))
-        self.check(self.lib.lh_eval_ancestral_candidates_batch(h, n, n_tips, max_depth, *_tree_ptrs(arrays), num_rates,
-                                                               _ptr(path, c_i32p), path.shape[1], node, C.byref(outs)))
+        self.check(getattr(self.lib, entry)(h, n, n_tips, max_depth, *_tree_ptrs(arrays), num_rates, _ptr(path, c_i32p),
+                                            path.shape[1], _node_arg(node, n), C.byref(outs)))
         return res
 
     def eval_ancestral_candidates_batch_device(self, family, n, n_tips, max_depth, ops_ptr, brlen_ptr, er_ptr, pi_ptr,
@@ -512,6 +539,14 @@ class HipLibrary:
         self.check(self.lib.lh_eval_ancestral_candidates_batch_device(
             _handle(family), n, n_tips, max_depth, ops_ptr, brlen_ptr, er_ptr, pi_ptr, alpha_ptr, num_rates, path_ptr,
             path_len, node, C.byref(o), stream))
+
+    def eval_ancestral_candidates_at_batch_device(self, family, n, n_tips, max_depth, ops_ptr, brlen_ptr, er_ptr, pi_ptr,
+                                                  alpha_ptr, num_rates, path_ptr, path_len, slot_ptr, outs, stream=0):
+        """lh_eval_ancestral_candidates_at_batch_device on device addresses (slot_ptr: int32 [n])."""
+        o = _AncestralProbsOutputsDevice(**{k: int(v) for k, v in outs.items() if v})
+        self.check(self.lib.lh_eval_ancestral_candidates_at_batch_device(
+            _handle(family), n, n_tips, max_depth, ops_ptr, brlen_ptr, er_ptr, pi_ptr, alpha_ptr, num_rates, path_ptr,
+            path_len, slot_ptr, C.byref(o), stream))
 
     def ancestral_candidates_profile_read(self, family):
         """(tables ms, pair emissions and sweeps ms, reduction ms, launch groups) of K13 since the last read."""
@@ -524,6 +559,18 @@ class HipLibrary:
         node NODE_PARENT or NODE_MRCA.  Returns a dict with the members of `want`: loglik [n], codons [n, C, 64] (the node's
         triple 16 x1 + 4 x2 + x3 over A,C,G,T), change [n, C, 4] (identical, synonymous, replacement, naive triple with an
         N), weighted_codons [C, 64], weighted_change [C, 4], weight_stats [3]."""
+        return self._eval_node_codons("lh_eval_node_codons_batch", family, n_tips, max_depth, ops, brlen, er, pi, alpha,
+                                      num_rates, path, node, log_offset, want)
+
+    def eval_node_codons_at_batch(self, family, n_tips, max_depth, ops, brlen, er, pi, alpha, num_rates, path, slot,
+                                  log_offset=None, want=("loglik", "codons", "change", "weighted_codons", "weighted_change",
+                                                         "weight_stats")):
+        """eval_node_codons_batch at a node per row: slot [n] as eval_ancestral_candidates_at_batch takes it."""
+        return self._eval_node_codons("lh_eval_node_codons_at_batch", family, n_tips, max_depth, ops, brlen, er, pi, alpha,
+                                      num_rates, path, _slots(slot), log_offset, want)
+
+    def _eval_node_codons(self, entry, family, n_tips, max_depth, ops, brlen, er, pi, alpha, num_rates, path, node,
+                          log_offset, want):
         h = _handle(family)
         n, arrays = _tree_args(ops, brlen, er, pi, alpha)
         path = _i32(path)
@@ -533,8 +580,8 @@ class HipLibrary:
         nc = nc.value
         res, outs = _outputs(_NodeCodonsOutputs, want, log_offset, loglik=(n,), codons=(n, nc, 64), change=(n, nc, 4),
                              weighted_codons=(nc, 64), weighted_change=(nc, 4), weight_stats=(3,))
-        self.check(self.lib.lh_eval_node_codons_batch(h, n, n_tips, max_depth, *_tree_ptrs(arrays), num_rates,
-                                                      _ptr(path, c_i32p), path.shape[1], node, C.byref(outs)))
+        self.check(getattr(self.lib, entry)(h, n, n_tips, max_depth, *_tree_ptrs(arrays), num_rates, _ptr(path, c_i32p),
+                                            path.shape[1], _node_arg(node, n), C.byref(outs)))
         return res
 
     def eval_node_codons_batch_device(self, family, n, n_tips, max_depth, ops_ptr, brlen_ptr, er_ptr, pi_ptr, alpha_ptr,
@@ -544,6 +591,14 @@ class HipLibrary:
         self.check(self.lib.lh_eval_node_codons_batch_device(
             _handle(family), n, n_tips, max_depth, ops_ptr, brlen_ptr, er_ptr, pi_ptr, alpha_ptr, num_rates, path_ptr,
             path_len, node, C.byref(o), stream))
+
+    def eval_node_codons_at_batch_device(self, family, n, n_tips, max_depth, ops_ptr, brlen_ptr, er_ptr, pi_ptr, alpha_ptr,
+                                         num_rates, path_ptr, path_len, slot_ptr, outs, stream=0):
+        """lh_eval_node_codons_at_batch_device on device addresses (slot_ptr: int32 [n])."""
+        o = _NodeCodonsOutputsDevice(**{k: int(v) for k, v in outs.items() if v})
+        self.check(self.lib.lh_eval_node_codons_at_batch_device(
+            _handle(family), n, n_tips, max_depth, ops_ptr, brlen_ptr, er_ptr, pi_ptr, alpha_ptr, num_rates, path_ptr,
+            path_len, slot_ptr, C.byref(o), stream))
 
     def node_codons_profile_read(self, family):
         """(K9 + tables ms, contraction ms, reduction ms, launch groups) of K14 since the last read."""
@@ -963,6 +1018,32 @@ def _n_rows(n, arrays, log_offset):
         (log_offset is None or np.asarray(log_offset).shape == (n,))
 
 
+class _Slots:
+    """The int32 [n] slot array of an `_at` entry point (the wrappers pass it where `node` goes)."""
+
+    def __init__(self, a):
+        self.a = _i32(a)
+        assert self.a.ndim == 1
+
+
+def _slots(slot):
+    return _Slots(slot)
+
+
+def _node_arg(node, n):
+    """What an entry point takes in the place of `node`: the integer, or the pointer to a _Slots array of n entries."""
+    if isinstance(node, _Slots):
+        assert node.a.shape[0] == n
+        return _ptr(node.a, c_i32p)
+    return node
+
+
+def clade_slot(n_tips, children, root, seed_tip, with_tips):
+    """(path, slot) of the most recent common ancestor of a seed and other tips: host.clade_slot."""
+    from . import host
+    return host.clade_slot(n_tips, children, root, seed_tip, with_tips)
+
+
 def seed_path(n_tips, children, root, seed_tip):
     """The `path` row of a tip: host.seed_path (the host library's walk, shared with the lineage pipelines)."""
     from . import host
@@ -1261,6 +1342,23 @@ class Family:
         """lh_asr_node_codons_batch: asr_marginals_batch's trees and rates, the caller's naive codon posteriors
         naive_codons [n][C][125] (C = n_codons of set_codons' frame) and path [n][P]; returns (codons [n][C][64], change
         [n][C][4]), None for what `want` leaves out."""
+        return self._asr_node_codons("lh_asr_node_codons_batch", n_tips, max_depth, ops, brlen, er, pi, rates, naive_codons,
+                                     path, node, want)
+
+    def asr_node_codons_at_batch(self, n_tips, max_depth, ops, brlen, er, pi, rates, naive_codons, path, slot,
+                                 want=("codons", "change")):
+        """asr_node_codons_batch at a node per row: slot [n], for every sample the entry of its own path."""
+        return self._asr_node_codons("lh_asr_node_codons_at_batch", n_tips, max_depth, ops, brlen, er, pi, rates,
+                                     naive_codons, path, _slots(slot), want)
+
+    def asr_node_codons_at_batch_device(self, n, n_tips, max_depth, ops_ptr, brlen_ptr, er_ptr, pi_ptr, rates_ptr, num_rates,
+                                        naive_codons_ptr, path_ptr, path_len, slot_ptr, codons_ptr, change_ptr, stream=0):
+        """lh_asr_node_codons_at_batch_device on device addresses (slot_ptr: int32 [n]; codons_ptr / change_ptr may be 0)."""
+        self.hip.check(self.hip.lib.lh_asr_node_codons_at_batch_device(
+            self.handle, n, n_tips, max_depth, ops_ptr, brlen_ptr, er_ptr, pi_ptr, rates_ptr, num_rates, naive_codons_ptr,
+            path_ptr, path_len, slot_ptr, codons_ptr or None, change_ptr or None, stream))
+
+    def _asr_node_codons(self, entry, n_tips, max_depth, ops, brlen, er, pi, rates, naive_codons, path, node, want):
         _, arrays = _tree_args(ops, brlen, er, pi, rates)
         ops, brlen, er, pi, rates = arrays
         naive_codons = _f64(naive_codons)
@@ -1275,9 +1373,9 @@ class Family:
             raise ValueError("lh_asr_node_codons_batch: naive_codons has %d codons, the handle's frame %d" % (nc, have.value))
         codons = np.zeros((n, nc, 64)) if "codons" in want else None
         change = np.zeros((n, nc, 4)) if "change" in want else None
-        self.hip.check(self.hip.lib.lh_asr_node_codons_batch(
+        self.hip.check(getattr(self.hip.lib, entry)(
             self.handle, n, n_tips, max_depth, *_tree_ptrs(arrays), rates.shape[1], _ptr(naive_codons), _ptr(path, c_i32p),
-            path.shape[1], node, _ptr(codons), _ptr(change)))
+            path.shape[1], _node_arg(node, n), _ptr(codons), _ptr(change)))
         return codons, change
 
     # ---- K15: exact amino-acid replacement posteriors along the edges of a lineage ----

@@ -266,6 +266,41 @@ std::vector<int32_t> SeedPath(const int32_t* children, int T, int root, int seed
   return chain;
 }
 
+CladeSlotResult CladeSlot(const int32_t* children, int T, int root, int seed_tip, const std::vector<int32_t>& with_tips) {
+  const std::string who = "CladeSlot: ";
+  if (with_tips.empty()) throw std::invalid_argument(who + "no tip to join the seed with (empty list)");
+  std::vector<char> listed(std::max(T, 1), 0);
+  for (const int32_t t : with_tips) {
+    if (t == 0) throw std::invalid_argument(who + "tip 0 is naive: the node it shares with the seed is the MRCA (node 'mrca')");
+    if (t < 1 || t >= T)
+      throw std::invalid_argument(who + "tip " + std::to_string(t) + " is not one of the tips 1 .. " + std::to_string(T - 1));
+    if (t == seed_tip) throw std::invalid_argument(who + "tip " + std::to_string(t) + " is the seed itself");
+    if (listed[t]) throw std::invalid_argument(who + "tip " + std::to_string(t) + " is listed twice");
+    listed[t] = 1;
+  }
+  CladeSlotResult r;
+  r.path = SeedPath(children, T, root, seed_tip);
+  if (r.path.empty())
+    throw std::invalid_argument(who + "seed tip " + std::to_string(seed_tip) + " is not a tip 1 .. " + std::to_string(T - 1) +
+                                " that hangs below the root");
+  std::vector<int> slot_of(2 * (std::size_t)T - 2, -1);
+  for (std::size_t s = 0; s < r.path.size(); ++s) slot_of[r.path[s]] = (int)s;
+  r.slot = 0;
+  for (const int32_t t : with_tips) {
+    // the slot at which the tip's own path joins the seed's
+    const std::vector<int32_t> own = SeedPath(children, T, root, t);
+    int join = -1;
+    for (const int32_t v : own)
+      if (slot_of[v] >= 0) {
+        join = slot_of[v];
+        break;
+      }
+    if (join < 0) throw std::invalid_argument(who + "tip " + std::to_string(t) + " does not hang below the root");
+    r.slot = std::max(r.slot, join);
+  }
+  return r;
+}
+
 std::vector<std::string> LineageOfAnnotatedTree(const std::string& s, const std::string& seed_seq) {
   struct Node {
     int parent = -1;

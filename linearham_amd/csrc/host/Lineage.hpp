@@ -112,6 +112,17 @@ std::vector<double> LineageWeights(const std::vector<double>& log_weights, Linea
 /// one of the tips 1 .. T-1.
 std::vector<int32_t> SeedPath(const int32_t* children, int n_tips, int root, int seed_tip);
 
+/// The seed's path (SeedPath) and the index on it of the first node that is an ancestor of every tip of `with_tips`: the
+/// most recent common ancestor of the seed and those tips, which is the largest, over the tips, of the slot at which the
+/// tip's own path joins the seed's.  That node means the same in every tree sample; its slot does not.  Throws
+/// std::invalid_argument, naming the offender, for an empty list, tip 0 (naive: that node is the MRCA), a tip outside
+/// 1 .. T-1, the seed itself, a repeated tip, and a seed or tip that does not hang below the root.
+struct CladeSlotResult {
+  std::vector<int32_t> path;
+  int slot = 0;
+};
+CladeSlotResult CladeSlot(const int32_t* children, int n_tips, int root, int seed_tip, const std::vector<int32_t>& with_tips);
+
 /// One line of PhyloHMM::RunAsr's output (annotated Newick): the [&ancestral="..."] strings on the way seed, its
 /// ancestors up to the top node, then the tip `naive`, as seqs_of_tree collects them, reversed (naive first).
 /// Throws when the tree has no tip `seed_seq` or `naive`, or a node on the way has no annotation.

@@ -233,10 +233,28 @@ double CoveredMass(const AncestralProbsTable& t) {
   return mass;
 }
 
-int ParseLineageNode(const std::string& name) {
-  if (name == "parent") return 0;
-  if (name == "mrca") return 1;
-  throw std::runtime_error("--node must be 'parent' (the seed's parent) or 'mrca', not '" + name + "'");
+int ParseLineageNode(const std::string& name) { return ParseLineageNodeText(name).node; }
+
+LineageNode ParseLineageNodeText(const std::string& text) {
+  static const std::string kWith = "mrca-with:";
+  LineageNode n;
+  n.text = text;
+  if (text == "parent") return n;
+  n.node = 1;
+  if (text == "mrca") return n;
+  n.node = 2;
+  bool ok = text.compare(0, kWith.size(), kWith) == 0;
+  for (std::size_t a = kWith.size(); ok;) {
+    const std::size_t b = std::min(text.find(',', a), text.size());
+    n.with.push_back(text.substr(a, b - a));
+    ok = !n.with.back().empty() && std::count(n.with.begin(), n.with.end(), n.with.back()) == 1;
+    if (b == text.size()) break;
+    a = b + 1;
+  }
+  if (!ok)
+    throw std::runtime_error("--node must be 'parent' (the seed's parent), 'mrca' or 'mrca-with:<name>[,<name>...]' (the most "
+                             "recent common ancestor of the seed and the named sequences, each named once), not '" + text + "'");
+  return n;
 }
 
 void WriteNaiveTable(std::ostream& o, const NaiveProbsTable& t, bool with_sampled) {

@@ -48,8 +48,18 @@ struct AncestralProbsTable {
 void WriteAncestralProbsTable(std::ostream& o, const AncestralProbsTable& t);
 /// The sum of the probabilities of the candidates without an open site: distinct ones cover at most 1.
 double CoveredMass(const AncestralProbsTable& t);
-/// --node's values: "parent" -> 0 (the seed's parent), "mrca" -> 1; throws otherwise.
+/// --node's values: "parent" -> 0 (the seed's parent), "mrca" -> 1, "mrca-with:<name>[,<name>...]" -> 2 (the most recent
+/// common ancestor of the seed and the named sequences); throws otherwise.
 int ParseLineageNode(const std::string& name);
+/// --node as text: the value above and, for "mrca-with:...", the names (none empty, none repeated; whether they are
+/// sequences of the family is the caller's to say).  `text` is kept for the summary files.
+struct LineageNode {
+  int node = 0;
+  std::vector<std::string> with;
+  std::string text;
+  bool at_clade() const { return node == 2; }
+};
+LineageNode ParseLineageNodeText(const std::string& text);
 /// Candidate order sorted by probability, descending, ties by candidate order.
 std::vector<std::size_t> RankCandidates(const NaiveProbsTable& t);
 /// <prefix>.naive.tsv: rank, NaiveSequence, probability, log_prior[, sampled_count, sampled_frequency] ("%.17g";

@@ -2041,6 +2041,53 @@ void PhyloHMM::WriteSeedRows(std::ostream& rows, std::size_t first, const Weight
   }
 }
 
+std::vector<int32_t> PhyloHMM::WithTips(int seed_tip, const std::vector<std::string>& with) const {
+  const int T = (int)xmsa_labels_.size();
+  std::vector<int32_t> tips;
+  for (const std::string& name : with) {
+    Require(name != "naive", "--node mrca-with: the sequence cannot be 'naive': the node it shares with the seed is 'mrca'");
+    int tip = 0;
+    for (int v = 1; v < T && tip == 0; ++v)
+      if (xmsa_labels_[v] == name) tip = v;
+    Require(tip != 0, "--node mrca-with: '" + name + "' is not a sequence of this clonal family");
+    Require(tip != seed_tip, "--node mrca-with: '" + name + "' is the seed sequence itself");
+    tips.push_back(tip);
+  }
+  return tips;
+}
+
+std::vector<int32_t> PhyloHMM::CladeSlotsOf(const TableBatch& tb, int seed_tip, const std::vector<int32_t>& with_tips) const {
+  const int T = (int)xmsa_labels_.size();
+  std::vector<int32_t> slot;
+  if (with_tips.empty()) return slot;
+  slot.resize((std::size_t)tb.dev.n);
+  for (std::size_t i = 0; i < slot.size(); ++i)
+    slot[i] = CladeSlot(tb.children.data() + i * 2 * (std::size_t)(T - 2), T, tb.root[i], seed_tip, with_tips).slot;
+  return slot;
+}
+
+namespace {
+
+// a pipeline's node from the entry points' integer (0 or 1)
+LineageNode FixedLineageNode(int node) {
+  LineageNode n;
+  n.node = node;
+  return n;
+}
+
+// the lines a pipeline at a clade node adds to summary.tsv: the range of the slots over every row after the burn-in, the
+// rows skipped for a non-finite weight included (rows.tsv lists them too); NA where no row is left
+void WriteSlotSummary(std::ostream& summary, const std::vector<double>& slots) {
+  if (slots.empty()) {
+    summary << "slot_min\tNA\nslot_max\tNA\n";
+    return;
+  }
+  summary << "slot_min\t" << (int)*std::min_element(slots.begin(), slots.end()) << "\nslot_max\t"
+          << (int)*std::max_element(slots.begin(), slots.end()) << "\n";
+}
+
+}  // namespace
+
 void PhyloHMM::RunAncestralMarginalsPipeline(const std::string& input_path, const std::string& seed_seq,
                                              const std::string& output_prefix, int num_rates, double burnin_frac) {
   const int seed_tip = BeginPipeline("ancestral marginals", "posterior", burnin_frac, &seed_seq);
@@ -2595,19 +2642,31 @@ std::vector<double> PhyloHMM::CandidatePosterior(const std::vector<std::string>&
 // ---- K13: exact posterior probabilities of candidate ancestral sequences ----
 
 PhyloHMM::AncestralCandidateResult PhyloHMM::AncestralCandidatePosterior(const std::string& seed_seq, int node,
-                                                                         const std::vector<std::string>& candidates) {
-  Require(node == 0 || node == 1, "AncestralCandidatePosterior: node must be 0 (the seed's parent) or 1 (the MRCA)");
+                                                                         const std::vector<std::string>& candidates,
+                                                                         const std::vector<std::string>& with) {
+  Require(!with.empty() || node == 0 || node == 1,
+          "AncestralCandidatePosterior: node must be 0 (the seed's parent) or 1 (the MRCA)");
   Require(!candidates.empty(), "AncestralCandidatePosterior: no candidates");
   const int L = msa_.cols(), K = (int)candidates.size();
   const std::vector<uint8_t> bytes = EncodeSeqs(candidates, alphabet_, L);
+  const std::vector<int32_t> with_tips = with.empty() ? std::vector<int32_t>() : WithTips(SeedTip(seed_seq), with);
   SeedLineage s = OpenSeedLineage(seed_seq);
   CheckHip(lh_family_set_ancestral_candidates(family_, K, bytes.data()), "lh_family_set_ancestral_candidates");
   AncestralCandidateResult res;
-  res.node = node == 0 ? s.nodes.front() : s.nodes.back();
   res.log_cand.assign(K, 0.0);
   lh_ancestral_candidates_outputs outs{};
   outs.loglik = &res.loglik;
   outs.log_cand = res.log_cand.data();
+  if (!with_tips.empty()) {
+    const int32_t slot = CladeSlot(tree_.children.data(), tree_.n_tips, tree_.root, s.seed_tip, with_tips).slot;
+    res.node = s.nodes[slot];
+    CheckHip(lh_eval_ancestral_candidates_at_batch(family_, 1, tree_.n_tips, s.depth, s.ops.data(), tree_.brlen.data(), er_.data(),
+                                                   pi_.data(), &alpha_, num_rates_, s.nodes.data(), (int32_t)s.nodes.size(), &slot,
+                                                   &outs),
+             "lh_eval_ancestral_candidates_at_batch");
+    return res;
+  }
+  res.node = node == 0 ? s.nodes.front() : s.nodes.back();
   CheckHip(lh_eval_ancestral_candidates_batch(family_, 1, tree_.n_tips, s.depth, s.ops.data(), tree_.brlen.data(), er_.data(),
                                               pi_.data(), &alpha_, num_rates_, s.nodes.data(), (int32_t)s.nodes.size(), node, &outs),
            "lh_eval_ancestral_candidates_batch");
@@ -2617,8 +2676,23 @@ PhyloHMM::AncestralCandidateResult PhyloHMM::AncestralCandidatePosterior(const s
 void PhyloHMM::RunAncestralProbsPipeline(const std::string& input_path, const std::string& seed_seq, int node,
                                          const std::string& candidates_path, const std::string& output_prefix, int num_rates,
                                          double burnin_frac) {
-  // what can be refused without a device is refused first: the node, the candidate file, then BeginPipeline's checks
   Require(node == 0 || node == 1, "the ancestral-probabilities pipeline: node must be 0 (the seed's parent) or 1 (the MRCA)");
+  RunAncestralProbsPipelineAt(input_path, seed_seq, FixedLineageNode(node), candidates_path, output_prefix, num_rates, burnin_frac);
+}
+
+void PhyloHMM::RunAncestralProbsPipeline(const std::string& input_path, const std::string& seed_seq, const std::string& node_text,
+                                         const std::string& candidates_path, const std::string& output_prefix, int num_rates,
+                                         double burnin_frac) {
+  RunAncestralProbsPipelineAt(input_path, seed_seq, ParseLineageNodeText(node_text), candidates_path, output_prefix, num_rates,
+                              burnin_frac);
+}
+
+void PhyloHMM::RunAncestralProbsPipelineAt(const std::string& input_path, const std::string& seed_seq, const LineageNode& at,
+                                           const std::string& candidates_path, const std::string& output_prefix, int num_rates,
+                                           double burnin_frac) {
+  // what can be refused without a device is refused first: the node (by the callers), the candidate file, the names to join
+  // the seed with, then BeginPipeline's checks
+  const int node = at.node;
   const int L = msa_.cols();
   AncestralProbsTable t;
   {
@@ -2628,6 +2702,7 @@ void PhyloHMM::RunAncestralProbsPipeline(const std::string& input_path, const st
   }
   const std::size_t K = t.seqs.size();
   const std::vector<uint8_t> bytes = EncodeSeqs(t.seqs, alphabet_, L);
+  const std::vector<int32_t> with_tips = at.at_clade() ? WithTips(SeedTip(seed_seq), at.with) : std::vector<int32_t>();
   const int seed_tip = BeginPipeline("ancestral probabilities", "posterior", burnin_frac, &seed_seq);
   CheckHip(lh_family_set_ancestral_candidates(family_, (int32_t)K, bytes.data()), "lh_family_set_ancestral_candidates");
   TsvTable table = TsvTable::OpenRevBayesTable(input_path);
@@ -2636,16 +2711,25 @@ void PhyloHMM::RunAncestralProbsPipeline(const std::string& input_path, const st
   const std::size_t fit = std::max<std::size_t>(1, ((std::size_t)512 << 20) / (sizeof(double) * K));
   std::vector<double> log_cand;
   std::vector<int32_t> path_len(table.rows.size() - first, 0);
+  std::vector<double> slots(at.at_clade() ? table.rows.size() - first : 0);
   const WeightedRows w = SumWeightedRows(
       "ancestral probabilities", table, input_path, first, PipelineBatch(fit), K, true,
       [&](const TableBatch& tb, std::size_t off, double* ll) {
         const DeviceBatch& b = tb.dev;
         const SeedChains sc = SeedChainsOf(tb, off, seed_tip, seed_seq, path_len.data() + (off - first));
+        const std::vector<int32_t> slot = CladeSlotsOf(tb, seed_tip, with_tips);
+        if (!slot.empty()) std::copy(slot.begin(), slot.end(), slots.begin() + (off - first));
         log_cand.resize((std::size_t)b.n * K);
         lh_ancestral_candidates_outputs outs{};
         outs.loglik = ll;
         outs.log_cand = log_cand.data();
-        CheckHip(lh_eval_ancestral_candidates_batch(family_, b.n, b.n_tips, b.max_depth, b.ops.data(), b.brlen.data(),
+        if (!slot.empty())
+          CheckHip(lh_eval_ancestral_candidates_at_batch(family_, b.n, b.n_tips, b.max_depth, b.ops.data(), b.brlen.data(),
+                                                         b.er.data(), b.pi.data(), b.alpha.data(), num_rates, sc.path.data(),
+                                                         (int32_t)sc.P, slot.data(), &outs),
+                   "lh_eval_ancestral_candidates_at_batch");
+        else
+          CheckHip(lh_eval_ancestral_candidates_batch(family_, b.n, b.n_tips, b.max_depth, b.ops.data(), b.brlen.data(),
                                                     b.er.data(), b.pi.data(), b.alpha.data(), num_rates, sc.path.data(),
                                                     (int32_t)sc.P, node, &outs),
                  "lh_eval_ancestral_candidates_batch");
@@ -2657,12 +2741,16 @@ void PhyloHMM::RunAncestralProbsPipeline(const std::string& input_path, const st
   std::ofstream probs(output_prefix + ".probs.tsv"), rows(output_prefix + ".rows.tsv"), summary(output_prefix + ".summary.tsv");
   Require(probs.good() && rows.good() && summary.good(), "Can't write " + output_prefix + ".*.tsv");
   WriteAncestralProbsTable(probs, t);
-  WriteSeedRows(rows, first, w, path_len);
+  WriteSeedRows(rows, first, w, path_len, "slot", at.at_clade() ? &slots : nullptr);
   WriteSummary(summary, w.used(), w.skipped, Fmt17(w.acc.KishEss()));
   std::size_t constrained = 0;
   for (const std::string& q : t.seqs) constrained += q.find('N') == std::string::npos;
   summary << "candidates\t" << K << "\ncandidates_constrained\t" << constrained << "\ncovered_mass\t" << Fmt17(CoveredMass(t))
           << "\n";
+  if (at.at_clade()) {
+    summary << "node\t" << at.text << "\n";
+    WriteSlotSummary(summary, slots);
+  }
 }
 
 // ---- K14: exact codon marginals of a node of a seed's lineage ----
@@ -2689,8 +2777,10 @@ PhyloHMM::NodeCodonsResult UnpackNodeCodons(int frame, std::size_t C, const doub
 
 }  // namespace
 
-PhyloHMM::NodeCodonsResult PhyloHMM::NodeCodonMarginals(const std::string& seed_seq, int node, int frame) {
-  CheckNodeAndFrame("NodeCodonMarginals", node, frame);
+PhyloHMM::NodeCodonsResult PhyloHMM::NodeCodonMarginals(const std::string& seed_seq, int node, int frame,
+                                                        const std::vector<std::string>& with) {
+  CheckNodeAndFrame("NodeCodonMarginals", with.empty() ? node : 0, frame);
+  const std::vector<int32_t> with_tips = with.empty() ? std::vector<int32_t>() : WithTips(SeedTip(seed_seq), with);
   SeedLineage s = OpenSeedLineage(seed_seq);
   const CodonLayout lay = SetCodons(family_, frame);
   const std::size_t C = (std::size_t)lay.n_codons;
@@ -2700,11 +2790,19 @@ PhyloHMM::NodeCodonsResult PhyloHMM::NodeCodonMarginals(const std::string& seed_
   outs.loglik = &ll;
   outs.codons = codons.data();
   outs.change = change.data();
-  CheckHip(lh_eval_node_codons_batch(family_, 1, tree_.n_tips, s.depth, s.ops.data(), tree_.brlen.data(), er_.data(), pi_.data(),
-                                     &alpha_, num_rates_, s.nodes.data(), (int32_t)s.nodes.size(), node, &outs),
-           "lh_eval_node_codons_batch");
+  int32_t slot = node == 0 ? 0 : (int32_t)s.nodes.size() - 1;
+  if (!with_tips.empty()) {
+    slot = CladeSlot(tree_.children.data(), tree_.n_tips, tree_.root, s.seed_tip, with_tips).slot;
+    CheckHip(lh_eval_node_codons_at_batch(family_, 1, tree_.n_tips, s.depth, s.ops.data(), tree_.brlen.data(), er_.data(),
+                                          pi_.data(), &alpha_, num_rates_, s.nodes.data(), (int32_t)s.nodes.size(), &slot, &outs),
+             "lh_eval_node_codons_at_batch");
+  } else {
+    CheckHip(lh_eval_node_codons_batch(family_, 1, tree_.n_tips, s.depth, s.ops.data(), tree_.brlen.data(), er_.data(), pi_.data(),
+                                       &alpha_, num_rates_, s.nodes.data(), (int32_t)s.nodes.size(), node, &outs),
+             "lh_eval_node_codons_batch");
+  }
   NodeCodonsResult r = UnpackNodeCodons(frame, C, codons.data(), change.data());
-  r.node = node == 0 ? s.nodes.front() : s.nodes.back();
+  r.node = s.nodes[slot];
   r.loglik = ll;
   return r;
 }
@@ -2746,8 +2844,22 @@ void PhyloHMM::WriteChangeTable(std::ostream& o, const NodeCodonsResult& m) {
 
 void PhyloHMM::RunNodeCodonsPipeline(const std::string& input_path, const std::string& seed_seq, int node,
                                      const std::string& output_prefix, int num_rates, double burnin_frac, int frame) {
-  // what can be refused without a device is refused first: the node and the frame, then BeginPipeline's checks
   CheckNodeAndFrame("the node-codons pipeline", node, frame);
+  RunNodeCodonsPipelineAt(input_path, seed_seq, FixedLineageNode(node), output_prefix, num_rates, burnin_frac, frame);
+}
+
+void PhyloHMM::RunNodeCodonsPipeline(const std::string& input_path, const std::string& seed_seq, const std::string& node_text,
+                                     const std::string& output_prefix, int num_rates, double burnin_frac, int frame) {
+  RunNodeCodonsPipelineAt(input_path, seed_seq, ParseLineageNodeText(node_text), output_prefix, num_rates, burnin_frac, frame);
+}
+
+void PhyloHMM::RunNodeCodonsPipelineAt(const std::string& input_path, const std::string& seed_seq, const LineageNode& at,
+                                       const std::string& output_prefix, int num_rates, double burnin_frac, int frame) {
+  // what can be refused without a device is refused first: the node (by the callers) and the frame, the names to join the
+  // seed with, then BeginPipeline's checks
+  const int node = at.node;
+  CheckNodeAndFrame("the node-codons pipeline", at.at_clade() ? 0 : node, frame);
+  const std::vector<int32_t> with_tips = at.at_clade() ? WithTips(SeedTip(seed_seq), at.with) : std::vector<int32_t>();
   const int seed_tip = BeginPipeline("node codons", "codon", burnin_frac, &seed_seq);
   const CodonLayout lay = SetCodons(family_, frame);
   TsvTable table = TsvTable::OpenRevBayesTable(input_path);
@@ -2757,18 +2869,27 @@ void PhyloHMM::RunNodeCodonsPipeline(const std::string& input_path, const std::s
   const std::size_t fit = std::max<std::size_t>(1, ((std::size_t)512 << 20) / (sizeof(double) * std::max<std::size_t>(NC + NH, 1)));
   std::vector<double> codons, change;
   std::vector<int32_t> path_len(table.rows.size() - first, 0);
+  std::vector<double> slots(at.at_clade() ? table.rows.size() - first : 0);
   const WeightedRows w = SumWeightedRows(
       "node codons", table, input_path, first, PipelineBatch(fit), NC + NH, true,
       [&](const TableBatch& tb, std::size_t off, double* ll) {
         const DeviceBatch& b = tb.dev;
         const SeedChains sc = SeedChainsOf(tb, off, seed_tip, seed_seq, path_len.data() + (off - first));
+        const std::vector<int32_t> slot = CladeSlotsOf(tb, seed_tip, with_tips);
+        if (!slot.empty()) std::copy(slot.begin(), slot.end(), slots.begin() + (off - first));
         codons.resize((std::size_t)b.n * NC);
         change.resize((std::size_t)b.n * NH);
         lh_node_codons_outputs outs{};
         outs.loglik = ll;
         outs.codons = codons.data();
         outs.change = change.data();
-        CheckHip(lh_eval_node_codons_batch(family_, b.n, b.n_tips, b.max_depth, b.ops.data(), b.brlen.data(), b.er.data(),
+        if (!slot.empty())
+          CheckHip(lh_eval_node_codons_at_batch(family_, b.n, b.n_tips, b.max_depth, b.ops.data(), b.brlen.data(), b.er.data(),
+                                                b.pi.data(), b.alpha.data(), num_rates, sc.path.data(), (int32_t)sc.P,
+                                                slot.data(), &outs),
+                   "lh_eval_node_codons_at_batch");
+        else
+          CheckHip(lh_eval_node_codons_batch(family_, b.n, b.n_tips, b.max_depth, b.ops.data(), b.brlen.data(), b.er.data(),
                                            b.pi.data(), b.alpha.data(), num_rates, sc.path.data(), (int32_t)sc.P, node, &outs),
                  "lh_eval_node_codons_batch");
         return [&](std::size_t i, double* row) {
@@ -2783,15 +2904,16 @@ void PhyloHMM::RunNodeCodonsPipeline(const std::string& input_path, const std::s
   WriteNodeCodonTable(cod, res);
   WriteNodeAminoAcidTable(aa, res);
   WriteChangeTable(chg, res);
-  WriteSeedRows(rows, first, w, path_len);
+  WriteSeedRows(rows, first, w, path_len, "slot", at.at_clade() ? &slots : nullptr);
   WriteSummary(summary, w.used(), w.skipped, Fmt17(w.acc.KishEss()));
   double syn = 0.0, repl = 0.0;
   for (const auto& h : res.change) {
     syn += h[1];
     repl += h[2];
   }
-  summary << "frame\t" << frame << "\nnode\t" << (node == 0 ? "parent" : "mrca") << "\nexpected_synonymous\t" << Fmt17(syn)
-          << "\nexpected_replacement\t" << Fmt17(repl) << "\n";
+  summary << "frame\t" << frame << "\nnode\t" << (at.at_clade() ? at.text : node == 0 ? "parent" : "mrca")
+          << "\nexpected_synonymous\t" << Fmt17(syn) << "\nexpected_replacement\t" << Fmt17(repl) << "\n";
+  if (at.at_clade()) WriteSlotSummary(summary, slots);
 }
 
 // ---- K15: exact amino-acid replacement posteriors along the edges of a seed's lineage ----

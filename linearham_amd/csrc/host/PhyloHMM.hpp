@@ -19,6 +19,8 @@
 
 namespace linearham {
 
+struct LineageNode;  // --node as text (NaiveProbs.hpp)
+
 class PhyloHMM : public HMM {
  private:
   MatrixXi xmsa_;
@@ -261,8 +263,12 @@ class PhyloHMM : public HMM {
     double loglik = 0.0;
   };
   /// After InitializePhyloParameters: the candidates' log probabilities under the current tree.
+  /// `with` not empty: the node is the most recent common ancestor of the seed and the sequences named there
+  /// (lh_eval_ancestral_candidates_at_batch at CladeSlot's slot) and `node` is not looked at; a name that is no sequence
+  /// of the family, the seed itself and 'naive' are refused before any device work.
   AncestralCandidateResult AncestralCandidatePosterior(const std::string& seed_seq, int node,
-                                                       const std::vector<std::string>& candidates);
+                                                       const std::vector<std::string>& candidates,
+                                                       const std::vector<std::string>& with = {});
   /// The importance-weighted probabilities of the candidates of `candidates_path` (ReadNamedCandidateFile) over a RevBayes
   /// table, with RunAncestralMarginalsPipeline's reader, burn-in, weights, Kish ESS and one-device rule.  The node and the
   /// candidate file are checked first, before any device work.  The rows' probabilities are added up on the host in row
@@ -270,6 +276,12 @@ class PhyloHMM : public HMM {
   /// ranked), .rows.tsv (row, weight, chain_length) and .summary.tsv (rows used and skipped, Kish ESS, the candidates,
   /// those without an open site and the posterior mass these cover).
   void RunAncestralProbsPipeline(const std::string& input_path, const std::string& seed_seq, int node,
+                                 const std::string& candidates_path, const std::string& output_prefix, int num_rates,
+                                 double burnin_frac);
+  /// The same with the node as --node's text (ParseLineageNodeText).  For 'mrca-with:<names>' the node is the most recent
+  /// common ancestor of the seed and the named sequences, at a slot of its own in every row: .rows.tsv gains the column
+  /// `slot` and .summary.tsv the lines node, slot_min and slot_max.  For 'parent' and 'mrca' the files are the int form's.
+  void RunAncestralProbsPipeline(const std::string& input_path, const std::string& seed_seq, const std::string& node_text,
                                  const std::string& candidates_path, const std::string& output_prefix, int num_rates,
                                  double burnin_frac);
   /// K14: exact codon marginals of a node of the lineage of the tip `seed_seq` (lh_eval_node_codons_batch): node 0 = the
@@ -284,7 +296,9 @@ class PhyloHMM : public HMM {
     std::vector<std::array<double, 4>> change;
   };
   /// After InitializePhyloParameters: the tables of the current tree.  The node and the frame are checked first.
-  NodeCodonsResult NodeCodonMarginals(const std::string& seed_seq, int node, int frame);
+  /// `with` not empty: as AncestralCandidatePosterior's (lh_eval_node_codons_at_batch).
+  NodeCodonsResult NodeCodonMarginals(const std::string& seed_seq, int node, int frame,
+                                      const std::vector<std::string>& with = {});
   /// The importance-weighted tables over a RevBayes table, with RunAncestralMarginalsPipeline's reader, burn-in, weights,
   /// Kish ESS and one-device rule.  What needs no device (the node, the frame, the burn-in, the seed) is refused before the
   /// family is created.  The rows' tables are added up on the host in row order, so the files do not depend on
@@ -293,6 +307,10 @@ class PhyloHMM : public HMM {
   /// chain_length) and .summary.tsv (with frame, node, expected_synonymous and expected_replacement, the column sums of
   /// the changes table).
   void RunNodeCodonsPipeline(const std::string& input_path, const std::string& seed_seq, int node,
+                             const std::string& output_prefix, int num_rates, double burnin_frac, int frame);
+  /// The same with the node as --node's text, as RunAncestralProbsPipeline's text form: for 'mrca-with:<names>' .rows.tsv
+  /// gains `slot`, .summary.tsv's node line holds the text and slot_min and slot_max follow it.
+  void RunNodeCodonsPipeline(const std::string& input_path, const std::string& seed_seq, const std::string& node_text,
                              const std::string& output_prefix, int num_rates, double burnin_frac, int frame);
   /// numbers printed with %.17g; entries of probability 0 are left out of the first two
   static void WriteNodeCodonTable(std::ostream& o, const NodeCodonsResult& m);
@@ -427,6 +445,16 @@ class PhyloHMM : public HMM {
   SeedChains SeedChainsOf(const TableBatch& tb, std::size_t off, int seed_tip, const std::string& seed_seq, int32_t* path_len) const;
   static void WriteSeedRows(std::ostream& rows, std::size_t first, const WeightedRows& w, const std::vector<int32_t>& path_len,
                             const char* extra_name = nullptr, const std::vector<double>* extra = nullptr);
+  /// The tips of the sequences `with` names, to join the seed (tip seed_tip) with: no device is touched.  Throws, naming
+  /// the name, for 'naive', the seed itself and a name that is no sequence of the family.
+  std::vector<int32_t> WithTips(int seed_tip, const std::vector<std::string>& with) const;
+  /// slot[m] of a batch of table rows (CladeSlot under every row's own tree); nothing is done for an empty `with_tips`
+  std::vector<int32_t> CladeSlotsOf(const TableBatch& tb, int seed_tip, const std::vector<int32_t>& with_tips) const;
+  void RunAncestralProbsPipelineAt(const std::string& input_path, const std::string& seed_seq, const LineageNode& node,
+                                   const std::string& candidates_path, const std::string& output_prefix, int num_rates,
+                                   double burnin_frac);
+  void RunNodeCodonsPipelineAt(const std::string& input_path, const std::string& seed_seq, const LineageNode& node,
+                               const std::string& output_prefix, int num_rates, double burnin_frac, int frame);
   struct AsrRow;
   /// The rows of a RunPipeline table as RunAsr and RunLineagePipeline read them; *num_rates = the sr[] columns.
   std::vector<AsrRow> ReadAsrRows(const std::string& input_path, int* num_rates) const;

@@ -292,6 +292,20 @@ int lhh_seed_path(const int32_t* children, int n_tips, int root, int seed_tip, i
   });
 }
 
+// linearham::CladeSlot (no family, no device): with_tips [n_with]; path [cap >= n_tips - 2], *n its length, *slot the index
+// on it of the most recent common ancestor of the seed and the listed tips.
+int lhh_clade_slot(const int32_t* children, int n_tips, int root, int seed_tip, const int32_t* with_tips, int n_with,
+                   int32_t* path, int cap, int* n, int* slot) {
+  return Guard([&] {
+    const linearham::CladeSlotResult r = linearham::CladeSlot(
+        children, n_tips, root, seed_tip, std::vector<int32_t>(with_tips, with_tips + std::max(n_with, 0)));
+    if ((int)r.path.size() > cap) throw std::runtime_error("lhh_clade_slot: output too small");
+    std::copy(r.path.begin(), r.path.end(), path);
+    *n = (int)r.path.size();
+    *slot = r.slot;
+  });
+}
+
 // PhyloHMM::AncestralMarginals: nodes [cap_slots], marg [cap_slots][L][4], rate_post [L][R]; *n_slots receives the chain's
 // length, *num_rates R.  marg == NULL: only those two.
 int lhh_phylo_ancestral_marginals(void* h, const char* seed_seq, int32_t* nodes, double* marg, double* rate_post,
@@ -366,6 +380,32 @@ int lhh_phylo_ancestral_candidate_posterior(void* h, const char* seed_seq, int n
   });
 }
 
+// The same with the node as --node's text (ParseLineageNodeText): 'parent', 'mrca' or 'mrca-with:<name>[,<name>...]'
+int lhh_phylo_ancestral_candidate_posterior_at(void* h, const char* seed_seq, const char* node_text, const char* candidates,
+                                               int K, double* log_cand, int* node_id, double* loglik) {
+  return Guard([&] {
+    std::vector<std::string> seqs;
+    std::istringstream in(candidates);
+    for (std::string line; std::getline(in, line);) seqs.push_back(line);
+    if ((int)seqs.size() != K) throw std::runtime_error("lhh_phylo_ancestral_candidate_posterior_at: K does not match the candidates");
+    const linearham::LineageNode n = linearham::ParseLineageNodeText(node_text);
+    const PhyloHMM::AncestralCandidateResult r =
+        dynamic_cast<PhyloHMM&>(*static_cast<HMM*>(h)).AncestralCandidatePosterior(seed_seq, n.node, seqs, n.with);
+    std::copy(r.log_cand.begin(), r.log_cand.end(), log_cand);
+    if (node_id) *node_id = r.node;
+    if (loglik) *loglik = r.loglik;
+  });
+}
+
+int lhh_run_ancestral_probs_pipeline_at(void* h, const char* input_path, const char* seed_seq, const char* node_text,
+                                        const char* candidates_path, const char* output_prefix, int num_rates,
+                                        double burnin_frac) {
+  return Guard([&] {
+    dynamic_cast<PhyloHMM&>(*static_cast<HMM*>(h)).RunAncestralProbsPipeline(input_path, seed_seq, std::string(node_text),
+                                                                           candidates_path, output_prefix, num_rates, burnin_frac);
+  });
+}
+
 int lhh_run_ancestral_probs_pipeline(void* h, const char* input_path, const char* seed_seq, int node, const char* candidates_path,
                                      const char* output_prefix, int num_rates, double burnin_frac) {
   return Guard([&] {
@@ -390,24 +430,50 @@ static const char* NodeCodonsText(const PhyloHMM::NodeCodonsResult& m) {
 // PhyloHMM::NodeCodonMarginals: codons [cap_codons][64], change [cap_codons][4]; *n_codons receives the count, *text the
 // three tables as the writers print them.  codons == NULL: only *n_codons (after the node and frame checks), nothing is
 // evaluated.
+// The body of both forms below, behind their check of the node: `with` empty: the node is `node`.
+static void NodeCodonMarginalsOut(void* h, const char* seed_seq, int node, const std::vector<std::string>& with, int frame,
+                                  double* codons, double* change, int cap_codons, int* n_codons, int* node_id, double* loglik,
+                                  const char** text) {
+  PhyloHMM& p = dynamic_cast<PhyloHMM&>(*static_cast<HMM*>(h));
+  if (frame < 0 || frame > 2) throw std::runtime_error("NodeCodonMarginals: frame must be 0, 1 or 2");
+  const int L = (int)p.msa().cols();
+  *n_codons = L >= frame ? (L - frame) / 3 : 0;
+  if (!codons) return;
+  const PhyloHMM::NodeCodonsResult m = p.NodeCodonMarginals(seed_seq, node, frame, with);
+  if ((int)m.codons.size() > cap_codons) throw std::runtime_error("lhh_phylo_node_codon_marginals: output too small");
+  for (std::size_t c = 0; c < m.codons.size(); ++c) {
+    std::copy(m.codons[c].begin(), m.codons[c].end(), codons + c * 64);
+    if (change) std::copy(m.change[c].begin(), m.change[c].end(), change + c * 4);
+  }
+  if (node_id) *node_id = m.node;
+  if (loglik) *loglik = m.loglik;
+  if (text) *text = NodeCodonsText(m);
+}
+
 int lhh_phylo_node_codon_marginals(void* h, const char* seed_seq, int node, int frame, double* codons, double* change,
                                    int cap_codons, int* n_codons, int* node_id, double* loglik, const char** text) {
   return Guard([&] {
-    PhyloHMM& p = dynamic_cast<PhyloHMM&>(*static_cast<HMM*>(h));
     if (node != 0 && node != 1) throw std::runtime_error("NodeCodonMarginals: node must be 0 (the seed's parent) or 1 (the MRCA)");
-    if (frame < 0 || frame > 2) throw std::runtime_error("NodeCodonMarginals: frame must be 0, 1 or 2");
-    const int L = (int)p.msa().cols();
-    *n_codons = L >= frame ? (L - frame) / 3 : 0;
-    if (!codons) return;
-    const PhyloHMM::NodeCodonsResult m = p.NodeCodonMarginals(seed_seq, node, frame);
-    if ((int)m.codons.size() > cap_codons) throw std::runtime_error("lhh_phylo_node_codon_marginals: output too small");
-    for (std::size_t c = 0; c < m.codons.size(); ++c) {
-      std::copy(m.codons[c].begin(), m.codons[c].end(), codons + c * 64);
-      if (change) std::copy(m.change[c].begin(), m.change[c].end(), change + c * 4);
-    }
-    if (node_id) *node_id = m.node;
-    if (loglik) *loglik = m.loglik;
-    if (text) *text = NodeCodonsText(m);
+    NodeCodonMarginalsOut(h, seed_seq, node, {}, frame, codons, change, cap_codons, n_codons, node_id, loglik, text);
+  });
+}
+
+// The same with the node as --node's text; codons as lhh_phylo_node_codon_marginals takes them (NULL: only *n_codons,
+// after the node text and the frame have been checked)
+int lhh_phylo_node_codon_marginals_at(void* h, const char* seed_seq, const char* node_text, int frame, double* codons,
+                                      double* change, int cap_codons, int* n_codons, int* node_id, double* loglik,
+                                      const char** text) {
+  return Guard([&] {
+    const linearham::LineageNode n = linearham::ParseLineageNodeText(node_text);
+    NodeCodonMarginalsOut(h, seed_seq, n.node, n.with, frame, codons, change, cap_codons, n_codons, node_id, loglik, text);
+  });
+}
+
+int lhh_run_node_codons_pipeline_at(void* h, const char* input_path, const char* seed_seq, const char* node_text,
+                                    const char* output_prefix, int num_rates, double burnin_frac, int frame) {
+  return Guard([&] {
+    dynamic_cast<PhyloHMM&>(*static_cast<HMM*>(h)).RunNodeCodonsPipeline(input_path, seed_seq, std::string(node_text),
+                                                                       output_prefix, num_rates, burnin_frac, frame);
   });
 }
 
@@ -538,6 +604,17 @@ int lhh_read_named_candidates(const char* path, int n_sites, const char** out) {
 
 int lhh_parse_lineage_node(const char* name, int* node) {
   return Guard([&] { *node = linearham::ParseLineageNode(name); });
+}
+
+// ParseLineageNodeText: *names receives the names of 'mrca-with:...' joined by '\n' (empty for the two fixed nodes)
+int lhh_parse_lineage_node_text(const char* text, int* node, const char** names) {
+  return Guard([&] {
+    const linearham::LineageNode n = linearham::ParseLineageNodeText(text);
+    *node = n.node;
+    g_out.clear();
+    for (const std::string& s : n.with) g_out += (g_out.empty() ? "" : "\n") + s;
+    *names = g_out.c_str();
+  });
 }
 
 int lhh_run_lineage_substitutions_pipeline(void* h, const char* input_path, const char* seed_seq, const char* output_prefix,

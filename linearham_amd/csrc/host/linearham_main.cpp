@@ -102,18 +102,20 @@ int main(int argc, char** argv) {
                    "  --lineage-substitutions-pipeline --input-path <RevBayes table> --output-path <prefix> --seed-seq <name>\n"
                    "    [--burnin-frac <f>]: writes <prefix>.substitutions.tsv, <prefix>.seed_edge.tsv, <prefix>.naive_edge.tsv,\n"
                    "    <prefix>.rows.tsv and <prefix>.summary.tsv (one device)\n"
-                   "  --ancestral-probs --seed-seq <name> --node <parent|mrca> --candidates <fasta>: the arguments of --marginals;\n"
+                   "  --ancestral-probs --seed-seq <name> --node <parent|mrca|mrca-with:NAME[,NAME...]> --candidates <fasta>: the arguments of --marginals;\n"
                    "    prints the exact posterior probability of every candidate sequence at the parent of the sequence <name>\n"
-                   "    or at its MRCA with naive (name, sequence, probability, ranked; N leaves a site open)\n"
+                   "    or at its MRCA with naive (name, sequence, probability, ranked; N leaves a site open);\n"
+                   "    --node mrca-with:NAME[,NAME...] selects the most recent common ancestor of <name> and the named sequences of\n"
+                   "    the family instead, here and in the three commands below\n"
                    "  --ancestral-probs-pipeline --input-path <RevBayes table> --output-path <prefix> --seed-seq <name>\n"
-                   "    --node <parent|mrca> --candidates <fasta> [--burnin-frac <f>]: writes <prefix>.probs.tsv, <prefix>.rows.tsv\n"
+                   "    --node <parent|mrca|mrca-with:NAME[,NAME...]> --candidates <fasta> [--burnin-frac <f>]: writes <prefix>.probs.tsv, <prefix>.rows.tsv\n"
                    "    and <prefix>.summary.tsv (one device)\n"
-                   "  --node-codons --seed-seq <name> --node <parent|mrca> [--frame <0|1|2>]: the arguments of --marginals; prints\n"
+                   "  --node-codons --seed-seq <name> --node <parent|mrca|mrca-with:NAME[,NAME...]> [--frame <0|1|2>]: the arguments of --marginals; prints\n"
                    "    the exact codon table of the parent of the sequence <name> or of its MRCA with naive for that tree, its\n"
                    "    amino-acid table, and per codon the probabilities that it is identical to the naive codon, a synonymous\n"
                    "    change of it, a replacement, or undetermined (the naive codon holds an N)\n"
                    "  --node-codons-pipeline --input-path <RevBayes table> --output-path <prefix> --seed-seq <name>\n"
-                   "    --node <parent|mrca> [--frame <0|1|2>] [--burnin-frac <f>]: writes <prefix>.codons.tsv, <prefix>.aa.tsv,\n"
+                   "    --node <parent|mrca|mrca-with:NAME[,NAME...]> [--frame <0|1|2>] [--burnin-frac <f>]: writes <prefix>.codons.tsv, <prefix>.aa.tsv,\n"
                    "    <prefix>.changes.tsv, <prefix>.rows.tsv and <prefix>.summary.tsv (one device)\n"
                    "  --lineage-replacements --seed-seq <name> [--frame <0|1|2>]: the arguments of --marginals; prints per codon the\n"
                    "    expected number of lineage edges, naive to the sequence <name>, on which its amino acid goes from one residue\n"
@@ -237,13 +239,13 @@ int main(int argc, char** argv) {
       return EXIT_SUCCESS;
     }
     if (subcmd == "--ancestral-probs-pipeline") {
-      phylo_hmm_ptr->RunAncestralProbsPipeline(a.one("input-path"), a.one("seed-seq"), linearham::ParseLineageNode(a.one("node")),
+      phylo_hmm_ptr->RunAncestralProbsPipeline(a.one("input-path"), a.one("seed-seq"), std::string(a.one("node")),
                                                a.one("candidates"), a.one("output-path"), num_rates,
                                                std::stod(a.opt("burnin-frac", "0")));
       return EXIT_SUCCESS;
     }
     if (subcmd == "--node-codons-pipeline") {
-      phylo_hmm_ptr->RunNodeCodonsPipeline(a.one("input-path"), a.one("seed-seq"), linearham::ParseLineageNode(a.one("node")),
+      phylo_hmm_ptr->RunNodeCodonsPipeline(a.one("input-path"), a.one("seed-seq"), std::string(a.one("node")),
                                            a.one("output-path"), num_rates, std::stod(a.opt("burnin-frac", "0")),
                                            std::stoi(a.opt("frame", "0")));
       return EXIT_SUCCESS;
@@ -280,18 +282,19 @@ int main(int argc, char** argv) {
       return EXIT_SUCCESS;
     }
     // --ancestral-probs: the node and the candidate file are refused before anything is evaluated
-    int probs_node = 0;
+    linearham::LineageNode probs_node;
     linearham::AncestralProbsTable probs;
     if (subcmd == "--ancestral-probs") {
-      probs_node = linearham::ParseLineageNode(a.one("node"));
+      probs_node = linearham::ParseLineageNodeText(a.one("node"));
       linearham::NamedCandidates c = linearham::ReadNamedCandidateFile(a.one("candidates"), (int)phylo_hmm_ptr->msa().cols());
       probs.names = std::move(c.names);
       probs.seqs = std::move(c.seqs);
     }
     // --node-codons: the node and the frame are refused before anything is evaluated
-    int codons_node = 0, codons_frame = 0;
+    linearham::LineageNode codons_node;
+    int codons_frame = 0;
     if (subcmd == "--node-codons") {
-      codons_node = linearham::ParseLineageNode(a.one("node"));
+      codons_node = linearham::ParseLineageNodeText(a.one("node"));
       codons_frame = std::stoi(a.opt("frame", "0"));
       if (codons_frame < 0 || codons_frame > 2) throw std::invalid_argument("--frame must be 0, 1 or 2");
     }
@@ -343,11 +346,13 @@ int main(int argc, char** argv) {
       }
       linearham::PhyloHMM::WriteRateTable(std::cout, m.rate_post.data(), L, m.num_rates);
     } else if (subcmd == "--ancestral-probs") {
-      for (double x : phylo_hmm_ptr->AncestralCandidatePosterior(a.one("seed-seq"), probs_node, probs.seqs).log_cand)
+      for (double x : phylo_hmm_ptr->AncestralCandidatePosterior(a.one("seed-seq"), probs_node.node, probs.seqs, probs_node.with)
+                          .log_cand)
         probs.prob.push_back(std::exp(x));
       linearham::WriteAncestralProbsTable(std::cout, probs);
     } else if (subcmd == "--node-codons") {
-      const linearham::PhyloHMM::NodeCodonsResult m = phylo_hmm_ptr->NodeCodonMarginals(a.one("seed-seq"), codons_node, codons_frame);
+      const linearham::PhyloHMM::NodeCodonsResult m = phylo_hmm_ptr->NodeCodonMarginals(a.one("seed-seq"), codons_node.node, codons_frame,
+                                                                                               codons_node.with);
       linearham::PhyloHMM::WriteNodeCodonTable(std::cout, m);
       std::cout << "\n";
       linearham::PhyloHMM::WriteNodeAminoAcidTable(std::cout, m);

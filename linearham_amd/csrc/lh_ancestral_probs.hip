@@ -39,14 +39,19 @@ namespace lh {
 
 namespace {
 
-template <bool kMrca>
+// kForm: kCondParent (the walk down the chain ends at slot 0), kCondMrca (no down step) or kCondSlot (the walk ends at
+// slot[sample] of the sample's own path; a workgroup serves one (sample, rate), so the slot is uniform over it).
+enum { kCondParent = 0, kCondMrca = 1, kCondSlot = 2 };
+
+template <int kForm>
 __global__ void __launch_bounds__(256) cond_kernel(int R, int T, int n_prune, int P, const uint8_t* __restrict__ msa,
                                                    const AsrOp* __restrict__ desc, const double* __restrict__ brlen,
                                                    const double* __restrict__ rates, const double* __restrict__ eig,
                                                    const double* __restrict__ pi, const double* __restrict__ site_lik,
                                                    const int32_t* __restrict__ site_scal, const int32_t* __restrict__ chain,
                                                    const int32_t* __restrict__ plen, double2* clv, int Lp,
-                                                   double* __restrict__ part) {
+                                                   double* __restrict__ part, const int32_t* __restrict__ slot) {
+  constexpr bool kMrca = kForm == kCondMrca;
   extern __shared__ double2 cond_smem[];
   const TreeTables tt = tree_prologue(cond_smem, R, T, desc, brlen, rates, eig, plen, clv, Lp);
   const int len = tt.len;
@@ -61,6 +66,8 @@ __global__ void __launch_bounds__(256) cond_kernel(int R, int T, int n_prune, in
   const double* __restrict__ p4 = pi + (size_t)sample * 4;
   const int32_t* __restrict__ ch = chain + (size_t)sample * P;
   double* part_s = part + ((size_t)sample * R + rate) * (size_t)NP * 20;
+  // (slot_check_kernel has left len 0 where the slot lies outside the path)
+  const int stop = kForm == kCondSlot ? slot[sample] : 0;
 
   for (int s0 = wave * 64; s0 < NP; s0 += n_waves * 64) {
     const bool live = s0 + lane < NP;
@@ -97,14 +104,14 @@ __global__ void __launch_bounds__(256) cond_kernel(int R, int T, int n_prune, in
     }
     if (!kMrca) {
       const double2* cbase = tt.clv_s + pat;
-      for (int s = len - 1; s >= 1; --s) {
+      for (int s = len - 1; s > stop; --s) {
         // the message into v_{s-1}: the sibling off the path times the message from above, through v_{s-1}'s branch
         double m[4];
         const int kc = tree_sibling_message(tt, ch[s], msa, n_prune, pat, all_n, m);
 #pragma unroll
         for (int b = 0; b < 5; ++b) tree_descend(tt.pin, kc, m, A[b]);
       }
-      const double2* cv = cbase + (size_t)chain_op(ch[0]) * 2 * plane;
+      const double2* cv = cbase + (size_t)chain_op(ch[stop]) * 2 * plane;
       const double2 lo = cv[0], hi = cv[plane];
       node[0] = lo.x;
       node[1] = lo.y;
@@ -124,6 +131,19 @@ __global__ void __launch_bounds__(256) cond_kernel(int R, int T, int n_prune, in
       }
     }
   }
+}
+
+// Beside K11c: a sample whose slot lies outside its path becomes a sample without a path (plen 0: NaN tables, no weight).
+// Bit 2 of err[0] is raised and err[1] keeps 0x7fffffff - (the first such row of the call), 0 while there is none.
+__global__ void __launch_bounds__(256) slot_check_kernel(int n, int row0, const int32_t* __restrict__ slot, int32_t* plen,
+                                                         int32_t* err) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int len = plen[i], s = slot[i];
+  if (len == 0 || (s >= 0 && s < len)) return;
+  plen[i] = 0;
+  atomicOr(err, 4);
+  atomicMax(err + 1, 0x7fffffff - (row0 + i));
 }
 
 __global__ void __launch_bounds__(256) cond_sites_kernel(int n, int L, int n_prune, const int32_t* __restrict__ site_pat,
@@ -196,21 +216,26 @@ int launch_ancestral_cond(const DevFamily& fam, int n, int R, int T, const int32
                           const double* rates, const double* eig, const double* pi, const double* site_lik,
                           const int32_t* site_scal, const double* naive_prob, const int32_t* path, int P, int node,
                           const AncWs& ws, double* table, double* cond, const int4* hdr, int32_t* err_flag,
-                          hipStream_t stream) {
+                          hipStream_t stream, const int32_t* slot, int slot_row0) {
   const int L = fam.n_sites, NP = fam.n_prune + 1;
-  if (n < 1 || n > 65535 || L < 1 || P < 1 || node < 0 || node > 1) return 1;  // (one grid row per sample)
+  if (n < 1 || n > 65535 || L < 1 || P < 1 || (!slot && (node < 0 || node > 1))) return 1;  // (one grid row per sample)
   const size_t lds = anc_lds_bytes(T);
   if (lds > 160 * 1024) return 1;
   launch_ancestral_front(fam, n, R, T, ops, pi, site_lik, site_scal, naive_prob, path, P, ws, nullptr, hdr, err_flag, stream);
   auto run = [&](auto kernel) {
     launch_lds(kernel, dim3(R, n), dim3(256), lds, stream, R, T, fam.n_prune, P, fam.msa,
                static_cast<const AsrOp*>(ws.desc), brlen, rates, eig, pi, site_lik, site_scal, ws.chain, ws.plen,
-               reinterpret_cast<double2*>(ws.clv), (int)anc_lp(fam.n_prune), ws.part);
+               reinterpret_cast<double2*>(ws.clv), (int)anc_lp(fam.n_prune), ws.part, slot);
   };
-  if (node == 1)
-    run(cond_kernel<true>);
-  else
-    run(cond_kernel<false>);
+  if (slot) {
+    hipLaunchKernelGGL(slot_check_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, n, slot_row0, slot, ws.plen,
+                       err_flag);
+    run(cond_kernel<kCondSlot>);
+  } else if (node == 1) {
+    run(cond_kernel<kCondMrca>);
+  } else {
+    run(cond_kernel<kCondParent>);
+  }
   launch_rate_sum(n, R, 1, (size_t)NP * 20, false, ws.plen, ws.part, table, stream);
   if (cond) {
     const long long out = (long long)n * L * 5;

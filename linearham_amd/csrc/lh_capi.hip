@@ -229,7 +229,7 @@ struct AsrWs {  // K3's scratch
 
 struct AncestralWs {  // K11's scratch (lh::AncWs) and the arrays its callers do not hand in
   DevBuf clv, part, tvec, rho, chain, plen, desc;
-  DevBuf naive_prob, path;  // the host-pointer forms' device copies
+  DevBuf naive_prob, path, slot;  // the host-pointer forms' device copies
   DevBuf marg, rate_post;
   // lh_eval_ancestral_batch: K11a's table (built by the first call), its output, and the reduction's arrays
   bool have_table = false;
@@ -489,7 +489,9 @@ struct lh_family {
   lh::DevSampler sampler{};  // device pointers inside (arena)
   const lh::DevSampler* sampler_dev = nullptr;  // its device copy (K4 reads the tables' addresses from memory)
   int32_t n_ucol_used = 0;  // (naive base, pattern) pairs some xMSA column has (lh_family_info)
-  int32_t* err_flag = nullptr;  // device word (arena): K0c sets it when a schedule is malformed (lh_family_status)
+  // two device words (arena).  [0]: bit 0, K0c met a malformed schedule; bit 1, K11c / K12c a bad path or seed; bit 2, a slot
+  // outside its path, and [1] = 0x7fffffff - the first such row of its call (lh_family_status reads and clears both)
+  int32_t* err_flag = nullptr;
   std::string k1_form;          // the K1 kernel form of the last evaluation (lh_family_prune_form)
   std::string k2_form;          // the K2 kernels of the last forward sweep (lh_family_forward_form)
   int k2_dj_samples = 0;        // samples per wave of its D-J kernel (lh_family_forward_dj_samples)
@@ -819,11 +821,15 @@ int run_forward(lh_family* f, int n, int R, const double* site_lik, const int32_
 
 // Reads (and clears) the handle's asynchronous error word after synchronising its device.
 int check_async_error(lh_family* f, const char* who) {
-  int32_t flag = 0;
+  int32_t word[2] = {0, 0};
   LH_HIP(hipDeviceSynchronize());
-  LH_HIP(hipMemcpy(&flag, f->err_flag, sizeof(flag), hipMemcpyDeviceToHost));
+  LH_HIP(hipMemcpy(word, f->err_flag, sizeof(word), hipMemcpyDeviceToHost));
+  const int32_t flag = word[0];
   if (flag) {
-    LH_HIP(hipMemset(f->err_flag, 0, sizeof(flag)));
+    LH_HIP(hipMemset(f->err_flag, 0, sizeof(word)));
+    if ((flag & 4) && !(flag & 1))  // (K13b's slot check; it takes the place of the path's message)
+      return fail(std::string(who) + ": slot of sample " + std::to_string(0x7fffffff - word[1]) +
+                  " lies outside the sample's lineage path (0 .. its length - 1); the affected samples' results are NaN");
     if (flag == 2)  // (K11c's and K12c's bit alone)
       return fail(std::string(who) + ": lineage path that is not a chain up to the root, or (edge tables) a seed tip that is not a "
                                      "child of its first node; the affected samples' results are NaN");
@@ -1173,7 +1179,7 @@ int lh_family_create(const lh_family_desc* desc, lh_family** out) {
   }
   {
     void* p = nullptr;
-    if (arena_alloc(f, sizeof(int32_t), &p) || hipMemset(p, 0, sizeof(int32_t)) != hipSuccess) {
+    if (arena_alloc(f, 2 * sizeof(int32_t), &p) || hipMemset(p, 0, 2 * sizeof(int32_t)) != hipSuccess) {
       lh_family_destroy(f);
       return fail("lh_family_create: device allocation failed");
     }
@@ -2308,6 +2314,7 @@ struct LineageCall {
   std::vector<RowOut> rows;
   const double* log_offset = nullptr;  // the eval forms' (lh_posterior_outputs' members)
   double *loglik = nullptr, *weight_stats = nullptr;
+  const int32_t* slot = nullptr;  // K13 / K14 at a node per row: [n] slots of `path` (null: the entry point's `node`)
   double* em_out = nullptr;  // the eval forms': a launch group's emissions in caller columns, [chunk][n_xmsa] (null: not formed)
   // the eval forms': called per launch group with (samples, first sample, the group's forward arrays, its log-likelihoods,
   // stream) before K5 overwrites the forward arrays (K14 runs K9 there); empty: nothing is called
@@ -2434,6 +2441,13 @@ int lineage_batch(lh_family* f, const std::string& W, const TreeBatch& host, con
                   " is not a chain of inner nodes, each the child of the next, that ends at the root (padding after it)");
     if (bad == kNotChild)
       return fail(W + ": seed_tip " + std::to_string(c.seed_tip) + " is not a child of path[0] of sample " + std::to_string(i));
+    if (c.slot) {
+      int len = 0;  // (a chain: the inner nodes lead)
+      while (len < P && c.path[i * P + len] >= host.T && c.path[i * P + len] <= 2 * host.T - 3) ++len;
+      if (c.slot[i] < 0 || c.slot[i] >= len)
+        return fail(W + ": slot " + std::to_string(c.slot[i]) + " of sample " + std::to_string(i) +
+                    " lies outside the sample's lineage path (0 .. " + std::to_string(len - 1) + ")");
+    }
   }
   AncestralWs& a = f->anc;
   HostOutputs& out = f->out;
@@ -2456,13 +2470,15 @@ int lineage_batch(lh_family* f, const std::string& W, const TreeBatch& host, con
         stage_batch(f, host.slice((int)off, (int)m),
                     {{c.naive_prob ? c.naive_prob + off * NP : nullptr, sizeof(double) * NP * m, &a.naive_prob},
                      {c.log_offset ? c.log_offset + off : nullptr, sizeof(double) * m, &f->in.log_offset},
-                     {c.path + off * P, sizeof(int32_t) * P * m, &a.path}},
+                     {c.path + off * P, sizeof(int32_t) * P * m, &a.path},
+                     {c.slot ? c.slot + off : nullptr, sizeof(int32_t) * m, &a.slot}},
                     &dev))
       return 1;
     back.push_back({c.weight_stats, d.weight_stats, sizeof(double) * 3});
     d.naive_prob = c.naive_prob ? a.naive_prob.get<const double>() : nullptr;
     d.log_offset = c.log_offset ? f->in.log_offset.get<const double>() : nullptr;
     d.path = a.path.get<const int32_t>();
+    d.slot = c.slot ? a.slot.get<const int32_t>() : nullptr;
     if (device(dev, d)) return 1;
     if (evaluated ? finish_batch(f, W.c_str(), host.slice((int)off, (int)m), back) : copy_back(f, W.c_str(), back)) return 1;
   }
@@ -2608,9 +2624,9 @@ LineageCall probs_call(lh_family* f, int P, const int32_t* path, const lh_ancest
   return {nullptr, path, P, 0, probs_rows(f, o), o.log_offset, o.loglik, o.weight_stats};
 }
 
-int probs_check(const lh_family* f, const std::string& W, const TreeBatch& b, int P, int node) {
+int probs_check(const lh_family* f, const std::string& W, const TreeBatch& b, int P, int node, bool at_slot = false) {
   if (ancestral_check(f, W, b, P)) return 1;
-  if (node != 0 && node != 1) return fail(W + ": node must be 0 (the seed's parent) or 1 (the MRCA)");
+  if (!at_slot && node != 0 && node != 1) return fail(W + ": node must be 0 (the seed's parent) or 1 (the MRCA)");
   if (f->probs.K == 0) return fail(W + ": lh_family_set_ancestral_candidates has not been called");
   if (f->extended)
     return fail(W + ": not available on a handle in the extended-range mode: the candidates' sweeps run on plain doubles, and the "
@@ -2664,7 +2680,8 @@ auto probs_launch(lh_family* f, const LineageCall& c, int node, size_t pairs, bo
     if (f->profile && t.begin(stream)) return 1;
     if (lh::launch_ancestral_cond(f->host, g.n, g.R, g.T, g.ops, g.brlen, rates, w.eig.get<double>(), g.pi,
                                   w.site_lik.get<double>(), w.site_scal.get<int32_t>(), naive_prob, c.path + off * c.P, c.P, node,
-                                  ws, p.table.get<double>(), c.rows[kCond].group(off), w.prune.hdr, f->err_flag, stream))
+                                  ws, p.table.get<double>(), c.rows[kCond].group(off), w.prune.hdr, f->err_flag, stream,
+                                  c.slot ? c.slot + off : nullptr, (int)off))
       return 1;
     if (f->profile && t.mark(1, stream)) return 1;
     if (sweeps) {
@@ -2716,9 +2733,9 @@ std::vector<RowOut> node_codons_rows(lh_family* f, bool given, const lh_node_cod
           {o.change, C * 4, &k.out_change, &k.change, false, o.weighted_change, &k.partial_h, &k.out_wchange}};
 }
 
-int node_codons_check(const lh_family* f, const std::string& W, const TreeBatch& b, int P, int node) {
+int node_codons_check(const lh_family* f, const std::string& W, const TreeBatch& b, int P, int node, bool at_slot = false) {
   if (ancestral_check(f, W, b, P)) return 1;
-  if (node != 0 && node != 1) return fail(W + ": node must be 0 (the seed's parent) or 1 (the MRCA)");
+  if (!at_slot && node != 0 && node != 1) return fail(W + ": node must be 0 (the seed's parent) or 1 (the MRCA)");
   if (f->codon.frame < 0) return fail(W + ": lh_family_set_codons has not been called");
   return 0;
 }
@@ -2817,7 +2834,8 @@ auto node_codons_launch(lh_family* f, const LineageCall& c, int node, bool given
     if (f->profile && t.begin(stream)) return 1;
     if (lh::launch_ancestral_cond(f->host, g.n, g.R, g.T, g.ops, g.brlen, rates, w.eig.get<double>(), g.pi,
                                   w.site_lik.get<double>(), w.site_scal.get<int32_t>(), site_base, c.path + off * c.P, c.P, node,
-                                  ws, p.table.get<double>(), nullptr, w.prune.hdr, f->err_flag, stream))
+                                  ws, p.table.get<double>(), nullptr, w.prune.hdr, f->err_flag, stream, c.slot ? c.slot + off : nullptr,
+                                  (int)off))
       return 1;
     if (!given)
       lh::launch_naive_codons(k.tab, g.n, k.windows.get<const double>(), k.genes.get<const double>(), k.naive.get<double>(), stream);
@@ -2871,6 +2889,59 @@ LineageCall node_codons_call(lh_family* f, int P, const double* naive_codons, co
   o.codons = codons;
   o.change = change;
   return {naive_codons, path, P, 0, node_codons_rows(f, true, o)};
+}
+
+// The bodies of K13's and K14's entry points.  `at` false: the node is `node` (0 or 1); else slot[i], a slot of its own path for
+// every row (`at`; `node` is not looked at).  `device`: the arrays are the device's and the call is queued on
+// hip_stream; else they are the host's.
+
+int candidates_entry(lh_family* f, const std::string& W, const TreeBatch& b, const int32_t* path, int P, int node,
+                     bool at, const int32_t* slot, const lh_ancestral_candidates_outputs* outs, bool device, void* hip_stream) {
+  if (int rc = check_batch(f, W, b, true)) return rc > 0;
+  if (probs_check(f, W, b, P, node, at)) return 1;
+  DeviceGuard guard(f);
+  if (!b.has_arrays() || !path || (at && !slot)) return fail(W + ": null array");
+  LineageCall c = probs_call(f, P, path, outs);
+  c.slot = slot;
+  if (device) return eval_probs_device(f, W, b, c, node, hip_stream);
+  if (!c.asked()) return 0;
+  if (refuse_oversize(W, b.n, c, lh::debug_options().anc_out_mb)) return 1;  // (K11's rule)
+  return lineage_batch(f, W, b, c, b.n,
+                       [&](const TreeBatch& dev, LineageCall d) { return eval_probs_device(f, W, dev, d, node, nullptr); });
+}
+
+int eval_node_codons_entry(lh_family* f, const std::string& W, const TreeBatch& b, const int32_t* path, int P, int node,
+                           bool at, const int32_t* slot, const lh_node_codons_outputs* outs, bool device, void* hip_stream) {
+  if (int rc = check_batch(f, W, b, true)) return rc > 0;
+  if (node_codons_check(f, W, b, P, node, at)) return 1;
+  DeviceGuard guard(f);
+  if (!b.has_arrays() || !path || (at && !slot)) return fail(W + ": null array");
+  LineageCall c = node_codons_call(f, P, path, outs);
+  c.slot = slot;
+  if (device) return eval_node_codons_device(f, W, b, c, node, hip_stream);
+  if (!c.asked()) return 0;
+  if (refuse_oversize(W, b.n, c, lh::debug_options().anc_out_mb)) return 1;  // (K11's rule)
+  return lineage_batch(f, W, b, c, b.n,
+                       [&](const TreeBatch& dev, LineageCall d) { return eval_node_codons_device(f, W, dev, d, node, nullptr); });
+}
+
+int asr_node_codons_entry(lh_family* f, const std::string& W, const TreeBatch& b, const double* naive_codons,
+                          const int32_t* path, int P, int node, bool at, const int32_t* slot, double* codons, double* change,
+                          bool device, void* hip_stream) {
+  if (int rc = check_batch(f, W, b)) return rc > 0;
+  if (node_codons_check(f, W, b, P, node, at)) return 1;
+  DeviceGuard guard(f);
+  if (!b.has_arrays() || !naive_codons || !path || (at && !slot)) return fail(W + ": null array");
+  LineageCall c = node_codons_call(f, P, naive_codons, path, codons, change);
+  c.slot = slot;
+  if (!c.asked()) return 0;  // nothing asked for
+  if (device) return asr_node_codons_device(f, W, b, c, node, hip_stream);
+  // no refusal here: sub-batches bound the device copies of the inputs and outputs (as lh_asr_marginals_batch)
+  const size_t per = c.copy_bytes(true) + c.rows[kSiteBase].bytes(1);
+  const size_t sub = std::max<size_t>(1, std::min<size_t>(b.n, ((size_t)1 << 30) / std::max<size_t>(per, 1)));
+  return lineage_batch(f, W, b, c, sub, [&](const TreeBatch& dev, const LineageCall& d) {
+    return asr_node_codons_device(f, W, dev, d, node, nullptr);
+  });
 }
 
 // ---- K15: exact amino-acid replacement posteriors along the edges of a seed's lineage (lh_codon_edges.hip) ----
@@ -3177,31 +3248,32 @@ int lh_eval_ancestral_candidates_batch_device(lh_family* f, int32_t n, int32_t T
                                               const double* brlen, const double* er, const double* pi, const double* alpha,
                                               int32_t R, const int32_t* path, int32_t P, int32_t node,
                                               const lh_ancestral_candidates_outputs* outs, void* hip_stream) {
-  const TreeBatch b{n, T, max_depth, ops, brlen, er, pi, alpha, R};
-  const std::string W = "lh_eval_ancestral_candidates_batch";
-  if (int rc = check_batch(f, W, b, true)) return rc > 0;
-  if (probs_check(f, W, b, P, node)) return 1;
-  DeviceGuard guard(f);
-  if (!b.has_arrays() || !path) return fail(W + ": null array");
-  LineageCall c = probs_call(f, P, path, outs);
-  return eval_probs_device(f, W, b, c, node, hip_stream);
+  return candidates_entry(f, "lh_eval_ancestral_candidates_batch", {n, T, max_depth, ops, brlen, er, pi, alpha, R}, path, P, node,
+                          false, nullptr, outs, true, hip_stream);
 }
 
 int lh_eval_ancestral_candidates_batch(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops,
                                        const double* brlen, const double* er, const double* pi, const double* alpha, int32_t R,
                                        const int32_t* path, int32_t P, int32_t node,
                                        const lh_ancestral_candidates_outputs* outs) {
-  const TreeBatch host{n, T, max_depth, ops, brlen, er, pi, alpha, R};
-  const std::string W = "lh_eval_ancestral_candidates_batch";
-  if (int rc = check_batch(f, W, host, true)) return rc > 0;
-  if (probs_check(f, W, host, P, node)) return 1;
-  DeviceGuard guard(f);
-  if (!host.has_arrays() || !path) return fail(W + ": null array");
-  const LineageCall c = probs_call(f, P, path, outs);
-  if (!c.asked()) return 0;
-  if (refuse_oversize(W, n, c, lh::debug_options().anc_out_mb)) return 1;  // (K11's rule)
-  return lineage_batch(f, W, host, c, n,
-                       [&](const TreeBatch& dev, LineageCall d) { return eval_probs_device(f, W, dev, d, node, nullptr); });
+  return candidates_entry(f, "lh_eval_ancestral_candidates_batch", {n, T, max_depth, ops, brlen, er, pi, alpha, R}, path, P, node,
+                          false, nullptr, outs, false, nullptr);
+}
+
+int lh_eval_ancestral_candidates_at_batch_device(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops,
+                                                 const double* brlen, const double* er, const double* pi, const double* alpha,
+                                                 int32_t R, const int32_t* path, int32_t P, const int32_t* slot,
+                                                 const lh_ancestral_candidates_outputs* outs, void* hip_stream) {
+  return candidates_entry(f, "lh_eval_ancestral_candidates_at_batch", {n, T, max_depth, ops, brlen, er, pi, alpha, R}, path, P, 0,
+                          true, slot, outs, true, hip_stream);
+}
+
+int lh_eval_ancestral_candidates_at_batch(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops,
+                                          const double* brlen, const double* er, const double* pi, const double* alpha, int32_t R,
+                                          const int32_t* path, int32_t P, const int32_t* slot,
+                                          const lh_ancestral_candidates_outputs* outs) {
+  return candidates_entry(f, "lh_eval_ancestral_candidates_at_batch", {n, T, max_depth, ops, brlen, er, pi, alpha, R}, path, P, 0,
+                          true, slot, outs, false, nullptr);
 }
 
 int lh_ancestral_candidates_profile_read(lh_family* f, double* ms, int64_t* n_launches) {
@@ -3221,64 +3293,60 @@ int lh_eval_node_codons_batch_device(lh_family* f, int32_t n, int32_t T, int32_t
                                      const double* brlen, const double* er, const double* pi, const double* alpha, int32_t R,
                                      const int32_t* path, int32_t P, int32_t node, const lh_node_codons_outputs* outs,
                                      void* hip_stream) {
-  const TreeBatch b{n, T, max_depth, ops, brlen, er, pi, alpha, R};
-  const std::string W = "lh_eval_node_codons_batch";
-  if (int rc = check_batch(f, W, b, true)) return rc > 0;
-  if (node_codons_check(f, W, b, P, node)) return 1;
-  DeviceGuard guard(f);
-  if (!b.has_arrays() || !path) return fail(W + ": null array");
-  LineageCall c = node_codons_call(f, P, path, outs);
-  return eval_node_codons_device(f, W, b, c, node, hip_stream);
+  return eval_node_codons_entry(f, "lh_eval_node_codons_batch", {n, T, max_depth, ops, brlen, er, pi, alpha, R}, path, P, node,
+                                false, nullptr, outs, true, hip_stream);
 }
 
 int lh_eval_node_codons_batch(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops, const double* brlen,
                               const double* er, const double* pi, const double* alpha, int32_t R, const int32_t* path, int32_t P,
                               int32_t node, const lh_node_codons_outputs* outs) {
-  const TreeBatch host{n, T, max_depth, ops, brlen, er, pi, alpha, R};
-  const std::string W = "lh_eval_node_codons_batch";
-  if (int rc = check_batch(f, W, host, true)) return rc > 0;
-  if (node_codons_check(f, W, host, P, node)) return 1;
-  DeviceGuard guard(f);
-  if (!host.has_arrays() || !path) return fail(W + ": null array");
-  const LineageCall c = node_codons_call(f, P, path, outs);
-  if (!c.asked()) return 0;
-  if (refuse_oversize(W, n, c, lh::debug_options().anc_out_mb)) return 1;  // (K11's rule)
-  return lineage_batch(f, W, host, c, n,
-                       [&](const TreeBatch& dev, LineageCall d) { return eval_node_codons_device(f, W, dev, d, node, nullptr); });
+  return eval_node_codons_entry(f, "lh_eval_node_codons_batch", {n, T, max_depth, ops, brlen, er, pi, alpha, R}, path, P, node,
+                                false, nullptr, outs, false, nullptr);
+}
+
+int lh_eval_node_codons_at_batch_device(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops,
+                                        const double* brlen, const double* er, const double* pi, const double* alpha, int32_t R,
+                                        const int32_t* path, int32_t P, const int32_t* slot, const lh_node_codons_outputs* outs,
+                                        void* hip_stream) {
+  return eval_node_codons_entry(f, "lh_eval_node_codons_at_batch", {n, T, max_depth, ops, brlen, er, pi, alpha, R}, path, P, 0,
+                                true, slot, outs, true, hip_stream);
+}
+
+int lh_eval_node_codons_at_batch(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops, const double* brlen,
+                                 const double* er, const double* pi, const double* alpha, int32_t R, const int32_t* path,
+                                 int32_t P, const int32_t* slot, const lh_node_codons_outputs* outs) {
+  return eval_node_codons_entry(f, "lh_eval_node_codons_at_batch", {n, T, max_depth, ops, brlen, er, pi, alpha, R}, path, P, 0,
+                                true, slot, outs, false, nullptr);
 }
 
 int lh_asr_node_codons_batch_device(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops,
                                     const double* brlen, const double* er, const double* pi, const double* rates, int32_t R,
                                     const double* naive_codons, const int32_t* path, int32_t P, int32_t node, double* codons,
                                     double* change, void* hip_stream) {
-  const TreeBatch b{n, T, max_depth, ops, brlen, er, pi, rates, R, true};
-  const std::string W = "lh_asr_node_codons_batch";
-  if (int rc = check_batch(f, W, b)) return rc > 0;
-  if (node_codons_check(f, W, b, P, node)) return 1;
-  DeviceGuard guard(f);
-  if (!b.has_arrays() || !naive_codons || !path) return fail(W + ": null array");
-  const LineageCall c = node_codons_call(f, P, naive_codons, path, codons, change);
-  if (!c.asked()) return 0;  // nothing asked for
-  return asr_node_codons_device(f, W, b, c, node, hip_stream);
+  return asr_node_codons_entry(f, "lh_asr_node_codons_batch", {n, T, max_depth, ops, brlen, er, pi, rates, R, true}, naive_codons,
+                               path, P, node, false, nullptr, codons, change, true, hip_stream);
 }
 
 int lh_asr_node_codons_batch(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops, const double* brlen,
                              const double* er, const double* pi, const double* rates, int32_t R, const double* naive_codons,
                              const int32_t* path, int32_t P, int32_t node, double* codons, double* change) {
-  const TreeBatch host{n, T, max_depth, ops, brlen, er, pi, rates, R, true};
-  const std::string W = "lh_asr_node_codons_batch";
-  if (int rc = check_batch(f, W, host)) return rc > 0;
-  if (node_codons_check(f, W, host, P, node)) return 1;
-  DeviceGuard guard(f);
-  if (!host.has_arrays() || !naive_codons || !path) return fail(W + ": null array");
-  const LineageCall c = node_codons_call(f, P, naive_codons, path, codons, change);
-  if (!c.asked()) return 0;
-  // no refusal here: sub-batches bound the device copies of the inputs and outputs (as lh_asr_marginals_batch)
-  const size_t per = c.copy_bytes(true) + c.rows[kSiteBase].bytes(1);
-  const size_t sub = std::max<size_t>(1, std::min<size_t>(n, ((size_t)1 << 30) / std::max<size_t>(per, 1)));
-  return lineage_batch(f, W, host, c, sub, [&](const TreeBatch& dev, const LineageCall& d) {
-    return asr_node_codons_device(f, W, dev, d, node, nullptr);
-  });
+  return asr_node_codons_entry(f, "lh_asr_node_codons_batch", {n, T, max_depth, ops, brlen, er, pi, rates, R, true}, naive_codons,
+                               path, P, node, false, nullptr, codons, change, false, nullptr);
+}
+
+int lh_asr_node_codons_at_batch_device(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops,
+                                       const double* brlen, const double* er, const double* pi, const double* rates, int32_t R,
+                                       const double* naive_codons, const int32_t* path, int32_t P, const int32_t* slot,
+                                       double* codons, double* change, void* hip_stream) {
+  return asr_node_codons_entry(f, "lh_asr_node_codons_at_batch", {n, T, max_depth, ops, brlen, er, pi, rates, R, true},
+                               naive_codons, path, P, 0, true, slot, codons, change, true, hip_stream);
+}
+
+int lh_asr_node_codons_at_batch(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops, const double* brlen,
+                                const double* er, const double* pi, const double* rates, int32_t R, const double* naive_codons,
+                                const int32_t* path, int32_t P, const int32_t* slot, double* codons, double* change) {
+  return asr_node_codons_entry(f, "lh_asr_node_codons_at_batch", {n, T, max_depth, ops, brlen, er, pi, rates, R, true},
+                               naive_codons, path, P, 0, true, slot, codons, change, false, nullptr);
 }
 
 int lh_node_codon_classes(uint8_t* classes) {

@@ -521,6 +521,10 @@ int launch_substitutions(const DevFamily& fam, int n, int R, int T, const int32_
 // [n][n_prune + 1][5][4], P(x_node = c | column of the pattern, naive base b), NaN for a sample without a valid path (*err_flag
 // raised, ws.plen 0); cond[n][n_sites][5][4] (may be null) is the same table per site.  Scratch: AncWs with `part` sized by
 // cond_ws_bytes.  Returns nonzero if the launch cannot be made (LDS tables, grid).
+// slot (may be null: `node` decides, and the launch is one of the two fixed forms): [n] device array, for every sample the
+// slot of its own path the table is formed at; `node` is then not looked at.  A slot outside 0 .. plen - 1 leaves the sample
+// without a path (ws.plen 0) and raises bit 2 of err_flag[0]; err_flag[1] keeps 0x7fffffff - (slot_row0 + the first such
+// sample), slot_row0 being the launch group's first row in its call.
 struct CondWsBytes {
   size_t part, table;  // per sample
 };
@@ -529,7 +533,7 @@ int launch_ancestral_cond(const DevFamily& fam, int n, int R, int T, const int32
                           const double* rates, const double* eig, const double* pi, const double* site_lik,
                           const int32_t* site_scal, const double* naive_prob, const int32_t* path, int P, int node,
                           const AncWs& ws, double* table, double* cond, const int4* hdr, int32_t* err_flag,
-                          hipStream_t stream);
+                          hipStream_t stream, const int32_t* slot = nullptr, int slot_row0 = 0);
 // em[n][C] = 0 in the rows whose plen is 0
 void launch_row_mask(int n, int C, const int32_t* plen, double* em, hipStream_t stream);
 // K13e for the pairs q0 .. q0 + count of a launch group, pair q = row * K + candidate: out[count][C] from the group's

@@ -83,6 +83,28 @@ def seed_path(n_tips, children, root, seed_tip):
     return [int(v) for v in path[:n.value]]
 
 
+def clade_slot(n_tips, children, root, seed_tip, with_tips):
+    """(path, slot): the seed's `path` row (seed_path) and the index on it of the most recent common ancestor of the seed
+    and the tips `with_tips` -- linearham::CladeSlot.  That node means the same in every tree sample though its slot
+    differs; the `_at` entry points of K13 and K14 take the slot per row.  Raises ValueError, naming the offender, for an
+    empty list, tip 0 (naive), a tip outside 1 .. n_tips - 1, the seed itself or a repeated tip.  No device needed."""
+    import numpy as np
+    children = np.ascontiguousarray(children, dtype=np.int32).ravel()
+    T = int(n_tips)
+    if children.size != 2 * (T - 2):
+        raise ValueError("clade_slot: children must hold 2 (n_tips - 2) entries")
+    tips = np.ascontiguousarray([int(t) for t in with_tips], dtype=np.int32)
+    path = np.zeros(max(T - 2, 1), dtype=np.int32)
+    n, slot = C.c_int(), C.c_int()
+    lib = load_host()
+    lib.lhh_clade_slot.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                   C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    if lib.lhh_clade_slot(children.ctypes.data, T, int(root), int(seed_tip), tips.ctypes.data, len(tips), path.ctypes.data,
+                          len(path), C.byref(n), C.byref(slot)) != 0:
+        raise ValueError(lib.lhh_last_error().decode())
+    return [int(v) for v in path[:n.value]], slot.value
+
+
 def read_ancestral_marginals(prefix):
     """The files of PhyloHMM::RunAncestralMarginalsPipeline: dict(parent [L][4], mrca [L][4], map_base {"parent", "mrca"},
     rates [L][R], rows [(row, weight, chain_length)], summary)."""
@@ -112,10 +134,8 @@ def read_ancestral_probs(prefix):
     import numpy as np
     lines = [ln.split("\t") for ln in open(prefix + ".probs.tsv").read().strip("\n").split("\n")]
     assert lines[0] == ["name", "sequence", "probability"], lines[0]
-    rows = [ln.split("\t") for ln in open(prefix + ".rows.tsv").read().strip().split("\n")]
-    assert rows[0] == ["row", "weight", "chain_length"]
     return dict(names=[c[0] for c in lines[1:]], seqs=[c[1] for c in lines[1:]], prob=np.array([float(c[2]) for c in lines[1:]]),
-                rows=[(int(r[0]), float(r[1]), int(r[2])) for r in rows[1:]],
+                rows=_seed_rows(prefix),
                 summary=_parse_summary(open(prefix + ".summary.tsv").read()))
 
 
@@ -143,13 +163,12 @@ def read_node_codons(prefix):
     """The files of PhyloHMM::RunNodeCodonsPipeline: parse_node_codons' dict plus rows [(row, weight, chain_length)] and
     summary."""
     res = parse_node_codons("\n".join(open(prefix + ext).read() for ext in (".codons.tsv", ".aa.tsv", ".changes.tsv")))
-    rows = [ln.split("\t") for ln in open(prefix + ".rows.tsv").read().strip().split("\n")]
-    assert rows[0] == ["row", "weight", "chain_length"]
-    res["rows"] = [(int(r[0]), float(r[1]), int(r[2])) for r in rows[1:]]
+    res["rows"] = _seed_rows(prefix)
     summary = {}
     for ln in open(prefix + ".summary.tsv").read().strip().split("\n")[1:]:
         k, v = ln.split("\t")
-        summary[k] = v if k == "node" else int(v) if k in ("rows_used", "rows_skipped_nonfinite", "frame") else float(v)
+        summary[k] = v if k == "node" else None if v == "NA" else \
+            int(v) if k in ("rows_used", "rows_skipped_nonfinite", "frame", "slot_min", "slot_max") else float(v)
     res["summary"] = summary
     return res
 
@@ -224,7 +243,8 @@ def lineage_replacements_write(codon_counts, aa_counts, seed_change, frame=0):
 
 
 def parse_lineage_node(name):
-    """--node's values: "parent" -> 0 (the seed's parent), "mrca" -> 1 (linearham::ParseLineageNode)."""
+    """--node's values: "parent" -> 0 (the seed's parent), "mrca" -> 1, "mrca-with:<name>[,<name>...]" -> NODE_MRCA_WITH
+    (linearham::ParseLineageNode; parse_lineage_node_text also gives the names)."""
     lib = load_host()
     lib.lhh_parse_lineage_node.argtypes = [C.c_char_p, C.POINTER(C.c_int)]
     node = C.c_int()
@@ -239,6 +259,38 @@ def read_named_candidates(path, n_sites):
     out = C.c_char_p()
     _check(lib.lhh_read_named_candidates(path.encode(), n_sites, C.byref(out)))
     return [tuple(ln.split("\t")) for ln in out.value.decode().strip("\n").split("\n")]
+
+
+NODE_MRCA_WITH = 2  # parse_lineage_node's value for "mrca-with:<name>[,<name>...]"
+
+
+def parse_lineage_node_text(text):
+    """(node, names) of --node's text (linearham::ParseLineageNodeText): (0, []) for "parent", (1, []) for "mrca" and
+    (NODE_MRCA_WITH, names) for "mrca-with:<name>[,<name>...]", the most recent common ancestor of the seed and the named
+    sequences."""
+    lib = load_host()
+    lib.lhh_parse_lineage_node_text.argtypes = [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_char_p)]
+    node, names = C.c_int(), C.c_char_p()
+    _check(lib.lhh_parse_lineage_node_text(text.encode(), C.byref(node), C.byref(names)))
+    return node.value, [n for n in names.value.decode().split("\n") if n]
+
+
+def _node_arg(node):
+    """How PhyloHMM's methods hand `node` on: (entry-point suffix, argument, its ctype).  "mrca-with:..." goes as text to
+    the `_at` entry points; the two old words and integers take the integer ones, as before."""
+    if isinstance(node, str) and node.startswith("mrca-with:"):
+        return "_at", node.encode(), C.c_char_p
+    if isinstance(node, str):
+        node = parse_lineage_node(node)
+    return "", node, C.c_int
+
+
+def _seed_rows(prefix):
+    """.rows.tsv of a pipeline over a seed's lineage: (row, weight, chain_length), and the slot where the node is a
+    'mrca-with' one."""
+    rows = [ln.split("\t") for ln in open(prefix + ".rows.tsv").read().strip().split("\n")]
+    assert rows[0] in (["row", "weight", "chain_length"], ["row", "weight", "chain_length", "slot"]), rows[0]
+    return [(int(r[0]), float(r[1])) + tuple(int(x) for x in r[2:]) for r in rows[1:]]
 
 
 def read_lineage_substitutions(prefix):
@@ -381,7 +433,7 @@ def _parse_summary(text):
     out = {}
     for ln in text.strip().split("\n")[1:]:
         k, v = ln.split("\t")
-        out[k] = None if v == "NA" else (float(v) if k in ("kish_ess", "covered_mass") else int(v))
+        out[k] = None if v == "NA" else v if k == "node" else (float(v) if k in ("kish_ess", "covered_mass") else int(v))
     return out
 
 
@@ -636,44 +688,40 @@ class PhyloHMM(_HMM):
     def ancestral_candidate_posterior(self, seed_seq, node, candidates):
         """PhyloHMM::AncestralCandidatePosterior of the current tree: dict(log_cand [K], node, loglik) for candidate strings
         over ACGTN (N leaves the site open) at node 0 / "parent" (the seed's parent) or 1 / "mrca"."""
-        if isinstance(node, str):
-            node = parse_lineage_node(node)
+        at, node, node_t = _node_arg(node)
         lib = self.lib
-        lib.lhh_phylo_ancestral_candidate_posterior.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_char_p, C.c_int, C.c_void_p,
-                                                                C.POINTER(C.c_int), C.POINTER(C.c_double)]
+        f = getattr(lib, "lhh_phylo_ancestral_candidate_posterior" + at)
+        f.argtypes = [C.c_void_p, C.c_char_p, node_t, C.c_char_p, C.c_int, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_double)]
         lc = np.zeros(len(candidates))
         v, ll = C.c_int(), C.c_double()
-        _check(lib.lhh_phylo_ancestral_candidate_posterior(self.h, seed_seq.encode(), node, "\n".join(candidates).encode(),
-                                                           len(candidates), lc.ctypes.data, C.byref(v), C.byref(ll)))
+        _check(f(self.h, seed_seq.encode(), node, "\n".join(candidates).encode(), len(candidates), lc.ctypes.data, C.byref(v),
+                 C.byref(ll)))
         return dict(log_cand=lc, node=v.value, loglik=ll.value)
 
     def run_ancestral_probs_pipeline(self, input_path, seed_seq, node, candidates_path, output_prefix, num_rates,
                                      burnin_frac=0.0):
         """PhyloHMM::RunAncestralProbsPipeline: importance-weighted exact probabilities of the candidate sequences of a file
         at the seed's parent or MRCA over a RevBayes table; returns read_ancestral_probs(output_prefix)."""
-        if isinstance(node, str):
-            node = parse_lineage_node(node)
-        self.lib.lhh_run_ancestral_probs_pipeline.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_int, C.c_char_p, C.c_char_p,
-                                                              C.c_int, C.c_double]
-        _check(self.lib.lhh_run_ancestral_probs_pipeline(self.h, input_path.encode(), seed_seq.encode(), node,
-                                                         candidates_path.encode(), output_prefix.encode(), num_rates,
-                                                         C.c_double(burnin_frac)))
+        at, node, node_t = _node_arg(node)
+        f = getattr(self.lib, "lhh_run_ancestral_probs_pipeline" + at)
+        f.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, node_t, C.c_char_p, C.c_char_p, C.c_int, C.c_double]
+        _check(f(self.h, input_path.encode(), seed_seq.encode(), node, candidates_path.encode(), output_prefix.encode(),
+                 num_rates, C.c_double(burnin_frac)))
         return read_ancestral_probs(output_prefix)
 
     def node_codon_marginals(self, seed_seq, node, frame=0):
         """PhyloHMM::NodeCodonMarginals of the current tree: dict(codons [n_codons][64], change [n_codons][4], aa, node,
         loglik) at node 0 / "parent" (the seed's parent) or 1 / "mrca"; aa as the host's writer folds it."""
-        if isinstance(node, str):
-            node = parse_lineage_node(node)
+        at, node, node_t = _node_arg(node)
         lib = self.lib
-        lib.lhh_phylo_node_codon_marginals.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
-                                                       C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double),
-                                                       C.POINTER(C.c_char_p)]
+        f = getattr(lib, "lhh_phylo_node_codon_marginals" + at)
+        f.argtypes = [C.c_void_p, C.c_char_p, node_t, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int),
+                      C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_char_p)]
         nc, v, ll, text = C.c_int(), C.c_int(), C.c_double(), C.c_char_p()
-        _check(lib.lhh_phylo_node_codon_marginals(self.h, seed_seq.encode(), node, frame, None, None, 0, C.byref(nc), None, None,
+        _check(f(self.h, seed_seq.encode(), node, frame, None, None, 0, C.byref(nc), None, None,
                                                   None))
         codons, change = np.zeros((nc.value, 64)), np.zeros((nc.value, 4))
-        _check(lib.lhh_phylo_node_codon_marginals(self.h, seed_seq.encode(), node, frame, codons.ctypes.data, change.ctypes.data,
+        _check(f(self.h, seed_seq.encode(), node, frame, codons.ctypes.data, change.ctypes.data,
                                                   nc.value, C.byref(nc), C.byref(v), C.byref(ll), C.byref(text)))
         return dict(codons=codons, change=change, aa=parse_node_codons(text.value.decode())["aa"], node=v.value,
                     loglik=ll.value)
@@ -681,12 +729,11 @@ class PhyloHMM(_HMM):
     def run_node_codons_pipeline(self, input_path, seed_seq, node, output_prefix, num_rates, burnin_frac=0.0, frame=0):
         """PhyloHMM::RunNodeCodonsPipeline: the importance-weighted codon, amino-acid and change tables of the seed's parent
         or MRCA over a RevBayes table; returns read_node_codons(output_prefix)."""
-        if isinstance(node, str):
-            node = parse_lineage_node(node)
-        self.lib.lhh_run_node_codons_pipeline.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_int, C.c_char_p, C.c_int,
-                                                          C.c_double, C.c_int]
-        _check(self.lib.lhh_run_node_codons_pipeline(self.h, input_path.encode(), seed_seq.encode(), node, output_prefix.encode(),
-                                                     num_rates, C.c_double(burnin_frac), frame))
+        at, node, node_t = _node_arg(node)
+        f = getattr(self.lib, "lhh_run_node_codons_pipeline" + at)
+        f.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, node_t, C.c_char_p, C.c_int, C.c_double, C.c_int]
+        _check(f(self.h, input_path.encode(), seed_seq.encode(), node, output_prefix.encode(), num_rates,
+                 C.c_double(burnin_frac), frame))
         return read_node_codons(output_prefix)
 
     def lineage_replacements(self, seed_seq, frame=0):
