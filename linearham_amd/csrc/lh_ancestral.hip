@@ -236,7 +236,6 @@ __global__ void __launch_bounds__(256) anc_kernel(int R, int T, int L, int n_pru
     const int site = min(s0 + lane, L - 1);
     const int pat = min(site_pat[site], n_prune);
     const bool all_n = pat >= n_prune;
-    const double2* cbase = tt.clv_s + pat;
     const double* __restrict__ tj = tvec + ((size_t)sample * L + site) * 5;
     const double rj = rho[((size_t)sample * L + site) * R + rate];
     double A[4];
@@ -250,9 +249,9 @@ __global__ void __launch_bounds__(256) anc_kernel(int R, int T, int L, int n_pru
     }
     for (int s = len - 1; s >= 0; --s) {
       const int word = ch[s];
-      const double2* cv = cbase + (size_t)chain_op(word) * 2 * plane;
-      const double2 lo = cv[0], hi = cv[plane];
-      const double post[4] = {A[0] * lo.x, A[1] * lo.y, A[2] * hi.x, A[3] * hi.y};
+      double c[4];
+      tree_load_clv(tt.clv_s, plane, chain_op(word), pat, c);
+      const double post[4] = {A[0] * c[0], A[1] * c[1], A[2] * c[2], A[3] * c[3]};
       const double sum = (post[0] + post[1]) + (post[2] + post[3]);
       // a category with rho = 0 or an all-zero post contributes 0, not NaN
       const double f = (sum == 0.0 || rj == 0.0) ? 0.0 : rj / sum;
@@ -294,6 +293,22 @@ __global__ void __launch_bounds__(256) rate_sum_kernel(int n, int R, int slots, 
   out[gid] = v;
 }
 
+// out[rows][L][2 W2] from table[rows][n_prune + 1][2 W2], a thread per double2 of the output (W2 a constant: the index
+// arithmetic divides by it)
+template <int W2>
+__global__ void __launch_bounds__(256) site_gather_kernel(long long total, int L, int n_prune,
+                                                          const int32_t* __restrict__ site_pat,
+                                                          const double* __restrict__ table, double* __restrict__ out) {
+  const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (gid >= total) return;
+  const long long cell = gid / W2;  // (row, site)
+  const int q = (int)(gid - cell * W2);
+  const long long row = cell / L;
+  const int site = (int)(cell - row * L);
+  const int pat = min(site_pat[site], n_prune);
+  reinterpret_cast<double2*>(out)[gid] = reinterpret_cast<const double2*>(table)[(row * (n_prune + 1) + pat) * W2 + q];
+}
+
 }  // namespace
 
 void launch_rate_sum(int n, int R, int slots, size_t width, bool last_live, const int32_t* plen, const double* part,
@@ -302,6 +317,19 @@ void launch_rate_sum(int n, int R, int slots, size_t width, bool last_live, cons
   const long long cells = (long long)n * slots * (long long)width;
   hipLaunchKernelGGL(rate_sum_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, stream, n, R, slots,
                      (long long)width, last_live, plen, part, out);
+}
+
+void launch_site_gather(const DevFamily& fam, long long rows, int width, const double* table, double* out,
+                        hipStream_t stream) {
+  const long long total = rows * fam.n_sites * (width / 2);
+  auto run = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, total, fam.n_sites, fam.n_prune,
+                       fam.site_pat, table, out);
+  };
+  if (width == 20)
+    run(site_gather_kernel<10>);  // K13's cond
+  else
+    run(site_gather_kernel<40>);  // K15's cond_edge
 }
 
 size_t anc_lp(int n_prune) { return ((size_t)n_prune + 1 + 7) & ~(size_t)7; }

@@ -23,7 +23,7 @@
 //    The node is a template switch.  kMrca: no down step, the root's CLV stays in the lane's registers and the upward
 //    pass stores only what a later op pops from its stack.  Otherwise (the seed's parent): K11b's walk down the chain.
 //  * K13m (K11m's rate_sum_kernel, lh_ancestral.hip), a thread per cell: the R partial tables added in rate order
-//    (fixed order, no atomics); NaN for a sample without a valid path.  cond_sites_kernel spreads the patterns' tables
+//    (fixed order, no atomics); NaN for a sample without a valid path.  site_gather_kernel spreads the patterns' tables
 //    over the sites for a caller who takes them: cond[n][L][5][4].
 //  * K13e (pair_emission_kernel), a thread per (pair, caller column) of a group of (row, candidate) pairs, pair q = row * K
 //    + candidate: the emissions above.  Rows without a path get 0 (row_mask_kernel does the same to the rows' own
@@ -78,32 +78,12 @@ __global__ void __launch_bounds__(256) cond_kernel(int R, int T, int n_prune, in
 
     // the weight of this category under each naive base
     double w[5];
-    if (all_n) {
-#pragma unroll
-      for (int b = 0; b < 5; ++b) w[b] = 1.0 / (double)R;
-    } else {
-      const RatePlanes planes = rate_planes(site_scal, site_lik, sample, R, n_prune, pat);
-      double z[5], v[5];
-      planes.totals(R, z);
-      planes.values(rate, v);
-#pragma unroll
-      for (int b = 0; b < 5; ++b) w[b] = (z[b] == 0.0 || v[b] == 0.0) ? 0.0 : v[b] / z[b];
-    }
+    tree_rate_weights(site_scal, site_lik, sample, rate, R, n_prune, pat, all_n, w);
 
     // the message into the root from above, per basis vector of the naive tip
     double A[5][4];
-    {
-      double n4[4];
-      tree_tip_col(tiptab, 0, 4, n4);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-#pragma unroll
-        for (int b = 0; b < 4; ++b) A[b][i] = p4[i] * tiptab[b * 4 + i];
-        A[4][i] = p4[i] * n4[i];
-      }
-    }
+    tree_root_messages(tiptab, p4, A);
     if (!kMrca) {
-      const double2* cbase = tt.clv_s + pat;
       for (int s = len - 1; s > stop; --s) {
         // the message into v_{s-1}: the sibling off the path times the message from above, through v_{s-1}'s branch
         double m[4];
@@ -111,12 +91,7 @@ __global__ void __launch_bounds__(256) cond_kernel(int R, int T, int n_prune, in
 #pragma unroll
         for (int b = 0; b < 5; ++b) tree_descend(tt.pin, kc, m, A[b]);
       }
-      const double2* cv = cbase + (size_t)chain_op(ch[stop]) * 2 * plane;
-      const double2 lo = cv[0], hi = cv[plane];
-      node[0] = lo.x;
-      node[1] = lo.y;
-      node[2] = hi.x;
-      node[3] = hi.y;
+      tree_load_clv(tt.clv_s, plane, chain_op(ch[stop]), pat, node);
     }
     if (live) {
       double2* o = reinterpret_cast<double2*>(part_s + (size_t)pat * 20);
@@ -144,21 +119,6 @@ __global__ void __launch_bounds__(256) slot_check_kernel(int n, int row0, const 
   plen[i] = 0;
   atomicOr(err, 4);
   atomicMax(err + 1, 0x7fffffff - (row0 + i));
-}
-
-__global__ void __launch_bounds__(256) cond_sites_kernel(int n, int L, int n_prune, const int32_t* __restrict__ site_pat,
-                                                         const double* __restrict__ table, double* __restrict__ cond) {
-  const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  const long long per = (long long)L * 5;
-  if (gid >= (long long)n * per) return;
-  const int sample = (int)(gid / per);
-  const long long cell = gid - (long long)sample * per;
-  const int site = (int)(cell / 5), b = (int)(cell - (long long)site * 5);
-  const int pat = min(site_pat[site], n_prune);
-  const double2* t = reinterpret_cast<const double2*>(table + (((size_t)sample * (n_prune + 1) + pat) * 5 + b) * 4);
-  double2* o = reinterpret_cast<double2*>(cond + (size_t)gid * 4);
-  o[0] = t[0];
-  o[1] = t[1];
 }
 
 __global__ void __launch_bounds__(256) row_mask_kernel(int n, int C, const int32_t* __restrict__ plen, double* __restrict__ em) {
@@ -237,11 +197,7 @@ int launch_ancestral_cond(const DevFamily& fam, int n, int R, int T, const int32
     run(cond_kernel<kCondParent>);
   }
   launch_rate_sum(n, R, 1, (size_t)NP * 20, false, ws.plen, ws.part, table, stream);
-  if (cond) {
-    const long long out = (long long)n * L * 5;
-    hipLaunchKernelGGL(cond_sites_kernel, dim3((unsigned)((out + 255) / 256)), dim3(256), 0, stream, n, L, fam.n_prune,
-                       fam.site_pat, table, cond);
-  }
+  if (cond) launch_site_gather(fam, n, 20, table, cond, stream);
   return 0;
 }
 

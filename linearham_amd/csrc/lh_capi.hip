@@ -2173,24 +2173,39 @@ int ancestral_check(const lh_family* f, const std::string& W, const TreeBatch& b
   return 0;
 }
 
-// samples per launch group of K11: at most kChunk and 8192 samples and ~8 GB of K11's scratch plus K1's workspace (as asr_group
-// bounds K3's: a group size by memory, at least one sample)
-size_t ancestral_group(const lh_family* f, int T, int R, int P) {
-  const size_t per = lh::anc_ws_bytes(T, f->host.n_sites, R, f->host.n_prune, P).total() + lh::asr_desc_bytes(T) +
-                     eval_bytes_per_sample(f, T, R);
-  return std::max<size_t>(1, std::min<size_t>({(size_t)kChunk, (size_t)8192, ((size_t)8 << 30) / per}));
+// Samples per launch group of a lineage kernel (K11 to K15): at most kChunk and 8192 samples and `budget` bytes of K11's
+// scratch with the family's `own` bytes per sample in place of K11b's partials, K3s's descriptors and K1's workspace (as
+// asr_group bounds K3's: a group size by memory, at least one sample)
+size_t lineage_group(const lh_family* f, int T, int R, int P, size_t own, size_t budget = (size_t)8 << 30) {
+  const lh::AncWsBytes z = lh::anc_ws_bytes(T, f->host.n_sites, R, f->host.n_prune, P);
+  const size_t per = z.total() - z.part + own + lh::asr_desc_bytes(T) + eval_bytes_per_sample(f, T, R);
+  return std::max<size_t>(1, std::min<size_t>({(size_t)kChunk, (size_t)8192, budget / per}));
 }
 
-int ancestral_workspace(lh_family* f, int chunk, int T, int R, int P, bool own_rho, lh::AncWs* ws) {
+// The scratch every lineage kernel takes for a launch group of `chunk` samples: K11's CLVs, K11r's vectors (rho only where
+// no caller's rate_post serves), K11c's chains and lengths, K3s's descriptors, and `part` (null: none), the buffer of the
+// family's per-rate partials at part_bytes a sample.
+int lineage_workspace(lh_family* f, int chunk, int T, int R, int P, bool own_rho, DevBuf* part, size_t part_bytes, lh::AncWs* ws) {
   AncestralWs& a = f->anc;
   const lh::AncWsBytes z = lh::anc_ws_bytes(T, f->host.n_sites, R, f->host.n_prune, P);
   const size_t m = chunk;
-  if (a.clv.ensure(z.clv * m) || a.part.ensure(z.part * m) || a.tvec.ensure(z.tvec * m) || (own_rho && a.rho.ensure(z.rho * m)) ||
-      a.chain.ensure(z.chain * m) || a.plen.ensure(sizeof(int32_t) * m) || a.desc.ensure(lh::asr_desc_bytes(T) * m))
+  if (a.clv.ensure(z.clv * m) || (part && part->ensure(part_bytes * m)) || a.tvec.ensure(z.tvec * m) ||
+      (own_rho && a.rho.ensure(z.rho * m)) || a.chain.ensure(z.chain * m) || a.plen.ensure(sizeof(int32_t) * m) ||
+      a.desc.ensure(lh::asr_desc_bytes(T) * m))
     return 1;
-  *ws = {a.clv.get<double>(), a.part.get<double>(), a.tvec.get<double>(), a.rho.get<double>(), a.chain.get<int32_t>(),
-         a.plen.get<int32_t>(), a.desc.get()};
+  *ws = {a.clv.get<double>(), part ? part->get<double>() : nullptr, a.tvec.get<double>(), a.rho.get<double>(),
+         a.chain.get<int32_t>(), a.plen.get<int32_t>(), a.desc.get()};
   return 0;
+}
+
+// K11's own bytes per sample are K11b's partials
+size_t ancestral_group(const lh_family* f, int T, int R, int P) {
+  return lineage_group(f, T, R, P, lh::anc_ws_bytes(T, f->host.n_sites, R, f->host.n_prune, P).part);
+}
+
+int ancestral_workspace(lh_family* f, int chunk, int T, int R, int P, bool own_rho, lh::AncWs* ws) {
+  return lineage_workspace(f, chunk, T, R, P, own_rho, &f->anc.part,
+                           lh::anc_ws_bytes(T, f->host.n_sites, R, f->host.n_prune, P).part, ws);
 }
 
 // K11a's table: per (site, base) the compact entries (lh_eval_outputs.forward's layout) whose state writes that base on
@@ -2248,29 +2263,20 @@ int edges_check(const lh_family* f, const std::string& W, const TreeBatch& b, in
   return 0;
 }
 
-// samples per launch group of K12, by memory as ancestral_group: K11's scratch without its partials, K12's with the
-// per-slot partials (four times K11's) only where edge is asked for
+// samples per launch group of K12: its own bytes are K12b's partials, the per-slot ones (four times K11's) only where edge is
+// asked for
 size_t edges_group(const lh_family* f, int T, int R, int P, bool with_edge) {
-  const lh::AncWsBytes z = lh::anc_ws_bytes(T, f->host.n_sites, R, f->host.n_prune, P);
-  const size_t per = z.total() - z.part + lh::sub_ws_bytes(f->host.n_sites, R, P).total(with_edge) + lh::asr_desc_bytes(T) +
-                     eval_bytes_per_sample(f, T, R);
-  return std::max<size_t>(1, std::min<size_t>({(size_t)kChunk, (size_t)8192, ((size_t)8 << 30) / per}));
+  return lineage_group(f, T, R, P, lh::sub_ws_bytes(f->host.n_sites, R, P).total(with_edge));
 }
 
 int edges_workspace(lh_family* f, int chunk, int T, int R, int P, bool own_rho, bool with_edge, bool with_seed, lh::AncWs* ws,
                     lh::SubWs* sws) {
-  AncestralWs& a = f->anc;
   EdgesWs& e = f->edges;
-  const lh::AncWsBytes z = lh::anc_ws_bytes(T, f->host.n_sites, R, f->host.n_prune, P);
   const lh::SubWsBytes y = lh::sub_ws_bytes(f->host.n_sites, R, P);
   const size_t m = chunk;
-  if (a.clv.ensure(z.clv * m) || a.tvec.ensure(z.tvec * m) || (own_rho && a.rho.ensure(z.rho * m)) || a.chain.ensure(z.chain * m) ||
-      a.plen.ensure(sizeof(int32_t) * m) || a.desc.ensure(lh::asr_desc_bytes(T) * m) || e.cc.ensure(y.cc * m) ||
-      e.ne.ensure(y.ne * m) || (with_seed && e.se.ensure(y.se * m)) || e.el.ensure(y.el * m) ||
-      (with_edge && e.edge.ensure(y.edge * m)))
+  if (lineage_workspace(f, chunk, T, R, P, own_rho, nullptr, 0, ws) || e.cc.ensure(y.cc * m) || e.ne.ensure(y.ne * m) ||
+      (with_seed && e.se.ensure(y.se * m)) || e.el.ensure(y.el * m) || (with_edge && e.edge.ensure(y.edge * m)))
     return 1;
-  *ws = {a.clv.get<double>(), nullptr, a.tvec.get<double>(), a.rho.get<double>(), a.chain.get<int32_t>(), a.plen.get<int32_t>(),
-         a.desc.get()};
   *sws = {e.cc.get<double>(), e.ne.get<double>(), e.se.get<double>(), e.el.get<double>(), e.edge.get<double>()};
   return 0;
 }
@@ -2487,7 +2493,9 @@ int lineage_batch(lh_family* f, const std::string& W, const TreeBatch& host, con
 
 // ---- K11: exact ancestral-state marginals along a seed's lineage (lh_ancestral.hip) ----
 
-// K11's per-row outputs; `ends` are the two slots of marg that mean the same in every tree, which weighted_sum sums
+// K11's per-row outputs; `ends` are the two slots of marg that mean the same in every tree, which weighted_sum sums.
+// Row 0 (site_base) has a device copy of its own: the given-rates form's input, naive_prob, is staged at its width, and
+// asr_entry's sub-batch rule counts it through copy_bytes.
 enum { kMarg = 1, kEnds, kRatePost };
 std::vector<RowOut> ancestral_rows(lh_family* f, int P, int R, double* site_base, double* marg, double* rate_post,
                                    double* weighted_sum, double* weighted_rate) {
@@ -2634,14 +2642,10 @@ int probs_check(const lh_family* f, const std::string& W, const TreeBatch& b, in
   return 0;
 }
 
-// samples per launch group of K13, by memory as ancestral_group: K11's scratch with K13b's partials in place of K11b's, the
-// tables and the rows' emissions
+// samples per launch group of K13: its own bytes are K13b's partials, the tables and the rows' emissions
 size_t probs_group(const lh_family* f, int T, int R, int P) {
-  const lh::AncWsBytes z = lh::anc_ws_bytes(T, f->host.n_sites, R, f->host.n_prune, P);
   const lh::CondWsBytes y = lh::cond_ws_bytes(R, f->host.n_prune);
-  const size_t per = z.total() - z.part + y.part + y.table + sizeof(double) * (size_t)f->host.n_xmsa + lh::asr_desc_bytes(T) +
-                     eval_bytes_per_sample(f, T, R);
-  return std::max<size_t>(1, std::min<size_t>({(size_t)kChunk, (size_t)8192, ((size_t)8 << 30) / per}));
+  return lineage_group(f, T, R, P, y.part + y.table + sizeof(double) * (size_t)f->host.n_xmsa);
 }
 
 // (row, candidate) pairs per sweep: 256 MiB of emissions, C doubles a pair, at most 32 768 pairs (LH_ANC_PAIRS: test hook)
@@ -2652,20 +2656,12 @@ size_t probs_pairs(const lh_family* f, size_t chunk) {
 }
 
 int probs_workspace(lh_family* f, int chunk, int T, int R, int P, size_t pairs, bool sweeps, lh::AncWs* ws) {
-  AncestralWs& a = f->anc;
   AncProbsWs& p = f->probs;
-  const lh::AncWsBytes z = lh::anc_ws_bytes(T, f->host.n_sites, R, f->host.n_prune, P);
   const lh::CondWsBytes y = lh::cond_ws_bytes(R, f->host.n_prune);
   const size_t m = chunk, C = f->host.n_xmsa;
-  if (a.clv.ensure(z.clv * m) || a.tvec.ensure(z.tvec * m) || a.rho.ensure(z.rho * m) || a.chain.ensure(z.chain * m) ||
-      a.plen.ensure(sizeof(int32_t) * m) || a.desc.ensure(lh::asr_desc_bytes(T) * m) || p.part.ensure(y.part * m) ||
-      p.table.ensure(y.table * m) ||
-      (sweeps && (p.em.ensure(sizeof(double) * C * m) || p.open_ll.ensure(sizeof(double) * m) ||
-                  p.pair_em.ensure(sizeof(double) * C * pairs) || p.pair_ll.ensure(sizeof(double) * pairs))))
-    return 1;
-  *ws = {a.clv.get<double>(), p.part.get<double>(), a.tvec.get<double>(), a.rho.get<double>(), a.chain.get<int32_t>(),
-         a.plen.get<int32_t>(), a.desc.get()};
-  return 0;
+  return lineage_workspace(f, chunk, T, R, P, true, &p.part, y.part, ws) || p.table.ensure(y.table * m) ||
+         (sweeps && (p.em.ensure(sizeof(double) * C * m) || p.open_ll.ensure(sizeof(double) * m) ||
+                     p.pair_em.ensure(sizeof(double) * C * pairs) || p.pair_ll.ensure(sizeof(double) * pairs)));
 }
 
 // K13b on a launch group, then (sweeps) the twin's sweep of the rows' own emissions and, `pairs` pairs at a time, K13e, the
@@ -2722,7 +2718,8 @@ int eval_probs_device(lh_family* f, const std::string& W, const TreeBatch& b, Li
 // ---- K14: exact codon marginals of a node of a seed's lineage (lh_node_codon.hip) ----
 
 // K14's per-row outputs.  Row 0 is what the skeletons lead with: the eval form's site_base (K11r reads it; nobody takes it), the
-// given-rates form's input, the caller's naive codon posteriors.
+// given-rates form's input, the caller's naive codon posteriors.  It has no copy of its own (nobody takes it back), so
+// asr_entry's sub-batch rule adds its bytes to copy_bytes.
 enum { kNodeCodons = 1, kNodeChange };
 std::vector<RowOut> node_codons_rows(lh_family* f, bool given, const lh_node_codons_outputs& o) {
   AncestralWs& a = f->anc;
@@ -2793,30 +2790,62 @@ size_t node_codons_bytes(const lh_family* f) {
   return sizeof(double) * ((size_t)cw.tab.n_window * 125 + cw.tab.n_genes + (size_t)cw.n_codons * 125);
 }
 
-// samples per launch group of K14, by memory as probs_group
+// samples per launch group of K14: its own bytes are K13b's partials, the tables and K14's group arrays
 size_t node_codons_group(const lh_family* f, int T, int R, int P) {
-  const lh::AncWsBytes z = lh::anc_ws_bytes(T, f->host.n_sites, R, f->host.n_prune, P);
   const lh::CondWsBytes y = lh::cond_ws_bytes(R, f->host.n_prune);
-  const size_t per = z.total() - z.part + y.part + y.table + node_codons_bytes(f) + lh::asr_desc_bytes(T) +
-                     eval_bytes_per_sample(f, T, R);
-  return std::max<size_t>(1, std::min<size_t>({(size_t)kChunk, (size_t)8192, ((size_t)8 << 30) / per}));
+  return lineage_group(f, T, R, P, y.part + y.table + node_codons_bytes(f));
 }
 
-// K13's scratch (probs_workspace without the sweeps) and K14's group arrays
-int node_codons_workspace(lh_family* f, int chunk, int T, int R, int P, bool given, lh::AncWs* ws) {
+// ---- what K14 and K15 share around the naive codons ----
+
+// Their group arrays: the given-rates forms' zeros for K11r; else K9's outputs and scratch and the naive codon posteriors
+int naive_codons_workspace(lh_family* f, int chunk, bool given) {
   NodeCodonsWs& k = f->node_codons;
   const CodonWs& cw = f->codon;
   const size_t m = chunk;
-  if (probs_workspace(f, chunk, T, R, P, 0, false, ws)) return 1;
   if (given) return k.zero.ensure(sizeof(double) * 5 * (size_t)f->host.n_sites * m);
   return k.windows.ensure(sizeof(double) * 125 * (size_t)cw.tab.n_window * m) ||
          k.genes.ensure(sizeof(double) * (size_t)cw.tab.n_genes * m) || k.naive.ensure(sizeof(double) * 125 * (size_t)cw.n_codons * m) ||
          f->codon.scratch.ensure(sizeof(double) * 4 * (size_t)cw.tab.max_vec * lh::codon_slots(chunk));
 }
 
-// K13b + K13m on a launch group, the naive codon posteriors of every codon (eval form: from K9's outputs, which
-// before_smoothing left in the handle's arrays; given-rates form: the caller's, handed in as the skeleton's naive_prob) and
-// the contraction.  *group_ll: the group's log-likelihoods (eval form), null otherwise.
+// The eval forms' before_smoothing: K9 on a launch group, reading the forward arrays before K5 smooths them in place; its
+// outputs stay in the handle's arrays, *group_ll receives the group's log-likelihoods.
+auto naive_codons_k9(lh_family* f, KernelTimer<1> lh_family::*timer, const double** group_ll) {
+  return [f, timer, group_ll](int m, size_t, const double* fwd, const double* ll, hipStream_t stream) -> int {
+    NodeCodonsWs& k = f->node_codons;
+    KernelTimer<1>& t = f->*timer;
+    *group_ll = ll;
+    if (f->profile && t.begin(stream)) return 1;
+    lh::launch_codons(f->sampler_dev, f->codon.tab, m, fwd, f->host.forward_size, ll, f->codon.scratch.get<double>(),
+                      k.windows.get<double>(), k.genes.get<double>(), stream);
+    if (f->profile && t.end(stream)) return 1;
+    return 0;
+  };
+}
+
+// Where a launch group of n samples takes the naive codon posteriors *Q and K11r's input *site_base from.  Eval form: the
+// handle's array (launch_naive_codons fills it from K9's outputs behind this) and the skeleton's naive_prob.  Given-rates
+// form: the caller's posteriors, handed in as the skeleton's naive_prob, and zeros (nobody takes K11r's output).
+int naive_codons_inputs(lh_family* f, bool given, int n, const double* naive_prob, hipStream_t stream, const double** Q,
+                        const double** site_base) {
+  NodeCodonsWs& k = f->node_codons;
+  *Q = k.naive.get<const double>();
+  *site_base = naive_prob;
+  if (!given) return 0;
+  *Q = naive_prob;
+  LH_HIP(hipMemsetAsync(k.zero.get(), 0, sizeof(double) * 5 * (size_t)f->host.n_sites * n, stream));
+  *site_base = k.zero.get<const double>();
+  return 0;
+}
+
+// K13's scratch (probs_workspace without the sweeps) and K14's group arrays
+int node_codons_workspace(lh_family* f, int chunk, int T, int R, int P, bool given, lh::AncWs* ws) {
+  return probs_workspace(f, chunk, T, R, P, 0, false, ws) || naive_codons_workspace(f, chunk, given);
+}
+
+// K13b + K13m on a launch group, the naive codon posteriors of every codon (naive_codons_inputs) and the contraction.
+// *group_ll: the group's log-likelihoods (eval form), null otherwise.
 auto node_codons_launch(lh_family* f, const LineageCall& c, int node, bool given, const double* const* group_ll) {
   return [f, &c, node, given, group_ll](const TreeBatch& g, size_t off, const double* rates, const double* naive_prob,
                                         const lh::AncWs& ws, hipStream_t stream) -> int {
@@ -2824,13 +2853,8 @@ auto node_codons_launch(lh_family* f, const LineageCall& c, int node, bool given
     AncProbsWs& p = f->probs;
     NodeCodonsWs& k = f->node_codons;
     KernelTimer<2>& t = f->node_codons_stage_timer;
-    const double* site_base = naive_prob;
-    const double* Q = k.naive.get<const double>();
-    if (given) {
-      Q = naive_prob;
-      LH_HIP(hipMemsetAsync(k.zero.get(), 0, sizeof(double) * 5 * (size_t)f->host.n_sites * g.n, stream));
-      site_base = k.zero.get<const double>();
-    }
+    const double *Q, *site_base;
+    if (naive_codons_inputs(f, given, g.n, naive_prob, stream, &Q, &site_base)) return 1;
     if (f->profile && t.begin(stream)) return 1;
     if (lh::launch_ancestral_cond(f->host, g.n, g.R, g.T, g.ops, g.brlen, rates, w.eig.get<double>(), g.pi,
                                   w.site_lik.get<double>(), w.site_scal.get<int32_t>(), site_base, c.path + off * c.P, c.P, node,
@@ -2853,17 +2877,7 @@ int eval_node_codons_device(lh_family* f, const std::string& W, const TreeBatch&
   lh::AncWs ws;
   if (ensure_workspace(f, chunk, b.R, b.T) || node_codons_workspace(f, chunk, b.T, b.R, c.P, false, &ws)) return 1;
   const double* group_ll = nullptr;
-  // K9 reads the forward arrays before K5 smooths them in place
-  c.before_smoothing = [f, &group_ll](int m, size_t, const double* fwd, const double* ll, hipStream_t stream) -> int {
-    NodeCodonsWs& k = f->node_codons;
-    KernelTimer<1>& t = f->node_codons_k9_timer;
-    group_ll = ll;
-    if (f->profile && t.begin(stream)) return 1;
-    lh::launch_codons(f->sampler_dev, f->codon.tab, m, fwd, f->host.forward_size, ll, f->codon.scratch.get<double>(),
-                      k.windows.get<double>(), k.genes.get<double>(), stream);
-    if (f->profile && t.end(stream)) return 1;
-    return 0;
-  };
+  c.before_smoothing = naive_codons_k9(f, &lh_family::node_codons_k9_timer, &group_ll);
   // K11c checks the paths wherever a table is formed
   const bool tables = c.rows[kNodeCodons].wanted() || c.rows[kNodeChange].wanted();
   const int rc = lineage_eval_device(f, W, b, c, chunk, ws, &lh_family::node_codons_timer, tables, -1, -1, hip_stream,
@@ -2891,62 +2905,10 @@ LineageCall node_codons_call(lh_family* f, int P, const double* naive_codons, co
   return {naive_codons, path, P, 0, node_codons_rows(f, true, o)};
 }
 
-// The bodies of K13's and K14's entry points.  `at` false: the node is `node` (0 or 1); else slot[i], a slot of its own path for
-// every row (`at`; `node` is not looked at).  `device`: the arrays are the device's and the call is queued on
-// hip_stream; else they are the host's.
-
-int candidates_entry(lh_family* f, const std::string& W, const TreeBatch& b, const int32_t* path, int P, int node,
-                     bool at, const int32_t* slot, const lh_ancestral_candidates_outputs* outs, bool device, void* hip_stream) {
-  if (int rc = check_batch(f, W, b, true)) return rc > 0;
-  if (probs_check(f, W, b, P, node, at)) return 1;
-  DeviceGuard guard(f);
-  if (!b.has_arrays() || !path || (at && !slot)) return fail(W + ": null array");
-  LineageCall c = probs_call(f, P, path, outs);
-  c.slot = slot;
-  if (device) return eval_probs_device(f, W, b, c, node, hip_stream);
-  if (!c.asked()) return 0;
-  if (refuse_oversize(W, b.n, c, lh::debug_options().anc_out_mb)) return 1;  // (K11's rule)
-  return lineage_batch(f, W, b, c, b.n,
-                       [&](const TreeBatch& dev, LineageCall d) { return eval_probs_device(f, W, dev, d, node, nullptr); });
-}
-
-int eval_node_codons_entry(lh_family* f, const std::string& W, const TreeBatch& b, const int32_t* path, int P, int node,
-                           bool at, const int32_t* slot, const lh_node_codons_outputs* outs, bool device, void* hip_stream) {
-  if (int rc = check_batch(f, W, b, true)) return rc > 0;
-  if (node_codons_check(f, W, b, P, node, at)) return 1;
-  DeviceGuard guard(f);
-  if (!b.has_arrays() || !path || (at && !slot)) return fail(W + ": null array");
-  LineageCall c = node_codons_call(f, P, path, outs);
-  c.slot = slot;
-  if (device) return eval_node_codons_device(f, W, b, c, node, hip_stream);
-  if (!c.asked()) return 0;
-  if (refuse_oversize(W, b.n, c, lh::debug_options().anc_out_mb)) return 1;  // (K11's rule)
-  return lineage_batch(f, W, b, c, b.n,
-                       [&](const TreeBatch& dev, LineageCall d) { return eval_node_codons_device(f, W, dev, d, node, nullptr); });
-}
-
-int asr_node_codons_entry(lh_family* f, const std::string& W, const TreeBatch& b, const double* naive_codons,
-                          const int32_t* path, int P, int node, bool at, const int32_t* slot, double* codons, double* change,
-                          bool device, void* hip_stream) {
-  if (int rc = check_batch(f, W, b)) return rc > 0;
-  if (node_codons_check(f, W, b, P, node, at)) return 1;
-  DeviceGuard guard(f);
-  if (!b.has_arrays() || !naive_codons || !path || (at && !slot)) return fail(W + ": null array");
-  LineageCall c = node_codons_call(f, P, naive_codons, path, codons, change);
-  c.slot = slot;
-  if (!c.asked()) return 0;  // nothing asked for
-  if (device) return asr_node_codons_device(f, W, b, c, node, hip_stream);
-  // no refusal here: sub-batches bound the device copies of the inputs and outputs (as lh_asr_marginals_batch)
-  const size_t per = c.copy_bytes(true) + c.rows[kSiteBase].bytes(1);
-  const size_t sub = std::max<size_t>(1, std::min<size_t>(b.n, ((size_t)1 << 30) / std::max<size_t>(per, 1)));
-  return lineage_batch(f, W, b, c, sub, [&](const TreeBatch& dev, const LineageCall& d) {
-    return asr_node_codons_device(f, W, dev, d, node, nullptr);
-  });
-}
-
 // ---- K15: exact amino-acid replacement posteriors along the edges of a seed's lineage (lh_codon_edges.hip) ----
 
-// K15's per-row outputs.  Row 0 as K14's: the eval form's site_base, the given-rates form's naive codon posteriors.
+// K15's per-row outputs.  Row 0 as K14's: the eval form's site_base, the given-rates form's naive codon posteriors (no copy
+// of its own: asr_entry's sub-batch rule adds its bytes).
 enum { kCeCounts = 1, kCeAa, kCeSeed, kCeEdgeChange, kCeEdgeLoad, kCeCond };
 std::vector<RowOut> codon_edges_rows(lh_family* f, bool given, int P, const lh_codon_edges_outputs& o, double* cond_edge) {
   AncestralWs& a = f->anc;
@@ -2967,37 +2929,21 @@ int codon_edges_check(const lh_family* f, const std::string& W, const TreeBatch&
   return 0;
 }
 
-// samples per launch group of K15, by memory as edges_group and node_codons_group: K11's scratch with K15b's per-slot
-// partials and K15m's tables in place of K11b's (LH_CODON_EDGES_MB: the budget, a test hook)
+// samples per launch group of K15: its own bytes are K15b's per-slot partials, K15m's tables and K14's group arrays
+// (LH_CODON_EDGES_MB: the budget, a test hook)
 size_t codon_edges_group(const lh_family* f, int T, int R, int P) {
-  const lh::AncWsBytes z = lh::anc_ws_bytes(T, f->host.n_sites, R, f->host.n_prune, P);
   const lh::CondEdgeWsBytes y = lh::cond_edge_ws_bytes(R, f->host.n_prune, P);
-  const size_t per = z.total() - z.part + y.part + y.table + node_codons_bytes(f) + lh::asr_desc_bytes(T) +
-                     eval_bytes_per_sample(f, T, R);
   const size_t hook = (size_t)lh::debug_options().codon_edges_mb;
-  const size_t budget = hook ? hook << 20 : (size_t)8 << 30;
-  return std::max<size_t>(1, std::min<size_t>({(size_t)kChunk, (size_t)8192, budget / per}));
+  return lineage_group(f, T, R, P, y.part + y.table + node_codons_bytes(f), hook ? hook << 20 : (size_t)8 << 30);
 }
 
 int codon_edges_workspace(lh_family* f, int chunk, int T, int R, int P, bool given, bool ec_tmp, lh::AncWs* ws) {
-  AncestralWs& a = f->anc;
-  NodeCodonsWs& k = f->node_codons;
   CodonEdgesWs& e = f->codon_edges;
-  const CodonWs& cw = f->codon;
-  const lh::AncWsBytes z = lh::anc_ws_bytes(T, f->host.n_sites, R, f->host.n_prune, P);
   const lh::CondEdgeWsBytes y = lh::cond_edge_ws_bytes(R, f->host.n_prune, P);
   const size_t m = chunk;
-  if (a.clv.ensure(z.clv * m) || a.tvec.ensure(z.tvec * m) || a.rho.ensure(z.rho * m) || a.chain.ensure(z.chain * m) ||
-      a.plen.ensure(sizeof(int32_t) * m) || a.desc.ensure(lh::asr_desc_bytes(T) * m) || e.part.ensure(y.part * m) ||
-      e.table.ensure(y.table * m) ||
-      (ec_tmp && e.ec_tmp.ensure(sizeof(double) * ((size_t)P + 1) * cw.n_codons * 3 * m)))
-    return 1;
-  *ws = {a.clv.get<double>(), e.part.get<double>(), a.tvec.get<double>(), a.rho.get<double>(), a.chain.get<int32_t>(),
-         a.plen.get<int32_t>(), a.desc.get()};
-  if (given) return k.zero.ensure(sizeof(double) * 5 * (size_t)f->host.n_sites * m);
-  return k.windows.ensure(sizeof(double) * 125 * (size_t)cw.tab.n_window * m) ||
-         k.genes.ensure(sizeof(double) * (size_t)cw.tab.n_genes * m) || k.naive.ensure(sizeof(double) * 125 * (size_t)cw.n_codons * m) ||
-         f->codon.scratch.ensure(sizeof(double) * 4 * (size_t)cw.tab.max_vec * lh::codon_slots(chunk));
+  return lineage_workspace(f, chunk, T, R, P, true, &e.part, y.part, ws) || e.table.ensure(y.table * m) ||
+         (ec_tmp && e.ec_tmp.ensure(sizeof(double) * ((size_t)P + 1) * f->codon.n_codons * 3 * m)) ||
+         naive_codons_workspace(f, chunk, given);
 }
 
 // K15b + K15m on a launch group, the naive codon posteriors of every codon (as node_codons_launch) and the contraction
@@ -3009,13 +2955,8 @@ auto codon_edges_launch(lh_family* f, const LineageCall& c, bool given, const do
     CodonEdgesWs& e = f->codon_edges;
     KernelTimer<2>& t = f->codon_edges_stage_timer;
     const std::vector<RowOut>& r = c.rows;
-    const double* site_base = naive_prob;
-    const double* Q = k.naive.get<const double>();
-    if (given) {
-      Q = naive_prob;
-      LH_HIP(hipMemsetAsync(k.zero.get(), 0, sizeof(double) * 5 * (size_t)f->host.n_sites * g.n, stream));
-      site_base = k.zero.get<const double>();
-    }
+    const double *Q, *site_base;
+    if (naive_codons_inputs(f, given, g.n, naive_prob, stream, &Q, &site_base)) return 1;
     if (f->profile && t.begin(stream)) return 1;
     if (lh::launch_cond_edges(f->host, g.n, g.R, g.T, g.ops, g.brlen, rates, w.eig.get<double>(), g.pi, w.site_lik.get<double>(),
                               w.site_scal.get<int32_t>(), site_base, c.path + off * c.P, c.P, c.seed_tip, ws,
@@ -3043,17 +2984,7 @@ int eval_codon_edges_device(lh_family* f, const std::string& W, const TreeBatch&
   if (ensure_workspace(f, chunk, b.R, b.T) || codon_edges_workspace(f, chunk, b.T, b.R, c.P, false, codon_edges_tmp(c), &ws))
     return 1;
   const double* group_ll = nullptr;
-  // K9 reads the forward arrays before K5 smooths them in place
-  c.before_smoothing = [f, &group_ll](int m, size_t, const double* fwd, const double* ll, hipStream_t stream) -> int {
-    NodeCodonsWs& k = f->node_codons;
-    KernelTimer<1>& t = f->codon_edges_k9_timer;
-    group_ll = ll;
-    if (f->profile && t.begin(stream)) return 1;
-    lh::launch_codons(f->sampler_dev, f->codon.tab, m, fwd, f->host.forward_size, ll, f->codon.scratch.get<double>(),
-                      k.windows.get<double>(), k.genes.get<double>(), stream);
-    if (f->profile && t.end(stream)) return 1;
-    return 0;
-  };
+  c.before_smoothing = naive_codons_k9(f, &lh_family::codon_edges_k9_timer, &group_ll);
   // K11c and K12c check the paths wherever a table is formed
   const bool tables = std::any_of(c.rows.begin() + 1, c.rows.end(), [](const RowOut& r) { return r.wanted(); });
   const int rc = lineage_eval_device(f, W, b, c, chunk, ws, &lh_family::codon_edges_timer, tables, -1, -1, hip_stream,
@@ -3087,6 +3018,138 @@ LineageCall codon_edges_call(lh_family* f, int P, const double* naive_codons, co
   return {naive_codons, path, P, seed_tip, codon_edges_rows(f, true, P, o, cond_edge)};
 }
 
+// ---- the bodies of the entry points of K11 to K15 ----
+// check(): the family's argument check; `missing`: one of the entry point's own arrays (path, the given-rates forms'
+// input, an `at` form's slots) is null; call(): its LineageCall, built behind those tests; run(batch, call, stream): its
+// _device form's body.  slot: the `at` forms' (K13, K14), the node is slot[i], a slot of its own path for every row.
+// `device`: the arrays are the device's and the call is queued on hip_stream; else they are the host's, and the device
+// copies of the per-row outputs bound the batch.
+
+// The eval forms: a batch whose copies pass out_mb MiB is refused (K11's rule).
+template <class Check, class Call, class Run>
+int eval_entry(lh_family* f, const std::string& W, const TreeBatch& b, bool missing, const int32_t* slot, int out_mb,
+               bool device, void* hip_stream, Check&& check, Call&& call, Run&& run) {
+  if (int rc = check_batch(f, W, b, true)) return rc > 0;
+  if (check()) return 1;
+  DeviceGuard guard(f);
+  if (!b.has_arrays() || missing) return fail(W + ": null array");
+  LineageCall c = call();
+  c.slot = slot;
+  if (device) return run(b, c, hip_stream);
+  if (!c.asked()) return 0;
+  if (refuse_oversize(W, b.n, c, out_mb)) return 1;
+  return lineage_batch(f, W, b, c, b.n, [&](const TreeBatch& dev, LineageCall d) { return run(dev, d, nullptr); });
+}
+
+// The given-rates (asr) forms.  out_mb 0: no refusal, sub-batches bound the device copies of the inputs and outputs at
+// 1 GiB (marg: 32 P L bytes per sample).  The input is staged at row 0's width: where the family declares row 0 with a copy
+// (K11: ancestral_rows) copy_bytes has counted it, where it declares none (K14, K15) its bytes are added here.
+template <class Check, class Call, class Run>
+int asr_entry(lh_family* f, const std::string& W, const TreeBatch& b, bool missing, const int32_t* slot, int out_mb,
+              bool device, void* hip_stream, Check&& check, Call&& call, Run&& run) {
+  if (int rc = check_batch(f, W, b)) return rc > 0;
+  if (check()) return 1;
+  DeviceGuard guard(f);
+  if (!b.has_arrays() || missing) return fail(W + ": null array");
+  LineageCall c = call();
+  c.slot = slot;
+  if (!c.asked()) return 0;  // nothing asked for
+  if (device) return run(b, c, hip_stream);
+  size_t sub = b.n;
+  if (out_mb) {
+    if (refuse_oversize(W, b.n, c, out_mb)) return 1;
+  } else {
+    const RowOut& in = c.rows[kSiteBase];
+    const size_t per = c.copy_bytes(true) + (in.copy ? 0 : in.bytes(1));
+    sub = std::max<size_t>(1, std::min<size_t>(b.n, ((size_t)1 << 30) / std::max<size_t>(per, 1)));
+  }
+  return lineage_batch(f, W, b, c, sub, [&](const TreeBatch& dev, const LineageCall& d) { return run(dev, d, nullptr); });
+}
+
+int asr_marginals_entry(lh_family* f, const TreeBatch& b, const double* naive_prob, const int32_t* path, int P, double* marg,
+                        double* rate_post, bool device, void* hip_stream) {
+  const std::string W = "lh_asr_marginals_batch";
+  return asr_entry(
+      f, W, b, !naive_prob || !path, nullptr, 0, device, hip_stream, [&] { return ancestral_check(f, W, b, P); },
+      [&] { return LineageCall{naive_prob, path, P, 0, ancestral_rows(f, P, b.R, nullptr, marg, rate_post, nullptr, nullptr)}; },
+      [&](const TreeBatch& g, const LineageCall& c, void* s) { return asr_marginals_device(f, W, g, c, s); });
+}
+
+int eval_ancestral_entry(lh_family* f, const TreeBatch& b, const int32_t* path, int P, const lh_ancestral_outputs* outs,
+                         bool device, void* hip_stream) {
+  const std::string W = "lh_eval_ancestral_batch";
+  return eval_entry(
+      f, W, b, !path, nullptr, lh::debug_options().anc_out_mb, device, hip_stream, [&] { return ancestral_check(f, W, b, P); },
+      [&] { return ancestral_call(f, P, b.R, path, outs); },
+      [&](const TreeBatch& g, LineageCall& c, void* s) { return eval_ancestral_device(f, W, g, c, s); });
+}
+
+int asr_edges_entry(lh_family* f, const TreeBatch& b, const double* naive_prob, const int32_t* path, int P, int seed_tip,
+                    const lh_edges_outputs* outs, bool device, void* hip_stream) {
+  const std::string W = "lh_asr_edges_batch";
+  return asr_entry(
+      f, W, b, !naive_prob || !path, nullptr, lh::debug_options().edge_out_mb, device, hip_stream,
+      [&] { return edges_check(f, W, b, P, seed_tip); }, [&] { return edges_call(f, P, b.R, naive_prob, path, seed_tip, outs); },
+      [&](const TreeBatch& g, const LineageCall& c, void* s) { return asr_edges_device(f, W, g, c, s); });
+}
+
+int eval_edges_entry(lh_family* f, const TreeBatch& b, const int32_t* path, int P, int seed_tip, const lh_eval_edges_outputs* outs,
+                     bool device, void* hip_stream) {
+  const std::string W = "lh_eval_edges_batch";
+  return eval_entry(
+      f, W, b, !path, nullptr, lh::debug_options().edge_out_mb, device, hip_stream,
+      [&] { return edges_check(f, W, b, P, seed_tip); },
+      [&] { return edges_call(f, P, b.R, nullptr, path, seed_tip, outs ? *outs : lh_eval_edges_outputs{}); },
+      [&](const TreeBatch& g, LineageCall& c, void* s) { return eval_edges_device(f, W, g, c, s); });
+}
+
+int candidates_entry(lh_family* f, const std::string& W, const TreeBatch& b, const int32_t* path, int P, int node, bool at,
+                     const int32_t* slot, const lh_ancestral_candidates_outputs* outs, bool device, void* hip_stream) {
+  return eval_entry(
+      f, W, b, !path || (at && !slot), slot, lh::debug_options().anc_out_mb, device, hip_stream, [&] { return probs_check(f, W, b, P, node, at); },
+      [&] { return probs_call(f, P, path, outs); },
+      [&](const TreeBatch& g, LineageCall& c, void* s) { return eval_probs_device(f, W, g, c, node, s); });
+}
+
+int eval_node_codons_entry(lh_family* f, const std::string& W, const TreeBatch& b, const int32_t* path, int P, int node, bool at,
+                           const int32_t* slot, const lh_node_codons_outputs* outs, bool device, void* hip_stream) {
+  return eval_entry(
+      f, W, b, !path || (at && !slot), slot, lh::debug_options().anc_out_mb, device, hip_stream,
+      [&] { return node_codons_check(f, W, b, P, node, at); }, [&] { return node_codons_call(f, P, path, outs); },
+      [&](const TreeBatch& g, LineageCall& c, void* s) { return eval_node_codons_device(f, W, g, c, node, s); });
+}
+
+int asr_node_codons_entry(lh_family* f, const std::string& W, const TreeBatch& b, const double* naive_codons, const int32_t* path,
+                          int P, int node, bool at, const int32_t* slot, double* codons, double* change, bool device,
+                          void* hip_stream) {
+  return asr_entry(
+      f, W, b, !naive_codons || !path || (at && !slot), slot, 0, device, hip_stream, [&] { return node_codons_check(f, W, b, P, node, at); },
+      [&] { return node_codons_call(f, P, naive_codons, path, codons, change); },
+      [&](const TreeBatch& g, const LineageCall& c, void* s) { return asr_node_codons_device(f, W, g, c, node, s); });
+}
+
+int eval_codon_edges_entry(lh_family* f, const TreeBatch& b, const int32_t* path, int P, int seed_tip,
+                           const lh_codon_edges_outputs* outs, bool device, void* hip_stream) {
+  const std::string W = "lh_eval_codon_edges_batch";
+  return eval_entry(
+      f, W, b, !path, nullptr, lh::debug_options().edge_out_mb, device, hip_stream,
+      [&] { return codon_edges_check(f, W, b, P, seed_tip); }, [&] { return codon_edges_call(f, P, path, seed_tip, outs); },
+      [&](const TreeBatch& g, LineageCall& c, void* s) { return eval_codon_edges_device(f, W, g, c, s); });
+}
+
+int asr_codon_edges_entry(lh_family* f, const TreeBatch& b, const double* naive_codons, const int32_t* path, int P, int seed_tip,
+                          double* codon_counts, double* aa_counts, double* seed_change, double* edge_change, double* edge_load,
+                          double* cond_edge, bool device, void* hip_stream) {
+  const std::string W = "lh_asr_codon_edges_batch";
+  return asr_entry(
+      f, W, b, !naive_codons || !path, nullptr, 0, device, hip_stream, [&] { return codon_edges_check(f, W, b, P, seed_tip); },
+      [&] {
+        return codon_edges_call(f, P, naive_codons, path, seed_tip, codon_counts, aa_counts, seed_change, edge_change, edge_load,
+                                cond_edge);
+      },
+      [&](const TreeBatch& g, const LineageCall& c, void* s) { return asr_codon_edges_device(f, W, g, c, s); });
+}
+
 }  // namespace
 
 extern "C" {
@@ -3095,60 +3158,27 @@ int lh_asr_marginals_batch_device(lh_family* f, int32_t n, int32_t T, int32_t ma
                                   const double* brlen, const double* er, const double* pi, const double* rates, int32_t R,
                                   const double* naive_prob, const int32_t* path, int32_t P, double* marg, double* rate_post,
                                   void* hip_stream) {
-  const TreeBatch b{n, T, max_depth, ops, brlen, er, pi, rates, R, true};
-  const std::string W = "lh_asr_marginals_batch";
-  if (int rc = check_batch(f, W, b)) return rc > 0;
-  if (ancestral_check(f, W, b, P)) return 1;
-  DeviceGuard guard(f);
-  if (!b.has_arrays() || !naive_prob || !path) return fail(W + ": null array");
-  const LineageCall c{naive_prob, path, P, 0, ancestral_rows(f, P, R, nullptr, marg, rate_post, nullptr, nullptr)};
-  if (!c.asked()) return 0;  // nothing asked for
-  return asr_marginals_device(f, W, b, c, hip_stream);
+  return asr_marginals_entry(f, {n, T, max_depth, ops, brlen, er, pi, rates, R, true}, naive_prob, path, P, marg, rate_post, true,
+                             hip_stream);
 }
 
 int lh_asr_marginals_batch(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops, const double* brlen,
                            const double* er, const double* pi, const double* rates, int32_t R, const double* naive_prob,
                            const int32_t* path, int32_t P, double* marg, double* rate_post) {
-  const TreeBatch host{n, T, max_depth, ops, brlen, er, pi, rates, R, true};
-  const std::string W = "lh_asr_marginals_batch";
-  if (int rc = check_batch(f, W, host)) return rc > 0;
-  if (ancestral_check(f, W, host, P)) return 1;
-  DeviceGuard guard(f);
-  if (!host.has_arrays() || !naive_prob || !path) return fail(W + ": null array");
-  const LineageCall c{naive_prob, path, P, 0, ancestral_rows(f, P, R, nullptr, marg, rate_post, nullptr, nullptr)};
-  if (!c.asked()) return 0;
-  // no refusal here: sub-batches bound the device copies of the inputs and outputs (marg: 32 P L bytes per sample)
-  const size_t sub = std::max<size_t>(1, std::min<size_t>(n, ((size_t)1 << 30) / c.copy_bytes(true)));
-  return lineage_batch(f, W, host, c, sub,
-                       [&](const TreeBatch& dev, const LineageCall& d) { return asr_marginals_device(f, W, dev, d, nullptr); });
+  return asr_marginals_entry(f, {n, T, max_depth, ops, brlen, er, pi, rates, R, true}, naive_prob, path, P, marg, rate_post, false,
+                             nullptr);
 }
 
 int lh_eval_ancestral_batch_device(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops,
                                    const double* brlen, const double* er, const double* pi, const double* alpha, int32_t R,
                                    const int32_t* path, int32_t P, const lh_ancestral_outputs* outs, void* hip_stream) {
-  const TreeBatch b{n, T, max_depth, ops, brlen, er, pi, alpha, R};
-  const std::string W = "lh_eval_ancestral_batch";
-  if (int rc = check_batch(f, W, b, true)) return rc > 0;
-  if (ancestral_check(f, W, b, P)) return 1;
-  DeviceGuard guard(f);
-  if (!b.has_arrays() || !path) return fail(W + ": null array");
-  LineageCall c = ancestral_call(f, P, R, path, outs);
-  return eval_ancestral_device(f, W, b, c, hip_stream);
+  return eval_ancestral_entry(f, {n, T, max_depth, ops, brlen, er, pi, alpha, R}, path, P, outs, true, hip_stream);
 }
 
 int lh_eval_ancestral_batch(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops, const double* brlen,
                             const double* er, const double* pi, const double* alpha, int32_t R, const int32_t* path, int32_t P,
                             const lh_ancestral_outputs* outs) {
-  const TreeBatch host{n, T, max_depth, ops, brlen, er, pi, alpha, R};
-  const std::string W = "lh_eval_ancestral_batch";
-  if (int rc = check_batch(f, W, host, true)) return rc > 0;
-  if (ancestral_check(f, W, host, P)) return 1;
-  DeviceGuard guard(f);
-  if (!host.has_arrays() || !path) return fail(W + ": null array");
-  const LineageCall c = ancestral_call(f, P, R, path, outs);
-  if (!c.asked()) return 0;
-  if (refuse_oversize(W, n, c, lh::debug_options().anc_out_mb)) return 1;
-  return lineage_batch(f, W, host, c, n, [&](const TreeBatch& dev, LineageCall d) { return eval_ancestral_device(f, W, dev, d, nullptr); });
+  return eval_ancestral_entry(f, {n, T, max_depth, ops, brlen, er, pi, alpha, R}, path, P, outs, false, nullptr);
 }
 
 int lh_ancestral_profile_read(lh_family* f, double* ms, int64_t* n_launches) {
@@ -3158,58 +3188,27 @@ int lh_ancestral_profile_read(lh_family* f, double* ms, int64_t* n_launches) {
 int lh_asr_edges_batch_device(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops, const double* brlen,
                               const double* er, const double* pi, const double* rates, int32_t R, const double* naive_prob,
                               const int32_t* path, int32_t P, int32_t seed_tip, const lh_edges_outputs* outs, void* hip_stream) {
-  const TreeBatch b{n, T, max_depth, ops, brlen, er, pi, rates, R, true};
-  const std::string W = "lh_asr_edges_batch";
-  if (int rc = check_batch(f, W, b)) return rc > 0;
-  if (edges_check(f, W, b, P, seed_tip)) return 1;
-  DeviceGuard guard(f);
-  if (!b.has_arrays() || !naive_prob || !path) return fail(W + ": null array");
-  const LineageCall c = edges_call(f, P, R, naive_prob, path, seed_tip, outs);
-  if (!c.asked()) return 0;  // nothing asked for
-  return asr_edges_device(f, W, b, c, hip_stream);
+  return asr_edges_entry(f, {n, T, max_depth, ops, brlen, er, pi, rates, R, true}, naive_prob, path, P, seed_tip, outs, true,
+                         hip_stream);
 }
 
 int lh_asr_edges_batch(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops, const double* brlen,
                        const double* er, const double* pi, const double* rates, int32_t R, const double* naive_prob,
                        const int32_t* path, int32_t P, int32_t seed_tip, const lh_edges_outputs* outs) {
-  const TreeBatch host{n, T, max_depth, ops, brlen, er, pi, rates, R, true};
-  const std::string W = "lh_asr_edges_batch";
-  if (int rc = check_batch(f, W, host)) return rc > 0;
-  if (edges_check(f, W, host, P, seed_tip)) return 1;
-  DeviceGuard guard(f);
-  if (!host.has_arrays() || !naive_prob || !path) return fail(W + ": null array");
-  const LineageCall c = edges_call(f, P, R, naive_prob, path, seed_tip, outs);
-  if (!c.asked()) return 0;
-  if (refuse_oversize(W, n, c, lh::debug_options().edge_out_mb)) return 1;  // (K11's rule)
-  return lineage_batch(f, W, host, c, n, [&](const TreeBatch& dev, const LineageCall& d) { return asr_edges_device(f, W, dev, d, nullptr); });
+  return asr_edges_entry(f, {n, T, max_depth, ops, brlen, er, pi, rates, R, true}, naive_prob, path, P, seed_tip, outs, false,
+                         nullptr);
 }
 
 int lh_eval_edges_batch_device(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops, const double* brlen,
                                const double* er, const double* pi, const double* alpha, int32_t R, const int32_t* path, int32_t P,
                                int32_t seed_tip, const lh_eval_edges_outputs* outs, void* hip_stream) {
-  const TreeBatch b{n, T, max_depth, ops, brlen, er, pi, alpha, R};
-  const std::string W = "lh_eval_edges_batch";
-  if (int rc = check_batch(f, W, b, true)) return rc > 0;
-  if (edges_check(f, W, b, P, seed_tip)) return 1;
-  DeviceGuard guard(f);
-  if (!b.has_arrays() || !path) return fail(W + ": null array");
-  LineageCall c = edges_call(f, P, R, nullptr, path, seed_tip, outs ? *outs : lh_eval_edges_outputs{});
-  return eval_edges_device(f, W, b, c, hip_stream);
+  return eval_edges_entry(f, {n, T, max_depth, ops, brlen, er, pi, alpha, R}, path, P, seed_tip, outs, true, hip_stream);
 }
 
 int lh_eval_edges_batch(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops, const double* brlen,
                         const double* er, const double* pi, const double* alpha, int32_t R, const int32_t* path, int32_t P,
                         int32_t seed_tip, const lh_eval_edges_outputs* outs) {
-  const TreeBatch host{n, T, max_depth, ops, brlen, er, pi, alpha, R};
-  const std::string W = "lh_eval_edges_batch";
-  if (int rc = check_batch(f, W, host, true)) return rc > 0;
-  if (edges_check(f, W, host, P, seed_tip)) return 1;
-  DeviceGuard guard(f);
-  if (!host.has_arrays() || !path) return fail(W + ": null array");
-  const LineageCall c = edges_call(f, P, R, nullptr, path, seed_tip, outs ? *outs : lh_eval_edges_outputs{});
-  if (!c.asked()) return 0;
-  if (refuse_oversize(W, n, c, lh::debug_options().edge_out_mb)) return 1;  // (K11's rule)
-  return lineage_batch(f, W, host, c, n, [&](const TreeBatch& dev, LineageCall d) { return eval_edges_device(f, W, dev, d, nullptr); });
+  return eval_edges_entry(f, {n, T, max_depth, ops, brlen, er, pi, alpha, R}, path, P, seed_tip, outs, false, nullptr);
 }
 
 int lh_edges_profile_read(lh_family* f, double* ms, int64_t* n_launches) {
@@ -3373,30 +3372,13 @@ int lh_eval_codon_edges_batch_device(lh_family* f, int32_t n, int32_t T, int32_t
                                      const double* brlen, const double* er, const double* pi, const double* alpha, int32_t R,
                                      const int32_t* path, int32_t P, int32_t seed_tip, const lh_codon_edges_outputs* outs,
                                      void* hip_stream) {
-  const TreeBatch b{n, T, max_depth, ops, brlen, er, pi, alpha, R};
-  const std::string W = "lh_eval_codon_edges_batch";
-  if (int rc = check_batch(f, W, b, true)) return rc > 0;
-  if (codon_edges_check(f, W, b, P, seed_tip)) return 1;
-  DeviceGuard guard(f);
-  if (!b.has_arrays() || !path) return fail(W + ": null array");
-  LineageCall c = codon_edges_call(f, P, path, seed_tip, outs);
-  return eval_codon_edges_device(f, W, b, c, hip_stream);
+  return eval_codon_edges_entry(f, {n, T, max_depth, ops, brlen, er, pi, alpha, R}, path, P, seed_tip, outs, true, hip_stream);
 }
 
 int lh_eval_codon_edges_batch(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops, const double* brlen,
                               const double* er, const double* pi, const double* alpha, int32_t R, const int32_t* path, int32_t P,
                               int32_t seed_tip, const lh_codon_edges_outputs* outs) {
-  const TreeBatch host{n, T, max_depth, ops, brlen, er, pi, alpha, R};
-  const std::string W = "lh_eval_codon_edges_batch";
-  if (int rc = check_batch(f, W, host, true)) return rc > 0;
-  if (codon_edges_check(f, W, host, P, seed_tip)) return 1;
-  DeviceGuard guard(f);
-  if (!host.has_arrays() || !path) return fail(W + ": null array");
-  const LineageCall c = codon_edges_call(f, P, path, seed_tip, outs);
-  if (!c.asked()) return 0;
-  if (refuse_oversize(W, n, c, lh::debug_options().edge_out_mb)) return 1;  // (K11's rule)
-  return lineage_batch(f, W, host, c, n,
-                       [&](const TreeBatch& dev, LineageCall d) { return eval_codon_edges_device(f, W, dev, d, nullptr); });
+  return eval_codon_edges_entry(f, {n, T, max_depth, ops, brlen, er, pi, alpha, R}, path, P, seed_tip, outs, false, nullptr);
 }
 
 int lh_asr_codon_edges_batch_device(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops,
@@ -3404,37 +3386,16 @@ int lh_asr_codon_edges_batch_device(lh_family* f, int32_t n, int32_t T, int32_t 
                                     const double* naive_codons, const int32_t* path, int32_t P, int32_t seed_tip,
                                     double* codon_counts, double* aa_counts, double* seed_change, double* edge_change,
                                     double* edge_load, double* cond_edge, void* hip_stream) {
-  const TreeBatch b{n, T, max_depth, ops, brlen, er, pi, rates, R, true};
-  const std::string W = "lh_asr_codon_edges_batch";
-  if (int rc = check_batch(f, W, b)) return rc > 0;
-  if (codon_edges_check(f, W, b, P, seed_tip)) return 1;
-  DeviceGuard guard(f);
-  if (!b.has_arrays() || !naive_codons || !path) return fail(W + ": null array");
-  const LineageCall c =
-      codon_edges_call(f, P, naive_codons, path, seed_tip, codon_counts, aa_counts, seed_change, edge_change, edge_load, cond_edge);
-  if (!c.asked()) return 0;  // nothing asked for
-  return asr_codon_edges_device(f, W, b, c, hip_stream);
+  return asr_codon_edges_entry(f, {n, T, max_depth, ops, brlen, er, pi, rates, R, true}, naive_codons, path, P, seed_tip,
+                               codon_counts, aa_counts, seed_change, edge_change, edge_load, cond_edge, true, hip_stream);
 }
 
 int lh_asr_codon_edges_batch(lh_family* f, int32_t n, int32_t T, int32_t max_depth, const int32_t* ops, const double* brlen,
                              const double* er, const double* pi, const double* rates, int32_t R, const double* naive_codons,
                              const int32_t* path, int32_t P, int32_t seed_tip, double* codon_counts, double* aa_counts,
                              double* seed_change, double* edge_change, double* edge_load, double* cond_edge) {
-  const TreeBatch host{n, T, max_depth, ops, brlen, er, pi, rates, R, true};
-  const std::string W = "lh_asr_codon_edges_batch";
-  if (int rc = check_batch(f, W, host)) return rc > 0;
-  if (codon_edges_check(f, W, host, P, seed_tip)) return 1;
-  DeviceGuard guard(f);
-  if (!host.has_arrays() || !naive_codons || !path) return fail(W + ": null array");
-  const LineageCall c =
-      codon_edges_call(f, P, naive_codons, path, seed_tip, codon_counts, aa_counts, seed_change, edge_change, edge_load, cond_edge);
-  if (!c.asked()) return 0;
-  // no refusal here: sub-batches bound the device copies of the inputs and outputs (as lh_asr_node_codons_batch)
-  const size_t per = c.copy_bytes(true) + c.rows[kSiteBase].bytes(1);
-  const size_t sub = std::max<size_t>(1, std::min<size_t>(n, ((size_t)1 << 30) / std::max<size_t>(per, 1)));
-  return lineage_batch(f, W, host, c, sub, [&](const TreeBatch& dev, const LineageCall& d) {
-    return asr_codon_edges_device(f, W, dev, d, nullptr);
-  });
+  return asr_codon_edges_entry(f, {n, T, max_depth, ops, brlen, er, pi, rates, R, true}, naive_codons, path, P, seed_tip,
+                               codon_counts, aa_counts, seed_change, edge_change, edge_load, cond_edge, false, nullptr);
 }
 
 int lh_codon_edge_symbols(uint8_t* sym) {

@@ -19,10 +19,13 @@
 // Kernels:
 //  * K11r, K3s, K11c (launch_ancestral_front) and K12c (launch_sub_seed) run in front, unchanged.
 //  * K15b (cond_edge_kernel), a workgroup per (rate category, sample) as K13b's cond_kernel<false>: its prologue, its
-//    upward pass with a lane per pattern, its 4 x 5 block down the chain.  Per step tree_sibling_message once, then per
-//    basis the 16 cells M(a) P_below(a, c) L_below(c) from tree_join's M, normalised by their sum and weighted by w_r:
+//    upward pass with a lane per pattern, its category weights and its 4 x 5 block (tree_rate_weights, tree_root_messages)
+//    down the chain.  Per step tree_sibling_message once (at slot 0 K12b's tree_seed_edge), then per basis the 16 cells
+//    M(a) P_below(a, c) L_below(c) from tree_join's M, normalised by their sum and weighted by w_r:
 //    part[sample][rate][slot][pattern][5][16].  Contraction is off in the down pass, fma is written where it is meant.
+//    All of the tree pass is lh_treepass.h's; the kernel's own are the cells (cond_edge_below, cond_edge_cells).
 //  * K15m (K11m's rate_sum_kernel): the R partials in rate order; NaN for a row without a path, 0 in padding slots.
+//    K13's site_gather_kernel (lh_ancestral.hip) spreads the table over the sites for a caller who takes cond_edge.
 //  * K15 (codon_edge_kernel), a wave per (row, codon), lane = the upper triple x of an inner edge (the MRCA's triple on
 //    the naive edge).  Q is read at wave-uniform addresses, a zero entry skipped by a uniform branch.  Per non-zero b the
 //    lane forms the 64 products of its three 4-vectors H[j_k][b_k][x_k][.] (an edge's 3 x 80 doubles are staged in LDS by a
@@ -93,8 +96,9 @@ __device__ __forceinline__ void cond_edge_cells(const double (&M)[4], const doub
   }
 }
 
-// K15b
-__global__ void __launch_bounds__(256) cond_edge_kernel(int R, int T, int n_prune, int P, const uint8_t* __restrict__ msa,
+// K15b.  Three waves per SIMD (at most 168 vector registers) is what the five bases' cells are ordered for; the bound is
+// declared because the kernel lies within a few registers of it.
+__global__ void __launch_bounds__(256, 3) cond_edge_kernel(int R, int T, int n_prune, int P, const uint8_t* __restrict__ msa,
                                                         const AsrOp* __restrict__ desc, const double* __restrict__ brlen,
                                                         const double* __restrict__ rates, const double* __restrict__ eig,
                                                         const double* __restrict__ pi, const double* __restrict__ site_lik,
@@ -108,7 +112,6 @@ __global__ void __launch_bounds__(256) cond_edge_kernel(int R, int T, int n_prun
   const int NP = n_prune + 1;
   const int sample = blockIdx.y, rate = blockIdx.x;
   const double *tiptab = tt.tiptab, *pin = tt.pin;
-  const AsrOp* __restrict__ dsc = tt.dsc;
   const size_t plane = tt.plane;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -123,65 +126,24 @@ __global__ void __launch_bounds__(256) cond_edge_kernel(int R, int T, int n_prun
     const bool all_n = pat >= n_prune;
     {
       double root[4];  // every inner CLV is stored: the down pass reads the lane's own back
-      tree_upward_pattern<true>(T - 2, n_prune, pat, msa, dsc, tiptab, pin, tt.clv_s, plane, root);
+      tree_upward_pattern<true>(T - 2, n_prune, pat, msa, tt.dsc, tiptab, pin, tt.clv_s, plane, root);
     }
 
     // the weight of this category under each naive base
     double w[5];
-    if (all_n) {
-#pragma unroll
-      for (int b = 0; b < 5; ++b) w[b] = 1.0 / (double)R;
-    } else {
-      const RatePlanes planes = rate_planes(site_scal, site_lik, sample, R, n_prune, pat);
-      double z[5], v[5];
-      planes.totals(R, z);
-      planes.values(rate, v);
-#pragma unroll
-      for (int b = 0; b < 5; ++b) w[b] = (z[b] == 0.0 || v[b] == 0.0) ? 0.0 : v[b] / z[b];
-    }
+    tree_rate_weights(site_scal, site_lik, sample, rate, R, n_prune, pat, all_n, w);
 
     // the message into the root from above, per basis vector of the naive tip
     double A[5][4];
-    {
-      double n4[4];
-      tree_tip_col(tiptab, 0, 4, n4);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-#pragma unroll
-        for (int b = 0; b < 4; ++b) A[b][i] = p4[i] * tiptab[b * 4 + i];
-        A[4][i] = p4[i] * n4[i];
-      }
-    }
-    const double2* cbase = tt.clv_s + pat;
+    tree_root_messages(tiptab, p4, A);
     for (int s = len - 1; s >= 0; --s) {
 #pragma clang fp contract(off)
       const int word = ch[s];
       double* o = part_s + ((size_t)s * NP + pat) * 80;
       double m[4];
       if (s == 0) {
-        const int k = chain_op(word);
-        const int4 da = dsc[k].a, db = dsc[k].b;
-        const bool flag = chain_flag(word);  // the seed is the cherry's z child
-        // the seed edge: the sibling is the cherry's other tip, or the accumulator child of a tip-accumulate op
-        int useed, srow;
-        if ((da.x & 15) == OP_CHERRY) {
-          const int sib = flag ? db.x : db.y, sib_row = flag ? da.y : da.z;
-          useed = flag ? db.y : db.x;
-          srow = flag ? da.z : da.y;
-          const int ss = all_n ? 4 : (int)msa[(size_t)sib_row * n_prune + pat];
-          tree_tip_col(tiptab, sib, ss, m);
-        } else {
-          useed = db.x;
-          srow = da.y;
-          const double2* cw = cbase + (size_t)(k - 1) * 2 * plane;
-          const double2 wlo = cw[0], whi = cw[plane];
-          const double y[4] = {wlo.x, wlo.y, whi.x, whi.y};
-          tree_matvec(pin + (size_t)(k - 1) * 16, y, m);
-        }
-        const int st = all_n ? 4 : (int)msa[(size_t)srow * n_prune + pat];
         double Lb[4];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) Lb[c] = (st >= 4 || st == c) ? 1.0 : 0.0;
+        const int useed = tree_seed_edge(tt, word, msa, n_prune, pat, all_n, m, Lb);
         // the tip table holds columns: P_u[a][c] at [c * 4 + a]
         const double* pu = tiptab + (size_t)useed * 16;
         double tb[4];
@@ -194,9 +156,8 @@ __global__ void __launch_bounds__(256) cond_edge_kernel(int R, int T, int n_prun
         }
       } else {
         const int kc = tree_sibling_message(tt, word, msa, n_prune, pat, all_n, m);
-        const double2* cv = cbase + (size_t)kc * 2 * plane;
-        const double2 lo = cv[0], hi = cv[plane];
-        const double Lb[4] = {lo.x, lo.y, hi.x, hi.y};
+        double Lb[4];
+        tree_load_clv(tt.clv_s, plane, kc, pat, Lb);
         const double* pc = pin + (size_t)kc * 16;
         double tb[4];
         cond_edge_below<4, 1>(pc, Lb, tb);
@@ -210,28 +171,6 @@ __global__ void __launch_bounds__(256) cond_edge_kernel(int R, int T, int n_prun
       }
     }
   }
-}
-
-// cond_edge[n][P][L][80] from table[n][P][n_prune + 1][80]
-__global__ void __launch_bounds__(256) cond_edge_sites_kernel(long long total, int L, int n_prune,
-                                                              const int32_t* __restrict__ site_pat,
-                                                              const double* __restrict__ table, double* __restrict__ out) {
-  // a thread per double2 of the output
-  const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (gid >= total) return;
-  const long long cell = gid / 40;  // (sample, slot, site)
-  const int q = (int)(gid - cell * 40);
-  const long long slot = cell / L;  // sample * P + slot
-  const int site = (int)(cell - slot * L);
-  const int pat = min(site_pat[site], n_prune);
-  reinterpret_cast<double2*>(out)[gid] =
-      reinterpret_cast<const double2*>(table)[(slot * (n_prune + 1) + pat) * 40 + q];
-}
-
-__device__ __forceinline__ double edge_wave_sum(double v) {
-#pragma unroll
-  for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m, 64);
-  return v;
 }
 
 __device__ __forceinline__ double pick4(const double (&h)[4], int i) {
@@ -403,8 +342,8 @@ __global__ void __launch_bounds__(64) codon_edge_kernel(int C, int frame, int n_
 #pragma unroll
     for (int k = 0; k < kSymbols; ++k) total += acc[k];
     const double diag = pick_symbol(acc, my_sym, all21);
-    ident = edge_wave_sum(ident);
-    const double syn = edge_wave_sum(diag) - ident, repl = edge_wave_sum(total - diag);
+    ident = wave_sum(ident);
+    const double syn = wave_sum(diag) - ident, repl = wave_sum(total - diag);
     n_same += ident;
     n_syn += syn;
     n_repl += repl;
@@ -469,8 +408,8 @@ __global__ void __launch_bounds__(64) codon_edge_kernel(int C, int frame, int n_
       acc[k] += e[k];
     }
     const double diag = pick_symbol(e, my_sym, all21);
-    same = edge_wave_sum(same);
-    const double syn = edge_wave_sum(diag) - same, repl = edge_wave_sum(total - diag);
+    same = wave_sum(same);
+    const double syn = wave_sum(diag) - same, repl = wave_sum(total - diag);
     n_same += same;
     n_syn += syn;
     n_repl += repl;
@@ -541,11 +480,7 @@ int launch_cond_edges(const DevFamily& fam, int n, int R, int T, const int32_t* 
              static_cast<const AsrOp*>(ws.desc), brlen, rates, eig, pi, site_lik, site_scal, ws.chain, ws.plen,
              reinterpret_cast<double2*>(ws.clv), (int)anc_lp(fam.n_prune), ws.part);
   launch_rate_sum(n, R, P, (size_t)NP * 80, false, ws.plen, ws.part, table, stream);
-  if (cond_edge) {
-    const long long total = (long long)n * P * L * 40;
-    hipLaunchKernelGGL(cond_edge_sites_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, total, L,
-                       fam.n_prune, fam.site_pat, table, cond_edge);
-  }
+  if (cond_edge) launch_site_gather(fam, (long long)n * P, 80, table, cond_edge, stream);
   return 0;
 }
 

@@ -23,6 +23,27 @@ static inline void launch_lds(void (*kernel)(P...), dim3 grid, dim3 block, size_
   hipLaunchKernelGGL(kernel, grid, block, lds, stream, args...);
 }
 
+// Wave helpers of the kernels.  wave_sum: the butterfly sum of a wave of 64 in ascending xor distance (a fixed order: the
+// kernels that use it promise the same bits whatever the batch); every lane ends with the same value.
+__device__ static __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m, 64);
+  return v;
+}
+
+// lane j's v, j wave-uniform
+__device__ static __forceinline__ double read_lane(double v, int j) {
+  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), j), __builtin_amdgcn_readlane(__double2loint(v), j));
+}
+
+// v of the lane the DPP control kCtrl pairs this one with, inside its row of 16 lanes
+template <int kCtrl>
+__device__ static __forceinline__ double dpp_move(double v) {
+  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), kCtrl, 0xf, 0xf, true);
+  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), kCtrl, 0xf, 0xf, true);
+  return __hiloint2double(hi, lo);
+}
+
 // schedule op kinds (ops[4k] & 15); bit 4 = push the accumulator to stack slot ops[4k+3] first
 // bits 8..: for a tip-into-accumulator / pop op, the number of inner-branch P-matrices the earlier ops need (its own
 // one or two follow): K1's prologue packs its matrix work by it
@@ -486,6 +507,10 @@ size_t anc_lp(int n_prune);  // patterns per CLV plane: n_prune + 1 rounded up t
 // last_live; every other slot gets 0, a sample whose plen is 0 NaN.
 void launch_rate_sum(int n, int R, int slots, size_t width, bool last_live, const int32_t* plen, const double* part,
                      double* out, hipStream_t stream);
+// A table per pattern spread over the sites (site_gather_kernel, lh_ancestral.hip; K13's cond, K15's cond_edge):
+// table[rows][n_prune + 1][width] -> out[rows][n_sites][width], width 20 (K13) or 80 (K15).
+void launch_site_gather(const DevFamily& fam, long long rows, int width, const double* table, double* out,
+                        hipStream_t stream);
 
 // K12 (lh_substitutions.hip): exact joint posteriors of the two ends of every edge of a seed's lineage.  Inputs as
 // launch_ancestral's plus seed_tip (1 .. T-1, the same for every sample): the tip must be a child of path[0] under the

@@ -668,24 +668,12 @@ __global__ void __launch_bounds__(kFwdThreads) __attribute__((amdgpu_num_sgpr(80
 // Wave-wide reductions without LDS traffic: four DPP steps fold each row of 16 lanes (quad swaps, then
 // the two mirror patterns), four v_readlane pick the row totals.  A __shfl_xor butterfly costs six
 // dependent ds_bpermute round trips per value, which was the longest single item of a junction row.
-template <int kCtrl>
-__device__ static inline double dpp_move(double v) {
-  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), kCtrl, 0xf, 0xf, true);
-  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), kCtrl, 0xf, 0xf, true);
-  return __hiloint2double(hi, lo);
-}
-
-__device__ static inline double read_lane(double v, int lane) {
-  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), lane),
-                          __builtin_amdgcn_readlane(__double2loint(v), lane));
-}
-
 constexpr int kDppQuadSwap1 = 0xB1;    // quad_perm [1,0,3,2]
 constexpr int kDppQuadSwap2 = 0x4E;    // quad_perm [2,3,0,1]
 constexpr int kDppHalfMirror = 0x141;  // lane i <-> 7 - i within each 8
 constexpr int kDppMirror = 0x140;      // lane i <-> 15 - i within each 16
 
-__device__ static inline double wave_sum(double v) {
+__device__ static inline double dpp_wave_sum(double v) {
   v += dpp_move<kDppQuadSwap1>(v);
   v += dpp_move<kDppQuadSwap2>(v);
   v += dpp_move<kDppHalfMirror>(v);
@@ -928,7 +916,7 @@ __device__ static int junction_wave(const DevJunction& J, const double* jem, con
     double part = 0.0;
 #pragma unroll
     for (int q = 0; q < GL; ++q) part += f_in[q] * J.enter_lo[lane + 64u * q];
-    A = wave_sum(part);
+    A = dpp_wave_sum(part);
   }
 
   // Row i: compute every live state from row i-1, one reduction for (rank-one sum, smallest binade),
@@ -946,7 +934,7 @@ __device__ static int junction_wave(const DevJunction& J, const double* jem, con
 #pragma unroll
     for (int q = 0; q < GR; ++q)
       key = right_gene_step<kExt>(key, fN[q], fR[q], A, nli[q], ntt_lds, lane + 64u * q, t.right[q], jem);
-    A = wave_sum(part);
+    A = dpp_wave_sum(part);
     const RowScale sc = wave_row_scale<kExt>(key);
     if constexpr (kExt) count += jrs[i];
     if (sc.k != 0) {  // wave-uniform, a few rows per junction
@@ -1134,8 +1122,8 @@ __device__ static void junction_vd_pair(const DevJunction& J, const double* jemA
       pa += fA_in[q] * lo;
       pb += fB_in[q] * lo;
     }
-    AA = wave_sum(pa);
-    AB = wave_sum(pb);
+    AA = dpp_wave_sum(pa);
+    AB = dpp_wave_sum(pb);
   }
   auto combine = [](unsigned a, unsigned b) { return kExt ? max(a, b) : min(a, b); };
   for (int i = 0; i < W; ++i) {
@@ -1169,8 +1157,8 @@ __device__ static void junction_vd_pair(const DevJunction& J, const double* jemA
       else
         keyA = combine(keyA, keyR);
     }
-    AA = wave_sum(partA);
-    AB = wave_sum(partB);
+    AA = dpp_wave_sum(partA);
+    AB = dpp_wave_sum(partB);
     const RowScale sa = wave_row_scale<kExt>(keyA), sb = wave_row_scale<kExt>(keyB);
     if constexpr (kExt) {
       countA += jrsA[i];
@@ -1739,7 +1727,7 @@ __global__ void __launch_bounds__(64 * kJunctionWaves)
   double part = 0.0;
 #pragma unroll
   for (int q = 0; q < GB; ++q) part += gJ[q];  // zero beyond the last J gene
-  part = wave_sum(part);
+  part = dpp_wave_sum(part);
   if (lane == 0) loglik[s] = log(part) - jcount * kLogScaleFactor;
 }
 

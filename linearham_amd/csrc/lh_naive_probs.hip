@@ -54,8 +54,7 @@ __global__ void __launch_bounds__(kThreads)
     const double a = agree[j];
     if (a != 0.0) acc += a * l[j];
   }
-#pragma unroll
-  for (int m = 1; m < 64; m <<= 1) acc += __shfl_xor(acc, m, 64);
+  acc = wave_sum(acc);
   if (lane == 0) base[i] = isfinite(loglik[i]) ? acc - loglik[i] : __builtin_nan("");
 }
 

@@ -47,11 +47,6 @@ constexpr SameAa make_same_aa() {
 constexpr SameAa kSameAaHost = make_same_aa();
 __device__ const SameAa kSameAa = make_same_aa();
 
-__device__ inline double read_lane(double v, int j) {  // lane j's v, j uniform
-  const int lo = __builtin_amdgcn_readlane(__double2loint(v), j), hi = __builtin_amdgcn_readlane(__double2hiint(v), j);
-  return __hiloint2double(hi, lo);
-}
-
 __global__ void __launch_bounds__(256) naive_codon_kernel(NodeCodonTables t, int n, const double* __restrict__ windows,
                                                           const double* __restrict__ genes, double* __restrict__ Q) {
   const int lane = threadIdx.x & 63;
@@ -84,12 +79,6 @@ __global__ void __launch_bounds__(256) naive_codon_kernel(NodeCodonTables t, int
   }
   q[lane] = lo;
   if (lane + 64 < 125) q[lane + 64] = hi;
-}
-
-__device__ inline double wave_sum(double v) {
-#pragma unroll
-  for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m, 64);
-  return v;
 }
 
 __global__ void __launch_bounds__(256) node_codon_kernel(int n, int C, int frame, int n_prune,

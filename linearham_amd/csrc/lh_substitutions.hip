@@ -35,8 +35,8 @@
 //    child it is; a failure leaves length 0 and raises bit 1 of the error word, as a bad path does.  seed_tip itself is
 //    checked on the host (1 .. T-1) and only compared, never used as an index, before this verdict.
 //  * K12b (sub_kernel<kWriteEdges>), a workgroup per (rate category, sample): K11b's prologue, upward pass and step down
-//    the lineage (shared code, lh_treepass.h; the seed edge at slot 0 and the message into the root are written here), a
-//    lane per site in the down pass.  Per step: the 16 cells, their sum, the weight rho_r / sum.
+//    the lineage, the seed edge at slot 0 included (shared code, lh_treepass.h; the message into the root is written
+//    here), a lane per site in the down pass.  Per step: the 16 cells, their sum, the weight rho_r / sum.
 //    The site's chain_counts partial lives in 16 registers; the step's off-diagonal mass is reduced across the wave with
 //    shuffles and added to the wave's row of an LDS table by one lane.  Only the kWriteEdges form writes [slot][site][16]
 //    per rate; the lean form writes [site][16] (chain_counts), [site][20] (naive edge), [P+1] (edge_load) and, where the
@@ -76,13 +76,6 @@ __global__ void __launch_bounds__(256) sub_seed_kernel(int n, int T, int P, int 
   } else {
     ch[0] = k | (which << 30);
   }
-}
-
-// the butterfly sum of a wave; every lane ends with the same value
-__device__ __forceinline__ double sub_wave_sum(double v) {
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) v += __shfl_xor(v, d, 64);
-  return v;
 }
 
 // One edge's table: J[a*4+c] = M[a] * p[a*SA + c*SC] * Lb[c], weighted by rj / sum.  Adds the weighted cells to cc, returns
@@ -139,14 +132,13 @@ __global__ void __launch_bounds__(kSubWaves * 64) sub_kernel(int R, int T, int L
   const int n_ops = T - 2;
   const int sample = blockIdx.y, rate = blockIdx.x;
   const double *tiptab = tt.tiptab, *pin = tt.pin;
-  const AsrOp* __restrict__ dsc = tt.dsc;
   const size_t plane = tt.plane;
   double* load = tt.pin + (size_t)n_ops * 16;  // [kSubWaves][P + 1] edge_load partials of the waves
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   for (int i = tid; i < kSubWaves * (P + 1); i += blockDim.x) load[i] = 0.0;
 
-  tree_upward(n_ops, n_prune, msa, dsc, tiptab, pin, tt.clv_s, plane, wave, kSubWaves, lane);
+  tree_upward(n_ops, n_prune, msa, tt.dsc, tiptab, pin, tt.clv_s, plane, wave, kSubWaves, lane);
   // the sites' lanes below read CLVs that other lanes and waves of this workgroup stored above, and the zeroed load table
   __threadfence_block();
   __syncthreads();
@@ -162,7 +154,6 @@ __global__ void __launch_bounds__(kSubWaves * 64) sub_kernel(int R, int T, int L
     const int site = min(s0 + lane, L - 1);
     const int pat = min(site_pat[site], n_prune);
     const bool all_n = pat >= n_prune;
-    const double2* cbase = tt.clv_s + pat;
     const double* __restrict__ tj = tvec + ((size_t)sample * L + site) * 5;
     const double rj = rho[((size_t)sample * L + site) * R + rate];
     double cc[16];
@@ -171,11 +162,8 @@ __global__ void __launch_bounds__(kSubWaves * 64) sub_kernel(int R, int T, int L
     double A[4];
     {
       // the naive edge: J(b, i) = t(b) pi_i P_naive[i][b] L_root(i), 20 cells; A(i) = sum_b of the first three factors
-      const int kr = chain_op(ch[len - 1]);
-      const double2* cv = cbase + (size_t)kr * 2 * plane;
-      const double2 lo = cv[0], hi = cv[plane];
-      const double Lr[4] = {lo.x, lo.y, hi.x, hi.y};
-      double n4[4];
+      double Lr[4], n4[4];
+      tree_load_clv(tt.clv_s, plane, chain_op(ch[len - 1]), pat, Lr);
       tree_tip_col(tiptab, 0, 4, n4);
       const double t[5] = {tj[0], tj[1], tj[2], tj[3], tj[4]};
       double J[20];
@@ -205,7 +193,7 @@ __global__ void __launch_bounds__(kSubWaves * 64) sub_kernel(int R, int T, int L
 #pragma unroll
         for (int i = 0; i < 10; ++i) o[i] = make_double2(J[2 * i], J[2 * i + 1]);
       }
-      const double tot = sub_wave_sum(live ? off : 0.0);
+      const double tot = wave_sum(live ? off : 0.0);
       if (lane == 0) load_w[P] += tot;
 #pragma unroll
       for (int i = 0; i < 4; ++i)
@@ -216,29 +204,8 @@ __global__ void __launch_bounds__(kSubWaves * 64) sub_kernel(int R, int T, int L
       double m[4], M[4], J[16];
       double off;
       if (s == 0) {
-        const int k = chain_op(word);
-        const int4 da = dsc[k].a, db = dsc[k].b;
-        const bool flag = chain_flag(word);  // the seed is the cherry's z child
-        // the seed edge: the sibling is the cherry's other tip, or the accumulator child of a tip-accumulate op
-        int useed, srow;
-        if ((da.x & 15) == OP_CHERRY) {
-          const int sib = flag ? db.x : db.y, sib_row = flag ? da.y : da.z;
-          useed = flag ? db.y : db.x;
-          srow = flag ? da.z : da.y;
-          const int ss = all_n ? 4 : (int)msa[(size_t)sib_row * n_prune + pat];
-          tree_tip_col(tiptab, sib, ss, m);
-        } else {
-          useed = db.x;
-          srow = da.y;
-          const double2* cw = cbase + (size_t)(k - 1) * 2 * plane;
-          const double2 wlo = cw[0], whi = cw[plane];
-          const double y[4] = {wlo.x, wlo.y, whi.x, whi.y};
-          tree_matvec(pin + (size_t)(k - 1) * 16, y, m);
-        }
-        const int st = all_n ? 4 : (int)msa[(size_t)srow * n_prune + pat];
         double Lb[4];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) Lb[c] = (st >= 4 || st == c) ? 1.0 : 0.0;
+        const int useed = tree_seed_edge(tt, word, msa, n_prune, pat, all_n, m, Lb);
         tree_join(A, m, M);
         // the tip table holds columns: P_u[a][c] at [c * 4 + a]
         off = sub_edge<1, 4>(M, tiptab + (size_t)useed * 16, Lb, rj, J, cc);
@@ -246,14 +213,13 @@ __global__ void __launch_bounds__(kSubWaves * 64) sub_kernel(int R, int T, int L
       } else {
         const int kc = tree_sibling_message(tt, word, msa, n_prune, pat, all_n, m);
         tree_join(A, m, M);
-        const double2* cv = cbase + (size_t)kc * 2 * plane;
-        const double2 lo = cv[0], hi = cv[plane];
-        const double Lb[4] = {lo.x, lo.y, hi.x, hi.y};
+        double Lb[4];
+        tree_load_clv(tt.clv_s, plane, kc, pat, Lb);
         off = sub_edge<4, 1>(M, pin + (size_t)kc * 16, Lb, rj, J, cc);
         tree_push_down(pin, kc, M, A);  // the message into v_{s-1}
       }
       if (kWriteEdges && live) sub_store16(edge_part + ((sr * P + s) * L + site) * 16, J);
-      const double tot = sub_wave_sum(live ? off : 0.0);
+      const double tot = wave_sum(live ? off : 0.0);
       if (lane == 0) load_w[s] += tot;
     }
     if (live) sub_store16(cc_part + (sr * L + site) * 16, cc);

@@ -1,11 +1,16 @@
-// The tree pass that K3 (lh_asr.hip), K11 (lh_ancestral.hip), K12 (lh_substitutions.hip) and K13 (lh_ancestral_probs.hip)
-// run on, defined once and inlined into each kernel: the 4-vector helpers, the per-rate planes' weights, the LDS tables of a
-// (sample, rate), the upward pass over patterns into a [op][2][plane] CLV area and one step down a seed's lineage.
+// The tree pass that K3 (lh_asr.hip), K11 (lh_ancestral.hip), K12 (lh_substitutions.hip), K13 (lh_ancestral_probs.hip),
+// K14 (K13b's table, lh_node_codon.hip) and K15 (lh_codon_edges.hip) run on, defined once and inlined into each kernel: the
+// 4-vector helpers, the per-rate planes' weights, the LDS tables of a (sample, rate), the upward pass over patterns into a
+// [op][2][plane] CLV area, one step down a seed's lineage, the seed edge at slot 0 (K12b, K15b) and what the kernels that
+// condition on the naive base share (K13b, K15b): a category's weight under each naive base and the five messages into the
+// root.
 //
-// Floating-point contraction is lexical, so everything here is compiled under the compiler's default whoever calls it; K12b's
-// down pass runs with contraction off.  Hence only contraction-neutral arithmetic lives here: single multiplications, fma
-// written out, sums of loaded values.  An expression a kernel's setting could fuse (the message into the root) stays in
-// the kernel.  No private array is reached by a dynamic index: the 4-vectors are indexed by unrolled loops only.
+// Floating-point contraction is lexical, so everything here is compiled under the compiler's default whoever calls it; the
+// down passes of K12b and K15b run with contraction off.  Hence only contraction-neutral arithmetic lives here: selects,
+// single multiplications, one division, fma written out, sums of loaded values.  The seed edge stood inside the
+// contraction-off region of both its kernels before it came here; being neutral, it compiles to the same arithmetic
+// outside.  An expression a kernel's setting could fuse (K11b's and K12b's message into the root) stays in the kernel.
+// No private array is reached by a dynamic index: the 4-vectors are indexed by unrolled loops only.
 #pragma once
 
 #include "lh_device.h"
@@ -156,6 +161,16 @@ __device__ static __forceinline__ TreeTables tree_prologue(double2* smem, int R,
   return t;
 }
 
+// The CLV of the lane's pattern that op k stored (clv_s: the (sample, rate)'s area), as four doubles.
+__device__ static __forceinline__ void tree_load_clv(const double2* clv_s, size_t plane, int k, int pat, double (&y)[4]) {
+  const double2* c = clv_s + (size_t)k * 2 * plane + pat;
+  const double2 lo = c[0], hi = c[plane];
+  y[0] = lo.x;
+  y[1] = lo.y;
+  y[2] = hi.x;
+  y[3] = hi.y;
+}
+
 // K3b's upward pass of one pattern (n_prune: the all-N one), the lane's, without K3b's software pipeline: every inner CLV
 // stored.  kStoreAll = false (K13b's MRCA form) stores only what a later op pops from the stack, which the lane itself
 // reads back.  `a` leaves as the root's CLV.
@@ -181,9 +196,8 @@ __device__ static __forceinline__ void tree_upward_pattern(int n_ops, int n_prun
         const int sa = all_n ? 4 : (int)msa[(size_t)da.y * n_prune + pat];
         tree_tip_col(tiptab, db.x, sa, u);
       } else {
-        const double2* cq = clv_s + (size_t)da.w * 2 * plane + pat;
-        const double2 lo = cq[0], hi = cq[plane];
-        const double y[4] = {lo.x, lo.y, hi.x, hi.y};
+        double y[4];
+        tree_load_clv(clv_s, plane, da.w, pat, y);
         tree_matvec(pin + (size_t)da.w * 16, y, u);
       }
     }
@@ -229,11 +243,70 @@ __device__ static __forceinline__ int tree_sibling_message(const TreeTables& t, 
   }
   const bool via_pop = chain_flag(word);
   const int kw = via_pop ? k - 1 : da.w;
-  const double2* cw = t.clv_s + pat + (size_t)kw * 2 * t.plane;
-  const double2 wlo = cw[0], whi = cw[t.plane];
-  const double y[4] = {wlo.x, wlo.y, whi.x, whi.y};
+  double y[4];
+  tree_load_clv(t.clv_s, t.plane, kw, pat, y);
   tree_matvec(t.pin + (size_t)kw * 16, y, m);
   return via_pop ? da.w : k - 1;
+}
+
+// The seed edge, slot 0 (chain word `word`, marked by K12c): m = the message of the seed tip's sibling -- the cherry's other
+// tip, or the accumulator child of a tip-accumulate op --, Lb = the seed tip's indicator vector (all ones for N).  Returns
+// the seed tip's index in the tip table.
+__device__ static __forceinline__ int tree_seed_edge(const TreeTables& t, int word, const uint8_t* __restrict__ msa,
+                                                     int n_prune, int pat, bool all_n, double (&m)[4], double (&Lb)[4]) {
+  const int k = chain_op(word);
+  const int4 da = t.dsc[k].a, db = t.dsc[k].b;
+  const bool flag = chain_flag(word);  // the seed is the cherry's z child
+  int useed, srow;
+  if ((da.x & 15) == OP_CHERRY) {
+    const int sib = flag ? db.x : db.y, sib_row = flag ? da.y : da.z;
+    useed = flag ? db.y : db.x;
+    srow = flag ? da.z : da.y;
+    const int ss = all_n ? 4 : (int)msa[(size_t)sib_row * n_prune + pat];
+    tree_tip_col(t.tiptab, sib, ss, m);
+  } else {
+    useed = db.x;
+    srow = da.y;
+    double y[4];
+    tree_load_clv(t.clv_s, t.plane, k - 1, pat, y);
+    tree_matvec(t.pin + (size_t)(k - 1) * 16, y, m);
+  }
+  const int st = all_n ? 4 : (int)msa[(size_t)srow * n_prune + pat];
+#pragma unroll
+  for (int c = 0; c < 4; ++c) Lb[c] = (st >= 4 || st == c) ? 1.0 : 0.0;
+  return useed;
+}
+
+// w[b] = lik_rate(pat, b) / Z_pat(b), the weight of the category under each naive base, from K1's unmixed planes; 0 where
+// Z or the category's plane is 0.  The all-N pattern takes K11r's convention (likelihood pi_b whatever the category): 1 / R.
+__device__ static __forceinline__ void tree_rate_weights(const int32_t* __restrict__ site_scal,
+                                                         const double* __restrict__ site_lik, int sample, int rate, int R,
+                                                         int n_prune, int pat, bool all_n, double (&w)[5]) {
+  if (all_n) {
+#pragma unroll
+    for (int b = 0; b < 5; ++b) w[b] = 1.0 / (double)R;
+  } else {
+    const RatePlanes planes = rate_planes(site_scal, site_lik, sample, R, n_prune, pat);
+    double z[5], v[5];
+    planes.totals(R, z);
+    planes.values(rate, v);
+#pragma unroll
+    for (int b = 0; b < 5; ++b) w[b] = (z[b] == 0.0 || v[b] == 0.0) ? 0.0 : v[b] / z[b];
+  }
+}
+
+// The message into the root from above for each basis vector of the naive tip (A, C, G, T, N): A[b][i] = pi_i P_naive[i][b],
+// the row sums of P_naive for N.
+__device__ static __forceinline__ void tree_root_messages(const double* tiptab, const double* __restrict__ p4,
+                                                          double (&A)[5][4]) {
+  double n4[4];
+  tree_tip_col(tiptab, 0, 4, n4);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+#pragma unroll
+    for (int b = 0; b < 4; ++b) A[b][i] = p4[i] * tiptab[b * 4 + i];
+    A[4][i] = p4[i] * n4[i];
+  }
 }
 
 // The descent, in the two halves K12b puts its edge table between.  M = A o m: the message from above into v_s, A, times the

@@ -40,18 +40,6 @@ namespace {
 constexpr int kVitWaves = 4;  // samples per workgroup
 constexpr double kLn2 = 0.693147180559945309417;
 
-template <int kCtrl>
-__device__ inline double dpp_move(double v) {
-  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), kCtrl, 0xf, 0xf, true);
-  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), kCtrl, 0xf, 0xf, true);
-  return __hiloint2double(hi, lo);
-}
-
-__device__ inline double read_lane(double v, int lane) {
-  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), lane),
-                          __builtin_amdgcn_readlane(__double2loint(v), lane));
-}
-
 // the largest of the wave's values (all >= 0), wave-uniform
 __device__ inline double wave_max(double v) {
   v = fmax(v, dpp_move<0xB1>(v));   // quad_perm [1,0,3,2]

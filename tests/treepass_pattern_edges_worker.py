@@ -154,7 +154,7 @@ def run_case(hip, case, R, workdir):
             far("k13_cond_" + name, np.abs(cond[i] - G_all[i][at[i]]).max())
             far("k13_cond_vs_k11", np.abs(cond[i] - k11[i, at[i]]).max())
             far("k13_cond_sum_to_one", np.abs(cond[i].sum(axis=-1) - 1).max())
-            # a site's table is that of every other site with its pattern, bit for bit (cond_sites_kernel, site_pat)
+            # a site's table is that of every other site with its pattern, bit for bit (site_gather_kernel, site_pat)
             note(all(np.array_equal(cond[i, s[0]], cond[i, j]) for s in same for j in s[1:]),
                  "K13b %s: sites of one pattern differ, pair %d" % (name, i))
             if name == "parent":
